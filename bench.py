@@ -196,6 +196,41 @@ def parity_check(ctx, step, B, uniq, F, P, H, inn, dR, gate, no_gating, tol_P=1e
     return out      # (a failure is raised by main() AFTER the ranks have exchanged their results: no rank left in a collective)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(ctx, out_dir, B, F, gated, frame):
+    """--dump-outputs: what the LAST timed step handed back to its caller, one DIR/<name>.npy each (float64; masks float32),
+    at most 64 MB in all: dx of every filter, its status and - gated runs - the inlier mask and Mahalanobis distances of
+    the gate; whole-frame runs also the nominal state after AbsorbError (pose, feature positions). When those rows do not
+    fit, a seeded sample of filters (filters.npy holds their indices). P+ of a seeded sample of filters (P_filters.npy).
+    Reads only - the context's state is left as the timed loop left it."""
+    N = ctx.N
+    rng = np.random.default_rng(20261015)
+    pick = lambda n: np.arange(B) if n >= B else np.sort(rng.choice(B, size=n, replace=False))
+    row_bytes = N * 8 + 8 + (F * 12 if gated else 0) + (336 + F * 24 if frame else 0)
+    rows = pick(max(1, (40 << 20) // row_bytes))
+    p_rows = pick(max(1, min(64, (20 << 20) // (N * N * 8))))
+    out = {"dx": ctx.get_err(0, B)[rows], "status": ctx.get_status(0, B, check=False)[rows].astype(np.float64)}
+    if gated:
+        mask, dist = ctx.get_gate(F, B)
+        out["inlier_mask"], out["mh_distance"] = mask[rows].astype(np.float32), dist[rows]
+    if frame:
+        poses, _, feats = ctx.get_scene(0, B)
+        out["pose"] = np.concatenate([poses[k].reshape(B, -1) for k in poses.dtype.names], axis=1)[rows]
+        out["feature_x"] = feats["x"][rows]
+    if len(rows) < B:
+        out["filters"] = rows.astype(np.float64)
+    out["P"] = np.stack([ctx.download_P(b0=int(b), nb=1)[0] for b in p_rows])
+    out["P_filters"] = p_rows.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "files": sorted(out), "bytes": int(total)}
+
+
 def parity_last_step(ctx, n_steps, B, uniq, F, P, H, inn, dR, gate, no_gating, tol_P=1e-6, tol_dx=1e-8):
     """The state the TIMED loop left behind (n_steps updates of the resident covariance with the same measurements, warm-up
     included) against the oracle applying the same n_steps updates one after the other - gating re-evaluated on the shrinking
@@ -548,7 +583,12 @@ def main():
                     help="where the verbose record goes (default gpurun_out/bench_full.json; the printed line is the compact one)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / reduction path only, no device work (CPU-box test of --gpus N)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's filters) as DIR/<name>.npy, "
+                         "at most 64 MB in all: the same arguments give the same inputs, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: become the launcher (one rank per GPU, LOCAL_RANK -> hipSetDevice, gloo control plane)
@@ -765,6 +805,10 @@ def main():
     per_rank = gather_over_ranks(dist, B * args.steps / dt_rank)
     status = ctx.get_status(check=False)
     sparse_path = ctx.last_path() == 1
+    dumped = None
+    if args.dump_outputs and rank == 0:      # before anything below runs the path again
+        gated = not args.no_gating or oos_on or (args.level == "G" and args.ransac)
+        dumped = dump_outputs(ctx, args.dump_outputs, B, F, gated, frame)
     # the state the timed loop left behind against the oracle doing the same number of updates in a row (every rank, its
     # own filters)
     parity_last = None
@@ -966,6 +1010,8 @@ def main():
             "roofline": roofline,
             "stage_ms_per_step": {k: v["ms"] / args.steps for k, v in prof.items() if v["launches"]},
         }
+        if dumped:
+            out["dumped_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(N, F)
             out["cpu_baseline"]["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]

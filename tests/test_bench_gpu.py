@@ -73,6 +73,25 @@ def test_printed_line_is_compact_and_complete(built):
     assert d["config"]["cfg2_upd_s"] == [r for r in d["configs"] if r["k"] == "cfg2"][0]["v"]
 
 
+def test_dump_outputs_repeat_bit_for_bit(built, tmp_path):
+    """--dump-outputs: the last timed step's dx / status / gate of every filter and P+ of a seeded sample, under 64 MB; two runs
+    with the same arguments write the same arrays (the inputs are seeded), and the state they come from passes parity_last."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        rec = _run("--no-configs", "--no-dropin", "--no-mixed", "--dump-outputs", str(d))
+        assert rec["parity_check_last_timed_step"]["ok"] and rec["dumped_outputs"]["bytes"] <= 64 << 20
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    a, b = dumps
+    assert set(a) == {"dx", "status", "inlier_mask", "mh_distance", "P", "P_filters"}
+    assert a["dx"].shape == (512, 250) and a["inlier_mask"].shape == (512, 80) and a["P"].shape[1:] == (250, 250)
+    assert all(a[k].dtype in (np.float32, np.float64) for k in a)
+    assert (a["status"] == 0).all() and np.abs(a["dx"]).max() > 0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_feature_level_and_config3_lines(built):
     d = _run("--level", "G", "--ransac")
     assert d["value"] > 0 and "OnePointRANSAC" in d["config"]["workload"]

@@ -4,7 +4,8 @@
     (src/test/unittest_jacobians_instate.cpp:28-29 tol 9e-4, ..._oos.cpp tol 1e-5);
  3. committed golden vectors generated from oracle/_ref - the reference's own Eigen /
     Sophus / helpers.cpp / camera arithmetic (tests/golden/make_golden.py);
- 4. live comparison against oracle/_ref when the prebuilt library is present."""
+ 4. comparison against oracle/_ref - live where the library is built, else against the calls it answered on the same
+    inputs, stored in tests/golden/ref_calls.npz (tests/ref_replay.py, tests/golden/make_ref_calls.py)."""
 import math
 import os
 
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 
 import xivo_oracle as orc
+from ref_replay import reference
 from xivo_amd import synth
 
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "golden_v1.npz"))
@@ -173,18 +175,15 @@ def test_golden_propagation_tail_and_so3():
         assert np.abs(orc.so3_exp(w) - R).max() < 1e-12
 
 
-# ---- 4. live against oracle/_ref (prebuilt library travels with the repo) ---------------
-def _ref():
+# ---- 4. against oracle/_ref: live where it is built, its stored calls elsewhere (tests/ref_replay.py) ---------------
+def _ref(stored=True):
     import ref_binding
-    try:
-        return ref_binding.load()
-    except (FileNotFoundError, OSError):
-        pytest.skip("oracle/_ref not built")
+    return reference("ref", ref_binding.load, stored)
 
 
 @pytest.mark.parametrize("N,F", [(150, 50), (250, 80), (203, 30)])
 def test_live_update_joseph_vs_ref(N, F):
-    ref = _ref()
+    ref = _ref(stored=False)     # (library only: without it, test_golden_update_joseph / _at_baseline_sizes make this comparison)
     P, H, inn, dR = synth.s_level(N, F, 1, seed=N + F)
     e1, P1 = ref.update_joseph(H[0], P[0], inn[0], dR[0])
     e2, P2, _ = orc.update_joseph(H[0], P[0], inn[0], dR[0])
@@ -198,7 +197,7 @@ def test_ldlt_restatement_vs_eigen_ldlt(case):
     zero pivots (two all-zero measurement rows with R = 0: Eigen leaves a zero pivot undivided and its solve drops the
     component - the update equals the one without those rows), and a P_ that is not symmetric (the reference never
     re-symmetrises; it reads P_ as stored)."""
-    ref = _ref()
+    ref = _ref(stored=False)     # (library only: five 100 x 100 covariances of the reference's rounding are not kept)
     N, F = 100, 20
     P, H, inn, dR = synth.s_level(N, F, 1, seed=41)
     P, H, inn, dR = P[0], H[0], inn[0], dR[0]
@@ -410,7 +409,7 @@ def test_golden_one_point_ransac(tag, cam):
 
 
 def test_live_one_point_ransac_core_vs_ref():
-    ref = _ref()
+    ref = _ref(stored=False)     # (library only: without it, test_golden_one_point_ransac makes this comparison)
     for seed in range(6):
         cam = [synth.PINHOLE, synth.EQUI, synth.RADTAN][seed % 3]
         ng, nf = 4, 11
@@ -454,12 +453,9 @@ def test_golden_update_joseph_at_baseline_sizes(tag):
 
 
 # ---- round 4 pins: the reference's OWN TEXT compiled (oracle/ref/extract_reference.py -> oracle/ref/xivo_refx.cpp) -------------
-def _refx(N):
-    try:
-        import ref_binding
-        return ref_binding.loadx(N)
-    except (FileNotFoundError, OSError):
-        pytest.skip("oracle/_ref extracted libraries not built")
+def _refx(N, stored=True):
+    import ref_binding
+    return reference(f"refx_{N}", lambda: ref_binding.loadx(N), stored)
 
 
 def test_extracted_build_layout_constants():
@@ -477,7 +473,8 @@ def test_extracted_update_joseph_form_equals_the_retyped_driver_bit_for_bit(N, F
     """Estimator::UpdateJosephForm: the text of src/estimator.cpp:1257-1288 compiled as is == the line-by-line retyping
     of oracle/ref/xivo_ref.cpp, BIT FOR BIT (same Eigen expressions on the same dynamic types) - and hence the numpy
     oracle's distance to either is the same number."""
-    ref, x = _ref(), _refx(203)
+    # (library against library: only the libraries can show it; the oracle's half is test_golden_update_joseph's)
+    ref, x = _ref(stored=False), _refx(203, stored=False)
     P, H, inn, dR = synth.s_level(N, F, 2, seed=5 + N)
     for b in range(2):
         e1, P1 = ref.update_joseph(H[b], P[b], inn[b], dR[b])
@@ -526,7 +523,7 @@ def test_extracted_filter_update_stacking_quirk_update_and_absorb(N):
     incl. the :675-676 overwrite of the group block), UpdateJosephForm, AbsorbError (src/estimator.cpp:875-921 with
     State::operator+= of src/core.h:135-165 and Feature::UpdateState) - vs the oracle's stack_measurements / update_joseph /
     absorb_error: H identical entry for entry (a copy), dx 1e-9, P 1e-11, the retracted state and the features 1e-12."""
-    x = _refx(N)
+    x = _refx(N, stored=False)    # (library only: without it, test_golden_v3_filter_update makes this comparison)
     ng, nf = (15, 30) if N == 203 else (8, 60)
     lay = orc.Layout(ng, nf)
     from scene_util import scene_arrays, oracle_jacobians, spd
@@ -557,7 +554,9 @@ def test_extracted_integrator_steps_vs_retyped_and_oracle(N):
     reference's SPARSE F_ / G_ (src/estimator.h:467-470; the retyping uses dense matrices: same sums, the sparse products
     skip the structural zeros) and the compile-time block sizes - vs the retyped driver and the oracle's tableau form:
     state 1e-13, P 1e-13 relative (measured ~1e-16)."""
-    x, ref = _refx(N), _ref()
+    # (library only: without it, test_golden_v3_integrator_steps / test_golden_rk4_step / test_golden_prince_dormand_step make
+    #  the comparison with the oracle)
+    x, ref = _refx(N, stored=False), _ref(stored=False)
     rng = np.random.default_rng(19 + N)
     for k in range(3):
         A = rng.uniform(-1, 1, size=(N, N)); P = A @ A.T / N * 1e-3 + 1e-6 * np.eye(N)
@@ -667,11 +666,7 @@ def test_extracted_compute_jacobian_online_calibration_build(name):
     """The same text compiled with -DUSE_ONLINE_TEMPORAL_CALIB -DUSE_ONLINE_IMU_CALIB -DUSE_ONLINE_CAMERA_CALIB
     (src/CMakeLists.txt:13-15): kMotionSize 39, N = 228; the extracted enum Index gives the slots, the oracle's calib_layout
     derives the same ones; the td / Cg / bg / intrinsics blocks of J and of the stacked rows agree to 1e-12."""
-    try:
-        import ref_binding
-        x = ref_binding.loadx("calib")
-    except (FileNotFoundError, OSError):
-        pytest.skip("oracle/_ref calibration build not built")
+    x = _refx("calib")
     lay = orc.calib_layout(15, 30, True, True, CAM_DIM[name])
     td, Cg, cam_begin, max_cam, motion = x.calib_slots()
     assert (lay.N, lay.group_begin, lay.feature_begin, lay.td, lay.Cg, lay.cam_begin) == (x.N, x.group_begin, x.feature_begin, td, Cg, cam_begin)
@@ -772,11 +767,7 @@ def test_golden_v5_calibration_motion_side(seed):
 
 def test_extracted_calibration_build_motion_side_live():
     """the same against the library itself when it is here (a fresh seed)"""
-    try:
-        import ref_binding
-        x = ref_binding.loadx("calib")
-    except (FileNotFoundError, OSError):
-        pytest.skip("oracle/_ref calibration build not built")
+    x = _refx("calib")
     m = _v5()
     lay = orc.calib_layout(15, 30, True, True, 9)
     assert x.index_Ca() == lay.Ca and x.calib_slots()[4] == lay.motion_size
@@ -1047,10 +1038,7 @@ def test_golden_v7_prince_dormand_step_size_control_as_coded(seed):
 def test_live_prince_dormand_step_size_control_vs_ref():
     """The same chain on a private copy of the extracted library (fresh function-local statics), live"""
     m7 = _v7()
-    try:
-        rx = m7.private_refx(203)
-    except (FileNotFoundError, OSError, TypeError):
-        pytest.skip("oracle/_ref not built")
+    rx = reference("refx_private_203", lambda: m7.private_refx(203))
     if not hasattr(rx.lib, "refx_pd_control"):
         pytest.skip("oracle/_ref predates refx_pd_control")
     c, ref_outs = m7.run_chain(rx, 2)
