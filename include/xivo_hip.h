@@ -257,6 +257,12 @@ int xivo_hip_update_joseph_host(xivo_hip_ctx* ctx, int b, int M, const double* H
  * P+ at 10 / 13 column blocks: every block pair exactly once, the counts the kernel's dispatch assumes, per_simd[4] (optional)
  * the tiles per SIMD. 0 = consistent, -1 = no table for that size. No GPU needed. */
 int xivo_hip_selftest_fused_tiles(int column_blocks, int* per_simd);
+/* Host-only check of the one-kernel update's admission test for a padded shape (Mp, Np multiples of 16) and pw private
+ * slots: -1 when the shape takes the multi-kernel pipeline; else the kernel label that would run is written to label[n]
+ * (optional) and the return value is a bitmask of broken invariants - 1 more block rows of the factor than waves
+ * (Mp > Np), 2 LDS map beyond 160 KB, 4 no column block per product phase, 8 gather staging past the coefficients,
+ * 16 more waves than the instantiation's workgroup. 0 = all hold. No GPU needed. */
+int xivo_hip_selftest_fused_shape(int Mp, int Np, int pw, char* label, int n);
 int xivo_hip_selftest_host_compress(const double* H, int ldh, int M, int N, int pairs_clear, int* idx, double* val, int* nc, int* pw);
 /* Estimator::MHGating numeric core on dense rows (src/update.cpp:60-96):
  * rows 2f,2f+1 of the staged H are feature f's J. Writes the inlier mask and

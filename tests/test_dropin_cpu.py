@@ -109,3 +109,61 @@ def test_fused_update_tile_tables_cover_every_block_pair_once(built):
         assert lib.xivo_hip_selftest_fused_tiles(nwl, simd) == 0
         assert sorted(simd) == sorted(want) and sum(simd) == nwl * (nwl + 1) // 2
     assert lib.xivo_hip_selftest_fused_tiles(12, None) == -1
+
+
+# the instantiations of the one-kernel update the admission test can reach (XC 64 / 48 / 32, gather depth 2 / 1, 6 / 9 slots)
+FUSED_REACHABLE = {"fused_update_f64_kernel<%s>" % s for s in (
+    "4,16,64,2,6", "4,16,64,2,9", "4,16,64,1,9", "4,16,32,1,9", "7,12,48,2,6", "7,12,48,2,9", "7,12,48,1,9", "7,12,32,2,9")}
+
+
+def _fused_shape(lib, Mp, Np, pw):
+    buf = C.create_string_buffer(64)
+    rc = lib.xivo_hip_selftest_fused_shape(Mp, Np, pw, buf, len(buf))
+    return rc, buf.value.decode()
+
+
+def test_fused_update_admits_only_shapes_its_kernels_hold(built):
+    """Every padded shape the one-kernel update admits (fused_pick in csrc/fused_update.hip) - Mp 16..384, Np 16..512, 1..9
+    private slots - holds what the launch and the kernel assume: a wave for every block row of the factor (Mp <= Np), the LDS
+    map within 160 KB, at least one column block per product phase, the gather staging of the chosen depth in front of the
+    coefficients, no more waves than the instantiation's workgroup. The labels the sweep reaches are exactly the
+    instantiations there are. Host code only."""
+    from xivo_amd.lib import load_library
+    lib = load_library()
+    bad, labels = [], set()
+    for Mp in range(16, 385, 16):
+        for Np in range(16, 513, 16):
+            for pw in range(1, 10):
+                rc, label = _fused_shape(lib, Mp, Np, pw)
+                if rc == -1:
+                    continue
+                labels.add(label)
+                if rc != 0:
+                    bad.append((Mp, Np, pw, rc, label))
+    assert not bad, "%d admitted shapes break an invariant (Mp, Np, pw, mask, kernel), e.g. %s" % (len(bad), bad[:8])
+    assert labels == FUSED_REACHABLE, labels ^ FUSED_REACHABLE
+    assert _fused_shape(lib, 64, 48, 6)[0] == -1 and _fused_shape(lib, 112, 96, 9)[0] == -1     # factor taller than the state
+    assert _fused_shape(lib, 128, 192, 6)[0] == -1 and _fused_shape(lib, 64, 272, 6)[0] == -1  # past the instantiations
+    assert _fused_shape(lib, 60, 64, 6)[0] == -1                                              # not padded
+
+
+def test_edge_case_table_reaches_every_fused_instantiation(built):
+    """The GPU cases of tests/test_update_edges_gpu.py, checked where no GPU is: the compressed form of each generated H has
+    the (nc, pw) the case names, every case the table sends to the one-kernel route is admitted with the label the case
+    expects, every other case is declined by the shape, nc > 12 or pw > 9, and the fused cases reach every instantiation."""
+    from xivo_amd.lib import load_library
+    import test_update_edges_gpu as edges
+    lib = load_library()
+    reached = set()
+    for case in edges.EDGE_CASES:
+        name, N, M, nb, nwl, nc, pw, B, flags, route, kern = case[:11]
+        _, H, _, _ = edges.edge_inputs(case)
+        edges.check_intent(lib, case, H)
+        nc_max = max(edges._per_filter(nc, B)); pw_max = max(max(edges._per_filter(pw, B)), 1)
+        rc, label = _fused_shape(lib, 16 * nb, 16 * nwl, pw_max)
+        admitted = rc == 0 and nc_max <= 12 and pw_max <= 9 and not flags & edges.MT
+        assert admitted == (route == "fused"), (name, rc, nc_max, pw_max, route)
+        if admitted:
+            assert label == kern, (name, label, kern)
+            reached.add(label)
+    assert reached == FUSED_REACHABLE, FUSED_REACHABLE - reached

@@ -315,11 +315,12 @@ int gemm(xivo_hip_ctx* c, int stage, int B, int rows, int cols, const double* A0
 // ---------------------------------------------------------------------------------------------------------------------
 // Route selection of Estimator::UpdateJosephForm (src/estimator.cpp:1257-1288), in ONE place. Every pass of the update
 // (update_joseph_range) asks plan_update() once; the pipelines below only execute what the plan says, and
-// tests/test_update_gpu.py::test_every_route_of_the_plan enumerates the routes of this table against the oracle.
+// tests/test_update_gpu.py::test_every_route_of_the_plan enumerates the routes of this table against the oracle,
+// tests/test_update_edges_gpu.py runs shapes on both sides of each of its limits.
 //
 //   route              | rows of H                   | gain + covariance                                   | when
 //   -------------------+-----------------------------+-----------------------------------------------------+--------------------------
-//   FUSED              | row-pair compressed         | one kernel per filter (fused_update.hip)            | M <= 64 / N <= 256 or M <= 112 / N <= 192, default form
+//   FUSED              | row-pair compressed         | one kernel per filter (fused_update.hip)            | M <= 64 / N <= 256 or M <= 112 / N <= 192, and M <= N (rounded to 16), default form
 //   SPARSE_IN_SOLVE    | compressed (+ OOS / lead)   | whitened Joseph form inside the solve kernel        | N <= 256, M <= 176, > 64 filters
 //   SPARSE_WHITENED    | compressed (+ OOS / lead)   | whitened outputs V^T, Y^T + tiled P - V^T Y         | wider shapes; <= 64 filters (latency route)
 //   SPARSE_SYMMETRIC   | compressed                  | P - W^T W, forward substitution only                | XIVO_HIP_FLAG_SYMMETRIC_FORM
@@ -1233,10 +1234,14 @@ static int host_compress(xivo_hip_ctx::HostCompressScratch& sc, const double* H,
   return over;
 }
 
+int xivo_hip_selftest_fused_tiles(int column_blocks, int* per_simd) { return fused_tiles_selftest(column_blocks, per_simd); }
+// test hook (no device): the one-kernel update's admission of a padded shape and the invariants of what it would launch
+int xivo_hip_selftest_fused_shape(int Mp, int Np, int pw, char* label, int n) {
+  return fused_shape_selftest(Mp, Np, pw, label, n > 0 ? (size_t)n : 0);
+}
+
 // test hook (no device, no context): the host-side row compression on its own, for the CPU test that pins it to the format
 // of ell.h / meas_compress_kernel. idx [pairs_clear][28], val [pairs_clear][28][2]; returns over.
-int xivo_hip_selftest_fused_tiles(int column_blocks, int* per_simd) { return fused_tiles_selftest(column_blocks, per_simd); }
-
 int xivo_hip_selftest_host_compress(const double* H, int ldh, int M, int N, int pairs_clear, int* idx, double* val, int* nc, int* pw) {
   if (!H || !idx || !val || !nc || !pw || M <= 0 || N <= 0 || ldh < M || 2 * pairs_clear < M) return XIVO_HIP_ERR_INVALID;
   xivo_hip_ctx::HostCompressScratch sc;

@@ -866,6 +866,19 @@ __global__ __launch_bounds__(64 * NWV, 1) void fused_update_f64_kernel(FusedArgs
   FTR2(31);
 }
 
+// doubles per gather staging unit of the kernel's phase 1 (USZ there) for `pws` private slots
+static int fused_stage_unit(int pws) { return (4 * pws + 7) / 8 * 128; }
+// product phase: every column block's operand at once when it fits (one phase, one buffer), else two buffers. Returns the
+// column blocks per phase (jbp) and the operand bytes; + one 16 x 16 transpose scratch per wave (tsc)
+static int fused_product_phase(int nb, int nwl, size_t& opbytes, size_t& tsc) {
+  const size_t cap = 160 * 1024, per = (size_t)nb * 256 * sizeof(double);
+  tsc = (size_t)nwl * 256 * sizeof(double);
+  if ((size_t)nwl * per + tsc <= cap) { opbytes = (size_t)nwl * per; return nwl; }
+  const int jbp = tsc < cap ? (int)((cap - tsc) / 2 / per) : 0;
+  opbytes = (size_t)2 * jbp * per;
+  return jbp;
+}
+
 template <int NBM, int NWV, int XC, int GD, int PW>
 int launch_fused_update_g(const FusedArgs& g_in, hipStream_t stream) {
   FusedArgs g = g_in;
@@ -874,11 +887,10 @@ int launch_fused_update_g(const FusedArgs& g_in, hipStream_t stream) {
   const size_t cap = 160 * 1024;
   size_t lds = (size_t)map.total * sizeof(double);
   if (lds > cap) return (int)hipErrorInvalidValue;
-  // product phase: every column block's operand at once when it fits (one phase, one buffer), else two buffers
-  const size_t per = (size_t)nb * 256 * sizeof(double), tsc = (size_t)nwl * 256 * sizeof(double);   // + one 16 x 16 transpose scratch per wave
-  size_t opbytes;
-  if ((size_t)nwl * per + tsc <= cap) { g.jbp = nwl; opbytes = (size_t)nwl * per; }
-  else { g.jbp = (int)((cap - tsc) / 2 / per); opbytes = (size_t)2 * g.jbp * per; }
+  if (nb > nwl || nwl > NWV) return (int)hipErrorInvalidValue;              // block row i of the factor belongs to wave i
+  if (nwl * GD * fused_stage_unit(PW) > map.ops) return (int)hipErrorInvalidValue;   // phase-1 staging in front of the coefficients
+  size_t opbytes, tsc;
+  g.jbp = fused_product_phase(nb, nwl, opbytes, tsc);
   if (g.jbp < 1) return (int)hipErrorInvalidValue;
   g.tsc_off = (int)(opbytes / sizeof(double));
   if (opbytes + tsc > lds) lds = opbytes + tsc;
@@ -894,8 +906,7 @@ int launch_fused_update_g(const FusedArgs& g_in, hipStream_t stream) {
 static int fused_private_slots(int pw, int XC) { return (pw <= 6 && (XC == 64 || XC == 48)) ? 6 : 9; }
 static int fused_gather_depth(int Np, int Mp, int XC, int pws) {
   const int room = fused_lds_map(Np, Mp, XC).ops;   // doubles in front of the coefficients (live during the gather)
-  const int usz = (4 * pws + 7) / 8 * 128;
-  return (Np / 16) * 2 * usz <= room ? 2 : 1;
+  return (Np / 16) * 2 * fused_stage_unit(pws) <= room ? 2 : 1;
 }
 // (slots, staging depth) of the instantiation launch_fused_update_t picks
 static void fused_variant(int Np, int Mp, int XC, int pw, int& pws, int& gd) {
@@ -917,9 +928,12 @@ int launch_fused_update_t(const FusedArgs& g, hipStream_t stream) {
 }  // namespace
 
 // instantiations (NBM, NWV, XC; x two gather depths): <4, 16, 64> M <= 64 on any state one workgroup holds (128 VGPRs; <4, 16, 32>: where the 64-wide slab does not fit next to S); <7, 12, 48> (slab in three passes; <7, 12, 32>: four, where 48 columns do not fit) M <= 112, N <= 192 (168 VGPRs)
+// In every case M <= N (rounded to 16): the in-LDS Cholesky gives block row i of the factor to wave i, and the workgroup has
+// nwl = Np / 16 waves - a factor taller than the state would leave its last block rows unfactored.
 static int fused_pick(int Mp, int Np) {
   if (Np % 16 || Mp % 16 || Np < 16 || Mp < 16) return 0;   // (A/B against the multi-kernel pipeline: XIVO_HIP_FLAG_MULTI_KERNEL)
   const int nb = Mp / 16, nwl = Np / 16;
+  if (nb > nwl) return 0;
   if (nb <= 4 && nwl <= 16 && (size_t)fused_lds_map(Np, Mp, 64).total * 8 <= 160 * 1024) return 1;
   if (nb <= 4 && nwl <= 16 && (size_t)fused_lds_map(Np, Mp, 32).total * 8 <= 160 * 1024) return 3;
   if (nb <= 7 && nwl <= 12 && (size_t)fused_lds_map(Np, Mp, 48).total * 8 <= 160 * 1024) return 4;
@@ -985,6 +999,28 @@ void fused_update_label(int Mp, int Np, int pw, char* buf, size_t n) {
   int pws, gd;
   fused_variant(Np, Mp, xc, pw, pws, gd);
   snprintf(buf, n, "fused_update_f64_kernel<%s,%d,%d,%d>", (k == 1 || k == 3) ? "4,16" : "7,12", xc, gd, pws);
+}
+// The admission test (fused_pick) against what the launch and the kernel assume, on the host: -1 when the shape is declined,
+// else the label of the instantiation that would run and a bitmask of the invariants it breaks - 1 a block row of the factor
+// without a wave of its own (nb > nwl), 2 the LDS map beyond 160 KB, 4 no column block per product phase, 8 the gather
+// staging of the chosen depth past the coefficients, 16 more waves than the instantiation's workgroup. 0: all hold.
+int fused_shape_selftest(int Mp, int Np, int pw, char* label, size_t n) {
+  const int k = fused_pick(Mp, Np);
+  if (k == 0) return -1;
+  const int xc = (k == 1) ? 64 : (k == 4 ? 48 : 32), nwv = (k == 1 || k == 3) ? 16 : 12;
+  const int nb = Mp / 16, nwl = Np / 16;
+  int pws, gd;
+  fused_variant(Np, Mp, xc, pw, pws, gd);
+  if (label && n > 0) fused_update_label(Mp, Np, pw, label, n);
+  const FusedLds map = fused_lds_map(Np, Mp, xc);
+  size_t opbytes, tsc;
+  int bad = 0;
+  if (nb > nwl) bad |= 1;
+  if ((size_t)map.total * sizeof(double) > 160 * 1024) bad |= 2;
+  if (fused_product_phase(nb, nwl, opbytes, tsc) < 1) bad |= 4;
+  if (nwl * gd * fused_stage_unit(pws) > map.ops) bad |= 8;
+  if (nwl > nwv) bad |= 16;
+  return bad;
 }
 #endif
 
