@@ -586,7 +586,7 @@ int xivo_hip_bench_mfma_peak(xivo_hip_ctx* ctx, double* out4);
 void xivo_hip_gemm_tile(int rows, int cols, int symmetric, int* bm, int* bn);
 /* which rows the last update call used: 0 = dense, 1 = row-pair compressed (sparse-H) */
 int xivo_hip_last_path(xivo_hip_ctx* ctx);
-/* the route the last update pass took (round 6: the one table in capi.hip, plan_update): 0 fused (one kernel), 1 sparse rows +
+/* the route the last update pass took (round 6: the one table in capi_update.hip, plan_update): 0 fused (one kernel), 1 sparse rows +
  * in-solve whitened update, 2 sparse rows + whitened outputs + tiled product, 3 sparse symmetric form, 4 sparse stand-alone tail,
  * 5 dense as-coded, 6 dense rows + whitened update, 7 dense symmetric form; xivo_hip_route_name gives the table's name */
 int xivo_hip_last_route(xivo_hip_ctx* ctx);

@@ -1,5 +1,5 @@
 """The measurement update (Estimator::UpdateJosephForm, src/estimator.cpp:1257-1288) on both sides of every admission limit
-of the route table (plan_update in xivo_amd/csrc/capi.hip) and of the one-kernel update's instantiations (fused_pick /
+of the route table (plan_update in xivo_amd/csrc/capi_update.hip) and of the one-kernel update's instantiations (fused_pick /
 fused_variant in xivo_amd/csrc/fused_update.hip), against the oracle.
 
 Each case names the shape it means - block rows of the factor nb = round16(M) / 16, column blocks of the state

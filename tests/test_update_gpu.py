@@ -520,7 +520,7 @@ def test_update_matches_the_eigen_driver_directly(built, N, F):
 
 
 def _route_cases():
-    """Every route of plan_update (xivo_amd/csrc/capi.hip) on seeded random shapes: (flags, dense H?, filters) -> the route the
+    """Every route of plan_update (xivo_amd/csrc/capi_update.hip) on seeded random shapes: (flags, dense H?, filters) -> the route the
     table names for it. Shapes: state dim 24..419, 1..149 features."""
     from xivo_amd.lib import FLAG_DENSE_H, FLAG_SYMMETRIC_FORM, FLAG_STANDALONE_TAIL
     rng = np.random.default_rng(20260924)
@@ -542,7 +542,7 @@ def _route_cases():
 
 @pytest.mark.parametrize("N,F,B,flags,dense,route,seed", _route_cases())
 def test_every_route_of_the_plan(built, N, F, B, flags, dense, route, seed):
-    """Seeded random shapes through every route of the one table that selects them (plan_update in capi.hip): the one-kernel
+    """Seeded random shapes through every route of the one table that selects them (plan_update in capi_update.hip): the one-kernel
     update, the whitened form inside the solve kernel / from the whitened outputs (chunked, streamed, the latency route), the
     stand-alone tail, the symmetric form, the as-coded dense sequence, the whitened update on dense rows. The route the
     library reports is one the table allows for the flags; P+ 1e-6, dx 1e-8, symmetric output."""

@@ -1,0 +1,802 @@
+// C ABI, feature level (include/xivo_hip.h): layout, scene, calibration, Jacobians, MH gating, stacking, OOS rows, RANSAC, loop
+// closure, measurement compression, filter_update, Givens / QR, sub-filter, candidate order, absorb, edits, pixels. Host-side
+// orchestration only (capi_internal.h).
+#include <algorithm>
+#include <cmath>
+
+#include "capi_internal.h"
+
+using namespace xivo_hip;
+using namespace xivo_hip::capi;
+
+namespace {
+
+int gate_impl(xivo_hip_ctx* c, int B, double R, double th, double mult, int min_inl, int use_gating) {
+  GateArgs a{};
+  a.sb = scene_buffers(c); a.lay = c->lay; a.P = c->P; a.strideP = c->sP; a.ldp = c->Np;
+  a.R = R; a.thresh = th; a.mult = mult; a.min_inliers = min_inl; a.batch = B; a.use_gating = use_gating;
+  StageTimer st(c, ST_GATE, 0.0, "gate_sparse_kernel");
+  c->gate_sparse_last = 1;
+  return launch_gate_sparse(a, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
+}
+
+int stack_impl(xivo_hip_ctx* c, int B, double R, int write_dense, unsigned char* mask_override = nullptr, int full_rows = 0) {
+  StackArgs a{};
+  a.sb = scene_buffers(c); a.lay = c->lay; a.mb = meas_buffers(c);
+  if (write_dense) c->ht_valid = true;
+  if (mask_override) a.sb.mask = mask_override;
+  a.Mp = c->Mpmax; a.Np = c->Np; a.batch = B; a.R = R;
+  a.fix_group_block = (full_rows || (c->flags & XIVO_HIP_FLAG_FIX_GROUP_BLOCK)) ? 1 : 0;
+  a.rows_instate = c->rows_instate;
+  a.ell = c->ell; a.emit_ell = 1; a.write_dense = write_dense;
+  // as-coded stacking of an online-calibration build on the sparse pipeline: compressed rows + the leading dense block
+  // (full_rows - the whole-row stackings of the gate / RANSAC - stay dense rows)
+  if (!full_rows && !write_dense && calib_sparse(c)) { a.lead = c->Hlead; a.strideLead = (long)c->Mpmax * LEAD_K; a.lead_k = LEAD_K; }
+  StageTimer st(c, ST_STACK, 0.0, "stack_kernel");
+  return launch_stack(a, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
+}
+
+// Estimator::MHGating of an online-calibration build: the gate needs the WHOLE row J() incl. the td / Cg / bg / intrinsics
+// blocks (update.cpp:60-70), which is not the row FillJacobianBlock stacks (the :675-676 overwrite): every present feature is
+// stacked once as its full J() (dense rows) and gated on (J P) J^T + R by the dense-row gate. gate = 0: every present feature
+// is an inlier (Estimator::OutlierRejection does not gate F <= min_required_inliers_, src/manager.cpp:635).
+int calib_gate(xivo_hip_ctx* c, int B, double R, double mh_thresh, double mh_mult, int min_inliers, int gate) {
+  int rc = gate_impl(c, B, R, mh_thresh, mh_mult, min_inliers, 0);
+  if (rc) return rc;
+  if (gate) {
+    c->M = 2 * c->F; c->Mp = round_up16(c->M);
+    c->dense_valid = true; c->dense_from_ell = false; c->stack_R = R; c->stack_B = B; c->oos_row0 = -1; c->mixed_row0 = -1; c->h_clean = false;
+    rc = stack_impl(c, B, R, 1, nullptr, /*full_rows=*/1);
+    if (rc) return rc;
+    GateDenseArgs a{};
+    a.mask = c->mask; a.dist = c->dist; a.F = c->F; a.mask_ld = c->Fmax;   // (the stride xivo_hip_stack reads the mask with)
+    a.R = R; a.thresh = mh_thresh; a.mult = mh_mult; a.min_inliers = min_inliers; a.have_ell = 0;
+    a.feats = c->feats; a.Fmax = c->Fmax;        // absent entries of ragged batches are no candidates (per-filter present count)
+    rc = gate_dense_rows(c, B, a);
+    if (rc) return rc;
+    c->gate_sparse_last = 1;
+  }
+  return XIVO_HIP_OK;
+}
+
+}  // namespace
+
+namespace xivo_hip::capi {
+
+int ensure_gate_buffers(xivo_hip_ctx* c, int F) {
+  if (F <= c->Fmax && c->mask) return XIVO_HIP_OK;
+  const int Fm = F > c->Mpmax / 2 ? F : c->Mpmax / 2;
+  void* olds[] = {c->feats, c->J, c->finn, c->dist, c->mask, c->Jc};
+  for (void* p : olds) if (p) hipFree(p);
+  c->feats = nullptr; c->J = nullptr; c->finn = nullptr; c->dist = nullptr; c->mask = nullptr; c->Jc = nullptr;
+  const size_t B = c->Bmax;
+  int rc = dev_alloc(&c->feats, B * Fm);
+  if (!rc) rc = dev_alloc(&c->J, B * Fm * 42);
+  if (!rc) rc = dev_alloc(&c->finn, B * Fm * 2);
+  if (!rc) rc = dev_alloc(&c->dist, B * Fm);
+  if (!rc) rc = dev_alloc(&c->mask, B * Fm);
+  if (!rc && c->calib_on) rc = dev_alloc(&c->Jc, B * Fm * 44);
+  if (!rc && !c->rows_instate) rc = dev_alloc(&c->rows_instate, B);
+  // every entry starts absent (sind = -1) and masked out until a scene / edit writes it
+  if (!rc && hipMemsetAsync(c->feats, 0xFF, B * Fm * sizeof(xivo_feat_in), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (!rc && hipMemsetAsync(c->mask, 0, B * Fm, c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (!rc) c->Fmax = Fm;
+  return rc;
+}
+
+// the transposed dense copy: a G-level producer may have skipped it (mixed stacking); a consumer that needs it - the dense-row gate, the as-coded K H - I - rebuilds it from H here
+int ensure_HT(xivo_hip_ctx* c) {
+  if (c->ht_valid) return XIVO_HIP_OK;
+  StageTimer st(c, ST_STACK, 0.0, "transpose_H_kernel");
+  if (launch_transpose_H(c->H, c->sH, c->Mpmax, c->HT, c->sHT, c->Np, c->Mpmax, c->Np, c->Bmax, c->stream)) return XIVO_HIP_ERR_HIP;
+  c->ht_valid = true;
+  return XIVO_HIP_OK;
+}
+
+// the dense copies of the stacked rows, for the consumers that need them (dense pipeline, OOS rows, get_H)
+int ensure_dense(xivo_hip_ctx* c) {
+  if (c->dense_valid) return XIVO_HIP_OK;
+  c->dense_valid = true;
+  if (c->mixed_row0 >= 0) {   // mixed stacking: the in-state rows come from the compressed form, the OOS rows are in place
+    c->h_clean = false; c->ht_valid = false;
+    StageTimer st(c, ST_STACK, 0.0, "ell_to_dense_kernel");
+    return launch_ell_to_dense(c->ell, c->H, c->sH, c->Mpmax, nullptr, c->sHT, c->Np, c->Mpmax, c->Np, c->Bmax, c->stream, c->mixed_row0)
+               ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
+  }
+  c->h_clean = false;
+  if (c->dense_from_ell) {   // S-level hand-over: the compressed rows are the source (filters that do not fit hold dense rows already)
+    StageTimer st(c, ST_STACK, 0.0, "ell_to_dense_kernel");
+    return launch_ell_to_dense(c->ell, c->H, c->sH, c->Mpmax, c->HT, c->sHT, c->Np, c->Mpmax, c->Np, c->Bmax, c->stream)
+               ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
+  }
+  if (c->lead_valid) {   // online-calibration stacking on the sparse pipeline: dense rows carry the calibration columns themselves
+    c->lead_valid = false;
+    for (int b = 0; b < c->stack_B; ++b) c->ell_over_h[b] = 1;
+  }
+  return stack_impl(c, c->stack_B, c->stack_R, 1);
+}
+
+int gate_dense_rows(xivo_hip_ctx* c, int B, GateDenseArgs a) {
+  int rc = ensure_HT(c);   // (the gate reads - and neutralises - the transposed rows too)
+  if (rc) return rc;
+  const int Np = c->Np, ldh = c->Mpmax;
+  GemmExtra x; x.C2 = c->PHT; x.sC2 = c->sK; x.ldc2 = Np;
+  rc = gemm(c, ST_HP, B, c->Mp, Np, c->H, c->sH, ldh, c->P, c->sP, Np, Np, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, c->HP, c->sH, ldh, x);
+  if (rc) return rc;
+  a.H = c->H; a.strideH = c->sH; a.ldh = ldh; a.HP = c->HP; a.strideHP = c->sH; a.ldhp = ldh;
+  a.Hw = c->H; a.HTw = c->HT; a.strideHT = c->sHT; a.ldht = Np; a.HPw = nullptr; a.PHTw = nullptr; a.PHTr = c->PHT;
+  a.inn = c->inn; a.strideInn = c->Mpmax; a.diagR = c->diagR; a.strideR = c->Mpmax; a.Np = Np; a.batch = B; a.ell = c->ell;
+  StageTimer st(c, ST_GATE, 0.0, "gate_dense_kernel");
+  HIP_TRY((hipError_t)launch_gate_dense(a, c->stream));
+  return XIVO_HIP_OK;
+}
+
+}  // namespace xivo_hip::capi
+
+extern "C" {
+
+int xivo_hip_set_layout(xivo_hip_ctx* c, const xivo_layout* lay, const xivo_cam* cam) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !lay || !cam) return XIVO_HIP_ERR_INVALID;
+  if (lay->N != c->N || lay->group_begin < 21 || lay->n_groups <= 0 || lay->n_features <= 0 ||
+      lay->feature_begin < lay->group_begin + 6 * lay->n_groups ||
+      lay->feature_begin + 3 * lay->n_features > lay->N)
+    return XIVO_HIP_ERR_INVALID;
+  if (cam->model < XIVO_CAM_PINHOLE || cam->model > XIVO_CAM_EQUI) return XIVO_HIP_ERR_INVALID;
+  c->lay = *lay; c->cam = *cam; c->have_layout = true;
+  if (!c->poses) {
+    int rc = dev_alloc(&c->poses, (size_t)c->Bmax);
+    if (!rc) rc = dev_alloc(&c->absorb_count, (size_t)c->Bmax);
+    if (!rc) rc = dev_alloc(&c->groups, (size_t)c->Bmax * lay->n_groups);
+    if (rc) return rc;
+  }
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_set_scene(xivo_hip_ctx* c, int b0, int nb, int F, const xivo_pose_in* poses,
+                       const xivo_group_in* groups, const xivo_feat_in* feats) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->have_layout || F <= 0 || 2 * F > c->Mmax || !poses || !groups || !feats)
+    return XIVO_HIP_ERR_INVALID;
+  int rc = ensure_gate_buffers(c, F);
+  if (rc) return rc;
+  for (long i = 0; i < (long)nb * F; ++i) {
+    const xivo_feat_in& f = feats[i];
+    if (f.sind == -1) continue;   // absent entry
+    if (f.ref_sind < 0 || f.ref_sind >= c->lay.n_groups || f.sind < 0 || f.sind >= c->lay.n_features)
+      return XIVO_HIP_ERR_INVALID;
+  }
+  c->F = F;
+  HIP_TRY(hipMemcpyAsync(c->poses + b0, poses, (size_t)nb * sizeof(xivo_pose_in), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->groups + (size_t)b0 * c->lay.n_groups, groups,
+                         (size_t)nb * c->lay.n_groups * sizeof(xivo_group_in), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpy2DAsync(c->feats + (size_t)b0 * c->Fmax, (size_t)c->Fmax * sizeof(xivo_feat_in), feats,
+                           (size_t)F * sizeof(xivo_feat_in), (size_t)F * sizeof(xivo_feat_in), nb,
+                           hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_jacobians_instate(xivo_hip_ctx* c, int B) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0) return XIVO_HIP_ERR_INVALID;
+  StageTimer st(c, ST_JAC, 0.0, "jac_instate_kernel");
+  return launch_jac_instate(scene_buffers(c), c->lay, c->cam, B, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
+}
+
+int xivo_hip_get_jacobians(xivo_hip_ctx* c, int b0, int nb, double* J, double* inn) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || c->F <= 0) return XIVO_HIP_ERR_INVALID;
+  const size_t F = c->F, Fm = c->Fmax;
+  if (J) {
+    int rc = d2h_rows(c, J, F * 42 * sizeof(double), c->J + (size_t)b0 * Fm * 42, Fm * 42 * sizeof(double),
+                      F * 42 * sizeof(double), nb);
+    if (rc) return rc;
+  }
+  if (inn) {
+    int rc = d2h_rows(c, inn, F * 2 * sizeof(double), c->finn + (size_t)b0 * Fm * 2, Fm * 2 * sizeof(double),
+                      F * 2 * sizeof(double), nb);
+    if (rc) return rc;
+  }
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_set_calib(xivo_hip_ctx* c, const xivo_calib_layout* layout) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !c->have_layout) return XIVO_HIP_ERR_INVALID;
+  if (!layout) { c->calib_on = false; c->calib_motion = false; c->cl = xivo_calib_layout{-1, -1, 0, 0}; return XIVO_HIP_OK; }
+  const xivo_calib_layout& l = *layout;
+  const int N = c->N;
+  if (l.td >= N || (l.Cg >= 0 && l.Cg + 15 > N) || l.cam_dim < 0 || l.cam_dim > 9 ||
+      (l.cam_dim > 0 && (l.cam_begin < 0 || l.cam_begin + l.cam_dim > N)))
+    return XIVO_HIP_ERR_INVALID;
+  // slots as src/core.h:40-75 numbers them: td right behind Wsg, Cg behind td (or Wsg), the intrinsics behind the motion block
+  if ((l.td >= 0 && l.td != 23) || (l.Cg >= 0 && l.Cg != (l.td >= 0 ? 24 : 23))) return XIVO_HIP_ERR_INVALID;
+  if (!c->calib) { int rc = dev_alloc(&c->calib, (size_t)c->Bmax); if (rc) return rc; }
+  if (!c->Jc && c->Fmax > 0) { int rc = dev_alloc(&c->Jc, (size_t)c->Bmax * c->Fmax * 44); if (rc) return rc; }
+  if (!c->Hlead) { int rc = dev_alloc(&c->Hlead, (size_t)c->Bmax * c->Mpmax * LEAD_K); if (rc) return rc; }
+  c->lead_valid = false;
+  c->cl = l;
+  c->calib_on = l.td >= 0 || l.cam_dim > 0;       // measurement side: blocks beyond the default build's (the Cg / bg blocks sit inside the td block)
+  c->calib_motion = l.td >= 0 || l.Cg >= 0;       // motion side: kMotionSize > 23
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_set_calib_state(xivo_hip_ctx* c, int b0, int nb, const xivo_calib_in* calib) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !calib || !c->calib) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  HIP_TRY(hipMemcpyAsync(c->calib + b0, calib, (size_t)nb * sizeof(xivo_calib_in), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));    // host buffer is only borrowed for the call
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_set_calib_gyro(xivo_hip_ctx* c, int b0, int nb, const double* gyro3) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !gyro3 || !c->calib) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  static_assert(offsetof(xivo_calib_in, gyro) == 0, "gyro leads xivo_calib_in");
+  HIP_TRY(hipMemcpy2DAsync(c->calib + b0, sizeof(xivo_calib_in), gyro3, 3 * sizeof(double), 3 * sizeof(double), (size_t)nb,
+                           hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_get_calib_state(xivo_hip_ctx* c, int b0, int nb, xivo_calib_in* calib) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !calib || !c->calib) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  HIP_TRY(hipMemcpyAsync(calib, c->calib + b0, (size_t)nb * sizeof(xivo_calib_in), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_get_jacobians_calib(xivo_hip_ctx* c, int b0, int nb, double* Jc) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || c->F <= 0 || !Jc || !c->calib_on || !c->Jc) return XIVO_HIP_ERR_INVALID;
+  const size_t F = c->F, Fm = c->Fmax;
+  return d2h_rows(c, Jc, F * 44 * sizeof(double), c->Jc + (size_t)b0 * Fm * 44, Fm * 44 * sizeof(double), F * 44 * sizeof(double), nb);
+}
+
+int xivo_hip_mh_gate(xivo_hip_ctx* c, int B, double R, double mh_thresh, double mh_mult, int min_inliers,
+                     unsigned char* mask_out, double* dist_out) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0) return XIVO_HIP_ERR_INVALID;
+  // (online-calibration builds: the compact gate works on the whole row too - 43 columns, gate_sparse_kernel's wide form;
+  //  with XIVO_HIP_FLAG_DENSE_H the dense-row gate of round 4)
+  int rc = (c->calib_on && !calib_sparse(c)) ? calib_gate(c, B, R, mh_thresh, mh_mult, min_inliers, 1)
+                                             : gate_impl(c, B, R, mh_thresh, mh_mult, min_inliers, 1);
+  if (rc) return rc;
+  const size_t F = c->F, Fm = c->Fmax;
+  if (mask_out) { rc = d2h_rows(c, mask_out, F, c->mask, Fm, F, B); if (rc) return rc; }
+  if (dist_out) {
+    rc = d2h_rows(c, dist_out, F * sizeof(double), c->dist, Fm * sizeof(double), F * sizeof(double), B);
+    if (rc) return rc;
+  }
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_stack(xivo_hip_ctx* c, int B, double R) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0) return XIVO_HIP_ERR_INVALID;
+  c->M = 2 * c->F; c->Mp = round_up16(c->M);
+  const bool csp = calib_sparse(c);
+  for (int b = 0; b < B; ++b) {
+    // (calibration blocks: up to 34 shared columns - dense rows, or compressed rows + the leading dense block)
+    c->ell_over_h[b] = (c->calib_on && !csp) ? 1 : 0; c->ell_nc_h[b] = 12;
+    c->ell_pw_h[b] = (c->flags & XIVO_HIP_FLAG_FIX_GROUP_BLOCK) ? 9 : 6;   // group block(s) + feature block
+  }
+  c->lead_valid = csp;
+  // the sparse-H pipeline reads only the compressed rows: skip the 2 x Mp x Np dense zero-fill + scatter
+  const int dense = ((c->flags & XIVO_HIP_FLAG_DENSE_H) || (c->calib_on && !csp)) ? 1 : 0;
+  c->dense_valid = dense != 0; c->dense_from_ell = false; c->stack_R = R; c->stack_B = B; c->oos_row0 = -1;
+  c->mixed_row0 = -1; if (dense) c->h_clean = false;
+  return stack_impl(c, B, R, dense);
+}
+
+int xivo_hip_oos_project(xivo_hip_ctx* c, int b0, int nb, int n_oos, const xivo_oos_in* feats, double Roos,
+                         int* rows_out) {
+  return xivo_hip_oos_project_ex(c, b0, nb, n_oos, feats, Roos, rows_out, 0u);
+}
+
+int xivo_hip_oos_project_ex(xivo_hip_ctx* c, int b0, int nb, int n_oos, const xivo_oos_in* feats, double Roos,
+                            int* rows_out, unsigned options) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->have_layout || n_oos <= 0 || b0 != 0) return XIVO_HIP_ERR_INVALID;
+  if (options & ~XIVO_HIP_OOS_WHOLE_BUFFER) return XIVO_HIP_ERR_INVALID;
+  // XIVO_HIP_OOS_WHOLE_BUFFER (src/oos.cpp:28 as coded): SlowGivens sees the whole 2 kMaxGroup-row buffers of the feature, so
+  // every feature contributes 2 kMaxGroup - 3 rows; the rows behind its 2 k observations are zero (include/xivo_hip.h)
+  const int whole = (options & XIVO_HIP_OOS_WHOLE_BUFFER) ? 2 * c->lay.n_groups : 0;
+  // feats == NULL: the list uploaded by the previous call is still resident (same nb, n_oos) - project it again
+  if (!feats && (!c->oos || c->oos_nb != nb || c->oos_n != n_oos || c->oos_whole != whole)) return XIVO_HIP_ERR_INVALID;
+  int max_rows = feats ? 0 : c->oos_max_rows;
+  for (int b = 0; feats && b < nb; ++b) {
+    int rows = 0;
+    for (int o = 0; o < n_oos; ++o) {
+      const xivo_oos_in& f = feats[(size_t)b * n_oos + o];
+      if (f.n_obs < 2 || f.n_obs > XIVO_OOS_MAX_OBS) return XIVO_HIP_ERR_INVALID;
+      for (int q = 0; q < f.n_obs; ++q)
+        if (f.group_sind[q] < 0 || f.group_sind[q] >= c->lay.n_groups) return XIVO_HIP_ERR_INVALID;
+      if (whole && 2 * f.n_obs > whole) return XIVO_HIP_ERR_INVALID;     // (more observations than the reference's buffer has rows)
+      rows += whole ? whole - 3 : 2 * f.n_obs - 3;
+    }
+    if (rows > max_rows) max_rows = rows;
+  }
+  if (c->M + max_rows > c->Mmax) return XIVO_HIP_ERR_INVALID;
+  // Mixed stacking (round 3, default whenever the in-state rows were stacked in the compressed form only and nothing
+  // forces the dense pipeline): the OOS rows go to the dense buffer behind the in-state rows and the update keeps the
+  // sparse walk for the in-state rows - only the OOS block takes the MFMA products (update_sparse_range). Needs a
+  // 16-row-padded OOS block inside the allocation; otherwise (and with XIVO_HIP_FLAG_DENSE_H) every row
+  // becomes dense as before.
+  const bool mixed = !c->calib_on && !c->dense_valid && !c->dense_from_ell && c->oos_row0 < 0 && b0 == 0 &&
+                     !(c->flags & XIVO_HIP_FLAG_DENSE_H) && (c->M % 2 == 0) &&
+                     c->M + round_up16(max_rows + 16) <= c->Mpmax && c->Np <= 512;
+  if (!mixed) { int rcd = ensure_dense(c); if (rcd) return rcd; c->mixed_row0 = -1; }
+  else {
+    // the OOS rows must start from zero: only the extrinsics and group columns are ever written there in this mode, so
+    // those are cleared (whole rows once, if anything else has used the dense buffer since it was allocated)
+    const int nz = round_up16(max_rows + 16) < c->Mpmax - c->M ? round_up16(max_rows + 16) : c->Mpmax - c->M;
+    if (!c->h_clean) {
+      HIP_TRY((hipError_t)launch_zero_rows(c->H, c->sH, c->Mpmax, 0, c->Mpmax, 0, c->Np, c->Bmax, c->stream));
+      c->h_clean = true;
+    } else {
+      HIP_TRY((hipError_t)launch_zero_rows(c->H, c->sH, c->Mpmax, c->M, nz, 15, 21, nb, c->stream));
+      HIP_TRY((hipError_t)launch_zero_rows(c->H, c->sH, c->Mpmax, c->M, nz, c->lay.group_begin, c->lay.group_begin + 6 * c->lay.n_groups, nb, c->stream));
+    }
+    c->mixed_row0 = c->M;
+  }
+  if (n_oos * nb > c->oos_cap) {
+    if (c->oos) hipFree(c->oos);
+    c->oos = nullptr; c->oos_cap = 0;
+    if (!feats) return XIVO_HIP_ERR_INVALID;
+    int rc = dev_alloc(&c->oos, (size_t)n_oos * c->Bmax);
+    if (rc) return rc;
+    c->oos_cap = n_oos * c->Bmax;
+  }
+  if (!c->oos_rows) { int rc = dev_alloc(&c->oos_rows, (size_t)c->Bmax); if (rc) return rc; }
+  if (feats) {
+    HIP_TRY(hipMemcpyAsync(c->oos, feats, (size_t)nb * n_oos * sizeof(xivo_oos_in), hipMemcpyHostToDevice, c->stream));
+    c->oos_nb = nb; c->oos_n = n_oos; c->oos_max_rows = max_rows; c->oos_whole = whole;
+  }
+  OosArgs a{};
+  a.feats = c->oos; a.n_oos = n_oos; a.poses = c->poses; a.groups = c->groups; a.lay = c->lay; a.cam = c->cam;
+  a.calib = c->calib_on ? c->calib : nullptr; a.cam_dim = c->calib_on ? c->cl.cam_dim : 0;
+  a.mb = meas_buffers(c); a.row0 = c->M; a.Mp = c->Mpmax; a.Np = c->Np; a.batch = nb; a.Roos = Roos; a.whole = whole;
+  if (mixed) { a.mb.HT = nullptr; c->ht_valid = false; }
+  c->oos_row0 = c->M; c->oos_R = Roos;
+  a.rows_out = c->oos_rows;
+  {
+    StageTimer st(c, ST_OTHER, 0.0);
+    HIP_TRY((hipError_t)launch_oos(a, c->stream));
+  }
+  if (rows_out) HIP_TRY(hipMemcpyAsync(rows_out, c->oos_rows, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->M += max_rows; c->Mp = round_up16(c->M);
+  if (!mixed) for (int b = b0; b < b0 + nb; ++b) c->ell_over_h[b] = 1;   // OOS rows are dense over the group blocks: dense path
+  return XIVO_HIP_OK;
+}
+
+// Estimator::OnePointRANSAC (src/update.cpp:213-393) for filters [0,B) on the resident state, after
+// xivo_hip_jacobians_instate + xivo_hip_mh_gate (the MH inlier mask is the input set):
+//   select (low-innovation set, temporary reference group)                       :238-301   ransac_select_kernel
+//   BackupState: P, nominal state, groups                                        :283       device-to-device copies
+//   zero P rows / cols of non-members                                            :299-316   ransac_zero_kernel
+//   partial update on the FULL rows J() of the low-innovation set + AbsorbError  :320-333   stack (full rows) + update + absorb
+//   re-Jacobians at the updated state, chi-square rescue                         :343-369   jac_instate + ransac_rescue_kernel
+//   RestoreState, re-Jacobians at the original state                             :383-387
+// The resulting inlier set replaces the MH mask (what xivo_hip_stack / xivo_hip_absorb_error read afterwards).
+int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_thresh, double ransac_chi2,
+                              const int* gauge_group, const unsigned long long* absorb_groups,
+                              unsigned char* inlier_mask_out, double* chi2_out, int* n_rejected_out) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0 || !c->mask || !c->poses) return XIVO_HIP_ERR_INVALID;
+  if (c->lay.n_groups > 64) return XIVO_HIP_ERR_UNSUPPORTED;
+  const size_t Bm = c->Bmax, ng = c->lay.n_groups;
+  // online-calibration builds: the calibration state is backed up / restored with X_ (imu_.BackupState, Camera::BackupState,
+  // src/estimator.cpp:1421-1427), the partial update stacks the whole rows J() as dense rows, AbsorbError retracts td / Cg / Ca /
+  // the intrinsics too, and the rescue test uses the whole-row distances of the dense-row gate
+  const bool cal = c->calib_on;
+  if (cal && !c->calib_rs) { int rc = dev_alloc(&c->calib_rs, Bm); if (rc) return rc; }
+  if (!c->Prs || c->rs_Fmax != c->Fmax) {
+    void* olds[] = {c->rs_low, c->rs_lowkeep, c->rs_keep, c->rs_chi};
+    for (void* p : olds) if (p) hipFree(p);
+    c->rs_low = c->rs_lowkeep = c->rs_keep = nullptr; c->rs_chi = nullptr;
+    int rc = XIVO_HIP_OK;
+    auto A = [&](auto** p, size_t n) { if (rc == XIVO_HIP_OK && !*p) rc = dev_alloc(p, n); };
+    A(&c->Prs, Bm * c->sP); A(&c->poses_rs, Bm); A(&c->groups_rs, Bm * ng);
+    A(&c->rs_low, Bm * c->Fmax); A(&c->rs_lowkeep, Bm * c->Fmax); A(&c->rs_keep, Bm * c->Fmax); A(&c->rs_chi, Bm * c->Fmax);
+    A(&c->rs_zg, Bm); A(&c->rs_gmask, Bm); A(&c->rs_state, Bm); A(&c->rs_gauge, Bm); A(&c->rs_nrej, Bm);
+    if (rc) return rc;
+    c->rs_Fmax = c->Fmax;
+  }
+  if (gauge_group) HIP_TRY(hipMemcpyAsync(c->rs_gauge, gauge_group, (size_t)B * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  else HIP_TRY(hipMemsetAsync(c->rs_gauge, 0xFF, (size_t)B * sizeof(int), c->stream));
+  if (absorb_groups) HIP_TRY(hipMemcpyAsync(c->rs_gmask, absorb_groups, (size_t)B * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+  RansacArgs a{};
+  a.sb = scene_buffers(c); a.lay = c->lay; a.P = c->P; a.strideP = c->sP; a.ldp = c->Np; a.Np = c->Np;
+  a.R = R; a.thresh = ransac_thresh; a.chi2 = ransac_chi2; a.gauge = c->rs_gauge;
+  a.low = c->rs_low; a.low_keep = c->rs_lowkeep; a.zero_groups = c->rs_zg; a.state = c->rs_state;
+  a.keep = c->rs_keep; a.chi = c->rs_chi; a.n_rejected = c->rs_nrej; a.batch = B;
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "ransac_select_kernel");
+    HIP_TRY((hipError_t)launch_ransac_select(a, c->stream));
+  }
+  // the low-innovation set as select found it (filters with nothing to update get an all-neutral stacking mask)
+  HIP_TRY(hipMemcpyAsync(c->rs_lowkeep, c->rs_low, (size_t)B * c->Fmax, hipMemcpyDeviceToDevice, c->stream));
+  // BackupState (src/estimator.cpp:1410-1428)
+  HIP_TRY(hipMemcpyAsync(c->Prs, c->P, (size_t)B * c->sP * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->poses_rs, c->poses, (size_t)B * sizeof(xivo_pose_in), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->groups_rs, c->groups, (size_t)B * ng * sizeof(xivo_group_in), hipMemcpyDeviceToDevice, c->stream));
+  if (cal) HIP_TRY(hipMemcpyAsync(c->calib_rs, c->calib, (size_t)B * sizeof(xivo_calib_in), hipMemcpyDeviceToDevice, c->stream));
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "ransac_zero_kernel");
+    HIP_TRY((hipError_t)launch_ransac_zero(a, c->P, c->stream));
+  }
+  // partial update: H_ rows = the full J() of the low-innovation inliers (:326 - no FillJacobianBlock), R_ on the diagonal
+  c->M = 2 * c->F; c->Mp = round_up16(c->M);
+  for (int b = 0; b < B; ++b) { c->ell_over_h[b] = cal ? 1 : 0; c->ell_nc_h[b] = 12; c->ell_pw_h[b] = 9; }
+  c->lead_valid = false;
+  const int dense = ((c->flags & XIVO_HIP_FLAG_DENSE_H) || cal) ? 1 : 0;
+  c->dense_valid = dense != 0; c->dense_from_ell = !cal; c->stack_R = R; c->stack_B = B;
+  c->oos_row0 = -1;   // the partial stacking replaces the rows of any earlier xivo_hip_oos_project (as xivo_hip_stack does)
+  c->mixed_row0 = -1; if (dense) c->h_clean = false;
+  int rc = stack_impl(c, B, R, dense, c->rs_low, 1);
+  if (rc) return rc;
+  rc = xivo_hip_update_joseph(c, B);
+  if (rc) return rc;
+  {  // AbsorbError (:333): in_current_ekf_update_ is empty at this point of Estimator::UpdateStep (cleared at
+     // src/manager.cpp:28, filled after OutlierRejection), so no feature state moves; State::counter is restored with X_
+    AbsorbArgs ab{};
+    ab.poses = c->poses; ab.groups = c->groups; ab.feats = c->feats; ab.mask = nullptr; ab.err = c->err; ab.strideErr = c->Np;
+    ab.lay = c->lay; ab.F = c->F; ab.Fmax = c->Fmax; ab.batch = B; ab.counter = nullptr; ab.status = c->status;
+    ab.group_mask = absorb_groups ? c->rs_gmask : nullptr;
+    ab.calib = (c->calib_on || c->calib_motion) ? c->calib : nullptr; ab.cl = c->cl;
+    StageTimer st(c, ST_OTHER, 0.0, "absorb_error_kernel");
+    HIP_TRY((hipError_t)launch_absorb_error(ab, c->stream));
+  }
+  rc = xivo_hip_jacobians_instate(c, B);                                   // :348 at the updated state
+  if (rc) return rc;
+  if (!cal) {
+    StageTimer st(c, ST_OTHER, 0.0, "ransac_rescue_kernel");
+    HIP_TRY((hipError_t)launch_ransac_rescue(a, c->stream));
+  } else {
+    // S = J P J^T + R of every MH inlier on its WHOLE row at the updated state against the partially updated P (:350-356):
+    // the rows stacked once more in full (scratch: xivo_hip_stack re-stacks the final inlier set), H P, the dense-row distances
+    c->dense_valid = true; c->dense_from_ell = false; c->h_clean = false;
+    rc = stack_impl(c, B, R, 1, nullptr, /*full_rows=*/1);
+    if (rc) return rc;
+    GateDenseArgs ga{};
+    // (scratch outputs: the mask goes to rs_low - dead once the partial update is stacked -, the distances to rs_chi, where the
+    //  decision kernel below reads them and leaves chi2 per tested feature; c->dist keeps the MH distances)
+    ga.mask = c->rs_low; ga.dist = c->rs_chi; ga.F = c->F; ga.mask_ld = c->Fmax;
+    ga.R = R; ga.thresh = ransac_chi2; ga.mult = 1.0; ga.min_inliers = -1; ga.no_relax = 1;
+    ga.have_ell = 0; ga.feats = c->feats; ga.Fmax = c->Fmax;
+    rc = gate_dense_rows(c, B, ga);
+    if (rc) return rc;
+    StageTimer st(c, ST_OTHER, 0.0, "ransac_rescue_dist_kernel");
+    HIP_TRY((hipError_t)launch_ransac_rescue_dist(a, c->rs_chi, c->Fmax, c->stream));
+  }
+  // RestoreState + Jacobians at the original state (:383-387)
+  HIP_TRY(hipMemcpyAsync(c->P, c->Prs, (size_t)B * c->sP * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->poses, c->poses_rs, (size_t)B * sizeof(xivo_pose_in), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->groups, c->groups_rs, (size_t)B * ng * sizeof(xivo_group_in), hipMemcpyDeviceToDevice, c->stream));
+  if (cal) HIP_TRY(hipMemcpyAsync(c->calib, c->calib_rs, (size_t)B * sizeof(xivo_calib_in), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->mask, c->rs_keep, (size_t)B * c->Fmax, hipMemcpyDeviceToDevice, c->stream));
+  rc = xivo_hip_jacobians_instate(c, B);
+  if (rc) return rc;
+  c->gate_sparse_last = 1;
+  const size_t F = c->F, Fm = c->Fmax;
+  if (inlier_mask_out) { rc = d2h_rows(c, inlier_mask_out, F, c->mask, Fm, F, B); if (rc) return rc; }
+  if (chi2_out) { rc = d2h_rows(c, chi2_out, F * sizeof(double), c->rs_chi, Fm * sizeof(double), F * sizeof(double), B); if (rc) return rc; }
+  if (n_rejected_out) HIP_TRY(hipMemcpyAsync(n_rejected_out, c->rs_nrej, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // gauge_group / absorb_groups are borrowed host memory
+  return XIVO_HIP_OK;
+}
+
+// Estimator::CloseLoopInternal's stacking (src/update.cpp:183-196) with Feature::ComputeLCJacobian (src/oos.cpp:92-145) on the
+// resident scene: the 2n rows of every filter are built dense in a scratch block (lc_rows_kernel) and handed over like any
+// device-resident H_ (stage_measurements: row-pair compressed where they fit - group block private, extrinsics [+ intrinsics]
+// common -, so the update that follows takes the sparse pipeline). The inlier mask of the last gating pass is left alone:
+// AbsorbError after a loop closure updates in_current_ekf_update_ as the last FilterUpdate left it (src/estimator.cpp:906-912).
+int xivo_hip_close_loop_stack(xivo_hip_ctx* c, int b0, int nb, int n, const xivo_lc_match* matches, double Rlc) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->have_layout || !c->poses || !c->feats || n <= 0 || 2 * n > c->Mmax || !matches || !(Rlc > 0.0))
+    return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  for (size_t i = 0; i < (size_t)nb * n; ++i) {
+    const xivo_lc_match& m = matches[i];
+    if (m.feat >= c->F || (m.feat >= 0 && (m.group_sind < 0 || m.group_sind >= c->lay.n_groups))) return XIVO_HIP_ERR_INVALID;
+  }
+  const int M = 2 * n, N = c->N;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_m = 0, o_H = al((size_t)nb * n * sizeof(xivo_lc_match)), o_inn = al(o_H + (size_t)nb * M * N * sizeof(double)),
+               o_R = al(o_inn + (size_t)nb * M * sizeof(double)), total = al(o_R + (size_t)nb * M * sizeof(double));
+  if (total > c->lc_cap) {
+    if (c->lc_buf) hipFree(c->lc_buf);
+    c->lc_buf = nullptr; c->lc_cap = 0;
+    if (hipMalloc(&c->lc_buf, total) != hipSuccess) { (void)hipGetLastError(); return XIVO_HIP_ERR_NOMEM; }
+    c->lc_cap = total;
+  }
+  char* base = static_cast<char*>(c->lc_buf);
+  HIP_TRY(hipMemcpyAsync(base + o_m, matches, (size_t)nb * n * sizeof(xivo_lc_match), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(base + o_H, 0, (size_t)nb * M * N * sizeof(double), c->stream));     // H_.setZero(2n, N) (update.cpp:184)
+  LcArgs a{};
+  a.matches = reinterpret_cast<const xivo_lc_match*>(base + o_m); a.n = n;
+  a.poses = c->poses + b0; a.groups = c->groups + (size_t)b0 * c->lay.n_groups; a.feats = c->feats + (size_t)b0 * c->Fmax; a.Fmax = c->Fmax;
+  a.lay = c->lay; a.cam = c->cam; a.calib = c->calib_on ? c->calib + b0 : nullptr;
+  a.cl = c->calib_on ? c->cl : xivo_calib_layout{-1, -1, 0, 0}; a.invdepth = (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0;
+  a.H = reinterpret_cast<double*>(base + o_H); a.strideH = (long)M * N; a.ldh = M;
+  a.inn = reinterpret_cast<double*>(base + o_inn); a.diagR = reinterpret_cast<double*>(base + o_R); a.strideV = M;
+  a.Rlc = Rlc; a.batch = nb;
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "lc_rows_kernel");
+    HIP_TRY((hipError_t)launch_lc_rows(a, c->stream));
+  }
+  c->oos_row0 = -1;
+  return stage_measurements(c, b0, nb, M, a.H, a.strideH, a.ldh, a.inn, a.strideV, a.diagR, a.strideV);
+}
+
+// Measurement compression of the OOS rows appended by the last xivo_hip_oos_project (use_compression_ /
+// compression_trigger_ratio_, src/estimator.h:399-402; xivo::QR, src/helpers.cpp:77-101): per filter, when the block
+// has more than trigger_ratio times as many rows as non-zero columns, it is replaced by the triangular factor of its QR
+// decomposition (oos_compress_kernel) and the row count of the stacked measurement shrinks accordingly.
+int xivo_hip_compress_oos(xivo_hip_ctx* c, int B, double trigger_ratio, int* rows_out) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->oos_row0 < 0 || !c->oos_rows || B != c->oos_nb || !(trigger_ratio >= 1.0))
+    return XIVO_HIP_ERR_INVALID;
+  OosCompressArgs a{};
+  a.lay = c->lay; a.mb = meas_buffers(c); a.row0 = c->oos_row0; a.rows = c->oos_rows; a.rows_out = c->oos_rows;
+  if (c->mixed_row0 >= 0) { a.mb.HT = nullptr; c->ht_valid = false; }
+  a.ratio = trigger_ratio; a.Roos = c->oos_R; a.batch = B;
+  int rc;
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "oos_compress_kernel");
+    rc = launch_oos_compress(a, c->oos_max_rows, c->stream);
+  }
+  if (rc > 0) return XIVO_HIP_ERR_HIP;
+  std::vector<int> rows(B);
+  HIP_TRY(hipMemcpyAsync(rows.data(), c->oos_rows, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int mx = 0;
+  for (int b = 0; b < B; ++b) mx = rows[b] > mx ? rows[b] : mx;
+  // (rc == -1: block larger than the built kernels - rows are left as they are, which is always valid)
+  c->M = c->oos_row0 + mx; c->Mp = round_up16(c->M); c->oos_max_rows = mx;
+  if (rows_out) memcpy(rows_out, rows.data(), (size_t)B * sizeof(int));
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_filter_update(xivo_hip_ctx* c, int B, double R, double mh_thresh, double mh_mult, int min_inliers,
+                           int use_gating) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0) return XIVO_HIP_ERR_INVALID;
+  int rc = xivo_hip_jacobians_instate(c, B);
+  if (rc) return rc;
+  // Estimator::OutlierRejection only gates when F > min_required_inliers_ (src/manager.cpp:635)
+  const int gate = use_gating && c->F > min_inliers;
+  if (c->calib_on && !calib_sparse(c)) {
+    // online-calibration builds on dense rows (XIVO_HIP_FLAG_DENSE_H): the gate needs the WHOLE row J() incl. the td / Cg / bg / intrinsics blocks (update.cpp:60-70),
+    // which is not the row FillJacobianBlock stacks (the :675-676 overwrite): every present feature is stacked once as its
+    // full J() (dense rows), gated on (J P) J^T + R by the dense-row gate, then the inliers are stacked as coded and updated
+    rc = calib_gate(c, B, R, mh_thresh, mh_mult, min_inliers, gate);
+    if (rc) return rc;
+    rc = xivo_hip_stack(c, B, R);
+    if (rc) return rc;
+    return xivo_hip_update_joseph(c, B);
+  }
+  rc = gate_impl(c, B, R, mh_thresh, mh_mult, min_inliers, gate);
+  if (rc) return rc;
+  rc = xivo_hip_stack(c, B, R);
+  if (rc) return rc;
+  return xivo_hip_update_joseph(c, B);
+}
+
+static int givens_impl(xivo_hip_ctx* c, int nb, int rows, int nx, int nf, double* x, double* Hx, double* Hf,
+                       int effective_rows, int* rows_out, int qr) {
+  if (!c || nb <= 0 || rows < 2 || nx <= 0 || !x || !Hx || (!qr && (!Hf || nf <= 0 || nf > 64)) || (qr && nx > 512))
+    return XIVO_HIP_ERR_INVALID;
+  const int eff = effective_rows < 0 ? rows : effective_rows;
+  // the reference CHECKs these (helpers.cpp:49-53, 79-84); here they are an error code
+  if (eff > rows || eff < 2 || (qr ? eff <= nx : eff < nf)) return XIVO_HIP_ERR_INVALID;
+  const size_t ex = (size_t)nb * rows, ehx = (size_t)nb * rows * nx, ehf = qr ? 0 : (size_t)nb * rows * nf;
+  int rc = ensure_staging(c, ex + ehx + ehf);
+  if (rc) return rc;
+  double* dx = c->staging; double* dHx = dx + ex; double* dHf = dHx + ehx;
+  HIP_TRY(hipMemcpyAsync(dx, x, ex * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dHx, Hx, ehx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (!qr) HIP_TRY(hipMemcpyAsync(dHf, Hf, ehf * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  GivensArgs a{}; a.x = dx; a.Hx = dHx; a.Hf = qr ? nullptr : dHf; a.rows = rows; a.nx = nx; a.nf = nf; a.eff = effective_rows;
+  a.batch = nb; a.qr = qr;
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "givens_kernel");
+    HIP_TRY((hipError_t)launch_givens(a, c->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(x, dx, ex * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(Hx, dHx, ehx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (!qr) HIP_TRY(hipMemcpyAsync(Hf, dHf, ehf * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (rows_out) for (int b = 0; b < nb; ++b) rows_out[b] = qr ? eff : eff - nf;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_givens(xivo_hip_ctx* c, int nb, int rows, int nx, int nf, double* x, double* Hx, double* Hf,
+                    int effective_rows, int* rows_out) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  return givens_impl(c, nb, rows, nx, nf, x, Hx, Hf, effective_rows, rows_out, 0);
+}
+
+int xivo_hip_qr(xivo_hip_ctx* c, int nb, int rows, int nx, double* x, double* Hx, int effective_rows, int* rows_out) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  return givens_impl(c, nb, rows, nx, 0, x, Hx, nullptr, effective_rows, rows_out, 1);
+}
+
+int xivo_hip_subfilter_update(xivo_hip_ctx* c, int b0, int nb, int n, xivo_subfilter_feat* feats,
+                              const xivo_subfilter_opts* opts) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->have_layout || !c->poses || n <= 0 || !feats || !opts) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  for (size_t i = 0; i < (size_t)nb * n; ++i)
+    if (feats[i].ref_sind < 0 || feats[i].ref_sind >= c->lay.n_groups) return XIVO_HIP_ERR_INVALID;
+  const size_t bytes = (size_t)nb * n * sizeof(xivo_subfilter_feat);
+  if (bytes > c->sub_cap) {
+    if (c->sub) hipFree(c->sub);
+    c->sub = nullptr; c->sub_cap = 0;
+    if (hipMalloc((void**)&c->sub, bytes) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
+    c->sub_cap = bytes;
+  }
+  HIP_TRY(hipMemcpyAsync(c->sub, feats, bytes, hipMemcpyHostToDevice, c->stream));
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "subfilter_kernel");
+    if (launch_subfilter(c->sub, n, c->poses + b0, c->groups + (size_t)b0 * c->lay.n_groups, c->lay.n_groups, c->cam,
+                         *opts, nb, c->stream, c->calib_on ? c->calib + b0 : nullptr, c->calib_on ? c->cl.cam_dim : 0,
+                         (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0))
+      return XIVO_HIP_ERR_HIP;
+  }
+  HIP_TRY(hipMemcpyAsync(feats, c->sub, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+// Criteria::CandidateComparison (src/options.cpp:34-61) and the selection order of SelectAndAddNewFeatures /
+// AddFeaturesToState-style loops (src/manager.cpp:364-376,417-421): host arithmetic on the array
+// xivo_hip_subfilter_update returned - no device work.
+int xivo_hip_candidate_order(const xivo_subfilter_feat* feats, int nb, int n, int strict, int score_type, int* order_out,
+                             int* n_out, double* score_out) {
+  if (!feats || nb < 0 || n <= 0 || !order_out || !n_out || score_type < 0 || score_type > 2) return XIVO_HIP_ERR_INVALID;
+  for (int b = 0; b < nb; ++b) {
+    const xivo_subfilter_feat* f = feats + (size_t)b * n;
+    std::vector<int> idx;
+    for (int i = 0; i < n; ++i) {
+      if (score_out) {
+        const double dn = sqrt(f[i].P[0] * f[i].P[0] + f[i].P[4] * f[i].P[4] + f[i].P[8] * f[i].P[8]);   // P().diagonal().norm()
+        score_out[(size_t)b * n + i] = score_type == 0 ? -1.0 * f[i].P[8] : (score_type == 1 ? -1.0 * dn : -1.0 * (dn + f[i].outlier_counter));
+      }
+      if (f[i].candidate & (strict ? 2 : 1)) idx.push_back(i);
+    }
+    // as coded, the comparison ignores the score it has just computed from comparison_score_type and orders by
+    // status, then Feature::score() = -P(2,2) (options.cpp:60); FeatureStatus READY = 2 > INITIALIZING = 1 (core.h:190-199).
+    // std::sort leaves the order of equivalent elements unspecified: here ties keep the list order.
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int c2) {
+      const int s1 = f[a].status == XIVO_FEAT_READY ? 2 : 1, s2 = f[c2].status == XIVO_FEAT_READY ? 2 : 1;
+      return (s1 > s2) || (s1 == s2 && -f[a].P[8] > -f[c2].P[8]);
+    });
+    n_out[b] = (int)idx.size();
+    for (int i = 0; i < n; ++i) order_out[(size_t)b * n + i] = i < (int)idx.size() ? idx[i] : -1;
+  }
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_absorb_error(xivo_hip_ctx* c, int B) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0 || !c->mask) return XIVO_HIP_ERR_INVALID;
+  AbsorbArgs a{};
+  a.poses = c->poses; a.groups = c->groups; a.feats = c->feats; a.mask = c->mask; a.err = c->err; a.strideErr = c->Np;
+  a.lay = c->lay; a.F = c->F; a.Fmax = c->Fmax; a.batch = B; a.counter = c->absorb_count; a.status = c->status;
+  a.calib = (c->calib_on || c->calib_motion) ? c->calib : nullptr; a.cl = c->cl;
+  StageTimer st(c, ST_OTHER, 0.0);
+  return launch_absorb_error(a, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
+}
+
+int xivo_hip_edit_batch(xivo_hip_ctx* c, int F, int n_ops, const xivo_edit_op* ops) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !c->have_layout || !c->poses || F <= 0 || 2 * F > c->Mmax || n_ops < 0 || (n_ops > 0 && !ops))
+    return XIVO_HIP_ERR_INVALID;
+  int rc = ensure_gate_buffers(c, F);
+  if (rc) return rc;
+  const xivo_layout& L = c->lay;
+  std::vector<int> wg_filter, wg_begin;
+  for (int o = 0; o < n_ops; ++o) {
+    const xivo_edit_op& e = ops[o];
+    if (e.b < 0 || e.b >= c->Bmax || (o > 0 && e.b < ops[o - 1].b)) return XIVO_HIP_ERR_INVALID;
+    bool ok = false;
+    switch (e.kind) {
+      case XIVO_EDIT_P_ZERO_RC: ok = e.i0 >= 0 && e.i1 >= 0 && e.i0 + e.i1 <= c->N; break;
+      case XIVO_EDIT_P_COPY_RC: ok = e.i0 >= 0 && e.i1 >= 0 && e.i2 >= 0 && e.i0 + e.i2 <= c->N && e.i1 + e.i2 <= c->N; break;
+      case XIVO_EDIT_P_SET_BLOCK3: ok = e.i0 >= 0 && e.i0 + 3 <= c->N; break;
+      case XIVO_EDIT_ADD_GROUP: case XIVO_EDIT_REMOVE_GROUP: ok = e.i0 >= 0 && e.i0 < L.n_groups; break;
+      case XIVO_EDIT_ADD_FEATURE:
+        ok = e.i0 >= 0 && e.i0 < F && e.i1 >= 0 && e.i1 < L.n_features && e.i2 >= 0 && e.i2 < L.n_groups; break;
+      case XIVO_EDIT_REMOVE_FEATURE: case XIVO_EDIT_SET_XP: ok = e.i0 >= 0 && e.i0 < F; break;
+      default: ok = false;
+    }
+    if (!ok) return XIVO_HIP_ERR_INVALID;
+    if (o == 0 || e.b != ops[o - 1].b) { wg_filter.push_back(e.b); wg_begin.push_back(o); }
+  }
+  c->F = F;
+  if (n_ops == 0) return XIVO_HIP_OK;
+  wg_begin.push_back(n_ops);
+  const int n_wg = (int)wg_filter.size();
+  const size_t bytes_ops = (size_t)n_ops * sizeof(xivo_edit_op);
+  const size_t bytes = bytes_ops + (size_t)(2 * n_wg + 1) * sizeof(int);
+  if (bytes > c->edit_cap) {
+    if (c->edit_buf) hipFree(c->edit_buf);
+    c->edit_buf = nullptr; c->edit_cap = 0;
+    const size_t cap = bytes * 2;
+    if (hipMalloc(&c->edit_buf, cap) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
+    c->edit_cap = cap;
+  }
+  char* d = (char*)c->edit_buf;
+  HIP_TRY(hipMemcpyAsync(d, ops, bytes_ops, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + bytes_ops, wg_filter.data(), (size_t)n_wg * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + bytes_ops + (size_t)n_wg * sizeof(int), wg_begin.data(), (size_t)(n_wg + 1) * sizeof(int),
+                         hipMemcpyHostToDevice, c->stream));
+  EditArgs a{};
+  a.ops = (const xivo_edit_op*)d; a.wg_filter = (const int*)(d + bytes_ops); a.wg_begin = a.wg_filter + n_wg;
+  a.P = c->P; a.strideP = c->sP; a.ldp = c->Np; a.Np = c->Np; a.lay = L;
+  a.poses = c->poses; a.groups = c->groups; a.feats = c->feats; a.Fmax = c->Fmax;
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "edit_batch_kernel");
+    HIP_TRY((hipError_t)launch_edit_batch(a, n_wg, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));   // the host vectors above are pageable staging
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_set_pixels(xivo_hip_ctx* c, int b0, int nb, int F, const double* xp) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->have_layout || !c->poses || F <= 0 || 2 * F > c->Mmax || !xp) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  int rc = ensure_gate_buffers(c, F);
+  if (rc) return rc;
+  rc = ensure_staging(c, (size_t)nb * F * 2);
+  if (rc) return rc;
+  c->F = F;
+  HIP_TRY(hipMemcpyAsync(c->staging, xp, (size_t)nb * F * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY((hipError_t)launch_set_pixels(c->feats + (size_t)b0 * c->Fmax, c->Fmax, F, c->staging, nb, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // xp is borrowed host memory
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_get_scene(xivo_hip_ctx* c, int b0, int nb, xivo_pose_in* poses, xivo_group_in* groups, xivo_feat_in* feats) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->have_layout || !c->poses) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  if (poses) HIP_TRY(hipMemcpyAsync(poses, c->poses + b0, (size_t)nb * sizeof(xivo_pose_in), hipMemcpyDeviceToHost, c->stream));
+  if (groups) HIP_TRY(hipMemcpyAsync(groups, c->groups + (size_t)b0 * c->lay.n_groups,
+                                     (size_t)nb * c->lay.n_groups * sizeof(xivo_group_in), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (feats && c->F > 0) {
+    int rc = d2h_rows(c, feats, (size_t)c->F * sizeof(xivo_feat_in), c->feats + (size_t)b0 * c->Fmax,
+                      (size_t)c->Fmax * sizeof(xivo_feat_in), (size_t)c->F * sizeof(xivo_feat_in), nb);
+    if (rc) return rc;
+  }
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_get_H(xivo_hip_ctx* c, int b, int* M_out, double* H, int ldh, double* inn, double* diagR) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b, 1) || c->M <= 0) return XIVO_HIP_ERR_INVALID;
+  const int M = c->M;
+  if (M_out) *M_out = M;
+  if (H) {
+    if (ldh < M) return XIVO_HIP_ERR_INVALID;
+    { int rcd = ensure_dense(c); if (rcd) return rcd; }
+    HIP_TRY(hipMemcpy2DAsync(H, (size_t)ldh * sizeof(double), c->H + (long)b * c->sH, (size_t)c->Mpmax * sizeof(double),
+                             (size_t)M * sizeof(double), c->N, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (inn) HIP_TRY(hipMemcpyAsync(inn, c->inn + (long)b * c->Mpmax, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (diagR) HIP_TRY(hipMemcpyAsync(diagR, c->diagR + (long)b * c->Mpmax, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+}  // extern "C"

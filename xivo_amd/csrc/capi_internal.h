@@ -1,0 +1,215 @@
+// Host-side internals shared by the translation units of the C ABI (include/xivo_hip.h):
+//   capi.hip            context, P residency, resident device buffers, timing / profile, the helpers declared below
+//   capi_update.hip     route table, measurement hand-over, the update pipelines, the L D L^T fallback, the one-filter call
+//   capi_glevel.hip     feature level: scene, Jacobians, gate, stacking, OOS rows, RANSAC, loop closure, Givens / QR, edits
+//   capi_propagate.hip  propagation
+// Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
+// defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <vector>
+
+#include "../../include/xivo_hip.h"
+#include "common.h"
+#include "ekf_kernels.h"
+#include "ell.h"
+#include "fused_update.h"
+
+namespace xivo_hip::capi {
+
+enum Stage : int {
+  ST_JAC = 0, ST_GATE, ST_STACK, ST_HP, ST_S, ST_CHOL, ST_TRSM, ST_KH, ST_AP, ST_PNEW, ST_OTHER, ST_PROP_STATE, ST_PROP_TAIL, ST_COUNT
+};
+inline const char* const kStageNames[ST_COUNT] = {"jac_instate", "mh_gate", "stack_H", "gemm_HP", "gemm_S", "chol_S",
+                                                  "trsm_gain", "gemm_KH_I", "gemm_AP", "gemm_Pnew", "other", "propagate_state",
+                                                  "propagate_tail"};
+
+struct EventPair { hipEvent_t a, b; int stage; };
+
+}  // namespace xivo_hip::capi
+
+struct xivo_hip_ctx {
+  int device = 0;
+  int N = 0, Np = 0, Mmax = 0, Mpmax = 0, Bmax = 0;
+  unsigned flags = 0;
+  hipStream_t stream = nullptr;
+  // per-filter device buffers
+  double *P = nullptr, *Psnap = nullptr, *H = nullptr, *HT = nullptr, *HP = nullptr, *PHT = nullptr, *S = nullptr;
+  double *K = nullptr, *A = nullptr, *T = nullptr, *invD = nullptr, *inn = nullptr, *diagR = nullptr;
+  double *err = nullptr, *staging = nullptr, *scratch = nullptr;
+  double *neg1 = nullptr, *yvec = nullptr;   // symmetric form: a vector of -1 (operand scale), y = L^-1 inn per filter
+  int* status = nullptr;
+  // row-pair compressed H (ell.h) + host mirror of the per-filter "does not fit" flag
+  xivo_hip::EllBuffers ell{};
+  std::vector<int> ell_over_h, ell_nc_h, ell_pw_h;
+  int* ell_flags_h = nullptr;   // pinned, device-mapped [Bmax][3]: over / nc / pw as the hand-over kernel leaves them
+  int* ell_flags_d = nullptr;   // its device alias
+  int last_path = 0;
+  int last_route = 0;   // UpdateRoute of the last pass (xivo_hip_last_route)
+  // dense H / H^T of the stacked rows: written eagerly by set_measurements, lazily after xivo_hip_stack
+  bool dense_valid = true;
+  bool dense_from_ell = false;   // the stacked rows came in through set_measurements (compressed rows are the source)
+  bool ht_valid = true;          // the transposed dense copy H^T matches H (false after a producer skipped it: mixed stacking)
+  // mixed stacking (round 3): in-state rows [0, mixed_row0) exist in the row-pair compressed form only, the OOS rows
+  // appended by xivo_hip_oos_project from row mixed_row0 on in the dense buffer only; -1: not in that mode
+  int mixed_row0 = -1;
+  bool h_clean = true;           // every row of the dense H buffer the mixed mode has not written itself is zero
+  double stack_R = 0.0; int stack_B = 0;
+  size_t staging_elems = 0;
+  long sP = 0, sH = 0, sHT = 0, sS = 0, sK = 0, sInvD = 0, sA = 0;   // sA: A buffer, max(N x N, N x M)
+  int M = 0, Mp = 0;  // rows currently staged
+  int chunk = 0;      // filters per pipeline pass (0 = whole batch)
+  int call_batch = 0; // filters of the whole update call being walked in chunks (0: not chunked)
+  int* ldlt_used = nullptr;     // per filter: 1 = the last update went through the pivoted L D L^T fallback
+  // G-level
+  xivo_layout lay{};
+  xivo_cam cam{};
+  bool have_layout = false;
+  // online-calibration builds, measurement side (xivo_hip_set_calib): extra Jacobian blocks, dense stacking
+  bool calib_on = false;       // measurement side of an online-calibration build (td / Cg / bg / intrinsics blocks)
+  bool calib_motion = false;   // motion side: kMotionSize > 23 (xivo_hip_propagate_calib)
+  xivo_calib_layout cl{-1, -1, 0, 0};
+  xivo_calib_in* calib = nullptr;   // [Bmax]
+  double* Jc = nullptr;             // [Bmax x Fmax x 44]
+  int Fmax = 0, F = 0;
+  xivo_pose_in* poses = nullptr;
+  int* absorb_count = nullptr;   // State::counter of every filter (src/core.h:120-122)
+  // OnePointRANSAC scratch (allocated on first use): BackupState copies, selection results
+  double* Prs = nullptr; xivo_pose_in* poses_rs = nullptr; xivo_group_in* groups_rs = nullptr;
+  unsigned char *rs_low = nullptr, *rs_lowkeep = nullptr, *rs_keep = nullptr;
+  unsigned long long *rs_zg = nullptr, *rs_gmask = nullptr;
+  int *rs_state = nullptr, *rs_gauge = nullptr, *rs_nrej = nullptr;
+  double* rs_chi = nullptr;
+  int rs_Fmax = 0;
+  xivo_group_in* groups = nullptr;
+  xivo_feat_in* feats = nullptr;
+  double *J = nullptr, *finn = nullptr, *dist = nullptr;
+  unsigned char* mask = nullptr;
+  int gate_sparse_last = 0;   // mask/dist row stride: Fmax after the layout-faithful gate, F after the dense one
+  int* rows_instate = nullptr;
+  xivo_oos_in* oos = nullptr;
+  int oos_cap = 0;
+  int oos_row0 = -1;   // first row of the OOS block of the last xivo_hip_oos_project (-1: none since the last stacking)
+  double oos_R = 0.0;
+  double* pd_h = nullptr; double pd_h0 = 0.0;   // step-size-controlled Dormand-Prince: the step each filter carries (xivo_hip_propagate)
+  int oos_nb = 0, oos_n = 0, oos_max_rows = 0, oos_whole = 0;   // shape of the resident OOS list (xivo_hip_oos_project with feats == NULL)
+  int* oos_rows = nullptr;
+  xivo_calib_in* calib_rs = nullptr;            // BackupState of the calibration state (OnePointRANSAC, online-calibration builds)
+  // online-calibration builds on the sparse pipeline (round 5): the calibration columns of the stacked rows as a dense
+  // [Mpmax x LEAD_K] block per filter next to the row-pair compressed rows; lead_valid: the current stacking has one
+  double* Hlead = nullptr; bool lead_valid = false;
+  void* lc_buf = nullptr; size_t lc_cap = 0;   // xivo_hip_close_loop_stack: matches | dense rows | inn | diagR
+  xivo_subfilter_feat* sub = nullptr;   // staging of xivo_hip_subfilter_update
+  std::vector<char> hstage;                        // host staging of d2h_rows
+  void* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
+  // one-filter plumbing call (xivo_hip_update_joseph_host): page-locked, device-mapped staging block owned by the context,
+  // scratch of the host-side row compression
+  char* pin_h = nullptr; char* pin_d = nullptr; size_t pin_bytes = 0;
+  struct HostCompressScratch { std::vector<int> cnt, occ, cslot, n; std::vector<double> v; } hc;
+  size_t sub_cap = 0;
+  // timing
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  std::vector<xivo_hip::capi::EventPair> pool;
+  size_t pool_used = 0;
+  float stage_ms[xivo_hip::capi::ST_COUNT] = {0};
+  int stage_launches[xivo_hip::capi::ST_COUNT] = {0};
+  double stage_flops[xivo_hip::capi::ST_COUNT] = {0};
+  double stage_bytes[xivo_hip::capi::ST_COUNT] = {0};         // algorithmic HBM bytes of the stage's last launch (inputs once + outputs once)
+  char stage_kernel[xivo_hip::capi::ST_COUNT][64] = {{0}};   // kernel instantiation of the stage's last launch (as rocprofv3 names it)
+};
+
+#pragma GCC visibility push(hidden)
+namespace xivo_hip::capi {
+
+// XIVO_HIP_DEBUG=1: name the failing runtime call on stderr (the C ABI itself only returns a status)
+inline bool debug_on() { static const bool on = getenv("XIVO_HIP_DEBUG") != nullptr; return on; }
+#define HIP_TRY(expr)                              \
+  do {                                             \
+    hipError_t e_ = (expr);                        \
+    if (e_ != hipSuccess) {                        \
+      if (xivo_hip::capi::debug_on()) fprintf(stderr, "xivo_hip: %s -> %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+      return XIVO_HIP_ERR_HIP;                     \
+    }                                              \
+  } while (0)
+
+template <class T>
+int dev_alloc(T** p, size_t n) {
+  if (n == 0) { *p = nullptr; return XIVO_HIP_OK; }
+  hipError_t e = hipMalloc((void**)p, n * sizeof(T));
+  if (e != hipSuccess) return XIVO_HIP_ERR_NOMEM;
+  e = hipMemset(*p, 0, n * sizeof(T));
+  return e == hipSuccess ? XIVO_HIP_OK : XIVO_HIP_ERR_HIP;
+}
+
+struct StageTimer {
+  xivo_hip_ctx* c; EventPair* ep = nullptr;
+  StageTimer(xivo_hip_ctx* ctx, int stage, double flops, const char* kernel = nullptr, double bytes = 0.0) : c(ctx) {
+    if (!(c->flags & XIVO_HIP_FLAG_PROFILE)) return;
+    c->stage_bytes[stage] = bytes;
+    if (kernel) { strncpy(c->stage_kernel[stage], kernel, 63); c->stage_kernel[stage][63] = 0; }
+    if (c->pool_used >= c->pool.size()) {
+      EventPair np; np.stage = stage;
+      if (hipEventCreate(&np.a) != hipSuccess || hipEventCreate(&np.b) != hipSuccess) return;
+      c->pool.push_back(np);
+    }
+    ep = &c->pool[c->pool_used++];
+    ep->stage = stage;
+    c->stage_launches[stage]++;
+    c->stage_flops[stage] = flops;
+    hipEventRecord(ep->a, c->stream);
+  }
+  ~StageTimer() { if (ep) hipEventRecord(ep->b, c->stream); }
+};
+
+struct GemmExtra {
+  int epi = EPI_NONE;
+  const double* diag = nullptr; long sDiag = 0;
+  const double* msub = nullptr; long sMsub = 0; int ldmsub = 0;
+  const double* mcol = nullptr; long sMcol = 0;
+  double* C2 = nullptr; long sC2 = 0; int ldc2 = 0;
+  int c2_rows = 0;   // > 0: the transposed copy only of the leading c2_rows rows of C (the columns of C2 a consumer reads)
+  int lower_only = 0;
+  int fp32 = 0;
+  int a_f32 = 0;   // first operand stored as float
+  int b_f32 = 0;   // second operand stored as float
+  int no_mirror = 0;
+  const int* skip = nullptr;   // per-filter status: non-zero = leave the output of that filter untouched
+  const double* scale0 = nullptr;   // per-k scale of the first segment's B operand (same vector for every filter)
+  int small_tiles = 0;   // symmetric output on 64 x 64 tiles (latency route)
+};
+
+// leading state columns the calibration blocks live in: td 23, Cg 24..32, (Ca 33..38,) bg 9..11, intrinsics up to 39..47
+constexpr int LEAD_K = 48;
+
+// ---- capi.hip
+bool bad_range(xivo_hip_ctx* c, int b0, int nb);
+MeasBuffers meas_buffers(xivo_hip_ctx* c);
+SceneBuffers scene_buffers(xivo_hip_ctx* c);
+bool calib_sparse(const xivo_hip_ctx* c);
+// C = A0 B0^T (+ A1 diag(scale1) B1^T) over the batch, on the MFMA product kernels, timed as `stage`
+int gemm(xivo_hip_ctx* c, int stage, int B, int rows, int cols, const double* A0, long sA0, int lda0,
+         const double* B0, long sB0, int ldb0, int K0, const double* A1, long sA1, int lda1, const double* B1,
+         long sB1, int ldb1, int K1, const double* scale1, long sScale1, double* C, long sC, int ldc,
+         const GemmExtra& x);
+int ensure_staging(xivo_hip_ctx* c, size_t elems);
+int d2h_rows(xivo_hip_ctx* c, void* dst, size_t hpitch, const void* src, size_t dpitch, size_t width, size_t rows);
+int h2d_packed(xivo_hip_ctx* c, double* dst, const double* src, int nb, int rows, int cols, long stride, int ld);
+int d2h_packed(xivo_hip_ctx* c, double* dst, const double* src, int nb, int rows, int cols, long stride, int ld);
+
+// ---- capi_update.hip
+int stage_measurements(xivo_hip_ctx* c, int b0, int nb, int M, const double* dH, long strideH, int ldh,
+                       const double* dInn, long strideInn, const double* dR, long strideR);
+
+// ---- capi_glevel.hip
+int ensure_gate_buffers(xivo_hip_ctx* c, int F);
+int ensure_dense(xivo_hip_ctx* c);
+int ensure_HT(xivo_hip_ctx* c);
+// H P (+ P H^T) of the stacked dense rows of filters [0, B) and the dense-row gate on them (gate_dense_kernel); `a` brings the
+// gate's own parameters and outputs, the row buffers are filled in here
+int gate_dense_rows(xivo_hip_ctx* c, int B, GateDenseArgs a);
+
+}  // namespace xivo_hip::capi
+#pragma GCC visibility pop

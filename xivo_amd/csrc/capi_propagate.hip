@@ -1,0 +1,139 @@
+// C ABI, propagation (include/xivo_hip.h): the covariance tail on given transition matrices, and Estimator::Propagate of the
+// default and the online-calibration builds (propagate_state* kernels + the tail). Host-side orchestration only
+// (capi_internal.h).
+#include <cmath>
+
+#include "capi_internal.h"
+
+using namespace xivo_hip;
+using namespace xivo_hip::capi;
+
+namespace {
+
+// control_stepsize (src/princedormand.cpp:26-60): Dormand-Prince with a positive cfg step and a growth factor only. The
+// reference's function-local static `h` starts at the cfg step (:23): one per filter here, reset when the cfg step changes.
+int prop_step_control(xivo_hip_ctx* c, const xivo_prop_opts* o) {
+  if (!o->control_stepsize) return XIVO_HIP_OK;
+  if (o->method != 1 || !(o->stepsize > 0) || !(o->max_scale_factor > 0)) return XIVO_HIP_ERR_INVALID;
+  if (c->pd_h && c->pd_h0 == o->stepsize) return XIVO_HIP_OK;
+  if (!c->pd_h) { int rcd = dev_alloc(&c->pd_h, (size_t)c->Bmax); if (rcd) return rcd; }
+  std::vector<double> h0((size_t)c->Bmax, o->stepsize);
+  HIP_TRY(hipMemcpy(c->pd_h, h0.data(), h0.size() * sizeof(double), hipMemcpyHostToDevice));
+  c->pd_h0 = o->stepsize;
+  return XIVO_HIP_OK;
+}
+
+// What both integrators take: the staging block (Phi [nb][nm x nm] | P_mm [nb][nm x nm] | Qimu 12 x 12 | Qmodel nm x nm | imu),
+// its uploads and the arguments of the state kernel the two share. The caller adds its own (nm, iCg, calib) and launches.
+int prop_stage(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_imu_in* imu, const xivo_prop_opts* o, int nm,
+               const double* Qmodel, PropStateArgs& a) {
+  const size_t per = (size_t)nm * nm;
+  const size_t imu_d = ((size_t)nb * n_imu * sizeof(xivo_imu_in) + 7) / 8;      // in doubles
+  int rc = ensure_staging(c, 2 * per * nb + 144 + per + imu_d);
+  if (rc) return rc;
+  double* dPhi = c->staging; double* dPmm = dPhi + per * nb; double* dQi = dPmm + per * nb; double* dQm = dQi + 144;
+  xivo_imu_in* dImu = reinterpret_cast<xivo_imu_in*>(dQm + per);
+  HIP_TRY(hipMemcpyAsync(dQi, o->Qimu, 144 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dQm, Qmodel, per * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dImu, imu, (size_t)nb * n_imu * sizeof(xivo_imu_in), hipMemcpyHostToDevice, c->stream));
+  a = PropStateArgs{};
+  a.poses = c->poses + b0; a.imu = dImu; a.n_imu = n_imu; a.Qimu = dQi; a.Qmodel = dQm;
+  a.g[0] = o->g[0]; a.g[1] = o->g[1]; a.g[2] = o->g[2]; a.method = o->method; a.stepsize = o->stepsize;
+  a.P = c->P + (long)b0 * c->sP; a.strideP = c->sP; a.ldp = c->Np; a.Phi_out = dPhi; a.Pmm_out = dPmm; a.batch = nb;
+  if (o->control_stepsize) {
+    a.pd_h = c->pd_h + b0; a.pd_tol = o->tolerance; a.pd_min_scale = o->min_scale_factor; a.pd_max_scale = o->max_scale_factor;
+  }
+  return XIVO_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int xivo_hip_propagate_cov(xivo_hip_ctx* c, int b0, int nb, int nm, const double* Phi, const double* Pmm) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || nm <= 0 || nm > 40 || nm > c->N || !Phi || !Pmm) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  const size_t per = (size_t)nm * nm;
+  int rc = ensure_staging(c, 2 * per * nb);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(c->staging, Phi, per * nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->staging + per * nb, Pmm, per * nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  {
+    StageTimer st(c, ST_OTHER, 0.0);
+    if (launch_propagate_cov(c->P, c->sP, c->Np, c->N, c->Np, nm, c->staging, c->staging + per * nb, b0, nb, c->stream))
+      return XIVO_HIP_ERR_HIP;
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_propagate(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_imu_in* imu, const xivo_prop_opts* o) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->have_layout || !c->poses || !imu || !o || n_imu <= 0 || c->N < 23 || c->lay.group_begin < 23)
+    return XIVO_HIP_ERR_INVALID;
+  if (c->calib_motion) return XIVO_HIP_ERR_UNSUPPORTED;   // kMotionSize > 23: xivo_hip_propagate_calib
+  if (nb == 0) return XIVO_HIP_OK;
+  for (size_t b = 0; b < (size_t)nb * n_imu; ++b)
+    if (!(imu[b].dt > 0.0) || (o->stepsize >= 0 && o->stepsize < 1e-6)) return XIVO_HIP_ERR_INVALID;
+  int rc = prop_step_control(c, o);
+  if (rc) return rc;
+  PropStateArgs a;
+  rc = prop_stage(c, b0, nb, n_imu, imu, o, 23, o->Qmodel, a);
+  if (rc) return rc;
+  {
+    char plabel[64];
+    snprintf(plabel, sizeof(plabel), "propagate_state_wave_kernel<%d>", a.method ? 7 : 4);
+    // algorithmic flops: per integrator sub-step and stage the 23 x 23 Lyapunov right-hand side
+    // F P + P F^T (2 * 2 * 23^3) and the transition recursion F + c F FK (2 * 23^3), as the reference codes them (dense);
+    // sub-steps as src/rk4.cpp:19-31 cuts a sample: ceil(dt / stepsize), the sample's own dt when stepsize <= 0
+    double substeps = 0.0;
+    for (int s = 0; s < n_imu; ++s) substeps += o->stepsize > 0 ? std::ceil(imu[s].dt / o->stepsize) : 1.0;
+    const double stage_flops = 6.0 * 23.0 * 23.0 * 23.0 + 2.0 * 23.0 * 12.0 * (12.0 + 23.0);
+    StageTimer st(c, ST_PROP_STATE, (double)nb * substeps * (a.method ? 7.0 : 4.0) * stage_flops, plabel,
+                  (double)nb * (3.0 * 529 + n_imu * sizeof(xivo_imu_in) / 8.0 + 60.0) * sizeof(double));
+    HIP_TRY((hipError_t)launch_propagate_state(a, c->stream));
+  }
+  {
+    // tail: reads and writes the 23 rows and 23 columns of P that change (+ Phi, P_mm)
+    StageTimer st(c, ST_PROP_TAIL, (double)nb * 2.0 * (2.0 * 23.0 * 23.0 * (c->N - 23)), "propagate_cov_fixed_kernel<23>",
+                  (double)nb * (4.0 * 23 * c->N + 2.0 * 529) * sizeof(double));
+    HIP_TRY((hipError_t)launch_propagate_cov(c->P, c->sP, c->Np, c->N, c->Np, 23, a.Phi_out, a.Pmm_out, b0, nb, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));   // imu / opts are borrowed host memory
+  return XIVO_HIP_OK;
+}
+
+// Estimator::Propagate of an online-calibration build (kMotionSize = 24 / 38 / 39): propagate_state_calib_kernel + the
+// run-time-nm tail
+int xivo_hip_propagate_calib(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_imu_in* imu, const xivo_prop_opts* o,
+                             const double* Qmodel) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->have_layout || !c->poses || !imu || !o || !Qmodel || n_imu <= 0 || !c->calib_motion || !c->calib)
+    return XIVO_HIP_ERR_INVALID;
+  const int nm = c->cl.Cg >= 0 ? c->cl.Cg + 15 : c->cl.td + 1;
+  if (nm > 40 || c->N < nm || c->lay.group_begin < nm) return XIVO_HIP_ERR_INVALID;
+  int rc = prop_step_control(c, o);   // (before the empty-range return, unlike xivo_hip_propagate)
+  if (rc) return rc;
+  if (nb == 0) return XIVO_HIP_OK;
+  for (size_t b = 0; b < (size_t)nb * n_imu; ++b)
+    if (!(imu[b].dt > 0.0) || (o->stepsize >= 0 && o->stepsize < 1e-6)) return XIVO_HIP_ERR_INVALID;
+  PropStateArgs a;
+  rc = prop_stage(c, b0, nb, n_imu, imu, o, nm, Qmodel, a);
+  if (rc) return rc;
+  a.nm = nm; a.iCg = c->cl.Cg; a.calib = c->calib + b0;
+  {
+    char plabel[64];
+    snprintf(plabel, sizeof(plabel), "propagate_state_calib_kernel<%d>", a.method ? 7 : 4);
+    StageTimer st(c, ST_PROP_STATE, 0.0, plabel);
+    HIP_TRY((hipError_t)launch_propagate_state_calib(a, c->stream));
+  }
+  {
+    StageTimer st(c, ST_PROP_TAIL, 0.0, "propagate_cov_kernel", (double)nb * (4.0 * nm * c->N + 2.0 * nm * nm) * sizeof(double));
+    HIP_TRY((hipError_t)launch_propagate_cov(c->P, c->sP, c->Np, c->N, c->Np, nm, a.Phi_out, a.Pmm_out, b0, nb, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));   // imu / opts / Qmodel are borrowed host memory
+  return XIVO_HIP_OK;
+}
+
+}  // extern "C"

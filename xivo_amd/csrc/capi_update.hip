@@ -1,0 +1,864 @@
+// C ABI, measurement update (include/xivo_hip.h): the route table, the hand-over of measurements, the update pipelines, the
+// L D L^T fallback, the one-filter plumbing call and the update's getters. Host-side orchestration only (capi_internal.h).
+#include <algorithm>
+
+#include "capi_internal.h"
+
+using namespace xivo_hip;
+using namespace xivo_hip::capi;
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Route selection of Estimator::UpdateJosephForm (src/estimator.cpp:1257-1288), in ONE place. Every pass of the update
+// (update_joseph_range) asks plan_update() once; the pipelines below only execute what the plan says, and
+// tests/test_update_gpu.py::test_every_route_of_the_plan enumerates the routes of this table against the oracle,
+// tests/test_update_edges_gpu.py runs shapes on both sides of each of its limits.
+//
+//   route              | rows of H                   | gain + covariance                                   | when
+//   -------------------+-----------------------------+-----------------------------------------------------+--------------------------
+//   FUSED              | row-pair compressed         | one kernel per filter (fused_update.hip)            | M <= 64 / N <= 256 or M <= 112 / N <= 192, and M <= N (rounded to 16), default form
+//   SPARSE_IN_SOLVE    | compressed (+ OOS / lead)   | whitened Joseph form inside the solve kernel        | N <= 256, M <= 176, > 64 filters
+//   SPARSE_WHITENED    | compressed (+ OOS / lead)   | whitened outputs V^T, Y^T + tiled P - V^T Y         | wider shapes; <= 64 filters (latency route)
+//   SPARSE_SYMMETRIC   | compressed                  | P - W^T W, forward substitution only                | XIVO_HIP_FLAG_SYMMETRIC_FORM
+//   SPARSE_TAIL        | compressed                  | T = K(HP) - P, G = T H^T + K R, P+ = G K^T - T      | XIVO_HIP_FLAG_STANDALONE_TAIL
+//   DENSE_ASCODED      | dense                       | A = KH - I, T = A P, P+ = T A^T + K R K^T           | XIVO_HIP_FLAG_DENSE_H
+//   DENSE_WHITENED     | dense (H does not compress) | dense H P and S, then as SPARSE_IN_SOLVE / _WHITENED | an H without XIVO's row structure
+//   DENSE_SYMMETRIC    | dense                       | as SPARSE_SYMMETRIC                                 | SYMMETRIC_FORM on dense rows
+enum UpdateRoute : int { ROUTE_FUSED = 0, ROUTE_SPARSE_IN_SOLVE, ROUTE_SPARSE_WHITENED, ROUTE_SPARSE_SYMMETRIC, ROUTE_SPARSE_TAIL,
+                         ROUTE_DENSE_ASCODED, ROUTE_DENSE_WHITENED, ROUTE_DENSE_SYMMETRIC, ROUTE_COUNT };
+static const char* kRouteNames[ROUTE_COUNT] = {"fused", "sparse_in_solve", "sparse_whitened", "sparse_symmetric", "sparse_tail",
+                                               "dense_ascoded", "dense_whitened", "dense_symmetric"};
+struct UpdatePlan {
+  int route;
+  bool sparse;        // the rows are used in their compressed form
+  bool in_solve;      // the covariance update runs inside the solve kernel (one workgroup per filter)
+  bool latency;       // few filters: streamed solve on four-wave workgroups + the product on 64 x 64 tiles
+  bool stream8;       // N > 256 with a short factor: the streamed solve on eight-wave workgroups
+  bool f32_whitened;  // XIVO_HIP_FLAG_FP32_WHITENED applies (the product runs outside the solve kernel because of the SHAPE)
+};
+
+// (B = the filters of this pass; with the batch walked in chunks - XIVO_HIP_CHUNK - the few-filter decision is made on the
+//  WHOLE call's batch, c->call_batch: chunks of <= 64 filters of a large batch must not take the few-filter kernels)
+static UpdatePlan plan_update(const xivo_hip_ctx* c, int b0, int B, bool gate) {
+  const int Np = c->Np, Mp = c->Mp;
+  const unsigned f = c->flags;
+  UpdatePlan p{};
+  bool sparse = !(f & XIVO_HIP_FLAG_DENSE_H);
+  int nc_max = 0, pw_max = 1;
+  for (int b = b0; b < b0 + B; ++b) {
+    sparse = sparse && c->ell_over_h[b] == 0;
+    nc_max = std::max(nc_max, c->ell_nc_h[b]); pw_max = std::max(pw_max, c->ell_pw_h[b]);
+  }
+  const bool extra_rows = c->mixed_row0 >= 0 || c->lead_valid;     // dense OOS rows / the leading calibration block next to the compressed rows
+  // the stand-alone tail's G = T H^T walks compressed rows of ALL of H, and the compact gate of a calibration stacking reads whole rows
+  if (sparse && extra_rows && ((f & XIVO_HIP_FLAG_STANDALONE_TAIL) || (c->lead_valid && gate))) sparse = false;
+  if (sparse && c->lead_valid && (f & XIVO_HIP_FLAG_SYMMETRIC_FORM)) sparse = false;
+  p.sparse = sparse;
+  const bool holds = trsm_forms_T(Mp, Np);                          // one workgroup per filter holds the factor and every column of the state
+  const int Ball = c->call_batch > B ? c->call_batch : B;
+  p.latency = !(f & (XIVO_HIP_FLAG_THROUGHPUT_ROUTE | XIVO_HIP_FLAG_STANDALONE_TAIL | XIVO_HIP_FLAG_SYMMETRIC_FORM)) &&
+              trsm_latency_route(Mp, Ball) && (sparse || !(f & XIVO_HIP_FLAG_DENSE_H));
+  p.stream8 = !p.latency && Np > 256 && Mp / 16 <= 8;               // (N = 276, M = 120: 2.01 -> 1.39 ms per 4096 filters)
+  if (f & XIVO_HIP_FLAG_SYMMETRIC_FORM) { p.route = sparse ? ROUTE_SPARSE_SYMMETRIC : ROUTE_DENSE_SYMMETRIC; p.in_solve = holds; return p; }
+  if (!sparse && (f & XIVO_HIP_FLAG_DENSE_H)) { p.route = ROUTE_DENSE_ASCODED; return p; }
+  if (sparse && (f & XIVO_HIP_FLAG_STANDALONE_TAIL)) { p.route = ROUTE_SPARSE_TAIL; return p; }
+  if (sparse && !extra_rows && !(f & XIVO_HIP_FLAG_MULTI_KERNEL) && nc_max <= 12 && pw_max <= 9 && fused_update_supported(Mp, Np)) {
+    p.route = ROUTE_FUSED; p.latency = false; return p;
+  }
+  p.in_solve = holds && !p.latency;
+  p.f32_whitened = (f & XIVO_HIP_FLAG_FP32_WHITENED) && !holds;
+  p.route = sparse ? (p.in_solve ? ROUTE_SPARSE_IN_SOLVE : ROUTE_SPARSE_WHITENED) : ROUTE_DENSE_WHITENED;
+  return p;
+}
+
+// One pass of the update pipeline over filters [b0, b0 + B).
+struct GateParams { int F; double R, thresh, mult; int min_inliers; };
+
+// The row-pair compressed rows of filters [b0, ...)
+EllBuffers ell_range(const EllBuffers& ell, int b0) {
+  EllBuffers e = ell;
+  e.idx += (long)b0 * e.stride_idx(); e.val += (long)b0 * e.stride_val(); e.nc += b0; e.pw += b0; e.over += b0;
+  return e;
+}
+
+// The context's per-filter buffers from filter b0 on. Each keeps the stride it is allocated with (c->sP, c->sH, ...), except A,
+// which has two views: A (stride sA: G of the whitened / tail forms, the fallback's A) and A_sP (stride sP: A = K H - I of the
+// as-coded dense pipeline).
+struct RangeView {
+  double *P, *H, *HT, *HP, *PHT, *S, *K, *A, *A_sP, *T, *invD, *inn, *diagR, *err, *y, *lead;
+  int *status, *ldlt_used;
+  EllBuffers ell;
+};
+
+RangeView range_view(xivo_hip_ctx* c, int b0) {
+  RangeView v;
+  v.P = c->P + (long)b0 * c->sP; v.H = c->H + (long)b0 * c->sH; v.HT = c->HT + (long)b0 * c->sHT; v.HP = c->HP + (long)b0 * c->sH;
+  v.PHT = c->PHT + (long)b0 * c->sK; v.S = c->S + (long)b0 * c->sS; v.K = c->K + (long)b0 * c->sK;
+  v.A = c->A + (long)b0 * c->sA; v.A_sP = c->A + (long)b0 * c->sP; v.T = c->T + (long)b0 * c->sP;
+  v.invD = c->invD + (long)b0 * c->sInvD; v.inn = c->inn + (long)b0 * c->Mpmax; v.diagR = c->diagR + (long)b0 * c->Mpmax;
+  v.err = c->err + (long)b0 * c->Np; v.y = c->yvec + (long)b0 * c->Mpmax;
+  v.lead = c->Hlead ? c->Hlead + (long)b0 * c->Mpmax * LEAD_K : nullptr;
+  v.status = c->status + b0; v.ldlt_used = c->ldlt_used + b0;
+  v.ell = ell_range(c->ell, b0);
+  return v;
+}
+
+// S = L L^T (chol_f64.hip) over B filters, the gate folded into its prologue when `cg` is given. `flops`: what the calling
+// pipeline counts for the stage.
+int factor_S(xivo_hip_ctx* c, const RangeView& v, int B, int latency, const CholGateArgs* cg, double flops) {
+  const int Mp = c->Mp;
+  CholArgs a{}; a.S = v.S; a.strideS = c->sS; a.lds = c->Mpmax; a.Mp = Mp; a.invD = v.invD; a.strideInvD = c->sInvD;
+  a.status = v.status; a.batch = B; a.latency = latency;
+  char clabel[64]; chol_kernel_label(Mp, B, clabel, sizeof(clabel));
+  if (cg) { const size_t n = strlen(clabel); snprintf(clabel + n, sizeof(clabel) - n, "+gate"); }
+  StageTimer st(c, ST_CHOL, flops, clabel, 8.0 * B * ((double)Mp * (Mp + 1) + Mp / 16 * 512.0));
+  HIP_TRY((hipError_t)launch_chol_f64(a, c->stream, cg));
+  return XIVO_HIP_OK;
+}
+
+// The arguments every launch of the substitution kernels shares: the factor, P H^T in, the gain and dx out. The caller adds
+// what its form needs (the mode, T / Pm / Yout, joseph, fwd_only / y, latency / stream8 / out_f32).
+TrsmArgs trsm_args(const xivo_hip_ctx* c, const RangeView& v, int B) {
+  TrsmArgs a{}; a.LU = v.S; a.strideLU = c->sS; a.ldlu = c->Mpmax; a.invD = v.invD; a.strideInvD = c->sInvD;
+  a.PHT = v.PHT; a.stridePHT = c->sK; a.ldpht = c->Np; a.K = v.K; a.strideK = c->sK; a.ldk = c->Np;
+  a.inn = v.inn; a.strideInn = c->Mpmax; a.err = v.err; a.strideErr = c->Np; a.Mp = c->Mp; a.Np = c->Np; a.batch = B;
+  return a;
+}
+// XIVO_HIP_FLAG_SYMMETRIC_FORM: gain and covariance in the symmetric "square-root" form. With S = L L^T and
+// W = L^-1 (H P) (forward substitution only):  K (H P) = W^T W,  dx = K inn = W^T (L^-1 inn),  P+ = P - W^T W.
+// This is the covariance the Joseph form of src/estimator.cpp:1276-1287 evaluates to for the optimal gain (the Joseph
+// correction term vanishes identically), computed without the backward substitution, the residual G and the second
+// N x N x M product; its rounding error grows with cond(L) = sqrt(cond(S)), not cond(S). Opt-in: the reference codes
+// the Joseph form, which stays the default.
+static int finish_symmetric(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeView& v, int B) {
+  const int Np = c->Np, Mp = c->Mp;
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "fwd_vec_kernel");
+    HIP_TRY((hipError_t)launch_fwd_vec(v.S, c->sS, c->Mpmax, v.invD, c->sInvD, v.inn, c->Mpmax, v.y, c->Mpmax, Mp, B, c->stream));
+  }
+  {
+    TrsmArgs a = trsm_args(c, v, B);
+    a.fwd_only = 1; a.y = v.y; a.strideY = c->Mpmax;
+    // the solve kernel goes on to P+ = P - W^T W in place, W^T still in its registers (blocks exchanged through LDS)
+    const bool p_here = plan.in_solve;
+    if (p_here) { a.T = v.P; a.strideT = c->sP; a.ldt = Np; a.skip_status = v.status; }
+    char label[64]; trsm_kernel_label(Mp, label, sizeof(label), p_here ? 2 : 0);
+    const double outs = 0.5 * Np * (Np + 1.0), Nf = c->N, Mf = c->M;
+    StageTimer st(c, ST_TRSM, (1.0 * Mf * Mf * Nf + (p_here ? Nf * (Nf + 1.0) * Mf : 0.0)) * B, label,
+                  8.0 * B * (0.5 * Mp * (Mp + 1) + Mp / 16 * 512.0 + (p_here ? 1.0 : 2.0) * Np * Mp + (p_here ? outs + (double)Np * Np : 0.0)));
+    HIP_TRY((hipError_t)launch_trsm_f64(a, c->stream));
+    if (p_here) return XIVO_HIP_OK;
+  }
+  // P+ = P - W^T W in place: the accumulators start at -P (every tile reads its part of P before it stores anything)
+  // and the result is negated on the way out
+  GemmExtra x; x.epi = EPI_RSUB_MAT; x.msub = v.P; x.sMsub = c->sP; x.ldmsub = Np; x.lower_only = 1;
+  x.skip = v.status;
+  return gemm(c, ST_PNEW, B, Np, Np, v.K, c->sK, Np, v.K, c->sK, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, v.P, c->sP, Np, x);
+}
+
+// The factorisation, the gain, dx and the covariance update once P H^T and S are formed - shared by the sparse and the dense
+// whitened pipelines (they differ in how H P and S are built, not behind them):
+//   S = L L^T (gate folded into its prologue when `cg` is given)                 estimator.cpp:1266
+//   in_solve : W = L^-1 (HP), K^T = L^-T W, dx, P+ = P - (W - D)^T (W + D) inside the solve kernel  estimator.cpp:1265-1287
+//   else     : V^T, Y^T leave the (chunked / streamed) solve, P+ = P - V^T Y as one tiled symmetric product
+static int finish_whitened(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeView& v, int B, const CholGateArgs* cg) {
+  const int Np = c->Np, Mp = c->Mp;
+  const double Nf = c->N, Mf = c->M;
+  // (the streamed solve reads the mirrored upper triangle)
+  int rc = factor_S(c, v, B, plan.latency || plan.stream8, cg, Mf * Mf * Mf / 3.0 * B);
+  if (rc) return rc;
+  double* G = v.A;
+  {
+    TrsmArgs a = trsm_args(c, v, B);
+    if (plan.in_solve) { a.T = v.P; a.strideT = c->sP; a.ldt = Np; a.joseph = 2; a.skip_status = v.status; }
+    else { a.Yout = G; a.strideY2 = c->sA; a.ldy2 = Np; a.latency = plan.latency; a.stream8 = plan.stream8 ? 1 : 0; a.out_f32 = plan.f32_whitened ? 1 : 0; }
+    char label[64]; trsm_kernel_label(Mp, label, sizeof(label), plan.in_solve ? 4 : 5, plan.latency, plan.stream8);
+    // seven block rows on a narrow state: the ten- / twelve-wave instantiation with W in registers (solve_fused.hip)
+    const bool narrow = plan.in_solve && trsm_narrow_supported(Mp, Np);
+    if (narrow) trsm_narrow_label(Mp, Np, label, sizeof(label));
+    const double t_outs = 0.5 * Np * (Np + 1.0), t_outs_f = 0.5 * Nf * (Nf + 1.0);
+    // algorithmic flops (true N, M): the two triangular solves (M^2 N each), the residual blocks of the whitened form
+    // (2 * 16 * M * N) and, in the solve kernel, the symmetric N x N x M product (lower triangle). Algorithmic bytes: the
+    // factor, P H^T once, P's lower triangle in, P out (the gain is not stored)
+    StageTimer st(c, ST_TRSM, (2.0 * Mf * Mf * Nf + 32.0 * Mf * Nf + (plan.in_solve ? 2.0 * t_outs_f * Mf : 0.0)) * B, label,
+                  8.0 * B * (0.5 * Mp * (Mp + 1) + Mp / 16 * 512.0 + (plan.in_solve ? 1.0 : 3.0) * Np * Mp + (plan.in_solve ? t_outs + (double)Np * Np : 0.0)));
+    HIP_TRY((hipError_t)(narrow ? launch_trsm_narrow(a, c->stream) : launch_trsm_f64(a, c->stream)));
+    if (plan.in_solve) return XIVO_HIP_OK;
+  }
+  // P+ = P - V^T Y in place (V^T in the K buffer, Y^T in the G buffer), lower triangle + mirror
+  GemmExtra x; x.epi = EPI_RSUB_MAT; x.msub = v.P; x.sMsub = c->sP; x.ldmsub = Np; x.lower_only = 1; x.skip = v.status;
+  x.small_tiles = plan.latency;
+  if (plan.f32_whitened) {   // XIVO_HIP_FLAG_FP32_WHITENED: both operands left the solve as float (Y^T at float 0, V^T at float Np Mp of G)
+    x.fp32 = 1; x.a_f32 = 1; x.b_f32 = 1;
+    const double* Vf = reinterpret_cast<const double*>(reinterpret_cast<const float*>(G) + (long)Np * Mp);
+    return gemm(c, ST_PNEW, B, Np, Np, Vf, 2 * c->sA, Np, G, 2 * c->sA, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, v.P, c->sP, Np, x);
+  }
+  return gemm(c, ST_PNEW, B, Np, Np, v.K, c->sK, Np, G, c->sA, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, v.P, c->sP, Np, x);
+}
+
+// Sparse-H pipelines (ell.h): H P, S and T H^T skip the structural zeros of H; the factorisation, the gain and the
+// N x N x M covariance products stay on the MFMA kernels.
+//   FUSED            everything in one kernel per filter                                     fused_update.hip
+//   otherwise        HP = H P (+ P H^T)            ell_mul<HP>                               estimator.cpp:1259
+//                    S = (HP) H^T + R              ell_mul<S>                                estimator.cpp:1259-1263
+//                    [MH gating]                   in the prologue of the factorisation / gate_ell    update.cpp:60-96
+//                    then finish_whitened / finish_symmetric, or (SPARSE_TAIL)
+//                    T = K (HP) - P, G = T H^T + K R, P+ = G K^T - T                          estimator.cpp:1276-1287 re-associated
+static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeView& v, int b0, int B, const GateParams* gate) {
+  const int Np = c->Np, Mp = c->Mp, ldh = c->Mpmax, lds = c->Mpmax;
+  double *P = v.P, *HP = v.HP, *PHT = v.PHT, *S = v.S, *K = v.K, *G = v.A, *T = v.T, *inn = v.inn, *diagR = v.diagR;
+  const EllBuffers& e = v.ell;
+  int nc_max = 0, pw_max = 1;
+  for (int b = b0; b < b0 + B; ++b) { nc_max = std::max(nc_max, c->ell_nc_h[b]); pw_max = std::max(pw_max, c->ell_pw_h[b]); }
+  // algorithmic flops are counted on the TRUE sizes N, M (the padded Np, Mp only size the launches and the bytes)
+  const double Nf = c->N, Mf = c->M;
+  const double nnz_flops = 2.0 * Mf * 21.0;   // per contiguous-index value: 21 structural non-zeros per row
+  int rc;
+  if (plan.route == ROUTE_FUSED) {
+    // Round 6: the shapes a CU holds (TUM-VI 203 / 60, BASELINE config 2 150 / 100) take ONE kernel for the whole update -
+    // P H^T, S, the gate, the factor, both substitutions and the covariance product stay in the registers and the LDS of the
+    // workgroup that owns the filter; nothing but P, P+ and the compressed rows crosses HBM.
+    FusedArgs a{};
+    a.P = P; a.strideP = c->sP; a.ldp = Np; a.ell = e; a.inn = inn; a.strideInn = c->Mpmax; a.diagR = diagR; a.strideR = c->Mpmax;
+    a.err = v.err; a.strideErr = Np; a.PHT = PHT; a.stridePHT = c->sK; a.ldpht = Np; a.status = v.status;
+    a.Np = Np; a.Mp = Mp; a.batch = B; a.pw = pw_max;
+    if (gate) {
+      a.gate = 1; a.F = gate->F; a.R = gate->R; a.thresh = gate->thresh; a.mult = gate->mult; a.min_inliers = gate->min_inliers;
+      a.mask = c->mask + (long)b0 * gate->F; a.dist = c->dist + (long)b0 * gate->F;
+      if (c->dense_valid) { a.H = v.H; a.strideH = c->sH; a.ldh = ldh; a.HT = v.HT; a.strideHT = c->sHT; a.ldht = Np; }
+      c->gate_sparse_last = 0;
+    }
+    char label[64]; fused_update_label(Mp, Np, pw_max, label, sizeof(label));
+    const double t_outs_f = 0.5 * Nf * (Nf + 1.0);
+    StageTimer st(c, ST_TRSM, (nnz_flops * (Nf + Mf) + Mf * Mf * Mf / 3.0 + 2.0 * Mf * Mf * Nf + 32.0 * Mf * Nf + 2.0 * t_outs_f * Mf) * B, label,
+                  B * (16.0 * Np * Np + (Mp / 2) * ELL_W * 20.0));
+    HIP_TRY((hipError_t)launch_fused_update(a, c->stream));
+    return XIVO_HIP_OK;
+  }
+  // mixed stacking: rows [0, mr0) of H are the compressed in-state rows, rows [mr0, M) the dense OOS rows appended by
+  // xivo_hip_oos_project (non-zero over the extrinsics + group columns only: src/oos.cpp:74-88). The in-state rows keep the
+  // sparse walk below; the OOS block goes through two small MFMA products (rows padded to 16 from mr0 on).
+  const int mr0 = c->mixed_row0;
+  const int Mp_ell = mr0 >= 0 ? round_up16(mr0) : Mp;
+  const int oos_pad = mr0 >= 0 ? round_up16(Mp - mr0) : 0;
+  // the OOS rows are zero beyond the extrinsics and group columns (the mode clears and writes nothing else there): the two
+  // products of the OOS block contract over the leading oos_k state columns only
+  bool walk_tiled = false;
+  const int oos_k = (mr0 >= 0 && c->have_layout) ? std::min(Np, round_up16(c->lay.group_begin + 6 * c->lay.n_groups)) : Np;
+  {
+    EllMulArgs a{}; a.ell = e; a.Src = P; a.strideSrc = c->sP; a.ldsrc = Np; a.out = PHT; a.strideOut = c->sK; a.ldo = Np;
+    a.out2 = HP; a.strideOut2 = c->sH; a.ldo2 = ldh; a.X = Np; a.Mp = Mp_ell; a.batch = B; a.nc_max = nc_max; a.pw_max = pw_max; a.cols = Np;
+    char label[64]; ell_kernel_label(ELL_HP, a, label, sizeof(label));
+    walk_tiled = ell_uses_slab_form(a);   // (the same decision for ell<S> below: it depends on the shape and slot counts only)
+    StageTimer st(c, ST_HP, nnz_flops * Nf * B, label, 8.0 * B * ((double)Np * Np + (double)Np * Mp));
+    HIP_TRY((hipError_t)launch_ell_mul(ELL_HP, a, c->stream));
+  }
+  if (mr0 >= 0) {   // (H P)_oos = H_oos P, with its transpose into the P H^T columns behind the in-state ones
+    const double* Hd = v.H + mr0;
+    GemmExtra x; x.C2 = PHT + (long)mr0 * Np; x.sC2 = c->sK; x.ldc2 = Np;
+    rc = gemm(c, ST_HP, B, oos_pad, Np, Hd, c->sH, ldh, P, c->sP, Np, oos_k, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, HP + mr0, c->sH, ldh, x);
+    if (rc) return rc;
+  }
+  // online-calibration stacking on the sparse pipeline: the calibration columns of H live in the leading dense block
+  // L [Mp x LEAD_K] (stack_kernel): P H^T += P[:, 0:LEAD_K] L^T on the MFMA product
+  const bool lead = c->lead_valid && mr0 < 0;
+  const double* Ld = lead ? v.lead : nullptr;
+  const long sLd = (long)c->Mpmax * LEAD_K;
+  const int ldl = c->Mpmax;   // (stack_kernel lays the block out on the allocated row count)
+  if (lead) {
+    // (the tiled walk writes P H^T only: this product completes it in place and leaves H P as its transposed copy - the
+    //  leading LEAD_K columns the S product below reads, or all of it where ell<S> takes the gather form, which reads H P)
+    GemmExtra x; x.epi = EPI_ADD_MAT; x.msub = PHT; x.sMsub = c->sK; x.ldmsub = Np; x.C2 = HP; x.sC2 = c->sH; x.ldc2 = ldh;
+    x.c2_rows = walk_tiled ? LEAD_K : 0;
+    rc = gemm(c, ST_HP, B, Np, Mp, P, c->sP, Np, Ld, sLd, ldl, LEAD_K, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, PHT, c->sK, Np, x);
+    if (rc) return rc;
+  }
+  GateEllArgs ga{};
+  if (gate) {
+    ga.ell = e;
+    ga.H = c->dense_valid ? v.H : nullptr; ga.strideH = c->sH; ga.ldh = ldh;
+    ga.HT = c->dense_valid ? v.HT : nullptr; ga.strideHT = c->sHT; ga.ldht = Np; ga.PHT = PHT;
+    ga.HP = nullptr;   // H P [Mp x Np] has no reader behind this point (S is formed already, the solve reads P H^T)
+    ga.inn = inn; ga.strideInn = c->Mpmax; ga.diagR = diagR; ga.strideR = c->Mpmax;
+    ga.mask = c->mask + (long)b0 * gate->F; ga.dist = c->dist + (long)b0 * gate->F;
+    ga.F = gate->F; ga.Np = Np; ga.batch = B;
+    ga.S = S; ga.strideS = c->sS; ga.lds = lds; ga.Mp = Mp; ga.from_S = 1;   // distances from the diagonal blocks of S
+    ga.R = gate->R; ga.thresh = gate->thresh; ga.mult = gate->mult; ga.min_inliers = gate->min_inliers;
+  }
+  int diag_done = 0;
+  {
+    EllMulArgs a{}; a.ell = e; a.Src = PHT; a.strideSrc = c->sK; a.ldsrc = Np; a.SrcAlt = HP; a.strideSrcAlt = c->sH; a.ldsrcAlt = ldh;
+    a.out = S; a.strideOut = c->sS; a.ldo = lds; a.cols = Np;
+    a.diagR = diagR; a.strideR = c->Mpmax; a.X = Mp; a.Mp = Mp_ell; a.batch = B; a.nc_max = nc_max; a.pw_max = pw_max;
+    // the 2 x 2 diagonal blocks of S once more, compact (the T buffer is free until the solve): what the gate reads
+    if (gate && mr0 < 0 && !lead && (long)2 * Mp <= c->sP) { a.diag_out = T; a.strideDiag = c->sP; a.diag_done = &diag_done; }
+    char label[64]; ell_kernel_label(ELL_S, a, label, sizeof(label));
+    StageTimer st(c, ST_S, nnz_flops * Mf * B, label, 8.0 * B * ((double)Np * Mp + (double)Mp * Mp));
+    HIP_TRY((hipError_t)launch_ell_mul(ELL_S, a, c->stream));
+  }
+  if (mr0 >= 0) {   // the OOS x OOS block of S (the OOS x in-state block came out of the walk above: rows of S run over all M)
+    const double* Hd = v.H + mr0;
+    GemmExtra x; x.epi = EPI_ADD_DIAG; x.diag = diagR + mr0; x.sDiag = c->Mpmax; x.lower_only = 1;
+    rc = gemm(c, ST_S, B, oos_pad, oos_pad, HP + mr0, c->sH, ldh, Hd, c->sH, ldh, oos_k, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0,
+              S + mr0 + (long)mr0 * lds, c->sS, lds, x);
+    if (rc) return rc;
+  }
+  if (lead) {
+    // S += (H P)[:, 0:LEAD_K] L^T. The walk above left, in the lower triangle, S[i, j] = sum over the COMPRESSED columns k of
+    // row j of (H P)[i, k] H[j, k] with the complete H P: what is missing is the same sum over row j's calibration columns
+    // (the order of the operands matters - L (H P)^T is the transpose, and neither term is symmetric on its own)
+    GemmExtra x; x.epi = EPI_ADD_MAT; x.msub = S; x.sMsub = c->sS; x.ldmsub = lds; x.lower_only = 1;
+    rc = gemm(c, ST_S, B, Mp, Mp, HP, c->sH, ldh, Ld, sLd, ldl, LEAD_K, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, S, c->sS, lds, x);
+    if (rc) return rc;
+  }
+  if (gate) c->gate_sparse_last = 0;
+  // With thousands of factors the gate rides in the prologue of the factorisation (chol_f64.hip, GATE): the distances come
+  // from the compact diagonal blocks ell<S> just left, the rejected pairs are decoupled where the factor loads S - no gate
+  // launch, no extra pass over S. (Few filters, dense copies of H alive, mixed stacking: the gate kernel.)
+  CholGateArgs cg{};
+  bool gate_folded = false;
+  if (gate) {
+    if (diag_done) { ga.Sdiag = T; ga.strideSdiag = c->sP; }
+    gate_folded = diag_done && !c->dense_valid && mr0 < 0 && !plan.latency && chol_gate_supported(Mp, B);
+    if (gate_folded) {
+      cg.Sdiag = ga.Sdiag; cg.strideSdiag = ga.strideSdiag; cg.inn = inn; cg.strideInn = c->Mpmax; cg.diagR = diagR; cg.strideR = c->Mpmax;
+      cg.ellval = e.val; cg.strideVal = e.stride_val(); cg.ell_w = ELL_W; cg.PHT = PHT; cg.stridePHT = c->sK; cg.ldpht = Np; cg.Np = Np;
+      cg.mask = ga.mask; cg.dist = ga.dist; cg.F = gate->F; cg.R = gate->R; cg.thresh = gate->thresh; cg.mult = gate->mult;
+      cg.min_inliers = gate->min_inliers;
+    } else {
+      StageTimer st(c, ST_GATE, 0.0, "gate_ell_kernel");
+      HIP_TRY((hipError_t)launch_gate_ell(ga, c->stream));
+    }
+  }
+  if (plan.route != ROUTE_SPARSE_TAIL && plan.route != ROUTE_SPARSE_SYMMETRIC)
+    return finish_whitened(c, plan, v, B, gate_folded ? &cg : nullptr);
+  rc = factor_S(c, v, B, 0, gate_folded ? &cg : nullptr, Mf * Mf * Mf / 3.0 * B);
+  if (rc) return rc;
+  if (plan.route == ROUTE_SPARSE_SYMMETRIC) return finish_symmetric(c, plan, v, B);
+  // ---- SPARSE_TAIL (XIVO_HIP_FLAG_STANDALONE_TAIL): K^T = S^-1 (HP), dx; T = K (HP) - P; G = T H^T + K R; P+ = G K^T - T
+  const bool t_here = trsm_forms_T(Mp, Np);      // the solve forms T on the gain still in its registers
+  {
+    TrsmArgs a = trsm_args(c, v, B);
+    if (t_here) { a.T = T; a.strideT = c->sP; a.ldt = Np; a.Pm = P; a.stridePm = c->sP; a.ldpm = Np; }
+    char label[64]; trsm_kernel_label(Mp, label, sizeof(label), t_here ? 1 : 0);
+    const double t_outs = 0.5 * Np * (Np + 1.0), t_outs_f = 0.5 * Nf * (Nf + 1.0);
+    StageTimer st(c, ST_TRSM, (2.0 * Mf * Mf * Nf + (t_here ? 2.0 * t_outs_f * Mf : 0.0)) * B, label,
+                  8.0 * B * (0.5 * Mp * (Mp + 1) + Mp / 16 * 512.0 + 2.0 * Np * Mp + (t_here ? t_outs + (double)Np * Np : 0.0)));
+    HIP_TRY((hipError_t)launch_trsm_f64(a, c->stream));
+  }
+  if (!t_here) {  // T = K (HP) - P = (HP)^T S^-1 (HP) - P: symmetric up to the rounding of the solve, so the lower
+                  // triangle is computed and mirrored
+    GemmExtra x; x.epi = EPI_SUB_MAT; x.msub = P; x.sMsub = c->sP; x.ldmsub = Np; x.lower_only = 1;
+    rc = gemm(c, ST_AP, B, Np, Np, K, c->sK, Np, PHT, c->sK, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, T, c->sP, Np, x);
+    if (rc) return rc;
+  }
+  {  // G = T H^T + K diag(R)   [Np x Mp, in the A buffer]
+    EllMulArgs a{}; a.ell = e; a.Src = T; a.strideSrc = c->sP; a.ldsrc = Np; a.out = G; a.strideOut = c->sA; a.ldo = Np;
+    a.diagR = diagR; a.strideR = c->Mpmax; a.K = K; a.strideK = c->sK; a.ldk = Np; a.X = Np; a.Mp = Mp; a.batch = B; a.nc_max = nc_max; a.pw_max = pw_max; a.cols = Np;
+    char label[64]; ell_kernel_label(ELL_G, a, label, sizeof(label));
+    StageTimer st(c, ST_KH, nnz_flops * Np * B, label, 8.0 * B * ((double)Np * Np + 2.0 * Np * Mp));
+    HIP_TRY((hipError_t)launch_ell_mul(ELL_G, a, c->stream));
+  }
+  if (pnew_reg_supported(Mp, Np)) {
+    // P+ = G K^T - T, all fp64: rows of G in registers, blocks of K through LDS, one workgroup per filter
+    PnewRegArgs a{}; a.G = G; a.strideG = c->sA; a.ldg = Np; a.K = K; a.strideK = c->sK; a.ldk = Np;
+    a.T = T; a.strideT = c->sP; a.ldt = Np; a.P = P; a.strideP = c->sP; a.ldp = Np;
+    a.skip_status = v.status; a.Mp = Mp; a.Np = Np; a.batch = B;
+    char label[64]; pnew_reg_kernel_label(Mp, label, sizeof(label));
+    const double outs = 0.5 * Np * (Np + 1.0);
+    StageTimer st(c, ST_PNEW, 2.0 * outs * Mp * B, label, 8.0 * B * (2.0 * Np * Mp + outs + (double)Np * Np));
+    HIP_TRY((hipError_t)launch_pnew_reg_f64(a, c->stream));
+    return XIVO_HIP_OK;
+  }
+  // P+ = G K^T - T   (lower triangle + mirror)
+  GemmExtra x; x.epi = EPI_SUB_MAT; x.msub = T; x.sMsub = c->sP; x.ldmsub = Np; x.lower_only = 1;
+  x.skip = v.status;   // S not positive definite: P of that filter stays the prior (reported through xivo_hip_get_status)
+  return gemm(c, ST_PNEW, B, Np, Np, G, c->sA, Np, K, c->sK, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, P, c->sP, Np, x);
+}
+
+static int update_dense_range(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeView& v, int b0, int B, const GateParams* gate) {
+  const int Np = c->Np, Mp = c->Mp, ldh = c->Mpmax, lds = c->Mpmax;
+  const double *H = v.H, *HT = v.HT, *inn = v.inn, *diagR = v.diagR;
+  double *P = v.P, *HP = v.HP, *PHT = v.PHT, *S = v.S, *K = v.K, *A = v.A_sP, *T = v.T;
+  int rc = ensure_dense(c);   // (mixed stacking / a leading block: the in-state rows are rebuilt densely next to the rows already in place)
+  if (rc) return rc;
+  {  // HP = H * P and its transpose PH^T (estimator.cpp:1259 first product; P symmetric => B operand = P rows)
+    GemmExtra x; x.C2 = PHT; x.sC2 = c->sK; x.ldc2 = Np;
+    rc = gemm(c, ST_HP, B, Mp, Np, H, c->sH, ldh, P, c->sP, Np, Np, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0,
+              HP, c->sH, ldh, x);
+    if (rc) return rc;
+  }
+  if (gate) {  // Estimator::MHGating on the rows just multiplied (update.cpp:60-96): S_f = (HP)_f H_f^T + R
+    rc = ensure_HT(c);   // the gate reads (and neutralises) the transposed rows
+    if (rc) return rc;
+    GateDenseArgs a{};
+    a.H = H; a.strideH = c->sH; a.ldh = ldh; a.HP = HP; a.strideHP = c->sH; a.ldhp = ldh;
+    a.Hw = v.H; a.HTw = v.HT; a.strideHT = c->sHT; a.ldht = Np;
+    a.HPw = HP; a.PHTw = PHT; a.PHTr = PHT;
+    a.inn = v.inn; a.strideInn = c->Mpmax; a.diagR = v.diagR;
+    a.strideR = c->Mpmax; a.mask = c->mask + (long)b0 * gate->F; a.dist = c->dist + (long)b0 * gate->F;
+    a.F = gate->F; a.Np = Np; a.batch = B;
+    a.R = gate->R; a.thresh = gate->thresh; a.mult = gate->mult; a.min_inliers = gate->min_inliers;
+    a.ell = c->ell; a.have_ell = 0;
+    StageTimer st(c, ST_GATE, 0.0, "gate_dense_kernel");
+    c->gate_sparse_last = 0;
+    HIP_TRY((hipError_t)launch_gate_dense(a, c->stream));
+  }
+  {  // S = HP * H^T + diag(R)  (estimator.cpp:1259-1263); lower triangle + mirror
+    GemmExtra x; x.epi = EPI_ADD_DIAG; x.diag = diagR; x.sDiag = c->Mpmax; x.lower_only = 1;
+    rc = gemm(c, ST_S, B, Mp, Mp, HP, c->sH, ldh, H, c->sH, ldh, Np, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0,
+              S, c->sS, lds, x);
+    if (rc) return rc;
+  }
+  if (plan.route == ROUTE_DENSE_WHITENED)      // an H without XIVO's row structure: everything behind S as on the sparse pipeline
+    return finish_whitened(c, plan, v, B, nullptr);
+  rc = factor_S(c, v, B, 0, nullptr, (double)Mp * Mp * Mp / 3.0 * B);   // S = L L^T (flops counted on the padded size)
+  if (rc) return rc;
+  if (plan.route == ROUTE_DENSE_SYMMETRIC) return finish_symmetric(c, plan, v, B);
+  // ---- DENSE_ASCODED (XIVO_HIP_FLAG_DENSE_H): the products of estimator.cpp:1265-1287 as they are written
+  {  // K^T = S^-1 HP ; dx = K inn  (estimator.cpp:1265-1267)
+    TrsmArgs a = trsm_args(c, v, B);
+    char label[64]; trsm_kernel_label(Mp, label, sizeof(label), 0);
+    StageTimer st(c, ST_TRSM, 2.0 * Mp * Mp * Np * B, label, 8.0 * B * (0.5 * Mp * (Mp + 1) + Mp / 16 * 512.0 + 2.0 * Np * Mp));
+    HIP_TRY((hipError_t)launch_trsm_f64(a, c->stream));
+  }
+  rc = ensure_HT(c);
+  if (rc) return rc;
+  {  // A = K * H - I  (estimator.cpp:1276-1279)
+    GemmExtra x; x.epi = EPI_SUB_IDENT;
+    rc = gemm(c, ST_KH, B, Np, Np, K, c->sK, Np, HT, c->sHT, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0,
+              A, c->sP, Np, x);
+    if (rc) return rc;
+  }
+  {  // T = A * P = K * (HP) - P  (estimator.cpp:1280, left product; distributes over the already
+     // formed HP, 2MN^2 instead of 2N^3 flops, same value up to rounding)
+    GemmExtra x; x.epi = EPI_SUB_MAT; x.msub = P; x.sMsub = c->sP; x.ldmsub = Np;
+    rc = gemm(c, ST_AP, B, Np, Np, K, c->sK, Np, PHT, c->sK, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0,
+              T, c->sP, Np, x);
+    if (rc) return rc;
+  }
+  {  // P = T * A^T + K diag(R) K^T  (estimator.cpp:1280-1287, fused; lower triangle + mirror)
+    GemmExtra x; x.lower_only = 1;
+    x.skip = v.status;
+    rc = gemm(c, ST_PNEW, B, Np, Np, T, c->sP, Np, A, c->sP, Np, Np, K, c->sK, Np, K, c->sK, Np, Mp, diagR,
+              c->Mpmax, P, c->sP, Np, x);
+  }
+  return rc;
+}
+
+// One pass of the update over filters [b0, b0 + B), then the device answer to a filter whose S the un-pivoted Cholesky
+// could not factor: Eigen's diagonally pivoted L D L^T (what src/estimator.cpp:1266 runs for EVERY filter) and the
+// as-coded Joseph update, on exactly those filters (ldlt_fallback.hip). Every pipeline leaves the covariance of such a
+// filter untouched and its status set, so the fallback starts from the prior.
+static int update_joseph_range(xivo_hip_ctx* c, int b0, int B, const GateParams* gate = nullptr) {
+  const RangeView v = range_view(c, b0);
+  const UpdatePlan plan = plan_update(c, b0, B, gate != nullptr);
+  c->last_path = plan.sparse ? 1 : 0;
+  c->last_route = plan.route;
+  int rc = plan.sparse ? update_sparse_range(c, plan, v, b0, B, gate) : update_dense_range(c, plan, v, b0, B, gate);
+  if (rc || (c->flags & XIVO_HIP_FLAG_NO_LDLT_FALLBACK)) {   // no fallback launch: clear the flags of this call here
+    HIP_TRY(hipMemsetAsync(v.ldlt_used, 0, (size_t)B * sizeof(int), c->stream));
+    return rc;
+  }
+  // (the fallback kernel writes ldlt_used of EVERY filter of the range: 0 where the Cholesky succeeded, 1 where it stepped in)
+  LdltFallbackArgs a{};
+  a.status = v.status; a.used = v.ldlt_used; a.ell = v.ell;
+  a.H = v.H; a.strideH = c->sH; a.ldh = c->Mpmax; a.use_dense = c->last_path == 0 ? 1 : 0;
+  a.mixed_row0 = c->last_path == 1 ? c->mixed_row0 : -1;
+  if (c->last_path == 1 && c->lead_valid) { a.lead = v.lead; a.strideLead = (long)c->Mpmax * LEAD_K; a.ldlead = c->Mpmax; a.lead_k = LEAD_K; }
+  a.PHT = v.PHT; a.stridePHT = c->sK; a.ldpht = c->Np;
+  a.S = v.S; a.strideS = c->sS; a.lds = c->Mpmax;
+  a.K = v.K; a.strideK = c->sK; a.ldk = c->Np;
+  a.A = v.A; a.strideA = c->sA; a.lda = c->Np;
+  a.T = v.T; a.strideT = c->sP; a.ldt = c->Np;
+  a.P = v.P; a.strideP = c->sP; a.ldp = c->Np;
+  a.inn = v.inn; a.strideInn = c->Mpmax; a.diagR = v.diagR; a.strideR = c->Mpmax;
+  a.err = v.err; a.strideErr = c->Np;
+  a.N = c->N; a.M = c->M; a.batch = B;
+  StageTimer st(c, ST_OTHER, 0.0, "ldlt_fallback_kernel");
+  HIP_TRY((hipError_t)launch_ldlt_fallback(a, c->stream));
+  return XIVO_HIP_OK;
+}
+
+// Filters are independent, so the batch is walked in chunks (XIVO_HIP_CHUNK) whose intermediates (HP, PH^T, S, K, A, T:
+// ~2.7 MB per filter at N=250/M=160) stay resident in the 256 MiB Infinity Cache between consecutive kernels instead of
+// round-tripping HBM.
+static int update_chunks(xivo_hip_ctx* c, int B, const GateParams* gate) {
+  const int chunk = c->chunk > 0 ? c->chunk : B;
+  c->call_batch = chunk < B ? B : 0;
+  for (int b0 = 0; b0 < B; b0 += chunk) {
+    const int nb = B - b0 < chunk ? B - b0 : chunk;
+    int rc = update_joseph_range(c, b0, nb, gate);
+    if (rc) { c->call_batch = 0; return rc; }
+  }
+  c->call_batch = 0;
+  return XIVO_HIP_OK;
+}
+
+// ------------------------------------------------------------------ one-filter plumbing call
+// Estimator::UpdateJosephForm() as the reference calls it (src/update.cpp:141, :332): members in host memory in, members in
+// host memory out, ONE call, ONE host synchronisation. See include/xivo_hip.h.
+// Row-pair compression of ONE dense H_ on the host: the arithmetic-free format conversion meas_compress_kernel does for a
+// batch (ell_kernels.hip - same lists, same common-column rule, same slot order, so the rows are those the device would have
+// built, bit for bit), done while the matrix is staged: the host has to touch every byte of H_ once anyway, and the
+// compressed rows are 1/7 of it. Returns over (1: the rows do not fit the compressed form).
+static int host_compress(xivo_hip_ctx::HostCompressScratch& sc, const double* H, int ldh, int M, int N, int pairs_clear, int* idx,
+                         double* val, int* nc_out, int* pw_out) {
+  const int pairs = (M + 1) / 2;
+  sc.cnt.assign(pairs_clear, 0); sc.occ.assign(N, 0); sc.cslot.assign(N, 0);
+  sc.n.resize((size_t)pairs_clear * ELL_W); sc.v.resize((size_t)pairs_clear * ELL_W * 2);
+  int* cnt = sc.cnt.data(); int* occ = sc.occ.data(); int* cslot = sc.cslot.data();
+  int* ln = sc.n.data(); double* lv = sc.v.data();
+  const int Me = M & ~1;                            // rows covered by complete pairs
+  for (int n = 0; n < N; ++n) {
+    const double* col = H + (size_t)n * ldh;
+    const uint64_t* cb = reinterpret_cast<const uint64_t*>(col);
+    int m = 0;
+    for (; m + 8 <= Me; m += 8) {                   // four pairs at a time: all-zero runs (most of H_) cost one test
+      const uint64_t any = cb[m] | cb[m + 1] | cb[m + 2] | cb[m + 3] | cb[m + 4] | cb[m + 5] | cb[m + 6] | cb[m + 7];
+      if ((any << 1) == 0) continue;                // +0.0 / -0.0 only
+      for (int q = m; q < m + 8; q += 2) {
+        const double v0 = col[q], v1 = col[q + 1];
+        if (v0 != 0.0 || v1 != 0.0) {
+          const int p = q >> 1;
+          if (cnt[p] < ELL_W) { ln[p * ELL_W + cnt[p]] = n; lv[2 * (p * ELL_W + cnt[p])] = v0; lv[2 * (p * ELL_W + cnt[p]) + 1] = v1; }
+          ++cnt[p]; ++occ[n];
+        }
+      }
+    }
+    for (; m < M; m += 2) {
+      const double v0 = col[m], v1 = m + 1 < M ? col[m + 1] : 0.0;
+      if (v0 != 0.0 || v1 != 0.0) {
+        const int p = m >> 1;
+        if (cnt[p] < ELL_W) { ln[p * ELL_W + cnt[p]] = n; lv[2 * (p * ELL_W + cnt[p])] = v0; lv[2 * (p * ELL_W + cnt[p]) + 1] = v1; }
+        ++cnt[p]; ++occ[n];
+      }
+    }
+  }
+  int ne = 0;
+  for (int p = 0; p < pairs; ++p) ne += cnt[p] > 0;
+  int ccols[ELL_CW] = {0};
+  int flagged = 0;
+  for (int n = 0; n < N; ++n) {                     // columns used by more than half of the non-empty pairs, ascending
+    if (ne > 0 && 2 * occ[n] > ne) {
+      if (flagged < ELL_CW) { cslot[n] = flagged + 1; ccols[flagged] = n; }
+      ++flagged;
+    }
+  }
+  const int nc = flagged < ELL_CW ? flagged : ELL_CW;
+  int pw = 0, over = 0;
+  for (int p = 0; p < pairs_clear; ++p) {
+    int* pi = idx + (size_t)p * ELL_W;
+    double* pv = val + (size_t)p * ELL_W * 2;
+    for (int t = 0; t < ELL_W; ++t) { pi[t] = t < nc ? ccols[t] : 0; pv[2 * t] = 0.0; pv[2 * t + 1] = 0.0; }
+    int pos = 0;
+    const int walk = cnt[p] < ELL_W ? cnt[p] : ELL_W;
+    for (int k = 0; k < walk; ++k) {
+      const int n = ln[p * ELL_W + k];
+      const double v0 = lv[2 * (p * ELL_W + k)], v1 = lv[2 * (p * ELL_W + k) + 1];
+      const int cs = cslot[n];
+      if (cs) { pv[2 * (cs - 1)] = v0; pv[2 * (cs - 1) + 1] = v1; }
+      else {
+        if (pos < ELL_PW) { pi[ELL_CW + pos] = n; pv[2 * (ELL_CW + pos)] = v0; pv[2 * (ELL_CW + pos) + 1] = v1; }
+        ++pos;
+      }
+    }
+    if (cnt[p] > ELL_W) pos = ELL_PW + 1;           // more than 28 non-zero columns cannot fit
+    if (pos > ELL_PW) over = 1;
+    if (pos > pw) pw = pos;
+  }
+  *nc_out = nc; *pw_out = pw;
+  return over;
+}
+
+}  // namespace
+
+namespace xivo_hip::capi {
+
+// Hand-over of dense measurements that already live in device memory (dH: M x N column-major per filter): ONE
+// launch builds the row-pair compressed rows of the whole range; the padded dense copies are written only for
+// the filters that do not fit it (they take the dense pipeline) and otherwise rebuilt from the compressed rows
+// on demand (ensure_dense).
+int stage_measurements(xivo_hip_ctx* c, int b0, int nb, int M, const double* dH, long strideH, int ldh,
+                       const double* dInn, long strideInn, const double* dR, long strideR) {
+  const int N = c->N;
+  MeasBuffers mb = meas_buffers(c);
+  mb.H += (long)b0 * mb.strideH; mb.HT += (long)b0 * mb.strideHT;
+  mb.inn += (long)b0 * mb.strideInn; mb.diagR += (long)b0 * mb.strideR;
+  c->M = M; c->Mp = round_up16(M);
+  const EllBuffers e = ell_range(c->ell, b0);
+  c->lead_valid = false;
+  // (XIVO_HIP_NO_COMPRESS: test hook for the branch very wide states take - the shape limit itself is N > ~2800 at M = 384)
+  static const bool no_compress = getenv("XIVO_HIP_NO_COMPRESS") != nullptr;
+  if (!meas_compress_fits(c->Mpmax, c->Np) || no_compress) {
+    // the compression kernel's LDS lists do not fit this shape: every filter keeps its dense rows and takes the dense pipeline
+    StageTimer st(c, ST_STACK, 0.0, "unpack_meas_kernel", 8.0 * nb * (3.0 * M * N + 4.0 * M));
+    HIP_TRY((hipError_t)launch_meas_vectors(dInn, strideInn, dR, strideR, M, c->Mpmax, e, mb.inn, mb.strideInn, mb.diagR, mb.strideR, nb, c->stream));
+    HIP_TRY((hipError_t)launch_unpack_meas(dH, strideH, ldh, nullptr, mb, M, c->Mpmax, N, c->Np, nb, c->stream));
+    for (int b = b0; b < b0 + nb; ++b) { c->ell_over_h[b] = 1; c->ell_nc_h[b] = ELL_CW; c->ell_pw_h[b] = ELL_PW + 1; }
+    c->dense_valid = true; c->dense_from_ell = true; c->ht_valid = true; c->mixed_row0 = -1; c->h_clean = false;
+    return XIVO_HIP_OK;
+  }
+  {
+    StageTimer st(c, ST_STACK, 0.0, "meas_compress_kernel", 8.0 * nb * ((double)M * N + 4.0 * M) + (double)nb * c->ell.pairs_max * ELL_W * 20.0);
+    // clear up to the allocated row count so stale rows of a previous, larger M vanish
+    HIP_TRY((hipError_t)launch_meas_compress(dH, strideH, ldh, dInn, strideInn, dR, strideR, M, N, c->Np, c->Mpmax, e, mb.inn,
+                                             mb.strideInn, mb.diagR, mb.strideR, nb, c->stream,
+                                             c->ell_flags_d ? c->ell_flags_d + 3 * (long)b0 : nullptr));
+  }
+  if (c->ell_flags_h) {
+    HIP_TRY(hipStreamSynchronize(c->stream));     // kernel end = system-scope release: the mirrored flags are in host memory
+    const int* f = c->ell_flags_h + 3 * (long)b0;
+    for (int b = 0; b < nb; ++b) { c->ell_over_h[b0 + b] = f[3 * b]; c->ell_nc_h[b0 + b] = f[3 * b + 1]; c->ell_pw_h[b0 + b] = f[3 * b + 2]; }
+  } else {
+    HIP_TRY(hipMemcpyAsync(c->ell_over_h.data() + b0, e.over, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ell_nc_h.data() + b0, e.nc, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ell_pw_h.data() + b0, e.pw, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  bool any_over = false;
+  for (int b = b0; b < b0 + nb && !any_over; ++b) any_over = c->ell_over_h[b] != 0;
+  if (debug_on()) fprintf(stderr, "xivo_hip: hand-over b0=%d nb=%d M=%d any_over=%d nc0=%d pw0=%d\n", b0, nb, M, (int)any_over, c->ell_nc_h[b0], c->ell_pw_h[b0]);
+  if (any_over) HIP_TRY((hipError_t)launch_unpack_meas(dH, strideH, ldh, e.over, mb, M, c->Mpmax, N, c->Np, nb, c->stream));
+  c->dense_valid = false; c->dense_from_ell = true; c->ht_valid = true;   // (ensure_dense rebuilds H and H^T together)
+  c->mixed_row0 = -1; if (any_over) c->h_clean = false;
+  return XIVO_HIP_OK;
+}
+
+}  // namespace xivo_hip::capi
+
+extern "C" {
+
+int xivo_hip_set_measurements(xivo_hip_ctx* c, int b0, int nb, int M, const double* H, long strideH, int ldh,
+                              const double* inn, long strideInn, const double* diagR, long strideR) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !H || !inn || !diagR || M <= 0 || M > c->Mmax || ldh < M) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  const int N = c->N;
+  const size_t per = (size_t)M * N + 2 * (size_t)M;
+  int rc = ensure_staging(c, (size_t)nb * per);
+  if (rc) return rc;
+  double* sH = c->staging;
+  double* sInn = sH + (size_t)nb * M * N;
+  double* sR = sInn + (size_t)nb * M;
+  rc = h2d_packed(c, sH, H, nb, M, N, strideH, ldh);
+  if (rc) return rc;
+  rc = h2d_packed(c, sInn, inn, nb, M, 1, strideInn, M);
+  if (rc) return rc;
+  rc = h2d_packed(c, sR, diagR, nb, M, 1, strideR, M);
+  if (rc) return rc;
+  rc = stage_measurements(c, b0, nb, M, sH, (long)M * N, M, sInn, M, sR, M);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));   // host buffers are only borrowed for the call
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_set_measurements_device(xivo_hip_ctx* c, int b0, int nb, int M, const double* dH, long strideH, int ldh,
+                                     const double* dInn, long strideInn, const double* dR, long strideR) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !dH || !dInn || !dR || M <= 0 || M > c->Mmax || ldh < M || strideH < 0) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  return stage_measurements(c, b0, nb, M, dH, strideH, ldh, dInn, strideInn, dR, strideR);
+}
+
+int xivo_hip_update_joseph(xivo_hip_ctx* c, int B) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || B <= 0 || B > c->Bmax || c->Mp <= 0) return XIVO_HIP_ERR_INVALID;
+  return update_chunks(c, B, nullptr);
+}
+
+int xivo_hip_update_dense_gated(xivo_hip_ctx* c, int B, int F, double R, double mh_thresh, double mh_mult,
+                                int min_inliers) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || B <= 0 || B > c->Bmax || c->Mp <= 0 || F <= 0 || 2 * F > c->M) return XIVO_HIP_ERR_INVALID;
+  int rc = ensure_gate_buffers(c, F);
+  if (rc) return rc;
+  GateParams gp{F, R, mh_thresh, mh_mult, min_inliers};
+  // Estimator::OutlierRejection only gates when F > min_required_inliers_ (src/manager.cpp:635)
+  return update_chunks(c, B, F > min_inliers ? &gp : nullptr);
+}
+
+int xivo_hip_last_path(xivo_hip_ctx* c) { return c ? c->last_path : -1; }
+int xivo_hip_last_route(xivo_hip_ctx* c) { return c ? c->last_route : -1; }
+const char* xivo_hip_route_name(int route) { return route >= 0 && route < ROUTE_COUNT ? kRouteNames[route] : ""; }
+
+double xivo_hip_stage_bytes(xivo_hip_ctx* c, int stage) {
+  return (c && stage >= 0 && stage < ST_COUNT) ? c->stage_bytes[stage] : 0.0;
+}
+
+const char* xivo_hip_stage_kernel(xivo_hip_ctx* c, int stage) {
+  return (c && stage >= 0 && stage < ST_COUNT) ? c->stage_kernel[stage] : "";
+}
+
+int xivo_hip_get_gate(xivo_hip_ctx* c, int B, int F, unsigned char* mask_out, double* dist_out) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || B <= 0 || B > c->Bmax || F <= 0 || !c->mask) return XIVO_HIP_ERR_INVALID;
+  // the dense gate packs [B][F]; the layout-faithful gate (xivo_hip_mh_gate / filter_update) strides by Fmax
+  const size_t ld = c->gate_sparse_last ? (size_t)c->Fmax : (size_t)F;
+  if (c->gate_sparse_last && F != c->F) return XIVO_HIP_ERR_INVALID;
+  if (mask_out) { int rc = d2h_rows(c, mask_out, F, c->mask, ld, F, B); if (rc) return rc; }
+  if (dist_out) {
+    int rc = d2h_rows(c, dist_out, F * sizeof(double), c->dist, ld * sizeof(double), F * sizeof(double), B);
+    if (rc) return rc;
+  }
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_get_err(xivo_hip_ctx* c, int b0, int nb, double* err, long stride) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !err || stride < c->N) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  return d2h_rows(c, err, (size_t)stride * sizeof(double), c->err + (long)b0 * c->Np, (size_t)c->Np * sizeof(double),
+                  (size_t)c->N * sizeof(double), nb);
+}
+
+int xivo_hip_get_ldlt_used(xivo_hip_ctx* c, int b0, int nb, int* used) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !used) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  HIP_TRY(hipMemcpyAsync(used, c->ldlt_used + b0, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_get_status(xivo_hip_ctx* c, int b0, int nb, int* status) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !status) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  HIP_TRY(hipMemcpyAsync(status, c->status + b0, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int i = 0; i < nb; ++i) if (status[i]) return XIVO_HIP_ERR_NOT_SPD;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_selftest_fused_tiles(int column_blocks, int* per_simd) { return fused_tiles_selftest(column_blocks, per_simd); }
+// test hook (no device): the one-kernel update's admission of a padded shape and the invariants of what it would launch
+int xivo_hip_selftest_fused_shape(int Mp, int Np, int pw, char* label, int n) {
+  return fused_shape_selftest(Mp, Np, pw, label, n > 0 ? (size_t)n : 0);
+}
+
+// test hook (no device, no context): the host-side row compression on its own, for the CPU test that pins it to the format
+// of ell.h / meas_compress_kernel. idx [pairs_clear][28], val [pairs_clear][28][2]; returns over.
+int xivo_hip_selftest_host_compress(const double* H, int ldh, int M, int N, int pairs_clear, int* idx, double* val, int* nc, int* pw) {
+  if (!H || !idx || !val || !nc || !pw || M <= 0 || N <= 0 || ldh < M || 2 * pairs_clear < M) return XIVO_HIP_ERR_INVALID;
+  xivo_hip_ctx::HostCompressScratch sc;
+  return host_compress(sc, H, ldh, M, N, pairs_clear, idx, val, nc, pw);
+}
+
+int xivo_hip_update_joseph_host(xivo_hip_ctx* c, int b, int M, const double* H, int ldh, const double* inn,
+                                const double* diagR, double* P, int ldp, double* err_out, unsigned mode) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  const bool p_up = !(mode & XIVO_HIP_HOST_P_RESIDENT), p_down = !(mode & XIVO_HIP_HOST_KEEP_P);
+  if (bad_range(c, b, 1) || !H || !inn || !diagR || !err_out || M <= 0 || M > c->Mmax || ldh < M ||
+      ((p_up || p_down) && (!P || ldp < c->N)))
+    return XIVO_HIP_ERR_INVALID;
+  const int N = c->N, Np = c->Np, pairs_clear = c->Mpmax / 2;
+  // the staged block: compressed rows | inn | diagR | flags | P in | P out | err | status
+  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+  const size_t o_idx = 0, o_val = al(o_idx + (size_t)pairs_clear * ELL_W * sizeof(int)),
+               o_inn = al(o_val + (size_t)pairs_clear * ELL_W * 2 * sizeof(double)), o_R = al(o_inn + (size_t)c->Mpmax * sizeof(double)),
+               o_flags = al(o_R + (size_t)c->Mpmax * sizeof(double)), o_Pin = al(o_flags + 4 * sizeof(int)),
+               o_Pout = al(o_Pin + (size_t)N * N * sizeof(double)), o_err = al(o_Pout + (size_t)N * N * sizeof(double)),
+               o_st = al(o_err + (size_t)N * sizeof(double)), total = al(o_st + 4 * sizeof(int));
+  if (!c->pin_h) {
+    if (hipHostMalloc(reinterpret_cast<void**>(&c->pin_h), total, hipHostMallocMapped) != hipSuccess) { c->pin_h = nullptr; (void)hipGetLastError(); return XIVO_HIP_ERR_NOMEM; }
+    if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->pin_d), c->pin_h, 0) != hipSuccess || !c->pin_d) {
+      hipHostFree(c->pin_h); c->pin_h = nullptr; c->pin_d = nullptr; (void)hipGetLastError(); return XIVO_HIP_ERR_HIP;
+    }
+    c->pin_bytes = total;
+  }
+  // the row-pair compressed rows, built while H_ is staged; an H_ that does not fit them (dense rows, stacked OOS rows) or a
+  // context pinned to the dense / fp32 pipelines takes the general entry points - same results, more crossings
+  int nc = 0, pw = 0, over = 1;
+  const bool want_ell = !(c->flags & XIVO_HIP_FLAG_DENSE_H) && meas_compress_fits(c->Mpmax, Np);
+  if (want_ell)
+    over = host_compress(c->hc, H, ldh, M, N, pairs_clear, reinterpret_cast<int*>(c->pin_h + o_idx),
+                         reinterpret_cast<double*>(c->pin_h + o_val), &nc, &pw);
+  if (over) {
+    int rc = XIVO_HIP_OK;
+    if (p_up) rc = xivo_hip_upload_P(c, b, 1, P, (long)ldp * N, ldp);
+    if (!rc) rc = xivo_hip_set_measurements(c, b, 1, M, H, (long)ldh * N, ldh, inn, M, diagR, M);
+    if (!rc) rc = update_joseph_range(c, b, 1);
+    if (rc) return rc;
+    int st = 0;
+    rc = xivo_hip_get_status(c, b, 1, &st);
+    if (rc) return rc;
+    rc = xivo_hip_get_err(c, b, 1, err_out, N);
+    if (!rc && p_down) rc = xivo_hip_download_P(c, b, 1, P, (long)ldp * N, ldp);
+    return rc;
+  }
+  double* s_inn = reinterpret_cast<double*>(c->pin_h + o_inn);
+  double* s_R = reinterpret_cast<double*>(c->pin_h + o_R);
+  for (int m = 0; m < c->Mpmax; ++m) { s_inn[m] = m < M ? inn[m] : 0.0; s_R[m] = m < M ? diagR[m] : 1.0; }
+  int* s_flags = reinterpret_cast<int*>(c->pin_h + o_flags);
+  s_flags[0] = nc; s_flags[1] = pw; s_flags[2] = 0;
+  // P_ crosses through the context's page-locked block: one host copy each way (~9 us per 500 KB), the boundary kernels
+  // read / write the block over PCIe. (Page-locking the caller's own P_ in place - hipHostRegister - saved 18 us per call
+  // and was dropped: with large pageable copies elsewhere in the process the runtime's own pinning of recycled heap
+  // addresses left the device faulting on the registered pages, scripts/register_stress.py)
+  DropinInArgs ia{};
+  if (p_up) {
+    double* sp = reinterpret_cast<double*>(c->pin_h + o_Pin);   // (the lower triangle is all the device reads: p_unpack_device.h)
+    for (int j = 0; j < N; ++j) memcpy(sp + (size_t)j * N + j, P + (size_t)j * ldp + j, (size_t)(N - j) * sizeof(double));
+    ia.Psrc = reinterpret_cast<const double*>(c->pin_d + o_Pin); ia.ldps = N;
+  }
+  const RangeView v = range_view(c, b);
+  ia.P = v.P; ia.N = N; ia.Np = Np; ia.ldp = Np;
+  ia.block = c->pin_d; ia.off_idx = (int)o_idx; ia.off_val = (int)o_val; ia.off_inn = (int)o_inn; ia.off_R = (int)o_R; ia.off_flags = (int)o_flags;
+  ia.pairs_clear = pairs_clear; ia.Mpmax = c->Mpmax;
+  ia.idx = v.ell.idx; ia.val = v.ell.val; ia.inn = v.inn; ia.diagR = v.diagR;
+  ia.nc = v.ell.nc; ia.pw = v.ell.pw; ia.over = v.ell.over;
+  {
+    StageTimer st(c, ST_STACK, 0.0, "dropin_in_kernel", (p_up ? 8.0 * N * N : 0.0) + (double)pairs_clear * ELL_W * 20.0 + 16.0 * c->Mpmax);
+    HIP_TRY((hipError_t)launch_dropin_in(ia, c->stream));
+  }
+  // what stage_measurements leaves behind for the pipeline
+  c->M = M; c->Mp = round_up16(M);
+  c->ell_over_h[b] = 0; c->ell_nc_h[b] = nc; c->ell_pw_h[b] = pw;
+  c->dense_valid = false; c->dense_from_ell = true; c->ht_valid = true; c->mixed_row0 = -1;
+  // (from here on kernels that read the context's pinned block may be in flight: an early return drains the stream first,
+  //  the next call overwrites that block)
+  int rc = update_joseph_range(c, b, 1);
+  if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+  DropinOutArgs oa{};
+  oa.P = v.P; oa.N = N; oa.ldp = Np;
+  if (p_down) { oa.Pdst = reinterpret_cast<double*>(c->pin_d + o_Pout); oa.ldpd = N; }
+  oa.err = v.err; oa.err_dst = reinterpret_cast<double*>(c->pin_d + o_err);
+  oa.status = v.status; oa.ldlt_used = v.ldlt_used; oa.flags_dst = reinterpret_cast<int*>(c->pin_d + o_st);
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "dropin_out_kernel", (p_down ? 8.0 * N * N : 0.0) + 8.0 * N);
+    if (launch_dropin_out(oa, c->stream) != 0) { (void)hipStreamSynchronize(c->stream); return XIVO_HIP_ERR_HIP; }
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));        // the one synchronisation of the call: kernel end = system-scope release
+  const int* s_st = reinterpret_cast<const int*>(c->pin_h + o_st);
+  memcpy(err_out, c->pin_h + o_err, (size_t)N * sizeof(double));
+  if (p_down) {
+    const double* sp = reinterpret_cast<const double*>(c->pin_h + o_Pout);
+    if (ldp == N) memcpy(P, sp, (size_t)N * N * sizeof(double));
+    else for (int j = 0; j < N; ++j) memcpy(P + (size_t)j * ldp, sp + (size_t)j * N, (size_t)N * sizeof(double));
+  }
+  return s_st[0] ? XIVO_HIP_ERR_NOT_SPD : XIVO_HIP_OK;
+}
+
+int xivo_hip_mh_gate_dense(xivo_hip_ctx* c, int B, int F, double R, double mh_thresh, double mh_mult,
+                           int min_inliers, unsigned char* mask_out, double* dist_out) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || B <= 0 || B > c->Bmax || F <= 0 || 2 * F > c->M) return XIVO_HIP_ERR_INVALID;
+  int rc = ensure_gate_buffers(c, F);
+  if (rc) return rc;
+  rc = ensure_dense(c);
+  if (rc) return rc;
+  GateDenseArgs a{};
+  a.mask = c->mask; a.dist = c->dist; a.F = F; a.R = R; a.thresh = mh_thresh; a.mult = mh_mult; a.min_inliers = min_inliers;
+  a.have_ell = 1;
+  rc = gate_dense_rows(c, B, a);
+  if (rc) return rc;
+  c->gate_sparse_last = 0;
+  if (mask_out) HIP_TRY(hipMemcpyAsync(mask_out, c->mask, (size_t)B * F, hipMemcpyDeviceToHost, c->stream));
+  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, c->dist, (size_t)B * F * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (mask_out || dist_out) HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+}  // extern "C"

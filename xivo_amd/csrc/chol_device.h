@@ -18,7 +18,7 @@ namespace {
 // d = sqrt(p) and rd = 1 / sqrt(p) of a pivot: hardware estimate + two Newton steps, d = p * rd with one correction - no
 // sqrt / divide in the serial chain. BOTH Cholesky kernels use this routine and the same operand order everywhere else
 // (two accumulators over the k-slices of a block product, inverse rows scaled by rd), so that they produce the SAME bits:
-// which of them a node runs faster (chol_pick in capi.hip) then changes the time, never the result.
+// which of them a node runs faster (the pick of launch_chol_f64, chol_f64.hip) then changes the time, never the result.
 __device__ __forceinline__ void pivot_scale(double p, double& d, double& rd) {
 #pragma clang fp contract(off)
   rd = __builtin_amdgcn_rsq(p);
@@ -51,7 +51,7 @@ __device__ __forceinline__ void factor_invert_diag(d4& x, d4& y, int& bad, const
   // some nodes of the pool than on others.
 #pragma unroll
   for (int rc = 0; rc < 4; ++rc) {
-#if XIVO_CHOL_UNROLL16     // A/B build (scripts/ab_chol.sh): all sixteen columns unrolled
+#if XIVO_CHOL_UNROLL16     // A/B build (scripts/build_variant.sh): all sixteen columns unrolled
 #pragma unroll
 #else
 #pragma unroll 1

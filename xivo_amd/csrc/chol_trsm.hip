@@ -384,7 +384,7 @@ void pnew_reg_kernel_label(int Mp, char* buf, size_t n) { snprintf(buf, n, "pnew
 
 // Few filters (fewer one-per-filter workgroups than a quarter of the CUs): the solve spreads over 128-column workgroups of
 // the streamed kernel and the covariance product over the tiles of the stand-alone GEMM, instead of one CU per filter doing
-// all 13 000 MFMAs of an update by itself (87 us at the issue rate for N = 250, M = 160). The caller (capi.hip) combines this
+// all 13 000 MFMAs of an update by itself (87 us at the issue rate for N = 250, M = 160). The caller (capi_update.hip) combines this
 // with the pipeline's own conditions and XIVO_HIP_FLAG_THROUGHPUT_ROUTE.
 bool trsm_latency_route(int Mp, int batch) { return Mp / 16 <= 14 && batch <= 64; }
 

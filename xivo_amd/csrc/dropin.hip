@@ -1,4 +1,4 @@
-// The two boundary kernels of the one-filter "plumbing" call (capi.hip: xivo_hip_update_joseph_host).
+// The two boundary kernels of the one-filter "plumbing" call (capi_update.hip: xivo_hip_update_joseph_host).
 //
 // The reference's Estimator::UpdateJosephForm (/root/reference/src/estimator.cpp:1257-1288) works on members that live
 // in host memory: P_, H_, inn_, diagR_ in, err_ and P_ out. A drop-in keeps that contract, so every call crosses PCIe

@@ -11,7 +11,7 @@ int launch_unpack_P(const double* raw, double* P, int N, int Np, int ldp, long s
                     hipStream_t s);
 int launch_pack_P(const double* P, double* raw, int N, int ldp, long strideP, int batch, hipStream_t s);
 
-// One-filter plumbing call (dropin.hip, capi.hip: xivo_hip_update_joseph_host): the boundary kernels address page-locked
+// One-filter plumbing call (dropin.hip, capi_update.hip: xivo_hip_update_joseph_host): the boundary kernels address page-locked
 // host memory directly. `block` = the staged compressed rows of the filter: ints idx[pairs_clear][ELL_W] at off_idx,
 // doubles val[pairs_clear][ELL_W][2] at off_val, inn[Mpmax] at off_inn, diagR[Mpmax] at off_R, ints {nc, pw, over} at off_flags.
 struct DropinInArgs {
@@ -42,7 +42,7 @@ int launch_unpack_meas(const double* rawH, long strideRaw, int ldraw, const int*
                        int M, int Mp, int N, int Np, int batch, hipStream_t s);
 
 // P edits
-// H^T rebuilt from the dense H of every filter (the G-level producers may skip writing it: capi.hip skip_HT)
+// H^T rebuilt from the dense H of every filter (the G-level producers may skip writing it: capi_glevel.hip, ht_valid)
 int launch_transpose_H(const double* H, long strideH, int ldh, double* HT, long strideHT, int ldht, int Mp, int Np, int batch,
                        hipStream_t s);
 int launch_p_zero_rc(double* P, int ldp, int Np, int off, int len, hipStream_t s);

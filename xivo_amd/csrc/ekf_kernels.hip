@@ -2676,7 +2676,7 @@ int launch_unpack_meas(const double* rawH, long strideRaw, int ldraw, const int*
   CHECK_LAUNCH();
 }
 // H^T [Np x Mp, ldht] from the dense H [Mp x Np, ldh] of every filter: the transposed copy is optional for the G-level
-// producers (capi.hip: skip_HT) and rebuilt here when a consumer turns up after all. 32 x 32 tiles through LDS so that
+// producers (capi_glevel.hip: ht_valid) and rebuilt here when a consumer turns up after all. 32 x 32 tiles through LDS so that
 // both sides move 256-byte runs.
 __global__ __launch_bounds__(256) void transpose_H_kernel(const double* __restrict__ Hall, long strideH, int ldh,
                                                          double* __restrict__ HTall, long strideHT, int ldht, int Mp, int Np) {

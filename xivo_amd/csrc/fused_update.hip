@@ -3,7 +3,7 @@
 // P_ = (K H - I) P (K H - I)^T + K R K^T` (/root/reference/src/estimator.cpp:1257-1288) and, in front of it, the numeric core
 // of Estimator::MHGating (/root/reference/src/update.cpp:60-96) on the 2 x 2 diagonal blocks of S.
 //
-// The five-kernel sparse pipeline (capi.hip, update_sparse_range) moves ~2.2 MB per filter at these sizes against 0.45 MB of
+// The five-kernel sparse pipeline (capi_update.hip, update_sparse_range) moves ~2.2 MB per filter at these sizes against 0.45 MB of
 // compulsory traffic: P H^T, S, the factor and its inverse blocks, the gated right-hand sides all cross HBM between kernels.
 // Here they never leave the CU - one workgroup per filter, wave w owns state rows [16 w, 16 w + 16):
 //   1  H P (rows of H x the wave's 16 state columns) straight into the MFMA accumulator layout the solve wants:

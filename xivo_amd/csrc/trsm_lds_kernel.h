@@ -8,7 +8,7 @@
 #include "mfma_util.h"
 #include "chol_device.h"
 
-// XIVO_ABL: timing-only ablations of trsm_lds_f64_kernel<., 4> (scripts/ablate_solve.sh builds one library per value; the
+// XIVO_ABL: timing-only ablations of trsm_lds_f64_kernel<., 4> (scripts/build_variant.sh builds one library per value; the
 // results are WRONG for any value but 0): 1 stop after the substitutions, 2 skip the substitutions, 3 no fix-up pass /
 // barrier, 4 no stores of P+, 5 no dx accumulation in the backward loop, 6 no stash write / read-back, 7 no loads of the P
 // tiles, 8 no operand DMA, 9 LDS-only barrier at the phase start (no vmcnt drain), 10 two row blocks per phase,

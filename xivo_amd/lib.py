@@ -528,7 +528,7 @@ class Context:
         return int(self.lib.xivo_hip_last_path(self.h))
 
     def last_route(self):
-        """Name of the route the last update pass took (the table of plan_update in capi.hip): fused, sparse_in_solve,
+        """Name of the route the last update pass took (the table of plan_update in capi_update.hip): fused, sparse_in_solve,
         sparse_whitened, sparse_symmetric, sparse_tail, dense_ascoded, dense_whitened, dense_symmetric."""
         return self.lib.xivo_hip_route_name(int(self.lib.xivo_hip_last_route(self.h))).decode()
 
