@@ -264,6 +264,20 @@ int xivo_hip_selftest_fused_tiles(int column_blocks, int* per_simd);
  * 16 more waves than the instantiation's workgroup. 0 = all hold. No GPU needed. */
 int xivo_hip_selftest_fused_shape(int Mp, int Np, int pw, char* label, int n);
 int xivo_hip_selftest_host_compress(const double* H, int ldh, int M, int N, int pairs_clear, int* idx, double* val, int* nc, int* pw);
+/* Host-only answer to "which kernel would this shape launch" for the feature-level and propagation kernels whose launch picks
+ * by size (csrc/ekf_kernels.hip; the launch calls the same function). label[n] (optional) receives the stage label that
+ * xivo_hip_stage_kernel reports for that launch. No GPU needed.
+ *   XIVO_HIP_LAUNCH_GATE          a = filters in the call, b = F, c = online-calibration build (0 / 1): returns the threads per
+ *                                 filter of gate_sparse_kernel; label "gate_sparse_kernel@<threads>".
+ *   XIVO_HIP_LAUNCH_OOS_COMPRESS  a = n_groups, b = the largest OOS row count of the call: returns 0 <36,1>, 1 <64,1>,
+ *                                 2 <36,2>, -1 when none is built (xivo_hip_compress_oos leaves the rows as they are; label "").
+ *   XIVO_HIP_LAUNCH_PROP_TAIL     a = nm, b = N: returns the passes of 256 tail columns over N - nm (0 when N = nm), -1 when
+ *                                 nm is outside 1..40 or above N (refused); label "propagate_cov_fixed_kernel<23>" or
+ *                                 "propagate_cov_kernel". */
+#define XIVO_HIP_LAUNCH_GATE 0
+#define XIVO_HIP_LAUNCH_OOS_COMPRESS 1
+#define XIVO_HIP_LAUNCH_PROP_TAIL 2
+int xivo_hip_selftest_glevel_launch(int kind, int a, int b, int c, char* label, int n);
 /* Estimator::MHGating numeric core on dense rows (src/update.cpp:60-96):
  * rows 2f,2f+1 of the staged H are feature f's J. Writes the inlier mask and
  * Mahalanobis distances; rejected rows are then neutralised in the staged
@@ -592,7 +606,8 @@ int xivo_hip_last_path(xivo_hip_ctx* ctx);
 int xivo_hip_last_route(xivo_hip_ctx* ctx);
 const char* xivo_hip_route_name(int route);
 /* kernel instantiation the last launch of profile stage `stage` ran (index as in xivo_hip_profile_get; needs
- * XIVO_HIP_FLAG_PROFILE), spelled as rocprofv3 --kernel-trace prints it minus spaces; "" if none */
+ * XIVO_HIP_FLAG_PROFILE), spelled as rocprofv3 --kernel-trace prints it minus spaces, template arguments included; "" if none.
+ * A kernel whose workgroup size depends on the shape has it appended after an '@' (gate_sparse_kernel@1024). */
 const char* xivo_hip_stage_kernel(xivo_hip_ctx* ctx, int stage);
 /* algorithmic HBM bytes of that launch: every input and every output of the stage once */
 double xivo_hip_stage_bytes(xivo_hip_ctx* ctx, int stage);

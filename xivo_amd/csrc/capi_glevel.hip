@@ -15,7 +15,9 @@ int gate_impl(xivo_hip_ctx* c, int B, double R, double th, double mult, int min_
   GateArgs a{};
   a.sb = scene_buffers(c); a.lay = c->lay; a.P = c->P; a.strideP = c->sP; a.ldp = c->Np;
   a.R = R; a.thresh = th; a.mult = mult; a.min_inliers = min_inl; a.batch = B; a.use_gating = use_gating;
-  StageTimer st(c, ST_GATE, 0.0, "gate_sparse_kernel");
+  char label[64];
+  gate_sparse_threads(B, a.sb.F, a.sb.Jc ? 1 : 0, label, sizeof(label));
+  StageTimer st(c, ST_GATE, 0.0, label);
   c->gate_sparse_last = 1;
   return launch_gate_sparse(a, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
 }
@@ -366,7 +368,7 @@ int xivo_hip_oos_project_ex(xivo_hip_ctx* c, int b0, int nb, int n_oos, const xi
   c->oos_row0 = c->M; c->oos_R = Roos;
   a.rows_out = c->oos_rows;
   {
-    StageTimer st(c, ST_OTHER, 0.0);
+    StageTimer st(c, ST_OTHER, 0.0, "oos_kernel");
     HIP_TRY((hipError_t)launch_oos(a, c->stream));
   }
   if (rows_out) HIP_TRY(hipMemcpyAsync(rows_out, c->oos_rows, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -548,9 +550,10 @@ int xivo_hip_compress_oos(xivo_hip_ctx* c, int B, double trigger_ratio, int* row
   a.lay = c->lay; a.mb = meas_buffers(c); a.row0 = c->oos_row0; a.rows = c->oos_rows; a.rows_out = c->oos_rows;
   if (c->mixed_row0 >= 0) { a.mb.HT = nullptr; c->ht_valid = false; }
   a.ratio = trigger_ratio; a.Roos = c->oos_R; a.batch = B;
-  int rc;
-  {
-    StageTimer st(c, ST_OTHER, 0.0, "oos_compress_kernel");
+  int rc = -1;
+  char label[64];
+  if (oos_compress_pick(c->lay.n_groups, c->oos_max_rows, label, sizeof(label)) >= 0) {
+    StageTimer st(c, ST_OTHER, 0.0, label);
     rc = launch_oos_compress(a, c->oos_max_rows, c->stream);
   }
   if (rc > 0) return XIVO_HIP_ERR_HIP;
@@ -692,7 +695,7 @@ int xivo_hip_absorb_error(xivo_hip_ctx* c, int B) {
   a.poses = c->poses; a.groups = c->groups; a.feats = c->feats; a.mask = c->mask; a.err = c->err; a.strideErr = c->Np;
   a.lay = c->lay; a.F = c->F; a.Fmax = c->Fmax; a.batch = B; a.counter = c->absorb_count; a.status = c->status;
   a.calib = (c->calib_on || c->calib_motion) ? c->calib : nullptr; a.cl = c->cl;
-  StageTimer st(c, ST_OTHER, 0.0);
+  StageTimer st(c, ST_OTHER, 0.0, "absorb_error_kernel");
   return launch_absorb_error(a, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
 }
 
@@ -797,6 +800,25 @@ int xivo_hip_get_H(xivo_hip_ctx* c, int b, int* M_out, double* H, int ldh, doubl
   if (diagR) HIP_TRY(hipMemcpyAsync(diagR, c->diagR + (long)b * c->Mpmax, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return XIVO_HIP_OK;
+}
+
+// test hook (no device, no context): the launch choice of a feature-level or propagation kernel for a shape, from the same
+// function the launch calls (include/xivo_hip.h)
+int xivo_hip_selftest_glevel_launch(int kind, int a, int b, int c, char* label, int n) {
+  const size_t ln = label && n > 0 ? (size_t)n : 0;
+  if (ln) label[0] = 0;
+  switch (kind) {
+    case XIVO_HIP_LAUNCH_GATE:
+      if (a <= 0 || b <= 0) return XIVO_HIP_ERR_INVALID;
+      return gate_sparse_threads(a, b, c ? 1 : 0, label, ln);
+    case XIVO_HIP_LAUNCH_OOS_COMPRESS:
+      if (a <= 0 || b <= 0) return XIVO_HIP_ERR_INVALID;
+      return oos_compress_pick(a, b, label, ln);
+    case XIVO_HIP_LAUNCH_PROP_TAIL:
+      return propagate_cov_pick(a, b, label, ln);
+    default:
+      return XIVO_HIP_ERR_INVALID;
+  }
 }
 
 }  // extern "C"

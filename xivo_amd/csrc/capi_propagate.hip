@@ -60,7 +60,9 @@ int xivo_hip_propagate_cov(xivo_hip_ctx* c, int b0, int nb, int nm, const double
   HIP_TRY(hipMemcpyAsync(c->staging, Phi, per * nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->staging + per * nb, Pmm, per * nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
   {
-    StageTimer st(c, ST_OTHER, 0.0);
+    char label[64];
+    propagate_cov_pick(nm, c->N, label, sizeof(label));
+    StageTimer st(c, ST_OTHER, 0.0, label);
     if (launch_propagate_cov(c->P, c->sP, c->Np, c->N, c->Np, nm, c->staging, c->staging + per * nb, b0, nb, c->stream))
       return XIVO_HIP_ERR_HIP;
   }
@@ -129,7 +131,9 @@ int xivo_hip_propagate_calib(xivo_hip_ctx* c, int b0, int nb, int n_imu, const x
     HIP_TRY((hipError_t)launch_propagate_state_calib(a, c->stream));
   }
   {
-    StageTimer st(c, ST_PROP_TAIL, 0.0, "propagate_cov_kernel", (double)nb * (4.0 * nm * c->N + 2.0 * nm * nm) * sizeof(double));
+    char label[64];
+    propagate_cov_pick(nm, c->N, label, sizeof(label));
+    StageTimer st(c, ST_PROP_TAIL, 0.0, label, (double)nb * (4.0 * nm * c->N + 2.0 * nm * nm) * sizeof(double));
     HIP_TRY((hipError_t)launch_propagate_cov(c->P, c->sP, c->Np, c->N, c->Np, nm, a.Phi_out, a.Pmm_out, b0, nb, c->stream));
   }
   HIP_TRY(hipStreamSynchronize(c->stream));   // imu / opts / Qmodel are borrowed host memory

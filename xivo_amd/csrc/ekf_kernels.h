@@ -92,6 +92,11 @@ struct GateArgs {
   double R, thresh, mult; int min_inliers; int batch; int use_gating;
 };
 int launch_gate_sparse(const GateArgs& a, hipStream_t s);
+// the launch choices below are made here only: the launch and xivo_hip_selftest_glevel_launch (capi_glevel.hip) call the same
+// functions. Each writes the stage label (the kernel as rocprofv3 names it; the gate's block size after an '@') to label[n].
+// gate_sparse_kernel: threads per filter - 1024 below 256 filters, 256 from there, halved while the LDS passes 64 KB
+// (online-calibration builds, wide != 0, carry more scratch per wave)
+int gate_sparse_threads(int batch, int F, int wide, char* label, size_t n);
 struct StackArgs {
   SceneBuffers sb; xivo_layout lay; MeasBuffers mb;
   int Mp, Np, batch; double R; int fix_group_block;
@@ -208,10 +213,15 @@ struct OosCompressArgs {
   double ratio, Roos;
   int batch;
 };
+// the instantiation for n_groups group slots (6 + 6 n_groups candidate columns + the residual) and rows_max rows:
+// 0 <36,1> (<= 64 columns, <= 144 rows), 1 <64,1> (<= 64, <= 256), 2 <36,2> (<= 128, <= 144), -1 none is built
+int oos_compress_pick(int n_groups, int rows_max, char* label, size_t n);
 // returns -1 (nothing launched) when the block is larger than the built instantiations
 int launch_oos_compress(const OosCompressArgs& a, int rows_max, hipStream_t s);
 
-// propagation tail (rk4.cpp:92-102)
+// propagation tail (rk4.cpp:92-102): the kernel for motion size nm (propagate_cov_fixed_kernel<23> for 23, else
+// propagate_cov_kernel) and the passes of 256 tail columns it makes over N - nm; -1 for nm outside 1..40 (MAXM)
+int propagate_cov_pick(int nm, int N, char* label, size_t n);
 int launch_propagate_cov(double* P, long strideP, int ldp, int N, int Np, int nm, const double* Phi,
                          const double* Pmm, int b0, int nb, hipStream_t s);
 

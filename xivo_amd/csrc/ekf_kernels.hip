@@ -16,6 +16,8 @@
 // (all paths relative to /root/reference). These are HBM/L2-bound byte movers
 // or tiny per-feature 3x3 chains: one thread / one wave64 per feature, wave
 // reductions for the chi-square gating, no MFMA.
+#include <cstdio>
+
 #include "ekf_kernels.h"
 #include "camera_device.h"
 #include "gate_device.h"
@@ -2720,14 +2722,21 @@ int launch_jac_instate(const SceneBuffers& sb, const xivo_layout& lay, const xiv
   hipLaunchKernelGGL(jac_instate_kernel, dim3((tot + 127) / 128), dim3(128), 0, s, sb, lay, cam, batch);
   CHECK_LAUNCH();
 }
+// distances + threshold | slot indices | per-wave scratch of feature_chi2_lds (64 KB without an opt-in: fewer waves if F is large)
+static size_t gate_sparse_lds(int F, int wide, int nt) {
+  const size_t scr = wide ? WIDE_SCR : 484, pss = wide ? WIDE_PSS : 0;
+  return ((size_t)(F + 1) + (2 * F + 1) / 2 + pss + (size_t)(nt / 64) * scr) * sizeof(double);
+}
+int gate_sparse_threads(int batch, int F, int wide, char* label, size_t n) {
+  int nt = batch < 256 ? 1024 : 256;
+  while (nt > 64 && gate_sparse_lds(F, wide, nt) > 65536) nt /= 2;
+  if (label && n) snprintf(label, n, "gate_sparse_kernel@%d", nt);
+  return nt;
+}
 int launch_gate_sparse(const GateArgs& a, hipStream_t s) {
-  int nt = a.batch < 256 ? 1024 : 256;
-  // distances + threshold | slot indices | per-wave scratch of feature_chi2_lds (64 KB without an opt-in: fewer waves if F is large)
-  const size_t scr = a.sb.Jc ? WIDE_SCR : 484, pss = a.sb.Jc ? WIDE_PSS : 0;
-  auto lds_of = [&](int t) { return ((size_t)(a.sb.F + 1) + (2 * a.sb.F + 1) / 2 + pss + (size_t)(t / 64) * scr) * sizeof(double); };
-  while (nt > 64 && lds_of(nt) > 65536) nt /= 2;
-  const size_t lds = lds_of(nt);
-  hipLaunchKernelGGL(gate_sparse_kernel, dim3(a.batch), dim3(nt), lds, s, a);
+  const int wide = a.sb.Jc ? 1 : 0;
+  const int nt = gate_sparse_threads(a.batch, a.sb.F, wide, nullptr, 0);
+  hipLaunchKernelGGL(gate_sparse_kernel, dim3(a.batch), dim3(nt), gate_sparse_lds(a.sb.F, wide, nt), s, a);
   CHECK_LAUNCH();
 }
 int launch_stack(const StackArgs& a, hipStream_t s) {
@@ -2757,12 +2766,20 @@ int launch_edit_batch(const EditArgs& a, int n_wg, hipStream_t s) {
   hipLaunchKernelGGL(edit_batch_kernel, dim3(n_wg), dim3(256), 0, s, a);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
+int oos_compress_pick(int n_groups, int rows_max, char* label, size_t n) {
+  const int ncols = 6 + 6 * n_groups + 1;            // candidates + the residual column
+  const int pick = (ncols <= 64 && rows_max <= 144) ? 0 : (ncols <= 64 && rows_max <= 256) ? 1 : (ncols <= 128 && rows_max <= 144) ? 2 : -1;
+  static const char* const names[] = {"oos_compress_kernel<36,1>", "oos_compress_kernel<64,1>", "oos_compress_kernel<36,2>"};
+  if (label && n) snprintf(label, n, "%s", pick < 0 ? "" : names[pick]);
+  return pick;
+}
 int launch_oos_compress(const OosCompressArgs& a, int rows_max, hipStream_t s) {
-  const int ncols = 6 + 6 * a.lay.n_groups + 1;      // candidates + the residual column
-  if (ncols <= 64 && rows_max <= 144) hipLaunchKernelGGL((oos_compress_kernel<36, 1>), dim3(a.batch), dim3(256), 0, s, a);
-  else if (ncols <= 64 && rows_max <= 256) hipLaunchKernelGGL((oos_compress_kernel<64, 1>), dim3(a.batch), dim3(256), 0, s, a);
-  else if (ncols <= 128 && rows_max <= 144) hipLaunchKernelGGL((oos_compress_kernel<36, 2>), dim3(a.batch), dim3(256), 0, s, a);
-  else return -1;                                     // not built for this size: the caller leaves the rows as they are
+  switch (oos_compress_pick(a.lay.n_groups, rows_max, nullptr, 0)) {
+    case 0: hipLaunchKernelGGL((oos_compress_kernel<36, 1>), dim3(a.batch), dim3(256), 0, s, a); break;
+    case 1: hipLaunchKernelGGL((oos_compress_kernel<64, 1>), dim3(a.batch), dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((oos_compress_kernel<36, 2>), dim3(a.batch), dim3(256), 0, s, a); break;
+    default: return -1;                               // not built for this size: the caller leaves the rows as they are
+  }
   CHECK_LAUNCH();
 }
 int launch_ransac_select(const RansacArgs& a, hipStream_t s) {
@@ -2796,10 +2813,15 @@ int launch_oos(const OosArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(oos_kernel, dim3(a.n_oos, a.batch), dim3(64), 0, s, a);
   CHECK_LAUNCH();
 }
+int propagate_cov_pick(int nm, int N, char* label, size_t n) {
+  if (nm <= 0 || nm > 40 || N < nm) { if (label && n) label[0] = 0; return -1; }
+  if (label && n) snprintf(label, n, "%s", nm == 23 ? "propagate_cov_fixed_kernel<23>" : "propagate_cov_kernel");
+  return (N - nm + 255) / 256;                         // both kernels: one thread per tail column, 256 columns a pass
+}
 int launch_propagate_cov(double* P, long strideP, int ldp, int N, int Np, int nm, const double* Phi,
                          const double* Pmm, int b0, int nb, hipStream_t s) {
   (void)Np;
-  if (nm > 40) return (int)hipErrorInvalidValue;
+  if (propagate_cov_pick(nm, N, nullptr, 0) < 0) return (int)hipErrorInvalidValue;
   if (nm == 23) {
     hipLaunchKernelGGL(propagate_cov_fixed_kernel<23>, dim3(nb), dim3(256), 0, s, P, strideP, ldp, N, Phi, Pmm, b0);
     CHECK_LAUNCH();

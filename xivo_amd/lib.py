@@ -155,6 +155,7 @@ _SIGS = {
     "xivo_hip_selftest_fused_tiles": [C.c_int, C.c_void_p],
     "xivo_hip_selftest_fused_shape": [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int],
     "xivo_hip_selftest_host_compress": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_selftest_glevel_launch": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int],
 }
 HOST_P_RESIDENT, HOST_KEEP_P = 1, 2
 
