@@ -451,8 +451,8 @@ print(json.dumps(out))
 
 
 def test_cholesky_kernels_are_bit_identical(built):
-    """The one-wave and the four-wave register Cholesky run the same arithmetic in the same order (factor_invert_diag on
-    the matrix pipe, pivot_scale, two accumulators per block product): whichever kernel runs (XIVO_HIP_CHOL_WAVE: the one-wave
+    """The one-wave and the four-wave register Cholesky run the same arithmetic in the same order (factor_invert_diag,
+    chol_device.h, and two accumulators per block product): whichever kernel runs (XIVO_HIP_CHOL_WAVE: the one-wave
     kernel for every size - the one A/B knob the factorisation keeps) and whichever instantiation of the register kernel
     (four waves per factor or eight, three workgroups per CU / two), P+ and dx come out bit for bit the same - across nodes,
     ranks, runs and batch sizes."""

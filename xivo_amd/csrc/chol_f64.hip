@@ -7,24 +7,15 @@
 //   inverse of every diagonal block is kept so every panel / triangular-solve step is an MFMA.
 //   Output: L in the lower triangle, L^T mirrored into the upper triangle.
 // chol_reg_f64_kernel : four waves per filter, the factor in registers (M <= 192).
-// Both factor and invert a diagonal block with the SAME routine (factor_invert_diag) and use the same operand order
-// everywhere else, so they produce the same bits: which of them a node runs faster changes the time, never the result.
+// Both factor and invert a diagonal block with the SAME routine (factor_invert_diag, chol_device.h: four steps of four columns;
+// chol_S 1.95 -> 1.86 ms per 16384 at M = 160, 2.65 -> 2.48 per 4096 at M = 300, 0.27 -> 0.25 at M = 120 against the
+// sixteen-column loop of rounds 3-5) and use the same operand order everywhere else, so they produce the same bits: which of
+// them a node runs faster changes the time, never the result.
 #include <stdlib.h>
 #include <stdio.h>
 
 #include "mfma_util.h"
 #include "chol_device.h"
-
-// The diagonal-block step of both Cholesky kernels: the four-column form (chol_device.h, round 6; chol_S 1.95 -> 1.86 ms per 16384 at
-// M = 160, 2.65 -> 2.48 per 4096 at M = 300, 0.27 -> 0.25 at M = 120) - or, -DXIVO_CHOL_BLOCKED=0, the sixteen-column loop of rounds 3-5
-#ifndef XIVO_CHOL_BLOCKED
-#define XIVO_CHOL_BLOCKED 1
-#endif
-#if XIVO_CHOL_BLOCKED
-#define XIVO_CHOL_DIAG factor_invert_diag_blocked2<9>
-#else
-#define XIVO_CHOL_DIAG factor_invert_diag
-#endif
 #include "gate_device.h"
 
 namespace xivo_hip {
@@ -65,7 +56,7 @@ __global__ __launch_bounds__(64, 4) void chol_f64_kernel(CholArgs g) {
       d4 x, y;
 #pragma unroll
       for (int r = 0; r < 4; ++r) x[r] = S[(16 * j + li) + (long)(16 * j + lg + 4 * r) * ld] - (acc0[r] + acc1[r]);
-      XIVO_CHOL_DIAG(x, y, bad, 16 * j, li, lg);
+      factor_invert_diag(x, y, bad, 16 * j, li, lg);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int c = lg + 4 * r;
@@ -293,7 +284,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void chol_reg_f64_kernel(CholArgs g,
     if (wave == owner) {
       int bad = 0;
       d4 y;
-      XIVO_CHOL_DIAG(x, y, bad, 16 * j, li, lg);
+      factor_invert_diag(x, y, bad, 16 * j, li, lg);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int c = lg + 4 * r;
@@ -368,9 +359,9 @@ int launch_chol_f64(const CholArgs& g, hipStream_t stream, const CholGateArgs* g
   const CholGateArgs nogate{};
   if (gate && !chol_gate_supported(g.Mp, g.batch)) return (int)hipErrorInvalidValue;
   const int nb = g.Mp / 16;
-  // Round 3 (factor_invert_diag on the matrix pipe): the register kernel is ~11 500 instructions at ten block rows (it
+  // Round 3 (the diagonal-block step on the matrix pipe): the register kernel is ~11 500 instructions at ten block rows (it
   // was ~45 000: 170-200 KB of straight-line code that lost 2.6x on nodes with slow instruction fetch) and is the
-  // default for every batch size it holds; the k-slice loop of factor_invert_diag then brought it to 42 KB. Measured at
+  // default for every batch size it holds; the k-slice loop of that step then brought it to 42 KB. Measured at
   // M = 160: one factor 48-52 us (round 2: 80), 16384 factors 1.6-1.7 ms (register kernel, three workgroups per CU, no
   // look-ahead) against 2.4-2.6 ms for the one-wave kernel and 2.3-2.4 ms for either kernel before. Thirteen to nineteen
   // block rows run the same kernel on eight waves (below); the one-wave kernel serves what is left (M > 304).

@@ -327,7 +327,6 @@ int launch_trsm_lds_tf(const TrsmArgs& g_in, hipStream_t stream) {
     lds = 160 * 1024;
     g.t_jbp = (int)(lds / 2 / ((size_t)nb * 4 * 64 * sizeof(double)));   // two buffers
     if (g.t_jbp > 16) g.t_jbp = 16;
-    if (XIVO_ABL == 10) g.t_jbp = 2;
   }
   static bool attr_set = false;
   if (!attr_set) {

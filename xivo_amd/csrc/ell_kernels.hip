@@ -390,12 +390,6 @@ __global__ __launch_bounds__(1024) void gate_ell_kernel(GateEllArgs a) {
 // LDS: slab[cols][XC] doubles, element (k, x) at k * XC + (x ^ (k & 15)) - the XOR keeps both the
 // row-wise loads and the transposing load of ELL_S (lanes = k) conflict-free without a pad column;
 // then ops[pairs][CWU + ELL_PW][2].
-#ifndef XIVO_ELL_HP_PF
-#define XIVO_ELL_HP_PF 0   // A/B: P H^T with 8 waves and the next slab prefetched into registers under the walk
-#endif
-#ifndef XIVO_ELL_ABL
-#define XIVO_ELL_ABL 0   // timing-only ablations of ell_tile_kernel (scripts/build_variant.sh): 1 no pair walk, 2 no slab loads, 3 no output stores
-#endif
 typedef __attribute__((address_space(4))) const double ell_cdouble;
 typedef __attribute__((address_space(4))) const int ell_cint;
 
@@ -404,7 +398,7 @@ typedef __attribute__((address_space(4))) const int ell_cint;
 // prefetch variant (next slab fetched into registers under the pair walk): the hot configuration only
 constexpr bool ell_tile_pf(int mode, int cwu, int xc, int pwu) {
   // (tried for the P H^T and G instantiations too, at 8 waves / 256 VGPRs: 0.83 -> 0.92 and 0.88 -> 1.79 ms)
-  return xc == 64 && cwu == 12 && (mode == ELL_S || (XIVO_ELL_HP_PF && mode == ELL_HP && pwu == 9)) && pwu >= 0;
+  return xc == 64 && cwu == 12 && mode == ELL_S && pwu >= 0;
 }
 // raw buffer access: one 32-bit per-lane offset + a scalar offset per access, no 64-bit address registers per store
 typedef unsigned ell_u2 __attribute__((ext_vector_type(2)));
@@ -500,7 +494,7 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
 #pragma unroll
         for (int u = 0; u < KU; ++u) {
           const int k = lane + 64 * u;
-          r[q * KU + u] = (XIVO_ELL_ABL != 2 && ok && k < cols) ? ell_buf_ld(rs, vo, so + (unsigned)(64 * u) * 8u) : 0.0;
+          r[q * KU + u] = (ok && k < cols) ? ell_buf_ld(rs, vo, so + (unsigned)(64 * u) * 8u) : 0.0;
         }
       }
     } else {
@@ -515,7 +509,7 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
 #pragma unroll
       for (int u = 0; u < RN; ++u) {
         double v = 0.0;
-        if (XIVO_ELL_ABL != 2 && u < nu) v = *reinterpret_cast<const double*>(base + (size_t)u * step + voff);
+        if (u < nu) v = *reinterpret_cast<const double*>(base + (size_t)u * step + voff);
         r[u] = ok ? v : 0.0;
       }
     }
@@ -569,7 +563,7 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
       const double* __restrict__ row = Src + x0 + (ok ? xq : 0);
       for (int k0 = 0; k0 < cols; k0 += (NT / XC) * 8) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) { const int k = k0 + kq + (NT / XC) * u; r[u] = (XIVO_ELL_ABL != 2 && ok && k < cols) ? row[(long)k * a.ldsrc] : 0.0; }
+        for (int u = 0; u < 8; ++u) { const int k = k0 + kq + (NT / XC) * u; r[u] = (ok && k < cols) ? row[(long)k * a.ldsrc] : 0.0; }
 #pragma unroll
         for (int u = 0; u < 8; ++u) { const int k = k0 + kq + (NT / XC) * u; if (k < cols) tile[k * XC + (xq ^ (k & 15))] = r[u]; }
       }
@@ -613,7 +607,7 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
         for (int c = 0; c < NC; ++c) if (x0 + 16 * c + li < a.X) dRc[c] = a.diagR[(long)filt * a.strideR + x0 + 16 * c + li];
       }
       // (S: the row-pair blocks to the right of this slab's diagonal square are skipped - lower triangle + diagonal blocks)
-      const int rb_end = XIVO_ELL_ABL == 1 ? 0 : (MODE == ELL_S ? min(pairs / 8, NC * (sidx + 1)) : pairs / 8);
+      const int rb_end = MODE == ELL_S ? min(pairs / 8, NC * (sidx + 1)) : pairs / 8;
       const int pa = (li & 3) + 4 * (li >> 3), ra = (li >> 2) & 1;     // A operand: MFMA row li = pair pa, row ra of it
       for (int rb = wave; rb < rb_end; rb += NW) {
         const int p0 = 8 * rb;
@@ -724,7 +718,7 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
           const int x = x0 + 16 * c + li;
-          if (x >= a.X || (XIVO_ELL_ABL == 3 && acc[c][0] != 12345.678)) continue;
+          if (x >= a.X) continue;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int pp = p0 + lg + 4 * (r >> 1), i = r & 1, m = 2 * pp + i;
@@ -751,7 +745,7 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
     for (int t = 0; t < CWU; ++t) cm[t] = slab(idx0[t]);
     // S is symmetric and every reader (gating, both Cholesky kernels) takes its lower triangle + the diagonal blocks: lane
     // = row x of S, pair p = columns 2p, 2p + 1 - the pairs to the right of this slab's 64 x 64 diagonal square are skipped
-    const int p_end = XIVO_ELL_ABL == 1 ? 0 : (MODE == ELL_S ? min(pairs, (sidx * XC + XC) / 2) : pairs);
+    const int p_end = MODE == ELL_S ? min(pairs, (sidx * XC + XC) / 2) : pairs;
     // ELL_S: lane = row x of S adds R to its own diagonal element only - one vector load per slab instead of a scalar
     // load (and an lgkmcnt drain) per stored row
     double dRx = 0.0;
@@ -776,7 +770,7 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
       for (int t = 0; t < CWU; ++t) { const d2 v = pv[t]; a0 = fma(v[0], cm[t], a0); a1 = fma(v[1], cm[t], a1); }
 #pragma unroll
       for (int t = 0; t < PWU; ++t) { const d2 v = pv[CWU + t]; a0 = fma(v[0], sv[t], a0); a1 = fma(v[1], sv[t], a1); }
-      if (!live || (XIVO_ELL_ABL == 3 && a0 != 12345.678)) continue;
+      if (!live) continue;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         if (XC == 32 && i != half) continue;      // XC = 32: each half-wave stores its own row

@@ -29,6 +29,7 @@ __device__ unsigned long long xivo_fused_trace2_buf[128 * 16 * 32];
     xivo_fused_trace2_buf[((blockIdx.x >> 6) * 16 + (threadIdx.x >> 6)) * 32 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
 #endif
 #include "trsm_lds_kernel.h"
+#include "chol_device.h"
 #include "ell.h"
 #include "gate_device.h"
 #include "fused_update.h"
@@ -55,26 +56,8 @@ extern "C" int xivo_hip_debug_read_fused_trace2(unsigned long long* out, int n) 
 #define FTR2(slot) do {} while (0)
 #endif
 
-// XIVO_FUSED_ABL (timing-only ablations, scripts/build_variant.sh; results are WRONG for any value but 0): 1 stop behind the
-// gathers of phase 1, 2 stop behind the factorisation, 3 no stores of P+, 4 no mirror stores, 5 no loads of the P tiles,
-// 6 stop in front of the factorisation, 8 no forward substitution next to the factorisation and stop behind it
-#ifndef XIVO_FUSED_ABL
-#define XIVO_FUSED_ABL 0
-#endif
-#ifndef XIVO_FUSED_DIAG_CHAIN
-#define XIVO_FUSED_DIAG_CHAIN 0   // A/B: the sixteen-pivot chain (factor_invert_diag_chain) instead of the four-column form
-#endif
-#ifndef XIVO_FUSED_BALANCE
-#define XIVO_FUSED_BALANCE 1      // product tiles oriented by SIMD load at 10 / 13 column blocks (0: the cyclic rule everywhere)
-#endif
 #ifndef XIVO_FUSED_TU
 #define XIVO_FUSED_TU 4
-#endif
-#ifndef XIVO_FUSED_FWD_LATE
-#define XIVO_FUSED_FWD_LATE 0   // A/B: the forward substitution behind the factorisation instead of next to it
-#endif
-#ifndef XIVO_FUSED_GVAR
-#define XIVO_FUSED_GVAR 0   // timing-only variants of the gather's address pattern (with XIVO_FUSED_ABL=1)
 #endif
 
 namespace xivo_hip {
@@ -168,7 +151,7 @@ __device__ __forceinline__ void fused_product_one_phase(const d4 (&X)[NBM], cons
     int jb; bool real; block_of(t, jb, real);
     const int ba = jb <= wave ? wave : jb, bb = jb <= wave ? jb : wave;       // block (ba, bb), ba >= bb: P's lower triangle
 #pragma unroll
-    for (int r = 0; r < 4; ++r) ring[t % PD][r] = XIVO_FUSED_ABL == 5 ? 1.0 : buf_ld_once(rO, vM, (unsigned)(16 * ba + (16 * bb + 4 * r) * ldp) * 8u);
+    for (int r = 0; r < 4; ++r) ring[t % PD][r] = buf_ld_once(rO, vM, (unsigned)(16 * ba + (16 * bb + 4 * r) * ldp) * 8u);
   };
   static_for<(PD < NTU ? PD : NTU)>([&](auto tc) { request(tc); });
   lds_barrier();                                   // every wave's operand W + D is in place
@@ -209,14 +192,10 @@ __device__ __forceinline__ void fused_product_one_phase(const d4 (&X)[NBM], cons
       mv[r] = (jb != wave || lg + 4 * r > li) ? v : -acc[r];                                      // diagonal tile: the lower triangle is authoritative
     }
     if (t + 1 < NTU || real) {                     // (only the last step can be a dummy: nothing is counted behind it)
-      if (XIVO_FUSED_ABL != 3) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) buf_st_out(-acc[r], rO, vM, (unsigned)(16 * ba + (16 * bbk + 4 * r) * ldp) * 8u);
-      }
-      if (XIVO_FUSED_ABL != 3 && XIVO_FUSED_ABL != 4) {
+      for (int r = 0; r < 4; ++r) buf_st_out(-acc[r], rO, vM, (unsigned)(16 * ba + (16 * bbk + 4 * r) * ldp) * 8u);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) buf_st_out(mv[r], rO, vM, (unsigned)(16 * bbk + (16 * ba + 4 * r) * ldp) * 8u);
-      }
+      for (int r = 0; r < 4; ++r) buf_st_out(mv[r], rO, vM, (unsigned)(16 * bbk + (16 * ba + 4 * r) * ldp) * 8u);
     }
   });
 }
@@ -364,13 +343,6 @@ __global__ __launch_bounds__(64 * NWV, 1) void fused_update_f64_kernel(FusedArgs
   }
   FTR(2);
   FTR2(29);
-  if (XIVO_FUSED_ABL == 1) {
-    double chk = 0.0;
-#pragma unroll
-    for (int i = 0; i < NBM; ++i) chk += X[i][0] + X[i][1] + X[i][2] + X[i][3];
-    if (chk == 12345.678) g.err[(long)filt * g.strideErr + c0 + li] = chk;
-    return;
-  }
 
   // ---- 2  S = H (P H^T) + diag(R): the waves park their columns of H P as the slab of ell<S> (row k = state index,
   //         column = measurement row of the pass, XOR swizzle as in ell_tile_kernel) and walk the row pairs over it
@@ -530,15 +502,8 @@ __global__ __launch_bounds__(64 * NWV, 1) void fused_update_f64_kernel(FusedArgs
     }
   }
   FTR(4);
-  if (XIVO_FUSED_ABL == 6) {                                   // stop in front of the factorisation
-    double chk = 0.0;
-#pragma unroll
-    for (int i = 0; i < NBM; ++i) chk += X[i][0] + X[i][1] + X[i][2] + X[i][3];
-    if (chk == 12345.678) g.err[(long)filt * g.strideErr + c0 + li] = chk;
-    return;
-  }
 
-  // ---- 4  S = L L^T in LDS (trsm_lds_kernel.h, CHOL): block row i belongs to wave i. The forward substitution rides along:
+  // ---- 4  S = L L^T in LDS (chol_device.h): block row i belongs to wave i. The forward substitution rides along:
   //         step k needs inv(L_kk) and the blocks L_ik below it - complete behind the barrier of column k + 1 - so every wave
   //         runs step j - 1 next to column j's panel while the next owner factors (which defers its own step by one column:
   //         the chain of diagonal blocks is the critical path). Each X[i] still receives its terms in ascending k: same bits.
@@ -583,11 +548,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void fused_update_f64_kernel(FusedArgs
           for (int r = 0; r < 4; ++r) x[r] = sD[j * BLK + lo + 68 * r] - (acc0[r] + acc1[r]);
           int bad = 0;
           FTR2(4 * j + 1);
-#if XIVO_FUSED_DIAG_CHAIN
-          factor_invert_diag_chain(x, y, bad, 16 * j, li, lg);
-#else
-          factor_invert_diag_blocked2<9>(x, y, bad, 16 * j, li, lg);
-#endif
+          factor_invert_diag(x, y, bad, 16 * j, li, lg);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int c = lg + 4 * r;
@@ -656,25 +617,15 @@ __global__ __launch_bounds__(64 * NWV, 1) void fused_update_f64_kernel(FusedArgs
           }
         }
         // (a broken factor leaves NaNs at worst: nothing of X is used then)
-        if (!XIVO_FUSED_FWD_LATE && XIVO_FUSED_ABL != 8) {
-          if (wave == j) static_for<NBM>([&](auto kc) { constexpr int k = decltype(kc)::value; if (k == j - 2) forward(kc); });
-          if (wave != j + 1 || j + 1 >= nb) static_for<NBM>([&](auto kc) { constexpr int k = decltype(kc)::value; if (k == j - 1) forward(kc); });
-        }
+        if (wave == j) static_for<NBM>([&](auto kc) { constexpr int k = decltype(kc)::value; if (k == j - 2) forward(kc); });
+        if (wave != j + 1 || j + 1 >= nb) static_for<NBM>([&](auto kc) { constexpr int k = decltype(kc)::value; if (k == j - 1) forward(kc); });
       }
     }
     lds_barrier();
-    if (XIVO_FUSED_FWD_LATE) static_for<NBM>([&](auto kc) { constexpr int k = decltype(kc)::value; if (k < nb - 1) forward(kc); });
   }
   const int chol_bad = sBad;
   if (tid == 0) g.status[filt] = chol_bad;
   FTR(5);
-  if (XIVO_FUSED_ABL == 2 || XIVO_FUSED_ABL == 8) {
-    double chk = 0.0;
-#pragma unroll
-    for (int i = 0; i < NBM; ++i) chk += X[i][0] + X[i][1] + X[i][2] + X[i][3];
-    if (chk == 12345.678) g.err[(long)filt * g.strideErr + c0 + li] = chk;
-    return;
-  }
   if (chol_bad) {
     // S is not positive definite: the pivoted L D L^T fallback (ldlt_fallback.hip) takes this filter from the prior. What it
     // reads from the pipeline is the gated P H^T - rebuilt here from the coefficients still in LDS (the registers are part-way
@@ -779,18 +730,18 @@ __global__ __launch_bounds__(64 * NWV, 1) void fused_update_f64_kernel(FusedArgs
     auto request = [&](int jb, d4& dst) {
       const int ba = jb <= wave ? wave : jb, bb = jb <= wave ? jb : wave;       // block (ba, bb), ba >= bb: P's lower triangle
 #pragma unroll
-      for (int r = 0; r < 4; ++r) dst[r] = XIVO_FUSED_ABL == 5 ? 1.0 : buf_ld_once(rO, vM, (unsigned)(16 * ba + (16 * bb + 4 * r) * g.ldp) * 8u);
+      for (int r = 0; r < 4; ++r) dst[r] = buf_ld_once(rO, vM, (unsigned)(16 * ba + (16 * bb + 4 * r) * g.ldp) * 8u);
     };
     if (!early) __syncthreads();                   // the factor is dead: the LDS takes the operands
     write_y(0);
     if (nph == 1 && (nwl / 2 + 1 == 7 || nwl / 2 + 1 == 6)) {   // the two target shapes (13 / 10 column blocks): hand-counted waits
       double* tscw = sm + g.tsc_off + wave * 256;
-      if (XIVO_FUSED_BALANCE && nwl == 10) {         // tiles oriented for 3 + 3 + 2 + 2 waves on the four SIMDs (tables above)
+      if (nwl == 10) {          // tiles oriented for 3 + 3 + 2 + 2 waves on the four SIMDs (tables above)
         const int ntw = (wave == 2 || wave == 3 || wave == 6 || wave == 7) ? 7 : ((wave == 0 || wave == 1 || wave == 4) ? 5 : 4);
         if (ntw == 7) fused_product_one_phase<NBM, 7, 10>(X, sm, tscw, Pio, g.ldp, nb, nwl, wave, lane);
         else if (ntw == 5) fused_product_one_phase<NBM, 5, 10>(X, sm, tscw, Pio, g.ldp, nb, nwl, wave, lane);
         else fused_product_one_phase<NBM, 4, 10>(X, sm, tscw, Pio, g.ldp, nb, nwl, wave, lane);
-      } else if (XIVO_FUSED_BALANCE && nwl == 13) {  // 4 + 3 + 3 + 3 waves
+      } else if (nwl == 13) {   // 4 + 3 + 3 + 3 waves
         const int ntw = (wave == 12) ? 5 : ((wave & 3) == 0 ? 6 : ((wave == 7 || wave >= 9) ? 7 : 8));
         if (ntw == 8) fused_product_one_phase<NBM, 8, 13>(X, sm, tscw, Pio, g.ldp, nb, nwl, wave, lane);
         else if (ntw == 7) fused_product_one_phase<NBM, 7, 13>(X, sm, tscw, Pio, g.ldp, nb, nwl, wave, lane);
@@ -843,14 +794,14 @@ __global__ __launch_bounds__(64 * NWV, 1) void fused_update_f64_kernel(FusedArgs
           for (int r = 0; r < 4; ++r) tsc[(lg + 4 * r) * 16 + (li ^ (lg + 4 * r))] = -acc[r];      // element (a = li, b = lg + 4 r)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            if ((jb != wave || li >= lg + 4 * r) && XIVO_FUSED_ABL != 3)                              // diagonal tile: the lower triangle is authoritative
+            if (jb != wave || li >= lg + 4 * r)   // diagonal tile: the lower triangle is authoritative
               buf_st_out(-acc[r], rO, vM, (unsigned)(16 * ba + (16 * bbk + 4 * r) * g.ldp) * 8u);
           }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const double v = tsc[li * 16 + ((lg + 4 * r) ^ li)];                                        // element (a = lg + 4 r, b = li)
-            if ((jb != wave || lg + 4 * r > li) && XIVO_FUSED_ABL != 3 && XIVO_FUSED_ABL != 4)
+            if (jb != wave || lg + 4 * r > li)
               buf_st_out(v, rO, vM, (unsigned)(16 * bbk + (16 * ba + 4 * r) * g.ldp) * 8u);
           }
         }

@@ -6,16 +6,6 @@
 #include <stdio.h>
 
 #include "mfma_util.h"
-#include "chol_device.h"
-
-// XIVO_ABL: timing-only ablations of trsm_lds_f64_kernel<., 4> (scripts/build_variant.sh builds one library per value; the
-// results are WRONG for any value but 0): 1 stop after the substitutions, 2 skip the substitutions, 3 no fix-up pass /
-// barrier, 4 no stores of P+, 5 no dx accumulation in the backward loop, 6 no stash write / read-back, 7 no loads of the P
-// tiles, 8 no operand DMA, 9 LDS-only barrier at the phase start (no vmcnt drain), 10 two row blocks per phase,
-// 11 = 2 + no MFMA in the product phase: the memory floor of the product's access pattern (round 5)
-#ifndef XIVO_ABL
-#define XIVO_ABL 0
-#endif
 
 // XIVO_TRACE (scripts/build_variant.sh trace "-DXIVO_TRACE=1"; scripts/trace_solve.py reads it back): shader-clock stamps inside
 // trsm_lds_f64_kernel<., 4> of every 64th workgroup - wave 0 at the phase boundaries of the kernel (XTR / XTRP), every wave
@@ -102,7 +92,7 @@ __device__ __forceinline__ void sym_tiles_from_regs(const d4 (&X)[NBM], const d4
       }
       return;
     }
-    for (int q = wave; q < (XIVO_ABL == 8 ? 0 : nj * 2 * nb); q += NWV) {
+    for (int q = wave; q < nj * 2 * nb; q += NWV) {
       const int jl = q / (2 * nb), t = q - jl * 2 * nb;
       const double* src = Src + (16 * (jb0 + jl) + 2 * (lane & 7)) + (long)(8 * t + (lane >> 3)) * ldsrc;
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
@@ -131,7 +121,7 @@ __device__ __forceinline__ void sym_tiles_from_regs(const d4 (&X)[NBM], const d4
     const int ba = jb <= w ? w : jb, bb = jb <= w ? jb : w;       // block (ba, bb), ba >= bb
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      acc[r] = XIVO_ABL == 7 ? 1.0 : buf_ld_once(rM, vM, (unsigned)(16 * ba + (16 * bb + 4 * r) * ldm) * 8u);   // (negated where it is consumed: no wait here)
+      acc[r] = buf_ld_once(rM, vM, (unsigned)(16 * ba + (16 * bb + 4 * r) * ldm) * 8u);   // (negated where it is consumed: no wait here)
   };
   issue(0);
   unsigned todo = my_tiles(0);
@@ -139,18 +129,15 @@ __device__ __forceinline__ void sym_tiles_from_regs(const d4 (&X)[NBM], const d4
   if (todo) load_m(__builtin_ctz(todo), nxt);
   for (int p = 0; p < nph; ++p) {
     XTRP(8 + 3 * p);
-    if (XIVO_ABL == 9) lds_barrier();
-    else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     XTRP(9 + 3 * p);
     __syncthreads();                               // phase p landed for every wave; the other buffer is free again
-    }
     XTRP(10 + 3 * p);
     XTR2(p, 0);
     int tslot = 2;
     const int jb0 = p * jbp;
     const double* buf = sL + (p & 1) * bufsz;
-    if (FIXUP && XIVO_ABL != 3) {
+    if (FIXUP) {
       if (live && w >= jb0 && w < jb0 + min(jbp, nwl - jb0)) {
         double* dst = sL + (p & 1) * bufsz + (w - jb0) * nb * 256 + lane;
 #pragma unroll
@@ -173,9 +160,7 @@ __device__ __forceinline__ void sym_tiles_from_regs(const d4 (&X)[NBM], const d4
       if (fetch) { asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3])); issue(p + 1); fetch = false; }
       if (todo) load_m(jb0 + __builtin_ctz(todo), nxt);
       const double* Bop = buf + jl * nb * 256 + lane;
-      if (XIVO_ABL == 11) {   // the product phase's memory traffic alone: tile loads, operand DMA, stores - no MFMA (one LDS read per tile)
-        acc[0] += 0.0 * Bop[0];   // (P+ = P: every step of the timing loop sees the same, factorisable, covariance)
-      } else if (jb <= w) {
+      if (jb <= w) {
 #pragma unroll
         for (int mb = 0; mb < NBM; ++mb) {
           if (mb < nb) {
@@ -198,7 +183,7 @@ __device__ __forceinline__ void sym_tiles_from_regs(const d4 (&X)[NBM], const d4
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int bb = b + 4 * r;
-        if ((jb != w || a >= bb) && !(XIVO_ABL == 4 && acc[r] != 12345.678)) {   // diagonal tile: the lower triangle is authoritative
+        if (jb != w || a >= bb) {   // diagonal tile: the lower triangle is authoritative
           const double v = NEG_OUT ? -acc[r] : acc[r];
           buf_st_out(v, rO, vO, (unsigned)(16 * ba + (16 * bbk + 4 * r) * ldo) * 8u);
           if (a != bb) buf_st_out(v, rO, vOt, (unsigned)(16 * bbk + 4 * r + 16 * ba * ldo) * 8u);
@@ -361,7 +346,7 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
   // forward: L Y = HP
 #pragma unroll
   for (int k = 0; k < NBM; ++k) {
-    if (k < nb && !(T4 && (XIVO_ABL == 2 || XIVO_ABL == 11))) {
+    if (k < nb) {
       const double* Dk = sL + (k * (k + 1) / 2 + k) * BLK;
       d4 t = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -389,7 +374,7 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
 #pragma unroll
     for (int i = 0; i < NBM; ++i) Wk[i] = X[i];
   }
-  if (T4 && !KEEPW && XIVO_ABL != 6) {
+  if (T4 && !KEEPW) {
     // the forward-substituted columns W^T = (L^-1 H P)^T leave for the stash (the K buffer: the gain itself is never
     // stored by this variant) - the backward substitution below destroys them and the covariance update needs them again
 #pragma unroll
@@ -404,7 +389,7 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
   // backward: L^T K^T = Y
 #pragma unroll
   for (int k = NBM - 1; k >= 0; --k) {
-    if (k < nb && !g.fwd_only && !(T4 && (XIVO_ABL == 2 || XIVO_ABL == 11))) {
+    if (k < nb && !g.fwd_only) {
       const double* Dk = sL + (k * (k + 1) / 2 + k) * BLK;
       // TF == 4: W_k comes back from the stash while this step's MFMAs run (requested here, used at the end of the step;
       // the last block row has not been touched yet: it is still in X)
@@ -412,7 +397,7 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
       if (KEEPW) wk = Wk[k];
       else if (T4) {
         if (k == nb - 1) wk = X[k];
-        else if (XIVO_ABL != 6) {
+        else {
 #pragma unroll
           for (int r = 0; r < 4; ++r) wk[r] = buf_ld(rK, vK, (unsigned)((16 * k + 4 * r) * g.ldk) * 8u);
         }
@@ -441,7 +426,7 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
           }
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) part = fma(t[r], XIVO_ABL == 5 ? 1.0 : buf_ld(rInn, (unsigned)lg * 8u, (unsigned)(16 * k + 4 * r) * 8u), part);
+        for (int r = 0; r < 4; ++r) part = fma(t[r], buf_ld(rInn, (unsigned)lg * 8u, (unsigned)(16 * k + 4 * r) * 8u), part);
       } else {
         X[k] = t;
       }
@@ -510,7 +495,6 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
     }
     // ---- P+ = P - (W - D)^T (W + D) in place: W arrives from the stash by DMA, the owner waves turn it into W + D
     if (g.skip_status && g.skip_status[filt] != 0) return;   // S not positive definite: P stays the prior
-    if (XIVO_ABL == 1) return;
     double* Pio = g.T + (long)filt * g.strideT;
     if constexpr (KEEPW) sym_tiles_from_regs<NBM, true, true, false, true, NWV>(X, Wk, sL, nullptr, 0, Pio, g.ldt, Pio, g.ldt, nb, g.Np / 16, g.t_jbp,
                                                                  live, c0 >> 4, wave, lane);
