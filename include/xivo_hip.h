@@ -468,6 +468,48 @@ int xivo_hip_subfilter_update(xivo_hip_ctx* ctx, int b0, int nb, int n, xivo_sub
 int xivo_hip_candidate_order(const xivo_subfilter_feat* feats, int nb, int n, int strict, int score_type,
                              int* order_out, int* n_out, double* score_out);
 
+/* ---- resident out-of-state feature pool: the reference's life cycle of a new track (src/manager.cpp:18-130) ----
+ * Per filter, a pool of `pool_max` entries - features that are tracked but not in the state yet, each running the depth
+ * sub-filter above - and a table of `anchor_max` anchors, the groups those features are anchored to (Group::Create from
+ * the frame's pose, src/manager.cpp:121-126). An anchor is either linked to an in-state group slot (its pose is then that
+ * slot's resident pose) or unlinked with a frozen pose of its own (a group that is not, or no longer, in the state). The
+ * entries' data never leave the device; only the selection order (and which entries are still live) comes back.
+ * pool_max <= XIVO_POOL_MAX_ENTRIES (the per-filter ordering sorts in one workgroup's LDS), else XIVO_HIP_ERR_UNSUPPORTED.
+ * Calling xivo_hip_pool_config again re-allocates and empties everything. */
+#define XIVO_POOL_MAX_ENTRIES 512
+int xivo_hip_pool_config(xivo_hip_ctx* ctx, int pool_max, int anchor_max, const xivo_subfilter_opts* opts,
+                         double remove_outlier_counter);
+/* Group::Create(X_.Rsb, X_.Tsb): anchor slot[b] of filter b0 + b <- that filter's current resident pose, unlinked */
+int xivo_hip_pool_anchor(xivo_hip_ctx* ctx, int b0, int nb, const int* slot /* nb; -1 = none for that filter */);
+/* Feature::Initialize (src/feature.cpp:144-160) of new tracks: x = (UnProject(xp), log z0) - 1 / z0 under
+ * XIVO_HIP_FLAG_INVDEPTH -, P = diag(std_xyz)^2, status INITIALIZING, counters 0, anchored at `anchor`. Camera::UnProject
+ * runs on the device for every model (common/camera_{pinhole,atan,radtan,equidist}.h; radtan / equidistant with the
+ * reference's default max_iter = 15 iterations and no early exit), with the filter's own intrinsics when the context has
+ * camera calibration on (cam_dim > 0). Records of one call must name distinct (b, entry) pairs. */
+typedef struct {
+  int b;              /* filter */
+  int entry;          /* pool entry (overwritten if live) */
+  int anchor;         /* anchor the feature is anchored to */
+  int reserved;
+  double xp[2];       /* first pixel (Feature::back()) */
+  double z0;          /* initial depth (initial_z, or the simulator's depth) */
+  double std_xyz[3];  /* initial std of (x, y, depth coordinate) */
+} xivo_pool_new;
+int xivo_hip_pool_add(xivo_hip_ctx* ctx, int n, const xivo_pool_new* recs);
+/* The out-of-state branch of ProcessTracks (src/manager.cpp:171-250) for every live entry of filters [0, B):
+ * xp [B][pool_max][2] is the frame's pixel of each entry; NaN = the track was dropped: the entry is freed. Otherwise
+ * Feature::SubfilterUpdate against the current pose and the anchor's pose (same device code and arithmetic as
+ * xivo_hip_subfilter_update), then outlier_counter > remove_outlier_counter frees the entry. Then Criteria::Candidate
+ * (strict = 0) / CandidateStrict (strict = 1) and the CandidateComparison order of the passing entries, exactly as
+ * xivo_hip_candidate_order returns it for the pool as one [B x pool_max] array: order_out [B][pool_max] (entry indices, best
+ * first, padded with -1), n_out [B], live_out [B][pool_max] (1 = entry still live). */
+int xivo_hip_pool_step(xivo_hip_ctx* ctx, int B, const double* xp, int strict, int* order_out, int* n_out,
+                       unsigned char* live_out);
+/* download the pool / anchors of filters [b0, b0 + nb) (tests, diagnostics): entries as xivo_subfilter_feat with ref_sind =
+ * the entry's anchor (-1: free entry); anchors as their frozen pose and linked slot (-1: unlinked). Either pointer may be NULL. */
+int xivo_hip_pool_get(xivo_hip_ctx* ctx, int b0, int nb, xivo_subfilter_feat* entries /* nb x pool_max */,
+                      xivo_group_in* anchor_poses /* nb x anchor_max */, int* anchor_slots /* nb x anchor_max */);
+
 /* ---- Estimator::Propagate on the device-resident state ----
  * For filters [b0, b0 + nb): integrates the nominal motion state (Rsb, Tsb, Vsb, bg, ba, Rsg of the resident
  * xivo_pose_in, xivo_hip_set_scene) over dt with RK4Step (src/rk4.cpp:35-103) or PrinceDormandStep
@@ -554,7 +596,16 @@ enum {
    * and the entry becomes absent (sind = -1) */
   XIVO_EDIT_REMOVE_FEATURE = 6,
   /* new tracked pixel of the feature at position i0 (Feature::back()), v[0..1] = xp */
-  XIVO_EDIT_SET_XP = 7
+  XIVO_EDIT_SET_XP = 7,
+  /* feature pool (xivo_hip_pool_config): AddGroupToState (src/estimator.cpp:801-816) of the group behind anchor i1 into
+   * group slot i0 - the group keeps its own creation pose (the anchor's), P rows then columns of the slot <- those of Wsb,
+   * then of Tsb; the anchor is linked to the slot. XIVO_EDIT_REMOVE_GROUP of a slot an anchor links to first copies the
+   * slot's resident pose into the anchor and unlinks it (the Group outlives its slot with its last pose). */
+  XIVO_EDIT_ADD_GROUP_ANCHOR = 8,
+  /* feature pool: AddFeatureToState + FillCovarianceBlock (as XIVO_EDIT_ADD_FEATURE) from pool entry i2's x / P / xp, at list
+   * position i0 and feature slot i1, anchored at the slot its anchor links to; the entry is freed. The launch fails
+   * (XIVO_HIP_ERR_INVALID) if the anchor is unlinked at that point of the op list. */
+  XIVO_EDIT_ADMIT_POOL = 9
 };
 typedef struct {
   int b;             /* filter */

@@ -4,7 +4,8 @@
 // (/root/reference/common/camera_pinhole.h:17-37, camera_equidist.h:23-95,
 // camera_radtan.h:23-90, camera_atan.h:22-67) behind the dispatcher
 // CameraManager::Project (/root/reference/src/camera_manager.h:33-49).
-// camera_project: xp and jac = d(xp)/d(xc). camera_project_jacc: additionally the intrinsics Jacobian `jacc` of the
+// camera_project: xp and jac = d(xp)/d(xc). camera_unproject: the UnProject() members (camera_pinhole.h:39-53,
+// camera_atan.h:94-128, camera_radtan.h:100-168, camera_equidist.h:97-160) - xc only, Jacobians are not needed. camera_project_jacc: additionally the intrinsics Jacobian `jacc` of the
 // USE_ONLINE_CAMERA_CALIB builds (camera_pinhole.h:31-35, camera_atan.h:62-91, camera_radtan.h:78-96,
 // camera_equidist.h:80-94), parameter order as each model's comment states it.
 #pragma once
@@ -138,6 +139,72 @@ XIVO_HD int camera_project_jacc(const xivo_cam& c, double x, double y, double xp
     const double df_dw = df_dinvw * dinvw_dw + df_datanw2R * datanw2R_dw2R * dw2R_dw2 * dw2_dw;
     jacc[0][4] = fx * x * df_dw; jacc[1][4] = fy * y * df_dw;
     return 5;
+  }
+}
+
+// Camera::UnProject, pixel xp -> normalised camera coordinates xc, in each reference model's arithmetic order. Radtan and
+// equidistant iterate as the reference does: a fixed kUnprojectIter steps (max_iter, the constructors' default,
+// camera_radtan.h:16, camera_equidist.h:18; src/camera_manager.cpp:31), no early exit.
+constexpr int kUnprojectIter = 15;
+XIVO_HD void camera_unproject(const xivo_cam& c, double u, double v, double xc[2]) {
+  const double fx = c.fx, fy = c.fy, cx = c.cx, cy = c.cy;
+  if (c.model == XIVO_CAM_PINHOLE) {
+    xc[0] = (u - cx) / fx;
+    xc[1] = (v - cy) / fy;
+  } else if (c.model == XIVO_CAM_ATAN) {
+    const double w = c.d[0], w2 = 2.0 * tan(w * 0.5);
+    const double t0 = (u - cx) / fx, t1 = (v - cy) / fy;
+    const double R = sqrt(t0 * t0 + t1 * t1);
+    const double RR = w == 0 ? R : tan(R * w) / w2;
+    const double f = R > 0.01 ? RR / R : 1.0;
+    xc[0] = f * t0;
+    xc[1] = f * t1;
+  } else if (c.model == XIVO_CAM_RADTAN) {
+    // Newton's method on distort(xc) = xk from xc = xk
+    const double p1 = c.d[0], p2 = c.d[1], k1 = c.d[2], k2 = c.d[3], k3 = c.d[4];
+    const double xk0 = (u - cx) / fx, xk1 = (v - cy) / fy;
+    double x = xk0, y = xk1;
+    for (int i = 0; i < kUnprojectIter; ++i) {
+      const double t2 = x * x, t3 = y * y;
+      const double t4 = k1 * x * 2.0, t5 = k1 * y * 2.0, t6 = p1 * x * 2.0, t7 = p2 * y * 2.0;
+      const double t8 = t2 + t3, t9 = t8 * t8, t10 = t8 * t8 * t8, t11 = k1 * t8;
+      const double t14 = k2 * t8 * x * 4.0, t15 = k2 * t8 * y * 4.0;
+      const double t12 = k2 * t9, t13 = k3 * t10;
+      const double t16 = k3 * t9 * x * 6.0, t17 = k3 * t9 * y * 6.0;
+      const double t18 = t4 + t14 + t16, t19 = t5 + t15 + t17, t20 = t11 + t12 + t13 + 1.0;
+      const double xkk = t20 * x + t6 * y + p2 * (t2 * 2.0 + t8);
+      const double ykk = t7 * x + t20 * y + p1 * (t3 * 2.0 + t8);
+      const double g00 = t20 + p2 * x * 6.0 + p1 * y * 2.0 + t18 * x, g01 = t6 + t7 + t19 * x;
+      const double g10 = t6 + t7 + t18 * y, g11 = t20 + p2 * x * 2.0 + p1 * y * 6.0 + t19 * y;
+      const double f0 = xkk - xk0, f1 = ykk - xk1;
+      // Eigen's 2x2 inverse (adjugate times 1 / determinant), then xc - inv * f
+      const double idet = 1.0 / (g00 * g11 - g10 * g01);
+      const double i00 = g11 * idet, i10 = -g10 * idet, i01 = -g01 * idet, i11 = g00 * idet;
+      const double d0 = i00 * f0 + i01 * f1, d1 = i10 * f0 + i11 * f1;
+      x = x - d0;
+      y = y - d1;
+    }
+    xc[0] = x;
+    xc[1] = y;
+  } else {  // XIVO_CAM_EQUI: Newton steps on (r(th) - rth)^2, r(th) = th + k0 th^3 + k1 th^5 + k2 th^7 + k3 th^9
+    const double k0 = c.d[0], k1 = c.d[1], k2 = c.d[2], k3 = c.d[3];
+    const double xn = u - cx, yn = v - cy;
+    const double b = fx * yn, a = fy * xn;
+    const double phi = atan2(b, a);
+    const double cos_phi = cos(phi), sin_phi = sin(phi);
+    const double rth = xn / (fx * cos_phi);
+    double th = rth;
+    for (int i = 0; i < kUnprojectIter; ++i) {
+      const double th2 = th * th, th3 = th2 * th, th4 = th2 * th2, th6 = th4 * th2;
+      const double x0 = k0 * th3 + k1 * th4 * th + k2 * th6 * th + k3 * th6 * th3 - rth + th;
+      const double x1 = 3 * k0 * th2 + 5 * k1 * th4 + 7 * k2 * th6 + 9 * k3 * th6 * th2 + 1;
+      const double d = 2 * x0 * x1;
+      const double d2 = 4 * th * x0 * (3 * k0 + 10 * k1 * th2 + 21 * k2 * th4 + 36 * k3 * th6) + 2 * x1 * x1;
+      th -= d / d2;
+    }
+    const double tan_th = tan(th);
+    xc[0] = tan_th * cos_phi;
+    xc[1] = tan_th * sin_phi;
   }
 }
 

@@ -688,6 +688,143 @@ int xivo_hip_candidate_order(const xivo_subfilter_feat* feats, int nb, int n, in
   return XIVO_HIP_OK;
 }
 
+// ---- out-of-state feature pool
+static int ensure_pool_io(xivo_hip_ctx* c, size_t bytes) {
+  if (bytes <= c->pool_io_cap) return XIVO_HIP_OK;
+  if (c->pool_io) hipFree(c->pool_io);
+  c->pool_io = nullptr; c->pool_io_cap = 0;
+  if (hipMalloc(&c->pool_io, bytes) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
+  c->pool_io_cap = bytes;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pool_config(xivo_hip_ctx* c, int pool_max, int anchor_max, const xivo_subfilter_opts* opts,
+                         double remove_outlier_counter) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || pool_max < 1 || anchor_max < 1 || !opts) return XIVO_HIP_ERR_INVALID;
+  if (pool_max > XIVO_POOL_MAX_ENTRIES) return XIVO_HIP_ERR_UNSUPPORTED;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->fpool) hipFree(c->fpool);
+  if (c->anchors) hipFree(c->anchors);
+  c->fpool = nullptr; c->anchors = nullptr; c->pool_max = c->anchor_max = 0;
+  const size_t ne = (size_t)c->Bmax * pool_max, na = (size_t)c->Bmax * anchor_max;
+  if (hipMalloc((void**)&c->fpool, ne * sizeof(xivo_subfilter_feat)) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
+  if (hipMalloc((void**)&c->anchors, na * sizeof(PoolAnchor)) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
+  // all bytes 0xff: every entry's anchor (ref_sind) and every anchor's slot read -1 - free / unlinked
+  HIP_TRY(hipMemsetAsync(c->fpool, 0xff, ne * sizeof(xivo_subfilter_feat), c->stream));
+  HIP_TRY(hipMemsetAsync(c->anchors, 0xff, na * sizeof(PoolAnchor), c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->pool_anchor_h.assign(ne, -1);
+  c->anchor_link_h.assign(na, -2);   // -2: never created (xivo_hip_pool_anchor), -1: unlinked, >= 0: linked slot
+  c->pool_max = pool_max; c->anchor_max = anchor_max;
+  c->pool_opts = *opts; c->pool_remove_outlier = remove_outlier_counter;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pool_anchor(xivo_hip_ctx* c, int b0, int nb, const int* slot) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->fpool || !c->poses || (nb > 0 && !slot)) return XIVO_HIP_ERR_INVALID;
+  for (int b = 0; b < nb; ++b) {
+    if (slot[b] < -1 || slot[b] >= c->anchor_max) return XIVO_HIP_ERR_INVALID;
+    if (slot[b] >= 0 && c->anchor_link_h[(size_t)(b0 + b) * c->anchor_max + slot[b]] >= 0) return XIVO_HIP_ERR_INVALID;   // linked
+  }
+  if (nb == 0) return XIVO_HIP_OK;
+  int rc = ensure_pool_io(c, (size_t)nb * sizeof(int));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(c->pool_io, slot, (size_t)nb * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "pool_anchor_kernel");
+    HIP_TRY((hipError_t)launch_pool_anchor(c->anchors + (size_t)b0 * c->anchor_max, c->anchor_max, c->poses + b0,
+                                           (const int*)c->pool_io, nb, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));   // slot is borrowed host memory
+  for (int b = 0; b < nb; ++b)
+    if (slot[b] >= 0) c->anchor_link_h[(size_t)(b0 + b) * c->anchor_max + slot[b]] = -1;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pool_add(xivo_hip_ctx* c, int n, const xivo_pool_new* recs) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !c->fpool || !c->have_layout || n < 0 || (n > 0 && !recs)) return XIVO_HIP_ERR_INVALID;
+  std::vector<long> keys((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const xivo_pool_new& r = recs[i];
+    if (r.b < 0 || r.b >= c->Bmax || r.entry < 0 || r.entry >= c->pool_max || r.anchor < 0 || r.anchor >= c->anchor_max ||
+        c->anchor_link_h[(size_t)r.b * c->anchor_max + r.anchor] == -2 || !(r.z0 > 0.0))
+      return XIVO_HIP_ERR_INVALID;
+    keys[i] = (long)r.b * c->pool_max + r.entry;
+  }
+  std::sort(keys.begin(), keys.end());
+  if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return XIVO_HIP_ERR_INVALID;   // one record per entry
+  if (n == 0) return XIVO_HIP_OK;
+  int rc = ensure_pool_io(c, (size_t)n * sizeof(xivo_pool_new));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(c->pool_io, recs, (size_t)n * sizeof(xivo_pool_new), hipMemcpyHostToDevice, c->stream));
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "pool_add_kernel");
+    HIP_TRY((hipError_t)launch_pool_add(c->fpool, c->pool_max, (const xivo_pool_new*)c->pool_io, n, c->cam,
+                                        c->calib_on ? c->calib : nullptr, c->calib_on ? c->cl.cam_dim : 0,
+                                        (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));   // recs is borrowed host memory
+  for (int i = 0; i < n; ++i) c->pool_anchor_h[(size_t)recs[i].b * c->pool_max + recs[i].entry] = recs[i].anchor;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pool_step(xivo_hip_ctx* c, int B, const double* xp, int strict, int* order_out, int* n_out,
+                       unsigned char* live_out) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !c->fpool || !c->have_layout || !c->poses || B <= 0 || B > c->Bmax || !xp || !order_out || !n_out || !live_out)
+    return XIVO_HIP_ERR_INVALID;
+  const size_t ne = (size_t)B * c->pool_max;
+  const size_t b_xp = ne * 2 * sizeof(double), b_ord = ne * sizeof(int), b_n = (size_t)B * sizeof(int);
+  int rc = ensure_pool_io(c, b_xp + b_ord + b_n + ne);
+  if (rc) return rc;
+  char* io = (char*)c->pool_io;
+  PoolStepArgs a{};
+  a.pool = c->fpool; a.anchors = c->anchors; a.pool_max = c->pool_max; a.anchor_max = c->anchor_max;
+  a.poses = c->poses; a.groups = c->groups; a.n_groups = c->lay.n_groups;
+  a.cam = c->cam; a.calib = c->calib_on ? c->calib : nullptr; a.cam_dim = c->calib_on ? c->cl.cam_dim : 0;
+  a.invdepth = (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0;
+  a.o = c->pool_opts; a.remove_outlier = c->pool_remove_outlier; a.strict = strict ? 1 : 0; a.batch = B;
+  a.xp = (const double*)io; a.order = (int*)(io + b_xp); a.n = (int*)(io + b_xp + b_ord);
+  a.live = (unsigned char*)(io + b_xp + b_ord + b_n);
+  HIP_TRY(hipMemcpyAsync(io, xp, b_xp, hipMemcpyHostToDevice, c->stream));
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "pool_step_kernel");
+    HIP_TRY((hipError_t)launch_pool_step(a, c->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(order_out, a.order, b_ord, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(n_out, a.n, b_n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(live_out, a.live, ne, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < ne; ++i)
+    if (!live_out[i]) c->pool_anchor_h[i] = -1;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pool_get(xivo_hip_ctx* c, int b0, int nb, xivo_subfilter_feat* entries, xivo_group_in* anchor_poses,
+                      int* anchor_slots) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->fpool) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  if (entries)
+    HIP_TRY(hipMemcpyAsync(entries, c->fpool + (size_t)b0 * c->pool_max, (size_t)nb * c->pool_max * sizeof(xivo_subfilter_feat),
+                           hipMemcpyDeviceToHost, c->stream));
+  std::vector<PoolAnchor> anc;
+  if (anchor_poses || anchor_slots) {
+    anc.resize((size_t)nb * c->anchor_max);
+    HIP_TRY(hipMemcpyAsync(anc.data(), c->anchors + (size_t)b0 * c->anchor_max, anc.size() * sizeof(PoolAnchor),
+                           hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < anc.size(); ++i) {
+    if (anchor_poses) anchor_poses[i] = anc[i].g;
+    if (anchor_slots) anchor_slots[i] = anc[i].slot;
+  }
+  return XIVO_HIP_OK;
+}
+
 int xivo_hip_absorb_error(xivo_hip_ctx* c, int B) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0 || !c->mask) return XIVO_HIP_ERR_INVALID;
@@ -707,9 +844,13 @@ int xivo_hip_edit_batch(xivo_hip_ctx* c, int F, int n_ops, const xivo_edit_op* o
   if (rc) return rc;
   const xivo_layout& L = c->lay;
   std::vector<int> wg_filter, wg_begin;
+  std::vector<std::pair<int*, int>> undo;
   for (int o = 0; o < n_ops; ++o) {
     const xivo_edit_op& e = ops[o];
-    if (e.b < 0 || e.b >= c->Bmax || (o > 0 && e.b < ops[o - 1].b)) return XIVO_HIP_ERR_INVALID;
+    if (e.b < 0 || e.b >= c->Bmax || (o > 0 && e.b < ops[o - 1].b)) {
+      for (size_t k = undo.size(); k-- > 0;) *undo[k].first = undo[k].second;
+      return XIVO_HIP_ERR_INVALID;
+    }
     bool ok = false;
     switch (e.kind) {
       case XIVO_EDIT_P_ZERO_RC: ok = e.i0 >= 0 && e.i1 >= 0 && e.i0 + e.i1 <= c->N; break;
@@ -719,9 +860,34 @@ int xivo_hip_edit_batch(xivo_hip_ctx* c, int F, int n_ops, const xivo_edit_op* o
       case XIVO_EDIT_ADD_FEATURE:
         ok = e.i0 >= 0 && e.i0 < F && e.i1 >= 0 && e.i1 < L.n_features && e.i2 >= 0 && e.i2 < L.n_groups; break;
       case XIVO_EDIT_REMOVE_FEATURE: case XIVO_EDIT_SET_XP: ok = e.i0 >= 0 && e.i0 < F; break;
+      case XIVO_EDIT_ADD_GROUP_ANCHOR:
+        ok = c->fpool && e.i0 >= 0 && e.i0 < L.n_groups && e.i1 >= 0 && e.i1 < c->anchor_max &&
+             c->anchor_link_h[(size_t)e.b * c->anchor_max + e.i1] == -1;
+        for (int k = 0; ok && k < c->anchor_max; ++k) ok = c->anchor_link_h[(size_t)e.b * c->anchor_max + k] != e.i0;
+        break;
+      case XIVO_EDIT_ADMIT_POOL:
+        ok = c->fpool && e.i0 >= 0 && e.i0 < F && e.i1 >= 0 && e.i1 < L.n_features && e.i2 >= 0 && e.i2 < c->pool_max;
+        if (ok) {
+          const int anc = c->pool_anchor_h[(size_t)e.b * c->pool_max + e.i2];
+          ok = anc >= 0 && c->anchor_link_h[(size_t)e.b * c->anchor_max + anc] >= 0;
+        }
+        break;
       default: ok = false;
     }
-    if (!ok) return XIVO_HIP_ERR_INVALID;
+    // the pool's host mirrors follow the ops in order (an op may rely on a link an earlier op of the call makes); undone
+    // when a later op is rejected
+    if (ok && c->fpool) {
+      auto set = [&](int& slot, int v) { undo.emplace_back(&slot, slot); slot = v; };
+      if (e.kind == XIVO_EDIT_ADD_GROUP_ANCHOR) set(c->anchor_link_h[(size_t)e.b * c->anchor_max + e.i1], e.i0);
+      if (e.kind == XIVO_EDIT_REMOVE_GROUP)
+        for (int k = 0; k < c->anchor_max; ++k)
+          if (c->anchor_link_h[(size_t)e.b * c->anchor_max + k] == e.i0) set(c->anchor_link_h[(size_t)e.b * c->anchor_max + k], -1);
+      if (e.kind == XIVO_EDIT_ADMIT_POOL) set(c->pool_anchor_h[(size_t)e.b * c->pool_max + e.i2], -1);
+    }
+    if (!ok) {
+      for (size_t k = undo.size(); k-- > 0;) *undo[k].first = undo[k].second;
+      return XIVO_HIP_ERR_INVALID;
+    }
     if (o == 0 || e.b != ops[o - 1].b) { wg_filter.push_back(e.b); wg_begin.push_back(o); }
   }
   c->F = F;
@@ -746,6 +912,7 @@ int xivo_hip_edit_batch(xivo_hip_ctx* c, int F, int n_ops, const xivo_edit_op* o
   a.ops = (const xivo_edit_op*)d; a.wg_filter = (const int*)(d + bytes_ops); a.wg_begin = a.wg_filter + n_wg;
   a.P = c->P; a.strideP = c->sP; a.ldp = c->Np; a.Np = c->Np; a.lay = L;
   a.poses = c->poses; a.groups = c->groups; a.feats = c->feats; a.Fmax = c->Fmax;
+  a.pool = c->fpool; a.anchors = c->anchors; a.pool_max = c->pool_max; a.anchor_max = c->anchor_max;
   {
     StageTimer st(c, ST_OTHER, 0.0, "edit_batch_kernel");
     HIP_TRY((hipError_t)launch_edit_batch(a, n_wg, c->stream));

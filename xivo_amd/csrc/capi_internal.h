@@ -103,6 +103,16 @@ struct xivo_hip_ctx {
   double* Hlead = nullptr; bool lead_valid = false;
   void* lc_buf = nullptr; size_t lc_cap = 0;   // xivo_hip_close_loop_stack: matches | dense rows | inn | diagR
   xivo_subfilter_feat* sub = nullptr;   // staging of xivo_hip_subfilter_update
+  // out-of-state feature pool (xivo_hip_pool_*): entries [Bmax][pool_max] (ref_sind = the entry's anchor, -1: free), anchors
+  // [Bmax][anchor_max]; host mirrors of who is live / linked, which validate pool_add and the pool's edit kinds
+  int pool_max = 0, anchor_max = 0;
+  xivo_subfilter_opts pool_opts{};
+  double pool_remove_outlier = 0.0;
+  xivo_subfilter_feat* fpool = nullptr;
+  xivo_hip::PoolAnchor* anchors = nullptr;
+  void* pool_io = nullptr; size_t pool_io_cap = 0;   // per-call device staging: records / pixels in, order / counts / live out
+  std::vector<int> pool_anchor_h;   // [Bmax][pool_max]: anchor of a live entry, -1 = free
+  std::vector<int> anchor_link_h;   // [Bmax][anchor_max]: linked group slot, -1 = unlinked
   std::vector<char> hstage;                        // host staging of d2h_rows
   void* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
   // one-filter plumbing call (xivo_hip_update_joseph_host): page-locked, device-mapped staging block owned by the context,

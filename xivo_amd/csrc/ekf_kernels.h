@@ -114,6 +114,26 @@ int launch_subfilter(xivo_subfilter_feat* feats, int n, const xivo_pose_in* pose
                      int n_groups, xivo_cam cam, xivo_subfilter_opts o, int batch, hipStream_t s,
                      const xivo_calib_in* calib = nullptr, int cam_dim = 0, int invdepth = 0);
 
+// One anchor of the out-of-state feature pool (xivo_hip_pool_config): the frozen pose of its group and the in-state group slot
+// it is linked to (-1: unlinked, the frozen pose is the anchor's pose)
+struct PoolAnchor {
+  xivo_group_in g;
+  int slot, reserved;
+};
+// Out-of-state feature pool (xivo_hip_pool_*): entries are xivo_subfilter_feat with ref_sind = the entry's anchor (-1: free)
+int launch_pool_anchor(PoolAnchor* anchors, int anchor_max, const xivo_pose_in* poses, const int* slot, int nb, hipStream_t s);
+int launch_pool_add(xivo_subfilter_feat* pool, int pool_max, const xivo_pool_new* recs, int n, xivo_cam cam,
+                    const xivo_calib_in* calib, int cam_dim, int invdepth, hipStream_t s);
+struct PoolStepArgs {
+  xivo_subfilter_feat* pool; const PoolAnchor* anchors; int pool_max, anchor_max;   // [batch][pool_max] / [batch][anchor_max]
+  const xivo_pose_in* poses; const xivo_group_in* groups; int n_groups;
+  xivo_cam cam; const xivo_calib_in* calib; int cam_dim, invdepth;
+  xivo_subfilter_opts o; double remove_outlier; int strict, batch;
+  const double* xp;                                  // [batch][pool_max][2]
+  int* order; int* n; unsigned char* live;           // out: [batch][pool_max], [batch], [batch][pool_max]
+};
+int launch_pool_step(const PoolStepArgs& a, hipStream_t s);
+
 // Estimator::Propagate state + covariance stages (rk4.cpp, princedormand.cpp, estimator.cpp:598-704): one wave per
 // filter; writes the accumulated transition Phi and the new P_mm (23 x 23 each, column-major) for the tail kernel
 struct PropStateArgs {
@@ -176,6 +196,7 @@ struct EditArgs {
   const xivo_edit_op* ops; const int* wg_filter; const int* wg_begin;
   double* P; long strideP; int ldp, Np; xivo_layout lay;
   xivo_pose_in* poses; xivo_group_in* groups; xivo_feat_in* feats; int Fmax;
+  xivo_subfilter_feat* pool; PoolAnchor* anchors; int pool_max, anchor_max;   // null / 0: no pool configured
 };
 int launch_edit_batch(const EditArgs& a, int n_wg, hipStream_t s);
 int launch_set_pixels(xivo_feat_in* feats /* already offset to b0 */, int Fmax, int F, const double* xp, int nb, hipStream_t s);

@@ -749,18 +749,11 @@ __global__ __launch_bounds__(256) void stack_kernel(StackArgs a) {
 }
 
 // ---------------------------------------------------------------- depth sub-filter
-// One thread per (filter, feature): every product below is 3x3 / 2x3 / 2x2 and is written in the
-// reference's association order (feature.cpp:246-297).
-__global__ void subfilter_kernel(xivo_subfilter_feat* feats, int n, const xivo_pose_in* poses,
-                                 const xivo_group_in* groups, int n_groups, xivo_cam cam_ctx, xivo_subfilter_opts o,
-                                 int batch, const xivo_calib_in* calib, int cam_dim, int invdepth) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= batch * n) return;
-  const int filt = t / n;
-  const xivo_cam cam = filter_cam(cam_ctx, calib, cam_dim, filt);
-  xivo_subfilter_feat& f = feats[t];
-  const xivo_pose_in& pose = poses[filt];
-  const xivo_group_in& grp = groups[(long)filt * n_groups + f.ref_sind];
+// Feature::SubfilterUpdate of one feature against the sensor pose and its anchor's pose, then Criteria::Candidate(Strict) and
+// Feature::score. Every product below is 3x3 / 2x3 / 2x2 and is written in the reference's association order
+// (feature.cpp:246-297). Shared by subfilter_kernel and pool_step_kernel, which must agree bit for bit.
+__device__ __forceinline__ void subfilter_step(xivo_subfilter_feat& f, const xivo_pose_in& pose, const xivo_group_in& grp,
+                                               const xivo_cam& cam, const xivo_subfilter_opts& o, int invdepth) {
   const M3 Rsb = m3_from_colmajor(pose.Rsb), Rbc = m3_from_colmajor(pose.Rbc), Rsbr = m3_from_colmajor(grp.Rsb);
   const V3 Tsb{{pose.Tsb[0], pose.Tsb[1], pose.Tsb[2]}}, Tbc{{pose.Tbc[0], pose.Tbc[1], pose.Tbc[2]}};
   const V3 Tsbr{{grp.Tsb[0], grp.Tsb[1], grp.Tsb[2]}};
@@ -851,6 +844,120 @@ __global__ void subfilter_kernel(xivo_subfilter_feat* feats, int n, const xivo_p
   const bool ok = outlier < o.max_subfilter_outlier && zed > o.min_depth && zed < o.max_depth;
   f.candidate = (ok ? 1 : 0) | ((ok && status == XIVO_FEAT_READY) ? 2 : 0);
   f.score = -Pn.m[2][2];
+}
+// One thread per (filter, feature)
+__global__ void subfilter_kernel(xivo_subfilter_feat* feats, int n, const xivo_pose_in* poses,
+                                 const xivo_group_in* groups, int n_groups, xivo_cam cam_ctx, xivo_subfilter_opts o,
+                                 int batch, const xivo_calib_in* calib, int cam_dim, int invdepth) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= batch * n) return;
+  const int filt = t / n;
+  const xivo_cam cam = filter_cam(cam_ctx, calib, cam_dim, filt);
+  xivo_subfilter_feat& f = feats[t];
+  subfilter_step(f, poses[filt], groups[(long)filt * n_groups + f.ref_sind], cam, o, invdepth);
+}
+
+// ---------------------------------------------------------------- out-of-state feature pool (xivo_hip_pool_*)
+// Group::Create(X_.Rsb, X_.Tsb): one thread per filter
+__global__ void pool_anchor_kernel(PoolAnchor* anchors, int anchor_max, const xivo_pose_in* poses, const int* slot, int nb) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= nb || slot[b] < 0) return;
+  PoolAnchor& A = anchors[(long)b * anchor_max + slot[b]];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) A.g.Rsb[i] = poses[b].Rsb[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) A.g.Tsb[i] = poses[b].Tsb[i];
+  A.slot = -1;
+}
+// Feature::Initialize (feature.cpp:144-160): one thread per new track
+__global__ void pool_add_kernel(xivo_subfilter_feat* pool, int pool_max, const xivo_pool_new* recs, int n, xivo_cam cam_ctx,
+                                const xivo_calib_in* calib, int cam_dim, int invdepth) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const xivo_pool_new& r = recs[t];
+  const xivo_cam cam = filter_cam(cam_ctx, calib, cam_dim, r.b);
+  xivo_subfilter_feat& f = pool[(long)r.b * pool_max + r.entry];
+  double xc[2];
+  camera_unproject(cam, r.xp[0], r.xp[1], xc);
+  f.x[0] = xc[0]; f.x[1] = xc[1];
+  f.x[2] = invdepth ? 1.0 / r.z0 : log(r.z0);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) f.P[i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) f.P[4 * i] = r.std_xyz[i] * r.std_xyz[i];   // P_ = diag(std); P_ *= P_
+  f.xp[0] = r.xp[0]; f.xp[1] = r.xp[1];
+  f.outlier_counter = 0.0; f.score = 0.0;
+  f.ref_sind = r.anchor; f.status = XIVO_FEAT_INITIALIZING; f.init_counter = 0; f.candidate = 0;
+}
+// The out-of-state branch of ProcessTracks (manager.cpp:171-250) and the candidate order, one workgroup per filter: its threads
+// take the entries (one thread per entry for pool_max <= 256), then sort the keys (rank, P(2,2), entry) in LDS by a bitonic
+// network over the next power of two >= pool_max. rank 2 = passing and READY, 1 = passing and INITIALIZING, 0 = not passing
+// (sorted last); best first = higher rank, then smaller P(2,2) (larger Feature::score), then the lower entry - the order
+// std::stable_sort gives xivo_hip_candidate_order.
+__device__ __forceinline__ bool pool_before(int ra, double pa, int ia, int rb, double pb, int ib) {
+  return ra > rb || (ra == rb && (pa < pb || (pa == pb && ia < ib)));
+}
+__global__ __launch_bounds__(256) void pool_step_kernel(PoolStepArgs a) {
+  __shared__ double key_p[XIVO_POOL_MAX_ENTRIES];
+  __shared__ int key_r[XIVO_POOL_MAX_ENTRIES], key_i[XIVO_POOL_MAX_ENTRIES];
+  __shared__ int n_pass;
+  const int filt = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, pm = a.pool_max;
+  int p2 = 1;
+  while (p2 < pm) p2 <<= 1;
+  if (tid == 0) n_pass = 0;
+  __syncthreads();
+  const xivo_cam cam = filter_cam(a.cam, a.calib, a.cam_dim, filt);
+  const xivo_pose_in& pose = a.poses[filt];
+  const int want = a.strict ? 2 : 1;
+  for (int e = tid; e < p2; e += nt) {
+    int rank = 0;
+    double p22 = 0.0;
+    if (e < pm) {
+      const long ent = (long)filt * pm + e;
+      xivo_subfilter_feat& f = a.pool[ent];
+      unsigned char live = 0;
+      if (f.ref_sind >= 0) {
+        const double u = a.xp[2 * ent], v = a.xp[2 * ent + 1];
+        if (u != u || v != v) {
+          f.ref_sind = -1;                                  // dropped by the tracker while out of state
+        } else {
+          f.xp[0] = u; f.xp[1] = v;
+          const PoolAnchor& A = a.anchors[(long)filt * a.anchor_max + f.ref_sind];
+          subfilter_step(f, pose, A.slot >= 0 ? a.groups[(long)filt * a.n_groups + A.slot] : A.g, cam, a.o, a.invdepth);
+          if (f.outlier_counter > a.remove_outlier) {
+            f.ref_sind = -1;                                // manager.cpp:236-240
+          } else {
+            live = 1;
+            if (f.candidate & want) {
+              rank = f.status == XIVO_FEAT_READY ? 2 : 1;
+              p22 = f.P[8];
+              atomicAdd(&n_pass, 1);
+            }
+          }
+        }
+      }
+      a.live[ent] = live;
+    }
+    key_r[e] = rank; key_p[e] = p22; key_i[e] = e;
+  }
+  __syncthreads();
+  for (int k = 2; k <= p2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (p2 >> 1); t += nt) {
+        const int i = 2 * j * (t / j) + (t % j), l = i + j;
+        const bool up = (i & k) == 0;   // this half of the bitonic sequence is sorted best first
+        if (pool_before(key_r[l], key_p[l], key_i[l], key_r[i], key_p[i], key_i[i]) == up) {
+          const int r = key_r[i], ix = key_i[i];
+          const double p = key_p[i];
+          key_r[i] = key_r[l]; key_p[i] = key_p[l]; key_i[i] = key_i[l];
+          key_r[l] = r; key_p[l] = p; key_i[l] = ix;
+        }
+      }
+      __syncthreads();
+    }
+  const int n = n_pass;
+  for (int e = tid; e < pm; e += nt) a.order[(long)filt * pm + e] = e < n ? key_i[e] : -1;
+  if (tid == 0) a.n[filt] = n;
 }
 
 // ---------------------------------------------------------------- Givens / QR
@@ -1050,7 +1157,14 @@ __global__ __launch_bounds__(256) void edit_batch_kernel(EditArgs a) {
         edit_copy_rc(P, a.ldp, a.Np, off + 3, 3, 3, tid);   // Index::Tsb
         break;
       }
-      case XIVO_EDIT_REMOVE_GROUP: edit_zero_rc(P, a.ldp, a.Np, a.lay.group_begin + 6 * op.i0, 6, tid); break;
+      case XIVO_EDIT_REMOVE_GROUP:
+        // an anchor linked to the slot keeps the group's last pose and becomes unlinked (no pool: anchor_max = 0)
+        for (int t = tid; t < a.anchor_max; t += 256) {
+          PoolAnchor& A = a.anchors[(long)filt * a.anchor_max + t];
+          if (A.slot == op.i0) { A.g = groups[op.i0]; A.slot = -1; }
+        }
+        edit_zero_rc(P, a.ldp, a.Np, a.lay.group_begin + 6 * op.i0, 6, tid);
+        break;
       case XIVO_EDIT_ADD_FEATURE: {
         if (tid == 0) {
           xivo_feat_in& f = feats[op.i0];
@@ -1078,6 +1192,35 @@ __global__ __launch_bounds__(256) void edit_batch_kernel(EditArgs a) {
         if (tid < 2) feats[op.i0].xp[tid] = op.v[tid];
         __syncthreads();
         break;
+      case XIVO_EDIT_ADD_GROUP_ANCHOR: {
+        PoolAnchor& A = a.anchors[(long)filt * a.anchor_max + op.i1];
+        if (tid < 9) groups[op.i0].Rsb[tid] = A.g.Rsb[tid];
+        else if (tid < 12) groups[op.i0].Tsb[tid - 9] = A.g.Tsb[tid - 9];
+        const int off = a.lay.group_begin + 6 * op.i0;
+        edit_copy_rc(P, a.ldp, a.Np, off, 0, 3, tid);       // Index::Wsb
+        edit_copy_rc(P, a.ldp, a.Np, off + 3, 3, 3, tid);   // Index::Tsb
+        if (tid == 0) A.slot = op.i0;
+        __syncthreads();
+        break;
+      }
+      case XIVO_EDIT_ADMIT_POOL: {
+        // as XIVO_EDIT_ADD_FEATURE with (x, xp, P) taken from the pool entry; the host checked that its anchor is linked
+        xivo_subfilter_feat& e = a.pool[(long)filt * a.pool_max + op.i2];
+        const int slot = a.anchors[(long)filt * a.anchor_max + e.ref_sind].slot;
+        const double pv = tid < 9 ? e.P[tid] : 0.0;
+        if (tid == 0) {
+          xivo_feat_in& f = feats[op.i0];
+          f.x[0] = e.x[0]; f.x[1] = e.x[1]; f.x[2] = e.x[2];
+          f.xp[0] = e.xp[0]; f.xp[1] = e.xp[1];
+          f.sind = op.i1; f.ref_sind = slot;
+        }
+        const int off = a.lay.feature_begin + 3 * op.i1;
+        edit_zero_rc(P, a.ldp, a.Np, off, 3, tid);
+        if (tid < 9) P[(off + tid % 3) + (long)(off + tid / 3) * a.ldp] = pv;
+        if (tid == 0) e.ref_sind = -1;
+        __syncthreads();
+        break;
+      }
       default: break;
     }
   }
@@ -2750,6 +2893,29 @@ int launch_subfilter(xivo_subfilter_feat* feats, int n, const xivo_pose_in* pose
   if (tot <= 0) return 0;
   hipLaunchKernelGGL(subfilter_kernel, dim3((tot + 127) / 128), dim3(128), 0, s, feats, n, poses, groups, n_groups, cam,
                      o, batch, calib, cam_dim, invdepth);
+  CHECK_LAUNCH();
+}
+int launch_pool_anchor(PoolAnchor* anchors, int anchor_max, const xivo_pose_in* poses, const int* slot, int nb, hipStream_t s) {
+  if (nb <= 0) return 0;
+  hipLaunchKernelGGL(pool_anchor_kernel, dim3((nb + 63) / 64), dim3(64), 0, s, anchors, anchor_max, poses, slot, nb);
+  CHECK_LAUNCH();
+}
+int launch_pool_add(xivo_subfilter_feat* pool, int pool_max, const xivo_pool_new* recs, int n, xivo_cam cam,
+                    const xivo_calib_in* calib, int cam_dim, int invdepth, hipStream_t s) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(pool_add_kernel, dim3((n + 127) / 128), dim3(128), 0, s, pool, pool_max, recs, n, cam, calib, cam_dim,
+                     invdepth);
+  CHECK_LAUNCH();
+}
+// threads per workgroup: one per entry up to 256, at least one wave
+int pool_step_threads(int pool_max) {
+  const int t = (pool_max + 63) / 64 * 64;
+  return t < 64 ? 64 : (t > 256 ? 256 : t);
+}
+int launch_pool_step(const PoolStepArgs& a, hipStream_t s) {
+  if (a.batch <= 0) return 0;
+  if (a.pool_max < 1 || a.pool_max > XIVO_POOL_MAX_ENTRIES) return 1;
+  hipLaunchKernelGGL(pool_step_kernel, dim3(a.batch), dim3(pool_step_threads(a.pool_max)), 0, s, a);
   CHECK_LAUNCH();
 }
 int launch_givens(const GivensArgs& a, hipStream_t s) {

@@ -124,7 +124,34 @@ void BatchEstimator::DiscardEmptyGroups(int b, std::vector<xivo_edit_op>& ops) {
     if (bk.group_refs[g] == 0) {
       ops.push_back(make_op(b, XIVO_EDIT_REMOVE_GROUP, g));
       bk.group_refs[g] = -1;
+      if (subfilter_)   // the device freezes the anchor of the group at its last pose
+        for (int& link : pools_[b].anc_link) if (link == g) link = -1;
     }
+}
+
+// FilterUpdate on the tracked in-state features of every filter, the inlier mask into mask_, then AbsorbError
+void BatchEstimator::RunUpdate() {
+  const int F = cfg_.n_features;
+  const double R = cfg_.visual_meas_std * cfg_.visual_meas_std;
+  if (cfg_.use_1pt_RANSAC) {
+    // Estimator::OutlierRejection with use_1pt_RANSAC (src/manager.cpp:629-650): MH gating, OnePointRANSAC on its inliers,
+    // the update on what it keeps. (No gauge group / previous-frame group list in this simplified life cycle.)
+    Check(xivo_hip_jacobians_instate(ctx_, B_), "jacobians_instate");
+    Check(xivo_hip_mh_gate(ctx_, B_, R, cfg_.MH_thresh, cfg_.MH_adjust_factor, cfg_.use_MH_gating ? cfg_.min_inliers : (1 << 30), nullptr, nullptr), "mh_gate");
+    Check(xivo_hip_one_point_ransac(ctx_, B_, R, cfg_.ransac_thresh, cfg_.ransac_Chi2, nullptr, nullptr, nullptr, nullptr, nullptr), "one_point_ransac");
+    Check(xivo_hip_stack(ctx_, B_, R), "stack");
+    Check(xivo_hip_update_joseph(ctx_, B_), "update_joseph");
+  } else {
+    Check(xivo_hip_filter_update(ctx_, B_, R, cfg_.MH_thresh, cfg_.MH_adjust_factor, cfg_.min_inliers, cfg_.use_MH_gating), "filter_update");
+  }
+  Check(xivo_hip_get_gate(ctx_, B_, F, mask_.data(), nullptr), "get_gate");
+  // a filter whose S was not positive definite keeps its prior P and absorbs nothing (the device skips both); it is
+  // counted and reported here - the reference's pivoted LDL^T cannot fail, so there is no reference behaviour to mirror
+  status_.resize(B_);
+  const int st = xivo_hip_get_status(ctx_, 0, B_, status_.data());
+  if (st == XIVO_HIP_ERR_NOT_SPD) { for (int b = 0; b < B_; ++b) n_not_spd_ += status_[b] != 0; }
+  else Check(st, "get_status");
+  Check(xivo_hip_absorb_error(ctx_, B_), "absorb_error");
 }
 
 void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_t* ids, const double* meas,
@@ -159,6 +186,12 @@ void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_
     host_s_ += now_s() - t0;
     Check(xivo_hip_propagate(ctx_, 0, B_, K, imu.data(), &cfg_.prop), "propagate");
     t0 = now_s();
+  }
+  if (subfilter_) {
+    host_s_ += now_s() - t0;
+    VisualSubfilter(off, ids, meas);
+    if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
+    return;
   }
   // --- before the update: tracker-dropped features leave (ProcessTracks, src/manager.cpp:152-169), tracked ones get
   // their new pixel
@@ -204,26 +237,7 @@ void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_
   Check(xivo_hip_edit_batch(ctx_, F, (int)ops.size(), ops.empty() ? nullptr : ops.data()), "edit_batch");
   Check(xivo_hip_set_pixels(ctx_, 0, B_, F, xp_.data()), "set_pixels");
   // --- measurement update on the tracked in-state features (src/manager.cpp:72-104), ragged over the filters
-  const double R = cfg_.visual_meas_std * cfg_.visual_meas_std;
-  if (cfg_.use_1pt_RANSAC) {
-    // Estimator::OutlierRejection with use_1pt_RANSAC (src/manager.cpp:629-650): MH gating, OnePointRANSAC on its inliers,
-    // the update on what it keeps. (No gauge group / previous-frame group list in this simplified life cycle.)
-    Check(xivo_hip_jacobians_instate(ctx_, B_), "jacobians_instate");
-    Check(xivo_hip_mh_gate(ctx_, B_, R, cfg_.MH_thresh, cfg_.MH_adjust_factor, cfg_.use_MH_gating ? cfg_.min_inliers : (1 << 30), nullptr, nullptr), "mh_gate");
-    Check(xivo_hip_one_point_ransac(ctx_, B_, R, cfg_.ransac_thresh, cfg_.ransac_Chi2, nullptr, nullptr, nullptr, nullptr, nullptr), "one_point_ransac");
-    Check(xivo_hip_stack(ctx_, B_, R), "stack");
-    Check(xivo_hip_update_joseph(ctx_, B_), "update_joseph");
-  } else {
-    Check(xivo_hip_filter_update(ctx_, B_, R, cfg_.MH_thresh, cfg_.MH_adjust_factor, cfg_.min_inliers, cfg_.use_MH_gating), "filter_update");
-  }
-  Check(xivo_hip_get_gate(ctx_, B_, F, mask_.data(), nullptr), "get_gate");
-  // a filter whose S was not positive definite keeps its prior P and absorbs nothing (the device skips both); it is
-  // counted and reported here - the reference's pivoted LDL^T cannot fail, so there is no reference behaviour to mirror
-  status_.resize(B_);
-  const int st = xivo_hip_get_status(ctx_, 0, B_, status_.data());
-  if (st == XIVO_HIP_ERR_NOT_SPD) { for (int b = 0; b < B_; ++b) n_not_spd_ += status_[b] != 0; }
-  else Check(st, "get_status");
-  Check(xivo_hip_absorb_error(ctx_, B_), "absorb_error");
+  RunUpdate();
   t0 = now_s();
   for (int b = 0; b < B_; ++b) n_updates_ += books_[b].id2slot.empty() ? 0 : 1;
   // --- after the update: MH-rejected features leave (src/update.cpp:105-113), new ones enter with a new group
@@ -279,6 +293,154 @@ void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_
   host_s_ += now_s() - t0;
   Check(xivo_hip_edit_batch(ctx_, F, (int)ops.size(), ops.empty() ? nullptr : ops.data()), "edit_batch");
   if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
+}
+
+void BatchEstimator::EnableSubfilter(const SubfilterConfig& sc) {
+  sc_ = sc;
+  Check(xivo_hip_pool_config(ctx_, sc.pool_max, sc.anchor_max, &sc.opts, sc.remove_outlier_counter), "pool_config");
+  pools_.assign(B_, PoolBook{});
+  for (auto& pb : pools_) {
+    pb.ent_id.assign(sc.pool_max, -1); pb.ent_anchor.assign(sc.pool_max, -1); pb.ent_born.assign(sc.pool_max, 0);
+    pb.anc_used.assign(sc.anchor_max, 0); pb.anc_life.assign(sc.anchor_max, 0); pb.anc_link.assign(sc.anchor_max, -1);
+  }
+  subfilter_ = true;
+}
+
+// One camera frame of the "subfilter" life cycle, decision for decision SequenceRunner._frame_subfilter of
+// xivo_amd/sequence.py (the order of Estimator::UpdateStep, src/manager.cpp:18-130)
+void BatchEstimator::VisualSubfilter(const int* off, const int64_t* ids, const double* meas) {
+  const int F = cfg_.n_features, PM = sc_.pool_max, AM = sc_.anchor_max;
+  ++vision_counter_;
+  for (auto& pb : pools_)                               // Group::IncrementLifetime (:36-41)
+    for (int a = 0; a < AM; ++a) pb.anc_life[a] = pb.anc_used[a] ? pb.anc_life[a] + 1 : 0;
+  std::vector<std::unordered_map<int64_t, int>> pos(B_);
+  for (int b = 0; b < B_; ++b)
+    for (int k = off[b]; k < off[b + 1]; ++k) pos[b][ids[k]] = k;
+  // --- ProcessTracks (:171-250)
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<xivo_edit_op> ops;
+  std::vector<double> xpp((size_t)B_ * PM * 2, nan);
+  for (int b = 0; b < B_; ++b) {
+    Book& bk = books_[b];
+    PoolBook& pb = pools_[b];
+    for (int j = 0; j < F; ++j)
+      if (bk.feat_id[j] >= 0 && !pos[b].count(bk.feat_id[j])) {
+        ops.push_back(make_op(b, XIVO_EDIT_REMOVE_FEATURE, j));
+        DropFeature(bk, j);
+      }
+    DiscardEmptyGroups(b, ops);
+    for (int e = 0; e < PM; ++e) {
+      if (pb.ent_id[e] < 0) continue;
+      auto it = pos[b].find(pb.ent_id[e]);
+      if (it != pos[b].end()) {
+        xpp[((size_t)b * PM + e) * 2] = meas[(size_t)it->second * 3];
+        xpp[((size_t)b * PM + e) * 2 + 1] = meas[(size_t)it->second * 3 + 1];
+      } else {
+        pb.FreeEntry(e);
+      }
+    }
+  }
+  std::vector<int> order((size_t)B_ * PM), n_cand(B_);
+  std::vector<unsigned char> live((size_t)B_ * PM);
+  Check(xivo_hip_pool_step(ctx_, B_, xpp.data(), vision_counter_ >= sc_.strict_criteria_timesteps ? 1 : 0, order.data(),
+                           n_cand.data(), live.data()), "pool_step");
+  // --- SelectAndAddNewFeatures / ZeroGaugeXYAddFeatures (:332-450): candidates in device order into free slots
+  for (int b = 0; b < B_; ++b) {
+    Book& bk = books_[b];
+    PoolBook& pb = pools_[b];
+    for (int e = 0; e < PM; ++e)
+      if (pb.ent_id[e] >= 0 && !live[(size_t)b * PM + e]) pb.FreeEntry(e);    // sub-filter outlier (:236-240)
+    std::vector<int> free_slots, gfree;
+    for (int j = 0; j < F; ++j) if (bk.feat_id[j] < 0) free_slots.push_back(j);
+    for (int g = 0; g < cfg_.n_groups; ++g) if (bk.group_refs[g] < 0) gfree.push_back(g);
+    size_t fq = 0, gq = 0;
+    for (int q = 0; q < n_cand[b] && fq < free_slots.size(); ++q) {
+      const int e = order[(size_t)b * PM + q], a = pb.ent_anchor[e];
+      if (pb.anc_link[a] < 0) {
+        if (gq >= gfree.size()) continue;                 // its group would need a free slot (:437-441)
+        const int g = gfree[gq++];
+        ops.push_back(make_op(b, XIVO_EDIT_ADD_GROUP_ANCHOR, g, a));
+        pb.anc_link[a] = g;
+        bk.group_refs[g] = 0;
+      }
+      const int g = pb.anc_link[a], j = free_slots[fq++];
+      const int64_t fid = pb.ent_id[e];
+      ops.push_back(make_op(b, XIVO_EDIT_ADMIT_POOL, j, j, e));
+      bk.feat_id[j] = fid; bk.feat_ref[j] = g; bk.id2slot[fid] = j;
+      bk.group_refs[g] += 1;
+      pb.FreeEntry(e);
+      ++n_admitted_;
+    }
+  }
+  // xivo_hip_edit_batch takes the ops grouped by filter (each filter's in the order they were made)
+  std::stable_sort(ops.begin(), ops.end(), [](const xivo_edit_op& x, const xivo_edit_op& y) { return x.b < y.b; });
+  Check(xivo_hip_edit_batch(ctx_, F, (int)ops.size(), ops.empty() ? nullptr : ops.data()), "edit_batch");
+  std::fill(xp_.begin(), xp_.end(), nan);
+  for (int b = 0; b < B_; ++b)
+    for (int j = 0; j < F; ++j)
+      if (books_[b].feat_id[j] >= 0) {
+        const int k = pos[b][books_[b].feat_id[j]];
+        xp_[((size_t)b * F + j) * 2] = meas[(size_t)k * 3];
+        xp_[((size_t)b * F + j) * 2 + 1] = meas[(size_t)k * 3 + 1];
+      }
+  Check(xivo_hip_set_pixels(ctx_, 0, B_, F, xp_.data()), "set_pixels");
+  // --- OutlierRejection + FilterUpdate, then DiscardAffectedGroups
+  RunUpdate();
+  for (int b = 0; b < B_; ++b) n_updates_ += books_[b].id2slot.empty() ? 0 : 1;
+  ops.clear();
+  for (int b = 0; b < B_; ++b) {
+    Book& bk = books_[b];
+    for (int j = 0; j < F; ++j)
+      if (bk.feat_id[j] >= 0 && !mask_[(size_t)b * F + j]) {
+        ops.push_back(make_op(b, XIVO_EDIT_REMOVE_FEATURE, j));
+        DropFeature(bk, j);
+        ++n_rejected_;
+      }
+    DiscardEmptyGroups(b, ops);
+  }
+  Check(xivo_hip_edit_batch(ctx_, F, (int)ops.size(), ops.empty() ? nullptr : ops.data()), "edit_batch");
+  // --- Group::Create(X_.Rsb, X_.Tsb) from the updated pose + InitializeJustCreatedTracks (:121-126, :575-600)
+  const double fl = 0.5 * std::sqrt(cfg_.cam.fx * cfg_.cam.fx + cfg_.cam.fy * cfg_.cam.fy);
+  std::vector<int> slots(B_, -1);
+  std::vector<xivo_pool_new> recs;
+  for (int b = 0; b < B_; ++b) {
+    Book& bk = books_[b];
+    PoolBook& pb = pools_[b];
+    std::vector<int> fresh;
+    for (int k = off[b]; k < off[b + 1]; ++k)
+      if (!bk.id2slot.count(ids[k]) && !pb.id2ent.count(ids[k])) fresh.push_back(k);
+    if (fresh.empty()) continue;
+    std::stable_sort(fresh.begin(), fresh.end(), [&](int a_, int b_) { return ids[a_] < ids[b_]; });
+    int a = -1;
+    for (int q = 0; q < AM; ++q) if (!pb.anc_used[q]) { a = q; break; }
+    if (a < 0) { n_pool_dropped_ += (long)fresh.size(); continue; }
+    slots[b] = a;
+    pb.anc_used[a] = 1; pb.anc_life[a] = 0; pb.anc_link[a] = -1;
+    size_t q = 0;
+    for (int e = 0; e < PM && q < fresh.size(); ++e) {
+      if (pb.ent_id[e] >= 0) continue;
+      const int k = fresh[q++];
+      xivo_pool_new r;
+      std::memset(&r, 0, sizeof(r));
+      r.b = b; r.entry = e; r.anchor = a;
+      r.xp[0] = meas[(size_t)k * 3]; r.xp[1] = meas[(size_t)k * 3 + 1];
+      r.z0 = sc_.initial_z;
+      r.std_xyz[0] = cfg_.initial_std_x / fl; r.std_xyz[1] = cfg_.initial_std_y / fl; r.std_xyz[2] = cfg_.initial_std_z;
+      recs.push_back(r);
+      pb.ent_id[e] = ids[k]; pb.ent_anchor[e] = a; pb.ent_born[e] = vision_counter_; pb.id2ent[ids[k]] = e;
+    }
+    n_pool_dropped_ += (long)(fresh.size() - q);
+  }
+  if (std::any_of(slots.begin(), slots.end(), [](int v) { return v >= 0; }))
+    Check(xivo_hip_pool_anchor(ctx_, 0, B_, slots.data()), "pool_anchor");
+  if (!recs.empty()) Check(xivo_hip_pool_add(ctx_, (int)recs.size(), recs.data()), "pool_add");
+  // --- EnforceMaxGroupLifetime (:282-304)
+  for (auto& pb : pools_) {
+    std::vector<char> held(AM, 0);
+    for (int e = 0; e < PM; ++e) if (pb.ent_id[e] >= 0) held[pb.ent_anchor[e]] = 1;
+    for (int a = 0; a < AM; ++a)
+      if (pb.anc_used[a] && pb.anc_link[a] < 0 && pb.anc_life[a] > sc_.max_group_lifetime && !held[a]) pb.anc_used[a] = 0;
+  }
 }
 
 void BatchEstimator::Poses(xivo_pose_in* out) {
@@ -343,6 +505,27 @@ void xivo_batch_stats(void* h, long* n_updates, long* n_rejected, double* host_s
   *n_updates = e->n_updates(); *n_rejected = e->n_rejected(); *host_seconds = e->host_seconds();
 }
 int xivo_batch_cfg_size(void) { return (int)sizeof(xivo_batch_cfg); }   // checked against the ctypes mirror (tests)
+struct xivo_batch_subfilter_cfg {   // flat mirror of xivo::hip::BatchEstimator::SubfilterConfig
+  double initial_z, remove_outlier_counter;
+  int strict_criteria_timesteps, max_group_lifetime;
+  xivo_subfilter_opts opts;
+  int pool_max, anchor_max;
+};
+int xivo_batch_enable_subfilter(void* h, const xivo_batch_subfilter_cfg* c) {
+  try {
+    xivo::hip::BatchEstimator::SubfilterConfig sc;
+    sc.initial_z = c->initial_z; sc.remove_outlier_counter = c->remove_outlier_counter;
+    sc.strict_criteria_timesteps = c->strict_criteria_timesteps; sc.max_group_lifetime = c->max_group_lifetime;
+    sc.opts = c->opts; sc.pool_max = c->pool_max; sc.anchor_max = c->anchor_max;
+    static_cast<xivo::hip::BatchEstimator*>(h)->EnableSubfilter(sc);
+    return 0;
+  } catch (const std::exception&) { return -1; }
+}
+int xivo_batch_subfilter_cfg_size(void) { return (int)sizeof(xivo_batch_subfilter_cfg); }
+void xivo_batch_pool_stats(void* h, long* admitted, long* dropped) {
+  auto* e = static_cast<xivo::hip::BatchEstimator*>(h);
+  *admitted = e->n_admitted(); *dropped = e->n_pool_dropped();
+}
 long xivo_batch_not_spd(void* h) { return static_cast<xivo::hip::BatchEstimator*>(h)->n_not_spd(); }
 void* xivo_batch_ctx(void* h) { return static_cast<xivo::hip::BatchEstimator*>(h)->ctx(); }
 

@@ -13,6 +13,9 @@
 // src/manager.cpp:588) anchored to a group created from the current pose; no gauge features, no reference-group
 // switching, no sub-filter warm-up. The host side holds only the slot book-keeping (gsel_ / fsel_,
 // src/estimator.h:496-503); every number of the filter stays on the device.
+// EnableSubfilter switches to the reference's sub-filter life cycle of a new track instead (initial_z, depth sub-filter
+// in the device-resident feature pool xivo_hip_pool_*, admission by Criteria::Candidate), decision for decision the
+// "subfilter" mode of xivo_amd/sequence.py.
 #pragma once
 #include <cstdint>
 #include <unordered_map>
@@ -66,6 +69,19 @@ class BatchEstimator {
   long n_rejected() const { return n_rejected_; }
   double host_seconds() const { return host_s_; }   // time spent in the host-side life cycle (not in C-ABI calls)
 
+  // the reference's life cycle of a new track on the device-resident feature pool (xivo_hip_pool_*), as
+  // xivo_amd/sequence.py runs it with feature_init = "subfilter": new tracks start from initial_z, take the depth sub-filter
+  // while out of the state and enter by Criteria::Candidate / CandidateStrict, best first
+  struct SubfilterConfig {
+    double initial_z = 2.5, remove_outlier_counter = 10.0;   // cfg initial_z, remove_outlier_counter
+    int strict_criteria_timesteps = 5, max_group_lifetime = 1;
+    xivo_subfilter_opts opts{12.25, 5.991, 5, 0.05, 10.0, 0.01};   // cfg "subfilter" (Rtri = visual_meas_std^2), depths, max_subfilter_outlier
+    int pool_max = 200, anchor_max = 64;                     // entries / anchors per filter
+  };
+  void EnableSubfilter(const SubfilterConfig& sc);   // before the first camera frame
+  long n_admitted() const { return n_admitted_; }
+  long n_pool_dropped() const { return n_pool_dropped_; }   // new tracks that found no free pool entry or anchor
+
   struct Book {                                     // one filter's slots
     std::vector<int> group_refs;                    // -1 free, else number of in-state features anchored there
     std::vector<int64_t> feat_id;                   // -1 free
@@ -78,6 +94,22 @@ class BatchEstimator {
   void Check(int rc, const char* what);
   void DropFeature(Book& bk, int j);
   void DiscardEmptyGroups(int b, std::vector<xivo_edit_op>& ops);
+  void RunUpdate();
+  void VisualSubfilter(const int* off, const int64_t* ids, const double* meas);
+
+  struct PoolBook {                                 // one filter's feature pool: tracks per entry, anchors and their links
+    std::vector<int64_t> ent_id;                    // -1 free
+    std::vector<int> ent_anchor, ent_born;
+    std::unordered_map<int64_t, int> id2ent;
+    std::vector<char> anc_used;
+    std::vector<int> anc_life, anc_link;            // Group::lifetime; group slot of the anchor's group (-1: not in the state)
+    void FreeEntry(int e) { id2ent.erase(ent_id[e]); ent_id[e] = -1; ent_anchor[e] = -1; }
+  };
+  bool subfilter_ = false;
+  SubfilterConfig sc_;
+  std::vector<PoolBook> pools_;
+  int vision_counter_ = 0;
+  long n_admitted_ = 0, n_pool_dropped_ = 0;
 
   BatchConfig cfg_;
   int B_;

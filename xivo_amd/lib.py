@@ -69,7 +69,12 @@ edit_dtype = np.dtype([("b", "i4"), ("kind", "i4"), ("i0", "i4"), ("i1", "i4"), 
                        ("v", "f8", 14)])
 assert edit_dtype.itemsize == 136
 EDIT_P_ZERO_RC, EDIT_P_COPY_RC, EDIT_P_SET_BLOCK3, EDIT_ADD_GROUP, EDIT_REMOVE_GROUP, EDIT_ADD_FEATURE, \
-    EDIT_REMOVE_FEATURE, EDIT_SET_XP = range(8)
+    EDIT_REMOVE_FEATURE, EDIT_SET_XP, EDIT_ADD_GROUP_ANCHOR, EDIT_ADMIT_POOL = range(10)
+# xivo_pool_new (include/xivo_hip.h): one new track for the out-of-state feature pool
+pool_new_dtype = np.dtype([("b", "i4"), ("entry", "i4"), ("anchor", "i4"), ("reserved", "i4"), ("xp", "f8", 2), ("z0", "f8"),
+                           ("std_xyz", "f8", 3)])
+assert pool_new_dtype.itemsize == 64
+POOL_MAX_ENTRIES = 512
 assert subfilter_dtype.itemsize == 144 and subfilter_opts_dtype.itemsize == 48
 assert feat_dtype.itemsize == 48 and pose_dtype.itemsize == 336 and group_dtype.itemsize == 96
 
@@ -129,6 +134,11 @@ _SIGS = {
     "xivo_hip_qr": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
     "xivo_hip_subfilter_update": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "xivo_hip_candidate_order": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_pool_config": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double],
+    "xivo_hip_pool_anchor": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_pool_add": [C.c_void_p, C.c_int, C.c_void_p],
+    "xivo_hip_pool_step": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_pool_get": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_edit_batch": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_set_pixels": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_get_scene": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -543,6 +553,43 @@ class Context:
         o["min_depth"], o["max_depth"], o["max_subfilter_outlier"] = min_depth, max_depth, max_subfilter_outlier
         self._check(self.lib.xivo_hip_subfilter_update(self.h, b0, nb, n, _ptr(feats), _ptr(o)))
         return feats
+
+    # ---- out-of-state feature pool (xivo_hip_pool_*)
+    def pool_config(self, pool_max, anchor_max, Rtri=3.5, MH_thresh=5.991, ready_steps=5, min_depth=0.05, max_depth=5.0,
+                    max_subfilter_outlier=0.01, remove_outlier_counter=10.0):
+        o = np.zeros(1, dtype=subfilter_opts_dtype)
+        o["Rtri"], o["MH_thresh"], o["ready_steps"] = Rtri, MH_thresh, ready_steps
+        o["min_depth"], o["max_depth"], o["max_subfilter_outlier"] = min_depth, max_depth, max_subfilter_outlier
+        self._check(self.lib.xivo_hip_pool_config(self.h, int(pool_max), int(anchor_max), _ptr(o), float(remove_outlier_counter)))
+        self.pool_max, self.anchor_max = int(pool_max), int(anchor_max)
+
+    def pool_anchor(self, slot, b0=0):
+        """slot [nb]: anchor of each filter that takes the filter's current pose (-1: none)"""
+        slot = np.ascontiguousarray(slot, dtype=np.int32)
+        self._check(self.lib.xivo_hip_pool_anchor(self.h, b0, int(slot.size), _ptr(slot)))
+
+    def pool_add(self, recs):
+        """recs: array of pool_new_dtype"""
+        recs = np.ascontiguousarray(recs, dtype=pool_new_dtype)
+        self._check(self.lib.xivo_hip_pool_add(self.h, int(recs.size), _ptr(recs) if recs.size else None))
+
+    def pool_step(self, xp, strict=False):
+        """xp [B, pool_max, 2] (NaN = dropped) -> (order [B, pool_max], n [B], live [B, pool_max] bool)"""
+        xp = np.ascontiguousarray(xp, dtype=np.float64)
+        B = xp.shape[0]
+        order = np.empty((B, self.pool_max), dtype=np.int32); n = np.empty(B, dtype=np.int32)
+        live = np.empty((B, self.pool_max), dtype=np.uint8)
+        self._check(self.lib.xivo_hip_pool_step(self.h, B, _ptr(xp), int(bool(strict)), _ptr(order), _ptr(n), _ptr(live)))
+        return order, n, live.astype(bool)
+
+    def pool_get(self, b0=0, nb=None):
+        """-> (entries [nb, pool_max] subfilter_dtype with ref_sind = anchor (-1: free), anchor poses [nb, anchor_max]
+        group_dtype, anchor slots [nb, anchor_max] (-1: unlinked))"""
+        nb = self.batch - b0 if nb is None else nb
+        ent = np.zeros((nb, self.pool_max), dtype=subfilter_dtype)
+        ap = np.zeros((nb, self.anchor_max), dtype=group_dtype); sl = np.zeros((nb, self.anchor_max), dtype=np.int32)
+        self._check(self.lib.xivo_hip_pool_get(self.h, b0, nb, _ptr(ent), _ptr(ap), _ptr(sl)))
+        return ent, ap, sl
 
     def givens(self, x, Hx, Hf, effective_rows=-1):
         """Batched xivo::Givens. x [nb, rows], Hx [nb, rows, nx], Hf [nb, rows, nf] (row-major numpy views of the

@@ -6,8 +6,10 @@
 in-state feature / group listings (src/estimator_accessors.cpp). One `Estimator` is one filter on the device (a context
 of batch 1); for many sequences at once use `xivo_amd.sequence.run_pcw`, which drives the same calls batched.
 
-Every numeric step is the C ABI (`xivo_amd/sequence.HipBackend`); the life cycle is the simplified one documented in
-`xivo_amd/sequence.py`. Image input (`VisualMeas`), the tracker-only modes, loop closure and the viewer are outside the
+Every numeric step is the C ABI (`xivo_amd/sequence.HipBackend`); the life cycles are documented in `xivo_amd/sequence.py`:
+after `InitWithSimDepths()` new features enter the state at once with the simulator's depth ("immediate"), without it
+they start from `initial_z` in the device-resident feature pool and enter through the depth sub-filter ("subfilter"), as
+the reference does for real input. Image input (`VisualMeas`), the tracker-only modes, loop closure and the viewer are outside the
 path this repository implements and raise NotImplementedError.
 """
 import json
@@ -68,9 +70,17 @@ def config_from_cfg(cfg):
     c.use_1pt_RANSAC = bool(cfg.get("use_1pt_RANSAC", c.use_1pt_RANSAC))
     c.ransac_thresh = float(cfg.get("1pt_RANSAC_thresh", c.ransac_thresh))
     c.ransac_Chi2 = float(cfg.get("1pt_RANSAC_Chi2", c.ransac_Chi2))
-    for k in ("initial_std_x", "initial_std_y", "initial_std_z", "min_depth", "max_depth"):
+    for k in ("initial_std_x", "initial_std_y", "initial_std_z", "min_depth", "max_depth", "initial_z", "remove_outlier_counter",
+              "max_subfilter_outlier"):
         if k in cfg:
             setattr(c, k, float(cfg[k]))
+    for k in ("strict_criteria_timesteps", "max_group_lifetime"):
+        if k in cfg:
+            setattr(c, k, int(cfg[k]))
+    c.subfilter = dict(c.subfilter)
+    for k in c.subfilter:
+        if k in cfg.get("subfilter", {}):
+            c.subfilter[k] = type(c.subfilter[k])(cfg["subfilter"][k])
     cam = cfg.get("camera_cfg")
     if cam:
         model = _CAM_MODELS[cam["model"]]
@@ -93,11 +103,10 @@ class Estimator:
         if tracker_only:
             raise NotImplementedError("tracker-only mode is outside the EKF update path")
         if isinstance(cfg, sequence.SequenceConfig):
-            self.cfg = cfg
+            import copy
+            self.cfg = copy.deepcopy(cfg)       # the life cycle is switched below, per estimator
         else:
             self.cfg = config_from_cfg(load_json_with_comments(cfg) if isinstance(cfg, str) else dict(cfg))
-        if self.cfg.cam["model"] != 0:
-            raise NotImplementedError("point-cloud input initialises features with a pinhole un-projection only")
         self.name = name
         c = self.cfg
         X0 = c.X0 or {k: np.zeros(3) for k in ("Wsb", "Tsb", "Vsb", "bg", "ba", "Wsg")}
@@ -132,10 +141,16 @@ class Estimator:
 
     def VisualMeasPointCloud(self, ts, feature_ids, xp_and_depths):
         """Estimator::VisualMeasPointCloud (src/estimator.cpp:1133-1180): tracks given as ids + (x, y, depth) rows.
-        Features enter with the given depth (InitWithSimDepths; without it the reference starts from `initial_z`
-        and the depth sub-filter, which this driver does not run)."""
-        if not self._sim_depths:
-            raise NotImplementedError("call InitWithSimDepths(): depth-less initialisation needs the sub-filter warm-up")
+        After InitWithSimDepths() features enter the state at once with the given depth; otherwise they start from
+        `initial_z` in the feature pool and enter through the depth sub-filter (the depth column is not read)."""
+        if not self._vision:
+            if self._sim_depths:
+                if self.cfg.cam["model"] != 0:
+                    raise NotImplementedError("simulator depths initialise features with a pinhole un-projection only")
+            else:
+                self.cfg.feature_init = "subfilter"
+                if not self._be.pool_on:
+                    self._be.enable_pool()
         ids = np.asarray(feature_ids, dtype=np.int64).reshape(-1)
         meas = np.asarray(xp_and_depths, dtype=float).reshape(-1, 3)
         imu = None

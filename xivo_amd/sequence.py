@@ -13,10 +13,23 @@ What is mirrored from the reference and what is simplified:
     (ProcessTracks, :152-169), the filter update runs on the tracked in-state features, MH-rejected features are
     removed (src/update.cpp:105-113), groups that lost all their features are discarded (DiscardAffectedGroups),
     then new features enter (SelectAndAddNewFeatures).
-  * SIMPLIFIED: a new feature enters the state in the frame it is first seen, with the simulator's depth
-    (`InitWithSimDepths`, scripts/pyxivo_pcw.py:139-140, src/manager.cpp:588) and the configured initial std
-    (src/estimator.cpp:349-353) - no depth sub-filter warm-up, no gauge features, no reference-group switching, no
-    group lifetime cap; its anchor is a group created from the current pose (AddGroupToState).
+  * new features, two life cycles (`SequenceConfig.feature_init`):
+    - "immediate" (default, SIMPLIFIED): a new feature enters the state in the frame it is first seen, with the
+      simulator's depth (`InitWithSimDepths`, scripts/pyxivo_pcw.py:139-140, src/manager.cpp:588) and the configured
+      initial std (src/estimator.cpp:349-353) - no depth sub-filter warm-up; its anchor is a group created from the
+      current pose (AddGroupToState).
+    - "subfilter": the reference's life cycle of a new track on the device-resident feature pool (xivo_hip_pool_*). A
+      new track starts from `initial_z` (Feature::Initialize, src/feature.cpp:144-160) anchored to an anchor made from
+      the frame's post-update pose (src/manager.cpp:121-126), runs Feature::SubfilterUpdate in every frame it stays out
+      of the state (ProcessTracks, :171-250; dropped tracks and outliers leave the pool) and enters the state before the
+      update once Criteria::Candidate - CandidateStrict from `strict_criteria_timesteps` frames on - passes, best first
+      (ZeroGaugeXYAddFeatures, :408-450): its anchor's group enters a free group slot with the anchor's own pose
+      (AddGroupToState, src/estimator.cpp:801-816) unless it is in the state already; without a free slot the candidate
+      waits. An anchor whose group left the state keeps the group's last pose; unlinked anchors without live entries are
+      freed after `max_group_lifetime` frames (EnforceMaxGroupLifetime, :282-304). New tracks that find no free pool
+      entry or anchor are dropped and counted (`SequenceRunner.n_pool_dropped`).
+  * NOT IN EITHER: pre-sub-filter triangulation and RefineDepth (`use_depth_opt`), gauge XY features and
+    SwitchRefGroup, ownership transfer, AdaptInitialDepth (`initial_z` stays fixed), OOS updates.
 The numerics of every step are the device path; this file holds no arithmetic of the filter itself.
 """
 import numpy as np
@@ -113,6 +126,16 @@ class SequenceConfig:
         # the reference's USE_INVDEPTH build (src/CMakeLists.txt:10): features are (X/Z, Y/Z, 1/Z); initial_std_z is then an
         # inverse-depth standard deviation
         self.use_invdepth = False
+        # life cycle of a new feature: "immediate" (enters the state at once with the simulator's depth) or "subfilter"
+        # (the reference's: depth sub-filter in the device-resident feature pool first). Reference cfg keys / defaults:
+        self.feature_init = "immediate"
+        self.initial_z = 2.5                    # initial_z (cfg/tumvi_cam0.json:115)
+        self.remove_outlier_counter = 10.0      # remove_outlier_counter (src/estimator.cpp:171)
+        self.strict_criteria_timesteps = 5      # strict_criteria_timesteps (src/estimator.cpp:374)
+        self.max_group_lifetime = 1             # max_group_lifetime (src/manager.cpp:285)
+        self.max_subfilter_outlier = 0.01       # max_subfilter_outlier (src/options.cpp:10-33)
+        self.subfilter = dict(visual_meas_std=3.5, MH_thresh=5.991, ready_steps=5)   # cfg "subfilter" (src/estimator.cpp:137-142)
+        self.pool_max, self.anchor_max = 200, 64   # feature pool / anchor table per filter (device resident)
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option " + k)
@@ -176,6 +199,27 @@ class HipBackend:
         feats["sind"] = -1
         self.ctx.set_scene(poses0, groups, feats)
         self.Qimu, self.Qmodel = cfg.Qimu_matrix(), cfg.Qmodel_matrix()
+        self.pool_on = False
+        if cfg.feature_init == "subfilter":
+            self.enable_pool()
+
+    def enable_pool(self):
+        """allocate the device-resident feature pool of the "subfilter" life cycle"""
+        c = self.cfg
+        sf = c.subfilter
+        self.ctx.pool_config(c.pool_max, c.anchor_max, Rtri=float(sf["visual_meas_std"]) ** 2, MH_thresh=float(sf["MH_thresh"]),
+                             ready_steps=int(sf["ready_steps"]), min_depth=c.min_depth, max_depth=c.max_depth,
+                             max_subfilter_outlier=c.max_subfilter_outlier, remove_outlier_counter=c.remove_outlier_counter)
+        self.pool_on = True
+
+    def pool_step(self, xp, strict):
+        return self.ctx.pool_step(xp, strict)
+
+    def pool_anchor(self, slot):
+        self.ctx.pool_anchor(slot)
+
+    def pool_add(self, recs):
+        self.ctx.pool_add(recs)
 
     def propagate(self, imu):
         self.ctx.propagate(imu, self.Qimu, self.Qmodel, self.cfg.gravity,
@@ -244,6 +288,28 @@ class _Book:
         return len(self.id2slot)
 
 
+class _PoolBook:
+    """host side of one filter's feature pool: which track sits in which entry, anchors and the group slot each links to"""
+
+    def __init__(self, pool_max, anchor_max):
+        self.ent_id = [-1] * pool_max            # track id held by pool entry e (-1: free)
+        self.ent_anchor = [-1] * pool_max
+        self.ent_born = [0] * pool_max           # camera frame the entry was created in
+        self.id2ent = {}
+        self.anc_used = [False] * anchor_max
+        self.anc_life = [0] * anchor_max         # Group::lifetime (frames since creation)
+        self.anc_link = [-1] * anchor_max        # group slot the anchor's group occupies (-1: not in the state)
+
+    def free_entry(self, e):
+        del self.id2ent[self.ent_id[e]]
+        self.ent_id[e] = -1; self.ent_anchor[e] = -1
+
+    def unlink_slot(self, g):
+        for a, s in enumerate(self.anc_link):
+            if s == g:
+                self.anc_link[a] = -1
+
+
 def _op(b, kind, i0=0, i1=0, i2=0, v=()):
     o = np.zeros((), dtype=L.edit_dtype)
     o["b"], o["kind"], o["i0"], o["i1"], o["i2"] = b, kind, i0, i1, i2
@@ -261,6 +327,10 @@ class SequenceRunner:
         self.books = [_Book(cfg.n_groups, cfg.n_features) for _ in range(B)]
         self.n_updates = 0
         self.n_rejected = 0
+        self.pools = None            # [B] _PoolBook in the "subfilter" life cycle
+        self.vision_counter = 0      # camera frames so far (Estimator::vision_counter_)
+        self.n_pool_dropped = 0      # new tracks dropped because the pool or the anchor table was full
+        self.admitted = []           # (frame, filter, track id, sub-filter steps taken) of every pool entry that entered the state
         self.timers = None       # set to {} to accumulate wall seconds per phase (adds a device sync per phase)
 
     def _tick(self, name, t0):
@@ -279,9 +349,15 @@ class SequenceRunner:
             if r == 0:
                 ops.append(_op(b, L.EDIT_REMOVE_GROUP, g))
                 bk.group_refs[g] = -1
+                if self.pools is not None:
+                    self.pools[b].unlink_slot(g)      # the device freezes the anchor at the group's last pose
 
     def frame(self, imu, tracks):
         """imu: [B x K] xivo_imu_in records or None; tracks: per filter (ids [n], xp_and_depths [n x 3])."""
+        if self.cfg.feature_init == "subfilter":
+            return self._frame_subfilter(imu, tracks)
+        if self.cfg.feature_init != "immediate":
+            raise ValueError("feature_init must be 'immediate' or 'subfilter'")
         import time
         cfg, be = self.cfg, self.be
         t0 = time.perf_counter()
@@ -349,6 +425,121 @@ class SequenceRunner:
         t0 = self._tick("host_post", t0) or t0
         be.edit(ops)
         self._tick("edit", t0)
+        return mask
+
+
+    def _frame_subfilter(self, imu, tracks):
+        """one camera frame in the order of Estimator::UpdateStep (src/manager.cpp:18-130) with the feature pool"""
+        cfg, be, B = self.cfg, self.be, self.B
+        if self.pools is None:
+            self.pools = [_PoolBook(cfg.pool_max, cfg.anchor_max) for _ in range(B)]
+        self.vision_counter += 1
+        if imu is not None:
+            be.propagate(imu)
+        for pb in self.pools:                                   # Group::IncrementLifetime (:36-41)
+            pb.anc_life = [life + 1 if u else 0 for life, u in zip(pb.anc_life, pb.anc_used)]
+        pos = [{int(i): k for k, i in enumerate(tracks[b][0])} for b in range(B)]
+        # --- ProcessTracks (:171-250): in-state features the tracker dropped leave the state, pool entries it dropped
+        # leave the pool, every other pool entry takes its sub-filter step
+        ops = []
+        xpp = np.full((B, cfg.pool_max, 2), np.nan)
+        for b in range(B):
+            bk, pb, meas = self.books[b], self.pools[b], tracks[b][1]
+            for j in range(cfg.n_features):
+                if bk.feat_id[j] >= 0 and bk.feat_id[j] not in pos[b]:
+                    ops.append(_op(b, L.EDIT_REMOVE_FEATURE, j))
+                    bk.drop_feature(j)
+            self._discard_empty_groups(b, ops)
+            for e, fid in enumerate(pb.ent_id):
+                if fid < 0:
+                    continue
+                if fid in pos[b]:
+                    xpp[b, e] = meas[pos[b][fid], :2]
+                else:
+                    pb.free_entry(e)
+        order, n_cand, live = be.pool_step(xpp, self.vision_counter >= cfg.strict_criteria_timesteps)
+        # --- SelectAndAddNewFeatures / ZeroGaugeXYAddFeatures (:332-450): candidates in device order into free slots
+        for b in range(B):
+            bk, pb = self.books[b], self.pools[b]
+            for e, fid in enumerate(pb.ent_id):
+                if fid >= 0 and not live[b, e]:
+                    pb.free_entry(e)                            # sub-filter outlier (:236-240)
+            free = [j for j in range(cfg.n_features) if bk.feat_id[j] < 0]
+            gfree = [g for g, r in enumerate(bk.group_refs) if r < 0]
+            for e in order[b, :n_cand[b]]:
+                if not free:
+                    break
+                a = pb.ent_anchor[e]
+                if pb.anc_link[a] < 0:
+                    if not gfree:
+                        continue                                # its group would need a free slot (:437-441)
+                    g = gfree.pop(0)
+                    ops.append(_op(b, L.EDIT_ADD_GROUP_ANCHOR, g, a))
+                    pb.anc_link[a] = g
+                    bk.group_refs[g] = 0; bk.group_gen[g] += 1
+                g, j, fid = pb.anc_link[a], free.pop(0), pb.ent_id[e]
+                ops.append(_op(b, L.EDIT_ADMIT_POOL, j, j, int(e)))
+                self.admitted.append((self.vision_counter, b, fid, self.vision_counter - pb.ent_born[e]))
+                bk.feat_id[j] = fid; bk.feat_ref[j] = g; bk.id2slot[fid] = j
+                bk.group_refs[g] += 1
+                pb.free_entry(int(e))
+        be.edit(np.array(ops, dtype=L.edit_dtype))
+        xp = np.full((B, cfg.n_features, 2), np.nan)
+        for b in range(B):
+            bk, meas = self.books[b], tracks[b][1]
+            for j in range(cfg.n_features):
+                if bk.feat_id[j] >= 0:
+                    xp[b, j] = meas[pos[b][bk.feat_id[j]], :2]
+        be.set_pixels(xp)
+        # --- OutlierRejection + FilterUpdate, then DiscardAffectedGroups
+        mask = be.update()
+        self.n_updates += sum(1 for bk in self.books if bk.n_instate() > 0)
+        ops = []
+        for b in range(B):
+            bk = self.books[b]
+            for j in range(cfg.n_features):
+                if bk.feat_id[j] >= 0 and not mask[b, j]:
+                    ops.append(_op(b, L.EDIT_REMOVE_FEATURE, j))
+                    bk.drop_feature(j)
+                    self.n_rejected += 1
+            self._discard_empty_groups(b, ops)
+        be.edit(np.array(ops, dtype=L.edit_dtype))
+        # --- Group::Create(X_.Rsb, X_.Tsb) from the updated pose + InitializeJustCreatedTracks (:121-126, :575-600)
+        fl = cfg.focal_length()
+        std = [cfg.initial_std_x / fl, cfg.initial_std_y / fl, cfg.initial_std_z]
+        slots = np.full(B, -1, dtype=np.int32)
+        recs = []
+        for b in range(B):
+            bk, pb = self.books[b], self.pools[b]
+            ids, meas = tracks[b]
+            new = [k for k in np.argsort(ids, kind="stable") if int(ids[k]) not in bk.id2slot and int(ids[k]) not in pb.id2ent]
+            if not new:
+                continue
+            afree = [a for a, u in enumerate(pb.anc_used) if not u]
+            efree = [e for e, fid in enumerate(pb.ent_id) if fid < 0]
+            if not afree:
+                self.n_pool_dropped += len(new)
+                continue
+            a = afree[0]
+            slots[b] = a
+            pb.anc_used[a] = True; pb.anc_life[a] = 0; pb.anc_link[a] = -1
+            self.n_pool_dropped += max(0, len(new) - len(efree))
+            for e, k in zip(efree, new):
+                r = np.zeros((), dtype=L.pool_new_dtype)
+                r["b"], r["entry"], r["anchor"], r["xp"], r["z0"], r["std_xyz"] = b, e, a, meas[k, :2], cfg.initial_z, std
+                recs.append(r)
+                pb.ent_id[e] = int(ids[k]); pb.ent_anchor[e] = a; pb.ent_born[e] = self.vision_counter
+                pb.id2ent[int(ids[k])] = e
+        if (slots >= 0).any():
+            be.pool_anchor(slots)
+        if recs:
+            be.pool_add(np.array(recs, dtype=L.pool_new_dtype))
+        # --- EnforceMaxGroupLifetime (:282-304): an anchor out of the state with no live entry is freed when too old
+        for pb in self.pools:
+            held = set(pb.ent_anchor)
+            for a in range(cfg.anchor_max):
+                if pb.anc_used[a] and pb.anc_link[a] < 0 and pb.anc_life[a] > cfg.max_group_lifetime and a not in held:
+                    pb.anc_used[a] = False
         return mask
 
 
