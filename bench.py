@@ -8,8 +8,13 @@ fp64, XIVO row sparsity, inputs resident in HBM before the timed region. Every
 step hands the dense H / inn / diagR of every filter over again (H changes with
 every camera frame, src/update.cpp:129-138): the dense -> row-pair compression is
 inside the timed step. `value` is the library's default mode: every product in fp64
-(no fp32 instruction runs unless XIVO_HIP_FLAG_FP32_WHITENED asks for one - the cfg4_f32w row);
-`value_symmetric_form` times the opt-in symmetric form next to it.
+(no fp32 instruction runs unless XIVO_HIP_FLAG_FP32_WHITENED asks for one - the cfg4_f32w row).
+
+A plain run does only what the headline figure needs: set up, warm up, time the steps, write --dump-outputs, print
+the line (with the per-stage times and the roofline of the timed steps, which cost no run of their own). `--full`
+adds everything else: parity against the oracle (first and last timed step), `value_symmetric_form` (the opt-in
+symmetric form, timed after the headline), the measured MFMA peak, the CPU baseline, the drop-in timings, the other
+BASELINE configurations (`configs`, child runs) and the verbose record.
 
 `python bench.py --gpus N` without a launcher spawns its N ranks itself.
 
@@ -446,7 +451,7 @@ def configs_block(device_budget_s=240.0):
             rows.append({"k": key, "skipped": "time budget"})
             full.append({"k": key, "name": name, "skipped": "time budget of the default run used up"})
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--sub", "--no-cpu-baseline", "--no-mixed"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--sub", "--full", "--no-cpu-baseline", "--no-mixed"] + extra
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=150)
@@ -579,8 +584,13 @@ def main():
     ap.add_argument("--tol-dx-last", type=float, default=1e-8,
                     help="tolerance on dx of the LAST update of the timed chain (the fp32 flag states 1e-6: dx of a later update "
                          "inherits the fp32 rounding of the earlier covariances)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: parity against the oracle, the symmetric form, the measured "
+                         "MFMA peak, the CPU baseline, the drop-in timings, the other configurations and the verbose record "
+                         "(a plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line)")
     ap.add_argument("--full-out", default=None,
-                    help="where the verbose record goes (default gpurun_out/bench_full.json; the printed line is the compact one)")
+                    help="where the verbose record goes (written by --full runs, default bench_out/bench_full.json, and by any "
+                         "run given this option; the printed line is the compact one)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / reduction path only, no device work (CPU-box test of --gpus N)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -809,10 +819,12 @@ def main():
     if args.dump_outputs and rank == 0:      # before anything below runs the path again
         gated = not args.no_gating or oos_on or (args.level == "G" and args.ransac)
         dumped = dump_outputs(ctx, args.dump_outputs, B, F, gated, frame)
+    # everything below the headline (checks, second figures, baselines) is --full only
+    checks = args.full and not args.no_parity_check
     # the state the timed loop left behind against the oracle doing the same number of updates in a row (every rank, its
     # own filters)
     parity_last = None
-    if args.level == "S" and not args.no_parity_check and not args.no_last_step_parity:
+    if args.level == "S" and checks and not args.no_last_step_parity:
         parity_last = parity_last_step(ctx, args.warmup + args.steps, B, uniq, F, P, H, inn, dR,
                                        (R_VIS, MH_THRESH, MH_MULT, MIN_INL), args.no_gating,
                                        tol_P=args.tol_P, tol_dx=args.tol_dx_last)
@@ -820,7 +832,7 @@ def main():
     # ---- second figure (opt-in library mode, NOT the headline): XIVO_HIP_FLAG_SYMMETRIC_FORM - P+ = P - W^T W with
     # W = L^-1 (H P), forward substitution only; equal to the Joseph form for the optimal gain, checked below
     symm = None
-    if not args.no_mixed and sparse_path and args.level == "S":
+    if args.full and not args.no_mixed and sparse_path and args.level == "S":
         from xivo_amd.lib import FLAG_SYMMETRIC_FORM
         ctx.set_flags(base_flags | FLAG_SYMMETRIC_FORM)
         ctx.restore_P()
@@ -831,19 +843,19 @@ def main():
                 "what": "XIVO_HIP_FLAG_SYMMETRIC_FORM: S = L L^T, W = L^-1 (H P) (forward substitution only), dx = W^T L^-1 inn, "
                         "P+ = P - W^T W - the value of the Joseph expression for the optimal gain, all fp64; opt-in, the "
                         "reference codes the Joseph form (= `value`)"}
-        if not args.no_parity_check:
+        if checks:
             symm["parity_check"] = parity_check(ctx, step, B, uniq, F, P, H, inn, dR, (R_VIS, MH_THRESH, MH_MULT, MIN_INL), args.no_gating, args.tol_P)
         ctx.set_flags(flags)
 
     # ---- parity at the benchmarked batch: one step from the initial P, filters spread over the launch
     # (first / last, both sides of an XCD group of 8, mid batch) against the oracle - checker only, outside the timing
     parity = None
-    if args.level == "S" and not args.no_parity_check:      # every rank checks its own GPU's results
+    if args.level == "S" and checks:      # every rank checks its own GPU's results
         parity = parity_check(ctx, step, B, uniq, F, P, H, inn, dR, (R_VIS, MH_THRESH, MH_MULT, MIN_INL), args.no_gating, args.tol_P)
-    elif args.level == "G" and not args.no_parity_check and frame:
+    elif args.level == "G" and checks and frame:
         parity = parity_frame(ctx, B, uniq, P, (poses, groups, feats), imu, Qimu, Qmodel, grav, args.integrator,
                               (R_VIS, MH_THRESH, MH_MULT, MIN_INL), args.no_gating, args.tol_P)
-    elif args.level == "G" and not args.no_parity_check:
+    elif args.level == "G" and checks:
         # (--ransac too: OnePointRANSAC restores the state and covariance it experimented on - src/update.cpp:375-387 - so the
         #  final update starts from the initial covariance, on the rows that survived)
         parity = parity_glevel(ctx, step, B, uniq, P, args.tol_P)
@@ -865,7 +877,7 @@ def main():
             dist.destroy_process_group()
         sys.exit(3)
 
-    peak_meas = ctx.bench_mfma_peak() if rank == 0 else None
+    peak_meas = ctx.bench_mfma_peak() if (rank == 0 and args.full) else None
 
     if rank == 0:
         updates = world * B * args.steps
@@ -1012,11 +1024,11 @@ def main():
         }
         if dumped:
             out["dumped_outputs"] = dumped
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(N, F)
             out["cpu_baseline"]["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
-        headline_default = (world == 1 and not args.sub and args.level == "S" and args.state_dim == 250 and args.features == 80
-                            and args.flags == 0 and not args.no_gating)
+        headline_default = (args.full and world == 1 and not args.sub and args.level == "S" and args.state_dim == 250
+                            and args.features == 80 and args.flags == 0 and not args.no_gating)
         if headline_default and not args.no_dropin:
             try:
                 out["dropin"] = dropin_block()
@@ -1028,14 +1040,15 @@ def main():
         if args.sub:
             print(json.dumps(out))           # the parent run reads the whole record and prints its own compact row
         else:
-            path = args.full_out or os.path.join(ROOT, "gpurun_out", "bench_full.json")
-            try:
-                os.makedirs(os.path.dirname(path), exist_ok=True)
-                with open(path, "w") as f:
-                    json.dump(out, f, indent=1)
-                out["full_record"] = os.path.relpath(path, ROOT)
-            except OSError:
-                pass
+            if args.full or args.full_out:
+                path = args.full_out or os.path.join(ROOT, "bench_out", "bench_full.json")
+                try:
+                    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                    with open(path, "w") as f:
+                        json.dump(out, f, indent=1)
+                    out["full_record"] = os.path.relpath(path, ROOT)
+                except OSError:
+                    pass
             print(json.dumps(compact_line(out), separators=(",", ":")))
     ctx.close()
     if dist is not None:

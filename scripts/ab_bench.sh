@@ -7,7 +7,7 @@ L=xivo_amd/csrc/build/abl
 for rep in 1 2; do
   for n in default "$@"; do
     if [ $n = default ]; then unset XIVO_HIP_LIBRARY; else export XIVO_HIP_LIBRARY=$PWD/$L/libxivo_hip_$n.so; fi
-    timeout 300 python bench.py --no-cpu-baseline --no-mixed --no-configs --no-dropin $A > $O/${n}_$rep.json 2> $O/${n}_$rep.err
+    timeout 300 python bench.py --full --no-cpu-baseline --no-mixed --no-configs --no-dropin $A > $O/${n}_$rep.json 2> $O/${n}_$rep.err
   done
 done
 unset XIVO_HIP_LIBRARY

@@ -6,8 +6,8 @@ mkdir -p $O
 for rep in 1 2; do
   for n in default "$@"; do
     tag=$(echo "$n" | tr -c 'A-Za-z0-9_=\n' '_')
-    if [ "$n" = default ]; then timeout 300 python bench.py --no-cpu-baseline --no-mixed --no-configs --no-dropin $A > $O/${tag}_$rep.json 2> $O/${tag}_$rep.err
-    else env $n timeout 300 python bench.py --no-cpu-baseline --no-mixed --no-configs --no-dropin $A > $O/${tag}_$rep.json 2> $O/${tag}_$rep.err; fi
+    if [ "$n" = default ]; then timeout 300 python bench.py --full --no-cpu-baseline --no-mixed --no-configs --no-dropin $A > $O/${tag}_$rep.json 2> $O/${tag}_$rep.err
+    else env $n timeout 300 python bench.py --full --no-cpu-baseline --no-mixed --no-configs --no-dropin $A > $O/${tag}_$rep.json 2> $O/${tag}_$rep.err; fi
   done
 done
 python - "$O" <<'PY'

@@ -1,5 +1,6 @@
-"""bench.py end to end on the GPU box at a small batch: one JSON line with the contract's keys, the default and the opt-in
-symmetric-form figure, the in-bench parity check, roofline and the per-stage times (the hand-over stage inside the timed step)."""
+"""bench.py end to end on the GPU box at a small batch: one JSON line with the contract's keys; with --full the default and the
+opt-in symmetric-form figure, the in-bench parity check, roofline and the per-stage times (the hand-over stage inside the timed
+step); a plain run times the headline and nothing else, and dumps what a --full run dumps."""
 import json
 import os
 import subprocess
@@ -11,15 +12,16 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*extra, full=True):
-    """-> the verbose record (--full-out) by default, the printed compact line with full=False."""
+def _run(*extra, full=True, plain=False):
+    """bench.py --full (plain=True: without it) -> the verbose record (--full-out) by default, the printed compact line with
+    full=False."""
     import tempfile
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     with tempfile.TemporaryDirectory() as td:
         path = os.path.join(td, "full.json")
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "512", "--steps", "2", "--warmup", "1",
-                            "--no-cpu-baseline", "--full-out", path, *extra], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                           text=True, timeout=600)
+                            *([] if plain else ["--full"]), "--no-cpu-baseline", "--full-out", path, *extra], env=env,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         assert len(lines) == 1
@@ -99,3 +101,23 @@ def test_feature_level_and_config3_lines(built):
     assert d["value"] > 0 and "QR-compressed" in d["config"]["workload"] and "mixed stacking" in d["config"]["pipeline"]
     d = _run("--level", "G", "--oos", "20", "--no-compression")
     assert d["value"] > 0 and "QR-compressed" not in d["config"]["workload"] and d["parity_check"]["ok"]
+
+
+def test_plain_run_is_the_headline_only(built, tmp_path):
+    """Without --full: the contract keys, the per-stage times and the roofline of the timed steps - no parity, no second figure,
+    no measured peak, no CPU baseline, no drop-in, no configurations - and --dump-outputs writes, array for array and bit for
+    bit, what a --full run writes (the dump is taken before anything else runs the path again)."""
+    import numpy as np
+    rec = _run("--dump-outputs", str(tmp_path / "plain"), plain=True)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline"):
+        assert k in rec, k
+    assert rec["value"] > 0 and rec["steps"] == 2 and rec["warmup"] == 1 and rec["dtype"] == "f64" and rec["unit"] == "updates/s"
+    assert rec["config"]["not_spd_filters"] == 0 and rec["stage_ms_per_step"]["stack_H"] > 0
+    assert rec["parity_check"] is None and rec["parity_check_last_timed_step"] is None and rec["symmetric_form"] is None
+    assert rec["roofline"]["mfma_peak_measured_tflops"] is None
+    assert not ({"cpu_baseline", "dropin", "configs"} & set(rec))
+    _run("--no-configs", "--no-dropin", "--dump-outputs", str(tmp_path / "full"))
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full"))
+    for f in names:
+        assert np.array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)), f
