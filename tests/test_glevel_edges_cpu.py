@@ -9,7 +9,7 @@ import test_glevel_edges_gpu as edges
 
 
 def _passes(case):
-    """passes of the loop the case's limit counts, from its shape (the kernels' loop bounds in csrc/ekf_kernels.hip)"""
+    """passes of the loop the case's limit counts, from its shape (the kernels' loop bounds: csrc/glevel_kernels.hip, state_kernels.hip)"""
     name, kernel, limit, side, entry, sh = case[:6]
     up = lambda a, b: -(-a // b)
     if kernel in ("relax_threshold", "ransac_select_kernel"):

@@ -1,6 +1,6 @@
-"""The feature-level kernels (csrc/ekf_kernels.hip through capi_glevel.hip) and the propagation tail (capi_propagate.hip) on
-both sides of every launch-shape limit, against plain float64 restatements (the oracle, or a numpy expression of the same
-operation).
+"""The feature-level kernels (csrc/glevel_kernels.hip and AbsorbError in csrc/state_kernels.hip, through capi_glevel.hip) and
+the propagation tail (csrc/propagate_kernels.hip through capi_propagate.hip) on both sides of every launch-shape limit,
+against plain float64 restatements (the oracle, or a numpy expression of the same operation).
 
 GLEVEL_EDGE_CASES names, per case, the kernel and the limit it targets, which side of the limit the shape is on, the entry
 point and the shape. Where the launch picks by size (the gate's block size, the OOS-compression instantiation, the tail

@@ -1,4 +1,5 @@
-// Launchers of the EKF-specific (non-GEMM) kernels. See ekf_kernels.hip.
+// Launchers of the EKF-specific (non-GEMM) kernels, one section per translation unit: state_kernels.hip,
+// glevel_kernels.hip, pool_kernels.hip, propagate_kernels.hip, then ldlt_fallback.hip and dropin.hip.
 #pragma once
 #include "common.h"
 #include "ell.h"
@@ -6,29 +7,14 @@
 
 namespace xivo_hip {
 
+struct PoolAnchor;   // pool_kernels.hip section
+
+// ================================================================ state_kernels.hip: resident-state plumbing
+
 // raw (n x n, ld = n, contiguous per filter) <-> padded (ld = ldp) covariance
 int launch_unpack_P(const double* raw, double* P, int N, int Np, int ldp, long strideP, int batch,
                     hipStream_t s);
 int launch_pack_P(const double* P, double* raw, int N, int ldp, long strideP, int batch, hipStream_t s);
-
-// One-filter plumbing call (dropin.hip, capi_update.hip: xivo_hip_update_joseph_host): the boundary kernels address page-locked
-// host memory directly. `block` = the staged compressed rows of the filter: ints idx[pairs_clear][ELL_W] at off_idx,
-// doubles val[pairs_clear][ELL_W][2] at off_val, inn[Mpmax] at off_inn, diagR[Mpmax] at off_R, ints {nc, pw, over} at off_flags.
-struct DropinInArgs {
-  const double* Psrc; int ldps;          // host-mapped N x N covariance (null: the device copy is current)
-  double* P; int N, Np, ldp;             // the filter's padded device covariance
-  const void* block; int off_idx, off_val, off_inn, off_R, off_flags;
-  int pairs_clear, Mpmax;
-  int* idx; double* val; double* inn; double* diagR; int* nc; int* pw; int* over;   // the filter's device buffers
-};
-struct DropinOutArgs {
-  const double* P; int N, ldp;           // the filter's padded device covariance
-  double* Pdst; int ldpd;                // host-mapped destination (null: P stays on the device)
-  const double* err; double* err_dst;    // dx [N]
-  const int* status; const int* ldlt_used; int* flags_dst;   // -> {status, ldlt_used}
-};
-int launch_dropin_in(const DropinInArgs& a, hipStream_t s);
-int launch_dropin_out(const DropinOutArgs& a, hipStream_t s);
 
 // raw H (M x N, ld = M), inn (M), diagR (M)  ->  padded H (Mp x Np, ld ldh),
 // H^T (Np x Mp, ld ldht), inn (Mp, zero pad), diagR (Mp, pad = 1)
@@ -40,35 +26,41 @@ struct MeasBuffers {
 };
 int launch_unpack_meas(const double* rawH, long strideRaw, int ldraw, const int* only_if, MeasBuffers mb,
                        int M, int Mp, int N, int Np, int batch, hipStream_t s);
-
-// P edits (SURVEY a17)
 // H^T rebuilt from the dense H of every filter (the G-level producers may skip writing it: capi_glevel.hip, ht_valid)
 int launch_transpose_H(const double* H, long strideH, int ldh, double* HT, long strideHT, int ldht, int Mp, int Np, int batch,
                        hipStream_t s);
+
+// P edits (SURVEY a17)
 int launch_p_zero_rc(double* P, int ldp, int Np, int off, int len, hipStream_t s);
 int launch_p_copy_rc(double* P, int ldp, int Np, int dst, int src, int len, hipStream_t s);
 int launch_p_diag(const double* P, int ldp, int N, double* out, hipStream_t s);
 
-// dense-row Mahalanobis gating (update.cpp:60-96) + neutralising rejected rows
-struct GateDenseArgs {
-  const double* H; long strideH; int ldh;       // candidate rows (J of feature f = rows 2f, 2f+1)
-  const double* HP; long strideHP; int ldhp;    // H * P of the same rows
-  double* Hw; double* HTw; long strideHT; int ldht;  // H / H^T to neutralise
-  double* HPw; double* PHTw;                         // optional: HP / (HP)^T rows to neutralise too
-  const double* PHTr;                                // (HP)^T = P H^T of the candidate rows [Np x Mp]
-  double* inn; long strideInn;
-  double* diagR; long strideR;
-  unsigned char* mask; double* dist;            // [batch x F]  (row stride mask_ld when it is set)
-  int F, Np, batch;
-  double R, thresh, mult; int min_inliers;
-  EllBuffers ell; int have_ell;                 // also zero the rejected pairs of the compressed form (ell.h)
-  int mask_ld;                                  // 0: rows of mask / dist are F entries apart
-  const xivo_feat_in* feats; int Fmax;          // optional [batch x Fmax]: entries with sind < 0 are absent (ragged batches)
-  int no_relax;                                 // 1: inlier <=> distance < thresh, no relaxation loop (min_inliers = -1: every filter tested)
+// batched resident edits (xivo_hip_edit_batch): wg_filter[w] = filter of workgroup w, its ops are
+// ops[wg_begin[w] .. wg_begin[w + 1])
+struct EditArgs {
+  const xivo_edit_op* ops; const int* wg_filter; const int* wg_begin;
+  double* P; long strideP; int ldp, Np; xivo_layout lay;
+  xivo_pose_in* poses; xivo_group_in* groups; xivo_feat_in* feats; int Fmax;
+  xivo_subfilter_feat* pool; PoolAnchor* anchors; int pool_max, anchor_max;   // null / 0: no pool configured
 };
-int launch_gate_dense(const GateDenseArgs& a, hipStream_t s);
+int launch_edit_batch(const EditArgs& a, int n_wg, hipStream_t s);
+int launch_set_pixels(xivo_feat_in* feats /* already offset to b0 */, int Fmax, int F, const double* xp, int nb, hipStream_t s);
 
-// G-level kernels
+// AbsorbError on the resident scene (estimator.cpp:875-921)
+struct AbsorbArgs {
+  xivo_pose_in* poses; xivo_group_in* groups; xivo_feat_in* feats; const unsigned char* mask;
+  double* err; long strideErr; xivo_layout lay; int F, Fmax, batch;
+  const int* status;   // [batch] factorisation status of the update that produced err: non-zero -> nothing is absorbed, err <- 0
+  const unsigned long long* group_mask;   // optional [batch]: bit g = group slot g is in instate_groups_ (null: every slot)
+  int* counter;   // [batch] State::counter (core.h:120-122): absorbs so far, drives the periodic SO3 re-normalisation
+  xivo_calib_in* calib; xivo_calib_layout cl;   // online-calibration builds: td / Cg / Ca / intrinsics retracted too (null: default build)
+};
+int launch_absorb_error(const AbsorbArgs& a, hipStream_t s);
+
+int launch_mfma_peak(double* sink, int iters, int blocks, hipStream_t s);
+
+// ================================================================ glevel_kernels.hip: feature-level kernels (capi_glevel.hip)
+
 struct SceneBuffers {
   const xivo_pose_in* poses;     // [batch]
   const xivo_group_in* groups;   // [batch x n_groups]
@@ -97,6 +89,26 @@ int launch_gate_sparse(const GateArgs& a, hipStream_t s);
 // gate_sparse_kernel: threads per filter - 1024 below 256 filters, 256 from there, halved while the LDS passes 64 KB
 // (online-calibration builds, wide != 0, carry more scratch per wave)
 int gate_sparse_threads(int batch, int F, int wide, char* label, size_t n);
+
+// dense-row Mahalanobis gating (update.cpp:60-96) + neutralising rejected rows
+struct GateDenseArgs {
+  const double* H; long strideH; int ldh;       // candidate rows (J of feature f = rows 2f, 2f+1)
+  const double* HP; long strideHP; int ldhp;    // H * P of the same rows
+  double* Hw; double* HTw; long strideHT; int ldht;  // H / H^T to neutralise
+  double* HPw; double* PHTw;                         // optional: HP / (HP)^T rows to neutralise too
+  const double* PHTr;                                // (HP)^T = P H^T of the candidate rows [Np x Mp]
+  double* inn; long strideInn;
+  double* diagR; long strideR;
+  unsigned char* mask; double* dist;            // [batch x F]  (row stride mask_ld when it is set)
+  int F, Np, batch;
+  double R, thresh, mult; int min_inliers;
+  EllBuffers ell; int have_ell;                 // also zero the rejected pairs of the compressed form (ell.h)
+  int mask_ld;                                  // 0: rows of mask / dist are F entries apart
+  const xivo_feat_in* feats; int Fmax;          // optional [batch x Fmax]: entries with sind < 0 are absent (ragged batches)
+  int no_relax;                                 // 1: inlier <=> distance < thresh, no relaxation loop (min_inliers = -1: every filter tested)
+};
+int launch_gate_dense(const GateDenseArgs& a, hipStream_t s);
+
 struct StackArgs {
   SceneBuffers sb; xivo_layout lay; MeasBuffers mb;
   int Mp, Np, batch; double R; int fix_group_block;
@@ -108,98 +120,6 @@ struct StackArgs {
   double* lead; long strideLead; int lead_k;
 };
 int launch_stack(const StackArgs& a, hipStream_t s);
-
-// Feature::SubfilterUpdate + candidate tests (feature.cpp:246-297, options.cpp:10-33)
-int launch_subfilter(xivo_subfilter_feat* feats, int n, const xivo_pose_in* poses, const xivo_group_in* groups,
-                     int n_groups, xivo_cam cam, xivo_subfilter_opts o, int batch, hipStream_t s,
-                     const xivo_calib_in* calib = nullptr, int cam_dim = 0, int invdepth = 0);
-
-// One anchor of the out-of-state feature pool (xivo_hip_pool_config): the frozen pose of its group and the in-state group slot
-// it is linked to (-1: unlinked, the frozen pose is the anchor's pose)
-struct PoolAnchor {
-  xivo_group_in g;
-  int slot, reserved;
-};
-// Out-of-state feature pool (xivo_hip_pool_*): entries are xivo_subfilter_feat with ref_sind = the entry's anchor (-1: free)
-int launch_pool_anchor(PoolAnchor* anchors, int anchor_max, const xivo_pose_in* poses, const int* slot, int nb, hipStream_t s);
-int launch_pool_add(xivo_subfilter_feat* pool, int pool_max, const xivo_pool_new* recs, int n, xivo_cam cam,
-                    const xivo_calib_in* calib, int cam_dim, int invdepth, hipStream_t s);
-struct PoolStepArgs {
-  xivo_subfilter_feat* pool; const PoolAnchor* anchors; int pool_max, anchor_max;   // [batch][pool_max] / [batch][anchor_max]
-  const xivo_pose_in* poses; const xivo_group_in* groups; int n_groups;
-  xivo_cam cam; const xivo_calib_in* calib; int cam_dim, invdepth;
-  xivo_subfilter_opts o; double remove_outlier; int strict, batch;
-  const double* xp;                                  // [batch][pool_max][2]
-  int* order; int* n; unsigned char* live;           // out: [batch][pool_max], [batch], [batch][pool_max]
-};
-int launch_pool_step(const PoolStepArgs& a, hipStream_t s);
-
-// Estimator::Propagate state + covariance stages (rk4.cpp, princedormand.cpp, estimator.cpp:598-704): one wave per
-// filter; writes the accumulated transition Phi and the new P_mm (23 x 23 each, column-major) for the tail kernel
-struct PropStateArgs {
-  xivo_pose_in* poses; const xivo_imu_in* imu;      // [nb] / [nb][n_imu] (poses already offset to b0)
-  int n_imu;
-  const double* Qimu; const double* Qmodel;         // device copies
-  double g[3]; int method; double stepsize;
-  const double* P; long strideP; int ldp;           // resident covariance (offset to b0)
-  double* Phi_out; double* Pmm_out;                 // [nb][529] ([nb][nm * nm] for the calibration kernel)
-  int batch;
-  // online-calibration builds (launch_propagate_state_calib): motion size, slot of Cg (-1: none; Ca follows at + 9), the
-  // resident calibration state (offset to b0); Qmodel is nm x nm
-  int nm, iCg; const xivo_calib_in* calib;
-  // step-size-controlled Dormand-Prince (princedormand.cpp:26-60; default-build kernel only): the per-filter step carried between
-  // samples and calls (the reference's function-local static h), null = fixed steps
-  double* pd_h; double pd_tol, pd_min_scale, pd_max_scale;
-};
-int launch_propagate_state(const PropStateArgs& a, hipStream_t s);
-int launch_propagate_state_calib(const PropStateArgs& a, hipStream_t s);
-
-// xivo::Givens / xivo::QR (helpers.cpp:27-101), one wave per problem, in place
-struct GivensArgs {
-  double* x; double* Hx; double* Hf;   // per problem: x [rows], Hx [rows x nx], Hf [rows x nf] (null for QR)
-  int rows, nx, nf, eff, batch, qr;
-};
-int launch_givens(const GivensArgs& a, hipStream_t s);
-
-// AbsorbError on the resident scene (estimator.cpp:875-921)
-struct AbsorbArgs {
-  xivo_pose_in* poses; xivo_group_in* groups; xivo_feat_in* feats; const unsigned char* mask;
-  double* err; long strideErr; xivo_layout lay; int F, Fmax, batch;
-  const int* status;   // [batch] factorisation status of the update that produced err: non-zero -> nothing is absorbed, err <- 0
-  const unsigned long long* group_mask;   // optional [batch]: bit g = group slot g is in instate_groups_ (null: every slot)
-  int* counter;   // [batch] State::counter (core.h:120-122): absorbs so far, drives the periodic SO3 re-normalisation
-  xivo_calib_in* calib; xivo_calib_layout cl;   // online-calibration builds: td / Cg / Ca / intrinsics retracted too (null: default build)
-};
-int launch_absorb_error(const AbsorbArgs& a, hipStream_t s);
-
-// Estimator::OnePointRANSAC on the resident state (update.cpp:213-393): selection, P zeroing, rescue test
-struct RansacArgs {
-  SceneBuffers sb; xivo_layout lay;
-  const double* P; long strideP; int ldp; int Np;
-  double R, thresh, chi2;
-  const int* gauge;                 // [batch] slot of gauge_group_ptr_ (-1: none), may be null
-  unsigned char* low;               // [batch x Fmax] out: low-innovation set (all 0 for filters in state 0 / 2)
-  const unsigned char* low_keep;    // rescue: the set select found (a copy - `low` doubles as the stacking mask)
-  unsigned long long* zero_groups;  // [batch] out
-  int* state;                       // [batch] out: 0 nothing to do, 1 partial update + rescue, 2 rescue against the prior
-  unsigned char* keep; double* chi; int* n_rejected;   // rescue outputs
-  int batch;
-};
-int launch_ransac_select(const RansacArgs& a, hipStream_t s);
-int launch_ransac_zero(const RansacArgs& a, double* P, hipStream_t s);
-int launch_ransac_rescue(const RansacArgs& a, hipStream_t s);
-int launch_ransac_rescue_dist(const RansacArgs& a, const double* dist /* [batch x ld] */, int ld, hipStream_t s);
-
-// batched resident edits (xivo_hip_edit_batch): wg_filter[w] = filter of workgroup w, its ops are
-// ops[wg_begin[w] .. wg_begin[w + 1])
-struct EditArgs {
-  const xivo_edit_op* ops; const int* wg_filter; const int* wg_begin;
-  double* P; long strideP; int ldp, Np; xivo_layout lay;
-  xivo_pose_in* poses; xivo_group_in* groups; xivo_feat_in* feats; int Fmax;
-  xivo_subfilter_feat* pool; PoolAnchor* anchors; int pool_max, anchor_max;   // null / 0: no pool configured
-};
-int launch_edit_batch(const EditArgs& a, int n_wg, hipStream_t s);
-int launch_set_pixels(xivo_feat_in* feats /* already offset to b0 */, int Fmax, int F, const double* xp, int nb, hipStream_t s);
 
 // OOS (MSCKF) rows: oos.cpp:39-89 + helpers.cpp:13-23
 struct OosArgs {
@@ -240,19 +160,90 @@ int oos_compress_pick(int n_groups, int rows_max, char* label, size_t n);
 // returns -1 (nothing launched) when the block is larger than the built instantiations
 int launch_oos_compress(const OosCompressArgs& a, int rows_max, hipStream_t s);
 
+// xivo::Givens / xivo::QR (helpers.cpp:27-101), one wave per problem, in place
+struct GivensArgs {
+  double* x; double* Hx; double* Hf;   // per problem: x [rows], Hx [rows x nx], Hf [rows x nf] (null for QR)
+  int rows, nx, nf, eff, batch, qr;
+};
+int launch_givens(const GivensArgs& a, hipStream_t s);
+
+// Estimator::OnePointRANSAC on the resident state (update.cpp:213-393): selection, P zeroing, rescue test
+struct RansacArgs {
+  SceneBuffers sb; xivo_layout lay;
+  const double* P; long strideP; int ldp; int Np;
+  double R, thresh, chi2;
+  const int* gauge;                 // [batch] slot of gauge_group_ptr_ (-1: none), may be null
+  unsigned char* low;               // [batch x Fmax] out: low-innovation set (all 0 for filters in state 0 / 2)
+  const unsigned char* low_keep;    // rescue: the set select found (a copy - `low` doubles as the stacking mask)
+  unsigned long long* zero_groups;  // [batch] out
+  int* state;                       // [batch] out: 0 nothing to do, 1 partial update + rescue, 2 rescue against the prior
+  unsigned char* keep; double* chi; int* n_rejected;   // rescue outputs
+  int batch;
+};
+int launch_ransac_select(const RansacArgs& a, hipStream_t s);
+int launch_ransac_zero(const RansacArgs& a, double* P, hipStream_t s);
+int launch_ransac_rescue(const RansacArgs& a, hipStream_t s);
+int launch_ransac_rescue_dist(const RansacArgs& a, const double* dist /* [batch x ld] */, int ld, hipStream_t s);
+
+// ================================================================ pool_kernels.hip: depth sub-filter and feature pool
+
+// Feature::SubfilterUpdate + candidate tests (feature.cpp:246-297, options.cpp:10-33)
+int launch_subfilter(xivo_subfilter_feat* feats, int n, const xivo_pose_in* poses, const xivo_group_in* groups,
+                     int n_groups, xivo_cam cam, xivo_subfilter_opts o, int batch, hipStream_t s,
+                     const xivo_calib_in* calib = nullptr, int cam_dim = 0, int invdepth = 0);
+
+// One anchor of the out-of-state feature pool (xivo_hip_pool_config): the frozen pose of its group and the in-state group slot
+// it is linked to (-1: unlinked, the frozen pose is the anchor's pose)
+struct PoolAnchor {
+  xivo_group_in g;
+  int slot, reserved;
+};
+// Out-of-state feature pool (xivo_hip_pool_*): entries are xivo_subfilter_feat with ref_sind = the entry's anchor (-1: free)
+int launch_pool_anchor(PoolAnchor* anchors, int anchor_max, const xivo_pose_in* poses, const int* slot, int nb, hipStream_t s);
+int launch_pool_add(xivo_subfilter_feat* pool, int pool_max, const xivo_pool_new* recs, int n, xivo_cam cam,
+                    const xivo_calib_in* calib, int cam_dim, int invdepth, hipStream_t s);
+struct PoolStepArgs {
+  xivo_subfilter_feat* pool; const PoolAnchor* anchors; int pool_max, anchor_max;   // [batch][pool_max] / [batch][anchor_max]
+  const xivo_pose_in* poses; const xivo_group_in* groups; int n_groups;
+  xivo_cam cam; const xivo_calib_in* calib; int cam_dim, invdepth;
+  xivo_subfilter_opts o; double remove_outlier; int strict, batch;
+  const double* xp;                                  // [batch][pool_max][2]
+  int* order; int* n; unsigned char* live;           // out: [batch][pool_max], [batch], [batch][pool_max]
+};
+int launch_pool_step(const PoolStepArgs& a, hipStream_t s);
+
+// ================================================================ propagate_kernels.hip: propagation (capi_propagate.hip)
+
+// Estimator::Propagate state + covariance stages (rk4.cpp, princedormand.cpp, estimator.cpp:598-704): one wave per
+// filter; writes the accumulated transition Phi and the new P_mm (23 x 23 each, column-major) for the tail kernel
+struct PropStateArgs {
+  xivo_pose_in* poses; const xivo_imu_in* imu;      // [nb] / [nb][n_imu] (poses already offset to b0)
+  int n_imu;
+  const double* Qimu; const double* Qmodel;         // device copies
+  double g[3]; int method; double stepsize;
+  const double* P; long strideP; int ldp;           // resident covariance (offset to b0)
+  double* Phi_out; double* Pmm_out;                 // [nb][529] ([nb][nm * nm] for the calibration kernel)
+  int batch;
+  // online-calibration builds (launch_propagate_state_calib): motion size, slot of Cg (-1: none; Ca follows at + 9), the
+  // resident calibration state (offset to b0); Qmodel is nm x nm
+  int nm, iCg; const xivo_calib_in* calib;
+  // step-size-controlled Dormand-Prince (princedormand.cpp:26-60; default-build kernel only): the per-filter step carried between
+  // samples and calls (the reference's function-local static h), null = fixed steps
+  double* pd_h; double pd_tol, pd_min_scale, pd_max_scale;
+};
+int launch_propagate_state(const PropStateArgs& a, hipStream_t s);
+int launch_propagate_state_calib(const PropStateArgs& a, hipStream_t s);
+
 // propagation tail (rk4.cpp:92-102): the kernel for motion size nm (propagate_cov_fixed_kernel<23> for 23, else
 // propagate_cov_kernel) and the passes of 256 tail columns it makes over N - nm; -1 for nm outside 1..40 (MAXM)
 int propagate_cov_pick(int nm, int N, char* label, size_t n);
 int launch_propagate_cov(double* P, long strideP, int ldp, int N, int Np, int nm, const double* Phi,
                          const double* Pmm, int b0, int nb, hipStream_t s);
 
-int launch_mfma_peak(double* sink, int iters, int blocks, hipStream_t s);
+// ================================================================ ldlt_fallback.hip
 
 // Diagonally pivoted L D L^T fallback (Eigen's S.ldlt().solve of src/estimator.cpp:1266) + the as-coded Joseph update for
 // the filters whose status is non-zero (ldlt_fallback.hip); clears their status and sets used[filt]
-}  // namespace xivo_hip
-#include "ell.h"
-namespace xivo_hip {
 struct LdltFallbackArgs {
   int* status; int* used;
   EllBuffers ell; const double* H; long strideH; int ldh; int use_dense;
@@ -270,5 +261,26 @@ struct LdltFallbackArgs {
   int N, M, batch;
 };
 int launch_ldlt_fallback(const LdltFallbackArgs& a, hipStream_t s);
+
+// ================================================================ dropin.hip
+
+// One-filter plumbing call (dropin.hip, capi_update.hip: xivo_hip_update_joseph_host): the boundary kernels address page-locked
+// host memory directly. `block` = the staged compressed rows of the filter: ints idx[pairs_clear][ELL_W] at off_idx,
+// doubles val[pairs_clear][ELL_W][2] at off_val, inn[Mpmax] at off_inn, diagR[Mpmax] at off_R, ints {nc, pw, over} at off_flags.
+struct DropinInArgs {
+  const double* Psrc; int ldps;          // host-mapped N x N covariance (null: the device copy is current)
+  double* P; int N, Np, ldp;             // the filter's padded device covariance
+  const void* block; int off_idx, off_val, off_inn, off_R, off_flags;
+  int pairs_clear, Mpmax;
+  int* idx; double* val; double* inn; double* diagR; int* nc; int* pw; int* over;   // the filter's device buffers
+};
+struct DropinOutArgs {
+  const double* P; int N, ldp;           // the filter's padded device covariance
+  double* Pdst; int ldpd;                // host-mapped destination (null: P stays on the device)
+  const double* err; double* err_dst;    // dx [N]
+  const int* status; const int* ldlt_used; int* flags_dst;   // -> {status, ldlt_used}
+};
+int launch_dropin_in(const DropinInArgs& a, hipStream_t s);
+int launch_dropin_out(const DropinOutArgs& a, hipStream_t s);
 
 }  // namespace xivo_hip

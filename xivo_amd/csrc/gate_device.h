@@ -1,4 +1,4 @@
-// Device helpers shared by the gating kernels (ekf_kernels.hip, ell_kernels.hip):
+// Device helpers shared by the gating kernels (glevel_kernels.hip, ell_kernels.hip):
 // the numeric core of Estimator::MHGating, src/update.cpp:60-96.
 #pragma once
 #include <hip/hip_runtime.h>
