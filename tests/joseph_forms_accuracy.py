@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """How far each way of evaluating the Joseph update lands from an extended-precision evaluation of the reference's
-expression (estimator.cpp:1257-1288 in numpy longdouble, 64-bit mantissa), as cond(S) grows:
+expression (estimator.cpp:1257-1288 in numpy longdouble, 64-bit mantissa: tests/precise_ref.py), as cond(S) grows:
   oracle     the as-coded fp64 sequence on the CPU (oracle/xivo_oracle.py)
   in_solve   library default: whitened form P - (W - D)^T (W + D) inside the solve kernel (trsm_lds_f64_kernel<.,4>)
   fused      the one-kernel route of round 6 at the same form (fused_update_f64_kernel); in_solve runs with XIVO_HIP_FLAG_MULTI_KERNEL
@@ -12,6 +12,8 @@ import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import numpy as np
+
+import precise_ref
 
 N, F, B = 150, 40, 2
 
@@ -33,25 +35,9 @@ def cases():
 
 
 def extended(H, P, R):
-    ld = np.longdouble
-    H, P = H.astype(ld), P.astype(ld)
-    S = H @ P @ H.T + np.diag(R.astype(ld))
-    # gain by extended-precision Cholesky + substitution (numpy.linalg has no longdouble solve)
-    M = S.shape[0]
-    L = np.zeros_like(S)
-    for j in range(M):
-        L[j, j] = np.sqrt(S[j, j] - L[j, :j] @ L[j, :j])
-        L[j + 1:, j] = (S[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
-    Y = np.zeros_like(H @ P)
-    HP = H @ P
-    for i in range(M):
-        Y[i] = (HP[i] - L[i, :i] @ Y[:i]) / L[i, i]
-    Kt = np.zeros_like(Y)
-    for i in range(M - 1, -1, -1):
-        Kt[i] = (Y[i] - L[i + 1:, i] @ Kt[i + 1:]) / L[i, i]
-    K = Kt.T
-    A = np.eye(P.shape[0], dtype=ld) - K @ H
-    return A @ P @ A.T + (K * R.astype(ld)) @ K.T, np.linalg.cond(S.astype(np.float64))
+    """(P+, cond(S)) of the extended-precision reference (tests/precise_ref.py)"""
+    ref = precise_ref.extended(H, P, np.zeros(len(R)), R)
+    return ref.P, ref.kappa
 
 
 def gpu(flags):

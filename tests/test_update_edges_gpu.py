@@ -7,14 +7,16 @@ nwl = round16(N) / 16, common columns nc and private columns per row pair pw of 
 first checks that the compressed form of its generated H really has those values (xivo_hip_selftest_host_compress), so a
 case cannot drift onto another route unnoticed. Then: status 0, no L D L^T fallback, the route the table names, for the
 one-kernel route the exact kernel label (the FLAG_PROFILE stage record), P+ within TOL_P, dx within TOL_DX, P+ exactly
-symmetric. tests/test_dropin_cpu.py checks on the host that EDGE_CASES reaches every instantiation the admission test can
-pick, and that every fused case's label is the one the library would launch."""
+symmetric; and in addition P+ (relative and in units of the prior correlation) and dx against the extended-precision reference
+of tests/precise_ref.py within 8 u (kappa_2(S) + N). tests/test_dropin_cpu.py checks on the host that EDGE_CASES reaches every
+instantiation the admission test can pick, and that every fused case's label is the one the library would launch."""
 import zlib
 
 import ctypes as C
 import numpy as np
 import pytest
 
+import precise_ref as pr
 import xivo_oracle as orc
 from helpers import rel_fro, TOL_P, TOL_DX
 from xivo_amd import synth
@@ -118,6 +120,7 @@ EDGE_CASES = [
     ("batch_one_pw10_b8", 203, 60, 4, 13, 12, (6, 9, 6, 6, 6, 6, 10, 6), 8, 0, "sparse_whitened", LAT % 4, "j", "gen"),
 ]
 CASES = {c[0]: c for c in EDGE_CASES}
+_REFS = {}                    # (case, gated) -> the extended-precision references of its distinct filters
 GATE = (5.991, 1.1, 5)        # MH threshold, relaxation, min inliers (src/update.cpp:60-96)
 R = 2.25
 
@@ -231,6 +234,17 @@ def test_update_at_the_edges(built, name, entry):
         assert rel_fro(Pn[b], P_ref) < TOL_P, (b, rel_fro(Pn[b], P_ref))
         assert rel_fro(err[b], e_ref) < TOL_DX, (b, rel_fro(err[b], e_ref))
         assert np.array_equal(Pn[b], Pn[b].T)
+    # the same results against the extended-precision reference (filters b and b + 8 of a batch are the same filter)
+    nd = min(B, 8)
+    key = (name, gated)
+    if key not in _REFS or len(_REFS[key]) < nd:
+        keep = [np.repeat(mask[b].astype(bool), 2) for b in range(nd)] if gated else None
+        _REFS[key] = pr.extended_batch(H[:nd], P[:nd], inn[:nd], dR[:nd], keep)
+    worst = np.zeros(3)
+    for b in range(B):
+        r = pr.check(_REFS[key][b % nd], Pn[b], err[b], what=(name, entry, b))
+        worst = np.maximum(worst, r)
+    print("accuracy %s %s-%s: rel %.3f corr %.3f dx %.3f x u (kappa + N)" % (route, name, entry, *worst))
 
 
 def test_create_factor_limit(built):
