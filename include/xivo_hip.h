@@ -510,6 +510,78 @@ int xivo_hip_pool_step(xivo_hip_ctx* ctx, int B, const double* xp, int strict, i
 int xivo_hip_pool_get(xivo_hip_ctx* ctx, int b0, int nb, xivo_subfilter_feat* entries /* nb x pool_max */,
                       xivo_group_in* anchor_poses /* nb x anchor_max */, int* anchor_slots /* nb x anchor_max */);
 
+/* ---- depth initialisation of new tracks: pre-sub-filter triangulation and AdaptInitialDepth ----
+ * Two-view triangulation (Feature::Triangulate, src/feature.cpp:686-751) with the five triangulators of src/helpers.cpp:103-371.
+ * Frame 1 is the anchor camera, frame 2 the current camera; g12 = (anchor gsb * gbc)^-1 (gsb * gbc) maps frame-2 points into
+ * frame 1, X is returned in frame 1. The reference's float narrowing is reproduced AS CODED: a0 / a1 (L1), lambda0 / lambda1
+ * (check_cheirality), theta0 / theta1 / beta (check_angular_reprojection / check_parallax) and both thresholds are float,
+ * everything else fp64. DIRECT_LINEAR_TRANSFORM_SVD takes the null vector of the 4x4 A from a one-sided Jacobi SVD (fixed
+ * sweep count) and returns X = V(0:3,3) / V(3,3), as coded; L2_ANGULAR takes V.col(1) of the 2x3 B in closed form (B t^ = 0:
+ * the minor eigenvector of B^T B in the plane perpendicular to t^; its sign does not enter the result). The depth range is
+ * tested as zmin <= z <= zmax, so a NaN depth counts as a bad triangulation. */
+enum {
+  XIVO_TRI_OFF = 0,
+  XIVO_TRI_DLT_SVD = 1,   /* "direct_linear_transform_svd" */
+  XIVO_TRI_DLT_AVG = 2,   /* "direct_linear_transform_avg" */
+  XIVO_TRI_L1 = 3,        /* "l1_angular" (the reference default, src/estimator.cpp:159) */
+  XIVO_TRI_L2 = 4,        /* "l2_angular"   */
+  XIVO_TRI_LINF = 5       /* "linf_angular" */
+};
+typedef struct {
+  int struct_size;          /* sizeof(xivo_triangulate_opts) */
+  int method;               /* XIVO_TRI_* */
+  double zmin, zmax;        /* cfg triangulation zmin / zmax (0.05, 5.0) */
+  double max_theta_thresh;  /* radians: the caller converts the cfg's degrees (src/estimator.cpp:163-164); used as float */
+  double beta_thresh;       /* radians (cfg key "beta_thesh"); used as float */
+} xivo_triangulate_opts;
+typedef struct {
+  double R12[9];   /* rotation of g12, column-major */
+  double t12[3];   /* translation of g12 */
+  double xc1[2];   /* UnProject(front()): normalised coordinates in the anchor camera */
+  double xc2[2];   /* UnProject(back()): normalised coordinates in the current camera */
+} xivo_tri_in;
+typedef struct {
+  double X[3];     /* the triangulated point in frame 1 (written whatever the return value, as the reference does) */
+  int ret;         /* the triangulator's return value */
+  int good;        /* ret && zmin <= X[2] <= zmax: Feature::Triangulate would set x = (X/z, Y/z, log z) */
+} xivo_tri_out;
+/* Stand-alone, batched: n problems from host arrays, one device thread each */
+int xivo_hip_triangulate(xivo_hip_ctx* ctx, int n, const xivo_tri_in* in, xivo_tri_out* out, const xivo_triangulate_opts* opts);
+/* triangulate_pre_subfilter for the pool (xivo_hip_pool_config): opts NULL or method XIVO_TRI_OFF disables it, the state
+ * after xivo_hip_pool_config. While enabled, xivo_hip_pool_step triangulates every live entry at its first step (init_counter
+ * == 0, the reference's f->size() == 2; src/manager.cpp:227-231) with this frame's pixel, before the sub-filter step (a
+ * kernel of its own, launched only while enabled, ahead of the step): g12 from the entry's anchor pose and the filter's
+ * current pose, xc1 = x[0:2], xc2 = UnProject(current pixel) with the filter's own intrinsics under camera calibration. x[0:2] equals UnProject(front()) at that point because only the
+ * sub-filter step, which also increments init_counter, writes x after xivo_hip_pool_add; the kernel checks init_counter == 0
+ * itself. A good triangulation sets x = (X/z, Y/z, log z) - 1/z under XIVO_HIP_FLAG_INVDEPTH -, P is left as it is. */
+int xivo_hip_pool_triangulation(xivo_hip_ctx* ctx, const xivo_triangulate_opts* opts);
+/* num_good_triangulations_ / num_bad_triangulations_ summed per filter over [b0, b0 + nb) since xivo_hip_pool_config; either
+ * pointer may be NULL */
+int xivo_hip_pool_tri_counts(xivo_hip_ctx* ctx, int b0, int nb, int* good_out, int* bad_out);
+/* AdaptInitialDepth (src/manager.cpp:255-278). Each filter keeps a resident init_z, set to initial_z for every filter by
+ * xivo_hip_pool_adapt_depth_config (and by xivo_hip_pool_config, to 0: unset). */
+typedef struct {
+  int struct_size;            /* sizeof(xivo_adapt_depth_opts) */
+  int min_feature_lifetime;   /* cfg adaptive_initial_depth.minimum_feature_lifetime (5) */
+  double initial_z;           /* cfg initial_z */
+  double median_weight;       /* cfg adaptive_initial_depth.median_weight (0.99) */
+  double min_z, max_z;        /* cfg min_depth / max_depth */
+} xivo_adapt_depth_opts;
+int xivo_hip_pool_adapt_depth_config(xivo_hip_ctx* ctx, const xivo_adapt_depth_opts* opts);
+/* One workgroup per filter of [0, B). The depth set is the in-state features of the resident feature list (sind >= 0, z from
+ * x[2]: exp, or 1/x under XIVO_HIP_FLAG_INVDEPTH) and the live READY pool entries whose lifetime exceeds
+ * min_feature_lifetime. An entry's lifetime is its init_counter: the pool frees an entry in the first frame it is not
+ * tracked, so the number of frames it lived through after its first is the number of sub-filter steps it took. Non-finite
+ * depths are left out of the set (the reference would place a NaN wherever its iteration order puts it). m = the order
+ * statistic of rank floor(n / 2); min_z <= m <= max_z: init_z <- (1 - beta) init_z + beta m, otherwise (or n = 0) init_z
+ * stays. DEVIATION: the reference takes depth[n >> 1] in std::unordered_map iteration order, unsorted - an order that is not
+ * a property of the input; this is the median the code names. init_z_out (host [B], may be NULL): init_z afterwards. */
+int xivo_hip_pool_adapt_depth(xivo_hip_ctx* ctx, int B, double* init_z_out);
+/* xivo_hip_pool_add with options: XIVO_POOL_ADD_ADAPTIVE_Z takes z0 from the filter's resident init_z instead of the record
+ * (the record's z0 is then ignored; xivo_hip_pool_adapt_depth_config must have run). options = 0 is xivo_hip_pool_add. */
+#define XIVO_POOL_ADD_ADAPTIVE_Z 1u
+int xivo_hip_pool_add_ex(xivo_hip_ctx* ctx, int n, const xivo_pool_new* recs, unsigned options);
+
 /* ---- Estimator::Propagate on the device-resident state ----
  * For filters [b0, b0 + nb): integrates the nominal motion state (Rsb, Tsb, Vsb, bg, ba, Rsg of the resident
  * xivo_pose_in, xivo_hip_set_scene) over dt with RK4Step (src/rk4.cpp:35-103) or PrinceDormandStep

@@ -28,6 +28,11 @@ batch_subfilter_cfg_dtype = np.dtype([("initial_z", "f8"), ("remove_outlier_coun
                                       ("anchor_max", "i4")])
 
 
+# struct xivo_batch_depth_init_cfg (xivo_amd/host/batch_estimator.cpp): triangulation / AdaptInitialDepth of new tracks
+batch_depth_init_cfg_dtype = np.dtype([("triangulate", "i4"), ("adaptive", "i4"), ("tri", L.tri_opts_dtype),
+                                       ("std_badtri", "f8", 3), ("adapt", L.adapt_opts_dtype)])
+
+
 def load_host_library():
     """libxivo_host.so (C++ adapter + batch estimator); raises if it has not been built - there is no fallback."""
     global _HOST
@@ -49,6 +54,8 @@ def load_host_library():
         _HOST.xivo_batch_enable_subfilter.argtypes = [C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_pool_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]
         _HOST.xivo_batch_pool_stats.restype = None
+        _HOST.xivo_batch_enable_depth_init.argtypes = [C.c_void_p, C.c_void_p]
+        _HOST.xivo_batch_init_z.argtypes = [C.c_void_p, C.c_void_p]
     return _HOST
 
 
@@ -91,6 +98,26 @@ class BatchEstimator:
             sc["pool_max"], sc["anchor_max"] = cfg.pool_max, cfg.anchor_max
             if self.host.xivo_batch_enable_subfilter(self.h, sc.ctypes.data) != 0:
                 raise RuntimeError("xivo_batch_enable_subfilter failed")
+            tri_on, adapt_on = bool(getattr(cfg, "triangulate_pre_subfilter", False)), bool(getattr(cfg, "adaptive_initial_depth", False))
+            if tri_on or adapt_on:
+                dc = np.zeros(1, dtype=batch_depth_init_cfg_dtype)
+                dc["triangulate"], dc["adaptive"] = int(tri_on), int(adapt_on)
+                t = cfg.triangulation
+                dc["tri"] = L.tri_options(t["method"], t["zmin"], t["zmax"], t["max_theta_thresh"], t["beta_thresh"])
+                dc["std_badtri"] = [cfg.initial_std_x_badtri, cfg.initial_std_y_badtri, cfg.initial_std_z_badtri]
+                a = dc["adapt"]
+                a["struct_size"] = L.adapt_opts_dtype.itemsize
+                a["initial_z"], a["median_weight"] = cfg.initial_z, cfg.adaptive_depth["median_weight"]
+                a["min_feature_lifetime"] = cfg.adaptive_depth["minimum_feature_lifetime"]
+                a["min_z"], a["max_z"] = cfg.min_depth, cfg.max_depth
+                dc["adapt"] = a
+                if self.host.xivo_batch_enable_depth_init(self.h, dc.ctypes.data) != 0:
+                    raise RuntimeError("xivo_batch_enable_depth_init failed")
+
+    def init_z(self):
+        """AdaptInitialDepth's init_z [B] after the last frame (None while adaptive_initial_depth is off)"""
+        z = np.zeros(self.B)
+        return z if self.host.xivo_batch_init_z(self.h, z.ctypes.data) == 0 else None
 
     def close(self):
         if self.h:

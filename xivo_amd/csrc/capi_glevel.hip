@@ -706,10 +706,17 @@ int xivo_hip_pool_config(xivo_hip_ctx* c, int pool_max, int anchor_max, const xi
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (c->fpool) hipFree(c->fpool);
   if (c->anchors) hipFree(c->anchors);
-  c->fpool = nullptr; c->anchors = nullptr; c->pool_max = c->anchor_max = 0;
+  if (c->tri_counts) hipFree(c->tri_counts);
+  if (c->init_z) hipFree(c->init_z);
+  c->fpool = nullptr; c->anchors = nullptr; c->tri_counts = nullptr; c->init_z = nullptr; c->pool_max = c->anchor_max = 0;
+  c->pool_tri = xivo_triangulate_opts{}; c->adapt = xivo_adapt_depth_opts{}; c->adapt_on = false;
   const size_t ne = (size_t)c->Bmax * pool_max, na = (size_t)c->Bmax * anchor_max;
   if (hipMalloc((void**)&c->fpool, ne * sizeof(xivo_subfilter_feat)) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
   if (hipMalloc((void**)&c->anchors, na * sizeof(PoolAnchor)) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
+  if (hipMalloc((void**)&c->tri_counts, 2 * (size_t)c->Bmax * sizeof(int)) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
+  if (hipMalloc((void**)&c->init_z, (size_t)c->Bmax * sizeof(double)) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
+  HIP_TRY(hipMemsetAsync(c->tri_counts, 0, 2 * (size_t)c->Bmax * sizeof(int), c->stream));
+  HIP_TRY(hipMemsetAsync(c->init_z, 0, (size_t)c->Bmax * sizeof(double), c->stream));
   // all bytes 0xff: every entry's anchor (ref_sind) and every anchor's slot read -1 - free / unlinked
   HIP_TRY(hipMemsetAsync(c->fpool, 0xff, ne * sizeof(xivo_subfilter_feat), c->stream));
   HIP_TRY(hipMemsetAsync(c->anchors, 0xff, na * sizeof(PoolAnchor), c->stream));
@@ -743,14 +750,19 @@ int xivo_hip_pool_anchor(xivo_hip_ctx* c, int b0, int nb, const int* slot) {
   return XIVO_HIP_OK;
 }
 
-int xivo_hip_pool_add(xivo_hip_ctx* c, int n, const xivo_pool_new* recs) {
+int xivo_hip_pool_add(xivo_hip_ctx* c, int n, const xivo_pool_new* recs) { return xivo_hip_pool_add_ex(c, n, recs, 0u); }
+
+int xivo_hip_pool_add_ex(xivo_hip_ctx* c, int n, const xivo_pool_new* recs, unsigned options) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || !c->fpool || !c->have_layout || n < 0 || (n > 0 && !recs)) return XIVO_HIP_ERR_INVALID;
+  if ((options & ~XIVO_POOL_ADD_ADAPTIVE_Z) != 0u) return XIVO_HIP_ERR_INVALID;
+  const bool adaptive = (options & XIVO_POOL_ADD_ADAPTIVE_Z) != 0u;
+  if (adaptive && !c->adapt_on) return XIVO_HIP_ERR_INVALID;
   std::vector<long> keys((size_t)n);
   for (int i = 0; i < n; ++i) {
     const xivo_pool_new& r = recs[i];
     if (r.b < 0 || r.b >= c->Bmax || r.entry < 0 || r.entry >= c->pool_max || r.anchor < 0 || r.anchor >= c->anchor_max ||
-        c->anchor_link_h[(size_t)r.b * c->anchor_max + r.anchor] == -2 || !(r.z0 > 0.0))
+        c->anchor_link_h[(size_t)r.b * c->anchor_max + r.anchor] == -2 || (!adaptive && !(r.z0 > 0.0)))
       return XIVO_HIP_ERR_INVALID;
     keys[i] = (long)r.b * c->pool_max + r.entry;
   }
@@ -764,7 +776,7 @@ int xivo_hip_pool_add(xivo_hip_ctx* c, int n, const xivo_pool_new* recs) {
     StageTimer st(c, ST_OTHER, 0.0, "pool_add_kernel");
     HIP_TRY((hipError_t)launch_pool_add(c->fpool, c->pool_max, (const xivo_pool_new*)c->pool_io, n, c->cam,
                                         c->calib_on ? c->calib : nullptr, c->calib_on ? c->cl.cam_dim : 0,
-                                        (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0, c->stream));
+                                        (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0, c->stream, adaptive ? c->init_z : nullptr));
   }
   HIP_TRY(hipStreamSynchronize(c->stream));   // recs is borrowed host memory
   for (int i = 0; i < n; ++i) c->pool_anchor_h[(size_t)recs[i].b * c->pool_max + recs[i].entry] = recs[i].anchor;
@@ -789,6 +801,7 @@ int xivo_hip_pool_step(xivo_hip_ctx* c, int B, const double* xp, int strict, int
   a.o = c->pool_opts; a.remove_outlier = c->pool_remove_outlier; a.strict = strict ? 1 : 0; a.batch = B;
   a.xp = (const double*)io; a.order = (int*)(io + b_xp); a.n = (int*)(io + b_xp + b_ord);
   a.live = (unsigned char*)(io + b_xp + b_ord + b_n);
+  a.tri = c->pool_tri; a.tri_good = c->tri_counts; a.tri_bad = c->tri_counts + c->Bmax;
   HIP_TRY(hipMemcpyAsync(io, xp, b_xp, hipMemcpyHostToDevice, c->stream));
   {
     StageTimer st(c, ST_OTHER, 0.0, "pool_step_kernel");
@@ -822,6 +835,80 @@ int xivo_hip_pool_get(xivo_hip_ctx* c, int b0, int nb, xivo_subfilter_feat* entr
     if (anchor_poses) anchor_poses[i] = anc[i].g;
     if (anchor_slots) anchor_slots[i] = anc[i].slot;
   }
+  return XIVO_HIP_OK;
+}
+
+// ---- depth initialisation of new tracks: triangulation and AdaptInitialDepth
+static bool tri_opts_ok(const xivo_triangulate_opts* o) {
+  return o->struct_size == (int)sizeof(xivo_triangulate_opts) && o->method >= XIVO_TRI_OFF && o->method <= XIVO_TRI_LINF;
+}
+
+int xivo_hip_triangulate(xivo_hip_ctx* c, int n, const xivo_tri_in* in, xivo_tri_out* out, const xivo_triangulate_opts* o) {
+  if (!c || n < 0 || !o || (n > 0 && (!in || !out)) || !tri_opts_ok(o) || o->method == XIVO_TRI_OFF) return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (n == 0) return XIVO_HIP_OK;
+  const size_t bi = (size_t)n * sizeof(xivo_tri_in), bo = (size_t)n * sizeof(xivo_tri_out);
+  int rc = ensure_pool_io(c, bi + bo);
+  if (rc) return rc;
+  char* io = (char*)c->pool_io;
+  HIP_TRY(hipMemcpyAsync(io, in, bi, hipMemcpyHostToDevice, c->stream));
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "triangulate_kernel");
+    HIP_TRY((hipError_t)launch_triangulate((const xivo_tri_in*)io, (xivo_tri_out*)(io + bi), n, *o, c->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(out, io + bi, bo, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pool_triangulation(xivo_hip_ctx* c, const xivo_triangulate_opts* o) {
+  if (!c || !c->fpool || (o && !tri_opts_ok(o))) return XIVO_HIP_ERR_INVALID;
+  c->pool_tri = o ? *o : xivo_triangulate_opts{};
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pool_tri_counts(xivo_hip_ctx* c, int b0, int nb, int* good_out, int* bad_out) {
+  if (bad_range(c, b0, nb) || !c->tri_counts) return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (nb == 0) return XIVO_HIP_OK;
+  if (good_out)
+    HIP_TRY(hipMemcpyAsync(good_out, c->tri_counts + b0, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (bad_out)
+    HIP_TRY(hipMemcpyAsync(bad_out, c->tri_counts + c->Bmax + b0, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pool_adapt_depth_config(xivo_hip_ctx* c, const xivo_adapt_depth_opts* o) {
+  if (!c || !c->init_z || !o || o->struct_size != (int)sizeof(xivo_adapt_depth_opts) || !(o->initial_z > 0.0) ||
+      !(o->median_weight >= 0.0 && o->median_weight <= 1.0))
+    return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  std::vector<double> z((size_t)c->Bmax, o->initial_z);
+  HIP_TRY(hipMemcpyAsync(c->init_z, z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->adapt = *o; c->adapt_on = true;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pool_adapt_depth(xivo_hip_ctx* c, int B, double* init_z_out) {
+  if (!c || !c->fpool || !c->adapt_on || B <= 0 || B > c->Bmax) return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (adapt_depth_lds(c->feats ? c->F : 0, c->pool_max) > 60 * 1024) return XIVO_HIP_ERR_UNSUPPORTED;
+  int rc = ensure_pool_io(c, (size_t)B * sizeof(double));
+  if (rc) return rc;
+  AdaptDepthArgs a{};
+  a.feats = c->feats; a.F = c->feats ? c->F : 0; a.Fmax = c->Fmax;
+  a.pool = c->fpool; a.pool_max = c->pool_max;
+  a.init_z = c->init_z; a.init_z_out = (double*)c->pool_io;
+  a.beta = c->adapt.median_weight; a.min_z = c->adapt.min_z; a.max_z = c->adapt.max_z;
+  a.min_lifetime = c->adapt.min_feature_lifetime; a.invdepth = (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0; a.batch = B;
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "adapt_depth_kernel");
+    HIP_TRY((hipError_t)launch_adapt_depth(a, c->stream));
+  }
+  if (init_z_out) HIP_TRY(hipMemcpyAsync(init_z_out, a.init_z_out, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return XIVO_HIP_OK;
 }
 

@@ -113,6 +113,13 @@ struct xivo_hip_ctx {
   void* pool_io = nullptr; size_t pool_io_cap = 0;   // per-call device staging: records / pixels in, order / counts / live out
   std::vector<int> pool_anchor_h;   // [Bmax][pool_max]: anchor of a live entry, -1 = free
   std::vector<int> anchor_link_h;   // [Bmax][anchor_max]: linked group slot, -1 = unlinked
+  // depth initialisation of new tracks (xivo_hip_pool_triangulation / xivo_hip_pool_adapt_depth*): triangulation options
+  // (method XIVO_TRI_OFF: off), per-filter good / bad counters and the resident init_z [Bmax] (allocated by pool_config)
+  xivo_triangulate_opts pool_tri{};
+  int* tri_counts = nullptr;        // [2][Bmax]: good, bad
+  double* init_z = nullptr;         // [Bmax]
+  xivo_adapt_depth_opts adapt{};
+  bool adapt_on = false;
   std::vector<char> hstage;                        // host staging of d2h_rows
   void* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
   // one-filter plumbing call (xivo_hip_update_joseph_host): page-locked, device-mapped staging block owned by the context,

@@ -201,7 +201,7 @@ struct PoolAnchor {
 // Out-of-state feature pool (xivo_hip_pool_*): entries are xivo_subfilter_feat with ref_sind = the entry's anchor (-1: free)
 int launch_pool_anchor(PoolAnchor* anchors, int anchor_max, const xivo_pose_in* poses, const int* slot, int nb, hipStream_t s);
 int launch_pool_add(xivo_subfilter_feat* pool, int pool_max, const xivo_pool_new* recs, int n, xivo_cam cam,
-                    const xivo_calib_in* calib, int cam_dim, int invdepth, hipStream_t s);
+                    const xivo_calib_in* calib, int cam_dim, int invdepth, hipStream_t s, const double* init_z = nullptr);
 struct PoolStepArgs {
   xivo_subfilter_feat* pool; const PoolAnchor* anchors; int pool_max, anchor_max;   // [batch][pool_max] / [batch][anchor_max]
   const xivo_pose_in* poses; const xivo_group_in* groups; int n_groups;
@@ -209,8 +209,21 @@ struct PoolStepArgs {
   xivo_subfilter_opts o; double remove_outlier; int strict, batch;
   const double* xp;                                  // [batch][pool_max][2]
   int* order; int* n; unsigned char* live;           // out: [batch][pool_max], [batch], [batch][pool_max]
+  xivo_triangulate_opts tri;                         // method XIVO_TRI_OFF: no triangulation
+  int* tri_good; int* tri_bad;                       // [batch]: accumulated while tri is on
 };
 int launch_pool_step(const PoolStepArgs& a, hipStream_t s);
+// Feature::Triangulate's triangulators on host-array problems (xivo_hip_triangulate)
+int launch_triangulate(const xivo_tri_in* in, xivo_tri_out* out, int n, const xivo_triangulate_opts& o, hipStream_t s);
+// AdaptInitialDepth (xivo_hip_pool_adapt_depth): one workgroup per filter
+struct AdaptDepthArgs {
+  const xivo_feat_in* feats; int F, Fmax;            // resident feature list [batch][Fmax], first F entries read
+  const xivo_subfilter_feat* pool; int pool_max;     // [batch][pool_max]
+  double* init_z; double* init_z_out;                // [batch] resident / copy out (may be null)
+  double beta, min_z, max_z; int min_lifetime, invdepth, batch;
+};
+size_t adapt_depth_lds(int F, int pool_max);
+int launch_adapt_depth(const AdaptDepthArgs& a, hipStream_t s);
 
 // ================================================================ propagate_kernels.hip: propagation (capi_propagate.hip)
 

@@ -5,12 +5,17 @@
 //                                                          src/feature.cpp:246-297,133-142, src/options.cpp:10-33
 //  pool_anchor_kernel   Group::Create(X_.Rsb, X_.Tsb)      src/group.cpp:17-24, src/manager.cpp:121
 //  pool_add_kernel      Feature::Initialize                src/feature.cpp:144-160
+//  pool_tri_kernel      Feature::Triangulate at an entry's first step (triangulate_pre_subfilter), before pool_step_kernel
+//                                                          src/manager.cpp:227-231, src/feature.cpp:686-751
 //  pool_step_kernel     the out-of-state branch of ProcessTracks + the candidate order
 //                                                          src/manager.cpp:171-250
+//  triangulate_kernel   the triangulators of src/helpers.cpp:103-371 on host-array problems (xivo_hip_triangulate)
+//  adapt_depth_kernel   Estimator::AdaptInitialDepth       src/manager.cpp:255-278
 // (paths relative to the reference tree). One thread per feature; one workgroup per filter for the pool step.
 #include "ekf_kernels.h"
 #include "camera_device.h"
 #include "geometry_device.h"
+#include "triangulate_device.h"
 
 namespace xivo_hip {
 
@@ -137,9 +142,10 @@ __global__ void pool_anchor_kernel(PoolAnchor* anchors, int anchor_max, const xi
   for (int i = 0; i < 3; ++i) A.g.Tsb[i] = poses[b].Tsb[i];
   A.slot = -1;
 }
-// Feature::Initialize (feature.cpp:144-160): one thread per new track
+// Feature::Initialize (feature.cpp:144-160): one thread per new track; init_z (non-null: XIVO_POOL_ADD_ADAPTIVE_Z): z0 is the
+// filter's resident init_z (AdaptInitialDepth's init_z_)
 __global__ void pool_add_kernel(xivo_subfilter_feat* pool, int pool_max, const xivo_pool_new* recs, int n, xivo_cam cam_ctx,
-                                const xivo_calib_in* calib, int cam_dim, int invdepth) {
+                                const xivo_calib_in* calib, int cam_dim, int invdepth, const double* init_z) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
   const xivo_pool_new& r = recs[t];
@@ -148,7 +154,8 @@ __global__ void pool_add_kernel(xivo_subfilter_feat* pool, int pool_max, const x
   double xc[2];
   camera_unproject(cam, r.xp[0], r.xp[1], xc);
   f.x[0] = xc[0]; f.x[1] = xc[1];
-  f.x[2] = invdepth ? 1.0 / r.z0 : log(r.z0);
+  const double z0 = init_z ? init_z[r.b] : r.z0;
+  f.x[2] = invdepth ? 1.0 / z0 : log(z0);
 #pragma unroll
   for (int i = 0; i < 9; ++i) f.P[i] = 0.0;
 #pragma unroll
@@ -164,6 +171,59 @@ __global__ void pool_add_kernel(xivo_subfilter_feat* pool, int pool_max, const x
 // std::stable_sort gives xivo_hip_candidate_order.
 __device__ __forceinline__ bool pool_before(int ra, double pa, int ia, int rb, double pb, int ib) {
   return ra > rb || (ra == rb && (pa < pb || (pa == pb && ia < ib)));
+}
+// g12 = (anchor gsb * gbc)^-1 (gsb * gbc) of Feature::Triangulate (feature.cpp:692): R12 = Ra^T Rc, t12 = Ra^T (Tc - Ta) with
+// Rc = Rsb Rbc, Tc = Rsb Tbc + Tsb and the same for the anchor. No contraction and every sum left to right, so a caller can
+// restate these values bit for bit in plain fp64 (xivo_hip_triangulate then reproduces the pool's triangulation exactly).
+__device__ __forceinline__ void pool_g12(const xivo_pose_in& pose, const xivo_group_in& anc, double R12[9], double t12[3]) {
+#pragma clang fp contract(off)
+  const double* Rsb = pose.Rsb; const double* Rbc = pose.Rbc; const double* Ra0 = anc.Rsb;   // column-major
+  double Rc[9], Ra[9], Tc[3], Ta[3];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) {
+      Rc[i + 3 * j] = (Rsb[i] * Rbc[3 * j] + Rsb[i + 3] * Rbc[1 + 3 * j]) + Rsb[i + 6] * Rbc[2 + 3 * j];
+      Ra[i + 3 * j] = (Ra0[i] * Rbc[3 * j] + Ra0[i + 3] * Rbc[1 + 3 * j]) + Ra0[i + 6] * Rbc[2 + 3 * j];
+    }
+    Tc[i] = ((Rsb[i] * pose.Tbc[0] + Rsb[i + 3] * pose.Tbc[1]) + Rsb[i + 6] * pose.Tbc[2]) + pose.Tsb[i];
+    Ta[i] = ((Ra0[i] * pose.Tbc[0] + Ra0[i + 3] * pose.Tbc[1]) + Ra0[i + 6] * pose.Tbc[2]) + anc.Tsb[i];
+  }
+  const double d[3] = {Tc[0] - Ta[0], Tc[1] - Ta[1], Tc[2] - Ta[2]};
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j)
+      R12[i + 3 * j] = (Ra[3 * i] * Rc[3 * j] + Ra[1 + 3 * i] * Rc[1 + 3 * j]) + Ra[2 + 3 * i] * Rc[2 + 3 * j];
+    t12[i] = (Ra[3 * i] * d[0] + Ra[1 + 3 * i] * d[1]) + Ra[2 + 3 * i] * d[2];
+  }
+}
+// triangulate_pre_subfilter (manager.cpp:227-231) for the entries of one pool step, launched just before pool_step_kernel
+// when the option is on: one thread per entry; a live entry with a pixel this frame and init_counter == 0 (f->size() == 2:
+// x[0:2] is still UnProject(front()), only the sub-filter step writes x after pool_add_kernel and it increments
+// init_counter) is triangulated from its anchor pose and the frame's pose. pool_step_kernel then stores the pixel and takes
+// the sub-filter step from the x written here - the order of ProcessTracks.
+__global__ void pool_tri_kernel(PoolStepArgs a) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)a.batch * a.pool_max) return;
+  const int filt = (int)(t / a.pool_max);
+  xivo_subfilter_feat& f = a.pool[t];
+  if (f.ref_sind < 0 || f.init_counter != 0) return;
+  const double u = a.xp[2 * t], v = a.xp[2 * t + 1];
+  if (u != u || v != v) return;                             // dropped this frame: pool_step_kernel frees it
+  const xivo_cam cam = filter_cam(a.cam, a.calib, a.cam_dim, filt);
+  const PoolAnchor& A = a.anchors[(long)filt * a.anchor_max + f.ref_sind];
+  const xivo_group_in& G = A.slot >= 0 ? a.groups[(long)filt * a.n_groups + A.slot] : A.g;
+  double R12[9], t12[3], xc2[2], X[3];
+  pool_g12(a.poses[filt], G, R12, t12);
+  camera_unproject(cam, u, v, xc2);
+  const double xc1[2] = {f.x[0], f.x[1]};
+  const bool ret = tri::triangulate_one(R12, t12, xc1, xc2, a.tri.method, (float)a.tri.max_theta_thresh,
+                                        (float)a.tri.beta_thresh, X);
+  if (!tri::triangulation_good(ret, X, a.tri)) {
+    atomicAdd(&a.tri_bad[filt], 1);
+    return;
+  }
+  const double z = X[2];
+  f.x[0] = X[0] / z; f.x[1] = X[1] / z;
+  f.x[2] = a.invdepth ? 1.0 / z : log(z);
+  atomicAdd(&a.tri_good[filt], 1);
 }
 __global__ __launch_bounds__(256) void pool_step_kernel(PoolStepArgs a) {
   __shared__ double key_p[XIVO_POOL_MAX_ENTRIES];
@@ -228,6 +288,64 @@ __global__ __launch_bounds__(256) void pool_step_kernel(PoolStepArgs a) {
   if (tid == 0) a.n[filt] = n;
 }
 
+// xivo_hip_triangulate: one thread per problem
+__global__ void triangulate_kernel(const xivo_tri_in* in, xivo_tri_out* out, int n, xivo_triangulate_opts o) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const xivo_tri_in& p = in[t];
+  double X[3];
+  const bool ret = tri::triangulate_one(p.R12, p.t12, p.xc1, p.xc2, o.method, (float)o.max_theta_thresh, (float)o.beta_thresh, X);
+  xivo_tri_out& r = out[t];
+  r.X[0] = X[0]; r.X[1] = X[1]; r.X[2] = X[2];
+  r.ret = ret ? 1 : 0;
+  r.good = tri::triangulation_good(ret, X, o) ? 1 : 0;
+}
+
+// AdaptInitialDepth (manager.cpp:255-278), one workgroup per filter: the depths of the in-state features [0, F) of the
+// resident list and of the live READY pool entries with init_counter > min_lifetime go to LDS; the value of rank n / 2 is the
+// one with exactly n / 2 smaller values before it in (value, index) order - one thread per candidate counts them.
+__global__ __launch_bounds__(256) void adapt_depth_kernel(AdaptDepthArgs a) {
+  extern __shared__ double dep[];
+  __shared__ int n_dep;
+  __shared__ double med;
+  __shared__ int found;
+  const int filt = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  if (tid == 0) { n_dep = 0; found = 0; }
+  __syncthreads();
+  // (a non-finite depth is left out: the rank count below needs a strict total order)
+  for (int j = tid; j < a.F; j += nt) {
+    const xivo_feat_in& f = a.feats[(long)filt * a.Fmax + j];
+    const double z = feature_depth(f.x[2], a.invdepth);
+    if (f.sind >= 0 && isfinite(z)) dep[atomicAdd(&n_dep, 1)] = z;
+  }
+  for (int e = tid; e < a.pool_max; e += nt) {
+    const xivo_subfilter_feat& f = a.pool[(long)filt * a.pool_max + e];
+    const double z = feature_depth(f.x[2], a.invdepth);
+    if (f.ref_sind >= 0 && f.status == XIVO_FEAT_READY && f.init_counter > a.min_lifetime && isfinite(z))
+      dep[atomicAdd(&n_dep, 1)] = z;
+  }
+  __syncthreads();
+  const int n = n_dep, k = n >> 1;
+  for (int i = tid; i < n; i += nt) {
+    const double di = dep[i];
+    int below = 0;
+    for (int j = 0; j < n; ++j) {
+      const double dj = dep[j];
+      below += (dj < di || (dj == di && j < i)) ? 1 : 0;
+    }
+    if (below == k) { med = di; found = 1; }   // exactly one i has rank k
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double z = a.init_z[filt];
+    if (found && med >= a.min_z && med <= a.max_z) {   // !(m < min_z || m > max_z)
+      z = (1.0 - a.beta) * z + a.beta * med;
+      a.init_z[filt] = z;
+    }
+    if (a.init_z_out) a.init_z_out[filt] = z;
+  }
+}
+
 }  // namespace
 
 #define CHECK_LAUNCH() return (int)hipGetLastError()
@@ -247,10 +365,24 @@ int launch_pool_anchor(PoolAnchor* anchors, int anchor_max, const xivo_pose_in* 
   CHECK_LAUNCH();
 }
 int launch_pool_add(xivo_subfilter_feat* pool, int pool_max, const xivo_pool_new* recs, int n, xivo_cam cam,
-                    const xivo_calib_in* calib, int cam_dim, int invdepth, hipStream_t s) {
+                    const xivo_calib_in* calib, int cam_dim, int invdepth, hipStream_t s, const double* init_z) {
   if (n <= 0) return 0;
   hipLaunchKernelGGL(pool_add_kernel, dim3((n + 127) / 128), dim3(128), 0, s, pool, pool_max, recs, n, cam, calib, cam_dim,
-                     invdepth);
+                     invdepth, init_z);
+  CHECK_LAUNCH();
+}
+int launch_triangulate(const xivo_tri_in* in, xivo_tri_out* out, int n, const xivo_triangulate_opts& o, hipStream_t s) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(triangulate_kernel, dim3((n + 127) / 128), dim3(128), 0, s, in, out, n, o);
+  CHECK_LAUNCH();
+}
+// LDS bytes of adapt_depth_kernel's depth list: one double per resident feature and pool entry
+size_t adapt_depth_lds(int F, int pool_max) { return (size_t)(F + pool_max) * sizeof(double); }
+int launch_adapt_depth(const AdaptDepthArgs& a, hipStream_t s) {
+  if (a.batch <= 0) return 0;
+  const size_t lds = adapt_depth_lds(a.F, a.pool_max);
+  if (lds > 60 * 1024) return 1;
+  hipLaunchKernelGGL(adapt_depth_kernel, dim3(a.batch), dim3(256), lds, s, a);
   CHECK_LAUNCH();
 }
 // threads per workgroup: one per entry up to 256, at least one wave
@@ -261,6 +393,12 @@ int pool_step_threads(int pool_max) {
 int launch_pool_step(const PoolStepArgs& a, hipStream_t s) {
   if (a.batch <= 0) return 0;
   if (a.pool_max < 1 || a.pool_max > XIVO_POOL_MAX_ENTRIES) return 1;
+  if (a.tri.method != XIVO_TRI_OFF) {
+    const long ne = (long)a.batch * a.pool_max;
+    hipLaunchKernelGGL(pool_tri_kernel, dim3((unsigned)((ne + 127) / 128)), dim3(128), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
   hipLaunchKernelGGL(pool_step_kernel, dim3(a.batch), dim3(pool_step_threads(a.pool_max)), 0, s, a);
   CHECK_LAUNCH();
 }

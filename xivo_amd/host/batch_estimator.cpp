@@ -306,6 +306,16 @@ void BatchEstimator::EnableSubfilter(const SubfilterConfig& sc) {
   subfilter_ = true;
 }
 
+void BatchEstimator::EnableDepthInit(const DepthInitConfig& dc) {
+  if (!subfilter_) throw std::runtime_error("EnableDepthInit needs EnableSubfilter first");
+  Check(xivo_hip_pool_triangulation(ctx_, dc.triangulate ? &dc.tri : nullptr), "pool_triangulation");
+  if (dc.adaptive) {
+    Check(xivo_hip_pool_adapt_depth_config(ctx_, &dc.adapt), "pool_adapt_depth_config");
+    init_z_.assign(B_, dc.adapt.initial_z);
+  }
+  dc_ = dc;
+}
+
 // One camera frame of the "subfilter" life cycle, decision for decision SequenceRunner._frame_subfilter of
 // xivo_amd/sequence.py (the order of Estimator::UpdateStep, src/manager.cpp:18-130)
 void BatchEstimator::VisualSubfilter(const int* off, const int64_t* ids, const double* meas) {
@@ -424,8 +434,12 @@ void BatchEstimator::VisualSubfilter(const int* off, const int64_t* ids, const d
       std::memset(&r, 0, sizeof(r));
       r.b = b; r.entry = e; r.anchor = a;
       r.xp[0] = meas[(size_t)k * 3]; r.xp[1] = meas[(size_t)k * 3 + 1];
-      r.z0 = sc_.initial_z;
-      r.std_xyz[0] = cfg_.initial_std_x / fl; r.std_xyz[1] = cfg_.initial_std_y / fl; r.std_xyz[2] = cfg_.initial_std_z;
+      r.z0 = sc_.initial_z;   // (ignored under adaptive_initial_depth: the device's resident init_z)
+      if (dc_.triangulate) {  // a new track is never triangulated yet: the badtri stds (manager.cpp:585-586)
+        r.std_xyz[0] = dc_.std_badtri[0] / fl; r.std_xyz[1] = dc_.std_badtri[1] / fl; r.std_xyz[2] = dc_.std_badtri[2];
+      } else {
+        r.std_xyz[0] = cfg_.initial_std_x / fl; r.std_xyz[1] = cfg_.initial_std_y / fl; r.std_xyz[2] = cfg_.initial_std_z;
+      }
       recs.push_back(r);
       pb.ent_id[e] = ids[k]; pb.ent_anchor[e] = a; pb.ent_born[e] = vision_counter_; pb.id2ent[ids[k]] = e;
     }
@@ -433,7 +447,10 @@ void BatchEstimator::VisualSubfilter(const int* off, const int64_t* ids, const d
   }
   if (std::any_of(slots.begin(), slots.end(), [](int v) { return v >= 0; }))
     Check(xivo_hip_pool_anchor(ctx_, 0, B_, slots.data()), "pool_anchor");
-  if (!recs.empty()) Check(xivo_hip_pool_add(ctx_, (int)recs.size(), recs.data()), "pool_add");
+  if (!recs.empty())
+    Check(xivo_hip_pool_add_ex(ctx_, (int)recs.size(), recs.data(), dc_.adaptive ? XIVO_POOL_ADD_ADAPTIVE_Z : 0u), "pool_add");
+  // --- AdaptInitialDepth (:131)
+  if (dc_.adaptive) Check(xivo_hip_pool_adapt_depth(ctx_, B_, init_z_.data()), "pool_adapt_depth");
   // --- EnforceMaxGroupLifetime (:282-304)
   for (auto& pb : pools_) {
     std::vector<char> held(AM, 0);
@@ -522,6 +539,31 @@ int xivo_batch_enable_subfilter(void* h, const xivo_batch_subfilter_cfg* c) {
   } catch (const std::exception&) { return -1; }
 }
 int xivo_batch_subfilter_cfg_size(void) { return (int)sizeof(xivo_batch_subfilter_cfg); }
+struct xivo_batch_depth_init_cfg {   // flat mirror of xivo::hip::BatchEstimator::DepthInitConfig
+  int triangulate, adaptive;
+  xivo_triangulate_opts tri;
+  double std_badtri[3];
+  xivo_adapt_depth_opts adapt;
+};
+int xivo_batch_enable_depth_init(void* h, const xivo_batch_depth_init_cfg* c) {
+  if (!h || !c) return -1;
+  try {
+    xivo::hip::BatchEstimator::DepthInitConfig dc;
+    dc.triangulate = c->triangulate != 0; dc.adaptive = c->adaptive != 0;
+    dc.tri = c->tri; dc.adapt = c->adapt;
+    for (int i = 0; i < 3; ++i) dc.std_badtri[i] = c->std_badtri[i];
+    static_cast<xivo::hip::BatchEstimator*>(h)->EnableDepthInit(dc);
+    return 0;
+  } catch (const std::exception&) { return -1; }
+}
+int xivo_batch_depth_init_cfg_size(void) { return (int)sizeof(xivo_batch_depth_init_cfg); }
+// AdaptInitialDepth's init_z [B] after the last frame; -1 while adaptive_initial_depth is off
+int xivo_batch_init_z(void* h, double* out) {
+  const auto& z = static_cast<xivo::hip::BatchEstimator*>(h)->init_z();
+  if (z.empty()) return -1;
+  std::copy(z.begin(), z.end(), out);
+  return 0;
+}
 void xivo_batch_pool_stats(void* h, long* admitted, long* dropped) {
   auto* e = static_cast<xivo::hip::BatchEstimator*>(h);
   *admitted = e->n_admitted(); *dropped = e->n_pool_dropped();

@@ -17,6 +17,7 @@
 // in the device-resident feature pool xivo_hip_pool_*, admission by Criteria::Candidate), decision for decision the
 // "subfilter" mode of xivo_amd/sequence.py.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <unordered_map>
 #include <vector>
@@ -79,6 +80,18 @@ class BatchEstimator {
     int pool_max = 200, anchor_max = 64;                     // entries / anchors per filter
   };
   void EnableSubfilter(const SubfilterConfig& sc);   // before the first camera frame
+  // the depth initialisation of new tracks in that life cycle (both opt-in), as SequenceConfig.triangulate_pre_subfilter /
+  // adaptive_initial_depth: pre-sub-filter triangulation (src/manager.cpp:227-231; new tracks then take the badtri stds,
+  // :585-586) and AdaptInitialDepth after the new tracks are added (:131, :255-278)
+  struct DepthInitConfig {
+    bool triangulate = false;
+    xivo_triangulate_opts tri{(int)sizeof(xivo_triangulate_opts), XIVO_TRI_L1, 0.05, 5.0, 0.1 * M_PI / 180, 0.25 * M_PI / 180};
+    double std_badtri[3] = {1.0, 1.0, 0.1};          // initial_std_{x,y}_badtri in pixels, initial_std_z_badtri
+    bool adaptive = false;
+    xivo_adapt_depth_opts adapt{(int)sizeof(xivo_adapt_depth_opts), 5, 2.5, 0.99, 0.05, 10.0};
+  };
+  void EnableDepthInit(const DepthInitConfig& dc);   // after EnableSubfilter, before the first camera frame
+  const std::vector<double>& init_z() const { return init_z_; }   // AdaptInitialDepth's init_z after the last frame
   long n_admitted() const { return n_admitted_; }
   long n_pool_dropped() const { return n_pool_dropped_; }   // new tracks that found no free pool entry or anchor
 
@@ -107,6 +120,8 @@ class BatchEstimator {
   };
   bool subfilter_ = false;
   SubfilterConfig sc_;
+  DepthInitConfig dc_;
+  std::vector<double> init_z_;
   std::vector<PoolBook> pools_;
   int vision_counter_ = 0;
   long n_admitted_ = 0, n_pool_dropped_ = 0;

@@ -75,6 +75,19 @@ pool_new_dtype = np.dtype([("b", "i4"), ("entry", "i4"), ("anchor", "i4"), ("res
                            ("std_xyz", "f8", 3)])
 assert pool_new_dtype.itemsize == 64
 POOL_MAX_ENTRIES = 512
+# depth initialisation of new tracks (include/xivo_hip.h): triangulation and AdaptInitialDepth
+TRI_OFF, TRI_DLT_SVD, TRI_DLT_AVG, TRI_L1, TRI_L2, TRI_LINF = range(6)
+TRI_METHODS = {"direct_linear_transform_svd": TRI_DLT_SVD, "direct_linear_transform_avg": TRI_DLT_AVG,
+               "l1_angular": TRI_L1, "l2_angular": TRI_L2, "linf_angular": TRI_LINF}
+tri_opts_dtype = np.dtype([("struct_size", "i4"), ("method", "i4"), ("zmin", "f8"), ("zmax", "f8"),
+                           ("max_theta_thresh", "f8"), ("beta_thresh", "f8")])
+tri_in_dtype = np.dtype([("R12", "f8", 9), ("t12", "f8", 3), ("xc1", "f8", 2), ("xc2", "f8", 2)])
+tri_out_dtype = np.dtype([("X", "f8", 3), ("ret", "i4"), ("good", "i4")])
+adapt_opts_dtype = np.dtype([("struct_size", "i4"), ("min_feature_lifetime", "i4"), ("initial_z", "f8"),
+                             ("median_weight", "f8"), ("min_z", "f8"), ("max_z", "f8")])
+assert tri_opts_dtype.itemsize == 40 and tri_in_dtype.itemsize == 128 and tri_out_dtype.itemsize == 32
+assert adapt_opts_dtype.itemsize == 40
+POOL_ADD_ADAPTIVE_Z = 1
 assert subfilter_dtype.itemsize == 144 and subfilter_opts_dtype.itemsize == 48
 assert feat_dtype.itemsize == 48 and pose_dtype.itemsize == 336 and group_dtype.itemsize == 96
 
@@ -139,6 +152,12 @@ _SIGS = {
     "xivo_hip_pool_add": [C.c_void_p, C.c_int, C.c_void_p],
     "xivo_hip_pool_step": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_pool_get": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_triangulate": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_pool_triangulation": [C.c_void_p, C.c_void_p],
+    "xivo_hip_pool_tri_counts": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "xivo_hip_pool_adapt_depth_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_pool_adapt_depth": [C.c_void_p, C.c_int, C.c_void_p],
+    "xivo_hip_pool_add_ex": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint],
     "xivo_hip_edit_batch": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_set_pixels": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_get_scene": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -168,6 +187,15 @@ _SIGS = {
     "xivo_hip_selftest_glevel_launch": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int],
 }
 HOST_P_RESIDENT, HOST_KEEP_P = 1, 2
+
+
+def tri_options(method, zmin=0.05, zmax=5.0, max_theta_thresh=0.1 * np.pi / 180, beta_thresh=0.25 * np.pi / 180):
+    """xivo_triangulate_opts; method = TRI_* or the cfg's name ("l1_angular", ...); thresholds in radians"""
+    o = np.zeros(1, dtype=tri_opts_dtype)
+    o["struct_size"] = tri_opts_dtype.itemsize
+    o["method"] = TRI_METHODS[method] if isinstance(method, str) else int(method)
+    o["zmin"], o["zmax"], o["max_theta_thresh"], o["beta_thresh"] = zmin, zmax, max_theta_thresh, beta_thresh
+    return o
 
 
 class CalibLayout(C.Structure):
@@ -590,6 +618,58 @@ class Context:
         ap = np.zeros((nb, self.anchor_max), dtype=group_dtype); sl = np.zeros((nb, self.anchor_max), dtype=np.int32)
         self._check(self.lib.xivo_hip_pool_get(self.h, b0, nb, _ptr(ent), _ptr(ap), _ptr(sl)))
         return ent, ap, sl
+
+    # ---- depth initialisation of new tracks: triangulation, AdaptInitialDepth
+    def triangulate(self, R12, t12, xc1, xc2, method, zmin=0.05, zmax=5.0, max_theta_thresh=0.1 * np.pi / 180,
+                    beta_thresh=0.25 * np.pi / 180):
+        """n two-view problems (R12 [n, 3, 3], t12 [n, 3], xc1 / xc2 [n, 2]; thresholds in radians) -> (X [n, 3], ret [n] bool,
+        good [n] bool) from xivo_hip_triangulate"""
+        R12 = np.asarray(R12, dtype=np.float64).reshape(-1, 3, 3)
+        n = R12.shape[0]
+        pin = np.zeros(n, dtype=tri_in_dtype)
+        pin["R12"] = np.transpose(R12, (0, 2, 1)).reshape(n, 9)   # column-major
+        pin["t12"] = np.asarray(t12, dtype=np.float64).reshape(n, 3)
+        pin["xc1"] = np.asarray(xc1, dtype=np.float64).reshape(n, 2)
+        pin["xc2"] = np.asarray(xc2, dtype=np.float64).reshape(n, 2)
+        out = np.zeros(n, dtype=tri_out_dtype)
+        o = tri_options(method, zmin, zmax, max_theta_thresh, beta_thresh)
+        self._check(self.lib.xivo_hip_triangulate(self.h, n, _ptr(pin), _ptr(out), _ptr(o)))
+        return out["X"].copy(), out["ret"].astype(bool), out["good"].astype(bool)
+
+    def pool_triangulation(self, method=None, zmin=0.05, zmax=5.0, max_theta_thresh=0.1 * np.pi / 180,
+                           beta_thresh=0.25 * np.pi / 180):
+        """triangulate_pre_subfilter on the pool's first steps; method None / TRI_OFF / "off" disables it"""
+        if method is None:
+            self._check(self.lib.xivo_hip_pool_triangulation(self.h, None))
+            return
+        o = tri_options(method, zmin, zmax, max_theta_thresh, beta_thresh)
+        self._check(self.lib.xivo_hip_pool_triangulation(self.h, _ptr(o)))
+
+    def pool_tri_counts(self, b0=0, nb=None):
+        """-> (good [nb], bad [nb]) triangulations since pool_config"""
+        nb = self.batch - b0 if nb is None else nb
+        g = np.zeros(nb, dtype=np.int32); b = np.zeros(nb, dtype=np.int32)
+        self._check(self.lib.xivo_hip_pool_tri_counts(self.h, b0, nb, _ptr(g), _ptr(b)))
+        return g, b
+
+    def pool_adapt_depth_config(self, initial_z, median_weight=0.99, min_feature_lifetime=5, min_z=0.05, max_z=5.0):
+        o = np.zeros(1, dtype=adapt_opts_dtype)
+        o["struct_size"] = adapt_opts_dtype.itemsize
+        o["initial_z"], o["median_weight"], o["min_feature_lifetime"] = initial_z, median_weight, min_feature_lifetime
+        o["min_z"], o["max_z"] = min_z, max_z
+        self._check(self.lib.xivo_hip_pool_adapt_depth_config(self.h, _ptr(o)))
+
+    def pool_adapt_depth(self, B=None):
+        """AdaptInitialDepth on filters [0, B) -> init_z [B] afterwards"""
+        B = self.batch if B is None else int(B)
+        z = np.zeros(B, dtype=np.float64)
+        self._check(self.lib.xivo_hip_pool_adapt_depth(self.h, B, _ptr(z)))
+        return z
+
+    def pool_add_ex(self, recs, options=0):
+        """recs: array of pool_new_dtype; options POOL_ADD_ADAPTIVE_Z: z0 from the filter's resident init_z"""
+        recs = np.ascontiguousarray(recs, dtype=pool_new_dtype)
+        self._check(self.lib.xivo_hip_pool_add_ex(self.h, int(recs.size), _ptr(recs) if recs.size else None, int(options)))
 
     def givens(self, x, Hx, Hf, effective_rows=-1):
         """Batched xivo::Givens. x [nb, rows], Hx [nb, rows, nx], Hf [nb, rows, nf] (row-major numpy views of the

@@ -77,6 +77,21 @@ def config_from_cfg(cfg):
     for k in ("strict_criteria_timesteps", "max_group_lifetime"):
         if k in cfg:
             setattr(c, k, int(cfg[k]))
+    # depth initialisation of new tracks (src/estimator.cpp:157-167, :356-358): triangulation thresholds in degrees in the cfg
+    c.triangulate_pre_subfilter = bool(cfg.get("triangulate_pre_subfilter", False))
+    tri = cfg.get("triangulation", {})
+    c.triangulation = dict(method=str(tri.get("method", "l1_angular")), zmin=float(tri.get("zmin", 0.05)),
+                           zmax=float(tri.get("zmax", 5.0)),
+                           max_theta_thresh=float(tri.get("max_theta_thresh", 0.1)) * np.pi / 180,
+                           beta_thresh=float(tri.get("beta_thesh", 0.25)) * np.pi / 180)   # the reference's key spelling
+    for k in ("initial_std_x_badtri", "initial_std_y_badtri", "initial_std_z_badtri"):
+        if k in cfg:
+            setattr(c, k, float(cfg[k]))
+    if "adaptive_initial_depth" in cfg:
+        a = cfg["adaptive_initial_depth"]
+        c.adaptive_initial_depth = True
+        c.adaptive_depth = dict(median_weight=float(a.get("median_weight", 0.99)),
+                                minimum_feature_lifetime=int(a.get("minimum_feature_lifetime", 5)))
     c.subfilter = dict(c.subfilter)
     for k in c.subfilter:
         if k in cfg.get("subfilter", {}):

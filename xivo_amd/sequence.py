@@ -28,8 +28,11 @@ What is mirrored from the reference and what is simplified:
       waits. An anchor whose group left the state keeps the group's last pose; unlinked anchors without live entries are
       freed after `max_group_lifetime` frames (EnforceMaxGroupLifetime, :282-304). New tracks that find no free pool
       entry or anchor are dropped and counted (`SequenceRunner.n_pool_dropped`).
-  * NOT IN EITHER: pre-sub-filter triangulation and RefineDepth (`use_depth_opt`), gauge XY features and
-    SwitchRefGroup, ownership transfer, AdaptInitialDepth (`initial_z` stays fixed), OOS updates.
+      Two opt-in parts of the depth initialisation, both on the device: `triangulate_pre_subfilter` triangulates every
+      pool entry at its second observation before its sub-filter step (Feature::Triangulate, src/feature.cpp:686-751;
+      new tracks then start with the `initial_std_*_badtri` stds, :585-586), and `adaptive_initial_depth` runs
+      AdaptInitialDepth (:255-278) after the new tracks are added, whose init_z the next frame's new tracks start from.
+  * NOT IN EITHER: RefineDepth (`use_depth_opt`), gauge XY features and SwitchRefGroup, ownership transfer, OOS updates.
 The numerics of every step are the device path; this file holds no arithmetic of the filter itself.
 """
 import numpy as np
@@ -136,6 +139,17 @@ class SequenceConfig:
         self.max_subfilter_outlier = 0.01       # max_subfilter_outlier (src/options.cpp:10-33)
         self.subfilter = dict(visual_meas_std=3.5, MH_thresh=5.991, ready_steps=5)   # cfg "subfilter" (src/estimator.cpp:137-142)
         self.pool_max, self.anchor_max = 200, 64   # feature pool / anchor table per filter (device resident)
+        # depth initialisation of new tracks in the "subfilter" life cycle (both off by default, as the reference's
+        # triangulate_pre_subfilter is, src/estimator.cpp:157-158). Thresholds in radians (the cfg's degrees * pi / 180,
+        # :163-164); the badtri stds replace initial_std_* for every new track while triangulation is on (manager.cpp:585-586)
+        self.triangulate_pre_subfilter = False
+        self.triangulation = dict(method="l1_angular", zmin=0.05, zmax=5.0, max_theta_thresh=0.1 * np.pi / 180,
+                                  beta_thresh=0.25 * np.pi / 180)
+        self.initial_std_x_badtri = self.initial_std_y_badtri = 1.0
+        self.initial_std_z_badtri = 0.10
+        # AdaptInitialDepth (src/manager.cpp:255-278): the init_z of new tracks follows the median feature depth
+        self.adaptive_initial_depth = False
+        self.adaptive_depth = dict(median_weight=0.99, minimum_feature_lifetime=5)   # cfg "adaptive_initial_depth"
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option " + k)
@@ -210,6 +224,15 @@ class HipBackend:
         self.ctx.pool_config(c.pool_max, c.anchor_max, Rtri=float(sf["visual_meas_std"]) ** 2, MH_thresh=float(sf["MH_thresh"]),
                              ready_steps=int(sf["ready_steps"]), min_depth=c.min_depth, max_depth=c.max_depth,
                              max_subfilter_outlier=c.max_subfilter_outlier, remove_outlier_counter=c.remove_outlier_counter)
+        if c.triangulate_pre_subfilter:
+            t = c.triangulation
+            self.ctx.pool_triangulation(t["method"], zmin=t["zmin"], zmax=t["zmax"], max_theta_thresh=t["max_theta_thresh"],
+                                        beta_thresh=t["beta_thresh"])
+        if c.adaptive_initial_depth:
+            a = c.adaptive_depth
+            self.ctx.pool_adapt_depth_config(c.initial_z, median_weight=a["median_weight"],
+                                             min_feature_lifetime=a["minimum_feature_lifetime"], min_z=c.min_depth,
+                                             max_z=c.max_depth)
         self.pool_on = True
 
     def pool_step(self, xp, strict):
@@ -219,7 +242,15 @@ class HipBackend:
         self.ctx.pool_anchor(slot)
 
     def pool_add(self, recs):
-        self.ctx.pool_add(recs)
+        """Feature::Initialize of new tracks; z0 from the resident init_z under adaptive_initial_depth"""
+        self.ctx.pool_add_ex(recs, L.POOL_ADD_ADAPTIVE_Z if self.cfg.adaptive_initial_depth else 0)
+
+    def adapt_depth(self):
+        """AdaptInitialDepth on every filter -> init_z [B]"""
+        return self.ctx.pool_adapt_depth(self.B)
+
+    def tri_counts(self):
+        return self.ctx.pool_tri_counts()
 
     def propagate(self, imu):
         self.ctx.propagate(imu, self.Qimu, self.Qmodel, self.cfg.gravity,
@@ -331,6 +362,7 @@ class SequenceRunner:
         self.vision_counter = 0      # camera frames so far (Estimator::vision_counter_)
         self.n_pool_dropped = 0      # new tracks dropped because the pool or the anchor table was full
         self.admitted = []           # (frame, filter, track id, sub-filter steps taken) of every pool entry that entered the state
+        self.init_z = None           # [B] AdaptInitialDepth's init_z after the last frame (adaptive_initial_depth)
         self.timers = None       # set to {} to accumulate wall seconds per phase (adds a device sync per phase)
 
     def _tick(self, name, t0):
@@ -506,7 +538,10 @@ class SequenceRunner:
         be.edit(np.array(ops, dtype=L.edit_dtype))
         # --- Group::Create(X_.Rsb, X_.Tsb) from the updated pose + InitializeJustCreatedTracks (:121-126, :575-600)
         fl = cfg.focal_length()
-        std = [cfg.initial_std_x / fl, cfg.initial_std_y / fl, cfg.initial_std_z]
+        if cfg.triangulate_pre_subfilter:   # a new track is never triangulated yet: the badtri stds (manager.cpp:585-586)
+            std = [cfg.initial_std_x_badtri / fl, cfg.initial_std_y_badtri / fl, cfg.initial_std_z_badtri]
+        else:
+            std = [cfg.initial_std_x / fl, cfg.initial_std_y / fl, cfg.initial_std_z]
         slots = np.full(B, -1, dtype=np.int32)
         recs = []
         for b in range(B):
@@ -534,6 +569,9 @@ class SequenceRunner:
             be.pool_anchor(slots)
         if recs:
             be.pool_add(np.array(recs, dtype=L.pool_new_dtype))
+        # --- AdaptInitialDepth (:131, after the new tracks took the old init_z)
+        if cfg.adaptive_initial_depth:
+            self.init_z = be.adapt_depth()
         # --- EnforceMaxGroupLifetime (:282-304): an anchor out of the state with no live entry is freed when too old
         for pb in self.pools:
             held = set(pb.ent_anchor)
