@@ -405,7 +405,9 @@ int xivo_hip_close_loop_stack(xivo_hip_ctx* ctx, int b0, int nb, int n, const xi
  * QR decomposition (Householder reflections on the device; the rows only touch the extrinsics and group columns, so
  * the 2k-3 rows of every OOS feature collapse to at most 6 + 6 n_groups rows in total). Orthogonal row operations with
  * isotropic noise leave S^-1-weighted quantities - K, dx, P+ - unchanged to rounding. rows_out[b] (host, may be NULL) =
- * OOS rows of filter b afterwards; the stacked row count M shrinks to in-state rows + the largest of them. */
+ * OOS rows of filter b afterwards; the stacked row count M shrinks to in-state rows + the largest of them. Any call that
+ * stages new rows after the projection (xivo_hip_set_measurements*, xivo_hip_stack, xivo_hip_close_loop_stack, the one-filter
+ * call) ends the OOS block: XIVO_HIP_ERR_INVALID until the next xivo_hip_oos_project. */
 int xivo_hip_compress_oos(xivo_hip_ctx* ctx, int B, double trigger_ratio, int* rows_out);
 /* Estimator::OnePointRANSAC (src/update.cpp:213-393) for filters [0,B) on the resident state; call after
  * xivo_hip_jacobians_instate + xivo_hip_mh_gate (the MH inliers are the input set, as OutlierRejection hands them over,

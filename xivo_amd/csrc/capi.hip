@@ -202,7 +202,7 @@ int xivo_hip_create(xivo_hip_ctx** out, int device, int N, int M_max, int batch_
   }
   c->ell.pairs_max = (int)(Mp / 2);
   A(&c->ell.idx, B * c->ell.stride_idx()); A(&c->ell.val, B * c->ell.stride_val()); A(&c->ell.nc, B); A(&c->ell.pw, B); A(&c->ell.over, B);
-  c->ell_over_h.assign(B, 1); c->ell_nc_h.assign(B, ELL_CW); c->ell_pw_h.assign(B, ELL_PW);
+  c->rows.sized(batch_max, ELL_CW, ELL_PW);
   // the hand-over kernel mirrors its three per-filter flags into host-mapped pinned memory: the host picks the kernel
   // instantiations from them after one stream synchronisation. (Three device-to-host copies into pageable vectors cost
   // 85 us of idle GPU per call - a third of a B = 1 step.) If the mapping is refused the copies are used.

@@ -18,14 +18,13 @@ int gate_impl(xivo_hip_ctx* c, int B, double R, double th, double mult, int min_
   char label[64];
   gate_sparse_threads(B, a.sb.F, a.sb.Jc ? 1 : 0, label, sizeof(label));
   StageTimer st(c, ST_GATE, 0.0, label);
-  c->gate_sparse_last = 1;
+  c->rows.gate_wrote(GateLayout::strided);
   return launch_gate_sparse(a, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
 }
 
 int stack_impl(xivo_hip_ctx* c, int B, double R, int write_dense, unsigned char* mask_override = nullptr, int full_rows = 0) {
   StackArgs a{};
   a.sb = scene_buffers(c); a.lay = c->lay; a.mb = meas_buffers(c);
-  if (write_dense) c->ht_valid = true;
   if (mask_override) a.sb.mask = mask_override;
   a.Mp = c->Mpmax; a.Np = c->Np; a.batch = B; a.R = R;
   a.fix_group_block = (full_rows || (c->flags & XIVO_HIP_FLAG_FIX_GROUP_BLOCK)) ? 1 : 0;
@@ -46,17 +45,14 @@ int calib_gate(xivo_hip_ctx* c, int B, double R, double mh_thresh, double mh_mul
   int rc = gate_impl(c, B, R, mh_thresh, mh_mult, min_inliers, 0);
   if (rc) return rc;
   if (gate) {
-    c->M = 2 * c->F; c->Mp = round_up16(c->M);
-    c->dense_valid = true; c->dense_from_ell = false; c->stack_R = R; c->stack_B = B; c->oos_row0 = -1; c->mixed_row0 = -1; c->h_clean = false;
+    c->rows.stacked(B, c->F, R, Stacking::full_rows, /*pw=*/9, /*dense=*/true, CalibCols::in_rows);
     rc = stack_impl(c, B, R, 1, nullptr, /*full_rows=*/1);
     if (rc) return rc;
     GateDenseArgs a{};
     a.mask = c->mask; a.dist = c->dist; a.F = c->F; a.mask_ld = c->Fmax;   // (the stride xivo_hip_stack reads the mask with)
     a.R = R; a.thresh = mh_thresh; a.mult = mh_mult; a.min_inliers = min_inliers; a.have_ell = 0;
     a.feats = c->feats; a.Fmax = c->Fmax;        // absent entries of ragged batches are no candidates (per-filter present count)
-    rc = gate_dense_rows(c, B, a);
-    if (rc) return rc;
-    c->gate_sparse_last = 1;
+    return gate_dense_rows(c, B, a);   // (mask / dist stay in the strided layout gate_impl left)
   }
   return XIVO_HIP_OK;
 }
@@ -88,34 +84,30 @@ int ensure_gate_buffers(xivo_hip_ctx* c, int F) {
 
 // the transposed dense copy: a G-level producer may have skipped it (mixed stacking); a consumer that needs it - the dense-row gate, the as-coded K H - I - rebuilds it from H here
 int ensure_HT(xivo_hip_ctx* c) {
-  if (c->ht_valid) return XIVO_HIP_OK;
+  if (c->rows.ht_alive()) return XIVO_HIP_OK;
   StageTimer st(c, ST_STACK, 0.0, "transpose_H_kernel");
   if (launch_transpose_H(c->H, c->sH, c->Mpmax, c->HT, c->sHT, c->Np, c->Mpmax, c->Np, c->Bmax, c->stream)) return XIVO_HIP_ERR_HIP;
-  c->ht_valid = true;
+  c->rows.ht_materialised();
   return XIVO_HIP_OK;
 }
 
 // the dense copies of the stacked rows, for the consumers that need them (dense pipeline, OOS rows, get_H)
 int ensure_dense(xivo_hip_ctx* c) {
-  if (c->dense_valid) return XIVO_HIP_OK;
-  c->dense_valid = true;
-  if (c->mixed_row0 >= 0) {   // mixed stacking: the in-state rows come from the compressed form, the OOS rows are in place
-    c->h_clean = false; c->ht_valid = false;
+  if (c->rows.dense_alive()) return XIVO_HIP_OK;
+  const int mr0 = c->rows.mixed_row0();
+  if (mr0 >= 0 || c->rows.dense_from_compressed()) {
+    // the compressed rows are the source. Mixed stacking: the in-state rows only, next to the OOS rows already in place (no H^T);
+    // S-level hand-over: H and H^T (filters that do not fit hold dense rows already)
     StageTimer st(c, ST_STACK, 0.0, "ell_to_dense_kernel");
-    return launch_ell_to_dense(c->ell, c->H, c->sH, c->Mpmax, nullptr, c->sHT, c->Np, c->Mpmax, c->Np, c->Bmax, c->stream, c->mixed_row0)
-               ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
+    if (launch_ell_to_dense(c->ell, c->H, c->sH, c->Mpmax, mr0 >= 0 ? nullptr : c->HT, c->sHT, c->Np, c->Mpmax, c->Np, c->Bmax, c->stream, mr0))
+      return XIVO_HIP_ERR_HIP;
+  } else {
+    if (int rc = stack_impl(c, c->rows.restack_args().B, c->rows.restack_args().R, 1)) return rc;
+    // online-calibration stacking on the sparse pipeline: dense rows carry the calibration columns themselves
+    if (c->rows.has_lead()) c->rows.lead_demoted();
   }
-  c->h_clean = false;
-  if (c->dense_from_ell) {   // S-level hand-over: the compressed rows are the source (filters that do not fit hold dense rows already)
-    StageTimer st(c, ST_STACK, 0.0, "ell_to_dense_kernel");
-    return launch_ell_to_dense(c->ell, c->H, c->sH, c->Mpmax, c->HT, c->sHT, c->Np, c->Mpmax, c->Np, c->Bmax, c->stream)
-               ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
-  }
-  if (c->lead_valid) {   // online-calibration stacking on the sparse pipeline: dense rows carry the calibration columns themselves
-    c->lead_valid = false;
-    for (int b = 0; b < c->stack_B; ++b) c->ell_over_h[b] = 1;
-  }
-  return stack_impl(c, c->stack_B, c->stack_R, 1);
+  c->rows.dense_materialised();
+  return XIVO_HIP_OK;
 }
 
 int gate_dense_rows(xivo_hip_ctx* c, int B, GateDenseArgs a) {
@@ -123,7 +115,7 @@ int gate_dense_rows(xivo_hip_ctx* c, int B, GateDenseArgs a) {
   if (rc) return rc;
   const int Np = c->Np, ldh = c->Mpmax;
   GemmExtra x; x.C2 = c->PHT; x.sC2 = c->sK; x.ldc2 = Np;
-  rc = gemm(c, ST_HP, B, c->Mp, Np, c->H, c->sH, ldh, c->P, c->sP, Np, Np, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, c->HP, c->sH, ldh, x);
+  rc = gemm(c, ST_HP, B, c->rows.rows_padded(), Np, c->H, c->sH, ldh, c->P, c->sP, Np, Np, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, c->HP, c->sH, ldh, x);
   if (rc) return rc;
   a.H = c->H; a.strideH = c->sH; a.ldh = ldh; a.HP = c->HP; a.strideHP = c->sH; a.ldhp = ldh;
   a.Hw = c->H; a.HTw = c->HT; a.strideHT = c->sHT; a.ldht = Np; a.HPw = nullptr; a.PHTw = nullptr; a.PHTr = c->PHT;
@@ -217,7 +209,7 @@ int xivo_hip_set_calib(xivo_hip_ctx* c, const xivo_calib_layout* layout) {
   if (!c->calib) { int rc = dev_alloc(&c->calib, (size_t)c->Bmax); if (rc) return rc; }
   if (!c->Jc && c->Fmax > 0) { int rc = dev_alloc(&c->Jc, (size_t)c->Bmax * c->Fmax * 44); if (rc) return rc; }
   if (!c->Hlead) { int rc = dev_alloc(&c->Hlead, (size_t)c->Bmax * c->Mpmax * LEAD_K); if (rc) return rc; }
-  c->lead_valid = false;
+  c->rows.lead_dropped();
   c->cl = l;
   c->calib_on = l.td >= 0 || l.cam_dim > 0;       // measurement side: blocks beyond the default build's (the Cg / bg blocks sit inside the td block)
   c->calib_motion = l.td >= 0 || l.Cg >= 0;       // motion side: kMotionSize > 23
@@ -268,31 +260,18 @@ int xivo_hip_mh_gate(xivo_hip_ctx* c, int B, double R, double mh_thresh, double 
   //  with XIVO_HIP_FLAG_DENSE_H the dense-row gate of round 4)
   int rc = (c->calib_on && !calib_sparse(c)) ? calib_gate(c, B, R, mh_thresh, mh_mult, min_inliers, 1)
                                              : gate_impl(c, B, R, mh_thresh, mh_mult, min_inliers, 1);
-  if (rc) return rc;
-  const size_t F = c->F, Fm = c->Fmax;
-  if (mask_out) { rc = d2h_rows(c, mask_out, F, c->mask, Fm, F, B); if (rc) return rc; }
-  if (dist_out) {
-    rc = d2h_rows(c, dist_out, F * sizeof(double), c->dist, Fm * sizeof(double), F * sizeof(double), B);
-    if (rc) return rc;
-  }
-  return XIVO_HIP_OK;
+  return rc ? rc : xivo_hip_get_gate(c, B, c->F, mask_out, dist_out);   // (in the strided layout the gate just left)
 }
 
 int xivo_hip_stack(xivo_hip_ctx* c, int B, double R) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0) return XIVO_HIP_ERR_INVALID;
-  c->M = 2 * c->F; c->Mp = round_up16(c->M);
-  const bool csp = calib_sparse(c);
-  for (int b = 0; b < B; ++b) {
-    // (calibration blocks: up to 34 shared columns - dense rows, or compressed rows + the leading dense block)
-    c->ell_over_h[b] = (c->calib_on && !csp) ? 1 : 0; c->ell_nc_h[b] = 12;
-    c->ell_pw_h[b] = (c->flags & XIVO_HIP_FLAG_FIX_GROUP_BLOCK) ? 9 : 6;   // group block(s) + feature block
-  }
-  c->lead_valid = csp;
+  // (calibration blocks: up to 34 shared columns - dense rows, or compressed rows + the leading dense block)
+  const CalibCols cc = !c->calib_on ? CalibCols::none : calib_sparse(c) ? CalibCols::lead_block : CalibCols::in_rows;
   // the sparse-H pipeline reads only the compressed rows: skip the 2 x Mp x Np dense zero-fill + scatter
-  const int dense = ((c->flags & XIVO_HIP_FLAG_DENSE_H) || (c->calib_on && !csp)) ? 1 : 0;
-  c->dense_valid = dense != 0; c->dense_from_ell = false; c->stack_R = R; c->stack_B = B; c->oos_row0 = -1;
-  c->mixed_row0 = -1; if (dense) c->h_clean = false;
+  const int dense = ((c->flags & XIVO_HIP_FLAG_DENSE_H) || cc == CalibCols::in_rows) ? 1 : 0;
+  const int pw = (c->flags & XIVO_HIP_FLAG_FIX_GROUP_BLOCK) ? 9 : 6;   // group block(s) + feature block
+  c->rows.stacked(B, c->F, R, Stacking::in_state_as_coded, pw, /*dense=*/dense != 0, cc);
   return stack_impl(c, B, R, dense);
 }
 
@@ -311,7 +290,7 @@ int xivo_hip_oos_project_ex(xivo_hip_ctx* c, int b0, int nb, int n_oos, const xi
   const int whole = (options & XIVO_HIP_OOS_WHOLE_BUFFER) ? 2 * c->lay.n_groups : 0;
   // feats == NULL: the list uploaded by the previous call is still resident (same nb, n_oos) - project it again
   if (!feats && (!c->oos || c->oos_nb != nb || c->oos_n != n_oos || c->oos_whole != whole)) return XIVO_HIP_ERR_INVALID;
-  int max_rows = feats ? 0 : c->oos_max_rows;
+  int max_rows = feats ? 0 : c->rows.oos_max_rows();
   for (int b = 0; feats && b < nb; ++b) {
     int rows = 0;
     for (int o = 0; o < n_oos; ++o) {
@@ -324,28 +303,28 @@ int xivo_hip_oos_project_ex(xivo_hip_ctx* c, int b0, int nb, int n_oos, const xi
     }
     if (rows > max_rows) max_rows = rows;
   }
-  if (c->M + max_rows > c->Mmax) return XIVO_HIP_ERR_INVALID;
+  const int M = c->rows.rows();
+  if (M + max_rows > c->Mmax) return XIVO_HIP_ERR_INVALID;
   // Mixed stacking (round 3, default whenever the in-state rows were stacked in the compressed form only and nothing
   // forces the dense pipeline): the OOS rows go to the dense buffer behind the in-state rows and the update keeps the
   // sparse walk for the in-state rows - only the OOS block takes the MFMA products (update_sparse_range). Needs a
   // 16-row-padded OOS block inside the allocation; otherwise (and with XIVO_HIP_FLAG_DENSE_H) every row
   // becomes dense as before.
-  const bool mixed = !c->calib_on && !c->dense_valid && !c->dense_from_ell && c->oos_row0 < 0 && b0 == 0 &&
-                     !(c->flags & XIVO_HIP_FLAG_DENSE_H) && (c->M % 2 == 0) &&
-                     c->M + round_up16(max_rows + 16) <= c->Mpmax && c->Np <= 512;
-  if (!mixed) { int rcd = ensure_dense(c); if (rcd) return rcd; c->mixed_row0 = -1; }
+  const bool mixed = !c->calib_on && !c->rows.dense_alive() && !c->rows.dense_from_compressed() && c->rows.oos_row0() < 0 && b0 == 0 &&
+                     !(c->flags & XIVO_HIP_FLAG_DENSE_H) && (M % 2 == 0) &&
+                     M + round_up16(max_rows + 16) <= c->Mpmax && c->Np <= 512;
+  if (!mixed) { int rcd = ensure_dense(c); if (rcd) return rcd; }
   else {
     // the OOS rows must start from zero: only the extrinsics and group columns are ever written there in this mode, so
     // those are cleared (whole rows once, if anything else has used the dense buffer since it was allocated)
-    const int nz = round_up16(max_rows + 16) < c->Mpmax - c->M ? round_up16(max_rows + 16) : c->Mpmax - c->M;
-    if (!c->h_clean) {
+    const int nz = std::min(round_up16(max_rows + 16), c->Mpmax - M);
+    if (!c->rows.dense_clean()) {
       HIP_TRY((hipError_t)launch_zero_rows(c->H, c->sH, c->Mpmax, 0, c->Mpmax, 0, c->Np, c->Bmax, c->stream));
-      c->h_clean = true;
+      c->rows.dense_zeroed();
     } else {
-      HIP_TRY((hipError_t)launch_zero_rows(c->H, c->sH, c->Mpmax, c->M, nz, 15, 21, nb, c->stream));
-      HIP_TRY((hipError_t)launch_zero_rows(c->H, c->sH, c->Mpmax, c->M, nz, c->lay.group_begin, c->lay.group_begin + 6 * c->lay.n_groups, nb, c->stream));
+      HIP_TRY((hipError_t)launch_zero_rows(c->H, c->sH, c->Mpmax, M, nz, 15, 21, nb, c->stream));
+      HIP_TRY((hipError_t)launch_zero_rows(c->H, c->sH, c->Mpmax, M, nz, c->lay.group_begin, c->lay.group_begin + 6 * c->lay.n_groups, nb, c->stream));
     }
-    c->mixed_row0 = c->M;
   }
   if (n_oos * nb > c->oos_cap) {
     if (c->oos) hipFree(c->oos);
@@ -358,14 +337,13 @@ int xivo_hip_oos_project_ex(xivo_hip_ctx* c, int b0, int nb, int n_oos, const xi
   if (!c->oos_rows) { int rc = dev_alloc(&c->oos_rows, (size_t)c->Bmax); if (rc) return rc; }
   if (feats) {
     HIP_TRY(hipMemcpyAsync(c->oos, feats, (size_t)nb * n_oos * sizeof(xivo_oos_in), hipMemcpyHostToDevice, c->stream));
-    c->oos_nb = nb; c->oos_n = n_oos; c->oos_max_rows = max_rows; c->oos_whole = whole;
+    c->oos_nb = nb; c->oos_n = n_oos; c->oos_whole = whole;
   }
   OosArgs a{};
   a.feats = c->oos; a.n_oos = n_oos; a.poses = c->poses; a.groups = c->groups; a.lay = c->lay; a.cam = c->cam;
   a.calib = c->calib_on ? c->calib : nullptr; a.cam_dim = c->calib_on ? c->cl.cam_dim : 0;
-  a.mb = meas_buffers(c); a.row0 = c->M; a.Mp = c->Mpmax; a.Np = c->Np; a.batch = nb; a.Roos = Roos; a.whole = whole;
-  if (mixed) { a.mb.HT = nullptr; c->ht_valid = false; }
-  c->oos_row0 = c->M; c->oos_R = Roos;
+  a.mb = meas_buffers(c); a.row0 = M; a.Mp = c->Mpmax; a.Np = c->Np; a.batch = nb; a.Roos = Roos; a.whole = whole;
+  if (mixed) a.mb.HT = nullptr;
   a.rows_out = c->oos_rows;
   {
     StageTimer st(c, ST_OTHER, 0.0, "oos_kernel");
@@ -373,8 +351,7 @@ int xivo_hip_oos_project_ex(xivo_hip_ctx* c, int b0, int nb, int n_oos, const xi
   }
   if (rows_out) HIP_TRY(hipMemcpyAsync(rows_out, c->oos_rows, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->M += max_rows; c->Mp = round_up16(c->M);
-  if (!mixed) for (int b = b0; b < b0 + nb; ++b) c->ell_over_h[b] = 1;   // OOS rows are dense over the group blocks: dense path
+  c->rows.oos_appended(max_rows, Roos, mixed, b0, nb);   // (not mixed: OOS rows are dense over the group blocks - dense path)
   return XIVO_HIP_OK;
 }
 
@@ -435,13 +412,9 @@ int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_th
     HIP_TRY((hipError_t)launch_ransac_zero(a, c->P, c->stream));
   }
   // partial update: H_ rows = the full J() of the low-innovation inliers (:326 - no FillJacobianBlock), R_ on the diagonal
-  c->M = 2 * c->F; c->Mp = round_up16(c->M);
-  for (int b = 0; b < B; ++b) { c->ell_over_h[b] = cal ? 1 : 0; c->ell_nc_h[b] = 12; c->ell_pw_h[b] = 9; }
-  c->lead_valid = false;
   const int dense = ((c->flags & XIVO_HIP_FLAG_DENSE_H) || cal) ? 1 : 0;
-  c->dense_valid = dense != 0; c->dense_from_ell = !cal; c->stack_R = R; c->stack_B = B;
-  c->oos_row0 = -1;   // the partial stacking replaces the rows of any earlier xivo_hip_oos_project (as xivo_hip_stack does)
-  c->mixed_row0 = -1; if (dense) c->h_clean = false;
+  const CalibCols cc = cal ? CalibCols::in_rows : CalibCols::none;
+  c->rows.stacked(B, c->F, R, Stacking::full_rows, /*pw=*/9, /*dense=*/dense != 0, cc);
   int rc = stack_impl(c, B, R, dense, c->rs_low, 1);
   if (rc) return rc;
   rc = xivo_hip_update_joseph(c, B);
@@ -464,7 +437,7 @@ int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_th
   } else {
     // S = J P J^T + R of every MH inlier on its WHOLE row at the updated state against the partially updated P (:350-356):
     // the rows stacked once more in full (scratch: xivo_hip_stack re-stacks the final inlier set), H P, the dense-row distances
-    c->dense_valid = true; c->dense_from_ell = false; c->h_clean = false;
+    c->rows.stacked(B, c->F, R, Stacking::full_rows, /*pw=*/9, /*dense=*/true, cc);
     rc = stack_impl(c, B, R, 1, nullptr, /*full_rows=*/1);
     if (rc) return rc;
     GateDenseArgs ga{};
@@ -486,7 +459,7 @@ int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_th
   HIP_TRY(hipMemcpyAsync(c->mask, c->rs_keep, (size_t)B * c->Fmax, hipMemcpyDeviceToDevice, c->stream));
   rc = xivo_hip_jacobians_instate(c, B);
   if (rc) return rc;
-  c->gate_sparse_last = 1;
+  c->rows.gate_wrote(GateLayout::strided);
   const size_t F = c->F, Fm = c->Fmax;
   if (inlier_mask_out) { rc = d2h_rows(c, inlier_mask_out, F, c->mask, Fm, F, B); if (rc) return rc; }
   if (chi2_out) { rc = d2h_rows(c, chi2_out, F * sizeof(double), c->rs_chi, Fm * sizeof(double), F * sizeof(double), B); if (rc) return rc; }
@@ -534,7 +507,6 @@ int xivo_hip_close_loop_stack(xivo_hip_ctx* c, int b0, int nb, int n, const xivo
     StageTimer st(c, ST_OTHER, 0.0, "lc_rows_kernel");
     HIP_TRY((hipError_t)launch_lc_rows(a, c->stream));
   }
-  c->oos_row0 = -1;
   return stage_measurements(c, b0, nb, M, a.H, a.strideH, a.ldh, a.inn, a.strideV, a.diagR, a.strideV);
 }
 
@@ -544,17 +516,17 @@ int xivo_hip_close_loop_stack(xivo_hip_ctx* c, int b0, int nb, int n, const xivo
 // decomposition (oos_compress_kernel) and the row count of the stacked measurement shrinks accordingly.
 int xivo_hip_compress_oos(xivo_hip_ctx* c, int B, double trigger_ratio, int* rows_out) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->oos_row0 < 0 || !c->oos_rows || B != c->oos_nb || !(trigger_ratio >= 1.0))
+  if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->rows.oos_row0() < 0 || !c->oos_rows || B != c->oos_nb || !(trigger_ratio >= 1.0))
     return XIVO_HIP_ERR_INVALID;
   OosCompressArgs a{};
-  a.lay = c->lay; a.mb = meas_buffers(c); a.row0 = c->oos_row0; a.rows = c->oos_rows; a.rows_out = c->oos_rows;
-  if (c->mixed_row0 >= 0) { a.mb.HT = nullptr; c->ht_valid = false; }
-  a.ratio = trigger_ratio; a.Roos = c->oos_R; a.batch = B;
+  a.lay = c->lay; a.mb = meas_buffers(c); a.row0 = c->rows.oos_row0(); a.rows = c->oos_rows; a.rows_out = c->oos_rows;
+  if (c->rows.mixed_row0() >= 0) a.mb.HT = nullptr;
+  a.ratio = trigger_ratio; a.Roos = c->rows.oos_R(); a.batch = B;
   int rc = -1;
   char label[64];
-  if (oos_compress_pick(c->lay.n_groups, c->oos_max_rows, label, sizeof(label)) >= 0) {
+  if (oos_compress_pick(c->lay.n_groups, c->rows.oos_max_rows(), label, sizeof(label)) >= 0) {
     StageTimer st(c, ST_OTHER, 0.0, label);
-    rc = launch_oos_compress(a, c->oos_max_rows, c->stream);
+    rc = launch_oos_compress(a, c->rows.oos_max_rows(), c->stream);
   }
   if (rc > 0) return XIVO_HIP_ERR_HIP;
   std::vector<int> rows(B);
@@ -563,7 +535,7 @@ int xivo_hip_compress_oos(xivo_hip_ctx* c, int B, double trigger_ratio, int* row
   int mx = 0;
   for (int b = 0; b < B; ++b) mx = rows[b] > mx ? rows[b] : mx;
   // (rc == -1: block larger than the built kernels - rows are left as they are, which is always valid)
-  c->M = c->oos_row0 + mx; c->Mp = round_up16(c->M); c->oos_max_rows = mx;
+  c->rows.oos_compressed(mx);
   if (rows_out) memcpy(rows_out, rows.data(), (size_t)B * sizeof(int));
   return XIVO_HIP_OK;
 }
@@ -576,17 +548,11 @@ int xivo_hip_filter_update(xivo_hip_ctx* c, int B, double R, double mh_thresh, d
   if (rc) return rc;
   // Estimator::OutlierRejection only gates when F > min_required_inliers_ (src/manager.cpp:635)
   const int gate = use_gating && c->F > min_inliers;
-  if (c->calib_on && !calib_sparse(c)) {
-    // online-calibration builds on dense rows (XIVO_HIP_FLAG_DENSE_H): the gate needs the WHOLE row J() incl. the td / Cg / bg / intrinsics blocks (update.cpp:60-70),
-    // which is not the row FillJacobianBlock stacks (the :675-676 overwrite): every present feature is stacked once as its
-    // full J() (dense rows), gated on (J P) J^T + R by the dense-row gate, then the inliers are stacked as coded and updated
-    rc = calib_gate(c, B, R, mh_thresh, mh_mult, min_inliers, gate);
-    if (rc) return rc;
-    rc = xivo_hip_stack(c, B, R);
-    if (rc) return rc;
-    return xivo_hip_update_joseph(c, B);
-  }
-  rc = gate_impl(c, B, R, mh_thresh, mh_mult, min_inliers, gate);
+  // online-calibration builds on dense rows (XIVO_HIP_FLAG_DENSE_H): the gate needs the WHOLE row J() incl. the td / Cg / bg / intrinsics blocks (update.cpp:60-70),
+  // which is not the row FillJacobianBlock stacks (the :675-676 overwrite): every present feature is stacked once as its
+  // full J() (dense rows), gated on (J P) J^T + R by the dense-row gate, then the inliers are stacked as coded and updated
+  rc = (c->calib_on && !calib_sparse(c)) ? calib_gate(c, B, R, mh_thresh, mh_mult, min_inliers, gate)
+                                         : gate_impl(c, B, R, mh_thresh, mh_mult, min_inliers, gate);
   if (rc) return rc;
   rc = xivo_hip_stack(c, B, R);
   if (rc) return rc;
@@ -1041,8 +1007,8 @@ int xivo_hip_get_scene(xivo_hip_ctx* c, int b0, int nb, xivo_pose_in* poses, xiv
 
 int xivo_hip_get_H(xivo_hip_ctx* c, int b, int* M_out, double* H, int ldh, double* inn, double* diagR) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (bad_range(c, b, 1) || c->M <= 0) return XIVO_HIP_ERR_INVALID;
-  const int M = c->M;
+  const int M = c ? c->rows.rows() : 0;
+  if (bad_range(c, b, 1) || M <= 0) return XIVO_HIP_ERR_INVALID;
   if (M_out) *M_out = M;
   if (H) {
     if (ldh < M) return XIVO_HIP_ERR_INVALID;

@@ -17,6 +17,7 @@
 #include "ekf_kernels.h"
 #include "ell.h"
 #include "fused_update.h"
+#include "staged_rows.h"
 
 namespace xivo_hip::capi {
 
@@ -42,25 +43,15 @@ struct xivo_hip_ctx {
   double *err = nullptr, *staging = nullptr, *scratch = nullptr;
   double *neg1 = nullptr, *yvec = nullptr;   // symmetric form: a vector of -1 (operand scale), y = L^-1 inn per filter
   int* status = nullptr;
-  // row-pair compressed H (ell.h) + host mirror of the per-filter "does not fit" flag
+  // row-pair compressed H (ell.h); which representations of the staged rows are valid right now: staged_rows.h
   xivo_hip::EllBuffers ell{};
-  std::vector<int> ell_over_h, ell_nc_h, ell_pw_h;
+  xivo_hip::capi::StagedRows rows;
   int* ell_flags_h = nullptr;   // pinned, device-mapped [Bmax][3]: over / nc / pw as the hand-over kernel leaves them
   int* ell_flags_d = nullptr;   // its device alias
   int last_path = 0;
   int last_route = 0;   // UpdateRoute of the last pass (xivo_hip_last_route)
-  // dense H / H^T of the stacked rows: written eagerly by set_measurements, lazily after xivo_hip_stack
-  bool dense_valid = true;
-  bool dense_from_ell = false;   // the stacked rows came in through set_measurements (compressed rows are the source)
-  bool ht_valid = true;          // the transposed dense copy H^T matches H (false after a producer skipped it: mixed stacking)
-  // mixed stacking (round 3): in-state rows [0, mixed_row0) exist in the row-pair compressed form only, the OOS rows
-  // appended by xivo_hip_oos_project from row mixed_row0 on in the dense buffer only; -1: not in that mode
-  int mixed_row0 = -1;
-  bool h_clean = true;           // every row of the dense H buffer the mixed mode has not written itself is zero
-  double stack_R = 0.0; int stack_B = 0;
   size_t staging_elems = 0;
   long sP = 0, sH = 0, sHT = 0, sS = 0, sK = 0, sInvD = 0, sA = 0;   // sA: A buffer, max(N x N, N x M)
-  int M = 0, Mp = 0;  // rows currently staged
   int chunk = 0;      // filters per pipeline pass (0 = whole batch)
   int call_batch = 0; // filters of the whole update call being walked in chunks (0: not chunked)
   int* ldlt_used = nullptr;     // per filter: 1 = the last update went through the pivoted L D L^T fallback
@@ -88,19 +79,16 @@ struct xivo_hip_ctx {
   xivo_feat_in* feats = nullptr;
   double *J = nullptr, *finn = nullptr, *dist = nullptr;
   unsigned char* mask = nullptr;
-  int gate_sparse_last = 0;   // mask/dist row stride: Fmax after the layout-faithful gate, F after the dense one
   int* rows_instate = nullptr;
   xivo_oos_in* oos = nullptr;
   int oos_cap = 0;
-  int oos_row0 = -1;   // first row of the OOS block of the last xivo_hip_oos_project (-1: none since the last stacking)
-  double oos_R = 0.0;
   double* pd_h = nullptr; double pd_h0 = 0.0;   // step-size-controlled Dormand-Prince: the step each filter carries (xivo_hip_propagate)
-  int oos_nb = 0, oos_n = 0, oos_max_rows = 0, oos_whole = 0;   // shape of the resident OOS list (xivo_hip_oos_project with feats == NULL)
+  int oos_nb = 0, oos_n = 0, oos_whole = 0;   // shape of the resident OOS list (xivo_hip_oos_project with feats == NULL; its row bound: rows)
   int* oos_rows = nullptr;
   xivo_calib_in* calib_rs = nullptr;            // BackupState of the calibration state (OnePointRANSAC, online-calibration builds)
   // online-calibration builds on the sparse pipeline (round 5): the calibration columns of the stacked rows as a dense
-  // [Mpmax x LEAD_K] block per filter next to the row-pair compressed rows; lead_valid: the current stacking has one
-  double* Hlead = nullptr; bool lead_valid = false;
+  // [Mpmax x LEAD_K] block per filter next to the row-pair compressed rows (rows.has_lead(): the current stacking has one)
+  double* Hlead = nullptr;
   void* lc_buf = nullptr; size_t lc_cap = 0;   // xivo_hip_close_loop_stack: matches | dense rows | inn | diagR
   xivo_subfilter_feat* sub = nullptr;   // staging of xivo_hip_subfilter_update
   // out-of-state feature pool (xivo_hip_pool_*): entries [Bmax][pool_max] (ref_sind = the entry's anchor, -1: free), anchors

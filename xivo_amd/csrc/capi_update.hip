@@ -41,19 +41,16 @@ struct UpdatePlan {
 // (B = the filters of this pass; with the batch walked in chunks - XIVO_HIP_CHUNK - the few-filter decision is made on the
 //  WHOLE call's batch, c->call_batch: chunks of <= 64 filters of a large batch must not take the few-filter kernels)
 static UpdatePlan plan_update(const xivo_hip_ctx* c, int b0, int B, bool gate) {
-  const int Np = c->Np, Mp = c->Mp;
+  const StagedRows& r = c->rows;
+  const int Np = c->Np, Mp = r.rows_padded();
   const unsigned f = c->flags;
   UpdatePlan p{};
-  bool sparse = !(f & XIVO_HIP_FLAG_DENSE_H);
-  int nc_max = 0, pw_max = 1;
-  for (int b = b0; b < b0 + B; ++b) {
-    sparse = sparse && c->ell_over_h[b] == 0;
-    nc_max = std::max(nc_max, c->ell_nc_h[b]); pw_max = std::max(pw_max, c->ell_pw_h[b]);
-  }
-  const bool extra_rows = c->mixed_row0 >= 0 || c->lead_valid;     // dense OOS rows / the leading calibration block next to the compressed rows
+  bool sparse = !(f & XIVO_HIP_FLAG_DENSE_H) && !r.any_over(b0, B);
+  const auto [nc_max, pw_max] = r.max_slots(b0, B);
+  const bool extra_rows = r.mixed_row0() >= 0 || r.has_lead();     // dense OOS rows / the leading calibration block next to the compressed rows
   // the stand-alone tail's G = T H^T walks compressed rows of ALL of H, and the compact gate of a calibration stacking reads whole rows
-  if (sparse && extra_rows && ((f & XIVO_HIP_FLAG_STANDALONE_TAIL) || (c->lead_valid && gate))) sparse = false;
-  if (sparse && c->lead_valid && (f & XIVO_HIP_FLAG_SYMMETRIC_FORM)) sparse = false;
+  if (sparse && extra_rows && ((f & XIVO_HIP_FLAG_STANDALONE_TAIL) || (r.has_lead() && gate))) sparse = false;
+  if (sparse && r.has_lead() && (f & XIVO_HIP_FLAG_SYMMETRIC_FORM)) sparse = false;
   p.sparse = sparse;
   const bool holds = trsm_forms_T(Mp, Np);                          // one workgroup per filter holds the factor and every column of the state
   const int Ball = c->call_batch > B ? c->call_batch : B;
@@ -107,7 +104,7 @@ RangeView range_view(xivo_hip_ctx* c, int b0) {
 // S = L L^T (chol_f64.hip) over B filters, the gate folded into its prologue when `cg` is given. `flops`: what the calling
 // pipeline counts for the stage.
 int factor_S(xivo_hip_ctx* c, const RangeView& v, int B, int latency, const CholGateArgs* cg, double flops) {
-  const int Mp = c->Mp;
+  const int Mp = c->rows.rows_padded();
   CholArgs a{}; a.S = v.S; a.strideS = c->sS; a.lds = c->Mpmax; a.Mp = Mp; a.invD = v.invD; a.strideInvD = c->sInvD;
   a.status = v.status; a.batch = B; a.latency = latency;
   char clabel[64]; chol_kernel_label(Mp, B, clabel, sizeof(clabel));
@@ -122,7 +119,7 @@ int factor_S(xivo_hip_ctx* c, const RangeView& v, int B, int latency, const Chol
 TrsmArgs trsm_args(const xivo_hip_ctx* c, const RangeView& v, int B) {
   TrsmArgs a{}; a.LU = v.S; a.strideLU = c->sS; a.ldlu = c->Mpmax; a.invD = v.invD; a.strideInvD = c->sInvD;
   a.PHT = v.PHT; a.stridePHT = c->sK; a.ldpht = c->Np; a.K = v.K; a.strideK = c->sK; a.ldk = c->Np;
-  a.inn = v.inn; a.strideInn = c->Mpmax; a.err = v.err; a.strideErr = c->Np; a.Mp = c->Mp; a.Np = c->Np; a.batch = B;
+  a.inn = v.inn; a.strideInn = c->Mpmax; a.err = v.err; a.strideErr = c->Np; a.Mp = c->rows.rows_padded(); a.Np = c->Np; a.batch = B;
   return a;
 }
 // XIVO_HIP_FLAG_SYMMETRIC_FORM: gain and covariance in the symmetric "square-root" form. With S = L L^T and
@@ -132,7 +129,7 @@ TrsmArgs trsm_args(const xivo_hip_ctx* c, const RangeView& v, int B) {
 // N x N x M product; its rounding error grows with cond(L) = sqrt(cond(S)), not cond(S). Opt-in: the reference codes
 // the Joseph form, which stays the default.
 static int finish_symmetric(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeView& v, int B) {
-  const int Np = c->Np, Mp = c->Mp;
+  const int Np = c->Np, Mp = c->rows.rows_padded();
   {
     StageTimer st(c, ST_OTHER, 0.0, "fwd_vec_kernel");
     HIP_TRY((hipError_t)launch_fwd_vec(v.S, c->sS, c->Mpmax, v.invD, c->sInvD, v.inn, c->Mpmax, v.y, c->Mpmax, Mp, B, c->stream));
@@ -144,7 +141,7 @@ static int finish_symmetric(xivo_hip_ctx* c, const UpdatePlan& plan, const Range
     const bool p_here = plan.in_solve;
     if (p_here) { a.T = v.P; a.strideT = c->sP; a.ldt = Np; a.skip_status = v.status; }
     char label[64]; trsm_kernel_label(Mp, label, sizeof(label), p_here ? 2 : 0);
-    const double outs = 0.5 * Np * (Np + 1.0), Nf = c->N, Mf = c->M;
+    const double outs = 0.5 * Np * (Np + 1.0), Nf = c->N, Mf = c->rows.rows();
     StageTimer st(c, ST_TRSM, (1.0 * Mf * Mf * Nf + (p_here ? Nf * (Nf + 1.0) * Mf : 0.0)) * B, label,
                   8.0 * B * (0.5 * Mp * (Mp + 1) + Mp / 16 * 512.0 + (p_here ? 1.0 : 2.0) * Np * Mp + (p_here ? outs + (double)Np * Np : 0.0)));
     HIP_TRY((hipError_t)launch_trsm_f64(a, c->stream));
@@ -163,8 +160,8 @@ static int finish_symmetric(xivo_hip_ctx* c, const UpdatePlan& plan, const Range
 //   in_solve : W = L^-1 (HP), K^T = L^-T W, dx, P+ = P - (W - D)^T (W + D) inside the solve kernel  estimator.cpp:1265-1287
 //   else     : V^T, Y^T leave the (chunked / streamed) solve, P+ = P - V^T Y as one tiled symmetric product
 static int finish_whitened(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeView& v, int B, const CholGateArgs* cg) {
-  const int Np = c->Np, Mp = c->Mp;
-  const double Nf = c->N, Mf = c->M;
+  const int Np = c->Np, Mp = c->rows.rows_padded();
+  const double Nf = c->N, Mf = c->rows.rows();
   // (the streamed solve reads the mirrored upper triangle)
   int rc = factor_S(c, v, B, plan.latency || plan.stream8, cg, Mf * Mf * Mf / 3.0 * B);
   if (rc) return rc;
@@ -206,13 +203,12 @@ static int finish_whitened(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeV
 //                    then finish_whitened / finish_symmetric, or (SPARSE_TAIL)
 //                    T = K (HP) - P, G = T H^T + K R, P+ = G K^T - T                          estimator.cpp:1276-1287 re-associated
 static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeView& v, int b0, int B, const GateParams* gate) {
-  const int Np = c->Np, Mp = c->Mp, ldh = c->Mpmax, lds = c->Mpmax;
+  const int Np = c->Np, Mp = c->rows.rows_padded(), ldh = c->Mpmax, lds = c->Mpmax;
   double *P = v.P, *HP = v.HP, *PHT = v.PHT, *S = v.S, *K = v.K, *G = v.A, *T = v.T, *inn = v.inn, *diagR = v.diagR;
   const EllBuffers& e = v.ell;
-  int nc_max = 0, pw_max = 1;
-  for (int b = b0; b < b0 + B; ++b) { nc_max = std::max(nc_max, c->ell_nc_h[b]); pw_max = std::max(pw_max, c->ell_pw_h[b]); }
+  const auto [nc_max, pw_max] = c->rows.max_slots(b0, B);
   // algorithmic flops are counted on the TRUE sizes N, M (the padded Np, Mp only size the launches and the bytes)
-  const double Nf = c->N, Mf = c->M;
+  const double Nf = c->N, Mf = c->rows.rows();
   const double nnz_flops = 2.0 * Mf * 21.0;   // per contiguous-index value: 21 structural non-zeros per row
   int rc;
   if (plan.route == ROUTE_FUSED) {
@@ -226,8 +222,7 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
     if (gate) {
       a.gate = 1; a.F = gate->F; a.R = gate->R; a.thresh = gate->thresh; a.mult = gate->mult; a.min_inliers = gate->min_inliers;
       a.mask = c->mask + (long)b0 * gate->F; a.dist = c->dist + (long)b0 * gate->F;
-      if (c->dense_valid) { a.H = v.H; a.strideH = c->sH; a.ldh = ldh; a.HT = v.HT; a.strideHT = c->sHT; a.ldht = Np; }
-      c->gate_sparse_last = 0;
+      if (c->rows.dense_alive()) { a.H = v.H; a.strideH = c->sH; a.ldh = ldh; a.HT = v.HT; a.strideHT = c->sHT; a.ldht = Np; }
     }
     char label[64]; fused_update_label(Mp, Np, pw_max, label, sizeof(label));
     const double t_outs_f = 0.5 * Nf * (Nf + 1.0);
@@ -239,7 +234,7 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
   // mixed stacking: rows [0, mr0) of H are the compressed in-state rows, rows [mr0, M) the dense OOS rows appended by
   // xivo_hip_oos_project (non-zero over the extrinsics + group columns only: src/oos.cpp:74-88). The in-state rows keep the
   // sparse walk below; the OOS block goes through two small MFMA products (rows padded to 16 from mr0 on).
-  const int mr0 = c->mixed_row0;
+  const int mr0 = c->rows.mixed_row0();
   const int Mp_ell = mr0 >= 0 ? round_up16(mr0) : Mp;
   const int oos_pad = mr0 >= 0 ? round_up16(Mp - mr0) : 0;
   // the OOS rows are zero beyond the extrinsics and group columns (the mode clears and writes nothing else there): the two
@@ -262,7 +257,7 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
   }
   // online-calibration stacking on the sparse pipeline: the calibration columns of H live in the leading dense block
   // L [Mp x LEAD_K] (stack_kernel): P H^T += P[:, 0:LEAD_K] L^T on the MFMA product
-  const bool lead = c->lead_valid && mr0 < 0;
+  const bool lead = c->rows.has_lead() && mr0 < 0;
   const double* Ld = lead ? v.lead : nullptr;
   const long sLd = (long)c->Mpmax * LEAD_K;
   const int ldl = c->Mpmax;   // (stack_kernel lays the block out on the allocated row count)
@@ -277,8 +272,8 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
   GateEllArgs ga{};
   if (gate) {
     ga.ell = e;
-    ga.H = c->dense_valid ? v.H : nullptr; ga.strideH = c->sH; ga.ldh = ldh;
-    ga.HT = c->dense_valid ? v.HT : nullptr; ga.strideHT = c->sHT; ga.ldht = Np; ga.PHT = PHT;
+    ga.H = c->rows.dense_alive() ? v.H : nullptr; ga.strideH = c->sH; ga.ldh = ldh;
+    ga.HT = c->rows.dense_alive() ? v.HT : nullptr; ga.strideHT = c->sHT; ga.ldht = Np; ga.PHT = PHT;
     ga.HP = nullptr;   // H P [Mp x Np] has no reader behind this point (S is formed already, the solve reads P H^T)
     ga.inn = inn; ga.strideInn = c->Mpmax; ga.diagR = diagR; ga.strideR = c->Mpmax;
     ga.mask = c->mask + (long)b0 * gate->F; ga.dist = c->dist + (long)b0 * gate->F;
@@ -312,7 +307,6 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
     rc = gemm(c, ST_S, B, Mp, Mp, HP, c->sH, ldh, Ld, sLd, ldl, LEAD_K, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, S, c->sS, lds, x);
     if (rc) return rc;
   }
-  if (gate) c->gate_sparse_last = 0;
   // With thousands of factors the gate rides in the prologue of the factorisation (chol_f64.hip, GATE): the distances come
   // from the compact diagonal blocks ell<S> just left, the rejected pairs are decoupled where the factor loads S - no gate
   // launch, no extra pass over S. (Few filters, dense copies of H alive, mixed stacking: the gate kernel.)
@@ -320,7 +314,7 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
   bool gate_folded = false;
   if (gate) {
     if (diag_done) { ga.Sdiag = T; ga.strideSdiag = c->sP; }
-    gate_folded = diag_done && !c->dense_valid && mr0 < 0 && !plan.latency && chol_gate_supported(Mp, B);
+    gate_folded = diag_done && !c->rows.dense_alive() && mr0 < 0 && !plan.latency && chol_gate_supported(Mp, B);
     if (gate_folded) {
       cg.Sdiag = ga.Sdiag; cg.strideSdiag = ga.strideSdiag; cg.inn = inn; cg.strideInn = c->Mpmax; cg.diagR = diagR; cg.strideR = c->Mpmax;
       cg.ellval = e.val; cg.strideVal = e.stride_val(); cg.ell_w = ELL_W; cg.PHT = PHT; cg.stridePHT = c->sK; cg.ldpht = Np; cg.Np = Np;
@@ -378,7 +372,7 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
 }
 
 static int update_dense_range(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeView& v, int b0, int B, const GateParams* gate) {
-  const int Np = c->Np, Mp = c->Mp, ldh = c->Mpmax, lds = c->Mpmax;
+  const int Np = c->Np, Mp = c->rows.rows_padded(), ldh = c->Mpmax, lds = c->Mpmax;
   const double *H = v.H, *HT = v.HT, *inn = v.inn, *diagR = v.diagR;
   double *P = v.P, *HP = v.HP, *PHT = v.PHT, *S = v.S, *K = v.K, *A = v.A_sP, *T = v.T;
   int rc = ensure_dense(c);   // (mixed stacking / a leading block: the in-state rows are rebuilt densely next to the rows already in place)
@@ -402,7 +396,6 @@ static int update_dense_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ran
     a.R = gate->R; a.thresh = gate->thresh; a.mult = gate->mult; a.min_inliers = gate->min_inliers;
     a.ell = c->ell; a.have_ell = 0;
     StageTimer st(c, ST_GATE, 0.0, "gate_dense_kernel");
-    c->gate_sparse_last = 0;
     HIP_TRY((hipError_t)launch_gate_dense(a, c->stream));
   }
   {  // S = HP * H^T + diag(R)  (estimator.cpp:1259-1263); lower triangle + mirror
@@ -456,6 +449,7 @@ static int update_joseph_range(xivo_hip_ctx* c, int b0, int B, const GateParams*
   const UpdatePlan plan = plan_update(c, b0, B, gate != nullptr);
   c->last_path = plan.sparse ? 1 : 0;
   c->last_route = plan.route;
+  if (gate) c->rows.gate_wrote(GateLayout::packed);   // every route's gate writes mask / dist [B][F]
   int rc = plan.sparse ? update_sparse_range(c, plan, v, b0, B, gate) : update_dense_range(c, plan, v, b0, B, gate);
   if (rc || (c->flags & XIVO_HIP_FLAG_NO_LDLT_FALLBACK)) {   // no fallback launch: clear the flags of this call here
     HIP_TRY(hipMemsetAsync(v.ldlt_used, 0, (size_t)B * sizeof(int), c->stream));
@@ -465,8 +459,8 @@ static int update_joseph_range(xivo_hip_ctx* c, int b0, int B, const GateParams*
   LdltFallbackArgs a{};
   a.status = v.status; a.used = v.ldlt_used; a.ell = v.ell;
   a.H = v.H; a.strideH = c->sH; a.ldh = c->Mpmax; a.use_dense = c->last_path == 0 ? 1 : 0;
-  a.mixed_row0 = c->last_path == 1 ? c->mixed_row0 : -1;
-  if (c->last_path == 1 && c->lead_valid) { a.lead = v.lead; a.strideLead = (long)c->Mpmax * LEAD_K; a.ldlead = c->Mpmax; a.lead_k = LEAD_K; }
+  a.mixed_row0 = c->last_path == 1 ? c->rows.mixed_row0() : -1;
+  if (c->last_path == 1 && c->rows.has_lead()) { a.lead = v.lead; a.strideLead = (long)c->Mpmax * LEAD_K; a.ldlead = c->Mpmax; a.lead_k = LEAD_K; }
   a.PHT = v.PHT; a.stridePHT = c->sK; a.ldpht = c->Np;
   a.S = v.S; a.strideS = c->sS; a.lds = c->Mpmax;
   a.K = v.K; a.strideK = c->sK; a.ldk = c->Np;
@@ -475,7 +469,7 @@ static int update_joseph_range(xivo_hip_ctx* c, int b0, int B, const GateParams*
   a.P = v.P; a.strideP = c->sP; a.ldp = c->Np;
   a.inn = v.inn; a.strideInn = c->Mpmax; a.diagR = v.diagR; a.strideR = c->Mpmax;
   a.err = v.err; a.strideErr = c->Np;
-  a.N = c->N; a.M = c->M; a.batch = B;
+  a.N = c->N; a.M = c->rows.rows(); a.batch = B;
   StageTimer st(c, ST_OTHER, 0.0, "ldlt_fallback_kernel");
   HIP_TRY((hipError_t)launch_ldlt_fallback(a, c->stream));
   return XIVO_HIP_OK;
@@ -586,18 +580,16 @@ int stage_measurements(xivo_hip_ctx* c, int b0, int nb, int M, const double* dH,
   MeasBuffers mb = meas_buffers(c);
   mb.H += (long)b0 * mb.strideH; mb.HT += (long)b0 * mb.strideHT;
   mb.inn += (long)b0 * mb.strideInn; mb.diagR += (long)b0 * mb.strideR;
-  c->M = M; c->Mp = round_up16(M);
   const EllBuffers e = ell_range(c->ell, b0);
-  c->lead_valid = false;
   // (XIVO_HIP_NO_COMPRESS: test hook for the branch very wide states take - the shape limit itself is N > ~2800 at M = 384)
   static const bool no_compress = getenv("XIVO_HIP_NO_COMPRESS") != nullptr;
-  if (!meas_compress_fits(c->Mpmax, c->Np) || no_compress) {
+  const bool compressed = meas_compress_fits(c->Mpmax, c->Np) && !no_compress;
+  c->rows.handed_over(b0, nb, M, compressed);
+  if (!compressed) {
     // the compression kernel's LDS lists do not fit this shape: every filter keeps its dense rows and takes the dense pipeline
     StageTimer st(c, ST_STACK, 0.0, "unpack_meas_kernel", 8.0 * nb * (3.0 * M * N + 4.0 * M));
     HIP_TRY((hipError_t)launch_meas_vectors(dInn, strideInn, dR, strideR, M, c->Mpmax, e, mb.inn, mb.strideInn, mb.diagR, mb.strideR, nb, c->stream));
     HIP_TRY((hipError_t)launch_unpack_meas(dH, strideH, ldh, nullptr, mb, M, c->Mpmax, N, c->Np, nb, c->stream));
-    for (int b = b0; b < b0 + nb; ++b) { c->ell_over_h[b] = 1; c->ell_nc_h[b] = ELL_CW; c->ell_pw_h[b] = ELL_PW + 1; }
-    c->dense_valid = true; c->dense_from_ell = true; c->ht_valid = true; c->mixed_row0 = -1; c->h_clean = false;
     return XIVO_HIP_OK;
   }
   {
@@ -610,19 +602,17 @@ int stage_measurements(xivo_hip_ctx* c, int b0, int nb, int M, const double* dH,
   if (c->ell_flags_h) {
     HIP_TRY(hipStreamSynchronize(c->stream));     // kernel end = system-scope release: the mirrored flags are in host memory
     const int* f = c->ell_flags_h + 3 * (long)b0;
-    for (int b = 0; b < nb; ++b) { c->ell_over_h[b0 + b] = f[3 * b]; c->ell_nc_h[b0 + b] = f[3 * b + 1]; c->ell_pw_h[b0 + b] = f[3 * b + 2]; }
+    for (int b = 0; b < nb; ++b) c->rows.fit_reported(b0 + b, f[3 * b], f[3 * b + 1], f[3 * b + 2]);
   } else {
-    HIP_TRY(hipMemcpyAsync(c->ell_over_h.data() + b0, e.over, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->ell_nc_h.data() + b0, e.nc, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->ell_pw_h.data() + b0, e.pw, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    std::vector<int> f(3 * (size_t)nb);   // over | nc | pw
+    const int* src[3] = {e.over, e.nc, e.pw};
+    for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpyAsync(f.data() + (size_t)k * nb, src[k], (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int b = 0; b < nb; ++b) c->rows.fit_reported(b0 + b, f[b], f[nb + b], f[2 * nb + b]);
   }
-  bool any_over = false;
-  for (int b = b0; b < b0 + nb && !any_over; ++b) any_over = c->ell_over_h[b] != 0;
-  if (debug_on()) fprintf(stderr, "xivo_hip: hand-over b0=%d nb=%d M=%d any_over=%d nc0=%d pw0=%d\n", b0, nb, M, (int)any_over, c->ell_nc_h[b0], c->ell_pw_h[b0]);
+  const bool any_over = c->rows.any_over(b0, nb);
+  if (debug_on()) fprintf(stderr, "xivo_hip: hand-over b0=%d nb=%d M=%d any_over=%d nc0=%d pw0=%d\n", b0, nb, M, (int)any_over, c->rows.nc(b0), c->rows.pw(b0));
   if (any_over) HIP_TRY((hipError_t)launch_unpack_meas(dH, strideH, ldh, e.over, mb, M, c->Mpmax, N, c->Np, nb, c->stream));
-  c->dense_valid = false; c->dense_from_ell = true; c->ht_valid = true;   // (ensure_dense rebuilds H and H^T together)
-  c->mixed_row0 = -1; if (any_over) c->h_clean = false;
   return XIVO_HIP_OK;
 }
 
@@ -664,14 +654,14 @@ int xivo_hip_set_measurements_device(xivo_hip_ctx* c, int b0, int nb, int M, con
 
 int xivo_hip_update_joseph(xivo_hip_ctx* c, int B) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (!c || B <= 0 || B > c->Bmax || c->Mp <= 0) return XIVO_HIP_ERR_INVALID;
+  if (!c || B <= 0 || B > c->Bmax || c->rows.rows_padded() <= 0) return XIVO_HIP_ERR_INVALID;
   return update_chunks(c, B, nullptr);
 }
 
 int xivo_hip_update_dense_gated(xivo_hip_ctx* c, int B, int F, double R, double mh_thresh, double mh_mult,
                                 int min_inliers) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (!c || B <= 0 || B > c->Bmax || c->Mp <= 0 || F <= 0 || 2 * F > c->M) return XIVO_HIP_ERR_INVALID;
+  if (!c || B <= 0 || B > c->Bmax || c->rows.rows_padded() <= 0 || F <= 0 || 2 * F > c->rows.rows()) return XIVO_HIP_ERR_INVALID;
   int rc = ensure_gate_buffers(c, F);
   if (rc) return rc;
   GateParams gp{F, R, mh_thresh, mh_mult, min_inliers};
@@ -695,8 +685,9 @@ int xivo_hip_get_gate(xivo_hip_ctx* c, int B, int F, unsigned char* mask_out, do
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || B <= 0 || B > c->Bmax || F <= 0 || !c->mask) return XIVO_HIP_ERR_INVALID;
   // the dense gate packs [B][F]; the layout-faithful gate (xivo_hip_mh_gate / filter_update) strides by Fmax
-  const size_t ld = c->gate_sparse_last ? (size_t)c->Fmax : (size_t)F;
-  if (c->gate_sparse_last && F != c->F) return XIVO_HIP_ERR_INVALID;
+  const bool strided = c->rows.gate_layout() == GateLayout::strided;
+  const size_t ld = strided ? (size_t)c->Fmax : (size_t)F;
+  if (strided && F != c->F) return XIVO_HIP_ERR_INVALID;
   if (mask_out) { int rc = d2h_rows(c, mask_out, F, c->mask, ld, F, B); if (rc) return rc; }
   if (dist_out) {
     int rc = d2h_rows(c, dist_out, F * sizeof(double), c->dist, ld * sizeof(double), F * sizeof(double), B);
@@ -814,9 +805,7 @@ int xivo_hip_update_joseph_host(xivo_hip_ctx* c, int b, int M, const double* H, 
     HIP_TRY((hipError_t)launch_dropin_in(ia, c->stream));
   }
   // what stage_measurements leaves behind for the pipeline
-  c->M = M; c->Mp = round_up16(M);
-  c->ell_over_h[b] = 0; c->ell_nc_h[b] = nc; c->ell_pw_h[b] = pw;
-  c->dense_valid = false; c->dense_from_ell = true; c->ht_valid = true; c->mixed_row0 = -1;
+  c->rows.handed_over(b, 1, M, true); c->rows.fit_reported(b, 0, nc, pw);
   // (from here on kernels that read the context's pinned block may be in flight: an early return drains the stream first,
   //  the next call overwrites that block)
   int rc = update_joseph_range(c, b, 1);
@@ -844,21 +833,17 @@ int xivo_hip_update_joseph_host(xivo_hip_ctx* c, int b, int M, const double* H, 
 int xivo_hip_mh_gate_dense(xivo_hip_ctx* c, int B, int F, double R, double mh_thresh, double mh_mult,
                            int min_inliers, unsigned char* mask_out, double* dist_out) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (!c || B <= 0 || B > c->Bmax || F <= 0 || 2 * F > c->M) return XIVO_HIP_ERR_INVALID;
+  if (!c || B <= 0 || B > c->Bmax || F <= 0 || 2 * F > c->rows.rows()) return XIVO_HIP_ERR_INVALID;
   int rc = ensure_gate_buffers(c, F);
   if (rc) return rc;
   rc = ensure_dense(c);
   if (rc) return rc;
   GateDenseArgs a{};
-  a.mask = c->mask; a.dist = c->dist; a.F = F; a.R = R; a.thresh = mh_thresh; a.mult = mh_mult; a.min_inliers = min_inliers;
-  a.have_ell = 1;
+  a.mask = c->mask; a.dist = c->dist; a.F = F; a.R = R; a.thresh = mh_thresh; a.mult = mh_mult; a.min_inliers = min_inliers; a.have_ell = 1;
   rc = gate_dense_rows(c, B, a);
   if (rc) return rc;
-  c->gate_sparse_last = 0;
-  if (mask_out) HIP_TRY(hipMemcpyAsync(mask_out, c->mask, (size_t)B * F, hipMemcpyDeviceToHost, c->stream));
-  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, c->dist, (size_t)B * F * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (mask_out || dist_out) HIP_TRY(hipStreamSynchronize(c->stream));
-  return XIVO_HIP_OK;
+  c->rows.gate_wrote(GateLayout::packed);
+  return xivo_hip_get_gate(c, B, F, mask_out, dist_out);
 }
 
 }  // extern "C"

@@ -26,7 +26,7 @@ struct MeasBuffers {
 };
 int launch_unpack_meas(const double* rawH, long strideRaw, int ldraw, const int* only_if, MeasBuffers mb,
                        int M, int Mp, int N, int Np, int batch, hipStream_t s);
-// H^T rebuilt from the dense H of every filter (the G-level producers may skip writing it: capi_glevel.hip, ht_valid)
+// H^T rebuilt from the dense H of every filter (the G-level producers may skip writing it: staged_rows.h, ht_alive)
 int launch_transpose_H(const double* H, long strideH, int ldh, double* HT, long strideHT, int ldht, int Mp, int Np, int batch,
                        hipStream_t s);
 

@@ -4,7 +4,7 @@
 //  unpack_P_kernel      host-layout P -> padded device P (lower triangle authoritative, p_unpack_device.h)
 //  pack_P_kernel        padded device P -> host layout
 //  unpack_meas_kernel   raw H -> padded H / H^T
-//  transpose_H_kernel   H^T from the dense H (capi_glevel.hip: ht_valid)
+//  transpose_H_kernel   H^T from the dense H (staged_rows.h: ht_alive)
 //  p_* kernels          host edits of P_; p_copy_rc: Estimator::AddGroupToState   src/estimator.cpp:808-816
 //  set_pixels_kernel    the tracker's pixels into the resident features (xivo_hip_set_pixels)
 //  edit_batch_kernel    Estimator::{Add,Remove}{Group,Feature}{To,From}State on P_ and the scene
@@ -377,7 +377,7 @@ int launch_unpack_meas(const double* rawH, long strideRaw, int ldraw, const int*
   CHECK_LAUNCH();
 }
 // H^T [Np x Mp, ldht] from the dense H [Mp x Np, ldh] of every filter: the transposed copy is optional for the G-level
-// producers (capi_glevel.hip: ht_valid) and rebuilt here when a consumer turns up after all. 32 x 32 tiles through LDS so that
+// producers (staged_rows.h: ht_alive) and rebuilt here when a consumer turns up after all. 32 x 32 tiles through LDS so that
 // both sides move 256-byte runs.
 __global__ __launch_bounds__(256) void transpose_H_kernel(const double* __restrict__ Hall, long strideH, int ldh,
                                                          double* __restrict__ HTall, long strideHT, int ldht, int Mp, int Np) {
