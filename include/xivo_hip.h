@@ -278,6 +278,9 @@ int xivo_hip_selftest_host_compress(const double* H, int ldh, int M, int N, int 
 #define XIVO_HIP_LAUNCH_OOS_COMPRESS 1
 #define XIVO_HIP_LAUNCH_PROP_TAIL 2
 int xivo_hip_selftest_glevel_launch(int kind, int a, int b, int c, char* label, int n);
+/* Test hook: the device blocks the context owns right now - *live their number, *bytes their total size (either may be
+ * null). Memory handed out by xivo_hip_dev_alloc belongs to the caller and is not counted. */
+int xivo_hip_selftest_ctx_allocs(xivo_hip_ctx* ctx, int* live, unsigned long long* bytes);
 /* Estimator::MHGating numeric core on dense rows (src/update.cpp:60-96):
  * rows 2f,2f+1 of the staged H are feature f's J. Writes the inlier mask and
  * Mahalanobis distances; rejected rows are then neutralised in the staged

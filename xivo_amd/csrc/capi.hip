@@ -22,17 +22,26 @@ static int collect_profile(xivo_hip_ctx* c) {
   return XIVO_HIP_OK;
 }
 
-MeasBuffers meas_buffers(xivo_hip_ctx* c) {
+// the owner's allocator: the only hipMalloc / hipFree of a context's own memory
+int device_alloc(void** p, size_t bytes, int zero) {
+  *p = nullptr;
+  if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return XIVO_HIP_ERR_NOMEM; }
+  if (zero && hipMemset(*p, 0, bytes) != hipSuccess) { hipFree(*p); *p = nullptr; return XIVO_HIP_ERR_HIP; }
+  return XIVO_HIP_OK;
+}
+void device_free(void* p) { hipFree(p); }
+
+MeasBuffers meas_buffers(xivo_hip_ctx* c, int b0) {
   MeasBuffers mb;
-  mb.H = c->H; mb.strideH = c->sH; mb.ldh = c->Mpmax;
-  mb.HT = c->HT; mb.strideHT = c->sHT; mb.ldht = c->Np;
-  mb.inn = c->inn; mb.strideInn = c->Mpmax;
-  mb.diagR = c->diagR; mb.strideR = c->Mpmax;
+  c->H.from(b0).to(mb.H, mb.strideH, mb.ldh);
+  c->HT.from(b0).to(mb.HT, mb.strideHT, mb.ldht);
+  c->inn.from(b0).to(mb.inn, mb.strideInn);
+  c->diagR.from(b0).to(mb.diagR, mb.strideR);
   return mb;
 }
 
 bool calib_sparse(const xivo_hip_ctx* c) {   // (XIVO_HIP_FLAG_DENSE_H keeps the round-4 dense stacking of these builds)
-  return c->calib_on && c->Hlead && c->cl.cam_begin + 9 <= LEAD_K && c->Np >= LEAD_K &&
+  return c->calib_on && c->Hlead.p && c->cl.cam_begin + 9 <= LEAD_K && c->Np >= LEAD_K &&
          !(c->flags & (XIVO_HIP_FLAG_DENSE_H | XIVO_HIP_FLAG_SYMMETRIC_FORM | XIVO_HIP_FLAG_STANDALONE_TAIL));
 }
 
@@ -66,12 +75,7 @@ int d2h_rows(xivo_hip_ctx* c, void* dst, size_t hpitch, const void* src, size_t 
 }
 
 int ensure_staging(xivo_hip_ctx* c, size_t elems) {
-  if (elems <= c->staging_elems) return XIVO_HIP_OK;
-  if (c->staging) hipFree(c->staging);
-  c->staging = nullptr; c->staging_elems = 0;
-  if (hipMalloc((void**)&c->staging, elems * sizeof(double)) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
-  c->staging_elems = elems;
-  return XIVO_HIP_OK;
+  return c->mem.grow(&c->staging, &c->staging_elems, elems);
 }
 
 // copy nb host matrices (rows x cols, leading dim ld, `stride` elements apart)
@@ -104,22 +108,21 @@ int d2h_packed(xivo_hip_ctx* c, double* dst, const double* src, int nb, int rows
 
 bool bad_range(xivo_hip_ctx* c, int b0, int nb) { return !c || b0 < 0 || nb < 0 || b0 + nb > c->Bmax; }
 
-int gemm(xivo_hip_ctx* c, int stage, int B, int rows, int cols, const double* A0, long sA0, int lda0,
-         const double* B0, long sB0, int ldb0, int K0, const double* A1, long sA1, int lda1, const double* B1,
-         long sB1, int ldb1, int K1, const double* scale1, long sScale1, double* C, long sC, int ldc,
-         const GemmExtra& x) {
+int gemm(xivo_hip_ctx* c, int stage, int B, int rows, int cols, const GemmProduct& seg, const BatchMat& C, const GemmExtra& x) {
+  const double *A0 = seg.A.p, *B0 = seg.B.p, *A1 = x.seg1.A.p;
+  const int K0 = seg.K, K1 = x.seg1.K;
   GemmArgs g;
   memset(&g, 0, sizeof(g));
-  g.seg[0] = GemmSeg{A0, B0, x.scale0, sA0, sB0, 0, lda0, ldb0, K0, x.a_f32, x.b_f32};
+  g.seg[0] = GemmSeg{A0, B0, x.scale0, seg.A.stride, seg.B.stride, 0, seg.A.ld, seg.B.ld, K0, x.a_f32, x.b_f32};
   g.nseg = 1;
   if (A1) {
-    g.seg[1] = GemmSeg{A1, B1, scale1, sA1, sB1, sScale1, lda1, ldb1, K1, 0, 0};
+    g.seg[1] = GemmSeg{A1, x.seg1.B.p, x.scale1.p, x.seg1.A.stride, x.seg1.B.stride, x.scale1.stride, x.seg1.A.ld, x.seg1.B.ld, K1, 0, 0};
     g.nseg = 2;
   }
-  g.C = C; g.strideC = sC; g.ldc = ldc; g.Mp = rows; g.Np = cols;
-  g.C2 = x.C2; g.strideC2 = x.sC2; g.ldc2 = x.ldc2; g.c2_rows = x.c2_rows;
-  g.diag = x.diag; g.strideDiag = x.sDiag; g.Msub = x.msub; g.strideMsub = x.sMsub; g.ldmsub = x.ldmsub;
-  g.McolScale = x.mcol; g.strideMcol = x.sMcol;
+  C.to(g.C, g.strideC, g.ldc); g.Mp = rows; g.Np = cols;
+  x.C2.to(g.C2, g.strideC2, g.ldc2); g.c2_rows = x.c2_rows;
+  x.diag.to(g.diag, g.strideDiag); x.msub.to(g.Msub, g.strideMsub, g.ldmsub);
+  x.mcol.to(g.McolScale, g.strideMcol);
   g.epilogue = x.epi; g.lower_only = x.lower_only; g.no_mirror = x.no_mirror; g.batch = B; g.fp32 = x.fp32;
   g.skip_status = x.skip; g.small_tiles = x.small_tiles;
   // algorithmic flops of the product: a symmetric output needs its lower triangle only
@@ -130,7 +133,7 @@ int gemm(xivo_hip_ctx* c, int stage, int B, int rows, int cols, const double* A0
   char label[64] = "gemm_sym_f64_kernel";
   if (!sym) gemm_kernel_label(g, label, sizeof(label));
   const double bytes = 8.0 * B * ((double)rows * K0 * (x.a_f32 ? 0.5 : 1.0) + (double)cols * K0 * (x.b_f32 ? 0.5 : 1.0) + (A1 ? ((double)rows + cols) * K1 : 0.0) +
-                                  (x.msub ? outs : 0.0) + (double)rows * cols + (x.C2 ? (double)rows * cols : 0.0))
+                                  (x.msub.p ? outs : 0.0) + (double)rows * cols + (x.C2.p ? (double)rows * cols : 0.0))
                        - (A0 == B0 ? 8.0 * B * (double)cols * K0 : 0.0);   // a symmetric product reads its one operand once
   StageTimer st(c, stage, flops, label, bytes);
   const int rc = sym ? launch_gemm_sym_f64(g, c->stream) : launch_gemm_nt_f64(g, c->stream);
@@ -158,11 +161,7 @@ void xivo_hip_destroy(xivo_hip_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
-  void* ptrs[] = {c->P, c->Psnap, c->H, c->HT, c->HP, c->PHT, c->S, c->K, c->A, c->T, c->invD, c->inn, c->diagR, c->err,
-                  c->staging, c->scratch, c->neg1, c->yvec, c->status, c->poses, c->groups, c->feats, c->J, c->finn, c->dist,
-                  c->mask, c->rows_instate, c->absorb_count, c->Prs, c->poses_rs, c->groups_rs, c->rs_low, c->rs_lowkeep, c->rs_keep,
-                  c->rs_zg, c->rs_gmask, c->rs_state, c->rs_gauge, c->rs_nrej, c->rs_chi, c->oos, c->oos_rows, c->ell.idx, c->ell.val, c->ell.nc, c->ell.pw, c->ell.over, c->sub, c->edit_buf, c->lc_buf, c->calib_rs, c->Hlead, c->ldlt_used, c->calib, c->Jc, c->pd_h, c->fpool, c->anchors, c->pool_io, c->tri_counts, c->init_z};
-  for (void* p : ptrs) if (p) hipFree(p);
+  c->mem.free_all();
   if (c->ell_flags_h) hipHostFree(c->ell_flags_h);
   if (c->pin_h) hipHostFree(c->pin_h);
   for (auto& ep : c->pool) { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
@@ -186,20 +185,21 @@ int xivo_hip_create(xivo_hip_ctx** out, int device, int N, int M_max, int batch_
   if (const char* e = getenv("XIVO_HIP_CHUNK")) c->chunk = atoi(e);
   const size_t B = batch_max;
   const size_t Np = c->Np, Mp = c->Mpmax;
-  c->sP = (long)(Np * Np); c->sH = (long)(Mp * Np); c->sHT = (long)(Np * Mp); c->sS = (long)(Mp * Mp);
-  c->sK = (long)(Np * Mp); c->sInvD = (long)(Mp / 16 * 512); c->sA = c->sP > c->sK ? c->sP : c->sK;
   int rc = XIVO_HIP_OK;
-  auto A = [&](auto** p, size_t n) { if (rc == XIVO_HIP_OK) rc = dev_alloc(p, n); };
+  auto A = [&](auto** p, size_t n) { if (rc == XIVO_HIP_OK) rc = c->mem.zeroed(p, n); };
+  // a view gets its stride and leading dimension here, once, and B * stride elements behind it
+  auto mat = [&](BatchMat& m, size_t rows, size_t cols, size_t stride = 0) {
+    m.stride = (long)(stride ? stride : rows * cols); m.ld = (int)rows; A(&m.p, B * m.stride);
+  };
+  auto vec = [&](BatchVec& v, size_t n) { v.stride = (long)n; A(&v.p, B * n); };
   if (hipStreamCreate(&c->stream) != hipSuccess) { delete c; return XIVO_HIP_ERR_HIP; }
-  A(&c->P, B * c->sP); A(&c->H, B * c->sH); A(&c->HT, B * c->sHT); A(&c->HP, B * c->sH); A(&c->PHT, B * c->sK);
-  A(&c->S, B * c->sS); A(&c->K, B * c->sK); A(&c->A, B * c->sA); A(&c->T, B * c->sP);
-  A(&c->invD, B * c->sInvD); A(&c->inn, B * Mp); A(&c->diagR, B * Mp); A(&c->err, B * Np);
+  mat(c->P, Np, Np); mat(c->H, Mp, Np); mat(c->HT, Np, Mp); mat(c->HP, Mp, Np); mat(c->PHT, Np, Mp);
+  mat(c->S, Mp, Mp); mat(c->K, Np, Mp); mat(c->G, Np, Mp, Np > Mp ? Np * Np : Np * Mp); mat(c->T, Np, Np);
+  c->KHI = BatchMat{c->G.p, c->P.stride, c->P.ld};
+  vec(c->invD, Mp / 16 * 512); vec(c->inn, Mp); vec(c->diagR, Mp); vec(c->err, Np);
   A(&c->status, B); A(&c->ldlt_used, B); A(&c->scratch, B * Np);
-  A(&c->neg1, Mp); A(&c->yvec, B * Mp);
-  if (rc == XIVO_HIP_OK) {
-    std::vector<double> m1(Mp, -1.0);
-    if (hipMemcpy(c->neg1, m1.data(), Mp * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
-  }
+  vec(c->yvec, Mp);
+  c->Hlead.stride = (long)(Mp * LEAD_K); c->Hlead.ld = (int)Mp;   // (allocated by xivo_hip_set_calib)
   c->ell.pairs_max = (int)(Mp / 2);
   A(&c->ell.idx, B * c->ell.stride_idx()); A(&c->ell.val, B * c->ell.stride_val()); A(&c->ell.nc, B); A(&c->ell.pw, B); A(&c->ell.over, B);
   c->rows.sized(batch_max, ELL_CW, ELL_PW);
@@ -264,7 +264,7 @@ int xivo_hip_upload_P(xivo_hip_ctx* c, int b0, int nb, const double* P, long str
   if (rc) return rc;
   rc = h2d_packed(c, c->staging, P, nb, N, N, stride, ld);
   if (rc) return rc;
-  HIP_TRY((hipError_t)launch_unpack_P(c->staging, c->P + (long)b0 * c->sP, N, c->Np, c->Np, c->sP, nb, c->stream));
+  HIP_TRY((hipError_t)launch_unpack_P(c->staging, c->P.from(b0).p, N, c->Np, c->P.ld, c->P.stride, nb, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // host buffer is only borrowed for the call
   return XIVO_HIP_OK;
 }
@@ -276,7 +276,7 @@ int xivo_hip_download_P(xivo_hip_ctx* c, int b0, int nb, double* P, long stride,
   const int N = c->N;
   int rc = ensure_staging(c, (size_t)nb * N * N);
   if (rc) return rc;
-  HIP_TRY((hipError_t)launch_pack_P(c->P + (long)b0 * c->sP, c->staging, N, c->Np, c->sP, nb, c->stream));
+  HIP_TRY((hipError_t)launch_pack_P(c->P.from(b0).p, c->staging, N, c->P.ld, c->P.stride, nb, c->stream));
   rc = d2h_packed(c, P, c->staging, nb, N, N, stride, ld);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -286,37 +286,36 @@ int xivo_hip_download_P(xivo_hip_ctx* c, int b0, int nb, double* P, long stride,
 int xivo_hip_snapshot_P(xivo_hip_ctx* c) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c) return XIVO_HIP_ERR_INVALID;
-  if (!c->Psnap) {
-    if (hipMalloc((void**)&c->Psnap, (size_t)c->Bmax * c->sP * sizeof(double)) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
-  }
-  HIP_TRY(hipMemcpyAsync(c->Psnap, c->P, (size_t)c->Bmax * c->sP * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  const size_t elems = (size_t)c->Bmax * c->P.stride;
+  if (!c->Psnap) { int rc = c->mem.raw(&c->Psnap, elems); if (rc) return rc; }
+  HIP_TRY(hipMemcpyAsync(c->Psnap, c->P.p, elems * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_restore_P(xivo_hip_ctx* c) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || !c->Psnap) return XIVO_HIP_ERR_INVALID;
-  HIP_TRY(hipMemcpyAsync(c->P, c->Psnap, (size_t)c->Bmax * c->sP * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->P.p, c->Psnap, (size_t)c->Bmax * c->P.stride * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_p_zero_rc(xivo_hip_ctx* c, int b, int off, int len) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (bad_range(c, b, 1) || off < 0 || len < 0 || off + len > c->N) return XIVO_HIP_ERR_INVALID;
-  return launch_p_zero_rc(c->P + (long)b * c->sP, c->Np, c->Np, off, len, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
+  return launch_p_zero_rc(c->P.from(b).p, c->P.ld, c->Np, off, len, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
 }
 
 int xivo_hip_p_copy_rc(xivo_hip_ctx* c, int b, int dst, int src, int len) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (bad_range(c, b, 1) || dst < 0 || src < 0 || len < 0 || dst + len > c->N || src + len > c->N) return XIVO_HIP_ERR_INVALID;
-  return launch_p_copy_rc(c->P + (long)b * c->sP, c->Np, c->Np, dst, src, len, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
+  return launch_p_copy_rc(c->P.from(b).p, c->P.ld, c->Np, dst, src, len, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
 }
 
 int xivo_hip_p_set_block3(xivo_hip_ctx* c, int b, int off, const double* P3) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (bad_range(c, b, 1) || !P3 || off < 0 || off + 3 > c->N) return XIVO_HIP_ERR_INVALID;
-  double* dst = c->P + (long)b * c->sP + off + (long)off * c->Np;
-  HIP_TRY(hipMemcpy2DAsync(dst, (size_t)c->Np * sizeof(double), P3, 3 * sizeof(double), 3 * sizeof(double), 3,
+  const BatchMat dst = c->P.from(b).at(off, off);
+  HIP_TRY(hipMemcpy2DAsync(dst.p, (size_t)dst.ld * sizeof(double), P3, 3 * sizeof(double), 3 * sizeof(double), 3,
                            hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return XIVO_HIP_OK;
@@ -325,7 +324,7 @@ int xivo_hip_p_set_block3(xivo_hip_ctx* c, int b, int off, const double* P3) {
 int xivo_hip_p_diag(xivo_hip_ctx* c, int b, double* out) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (bad_range(c, b, 1) || !out) return XIVO_HIP_ERR_INVALID;
-  HIP_TRY((hipError_t)launch_p_diag(c->P + (long)b * c->sP, c->Np, c->N, c->scratch, c->stream));
+  HIP_TRY((hipError_t)launch_p_diag(c->P.from(b).p, c->P.ld, c->N, c->scratch, c->stream));
   HIP_TRY(hipMemcpyAsync(out, c->scratch, (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return XIVO_HIP_OK;
@@ -358,6 +357,14 @@ int xivo_hip_dev_upload(xivo_hip_ctx* c, void* dst, const void* src, size_t byte
     have += n;
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+// test hook: what the context's owner holds right now (device_buffers.h)
+int xivo_hip_selftest_ctx_allocs(xivo_hip_ctx* c, int* live, unsigned long long* bytes) {
+  if (!c) return XIVO_HIP_ERR_INVALID;
+  if (live) *live = c->mem.live();
+  if (bytes) *bytes = c->mem.bytes();
   return XIVO_HIP_OK;
 }
 

@@ -13,7 +13,7 @@ namespace {
 
 int gate_impl(xivo_hip_ctx* c, int B, double R, double th, double mult, int min_inl, int use_gating) {
   GateArgs a{};
-  a.sb = scene_buffers(c); a.lay = c->lay; a.P = c->P; a.strideP = c->sP; a.ldp = c->Np;
+  a.sb = scene_buffers(c); a.lay = c->lay; c->P.to(a.P, a.strideP, a.ldp);
   a.R = R; a.thresh = th; a.mult = mult; a.min_inliers = min_inl; a.batch = B; a.use_gating = use_gating;
   char label[64];
   gate_sparse_threads(B, a.sb.F, a.sb.Jc ? 1 : 0, label, sizeof(label));
@@ -32,7 +32,7 @@ int stack_impl(xivo_hip_ctx* c, int B, double R, int write_dense, unsigned char*
   a.ell = c->ell; a.emit_ell = 1; a.write_dense = write_dense;
   // as-coded stacking of an online-calibration build on the sparse pipeline: compressed rows + the leading dense block
   // (full_rows - the whole-row stackings of the gate / RANSAC - stay dense rows)
-  if (!full_rows && !write_dense && calib_sparse(c)) { a.lead = c->Hlead; a.strideLead = (long)c->Mpmax * LEAD_K; a.lead_k = LEAD_K; }
+  if (!full_rows && !write_dense && calib_sparse(c)) { a.lead = c->Hlead.p; a.strideLead = c->Hlead.stride; a.lead_k = LEAD_K; }
   StageTimer st(c, ST_STACK, 0.0, "stack_kernel");
   return launch_stack(a, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
 }
@@ -62,19 +62,19 @@ int calib_gate(xivo_hip_ctx* c, int B, double R, double mh_thresh, double mh_mul
 namespace xivo_hip::capi {
 
 int ensure_gate_buffers(xivo_hip_ctx* c, int F) {
-  if (F <= c->Fmax && c->mask) return XIVO_HIP_OK;
-  const int Fm = F > c->Mpmax / 2 ? F : c->Mpmax / 2;
-  void* olds[] = {c->feats, c->J, c->finn, c->dist, c->mask, c->Jc};
-  for (void* p : olds) if (p) hipFree(p);
-  c->feats = nullptr; c->J = nullptr; c->finn = nullptr; c->dist = nullptr; c->mask = nullptr; c->Jc = nullptr;
+  // allocated once, for the most features a context can stage: every caller bounds 2 F by Mmax <= Mpmax. (Fmax stays 0 until
+  // the whole group is there, so a call after a failed one starts over; the owner releases what a slot still holds.)
+  const int Fm = c->Mpmax / 2;
+  if (F > Fm) return XIVO_HIP_ERR_INVALID;
+  if (c->Fmax == Fm) return XIVO_HIP_OK;
   const size_t B = c->Bmax;
-  int rc = dev_alloc(&c->feats, B * Fm);
-  if (!rc) rc = dev_alloc(&c->J, B * Fm * 42);
-  if (!rc) rc = dev_alloc(&c->finn, B * Fm * 2);
-  if (!rc) rc = dev_alloc(&c->dist, B * Fm);
-  if (!rc) rc = dev_alloc(&c->mask, B * Fm);
-  if (!rc && c->calib_on) rc = dev_alloc(&c->Jc, B * Fm * 44);
-  if (!rc && !c->rows_instate) rc = dev_alloc(&c->rows_instate, B);
+  int rc = c->mem.zeroed(&c->feats, B * Fm);
+  if (!rc) rc = c->mem.zeroed(&c->J, B * Fm * 42);
+  if (!rc) rc = c->mem.zeroed(&c->finn, B * Fm * 2);
+  if (!rc) rc = c->mem.zeroed(&c->dist, B * Fm);
+  if (!rc) rc = c->mem.zeroed(&c->mask, B * Fm);
+  if (!rc && c->calib_on) rc = c->mem.zeroed(&c->Jc, B * Fm * 44);
+  if (!rc && !c->rows_instate) rc = c->mem.zeroed(&c->rows_instate, B);
   // every entry starts absent (sind = -1) and masked out until a scene / edit writes it
   if (!rc && hipMemsetAsync(c->feats, 0xFF, B * Fm * sizeof(xivo_feat_in), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
   if (!rc && hipMemsetAsync(c->mask, 0, B * Fm, c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
@@ -86,7 +86,7 @@ int ensure_gate_buffers(xivo_hip_ctx* c, int F) {
 int ensure_HT(xivo_hip_ctx* c) {
   if (c->rows.ht_alive()) return XIVO_HIP_OK;
   StageTimer st(c, ST_STACK, 0.0, "transpose_H_kernel");
-  if (launch_transpose_H(c->H, c->sH, c->Mpmax, c->HT, c->sHT, c->Np, c->Mpmax, c->Np, c->Bmax, c->stream)) return XIVO_HIP_ERR_HIP;
+  if (launch_transpose_H(c->H.p, c->H.stride, c->H.ld, c->HT.p, c->HT.stride, c->HT.ld, c->Mpmax, c->Np, c->Bmax, c->stream)) return XIVO_HIP_ERR_HIP;
   c->rows.ht_materialised();
   return XIVO_HIP_OK;
 }
@@ -99,7 +99,7 @@ int ensure_dense(xivo_hip_ctx* c) {
     // the compressed rows are the source. Mixed stacking: the in-state rows only, next to the OOS rows already in place (no H^T);
     // S-level hand-over: H and H^T (filters that do not fit hold dense rows already)
     StageTimer st(c, ST_STACK, 0.0, "ell_to_dense_kernel");
-    if (launch_ell_to_dense(c->ell, c->H, c->sH, c->Mpmax, mr0 >= 0 ? nullptr : c->HT, c->sHT, c->Np, c->Mpmax, c->Np, c->Bmax, c->stream, mr0))
+    if (launch_ell_to_dense(c->ell, c->H.p, c->H.stride, c->H.ld, mr0 >= 0 ? nullptr : c->HT.p, c->HT.stride, c->HT.ld, c->Mpmax, c->Np, c->Bmax, c->stream, mr0))
       return XIVO_HIP_ERR_HIP;
   } else {
     if (int rc = stack_impl(c, c->rows.restack_args().B, c->rows.restack_args().R, 1)) return rc;
@@ -113,13 +113,13 @@ int ensure_dense(xivo_hip_ctx* c) {
 int gate_dense_rows(xivo_hip_ctx* c, int B, GateDenseArgs a) {
   int rc = ensure_HT(c);   // (the gate reads - and neutralises - the transposed rows too)
   if (rc) return rc;
-  const int Np = c->Np, ldh = c->Mpmax;
-  GemmExtra x; x.C2 = c->PHT; x.sC2 = c->sK; x.ldc2 = Np;
-  rc = gemm(c, ST_HP, B, c->rows.rows_padded(), Np, c->H, c->sH, ldh, c->P, c->sP, Np, Np, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, c->HP, c->sH, ldh, x);
+  const int Np = c->Np;
+  GemmExtra x; x.C2 = c->PHT;
+  rc = gemm(c, ST_HP, B, c->rows.rows_padded(), Np, {c->H, c->P, Np}, c->HP, x);
   if (rc) return rc;
-  a.H = c->H; a.strideH = c->sH; a.ldh = ldh; a.HP = c->HP; a.strideHP = c->sH; a.ldhp = ldh;
-  a.Hw = c->H; a.HTw = c->HT; a.strideHT = c->sHT; a.ldht = Np; a.HPw = nullptr; a.PHTw = nullptr; a.PHTr = c->PHT;
-  a.inn = c->inn; a.strideInn = c->Mpmax; a.diagR = c->diagR; a.strideR = c->Mpmax; a.Np = Np; a.batch = B; a.ell = c->ell;
+  c->H.to(a.H, a.strideH, a.ldh); c->HP.to(a.HP, a.strideHP, a.ldhp);
+  a.Hw = c->H.p; c->HT.to(a.HTw, a.strideHT, a.ldht); a.HPw = nullptr; a.PHTw = nullptr; a.PHTr = c->PHT.p;
+  c->inn.to(a.inn, a.strideInn); c->diagR.to(a.diagR, a.strideR); a.Np = Np; a.batch = B; a.ell = c->ell;
   StageTimer st(c, ST_GATE, 0.0, "gate_dense_kernel");
   HIP_TRY((hipError_t)launch_gate_dense(a, c->stream));
   return XIVO_HIP_OK;
@@ -139,9 +139,9 @@ int xivo_hip_set_layout(xivo_hip_ctx* c, const xivo_layout* lay, const xivo_cam*
   if (cam->model < XIVO_CAM_PINHOLE || cam->model > XIVO_CAM_EQUI) return XIVO_HIP_ERR_INVALID;
   c->lay = *lay; c->cam = *cam; c->have_layout = true;
   if (!c->poses) {
-    int rc = dev_alloc(&c->poses, (size_t)c->Bmax);
-    if (!rc) rc = dev_alloc(&c->absorb_count, (size_t)c->Bmax);
-    if (!rc) rc = dev_alloc(&c->groups, (size_t)c->Bmax * lay->n_groups);
+    int rc = c->mem.zeroed(&c->poses, (size_t)c->Bmax);
+    if (!rc) rc = c->mem.zeroed(&c->absorb_count, (size_t)c->Bmax);
+    if (!rc) rc = c->mem.zeroed(&c->groups, (size_t)c->Bmax * lay->n_groups);
     if (rc) return rc;
   }
   return XIVO_HIP_OK;
@@ -206,9 +206,9 @@ int xivo_hip_set_calib(xivo_hip_ctx* c, const xivo_calib_layout* layout) {
     return XIVO_HIP_ERR_INVALID;
   // slots as src/core.h:40-75 numbers them: td right behind Wsg, Cg behind td (or Wsg), the intrinsics behind the motion block
   if ((l.td >= 0 && l.td != 23) || (l.Cg >= 0 && l.Cg != (l.td >= 0 ? 24 : 23))) return XIVO_HIP_ERR_INVALID;
-  if (!c->calib) { int rc = dev_alloc(&c->calib, (size_t)c->Bmax); if (rc) return rc; }
-  if (!c->Jc && c->Fmax > 0) { int rc = dev_alloc(&c->Jc, (size_t)c->Bmax * c->Fmax * 44); if (rc) return rc; }
-  if (!c->Hlead) { int rc = dev_alloc(&c->Hlead, (size_t)c->Bmax * c->Mpmax * LEAD_K); if (rc) return rc; }
+  if (!c->calib) { int rc = c->mem.zeroed(&c->calib, (size_t)c->Bmax); if (rc) return rc; }
+  if (!c->Jc && c->Fmax > 0) { int rc = c->mem.zeroed(&c->Jc, (size_t)c->Bmax * c->Fmax * 44); if (rc) return rc; }
+  if (!c->Hlead.p) { int rc = c->mem.zeroed(&c->Hlead.p, (size_t)c->Bmax * c->Hlead.stride); if (rc) return rc; }
   c->rows.lead_dropped();
   c->cl = l;
   c->calib_on = l.td >= 0 || l.cam_dim > 0;       // measurement side: blocks beyond the default build's (the Cg / bg blocks sit inside the td block)
@@ -319,22 +319,18 @@ int xivo_hip_oos_project_ex(xivo_hip_ctx* c, int b0, int nb, int n_oos, const xi
     // those are cleared (whole rows once, if anything else has used the dense buffer since it was allocated)
     const int nz = std::min(round_up16(max_rows + 16), c->Mpmax - M);
     if (!c->rows.dense_clean()) {
-      HIP_TRY((hipError_t)launch_zero_rows(c->H, c->sH, c->Mpmax, 0, c->Mpmax, 0, c->Np, c->Bmax, c->stream));
+      HIP_TRY((hipError_t)launch_zero_rows(c->H.p, c->H.stride, c->H.ld, 0, c->Mpmax, 0, c->Np, c->Bmax, c->stream));
       c->rows.dense_zeroed();
     } else {
-      HIP_TRY((hipError_t)launch_zero_rows(c->H, c->sH, c->Mpmax, M, nz, 15, 21, nb, c->stream));
-      HIP_TRY((hipError_t)launch_zero_rows(c->H, c->sH, c->Mpmax, M, nz, c->lay.group_begin, c->lay.group_begin + 6 * c->lay.n_groups, nb, c->stream));
+      HIP_TRY((hipError_t)launch_zero_rows(c->H.p, c->H.stride, c->H.ld, M, nz, 15, 21, nb, c->stream));
+      HIP_TRY((hipError_t)launch_zero_rows(c->H.p, c->H.stride, c->H.ld, M, nz, c->lay.group_begin, c->lay.group_begin + 6 * c->lay.n_groups, nb, c->stream));
     }
   }
-  if (n_oos * nb > c->oos_cap) {
-    if (c->oos) hipFree(c->oos);
-    c->oos = nullptr; c->oos_cap = 0;
-    if (!feats) return XIVO_HIP_ERR_INVALID;
-    int rc = dev_alloc(&c->oos, (size_t)n_oos * c->Bmax);
+  if ((size_t)n_oos * nb > c->oos_cap) {   // (a resident list - feats == NULL - fits by the check above)
+    int rc = c->mem.grow(&c->oos, &c->oos_cap, (size_t)n_oos * c->Bmax);
     if (rc) return rc;
-    c->oos_cap = n_oos * c->Bmax;
   }
-  if (!c->oos_rows) { int rc = dev_alloc(&c->oos_rows, (size_t)c->Bmax); if (rc) return rc; }
+  if (!c->oos_rows) { int rc = c->mem.zeroed(&c->oos_rows, (size_t)c->Bmax); if (rc) return rc; }
   if (feats) {
     HIP_TRY(hipMemcpyAsync(c->oos, feats, (size_t)nb * n_oos * sizeof(xivo_oos_in), hipMemcpyHostToDevice, c->stream));
     c->oos_nb = nb; c->oos_n = n_oos; c->oos_whole = whole;
@@ -375,14 +371,11 @@ int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_th
   // src/estimator.cpp:1421-1427), the partial update stacks the whole rows J() as dense rows, AbsorbError retracts td / Cg / Ca /
   // the intrinsics too, and the rescue test uses the whole-row distances of the dense-row gate
   const bool cal = c->calib_on;
-  if (cal && !c->calib_rs) { int rc = dev_alloc(&c->calib_rs, Bm); if (rc) return rc; }
-  if (!c->Prs || c->rs_Fmax != c->Fmax) {
-    void* olds[] = {c->rs_low, c->rs_lowkeep, c->rs_keep, c->rs_chi};
-    for (void* p : olds) if (p) hipFree(p);
-    c->rs_low = c->rs_lowkeep = c->rs_keep = nullptr; c->rs_chi = nullptr;
+  if (cal && !c->calib_rs) { int rc = c->mem.zeroed(&c->calib_rs, Bm); if (rc) return rc; }
+  if (c->rs_Fmax != c->Fmax) {   // first use (Fmax never changes once it is set: ensure_gate_buffers)
     int rc = XIVO_HIP_OK;
-    auto A = [&](auto** p, size_t n) { if (rc == XIVO_HIP_OK && !*p) rc = dev_alloc(p, n); };
-    A(&c->Prs, Bm * c->sP); A(&c->poses_rs, Bm); A(&c->groups_rs, Bm * ng);
+    auto A = [&](auto** p, size_t n) { if (rc == XIVO_HIP_OK) rc = c->mem.zeroed(p, n); };
+    A(&c->Prs, Bm * c->P.stride); A(&c->poses_rs, Bm); A(&c->groups_rs, Bm * ng);
     A(&c->rs_low, Bm * c->Fmax); A(&c->rs_lowkeep, Bm * c->Fmax); A(&c->rs_keep, Bm * c->Fmax); A(&c->rs_chi, Bm * c->Fmax);
     A(&c->rs_zg, Bm); A(&c->rs_gmask, Bm); A(&c->rs_state, Bm); A(&c->rs_gauge, Bm); A(&c->rs_nrej, Bm);
     if (rc) return rc;
@@ -392,7 +385,7 @@ int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_th
   else HIP_TRY(hipMemsetAsync(c->rs_gauge, 0xFF, (size_t)B * sizeof(int), c->stream));
   if (absorb_groups) HIP_TRY(hipMemcpyAsync(c->rs_gmask, absorb_groups, (size_t)B * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
   RansacArgs a{};
-  a.sb = scene_buffers(c); a.lay = c->lay; a.P = c->P; a.strideP = c->sP; a.ldp = c->Np; a.Np = c->Np;
+  a.sb = scene_buffers(c); a.lay = c->lay; c->P.to(a.P, a.strideP, a.ldp); a.Np = c->Np;
   a.R = R; a.thresh = ransac_thresh; a.chi2 = ransac_chi2; a.gauge = c->rs_gauge;
   a.low = c->rs_low; a.low_keep = c->rs_lowkeep; a.zero_groups = c->rs_zg; a.state = c->rs_state;
   a.keep = c->rs_keep; a.chi = c->rs_chi; a.n_rejected = c->rs_nrej; a.batch = B;
@@ -403,13 +396,13 @@ int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_th
   // the low-innovation set as select found it (filters with nothing to update get an all-neutral stacking mask)
   HIP_TRY(hipMemcpyAsync(c->rs_lowkeep, c->rs_low, (size_t)B * c->Fmax, hipMemcpyDeviceToDevice, c->stream));
   // BackupState (src/estimator.cpp:1410-1428)
-  HIP_TRY(hipMemcpyAsync(c->Prs, c->P, (size_t)B * c->sP * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->Prs, c->P.p, (size_t)B * c->P.stride * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->poses_rs, c->poses, (size_t)B * sizeof(xivo_pose_in), hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->groups_rs, c->groups, (size_t)B * ng * sizeof(xivo_group_in), hipMemcpyDeviceToDevice, c->stream));
   if (cal) HIP_TRY(hipMemcpyAsync(c->calib_rs, c->calib, (size_t)B * sizeof(xivo_calib_in), hipMemcpyDeviceToDevice, c->stream));
   {
     StageTimer st(c, ST_OTHER, 0.0, "ransac_zero_kernel");
-    HIP_TRY((hipError_t)launch_ransac_zero(a, c->P, c->stream));
+    HIP_TRY((hipError_t)launch_ransac_zero(a, c->P.p, c->stream));
   }
   // partial update: H_ rows = the full J() of the low-innovation inliers (:326 - no FillJacobianBlock), R_ on the diagonal
   const int dense = ((c->flags & XIVO_HIP_FLAG_DENSE_H) || cal) ? 1 : 0;
@@ -422,7 +415,7 @@ int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_th
   {  // AbsorbError (:333): in_current_ekf_update_ is empty at this point of Estimator::UpdateStep (cleared at
      // src/manager.cpp:28, filled after OutlierRejection), so no feature state moves; State::counter is restored with X_
     AbsorbArgs ab{};
-    ab.poses = c->poses; ab.groups = c->groups; ab.feats = c->feats; ab.mask = nullptr; ab.err = c->err; ab.strideErr = c->Np;
+    ab.poses = c->poses; ab.groups = c->groups; ab.feats = c->feats; ab.mask = nullptr; c->err.to(ab.err, ab.strideErr);
     ab.lay = c->lay; ab.F = c->F; ab.Fmax = c->Fmax; ab.batch = B; ab.counter = nullptr; ab.status = c->status;
     ab.group_mask = absorb_groups ? c->rs_gmask : nullptr;
     ab.calib = (c->calib_on || c->calib_motion) ? c->calib : nullptr; ab.cl = c->cl;
@@ -452,7 +445,7 @@ int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_th
     HIP_TRY((hipError_t)launch_ransac_rescue_dist(a, c->rs_chi, c->Fmax, c->stream));
   }
   // RestoreState + Jacobians at the original state (:383-387)
-  HIP_TRY(hipMemcpyAsync(c->P, c->Prs, (size_t)B * c->sP * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->P.p, c->Prs, (size_t)B * c->P.stride * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->poses, c->poses_rs, (size_t)B * sizeof(xivo_pose_in), hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->groups, c->groups_rs, (size_t)B * ng * sizeof(xivo_group_in), hipMemcpyDeviceToDevice, c->stream));
   if (cal) HIP_TRY(hipMemcpyAsync(c->calib, c->calib_rs, (size_t)B * sizeof(xivo_calib_in), hipMemcpyDeviceToDevice, c->stream));
@@ -486,13 +479,8 @@ int xivo_hip_close_loop_stack(xivo_hip_ctx* c, int b0, int nb, int n, const xivo
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t o_m = 0, o_H = al((size_t)nb * n * sizeof(xivo_lc_match)), o_inn = al(o_H + (size_t)nb * M * N * sizeof(double)),
                o_R = al(o_inn + (size_t)nb * M * sizeof(double)), total = al(o_R + (size_t)nb * M * sizeof(double));
-  if (total > c->lc_cap) {
-    if (c->lc_buf) hipFree(c->lc_buf);
-    c->lc_buf = nullptr; c->lc_cap = 0;
-    if (hipMalloc(&c->lc_buf, total) != hipSuccess) { (void)hipGetLastError(); return XIVO_HIP_ERR_NOMEM; }
-    c->lc_cap = total;
-  }
-  char* base = static_cast<char*>(c->lc_buf);
+  if (int rc = c->mem.grow(&c->lc_buf, &c->lc_cap, total)) return rc;
+  char* base = c->lc_buf;
   HIP_TRY(hipMemcpyAsync(base + o_m, matches, (size_t)nb * n * sizeof(xivo_lc_match), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(base + o_H, 0, (size_t)nb * M * N * sizeof(double), c->stream));     // H_.setZero(2n, N) (update.cpp:184)
   LcArgs a{};
@@ -606,12 +594,7 @@ int xivo_hip_subfilter_update(xivo_hip_ctx* c, int b0, int nb, int n, xivo_subfi
   for (size_t i = 0; i < (size_t)nb * n; ++i)
     if (feats[i].ref_sind < 0 || feats[i].ref_sind >= c->lay.n_groups) return XIVO_HIP_ERR_INVALID;
   const size_t bytes = (size_t)nb * n * sizeof(xivo_subfilter_feat);
-  if (bytes > c->sub_cap) {
-    if (c->sub) hipFree(c->sub);
-    c->sub = nullptr; c->sub_cap = 0;
-    if (hipMalloc((void**)&c->sub, bytes) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
-    c->sub_cap = bytes;
-  }
+  if (int rc = c->mem.grow(&c->sub, &c->sub_cap, (size_t)nb * n)) return rc;
   HIP_TRY(hipMemcpyAsync(c->sub, feats, bytes, hipMemcpyHostToDevice, c->stream));
   {
     StageTimer st(c, ST_OTHER, 0.0, "subfilter_kernel");
@@ -655,14 +638,7 @@ int xivo_hip_candidate_order(const xivo_subfilter_feat* feats, int nb, int n, in
 }
 
 // ---- out-of-state feature pool
-static int ensure_pool_io(xivo_hip_ctx* c, size_t bytes) {
-  if (bytes <= c->pool_io_cap) return XIVO_HIP_OK;
-  if (c->pool_io) hipFree(c->pool_io);
-  c->pool_io = nullptr; c->pool_io_cap = 0;
-  if (hipMalloc(&c->pool_io, bytes) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
-  c->pool_io_cap = bytes;
-  return XIVO_HIP_OK;
-}
+static int ensure_pool_io(xivo_hip_ctx* c, size_t bytes) { return c->mem.grow(&c->pool_io, &c->pool_io_cap, bytes); }
 
 int xivo_hip_pool_config(xivo_hip_ctx* c, int pool_max, int anchor_max, const xivo_subfilter_opts* opts,
                          double remove_outlier_counter) {
@@ -670,17 +646,15 @@ int xivo_hip_pool_config(xivo_hip_ctx* c, int pool_max, int anchor_max, const xi
   if (!c || pool_max < 1 || anchor_max < 1 || !opts) return XIVO_HIP_ERR_INVALID;
   if (pool_max > XIVO_POOL_MAX_ENTRIES) return XIVO_HIP_ERR_UNSUPPORTED;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->fpool) hipFree(c->fpool);
-  if (c->anchors) hipFree(c->anchors);
-  if (c->tri_counts) hipFree(c->tri_counts);
-  if (c->init_z) hipFree(c->init_z);
-  c->fpool = nullptr; c->anchors = nullptr; c->tri_counts = nullptr; c->init_z = nullptr; c->pool_max = c->anchor_max = 0;
+  c->mem.release(&c->fpool, &c->anchors, &c->tri_counts, &c->init_z);
+  c->pool_max = c->anchor_max = 0;
   c->pool_tri = xivo_triangulate_opts{}; c->adapt = xivo_adapt_depth_opts{}; c->adapt_on = false;
   const size_t ne = (size_t)c->Bmax * pool_max, na = (size_t)c->Bmax * anchor_max;
-  if (hipMalloc((void**)&c->fpool, ne * sizeof(xivo_subfilter_feat)) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
-  if (hipMalloc((void**)&c->anchors, na * sizeof(PoolAnchor)) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
-  if (hipMalloc((void**)&c->tri_counts, 2 * (size_t)c->Bmax * sizeof(int)) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
-  if (hipMalloc((void**)&c->init_z, (size_t)c->Bmax * sizeof(double)) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
+  int rc = c->mem.raw(&c->fpool, ne);
+  if (!rc) rc = c->mem.raw(&c->anchors, na);
+  if (!rc) rc = c->mem.raw(&c->tri_counts, 2 * (size_t)c->Bmax);
+  if (!rc) rc = c->mem.raw(&c->init_z, (size_t)c->Bmax);
+  if (rc) return rc;
   HIP_TRY(hipMemsetAsync(c->tri_counts, 0, 2 * (size_t)c->Bmax * sizeof(int), c->stream));
   HIP_TRY(hipMemsetAsync(c->init_z, 0, (size_t)c->Bmax * sizeof(double), c->stream));
   // all bytes 0xff: every entry's anchor (ref_sind) and every anchor's slot read -1 - free / unlinked
@@ -758,7 +732,7 @@ int xivo_hip_pool_step(xivo_hip_ctx* c, int B, const double* xp, int strict, int
   const size_t b_xp = ne * 2 * sizeof(double), b_ord = ne * sizeof(int), b_n = (size_t)B * sizeof(int);
   int rc = ensure_pool_io(c, b_xp + b_ord + b_n + ne);
   if (rc) return rc;
-  char* io = (char*)c->pool_io;
+  char* io = c->pool_io;
   PoolStepArgs a{};
   a.pool = c->fpool; a.anchors = c->anchors; a.pool_max = c->pool_max; a.anchor_max = c->anchor_max;
   a.poses = c->poses; a.groups = c->groups; a.n_groups = c->lay.n_groups;
@@ -816,7 +790,7 @@ int xivo_hip_triangulate(xivo_hip_ctx* c, int n, const xivo_tri_in* in, xivo_tri
   const size_t bi = (size_t)n * sizeof(xivo_tri_in), bo = (size_t)n * sizeof(xivo_tri_out);
   int rc = ensure_pool_io(c, bi + bo);
   if (rc) return rc;
-  char* io = (char*)c->pool_io;
+  char* io = c->pool_io;
   HIP_TRY(hipMemcpyAsync(io, in, bi, hipMemcpyHostToDevice, c->stream));
   {
     StageTimer st(c, ST_OTHER, 0.0, "triangulate_kernel");
@@ -882,7 +856,7 @@ int xivo_hip_absorb_error(xivo_hip_ctx* c, int B) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0 || !c->mask) return XIVO_HIP_ERR_INVALID;
   AbsorbArgs a{};
-  a.poses = c->poses; a.groups = c->groups; a.feats = c->feats; a.mask = c->mask; a.err = c->err; a.strideErr = c->Np;
+  a.poses = c->poses; a.groups = c->groups; a.feats = c->feats; a.mask = c->mask; c->err.to(a.err, a.strideErr);
   a.lay = c->lay; a.F = c->F; a.Fmax = c->Fmax; a.batch = B; a.counter = c->absorb_count; a.status = c->status;
   a.calib = (c->calib_on || c->calib_motion) ? c->calib : nullptr; a.cl = c->cl;
   StageTimer st(c, ST_OTHER, 0.0, "absorb_error_kernel");
@@ -949,21 +923,18 @@ int xivo_hip_edit_batch(xivo_hip_ctx* c, int F, int n_ops, const xivo_edit_op* o
   const int n_wg = (int)wg_filter.size();
   const size_t bytes_ops = (size_t)n_ops * sizeof(xivo_edit_op);
   const size_t bytes = bytes_ops + (size_t)(2 * n_wg + 1) * sizeof(int);
-  if (bytes > c->edit_cap) {
-    if (c->edit_buf) hipFree(c->edit_buf);
-    c->edit_buf = nullptr; c->edit_cap = 0;
-    const size_t cap = bytes * 2;
-    if (hipMalloc(&c->edit_buf, cap) != hipSuccess) return XIVO_HIP_ERR_NOMEM;
-    c->edit_cap = cap;
+  if (bytes > c->edit_cap) {   // (twice the request: the op lists of consecutive frames differ by a few entries)
+    rc = c->mem.grow(&c->edit_buf, &c->edit_cap, bytes * 2);
+    if (rc) return rc;
   }
-  char* d = (char*)c->edit_buf;
+  char* d = c->edit_buf;
   HIP_TRY(hipMemcpyAsync(d, ops, bytes_ops, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d + bytes_ops, wg_filter.data(), (size_t)n_wg * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d + bytes_ops + (size_t)n_wg * sizeof(int), wg_begin.data(), (size_t)(n_wg + 1) * sizeof(int),
                          hipMemcpyHostToDevice, c->stream));
   EditArgs a{};
   a.ops = (const xivo_edit_op*)d; a.wg_filter = (const int*)(d + bytes_ops); a.wg_begin = a.wg_filter + n_wg;
-  a.P = c->P; a.strideP = c->sP; a.ldp = c->Np; a.Np = c->Np; a.lay = L;
+  c->P.to(a.P, a.strideP, a.ldp); a.Np = c->Np; a.lay = L;
   a.poses = c->poses; a.groups = c->groups; a.feats = c->feats; a.Fmax = c->Fmax;
   a.pool = c->fpool; a.anchors = c->anchors; a.pool_max = c->pool_max; a.anchor_max = c->anchor_max;
   {
@@ -1013,11 +984,11 @@ int xivo_hip_get_H(xivo_hip_ctx* c, int b, int* M_out, double* H, int ldh, doubl
   if (H) {
     if (ldh < M) return XIVO_HIP_ERR_INVALID;
     { int rcd = ensure_dense(c); if (rcd) return rcd; }
-    HIP_TRY(hipMemcpy2DAsync(H, (size_t)ldh * sizeof(double), c->H + (long)b * c->sH, (size_t)c->Mpmax * sizeof(double),
+    HIP_TRY(hipMemcpy2DAsync(H, (size_t)ldh * sizeof(double), c->H.from(b).p, (size_t)c->H.ld * sizeof(double),
                              (size_t)M * sizeof(double), c->N, hipMemcpyDeviceToHost, c->stream));
   }
-  if (inn) HIP_TRY(hipMemcpyAsync(inn, c->inn + (long)b * c->Mpmax, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (diagR) HIP_TRY(hipMemcpyAsync(diagR, c->diagR + (long)b * c->Mpmax, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (inn) HIP_TRY(hipMemcpyAsync(inn, c->inn.from(b).p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (diagR) HIP_TRY(hipMemcpyAsync(diagR, c->diagR.from(b).p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return XIVO_HIP_OK;
 }

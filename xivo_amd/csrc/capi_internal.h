@@ -5,6 +5,16 @@
 //   capi_propagate.hip  propagation
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
+//
+// Two things every one of those files goes through:
+//   c->mem (device_buffers.h)  owns every device block of the context. Allocation is c->mem.zeroed / raw / grow, re-sizing a
+//                              group of buffers is c->mem.release + allocation, xivo_hip_destroy is c->mem.free_all(). The only
+//                              hipMalloc / hipFree of the C ABI are the owner's two function pointers (capi.hip) and the
+//                              caller-owned blocks of xivo_hip_dev_alloc / xivo_hip_dev_free.
+//   BatchMat / BatchVec        a per-filter matrix (vector) of the context: pointer, per-filter stride and leading dimension as
+//                              ONE value. The context holds its buffers as such views, from(b0) is the view of the filters from
+//                              b0 on, to(...) writes the three into a kernel argument struct - a pointer cannot be passed with
+//                              another buffer's stride. A descriptor only: owns nothing, allocates nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -18,6 +28,7 @@
 #include "ell.h"
 #include "fused_update.h"
 #include "staged_rows.h"
+#include "device_buffers.h"
 
 namespace xivo_hip::capi {
 
@@ -30,6 +41,27 @@ inline const char* const kStageNames[ST_COUNT] = {"jac_instate", "mh_gate", "sta
 
 struct EventPair { hipEvent_t a, b; int stage; };
 
+// the owner's allocator (capi.hip): hipMalloc (+ hipMemset), hipFree
+__attribute__((visibility("hidden"))) int device_alloc(void** p, size_t bytes, int zero);
+__attribute__((visibility("hidden"))) void device_free(void* p);
+
+// leading state columns the calibration blocks live in: td 23, Cg 24..32, (Ca 33..38,) bg 9..11, intrinsics up to 39..47
+constexpr int LEAD_K = 48;
+
+// A per-filter vector: filter b starts at p + b * stride.
+struct BatchVec {
+  double* p = nullptr; long stride = 0;
+  BatchVec from(int b0) const { return {p ? p + (long)b0 * stride : nullptr, stride}; }
+  template <class P, class S> void to(P& ptr, S& str) const { ptr = p; str = stride; }
+};
+// A per-filter column-major matrix: element (i, j) of filter b at p[b * stride + i + j * ld].
+struct BatchMat {
+  double* p = nullptr; long stride = 0; int ld = 0;
+  BatchMat from(int b0) const { return {p ? p + (long)b0 * stride : nullptr, stride, ld}; }
+  BatchMat at(int i, int j) const { return {p + i + (long)j * ld, stride, ld}; }   // the block that starts at (i, j)
+  template <class P, class S, class L> void to(P& ptr, S& str, L& l) const { ptr = p; str = stride; l = ld; }
+};
+
 }  // namespace xivo_hip::capi
 
 struct xivo_hip_ctx {
@@ -37,11 +69,14 @@ struct xivo_hip_ctx {
   int N = 0, Np = 0, Mmax = 0, Mpmax = 0, Bmax = 0;
   unsigned flags = 0;
   hipStream_t stream = nullptr;
-  // per-filter device buffers
-  double *P = nullptr, *Psnap = nullptr, *H = nullptr, *HT = nullptr, *HP = nullptr, *PHT = nullptr, *S = nullptr;
-  double *K = nullptr, *A = nullptr, *T = nullptr, *invD = nullptr, *inn = nullptr, *diagR = nullptr;
-  double *err = nullptr, *staging = nullptr, *scratch = nullptr;
-  double *neg1 = nullptr, *yvec = nullptr;   // symmetric form: a vector of -1 (operand scale), y = L^-1 inn per filter
+  xivo_hip::capi::DeviceBuffers mem{xivo_hip::capi::device_alloc, xivo_hip::capi::device_free};   // every device block below
+  // per-filter device buffers, each with the stride and leading dimension it is allocated with (xivo_hip_create). The A buffer
+  // [max(N x N, N x M)] is read with two strides: G (G of the whitened / tail forms, the fallback's A) and KHI (A = K H - I of
+  // the as-coded dense pipeline, laid out like P)
+  xivo_hip::capi::BatchMat P, H, HT, HP, PHT, S, K, G, KHI, T;
+  xivo_hip::capi::BatchVec invD, inn, diagR, err;
+  xivo_hip::capi::BatchVec yvec;   // symmetric form: y = L^-1 inn per filter
+  double *Psnap = nullptr, *staging = nullptr, *scratch = nullptr;
   int* status = nullptr;
   // row-pair compressed H (ell.h); which representations of the staged rows are valid right now: staged_rows.h
   xivo_hip::EllBuffers ell{};
@@ -51,7 +86,6 @@ struct xivo_hip_ctx {
   int last_path = 0;
   int last_route = 0;   // UpdateRoute of the last pass (xivo_hip_last_route)
   size_t staging_elems = 0;
-  long sP = 0, sH = 0, sHT = 0, sS = 0, sK = 0, sInvD = 0, sA = 0;   // sA: A buffer, max(N x N, N x M)
   int chunk = 0;      // filters per pipeline pass (0 = whole batch)
   int call_batch = 0; // filters of the whole update call being walked in chunks (0: not chunked)
   int* ldlt_used = nullptr;     // per filter: 1 = the last update went through the pivoted L D L^T fallback
@@ -81,15 +115,15 @@ struct xivo_hip_ctx {
   unsigned char* mask = nullptr;
   int* rows_instate = nullptr;
   xivo_oos_in* oos = nullptr;
-  int oos_cap = 0;
+  size_t oos_cap = 0;
   double* pd_h = nullptr; double pd_h0 = 0.0;   // step-size-controlled Dormand-Prince: the step each filter carries (xivo_hip_propagate)
   int oos_nb = 0, oos_n = 0, oos_whole = 0;   // shape of the resident OOS list (xivo_hip_oos_project with feats == NULL; its row bound: rows)
   int* oos_rows = nullptr;
   xivo_calib_in* calib_rs = nullptr;            // BackupState of the calibration state (OnePointRANSAC, online-calibration builds)
   // online-calibration builds on the sparse pipeline (round 5): the calibration columns of the stacked rows as a dense
   // [Mpmax x LEAD_K] block per filter next to the row-pair compressed rows (rows.has_lead(): the current stacking has one)
-  double* Hlead = nullptr;
-  void* lc_buf = nullptr; size_t lc_cap = 0;   // xivo_hip_close_loop_stack: matches | dense rows | inn | diagR
+  xivo_hip::capi::BatchMat Hlead;
+  char* lc_buf = nullptr; size_t lc_cap = 0;   // xivo_hip_close_loop_stack: matches | dense rows | inn | diagR
   xivo_subfilter_feat* sub = nullptr;   // staging of xivo_hip_subfilter_update
   // out-of-state feature pool (xivo_hip_pool_*): entries [Bmax][pool_max] (ref_sind = the entry's anchor, -1: free), anchors
   // [Bmax][anchor_max]; host mirrors of who is live / linked, which validate pool_add and the pool's edit kinds
@@ -98,7 +132,7 @@ struct xivo_hip_ctx {
   double pool_remove_outlier = 0.0;
   xivo_subfilter_feat* fpool = nullptr;
   xivo_hip::PoolAnchor* anchors = nullptr;
-  void* pool_io = nullptr; size_t pool_io_cap = 0;   // per-call device staging: records / pixels in, order / counts / live out
+  char* pool_io = nullptr; size_t pool_io_cap = 0;   // per-call device staging: records / pixels in, order / counts / live out
   std::vector<int> pool_anchor_h;   // [Bmax][pool_max]: anchor of a live entry, -1 = free
   std::vector<int> anchor_link_h;   // [Bmax][anchor_max]: linked group slot, -1 = unlinked
   // depth initialisation of new tracks (xivo_hip_pool_triangulation / xivo_hip_pool_adapt_depth*): triangulation options
@@ -109,12 +143,12 @@ struct xivo_hip_ctx {
   xivo_adapt_depth_opts adapt{};
   bool adapt_on = false;
   std::vector<char> hstage;                        // host staging of d2h_rows
-  void* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
+  char* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
   // one-filter plumbing call (xivo_hip_update_joseph_host): page-locked, device-mapped staging block owned by the context,
   // scratch of the host-side row compression
-  char* pin_h = nullptr; char* pin_d = nullptr; size_t pin_bytes = 0;
+  char* pin_h = nullptr; char* pin_d = nullptr;
   struct HostCompressScratch { std::vector<int> cnt, occ, cslot, n; std::vector<double> v; } hc;
-  size_t sub_cap = 0;
+  size_t sub_cap = 0;   // entries
   // timing
   hipEvent_t t0 = nullptr, t1 = nullptr;
   std::vector<xivo_hip::capi::EventPair> pool;
@@ -140,15 +174,6 @@ inline bool debug_on() { static const bool on = getenv("XIVO_HIP_DEBUG") != null
     }                                              \
   } while (0)
 
-template <class T>
-int dev_alloc(T** p, size_t n) {
-  if (n == 0) { *p = nullptr; return XIVO_HIP_OK; }
-  hipError_t e = hipMalloc((void**)p, n * sizeof(T));
-  if (e != hipSuccess) return XIVO_HIP_ERR_NOMEM;
-  e = hipMemset(*p, 0, n * sizeof(T));
-  return e == hipSuccess ? XIVO_HIP_OK : XIVO_HIP_ERR_HIP;
-}
-
 struct StageTimer {
   xivo_hip_ctx* c; EventPair* ep = nullptr;
   StageTimer(xivo_hip_ctx* ctx, int stage, double flops, const char* kernel = nullptr, double bytes = 0.0) : c(ctx) {
@@ -169,12 +194,15 @@ struct StageTimer {
   ~StageTimer() { if (ep) hipEventRecord(ep->b, c->stream); }
 };
 
+// One K-segment of a batched product: A [rows x K] times B^T, B [cols x K]
+struct GemmProduct { BatchMat A, B; int K = 0; };
+
 struct GemmExtra {
   int epi = EPI_NONE;
-  const double* diag = nullptr; long sDiag = 0;
-  const double* msub = nullptr; long sMsub = 0; int ldmsub = 0;
-  const double* mcol = nullptr; long sMcol = 0;
-  double* C2 = nullptr; long sC2 = 0; int ldc2 = 0;
+  BatchVec diag;   // EPI_ADD_DIAG
+  BatchMat msub;   // EPI_SUB_MAT / EPI_ADD_MAT / EPI_RSUB_MAT operand, same shape as C
+  BatchVec mcol;   // optional per-column scale of msub
+  BatchMat C2;     // optional second output = C^T
   int c2_rows = 0;   // > 0: the transposed copy only of the leading c2_rows rows of C (the columns of C2 a consumer reads)
   int lower_only = 0;
   int fp32 = 0;
@@ -184,21 +212,18 @@ struct GemmExtra {
   const int* skip = nullptr;   // per-filter status: non-zero = leave the output of that filter untouched
   const double* scale0 = nullptr;   // per-k scale of the first segment's B operand (same vector for every filter)
   int small_tiles = 0;   // symmetric output on 64 x 64 tiles (latency route)
+  GemmProduct seg1;      // optional second segment (seg1.A.p set): + A1 diag(scale1) B1^T
+  BatchVec scale1;       // per-k scale of the second segment's B operand, per filter
 };
-
-// leading state columns the calibration blocks live in: td 23, Cg 24..32, (Ca 33..38,) bg 9..11, intrinsics up to 39..47
-constexpr int LEAD_K = 48;
 
 // ---- capi.hip
 bool bad_range(xivo_hip_ctx* c, int b0, int nb);
-MeasBuffers meas_buffers(xivo_hip_ctx* c);
+MeasBuffers meas_buffers(xivo_hip_ctx* c, int b0 = 0);   // the dense rows, inn and diagR of the filters from b0 on
 SceneBuffers scene_buffers(xivo_hip_ctx* c);
 bool calib_sparse(const xivo_hip_ctx* c);
-// C = A0 B0^T (+ A1 diag(scale1) B1^T) over the batch, on the MFMA product kernels, timed as `stage`
-int gemm(xivo_hip_ctx* c, int stage, int B, int rows, int cols, const double* A0, long sA0, int lda0,
-         const double* B0, long sB0, int ldb0, int K0, const double* A1, long sA1, int lda1, const double* B1,
-         long sB1, int ldb1, int K1, const double* scale1, long sScale1, double* C, long sC, int ldc,
-         const GemmExtra& x);
+// C [rows x cols] = seg.A seg.B^T (+ x.seg1.A diag(x.scale1) x.seg1.B^T) over B filters, on the MFMA product kernels, timed as
+// `stage`
+int gemm(xivo_hip_ctx* c, int stage, int B, int rows, int cols, const GemmProduct& seg, const BatchMat& C, const GemmExtra& x);
 int ensure_staging(xivo_hip_ctx* c, size_t elems);
 int d2h_rows(xivo_hip_ctx* c, void* dst, size_t hpitch, const void* src, size_t dpitch, size_t width, size_t rows);
 int h2d_packed(xivo_hip_ctx* c, double* dst, const double* src, int nb, int rows, int cols, long stride, int ld);

@@ -16,7 +16,7 @@ int prop_step_control(xivo_hip_ctx* c, const xivo_prop_opts* o) {
   if (!o->control_stepsize) return XIVO_HIP_OK;
   if (o->method != 1 || !(o->stepsize > 0) || !(o->max_scale_factor > 0)) return XIVO_HIP_ERR_INVALID;
   if (c->pd_h && c->pd_h0 == o->stepsize) return XIVO_HIP_OK;
-  if (!c->pd_h) { int rcd = dev_alloc(&c->pd_h, (size_t)c->Bmax); if (rcd) return rcd; }
+  if (!c->pd_h) { int rcd = c->mem.zeroed(&c->pd_h, (size_t)c->Bmax); if (rcd) return rcd; }
   std::vector<double> h0((size_t)c->Bmax, o->stepsize);
   HIP_TRY(hipMemcpy(c->pd_h, h0.data(), h0.size() * sizeof(double), hipMemcpyHostToDevice));
   c->pd_h0 = o->stepsize;
@@ -39,7 +39,7 @@ int prop_stage(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_imu_in* im
   a = PropStateArgs{};
   a.poses = c->poses + b0; a.imu = dImu; a.n_imu = n_imu; a.Qimu = dQi; a.Qmodel = dQm;
   a.g[0] = o->g[0]; a.g[1] = o->g[1]; a.g[2] = o->g[2]; a.method = o->method; a.stepsize = o->stepsize;
-  a.P = c->P + (long)b0 * c->sP; a.strideP = c->sP; a.ldp = c->Np; a.Phi_out = dPhi; a.Pmm_out = dPmm; a.batch = nb;
+  c->P.from(b0).to(a.P, a.strideP, a.ldp); a.Phi_out = dPhi; a.Pmm_out = dPmm; a.batch = nb;
   if (o->control_stepsize) {
     a.pd_h = c->pd_h + b0; a.pd_tol = o->tolerance; a.pd_min_scale = o->min_scale_factor; a.pd_max_scale = o->max_scale_factor;
   }
@@ -63,7 +63,7 @@ int xivo_hip_propagate_cov(xivo_hip_ctx* c, int b0, int nb, int nm, const double
     char label[64];
     propagate_cov_pick(nm, c->N, label, sizeof(label));
     StageTimer st(c, ST_OTHER, 0.0, label);
-    if (launch_propagate_cov(c->P, c->sP, c->Np, c->N, c->Np, nm, c->staging, c->staging + per * nb, b0, nb, c->stream))
+    if (launch_propagate_cov(c->P.p, c->P.stride, c->P.ld, c->N, c->Np, nm, c->staging, c->staging + per * nb, b0, nb, c->stream))
       return XIVO_HIP_ERR_HIP;
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -100,7 +100,7 @@ int xivo_hip_propagate(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_im
     // tail: reads and writes the 23 rows and 23 columns of P that change (+ Phi, P_mm)
     StageTimer st(c, ST_PROP_TAIL, (double)nb * 2.0 * (2.0 * 23.0 * 23.0 * (c->N - 23)), "propagate_cov_fixed_kernel<23>",
                   (double)nb * (4.0 * 23 * c->N + 2.0 * 529) * sizeof(double));
-    HIP_TRY((hipError_t)launch_propagate_cov(c->P, c->sP, c->Np, c->N, c->Np, 23, a.Phi_out, a.Pmm_out, b0, nb, c->stream));
+    HIP_TRY((hipError_t)launch_propagate_cov(c->P.p, c->P.stride, c->P.ld, c->N, c->Np, 23, a.Phi_out, a.Pmm_out, b0, nb, c->stream));
   }
   HIP_TRY(hipStreamSynchronize(c->stream));   // imu / opts are borrowed host memory
   return XIVO_HIP_OK;
@@ -134,7 +134,7 @@ int xivo_hip_propagate_calib(xivo_hip_ctx* c, int b0, int nb, int n_imu, const x
     char label[64];
     propagate_cov_pick(nm, c->N, label, sizeof(label));
     StageTimer st(c, ST_PROP_TAIL, 0.0, label, (double)nb * (4.0 * nm * c->N + 2.0 * nm * nm) * sizeof(double));
-    HIP_TRY((hipError_t)launch_propagate_cov(c->P, c->sP, c->Np, c->N, c->Np, nm, a.Phi_out, a.Pmm_out, b0, nb, c->stream));
+    HIP_TRY((hipError_t)launch_propagate_cov(c->P.p, c->P.stride, c->P.ld, c->N, c->Np, nm, a.Phi_out, a.Pmm_out, b0, nb, c->stream));
   }
   HIP_TRY(hipStreamSynchronize(c->stream));   // imu / opts / Qmodel are borrowed host memory
   return XIVO_HIP_OK;

@@ -79,33 +79,26 @@ EllBuffers ell_range(const EllBuffers& ell, int b0) {
   return e;
 }
 
-// The context's per-filter buffers from filter b0 on. Each keeps the stride it is allocated with (c->sP, c->sH, ...), except A,
-// which has two views: A (stride sA: G of the whitened / tail forms, the fallback's A) and A_sP (stride sP: A = K H - I of the
-// as-coded dense pipeline).
-struct RangeView {
-  double *P, *H, *HT, *HP, *PHT, *S, *K, *A, *A_sP, *T, *invD, *inn, *diagR, *err, *y, *lead;
+// The context's per-filter buffers from filter b0 on: the views of the context (capi_internal.h), each moved to b0.
+struct UpdateViews {
+  BatchMat P, H, HT, HP, PHT, S, K, G, KHI, T, lead;
+  BatchVec invD, inn, diagR, err, y;
   int *status, *ldlt_used;
   EllBuffers ell;
 };
 
-RangeView range_view(xivo_hip_ctx* c, int b0) {
-  RangeView v;
-  v.P = c->P + (long)b0 * c->sP; v.H = c->H + (long)b0 * c->sH; v.HT = c->HT + (long)b0 * c->sHT; v.HP = c->HP + (long)b0 * c->sH;
-  v.PHT = c->PHT + (long)b0 * c->sK; v.S = c->S + (long)b0 * c->sS; v.K = c->K + (long)b0 * c->sK;
-  v.A = c->A + (long)b0 * c->sA; v.A_sP = c->A + (long)b0 * c->sP; v.T = c->T + (long)b0 * c->sP;
-  v.invD = c->invD + (long)b0 * c->sInvD; v.inn = c->inn + (long)b0 * c->Mpmax; v.diagR = c->diagR + (long)b0 * c->Mpmax;
-  v.err = c->err + (long)b0 * c->Np; v.y = c->yvec + (long)b0 * c->Mpmax;
-  v.lead = c->Hlead ? c->Hlead + (long)b0 * c->Mpmax * LEAD_K : nullptr;
-  v.status = c->status + b0; v.ldlt_used = c->ldlt_used + b0;
-  v.ell = ell_range(c->ell, b0);
-  return v;
+UpdateViews views_from(xivo_hip_ctx* c, int b0) {
+  return {c->P.from(b0), c->H.from(b0), c->HT.from(b0), c->HP.from(b0), c->PHT.from(b0), c->S.from(b0), c->K.from(b0),
+          c->G.from(b0), c->KHI.from(b0), c->T.from(b0), c->Hlead.from(b0),
+          c->invD.from(b0), c->inn.from(b0), c->diagR.from(b0), c->err.from(b0), c->yvec.from(b0),
+          c->status + b0, c->ldlt_used + b0, ell_range(c->ell, b0)};
 }
 
 // S = L L^T (chol_f64.hip) over B filters, the gate folded into its prologue when `cg` is given. `flops`: what the calling
 // pipeline counts for the stage.
-int factor_S(xivo_hip_ctx* c, const RangeView& v, int B, int latency, const CholGateArgs* cg, double flops) {
+int factor_S(xivo_hip_ctx* c, const UpdateViews& v, int B, int latency, const CholGateArgs* cg, double flops) {
   const int Mp = c->rows.rows_padded();
-  CholArgs a{}; a.S = v.S; a.strideS = c->sS; a.lds = c->Mpmax; a.Mp = Mp; a.invD = v.invD; a.strideInvD = c->sInvD;
+  CholArgs a{}; v.S.to(a.S, a.strideS, a.lds); a.Mp = Mp; v.invD.to(a.invD, a.strideInvD);
   a.status = v.status; a.batch = B; a.latency = latency;
   char clabel[64]; chol_kernel_label(Mp, B, clabel, sizeof(clabel));
   if (cg) { const size_t n = strlen(clabel); snprintf(clabel + n, sizeof(clabel) - n, "+gate"); }
@@ -116,10 +109,10 @@ int factor_S(xivo_hip_ctx* c, const RangeView& v, int B, int latency, const Chol
 
 // The arguments every launch of the substitution kernels shares: the factor, P H^T in, the gain and dx out. The caller adds
 // what its form needs (the mode, T / Pm / Yout, joseph, fwd_only / y, latency / stream8 / out_f32).
-TrsmArgs trsm_args(const xivo_hip_ctx* c, const RangeView& v, int B) {
-  TrsmArgs a{}; a.LU = v.S; a.strideLU = c->sS; a.ldlu = c->Mpmax; a.invD = v.invD; a.strideInvD = c->sInvD;
-  a.PHT = v.PHT; a.stridePHT = c->sK; a.ldpht = c->Np; a.K = v.K; a.strideK = c->sK; a.ldk = c->Np;
-  a.inn = v.inn; a.strideInn = c->Mpmax; a.err = v.err; a.strideErr = c->Np; a.Mp = c->rows.rows_padded(); a.Np = c->Np; a.batch = B;
+TrsmArgs trsm_args(const xivo_hip_ctx* c, const UpdateViews& v, int B) {
+  TrsmArgs a{}; v.S.to(a.LU, a.strideLU, a.ldlu); v.invD.to(a.invD, a.strideInvD);
+  v.PHT.to(a.PHT, a.stridePHT, a.ldpht); v.K.to(a.K, a.strideK, a.ldk);
+  v.inn.to(a.inn, a.strideInn); v.err.to(a.err, a.strideErr); a.Mp = c->rows.rows_padded(); a.Np = c->Np; a.batch = B;
   return a;
 }
 // XIVO_HIP_FLAG_SYMMETRIC_FORM: gain and covariance in the symmetric "square-root" form. With S = L L^T and
@@ -128,18 +121,18 @@ TrsmArgs trsm_args(const xivo_hip_ctx* c, const RangeView& v, int B) {
 // correction term vanishes identically), computed without the backward substitution, the residual G and the second
 // N x N x M product; its rounding error grows with cond(L) = sqrt(cond(S)), not cond(S). Opt-in: the reference codes
 // the Joseph form, which stays the default.
-static int finish_symmetric(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeView& v, int B) {
+static int finish_symmetric(xivo_hip_ctx* c, const UpdatePlan& plan, const UpdateViews& v, int B) {
   const int Np = c->Np, Mp = c->rows.rows_padded();
   {
     StageTimer st(c, ST_OTHER, 0.0, "fwd_vec_kernel");
-    HIP_TRY((hipError_t)launch_fwd_vec(v.S, c->sS, c->Mpmax, v.invD, c->sInvD, v.inn, c->Mpmax, v.y, c->Mpmax, Mp, B, c->stream));
+    HIP_TRY((hipError_t)launch_fwd_vec(v.S.p, v.S.stride, v.S.ld, v.invD.p, v.invD.stride, v.inn.p, v.inn.stride, v.y.p, v.y.stride, Mp, B, c->stream));
   }
   {
     TrsmArgs a = trsm_args(c, v, B);
-    a.fwd_only = 1; a.y = v.y; a.strideY = c->Mpmax;
+    a.fwd_only = 1; v.y.to(a.y, a.strideY);
     // the solve kernel goes on to P+ = P - W^T W in place, W^T still in its registers (blocks exchanged through LDS)
     const bool p_here = plan.in_solve;
-    if (p_here) { a.T = v.P; a.strideT = c->sP; a.ldt = Np; a.skip_status = v.status; }
+    if (p_here) { v.P.to(a.T, a.strideT, a.ldt); a.skip_status = v.status; }
     char label[64]; trsm_kernel_label(Mp, label, sizeof(label), p_here ? 2 : 0);
     const double outs = 0.5 * Np * (Np + 1.0), Nf = c->N, Mf = c->rows.rows();
     StageTimer st(c, ST_TRSM, (1.0 * Mf * Mf * Nf + (p_here ? Nf * (Nf + 1.0) * Mf : 0.0)) * B, label,
@@ -149,9 +142,18 @@ static int finish_symmetric(xivo_hip_ctx* c, const UpdatePlan& plan, const Range
   }
   // P+ = P - W^T W in place: the accumulators start at -P (every tile reads its part of P before it stores anything)
   // and the result is negated on the way out
-  GemmExtra x; x.epi = EPI_RSUB_MAT; x.msub = v.P; x.sMsub = c->sP; x.ldmsub = Np; x.lower_only = 1;
+  GemmExtra x; x.epi = EPI_RSUB_MAT; x.msub = v.P; x.lower_only = 1;
   x.skip = v.status;
-  return gemm(c, ST_PNEW, B, Np, Np, v.K, c->sK, Np, v.K, c->sK, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, v.P, c->sP, Np, x);
+  return gemm(c, ST_PNEW, B, Np, Np, {v.K, v.K, Mp}, v.P, x);
+}
+
+// XIVO_HIP_FLAG_FP32_WHITENED: both whitened outputs left the solve as FLOAT in the G buffer - Y^T at float 0, V^T at float
+// Np Mp (TrsmArgs::out_f32). As operands of a product that reads floats (GemmExtra::a_f32 / b_f32: leading dimension and
+// stride count ELEMENTS): the same leading dimension, twice the stride of the buffer of doubles.
+struct WhitenedF32 { BatchMat V, Y; };
+static WhitenedF32 whitened_f32(const BatchMat& G, int Np, int Mp) {
+  double* V = reinterpret_cast<double*>(reinterpret_cast<float*>(G.p) + (long)Np * Mp);
+  return {BatchMat{V, 2 * G.stride, G.ld}, BatchMat{G.p, 2 * G.stride, G.ld}};
 }
 
 // The factorisation, the gain, dx and the covariance update once P H^T and S are formed - shared by the sparse and the dense
@@ -159,17 +161,16 @@ static int finish_symmetric(xivo_hip_ctx* c, const UpdatePlan& plan, const Range
 //   S = L L^T (gate folded into its prologue when `cg` is given)                 estimator.cpp:1266
 //   in_solve : W = L^-1 (HP), K^T = L^-T W, dx, P+ = P - (W - D)^T (W + D) inside the solve kernel  estimator.cpp:1265-1287
 //   else     : V^T, Y^T leave the (chunked / streamed) solve, P+ = P - V^T Y as one tiled symmetric product
-static int finish_whitened(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeView& v, int B, const CholGateArgs* cg) {
+static int finish_whitened(xivo_hip_ctx* c, const UpdatePlan& plan, const UpdateViews& v, int B, const CholGateArgs* cg) {
   const int Np = c->Np, Mp = c->rows.rows_padded();
   const double Nf = c->N, Mf = c->rows.rows();
   // (the streamed solve reads the mirrored upper triangle)
   int rc = factor_S(c, v, B, plan.latency || plan.stream8, cg, Mf * Mf * Mf / 3.0 * B);
   if (rc) return rc;
-  double* G = v.A;
   {
     TrsmArgs a = trsm_args(c, v, B);
-    if (plan.in_solve) { a.T = v.P; a.strideT = c->sP; a.ldt = Np; a.joseph = 2; a.skip_status = v.status; }
-    else { a.Yout = G; a.strideY2 = c->sA; a.ldy2 = Np; a.latency = plan.latency; a.stream8 = plan.stream8 ? 1 : 0; a.out_f32 = plan.f32_whitened ? 1 : 0; }
+    if (plan.in_solve) { v.P.to(a.T, a.strideT, a.ldt); a.joseph = 2; a.skip_status = v.status; }
+    else { v.G.to(a.Yout, a.strideY2, a.ldy2); a.latency = plan.latency; a.stream8 = plan.stream8 ? 1 : 0; a.out_f32 = plan.f32_whitened ? 1 : 0; }
     char label[64]; trsm_kernel_label(Mp, label, sizeof(label), plan.in_solve ? 4 : 5, plan.latency, plan.stream8);
     // seven block rows on a narrow state: the ten- / twelve-wave instantiation with W in registers (solve_fused.hip)
     const bool narrow = plan.in_solve && trsm_narrow_supported(Mp, Np);
@@ -184,14 +185,14 @@ static int finish_whitened(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeV
     if (plan.in_solve) return XIVO_HIP_OK;
   }
   // P+ = P - V^T Y in place (V^T in the K buffer, Y^T in the G buffer), lower triangle + mirror
-  GemmExtra x; x.epi = EPI_RSUB_MAT; x.msub = v.P; x.sMsub = c->sP; x.ldmsub = Np; x.lower_only = 1; x.skip = v.status;
+  GemmExtra x; x.epi = EPI_RSUB_MAT; x.msub = v.P; x.lower_only = 1; x.skip = v.status;
   x.small_tiles = plan.latency;
-  if (plan.f32_whitened) {   // XIVO_HIP_FLAG_FP32_WHITENED: both operands left the solve as float (Y^T at float 0, V^T at float Np Mp of G)
+  if (plan.f32_whitened) {
     x.fp32 = 1; x.a_f32 = 1; x.b_f32 = 1;
-    const double* Vf = reinterpret_cast<const double*>(reinterpret_cast<const float*>(G) + (long)Np * Mp);
-    return gemm(c, ST_PNEW, B, Np, Np, Vf, 2 * c->sA, Np, G, 2 * c->sA, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, v.P, c->sP, Np, x);
+    const WhitenedF32 w = whitened_f32(v.G, Np, Mp);
+    return gemm(c, ST_PNEW, B, Np, Np, {w.V, w.Y, Mp}, v.P, x);
   }
-  return gemm(c, ST_PNEW, B, Np, Np, v.K, c->sK, Np, G, c->sA, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, v.P, c->sP, Np, x);
+  return gemm(c, ST_PNEW, B, Np, Np, {v.K, v.G, Mp}, v.P, x);
 }
 
 // Sparse-H pipelines (ell.h): H P, S and T H^T skip the structural zeros of H; the factorisation, the gain and the
@@ -202,9 +203,10 @@ static int finish_whitened(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeV
 //                    [MH gating]                   in the prologue of the factorisation / gate_ell    update.cpp:60-96
 //                    then finish_whitened / finish_symmetric, or (SPARSE_TAIL)
 //                    T = K (HP) - P, G = T H^T + K R, P+ = G K^T - T                          estimator.cpp:1276-1287 re-associated
-static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeView& v, int b0, int B, const GateParams* gate) {
-  const int Np = c->Np, Mp = c->rows.rows_padded(), ldh = c->Mpmax, lds = c->Mpmax;
-  double *P = v.P, *HP = v.HP, *PHT = v.PHT, *S = v.S, *K = v.K, *G = v.A, *T = v.T, *inn = v.inn, *diagR = v.diagR;
+static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const UpdateViews& v, int b0, int B, const GateParams* gate) {
+  const int Np = c->Np, Mp = c->rows.rows_padded();
+  const BatchMat &P = v.P, &HP = v.HP, &PHT = v.PHT, &S = v.S, &K = v.K, &G = v.G, &T = v.T;
+  const BatchVec &inn = v.inn, &diagR = v.diagR;
   const EllBuffers& e = v.ell;
   const auto [nc_max, pw_max] = c->rows.max_slots(b0, B);
   // algorithmic flops are counted on the TRUE sizes N, M (the padded Np, Mp only size the launches and the bytes)
@@ -216,13 +218,13 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
     // P H^T, S, the gate, the factor, both substitutions and the covariance product stay in the registers and the LDS of the
     // workgroup that owns the filter; nothing but P, P+ and the compressed rows crosses HBM.
     FusedArgs a{};
-    a.P = P; a.strideP = c->sP; a.ldp = Np; a.ell = e; a.inn = inn; a.strideInn = c->Mpmax; a.diagR = diagR; a.strideR = c->Mpmax;
-    a.err = v.err; a.strideErr = Np; a.PHT = PHT; a.stridePHT = c->sK; a.ldpht = Np; a.status = v.status;
+    P.to(a.P, a.strideP, a.ldp); a.ell = e; inn.to(a.inn, a.strideInn); diagR.to(a.diagR, a.strideR);
+    v.err.to(a.err, a.strideErr); PHT.to(a.PHT, a.stridePHT, a.ldpht); a.status = v.status;
     a.Np = Np; a.Mp = Mp; a.batch = B; a.pw = pw_max;
     if (gate) {
       a.gate = 1; a.F = gate->F; a.R = gate->R; a.thresh = gate->thresh; a.mult = gate->mult; a.min_inliers = gate->min_inliers;
       a.mask = c->mask + (long)b0 * gate->F; a.dist = c->dist + (long)b0 * gate->F;
-      if (c->rows.dense_alive()) { a.H = v.H; a.strideH = c->sH; a.ldh = ldh; a.HT = v.HT; a.strideHT = c->sHT; a.ldht = Np; }
+      if (c->rows.dense_alive()) { v.H.to(a.H, a.strideH, a.ldh); v.HT.to(a.HT, a.strideHT, a.ldht); }
     }
     char label[64]; fused_update_label(Mp, Np, pw_max, label, sizeof(label));
     const double t_outs_f = 0.5 * Nf * (Nf + 1.0);
@@ -242,69 +244,66 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
   bool walk_tiled = false;
   const int oos_k = (mr0 >= 0 && c->have_layout) ? std::min(Np, round_up16(c->lay.group_begin + 6 * c->lay.n_groups)) : Np;
   {
-    EllMulArgs a{}; a.ell = e; a.Src = P; a.strideSrc = c->sP; a.ldsrc = Np; a.out = PHT; a.strideOut = c->sK; a.ldo = Np;
-    a.out2 = HP; a.strideOut2 = c->sH; a.ldo2 = ldh; a.X = Np; a.Mp = Mp_ell; a.batch = B; a.nc_max = nc_max; a.pw_max = pw_max; a.cols = Np;
+    EllMulArgs a{}; a.ell = e; P.to(a.Src, a.strideSrc, a.ldsrc); PHT.to(a.out, a.strideOut, a.ldo);
+    HP.to(a.out2, a.strideOut2, a.ldo2); a.X = Np; a.Mp = Mp_ell; a.batch = B; a.nc_max = nc_max; a.pw_max = pw_max; a.cols = Np;
     char label[64]; ell_kernel_label(ELL_HP, a, label, sizeof(label));
     walk_tiled = ell_uses_slab_form(a);   // (the same decision for ell<S> below: it depends on the shape and slot counts only)
     StageTimer st(c, ST_HP, nnz_flops * Nf * B, label, 8.0 * B * ((double)Np * Np + (double)Np * Mp));
     HIP_TRY((hipError_t)launch_ell_mul(ELL_HP, a, c->stream));
   }
   if (mr0 >= 0) {   // (H P)_oos = H_oos P, with its transpose into the P H^T columns behind the in-state ones
-    const double* Hd = v.H + mr0;
-    GemmExtra x; x.C2 = PHT + (long)mr0 * Np; x.sC2 = c->sK; x.ldc2 = Np;
-    rc = gemm(c, ST_HP, B, oos_pad, Np, Hd, c->sH, ldh, P, c->sP, Np, oos_k, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, HP + mr0, c->sH, ldh, x);
+    GemmExtra x; x.C2 = PHT.at(0, mr0);
+    rc = gemm(c, ST_HP, B, oos_pad, Np, {v.H.at(mr0, 0), P, oos_k}, HP.at(mr0, 0), x);
     if (rc) return rc;
   }
   // online-calibration stacking on the sparse pipeline: the calibration columns of H live in the leading dense block
-  // L [Mp x LEAD_K] (stack_kernel): P H^T += P[:, 0:LEAD_K] L^T on the MFMA product
+  // L [Mp x LEAD_K] (stack_kernel, laid out on the allocated row count): P H^T += P[:, 0:LEAD_K] L^T on the MFMA product
   const bool lead = c->rows.has_lead() && mr0 < 0;
-  const double* Ld = lead ? v.lead : nullptr;
-  const long sLd = (long)c->Mpmax * LEAD_K;
-  const int ldl = c->Mpmax;   // (stack_kernel lays the block out on the allocated row count)
   if (lead) {
     // (the tiled walk writes P H^T only: this product completes it in place and leaves H P as its transposed copy - the
     //  leading LEAD_K columns the S product below reads, or all of it where ell<S> takes the gather form, which reads H P)
-    GemmExtra x; x.epi = EPI_ADD_MAT; x.msub = PHT; x.sMsub = c->sK; x.ldmsub = Np; x.C2 = HP; x.sC2 = c->sH; x.ldc2 = ldh;
+    GemmExtra x; x.epi = EPI_ADD_MAT; x.msub = PHT; x.C2 = HP;
     x.c2_rows = walk_tiled ? LEAD_K : 0;
-    rc = gemm(c, ST_HP, B, Np, Mp, P, c->sP, Np, Ld, sLd, ldl, LEAD_K, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, PHT, c->sK, Np, x);
+    rc = gemm(c, ST_HP, B, Np, Mp, {P, v.lead, LEAD_K}, PHT, x);
     if (rc) return rc;
   }
   GateEllArgs ga{};
   if (gate) {
     ga.ell = e;
-    ga.H = c->rows.dense_alive() ? v.H : nullptr; ga.strideH = c->sH; ga.ldh = ldh;
-    ga.HT = c->rows.dense_alive() ? v.HT : nullptr; ga.strideHT = c->sHT; ga.ldht = Np; ga.PHT = PHT;
+    v.H.to(ga.H, ga.strideH, ga.ldh); v.HT.to(ga.HT, ga.strideHT, ga.ldht);
+    if (!c->rows.dense_alive()) { ga.H = nullptr; ga.HT = nullptr; }
+    ga.PHT = PHT.p;
     ga.HP = nullptr;   // H P [Mp x Np] has no reader behind this point (S is formed already, the solve reads P H^T)
-    ga.inn = inn; ga.strideInn = c->Mpmax; ga.diagR = diagR; ga.strideR = c->Mpmax;
+    inn.to(ga.inn, ga.strideInn); diagR.to(ga.diagR, ga.strideR);
     ga.mask = c->mask + (long)b0 * gate->F; ga.dist = c->dist + (long)b0 * gate->F;
     ga.F = gate->F; ga.Np = Np; ga.batch = B;
-    ga.S = S; ga.strideS = c->sS; ga.lds = lds; ga.Mp = Mp; ga.from_S = 1;   // distances from the diagonal blocks of S
+    S.to(ga.S, ga.strideS, ga.lds); ga.Mp = Mp; ga.from_S = 1;   // distances from the diagonal blocks of S
     ga.R = gate->R; ga.thresh = gate->thresh; ga.mult = gate->mult; ga.min_inliers = gate->min_inliers;
   }
+  // the compact copy of the 2 x 2 diagonal blocks of S lives in the T buffer (free until the solve): 2 Mp doubles per filter
+  const BatchVec Sdiag{T.p, T.stride};
   int diag_done = 0;
   {
-    EllMulArgs a{}; a.ell = e; a.Src = PHT; a.strideSrc = c->sK; a.ldsrc = Np; a.SrcAlt = HP; a.strideSrcAlt = c->sH; a.ldsrcAlt = ldh;
-    a.out = S; a.strideOut = c->sS; a.ldo = lds; a.cols = Np;
-    a.diagR = diagR; a.strideR = c->Mpmax; a.X = Mp; a.Mp = Mp_ell; a.batch = B; a.nc_max = nc_max; a.pw_max = pw_max;
-    // the 2 x 2 diagonal blocks of S once more, compact (the T buffer is free until the solve): what the gate reads
-    if (gate && mr0 < 0 && !lead && (long)2 * Mp <= c->sP) { a.diag_out = T; a.strideDiag = c->sP; a.diag_done = &diag_done; }
+    EllMulArgs a{}; a.ell = e; PHT.to(a.Src, a.strideSrc, a.ldsrc); HP.to(a.SrcAlt, a.strideSrcAlt, a.ldsrcAlt);
+    S.to(a.out, a.strideOut, a.ldo); a.cols = Np;
+    diagR.to(a.diagR, a.strideR); a.X = Mp; a.Mp = Mp_ell; a.batch = B; a.nc_max = nc_max; a.pw_max = pw_max;
+    // the 2 x 2 diagonal blocks of S once more, compact: what the gate reads
+    if (gate && mr0 < 0 && !lead && (long)2 * Mp <= Sdiag.stride) { Sdiag.to(a.diag_out, a.strideDiag); a.diag_done = &diag_done; }
     char label[64]; ell_kernel_label(ELL_S, a, label, sizeof(label));
     StageTimer st(c, ST_S, nnz_flops * Mf * B, label, 8.0 * B * ((double)Np * Mp + (double)Mp * Mp));
     HIP_TRY((hipError_t)launch_ell_mul(ELL_S, a, c->stream));
   }
   if (mr0 >= 0) {   // the OOS x OOS block of S (the OOS x in-state block came out of the walk above: rows of S run over all M)
-    const double* Hd = v.H + mr0;
-    GemmExtra x; x.epi = EPI_ADD_DIAG; x.diag = diagR + mr0; x.sDiag = c->Mpmax; x.lower_only = 1;
-    rc = gemm(c, ST_S, B, oos_pad, oos_pad, HP + mr0, c->sH, ldh, Hd, c->sH, ldh, oos_k, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0,
-              S + mr0 + (long)mr0 * lds, c->sS, lds, x);
+    GemmExtra x; x.epi = EPI_ADD_DIAG; x.diag = BatchVec{diagR.p + mr0, diagR.stride}; x.lower_only = 1;
+    rc = gemm(c, ST_S, B, oos_pad, oos_pad, {HP.at(mr0, 0), v.H.at(mr0, 0), oos_k}, S.at(mr0, mr0), x);
     if (rc) return rc;
   }
   if (lead) {
     // S += (H P)[:, 0:LEAD_K] L^T. The walk above left, in the lower triangle, S[i, j] = sum over the COMPRESSED columns k of
     // row j of (H P)[i, k] H[j, k] with the complete H P: what is missing is the same sum over row j's calibration columns
     // (the order of the operands matters - L (H P)^T is the transpose, and neither term is symmetric on its own)
-    GemmExtra x; x.epi = EPI_ADD_MAT; x.msub = S; x.sMsub = c->sS; x.ldmsub = lds; x.lower_only = 1;
-    rc = gemm(c, ST_S, B, Mp, Mp, HP, c->sH, ldh, Ld, sLd, ldl, LEAD_K, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, S, c->sS, lds, x);
+    GemmExtra x; x.epi = EPI_ADD_MAT; x.msub = S; x.lower_only = 1;
+    rc = gemm(c, ST_S, B, Mp, Mp, {HP, v.lead, LEAD_K}, S, x);
     if (rc) return rc;
   }
   // With thousands of factors the gate rides in the prologue of the factorisation (chol_f64.hip, GATE): the distances come
@@ -313,11 +312,11 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
   CholGateArgs cg{};
   bool gate_folded = false;
   if (gate) {
-    if (diag_done) { ga.Sdiag = T; ga.strideSdiag = c->sP; }
+    if (diag_done) Sdiag.to(ga.Sdiag, ga.strideSdiag);
     gate_folded = diag_done && !c->rows.dense_alive() && mr0 < 0 && !plan.latency && chol_gate_supported(Mp, B);
     if (gate_folded) {
-      cg.Sdiag = ga.Sdiag; cg.strideSdiag = ga.strideSdiag; cg.inn = inn; cg.strideInn = c->Mpmax; cg.diagR = diagR; cg.strideR = c->Mpmax;
-      cg.ellval = e.val; cg.strideVal = e.stride_val(); cg.ell_w = ELL_W; cg.PHT = PHT; cg.stridePHT = c->sK; cg.ldpht = Np; cg.Np = Np;
+      Sdiag.to(cg.Sdiag, cg.strideSdiag); inn.to(cg.inn, cg.strideInn); diagR.to(cg.diagR, cg.strideR);
+      cg.ellval = e.val; cg.strideVal = e.stride_val(); cg.ell_w = ELL_W; PHT.to(cg.PHT, cg.stridePHT, cg.ldpht); cg.Np = Np;
       cg.mask = ga.mask; cg.dist = ga.dist; cg.F = gate->F; cg.R = gate->R; cg.thresh = gate->thresh; cg.mult = gate->mult;
       cg.min_inliers = gate->min_inliers;
     } else {
@@ -334,7 +333,7 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
   const bool t_here = trsm_forms_T(Mp, Np);      // the solve forms T on the gain still in its registers
   {
     TrsmArgs a = trsm_args(c, v, B);
-    if (t_here) { a.T = T; a.strideT = c->sP; a.ldt = Np; a.Pm = P; a.stridePm = c->sP; a.ldpm = Np; }
+    if (t_here) { T.to(a.T, a.strideT, a.ldt); P.to(a.Pm, a.stridePm, a.ldpm); }
     char label[64]; trsm_kernel_label(Mp, label, sizeof(label), t_here ? 1 : 0);
     const double t_outs = 0.5 * Np * (Np + 1.0), t_outs_f = 0.5 * Nf * (Nf + 1.0);
     StageTimer st(c, ST_TRSM, (2.0 * Mf * Mf * Nf + (t_here ? 2.0 * t_outs_f * Mf : 0.0)) * B, label,
@@ -343,21 +342,21 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
   }
   if (!t_here) {  // T = K (HP) - P = (HP)^T S^-1 (HP) - P: symmetric up to the rounding of the solve, so the lower
                   // triangle is computed and mirrored
-    GemmExtra x; x.epi = EPI_SUB_MAT; x.msub = P; x.sMsub = c->sP; x.ldmsub = Np; x.lower_only = 1;
-    rc = gemm(c, ST_AP, B, Np, Np, K, c->sK, Np, PHT, c->sK, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, T, c->sP, Np, x);
+    GemmExtra x; x.epi = EPI_SUB_MAT; x.msub = P; x.lower_only = 1;
+    rc = gemm(c, ST_AP, B, Np, Np, {K, PHT, Mp}, T, x);
     if (rc) return rc;
   }
   {  // G = T H^T + K diag(R)   [Np x Mp, in the A buffer]
-    EllMulArgs a{}; a.ell = e; a.Src = T; a.strideSrc = c->sP; a.ldsrc = Np; a.out = G; a.strideOut = c->sA; a.ldo = Np;
-    a.diagR = diagR; a.strideR = c->Mpmax; a.K = K; a.strideK = c->sK; a.ldk = Np; a.X = Np; a.Mp = Mp; a.batch = B; a.nc_max = nc_max; a.pw_max = pw_max; a.cols = Np;
+    EllMulArgs a{}; a.ell = e; T.to(a.Src, a.strideSrc, a.ldsrc); G.to(a.out, a.strideOut, a.ldo);
+    diagR.to(a.diagR, a.strideR); K.to(a.K, a.strideK, a.ldk); a.X = Np; a.Mp = Mp; a.batch = B; a.nc_max = nc_max; a.pw_max = pw_max; a.cols = Np;
     char label[64]; ell_kernel_label(ELL_G, a, label, sizeof(label));
     StageTimer st(c, ST_KH, nnz_flops * Np * B, label, 8.0 * B * ((double)Np * Np + 2.0 * Np * Mp));
     HIP_TRY((hipError_t)launch_ell_mul(ELL_G, a, c->stream));
   }
   if (pnew_reg_supported(Mp, Np)) {
     // P+ = G K^T - T, all fp64: rows of G in registers, blocks of K through LDS, one workgroup per filter
-    PnewRegArgs a{}; a.G = G; a.strideG = c->sA; a.ldg = Np; a.K = K; a.strideK = c->sK; a.ldk = Np;
-    a.T = T; a.strideT = c->sP; a.ldt = Np; a.P = P; a.strideP = c->sP; a.ldp = Np;
+    PnewRegArgs a{}; G.to(a.G, a.strideG, a.ldg); K.to(a.K, a.strideK, a.ldk);
+    T.to(a.T, a.strideT, a.ldt); P.to(a.P, a.strideP, a.ldp);
     a.skip_status = v.status; a.Mp = Mp; a.Np = Np; a.batch = B;
     char label[64]; pnew_reg_kernel_label(Mp, label, sizeof(label));
     const double outs = 0.5 * Np * (Np + 1.0);
@@ -366,32 +365,30 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ra
     return XIVO_HIP_OK;
   }
   // P+ = G K^T - T   (lower triangle + mirror)
-  GemmExtra x; x.epi = EPI_SUB_MAT; x.msub = T; x.sMsub = c->sP; x.ldmsub = Np; x.lower_only = 1;
+  GemmExtra x; x.epi = EPI_SUB_MAT; x.msub = T; x.lower_only = 1;
   x.skip = v.status;   // S not positive definite: P of that filter stays the prior (reported through xivo_hip_get_status)
-  return gemm(c, ST_PNEW, B, Np, Np, G, c->sA, Np, K, c->sK, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, P, c->sP, Np, x);
+  return gemm(c, ST_PNEW, B, Np, Np, {G, K, Mp}, P, x);
 }
 
-static int update_dense_range(xivo_hip_ctx* c, const UpdatePlan& plan, const RangeView& v, int b0, int B, const GateParams* gate) {
-  const int Np = c->Np, Mp = c->rows.rows_padded(), ldh = c->Mpmax, lds = c->Mpmax;
-  const double *H = v.H, *HT = v.HT, *inn = v.inn, *diagR = v.diagR;
-  double *P = v.P, *HP = v.HP, *PHT = v.PHT, *S = v.S, *K = v.K, *A = v.A_sP, *T = v.T;
+static int update_dense_range(xivo_hip_ctx* c, const UpdatePlan& plan, const UpdateViews& v, int b0, int B, const GateParams* gate) {
+  const int Np = c->Np, Mp = c->rows.rows_padded();
+  const BatchMat &H = v.H, &HT = v.HT, &P = v.P, &HP = v.HP, &PHT = v.PHT, &S = v.S, &K = v.K, &A = v.KHI, &T = v.T;
   int rc = ensure_dense(c);   // (mixed stacking / a leading block: the in-state rows are rebuilt densely next to the rows already in place)
   if (rc) return rc;
   {  // HP = H * P and its transpose PH^T (estimator.cpp:1259 first product; P symmetric => B operand = P rows)
-    GemmExtra x; x.C2 = PHT; x.sC2 = c->sK; x.ldc2 = Np;
-    rc = gemm(c, ST_HP, B, Mp, Np, H, c->sH, ldh, P, c->sP, Np, Np, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0,
-              HP, c->sH, ldh, x);
+    GemmExtra x; x.C2 = PHT;
+    rc = gemm(c, ST_HP, B, Mp, Np, {H, P, Np}, HP, x);
     if (rc) return rc;
   }
   if (gate) {  // Estimator::MHGating on the rows just multiplied (update.cpp:60-96): S_f = (HP)_f H_f^T + R
     rc = ensure_HT(c);   // the gate reads (and neutralises) the transposed rows
     if (rc) return rc;
     GateDenseArgs a{};
-    a.H = H; a.strideH = c->sH; a.ldh = ldh; a.HP = HP; a.strideHP = c->sH; a.ldhp = ldh;
-    a.Hw = v.H; a.HTw = v.HT; a.strideHT = c->sHT; a.ldht = Np;
-    a.HPw = HP; a.PHTw = PHT; a.PHTr = PHT;
-    a.inn = v.inn; a.strideInn = c->Mpmax; a.diagR = v.diagR;
-    a.strideR = c->Mpmax; a.mask = c->mask + (long)b0 * gate->F; a.dist = c->dist + (long)b0 * gate->F;
+    H.to(a.H, a.strideH, a.ldh); HP.to(a.HP, a.strideHP, a.ldhp);
+    a.Hw = H.p; HT.to(a.HTw, a.strideHT, a.ldht);
+    a.HPw = HP.p; a.PHTw = PHT.p; a.PHTr = PHT.p;
+    v.inn.to(a.inn, a.strideInn); v.diagR.to(a.diagR, a.strideR);
+    a.mask = c->mask + (long)b0 * gate->F; a.dist = c->dist + (long)b0 * gate->F;
     a.F = gate->F; a.Np = Np; a.batch = B;
     a.R = gate->R; a.thresh = gate->thresh; a.mult = gate->mult; a.min_inliers = gate->min_inliers;
     a.ell = c->ell; a.have_ell = 0;
@@ -399,9 +396,8 @@ static int update_dense_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ran
     HIP_TRY((hipError_t)launch_gate_dense(a, c->stream));
   }
   {  // S = HP * H^T + diag(R)  (estimator.cpp:1259-1263); lower triangle + mirror
-    GemmExtra x; x.epi = EPI_ADD_DIAG; x.diag = diagR; x.sDiag = c->Mpmax; x.lower_only = 1;
-    rc = gemm(c, ST_S, B, Mp, Mp, HP, c->sH, ldh, H, c->sH, ldh, Np, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0,
-              S, c->sS, lds, x);
+    GemmExtra x; x.epi = EPI_ADD_DIAG; x.diag = v.diagR; x.lower_only = 1;
+    rc = gemm(c, ST_S, B, Mp, Mp, {HP, H, Np}, S, x);
     if (rc) return rc;
   }
   if (plan.route == ROUTE_DENSE_WHITENED)      // an H without XIVO's row structure: everything behind S as on the sparse pipeline
@@ -420,22 +416,20 @@ static int update_dense_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ran
   if (rc) return rc;
   {  // A = K * H - I  (estimator.cpp:1276-1279)
     GemmExtra x; x.epi = EPI_SUB_IDENT;
-    rc = gemm(c, ST_KH, B, Np, Np, K, c->sK, Np, HT, c->sHT, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0,
-              A, c->sP, Np, x);
+    rc = gemm(c, ST_KH, B, Np, Np, {K, HT, Mp}, A, x);
     if (rc) return rc;
   }
   {  // T = A * P = K * (HP) - P  (estimator.cpp:1280, left product; distributes over the already
      // formed HP, 2MN^2 instead of 2N^3 flops, same value up to rounding)
-    GemmExtra x; x.epi = EPI_SUB_MAT; x.msub = P; x.sMsub = c->sP; x.ldmsub = Np;
-    rc = gemm(c, ST_AP, B, Np, Np, K, c->sK, Np, PHT, c->sK, Np, Mp, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0,
-              T, c->sP, Np, x);
+    GemmExtra x; x.epi = EPI_SUB_MAT; x.msub = P;
+    rc = gemm(c, ST_AP, B, Np, Np, {K, PHT, Mp}, T, x);
     if (rc) return rc;
   }
   {  // P = T * A^T + K diag(R) K^T  (estimator.cpp:1280-1287, fused; lower triangle + mirror)
     GemmExtra x; x.lower_only = 1;
     x.skip = v.status;
-    rc = gemm(c, ST_PNEW, B, Np, Np, T, c->sP, Np, A, c->sP, Np, Np, K, c->sK, Np, K, c->sK, Np, Mp, diagR,
-              c->Mpmax, P, c->sP, Np, x);
+    x.seg1 = {K, K, Mp}; x.scale1 = v.diagR;
+    rc = gemm(c, ST_PNEW, B, Np, Np, {T, A, Np}, P, x);
   }
   return rc;
 }
@@ -445,7 +439,7 @@ static int update_dense_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Ran
 // as-coded Joseph update, on exactly those filters (ldlt_fallback.hip). Every pipeline leaves the covariance of such a
 // filter untouched and its status set, so the fallback starts from the prior.
 static int update_joseph_range(xivo_hip_ctx* c, int b0, int B, const GateParams* gate = nullptr) {
-  const RangeView v = range_view(c, b0);
+  const UpdateViews v = views_from(c, b0);
   const UpdatePlan plan = plan_update(c, b0, B, gate != nullptr);
   c->last_path = plan.sparse ? 1 : 0;
   c->last_route = plan.route;
@@ -458,17 +452,12 @@ static int update_joseph_range(xivo_hip_ctx* c, int b0, int B, const GateParams*
   // (the fallback kernel writes ldlt_used of EVERY filter of the range: 0 where the Cholesky succeeded, 1 where it stepped in)
   LdltFallbackArgs a{};
   a.status = v.status; a.used = v.ldlt_used; a.ell = v.ell;
-  a.H = v.H; a.strideH = c->sH; a.ldh = c->Mpmax; a.use_dense = c->last_path == 0 ? 1 : 0;
+  v.H.to(a.H, a.strideH, a.ldh); a.use_dense = c->last_path == 0 ? 1 : 0;
   a.mixed_row0 = c->last_path == 1 ? c->rows.mixed_row0() : -1;
-  if (c->last_path == 1 && c->rows.has_lead()) { a.lead = v.lead; a.strideLead = (long)c->Mpmax * LEAD_K; a.ldlead = c->Mpmax; a.lead_k = LEAD_K; }
-  a.PHT = v.PHT; a.stridePHT = c->sK; a.ldpht = c->Np;
-  a.S = v.S; a.strideS = c->sS; a.lds = c->Mpmax;
-  a.K = v.K; a.strideK = c->sK; a.ldk = c->Np;
-  a.A = v.A; a.strideA = c->sA; a.lda = c->Np;
-  a.T = v.T; a.strideT = c->sP; a.ldt = c->Np;
-  a.P = v.P; a.strideP = c->sP; a.ldp = c->Np;
-  a.inn = v.inn; a.strideInn = c->Mpmax; a.diagR = v.diagR; a.strideR = c->Mpmax;
-  a.err = v.err; a.strideErr = c->Np;
+  if (c->last_path == 1 && c->rows.has_lead()) { v.lead.to(a.lead, a.strideLead, a.ldlead); a.lead_k = LEAD_K; }
+  v.PHT.to(a.PHT, a.stridePHT, a.ldpht); v.S.to(a.S, a.strideS, a.lds); v.K.to(a.K, a.strideK, a.ldk);
+  v.G.to(a.A, a.strideA, a.lda); v.T.to(a.T, a.strideT, a.ldt); v.P.to(a.P, a.strideP, a.ldp);
+  v.inn.to(a.inn, a.strideInn); v.diagR.to(a.diagR, a.strideR); v.err.to(a.err, a.strideErr);
   a.N = c->N; a.M = c->rows.rows(); a.batch = B;
   StageTimer st(c, ST_OTHER, 0.0, "ldlt_fallback_kernel");
   HIP_TRY((hipError_t)launch_ldlt_fallback(a, c->stream));
@@ -577,9 +566,7 @@ namespace xivo_hip::capi {
 int stage_measurements(xivo_hip_ctx* c, int b0, int nb, int M, const double* dH, long strideH, int ldh,
                        const double* dInn, long strideInn, const double* dR, long strideR) {
   const int N = c->N;
-  MeasBuffers mb = meas_buffers(c);
-  mb.H += (long)b0 * mb.strideH; mb.HT += (long)b0 * mb.strideHT;
-  mb.inn += (long)b0 * mb.strideInn; mb.diagR += (long)b0 * mb.strideR;
+  const MeasBuffers mb = meas_buffers(c, b0);
   const EllBuffers e = ell_range(c->ell, b0);
   // (XIVO_HIP_NO_COMPRESS: test hook for the branch very wide states take - the shape limit itself is N > ~2800 at M = 384)
   static const bool no_compress = getenv("XIVO_HIP_NO_COMPRESS") != nullptr;
@@ -700,7 +687,7 @@ int xivo_hip_get_err(xivo_hip_ctx* c, int b0, int nb, double* err, long stride) 
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (bad_range(c, b0, nb) || !err || stride < c->N) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
-  return d2h_rows(c, err, (size_t)stride * sizeof(double), c->err + (long)b0 * c->Np, (size_t)c->Np * sizeof(double),
+  return d2h_rows(c, err, (size_t)stride * sizeof(double), c->err.from(b0).p, (size_t)c->err.stride * sizeof(double),
                   (size_t)c->N * sizeof(double), nb);
 }
 
@@ -757,7 +744,6 @@ int xivo_hip_update_joseph_host(xivo_hip_ctx* c, int b, int M, const double* H, 
     if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->pin_d), c->pin_h, 0) != hipSuccess || !c->pin_d) {
       hipHostFree(c->pin_h); c->pin_h = nullptr; c->pin_d = nullptr; (void)hipGetLastError(); return XIVO_HIP_ERR_HIP;
     }
-    c->pin_bytes = total;
   }
   // the row-pair compressed rows, built while H_ is staged; an H_ that does not fit them (dense rows, stacked OOS rows) or a
   // context pinned to the dense / fp32 pipelines takes the general entry points - same results, more crossings
@@ -794,11 +780,11 @@ int xivo_hip_update_joseph_host(xivo_hip_ctx* c, int b, int M, const double* H, 
     for (int j = 0; j < N; ++j) memcpy(sp + (size_t)j * N + j, P + (size_t)j * ldp + j, (size_t)(N - j) * sizeof(double));
     ia.Psrc = reinterpret_cast<const double*>(c->pin_d + o_Pin); ia.ldps = N;
   }
-  const RangeView v = range_view(c, b);
-  ia.P = v.P; ia.N = N; ia.Np = Np; ia.ldp = Np;
+  const UpdateViews v = views_from(c, b);
+  ia.P = v.P.p; ia.N = N; ia.Np = Np; ia.ldp = v.P.ld;
   ia.block = c->pin_d; ia.off_idx = (int)o_idx; ia.off_val = (int)o_val; ia.off_inn = (int)o_inn; ia.off_R = (int)o_R; ia.off_flags = (int)o_flags;
   ia.pairs_clear = pairs_clear; ia.Mpmax = c->Mpmax;
-  ia.idx = v.ell.idx; ia.val = v.ell.val; ia.inn = v.inn; ia.diagR = v.diagR;
+  ia.idx = v.ell.idx; ia.val = v.ell.val; ia.inn = v.inn.p; ia.diagR = v.diagR.p;
   ia.nc = v.ell.nc; ia.pw = v.ell.pw; ia.over = v.ell.over;
   {
     StageTimer st(c, ST_STACK, 0.0, "dropin_in_kernel", (p_up ? 8.0 * N * N : 0.0) + (double)pairs_clear * ELL_W * 20.0 + 16.0 * c->Mpmax);
@@ -811,9 +797,9 @@ int xivo_hip_update_joseph_host(xivo_hip_ctx* c, int b, int M, const double* H, 
   int rc = update_joseph_range(c, b, 1);
   if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
   DropinOutArgs oa{};
-  oa.P = v.P; oa.N = N; oa.ldp = Np;
+  oa.P = v.P.p; oa.N = N; oa.ldp = v.P.ld;
   if (p_down) { oa.Pdst = reinterpret_cast<double*>(c->pin_d + o_Pout); oa.ldpd = N; }
-  oa.err = v.err; oa.err_dst = reinterpret_cast<double*>(c->pin_d + o_err);
+  oa.err = v.err.p; oa.err_dst = reinterpret_cast<double*>(c->pin_d + o_err);
   oa.status = v.status; oa.ldlt_used = v.ldlt_used; oa.flags_dst = reinterpret_cast<int*>(c->pin_d + o_st);
   {
     StageTimer st(c, ST_OTHER, 0.0, "dropin_out_kernel", (p_down ? 8.0 * N * N : 0.0) + 8.0 * N);

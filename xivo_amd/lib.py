@@ -185,6 +185,7 @@ _SIGS = {
     "xivo_hip_selftest_fused_shape": [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int],
     "xivo_hip_selftest_host_compress": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_selftest_glevel_launch": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int],
+    "xivo_hip_selftest_ctx_allocs": [C.c_void_p, C.c_void_p, C.c_void_p],
 }
 HOST_P_RESIDENT, HOST_KEEP_P = 1, 2
 
@@ -296,6 +297,12 @@ class Context:
             self._dev_bufs = []
             self.lib.xivo_hip_destroy(self.h)
             self.h = None
+
+    def ctx_allocs(self):
+        """(live, bytes): number and total size of the device blocks the context owns right now (test hook)"""
+        live, nbytes = C.c_int(0), C.c_ulonglong(0)
+        self._check(self.lib.xivo_hip_selftest_ctx_allocs(self.h, C.byref(live), C.byref(nbytes)))
+        return live.value, nbytes.value
 
     def __del__(self):
         try:
