@@ -38,7 +38,8 @@ enum {
   XIVO_HIP_ERR_HIP = -2,         /* a HIP runtime call failed                   */
   XIVO_HIP_ERR_NOT_SPD = -3,     /* S = HPH^T + R not positive definite         */
   XIVO_HIP_ERR_NOMEM = -4,
-  XIVO_HIP_ERR_UNSUPPORTED = -5  /* size outside what the kernels are built for */
+  XIVO_HIP_ERR_UNSUPPORTED = -5, /* size outside what the kernels are built for */
+  XIVO_HIP_ERR_FULL = -6         /* the trajectory log holds T_max frames       */
 };
 
 /* flags for xivo_hip_create / stacking */
@@ -650,6 +651,52 @@ int xivo_hip_absorb_error(xivo_hip_ctx* ctx, int B);
 /* download the resident scene (any pointer may be NULL) */
 int xivo_hip_get_scene(xivo_hip_ctx* ctx, int b0, int nb, xivo_pose_in* poses, xivo_group_in* groups,
                        xivo_feat_in* feats);
+
+/* ---- trajectory log: each frame's estimate and marginal covariance, recorded on the device ----
+ * A sequence driver keeps thousands of filters resident; what it wants out per camera frame is each filter's motion state
+ * and the covariance of a few error-state columns - not the scene (xivo_hip_get_scene) or the N x N covariance
+ * (xivo_hip_download_P) of every filter. The log is device memory [T_max][batch_max] that one kernel launch per frame
+ * appends to; it is read back in one copy at the end, or in slices of frames and filters. Nothing is allocated until
+ * xivo_hip_traj_config. */
+#define XIVO_TRAJ_MAX_COLS 32
+typedef struct {
+  int T_max;                     /* frames the log holds; 0 releases it                                     */
+  int n_cols;                    /* 1 .. XIVO_TRAJ_MAX_COLS                                                  */
+  int cols[XIVO_TRAJ_MAX_COLS];  /* error-state columns in [0, N), distinct, any order                      */
+} xivo_traj_opts;
+/* what one frame keeps of one filter's nominal state (fields as in xivo_pose_in) */
+typedef struct {
+  double Rsb[9], Tsb[3], Vsb[3], bg[3], ba[3];
+  int status;    /* the filter's update status at that point (what xivo_hip_get_status would return for it) */
+  int reserved;
+} xivo_traj_rec;
+/* (Re-)allocates the log through the context's owner and empties it: T_max frames of batch_max records and of batch_max
+ * packed covariance blocks of n_cols (n_cols + 1) / 2 doubles. T_max = 0 (n_cols / cols are then not read) releases it. Bad
+ * columns, n_cols out of range, or a size that overflows: XIVO_HIP_ERR_INVALID and the log is left as it was. */
+int xivo_hip_traj_config(xivo_hip_ctx* ctx, const xivo_traj_opts* opts);
+/* Appends one frame for filters [0, B), B <= batch_max (records of the other filters of that frame are undefined): one
+ * launch on the context's stream, ordered after everything enqueued before it, no synchronisation. Per filter the record
+ * above from the resident xivo_pose_in and the lower triangle of P[cols, cols], packed row by row: the entry of list
+ * positions (i, j), i >= j, at i (i + 1) / 2 + j, read from the LOWER triangle of the stored P, P[max(ci, cj), min(ci, cj)].
+ * ts_ns is kept on the host. frame_out (may be NULL) receives the frame's index. Log full: XIVO_HIP_ERR_FULL, nothing is
+ * written or launched. Not configured (or no scene yet): XIVO_HIP_ERR_INVALID. */
+int xivo_hip_traj_record(xivo_hip_ctx* ctx, int B, long long ts_ns, int* frame_out);
+/* frames recorded so far (negative: a status) */
+int xivo_hip_traj_count(xivo_hip_ctx* ctx);
+/* count <- 0; the memory and the configuration are kept */
+int xivo_hip_traj_reset(xivo_hip_ctx* ctx);
+/* Frames [t0, t0 + nt) (all recorded) of filters [b0, b0 + nb) to host arrays, frame-major: recs [nt][nb],
+ * cov [nt][nb][n_cols (n_cols + 1) / 2], ts [nt]. A NULL pointer skips that part. One synchronisation. */
+int xivo_hip_traj_read(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, xivo_traj_rec* recs, double* cov, long long* ts);
+/* Consistency of the logged poses against ground truth, on the device. gt: host [nt][nb][12], the true Rsb (column-major)
+ * then Tsb of every entry of the slice. Columns 0..5 (Wsb, Tsb) must be among the recorded ones, else XIVO_HIP_ERR_INVALID.
+ * Per entry: e = (log(Rsb_est^T Rsb_gt), Tsb_gt - Tsb_est) - the error-state vector xivo_hip_absorb_error would need in
+ * columns 0..5 to move the estimate onto the truth -, Sigma = the 6 x 6 block of the record on those columns, Sigma = L L^T
+ * (un-pivoted Cholesky), nees = |L^-1 e|^2; a Sigma that is not positive definite gives NaN. anees[t] is the mean of the
+ * finite nees of frame t0 + t, n_used[t] their number (0: anees NaN); it is summed in a fixed order, so two calls on the same
+ * log return the same bits. Outputs (host, any may be NULL): err6 [nt][nb][6], nees [nt][nb], anees [nt], n_used [nt]. */
+int xivo_hip_traj_nees(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, const double* gt, double* err6, double* nees,
+                       double* anees, int* n_used);
 
 /* ---- resident state edits between updates, batched over filters ----
  * The reference edits X_/P_ one filter at a time on the host (the functions cited per kind). A sequence driver that

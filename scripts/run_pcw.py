@@ -12,6 +12,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from xivo_amd import formats, pcw, sequence  # noqa: E402
 
 
+def _consistency(out):
+    """-traj-log: mean over the frames of the ensemble-mean pose NEES (6 for a consistent filter), and how many (frame,
+    sequence) entries had a covariance block that was not positive definite (this rank's sequences)"""
+    if "anees" not in out:
+        return {}
+    return {"anees_pose": float(np.nanmean(out["anees"])),
+            "nees_not_spd": int(out["nees"].size - out["nees_used"].sum())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-sequences", type=int, default=256)
@@ -29,6 +38,10 @@ def main():
     ap.add_argument("-dump", default="", help="directory for per-sequence `ts Tsb Wsb` trajectories")
     ap.add_argument("-gpus", type=int, default=1,
                     help="BASELINE config 5 without a launcher: spawn this many ranks (one per GPU), sequence s on rank s mod gpus")
+    ap.add_argument("-traj-log", dest="traj_log", action="store_true",
+                    help="record every frame's estimate and motion-state covariance on the device (one read at the end) and "
+                         "report anees_pose: the 6-dof pose NEES against the simulator's ground truth, ensemble mean per frame, "
+                         "averaged over the frames (-host python and -vectorized)")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         from xivo_amd.shard import spawn_ranks
@@ -38,7 +51,7 @@ def main():
         tm = {}
         t0 = time.perf_counter()
         out = sequence.run_pcw_batch(cfg, a.sequences, total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
-                                     noise_vision_std=a.noise_vision_std, npts=a.npts, timers=tm)
+                                     noise_vision_std=a.noise_vision_std, npts=a.npts, timers=tm, trajectory_log=a.traj_log)
         wall = time.perf_counter() - t0
         st = out["estimator"].stats(); out["estimator"].close()
         frames = len(out["ts"])
@@ -47,6 +60,7 @@ def main():
             "sequences": a.sequences, "frames_per_sequence": frames, "N": cfg.N, "integration": a.integration_method,
             "host": "cpp, vectorised simulators",
             "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
+            **_consistency(out),
             "updates": st["updates"], "mh_rejected": st["mh_rejected"], "wall_s": wall, "simulator_s": tm.get("sim", 0.0),
             "frame_calls_s": tm.get("frame", 0.0), "host_cpp_lifecycle_s": st["host_seconds"],
             "frames_per_s_in_frame_calls": a.sequences * frames / tm["frame"],
@@ -82,7 +96,7 @@ def main():
     else:
         out = sequence.run_pcw(lambda c_, B_, p_, P_: sequence.HipBackend(c_, B_, p_, P_, device=device), cfg, worlds, sims,
                                total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
-                               noise_vision_std=a.noise_vision_std, timers=timers)
+                               noise_vision_std=a.noise_vision_std, timers=timers, trajectory_log=a.traj_log)
         out["backend"].close()
     wall = time.perf_counter() - t0
     frames = len(out["ts"])
@@ -107,6 +121,7 @@ def main():
         "sequences": B, "n_gpus": world, "frames_per_sequence": frames, "imu_samples_per_frame": int(round(a.vision_dt / a.imu_dt)),
         "N": cfg.N, "max_features": cfg.n_features, "integration": a.integration_method, "host": a.host,
         "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
+        **_consistency(out),
         "updates": n_upd, "mh_rejected": n_rej,
         "wall_s": wall, "device_path_s": dev,
         "phase_s": {k: round(v, 4) for k, v in sorted(timers.items())},

@@ -3,6 +3,7 @@
 //   capi_update.hip     route table, measurement hand-over, the update pipelines, the L D L^T fallback, the one-filter call
 //   capi_glevel.hip     feature level: scene, Jacobians, gate, stacking, OOS rows, RANSAC, loop closure, Givens / QR, edits
 //   capi_propagate.hip  propagation
+//   capi_traj.hip       trajectory log: per-frame records, read-out, NEES against ground truth
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
 //
@@ -142,6 +143,12 @@ struct xivo_hip_ctx {
   double* init_z = nullptr;         // [Bmax]
   xivo_adapt_depth_opts adapt{};
   bool adapt_on = false;
+  // trajectory log (xivo_hip_traj_*, capi_traj.hip): [traj_T][Bmax] records and packed covariance blocks of traj_cols, frames
+  // [0, traj_n) written; null until xivo_hip_traj_config. traj_io: per-call staging of xivo_hip_traj_nees
+  xivo_traj_rec* traj_rec = nullptr; double* traj_cov = nullptr;
+  int traj_T = 0, traj_n = 0, traj_ncols = 0, traj_cols[XIVO_TRAJ_MAX_COLS] = {0};
+  std::vector<long long> traj_ts;
+  char* traj_io = nullptr; size_t traj_io_cap = 0;
   std::vector<char> hstage;                        // host staging of d2h_rows
   char* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
   // one-filter plumbing call (xivo_hip_update_joseph_host): page-locked, device-mapped staging block owned by the context,

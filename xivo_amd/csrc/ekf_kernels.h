@@ -1,5 +1,5 @@
 // Launchers of the EKF-specific (non-GEMM) kernels, one section per translation unit: state_kernels.hip,
-// glevel_kernels.hip, pool_kernels.hip, propagate_kernels.hip, then ldlt_fallback.hip and dropin.hip.
+// traj_kernels.hip, glevel_kernels.hip, pool_kernels.hip, propagate_kernels.hip, then ldlt_fallback.hip and dropin.hip.
 #pragma once
 #include "common.h"
 #include "ell.h"
@@ -58,6 +58,22 @@ struct AbsorbArgs {
 int launch_absorb_error(const AbsorbArgs& a, hipStream_t s);
 
 int launch_mfma_peak(double* sink, int iters, int blocks, hipStream_t s);
+
+// ================================================================ traj_kernels.hip: trajectory log (capi_traj.hip)
+
+// one frame of the log: rec / cov already point at the frame; pack = n_cols (n_cols + 1) / 2 doubles per filter
+struct TrajRecordArgs {
+  const xivo_pose_in* poses; const int* status; const double* P; long strideP; int ldp;
+  xivo_traj_rec* rec; double* cov; int n_cols, pack; int cols[XIVO_TRAJ_MAX_COLS];
+};
+int launch_traj_record(const TrajRecordArgs& a, int batch, hipStream_t s);
+// NEES of the slice frames [t0, t0 + nt) x filters [b0, b0 + nb) against gt [nt][nb][12]; pos6[k] = list position of
+// error-state column k; outputs err6 [nt][nb][6], nees [nt][nb], anees [nt], n_used [nt] (device)
+struct TrajNeesArgs {
+  const xivo_traj_rec* rec; const double* cov; int Bmax, pack, b0, nb, t0, nt; int pos6[6];
+  const double* gt; double* err6; double* nees; double* anees; int* n_used;
+};
+int launch_traj_nees(const TrajNeesArgs& a, hipStream_t s);
 
 // ================================================================ glevel_kernels.hip: feature-level kernels (capi_glevel.hip)
 

@@ -1,6 +1,6 @@
 // Device helpers of the per-feature 3x3 chains, shared by glevel_kernels.hip, pool_kernels.hip, state_kernels.hip and
 // propagate_kernels.hip: 3x3 / 2x3 products, SO3::hat, pixel projection, the per-filter camera of the online-calibration
-// builds and Feature::Xc / Feature::z.
+// builds and Feature::Xc / Feature::z; SO3 exp / log (state_kernels.hip: AbsorbError, traj_kernels.hip: the pose error).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "camera_device.h"
@@ -66,6 +66,53 @@ __device__ __forceinline__ M3 hat(const V3& w) {
   r.m[2][0] = -w.v[1]; r.m[2][1] = w.v[0]; r.m[2][2] = 0;
   return r;
 }
+// ---------------------------------------------------------------- SO3 exp / log
+// SO3::exp (Rodrigues), as SO3_from_rotvec (src/helpers.cpp:374-378)
+__device__ __forceinline__ M3 so3_exp_dev(double wx, double wy, double wz) {
+  const double th = sqrt(wx * wx + wy * wy + wz * wz);
+  const V3 w{{wx, wy, wz}};
+  const M3 W = hat(w), W2 = m3_mul(W, W);
+  const double a = th < 1e-10 ? 1.0 : sin(th) / th, b = th < 1e-10 ? 0.5 : (1.0 - cos(th)) / (th * th);
+  M3 R;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) R.m[i][j] = (i == j ? 1.0 : 0.0) + a * W.m[i][j] + b * W2.m[i][j];
+  return R;
+}
+// rotation matrix -> unit quaternion
+__device__ __forceinline__ void rot_to_quat(const M3& R, double q[4]) {   // (w, x, y, z), Shepperd's branch on the largest diagonal term
+  const double t = R.m[0][0] + R.m[1][1] + R.m[2][2];
+  if (t > 0.0) {
+    const double s = sqrt(t + 1.0) * 2.0;
+    q[0] = 0.25 * s; q[1] = (R.m[2][1] - R.m[1][2]) / s; q[2] = (R.m[0][2] - R.m[2][0]) / s; q[3] = (R.m[1][0] - R.m[0][1]) / s;
+  } else if (R.m[0][0] > R.m[1][1] && R.m[0][0] > R.m[2][2]) {
+    const double s = sqrt(1.0 + R.m[0][0] - R.m[1][1] - R.m[2][2]) * 2.0;
+    q[0] = (R.m[2][1] - R.m[1][2]) / s; q[1] = 0.25 * s; q[2] = (R.m[0][1] + R.m[1][0]) / s; q[3] = (R.m[0][2] + R.m[2][0]) / s;
+  } else if (R.m[1][1] > R.m[2][2]) {
+    const double s = sqrt(1.0 + R.m[1][1] - R.m[0][0] - R.m[2][2]) * 2.0;
+    q[0] = (R.m[0][2] - R.m[2][0]) / s; q[1] = (R.m[0][1] + R.m[1][0]) / s; q[2] = 0.25 * s; q[3] = (R.m[1][2] + R.m[2][1]) / s;
+  } else {
+    const double s = sqrt(1.0 + R.m[2][2] - R.m[0][0] - R.m[1][1]) * 2.0;
+    q[0] = (R.m[1][0] - R.m[0][1]) / s; q[1] = (R.m[0][2] + R.m[2][0]) / s; q[2] = (R.m[1][2] + R.m[2][1]) / s; q[3] = 0.25 * s;
+  }
+  const double n = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  q[0] *= n; q[1] *= n; q[2] *= n; q[3] *= n;
+}
+// Sophus SO3::log on the unit quaternion of R: the rotation vector w with exp(w) = R
+__device__ __forceinline__ V3 so3_log_dev(const M3& R) {
+  double q[4];
+  rot_to_quat(R, q);
+  const double n2 = q[1] * q[1] + q[2] * q[2] + q[3] * q[3], w = q[0];
+  double k;
+  if (n2 < 1e-20) k = 2.0 / w - 2.0 / 3.0 * n2 / (w * w * w);
+  else {
+    const double n = sqrt(n2);
+    k = fabs(w) < 1e-10 ? (w > 0.0 ? 3.141592653589793 / n : -3.141592653589793 / n) : 2.0 * atan(n / w) / n;
+  }
+  return V3{{k * q[1], k * q[2], k * q[3]}};
+}
+
 // 2x3 = (2x3) * (3x3)
 __device__ __forceinline__ void m23_mul(const double a[2][3], const M3& b, double out[2][3]) {
 #pragma unroll

@@ -207,19 +207,6 @@ __global__ __launch_bounds__(256) void edit_batch_kernel(EditArgs a) {
 }
 
 // ---------------------------------------------------------------- AbsorbError
-// SO3::exp (Rodrigues), as SO3_from_rotvec (src/helpers.cpp:374-378)
-__device__ __forceinline__ M3 so3_exp_dev(double wx, double wy, double wz) {
-  const double th = sqrt(wx * wx + wy * wy + wz * wz);
-  const V3 w{{wx, wy, wz}};
-  const M3 W = hat(w), W2 = m3_mul(W, W);
-  const double a = th < 1e-10 ? 1.0 : sin(th) / th, b = th < 1e-10 ? 0.5 : (1.0 - cos(th)) / (th * th);
-  M3 R;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) R.m[i][j] = (i == j ? 1.0 : 0.0) + a * W.m[i][j] + b * W2.m[i][j];
-  return R;
-}
 __device__ __forceinline__ void rot_retract(double* Rcm, double wx, double wy, double wz) {   // R <- R exp(w), column-major storage
   const M3 R = m3_mul(m3_from_colmajor(Rcm), so3_exp_dev(wx, wy, wz));
 #pragma unroll
@@ -230,24 +217,6 @@ __device__ __forceinline__ void rot_retract(double* Rcm, double wx, double wy, d
 // The periodic re-normalisation of State::operator+= (src/core.h:154-162, every kEnforceSO3Freq = 50 absorbs):
 // Sophus SO3::normalize() on Rsb / Rbc (unit quaternion; here: matrix -> quaternion -> normalise -> matrix, which
 // also re-orthonormalises the stored matrix) and Rsg <- exp(log(Rsg) with its z component zeroed).
-__device__ __forceinline__ void rot_to_quat(const M3& R, double q[4]) {   // (w, x, y, z), Shepperd's branch on the largest diagonal term
-  const double t = R.m[0][0] + R.m[1][1] + R.m[2][2];
-  if (t > 0.0) {
-    const double s = sqrt(t + 1.0) * 2.0;
-    q[0] = 0.25 * s; q[1] = (R.m[2][1] - R.m[1][2]) / s; q[2] = (R.m[0][2] - R.m[2][0]) / s; q[3] = (R.m[1][0] - R.m[0][1]) / s;
-  } else if (R.m[0][0] > R.m[1][1] && R.m[0][0] > R.m[2][2]) {
-    const double s = sqrt(1.0 + R.m[0][0] - R.m[1][1] - R.m[2][2]) * 2.0;
-    q[0] = (R.m[2][1] - R.m[1][2]) / s; q[1] = 0.25 * s; q[2] = (R.m[0][1] + R.m[1][0]) / s; q[3] = (R.m[0][2] + R.m[2][0]) / s;
-  } else if (R.m[1][1] > R.m[2][2]) {
-    const double s = sqrt(1.0 + R.m[1][1] - R.m[0][0] - R.m[2][2]) * 2.0;
-    q[0] = (R.m[0][2] - R.m[2][0]) / s; q[1] = (R.m[0][1] + R.m[1][0]) / s; q[2] = 0.25 * s; q[3] = (R.m[1][2] + R.m[2][1]) / s;
-  } else {
-    const double s = sqrt(1.0 + R.m[2][2] - R.m[0][0] - R.m[1][1]) * 2.0;
-    q[0] = (R.m[1][0] - R.m[0][1]) / s; q[1] = (R.m[0][2] + R.m[2][0]) / s; q[2] = (R.m[1][2] + R.m[2][1]) / s; q[3] = 0.25 * s;
-  }
-  const double n = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  q[0] *= n; q[1] *= n; q[2] *= n; q[3] *= n;
-}
 __device__ __forceinline__ void quat_to_colmajor(const double q[4], double* Rcm) {
   const double w = q[0], x = q[1], y = q[2], z = q[3];
   Rcm[0] = 1.0 - 2.0 * (y * y + z * z); Rcm[3] = 2.0 * (x * y - w * z);       Rcm[6] = 2.0 * (x * z + w * y);
@@ -260,16 +229,8 @@ __device__ __forceinline__ void rot_normalize(double* Rcm) {
   quat_to_colmajor(q, Rcm);
 }
 __device__ __forceinline__ void rot_zero_log_z(double* Rcm) {   // Sophus SO3::log on the unit quaternion, z <- 0, exp
-  double q[4];
-  rot_to_quat(m3_from_colmajor(Rcm), q);
-  const double n2 = q[1] * q[1] + q[2] * q[2] + q[3] * q[3], w = q[0];
-  double k;
-  if (n2 < 1e-20) k = 2.0 / w - 2.0 / 3.0 * n2 / (w * w * w);
-  else {
-    const double n = sqrt(n2);
-    k = fabs(w) < 1e-10 ? (w > 0.0 ? 3.141592653589793 / n : -3.141592653589793 / n) : 2.0 * atan(n / w) / n;
-  }
-  const M3 R = so3_exp_dev(k * q[1], k * q[2], 0.0);
+  const V3 w = so3_log_dev(m3_from_colmajor(Rcm));
+  const M3 R = so3_exp_dev(w.v[0], w.v[1], 0.0);
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll

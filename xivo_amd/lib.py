@@ -90,6 +90,13 @@ assert adapt_opts_dtype.itemsize == 40
 POOL_ADD_ADAPTIVE_Z = 1
 assert subfilter_dtype.itemsize == 144 and subfilter_opts_dtype.itemsize == 48
 assert feat_dtype.itemsize == 48 and pose_dtype.itemsize == 336 and group_dtype.itemsize == 96
+# trajectory log (include/xivo_hip.h): xivo_traj_opts, xivo_traj_rec
+TRAJ_MAX_COLS = 32
+ERR_FULL = -6
+traj_opts_dtype = np.dtype([("T_max", "i4"), ("n_cols", "i4"), ("cols", "i4", TRAJ_MAX_COLS)])
+traj_dtype = np.dtype([("Rsb", "f8", 9), ("Tsb", "f8", 3), ("Vsb", "f8", 3), ("bg", "f8", 3), ("ba", "f8", 3),
+                       ("status", "i4"), ("reserved", "i4")])
+assert traj_dtype.itemsize == 176 and traj_opts_dtype.itemsize == 136
 
 
 def lib_path():
@@ -186,6 +193,13 @@ _SIGS = {
     "xivo_hip_selftest_host_compress": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_selftest_glevel_launch": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int],
     "xivo_hip_selftest_ctx_allocs": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_traj_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_traj_record": [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p],
+    "xivo_hip_traj_count": [C.c_void_p],
+    "xivo_hip_traj_reset": [C.c_void_p],
+    "xivo_hip_traj_read": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_traj_nees": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.c_void_p],
 }
 HOST_P_RESIDENT, HOST_KEEP_P = 1, 2
 
@@ -286,11 +300,23 @@ class Context:
         self.h = h
         self.flags = flags
 
+    @classmethod
+    def borrow(cls, handle, N, M_max, batch):
+        """View of a context that someone else owns and destroys (xivo_batch_ctx of the C++ BatchEstimator): close() leaves
+        the handle alone."""
+        self = cls.__new__(cls)
+        self.lib = load_library()
+        self.N, self.M_max, self.batch = int(N), int(M_max), int(batch)
+        self.h, self.flags, self._borrowed = C.c_void_p(handle), 0, True
+        return self
+
     def _check(self, rc):
         if rc != 0:
             raise XivoHipError(rc, self.lib.xivo_hip_strerror(rc).decode())
 
     def close(self):
+        if getattr(self, "_borrowed", False):
+            self.h = None
         if getattr(self, "h", None):
             for p in getattr(self, "_dev_bufs", []):
                 self.lib.xivo_hip_dev_free(self.h, p)
@@ -768,6 +794,60 @@ class Context:
         dR = np.empty(M)
         self._check(self.lib.xivo_hip_get_H(self.h, b, None, _ptr(H), M, _ptr(inn), _ptr(dR)))
         return H.T.copy(), inn, dR
+
+    # ---- trajectory log (xivo_hip_traj_*)
+    def traj_config(self, T_max, cols=()):
+        """a device log of T_max frames: per frame and filter the motion state and the packed lower triangle of
+        P[cols, cols]; T_max = 0 releases it"""
+        cols = np.asarray(cols, dtype=np.int64).reshape(-1)
+        o = np.zeros(1, dtype=traj_opts_dtype)
+        o["T_max"], o["n_cols"] = int(T_max), cols.size
+        if cols.size <= TRAJ_MAX_COLS:
+            o["cols"][0, :cols.size] = np.clip(cols, -1, 2 ** 31 - 1)
+        self._check(self.lib.xivo_hip_traj_config(self.h, _ptr(o)))
+        self.traj_cols = cols.astype(np.int32) if T_max > 0 else None
+
+    def traj_record(self, ts_ns=0, B=None):
+        """append one frame (asynchronous) -> its index"""
+        k = C.c_int(-1)
+        self._check(self.lib.xivo_hip_traj_record(self.h, self.batch if B is None else int(B), int(ts_ns), C.byref(k)))
+        return k.value
+
+    def traj_count(self):
+        n = self.lib.xivo_hip_traj_count(self.h)
+        if n < 0:
+            self._check(n)
+        return n
+
+    def traj_reset(self):
+        self._check(self.lib.xivo_hip_traj_reset(self.h))
+
+    def traj_read(self, b0=0, nb=None, t0=0, nt=None):
+        """-> (recs [nt, nb] traj_dtype, cov [nt, nb, n, n] symmetric (from the packed lower triangle), ts [nt] ns)"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        nt = self.traj_count() - t0 if nt is None else int(nt)
+        n = int(self.traj_cols.size)
+        recs = np.zeros((nt, nb), dtype=traj_dtype)
+        packed = np.zeros((nt, nb, n * (n + 1) // 2))
+        ts = np.zeros(nt, dtype=np.int64)
+        self._check(self.lib.xivo_hip_traj_read(self.h, b0, nb, t0, nt, _ptr(recs), _ptr(packed), _ptr(ts)))
+        cov = np.zeros((nt, nb, n, n))
+        i, j = np.tril_indices(n)      # row by row: (i, j) at i (i + 1) / 2 + j
+        cov[:, :, i, j] = packed
+        cov[:, :, j, i] = packed
+        return recs, cov, ts
+
+    def traj_nees(self, gt_Rsb, gt_Tsb, b0=0, t0=0):
+        """gt_Rsb [nt, nb, 3, 3], gt_Tsb [nt, nb, 3]: the true poses of the slice -> (err6 [nt, nb, 6] = (log(R_est^T R_gt),
+        T_gt - T_est), nees [nt, nb] (NaN: block not positive definite), anees [nt], n_used [nt])"""
+        R = np.asarray(gt_Rsb, dtype=np.float64)
+        nt, nb = R.shape[:2]
+        gt = np.empty((nt, nb, 12))
+        gt[:, :, :9] = np.transpose(R, (0, 1, 3, 2)).reshape(nt, nb, 9)      # column-major
+        gt[:, :, 9:] = np.asarray(gt_Tsb, dtype=np.float64).reshape(nt, nb, 3)
+        err6 = np.zeros((nt, nb, 6)); nees = np.zeros((nt, nb)); anees = np.zeros(nt); used = np.zeros(nt, dtype=np.int32)
+        self._check(self.lib.xivo_hip_traj_nees(self.h, b0, nb, t0, nt, _ptr(gt), _ptr(err6), _ptr(nees), _ptr(anees), _ptr(used)))
+        return err6, nees, anees, used
 
     def propagate_cov(self, Phi, Pmm, b0=0):
         Phi = np.asarray(Phi, dtype=np.float64)

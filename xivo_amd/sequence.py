@@ -192,6 +192,26 @@ class SequenceConfig:
 
 
 L_CAM_PINHOLE = 0
+TRAJ_LOG_COLS = tuple(range(15))      # trajectory_log=True: the covariance block of Wsb, Tsb, Vsb, bg, ba
+
+
+def _trajectory(ctx):
+    recs, cov, ts = ctx.traj_read()
+    n, B = recs.shape
+    return dict(ts=ts, Rsb=recs["Rsb"].reshape(n, B, 3, 3).transpose(0, 1, 3, 2).copy(), Tsb=recs["Tsb"].copy(),
+                Vsb=recs["Vsb"].copy(), bg=recs["bg"].copy(), ba=recs["ba"].copy(), status=recs["status"].copy(), cov=cov,
+                cols=ctx.traj_cols.copy())
+
+
+def _traj_cols(trajectory_log):
+    return TRAJ_LOG_COLS if trajectory_log is True else tuple(int(c) for c in trajectory_log)
+
+
+def _score(ctx, traj, gt_R, gt_T, out):
+    """NEES of the logged poses against the simulator's ground truth (xivo_hip_traj_nees), when the pose block is logged"""
+    out["trajectory"] = traj
+    if set(range(6)) <= set(int(c) for c in traj["cols"]):
+        out["err6"], out["nees"], out["anees"], out["nees_used"] = ctx.traj_nees(gt_R, gt_T)
 
 
 class HipBackend:
@@ -289,6 +309,20 @@ class HipBackend:
     def poses(self):
         p, _, _ = self.ctx.get_scene()
         return p["Rsb"].reshape(-1, 3, 3).transpose(0, 2, 1).copy(), p["Tsb"].copy()
+
+    def enable_trajectory_log(self, T_max, cols=None):
+        """device log of T_max frames (xivo_hip_traj_config); cols: the error-state columns whose covariance block is kept
+        (default: the motion state Wsb Tsb Vsb bg ba)"""
+        self.ctx.traj_config(T_max, TRAJ_LOG_COLS if cols is None else cols)
+
+    def record(self, ts):
+        """append the current estimate of every filter to the log (one launch, no synchronisation); ts in ns"""
+        return self.ctx.traj_record(ts, self.B)
+
+    def trajectory(self):
+        """the whole log in one read -> dict(ts [n] ns, Rsb [n, B, 3, 3], Tsb / Vsb / bg / ba [n, B, 3], status [n, B],
+        cov [n, B, k, k], cols [k])"""
+        return _trajectory(self.ctx)
 
     def covariance(self):
         return self.ctx.download_P()
@@ -597,9 +631,12 @@ def initial_poses(cfg, sims, t0=0.0):
 
 
 def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0,
-            timers=None):
+            timers=None, trajectory_log=False):
     """The loop of scripts/pyxivo_pcw.py:117-163 for B = len(sims) sequences at once.
-    -> dict(ts [n] ns, Tsb [n x B x 3], Wsb [n x B x 3], gt_Tsb [n x B x 3], runner, backend)"""
+    -> dict(ts [n] ns, Tsb [n x B x 3], Wsb [n x B x 3], gt_Tsb [n x B x 3], runner, backend)
+    trajectory_log (True, or the error-state columns to keep): the estimate of every frame is recorded on the device
+    (HipBackend.record) and read once at the end instead of a scene download per frame - the same Tsb / Wsb, plus
+    `trajectory` (HipBackend.trajectory) and, with the pose columns logged, err6 / nees / anees / nees_used."""
     B = len(sims)
     K = np.array([[cfg.cam["fx"], 0, cfg.cam["cx"]], [0, cfg.cam["fy"], cfg.cam["cy"]], [0, 0, 1.0]])
     Rbc = so3_exp(cfg.Wbc)
@@ -611,7 +648,9 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     m0 = [s.meas(0.0) for s in sims]
     feeder = ImuFeeder(B, 0.0, [m[1] for m in m0], [m[0] for m in m0])
     n_imu = int(round(total_time / imu_dt)); every = int(round(vision_dt / imu_dt))
-    ts, est_T, est_W, gt_T = [], [], [], []
+    ts, est_T, est_W, gt_T, gt_R = [], [], [], [], []
+    if trajectory_log:
+        be.enable_trajectory_log((n_imu + every - 1) // every, _traj_cols(trajectory_log))
     for k in range(n_imu):
         t = k * imu_dt
         if k > 0:
@@ -625,11 +664,21 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
                 tracks.append(worlds[b].generate_measurements(Rsb @ Rbc, Rsb @ cfg.Tbc + Tsb, K, cfg.cam["cols"],
                                                               cfg.cam["rows"], noise_vision_std))
             runner.frame(feeder.take(), tracks)
-            R, T = be.poses()
-            ts.append(int(round(t * 1e9))); est_T.append(T); est_W.append(np.array([so3_log(r) for r in R]))
+            ts.append(int(round(t * 1e9)))
+            if trajectory_log:
+                be.record(ts[-1])
+                gt_R.append(np.array([s.gsb(t)[0] for s in sims]))
+            else:
+                R, T = be.poses()
+                est_T.append(T); est_W.append(np.array([so3_log(r) for r in R]))
             gt_T.append(np.array([s.gsb(t)[1] for s in sims]))
-    return dict(ts=np.array(ts), Tsb=np.array(est_T), Wsb=np.array(est_W), gt_Tsb=np.array(gt_T), runner=runner,
-                backend=be)
+    out = dict(ts=np.array(ts), gt_Tsb=np.array(gt_T), runner=runner, backend=be)
+    if trajectory_log:
+        traj = be.trajectory()
+        est_T, est_W = traj["Tsb"], [[so3_log(r) for r in R] for R in traj["Rsb"]]
+        _score(be.ctx, traj, np.array(gt_R), out["gt_Tsb"], out)
+    out["Tsb"], out["Wsb"] = np.array(est_T), np.array(est_W)
+    return out
 
 
 def run_pcw_cpp(cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0, device=0):
@@ -661,9 +710,11 @@ def run_pcw_cpp(cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04
 
 
 def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0, npts=1000, seed=0, device=0,
-                  timers=None):
+                  timers=None, trajectory_log=False):
     """Thousands of sequences end to end: the vectorised simulators of xivo_amd/pcw.py (BatchTrajectorySim, BatchPCW) feed
-    xivo::hip::BatchEstimator message by message. -> dict(ts, Tsb [n x B x 3], gt_Tsb, estimator)"""
+    xivo::hip::BatchEstimator message by message. -> dict(ts, Tsb [n x B x 3], gt_Tsb, estimator)
+    trajectory_log: as in run_pcw - one record launch per frame on the estimator's context and one read at the end instead of
+    a pose download per frame; adds `trajectory` and err6 / nees / anees / nees_used."""
     import time
     from .batch import BatchEstimator
     from .pcw import BatchPCW, BatchTrajectorySim
@@ -680,7 +731,11 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     est = BatchEstimator(cfg, B, poses, cfg.P_init(), device=device)
     host = est.host
     n_imu = int(round(total_time / imu_dt)); every = int(round(vision_dt / imu_dt))
-    ts, est_T, gt_T = [], [], []
+    ts, est_T, gt_T, gt_R = [], [], [], []
+    ctx = None
+    if trajectory_log:      # the estimator's own context (it stays the owner)
+        ctx = L.Context.borrow(host.xivo_batch_ctx(est.h), cfg.N, 2 * cfg.n_features, B)
+        ctx.traj_config((n_imu + every - 1) // every, _traj_cols(trajectory_log))
     tm = timers if timers is not None else {}
     for k in range(n_imu):
         t = k * imu_dt
@@ -699,5 +754,15 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
             if host.xivo_batch_visual(est.h, float(t), off.ctypes.data, ids.ctypes.data, meas.ctypes.data, mask.ctypes.data) != 0:
                 raise RuntimeError("VisualMeasPointCloud failed")
             tm["frame"] = tm.get("frame", 0.0) + time.perf_counter() - t1
-            ts.append(int(round(t * 1e9))); est_T.append(est.poses()["Tsb"].copy()); gt_T.append(Tsb)
-    return dict(ts=np.array(ts), Tsb=np.array(est_T), gt_Tsb=np.array(gt_T), estimator=est)
+            ts.append(int(round(t * 1e9))); gt_T.append(Tsb)
+            if ctx is not None:
+                ctx.traj_record(ts[-1], B); gt_R.append(Rsb)
+            else:
+                est_T.append(est.poses()["Tsb"].copy())
+    out = dict(ts=np.array(ts), gt_Tsb=np.array(gt_T), estimator=est)
+    if ctx is not None:
+        traj = _trajectory(ctx)
+        est_T = traj["Tsb"]
+        _score(ctx, traj, np.array(gt_R), out["gt_Tsb"], out)
+    out["Tsb"] = np.array(est_T)
+    return out
