@@ -39,7 +39,7 @@ enum {
   XIVO_HIP_ERR_NOT_SPD = -3,     /* S = HPH^T + R not positive definite         */
   XIVO_HIP_ERR_NOMEM = -4,
   XIVO_HIP_ERR_UNSUPPORTED = -5, /* size outside what the kernels are built for */
-  XIVO_HIP_ERR_FULL = -6         /* the trajectory log holds T_max frames       */
+  XIVO_HIP_ERR_FULL = -6         /* the trajectory / landmark log holds T_max frames */
 };
 
 /* flags for xivo_hip_create / stacking */
@@ -697,6 +697,67 @@ int xivo_hip_traj_read(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, xivo_t
  * log return the same bits. Outputs (host, any may be NULL): err6 [nt][nb][6], nees [nt][nb], anees [nt], n_used [nt]. */
 int xivo_hip_traj_nees(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, const double* gt, double* err6, double* nees,
                        double* anees, int* n_used);
+
+/* ---- landmark log: each frame's in-state features, their world positions and covariances, recorded on the device ----
+ * The other half of a frame's answer next to the trajectory log: what Estimator::InstateFeaturePositionsAndCovs
+ * (src/estimator_accessors.cpp:308-357) returns for one filter - the in-state features ordered by FeatureCovComparison
+ * (src/estimator.cpp:1451-1455: the Frobenius norm of the feature's 3 x 3 block of P_), for the best n the world position Xs,
+ * that block, the last pixel - for every filter of the context, without moving the scene or the N x N covariance to the host.
+ * The block of P_ is in the feature's local coordinates (X/Z, Y/Z, log Z) of its anchor camera and cannot be compared with a
+ * world point; XIVO_MAP_WORLD_COV adds the covariance of Xs itself. Device memory [T_max][batch_max][n_out] that one kernel
+ * launch per frame appends to; nothing is allocated until the log is configured. Layouts with more than XIVO_MAP_MAX_OUT
+ * feature slots (n_features), or a resident feature list longer than that: XIVO_HIP_ERR_UNSUPPORTED. */
+#define XIVO_MAP_MAX_OUT 128
+enum { XIVO_MAP_WORLD_COV = 1u };
+typedef struct {
+  int T_max;        /* frames the log holds; 0 releases it (n_out / flags are then not read)       */
+  int n_out;        /* entries kept per filter and frame, 1 .. XIVO_MAP_MAX_OUT                      */
+  unsigned flags;   /* XIVO_MAP_*                                                                    */
+} xivo_map_opts;
+typedef struct {
+  double Xs[3];          /* Feature::Xs (src/feature.cpp:107-112): Rsb_g (Rbc Xc(x) + Tbc) + Tsb_g, g = the feature's anchor group */
+  double cov_local[6];   /* P block at feature_begin + 3 sind: (0,0),(0,1),(0,2),(1,1),(1,2),(2,2), as the reference packs
+                            it; entry (r, c) read from the LOWER triangle of the stored P, P[off + c, off + r]                 */
+  double cov_world[6];   /* same packing, J Pcc J^T (below); zeros without XIVO_MAP_WORLD_COV                                  */
+  double xp[2];          /* last pixel                                                                                         */
+  double score;          /* Frobenius norm of the 3 x 3 local block as stored (all nine entries; FeatureCovComparison's key)   */
+  int pos, sind, ref_sind, reserved;   /* position in the resident feature list, feature slot, anchor group slot               */
+} xivo_map_pt;
+/* (Re-)allocates the log through the context's owner and empties it: T_max frames of batch_max x n_out entries and of
+ * batch_max counts. n_out outside 1 .. XIVO_MAP_MAX_OUT, unknown flags, no layout yet or a size that overflows:
+ * XIVO_HIP_ERR_INVALID, and the log is left as it was. */
+int xivo_hip_map_config(xivo_hip_ctx* ctx, const xivo_map_opts* opts);
+/* Appends one frame for filters [0, B), B <= batch_max: one launch on the context's stream, ordered after everything enqueued
+ * before it, no synchronisation. Every entry of the resident feature list with sind >= 0 is a candidate, at whatever point of
+ * the frame the driver calls this. ORDER: ascending score, ties by ascending pos (a score that is NaN sorts as +infinity).
+ * The reference's comparator is `<=`, not a strict order, so what std::sort does with equal keys there is unspecified; this
+ * rule is deterministic. The first n_pts = min(count, n_out) entries are kept; the slots behind them are written as zeros
+ * with pos = sind = -1, so a read never returns stale memory.
+ * With XIVO_MAP_WORLD_COV: c = the 15 error-state columns Xs depends on - Wbc (15..17), Tbc (18..20), the anchor group's six at
+ * group_begin + 6 ref_sind (Wsb_g, Tsb_g), the feature's three at feature_begin + 3 sind; the calibration columns of an
+ * online-calibration context do not enter Xs. Pcc = P[c, c] from the lower triangle, mirrored. J (3 x 15) = dXs / d(error
+ * state) under the retraction the absorb call applies (R <- R exp(w), T <- T + dT, x <- x + dx), with Xb = Rbc Xc + Tbc:
+ *   [ -Rsb_g Rbc hat(Xc) | Rsb_g | -Rsb_g hat(Xb) | I | Rsb_g Rbc dXc/dx ]
+ * (dXc/dx of (X/Z, Y/Z, log Z), or of (X/Z, Y/Z, 1/Z) under XIVO_HIP_FLAG_INVDEPTH). cov_world = J Pcc J^T.
+ * ts_ns is kept on the host. frame_out (may be NULL) receives the frame's index. Log full: XIVO_HIP_ERR_FULL, nothing is
+ * written or launched. Not configured, no scene yet, or B out of range: XIVO_HIP_ERR_INVALID. */
+int xivo_hip_map_record(xivo_hip_ctx* ctx, int B, long long ts_ns, int* frame_out);
+/* frames recorded so far (negative: a status) */
+int xivo_hip_map_count(xivo_hip_ctx* ctx);
+/* count <- 0; the memory and the configuration are kept */
+int xivo_hip_map_reset(xivo_hip_ctx* ctx);
+/* Frames [t0, t0 + nt) (all recorded) of filters [b0, b0 + nb) to host arrays, frame-major: pts [nt][nb][n_out],
+ * n_pts [nt][nb], ts [nt]. A NULL pointer skips that part. One synchronisation. */
+int xivo_hip_map_read(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, xivo_map_pt* pts, int* n_pts, long long* ts);
+/* Consistency of the logged landmarks against true world points, on the device; needs a log configured with
+ * XIVO_MAP_WORLD_COV (else XIVO_HIP_ERR_INVALID). gt: host [nt][nb][n_out][3], the true point of every slot of the slice; a NaN
+ * means no truth for that entry. Per recorded entry with finite truth: e = gt - Xs, Sigma = cov_world = L L^T (un-pivoted 3 x 3
+ * Cholesky), nees = |L^-1 e|^2; a Sigma that is not positive definite gives NaN; slots behind n_pts and entries without truth
+ * give NaN (err3 too). anees[t] is the mean of the finite nees of frame t0 + t over filters and entries, n_used[t] their
+ * number (0: anees NaN); it is summed in a fixed order, so two calls on the same log return the same bits. Outputs (host, any
+ * may be NULL): err3 [nt][nb][n_out][3], nees [nt][nb][n_out], anees [nt], n_used [nt]. */
+int xivo_hip_map_nees(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, const double* gt, double* err3, double* nees,
+                      double* anees, int* n_used);
 
 /* ---- resident state edits between updates, batched over filters ----
  * The reference edits X_/P_ one filter at a time on the host (the functions cited per kind). A sequence driver that

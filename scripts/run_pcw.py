@@ -15,10 +15,13 @@ from xivo_amd import formats, pcw, sequence  # noqa: E402
 def _consistency(out):
     """-traj-log: mean over the frames of the ensemble-mean pose NEES (6 for a consistent filter), and how many (frame,
     sequence) entries had a covariance block that was not positive definite (this rank's sequences)"""
-    if "anees" not in out:
-        return {}
-    return {"anees_pose": float(np.nanmean(out["anees"])),
-            "nees_not_spd": int(out["nees"].size - out["nees_used"].sum())}
+    rep = {}
+    if "anees" in out:
+        rep.update({"anees_pose": float(np.nanmean(out["anees"])),
+                    "nees_not_spd": int(out["nees"].size - out["nees_used"].sum())})
+    if "anees_landmark" in out:      # -map-log: 3 for a consistent map; landmarks scored per sequence and frame
+        rep.update({"anees_landmark": out["anees_landmark"], "landmarks_scored_mean": out["landmarks_scored_mean"]})
+    return rep
 
 
 def main():
@@ -42,6 +45,11 @@ def main():
                     help="record every frame's estimate and motion-state covariance on the device (one read at the end) and "
                          "report anees_pose: the 6-dof pose NEES against the simulator's ground truth, ensemble mean per frame, "
                          "averaged over the frames (-host python and -vectorized)")
+    ap.add_argument("-map-log", dest="map_log", action="store_true",
+                    help="record every frame's in-state features, their world positions and covariances on the device (one read "
+                         "at the end) and report anees_landmark: the 3-dof NEES of the world points against the simulator's, "
+                         "ensemble mean per frame averaged over the frames, and the mean number of landmarks scored per "
+                         "sequence and frame (-host python and -vectorized)")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         from xivo_amd.shard import spawn_ranks
@@ -51,7 +59,8 @@ def main():
         tm = {}
         t0 = time.perf_counter()
         out = sequence.run_pcw_batch(cfg, a.sequences, total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
-                                     noise_vision_std=a.noise_vision_std, npts=a.npts, timers=tm, trajectory_log=a.traj_log)
+                                     noise_vision_std=a.noise_vision_std, npts=a.npts, timers=tm, trajectory_log=a.traj_log,
+                                     map_log=a.map_log)
         wall = time.perf_counter() - t0
         st = out["estimator"].stats(); out["estimator"].close()
         frames = len(out["ts"])
@@ -96,7 +105,8 @@ def main():
     else:
         out = sequence.run_pcw(lambda c_, B_, p_, P_: sequence.HipBackend(c_, B_, p_, P_, device=device), cfg, worlds, sims,
                                total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
-                               noise_vision_std=a.noise_vision_std, timers=timers, trajectory_log=a.traj_log)
+                               noise_vision_std=a.noise_vision_std, timers=timers, trajectory_log=a.traj_log,
+                               map_log=a.map_log)
         out["backend"].close()
     wall = time.perf_counter() - t0
     frames = len(out["ts"])

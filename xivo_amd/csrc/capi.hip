@@ -1,6 +1,6 @@
 // C ABI of the MI355X EKF measurement-update path (include/xivo_hip.h): the context, P residency, resident device buffers,
 // timing / profile, and the host helpers every part of the ABI shares (capi_internal.h). The update pipelines are in
-// capi_update.hip, the feature level in capi_glevel.hip, propagation in capi_propagate.hip, the trajectory log in capi_traj.hip. Host-side orchestration only:
+// capi_update.hip, the feature level in capi_glevel.hip, propagation in capi_propagate.hip, the trajectory log in capi_traj.hip, the landmark log in capi_map.hip. Host-side orchestration only:
 // owns the device buffers of a batch of filters, sequences the kernels on one HIP stream, never throws and never aborts.
 #include <new>
 
@@ -153,7 +153,7 @@ const char* xivo_hip_strerror(int s) {
     case XIVO_HIP_ERR_NOT_SPD: return "innovation covariance S is not positive definite";
     case XIVO_HIP_ERR_NOMEM: return "out of device memory";
     case XIVO_HIP_ERR_UNSUPPORTED: return "size not supported by the compiled kernels";
-    case XIVO_HIP_ERR_FULL: return "trajectory log is full";
+    case XIVO_HIP_ERR_FULL: return "the log is full (trajectory / landmark log)";
     default: return "unknown status";
   }
 }

@@ -4,6 +4,7 @@
 //   capi_glevel.hip     feature level: scene, Jacobians, gate, stacking, OOS rows, RANSAC, loop closure, Givens / QR, edits
 //   capi_propagate.hip  propagation
 //   capi_traj.hip       trajectory log: per-frame records, read-out, NEES against ground truth
+//   capi_map.hip        landmark log: per-frame in-state features, world positions and covariances, read-out, landmark NEES
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
 //
@@ -149,6 +150,12 @@ struct xivo_hip_ctx {
   int traj_T = 0, traj_n = 0, traj_ncols = 0, traj_cols[XIVO_TRAJ_MAX_COLS] = {0};
   std::vector<long long> traj_ts;
   char* traj_io = nullptr; size_t traj_io_cap = 0;
+  // landmark log (xivo_hip_map_*, capi_map.hip): [map_T][Bmax][map_nout] entries and [map_T][Bmax] counts, frames [0, map_n)
+  // written; null until xivo_hip_map_config. map_io: per-call staging of xivo_hip_map_nees
+  xivo_map_pt* map_pts = nullptr; int* map_npts = nullptr;
+  int map_T = 0, map_n = 0, map_nout = 0; unsigned map_flags = 0;
+  std::vector<long long> map_ts;
+  char* map_io = nullptr; size_t map_io_cap = 0;
   std::vector<char> hstage;                        // host staging of d2h_rows
   char* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
   // one-filter plumbing call (xivo_hip_update_joseph_host): page-locked, device-mapped staging block owned by the context,

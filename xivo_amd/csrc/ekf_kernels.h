@@ -1,5 +1,5 @@
 // Launchers of the EKF-specific (non-GEMM) kernels, one section per translation unit: state_kernels.hip,
-// traj_kernels.hip, glevel_kernels.hip, pool_kernels.hip, propagate_kernels.hip, then ldlt_fallback.hip and dropin.hip.
+// traj_kernels.hip, map_kernels.hip, glevel_kernels.hip, pool_kernels.hip, propagate_kernels.hip, then ldlt_fallback.hip and dropin.hip.
 #pragma once
 #include "common.h"
 #include "ell.h"
@@ -74,6 +74,24 @@ struct TrajNeesArgs {
   const double* gt; double* err6; double* nees; double* anees; int* n_used;
 };
 int launch_traj_nees(const TrajNeesArgs& a, hipStream_t s);
+
+// ================================================================ map_kernels.hip: landmark log (capi_map.hip)
+
+// one frame of the log: pts / n_pts already point at the frame ([batch][n_out] entries, [batch] counts). F = length of the
+// resident feature list (<= XIVO_MAP_MAX_OUT), world = XIVO_MAP_WORLD_COV
+struct MapRecordArgs {
+  const xivo_pose_in* poses; const xivo_group_in* groups; const xivo_feat_in* feats; int F, Fmax;
+  const double* P; long strideP; int ldp; xivo_layout lay; int invdepth, world;
+  xivo_map_pt* pts; int* n_pts; int n_out;
+};
+int launch_map_record(const MapRecordArgs& a, int batch, hipStream_t s);
+// NEES of the slice frames [t0, t0 + nt) x filters [b0, b0 + nb) x n_out slots against gt [nt][nb][n_out][3]; outputs
+// err3 [nt][nb][n_out][3] (may be null), nees [nt][nb][n_out], anees [nt], n_used [nt] (device)
+struct MapNeesArgs {
+  const xivo_map_pt* pts; const int* n_pts; int Bmax, n_out, b0, nb, t0, nt;
+  const double* gt; double* err3; double* nees; double* anees; int* n_used;
+};
+int launch_map_nees(const MapNeesArgs& a, hipStream_t s);
 
 // ================================================================ glevel_kernels.hip: feature-level kernels (capi_glevel.hip)
 

@@ -97,6 +97,13 @@ traj_opts_dtype = np.dtype([("T_max", "i4"), ("n_cols", "i4"), ("cols", "i4", TR
 traj_dtype = np.dtype([("Rsb", "f8", 9), ("Tsb", "f8", 3), ("Vsb", "f8", 3), ("bg", "f8", 3), ("ba", "f8", 3),
                        ("status", "i4"), ("reserved", "i4")])
 assert traj_dtype.itemsize == 176 and traj_opts_dtype.itemsize == 136
+# landmark log (include/xivo_hip.h): xivo_map_opts, xivo_map_pt
+MAP_MAX_OUT = 128
+MAP_WORLD_COV = 1
+map_opts_dtype = np.dtype([("T_max", "i4"), ("n_out", "i4"), ("flags", "u4")])
+map_pt_dtype = np.dtype([("Xs", "f8", 3), ("cov_local", "f8", 6), ("cov_world", "f8", 6), ("xp", "f8", 2), ("score", "f8"),
+                         ("pos", "i4"), ("sind", "i4"), ("ref_sind", "i4"), ("reserved", "i4")])
+assert map_pt_dtype.itemsize == 160 and map_opts_dtype.itemsize == 12
 
 
 def lib_path():
@@ -200,6 +207,13 @@ _SIGS = {
     "xivo_hip_traj_read": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_traj_nees": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                            C.c_void_p],
+    "xivo_hip_map_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_map_record": [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p],
+    "xivo_hip_map_count": [C.c_void_p],
+    "xivo_hip_map_reset": [C.c_void_p],
+    "xivo_hip_map_read": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_map_nees": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                          C.c_void_p],
 }
 HOST_P_RESIDENT, HOST_KEEP_P = 1, 2
 
@@ -848,6 +862,53 @@ class Context:
         err6 = np.zeros((nt, nb, 6)); nees = np.zeros((nt, nb)); anees = np.zeros(nt); used = np.zeros(nt, dtype=np.int32)
         self._check(self.lib.xivo_hip_traj_nees(self.h, b0, nb, t0, nt, _ptr(gt), _ptr(err6), _ptr(nees), _ptr(anees), _ptr(used)))
         return err6, nees, anees, used
+
+    # ---- landmark log (xivo_hip_map_*)
+    def map_config(self, T_max, n_out=0, world_cov=True):
+        """a device log of T_max frames: per frame and filter the best n_out in-state features (ascending norm of the local
+        covariance block, ties by list position) with world position, local block, pixel and - world_cov - the covariance
+        of the world position; T_max = 0 releases it"""
+        o = np.zeros(1, dtype=map_opts_dtype)
+        o["T_max"], o["n_out"], o["flags"] = int(T_max), int(n_out), MAP_WORLD_COV if world_cov else 0
+        self._check(self.lib.xivo_hip_map_config(self.h, _ptr(o)))
+        self.map_n_out = int(n_out) if T_max > 0 else None
+
+    def map_record(self, ts_ns=0, B=None):
+        """append one frame (asynchronous) -> its index"""
+        k = C.c_int(-1)
+        self._check(self.lib.xivo_hip_map_record(self.h, self.batch if B is None else int(B), int(ts_ns), C.byref(k)))
+        return k.value
+
+    def map_count(self):
+        n = self.lib.xivo_hip_map_count(self.h)
+        if n < 0:
+            self._check(n)
+        return n
+
+    def map_reset(self):
+        self._check(self.lib.xivo_hip_map_reset(self.h))
+
+    def map_read(self, b0=0, nb=None, t0=0, nt=None):
+        """-> (pts [nt, nb, n_out] map_pt_dtype, n_pts [nt, nb], ts [nt] ns); slots behind n_pts are zeros with pos = sind = -1"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        nt = self.map_count() - t0 if nt is None else int(nt)
+        pts = np.zeros((nt, nb, self.map_n_out), dtype=map_pt_dtype)
+        n_pts = np.zeros((nt, nb), dtype=np.int32)
+        ts = np.zeros(nt, dtype=np.int64)
+        self._check(self.lib.xivo_hip_map_read(self.h, b0, nb, t0, nt, _ptr(pts), _ptr(n_pts), _ptr(ts)))
+        return pts, n_pts, ts
+
+    def map_nees(self, gt, b0=0, t0=0):
+        """gt [nt, nb, n_out, 3]: the true world point of every slot of the slice (NaN: none) -> (err3 [nt, nb, n_out, 3] =
+        gt - Xs, nees [nt, nb, n_out] (NaN: no entry, no truth, covariance not positive definite), anees [nt], n_used [nt])"""
+        gt = _f64(gt)
+        nt, nb, n_out = gt.shape[:3]
+        if n_out != self.map_n_out or gt.shape[3:] != (3,):
+            raise ValueError("gt must be [nt, nb, n_out, 3]")
+        err3 = np.zeros((nt, nb, n_out, 3)); nees = np.zeros((nt, nb, n_out)); anees = np.zeros(nt)
+        used = np.zeros(nt, dtype=np.int32)
+        self._check(self.lib.xivo_hip_map_nees(self.h, b0, nb, t0, nt, _ptr(gt), _ptr(err3), _ptr(nees), _ptr(anees), _ptr(used)))
+        return err3, nees, anees, used
 
     def propagate_cov(self, Phi, Pmm, b0=0):
         Phi = np.asarray(Phi, dtype=np.float64)

@@ -322,6 +322,29 @@ class Estimator:
         P = self.P(); fb = 23 + 6 * self.cfg.n_groups
         return np.array([P[fb + 3 * j:fb + 3 * j + 3, fb + 3 * j:fb + 3 * j + 3].reshape(-1) for j in self._slots()]).reshape(-1, 9)[:n_output]
 
+    def InstateFeaturePositionsAndCovs(self, max_output):
+        """Estimator::InstateFeaturePositionsAndCovs (src/estimator_accessors.cpp:308-357): the in-state features ordered by
+        the norm of their 3 x 3 block of P (FeatureCovComparison; ties by list position here - the reference's `<=` leaves
+        them unspecified), the best npts = min(count, max_output) of them -> (npts, positions [npts, 3] = Xs, covs [npts, 6] =
+        the block's (0,0),(0,1),(0,2),(1,1),(1,2),(2,2), last_px [npts, 2], ids [npts]). One record of a one-frame landmark
+        log on the device (xivo_hip_map_record) - neither the scene nor P comes to the host. More than 128 are not returned."""
+        self._flush()
+        n_out = min(int(max_output), L.MAP_MAX_OUT)
+        if n_out <= 0 or not self._vision:
+            return 0, np.zeros((0, 3)), np.zeros((0, 6)), np.zeros((0, 2)), np.zeros(0, dtype=np.int64)
+        ctx = self._be.ctx
+        if getattr(self, "_map_n_out", None) != n_out:
+            ctx.map_config(1, n_out, world_cov=False)
+            self._map_n_out = n_out
+        ctx.map_reset()
+        ctx.map_record(self._ts, 1)
+        pts, n_pts, _ = ctx.map_read()
+        n = int(n_pts[0, 0])
+        p = pts[0, 0, :n]
+        bk = self._runner.books[0]
+        ids = np.array([bk.feat_id[j] for j in p["pos"]], dtype=np.int64)
+        return n, p["Xs"].copy(), p["cov_local"].copy(), p["xp"].copy(), ids
+
     def _gslots(self):
         return [g for g, r in enumerate(self._runner.books[0].group_refs) if r >= 0]
 

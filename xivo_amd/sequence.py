@@ -214,6 +214,57 @@ def _score(ctx, traj, gt_R, gt_T, out):
         out["err6"], out["nees"], out["anees"], out["nees_used"] = ctx.traj_nees(gt_R, gt_T)
 
 
+def truth_by_track(world_ids, world_Xs, fid):
+    """world points of the tracks in fid [B, F] (-1: none) -> [B, F, 3], NaN where the track is not a currently visible point.
+    world_ids [B, npts] (-1: not tracked) / world_Xs [B, npts, 3] as RandomPCW / BatchPCW keep them: a visible point holds its
+    track id, ids start at 10000 and count up per world."""
+    world_ids = np.asarray(world_ids); fid = np.asarray(fid)
+    B = fid.shape[0]
+    base = 10000
+    top = int(max(world_ids.max(initial=base - 1), fid.max(initial=base - 1))) - base + 1
+    lut = np.full((B, max(top, 1)), -1, dtype=np.int64)
+    bi, pi = np.nonzero(world_ids >= base)
+    lut[bi, world_ids[bi, pi] - base] = pi
+    have = fid >= base
+    pt = np.where(have, lut[np.arange(B)[:, None], np.where(have, fid - base, 0)], -1)
+    out = np.full(fid.shape + (3,), np.nan)
+    ok = pt >= 0
+    out[ok] = np.asarray(world_Xs)[np.nonzero(ok)[0], pt[ok]]
+    return out
+
+
+class _MapLog:
+    """Host side of the landmark log of a run: per frame the slot book (track id by list position) and the simulator's world
+    point of each; at the end one read of the device log, ids and truth translated through (pos), and the landmark NEES."""
+
+    def __init__(self, ctx, T_max, n_out, B):
+        self.ctx, self.B = ctx, B
+        ctx.map_config(T_max, n_out, world_cov=True)
+        self.fid, self.gt = [], []
+
+    def record(self, ts, fid, world_ids, world_Xs):
+        """fid [B, F]: the slot book after the frame (position in the resident feature list -> track id, -1: free)"""
+        self.ctx.map_record(ts, self.B)
+        fid = np.asarray(fid, dtype=np.int64)
+        self.fid.append(fid); self.gt.append(truth_by_track(world_ids, world_Xs, fid))
+
+    def finish(self, out):
+        pts, n_pts, ts = self.ctx.map_read()
+        fid, gtp = np.array(self.fid), np.array(self.gt)                  # [n, B, F], [n, B, F, 3]
+        pos = pts["pos"]
+        t, b = np.arange(pos.shape[0])[:, None, None], np.arange(pos.shape[1])[None, :, None]
+        ids = np.where(pos >= 0, fid[t, b, np.maximum(pos, 0)], -1)
+        gt = np.where((pos >= 0)[..., None], gtp[t, b, np.maximum(pos, 0)], np.nan)
+        err3, nees, anees, used = self.ctx.map_nees(gt)
+        out["map"] = dict(ts=ts, pts=pts, n_pts=n_pts, ids=ids, gt=gt)
+        out["landmark_err3"], out["landmark_nees"], out["landmark_anees"], out["landmarks_used"] = err3, nees, anees, used
+        scored = used > 0
+        # mean over the frames that scored any landmark of the frame's ensemble mean (3 for a consistent map); landmarks
+        # scored per sequence and frame
+        out["anees_landmark"] = float(np.mean(anees[scored])) if scored.any() else float("nan")
+        out["landmarks_scored_mean"] = float(used.mean() / self.B) if used.size else 0.0
+
+
 class HipBackend:
     """The product path: every numeric step is a C-ABI call on the resident state (fails loudly without the
     library / a GPU - there is no host fallback)."""
@@ -323,6 +374,19 @@ class HipBackend:
         """the whole log in one read -> dict(ts [n] ns, Rsb [n, B, 3, 3], Tsb / Vsb / bg / ba [n, B, 3], status [n, B],
         cov [n, B, k, k], cols [k])"""
         return _trajectory(self.ctx)
+
+    def enable_map_log(self, T_max, n_out=None, world_cov=True):
+        """device log of T_max frames of the in-state features (xivo_hip_map_config): the best n_out per filter (default: all
+        feature slots), with the covariance of the world position when world_cov"""
+        self.ctx.map_config(T_max, self.F if n_out is None else n_out, world_cov=world_cov)
+
+    def record_map(self, ts):
+        """append every filter's in-state features to the landmark log (one launch, no synchronisation); ts in ns"""
+        return self.ctx.map_record(ts, self.B)
+
+    def landmarks(self):
+        """the whole landmark log in one read -> (pts [n, B, n_out] map_pt_dtype, n_pts [n, B], ts [n] ns)"""
+        return self.ctx.map_read()
 
     def covariance(self):
         return self.ctx.download_P()
@@ -631,12 +695,16 @@ def initial_poses(cfg, sims, t0=0.0):
 
 
 def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0,
-            timers=None, trajectory_log=False):
+            timers=None, trajectory_log=False, map_log=False):
     """The loop of scripts/pyxivo_pcw.py:117-163 for B = len(sims) sequences at once.
     -> dict(ts [n] ns, Tsb [n x B x 3], Wsb [n x B x 3], gt_Tsb [n x B x 3], runner, backend)
     trajectory_log (True, or the error-state columns to keep): the estimate of every frame is recorded on the device
     (HipBackend.record) and read once at the end instead of a scene download per frame - the same Tsb / Wsb, plus
-    `trajectory` (HipBackend.trajectory) and, with the pose columns logged, err6 / nees / anees / nees_used."""
+    `trajectory` (HipBackend.trajectory) and, with the pose columns logged, err6 / nees / anees / nees_used.
+    map_log: the in-state features of every frame are recorded on the device after the frame (xivo_hip_map_record) and read
+    once at the end; the runner's slot book gives the track id of each, the worlds the true point. Adds `map` (pts, n_pts, ids,
+    gt), landmark_err3 / landmark_nees / landmark_anees / landmarks_used, anees_landmark and landmarks_scored_mean. Off:
+    nothing changes."""
     B = len(sims)
     K = np.array([[cfg.cam["fx"], 0, cfg.cam["cx"]], [0, cfg.cam["fy"], cfg.cam["cy"]], [0, 0, 1.0]])
     Rbc = so3_exp(cfg.Wbc)
@@ -651,6 +719,7 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     ts, est_T, est_W, gt_T, gt_R = [], [], [], [], []
     if trajectory_log:
         be.enable_trajectory_log((n_imu + every - 1) // every, _traj_cols(trajectory_log))
+    mlog = _MapLog(be.ctx, (n_imu + every - 1) // every, cfg.n_features, B) if map_log else None
     for k in range(n_imu):
         t = k * imu_dt
         if k > 0:
@@ -672,7 +741,12 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
                 R, T = be.poses()
                 est_T.append(T); est_W.append(np.array([so3_log(r) for r in R]))
             gt_T.append(np.array([s.gsb(t)[1] for s in sims]))
+            if mlog is not None:
+                mlog.record(ts[-1], [bk.feat_id for bk in runner.books], np.array([w.ids for w in worlds]),
+                            np.array([w.Xs for w in worlds]))
     out = dict(ts=np.array(ts), gt_Tsb=np.array(gt_T), runner=runner, backend=be)
+    if mlog is not None:
+        mlog.finish(out)
     if trajectory_log:
         traj = be.trajectory()
         est_T, est_W = traj["Tsb"], [[so3_log(r) for r in R] for R in traj["Rsb"]]
@@ -710,11 +784,12 @@ def run_pcw_cpp(cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04
 
 
 def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0, npts=1000, seed=0, device=0,
-                  timers=None, trajectory_log=False):
+                  timers=None, trajectory_log=False, map_log=False):
     """Thousands of sequences end to end: the vectorised simulators of xivo_amd/pcw.py (BatchTrajectorySim, BatchPCW) feed
     xivo::hip::BatchEstimator message by message. -> dict(ts, Tsb [n x B x 3], gt_Tsb, estimator)
     trajectory_log: as in run_pcw - one record launch per frame on the estimator's context and one read at the end instead of
-    a pose download per frame; adds `trajectory` and err6 / nees / anees / nees_used."""
+    a pose download per frame; adds `trajectory` and err6 / nees / anees / nees_used.
+    map_log: as in run_pcw, on the estimator's context; the slot book is the estimator's (BatchEstimator.book)."""
     import time
     from .batch import BatchEstimator
     from .pcw import BatchPCW, BatchTrajectorySim
@@ -736,6 +811,10 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     if trajectory_log:      # the estimator's own context (it stays the owner)
         ctx = L.Context.borrow(host.xivo_batch_ctx(est.h), cfg.N, 2 * cfg.n_features, B)
         ctx.traj_config((n_imu + every - 1) // every, _traj_cols(trajectory_log))
+    mlog = None
+    if map_log:
+        mctx = ctx if ctx is not None else L.Context.borrow(host.xivo_batch_ctx(est.h), cfg.N, 2 * cfg.n_features, B)
+        mlog = _MapLog(mctx, (n_imu + every - 1) // every, cfg.n_features, B)
     tm = timers if timers is not None else {}
     for k in range(n_imu):
         t = k * imu_dt
@@ -759,7 +838,11 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
                 ctx.traj_record(ts[-1], B); gt_R.append(Rsb)
             else:
                 est_T.append(est.poses()["Tsb"].copy())
+            if mlog is not None:
+                mlog.record(ts[-1], [est.book(b)[0] for b in range(B)], world.ids, world.Xs)
     out = dict(ts=np.array(ts), gt_Tsb=np.array(gt_T), estimator=est)
+    if mlog is not None:
+        mlog.finish(out)
     if ctx is not None:
         traj = _trajectory(ctx)
         est_T = traj["Tsb"]
