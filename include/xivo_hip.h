@@ -698,6 +698,43 @@ int xivo_hip_traj_read(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, xivo_t
 int xivo_hip_traj_nees(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, const double* gt, double* err6, double* nees,
                        double* anees, int* n_used);
 
+/* ---- trajectory score: aligned ATE and RPE of the logged poses against ground truth, on the device ----
+ * The accuracy score of a run next to its consistency score (xivo_hip_traj_nees): what the reference's ComputeATE /
+ * ComputeRPE (src/metrics.cpp) give for one trajectory, for every filter of a slice of the log, as one small record per
+ * filter. The direction is the reference's: the alignment (R, T) = gYX takes ground truth onto the estimate
+ * (metrics.cpp:17, r = Y - gYX X). A frame is used for a filter when all twelve values of its ground-truth entry and the
+ * Rsb, Tsb of its record are finite; a pair (t, t + rpe_lag) needs both of its frames used. */
+typedef struct {
+  int align;     /* 0: score est against gt as they are; 1: rigid SE(3) alignment first (no scale) */
+  int rpe_lag;   /* pairs (t, t + rpe_lag) in frames of the slice; 0: no RPE                         */
+} xivo_traj_score_opts;
+typedef struct {
+  double ate;          /* sqrt(mean |Tsb_est - (R Tsb_gt + T)|^2) over the used frames; -1 if none     */
+  double ate_raw;      /* the same with R = I, T = 0                                                   */
+  double rpe_pos, rpe_rot; /* RMS over the pairs; -1 if there is no pair (or rpe_lag = 0)              */
+  double R[9], T[3];   /* the alignment, gt -> est, R column-major; I, 0 when align = 0                */
+  double sv[3];        /* singular values of the centred cross-covariance, descending                  */
+  int n_used, n_pairs;
+  int flags;           /* bit 0: rotation not determined (sv[1] <= 1e-12 sv[0], or n_used < 3)         */
+  int reserved;
+} xivo_traj_score;
+#define XIVO_TRAJ_SCORE_UNDETERMINED 1
+/* Frames [t0, t0 + nt) (all recorded) of filters [b0, b0 + nb); gt: host [nt][nb][12] as for xivo_hip_traj_nees; out: host
+ * [nb]. Needs no particular columns recorded - it reads only the records. The alignment is the closed-form least-squares
+ * optimum (Horn / Kabsch): H = sum (y - ybar)(x - xbar)^T over the used frames, y the estimated and x the true Tsb,
+ * H = U diag(sv) V^T, R = U diag(1, 1, det(U V^T)) V^T, T = ybar - R xbar; centroids, H and the residuals are three passes
+ * over the frames. RPE (metrics.cpp:110-113): dgX = gX(t)^-1 gX(t + lag), dgY likewise for the estimate, E = dgX^-1 dgY,
+ * rpe_pos / rpe_rot = the roots of the means of |trans E|^2 / |log rot E|^2. Time association is the caller's: the lag is
+ * in frames. Every sum runs in a fixed order that depends on the slice's frames only - a filter's record does not depend on
+ * b0, nb or the other filters, and two calls return the same bits. One upload of gt, launches on the context's stream, one
+ * download of nb records, one synchronisation; the staging is the context's. Log not configured, a slice outside the
+ * recorded frames, rpe_lag < 0, a NULL ctx / gt / opts / out: XIVO_HIP_ERR_INVALID before any device work. nb = 0:
+ * XIVO_HIP_OK, nothing is written; nt = 0: every record is the one of a filter without a used frame. One 64-lane workgroup
+ * per filter: a slice of 2^26 filters or more would not fit one launch and is XIVO_HIP_ERR_UNSUPPORTED, also before any
+ * device work (a guard on the launch shape - batch_max bounds nb first, and no context of that size exists today). */
+int xivo_hip_traj_score(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, const double* gt,
+                        const xivo_traj_score_opts* opts, xivo_traj_score* out);
+
 /* ---- landmark log: each frame's in-state features, their world positions and covariances, recorded on the device ----
  * The other half of a frame's answer next to the trajectory log: what Estimator::InstateFeaturePositionsAndCovs
  * (src/estimator_accessors.cpp:308-357) returns for one filter - the in-state features ordered by FeatureCovComparison

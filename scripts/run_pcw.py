@@ -19,6 +19,11 @@ def _consistency(out):
     if "anees" in out:
         rep.update({"anees_pose": float(np.nanmean(out["anees"])),
                     "nees_not_spd": int(out["nees"].size - out["nees_used"].sum())})
+    if "ate_aligned" in out:         # per sequence, from the device (xivo_hip_traj_score); RPE: sequences with a pair
+        def q(v):
+            v = np.asarray(v)[np.asarray(v) >= 0]
+            return {"median": float(np.median(v)), "p90": float(np.quantile(v, 0.9)), "max": float(v.max())} if v.size else None
+        rep.update({"ate_aligned_m": q(out["ate_aligned"]), "rpe": {"pos_m": q(out["rpe_pos"]), "rot_rad": q(out["rpe_rot"])}})
     if "anees_landmark" in out:      # -map-log: 3 for a consistent map; landmarks scored per sequence and frame
         rep.update({"anees_landmark": out["anees_landmark"], "landmarks_scored_mean": out["landmarks_scored_mean"]})
     return rep
@@ -45,6 +50,10 @@ def main():
                     help="record every frame's estimate and motion-state covariance on the device (one read at the end) and "
                          "report anees_pose: the 6-dof pose NEES against the simulator's ground truth, ensemble mean per frame, "
                          "averaged over the frames (-host python and -vectorized)")
+    ap.add_argument("-rpe-dt", dest="rpe_dt", type=float, default=1.0,
+                    help="-traj-log: interval in seconds of the relative pose error (rpe), converted to camera frames with "
+                         "-vision_dt (the nearest whole number, at least one frame; 0: no rpe); next to it ate_aligned_m, the ATE "
+                         "after the least-squares rigid alignment, both scored on the device per sequence")
     ap.add_argument("-map-log", dest="map_log", action="store_true",
                     help="record every frame's in-state features, their world positions and covariances on the device (one read "
                          "at the end) and report anees_landmark: the 3-dof NEES of the world points against the simulator's, "
@@ -60,7 +69,7 @@ def main():
         t0 = time.perf_counter()
         out = sequence.run_pcw_batch(cfg, a.sequences, total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
                                      noise_vision_std=a.noise_vision_std, npts=a.npts, timers=tm, trajectory_log=a.traj_log,
-                                     map_log=a.map_log)
+                                     map_log=a.map_log, rpe_dt=a.rpe_dt)
         wall = time.perf_counter() - t0
         st = out["estimator"].stats(); out["estimator"].close()
         frames = len(out["ts"])
@@ -106,7 +115,7 @@ def main():
         out = sequence.run_pcw(lambda c_, B_, p_, P_: sequence.HipBackend(c_, B_, p_, P_, device=device), cfg, worlds, sims,
                                total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
                                noise_vision_std=a.noise_vision_std, timers=timers, trajectory_log=a.traj_log,
-                               map_log=a.map_log)
+                               map_log=a.map_log, rpe_dt=a.rpe_dt)
         out["backend"].close()
     wall = time.perf_counter() - t0
     frames = len(out["ts"])

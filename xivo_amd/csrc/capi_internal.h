@@ -4,6 +4,7 @@
 //   capi_glevel.hip     feature level: scene, Jacobians, gate, stacking, OOS rows, RANSAC, loop closure, Givens / QR, edits
 //   capi_propagate.hip  propagation
 //   capi_traj.hip       trajectory log: per-frame records, read-out, NEES against ground truth
+//   capi_score.hip      trajectory score: aligned / unaligned ATE and RPE of the logged poses against ground truth
 //   capi_map.hip        landmark log: per-frame in-state features, world positions and covariances, read-out, landmark NEES
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
@@ -145,7 +146,7 @@ struct xivo_hip_ctx {
   xivo_adapt_depth_opts adapt{};
   bool adapt_on = false;
   // trajectory log (xivo_hip_traj_*, capi_traj.hip): [traj_T][Bmax] records and packed covariance blocks of traj_cols, frames
-  // [0, traj_n) written; null until xivo_hip_traj_config. traj_io: per-call staging of xivo_hip_traj_nees
+  // [0, traj_n) written; null until xivo_hip_traj_config. traj_io: per-call staging of xivo_hip_traj_nees / xivo_hip_traj_score
   xivo_traj_rec* traj_rec = nullptr; double* traj_cov = nullptr;
   int traj_T = 0, traj_n = 0, traj_ncols = 0, traj_cols[XIVO_TRAJ_MAX_COLS] = {0};
   std::vector<long long> traj_ts;

@@ -1,5 +1,5 @@
 // Launchers of the EKF-specific (non-GEMM) kernels, one section per translation unit: state_kernels.hip,
-// traj_kernels.hip, map_kernels.hip, glevel_kernels.hip, pool_kernels.hip, propagate_kernels.hip, then ldlt_fallback.hip and dropin.hip.
+// traj_kernels.hip, score_kernels.hip, map_kernels.hip, glevel_kernels.hip, pool_kernels.hip, propagate_kernels.hip, then ldlt_fallback.hip and dropin.hip.
 #pragma once
 #include "common.h"
 #include "ell.h"
@@ -74,6 +74,16 @@ struct TrajNeesArgs {
   const double* gt; double* err6; double* nees; double* anees; int* n_used;
 };
 int launch_traj_nees(const TrajNeesArgs& a, hipStream_t s);
+
+// ================================================================ score_kernels.hip: trajectory score (capi_score.hip)
+
+// aligned / unaligned ATE and RPE of the slice frames [t0, t0 + nt) x filters [b0, b0 + nb) against gt [nt][nb][12];
+// out [nb] (device). One wave per filter: returns non-zero without launching when nb does not fit a grid dimension
+struct TrajScoreArgs {
+  const xivo_traj_rec* rec; int Bmax, b0, nb, t0, nt, align, rpe_lag;
+  const double* gt; xivo_traj_score* out;
+};
+int launch_traj_score(const TrajScoreArgs& a, hipStream_t s);
 
 // ================================================================ map_kernels.hip: landmark log (capi_map.hip)
 

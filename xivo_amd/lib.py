@@ -97,6 +97,12 @@ traj_opts_dtype = np.dtype([("T_max", "i4"), ("n_cols", "i4"), ("cols", "i4", TR
 traj_dtype = np.dtype([("Rsb", "f8", 9), ("Tsb", "f8", 3), ("Vsb", "f8", 3), ("bg", "f8", 3), ("ba", "f8", 3),
                        ("status", "i4"), ("reserved", "i4")])
 assert traj_dtype.itemsize == 176 and traj_opts_dtype.itemsize == 136
+# trajectory score (include/xivo_hip.h): xivo_traj_score_opts, xivo_traj_score
+TRAJ_SCORE_UNDETERMINED = 1
+traj_score_opts_dtype = np.dtype([("align", "i4"), ("rpe_lag", "i4")])
+traj_score_dtype = np.dtype([("ate", "f8"), ("ate_raw", "f8"), ("rpe_pos", "f8"), ("rpe_rot", "f8"), ("R", "f8", 9), ("T", "f8", 3),
+                             ("sv", "f8", 3), ("n_used", "i4"), ("n_pairs", "i4"), ("flags", "i4"), ("reserved", "i4")])
+assert traj_score_dtype.itemsize == 168 and traj_score_opts_dtype.itemsize == 8
 # landmark log (include/xivo_hip.h): xivo_map_opts, xivo_map_pt
 MAP_MAX_OUT = 128
 MAP_WORLD_COV = 1
@@ -207,6 +213,7 @@ _SIGS = {
     "xivo_hip_traj_read": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_traj_nees": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                            C.c_void_p],
+    "xivo_hip_traj_score": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_map_config": [C.c_void_p, C.c_void_p],
     "xivo_hip_map_record": [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p],
     "xivo_hip_map_count": [C.c_void_p],
@@ -862,6 +869,27 @@ class Context:
         err6 = np.zeros((nt, nb, 6)); nees = np.zeros((nt, nb)); anees = np.zeros(nt); used = np.zeros(nt, dtype=np.int32)
         self._check(self.lib.xivo_hip_traj_nees(self.h, b0, nb, t0, nt, _ptr(gt), _ptr(err6), _ptr(nees), _ptr(anees), _ptr(used)))
         return err6, nees, anees, used
+
+    def traj_score(self, gt, b0=0, nb=None, t0=0, nt=None, align=True, rpe_lag=0):
+        """ATE / RPE of the logged poses of the slice against ground truth, on the device (xivo_hip_traj_score).
+        gt: (gt_Rsb [nt, nb, 3, 3], gt_Tsb [nt, nb, 3]) or the packed [nt, nb, 12] (Rsb column-major, then Tsb)
+        -> traj_score_dtype [nb]; R as stored (column-major): rec["R"].reshape(3, 3).T is the matrix, gt -> est"""
+        if isinstance(gt, (tuple, list)):
+            R = np.asarray(gt[0], dtype=np.float64)
+            g = np.empty(R.shape[:2] + (12,))
+            g[:, :, :9] = np.transpose(R, (0, 1, 3, 2)).reshape(R.shape[:2] + (9,))
+            g[:, :, 9:] = np.asarray(gt[1], dtype=np.float64).reshape(R.shape[:2] + (3,))
+        else:
+            g = _f64(gt)
+        nb = self.batch - b0 if nb is None else int(nb)
+        nt = self.traj_count() - t0 if nt is None else int(nt)
+        if g.shape != (nt, nb, 12):
+            raise ValueError("gt must be [nt = %d, nb = %d, 12], got %s" % (nt, nb, g.shape))
+        o = np.zeros(1, dtype=traj_score_opts_dtype)
+        o["align"], o["rpe_lag"] = int(bool(align)), int(rpe_lag)
+        out = np.zeros(nb, dtype=traj_score_dtype)
+        self._check(self.lib.xivo_hip_traj_score(self.h, int(b0), nb, int(t0), nt, _ptr(g), _ptr(o), _ptr(out)))
+        return out
 
     # ---- landmark log (xivo_hip_map_*)
     def map_config(self, T_max, n_out=0, world_cov=True):

@@ -207,11 +207,20 @@ def _traj_cols(trajectory_log):
     return TRAJ_LOG_COLS if trajectory_log is True else tuple(int(c) for c in trajectory_log)
 
 
-def _score(ctx, traj, gt_R, gt_T, out):
-    """NEES of the logged poses against the simulator's ground truth (xivo_hip_traj_nees), when the pose block is logged"""
+def _score(ctx, traj, gt_R, gt_T, out, rpe_lag=0):
+    """NEES of the logged poses against the simulator's ground truth (xivo_hip_traj_nees), when the pose block is logged, and
+    the accuracy score of every sequence (xivo_hip_traj_score): aligned / unaligned ATE, RPE at rpe_lag frames"""
     out["trajectory"] = traj
     if set(range(6)) <= set(int(c) for c in traj["cols"]):
         out["err6"], out["nees"], out["anees"], out["nees_used"] = ctx.traj_nees(gt_R, gt_T)
+    sc = ctx.traj_score((gt_R, gt_T), align=True, rpe_lag=rpe_lag)
+    out["ate_aligned"], out["ate_raw"], out["rpe_pos"], out["rpe_rot"] = sc["ate"], sc["ate_raw"], sc["rpe_pos"], sc["rpe_rot"]
+
+
+def rpe_lag_frames(rpe_dt, vision_dt):
+    """the RPE interval in camera frames (xivo_hip_traj_score takes frames; time association is the driver's): the nearest
+    whole number of frames and at least one; rpe_dt <= 0 is lag 0, no RPE (rpe_pos = rpe_rot = -1)"""
+    return max(1, int(round(rpe_dt / vision_dt))) if rpe_dt > 0 else 0
 
 
 def truth_by_track(world_ids, world_Xs, fid):
@@ -695,12 +704,14 @@ def initial_poses(cfg, sims, t0=0.0):
 
 
 def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0,
-            timers=None, trajectory_log=False, map_log=False):
+            timers=None, trajectory_log=False, map_log=False, rpe_dt=1.0):
     """The loop of scripts/pyxivo_pcw.py:117-163 for B = len(sims) sequences at once.
     -> dict(ts [n] ns, Tsb [n x B x 3], Wsb [n x B x 3], gt_Tsb [n x B x 3], runner, backend)
     trajectory_log (True, or the error-state columns to keep): the estimate of every frame is recorded on the device
     (HipBackend.record) and read once at the end instead of a scene download per frame - the same Tsb / Wsb, plus
-    `trajectory` (HipBackend.trajectory) and, with the pose columns logged, err6 / nees / anees / nees_used.
+    `trajectory` (HipBackend.trajectory) and, with the pose columns logged, err6 / nees / anees / nees_used; and per sequence
+    ate_aligned / ate_raw / rpe_pos / rpe_rot from the device (xivo_hip_traj_score; RPE over rpe_dt seconds as
+    rpe_lag_frames turns them into frames, -1: no pair).
     map_log: the in-state features of every frame are recorded on the device after the frame (xivo_hip_map_record) and read
     once at the end; the runner's slot book gives the track id of each, the worlds the true point. Adds `map` (pts, n_pts, ids,
     gt), landmark_err3 / landmark_nees / landmark_anees / landmarks_used, anees_landmark and landmarks_scored_mean. Off:
@@ -750,7 +761,7 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     if trajectory_log:
         traj = be.trajectory()
         est_T, est_W = traj["Tsb"], [[so3_log(r) for r in R] for R in traj["Rsb"]]
-        _score(be.ctx, traj, np.array(gt_R), out["gt_Tsb"], out)
+        _score(be.ctx, traj, np.array(gt_R), out["gt_Tsb"], out, rpe_lag_frames(rpe_dt, vision_dt))
     out["Tsb"], out["Wsb"] = np.array(est_T), np.array(est_W)
     return out
 
@@ -784,11 +795,11 @@ def run_pcw_cpp(cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04
 
 
 def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0, npts=1000, seed=0, device=0,
-                  timers=None, trajectory_log=False, map_log=False):
+                  timers=None, trajectory_log=False, map_log=False, rpe_dt=1.0):
     """Thousands of sequences end to end: the vectorised simulators of xivo_amd/pcw.py (BatchTrajectorySim, BatchPCW) feed
     xivo::hip::BatchEstimator message by message. -> dict(ts, Tsb [n x B x 3], gt_Tsb, estimator)
     trajectory_log: as in run_pcw - one record launch per frame on the estimator's context and one read at the end instead of
-    a pose download per frame; adds `trajectory` and err6 / nees / anees / nees_used.
+    a pose download per frame; adds `trajectory`, err6 / nees / anees / nees_used and ate_aligned / ate_raw / rpe_pos / rpe_rot.
     map_log: as in run_pcw, on the estimator's context; the slot book is the estimator's (BatchEstimator.book)."""
     import time
     from .batch import BatchEstimator
@@ -846,6 +857,6 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     if ctx is not None:
         traj = _trajectory(ctx)
         est_T = traj["Tsb"]
-        _score(ctx, traj, np.array(gt_R), out["gt_Tsb"], out)
+        _score(ctx, traj, np.array(gt_R), out["gt_Tsb"], out, rpe_lag_frames(rpe_dt, vision_dt))
     out["Tsb"] = np.array(est_T)
     return out
