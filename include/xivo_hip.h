@@ -39,7 +39,7 @@ enum {
   XIVO_HIP_ERR_NOT_SPD = -3,     /* S = HPH^T + R not positive definite         */
   XIVO_HIP_ERR_NOMEM = -4,
   XIVO_HIP_ERR_UNSUPPORTED = -5, /* size outside what the kernels are built for */
-  XIVO_HIP_ERR_FULL = -6         /* the trajectory / landmark log holds T_max frames */
+  XIVO_HIP_ERR_FULL = -6         /* the trajectory / landmark / innovation log holds T_max frames */
 };
 
 /* flags for xivo_hip_create / stacking */
@@ -795,6 +795,56 @@ int xivo_hip_map_read(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, xivo_ma
  * may be NULL): err3 [nt][nb][n_out][3], nees [nt][nb][n_out], anees [nt], n_used [nt]. */
 int xivo_hip_map_nees(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, const double* gt, double* err3, double* nees,
                       double* anees, int* n_used);
+
+/* ---- innovation log: each update's normalised innovation squared (NIS), recorded on the device ----
+ * The consistency figure that needs no ground truth. With innovation inn and S = H P H^T + R it is inn^T S^-1 inn, to be held
+ * against the number of rows. After dx = K inn it needs no factor: r = inn - H dx (the post-fit residual) equals R S^-1 inn, so
+ *   nis = sum_i inn_i r_i / R_i,   prefit = sum_i inn_i^2 / R_i,   postfit = sum_i r_i^2 / R_i
+ * come out of one pass over the staged rows - in whatever representation the update left them - and the resident dx: nothing
+ * is factored, nothing staged is changed. PRICE: nis is what a cancellation leaves of prefit, so the rounding of r is
+ * amplified by prefit / nis ~ |S| / R: about 1e-9 relative at a ratio of 1e7, 2e-6 at 1e11. prefit is recorded so that the
+ * ratio can be seen. COUNTED ROWS: row i < M is counted when it has a non-zero H entry or inn_i != 0 - pairs a gate
+ * neutralised (values 0, inn 0, diagR 1) and absent features drop out; OOS and loop-closure rows count like any other.
+ * The record must be taken after the update and before xivo_hip_absorb_error (which zeroes dx): the context keeps a host-side
+ * "dx is current" flag PER FILTER that every update call sets for the filters it updates (xivo_hip_update_joseph,
+ * _dense_gated, _filter_update: [0, B); xivo_hip_update_joseph_host: its one filter) and xivo_hip_absorb_error, every
+ * producer of new rows (a hand-over: for its own range), xivo_hip_one_point_ransac and xivo_hip_restore_P clear; a record of
+ * filters [0, B) needs the flag of every one of them. Device memory [T_max][batch_max] records that one kernel launch per frame appends to; nothing
+ * is allocated until the log is configured, and nothing outside xivo_hip_innov_config allocates for it. */
+enum { XIVO_INNOV_FAILED = 1, XIVO_INNOV_LDLT = 2 };
+typedef struct { int T_max; } xivo_innov_opts;   /* frames the log holds; 0 releases it */
+typedef struct {                  /* 64 bytes */
+  double nis, prefit, postfit;    /* as above; NaN when flags has XIVO_INNOV_FAILED                                      */
+  double inn_max;                 /* max_i |inn_i| over the counted rows (0 if none; NaN if one of them is NaN)           */
+  double dx_max;                  /* max_k |dx_k|, k < N (NaN if an entry is NaN)                                         */
+  int dof;                        /* counted rows                                                                         */
+  int rows;                       /* staged row count M of the context at that point                                      */
+  int flags;                      /* XIVO_INNOV_FAILED: update status != 0 (prior kept, dx = 0); XIVO_INNOV_LDLT: the
+                                     pivoted L D L^T fallback produced this update                                        */
+  int reserved;
+  double reserved2;
+} xivo_innov_rec;
+/* (Re-)allocates the log through the context's owner and empties it: T_max frames of batch_max records and the staging of
+ * xivo_hip_innov_stats. A size that overflows: XIVO_HIP_ERR_INVALID and the log is left as it was. */
+int xivo_hip_innov_config(xivo_hip_ctx* ctx, const xivo_innov_opts* opts);
+/* Appends one frame for filters [0, B), B <= batch_max: one launch on the context's stream, no synchronisation. dx not
+ * current for one of them (see above), not configured, nothing staged, or B out of range: XIVO_HIP_ERR_INVALID; log full:
+ * XIVO_HIP_ERR_FULL; a state too wide for the kernel's LDS copy of dx (8 (N + M) + 4 M bytes over 48 KiB, N + M beyond about
+ * 6000): XIVO_HIP_ERR_UNSUPPORTED; nothing is written or launched in any of these cases. ts_ns is kept on the host; frame_out (may be NULL) gets the frame's index. */
+int xivo_hip_innov_record(xivo_hip_ctx* ctx, int B, long long ts_ns, int* frame_out);
+/* frames recorded so far (negative: a status) */
+int xivo_hip_innov_count(xivo_hip_ctx* ctx);
+/* count <- 0; the memory and the configuration are kept */
+int xivo_hip_innov_reset(xivo_hip_ctx* ctx);
+/* Frames [t0, t0 + nt) (all recorded) of filters [b0, b0 + nb) to host arrays, frame-major: recs [nt][nb], ts [nt]. A NULL
+ * pointer skips that part. One synchronisation. */
+int xivo_hip_innov_read(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, xivo_innov_rec* recs, long long* ts);
+/* Sums of the slice on the device: per frame over the slice's filters (frame_* [nt]) and per filter over the slice's frames
+ * (filt_* [nb]); any output may be NULL. Records with flags != 0 or a non-finite nis are left out; *_used counts those that
+ * went in. frame_nis[t] / frame_dof[t] is the figure to hold against 1. Fixed-shape strided partial sums and a tree, no
+ * atomics: two calls on the same log return the same bits, and a filter's sums depend on (t0, nt) only - not on b0, nb. */
+int xivo_hip_innov_stats(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, double* frame_nis, long long* frame_dof,
+                         int* frame_used, double* filt_nis, long long* filt_dof, int* filt_used);
 
 /* ---- resident state edits between updates, batched over filters ----
  * The reference edits X_/P_ one filter at a time on the host (the functions cited per kind). A sequence driver that

@@ -26,6 +26,13 @@ def _consistency(out):
         rep.update({"ate_aligned_m": q(out["ate_aligned"]), "rpe": {"pos_m": q(out["rpe_pos"]), "rot_rad": q(out["rpe_rot"])}})
     if "anees_landmark" in out:      # -map-log: 3 for a consistent map; landmarks scored per sequence and frame
         rep.update({"anees_landmark": out["anees_landmark"], "landmarks_scored_mean": out["landmarks_scored_mean"]})
+    if "nis_per_dof" in out:         # -innov-log: 1 for a consistent filter; needs no ground truth
+        seq = np.asarray(out["nis_per_dof_seq"]); seq = seq[np.isfinite(seq)]
+        frm = np.asarray(out["nis_per_dof"])
+        rep.update({"nis_per_dof": float(np.nanmean(frm)) if np.isfinite(frm).any() else None,
+                    "nis_per_dof_sequences": {"median": float(np.median(seq)), "p90": float(np.quantile(seq, 0.9)),
+                                              "max": float(seq.max())} if seq.size else None,
+                    "nis_records_left_out": out["nis_records_left_out"]})
     return rep
 
 
@@ -59,6 +66,11 @@ def main():
                          "at the end) and report anees_landmark: the 3-dof NEES of the world points against the simulator's, "
                          "ensemble mean per frame averaged over the frames, and the mean number of landmarks scored per "
                          "sequence and frame (-host python and -vectorized)")
+    ap.add_argument("-innov-log", dest="innov_log", action="store_true",
+                    help="record every update's normalised innovation squared on the device between the update and AbsorbError "
+                         "(one read at the end) and report nis_per_dof: the ensemble's sum of NIS over its sum of counted "
+                         "rows per frame, averaged over the frames (1 for a consistent filter; needs no ground truth), its "
+                         "median / p90 / max over the sequences and the records left out (-host python and -vectorized)")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         from xivo_amd.shard import spawn_ranks
@@ -69,7 +81,7 @@ def main():
         t0 = time.perf_counter()
         out = sequence.run_pcw_batch(cfg, a.sequences, total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
                                      noise_vision_std=a.noise_vision_std, npts=a.npts, timers=tm, trajectory_log=a.traj_log,
-                                     map_log=a.map_log, rpe_dt=a.rpe_dt)
+                                     map_log=a.map_log, rpe_dt=a.rpe_dt, innovation_log=a.innov_log)
         wall = time.perf_counter() - t0
         st = out["estimator"].stats(); out["estimator"].close()
         frames = len(out["ts"])
@@ -115,7 +127,7 @@ def main():
         out = sequence.run_pcw(lambda c_, B_, p_, P_: sequence.HipBackend(c_, B_, p_, P_, device=device), cfg, worlds, sims,
                                total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
                                noise_vision_std=a.noise_vision_std, timers=timers, trajectory_log=a.traj_log,
-                               map_log=a.map_log, rpe_dt=a.rpe_dt)
+                               map_log=a.map_log, rpe_dt=a.rpe_dt, innovation_log=a.innov_log)
         out["backend"].close()
     wall = time.perf_counter() - t0
     frames = len(out["ts"])

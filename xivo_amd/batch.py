@@ -56,6 +56,7 @@ def load_host_library():
         _HOST.xivo_batch_pool_stats.restype = None
         _HOST.xivo_batch_enable_depth_init.argtypes = [C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_init_z.argtypes = [C.c_void_p, C.c_void_p]
+        _HOST.xivo_batch_innov_log.argtypes = [C.c_void_p, C.c_int]
     return _HOST
 
 
@@ -118,6 +119,12 @@ class BatchEstimator:
         """AdaptInitialDepth's init_z [B] after the last frame (None while adaptive_initial_depth is off)"""
         z = np.zeros(self.B)
         return z if self.host.xivo_batch_init_z(self.h, z.ctypes.data) == 0 else None
+
+    def enable_innovation_log(self, T_max):
+        """BatchEstimator::EnableInnovationLog: every camera frame records the update's NIS on the estimator's context between
+        the update and AbsorbError (read it through a borrowed Context: innov_read / innov_stats); 0 releases the log"""
+        if self.host.xivo_batch_innov_log(self.h, int(T_max)) != 0:
+            raise RuntimeError("xivo_batch_innov_log failed")
 
     def close(self):
         if self.h:

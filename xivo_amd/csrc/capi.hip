@@ -296,6 +296,7 @@ int xivo_hip_snapshot_P(xivo_hip_ctx* c) {
 int xivo_hip_restore_P(xivo_hip_ctx* c) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || !c->Psnap) return XIVO_HIP_ERR_INVALID;
+  c->dx_clear();   // (innovation log: the restored covariance is not the one dx was computed against)
   HIP_TRY(hipMemcpyAsync(c->P.p, c->Psnap, (size_t)c->Bmax * c->P.stride * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   return XIVO_HIP_OK;
 }

@@ -46,6 +46,7 @@ int calib_gate(xivo_hip_ctx* c, int B, double R, double mh_thresh, double mh_mul
   if (rc) return rc;
   if (gate) {
     c->rows.stacked(B, c->F, R, Stacking::full_rows, /*pw=*/9, /*dense=*/true, CalibCols::in_rows);
+    c->dx_clear();
     rc = stack_impl(c, B, R, 1, nullptr, /*full_rows=*/1);
     if (rc) return rc;
     GateDenseArgs a{};
@@ -210,6 +211,7 @@ int xivo_hip_set_calib(xivo_hip_ctx* c, const xivo_calib_layout* layout) {
   if (!c->Jc && c->Fmax > 0) { int rc = c->mem.zeroed(&c->Jc, (size_t)c->Bmax * c->Fmax * 44); if (rc) return rc; }
   if (!c->Hlead.p) { int rc = c->mem.zeroed(&c->Hlead.p, (size_t)c->Bmax * c->Hlead.stride); if (rc) return rc; }
   c->rows.lead_dropped();
+  c->dx_clear();
   c->cl = l;
   c->calib_on = l.td >= 0 || l.cam_dim > 0;       // measurement side: blocks beyond the default build's (the Cg / bg blocks sit inside the td block)
   c->calib_motion = l.td >= 0 || l.Cg >= 0;       // motion side: kMotionSize > 23
@@ -272,6 +274,7 @@ int xivo_hip_stack(xivo_hip_ctx* c, int B, double R) {
   const int dense = ((c->flags & XIVO_HIP_FLAG_DENSE_H) || cc == CalibCols::in_rows) ? 1 : 0;
   const int pw = (c->flags & XIVO_HIP_FLAG_FIX_GROUP_BLOCK) ? 9 : 6;   // group block(s) + feature block
   c->rows.stacked(B, c->F, R, Stacking::in_state_as_coded, pw, /*dense=*/dense != 0, cc);
+  c->dx_clear();
   return stack_impl(c, B, R, dense);
 }
 
@@ -347,6 +350,7 @@ int xivo_hip_oos_project_ex(xivo_hip_ctx* c, int b0, int nb, int n_oos, const xi
   }
   if (rows_out) HIP_TRY(hipMemcpyAsync(rows_out, c->oos_rows, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  c->dx_clear();
   c->rows.oos_appended(max_rows, Roos, mixed, b0, nb);   // (not mixed: OOS rows are dense over the group blocks - dense path)
   return XIVO_HIP_OK;
 }
@@ -412,6 +416,7 @@ int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_th
   if (rc) return rc;
   rc = xivo_hip_update_joseph(c, B);
   if (rc) return rc;
+  c->dx_clear();   // (the partial update's dx is absorbed right here and the state restored: nothing to record)
   {  // AbsorbError (:333): in_current_ekf_update_ is empty at this point of Estimator::UpdateStep (cleared at
      // src/manager.cpp:28, filled after OutlierRejection), so no feature state moves; State::counter is restored with X_
     AbsorbArgs ab{};
@@ -524,6 +529,7 @@ int xivo_hip_compress_oos(xivo_hip_ctx* c, int B, double trigger_ratio, int* row
   for (int b = 0; b < B; ++b) mx = rows[b] > mx ? rows[b] : mx;
   // (rc == -1: block larger than the built kernels - rows are left as they are, which is always valid)
   c->rows.oos_compressed(mx);
+  c->dx_clear();
   if (rows_out) memcpy(rows_out, rows.data(), (size_t)B * sizeof(int));
   return XIVO_HIP_OK;
 }
@@ -859,6 +865,7 @@ int xivo_hip_absorb_error(xivo_hip_ctx* c, int B) {
   a.poses = c->poses; a.groups = c->groups; a.feats = c->feats; a.mask = c->mask; c->err.to(a.err, a.strideErr);
   a.lay = c->lay; a.F = c->F; a.Fmax = c->Fmax; a.batch = B; a.counter = c->absorb_count; a.status = c->status;
   a.calib = (c->calib_on || c->calib_motion) ? c->calib : nullptr; a.cl = c->cl;
+  c->dx_clear();   // the kernel zeroes dx
   StageTimer st(c, ST_OTHER, 0.0, "absorb_error_kernel");
   return launch_absorb_error(a, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
 }

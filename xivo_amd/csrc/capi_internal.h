@@ -6,6 +6,7 @@
 //   capi_traj.hip       trajectory log: per-frame records, read-out, NEES against ground truth
 //   capi_score.hip      trajectory score: aligned / unaligned ATE and RPE of the logged poses against ground truth
 //   capi_map.hip        landmark log: per-frame in-state features, world positions and covariances, read-out, landmark NEES
+//   capi_innov.hip      innovation log: per-frame NIS / pre- and post-fit sums of every filter's update, read-out, ensemble sums
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
 //
@@ -23,6 +24,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <vector>
 
 #include "../../include/xivo_hip.h"
@@ -157,6 +159,17 @@ struct xivo_hip_ctx {
   int map_T = 0, map_n = 0, map_nout = 0; unsigned map_flags = 0;
   std::vector<long long> map_ts;
   char* map_io = nullptr; size_t map_io_cap = 0;
+  // innovation log (xivo_hip_innov_*, capi_innov.hip): [innov_T][Bmax] records, frames [0, innov_n) written; null until
+  // xivo_hip_innov_config, which also allocates innov_io, the output staging of xivo_hip_innov_stats. dx_ok[b]: the err
+  // buffer of filter b holds the dx of the rows staged for it right now (set by the update calls for the filters they update;
+  // cleared by absorb, new rows, restore_P) - a record of filters [0, B) needs it of every one of them
+  xivo_innov_rec* innov_rec = nullptr; char* innov_io = nullptr;
+  int innov_T = 0, innov_n = 0;
+  std::vector<long long> innov_ts;
+  std::vector<char> dx_ok;
+  void dx_set(int b0, int nb, bool v) { if (dx_ok.size() != (size_t)Bmax) dx_ok.assign((size_t)Bmax, 0); std::fill_n(dx_ok.begin() + b0, nb, (char)v); }
+  void dx_clear() { std::fill(dx_ok.begin(), dx_ok.end(), (char)0); }
+  bool dx_current(int B) const { return dx_ok.size() >= (size_t)B && std::all_of(dx_ok.begin(), dx_ok.begin() + B, [](char v) { return v != 0; }); }
   std::vector<char> hstage;                        // host staging of d2h_rows
   char* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
   // one-filter plumbing call (xivo_hip_update_joseph_host): page-locked, device-mapped staging block owned by the context,

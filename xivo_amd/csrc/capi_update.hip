@@ -473,9 +473,10 @@ static int update_chunks(xivo_hip_ctx* c, int B, const GateParams* gate) {
   for (int b0 = 0; b0 < B; b0 += chunk) {
     const int nb = B - b0 < chunk ? B - b0 : chunk;
     int rc = update_joseph_range(c, b0, nb, gate);
-    if (rc) { c->call_batch = 0; return rc; }
+    if (rc) { c->call_batch = 0; c->dx_clear(); return rc; }
   }
   c->call_batch = 0;
+  c->dx_set(0, B, true);   // err holds the dx of the staged rows until something absorbs it or stages new rows (innovation log)
   return XIVO_HIP_OK;
 }
 
@@ -572,6 +573,7 @@ int stage_measurements(xivo_hip_ctx* c, int b0, int nb, int M, const double* dH,
   static const bool no_compress = getenv("XIVO_HIP_NO_COMPRESS") != nullptr;
   const bool compressed = meas_compress_fits(c->Mpmax, c->Np) && !no_compress;
   c->rows.handed_over(b0, nb, M, compressed);
+  c->dx_set(b0, nb, false);   // (a hand-over in pieces leaves the other filters' rows alone)
   if (!compressed) {
     // the compression kernel's LDS lists do not fit this shape: every filter keeps its dense rows and takes the dense pipeline
     StageTimer st(c, ST_STACK, 0.0, "unpack_meas_kernel", 8.0 * nb * (3.0 * M * N + 4.0 * M));
@@ -758,6 +760,7 @@ int xivo_hip_update_joseph_host(xivo_hip_ctx* c, int b, int M, const double* H, 
     if (!rc) rc = xivo_hip_set_measurements(c, b, 1, M, H, (long)ldh * N, ldh, inn, M, diagR, M);
     if (!rc) rc = update_joseph_range(c, b, 1);
     if (rc) return rc;
+    c->dx_set(b, 1, true);
     int st = 0;
     rc = xivo_hip_get_status(c, b, 1, &st);
     if (rc) return rc;
@@ -792,10 +795,12 @@ int xivo_hip_update_joseph_host(xivo_hip_ctx* c, int b, int M, const double* H, 
   }
   // what stage_measurements leaves behind for the pipeline
   c->rows.handed_over(b, 1, M, true); c->rows.fit_reported(b, 0, nc, pw);
+  c->dx_set(b, 1, false);
   // (from here on kernels that read the context's pinned block may be in flight: an early return drains the stream first,
   //  the next call overwrites that block)
   int rc = update_joseph_range(c, b, 1);
   if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+  c->dx_set(b, 1, true);
   DropinOutArgs oa{};
   oa.P = v.P.p; oa.N = N; oa.ldp = v.P.ld;
   if (p_down) { oa.Pdst = reinterpret_cast<double*>(c->pin_d + o_Pout); oa.ldpd = N; }

@@ -103,6 +103,30 @@ struct MapNeesArgs {
 };
 int launch_map_nees(const MapNeesArgs& a, hipStream_t s);
 
+// ================================================================ innov_kernels.hip: innovation log (capi_innov.hip)
+
+// one frame of the log: rec already points at the frame. Rows of filter b: dense (dense_all, or over[b] != 0) - all M rows from
+// H; else rows [0, ell_rows) row-pair compressed (+ the lead block's lead_k leading columns when lead != null) and rows
+// [ell_rows, M) dense from H (the mixed stacking's OOS rows)
+struct InnovRecordArgs {
+  const int* ell_idx; const double* ell_val; const int* over; long stride_idx, stride_val;
+  const double* H; long strideH; int ldh;
+  const double* lead; long strideLead; int ldlead, lead_k;
+  const double* inn; long strideInn; const double* diagR; long strideR; const double* err; long strideErr;
+  const int* status; const int* ldlt_used;
+  int M, N, ell_rows, dense_all;
+  xivo_innov_rec* rec;
+};
+int launch_innov_record(const InnovRecordArgs& a, int batch, hipStream_t s);
+size_t innov_record_lds(int M, int N);   // dynamic LDS of that launch; over 48 KiB (N + M beyond ~6000) it is refused
+// sums of nis / dof over the records that enter the statistic (innov_in_stats): group g of n_groups adds its n_elems records
+// rec[base + g * g_stride + e * e_stride], e ascending per thread of 256 (e = t, t + 256, ...), then a fixed tree
+struct InnovStatsArgs {
+  const xivo_innov_rec* rec; long base, g_stride, e_stride; int n_groups, n_elems;
+  double* nis; long long* dof; int* used;
+};
+int launch_innov_stats(const InnovStatsArgs& a, hipStream_t s);
+
 // ================================================================ glevel_kernels.hip: feature-level kernels (capi_glevel.hip)
 
 struct SceneBuffers {

@@ -151,12 +151,22 @@ void BatchEstimator::RunUpdate() {
   const int st = xivo_hip_get_status(ctx_, 0, B_, status_.data());
   if (st == XIVO_HIP_ERR_NOT_SPD) { for (int b = 0; b < B_; ++b) n_not_spd_ += status_[b] != 0; }
   else Check(st, "get_status");
+  // the update's innovation statistics need the dx AbsorbError is about to consume (Estimator::UpdateStep: between
+  // UpdateJosephForm and AbsorbError)
+  if (innov_log_) Check(xivo_hip_innov_record(ctx_, B_, (long long)std::llround(t_visual_ * 1e9), nullptr), "innov_record");
   Check(xivo_hip_absorb_error(ctx_, B_), "absorb_error");
+}
+
+void BatchEstimator::EnableInnovationLog(int T_max) {
+  const xivo_innov_opts o{T_max};
+  Check(xivo_hip_innov_config(ctx_, &o), "innov_config");
+  innov_log_ = T_max > 0;
 }
 
 void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_t* ids, const double* meas,
                                           unsigned char* mask_out) {
   double t0 = now_s();
+  t_visual_ = t;
   const int F = cfg_.n_features;
   // Estimator::Propagate, visual_meas == true (src/estimator.cpp:568-575): extrapolate along the last slope; dt == 0
   // (IMU and camera stamps coincide, the simulation case) propagates nothing (:550-555)
@@ -567,6 +577,10 @@ int xivo_batch_init_z(void* h, double* out) {
 void xivo_batch_pool_stats(void* h, long* admitted, long* dropped) {
   auto* e = static_cast<xivo::hip::BatchEstimator*>(h);
   *admitted = e->n_admitted(); *dropped = e->n_pool_dropped();
+}
+int xivo_batch_innov_log(void* h, int T_max) {
+  if (!h) return -1;
+  try { static_cast<xivo::hip::BatchEstimator*>(h)->EnableInnovationLog(T_max); return 0; } catch (const std::exception&) { return -1; }
 }
 long xivo_batch_not_spd(void* h) { return static_cast<xivo::hip::BatchEstimator*>(h)->n_not_spd(); }
 void* xivo_batch_ctx(void* h) { return static_cast<xivo::hip::BatchEstimator*>(h)->ctx(); }

@@ -93,6 +93,10 @@ class BatchEstimator {
   void EnableDepthInit(const DepthInitConfig& dc);   // after EnableSubfilter, before the first camera frame
   const std::vector<double>& init_z() const { return init_z_; }   // AdaptInitialDepth's init_z after the last frame
   long n_admitted() const { return n_admitted_; }
+  // the innovation log of the estimator's context (xivo_hip_innov_*): T_max frames, one record per camera frame between the
+  // update and AbsorbError, stamped with the frame's time in ns; T_max = 0 releases the log and stops recording. The caller
+  // reads it through ctx() (xivo_hip_innov_read / _stats).
+  void EnableInnovationLog(int T_max);
   long n_pool_dropped() const { return n_pool_dropped_; }   // new tracks that found no free pool entry or anchor
 
   struct Book {                                     // one filter's slots
@@ -137,6 +141,8 @@ class BatchEstimator {
   std::vector<std::vector<xivo_imu_in>> pending_;   // [message][B]
   long n_updates_ = 0, n_rejected_ = 0, n_not_spd_ = 0;
   std::vector<int> status_;
+  bool innov_log_ = false;
+  double t_visual_ = 0.0;                 // stamp of the camera frame being processed
   double host_s_ = 0.0;
   std::vector<unsigned char> mask_;
   std::vector<double> xp_;

@@ -110,6 +110,12 @@ map_opts_dtype = np.dtype([("T_max", "i4"), ("n_out", "i4"), ("flags", "u4")])
 map_pt_dtype = np.dtype([("Xs", "f8", 3), ("cov_local", "f8", 6), ("cov_world", "f8", 6), ("xp", "f8", 2), ("score", "f8"),
                          ("pos", "i4"), ("sind", "i4"), ("ref_sind", "i4"), ("reserved", "i4")])
 assert map_pt_dtype.itemsize == 160 and map_opts_dtype.itemsize == 12
+# innovation log (include/xivo_hip.h): xivo_innov_opts, xivo_innov_rec
+INNOV_FAILED, INNOV_LDLT = 1, 2
+innov_opts_dtype = np.dtype([("T_max", "i4")])
+innov_rec_dtype = np.dtype([("nis", "f8"), ("prefit", "f8"), ("postfit", "f8"), ("inn_max", "f8"), ("dx_max", "f8"),
+                            ("dof", "i4"), ("rows", "i4"), ("flags", "i4"), ("reserved", "i4"), ("reserved2", "f8")])
+assert innov_rec_dtype.itemsize == 64 and innov_opts_dtype.itemsize == 4
 
 
 def lib_path():
@@ -221,6 +227,13 @@ _SIGS = {
     "xivo_hip_map_read": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_map_nees": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                           C.c_void_p],
+    "xivo_hip_innov_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_innov_record": [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p],
+    "xivo_hip_innov_count": [C.c_void_p],
+    "xivo_hip_innov_reset": [C.c_void_p],
+    "xivo_hip_innov_read": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "xivo_hip_innov_stats": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_void_p],
 }
 HOST_P_RESIDENT, HOST_KEEP_P = 1, 2
 
@@ -937,6 +950,51 @@ class Context:
         used = np.zeros(nt, dtype=np.int32)
         self._check(self.lib.xivo_hip_map_nees(self.h, b0, nb, t0, nt, _ptr(gt), _ptr(err3), _ptr(nees), _ptr(anees), _ptr(used)))
         return err3, nees, anees, used
+
+    # ---- innovation log (xivo_hip_innov_*)
+    def innov_config(self, T_max):
+        """a device log of T_max frames: per frame and filter the normalised innovation squared of the update, its pre- and
+        post-fit sums, the counted rows and the update's flags; T_max = 0 releases it"""
+        o = np.zeros(1, dtype=innov_opts_dtype)
+        o["T_max"] = int(T_max)
+        self._check(self.lib.xivo_hip_innov_config(self.h, _ptr(o)))
+
+    def innov_record(self, ts_ns=0, B=None):
+        """append one frame (asynchronous; after the update, before absorb_error) -> its index"""
+        k = C.c_int(-1)
+        self._check(self.lib.xivo_hip_innov_record(self.h, self.batch if B is None else int(B), int(ts_ns), C.byref(k)))
+        return k.value
+
+    def innov_count(self):
+        n = self.lib.xivo_hip_innov_count(self.h)
+        if n < 0:
+            self._check(n)
+        return n
+
+    def innov_reset(self):
+        self._check(self.lib.xivo_hip_innov_reset(self.h))
+
+    def innov_read(self, b0=0, nb=None, t0=0, nt=None):
+        """-> (recs [nt, nb] innov_rec_dtype, ts [nt] ns)"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        nt = self.innov_count() - t0 if nt is None else int(nt)
+        recs = np.zeros((nt, nb), dtype=innov_rec_dtype)
+        ts = np.zeros(nt, dtype=np.int64)
+        self._check(self.lib.xivo_hip_innov_read(self.h, int(b0), nb, int(t0), nt, _ptr(recs), _ptr(ts)))
+        return recs, ts
+
+    def innov_stats(self, b0=0, nb=None, t0=0, nt=None):
+        """sums over the records with flags = 0 and a finite nis -> dict: frame_nis / frame_dof / frame_used [nt] over the
+        slice's filters, filt_nis / filt_dof / filt_used [nb] over its frames; frame_nis / frame_dof is the figure to hold
+        against 1"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        nt = self.innov_count() - t0 if nt is None else int(nt)
+        out = {"frame_nis": np.zeros(nt), "frame_dof": np.zeros(nt, dtype=np.int64), "frame_used": np.zeros(nt, dtype=np.int32),
+               "filt_nis": np.zeros(nb), "filt_dof": np.zeros(nb, dtype=np.int64), "filt_used": np.zeros(nb, dtype=np.int32)}
+        self._check(self.lib.xivo_hip_innov_stats(self.h, int(b0), nb, int(t0), nt, _ptr(out["frame_nis"]), _ptr(out["frame_dof"]),
+                                                  _ptr(out["frame_used"]), _ptr(out["filt_nis"]), _ptr(out["filt_dof"]),
+                                                  _ptr(out["filt_used"])))
+        return out
 
     def propagate_cov(self, Phi, Pmm, b0=0):
         Phi = np.asarray(Phi, dtype=np.float64)

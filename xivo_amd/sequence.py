@@ -274,6 +274,21 @@ class _MapLog:
         out["landmarks_scored_mean"] = float(used.mean() / self.B) if used.size else 0.0
 
 
+def _innovation(ctx, out):
+    """the innovation log of a run in one read (xivo_hip_innov_read / _stats): `innovation` (recs [n, B] innov_rec_dtype, ts),
+    nis_per_dof [n] - per frame the ensemble's sum of nis over its sum of counted rows, the figure to hold against 1 (NaN for
+    a frame no record entered) -, nis_per_dof_seq [B] the same per sequence over its frames, nis_used [n] the records that
+    entered and nis_records_left_out (flagged updates, non-finite sums)"""
+    recs, ts = ctx.innov_read()
+    st = ctx.innov_stats()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["nis_per_dof"] = np.where(st["frame_dof"] > 0, st["frame_nis"] / st["frame_dof"], np.nan)
+        out["nis_per_dof_seq"] = np.where(st["filt_dof"] > 0, st["filt_nis"] / st["filt_dof"], np.nan)
+    out["innovation"] = dict(recs=recs, ts=ts, stats=st)
+    out["nis_used"] = st["frame_used"]
+    out["nis_records_left_out"] = int(recs.size - st["frame_used"].sum())
+
+
 class HipBackend:
     """The product path: every numeric step is a C-ABI call on the resident state (fails loudly without the
     library / a GPU - there is no host fallback)."""
@@ -294,6 +309,7 @@ class HipBackend:
         self.ctx.set_scene(poses0, groups, feats)
         self.Qimu, self.Qmodel = cfg.Qimu_matrix(), cfg.Qmodel_matrix()
         self.pool_on = False
+        self.innov_on, self.frame_ts = False, 0   # innovation log: on / the stamp (ns) of the frame update() records under
         if cfg.feature_init == "subfilter":
             self.enable_pool()
 
@@ -360,6 +376,8 @@ class HipBackend:
         # a filter whose S was not positive definite keeps its prior P and absorbs nothing (device side); surfaced here
         self.last_status = self.ctx.get_status(check=False)
         self.n_not_spd = getattr(self, "n_not_spd", 0) + int((self.last_status != 0).sum())
+        if self.innov_on:   # between the update and AbsorbError, which consumes dx
+            self.ctx.innov_record(self.frame_ts, self.B)
         self.ctx.absorb_error()
         return mask
 
@@ -383,6 +401,12 @@ class HipBackend:
         """the whole log in one read -> dict(ts [n] ns, Rsb [n, B, 3, 3], Tsb / Vsb / bg / ba [n, B, 3], status [n, B],
         cov [n, B, k, k], cols [k])"""
         return _trajectory(self.ctx)
+
+    def enable_innovation_log(self, T_max):
+        """device log of T_max frames of every update's NIS (xivo_hip_innov_config); update() then records between the update
+        and absorb_error, stamped with frame_ts (ns, set by the driver before the frame); 0 releases it"""
+        self.ctx.innov_config(T_max)
+        self.innov_on = T_max > 0
 
     def enable_map_log(self, T_max, n_out=None, world_cov=True):
         """device log of T_max frames of the in-state features (xivo_hip_map_config): the best n_out per filter (default: all
@@ -704,7 +728,7 @@ def initial_poses(cfg, sims, t0=0.0):
 
 
 def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0,
-            timers=None, trajectory_log=False, map_log=False, rpe_dt=1.0):
+            timers=None, trajectory_log=False, map_log=False, rpe_dt=1.0, innovation_log=False):
     """The loop of scripts/pyxivo_pcw.py:117-163 for B = len(sims) sequences at once.
     -> dict(ts [n] ns, Tsb [n x B x 3], Wsb [n x B x 3], gt_Tsb [n x B x 3], runner, backend)
     trajectory_log (True, or the error-state columns to keep): the estimate of every frame is recorded on the device
@@ -715,7 +739,10 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     map_log: the in-state features of every frame are recorded on the device after the frame (xivo_hip_map_record) and read
     once at the end; the runner's slot book gives the track id of each, the worlds the true point. Adds `map` (pts, n_pts, ids,
     gt), landmark_err3 / landmark_nees / landmark_anees / landmarks_used, anees_landmark and landmarks_scored_mean. Off:
-    nothing changes."""
+    nothing changes.
+    innovation_log: every frame's update records its NIS on the device (HipBackend.enable_innovation_log) and the log is read
+    once at the end: adds `innovation`, nis_per_dof [n], nis_per_dof_seq [B], nis_used [n], nis_records_left_out
+    (_innovation). A backend without enable_innovation_log (the oracle) leaves the keys out."""
     B = len(sims)
     K = np.array([[cfg.cam["fx"], 0, cfg.cam["cx"]], [0, cfg.cam["fy"], cfg.cam["cy"]], [0, 0, 1.0]])
     Rbc = so3_exp(cfg.Wbc)
@@ -731,6 +758,9 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     if trajectory_log:
         be.enable_trajectory_log((n_imu + every - 1) // every, _traj_cols(trajectory_log))
     mlog = _MapLog(be.ctx, (n_imu + every - 1) // every, cfg.n_features, B) if map_log else None
+    ilog = bool(innovation_log) and hasattr(be, "enable_innovation_log")
+    if ilog:
+        be.enable_innovation_log((n_imu + every - 1) // every)
     for k in range(n_imu):
         t = k * imu_dt
         if k > 0:
@@ -743,6 +773,8 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
                 Rsb, Tsb = sims[b].gsb(t)
                 tracks.append(worlds[b].generate_measurements(Rsb @ Rbc, Rsb @ cfg.Tbc + Tsb, K, cfg.cam["cols"],
                                                               cfg.cam["rows"], noise_vision_std))
+            if ilog:
+                be.frame_ts = int(round(t * 1e9))
             runner.frame(feeder.take(), tracks)
             ts.append(int(round(t * 1e9)))
             if trajectory_log:
@@ -758,6 +790,8 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     out = dict(ts=np.array(ts), gt_Tsb=np.array(gt_T), runner=runner, backend=be)
     if mlog is not None:
         mlog.finish(out)
+    if ilog:
+        _innovation(be.ctx, out)
     if trajectory_log:
         traj = be.trajectory()
         est_T, est_W = traj["Tsb"], [[so3_log(r) for r in R] for R in traj["Rsb"]]
@@ -766,10 +800,12 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     return out
 
 
-def run_pcw_cpp(cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0, device=0):
+def run_pcw_cpp(cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0, device=0,
+                innovation_log=False):
     """run_pcw with the C++ host side: the same messages go to xivo::hip::BatchEstimator (xivo_amd/host/batch_estimator.h)
     through its InertialMeas / VisualMeasPointCloud entry points instead of ImuFeeder + SequenceRunner.
-    -> dict(ts, Tsb, Wsb, gt_Tsb, estimator)"""
+    -> dict(ts, Tsb, Wsb, gt_Tsb, estimator); innovation_log: as in run_pcw, recorded by the C++ frame
+    (BatchEstimator::EnableInnovationLog)"""
     from .batch import BatchEstimator
     B = len(sims)
     K = np.array([[cfg.cam["fx"], 0, cfg.cam["cx"]], [0, cfg.cam["fy"], cfg.cam["cy"]], [0, 0, 1.0]])
@@ -777,6 +813,8 @@ def run_pcw_cpp(cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04
     est = BatchEstimator(cfg, B, initial_poses(cfg, sims), cfg.P_init(), device=device)
     n_imu = int(round(total_time / imu_dt)); every = int(round(vision_dt / imu_dt))
     ts, est_T, est_W, gt_T = [], [], [], []
+    if innovation_log:
+        est.enable_innovation_log((n_imu + every - 1) // every)
     for k in range(n_imu):
         t = k * imu_dt
         m = [s.meas(t) for s in sims]
@@ -791,16 +829,20 @@ def run_pcw_cpp(cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04
             R, T = est.gsb()
             ts.append(int(round(t * 1e9))); est_T.append(T); est_W.append(np.array([so3_log(r) for r in R]))
             gt_T.append(np.array([s.gsb(t)[1] for s in sims]))
-    return dict(ts=np.array(ts), Tsb=np.array(est_T), Wsb=np.array(est_W), gt_Tsb=np.array(gt_T), estimator=est)
+    out = dict(ts=np.array(ts), Tsb=np.array(est_T), Wsb=np.array(est_W), gt_Tsb=np.array(gt_T), estimator=est)
+    if innovation_log:
+        _innovation(L.Context.borrow(est.host.xivo_batch_ctx(est.h), cfg.N, 2 * cfg.n_features, B), out)
+    return out
 
 
 def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0, npts=1000, seed=0, device=0,
-                  timers=None, trajectory_log=False, map_log=False, rpe_dt=1.0):
+                  timers=None, trajectory_log=False, map_log=False, rpe_dt=1.0, innovation_log=False):
     """Thousands of sequences end to end: the vectorised simulators of xivo_amd/pcw.py (BatchTrajectorySim, BatchPCW) feed
     xivo::hip::BatchEstimator message by message. -> dict(ts, Tsb [n x B x 3], gt_Tsb, estimator)
     trajectory_log: as in run_pcw - one record launch per frame on the estimator's context and one read at the end instead of
     a pose download per frame; adds `trajectory`, err6 / nees / anees / nees_used and ate_aligned / ate_raw / rpe_pos / rpe_rot.
-    map_log: as in run_pcw, on the estimator's context; the slot book is the estimator's (BatchEstimator.book)."""
+    map_log: as in run_pcw, on the estimator's context; the slot book is the estimator's (BatchEstimator.book).
+    innovation_log: as in run_pcw; the C++ frame records between its update and AbsorbError (BatchEstimator::EnableInnovationLog)."""
     import time
     from .batch import BatchEstimator
     from .pcw import BatchPCW, BatchTrajectorySim
@@ -826,6 +868,10 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     if map_log:
         mctx = ctx if ctx is not None else L.Context.borrow(host.xivo_batch_ctx(est.h), cfg.N, 2 * cfg.n_features, B)
         mlog = _MapLog(mctx, (n_imu + every - 1) // every, cfg.n_features, B)
+    ictx = None
+    if innovation_log:
+        est.enable_innovation_log((n_imu + every - 1) // every)
+        ictx = ctx if ctx is not None else L.Context.borrow(host.xivo_batch_ctx(est.h), cfg.N, 2 * cfg.n_features, B)
     tm = timers if timers is not None else {}
     for k in range(n_imu):
         t = k * imu_dt
@@ -854,6 +900,8 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     out = dict(ts=np.array(ts), gt_Tsb=np.array(gt_T), estimator=est)
     if mlog is not None:
         mlog.finish(out)
+    if ictx is not None:
+        _innovation(ictx, out)
     if ctx is not None:
         traj = _trajectory(ctx)
         est_T = traj["Tsb"]
