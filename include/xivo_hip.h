@@ -895,6 +895,70 @@ int xivo_hip_edit_batch(xivo_hip_ctx* ctx, int F, int n_ops, const xivo_edit_op*
  * tracked in this frame / absent entry). Sets the list length F like xivo_hip_edit_batch. */
 int xivo_hip_set_pixels(xivo_hip_ctx* ctx, int b0, int nb, int F, const double* xp);
 
+/* ---- device-resident feature life cycle ("immediate" mode; opt-in) -------------------------------------------------------
+ * What a sequence driver otherwise decides on the host per filter and frame and sends down as op lists (xivo_hip_edit_batch +
+ * xivo_hip_set_pixels): matching the tracker's ids to the in-state slots, removing the features the tracker dropped
+ * (ProcessTracks, src/manager.cpp:152-169) or the gate rejected (src/update.cpp:105-113) together with the groups they leave
+ * empty (RemoveGroupFromState, src/estimator.cpp:745-759), and admitting new features with a new group
+ * (SelectAndAddNewFeatures, src/manager.cpp:332-450; AddGroupToState / AddFeatureToState, src/estimator.cpp:801-846).
+ * One workgroup per filter; the slot book lives on the device: feat_id[F_max] (track id held by feature slot j, -1: free; list
+ * position j is feature slot j), group_refs[n_groups] (-1: free group slot, else the in-state features anchored there) and
+ * six counters per filter. A feature's reference group is the resident feats[j].ref_sind. A frame is
+ *   xivo_hip_life_begin -> update (xivo_hip_filter_update, or mh_gate / one_point_ransac / stack / update_joseph)
+ *   -> xivo_hip_absorb_error -> xivo_hip_life_end
+ * and no call of it synchronises or downloads anything. The results equal those of the op lists bit for bit, except x[2] =
+ * log z of a new feature, where the device's log and libm's may differ in the last place. */
+#define XIVO_LIFE_MAX_TRACKS 2048   /* tracks per filter and frame the kernels' LDS plan holds (ids 16 KiB + flags 8 KiB) */
+#define XIVO_LIFE_MAX_SLOTS 256     /* feature slots / group slots per filter of that plan */
+typedef struct {
+  int tracks_max;          /* most tracks one filter brings in a frame; 0 releases the book and the staging */
+  int min_new_features;    /* admit only with at least this many free feature slots, unless the state is empty */
+  double min_depth, max_depth;   /* a candidate's depth lies strictly between them */
+  double var_xyz[3];       /* diagonal of a new feature's 3 x 3 covariance (std^2, computed by the host) */
+} xivo_life_opts;
+typedef struct {
+  long long updates;       /* frames in which the filter held a feature at its update */
+  long long rejected;      /* features the gate rejected */
+  long long dropped;       /* features the tracker dropped */
+  long long admitted;      /* features that entered the state */
+  long long groups_added;
+  long long not_spd;       /* frames whose update status was non-zero */
+} xivo_life_stats;
+/* (Re-)allocates the book (all slots free, counters 0), the device copy of one frame's tracks and two page-locked staging
+ * blocks - everything the frame calls need. Each of the three blocks holds batch_max * tracks_max tracks of 32 bytes (id, u, v,
+ * depth) plus batch_max + 1 offsets, whatever a frame then brings: size tracks_max by the frames, not by the cap. XIVO_HIP_ERR_INVALID: a feature pool is configured on the context, no layout is set,
+ * tracks_max > XIVO_LIFE_MAX_TRACKS (or negative), min_depth / max_depth / var_xyz not finite; XIVO_HIP_ERR_UNSUPPORTED: a
+ * layout with more than XIVO_LIFE_MAX_SLOTS feature or group slots, a camera other than XIVO_CAM_PINHOLE (a new feature is
+ * un-projected as ((u - cx) / fx, (v - cy) / fy)). The camera is the context's xivo_cam, the depth parametrisation
+ * XIVO_HIP_FLAG_INVDEPTH. */
+int xivo_hip_life_config(xivo_hip_ctx* ctx, const xivo_life_opts* opts);
+/* Seeds the ids of filters [b0, b0 + nb) for a scene placed with xivo_hip_set_scene: feat_id is [nb][F] with F the resident
+ * list length; an id must be >= 0 exactly where the resident entry is present, and a present entry at position j must sit in
+ * feature slot j (else XIVO_HIP_ERR_INVALID, nothing changed). group_refs are counted from the resident sind / ref_sind. A
+ * set-up call: reads the resident features back and synchronises. */
+int xivo_hip_life_set_book(xivo_hip_ctx* ctx, int b0, int nb, const long long* feat_id);
+/* The book of filters [b0, b0 + nb): feat_id [nb][F], feat_ref [nb][F] (-1: free), group_refs [nb][n_groups]; any may be
+ * NULL. Synchronises. */
+int xivo_hip_life_get_book(xivo_hip_ctx* ctx, int b0, int nb, long long* feat_id, int* feat_ref, int* group_refs);
+/* Before the update. The frame's tracks of filters [0, B): off [B + 1] (off[0] = 0, non-decreasing), ids [n], meas [n][3] =
+ * (u, v, depth), n = off[B]. Per filter: an in-state feature whose id is among the tracks gets that track's pixel (an id that
+ * occurs twice: the last occurrence's), every other in-state feature leaves the state, groups left empty leave with them;
+ * updates[b] is incremented where a feature is left. Sets the list length F (F <= n_features) like xivo_hip_edit_batch.
+ * XIVO_HIP_ERR_INVALID before anything is launched or changed: not configured, a pool configured since, a filter with more
+ * than tracks_max tracks, a malformed off, life_begin twice without life_end. The host arrays are copied to page-locked
+ * staging before the call returns (two buffers: the copy waits only for the upload of the frame before the previous one). */
+int xivo_hip_life_begin(xivo_hip_ctx* ctx, int B, int F, const int* off, const long long* ids, const double* meas);
+/* After the update and xivo_hip_absorb_error, with the B of life_begin. Reads the resident inlier mask (what xivo_hip_get_gate
+ * downloads) and the update status. Per filter, in order: in-state features with a zero mask leave (rejected), their tracks
+ * are candidates again; empty groups are discarded; g = lowest free group slot; nothing is admitted without g, or with fewer
+ * than min_new_features free slots while the state is not empty; candidates = tracks not in the state with min_depth < depth <
+ * max_depth, by ascending id, ties by position; with a candidate, AddGroupToState(g) from the current pose, then the first
+ * min(#free, #candidates) enter the free slots in ascending slot order with x = ((u - cx) / fx, (v - cy) / fy, log z or 1 / z),
+ * xp = (u, v), P block = diag(var_xyz) after zeroing its rows and columns (as XIVO_EDIT_ADD_FEATURE). */
+int xivo_hip_life_end(xivo_hip_ctx* ctx, int B);
+/* The counters of filters [b0, b0 + nb). Synchronises. */
+int xivo_hip_life_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_life_stats* out);
+
 /* ---- covariance propagation tail (src/rk4.cpp:92-102, src/estimator.cpp:590) */
 /* P_mm <- Pmm_new ; P_ms <- Phi P_ms ; P_sm <- P_sm Phi^T. Phi and Pmm_new
  * are nm x nm (nm = kMotionSize: 23, or up to 40 for the online-calibration builds), one pair per filter. */

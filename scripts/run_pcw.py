@@ -71,12 +71,17 @@ def main():
                          "(one read at the end) and report nis_per_dof: the ensemble's sum of NIS over its sum of counted "
                          "rows per frame, averaged over the frames (1 for a consistent filter; needs no ground truth), its "
                          "median / p90 / max over the sequences and the records left out (-host python and -vectorized)")
+    ap.add_argument("-lifecycle", default="host", choices=["host", "device"],
+                    help="who runs the per-frame feature life cycle: the host side (op lists, the default) or the device "
+                         "(xivo_hip_life_begin / _end: nothing is downloaded during a frame)")
     a = ap.parse_args()
+    # (a sequence never brings more tracks than its world has points)
+    life = dict(lifecycle=a.lifecycle, tracks_max=min(a.npts, sequence.L.LIFE_MAX_TRACKS))
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         from xivo_amd.shard import spawn_ranks
         sys.exit(spawn_ranks([os.path.abspath(__file__)] + sys.argv[1:], a.gpus))
     if a.vectorized:
-        cfg = sequence.SequenceConfig(integration_method=a.integration_method, fix_group_block=not a.as_coded_group_block)
+        cfg = sequence.SequenceConfig(integration_method=a.integration_method, fix_group_block=not a.as_coded_group_block, **life)
         tm = {}
         t0 = time.perf_counter()
         out = sequence.run_pcw_batch(cfg, a.sequences, total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
@@ -88,11 +93,13 @@ def main():
         ate = np.sqrt(np.mean(np.sum((out["Tsb"] - out["gt_Tsb"]) ** 2, axis=2), axis=0))
         print(json.dumps({
             "sequences": a.sequences, "frames_per_sequence": frames, "N": cfg.N, "integration": a.integration_method,
-            "host": "cpp, vectorised simulators",
+            "host": "cpp, vectorised simulators", "lifecycle": a.lifecycle,
             "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
             **_consistency(out),
             "updates": st["updates"], "mh_rejected": st["mh_rejected"], "wall_s": wall, "simulator_s": tm.get("sim", 0.0),
             "frame_calls_s": tm.get("frame", 0.0), "host_cpp_lifecycle_s": st["host_seconds"],
+            # -lifecycle device: the part of frame_calls_s before the stream is waited for (the frame is only enqueued)
+            **({"frame_enqueue_s": tm["frame_enqueue"]} if "frame_enqueue" in tm else {}),
             "frames_per_s_in_frame_calls": a.sequences * frames / tm["frame"],
             "ms_per_frame_of_all_sequences": 1e3 * tm["frame"] / frames}))
         return
@@ -106,7 +113,7 @@ def main():
     from xivo_amd.shard import sequence_to_gpu
     mine = [s_ for s_ in range(a.sequences) if sequence_to_gpu(s_, world) == rank]
     B = len(mine)
-    cfg = sequence.SequenceConfig(integration_method=a.integration_method, fix_group_block=not a.as_coded_group_block)
+    cfg = sequence.SequenceConfig(integration_method=a.integration_method, fix_group_block=not a.as_coded_group_block, **life)
     worlds = [pcw.RandomPCW(npts=a.npts, seed=b) for b in mine]
     sims = [pcw.TrajectorySim("lissajous" if b % 2 == 0 else "trefoil", rate=0.08 + 0.04 * (b % 7) / 7, seed=1000 + b)
             for b in mine]
@@ -128,6 +135,11 @@ def main():
                                total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
                                noise_vision_std=a.noise_vision_std, timers=timers, trajectory_log=a.traj_log,
                                map_log=a.map_log, rpe_dt=a.rpe_dt, innovation_log=a.innov_log)
+        r_ = out["runner"]
+
+        class _R:      # (read before the context goes: the device life cycle keeps the counters there)
+            n_updates, n_rejected = r_.n_updates, r_.n_rejected
+        out["runner"] = _R
         out["backend"].close()
     wall = time.perf_counter() - t0
     frames = len(out["ts"])
@@ -151,6 +163,7 @@ def main():
     print(json.dumps({
         "sequences": B, "n_gpus": world, "frames_per_sequence": frames, "imu_samples_per_frame": int(round(a.vision_dt / a.imu_dt)),
         "N": cfg.N, "max_features": cfg.n_features, "integration": a.integration_method, "host": a.host,
+        "lifecycle": a.lifecycle,
         "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
         **_consistency(out),
         "updates": n_upd, "mh_rejected": n_rej,

@@ -57,6 +57,7 @@ def load_host_library():
         _HOST.xivo_batch_enable_depth_init.argtypes = [C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_init_z.argtypes = [C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_innov_log.argtypes = [C.c_void_p, C.c_int]
+        _HOST.xivo_batch_enable_device_lifecycle.argtypes = [C.c_void_p, C.c_int]
     return _HOST
 
 
@@ -87,6 +88,12 @@ class BatchEstimator:
         if self.host.xivo_batch_create(c.ctypes.data, B, device, poses0.ctypes.data, P0.ctypes.data, C.byref(h)) != 0:
             raise RuntimeError("xivo_batch_create failed")
         self.h = h
+        self.device_lifecycle = getattr(cfg, "lifecycle", "host") == "device"
+        self.want_mask = not self.device_lifecycle   # device life cycle: no mask download unless asked for
+        if self.device_lifecycle:
+            if getattr(cfg, "feature_init", "immediate") != "immediate":
+                raise ValueError("lifecycle='device' runs the 'immediate' life cycle only")
+            self.enable_device_lifecycle(cfg.tracks_max)
         if getattr(cfg, "feature_init", "immediate") == "subfilter":
             sc = np.zeros(1, dtype=batch_subfilter_cfg_dtype)
             sc["initial_z"], sc["remove_outlier_counter"] = cfg.initial_z, cfg.remove_outlier_counter
@@ -126,6 +133,19 @@ class BatchEstimator:
         if self.host.xivo_batch_innov_log(self.h, int(T_max)) != 0:
             raise RuntimeError("xivo_batch_innov_log failed")
 
+    def enable_device_lifecycle(self, tracks_max):
+        """BatchEstimator::EnableDeviceLifecycle: the slot book moves to the device (xivo_hip_life_*); VisualMeasPointCloud then
+        downloads nothing unless a mask is asked for, book() and stats() read the device"""
+        if self.host.xivo_batch_enable_device_lifecycle(self.h, int(tracks_max)) != 0:
+            raise RuntimeError("xivo_batch_enable_device_lifecycle failed")
+
+    def sync(self):
+        """wait for the estimator's stream (the device life cycle leaves a frame enqueued)"""
+        lib = L.load_library()
+        rc = lib.xivo_hip_sync(self.host.xivo_batch_ctx(self.h))
+        if rc != 0:
+            raise L.XivoHipError(rc, lib.xivo_hip_strerror(rc).decode())
+
     def close(self):
         if self.h:
             self.host.xivo_batch_destroy(self.h)
@@ -144,15 +164,17 @@ class BatchEstimator:
             raise RuntimeError("InertialMeas failed")
 
     def VisualMeasPointCloud(self, t, tracks):
-        """tracks: per filter (ids [n], xp_and_depths [n x 3]) -> inlier mask [B x F]"""
+        """tracks: per filter (ids [n], xp_and_depths [n x 3]) -> inlier mask [B x F] (None with the device life cycle unless
+        want_mask is set)"""
         off = np.zeros(self.B + 1, dtype=np.int32)
         off[1:] = np.cumsum([len(tr[0]) for tr in tracks])
         ids = np.ascontiguousarray(np.concatenate([np.asarray(tr[0], dtype=np.int64) for tr in tracks])) if off[-1] else np.zeros(1, dtype=np.int64)
         meas = np.ascontiguousarray(np.concatenate([np.asarray(tr[1], dtype=np.float64).reshape(-1, 3) for tr in tracks])) if off[-1] else np.zeros((1, 3))
-        mask = np.zeros((self.B, self.F), dtype=np.uint8)
-        if self.host.xivo_batch_visual(self.h, float(t), off.ctypes.data, ids.ctypes.data, meas.ctypes.data, mask.ctypes.data) != 0:
+        mask = np.zeros((self.B, self.F), dtype=np.uint8) if self.want_mask else None
+        if self.host.xivo_batch_visual(self.h, float(t), off.ctypes.data, ids.ctypes.data, meas.ctypes.data,
+                                       mask.ctypes.data if mask is not None else None) != 0:
             raise RuntimeError("VisualMeasPointCloud failed")
-        return mask.astype(bool)
+        return mask.astype(bool) if mask is not None else None
 
     def poses(self):
         p = np.zeros(self.B, dtype=L.pose_dtype)

@@ -165,6 +165,10 @@ void xivo_hip_destroy(xivo_hip_ctx* c) {
   c->mem.free_all();
   if (c->ell_flags_h) hipHostFree(c->ell_flags_h);
   if (c->pin_h) hipHostFree(c->pin_h);
+  for (int i = 0; i < 2; ++i) {   // the life cycle's page-locked staging (xivo_hip_life_config)
+    if (c->life_pin[i]) hipHostFree(c->life_pin[i]);
+    if (c->life_ev[i]) hipEventDestroy(c->life_ev[i]);
+  }
   for (auto& ep : c->pool) { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
   if (c->t0) hipEventDestroy(c->t0);
   if (c->t1) hipEventDestroy(c->t1);

@@ -7,6 +7,7 @@
 //   capi_score.hip      trajectory score: aligned / unaligned ATE and RPE of the logged poses against ground truth
 //   capi_map.hip        landmark log: per-frame in-state features, world positions and covariances, read-out, landmark NEES
 //   capi_innov.hip      innovation log: per-frame NIS / pre- and post-fit sums of every filter's update, read-out, ensemble sums
+//   capi_lifecycle.hip  device life cycle: the per-filter slot book, the two frame calls around the update, counters
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
 //
@@ -170,6 +171,16 @@ struct xivo_hip_ctx {
   void dx_set(int b0, int nb, bool v) { if (dx_ok.size() != (size_t)Bmax) dx_ok.assign((size_t)Bmax, 0); std::fill_n(dx_ok.begin() + b0, nb, (char)v); }
   void dx_clear() { std::fill(dx_ok.begin(), dx_ok.end(), (char)0); }
   bool dx_current(int B) const { return dx_ok.size() >= (size_t)B && std::all_of(dx_ok.begin(), dx_ok.begin() + B, [](char v) { return v != 0; }); }
+  // device life cycle (xivo_hip_life_*, capi_lifecycle.hip): the book [Bmax][life_ld] / [Bmax][n_groups] / [Bmax], null until
+  // xivo_hip_life_config; one device block of track storage (the frame between life_begin and life_end, life_B > 0: off | ids |
+  // meas of life_n tracks) and two page-locked staging blocks of that size, each with the event of its last upload; life_cur
+  // is the staging block the last life_begin filled
+  xivo_life_opts life_opts{};
+  long long* life_feat_id = nullptr; int* life_group_refs = nullptr; xivo_life_stats* life_stats = nullptr;
+  int life_ld = 0;
+  char* life_dev = nullptr; char* life_pin[2] = {nullptr, nullptr}; hipEvent_t life_ev[2] = {nullptr, nullptr};
+  size_t life_set_bytes = 0;
+  int life_cur = 0, life_B = 0, life_n = 0;
   std::vector<char> hstage;                        // host staging of d2h_rows
   char* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
   // one-filter plumbing call (xivo_hip_update_joseph_host): page-locked, device-mapped staging block owned by the context,

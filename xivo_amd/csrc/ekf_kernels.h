@@ -127,6 +127,24 @@ struct InnovStatsArgs {
 };
 int launch_innov_stats(const InnovStatsArgs& a, hipStream_t s);
 
+// ================================================================ lifecycle_kernels.hip: device life cycle (capi_lifecycle.hip)
+
+// one frame of every filter [0, batch): the resident scene and P, the filter's book (feat_id [batch][slot_ld], group_refs
+// [batch][n_groups], counters [batch]) and the frame's tracks (off [batch + 1]; ids, meas [off[batch]][3]). F <= slot_ld,
+// F <= XIVO_LIFE_MAX_SLOTS, n_groups <= XIVO_LIFE_MAX_SLOTS, every filter's track count <= XIVO_LIFE_MAX_TRACKS (the host
+// checks all four before a launch).
+struct LifeArgs {
+  double* P; long strideP; int ldp, Np; xivo_layout lay;
+  const xivo_pose_in* poses; xivo_group_in* groups; xivo_feat_in* feats; int Fmax, F;
+  long long* feat_id; int slot_ld; int* group_refs; xivo_life_stats* stats;
+  const int* off; const long long* ids; const double* meas;
+  // life_end only: the update's inlier mask (row stride mask_ld) and status, the admission options, the camera
+  const unsigned char* mask; int mask_ld; const int* status;
+  int min_new_features, invdepth; double min_depth, max_depth, var_xyz[3], fx, fy, cx, cy;
+};
+int launch_life_begin(const LifeArgs& a, int batch, hipStream_t s);
+int launch_life_end(const LifeArgs& a, int batch, hipStream_t s);
+
 // ================================================================ glevel_kernels.hip: feature-level kernels (capi_glevel.hip)
 
 struct SceneBuffers {

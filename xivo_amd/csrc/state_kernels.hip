@@ -12,6 +12,7 @@
 //  absorb_error_kernel  Estimator::AbsorbError             src/estimator.cpp:875-921
 //  mfma_peak_kernel     fp64 MFMA issue-rate probe (no reference counterpart)
 // (paths relative to the reference tree). Byte movers and one-workgroup-per-filter edits, no MFMA outside the probe.
+#include "edit_device.h"
 #include "ekf_kernels.h"
 #include "geometry_device.h"
 #include "p_unpack_device.h"
@@ -86,23 +87,7 @@ __global__ void p_diag_kernel(const double* P, int ldp, int N, double* out) {
 }
 
 // ---------------------------------------------------------------- batched resident edits (xivo_hip_edit_batch)
-__device__ __forceinline__ void edit_zero_rc(double* P, int ldp, int Np, int off, int len, int tid) {
-  for (int t = tid; t < Np; t += 256)
-    for (int r = 0; r < len; ++r) {
-      P[(off + r) + (long)t * ldp] = 0.0;
-      P[t + (long)(off + r) * ldp] = 0.0;
-    }
-  __syncthreads();
-}
-// rows, then columns (which re-read the rows just written): the order of src/estimator.cpp:808-816
-__device__ __forceinline__ void edit_copy_rc(double* P, int ldp, int Np, int dst, int src, int len, int tid) {
-  for (int t = tid; t < Np; t += 256)
-    for (int r = 0; r < len; ++r) P[(dst + r) + (long)t * ldp] = P[(src + r) + (long)t * ldp];
-  __syncthreads();
-  for (int t = tid; t < Np; t += 256)
-    for (int r = 0; r < len; ++r) P[t + (long)(dst + r) * ldp] = P[t + (long)(src + r) * ldp];
-  __syncthreads();
-}
+// (edit_zero_rc / edit_copy_rc: edit_device.h, shared with the device life cycle)
 // xivo_hip_set_pixels: one thread per (filter, list entry)
 __global__ void set_pixels_kernel(xivo_feat_in* feats, int Fmax, int F, const double* xp, int n) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;

@@ -144,13 +144,16 @@ void BatchEstimator::RunUpdate() {
   } else {
     Check(xivo_hip_filter_update(ctx_, B_, R, cfg_.MH_thresh, cfg_.MH_adjust_factor, cfg_.min_inliers, cfg_.use_MH_gating), "filter_update");
   }
-  Check(xivo_hip_get_gate(ctx_, B_, F, mask_.data(), nullptr), "get_gate");
+  if (!device_life_ || want_mask_) Check(xivo_hip_get_gate(ctx_, B_, F, mask_.data(), nullptr), "get_gate");
   // a filter whose S was not positive definite keeps its prior P and absorbs nothing (the device skips both); it is
   // counted and reported here - the reference's pivoted LDL^T cannot fail, so there is no reference behaviour to mirror
-  status_.resize(B_);
-  const int st = xivo_hip_get_status(ctx_, 0, B_, status_.data());
-  if (st == XIVO_HIP_ERR_NOT_SPD) { for (int b = 0; b < B_; ++b) n_not_spd_ += status_[b] != 0; }
-  else Check(st, "get_status");
+  // (device life cycle: xivo_hip_life_end counts it, nothing is downloaded)
+  if (!device_life_) {
+    status_.resize(B_);
+    const int st = xivo_hip_get_status(ctx_, 0, B_, status_.data());
+    if (st == XIVO_HIP_ERR_NOT_SPD) { for (int b = 0; b < B_; ++b) n_not_spd_ += status_[b] != 0; }
+    else Check(st, "get_status");
+  }
   // the update's innovation statistics need the dx AbsorbError is about to consume (Estimator::UpdateStep: between
   // UpdateJosephForm and AbsorbError)
   if (innov_log_) Check(xivo_hip_innov_record(ctx_, B_, (long long)std::llround(t_visual_ * 1e9), nullptr), "innov_record");
@@ -200,6 +203,16 @@ void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_
   if (subfilter_) {
     host_s_ += now_s() - t0;
     VisualSubfilter(off, ids, meas);
+    if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
+    return;
+  }
+  if (device_life_) {
+    // the whole life cycle on the device: the tracks go down as they came in, nothing comes back
+    host_s_ += now_s() - t0;
+    want_mask_ = mask_out != nullptr;
+    Check(xivo_hip_life_begin(ctx_, B_, F, off, reinterpret_cast<const long long*>(ids), meas), "life_begin");
+    RunUpdate();
+    Check(xivo_hip_life_end(ctx_, B_), "life_end");
     if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
     return;
   }
@@ -306,6 +319,7 @@ void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_
 }
 
 void BatchEstimator::EnableSubfilter(const SubfilterConfig& sc) {
+  if (device_life_) throw std::runtime_error("the device life cycle runs the immediate mode only");
   sc_ = sc;
   Check(xivo_hip_pool_config(ctx_, sc.pool_max, sc.anchor_max, &sc.opts, sc.remove_outlier_counter), "pool_config");
   pools_.assign(B_, PoolBook{});
@@ -314,6 +328,58 @@ void BatchEstimator::EnableSubfilter(const SubfilterConfig& sc) {
     pb.anc_used.assign(sc.anchor_max, 0); pb.anc_life.assign(sc.anchor_max, 0); pb.anc_link.assign(sc.anchor_max, -1);
   }
   subfilter_ = true;
+}
+
+void BatchEstimator::EnableDeviceLifecycle(int tracks_max) {
+  if (subfilter_) throw std::runtime_error("the device life cycle runs the immediate mode only");
+  if (tracks_max <= 0) {
+    // back to the host life cycle: the books and the counters come home before the device book is released
+    if (device_life_) {
+      for (int b = 0; b < B_; ++b) ReadBook(b);
+      n_updates_ += LifeCount(0); n_rejected_ += LifeCount(1); n_not_spd_ += LifeCount(5);
+    }
+    device_life_ = false;
+    xivo_life_opts off;
+    std::memset(&off, 0, sizeof(off));
+    Check(xivo_hip_life_config(ctx_, &off), "life_config");
+    return;
+  }
+  const double fx = cfg_.cam.fx, fy = cfg_.cam.fy;
+  const double fl = 0.5 * std::sqrt(fx * fx + fy * fy);   // Camera::GetFocalLength() (src/camera_manager.cpp:56)
+  const double sd[3] = {cfg_.initial_std_x / fl, cfg_.initial_std_y / fl, cfg_.initial_std_z};
+  xivo_life_opts o;
+  std::memset(&o, 0, sizeof(o));
+  o.tracks_max = tracks_max; o.min_new_features = cfg_.min_new_features;
+  o.min_depth = cfg_.min_depth; o.max_depth = cfg_.max_depth;
+  for (int i = 0; i < 3; ++i) o.var_xyz[i] = sd[i] * sd[i];   // P_ = diag(std)^2 (src/feature.cpp:158-159)
+  Check(xivo_hip_life_config(ctx_, &o), "life_config");
+  // adopt the book kept so far (all free before the first frame)
+  const int F = cfg_.n_features;
+  std::vector<long long> fid((size_t)B_ * F);
+  for (int b = 0; b < B_; ++b)
+    for (int j = 0; j < F; ++j) fid[(size_t)b * F + j] = books_[b].feat_id[j];
+  Check(xivo_hip_life_set_book(ctx_, 0, B_, fid.data()), "life_set_book");
+  device_life_ = true;
+}
+
+void BatchEstimator::ReadBook(int b) {
+  const int F = cfg_.n_features;
+  Book& bk = books_[b];
+  std::vector<long long> fid(F);
+  Check(xivo_hip_life_get_book(ctx_, b, 1, fid.data(), bk.feat_ref.data(), bk.group_refs.data()), "life_get_book");
+  bk.id2slot.clear();
+  for (int j = 0; j < F; ++j) { bk.feat_id[j] = fid[j]; if (fid[j] >= 0) bk.id2slot[fid[j]] = j; }
+}
+
+long BatchEstimator::LifeCount(int which) const {
+  std::vector<xivo_life_stats> st(B_);
+  if (xivo_hip_life_stats(ctx_, 0, B_, st.data()) != XIVO_HIP_OK) throw std::runtime_error("life_stats");
+  long n = 0;
+  for (const auto& s : st) {
+    const long long v[6] = {s.updates, s.rejected, s.dropped, s.admitted, s.groups_added, s.not_spd};
+    n += (long)v[which];
+  }
+  return n;
 }
 
 void BatchEstimator::EnableDepthInit(const DepthInitConfig& dc) {
@@ -522,14 +588,18 @@ int xivo_batch_poses(void* h, xivo_pose_in* out) {
 int xivo_batch_book(void* h, int b, long long* feat_id, int* feat_ref, int* group_refs) {
   auto* e = static_cast<xivo::hip::BatchEstimator*>(h);
   if (b < 0 || b >= e->B()) return -1;
-  const auto& bk = e->book(b);
-  for (size_t j = 0; j < bk.feat_id.size(); ++j) { feat_id[j] = bk.feat_id[j]; feat_ref[j] = bk.feat_ref[j]; }
-  for (size_t g = 0; g < bk.group_refs.size(); ++g) group_refs[g] = bk.group_refs[g];
-  return 0;
+  try {
+    const auto& bk = e->book(b);   // (device life cycle: read from the device)
+    for (size_t j = 0; j < bk.feat_id.size(); ++j) { feat_id[j] = bk.feat_id[j]; feat_ref[j] = bk.feat_ref[j]; }
+    for (size_t g = 0; g < bk.group_refs.size(); ++g) group_refs[g] = bk.group_refs[g];
+    return 0;
+  } catch (const std::exception&) { return -1; }
 }
 void xivo_batch_stats(void* h, long* n_updates, long* n_rejected, double* host_seconds) {
   auto* e = static_cast<xivo::hip::BatchEstimator*>(h);
-  *n_updates = e->n_updates(); *n_rejected = e->n_rejected(); *host_seconds = e->host_seconds();
+  *host_seconds = e->host_seconds();
+  try { *n_updates = e->n_updates(); *n_rejected = e->n_rejected(); }   // (device life cycle: read from the device)
+  catch (const std::exception&) { *n_updates = -1; *n_rejected = -1; }
 }
 int xivo_batch_cfg_size(void) { return (int)sizeof(xivo_batch_cfg); }   // checked against the ctypes mirror (tests)
 struct xivo_batch_subfilter_cfg {   // flat mirror of xivo::hip::BatchEstimator::SubfilterConfig
@@ -582,7 +652,13 @@ int xivo_batch_innov_log(void* h, int T_max) {
   if (!h) return -1;
   try { static_cast<xivo::hip::BatchEstimator*>(h)->EnableInnovationLog(T_max); return 0; } catch (const std::exception&) { return -1; }
 }
-long xivo_batch_not_spd(void* h) { return static_cast<xivo::hip::BatchEstimator*>(h)->n_not_spd(); }
+int xivo_batch_enable_device_lifecycle(void* h, int tracks_max) {
+  if (!h) return -1;
+  try { static_cast<xivo::hip::BatchEstimator*>(h)->EnableDeviceLifecycle(tracks_max); return 0; } catch (const std::exception&) { return -1; }
+}
+long xivo_batch_not_spd(void* h) {
+  try { return static_cast<xivo::hip::BatchEstimator*>(h)->n_not_spd(); } catch (const std::exception&) { return -1; }
+}
 void* xivo_batch_ctx(void* h) { return static_cast<xivo::hip::BatchEstimator*>(h)->ctx(); }
 
 }  // extern "C"

@@ -65,9 +65,9 @@ class BatchEstimator {
   int B() const { return B_; }
   const BatchConfig& cfg() const { return cfg_; }
   xivo_hip_ctx* ctx() { return ctx_; }
-  long n_updates() const { return n_updates_; }
-  long n_not_spd() const { return n_not_spd_; }   // updates skipped because S was not positive definite
-  long n_rejected() const { return n_rejected_; }
+  long n_updates() const { return n_updates_ + (device_life_ ? LifeCount(0) : 0); }
+  long n_not_spd() const { return n_not_spd_ + (device_life_ ? LifeCount(5) : 0); }   // updates skipped because S was not positive definite
+  long n_rejected() const { return n_rejected_ + (device_life_ ? LifeCount(1) : 0); }
   double host_seconds() const { return host_s_; }   // time spent in the host-side life cycle (not in C-ABI calls)
 
   // the reference's life cycle of a new track on the device-resident feature pool (xivo_hip_pool_*), as
@@ -98,6 +98,13 @@ class BatchEstimator {
   // reads it through ctx() (xivo_hip_innov_read / _stats).
   void EnableInnovationLog(int T_max);
   long n_pool_dropped() const { return n_pool_dropped_; }   // new tracks that found no free pool entry or anchor
+  // the "immediate" life cycle on the device (xivo_hip_life_*): the slot book moves to the context, VisualMeasPointCloud hands
+  // the frame's tracks down (at most tracks_max per filter) and makes no get_gate / get_status call unless mask_out is given;
+  // book(b), n_updates(), n_rejected() and n_not_spd() then read the device. The book kept so far is adopted
+  // (xivo_hip_life_set_book). tracks_max = 0 switches back: books and counters are read home, the device book is released.
+  // Not with EnableSubfilter, in either order (both throw).
+  void EnableDeviceLifecycle(int tracks_max);
+  bool device_lifecycle() const { return device_life_; }
 
   struct Book {                                     // one filter's slots
     std::vector<int> group_refs;                    // -1 free, else number of in-state features anchored there
@@ -105,7 +112,7 @@ class BatchEstimator {
     std::vector<int> feat_ref;
     std::unordered_map<int64_t, int> id2slot;
   };
-  const Book& book(int b) const { return books_[b]; }
+  const Book& book(int b) { if (device_life_) ReadBook(b); return books_[b]; }
 
  private:
   void Check(int rc, const char* what);
@@ -113,6 +120,9 @@ class BatchEstimator {
   void DiscardEmptyGroups(int b, std::vector<xivo_edit_op>& ops);
   void RunUpdate();
   void VisualSubfilter(const int* off, const int64_t* ids, const double* meas);
+  void ReadBook(int b);                 // device life cycle: books_[b] <- xivo_hip_life_get_book
+  long LifeCount(int which) const;      // device life cycle: one of xivo_life_stats' counters summed over the filters
+  bool device_life_ = false, want_mask_ = false;
 
   struct PoolBook {                                 // one filter's feature pool: tracks per entry, anchors and their links
     std::vector<int64_t> ent_id;                    // -1 free

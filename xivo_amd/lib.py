@@ -116,6 +116,13 @@ innov_opts_dtype = np.dtype([("T_max", "i4")])
 innov_rec_dtype = np.dtype([("nis", "f8"), ("prefit", "f8"), ("postfit", "f8"), ("inn_max", "f8"), ("dx_max", "f8"),
                             ("dof", "i4"), ("rows", "i4"), ("flags", "i4"), ("reserved", "i4"), ("reserved2", "f8")])
 assert innov_rec_dtype.itemsize == 64 and innov_opts_dtype.itemsize == 4
+# device life cycle (include/xivo_hip.h): xivo_life_opts, xivo_life_stats
+LIFE_MAX_TRACKS, LIFE_MAX_SLOTS = 2048, 256
+life_opts_dtype = np.dtype([("tracks_max", "i4"), ("min_new_features", "i4"), ("min_depth", "f8"), ("max_depth", "f8"),
+                            ("var_xyz", "f8", 3)])
+life_stats_dtype = np.dtype([("updates", "i8"), ("rejected", "i8"), ("dropped", "i8"), ("admitted", "i8"), ("groups_added", "i8"),
+                             ("not_spd", "i8")])
+assert life_opts_dtype.itemsize == 48 and life_stats_dtype.itemsize == 48
 
 
 def lib_path():
@@ -234,6 +241,12 @@ _SIGS = {
     "xivo_hip_innov_read": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "xivo_hip_innov_stats": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.c_void_p, C.c_void_p],
+    "xivo_hip_life_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_life_set_book": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_life_get_book": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_life_begin": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_life_end": [C.c_void_p, C.c_int],
+    "xivo_hip_life_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
 }
 HOST_P_RESIDENT, HOST_KEEP_P = 1, 2
 
@@ -994,6 +1007,51 @@ class Context:
         self._check(self.lib.xivo_hip_innov_stats(self.h, int(b0), nb, int(t0), nt, _ptr(out["frame_nis"]), _ptr(out["frame_dof"]),
                                                   _ptr(out["frame_used"]), _ptr(out["filt_nis"]), _ptr(out["filt_dof"]),
                                                   _ptr(out["filt_used"])))
+        return out
+
+    # ---- device life cycle (xivo_hip_life_*)
+    def life_config(self, tracks_max, min_depth=0.05, max_depth=10.0, min_new_features=3, var_xyz=(1.0, 1.0, 1.0)):
+        """the device-resident slot book and the track staging of the "immediate" life cycle: at most tracks_max tracks per
+        filter and frame (<= LIFE_MAX_TRACKS); var_xyz: diagonal of a new feature's covariance; tracks_max = 0 releases it"""
+        o = np.zeros(1, dtype=life_opts_dtype)
+        o["tracks_max"], o["min_new_features"], o["min_depth"], o["max_depth"] = int(tracks_max), int(min_new_features), min_depth, max_depth
+        o["var_xyz"] = np.asarray(var_xyz, dtype=np.float64)
+        self._check(self.lib.xivo_hip_life_config(self.h, _ptr(o)))
+
+    def life_set_book(self, feat_id, b0=0):
+        """feat_id [nb, F]: the track ids of the scene placed with set_scene (-1: absent entry)"""
+        feat_id = np.ascontiguousarray(feat_id, dtype=np.int64)
+        self._check(self.lib.xivo_hip_life_set_book(self.h, int(b0), feat_id.shape[0], _ptr(feat_id)))
+
+    def life_get_book(self, b0=0, nb=None):
+        """-> (feat_id [nb, F] int64, feat_ref [nb, F], group_refs [nb, n_groups]); one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        feat_id = np.full((nb, self.F), -1, dtype=np.int64)
+        feat_ref = np.full((nb, self.F), -1, dtype=np.int32)
+        group_refs = np.full((nb, self.layout.n_groups), -1, dtype=np.int32)
+        self._check(self.lib.xivo_hip_life_get_book(self.h, int(b0), nb, _ptr(feat_id), _ptr(feat_ref), _ptr(group_refs)))
+        return feat_id, feat_ref, group_refs
+
+    def life_begin(self, F, off, ids, meas, B=None):
+        """before the update (asynchronous): the frame's tracks as off [B + 1] int32, ids [n] int64, meas [n, 3] (u, v, depth)"""
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        meas = np.ascontiguousarray(meas, dtype=np.float64)
+        B = off.size - 1 if B is None else int(B)
+        if off.size != B + 1 or ids.size != int(off[-1]) or meas.size != 3 * ids.size:
+            raise ValueError("off [B + 1], ids [off[B]], meas [off[B], 3]")
+        self._check(self.lib.xivo_hip_life_begin(self.h, B, int(F), _ptr(off), _ptr(ids), _ptr(meas)))
+        self.F = int(F)
+
+    def life_end(self, B=None):
+        """after the update and absorb_error (asynchronous)"""
+        self._check(self.lib.xivo_hip_life_end(self.h, self.batch if B is None else int(B)))
+
+    def life_stats(self, b0=0, nb=None):
+        """-> [nb] life_stats_dtype: the per-filter counters; one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        out = np.zeros(nb, dtype=life_stats_dtype)
+        self._check(self.lib.xivo_hip_life_stats(self.h, int(b0), nb, _ptr(out)))
         return out
 
     def propagate_cov(self, Phi, Pmm, b0=0):

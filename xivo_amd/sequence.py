@@ -32,6 +32,10 @@ What is mirrored from the reference and what is simplified:
       pool entry at its second observation before its sub-filter step (Feature::Triangulate, src/feature.cpp:686-751;
       new tracks then start with the `initial_std_*_badtri` stds, :585-586), and `adaptive_initial_depth` runs
       AdaptInitialDepth (:255-278) after the new tracks are added, whose init_z the next frame's new tracks start from.
+  * who runs the "immediate" life cycle (`SequenceConfig.lifecycle`): "host" (default) - this file decides filter by filter and
+    sends op lists; "device" - the slot book lives on the device and the frame is xivo_hip_life_begin -> update ->
+    xivo_hip_life_end (lifecycle_kernels.hip): the tracks of all filters go down in one array, nothing is downloaded during
+    a frame, `books` / `n_updates` / `n_rejected` are read from the device on demand. Same decisions, same results.
   * NOT IN EITHER: RefineDepth (`use_depth_opt`), gauge XY features and SwitchRefGroup, ownership transfer, OOS updates.
 The numerics of every step are the device path; this file holds no arithmetic of the filter itself.
 """
@@ -150,6 +154,11 @@ class SequenceConfig:
         # AdaptInitialDepth (src/manager.cpp:255-278): the init_z of new tracks follows the median feature depth
         self.adaptive_initial_depth = False
         self.adaptive_depth = dict(median_weight=0.99, minimum_feature_lifetime=5)   # cfg "adaptive_initial_depth"
+        # who runs the per-frame life cycle of the "immediate" mode: "host" (SequenceRunner.frame decides filter by filter and
+        # sends op lists) or "device" (xivo_hip_life_begin / _end: the slot book is device resident, nothing is downloaded
+        # during a frame). tracks_max: the most tracks one filter may bring in a frame on the device path.
+        self.lifecycle = "host"
+        self.tracks_max = 1024
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option " + k)
@@ -299,6 +308,7 @@ class HipBackend:
             flags |= L.FLAG_FIX_GROUP_BLOCK
         if getattr(cfg, "use_invdepth", False):
             flags |= L.FLAG_INVDEPTH
+        check_lifecycle(cfg)
         self.ctx = L.Context(cfg.N, 2 * cfg.n_features, B, device=device, flags=flags)
         self.ctx.set_layout(cfg.N, 23, cfg.n_groups, 23 + 6 * cfg.n_groups, cfg.n_features, cfg.cam)
         self.ctx.upload_P(P0)
@@ -312,6 +322,30 @@ class HipBackend:
         self.innov_on, self.frame_ts = False, 0   # innovation log: on / the stamp (ns) of the frame update() records under
         if cfg.feature_init == "subfilter":
             self.enable_pool()
+        if cfg.lifecycle == "device":
+            self.enable_device_lifecycle()
+
+    def enable_device_lifecycle(self):
+        """allocate the device-resident slot book and track staging (xivo_hip_life_config). The new feature's variances are
+        computed here as the host life cycle computes them (std * std, src/estimator.cpp:349-353)."""
+        c = self.cfg
+        fl = c.focal_length()
+        std = np.array([c.initial_std_x / fl, c.initial_std_y / fl, c.initial_std_z])
+        self.ctx.life_config(c.tracks_max, min_depth=c.min_depth, max_depth=c.max_depth, min_new_features=c.min_new_features,
+                             var_xyz=std * std)
+
+    def life_begin(self, off, ids, meas):
+        self.ctx.life_begin(self.F, off, ids, meas, B=self.B)
+
+    def life_end(self):
+        self.ctx.life_end(self.B)
+
+    def life_book(self):
+        """(feat_id [B, F], feat_ref [B, F], group_refs [B, n_groups]) read from the device"""
+        return self.ctx.life_get_book(0, self.B)
+
+    def life_stats(self):
+        return self.ctx.life_stats(0, self.B)
 
     def enable_pool(self):
         """allocate the device-resident feature pool of the "subfilter" life cycle"""
@@ -358,7 +392,9 @@ class HipBackend:
     def set_pixels(self, xp):
         self.ctx.set_pixels(xp)
 
-    def update(self):
+    def update(self, download=True):
+        """the frame's measurement update and AbsorbError -> the inlier mask [B, F]; download=False (device life cycle): the
+        mask and the status stay on the device, nothing synchronises, None is returned"""
         c = self.cfg
         R = c.visual_meas_std ** 2
         if c.use_1pt_RANSAC:
@@ -372,10 +408,12 @@ class HipBackend:
             self.ctx.update_joseph()
         else:
             self.ctx.filter_update(R, c.MH_thresh, c.MH_adjust_factor, c.min_inliers, bool(c.use_MH_gating))
-        mask, _ = self.ctx.get_gate(self.F)
-        # a filter whose S was not positive definite keeps its prior P and absorbs nothing (device side); surfaced here
-        self.last_status = self.ctx.get_status(check=False)
-        self.n_not_spd = getattr(self, "n_not_spd", 0) + int((self.last_status != 0).sum())
+        mask = None
+        if download:
+            mask, _ = self.ctx.get_gate(self.F)
+            # a filter whose S was not positive definite keeps its prior P and absorbs nothing (device side); surfaced here
+            self.last_status = self.ctx.get_status(check=False)
+            self.n_not_spd = getattr(self, "n_not_spd", 0) + int((self.last_status != 0).sum())
         if self.innov_on:   # between the update and AbsorbError, which consumes dx
             self.ctx.innov_record(self.frame_ts, self.B)
         self.ctx.absorb_error()
@@ -472,6 +510,13 @@ class _PoolBook:
                 self.anc_link[a] = -1
 
 
+def check_lifecycle(cfg):
+    if cfg.lifecycle not in ("host", "device"):
+        raise ValueError("lifecycle must be 'host' or 'device'")
+    if cfg.lifecycle == "device" and cfg.feature_init != "immediate":
+        raise ValueError("lifecycle='device' runs the 'immediate' life cycle only (feature_init=%r)" % (cfg.feature_init,))
+
+
 def _op(b, kind, i0=0, i1=0, i2=0, v=()):
     o = np.zeros((), dtype=L.edit_dtype)
     o["b"], o["kind"], o["i0"], o["i1"], o["i2"] = b, kind, i0, i1, i2
@@ -485,16 +530,78 @@ class SequenceRunner:
     an oracle backend). `frame()` consumes the pending IMU records and one camera frame per filter."""
 
     def __init__(self, backend, cfg, B):
+        check_lifecycle(cfg)
         self.be, self.cfg, self.B = backend, cfg, B
-        self.books = [_Book(cfg.n_groups, cfg.n_features) for _ in range(B)]
-        self.n_updates = 0
-        self.n_rejected = 0
+        self.device_lifecycle = cfg.lifecycle == "device"
+        self._books = [_Book(cfg.n_groups, cfg.n_features) for _ in range(B)]
+        self._n_updates = 0
+        self._n_rejected = 0
+        self.want_mask = False       # device life cycle: download the inlier mask of every frame (frame() then returns it)
         self.pools = None            # [B] _PoolBook in the "subfilter" life cycle
         self.vision_counter = 0      # camera frames so far (Estimator::vision_counter_)
         self.n_pool_dropped = 0      # new tracks dropped because the pool or the anchor table was full
         self.admitted = []           # (frame, filter, track id, sub-filter steps taken) of every pool entry that entered the state
         self.init_z = None           # [B] AdaptInitialDepth's init_z after the last frame (adaptive_initial_depth)
         self.timers = None       # set to {} to accumulate wall seconds per phase (adds a device sync per phase)
+
+    # books / n_updates / n_rejected: the host life cycle keeps them here; the device life cycle reads them from the device
+    # on demand (one synchronising read each - not something to ask for every frame of a timed run)
+    @property
+    def books(self):
+        if not self.device_lifecycle:
+            return self._books
+        fid, fref, grefs = self.be.life_book()
+        out = []
+        for b in range(self.B):
+            bk = _Book(self.cfg.n_groups, self.cfg.n_features)
+            bk.feat_id[:fid.shape[1]] = fid[b].tolist()
+            bk.feat_ref[:fid.shape[1]] = fref[b].tolist()
+            bk.group_refs = grefs[b].tolist()
+            bk.id2slot = {i: j for j, i in enumerate(bk.feat_id) if i >= 0}
+            out.append(bk)
+        return out
+
+    @property
+    def n_updates(self):
+        return int(self.be.life_stats()["updates"].sum()) if self.device_lifecycle else self._n_updates
+
+    @n_updates.setter
+    def n_updates(self, v):
+        self._n_updates = v
+
+    @property
+    def n_rejected(self):
+        return int(self.be.life_stats()["rejected"].sum()) if self.device_lifecycle else self._n_rejected
+
+    @n_rejected.setter
+    def n_rejected(self, v):
+        self._n_rejected = v
+
+    def _frame_device(self, imu, tracks):
+        """one camera frame with the life cycle on the device: the tracks of all filters go down in the off / ids / meas layout
+        of xivo_batch_visual, then life_begin -> update -> life_end. No per-feature work here and nothing is downloaded
+        (unless want_mask)."""
+        import time
+        be = self.be
+        t0 = time.perf_counter()
+        if imu is not None:
+            be.propagate(imu)
+        t0 = self._tick("propagate", t0) or t0
+        off = np.zeros(self.B + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(t[0]) for t in tracks])
+        if off[-1] > 0:
+            ids = np.concatenate([np.asarray(t[0], dtype=np.int64).reshape(-1) for t in tracks])
+            meas = np.concatenate([np.asarray(t[1], dtype=np.float64).reshape(-1, 3) for t in tracks])
+        else:
+            ids, meas = np.zeros(0, dtype=np.int64), np.zeros((0, 3))
+        t0 = self._tick("host_pre", t0) or t0
+        be.life_begin(off, ids, meas)
+        t0 = self._tick("edit", t0) or t0
+        mask = be.update(download=self.want_mask)
+        t0 = self._tick("update", t0) or t0
+        be.life_end()
+        self._tick("edit", t0)
+        return mask
 
     def _tick(self, name, t0):
         if self.timers is None:
@@ -521,6 +628,8 @@ class SequenceRunner:
             return self._frame_subfilter(imu, tracks)
         if self.cfg.feature_init != "immediate":
             raise ValueError("feature_init must be 'immediate' or 'subfilter'")
+        if self.device_lifecycle:
+            return self._frame_device(imu, tracks)
         import time
         cfg, be = self.cfg, self.be
         t0 = time.perf_counter()
@@ -737,7 +846,8 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     ate_aligned / ate_raw / rpe_pos / rpe_rot from the device (xivo_hip_traj_score; RPE over rpe_dt seconds as
     rpe_lag_frames turns them into frames, -1: no pair).
     map_log: the in-state features of every frame are recorded on the device after the frame (xivo_hip_map_record) and read
-    once at the end; the runner's slot book gives the track id of each, the worlds the true point. Adds `map` (pts, n_pts, ids,
+    once at the end; the runner's slot book gives the track id of each, the worlds the true point (with lifecycle="device" the
+    book is on the device: one xivo_hip_life_get_book read per recorded frame). Adds `map` (pts, n_pts, ids,
     gt), landmark_err3 / landmark_nees / landmark_anees / landmarks_used, anees_landmark and landmarks_scored_mean. Off:
     nothing changes.
     innovation_log: every frame's update records its NIS on the device (HipBackend.enable_innovation_log) and the log is read
@@ -886,9 +996,15 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
                                             cfg.cam["rows"], noise_vision_std)
             t1 = time.perf_counter()
             tm["sim"] = tm.get("sim", 0.0) + t1 - t0
-            mask = np.zeros((B, cfg.n_features), dtype=np.uint8)
-            if host.xivo_batch_visual(est.h, float(t), off.ctypes.data, ids.ctypes.data, meas.ctypes.data, mask.ctypes.data) != 0:
+            mask = np.zeros((B, cfg.n_features), dtype=np.uint8) if est.want_mask else None   # (device life cycle: no download)
+            if host.xivo_batch_visual(est.h, float(t), off.ctypes.data, ids.ctypes.data, meas.ctypes.data,
+                                      mask.ctypes.data if mask is not None else None) != 0:
                 raise RuntimeError("VisualMeasPointCloud failed")
+            if est.device_lifecycle and timers is not None:
+                # the device life cycle only enqueues the frame: a timed run waits for it here, so that "frame" ends where the
+                # host life cycle's does (its last call synchronises); "frame_enqueue" is the host's share of it
+                tm["frame_enqueue"] = tm.get("frame_enqueue", 0.0) + time.perf_counter() - t1
+                est.sync()
             tm["frame"] = tm.get("frame", 0.0) + time.perf_counter() - t1
             ts.append(int(round(t * 1e9))); gt_T.append(Tsb)
             if ctx is not None:
