@@ -959,6 +959,54 @@ int xivo_hip_life_end(xivo_hip_ctx* ctx, int B);
 /* The counters of filters [b0, b0 + nb). Synchronises. */
 int xivo_hip_life_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_life_stats* out);
 
+/* ---- point-cloud world: the simulator's tracks produced on the device (opt-in; needs the device life cycle) ---------------
+ * What BatchPCW.generate (xivo_amd/pcw.py, after the reference's scripts/point_cloud_world.py:44-131) computes on the host per
+ * camera frame: every world point is projected through the frame's ground-truth camera pose, a point in front of the camera
+ * whose pixel lies in [0, imw] x [0, imh] is visible, a visible point without a track id takes the world's next one in ascending
+ * point order, a point that is not visible loses its id (so a point that returns is a new track), and the visible points - in
+ * ascending point order - are the frame's tracks (id, u + noise, v + noise, depth). The worlds stay on the device (points, the id
+ * each point holds, the next id of each world); a frame needs the camera poses only, 96 bytes per filter, and is
+ *   xivo_hip_propagate -> xivo_hip_pcw_tracks -> xivo_hip_life_begin_tracks -> update -> xivo_hip_absorb_error -> xivo_hip_life_end
+ * The tracks are written into the life cycle's device block, one row of tracks_max per filter; frames fed by
+ * xivo_hip_life_begin (host tracks) and by xivo_hip_life_begin_tracks may alternate freely. The evaluation order of the
+ * projection and the noise generator (Philox4x32-10 keyed by the seed, counter = point, filter, frame; one Box-Muller pair per
+ * point) are specified in xivo_amd/csrc/pcw_device.h; pcw.philox_normal restates the generator for host code. A point's
+ * noise depends on (seed, frame, filter, point) only. */
+typedef struct {
+  int struct_size;         /* sizeof(xivo_pcw_opts) */
+  int npts;                /* points per world; 0 releases the worlds */
+  double fx, fy, cx, cy;   /* pinhole intrinsics of the simulated camera (one set for all filters) */
+  double imw, imh;         /* image width and height in pixels; the borders count as inside */
+} xivo_pcw_opts;
+/* (Re-)allocates the resident worlds of batch_max filters - Xs [batch_max][npts][3], ids [batch_max][npts], next_id and the track
+ * count per filter - and two page-locked blocks of batch_max x 12 doubles for the poses. The worlds start empty (points at
+ * the origin, no ids, next id 0) until xivo_hip_pcw_set_world. XIVO_HIP_ERR_INVALID, nothing changed: no device life cycle is
+ * configured (xivo_hip_life_config), npts > its tracks_max (a filter can then never produce more tracks than its row of the
+ * block holds), a value that is not finite, a wrong struct_size, a frame open between life_begin and life_end.
+ * xivo_hip_life_config (whatever its arguments) and xivo_hip_destroy release the worlds too: configure them again after
+ * the life cycle. Synchronises. */
+int xivo_hip_pcw_config(xivo_hip_ctx* ctx, const xivo_pcw_opts* opts);
+/* The worlds of filters [b0, b0 + nb): Xs [nb][npts][3]; ids [nb][npts] (NULL: every id -1, no point is tracked); next_id [nb]
+ * (NULL: 10000, counter0 of src/feature.h). A set-up call: synchronises. */
+int xivo_hip_pcw_set_world(xivo_hip_ctx* ctx, int b0, int nb, const double* Xs, const long long* ids, const long long* next_id);
+/* ids [nb][npts] and next_id [nb] as the last frame left them; either may be NULL. Synchronises. */
+int xivo_hip_pcw_get_world(xivo_hip_ctx* ctx, int b0, int nb, long long* ids, long long* next_id);
+/* One camera frame of filters [0, B): gsc [B][12] is the ground-truth camera pose of each, Rsc row-major then Tsc (a world
+ * point X has camera coordinates Rsc^T (X - Tsc)). Copies the poses to page-locked staging, enqueues their upload and the
+ * producer; does not synchronise and allocates nothing. noise_px_std: standard deviation of the pixel noise (0: none, bit for
+ * bit the projection); seed, frame: the generator's key and the frame's part of its counter. XIVO_HIP_ERR_INVALID, nothing
+ * changed: no worlds configured, B out of range, called between xivo_hip_life_begin* and xivo_hip_life_end. */
+int xivo_hip_pcw_tracks(xivo_hip_ctx* ctx, int B, const double* gsc, double noise_px_std, unsigned long long seed,
+                        unsigned long long frame);
+/* xivo_hip_life_begin without the upload: consumes the tracks the last xivo_hip_pcw_tracks(B) left in the block (once);
+ * xivo_hip_life_end then reads them there too. XIVO_HIP_ERR_INVALID, nothing changed: no tracks were produced for this B since
+ * the last life_begin of either kind, and everything xivo_hip_life_begin refuses. */
+int xivo_hip_life_begin_tracks(xivo_hip_ctx* ctx, int B, int F);
+/* Read-back for tests and debugging of what the last xivo_hip_pcw_tracks left for filters [b0, b0 + nb) (within its B; gone
+ * after a host-track xivo_hip_life_begin): cnt [nb], ids [nb][tracks_max], meas [nb][tracks_max][3]; entries behind cnt[b]
+ * read -1 / 0. Any may be NULL. Synchronises. */
+int xivo_hip_pcw_get_tracks(xivo_hip_ctx* ctx, int b0, int nb, int* cnt, long long* ids, double* meas);
+
 /* ---- covariance propagation tail (src/rk4.cpp:92-102, src/estimator.cpp:590) */
 /* P_mm <- Pmm_new ; P_ms <- Phi P_ms ; P_sm <- P_sm Phi^T. Phi and Pmm_new
  * are nm x nm (nm = kMotionSize: 23, or up to 40 for the online-calibration builds), one pair per filter. */

@@ -74,9 +74,22 @@ def main():
     ap.add_argument("-lifecycle", default="host", choices=["host", "device"],
                     help="who runs the per-frame feature life cycle: the host side (op lists, the default) or the device "
                          "(xivo_hip_life_begin / _end: nothing is downloaded during a frame)")
+    ap.add_argument("-tracks", default="host", choices=["host", "device"],
+                    help="where a frame's tracks come from: the numpy point-cloud world, uploaded by the frame call (the "
+                         "default), or the worlds resident on the device (xivo_hip_pcw_tracks: only the ground-truth camera "
+                         "poses go down; pixel noise from its counter-based generator). Needs -lifecycle device and "
+                         "-npts <= %d; not with -host cpp" % sequence.L.LIFE_MAX_TRACKS)
     a = ap.parse_args()
     # (a sequence never brings more tracks than its world has points)
     life = dict(lifecycle=a.lifecycle, tracks_max=min(a.npts, sequence.L.LIFE_MAX_TRACKS))
+    if a.tracks == "device":
+        life.update(track_source="device", npts=a.npts)
+        if a.host == "cpp" and not a.vectorized:
+            ap.error("-tracks device runs with -host python or -vectorized")
+        try:      # before any rank is spawned: what check_lifecycle rejects
+            sequence.check_lifecycle(sequence.SequenceConfig(**life))
+        except ValueError as e:
+            ap.error(str(e))
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         from xivo_amd.shard import spawn_ranks
         sys.exit(spawn_ranks([os.path.abspath(__file__)] + sys.argv[1:], a.gpus))
@@ -86,17 +99,19 @@ def main():
         t0 = time.perf_counter()
         out = sequence.run_pcw_batch(cfg, a.sequences, total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
                                      noise_vision_std=a.noise_vision_std, npts=a.npts, timers=tm, trajectory_log=a.traj_log,
-                                     map_log=a.map_log, rpe_dt=a.rpe_dt, innovation_log=a.innov_log)
+                                     map_log=a.map_log, rpe_dt=a.rpe_dt, innovation_log=a.innov_log, track_source=a.tracks)
         wall = time.perf_counter() - t0
         st = out["estimator"].stats(); out["estimator"].close()
         frames = len(out["ts"])
         ate = np.sqrt(np.mean(np.sum((out["Tsb"] - out["gt_Tsb"]) ** 2, axis=2), axis=0))
         print(json.dumps({
             "sequences": a.sequences, "frames_per_sequence": frames, "N": cfg.N, "integration": a.integration_method,
-            "host": "cpp, vectorised simulators", "lifecycle": a.lifecycle,
+            "host": "cpp, vectorised simulators", "lifecycle": a.lifecycle, "tracks": a.tracks,
             "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
             **_consistency(out),
             "updates": st["updates"], "mh_rejected": st["mh_rejected"], "wall_s": wall, "simulator_s": tm.get("sim", 0.0),
+            # the two simulators' shares of simulator_s: IMU samples; the camera's ground-truth pose + (-tracks host) the tracks
+            "sim_imu_s": tm.get("sim_imu", 0.0), "sim_tracks_s": tm.get("sim_tracks", 0.0),
             "frame_calls_s": tm.get("frame", 0.0), "host_cpp_lifecycle_s": st["host_seconds"],
             # -lifecycle device: the part of frame_calls_s before the stream is waited for (the frame is only enqueued)
             **({"frame_enqueue_s": tm["frame_enqueue"]} if "frame_enqueue" in tm else {}),
@@ -163,7 +178,7 @@ def main():
     print(json.dumps({
         "sequences": B, "n_gpus": world, "frames_per_sequence": frames, "imu_samples_per_frame": int(round(a.vision_dt / a.imu_dt)),
         "N": cfg.N, "max_features": cfg.n_features, "integration": a.integration_method, "host": a.host,
-        "lifecycle": a.lifecycle,
+        "lifecycle": a.lifecycle, "tracks": a.tracks,
         "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
         **_consistency(out),
         "updates": n_upd, "mh_rejected": n_rej,

@@ -58,6 +58,8 @@ def load_host_library():
         _HOST.xivo_batch_init_z.argtypes = [C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_innov_log.argtypes = [C.c_void_p, C.c_int]
         _HOST.xivo_batch_enable_device_lifecycle.argtypes = [C.c_void_p, C.c_int]
+        _HOST.xivo_batch_enable_device_world.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _HOST.xivo_batch_visual_world.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_ulonglong, C.c_void_p]
     return _HOST
 
 
@@ -138,6 +140,28 @@ class BatchEstimator:
         downloads nothing unless a mask is asked for, book() and stats() read the device"""
         if self.host.xivo_batch_enable_device_lifecycle(self.h, int(tracks_max)) != 0:
             raise RuntimeError("xivo_batch_enable_device_lifecycle failed")
+
+    def enable_device_world(self, Xs):
+        """BatchEstimator::EnableDeviceWorld: the worlds' points Xs [B, npts, 3] go to the device once (camera: cfg.cam); the
+        frames are then VisualMeasDeviceWorld. Needs the device life cycle and npts <= tracks_max"""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 3 or Xs.shape[0] != self.B or Xs.shape[2] != 3:
+            raise ValueError("Xs [B, npts, 3]")
+        cam = self.cfg.cam
+        o = np.zeros(1, dtype=L.pcw_opts_dtype)
+        o["fx"], o["fy"], o["cx"], o["cy"], o["imw"], o["imh"] = cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["cols"], cam["rows"]
+        if self.host.xivo_batch_enable_device_world(self.h, Xs.shape[1], o.ctypes.data, Xs.ctypes.data) != 0:
+            raise RuntimeError("xivo_batch_enable_device_world failed")
+
+    def VisualMeasDeviceWorld(self, t, gsc, noise_px_std, seed, mask=None):
+        """the camera frame on tracks the device produces: gsc [B, 12] ground-truth camera poses (Rsc row-major, Tsc); mask:
+        a [B, F] uint8 array to receive the inlier mask, or None (nothing is downloaded)"""
+        gsc = np.ascontiguousarray(gsc, dtype=np.float64)
+        if gsc.shape != (self.B, 12):
+            raise ValueError("gsc [B, 12]")
+        if self.host.xivo_batch_visual_world(self.h, float(t), gsc.ctypes.data, float(noise_px_std), int(seed),
+                                             mask.ctypes.data if mask is not None else None) != 0:
+            raise RuntimeError("VisualMeasDeviceWorld failed")
 
     def sync(self):
         """wait for the estimator's stream (the device life cycle leaves a frame enqueued)"""

@@ -168,6 +168,8 @@ void xivo_hip_destroy(xivo_hip_ctx* c) {
   for (int i = 0; i < 2; ++i) {   // the life cycle's page-locked staging (xivo_hip_life_config)
     if (c->life_pin[i]) hipHostFree(c->life_pin[i]);
     if (c->life_ev[i]) hipEventDestroy(c->life_ev[i]);
+    if (c->pcw_pin[i]) hipHostFree(c->pcw_pin[i]);   // the world's pose staging (xivo_hip_pcw_config)
+    if (c->pcw_ev[i]) hipEventDestroy(c->pcw_ev[i]);
   }
   for (auto& ep : c->pool) { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
   if (c->t0) hipEventDestroy(c->t0);

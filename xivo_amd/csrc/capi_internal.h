@@ -8,6 +8,7 @@
 //   capi_map.hip        landmark log: per-frame in-state features, world positions and covariances, read-out, landmark NEES
 //   capi_innov.hip      innovation log: per-frame NIS / pre- and post-fit sums of every filter's update, read-out, ensemble sums
 //   capi_lifecycle.hip  device life cycle: the per-filter slot book, the two frame calls around the update, counters
+//   capi_pcw.hip        point-cloud world: the resident worlds, the per-frame track producer, read-back
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
 //
@@ -181,6 +182,15 @@ struct xivo_hip_ctx {
   char* life_dev = nullptr; char* life_pin[2] = {nullptr, nullptr}; hipEvent_t life_ev[2] = {nullptr, nullptr};
   size_t life_set_bytes = 0;
   int life_cur = 0, life_B = 0, life_n = 0;
+  bool life_strided = false;   // the open frame reads the strided form of the track block (xivo_hip_life_begin_tracks)
+  // point-cloud world (xivo_hip_pcw_*, capi_pcw.hip): the resident worlds Xs [Bmax][npts][3] / ids [Bmax][npts] / next_id [Bmax],
+  // the frame's camera poses [Bmax][12] with two page-locked staging blocks (the scheme of life_pin) and cnt [Bmax]; null until
+  // xivo_hip_pcw_config. The producer writes the strided form of life_dev: pcw_tracks_B is the B whose tracks the block holds
+  // (0: none - a host-track life_begin overwrote them), pcw_fresh whether a life_begin_tracks may still consume them
+  xivo_pcw_opts pcw_opts{};
+  double* pcw_Xs = nullptr; long long* pcw_ids = nullptr; long long* pcw_next_id = nullptr; int* pcw_cnt = nullptr;
+  double* pcw_gsc = nullptr; double* pcw_pin[2] = {nullptr, nullptr}; hipEvent_t pcw_ev[2] = {nullptr, nullptr};
+  int pcw_cur = 0, pcw_tracks_B = 0; bool pcw_fresh = false;
   std::vector<char> hstage;                        // host staging of d2h_rows
   char* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
   // one-filter plumbing call (xivo_hip_update_joseph_host): page-locked, device-mapped staging block owned by the context,
@@ -271,6 +281,14 @@ int d2h_packed(xivo_hip_ctx* c, double* dst, const double* src, int nb, int rows
 // ---- capi_update.hip
 int stage_measurements(xivo_hip_ctx* c, int b0, int nb, int M, const double* dH, long strideH, int ldh,
                        const double* dInn, long strideInn, const double* dR, long strideR);
+
+// ---- capi_lifecycle.hip
+// the strided form of the track block life_dev (behind the offsets' space): ids [Bmax][tracks_max], meas [Bmax][tracks_max][3]
+long long* life_strided_ids(xivo_hip_ctx* c);
+double* life_strided_meas(xivo_hip_ctx* c);
+
+// ---- capi_pcw.hip
+void pcw_release(xivo_hip_ctx* c);   // the worlds and the pose staging (the stream must be idle)
 
 // ---- capi_glevel.hip
 int ensure_gate_buffers(xivo_hip_ctx* c, int F);

@@ -1,5 +1,6 @@
 // C ABI, device-resident feature life cycle (include/xivo_hip.h, "device-resident feature life cycle"): configuration, the
-// book's set-up and read-out, the two frame calls and the counters. Host orchestration only - the kernels are in
+// book's set-up and read-out, the frame calls (life_begin on uploaded tracks, life_begin_tracks on the tracks capi_pcw.hip's
+// producer left in the block, life_end) and the counters. Host orchestration only - the kernels are in
 // lifecycle_kernels.hip, the decisions in lifecycle_device.h. Every entry point checks its arguments before it touches the
 // device; the frame calls allocate nothing and do not synchronise the stream.
 #include <math.h>
@@ -19,16 +20,18 @@ size_t set_bytes(int Bmax, int tracks_max) {
 }
 
 void life_release(xivo_hip_ctx* c) {
+  pcw_release(c);   // the producer writes into life_dev: it goes with it
   c->mem.release(&c->life_feat_id, &c->life_group_refs, &c->life_stats, &c->life_dev);
   for (int i = 0; i < 2; ++i) {
     if (c->life_pin[i]) { hipHostFree(c->life_pin[i]); c->life_pin[i] = nullptr; }
     if (c->life_ev[i]) { hipEventDestroy(c->life_ev[i]); c->life_ev[i] = nullptr; }
   }
-  c->life_set_bytes = 0; c->life_ld = 0; c->life_cur = 0; c->life_B = 0; c->life_n = 0;
+  c->life_set_bytes = 0; c->life_ld = 0; c->life_cur = 0; c->life_B = 0; c->life_n = 0; c->life_strided = false;
   c->life_opts = xivo_life_opts{};
 }
 
-// what both kernels take; the tracks are those of the frame in the device block
+// what both kernels take; the tracks are those of the frame in the device block: packed behind the B + 1 offsets as the host
+// uploaded them, or (c->life_strided) one row of tracks_max per filter with the counts next to them, as the producer left them
 LifeArgs life_args(xivo_hip_ctx* c, int B, int n) {
   LifeArgs a{};
   c->P.to(a.P, a.strideP, a.ldp); a.Np = c->Np; a.lay = c->lay;
@@ -39,10 +42,23 @@ LifeArgs life_args(xivo_hip_ctx* c, int B, int n) {
   a.off = reinterpret_cast<const int*>(d);
   a.ids = reinterpret_cast<const long long*>(d + off_bytes);
   a.meas = reinterpret_cast<const double*>(d + off_bytes + (size_t)n * sizeof(long long));
+  if (c->life_strided) {
+    a.ids = life_strided_ids(c); a.meas = life_strided_meas(c);
+    a.cnt = c->pcw_cnt; a.track_ld = c->life_opts.tracks_max;
+  }
   return a;
 }
 
 }  // namespace
+
+namespace xivo_hip::capi {
+long long* life_strided_ids(xivo_hip_ctx* c) {
+  return reinterpret_cast<long long*>(c->life_dev + pad8(((size_t)c->Bmax + 1) * sizeof(int)));
+}
+double* life_strided_meas(xivo_hip_ctx* c) {
+  return reinterpret_cast<double*>(life_strided_ids(c) + (size_t)c->Bmax * c->life_opts.tracks_max);
+}
+}  // namespace xivo_hip::capi
 
 extern "C" {
 
@@ -169,8 +185,27 @@ int xivo_hip_life_begin(xivo_hip_ctx* c, int B, int F, const int* off, const lon
   HIP_TRY(hipMemcpyAsync(c->life_dev, h, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipEventRecord(c->life_ev[set], c->stream));
   c->life_cur = set; c->life_n = n;
+  c->life_strided = false; c->pcw_tracks_B = 0; c->pcw_fresh = false;   // (the upload overwrites what the producer left)
   c->F = F;   // the list length, as xivo_hip_edit_batch / xivo_hip_set_pixels set it (neither touches the staged rows or dx_ok)
   const LifeArgs a = life_args(c, B, n);
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "life_begin_kernel");
+    if (launch_life_begin(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
+  }
+  c->life_B = B;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_life_begin_tracks(xivo_hip_ctx* c, int B, int F) {
+  if (!c || !c->life_feat_id || c->fpool || !c->have_layout || !c->poses || B <= 0 || B > c->Bmax || F <= 0 ||
+      F > c->life_ld || 2 * F > c->Mmax || c->life_B != 0 || !c->pcw_cnt || !c->pcw_fresh || c->pcw_tracks_B != B)
+    return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  int rc = ensure_gate_buffers(c, F);   // (allocated by life_config: checks F only)
+  if (rc) return rc;
+  c->life_strided = true; c->life_n = 0; c->pcw_fresh = false;
+  c->F = F;
+  const LifeArgs a = life_args(c, B, 0);
   {
     StageTimer st(c, ST_OTHER, 0.0, "life_begin_kernel");
     if (launch_life_begin(a, B, c->stream)) return XIVO_HIP_ERR_HIP;

@@ -1,0 +1,155 @@
+// C ABI, point-cloud world (include/xivo_hip.h, "point-cloud world"): the resident worlds, the per-frame track producer and the
+// read-back of what it left. Host orchestration only - the kernel is in pcw_kernels.hip, its rules in pcw_device.h. The frame
+// call checks its arguments before it touches the device, allocates nothing and does not synchronise the stream; the tracks
+// land in the strided form of the life cycle's track block (capi_lifecycle.hip), where xivo_hip_life_begin_tracks finds them.
+#include <math.h>
+#include <stdint.h>
+
+#include "capi_internal.h"
+
+using namespace xivo_hip;
+using namespace xivo_hip::capi;
+
+namespace xivo_hip::capi {
+
+void pcw_release(xivo_hip_ctx* c) {
+  c->mem.release(&c->pcw_Xs, &c->pcw_ids, &c->pcw_next_id, &c->pcw_cnt, &c->pcw_gsc);
+  for (int i = 0; i < 2; ++i) {
+    if (c->pcw_pin[i]) { hipHostFree(c->pcw_pin[i]); c->pcw_pin[i] = nullptr; }
+    if (c->pcw_ev[i]) { hipEventDestroy(c->pcw_ev[i]); c->pcw_ev[i] = nullptr; }
+  }
+  c->pcw_opts = xivo_pcw_opts{}; c->pcw_cur = 0; c->pcw_tracks_B = 0; c->pcw_fresh = false;
+}
+
+}  // namespace xivo_hip::capi
+
+namespace {
+
+bool pcw_ready(const xivo_hip_ctx* c) { return c && c->pcw_Xs && c->life_dev && c->pcw_opts.npts > 0; }
+
+}  // namespace
+
+extern "C" {
+
+int xivo_hip_pcw_config(xivo_hip_ctx* c, const xivo_pcw_opts* o) {
+  if (!c || !o || o->struct_size != (int)sizeof(xivo_pcw_opts) || o->npts < 0) return XIVO_HIP_ERR_INVALID;
+  if (o->npts > 0) {
+    if (!c->life_feat_id || !c->life_dev || o->npts > c->life_opts.tracks_max) return XIVO_HIP_ERR_INVALID;
+    const double v[6] = {o->fx, o->fy, o->cx, o->cy, o->imw, o->imh};
+    for (double x : v) if (!isfinite(x)) return XIVO_HIP_ERR_INVALID;
+  }
+  if (c->life_B != 0) return XIVO_HIP_ERR_INVALID;   // an open frame may be reading the producer's tracks
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  HIP_TRY(hipStreamSynchronize(c->stream));   // a frame call may still be using the blocks given back here
+  pcw_release(c);
+  if (o->npts == 0) return XIVO_HIP_OK;
+  const size_t B = c->Bmax, n = o->npts;
+  int rc = c->mem.raw(&c->pcw_Xs, B * n * 3);
+  if (!rc) rc = c->mem.raw(&c->pcw_ids, B * n);
+  if (!rc) rc = c->mem.raw(&c->pcw_next_id, B);
+  if (!rc) rc = c->mem.zeroed(&c->pcw_cnt, B);
+  if (!rc) rc = c->mem.zeroed(&c->pcw_gsc, B * 12);
+  // the poses as the tracks of xivo_hip_life_begin: one device block behind the stream's order, two page-locked blocks so that
+  // the host writes the next frame's poses while the previous upload may still be reading
+  for (int i = 0; i < 2 && !rc; ++i) {
+    if (hipHostMalloc(reinterpret_cast<void**>(&c->pcw_pin[i]), B * 12 * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+      c->pcw_pin[i] = nullptr; (void)hipGetLastError(); rc = XIVO_HIP_ERR_NOMEM;
+    }
+    if (!rc && hipEventCreateWithFlags(&c->pcw_ev[i], hipEventDisableTiming) != hipSuccess) { c->pcw_ev[i] = nullptr; rc = XIVO_HIP_ERR_HIP; }
+  }
+  // an empty world until xivo_hip_pcw_set_world: points at the origin, no track (all bytes 0xff: -1), ids from 0
+  if (!rc && hipMemsetAsync(c->pcw_Xs, 0, B * n * 3 * sizeof(double), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (!rc && hipMemsetAsync(c->pcw_ids, 0xff, B * n * sizeof(long long), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (!rc && hipMemsetAsync(c->pcw_next_id, 0, B * sizeof(long long), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (rc) { pcw_release(c); return rc; }
+  c->pcw_opts = *o;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pcw_set_world(xivo_hip_ctx* c, int b0, int nb, const double* Xs, const long long* ids, const long long* next_id) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !pcw_ready(c) || c->life_B != 0 || (nb > 0 && !Xs)) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  const size_t n = c->pcw_opts.npts;
+  std::vector<long long> fill;
+  if (!ids) { fill.assign((size_t)nb * n, -1); ids = fill.data(); }
+  std::vector<long long> first;
+  if (!next_id) { first.assign((size_t)nb, 10000); next_id = first.data(); }   // counter0 of src/feature.h
+  HIP_TRY(hipMemcpyAsync(c->pcw_Xs + (size_t)b0 * n * 3, Xs, (size_t)nb * n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->pcw_ids + (size_t)b0 * n, ids, (size_t)nb * n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->pcw_next_id + b0, next_id, (size_t)nb * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // pageable sources
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pcw_get_world(xivo_hip_ctx* c, int b0, int nb, long long* ids, long long* next_id) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !pcw_ready(c)) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  const size_t n = c->pcw_opts.npts;
+  if (ids) {
+    int rc = d2h_rows(c, ids, n * sizeof(long long), c->pcw_ids + (size_t)b0 * n, n * sizeof(long long), n * sizeof(long long), nb);
+    if (rc) return rc;
+  }
+  if (next_id) {
+    int rc = d2h_rows(c, next_id, sizeof(long long), c->pcw_next_id + b0, sizeof(long long), sizeof(long long), nb);
+    if (rc) return rc;
+  }
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pcw_tracks(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, unsigned long long seed,
+                        unsigned long long frame) {
+  if (!pcw_ready(c) || B <= 0 || B > c->Bmax || !gsc || c->life_B != 0 || !isfinite(noise_px_std)) return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  // the staging block the previous frame did not use; it is free once its upload (two frames back) has finished
+  const int set = c->pcw_cur ^ 1;
+  HIP_TRY(hipEventSynchronize(c->pcw_ev[set]));
+  const size_t bytes = (size_t)B * 12 * sizeof(double);
+  memcpy(c->pcw_pin[set], gsc, bytes);
+  HIP_TRY(hipMemcpyAsync(c->pcw_gsc, c->pcw_pin[set], bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(c->pcw_ev[set], c->stream));
+  c->pcw_cur = set;
+  const xivo_pcw_opts& o = c->pcw_opts;
+  PcwArgs a{};
+  a.Xs = c->pcw_Xs; a.ids = c->pcw_ids; a.next_id = c->pcw_next_id; a.gsc = c->pcw_gsc; a.npts = o.npts;
+  a.fx = o.fx; a.fy = o.fy; a.cx = o.cx; a.cy = o.cy; a.imw = o.imw; a.imh = o.imh;
+  a.noise_px_std = noise_px_std; a.seed = seed; a.frame = frame;
+  a.track_ids = life_strided_ids(c); a.track_meas = life_strided_meas(c); a.cnt = c->pcw_cnt; a.track_ld = c->life_opts.tracks_max;
+  c->pcw_tracks_B = 0; c->pcw_fresh = false;   // (whatever the block held is being overwritten)
+  {
+    // per filter: the points and their ids in, the ids that changed and at most npts tracks of 32 bytes out
+    StageTimer st(c, ST_OTHER, 0.0, "pcw_tracks_kernel", (double)B * o.npts * (24.0 + 8.0 + 8.0 + 32.0));
+    if (launch_pcw_tracks(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
+  }
+  c->pcw_tracks_B = B; c->pcw_fresh = true;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pcw_get_tracks(xivo_hip_ctx* c, int b0, int nb, int* cnt, long long* ids, double* meas) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !pcw_ready(c) || b0 + nb > c->pcw_tracks_B) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  const size_t ld = c->life_opts.tracks_max;
+  std::vector<int> n((size_t)nb);
+  int rc = d2h_rows(c, n.data(), sizeof(int), c->pcw_cnt + b0, sizeof(int), sizeof(int), nb);
+  if (rc) return rc;
+  if (ids) {
+    rc = d2h_rows(c, ids, ld * sizeof(long long), life_strided_ids(c) + (size_t)b0 * ld, ld * sizeof(long long), ld * sizeof(long long), nb);
+    if (rc) return rc;
+  }
+  if (meas) {
+    rc = d2h_rows(c, meas, 3 * ld * sizeof(double), life_strided_meas(c) + 3 * (size_t)b0 * ld, 3 * ld * sizeof(double), 3 * ld * sizeof(double), nb);
+    if (rc) return rc;
+  }
+  // behind cnt[b] a row holds whatever an earlier frame left: blanked, so that two read-backs compare equal
+  for (int b = 0; b < nb; ++b) {
+    if (ids) std::fill(ids + (size_t)b * ld + n[b], ids + (size_t)(b + 1) * ld, -1LL);
+    if (meas) std::fill(meas + 3 * ((size_t)b * ld + n[b]), meas + 3 * (size_t)(b + 1) * ld, 0.0);
+    if (cnt) cnt[b] = n[b];
+  }
+  return XIVO_HIP_OK;
+}
+
+}  // extern "C"

@@ -133,17 +133,33 @@ int launch_innov_stats(const InnovStatsArgs& a, hipStream_t s);
 // [batch][n_groups], counters [batch]) and the frame's tracks (off [batch + 1]; ids, meas [off[batch]][3]). F <= slot_ld,
 // F <= XIVO_LIFE_MAX_SLOTS, n_groups <= XIVO_LIFE_MAX_SLOTS, every filter's track count <= XIVO_LIFE_MAX_TRACKS (the host
 // checks all four before a launch).
+// The tracks come in one of two forms. Packed (cnt == nullptr): filter b's are ids[off[b] + k], meas[3 (off[b] + k)], k <
+// off[b + 1] - off[b] - what the host uploads. Strided (cnt != nullptr; off is not read): ids[b track_ld + k],
+// meas[3 (b track_ld + k)], k < cnt[b] - what pcw_tracks_kernel leaves, which cannot know the other filters' counts.
 struct LifeArgs {
   double* P; long strideP; int ldp, Np; xivo_layout lay;
   const xivo_pose_in* poses; xivo_group_in* groups; xivo_feat_in* feats; int Fmax, F;
   long long* feat_id; int slot_ld; int* group_refs; xivo_life_stats* stats;
   const int* off; const long long* ids; const double* meas;
+  const int* cnt; int track_ld;
   // life_end only: the update's inlier mask (row stride mask_ld) and status, the admission options, the camera
   const unsigned char* mask; int mask_ld; const int* status;
   int min_new_features, invdepth; double min_depth, max_depth, var_xyz[3], fx, fy, cx, cy;
 };
 int launch_life_begin(const LifeArgs& a, int batch, hipStream_t s);
 int launch_life_end(const LifeArgs& a, int batch, hipStream_t s);
+
+// ================================================================ pcw_kernels.hip: the point-cloud world's track producer (capi_pcw.hip)
+
+// one frame of the worlds of filters [0, batch): Xs [batch][npts][3], ids [batch][npts] (-1: no track), next_id [batch] and the
+// frame's camera poses gsc [batch][12] (Rsc row-major, Tsc) -> the strided track block (track_ids / track_meas, row length
+// track_ld >= npts) and cnt [batch]; the rules are pcw_device.h
+struct PcwArgs {
+  const double* Xs; long long* ids; long long* next_id; const double* gsc; int npts;
+  double fx, fy, cx, cy, imw, imh, noise_px_std; unsigned long long seed, frame;
+  long long* track_ids; double* track_meas; int* cnt; int track_ld;
+};
+int launch_pcw_tracks(const PcwArgs& a, int batch, hipStream_t s);
 
 // ================================================================ glevel_kernels.hip: feature-level kernels (capi_glevel.hip)
 

@@ -13,6 +13,9 @@
 // edit_batch_kernel (edit_device.h) in the order the host's op lists have, so P and the scene come out bit for bit as from the
 // op lists - up to log z, where libm and the device library may differ in the last place. Nothing crosses workgroups: no
 // atomics on global memory, the counters and the book belong to the filter's own workgroup (LDS atomics only).
+// The frame's tracks are read in one of two forms (LifeArgs, ekf_kernels.h): packed behind offsets as the host uploads them, or
+// one row per filter with a count as pcw_tracks_kernel (pcw_kernels.hip) leaves them; life_track_begin / life_track_count are
+// the only place that tells them apart.
 #include "edit_device.h"
 #include "ekf_kernels.h"
 #include "lifecycle_device.h"
@@ -35,6 +38,12 @@ struct LifeLds {
   int n_rm_feat, n_rm_group, g_new, n_free, open, n_cand;
 };
 
+// where filter b's tracks start and how many there are, in either form of the track block (ekf_kernels.h)
+__device__ __forceinline__ int life_track_begin(const LifeArgs& a, int b) { return a.cnt ? b * a.track_ld : a.off[b]; }
+__device__ __forceinline__ int life_track_count(const LifeArgs& a, int b) {
+  return min(a.cnt ? a.cnt[b] : a.off[b + 1] - a.off[b], kTracks);
+}
+
 __device__ __forceinline__ void life_load(const LifeArgs& a, LifeLds& s, int b, int n, int tid) {
   const int F = a.F, G = a.lay.n_groups;
   const long long* book_id = a.feat_id + (long)b * a.slot_ld;
@@ -47,7 +56,7 @@ __device__ __forceinline__ void life_load(const LifeArgs& a, LifeLds& s, int b, 
     s.slot_track[j] = -1;
   }
   for (int g = tid; g < G; g += 256) s.gref[g] = a.group_refs[(long)b * G + g];
-  const int k0 = a.off[b];
+  const int k0 = life_track_begin(a, b);
   for (int k = tid; k < n; k += 256) s.ids[k] = a.ids[k0 + k];
 }
 
@@ -77,7 +86,7 @@ __global__ __launch_bounds__(256) void life_begin_kernel(LifeArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x, F = a.F, G = a.lay.n_groups;
   double* P = a.P + (long)b * a.strideP;
   xivo_feat_in* feats = a.feats + (long)b * a.Fmax;
-  const int k0 = a.off[b], n = min(a.off[b + 1] - k0, kTracks);
+  const int k0 = life_track_begin(a, b), n = life_track_count(a, b);
   life_load(a, s, b, n, tid);
   __syncthreads();
   // association: one thread per track scans the in-state ids; of a repeated id the last occurrence feeds the slot
@@ -131,7 +140,7 @@ __global__ __launch_bounds__(256) void life_end_kernel(LifeArgs a) {
   double* P = a.P + (long)b * a.strideP;
   xivo_feat_in* feats = a.feats + (long)b * a.Fmax;
   xivo_group_in* groups = a.groups + (long)b * G;
-  const int k0 = a.off[b], n = min(a.off[b + 1] - k0, kTracks);
+  const int k0 = life_track_begin(a, b), n = life_track_count(a, b);
   life_load(a, s, b, n, tid);
   __syncthreads();
   if (tid == 0) {

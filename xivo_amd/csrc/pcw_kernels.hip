@@ -1,0 +1,81 @@
+// The point-cloud world's track producer on the device (gfx950): what BatchPCW.generate (xivo_amd/pcw.py, after the reference's
+// scripts/point_cloud_world.py:44-131) computes per camera frame on the host and the frame call would otherwise upload. The
+// worlds are resident - points, the track id each point holds, the next id of each world - and a frame needs the ground-truth
+// camera poses only. One workgroup of 256 threads (four waves) per filter walks its points in chunks of 256 consecutive
+// points; the rules and the arithmetic are the functions of pcw_device.h.
+//
+// Track ids and track positions are order preserving: the k-th visible point of a world, in point order, is track k of the
+// filter's row, and the k-th new one takes next_id + k. Both ranks are exclusive prefix counts over the chunk - the wave's
+// ballot and the population count of the lanes below, the four wave totals through LDS - plus the totals of the chunks before,
+// which every thread carries in registers. Nothing crosses workgroups and no atomic is used: a filter's world, its row of the
+// track block and its two counters belong to its own workgroup.
+#include "ekf_kernels.h"
+#include "pcw_device.h"
+
+namespace xivo_hip {
+
+namespace {
+
+constexpr int kPcwThreads = 256, kPcwWaves = kPcwThreads / 64;
+
+__global__ __launch_bounds__(kPcwThreads) void pcw_tracks_kernel(PcwArgs a) {
+  // wave totals (visible, new) of a chunk, two sets taken in turn: a wave may write the next chunk's while another still
+  // reads this one's, and the barrier of the next chunk keeps it from going further
+  __shared__ int tot[2][2][kPcwWaves];
+  __shared__ double g[12];
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, npts = a.npts;
+  if (tid < 12) g[tid] = a.gsc[(long)b * 12 + tid];
+  __syncthreads();
+  const PcwCam cam{a.fx, a.fy, a.cx, a.cy, a.imw, a.imh};
+  const double* Xs = a.Xs + (long)b * npts * 3;
+  long long* ids = a.ids + (long)b * npts;
+  long long* tid_out = a.track_ids + (long)b * a.track_ld;
+  double* meas_out = a.track_meas + 3 * (long)b * a.track_ld;
+  const long long next_id = a.next_id[b];
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int base_vis = 0, base_new = 0;
+  for (int p0 = 0, c = 0; p0 < npts; p0 += kPcwThreads, ++c) {
+    const int p = p0 + tid;
+    const bool in = p < npts;
+    double uvz[3] = {0.0, 0.0, 0.0};
+    long long id = -1;
+    bool vis = false;
+    if (in) {
+      const double X[3] = {Xs[3 * (long)p], Xs[3 * (long)p + 1], Xs[3 * (long)p + 2]};
+      id = ids[p];
+      vis = pcw_project(X, g, cam, uvz);
+    }
+    const bool is_new = pcw_is_new(vis, id);
+    const unsigned long long m_vis = __ballot(vis), m_new = __ballot(is_new);
+    if (lane == 0) { tot[c & 1][0][wave] = __popcll(m_vis); tot[c & 1][1][wave] = __popcll(m_new); }
+    __syncthreads();
+    int r_vis = base_vis + __popcll(m_vis & below), r_new = base_new + __popcll(m_new & below);
+    for (int w = 0; w < kPcwWaves; ++w) {
+      const int tv = tot[c & 1][0][w], tn = tot[c & 1][1][w];
+      if (w < wave) { r_vis += tv; r_new += tn; }
+      base_vis += tv; base_new += tn;
+    }
+    if (in) {
+      const long long id_after = pcw_id_after(vis, id, next_id, r_new);
+      if (id_after != id) ids[p] = id_after;
+      if (vis) {   // r_vis < number of visible points <= npts <= track_ld (xivo_hip_pcw_config)
+        double nu = 0.0, nv = 0.0;
+        if (a.noise_px_std != 0.0) pcw_normal_pair(a.seed, a.frame, b, p, &nu, &nv);
+        tid_out[r_vis] = id_after;
+        meas_out[3 * (long)r_vis] = pcw_noisy(uvz[0], a.noise_px_std, nu);
+        meas_out[3 * (long)r_vis + 1] = pcw_noisy(uvz[1], a.noise_px_std, nv);
+        meas_out[3 * (long)r_vis + 2] = uvz[2];
+      }
+    }
+  }
+  if (tid == 0) { a.next_id[b] = next_id + base_new; a.cnt[b] = base_vis; }
+}
+
+}  // namespace
+
+int launch_pcw_tracks(const PcwArgs& a, int batch, hipStream_t s) {
+  hipLaunchKernelGGL(pcw_tracks_kernel, dim3(batch), dim3(kPcwThreads), 0, s, a);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+}  // namespace xivo_hip

@@ -166,11 +166,10 @@ void BatchEstimator::EnableInnovationLog(int T_max) {
   innov_log_ = T_max > 0;
 }
 
-void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_t* ids, const double* meas,
-                                          unsigned char* mask_out) {
-  double t0 = now_s();
+// the camera frame's share of Estimator::Propagate and the pending IMU records in one xivo_hip_propagate call; t0: where the
+// caller's host-time interval started (moved past the call)
+void BatchEstimator::PropagateToFrame(double t, double& t0) {
   t_visual_ = t;
-  const int F = cfg_.n_features;
   // Estimator::Propagate, visual_meas == true (src/estimator.cpp:568-575): extrapolate along the last slope; dt == 0
   // (IMU and camera stamps coincide, the simulation case) propagates nothing (:550-555)
   if (have_imu_ && t != t_) {
@@ -200,6 +199,13 @@ void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_
     Check(xivo_hip_propagate(ctx_, 0, B_, K, imu.data(), &cfg_.prop), "propagate");
     t0 = now_s();
   }
+}
+
+void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_t* ids, const double* meas,
+                                          unsigned char* mask_out) {
+  double t0 = now_s();
+  const int F = cfg_.n_features;
+  PropagateToFrame(t, t0);
   if (subfilter_) {
     host_s_ += now_s() - t0;
     VisualSubfilter(off, ids, meas);
@@ -332,6 +338,7 @@ void BatchEstimator::EnableSubfilter(const SubfilterConfig& sc) {
 
 void BatchEstimator::EnableDeviceLifecycle(int tracks_max) {
   if (subfilter_) throw std::runtime_error("the device life cycle runs the immediate mode only");
+  device_world_ = false;   // xivo_hip_life_config releases the resident worlds with the track block
   if (tracks_max <= 0) {
     // back to the host life cycle: the books and the counters come home before the device book is released
     if (device_life_) {
@@ -360,6 +367,31 @@ void BatchEstimator::EnableDeviceLifecycle(int tracks_max) {
     for (int j = 0; j < F; ++j) fid[(size_t)b * F + j] = books_[b].feat_id[j];
   Check(xivo_hip_life_set_book(ctx_, 0, B_, fid.data()), "life_set_book");
   device_life_ = true;
+}
+
+void BatchEstimator::EnableDeviceWorld(int npts, const xivo_pcw_opts& cam, const double* Xs) {
+  if (!device_life_) throw std::runtime_error("the device world needs the device life cycle (EnableDeviceLifecycle)");
+  xivo_pcw_opts o = cam;
+  o.struct_size = (int)sizeof(o); o.npts = npts;
+  Check(xivo_hip_pcw_config(ctx_, &o), "pcw_config");
+  device_world_ = npts > 0;
+  world_frame_ = 0;
+  if (device_world_) Check(xivo_hip_pcw_set_world(ctx_, 0, B_, Xs, nullptr, nullptr), "pcw_set_world");
+}
+
+void BatchEstimator::VisualMeasDeviceWorld(double t, const double* gsc, double noise_px_std, unsigned long long seed,
+                                           unsigned char* mask_out) {
+  if (!device_life_ || !device_world_) throw std::runtime_error("VisualMeasDeviceWorld needs EnableDeviceLifecycle and EnableDeviceWorld");
+  double t0 = now_s();
+  PropagateToFrame(t, t0);
+  host_s_ += now_s() - t0;
+  want_mask_ = mask_out != nullptr;
+  // the frame's tracks are produced where the life cycle reads them: 96 bytes per filter go down, nothing comes back
+  Check(xivo_hip_pcw_tracks(ctx_, B_, gsc, noise_px_std, seed, world_frame_++), "pcw_tracks");
+  Check(xivo_hip_life_begin_tracks(ctx_, B_, cfg_.n_features), "life_begin_tracks");
+  RunUpdate();
+  Check(xivo_hip_life_end(ctx_, B_), "life_end");
+  if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
 }
 
 void BatchEstimator::ReadBook(int b) {
@@ -658,6 +690,15 @@ int xivo_batch_enable_device_lifecycle(void* h, int tracks_max) {
 }
 long xivo_batch_not_spd(void* h) {
   try { return static_cast<xivo::hip::BatchEstimator*>(h)->n_not_spd(); } catch (const std::exception&) { return -1; }
+}
+int xivo_batch_enable_device_world(void* h, int npts, const xivo_pcw_opts* cam, const double* Xs) {
+  if (!h || !cam) return -1;
+  try { static_cast<xivo::hip::BatchEstimator*>(h)->EnableDeviceWorld(npts, *cam, Xs); return 0; } catch (const std::exception&) { return -1; }
+}
+int xivo_batch_visual_world(void* h, double t, const double* gsc, double noise_px_std, unsigned long long seed, unsigned char* mask_out) {
+  if (!h) return -1;
+  try { static_cast<xivo::hip::BatchEstimator*>(h)->VisualMeasDeviceWorld(t, gsc, noise_px_std, seed, mask_out); return 0; }
+  catch (const std::exception&) { return -1; }
 }
 void* xivo_batch_ctx(void* h) { return static_cast<xivo::hip::BatchEstimator*>(h)->ctx(); }
 

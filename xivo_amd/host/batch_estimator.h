@@ -105,6 +105,16 @@ class BatchEstimator {
   // Not with EnableSubfilter, in either order (both throw).
   void EnableDeviceLifecycle(int tracks_max);
   bool device_lifecycle() const { return device_life_; }
+  // the point-cloud world's tracks from the device (xivo_hip_pcw_*; after EnableDeviceLifecycle, both calls throw without it):
+  // EnableDeviceWorld places one world of npts points per filter (Xs [B][npts][3]; nothing tracked yet, ids from 10000) seen by
+  // the pinhole camera in cam (fx .. imh; struct_size and npts are filled in here). npts <= tracks_max; npts = 0 releases the
+  // worlds, and so does every EnableDeviceLifecycle call. VisualMeasDeviceWorld is then the camera frame: gsc [B][12] are the
+  // ground-truth camera poses (Rsc row-major, Tsc), the tracks are produced on the device (pixel noise of standard deviation
+  // noise_px_std from the counter-based generator keyed by seed; the frame counter starts at 0 with EnableDeviceWorld) and the
+  // life cycle runs on them as in VisualMeasPointCloud. Frames of either kind may alternate.
+  void EnableDeviceWorld(int npts, const xivo_pcw_opts& cam, const double* Xs);
+  void VisualMeasDeviceWorld(double t, const double* gsc, double noise_px_std, unsigned long long seed, unsigned char* mask_out);
+  bool device_world() const { return device_world_; }
 
   struct Book {                                     // one filter's slots
     std::vector<int> group_refs;                    // -1 free, else number of in-state features anchored there
@@ -119,10 +129,12 @@ class BatchEstimator {
   void DropFeature(Book& bk, int j);
   void DiscardEmptyGroups(int b, std::vector<xivo_edit_op>& ops);
   void RunUpdate();
+  void PropagateToFrame(double t, double& t0);
   void VisualSubfilter(const int* off, const int64_t* ids, const double* meas);
   void ReadBook(int b);                 // device life cycle: books_[b] <- xivo_hip_life_get_book
   long LifeCount(int which) const;      // device life cycle: one of xivo_life_stats' counters summed over the filters
-  bool device_life_ = false, want_mask_ = false;
+  bool device_life_ = false, want_mask_ = false, device_world_ = false;
+  unsigned long long world_frame_ = 0;
 
   struct PoolBook {                                 // one filter's feature pool: tracks per entry, anchors and their links
     std::vector<int64_t> ent_id;                    // -1 free

@@ -123,6 +123,10 @@ life_opts_dtype = np.dtype([("tracks_max", "i4"), ("min_new_features", "i4"), ("
 life_stats_dtype = np.dtype([("updates", "i8"), ("rejected", "i8"), ("dropped", "i8"), ("admitted", "i8"), ("groups_added", "i8"),
                              ("not_spd", "i8")])
 assert life_opts_dtype.itemsize == 48 and life_stats_dtype.itemsize == 48
+# point-cloud world (include/xivo_hip.h): xivo_pcw_opts
+pcw_opts_dtype = np.dtype([("struct_size", "i4"), ("npts", "i4"), ("fx", "f8"), ("fy", "f8"), ("cx", "f8"), ("cy", "f8"),
+                           ("imw", "f8"), ("imh", "f8")])
+assert pcw_opts_dtype.itemsize == 56
 
 
 def lib_path():
@@ -247,6 +251,12 @@ _SIGS = {
     "xivo_hip_life_begin": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_life_end": [C.c_void_p, C.c_int],
     "xivo_hip_life_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_life_begin_tracks": [C.c_void_p, C.c_int, C.c_int],
+    "xivo_hip_pcw_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_pcw_set_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_pcw_get_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "xivo_hip_pcw_tracks": [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_ulonglong, C.c_ulonglong],
+    "xivo_hip_pcw_get_tracks": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
 }
 HOST_P_RESIDENT, HOST_KEEP_P = 1, 2
 
@@ -338,6 +348,8 @@ class Context:
     C-contiguous == column-major [rows x cols] per filter (Eigen's layout); the
     helpers below take/return [batch, rows, cols] arrays and do the transposes.
     """
+
+    pcw_npts = 0     # points per resident world (pcw_config; a borrowed context: set it to the owner's)
 
     def __init__(self, N, M_max, batch, device=0, flags=0):
         self.lib = load_library()
@@ -1042,6 +1054,60 @@ class Context:
             raise ValueError("off [B + 1], ids [off[B]], meas [off[B], 3]")
         self._check(self.lib.xivo_hip_life_begin(self.h, B, int(F), _ptr(off), _ptr(ids), _ptr(meas)))
         self.F = int(F)
+
+    def life_begin_tracks(self, F, B=None):
+        """life_begin on the tracks the last pcw_tracks(B) left on the device (asynchronous, no upload)"""
+        self._check(self.lib.xivo_hip_life_begin_tracks(self.h, self.batch if B is None else int(B), int(F)))
+        self.F = int(F)
+
+    # ---- point-cloud world on the device (xivo_hip_pcw_*)
+    def pcw_config(self, npts, fx=0.0, fy=0.0, cx=0.0, cy=0.0, imw=0.0, imh=0.0):
+        """the resident worlds of every filter, npts points each (<= the life cycle's tracks_max; 0 releases them), seen by
+        one pinhole camera; needs life_config first, and life_config releases them"""
+        o = np.zeros(1, dtype=pcw_opts_dtype)
+        o["struct_size"], o["npts"] = pcw_opts_dtype.itemsize, int(npts)
+        o["fx"], o["fy"], o["cx"], o["cy"], o["imw"], o["imh"] = fx, fy, cx, cy, imw, imh
+        self._check(self.lib.xivo_hip_pcw_config(self.h, _ptr(o)))
+        self.pcw_npts = int(npts)
+
+    def pcw_set_world(self, Xs, ids=None, next_id=None, b0=0):
+        """Xs [nb, npts, 3]; ids [nb, npts] int64 (None: no point is tracked); next_id [nb] (None: 10000)"""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 3 or Xs.shape[1:] != (self.pcw_npts, 3):
+            raise ValueError("Xs [nb, npts, 3]")
+        nb = Xs.shape[0]
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int64)
+        next_id = None if next_id is None else np.ascontiguousarray(next_id, dtype=np.int64)
+        if (ids is not None and ids.shape != (nb, self.pcw_npts)) or (next_id is not None and next_id.shape != (nb,)):
+            raise ValueError("ids [nb, npts], next_id [nb]")
+        self._check(self.lib.xivo_hip_pcw_set_world(self.h, int(b0), nb, _ptr(Xs), None if ids is None else _ptr(ids),
+                                                    None if next_id is None else _ptr(next_id)))
+
+    def pcw_get_world(self, b0=0, nb=None):
+        """-> (ids [nb, npts] int64, next_id [nb] int64); one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        ids = np.full((nb, self.pcw_npts), -1, dtype=np.int64)
+        next_id = np.zeros(nb, dtype=np.int64)
+        self._check(self.lib.xivo_hip_pcw_get_world(self.h, int(b0), nb, _ptr(ids), _ptr(next_id)))
+        return ids, next_id
+
+    def pcw_tracks(self, gsc, noise_px_std, seed, frame, B=None):
+        """one frame's tracks of filters [0, B) from the resident worlds (asynchronous): gsc [B, 12] = Rsc row-major, Tsc"""
+        gsc = np.ascontiguousarray(gsc, dtype=np.float64)
+        B = gsc.shape[0] if B is None else int(B)
+        if gsc.shape != (B, 12):
+            raise ValueError("gsc [B, 12]")
+        self._check(self.lib.xivo_hip_pcw_tracks(self.h, B, _ptr(gsc), float(noise_px_std), int(seed), int(frame)))
+
+    def pcw_get_tracks(self, tracks_max, b0=0, nb=None):
+        """what the last pcw_tracks left -> (cnt [nb] int32, ids [nb, tracks_max] int64, meas [nb, tracks_max, 3]); entries
+        behind cnt read -1 / 0; tracks_max: the life cycle's; one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        cnt = np.zeros(nb, dtype=np.int32)
+        ids = np.full((nb, int(tracks_max)), -1, dtype=np.int64)
+        meas = np.zeros((nb, int(tracks_max), 3))
+        self._check(self.lib.xivo_hip_pcw_get_tracks(self.h, int(b0), nb, _ptr(cnt), _ptr(ids), _ptr(meas)))
+        return cnt, ids, meas
 
     def life_end(self, B=None):
         """after the update and absorb_error (asynchronous)"""

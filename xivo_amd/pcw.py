@@ -198,11 +198,71 @@ class BatchTrajectorySim:
         return accel, gyro
 
 
+# ---- the device producer's noise stream on the host (xivo_amd/csrc/pcw_device.h is the specification)
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = np.uint32(0x9E3779B9), np.uint32(0xBB67AE85)
+_LO32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10: ctr [..., 4], key [..., 2] (uint32, broadcast against each other) -> words [..., 4] uint32"""
+    ctr, key = np.asarray(ctr, dtype=np.uint32), np.asarray(key, dtype=np.uint32)
+    shape = np.broadcast_shapes(ctr.shape[:-1], key.shape[:-1])
+    c = [np.broadcast_to(ctr[..., i], shape).copy() for i in range(4)]
+    k0, k1 = np.broadcast_to(key[..., 0], shape).copy(), np.broadcast_to(key[..., 1], shape).copy()
+    for r in range(10):
+        if r > 0:
+            with np.errstate(over="ignore"):               # uint32: meant to wrap
+                k0, k1 = k0 + _PHILOX_W0, k1 + _PHILOX_W1
+        p0, p1 = _PHILOX_M0 * c[0].astype(np.uint64), _PHILOX_M1 * c[2].astype(np.uint64)
+        c = [(p1 >> np.uint64(32)).astype(np.uint32) ^ c[1] ^ k0, (p1 & _LO32).astype(np.uint32),
+             (p0 >> np.uint64(32)).astype(np.uint32) ^ c[3] ^ k1, (p0 & _LO32).astype(np.uint32)]
+    return np.stack(c, axis=-1)
+
+
+def philox_words(seed, frame, b, p):
+    """the generator's four words of point p of filter b in that frame: key = the halves of seed, counter = (point, filter,
+    frame low, frame high); b and p broadcast -> [..., 4] uint32"""
+    b, p = np.broadcast_arrays(np.asarray(b, dtype=np.uint32), np.asarray(p, dtype=np.uint32))
+    seed, frame = int(seed) & (2 ** 64 - 1), int(frame) & (2 ** 64 - 1)
+    ctr = np.stack([p, b, np.full(p.shape, frame & 0xFFFFFFFF, dtype=np.uint32), np.full(p.shape, frame >> 32, dtype=np.uint32)], axis=-1)
+    return philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint32))
+
+
+def philox_normal(seed, frame, b, p):
+    """the pair of unit normals (noise_u, noise_v) the device producer draws for point p of filter b in that frame -> [..., 2].
+    Words to uniforms: u1 = ((w0 << 20 | w1 >> 12) + 0.5) 2^-52, u2 the same of (w2, w3); one Box-Muller pair. The words are
+    the device's exactly; log / sin / cos are numpy's, so a value may differ from the device's in the last places."""
+    w = philox_words(seed, frame, b, p).astype(np.uint64)
+    u1 = (((w[..., 0] << np.uint64(20)) | (w[..., 1] >> np.uint64(12))).astype(np.float64) + 0.5) * 2.0 ** -52
+    u2 = (((w[..., 2] << np.uint64(20)) | (w[..., 3] >> np.uint64(12))).astype(np.float64) + 0.5) * 2.0 ** -52
+    r, a = np.sqrt(-2.0 * np.log(u1)), 6.283185307179586 * u2
+    return np.stack([r * np.cos(a), r * np.sin(a)], axis=-1)
+
+
+def project_points(Xs, Rsc, Tsc, K, imw, imh):
+    """the projection and the visibility test in the evaluation order of pcw_device.h, elementwise (no einsum: its summation
+    order is not fixed): Xs [B, npts, 3], Rsc [B, 3, 3], Tsc [B, 3] -> (vis [B, npts] bool, u, v, Xc_2 [B, npts])"""
+    d = [Xs[..., i] - Tsc[:, None, i] for i in range(3)]
+    Xc = [(Rsc[:, None, 0, i] * d[0] + Rsc[:, None, 1, i] * d[1]) + Rsc[:, None, 2, i] * d[2] for i in range(3)]
+    front = Xc[2] > 0
+    z = np.where(front, Xc[2], 1.0)
+    u = K[0, 0] * Xc[0] / z + K[0, 2]
+    v = K[1, 1] * Xc[1] / z + K[1, 2]
+    return front & (u >= 0) & (v >= 0) & (u <= imw) & (v <= imh), u, v, Xc[2]
+
+
 class BatchPCW:
     """B point-cloud worlds with RandomPCW's track-id semantics; generate() returns the concatenated track lists in the
-    layout xivo::hip::BatchEstimator::VisualMeasPointCloud takes (offsets, ids, (x, y, depth) rows)."""
+    layout xivo::hip::BatchEstimator::VisualMeasPointCloud takes (offsets, ids, (x, y, depth) rows).
+    noise: "numpy" (default) draws the pixel noise from the world's numpy generator; "philox" draws the stream of the device
+    producer (philox_normal, keyed by noise_seed and the number of generate() calls so far as the frame) and projects in its
+    evaluation order (project_points), so that a host arm can be held against a device arm."""
 
-    def __init__(self, B, npts=1000, xlim=(-10, 10), ylim=(-10, 10), zlim=(-5, 5), seed=0, Xs=None):
+    def __init__(self, B, npts=1000, xlim=(-10, 10), ylim=(-10, 10), zlim=(-5, 5), seed=0, Xs=None, noise="numpy", noise_seed=0):
+        if noise not in ("numpy", "philox"):
+            raise ValueError("noise must be 'numpy' or 'philox'")
+        self.noise, self.noise_seed, self.frame = noise, int(noise_seed), 0
         self.rng = np.random.default_rng(seed)
         lo = np.array([xlim[0], ylim[0], zlim[0]], dtype=float); hi = np.array([xlim[1], ylim[1], zlim[1]], dtype=float)
         self.Xs = self.rng.uniform(lo, hi, size=(B, npts, 3)) if Xs is None else np.asarray(Xs, dtype=float)
@@ -210,13 +270,20 @@ class BatchPCW:
         self.next_pt_id = np.full(self.Xs.shape[0], 10000, dtype=np.int64)
 
     def generate(self, Rsc, Tsc, K, imw, imh, noise_px_std):
-        Xc = np.einsum("bpj,bji->bpi", self.Xs - Tsc[:, None, :], Rsc)       # Rsc^T (Xs - Tsc)
-        front = Xc[..., 2] > 0
-        z = np.where(front, Xc[..., 2], 1.0)
-        u = K[0, 0] * Xc[..., 0] / z + K[0, 2]
-        v = K[1, 1] * Xc[..., 1] / z + K[1, 2]
-        vis = front & (u >= 0) & (v >= 0) & (u <= imw) & (v <= imh)
-        noise = noise_px_std * self.rng.standard_normal(u.shape + (2,))
+        if self.noise == "philox":
+            vis, u, v, zc = project_points(self.Xs, Rsc, Tsc, K, imw, imh)
+            Xc = np.stack([u, v, zc], axis=-1)                                # (only [..., 2] is read below)
+            B, npts = u.shape
+            noise = noise_px_std * philox_normal(self.noise_seed, self.frame, np.arange(B)[:, None], np.arange(npts)[None, :])
+            self.frame += 1
+        else:
+            Xc = np.einsum("bpj,bji->bpi", self.Xs - Tsc[:, None, :], Rsc)   # Rsc^T (Xs - Tsc)
+            front = Xc[..., 2] > 0
+            z = np.where(front, Xc[..., 2], 1.0)
+            u = K[0, 0] * Xc[..., 0] / z + K[0, 2]
+            v = K[1, 1] * Xc[..., 1] / z + K[1, 2]
+            vis = front & (u >= 0) & (v >= 0) & (u <= imw) & (v <= imh)
+            noise = noise_px_std * self.rng.standard_normal(u.shape + (2,))
         new = vis & (self.ids < 0)
         rank = np.cumsum(new, axis=1) - 1                                     # order of appearance inside a world
         self.ids = np.where(new, self.next_pt_id[:, None] + rank, self.ids)

@@ -36,6 +36,11 @@ What is mirrored from the reference and what is simplified:
     sends op lists; "device" - the slot book lives on the device and the frame is xivo_hip_life_begin -> update ->
     xivo_hip_life_end (lifecycle_kernels.hip): the tracks of all filters go down in one array, nothing is downloaded during
     a frame, `books` / `n_updates` / `n_rejected` are read from the device on demand. Same decisions, same results.
+  * where the tracks come from (`SequenceConfig.track_source`): "host" (default) - the numpy worlds of xivo_amd/pcw.py, uploaded
+    by the frame call; "device" (needs lifecycle="device") - the worlds are resident and xivo_hip_pcw_tracks (pcw_kernels.hip)
+    produces each frame's tracks from the ground-truth camera poses straight into the block the life cycle reads
+    (`SequenceRunner.frame_world`): 96 bytes per filter go down instead of the tracks. Its pixel noise is the counter-based
+    stream pcw.philox_normal restates.
   * NOT IN EITHER: RefineDepth (`use_depth_opt`), gauge XY features and SwitchRefGroup, ownership transfer, OOS updates.
 The numerics of every step are the device path; this file holds no arithmetic of the filter itself.
 """
@@ -159,6 +164,10 @@ class SequenceConfig:
         # during a frame). tracks_max: the most tracks one filter may bring in a frame on the device path.
         self.lifecycle = "host"
         self.tracks_max = 1024
+        # where a frame's tracks come from: "host" (the simulator's arrays, uploaded) or "device" (xivo_hip_pcw_tracks on the
+        # resident worlds of npts points each; needs lifecycle = "device" and npts <= tracks_max)
+        self.track_source = "host"
+        self.npts = 1000
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option " + k)
@@ -324,6 +333,8 @@ class HipBackend:
             self.enable_pool()
         if cfg.lifecycle == "device":
             self.enable_device_lifecycle()
+        if cfg.track_source == "device":
+            self.enable_device_world()
 
     def enable_device_lifecycle(self):
         """allocate the device-resident slot book and track staging (xivo_hip_life_config). The new feature's variances are
@@ -333,6 +344,27 @@ class HipBackend:
         std = np.array([c.initial_std_x / fl, c.initial_std_y / fl, c.initial_std_z])
         self.ctx.life_config(c.tracks_max, min_depth=c.min_depth, max_depth=c.max_depth, min_new_features=c.min_new_features,
                              var_xyz=std * std)
+
+    def enable_device_world(self):
+        """allocate the resident worlds of the device track source (xivo_hip_pcw_config): cfg.npts points per filter, the
+        camera of cfg.cam"""
+        cam = self.cfg.cam
+        self.ctx.pcw_config(self.cfg.npts, cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["cols"], cam["rows"])
+
+    def set_world(self, Xs, ids=None, next_id=None):
+        """the world points [B, npts, 3] of every filter (ids None: nothing is tracked yet, next_id None: 10000)"""
+        self.ctx.pcw_set_world(Xs, ids, next_id)
+
+    def make_tracks(self, gsc, noise_px_std, seed, frame):
+        """the frame's tracks from the resident worlds (asynchronous): gsc [B, 12] ground-truth camera poses"""
+        self.ctx.pcw_tracks(gsc, noise_px_std, seed, frame, B=self.B)
+
+    def life_begin_tracks(self):
+        self.ctx.life_begin_tracks(self.F, B=self.B)
+
+    def world_ids(self):
+        """(ids [B, npts], next_id [B]) of the resident worlds; one synchronising read"""
+        return self.ctx.pcw_get_world(0, self.B)
 
     def life_begin(self, off, ids, meas):
         self.ctx.life_begin(self.F, off, ids, meas, B=self.B)
@@ -515,6 +547,14 @@ def check_lifecycle(cfg):
         raise ValueError("lifecycle must be 'host' or 'device'")
     if cfg.lifecycle == "device" and cfg.feature_init != "immediate":
         raise ValueError("lifecycle='device' runs the 'immediate' life cycle only (feature_init=%r)" % (cfg.feature_init,))
+    src = getattr(cfg, "track_source", "host")
+    if src not in ("host", "device"):
+        raise ValueError("track_source must be 'host' or 'device'")
+    if src == "device":
+        if cfg.lifecycle != "device":
+            raise ValueError("track_source='device' needs lifecycle='device'")
+        if not 0 < cfg.npts <= cfg.tracks_max:
+            raise ValueError("track_source='device' needs 0 < npts <= tracks_max (npts=%d, tracks_max=%d)" % (cfg.npts, cfg.tracks_max))
 
 
 def _op(b, kind, i0=0, i1=0, i2=0, v=()):
@@ -543,6 +583,7 @@ class SequenceRunner:
         self.admitted = []           # (frame, filter, track id, sub-filter steps taken) of every pool entry that entered the state
         self.init_z = None           # [B] AdaptInitialDepth's init_z after the last frame (adaptive_initial_depth)
         self.timers = None       # set to {} to accumulate wall seconds per phase (adds a device sync per phase)
+        self.noise_px_std, self.noise_seed = 0.0, 0   # frame_world: the device producer's pixel noise and its generator's key
 
     # books / n_updates / n_rejected: the host life cycle keeps them here; the device life cycle reads them from the device
     # on demand (one synchronising read each - not something to ask for every frame of a timed run)
@@ -596,6 +637,28 @@ class SequenceRunner:
             ids, meas = np.zeros(0, dtype=np.int64), np.zeros((0, 3))
         t0 = self._tick("host_pre", t0) or t0
         be.life_begin(off, ids, meas)
+        t0 = self._tick("edit", t0) or t0
+        mask = be.update(download=self.want_mask)
+        t0 = self._tick("update", t0) or t0
+        be.life_end()
+        self._tick("edit", t0)
+        return mask
+
+    def frame_world(self, imu, gsc, frame):
+        """one camera frame whose tracks the device produces (track_source="device"): gsc [B, 12] the ground-truth camera pose
+        of every filter (Rsc row-major, Tsc), frame the frame's number (the noise generator's counter). propagate -> pcw_tracks
+        -> life_begin_tracks -> update -> life_end; nothing but the poses goes down and nothing comes back (unless want_mask)."""
+        import time
+        if self.cfg.track_source != "device":
+            raise ValueError("frame_world needs track_source='device'")
+        be = self.be
+        t0 = time.perf_counter()
+        if imu is not None:
+            be.propagate(imu)
+        t0 = self._tick("propagate", t0) or t0
+        be.make_tracks(gsc, self.noise_px_std, self.noise_seed, frame)
+        t0 = self._tick("tracks", t0) or t0
+        be.life_begin_tracks()
         t0 = self._tick("edit", t0) or t0
         mask = be.update(download=self.want_mask)
         t0 = self._tick("update", t0) or t0
@@ -837,7 +900,7 @@ def initial_poses(cfg, sims, t0=0.0):
 
 
 def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0,
-            timers=None, trajectory_log=False, map_log=False, rpe_dt=1.0, innovation_log=False):
+            timers=None, trajectory_log=False, map_log=False, rpe_dt=1.0, innovation_log=False, noise_seed=0):
     """The loop of scripts/pyxivo_pcw.py:117-163 for B = len(sims) sequences at once.
     -> dict(ts [n] ns, Tsb [n x B x 3], Wsb [n x B x 3], gt_Tsb [n x B x 3], runner, backend)
     trajectory_log (True, or the error-state columns to keep): the estimate of every frame is recorded on the device
@@ -852,7 +915,10 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     nothing changes.
     innovation_log: every frame's update records its NIS on the device (HipBackend.enable_innovation_log) and the log is read
     once at the end: adds `innovation`, nis_per_dof [n], nis_per_dof_seq [B], nis_used [n], nis_records_left_out
-    (_innovation). A backend without enable_innovation_log (the oracle) leaves the keys out."""
+    (_innovation). A backend without enable_innovation_log (the oracle) leaves the keys out.
+    cfg.track_source = "device": the points of `worlds` go to the device once and every frame is SequenceRunner.frame_world
+    on the ground-truth camera poses; the worlds' own generate_measurements is not called, the pixel noise is the device's
+    stream keyed by noise_seed, and with map_log the world ids are downloaded once per recorded frame."""
     B = len(sims)
     K = np.array([[cfg.cam["fx"], 0, cfg.cam["cx"]], [0, cfg.cam["fy"], cfg.cam["cy"]], [0, 0, 1.0]])
     Rbc = so3_exp(cfg.Wbc)
@@ -861,6 +927,10 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     be = backend_factory(cfg, B, poses0, P0)
     runner = SequenceRunner(be, cfg, B)
     runner.timers = timers
+    dev_tracks = cfg.track_source == "device"
+    if dev_tracks:
+        be.set_world(np.array([w.Xs for w in worlds]))
+        runner.noise_px_std, runner.noise_seed = noise_vision_std, noise_seed
     m0 = [s.meas(0.0) for s in sims]
     feeder = ImuFeeder(B, 0.0, [m[1] for m in m0], [m[0] for m in m0])
     n_imu = int(round(total_time / imu_dt)); every = int(round(vision_dt / imu_dt))
@@ -881,11 +951,17 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
             tracks = []
             for b in range(B):
                 Rsb, Tsb = sims[b].gsb(t)
+                if dev_tracks:
+                    tracks.append(np.concatenate([(Rsb @ Rbc).reshape(-1), Rsb @ cfg.Tbc + Tsb]))
+                    continue
                 tracks.append(worlds[b].generate_measurements(Rsb @ Rbc, Rsb @ cfg.Tbc + Tsb, K, cfg.cam["cols"],
                                                               cfg.cam["rows"], noise_vision_std))
             if ilog:
                 be.frame_ts = int(round(t * 1e9))
-            runner.frame(feeder.take(), tracks)
+            if dev_tracks:
+                runner.frame_world(feeder.take(), np.array(tracks), len(ts))
+            else:
+                runner.frame(feeder.take(), tracks)
             ts.append(int(round(t * 1e9)))
             if trajectory_log:
                 be.record(ts[-1])
@@ -895,8 +971,8 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
                 est_T.append(T); est_W.append(np.array([so3_log(r) for r in R]))
             gt_T.append(np.array([s.gsb(t)[1] for s in sims]))
             if mlog is not None:
-                mlog.record(ts[-1], [bk.feat_id for bk in runner.books], np.array([w.ids for w in worlds]),
-                            np.array([w.Xs for w in worlds]))
+                mlog.record(ts[-1], [bk.feat_id for bk in runner.books],
+                            be.world_ids()[0] if dev_tracks else np.array([w.ids for w in worlds]), np.array([w.Xs for w in worlds]))
     out = dict(ts=np.array(ts), gt_Tsb=np.array(gt_T), runner=runner, backend=be)
     if mlog is not None:
         mlog.finish(out)
@@ -945,21 +1021,44 @@ def run_pcw_cpp(cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, vision_dt=0.04
     return out
 
 
+def camera_poses(Rsb, Tsb, Rbc, Tbc):
+    """ground-truth camera poses of B bodies -> (Rsc [B, 3, 3], Tsc [B, 3], gsc [B, 12] as xivo_hip_pcw_tracks takes them)"""
+    Rsc, Tsc = Rsb @ Rbc, np.einsum("bij,j->bi", Rsb, Tbc) + Tsb
+    return Rsc, Tsc, np.concatenate([Rsc.reshape(-1, 9), Tsc], axis=1)
+
+
 def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0, npts=1000, seed=0, device=0,
-                  timers=None, trajectory_log=False, map_log=False, rpe_dt=1.0, innovation_log=False):
+                  timers=None, trajectory_log=False, map_log=False, rpe_dt=1.0, innovation_log=False, track_source=None,
+                  noise="numpy", noise_seed=0):
     """Thousands of sequences end to end: the vectorised simulators of xivo_amd/pcw.py (BatchTrajectorySim, BatchPCW) feed
     xivo::hip::BatchEstimator message by message. -> dict(ts, Tsb [n x B x 3], gt_Tsb, estimator)
     trajectory_log: as in run_pcw - one record launch per frame on the estimator's context and one read at the end instead of
     a pose download per frame; adds `trajectory`, err6 / nees / anees / nees_used and ate_aligned / ate_raw / rpe_pos / rpe_rot.
     map_log: as in run_pcw, on the estimator's context; the slot book is the estimator's (BatchEstimator.book).
-    innovation_log: as in run_pcw; the C++ frame records between its update and AbsorbError (BatchEstimator::EnableInnovationLog)."""
+    innovation_log: as in run_pcw; the C++ frame records between its update and AbsorbError (BatchEstimator::EnableInnovationLog).
+    track_source ("host" / "device", default cfg.track_source): "device" keeps the worlds on the device
+    (BatchEstimator::EnableDeviceWorld) and every frame hands down the ground-truth camera poses only
+    (VisualMeasDeviceWorld); the pixel noise is then the stream of pcw.philox_normal keyed by noise_seed. noise="philox" gives
+    the host track source the same stream and projection order (BatchPCW(noise="philox")), for comparing the two. With map_log
+    and device tracks, the world's ids are read from the device once per recorded frame (xivo_hip_pcw_get_world: B x npts ids, a
+    synchronising download - not for a timed run).
+    timers: "sim_imu" and "sim_tracks" are the two simulators' shares, "sim" their sum; with device tracks "sim_tracks" is the
+    ground-truth pose alone."""
+    import copy
     import time
     from .batch import BatchEstimator
     from .pcw import BatchPCW, BatchTrajectorySim
+    dev_tracks = (track_source or cfg.track_source) == "device"
+    if track_source is not None or dev_tracks:
+        cfg = copy.copy(cfg)
+        cfg.track_source = "device" if dev_tracks else "host"
+        if dev_tracks:
+            cfg.npts = npts
+        check_lifecycle(cfg)
     motion = ["lissajous" if b % 2 == 0 else "trefoil" for b in range(B)]
     rate = 0.08 + 0.04 * (np.arange(B) % 7) / 7
     sim = BatchTrajectorySim(motion, rate, seed=seed + 1)
-    world = BatchPCW(B, npts=npts, seed=seed)
+    world = BatchPCW(B, npts=npts, seed=seed, noise=noise, noise_seed=noise_seed)
     K = np.array([[cfg.cam["fx"], 0, cfg.cam["cx"]], [0, cfg.cam["fy"], cfg.cam["cy"]], [0, 0, 1.0]])
     Rbc = so3_exp(cfg.Wbc)
     poses = np.zeros(B, dtype=L.pose_dtype)
@@ -968,6 +1067,8 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     poses["Rbc"] = Rbc.T.reshape(-1); poses["Tbc"] = cfg.Tbc; poses["Rsg"] = np.eye(3).reshape(-1)
     est = BatchEstimator(cfg, B, poses, cfg.P_init(), device=device)
     host = est.host
+    if dev_tracks:
+        est.enable_device_world(world.Xs)
     n_imu = int(round(total_time / imu_dt)); every = int(round(vision_dt / imu_dt))
     ts, est_T, gt_T, gt_R = [], [], [], []
     ctx = None
@@ -977,6 +1078,7 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     mlog = None
     if map_log:
         mctx = ctx if ctx is not None else L.Context.borrow(host.xivo_batch_ctx(est.h), cfg.N, 2 * cfg.n_features, B)
+        mctx.pcw_npts = npts
         mlog = _MapLog(mctx, (n_imu + every - 1) // every, cfg.n_features, B)
     ictx = None
     if innovation_log:
@@ -987,18 +1089,21 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
         t = k * imu_dt
         t0 = time.perf_counter()
         accel, gyro = sim.meas(t)
-        tm["sim"] = tm.get("sim", 0.0) + time.perf_counter() - t0
+        tm["sim_imu"] = tm.get("sim_imu", 0.0) + time.perf_counter() - t0
         est.InertialMeas(t, gyro, accel)
         if k % every == 0:
             t0 = time.perf_counter()
             Rsb, Tsb = sim.gsb(t)
-            off, ids, meas = world.generate(Rsb @ Rbc, np.einsum("bij,j->bi", Rsb, cfg.Tbc) + Tsb, K, cfg.cam["cols"],
-                                            cfg.cam["rows"], noise_vision_std)
+            Rsc, Tsc, gsc = camera_poses(Rsb, Tsb, Rbc, cfg.Tbc)
+            if not dev_tracks:
+                off, ids, meas = world.generate(Rsc, Tsc, K, cfg.cam["cols"], cfg.cam["rows"], noise_vision_std)
             t1 = time.perf_counter()
-            tm["sim"] = tm.get("sim", 0.0) + t1 - t0
+            tm["sim_tracks"] = tm.get("sim_tracks", 0.0) + t1 - t0
             mask = np.zeros((B, cfg.n_features), dtype=np.uint8) if est.want_mask else None   # (device life cycle: no download)
-            if host.xivo_batch_visual(est.h, float(t), off.ctypes.data, ids.ctypes.data, meas.ctypes.data,
-                                      mask.ctypes.data if mask is not None else None) != 0:
+            if dev_tracks:
+                est.VisualMeasDeviceWorld(t, gsc, noise_vision_std, noise_seed, mask)
+            elif host.xivo_batch_visual(est.h, float(t), off.ctypes.data, ids.ctypes.data, meas.ctypes.data,
+                                        mask.ctypes.data if mask is not None else None) != 0:
                 raise RuntimeError("VisualMeasPointCloud failed")
             if est.device_lifecycle and timers is not None:
                 # the device life cycle only enqueues the frame: a timed run waits for it here, so that "frame" ends where the
@@ -1012,7 +1117,9 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
             else:
                 est_T.append(est.poses()["Tsb"].copy())
             if mlog is not None:
-                mlog.record(ts[-1], [est.book(b)[0] for b in range(B)], world.ids, world.Xs)
+                mlog.record(ts[-1], [est.book(b)[0] for b in range(B)], mctx.pcw_get_world(0, B)[0] if dev_tracks else world.ids,
+                            world.Xs)
+    tm["sim"] = tm.get("sim_imu", 0.0) + tm.get("sim_tracks", 0.0)
     out = dict(ts=np.array(ts), gt_Tsb=np.array(gt_T), estimator=est)
     if mlog is not None:
         mlog.finish(out)
