@@ -77,8 +77,8 @@ __global__ __launch_bounds__(256) void fwd_vec_kernel(const double* __restrict__
 // All 16 waves of the workgroup must call it (barriers); `sL` = the whole 160 KB of LDS.
 // SRC_REGS: Src = A itself (a symmetric rank-k product, P - W^T W): the wave that owns a block copies its registers
 // into the LDS buffer - nothing is read back from memory. NEG_OUT: Out = Minit - A Src^T.
-// FIXUP: Src arrives by DMA as usual and the wave that owns a block then replaces it in LDS by 2 Src - A (its registers):
-// the whitened Joseph form needs (W - D)^T (W + D) with only W in memory (see TF == 4 below).
+// (The whitened Joseph form off a stash, (W - D)^T (W + D) with only W in memory, has a walk of its own:
+// whitened_tiles_from_stash.)
 // YREGS (with SRC_REGS): the LDS operand is 2 Wr - A from the owner waves' registers (short factors keep W in registers:
 // no stash, no DMA, no fix-up pass).
 // P+ = G K^T - T (estimator.cpp:1280-1287 re-associated) with the rows of G in registers: the same tile walk as the T

@@ -9,8 +9,10 @@
 
 // XIVO_TRACE (scripts/build_variant.sh trace "-DXIVO_TRACE=1"; scripts/trace_solve.py reads it back): shader-clock stamps inside
 // trsm_lds_f64_kernel<., 4> of every 64th workgroup - wave 0 at the phase boundaries of the kernel (XTR / XTRP), every wave
-// inside the product phases (XTR2: behind the fix-up, behind each tile's MFMA chain, behind each tile's stores). Timing
-// only, results unchanged; compiled out by default. Where the kernel's time goes: DESIGN.md 3.0.
+// inside the product phases of whitened_tiles_from_stash (XTR2: slot 0 behind the phase barrier, 1 behind the fix-up, 2 + 2 t /
+// 3 + 2 t behind the MFMA chain / the stores of the wave's t-th tile of the phase - at most jbp <= 5 tiles at the seven to
+// eleven block rows this product runs at, slots 2..11 - and 14 at the end of the phase). Timing only, results unchanged;
+// compiled out by default. Where the kernel's time goes: DESIGN.md 3.0.
 #ifndef XIVO_TRACE
 #define XIVO_TRACE 0
 #endif
@@ -19,9 +21,9 @@ __device__ unsigned long long xivo_trace_buf[512 * 32];
 __device__ unsigned long long xivo_trace2_buf[128 * 16 * 4 * 16];   // [workgroup][wave][phase][slot]
 #define XTR(i) do { if (T4 && !WOUT && threadIdx.x == 0 && (blockIdx.x & 63) == 0 && (blockIdx.x >> 6) < 512) \
     xivo_trace_buf[(blockIdx.x >> 6) * 32 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define XTRP(i) do { if (FIXUP && threadIdx.x == 0 && (blockIdx.x & 63) == 0 && (blockIdx.x >> 6) < 512) \
+#define XTRP(i) do { if (threadIdx.x == 0 && (blockIdx.x & 63) == 0 && (blockIdx.x >> 6) < 512) \
     xivo_trace_buf[(blockIdx.x >> 6) * 32 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define XTR2(ph, slot) do { if (FIXUP && (threadIdx.x & 63) == 0 && (blockIdx.x & 63) == 0 && (blockIdx.x >> 6) < 128 && (ph) < 4 && (slot) < 16) \
+#define XTR2(ph, slot) do { if ((threadIdx.x & 63) == 0 && (blockIdx.x & 63) == 0 && (blockIdx.x >> 6) < 128 && (ph) < 4 && (slot) < 16) \
     xivo_trace2_buf[(((blockIdx.x >> 6) * 16 + (threadIdx.x >> 6)) * 4 + (ph)) * 16 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
 extern "C" int xivo_hip_debug_read_trace(unsigned long long* out, int n) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(xivo_trace_buf), (size_t)n * sizeof(unsigned long long));
@@ -66,7 +68,7 @@ __device__ __forceinline__ void buf_st_out(double v, __amdgpu_buffer_rsrc_t r, u
   __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(bufu2, v), r, voff, soff, 0);
 }
 
-template <int NBM, bool SRC_REGS = false, bool NEG_OUT = false, bool FIXUP = false, bool YREGS = false, int NWV = 16>
+template <int NBM, bool SRC_REGS = false, bool NEG_OUT = false, bool YREGS = false, int NWV = 16>
 __device__ __forceinline__ void sym_tiles_from_regs(const d4 (&X)[NBM], const d4 (&Wr)[NBM], double* sL, const double* __restrict__ Src, int ldsrc,
                                                     const double* __restrict__ Minit, int ldm, double* __restrict__ Out, int ldo,
                                                     int nb, int nwl, int jbp, bool live, int w, int wave, int lane) {
@@ -128,29 +130,10 @@ __device__ __forceinline__ void sym_tiles_from_regs(const d4 (&X)[NBM], const d4
   d4 nxt = d4{0.0, 0.0, 0.0, 0.0};
   if (todo) load_m(__builtin_ctz(todo), nxt);
   for (int p = 0; p < nph; ++p) {
-    XTRP(8 + 3 * p);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    XTRP(9 + 3 * p);
     __syncthreads();                               // phase p landed for every wave; the other buffer is free again
-    XTRP(10 + 3 * p);
-    XTR2(p, 0);
-    int tslot = 2;
     const int jb0 = p * jbp;
     const double* buf = sL + (p & 1) * bufsz;
-    if (FIXUP) {
-      if (live && w >= jb0 && w < jb0 + min(jbp, nwl - jb0)) {
-        double* dst = sL + (p & 1) * bufsz + (w - jb0) * nb * 256 + lane;
-#pragma unroll
-        for (int mb = 0; mb < NBM; ++mb) {
-          if (mb < nb) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dst[(mb * 4 + r) * 64] = fma(2.0, dst[(mb * 4 + r) * 64], -X[mb][r]);
-          }
-        }
-      }
-      lds_barrier();
-    }
-    XTR2(p, 1);
     bool fetch = p + 1 < nph;                      // phase p + 1 is requested once the first tile has its -Minit (so that
     while (todo) {                                 // the wait on those loads does not sit behind the new requests)
       const int jl = __builtin_ctz(todo);
@@ -177,7 +160,6 @@ __device__ __forceinline__ void sym_tiles_from_regs(const d4 (&X)[NBM], const d4
           }
         }
       }
-      XTR2(p, tslot); ++tslot;
       const int ba = jb <= w ? w : jb, bbk = jb <= w ? jb : w;
       const int a = 16 * ba + li, b = 16 * bbk + lg;
 #pragma unroll
@@ -187,6 +169,138 @@ __device__ __forceinline__ void sym_tiles_from_regs(const d4 (&X)[NBM], const d4
           const double v = NEG_OUT ? -acc[r] : acc[r];
           buf_st_out(v, rO, vO, (unsigned)(16 * ba + (16 * bbk + 4 * r) * ldo) * 8u);
           if (a != bb) buf_st_out(v, rO, vOt, (unsigned)(16 * bbk + 4 * r + 16 * ba * ldo) * 8u);
+        }
+      }
+    }
+    if (fetch) issue(p + 1);
+    todo = my_tiles(p + 1);
+    if (todo) load_m((p + 1) * jbp + __builtin_ctz(todo), nxt);
+  }
+}
+
+// The whitened Joseph product off the stash,  P+ = P - (W - D)^T (W + D)  in place (TF == 4 with seven or more block rows):
+// the only copy of W is the stash, and it is read ONCE - by the DMA that brings it into LDS, jbp column blocks per phase,
+// two buffers, laid out as in sym_tiles_from_regs. Wave w enters with D (the residual of its backward substitution) in X.
+// In the phase in which its own block arrives, group(w) = w / jbp, it reads the block behind the phase barrier, forms
+// V = W - D and Y = 2 W - V (= W + D), writes V back to the LDS block and keeps Y in X: from then on the register
+// operand of a wave is Y and the LDS operand of a block is V (the same count of LDS reads and writes as a fix-up of the
+// LDS operand alone, followed by the same LDS-only barrier).
+// Who forms which tile: a pair {i, j} of column blocks with group(i) < group(j) is formed in phase group(j) by wave i (Y_i
+// in registers, V_j in LDS); the pairs inside one group and its diagonal tiles are shared among that group's nj waves by
+// the cyclic rule restricted to the group (d = (w - j) mod nj: 2 d < nj, or 2 d == nj and the larger index takes it) - every
+// unordered pair once. Tile counts per phase grow (10 / 26 / 42 / 58 at 16 blocks, jbp = 4) and the early waves form the
+// most tiles, but with waves w, w + 4, w + 8, w + 12 on one SIMD every SIMD gets the same total. Waves whose block has not
+// arrived only issue their share of the DMA and meet the barriers.
+// Tile orientation, the -P start of the accumulator with its one-tile-ahead prefetch, the lower-triangle-authoritative
+// diagonal tile, the stores and the order of the (mb, r) chain are those of sym_tiles_from_regs: every element of P+ is the
+// sum of the same products, of entry (a, b) or (b, a) of V^T Y (they differ by the antisymmetric term that the
+// lower-triangle + mirror evaluation drops; the diagonal tile is V_w^T Y_w entry (a, b)).
+// All NWV waves of the workgroup must call it (barriers); `sL` = the whole 160 KB of LDS.
+template <int NBM, int NWV>
+__device__ __forceinline__ void whitened_tiles_from_stash(d4 (&X)[NBM], double* sL, const double* __restrict__ Src, int ldsrc,
+                                                          double* __restrict__ Pio, int ldp, int nb, int nwl, int jbp, bool live,
+                                                          int w, int wave, int lane) {
+  const int li = lane & 15, lg = lane >> 4;
+  const int nph = (nwl + jbp - 1) / jbp;
+  const int bufsz = jbp * nb * 256;                // doubles per LDS buffer (two of them)
+  const int gw = w / jbp;                          // the phase in which this wave's own block arrives
+  auto issue = [&](int p) {                        // (as in sym_tiles_from_regs: 8 columns m x 16 rows j per instruction)
+    const int jb0 = p * jbp, nj = min(jbp, nwl - jb0);
+    double* buf = sL + (p & 1) * bufsz;
+    for (int q = wave; q < nj * 2 * nb; q += NWV) {
+      const int jl = q / (2 * nb), t = q - jl * 2 * nb;
+      const double* src = Src + (16 * (jb0 + jl) + 2 * (lane & 7)) + (long)(8 * t + (lane >> 3)) * ldsrc;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                       (__attribute__((address_space(3))) void*)(buf + jl * nb * 256 + t * 128), 16, 0, 0);
+    }
+  };
+  auto my_tiles = [&](int p) -> unsigned {
+    if (!live || p >= nph || gw > p) return 0u;
+    const int jb0 = p * jbp, nj = min(jbp, nwl - jb0);
+    if (gw < p) return (1u << nj) - 1u;            // every block of a later group
+    unsigned todo = 0;
+    for (int jl = 0; jl < nj; ++jl) {
+      int d = w - (jb0 + jl);
+      if (d < 0) d += nj;
+      if (2 * d < nj || (2 * d == nj && w > jb0 + jl)) todo |= 1u << jl;
+    }
+    return todo;
+  };
+  const __amdgpu_buffer_rsrc_t rP = buf_rsrc(Pio);
+  const unsigned vP = (unsigned)(li + lg * ldp) * 8u, vPt = (unsigned)(lg + li * ldp) * 8u;   // element (li, lg) of a block, and of its mirror image
+  auto load_m = [&](int jb, d4& acc) {
+    const int ba = jb <= w ? w : jb, bb = jb <= w ? jb : w;       // block (ba, bb), ba >= bb
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      acc[r] = buf_ld_once(rP, vP, (unsigned)(16 * ba + (16 * bb + 4 * r) * ldp) * 8u);   // (negated where it is consumed: no wait here)
+  };
+  issue(0);
+  unsigned todo = my_tiles(0);
+  d4 nxt = d4{0.0, 0.0, 0.0, 0.0};
+  if (todo) load_m(__builtin_ctz(todo), nxt);
+  for (int p = 0; p < nph; ++p) {
+    XTRP(8 + 3 * p);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    XTRP(9 + 3 * p);
+    __syncthreads();                               // phase p landed for every wave; the other buffer is free again
+    XTRP(10 + 3 * p);
+    XTR2(p, 0);
+    int tslot = 2;
+    const int jb0 = p * jbp;
+    const double* buf = sL + (p & 1) * bufsz;
+    if (live && gw == p) {                         // own block: W -> V in LDS, D -> Y in the registers
+      double* dst = sL + (p & 1) * bufsz + (w - jb0) * nb * 256 + lane;
+#pragma unroll
+      for (int mb = 0; mb < NBM; ++mb) {
+        if (mb < nb) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const double wv = dst[(mb * 4 + r) * 64];
+            const double v = wv - X[mb][r];
+            X[mb][r] = fma(2.0, wv, -v);
+            dst[(mb * 4 + r) * 64] = v;
+          }
+        }
+      }
+    }
+    lds_barrier();
+    XTR2(p, 1);
+    bool fetch = p + 1 < nph;                      // phase p + 1 is requested once the first tile has its -P (so that
+    while (todo) {                                 // the wait on those loads does not sit behind the new requests)
+      const int jl = __builtin_ctz(todo);
+      todo &= todo - 1;
+      const int jb = jb0 + jl;
+      d4 acc = -nxt;
+      if (fetch) { asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3])); issue(p + 1); fetch = false; }
+      if (todo) load_m(jb0 + __builtin_ctz(todo), nxt);
+      const double* Bop = buf + jl * nb * 256 + lane;
+      if (jb < w) {
+#pragma unroll
+        for (int mb = 0; mb < NBM; ++mb) {
+          if (mb < nb) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc = mfma(Bop[(mb * 4 + r) * 64], X[mb][r], acc);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int mb = 0; mb < NBM; ++mb) {
+          if (mb < nb) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc = mfma(X[mb][r], Bop[(mb * 4 + r) * 64], acc);
+          }
+        }
+      }
+      XTR2(p, tslot); ++tslot;
+      const int ba = jb <= w ? w : jb, bbk = jb <= w ? jb : w;
+      const int a = 16 * ba + li, b = 16 * bbk + lg;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int bb = b + 4 * r;
+        if (jb != w || a >= bb) {   // diagonal tile: the lower triangle is authoritative
+          const double v = -acc[r];
+          buf_st_out(v, rP, vP, (unsigned)(16 * ba + (16 * bbk + 4 * r) * ldp) * 8u);
+          if (a != bb) buf_st_out(v, rP, vPt, (unsigned)(16 * bbk + 4 * r + 16 * ba * ldp) * 8u);
         }
       }
       XTR2(p, tslot); ++tslot;
@@ -225,6 +339,9 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
   //  each - BASELINE config 2)
   constexpr bool KEEPW = T4 && (NBM <= 6 || (NBM == 7 && NWV <= 12 && MINB <= 3));
   constexpr bool PACK = T4 && NBM > 10;
+  // the in-kernel whitened product off a stash: the backward substitution leaves D in the registers and the product forms both of
+  // its operands from the copy of W that the DMA brings into LDS anyway (whitened_tiles_from_stash) - the stash is read once
+  constexpr bool DREGS = T4 && !KEEPW && !WOUT;
   extern __shared__ __attribute__((aligned(16))) double sL[];   // [nb(nb+1)/2][16 x 17]
   const int chunks = (g.Np + 16 * NWV - 1) / (16 * NWV);
   const int b = blockIdx.x;
@@ -391,11 +508,12 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
   for (int k = NBM - 1; k >= 0; --k) {
     if (k < nb && !g.fwd_only) {
       const double* Dk = sL + (k * (k + 1) / 2 + k) * BLK;
-      // TF == 4: W_k comes back from the stash while this step's MFMAs run (requested here, used at the end of the step;
-      // the last block row has not been touched yet: it is still in X)
+      // TF == 5 (and KEEPW from its registers): W_k comes back from the stash while this step's MFMAs run (requested here, used
+      // at the end of the step; the last block row has not been touched yet: it is still in X). The in-kernel product off the
+      // stash (DREGS) does not read it back: X[k] keeps D_k and meets W_k in LDS, where the product's DMA delivers it.
       d4 wk = d4{0.0, 0.0, 0.0, 0.0};
       if (KEEPW) wk = Wk[k];
-      else if (T4) {
+      else if (T4 && !DREGS) {
         if (k == nb - 1) wk = X[k];
         else {
 #pragma unroll
@@ -439,14 +557,15 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
         }
       }
       // TF == 4: V_k = W_k - D_k, the row block of V^T = (W - D)^T - the register operand of the covariance product below
-      // (or, for states wider than one workgroup, of the tiled product outside: then Y_k = W_k + D_k leaves for g.Yout here)
+      // (or, for states wider than one workgroup, of the tiled product outside: then Y_k = W_k + D_k leaves for g.Yout here).
+      // DREGS: X[k] stays D_k; the product forms V_k and Y_k itself.
       if (T4) {
         if (WOUT) {
           const __amdgpu_buffer_rsrc_t rY = buf_rsrc(g.Yout + (long)filt * g.strideY2);
 #pragma unroll
           for (int r = 0; r < 4; ++r) buf_st(wk[r] + X[k][r], rY, (unsigned)((c0 + li) + lg * g.ldy2) * 8u, (unsigned)((16 * k + 4 * r) * g.ldy2) * 8u);
         }
-        X[k] = wk - X[k];
+        if (!DREGS) X[k] = wk - X[k];
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -468,11 +587,11 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
   part += __shfl_xor(part, 32);
   if (lg == 0) g.err[(long)filt * g.strideErr + c0 + li] = part;
 
-  // TF == 4: X = V now. The covariance update is the Joseph expression for the gain just computed, in the whitened
+  // TF == 4: X = V now (DREGS: X = D, and V = W - D is formed in the product). The covariance update is the Joseph expression for the gain just computed, in the whitened
   // coordinates of the factor (S = L L^T, H P = L W, V = L^T K^T = W - D):
   //   P+ = P - K(HP) - (K(HP))^T + K S K^T = P - V^T W - W^T V + V^T V = P - (W - D)^T (W + D) + (W^T D - D^T W),
   // whose antisymmetric last term drops out of the lower-triangle + mirror evaluation every pipeline here uses. The rows
-  // of V^T = (W - D)^T are the register operand, W + D = 2 W - V the LDS operand (below).
+  // of V^T = (W - D)^T are the register operand, W + D = 2 W - V the LDS operand (below) - the other way round off a stash.
 
   }
   if (!TF) return;
@@ -493,24 +612,24 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
       }
       return;
     }
-    // ---- P+ = P - (W - D)^T (W + D) in place: W arrives from the stash by DMA, the owner waves turn it into W + D
+    // ---- P+ = P - (W - D)^T (W + D) in place: W arrives from the stash by DMA, the owner waves turn it into W - D (LDS) and
+    //      W + D (registers)
     if (g.skip_status && g.skip_status[filt] != 0) return;   // S not positive definite: P stays the prior
     double* Pio = g.T + (long)filt * g.strideT;
-    if constexpr (KEEPW) sym_tiles_from_regs<NBM, true, true, false, true, NWV>(X, Wk, sL, nullptr, 0, Pio, g.ldt, Pio, g.ldt, nb, g.Np / 16, g.t_jbp,
+    if constexpr (KEEPW) sym_tiles_from_regs<NBM, true, true, true, NWV>(X, Wk, sL, nullptr, 0, Pio, g.ldt, Pio, g.ldt, nb, g.Np / 16, g.t_jbp,
                                                                  live, c0 >> 4, wave, lane);
-    else sym_tiles_from_regs<NBM, false, true, true, false, NWV>(X, X, sL, g.K + (long)filt * g.strideK, g.ldk, Pio, g.ldt, Pio, g.ldt, nb, g.Np / 16, g.t_jbp,
-                                                     live, c0 >> 4, wave, lane);
+    else whitened_tiles_from_stash<NBM, NWV>(X, sL, g.K + (long)filt * g.strideK, g.ldk, Pio, g.ldt, nb, g.Np / 16, g.t_jbp, live, c0 >> 4, wave, lane);
     return;
   }
   if (TF == 2) {
     // ---- symmetric form: P+ = P - W^T W in place, W^T = the forward-substituted columns still in registers
     if (g.skip_status && g.skip_status[filt] != 0) return;   // S not positive definite: P stays the prior
     double* Pio = g.T + (long)filt * g.strideT;
-    sym_tiles_from_regs<NBM, true, true, false, false, NWV>(X, X, sL, nullptr, 0, Pio, g.ldt, Pio, g.ldt, nb, g.Np / 16, g.t_jbp, live, c0 >> 4, wave, lane);
+    sym_tiles_from_regs<NBM, true, true, false, NWV>(X, X, sL, nullptr, 0, Pio, g.ldt, Pio, g.ldt, nb, g.Np / 16, g.t_jbp, live, c0 >> 4, wave, lane);
     return;
   }
   // ---- T = K (HP) - P
-  sym_tiles_from_regs<NBM, false, false, false, false, NWV>(X, X, sL, PHT, g.ldpht, g.Pm + (long)filt * g.stridePm, g.ldpm, g.T + (long)filt * g.strideT, g.ldt,
+  sym_tiles_from_regs<NBM, false, false, false, NWV>(X, X, sL, PHT, g.ldpht, g.Pm + (long)filt * g.stridePm, g.ldpm, g.T + (long)filt * g.strideT, g.ldt,
                            nb, g.Np / 16, g.t_jbp, live, c0 >> 4, wave, lane);
 }
 
