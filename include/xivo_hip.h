@@ -583,6 +583,9 @@ int xivo_hip_pool_adapt_depth_config(xivo_hip_ctx* ctx, const xivo_adapt_depth_o
  * stays. DEVIATION: the reference takes depth[n >> 1] in std::unordered_map iteration order, unsorted - an order that is not
  * a property of the input; this is the median the code names. init_z_out (host [B], may be NULL): init_z afterwards. */
 int xivo_hip_pool_adapt_depth(xivo_hip_ctx* ctx, int B, double* init_z_out);
+/* The resident init_z of filters [b0, b0 + nb) as it is, without an AdaptInitialDepth step (the device pool life cycle runs that
+ * step itself and copies nothing out). Needs xivo_hip_pool_adapt_depth_config. Synchronises. */
+int xivo_hip_pool_get_init_z(xivo_hip_ctx* ctx, int b0, int nb, double* init_z_out);
 /* xivo_hip_pool_add with options: XIVO_POOL_ADD_ADAPTIVE_Z takes z0 from the filter's resident init_z instead of the record
  * (the record's z0 is then ignored; xivo_hip_pool_adapt_depth_config must have run). options = 0 is xivo_hip_pool_add. */
 #define XIVO_POOL_ADD_ADAPTIVE_Z 1u
@@ -958,6 +961,79 @@ int xivo_hip_life_begin(xivo_hip_ctx* ctx, int B, int F, const int* off, const l
 int xivo_hip_life_end(xivo_hip_ctx* ctx, int B);
 /* The counters of filters [b0, b0 + nb). Synchronises. */
 int xivo_hip_life_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_life_stats* out);
+
+/* ---- device-resident feature life cycle, "subfilter" mode: the pool life cycle (opt-in) ------------------------------------
+ * The reference's own life cycle of a new track (src/manager.cpp:18-130) decided on the device: what a sequence driver
+ * otherwise decides per filter on the host around xivo_hip_pool_step and sends down as op lists (XIVO_EDIT_REMOVE_*,
+ * XIVO_EDIT_ADD_GROUP_ANCHOR, XIVO_EDIT_ADMIT_POOL), xivo_hip_set_pixels, xivo_hip_pool_anchor and xivo_hip_pool_add. One
+ * workgroup per filter. Next to the in-state book of the immediate life cycle (feat_id, group_refs) a filter has a pool book:
+ * ent_id[pool_max] (track id held by pool entry e, -1: free), ent_born[pool_max] (frame counter at the entry's creation),
+ * anc_used[anchor_max], anc_life[anchor_max] (Group::lifetime). An entry's anchor is the resident entry's ref_sind, an anchor's
+ * link the resident anchor's slot (xivo_hip_pool_get). A frame is
+ *   xivo_hip_propagate -> xivo_hip_pool_life_begin -> update -> xivo_hip_absorb_error -> xivo_hip_pool_life_end
+ * and no call of it synchronises or downloads anything. P, the scene, the pool, the anchors and init_z equal those of the op
+ * lists bit for bit: both run the same device functions in the same order. Every camera model is supported (a new entry is
+ * initialised by the device code of xivo_hip_pool_add). The rules, per filter, in frame order:
+ *   begin  - a used anchor's life is incremented, an unused anchor's is 0 (Group::IncrementLifetime, :36-41);
+ *          - of a repeated id among the tracks the last occurrence supplies the pixel, for feature slots and pool entries;
+ *          - in-state features without a track leave the state, groups left empty leave with them (an anchor linked to such a
+ *            slot is frozen at the group's pose and unlinked, as XIVO_EDIT_REMOVE_GROUP does); pool entries without a track
+ *            are freed (ProcessTracks, :171-250);
+ *          - the pool step (as xivo_hip_pool_step, triangulation included when configured) on the other entries' pixels;
+ *          - entries the step did not leave live are freed; the step's order is walked: the walk stops when no feature slot is
+ *            free; an entry whose anchor is unlinked takes the lowest free group slot (ADD_GROUP_ANCHOR), and without a free
+ *            group slot that entry is skipped and the walk goes on; admission is ADMIT_POOL into the lowest free feature slot
+ *            (:332-450); every in-state feature then takes the frame's pixel.
+ *   end    - features with a zero inlier mask leave the state (rejected), groups left empty are discarded;
+ *          - new tracks are those whose id is in neither the state nor the pool after these removals, by ascending id, ties
+ *            by position; of a repeated id among them only the first takes part, the others are ignored and counted nowhere;
+ *          - with a new track: without a free anchor all are counted as pool_dropped; else the lowest free anchor is created
+ *            from the current pose, unlinked, life 0, the new tracks take the free entries in ascending order
+ *            (Feature::Initialize with z0 = initial_z, or the resident init_z with adaptive_z), the surplus is pool_dropped;
+ *          - a used, unlinked anchor with life > max_group_lifetime that no live entry references is freed
+ *            (EnforceMaxGroupLifetime, :282-304); then AdaptInitialDepth when xivo_hip_pool_adapt_depth_config is on. */
+#define XIVO_POOL_LIFE_MAX_ANCHORS 256   /* anchors per filter the kernels' LDS plan holds */
+typedef struct {
+  int struct_size;         /* sizeof(xivo_pool_life_opts) */
+  int tracks_max;          /* most tracks one filter brings in a frame; 0 releases everything the config allocated */
+  int max_group_lifetime;  /* EnforceMaxGroupLifetime's bound */
+  int adaptive_z;          /* != 0: a new entry's z0 is the filter's resident init_z (needs xivo_hip_pool_adapt_depth_config) */
+  double initial_z;        /* z0 of a new entry otherwise */
+  double std_xyz[3];       /* initial std of a new entry's (x, y, depth coordinate) */
+} xivo_pool_life_opts;
+typedef struct {
+  long long updates, rejected, dropped, admitted, groups_added, not_spd;   /* as xivo_life_stats */
+  long long pool_added;      /* new tracks that took a pool entry */
+  long long pool_dropped;    /* new tracks that found no entry or no anchor */
+  long long pool_outliers;   /* entries freed because the step did not leave them live (a tracker-dropped entry is not counted) */
+  long long anchors_created, anchors_freed;
+  long long admit_steps;     /* sum over admitted entries of the frames since the entry was created */
+} xivo_pool_life_stats;
+/* (Re-)allocates the books (everything free, counters 0, frame counter 0), the step's device xp / order / n / live, and the
+ * track block with its two page-locked staging blocks (as xivo_hip_life_config). Needs xivo_hip_pool_config with no live entry
+ * and no anchor created since, and a layout; else, or with the immediate device life cycle configured, a wrong struct_size,
+ * tracks_max outside [0, XIVO_LIFE_MAX_TRACKS], values that are not finite, initial_z <= 0, or adaptive_z without
+ * xivo_hip_pool_adapt_depth_config: XIVO_HIP_ERR_INVALID. More than XIVO_LIFE_MAX_SLOTS feature or group slots or more than
+ * XIVO_POOL_LIFE_MAX_ANCHORS anchors: XIVO_HIP_ERR_UNSUPPORTED. While configured, xivo_hip_pool_anchor, xivo_hip_pool_add(_ex),
+ * xivo_hip_pool_step and the XIVO_EDIT_ADD_GROUP_ANCHOR / XIVO_EDIT_ADMIT_POOL ops return XIVO_HIP_ERR_INVALID and change
+ * nothing (the context's host mirrors of the pool are stale); xivo_hip_pool_get / _tri_counts / _adapt_depth_config work.
+ * tracks_max = 0 releases and re-reads the mirrors from the device, after which the host life cycle can go on; so does
+ * xivo_hip_pool_config. Synchronises. */
+int xivo_hip_pool_life_config(xivo_hip_ctx* ctx, const xivo_pool_life_opts* opts);
+/* The in-state ids, as xivo_hip_life_set_book / xivo_hip_life_get_book; get_book also returns the pool book: ent_id
+ * [nb][pool_max], ent_born [nb][pool_max], anc_used [nb][anchor_max], anc_life [nb][anchor_max]. Any output may be NULL. */
+int xivo_hip_pool_life_set_book(xivo_hip_ctx* ctx, int b0, int nb, const long long* feat_id);
+int xivo_hip_pool_life_get_book(xivo_hip_ctx* ctx, int b0, int nb, long long* feat_id, int* feat_ref, int* group_refs,
+                                long long* ent_id, int* ent_born, int* anc_used, int* anc_life);
+/* Before the update: uploads the tracks (off / ids / meas as xivo_hip_life_begin; the depth column is not read), then the begin
+ * kernel, triangulation and the pool step, the admit kernel. strict: CandidateStrict (vision_counter >=
+ * strict_criteria_timesteps). Increments the frame counter. XIVO_HIP_ERR_INVALID before anything is copied or launched: not
+ * configured, a malformed off, a filter above tracks_max, begin twice without end. */
+int xivo_hip_pool_life_begin(xivo_hip_ctx* ctx, int B, int F, const int* off, const long long* ids, const double* meas, int strict);
+/* After the update and xivo_hip_absorb_error, with the B of begin: the end kernel, then AdaptInitialDepth when configured. */
+int xivo_hip_pool_life_end(xivo_hip_ctx* ctx, int B);
+/* The counters of filters [b0, b0 + nb). Synchronises. */
+int xivo_hip_pool_life_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_pool_life_stats* out);
 
 /* ---- point-cloud world: the simulator's tracks produced on the device (opt-in; needs the device life cycle) ---------------
  * What BatchPCW.generate (xivo_amd/pcw.py, after the reference's scripts/point_cloud_world.py:44-131) computes on the host per

@@ -74,6 +74,12 @@ def main():
     ap.add_argument("-lifecycle", default="host", choices=["host", "device"],
                     help="who runs the per-frame feature life cycle: the host side (op lists, the default) or the device "
                          "(xivo_hip_life_begin / _end: nothing is downloaded during a frame)")
+    ap.add_argument("-feature_init", default="immediate", choices=["immediate", "subfilter"],
+                    help="life cycle of a new feature: it enters the state at once with the simulator's depth (the default), or "
+                         "the reference's: from initial_z through the depth sub-filter in the device-resident feature pool")
+    ap.add_argument("-pool-lifecycle", dest="pool_lifecycle", default="host", choices=["host", "device"],
+                    help="-feature_init subfilter: who decides its life cycle, the host side around xivo_hip_pool_step (op lists, "
+                         "the default) or the device (xivo_hip_pool_life_begin / _end: nothing is downloaded during a frame)")
     ap.add_argument("-tracks", default="host", choices=["host", "device"],
                     help="where a frame's tracks come from: the numpy point-cloud world, uploaded by the frame call (the "
                          "default), or the worlds resident on the device (xivo_hip_pcw_tracks: only the ground-truth camera "
@@ -82,6 +88,12 @@ def main():
     a = ap.parse_args()
     # (a sequence never brings more tracks than its world has points)
     life = dict(lifecycle=a.lifecycle, tracks_max=min(a.npts, sequence.L.LIFE_MAX_TRACKS))
+    if a.feature_init != "immediate" or a.pool_lifecycle != "host":
+        life.update(feature_init=a.feature_init, pool_lifecycle=a.pool_lifecycle)
+        try:      # before any rank is spawned: what check_lifecycle rejects
+            sequence.check_lifecycle(sequence.SequenceConfig(**life))
+        except ValueError as e:
+            ap.error(str(e))
     if a.tracks == "device":
         life.update(track_source="device", npts=a.npts)
         if a.host == "cpp" and not a.vectorized:
@@ -107,6 +119,8 @@ def main():
         print(json.dumps({
             "sequences": a.sequences, "frames_per_sequence": frames, "N": cfg.N, "integration": a.integration_method,
             "host": "cpp, vectorised simulators", "lifecycle": a.lifecycle, "tracks": a.tracks,
+            "feature_init": a.feature_init, "pool_lifecycle": a.pool_lifecycle,
+            **({"admitted": st["admitted"], "pool_dropped": st["pool_dropped"]} if a.feature_init == "subfilter" else {}),
             "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
             **_consistency(out),
             "updates": st["updates"], "mh_rejected": st["mh_rejected"], "wall_s": wall, "simulator_s": tm.get("sim", 0.0),
@@ -178,7 +192,7 @@ def main():
     print(json.dumps({
         "sequences": B, "n_gpus": world, "frames_per_sequence": frames, "imu_samples_per_frame": int(round(a.vision_dt / a.imu_dt)),
         "N": cfg.N, "max_features": cfg.n_features, "integration": a.integration_method, "host": a.host,
-        "lifecycle": a.lifecycle, "tracks": a.tracks,
+        "lifecycle": a.lifecycle, "tracks": a.tracks, "feature_init": a.feature_init, "pool_lifecycle": a.pool_lifecycle,
         "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
         **_consistency(out),
         "updates": n_upd, "mh_rejected": n_rej,

@@ -58,6 +58,7 @@ def load_host_library():
         _HOST.xivo_batch_init_z.argtypes = [C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_innov_log.argtypes = [C.c_void_p, C.c_int]
         _HOST.xivo_batch_enable_device_lifecycle.argtypes = [C.c_void_p, C.c_int]
+        _HOST.xivo_batch_enable_device_pool_lifecycle.argtypes = [C.c_void_p, C.c_int]
         _HOST.xivo_batch_enable_device_world.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_visual_world.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_ulonglong, C.c_void_p]
     return _HOST
@@ -66,6 +67,8 @@ def load_host_library():
 class BatchEstimator:
     def __init__(self, cfg, B, poses0, P0, device=0):
         """cfg: xivo_amd.sequence.SequenceConfig; poses0: [B] pose_dtype; P0: [N, N] shared initial covariance"""
+        from .sequence import check_lifecycle
+        check_lifecycle(cfg)                     # (before anything is allocated)
         self.host = load_host_library()
         self.cfg, self.B, self.F = cfg, B, cfg.n_features
         c = np.zeros(1, dtype=batch_cfg_dtype)
@@ -91,7 +94,9 @@ class BatchEstimator:
             raise RuntimeError("xivo_batch_create failed")
         self.h = h
         self.device_lifecycle = getattr(cfg, "lifecycle", "host") == "device"
-        self.want_mask = not self.device_lifecycle   # device life cycle: no mask download unless asked for
+        self.device_pool_lifecycle = getattr(cfg, "pool_lifecycle", "host") == "device"
+        # device life cycles: no mask download unless asked for
+        self.want_mask = not (self.device_lifecycle or self.device_pool_lifecycle)
         if self.device_lifecycle:
             if getattr(cfg, "feature_init", "immediate") != "immediate":
                 raise ValueError("lifecycle='device' runs the 'immediate' life cycle only")
@@ -123,6 +128,8 @@ class BatchEstimator:
                 dc["adapt"] = a
                 if self.host.xivo_batch_enable_depth_init(self.h, dc.ctypes.data) != 0:
                     raise RuntimeError("xivo_batch_enable_depth_init failed")
+            if self.device_pool_lifecycle:
+                self.enable_device_pool_lifecycle(cfg.tracks_max)
 
     def init_z(self):
         """AdaptInitialDepth's init_z [B] after the last frame (None while adaptive_initial_depth is off)"""
@@ -140,6 +147,13 @@ class BatchEstimator:
         downloads nothing unless a mask is asked for, book() and stats() read the device"""
         if self.host.xivo_batch_enable_device_lifecycle(self.h, int(tracks_max)) != 0:
             raise RuntimeError("xivo_batch_enable_device_lifecycle failed")
+
+    def enable_device_pool_lifecycle(self, tracks_max):
+        """BatchEstimator::EnableDevicePoolLifecycle: after the sub-filter life cycle (and its depth initialisation) is set up,
+        its decisions move to the device (xivo_hip_pool_life_*); VisualMeasPointCloud then downloads nothing unless a mask is
+        asked for, book() and stats() read the device"""
+        if self.host.xivo_batch_enable_device_pool_lifecycle(self.h, int(tracks_max)) != 0:
+            raise RuntimeError("xivo_batch_enable_device_pool_lifecycle failed")
 
     def enable_device_world(self, Xs):
         """BatchEstimator::EnableDeviceWorld: the worlds' points Xs [B, npts, 3] go to the device once (camera: cfg.cam); the

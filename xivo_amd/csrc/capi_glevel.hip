@@ -644,6 +644,22 @@ int xivo_hip_candidate_order(const xivo_subfilter_feat* feats, int nb, int n, in
 }
 
 // ---- out-of-state feature pool
+}  // extern "C"
+namespace xivo_hip::capi {
+// one pool step of filters [0, B) on the context's pool: everything but where the pixels come from and the results go (xp, order,
+// n, live) - xivo_hip_pool_step points them at its per-call staging, xivo_hip_pool_life_begin at its resident buffers
+PoolStepArgs pool_step_args(xivo_hip_ctx* c, int B, int strict) {
+  PoolStepArgs a{};
+  a.pool = c->fpool; a.anchors = c->anchors; a.pool_max = c->pool_max; a.anchor_max = c->anchor_max;
+  a.poses = c->poses; a.groups = c->groups; a.n_groups = c->lay.n_groups;
+  a.cam = c->cam; a.calib = c->calib_on ? c->calib : nullptr; a.cam_dim = c->calib_on ? c->cl.cam_dim : 0;
+  a.invdepth = (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0;
+  a.o = c->pool_opts; a.remove_outlier = c->pool_remove_outlier; a.strict = strict ? 1 : 0; a.batch = B;
+  a.tri = c->pool_tri; a.tri_good = c->tri_counts; a.tri_bad = c->tri_counts + c->Bmax;
+  return a;
+}
+}  // namespace xivo_hip::capi
+extern "C" {
 static int ensure_pool_io(xivo_hip_ctx* c, size_t bytes) { return c->mem.grow(&c->pool_io, &c->pool_io_cap, bytes); }
 
 int xivo_hip_pool_config(xivo_hip_ctx* c, int pool_max, int anchor_max, const xivo_subfilter_opts* opts,
@@ -652,6 +668,7 @@ int xivo_hip_pool_config(xivo_hip_ctx* c, int pool_max, int anchor_max, const xi
   if (!c || pool_max < 1 || anchor_max < 1 || !opts) return XIVO_HIP_ERR_INVALID;
   if (pool_max > XIVO_POOL_MAX_ENTRIES) return XIVO_HIP_ERR_UNSUPPORTED;
   HIP_TRY(hipStreamSynchronize(c->stream));
+  pool_life_release(c);   // the device pool life cycle's books describe the pool given back here
   c->mem.release(&c->fpool, &c->anchors, &c->tri_counts, &c->init_z);
   c->pool_max = c->anchor_max = 0;
   c->pool_tri = xivo_triangulate_opts{}; c->adapt = xivo_adapt_depth_opts{}; c->adapt_on = false;
@@ -676,7 +693,7 @@ int xivo_hip_pool_config(xivo_hip_ctx* c, int pool_max, int anchor_max, const xi
 
 int xivo_hip_pool_anchor(xivo_hip_ctx* c, int b0, int nb, const int* slot) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (bad_range(c, b0, nb) || !c->fpool || !c->poses || (nb > 0 && !slot)) return XIVO_HIP_ERR_INVALID;
+  if (bad_range(c, b0, nb) || !c->fpool || c->plife_on || !c->poses || (nb > 0 && !slot)) return XIVO_HIP_ERR_INVALID;
   for (int b = 0; b < nb; ++b) {
     if (slot[b] < -1 || slot[b] >= c->anchor_max) return XIVO_HIP_ERR_INVALID;
     if (slot[b] >= 0 && c->anchor_link_h[(size_t)(b0 + b) * c->anchor_max + slot[b]] >= 0) return XIVO_HIP_ERR_INVALID;   // linked
@@ -700,7 +717,7 @@ int xivo_hip_pool_add(xivo_hip_ctx* c, int n, const xivo_pool_new* recs) { retur
 
 int xivo_hip_pool_add_ex(xivo_hip_ctx* c, int n, const xivo_pool_new* recs, unsigned options) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (!c || !c->fpool || !c->have_layout || n < 0 || (n > 0 && !recs)) return XIVO_HIP_ERR_INVALID;
+  if (!c || !c->fpool || c->plife_on || !c->have_layout || n < 0 || (n > 0 && !recs)) return XIVO_HIP_ERR_INVALID;
   if ((options & ~XIVO_POOL_ADD_ADAPTIVE_Z) != 0u) return XIVO_HIP_ERR_INVALID;
   const bool adaptive = (options & XIVO_POOL_ADD_ADAPTIVE_Z) != 0u;
   if (adaptive && !c->adapt_on) return XIVO_HIP_ERR_INVALID;
@@ -732,22 +749,17 @@ int xivo_hip_pool_add_ex(xivo_hip_ctx* c, int n, const xivo_pool_new* recs, unsi
 int xivo_hip_pool_step(xivo_hip_ctx* c, int B, const double* xp, int strict, int* order_out, int* n_out,
                        unsigned char* live_out) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (!c || !c->fpool || !c->have_layout || !c->poses || B <= 0 || B > c->Bmax || !xp || !order_out || !n_out || !live_out)
+  if (!c || !c->fpool || c->plife_on || !c->have_layout || !c->poses || B <= 0 || B > c->Bmax || !xp || !order_out || !n_out ||
+      !live_out)
     return XIVO_HIP_ERR_INVALID;
   const size_t ne = (size_t)B * c->pool_max;
   const size_t b_xp = ne * 2 * sizeof(double), b_ord = ne * sizeof(int), b_n = (size_t)B * sizeof(int);
   int rc = ensure_pool_io(c, b_xp + b_ord + b_n + ne);
   if (rc) return rc;
   char* io = c->pool_io;
-  PoolStepArgs a{};
-  a.pool = c->fpool; a.anchors = c->anchors; a.pool_max = c->pool_max; a.anchor_max = c->anchor_max;
-  a.poses = c->poses; a.groups = c->groups; a.n_groups = c->lay.n_groups;
-  a.cam = c->cam; a.calib = c->calib_on ? c->calib : nullptr; a.cam_dim = c->calib_on ? c->cl.cam_dim : 0;
-  a.invdepth = (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0;
-  a.o = c->pool_opts; a.remove_outlier = c->pool_remove_outlier; a.strict = strict ? 1 : 0; a.batch = B;
+  PoolStepArgs a = pool_step_args(c, B, strict);
   a.xp = (const double*)io; a.order = (int*)(io + b_xp); a.n = (int*)(io + b_xp + b_ord);
   a.live = (unsigned char*)(io + b_xp + b_ord + b_n);
-  a.tri = c->pool_tri; a.tri_good = c->tri_counts; a.tri_bad = c->tri_counts + c->Bmax;
   HIP_TRY(hipMemcpyAsync(io, xp, b_xp, hipMemcpyHostToDevice, c->stream));
   {
     StageTimer st(c, ST_OTHER, 0.0, "pool_step_kernel");
@@ -858,6 +870,15 @@ int xivo_hip_pool_adapt_depth(xivo_hip_ctx* c, int B, double* init_z_out) {
   return XIVO_HIP_OK;
 }
 
+int xivo_hip_pool_get_init_z(xivo_hip_ctx* c, int b0, int nb, double* init_z_out) {
+  if (bad_range(c, b0, nb) || !c->init_z || !c->adapt_on || (nb > 0 && !init_z_out)) return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (nb == 0) return XIVO_HIP_OK;
+  HIP_TRY(hipMemcpyAsync(init_z_out, c->init_z + b0, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
 int xivo_hip_absorb_error(xivo_hip_ctx* c, int B) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0 || !c->mask) return XIVO_HIP_ERR_INVALID;
@@ -895,12 +916,12 @@ int xivo_hip_edit_batch(xivo_hip_ctx* c, int F, int n_ops, const xivo_edit_op* o
         ok = e.i0 >= 0 && e.i0 < F && e.i1 >= 0 && e.i1 < L.n_features && e.i2 >= 0 && e.i2 < L.n_groups; break;
       case XIVO_EDIT_REMOVE_FEATURE: case XIVO_EDIT_SET_XP: ok = e.i0 >= 0 && e.i0 < F; break;
       case XIVO_EDIT_ADD_GROUP_ANCHOR:
-        ok = c->fpool && e.i0 >= 0 && e.i0 < L.n_groups && e.i1 >= 0 && e.i1 < c->anchor_max &&
+        ok = c->fpool && !c->plife_on && e.i0 >= 0 && e.i0 < L.n_groups && e.i1 >= 0 && e.i1 < c->anchor_max &&
              c->anchor_link_h[(size_t)e.b * c->anchor_max + e.i1] == -1;
         for (int k = 0; ok && k < c->anchor_max; ++k) ok = c->anchor_link_h[(size_t)e.b * c->anchor_max + k] != e.i0;
         break;
       case XIVO_EDIT_ADMIT_POOL:
-        ok = c->fpool && e.i0 >= 0 && e.i0 < F && e.i1 >= 0 && e.i1 < L.n_features && e.i2 >= 0 && e.i2 < c->pool_max;
+        ok = c->fpool && !c->plife_on && e.i0 >= 0 && e.i0 < F && e.i1 >= 0 && e.i1 < L.n_features && e.i2 >= 0 && e.i2 < c->pool_max;
         if (ok) {
           const int anc = c->pool_anchor_h[(size_t)e.b * c->pool_max + e.i2];
           ok = anc >= 0 && c->anchor_link_h[(size_t)e.b * c->anchor_max + anc] >= 0;

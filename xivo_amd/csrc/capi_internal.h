@@ -8,6 +8,7 @@
 //   capi_map.hip        landmark log: per-frame in-state features, world positions and covariances, read-out, landmark NEES
 //   capi_innov.hip      innovation log: per-frame NIS / pre- and post-fit sums of every filter's update, read-out, ensemble sums
 //   capi_lifecycle.hip  device life cycle: the per-filter slot book, the two frame calls around the update, counters
+//   capi_pool_lifecycle.hip  device pool life cycle ("subfilter" mode): the pool book, the two frame calls, counters
 //   capi_pcw.hip        point-cloud world: the resident worlds, the per-frame track producer, read-back
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
@@ -183,6 +184,18 @@ struct xivo_hip_ctx {
   size_t life_set_bytes = 0;
   int life_cur = 0, life_B = 0, life_n = 0;
   bool life_strided = false;   // the open frame reads the strided form of the track block (xivo_hip_life_begin_tracks)
+  // device pool life cycle (xivo_hip_pool_life_*, capi_pool_lifecycle.hip): the in-state book [Bmax][plife_ld] / [Bmax][n_groups],
+  // the pool book [Bmax][pool_max] / [Bmax][anchor_max], the counters [Bmax], what a frame's kernels hand each other
+  // (slot_track, ent_track, the step's xp / order / n / live); null until xivo_hip_pool_life_config. The track block is the one
+  // above (life_dev, life_pin, life_ev, life_B: the two life cycles exclude each other). plife_frame: the frame counter
+  bool plife_on = false;
+  xivo_pool_life_opts plife_opts{};
+  long long* plife_feat_id = nullptr; int* plife_group_refs = nullptr;
+  long long* plife_ent_id = nullptr; int* plife_ent_born = nullptr; int* plife_anc_used = nullptr; int* plife_anc_life = nullptr;
+  xivo_pool_life_stats* plife_stats = nullptr;
+  int* plife_slot_track = nullptr; int* plife_ent_track = nullptr;
+  double* plife_xp = nullptr; int* plife_order = nullptr; int* plife_n = nullptr; unsigned char* plife_live = nullptr;
+  int plife_ld = 0, plife_frame = 0;
   // point-cloud world (xivo_hip_pcw_*, capi_pcw.hip): the resident worlds Xs [Bmax][npts][3] / ids [Bmax][npts] / next_id [Bmax],
   // the frame's camera poses [Bmax][12] with two page-locked staging blocks (the scheme of life_pin) and cnt [Bmax]; null until
   // xivo_hip_pcw_config. The producer writes the strided form of life_dev: pcw_tracks_B is the B whose tracks the block holds
@@ -286,12 +299,27 @@ int stage_measurements(xivo_hip_ctx* c, int b0, int nb, int M, const double* dH,
 // the strided form of the track block life_dev (behind the offsets' space): ids [Bmax][tracks_max], meas [Bmax][tracks_max][3]
 long long* life_strided_ids(xivo_hip_ctx* c);
 double* life_strided_meas(xivo_hip_ctx* c);
+// the track block both device life cycles keep a frame's tracks in (life_dev, two page-locked staging blocks with an event each)
+int track_block_alloc(xivo_hip_ctx* c, int tracks_max);
+void track_block_release(xivo_hip_ctx* c);   // (the stream must be idle)
+bool track_block_frame_ok(int B, const int* off, const long long* ids, const double* meas, int tracks_max);
+int track_block_upload(xivo_hip_ctx* c, int B, const int* off, const long long* ids, const double* meas);
+void track_block_args(xivo_hip_ctx* c, int B, int n, LifeArgs& a);
+// the in-state book of either life cycle (xivo_hip_life_set_book / _get_book on the given device arrays)
+int book_set(xivo_hip_ctx* c, int b0, int nb, const long long* feat_id, long long* d_ids, int ld, int* d_refs);
+int book_get(xivo_hip_ctx* c, int b0, int nb, const long long* d_ids, int ld, const int* d_refs, long long* feat_id,
+             int* feat_ref, int* group_refs);
+
+// ---- capi_pool_lifecycle.hip
+void pool_life_release(xivo_hip_ctx* c);   // everything xivo_hip_pool_life_config allocated (the stream must be idle)
 
 // ---- capi_pcw.hip
 void pcw_release(xivo_hip_ctx* c);   // the worlds and the pose staging (the stream must be idle)
 
 // ---- capi_glevel.hip
 int ensure_gate_buffers(xivo_hip_ctx* c, int F);
+// the arguments of one pool step but xp / order / n / live (xivo_hip_pool_step and the device pool life cycle share them)
+PoolStepArgs pool_step_args(xivo_hip_ctx* c, int B, int strict);
 int ensure_dense(xivo_hip_ctx* c);
 int ensure_HT(xivo_hip_ctx* c);
 // H P (+ P H^T) of the stacked dense rows of filters [0, B) and the dense-row gate on them (gate_dense_kernel); `a` brings the

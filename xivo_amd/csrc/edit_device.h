@@ -1,9 +1,11 @@
 // Row / column edits of one filter's padded P by its own workgroup of 256 threads: the building blocks of
 // Estimator::{Add,Remove}{Group,Feature}{To,From}State (src/estimator.cpp:739-846) that edit_batch_kernel (state_kernels.hip)
-// and the device life cycle (lifecycle_kernels.hip) share. Every call ends on a workgroup barrier, so calls may follow each
+// and the device life cycles (lifecycle_kernels.hip, pool_lifecycle_kernels.hip) share. Every call ends on a workgroup barrier, so calls may follow each
 // other directly; all 256 threads must make the call.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "ekf_kernels.h"
 
 namespace xivo_hip {
 
@@ -22,6 +24,48 @@ __device__ __forceinline__ void edit_copy_rc(double* P, int ldp, int Np, int dst
   __syncthreads();
   for (int t = tid; t < Np; t += 256)
     for (int r = 0; r < len; ++r) P[t + (long)(dst + r) * ldp] = P[t + (long)(src + r) * ldp];
+  __syncthreads();
+}
+
+
+// ---- the edits of the scene and the pool that go with them (the cases of edit_batch_kernel of the same names); `anchors` /
+// `pool` / `groups` / `feats` are the filter's own rows
+// XIVO_EDIT_REMOVE_GROUP: an anchor linked to the slot keeps the group's last pose and becomes unlinked (no pool: anchor_max = 0)
+__device__ __forceinline__ void edit_remove_group(double* P, int ldp, int Np, const xivo_layout& lay, const xivo_group_in* groups,
+                                                  PoolAnchor* anchors, int anchor_max, int g, int tid) {
+  for (int t = tid; t < anchor_max; t += 256) {
+    PoolAnchor& A = anchors[t];
+    if (A.slot == g) { A.g = groups[g]; A.slot = -1; }
+  }
+  edit_zero_rc(P, ldp, Np, lay.group_begin + 6 * g, 6, tid);
+}
+// XIVO_EDIT_ADD_GROUP_ANCHOR: AddGroupToState (src/estimator.cpp:801-816) of anchor A's group into slot g, with the anchor's pose
+__device__ __forceinline__ void edit_add_group_anchor(double* P, int ldp, int Np, const xivo_layout& lay, xivo_group_in* groups,
+                                                      PoolAnchor& A, int g, int tid) {
+  if (tid < 9) groups[g].Rsb[tid] = A.g.Rsb[tid];
+  else if (tid < 12) groups[g].Tsb[tid - 9] = A.g.Tsb[tid - 9];
+  const int off = lay.group_begin + 6 * g;
+  edit_copy_rc(P, ldp, Np, off, 0, 3, tid);       // Index::Wsb
+  edit_copy_rc(P, ldp, Np, off + 3, 3, 3, tid);   // Index::Tsb
+  if (tid == 0) A.slot = g;
+  __syncthreads();
+}
+// XIVO_EDIT_ADMIT_POOL: as XIVO_EDIT_ADD_FEATURE with (x, xp, P) taken from pool entry e, whose anchor is linked; list position
+// j, feature slot sind
+__device__ __forceinline__ void edit_admit_pool(double* P, int ldp, int Np, const xivo_layout& lay, xivo_feat_in* feats,
+                                                xivo_subfilter_feat& e, const PoolAnchor* anchors, int j, int sind, int tid) {
+  const int slot = anchors[e.ref_sind].slot;
+  const double pv = tid < 9 ? e.P[tid] : 0.0;
+  if (tid == 0) {
+    xivo_feat_in& f = feats[j];
+    f.x[0] = e.x[0]; f.x[1] = e.x[1]; f.x[2] = e.x[2];
+    f.xp[0] = e.xp[0]; f.xp[1] = e.xp[1];
+    f.sind = sind; f.ref_sind = slot;
+  }
+  const int off = lay.feature_begin + 3 * sind;
+  edit_zero_rc(P, ldp, Np, off, 3, tid);
+  if (tid < 9) P[(off + tid % 3) + (long)(off + tid / 3) * ldp] = pv;
+  if (tid == 0) e.ref_sind = -1;
   __syncthreads();
 }
 

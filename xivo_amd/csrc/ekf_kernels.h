@@ -149,6 +149,29 @@ struct LifeArgs {
 int launch_life_begin(const LifeArgs& a, int batch, hipStream_t s);
 int launch_life_end(const LifeArgs& a, int batch, hipStream_t s);
 
+// ================================================================ pool_lifecycle_kernels.hip: device pool life cycle (capi_pool_lifecycle.hip)
+
+// one frame of every filter [0, batch) in the "subfilter" mode. life: P, the scene, the in-state book, the tracks, the mask and
+// the status as the immediate life cycle's kernels take them (life.stats and its admission options are not read). The pool
+// book: ent_id / ent_born [batch][pool_max], anc_used / anc_life [batch][anchor_max]. Between the kernels of a frame:
+// slot_track [batch][slot_ld] and ent_track [batch][pool_max] (the track that feeds a slot / an entry, -1: none), the step's
+// xp in, order / n / live out. pool_max <= XIVO_POOL_MAX_ENTRIES, anchor_max <= XIVO_POOL_LIFE_MAX_ANCHORS and LifeArgs' limits
+// (the host checks all before a launch).
+struct PoolLifeArgs {
+  LifeArgs life;
+  xivo_subfilter_feat* pool; PoolAnchor* anchors; int pool_max, anchor_max;
+  long long* ent_id; int* ent_born; int* anc_used; int* anc_life; xivo_pool_life_stats* stats;
+  int* slot_track; int* ent_track;
+  double* xp; const int* order; const int* n; const unsigned char* live;
+  int frame;   // the frame counter (vision_counter)
+  // pool_life_end only: EnforceMaxGroupLifetime's bound, Feature::Initialize of a new entry
+  int max_group_lifetime; double initial_z, std_xyz[3]; const double* init_z;   // init_z non-null: z0 is the resident init_z
+  xivo_cam cam; const xivo_calib_in* calib; int cam_dim;
+};
+int launch_pool_life_begin(const PoolLifeArgs& a, int batch, hipStream_t s);
+int launch_pool_life_admit(const PoolLifeArgs& a, int batch, hipStream_t s);
+int launch_pool_life_end(const PoolLifeArgs& a, int batch, hipStream_t s);
+
 // ================================================================ pcw_kernels.hip: the point-cloud world's track producer (capi_pcw.hip)
 
 // one frame of the worlds of filters [0, batch): Xs [batch][npts][3], ids [batch][npts] (-1: no track), next_id [batch] and the

@@ -14,11 +14,12 @@
 // op lists - up to log z, where libm and the device library may differ in the last place. Nothing crosses workgroups: no
 // atomics on global memory, the counters and the book belong to the filter's own workgroup (LDS atomics only).
 // The frame's tracks are read in one of two forms (LifeArgs, ekf_kernels.h): packed behind offsets as the host uploads them, or
-// one row per filter with a count as pcw_tracks_kernel (pcw_kernels.hip) leaves them; life_track_begin / life_track_count are
-// the only place that tells them apart.
+// one row per filter with a count as pcw_tracks_kernel (pcw_kernels.hip) leaves them; life_track_begin / life_track_count
+// (lifecycle_tracks_device.h) are the only place that tells them apart.
 #include "edit_device.h"
 #include "ekf_kernels.h"
 #include "lifecycle_device.h"
+#include "lifecycle_tracks_device.h"
 
 namespace xivo_hip {
 
@@ -37,12 +38,6 @@ struct LifeLds {
   int rm_feat[kSlots], rm_group[kSlots], free_slots[kSlots], pick[kSlots];
   int n_rm_feat, n_rm_group, g_new, n_free, open, n_cand;
 };
-
-// where filter b's tracks start and how many there are, in either form of the track block (ekf_kernels.h)
-__device__ __forceinline__ int life_track_begin(const LifeArgs& a, int b) { return a.cnt ? b * a.track_ld : a.off[b]; }
-__device__ __forceinline__ int life_track_count(const LifeArgs& a, int b) {
-  return min(a.cnt ? a.cnt[b] : a.off[b + 1] - a.off[b], kTracks);
-}
 
 __device__ __forceinline__ void life_load(const LifeArgs& a, LifeLds& s, int b, int n, int tid) {
   const int F = a.F, G = a.lay.n_groups;

@@ -15,6 +15,7 @@
 #include "ekf_kernels.h"
 #include "camera_device.h"
 #include "geometry_device.h"
+#include "pool_device.h"
 #include "triangulate_device.h"
 
 namespace xivo_hip {
@@ -135,12 +136,7 @@ __global__ void subfilter_kernel(xivo_subfilter_feat* feats, int n, const xivo_p
 __global__ void pool_anchor_kernel(PoolAnchor* anchors, int anchor_max, const xivo_pose_in* poses, const int* slot, int nb) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= nb || slot[b] < 0) return;
-  PoolAnchor& A = anchors[(long)b * anchor_max + slot[b]];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) A.g.Rsb[i] = poses[b].Rsb[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) A.g.Tsb[i] = poses[b].Tsb[i];
-  A.slot = -1;
+  pool_create_anchor(anchors[(long)b * anchor_max + slot[b]], poses[b]);
 }
 // Feature::Initialize (feature.cpp:144-160): one thread per new track; init_z (non-null: XIVO_POOL_ADD_ADAPTIVE_Z): z0 is the
 // filter's resident init_z (AdaptInitialDepth's init_z_)
@@ -150,19 +146,7 @@ __global__ void pool_add_kernel(xivo_subfilter_feat* pool, int pool_max, const x
   if (t >= n) return;
   const xivo_pool_new& r = recs[t];
   const xivo_cam cam = filter_cam(cam_ctx, calib, cam_dim, r.b);
-  xivo_subfilter_feat& f = pool[(long)r.b * pool_max + r.entry];
-  double xc[2];
-  camera_unproject(cam, r.xp[0], r.xp[1], xc);
-  f.x[0] = xc[0]; f.x[1] = xc[1];
-  const double z0 = init_z ? init_z[r.b] : r.z0;
-  f.x[2] = invdepth ? 1.0 / z0 : log(z0);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) f.P[i] = 0.0;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) f.P[4 * i] = r.std_xyz[i] * r.std_xyz[i];   // P_ = diag(std); P_ *= P_
-  f.xp[0] = r.xp[0]; f.xp[1] = r.xp[1];
-  f.outlier_counter = 0.0; f.score = 0.0;
-  f.ref_sind = r.anchor; f.status = XIVO_FEAT_INITIALIZING; f.init_counter = 0; f.candidate = 0;
+  pool_init_entry(pool[(long)r.b * pool_max + r.entry], cam, r.xp, init_z ? init_z[r.b] : r.z0, r.std_xyz, r.anchor, invdepth);
 }
 // The out-of-state branch of ProcessTracks (manager.cpp:171-250) and the candidate order, one workgroup per filter: its threads
 // take the entries (one thread per entry for pool_max <= 256), then sort the keys (rank, P(2,2), entry) in LDS by a bitonic

@@ -123,12 +123,7 @@ __global__ __launch_bounds__(256) void edit_batch_kernel(EditArgs a) {
         break;
       }
       case XIVO_EDIT_REMOVE_GROUP:
-        // an anchor linked to the slot keeps the group's last pose and becomes unlinked (no pool: anchor_max = 0)
-        for (int t = tid; t < a.anchor_max; t += 256) {
-          PoolAnchor& A = a.anchors[(long)filt * a.anchor_max + t];
-          if (A.slot == op.i0) { A.g = groups[op.i0]; A.slot = -1; }
-        }
-        edit_zero_rc(P, a.ldp, a.Np, a.lay.group_begin + 6 * op.i0, 6, tid);
+        edit_remove_group(P, a.ldp, a.Np, a.lay, groups, a.anchors + (long)filt * a.anchor_max, a.anchor_max, op.i0, tid);
         break;
       case XIVO_EDIT_ADD_FEATURE: {
         if (tid == 0) {
@@ -157,35 +152,13 @@ __global__ __launch_bounds__(256) void edit_batch_kernel(EditArgs a) {
         if (tid < 2) feats[op.i0].xp[tid] = op.v[tid];
         __syncthreads();
         break;
-      case XIVO_EDIT_ADD_GROUP_ANCHOR: {
-        PoolAnchor& A = a.anchors[(long)filt * a.anchor_max + op.i1];
-        if (tid < 9) groups[op.i0].Rsb[tid] = A.g.Rsb[tid];
-        else if (tid < 12) groups[op.i0].Tsb[tid - 9] = A.g.Tsb[tid - 9];
-        const int off = a.lay.group_begin + 6 * op.i0;
-        edit_copy_rc(P, a.ldp, a.Np, off, 0, 3, tid);       // Index::Wsb
-        edit_copy_rc(P, a.ldp, a.Np, off + 3, 3, 3, tid);   // Index::Tsb
-        if (tid == 0) A.slot = op.i0;
-        __syncthreads();
+      case XIVO_EDIT_ADD_GROUP_ANCHOR:
+        edit_add_group_anchor(P, a.ldp, a.Np, a.lay, groups, a.anchors[(long)filt * a.anchor_max + op.i1], op.i0, tid);
         break;
-      }
-      case XIVO_EDIT_ADMIT_POOL: {
-        // as XIVO_EDIT_ADD_FEATURE with (x, xp, P) taken from the pool entry; the host checked that its anchor is linked
-        xivo_subfilter_feat& e = a.pool[(long)filt * a.pool_max + op.i2];
-        const int slot = a.anchors[(long)filt * a.anchor_max + e.ref_sind].slot;
-        const double pv = tid < 9 ? e.P[tid] : 0.0;
-        if (tid == 0) {
-          xivo_feat_in& f = feats[op.i0];
-          f.x[0] = e.x[0]; f.x[1] = e.x[1]; f.x[2] = e.x[2];
-          f.xp[0] = e.xp[0]; f.xp[1] = e.xp[1];
-          f.sind = op.i1; f.ref_sind = slot;
-        }
-        const int off = a.lay.feature_begin + 3 * op.i1;
-        edit_zero_rc(P, a.ldp, a.Np, off, 3, tid);
-        if (tid < 9) P[(off + tid % 3) + (long)(off + tid / 3) * a.ldp] = pv;
-        if (tid == 0) e.ref_sind = -1;
-        __syncthreads();
+      case XIVO_EDIT_ADMIT_POOL:   // (the host checked that the entry's anchor is linked)
+        edit_admit_pool(P, a.ldp, a.Np, a.lay, feats, a.pool[(long)filt * a.pool_max + op.i2], a.anchors + (long)filt * a.anchor_max,
+                        op.i0, op.i1, tid);
         break;
-      }
       default: break;
     }
   }

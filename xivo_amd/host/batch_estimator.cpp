@@ -144,11 +144,12 @@ void BatchEstimator::RunUpdate() {
   } else {
     Check(xivo_hip_filter_update(ctx_, B_, R, cfg_.MH_thresh, cfg_.MH_adjust_factor, cfg_.min_inliers, cfg_.use_MH_gating), "filter_update");
   }
-  if (!device_life_ || want_mask_) Check(xivo_hip_get_gate(ctx_, B_, F, mask_.data(), nullptr), "get_gate");
+  const bool on_device = device_life_ || device_pool_life_;   // the life cycle reads the mask and the status where they are
+  if (!on_device || want_mask_) Check(xivo_hip_get_gate(ctx_, B_, F, mask_.data(), nullptr), "get_gate");
   // a filter whose S was not positive definite keeps its prior P and absorbs nothing (the device skips both); it is
   // counted and reported here - the reference's pivoted LDL^T cannot fail, so there is no reference behaviour to mirror
-  // (device life cycle: xivo_hip_life_end counts it, nothing is downloaded)
-  if (!device_life_) {
+  // (device life cycles: xivo_hip_life_end / xivo_hip_pool_life_end count it, nothing is downloaded)
+  if (!on_device) {
     status_.resize(B_);
     const int st = xivo_hip_get_status(ctx_, 0, B_, status_.data());
     if (st == XIVO_HIP_ERR_NOT_SPD) { for (int b = 0; b < B_; ++b) n_not_spd_ += status_[b] != 0; }
@@ -206,6 +207,18 @@ void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_
   double t0 = now_s();
   const int F = cfg_.n_features;
   PropagateToFrame(t, t0);
+  if (device_pool_life_) {
+    // the sub-filter life cycle on the device: the tracks go down as they came in, nothing comes back
+    host_s_ += now_s() - t0;
+    want_mask_ = mask_out != nullptr;
+    ++vision_counter_;
+    Check(xivo_hip_pool_life_begin(ctx_, B_, F, off, reinterpret_cast<const long long*>(ids), meas,
+                                   vision_counter_ >= sc_.strict_criteria_timesteps ? 1 : 0), "pool_life_begin");
+    RunUpdate();
+    Check(xivo_hip_pool_life_end(ctx_, B_), "pool_life_end");
+    if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
+    return;
+  }
   if (subfilter_) {
     host_s_ += now_s() - t0;
     VisualSubfilter(off, ids, meas);
@@ -326,6 +339,7 @@ void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_
 
 void BatchEstimator::EnableSubfilter(const SubfilterConfig& sc) {
   if (device_life_) throw std::runtime_error("the device life cycle runs the immediate mode only");
+  if (device_pool_life_) throw std::runtime_error("EnableSubfilter would empty the pool under the device pool life cycle");
   sc_ = sc;
   Check(xivo_hip_pool_config(ctx_, sc.pool_max, sc.anchor_max, &sc.opts, sc.remove_outlier_counter), "pool_config");
   pools_.assign(B_, PoolBook{});
@@ -369,6 +383,26 @@ void BatchEstimator::EnableDeviceLifecycle(int tracks_max) {
   device_life_ = true;
 }
 
+void BatchEstimator::EnableDevicePoolLifecycle(int tracks_max) {
+  if (!subfilter_) throw std::runtime_error("the device pool life cycle needs EnableSubfilter first");
+  if (device_life_) throw std::runtime_error("the device pool life cycle excludes the immediate device life cycle");
+  if (device_pool_life_ || vision_counter_ > 0) throw std::runtime_error("the device pool life cycle starts on an empty pool, once");
+  const double fx = cfg_.cam.fx, fy = cfg_.cam.fy;
+  const double fl = 0.5 * std::sqrt(fx * fx + fy * fy);   // Camera::GetFocalLength() (src/camera_manager.cpp:56)
+  xivo_pool_life_opts o;
+  std::memset(&o, 0, sizeof(o));
+  o.struct_size = (int)sizeof(o); o.tracks_max = tracks_max; o.max_group_lifetime = sc_.max_group_lifetime;
+  o.adaptive_z = dc_.adaptive ? 1 : 0; o.initial_z = sc_.initial_z;
+  if (dc_.triangulate) {  // a new track is never triangulated yet: the badtri stds (manager.cpp:585-586)
+    o.std_xyz[0] = dc_.std_badtri[0] / fl; o.std_xyz[1] = dc_.std_badtri[1] / fl; o.std_xyz[2] = dc_.std_badtri[2];
+  } else {
+    o.std_xyz[0] = cfg_.initial_std_x / fl; o.std_xyz[1] = cfg_.initial_std_y / fl; o.std_xyz[2] = cfg_.initial_std_z;
+  }
+  if (tracks_max <= 0) throw std::runtime_error("tracks_max must be positive");
+  Check(xivo_hip_pool_life_config(ctx_, &o), "pool_life_config");
+  device_pool_life_ = true;
+}
+
 void BatchEstimator::EnableDeviceWorld(int npts, const xivo_pcw_opts& cam, const double* Xs) {
   if (!device_life_) throw std::runtime_error("the device world needs the device life cycle (EnableDeviceLifecycle)");
   xivo_pcw_opts o = cam;
@@ -398,7 +432,11 @@ void BatchEstimator::ReadBook(int b) {
   const int F = cfg_.n_features;
   Book& bk = books_[b];
   std::vector<long long> fid(F);
-  Check(xivo_hip_life_get_book(ctx_, b, 1, fid.data(), bk.feat_ref.data(), bk.group_refs.data()), "life_get_book");
+  if (device_pool_life_)
+    Check(xivo_hip_pool_life_get_book(ctx_, b, 1, fid.data(), bk.feat_ref.data(), bk.group_refs.data(), nullptr, nullptr, nullptr,
+                                      nullptr), "pool_life_get_book");
+  else
+    Check(xivo_hip_life_get_book(ctx_, b, 1, fid.data(), bk.feat_ref.data(), bk.group_refs.data()), "life_get_book");
   bk.id2slot.clear();
   for (int j = 0; j < F; ++j) { bk.feat_id[j] = fid[j]; if (fid[j] >= 0) bk.id2slot[fid[j]] = j; }
 }
@@ -414,7 +452,20 @@ long BatchEstimator::LifeCount(int which) const {
   return n;
 }
 
+long BatchEstimator::PoolLifeCount(int which) const {
+  std::vector<xivo_pool_life_stats> st(B_);
+  if (xivo_hip_pool_life_stats(ctx_, 0, B_, st.data()) != XIVO_HIP_OK) throw std::runtime_error("pool_life_stats");
+  long n = 0;
+  for (const auto& s : st) {
+    const long long v[12] = {s.updates, s.rejected, s.dropped, s.admitted, s.groups_added, s.not_spd, s.pool_added,
+                             s.pool_dropped, s.pool_outliers, s.anchors_created, s.anchors_freed, s.admit_steps};
+    n += (long)v[which];
+  }
+  return n;
+}
+
 void BatchEstimator::EnableDepthInit(const DepthInitConfig& dc) {
+  if (device_pool_life_) throw std::runtime_error("EnableDepthInit comes before EnableDevicePoolLifecycle");
   if (!subfilter_) throw std::runtime_error("EnableDepthInit needs EnableSubfilter first");
   Check(xivo_hip_pool_triangulation(ctx_, dc.triangulate ? &dc.tri : nullptr), "pool_triangulation");
   if (dc.adaptive) {
@@ -678,7 +729,8 @@ int xivo_batch_init_z(void* h, double* out) {
 }
 void xivo_batch_pool_stats(void* h, long* admitted, long* dropped) {
   auto* e = static_cast<xivo::hip::BatchEstimator*>(h);
-  *admitted = e->n_admitted(); *dropped = e->n_pool_dropped();
+  try { *admitted = e->n_admitted(); *dropped = e->n_pool_dropped(); }   // (device pool life cycle: read from the device)
+  catch (const std::exception&) { *admitted = -1; *dropped = -1; }
 }
 int xivo_batch_innov_log(void* h, int T_max) {
   if (!h) return -1;
@@ -687,6 +739,10 @@ int xivo_batch_innov_log(void* h, int T_max) {
 int xivo_batch_enable_device_lifecycle(void* h, int tracks_max) {
   if (!h) return -1;
   try { static_cast<xivo::hip::BatchEstimator*>(h)->EnableDeviceLifecycle(tracks_max); return 0; } catch (const std::exception&) { return -1; }
+}
+int xivo_batch_enable_device_pool_lifecycle(void* h, int tracks_max) {
+  if (!h) return -1;
+  try { static_cast<xivo::hip::BatchEstimator*>(h)->EnableDevicePoolLifecycle(tracks_max); return 0; } catch (const std::exception&) { return -1; }
 }
 long xivo_batch_not_spd(void* h) {
   try { return static_cast<xivo::hip::BatchEstimator*>(h)->n_not_spd(); } catch (const std::exception&) { return -1; }

@@ -65,9 +65,9 @@ class BatchEstimator {
   int B() const { return B_; }
   const BatchConfig& cfg() const { return cfg_; }
   xivo_hip_ctx* ctx() { return ctx_; }
-  long n_updates() const { return n_updates_ + (device_life_ ? LifeCount(0) : 0); }
-  long n_not_spd() const { return n_not_spd_ + (device_life_ ? LifeCount(5) : 0); }   // updates skipped because S was not positive definite
-  long n_rejected() const { return n_rejected_ + (device_life_ ? LifeCount(1) : 0); }
+  long n_updates() const { return n_updates_ + DeviceCount(0); }
+  long n_not_spd() const { return n_not_spd_ + DeviceCount(5); }   // updates skipped because S was not positive definite
+  long n_rejected() const { return n_rejected_ + DeviceCount(1); }
   double host_seconds() const { return host_s_; }   // time spent in the host-side life cycle (not in C-ABI calls)
 
   // the reference's life cycle of a new track on the device-resident feature pool (xivo_hip_pool_*), as
@@ -92,12 +92,19 @@ class BatchEstimator {
   };
   void EnableDepthInit(const DepthInitConfig& dc);   // after EnableSubfilter, before the first camera frame
   const std::vector<double>& init_z() const { return init_z_; }   // AdaptInitialDepth's init_z after the last frame
-  long n_admitted() const { return n_admitted_; }
+  long n_admitted() const { return n_admitted_ + (device_pool_life_ ? DeviceCount(3) : 0); }
   // the innovation log of the estimator's context (xivo_hip_innov_*): T_max frames, one record per camera frame between the
   // update and AbsorbError, stamped with the frame's time in ns; T_max = 0 releases the log and stops recording. The caller
   // reads it through ctx() (xivo_hip_innov_read / _stats).
   void EnableInnovationLog(int T_max);
-  long n_pool_dropped() const { return n_pool_dropped_; }   // new tracks that found no free pool entry or anchor
+  long n_pool_dropped() const { return n_pool_dropped_ + (device_pool_life_ ? DeviceCount(7) : 0); }   // new tracks that found no free pool entry or anchor
+  // the sub-filter life cycle's decisions on the device (xivo_hip_pool_life_*): after EnableSubfilter (and EnableDepthInit, whose
+  // stds and adaptive depth it takes), before the first camera frame. Both books move to the context; VisualMeasPointCloud
+  // hands the frame's tracks down (at most tracks_max per filter) and makes no get_gate / get_status call unless mask_out is
+  // given; book(b) and the counters then read the device, init_z() stays as configured (xivo_hip_pool_get_init_z reads the
+  // resident one). Throws if EnableSubfilter has not run or the immediate device life cycle is on.
+  void EnableDevicePoolLifecycle(int tracks_max);
+  bool device_pool_lifecycle() const { return device_pool_life_; }
   // the "immediate" life cycle on the device (xivo_hip_life_*): the slot book moves to the context, VisualMeasPointCloud hands
   // the frame's tracks down (at most tracks_max per filter) and makes no get_gate / get_status call unless mask_out is given;
   // book(b), n_updates(), n_rejected() and n_not_spd() then read the device. The book kept so far is adopted
@@ -122,7 +129,7 @@ class BatchEstimator {
     std::vector<int> feat_ref;
     std::unordered_map<int64_t, int> id2slot;
   };
-  const Book& book(int b) { if (device_life_) ReadBook(b); return books_[b]; }
+  const Book& book(int b) { if (device_life_ || device_pool_life_) ReadBook(b); return books_[b]; }
 
  private:
   void Check(int rc, const char* what);
@@ -133,7 +140,9 @@ class BatchEstimator {
   void VisualSubfilter(const int* off, const int64_t* ids, const double* meas);
   void ReadBook(int b);                 // device life cycle: books_[b] <- xivo_hip_life_get_book
   long LifeCount(int which) const;      // device life cycle: one of xivo_life_stats' counters summed over the filters
-  bool device_life_ = false, want_mask_ = false, device_world_ = false;
+  long PoolLifeCount(int which) const;  // device pool life cycle: counter `which` of xivo_pool_life_stats summed over the filters
+  long DeviceCount(int which) const { return device_life_ ? LifeCount(which) : (device_pool_life_ ? PoolLifeCount(which) : 0); }
+  bool device_life_ = false, want_mask_ = false, device_world_ = false, device_pool_life_ = false;
   unsigned long long world_frame_ = 0;
 
   struct PoolBook {                                 // one filter's feature pool: tracks per entry, anchors and their links

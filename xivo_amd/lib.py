@@ -123,6 +123,14 @@ life_opts_dtype = np.dtype([("tracks_max", "i4"), ("min_new_features", "i4"), ("
 life_stats_dtype = np.dtype([("updates", "i8"), ("rejected", "i8"), ("dropped", "i8"), ("admitted", "i8"), ("groups_added", "i8"),
                              ("not_spd", "i8")])
 assert life_opts_dtype.itemsize == 48 and life_stats_dtype.itemsize == 48
+# device pool life cycle (include/xivo_hip.h): xivo_pool_life_opts, xivo_pool_life_stats
+pool_life_opts_dtype = np.dtype([("struct_size", "i4"), ("tracks_max", "i4"), ("max_group_lifetime", "i4"), ("adaptive_z", "i4"),
+                                 ("initial_z", "f8"), ("std_xyz", "f8", 3)])
+pool_life_stats_dtype = np.dtype([(k, "i8") for k in ("updates", "rejected", "dropped", "admitted", "groups_added", "not_spd",
+                                                       "pool_added", "pool_dropped", "pool_outliers", "anchors_created",
+                                                       "anchors_freed", "admit_steps")])
+assert pool_life_opts_dtype.itemsize == 48 and pool_life_stats_dtype.itemsize == 96
+POOL_LIFE_MAX_ANCHORS = 256
 # point-cloud world (include/xivo_hip.h): xivo_pcw_opts
 pcw_opts_dtype = np.dtype([("struct_size", "i4"), ("npts", "i4"), ("fx", "f8"), ("fy", "f8"), ("cx", "f8"), ("cy", "f8"),
                            ("imw", "f8"), ("imh", "f8")])
@@ -195,6 +203,7 @@ _SIGS = {
     "xivo_hip_pool_adapt_depth_config": [C.c_void_p, C.c_void_p],
     "xivo_hip_pool_adapt_depth": [C.c_void_p, C.c_int, C.c_void_p],
     "xivo_hip_pool_add_ex": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint],
+    "xivo_hip_pool_get_init_z": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_edit_batch": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_set_pixels": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_get_scene": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -252,6 +261,12 @@ _SIGS = {
     "xivo_hip_life_end": [C.c_void_p, C.c_int],
     "xivo_hip_life_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_life_begin_tracks": [C.c_void_p, C.c_int, C.c_int],
+    "xivo_hip_pool_life_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_pool_life_set_book": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_pool_life_get_book": [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7,
+    "xivo_hip_pool_life_begin": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+    "xivo_hip_pool_life_end": [C.c_void_p, C.c_int],
+    "xivo_hip_pool_life_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_pcw_config": [C.c_void_p, C.c_void_p],
     "xivo_hip_pcw_set_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_pcw_get_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
@@ -758,6 +773,13 @@ class Context:
         self._check(self.lib.xivo_hip_pool_adapt_depth(self.h, B, _ptr(z)))
         return z
 
+    def pool_get_init_z(self, b0=0, nb=None):
+        """-> [nb] the resident init_z as it is (no AdaptInitialDepth step); one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        z = np.zeros(nb)
+        self._check(self.lib.xivo_hip_pool_get_init_z(self.h, int(b0), nb, _ptr(z)))
+        return z
+
     def pool_add_ex(self, recs, options=0):
         """recs: array of pool_new_dtype; options POOL_ADD_ADAPTIVE_Z: z0 from the filter's resident init_z"""
         recs = np.ascontiguousarray(recs, dtype=pool_new_dtype)
@@ -1118,6 +1140,58 @@ class Context:
         nb = self.batch - b0 if nb is None else int(nb)
         out = np.zeros(nb, dtype=life_stats_dtype)
         self._check(self.lib.xivo_hip_life_stats(self.h, int(b0), nb, _ptr(out)))
+        return out
+
+    # ---- device pool life cycle (xivo_hip_pool_life_*)
+    def pool_life_config(self, tracks_max, max_group_lifetime=1, initial_z=2.5, std_xyz=(1.0, 1.0, 1.0), adaptive_z=False):
+        """the device-resident books, the step's device buffers and the track staging of the "subfilter" life cycle, after
+        pool_config on an empty pool: at most tracks_max tracks per filter and frame (<= LIFE_MAX_TRACKS); initial_z / std_xyz:
+        a new entry's depth and stds; adaptive_z: the depth is the resident init_z (after pool_adapt_depth_config);
+        tracks_max = 0 releases it and hands the pool back to the host calls"""
+        o = np.zeros(1, dtype=pool_life_opts_dtype)
+        o["struct_size"], o["tracks_max"], o["max_group_lifetime"] = pool_life_opts_dtype.itemsize, int(tracks_max), int(max_group_lifetime)
+        o["adaptive_z"], o["initial_z"], o["std_xyz"] = int(bool(adaptive_z)), float(initial_z), np.asarray(std_xyz, dtype=np.float64)
+        self._check(self.lib.xivo_hip_pool_life_config(self.h, _ptr(o)))
+
+    def pool_life_set_book(self, feat_id, b0=0):
+        """feat_id [nb, F]: the track ids of the scene placed with set_scene (-1: absent entry)"""
+        feat_id = np.ascontiguousarray(feat_id, dtype=np.int64)
+        self._check(self.lib.xivo_hip_pool_life_set_book(self.h, int(b0), feat_id.shape[0], _ptr(feat_id)))
+
+    def pool_life_get_book(self, b0=0, nb=None):
+        """-> dict(feat_id [nb, F] int64, feat_ref [nb, F], group_refs [nb, n_groups], ent_id [nb, pool_max] int64, ent_born
+        [nb, pool_max], anc_used / anc_life [nb, anchor_max]); one synchronising read. The entries' anchors and the anchors'
+        links are the resident ones: pool_get."""
+        nb = self.batch - b0 if nb is None else int(nb)
+        out = dict(feat_id=np.full((nb, self.F), -1, dtype=np.int64), feat_ref=np.full((nb, self.F), -1, dtype=np.int32),
+                   group_refs=np.full((nb, self.layout.n_groups), -1, dtype=np.int32),
+                   ent_id=np.full((nb, self.pool_max), -1, dtype=np.int64), ent_born=np.zeros((nb, self.pool_max), dtype=np.int32),
+                   anc_used=np.zeros((nb, self.anchor_max), dtype=np.int32), anc_life=np.zeros((nb, self.anchor_max), dtype=np.int32))
+        self._check(self.lib.xivo_hip_pool_life_get_book(self.h, int(b0), nb, *[_ptr(out[k]) for k in (
+            "feat_id", "feat_ref", "group_refs", "ent_id", "ent_born", "anc_used", "anc_life")]))
+        return out
+
+    def pool_life_begin(self, F, off, ids, meas, strict=False, B=None):
+        """before the update (asynchronous): the frame's tracks as off [B + 1] int32, ids [n] int64, meas [n, 3] (u, v, depth);
+        begin kernel, pool step, admit kernel"""
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        meas = np.ascontiguousarray(meas, dtype=np.float64)
+        B = off.size - 1 if B is None else int(B)
+        if off.size != B + 1 or ids.size != int(off[-1]) or meas.size != 3 * ids.size:
+            raise ValueError("off [B + 1], ids [off[B]], meas [off[B], 3]")
+        self._check(self.lib.xivo_hip_pool_life_begin(self.h, B, int(F), _ptr(off), _ptr(ids), _ptr(meas), int(bool(strict))))
+        self.F = int(F)
+
+    def pool_life_end(self, B=None):
+        """after the update and absorb_error (asynchronous)"""
+        self._check(self.lib.xivo_hip_pool_life_end(self.h, self.batch if B is None else int(B)))
+
+    def pool_life_stats(self, b0=0, nb=None):
+        """-> [nb] pool_life_stats_dtype: the per-filter counters; one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        out = np.zeros(nb, dtype=pool_life_stats_dtype)
+        self._check(self.lib.xivo_hip_pool_life_stats(self.h, int(b0), nb, _ptr(out)))
         return out
 
     def propagate_cov(self, Phi, Pmm, b0=0):

@@ -164,6 +164,11 @@ class SequenceConfig:
         # during a frame). tracks_max: the most tracks one filter may bring in a frame on the device path.
         self.lifecycle = "host"
         self.tracks_max = 1024
+        # who runs the per-frame life cycle of the "subfilter" mode: "host" (SequenceRunner._frame_subfilter decides filter by
+        # filter around pool_step and sends op lists, pixels, anchor slots and new-track records) or "device"
+        # (xivo_hip_pool_life_begin / _end: both books are device resident, nothing is downloaded during a frame; tracks_max as
+        # above). A name of its own: lifecycle="device" stays the "immediate" mode's switch.
+        self.pool_lifecycle = "host"
         # where a frame's tracks come from: "host" (the simulator's arrays, uploaded) or "device" (xivo_hip_pcw_tracks on the
         # resident worlds of npts points each; needs lifecycle = "device" and npts <= tracks_max)
         self.track_source = "host"
@@ -333,6 +338,8 @@ class HipBackend:
             self.enable_pool()
         if cfg.lifecycle == "device":
             self.enable_device_lifecycle()
+        if cfg.pool_lifecycle == "device":
+            self.enable_device_pool_lifecycle()
         if cfg.track_source == "device":
             self.enable_device_world()
 
@@ -344,6 +351,37 @@ class HipBackend:
         std = np.array([c.initial_std_x / fl, c.initial_std_y / fl, c.initial_std_z])
         self.ctx.life_config(c.tracks_max, min_depth=c.min_depth, max_depth=c.max_depth, min_new_features=c.min_new_features,
                              var_xyz=std * std)
+
+    def new_track_std(self):
+        """the stds a new pool entry starts with: a new track is never triangulated yet, so with triangulation on they are the
+        badtri stds (src/manager.cpp:585-586); pixels are divided by the focal length (src/estimator.cpp:351-352)"""
+        c = self.cfg
+        fl = c.focal_length()
+        if c.triangulate_pre_subfilter:
+            return [c.initial_std_x_badtri / fl, c.initial_std_y_badtri / fl, c.initial_std_z_badtri]
+        return [c.initial_std_x / fl, c.initial_std_y / fl, c.initial_std_z]
+
+    def enable_device_pool_lifecycle(self):
+        """allocate the device-resident books and track staging of the "subfilter" life cycle (xivo_hip_pool_life_config), after
+        enable_pool and on an empty pool"""
+        c = self.cfg
+        if not self.pool_on:
+            raise ValueError("enable_device_pool_lifecycle needs the feature pool (feature_init='subfilter')")
+        self.ctx.pool_life_config(c.tracks_max, max_group_lifetime=c.max_group_lifetime, initial_z=c.initial_z,
+                                  std_xyz=self.new_track_std(), adaptive_z=c.adaptive_initial_depth)
+
+    def pool_life_begin(self, off, ids, meas, strict):
+        self.ctx.pool_life_begin(self.F, off, ids, meas, strict, B=self.B)
+
+    def pool_life_end(self):
+        self.ctx.pool_life_end(self.B)
+
+    def pool_life_book(self):
+        """the in-state and the pool book read from the device (Context.pool_life_get_book)"""
+        return self.ctx.pool_life_get_book(0, self.B)
+
+    def pool_life_stats(self):
+        return self.ctx.pool_life_stats(0, self.B)
 
     def enable_device_world(self):
         """allocate the resident worlds of the device track source (xivo_hip_pcw_config): cfg.npts points per filter, the
@@ -547,6 +585,16 @@ def check_lifecycle(cfg):
         raise ValueError("lifecycle must be 'host' or 'device'")
     if cfg.lifecycle == "device" and cfg.feature_init != "immediate":
         raise ValueError("lifecycle='device' runs the 'immediate' life cycle only (feature_init=%r)" % (cfg.feature_init,))
+    plc = getattr(cfg, "pool_lifecycle", "host")
+    if plc not in ("host", "device"):
+        raise ValueError("pool_lifecycle must be 'host' or 'device'")
+    if plc == "device":
+        if cfg.feature_init != "subfilter":
+            raise ValueError("pool_lifecycle='device' runs the 'subfilter' life cycle only (feature_init=%r)" % (cfg.feature_init,))
+        if cfg.lifecycle == "device":
+            raise ValueError("pool_lifecycle='device' and lifecycle='device' exclude each other")
+        if not 0 < cfg.tracks_max <= L.LIFE_MAX_TRACKS:
+            raise ValueError("pool_lifecycle='device' needs 0 < tracks_max <= %d" % L.LIFE_MAX_TRACKS)
     src = getattr(cfg, "track_source", "host")
     if src not in ("host", "device"):
         raise ValueError("track_source must be 'host' or 'device'")
@@ -573,13 +621,14 @@ class SequenceRunner:
         check_lifecycle(cfg)
         self.be, self.cfg, self.B = backend, cfg, B
         self.device_lifecycle = cfg.lifecycle == "device"
+        self.device_pool_lifecycle = cfg.pool_lifecycle == "device"
         self._books = [_Book(cfg.n_groups, cfg.n_features) for _ in range(B)]
         self._n_updates = 0
         self._n_rejected = 0
         self.want_mask = False       # device life cycle: download the inlier mask of every frame (frame() then returns it)
         self.pools = None            # [B] _PoolBook in the "subfilter" life cycle
         self.vision_counter = 0      # camera frames so far (Estimator::vision_counter_)
-        self.n_pool_dropped = 0      # new tracks dropped because the pool or the anchor table was full
+        self._n_pool_dropped = 0     # new tracks dropped because the pool or the anchor table was full
         self.admitted = []           # (frame, filter, track id, sub-filter steps taken) of every pool entry that entered the state
         self.init_z = None           # [B] AdaptInitialDepth's init_z after the last frame (adaptive_initial_depth)
         self.timers = None       # set to {} to accumulate wall seconds per phase (adds a device sync per phase)
@@ -589,9 +638,13 @@ class SequenceRunner:
     # on demand (one synchronising read each - not something to ask for every frame of a timed run)
     @property
     def books(self):
-        if not self.device_lifecycle:
+        if not self.device_lifecycle and not self.device_pool_lifecycle:
             return self._books
-        fid, fref, grefs = self.be.life_book()
+        if self.device_pool_lifecycle:
+            bk = self.be.pool_life_book()
+            fid, fref, grefs = bk["feat_id"], bk["feat_ref"], bk["group_refs"]
+        else:
+            fid, fref, grefs = self.be.life_book()
         out = []
         for b in range(self.B):
             bk = _Book(self.cfg.n_groups, self.cfg.n_features)
@@ -602,9 +655,16 @@ class SequenceRunner:
             out.append(bk)
         return out
 
+    def _device_count(self, name):
+        """a counter of the device life cycle in use summed over the filters, None with the host life cycle"""
+        if self.device_pool_lifecycle:
+            return int(self.be.pool_life_stats()[name].sum())
+        return int(self.be.life_stats()[name].sum()) if self.device_lifecycle else None
+
     @property
     def n_updates(self):
-        return int(self.be.life_stats()["updates"].sum()) if self.device_lifecycle else self._n_updates
+        n = self._device_count("updates")
+        return self._n_updates if n is None else n
 
     @n_updates.setter
     def n_updates(self, v):
@@ -612,11 +672,53 @@ class SequenceRunner:
 
     @property
     def n_rejected(self):
-        return int(self.be.life_stats()["rejected"].sum()) if self.device_lifecycle else self._n_rejected
+        n = self._device_count("rejected")
+        return self._n_rejected if n is None else n
 
     @n_rejected.setter
     def n_rejected(self, v):
         self._n_rejected = v
+
+    @property
+    def n_pool_dropped(self):
+        return int(self.be.pool_life_stats()["pool_dropped"].sum()) if self.device_pool_lifecycle else self._n_pool_dropped
+
+    @n_pool_dropped.setter
+    def n_pool_dropped(self, v):
+        self._n_pool_dropped = v
+
+    def _pack_tracks(self, tracks):
+        """the tracks of all filters in the off / ids / meas layout of xivo_batch_visual"""
+        off = np.zeros(self.B + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(t[0]) for t in tracks])
+        if off[-1] > 0:
+            ids = np.concatenate([np.asarray(t[0], dtype=np.int64).reshape(-1) for t in tracks])
+            meas = np.concatenate([np.asarray(t[1], dtype=np.float64).reshape(-1, 3) for t in tracks])
+        else:
+            ids, meas = np.zeros(0, dtype=np.int64), np.zeros((0, 3))
+        return off, ids, meas
+
+    def _frame_subfilter_device(self, imu, tracks):
+        """one camera frame of the "subfilter" life cycle with the decisions on the device: propagate -> pool_life_begin (begin
+        kernel, pool step, admit kernel) -> update -> pool_life_end (end kernel, AdaptInitialDepth). No per-filter work here
+        and nothing is downloaded (unless want_mask); `admitted` stays empty - the counters admitted / admit_steps of
+        pool_life_stats stand for it."""
+        import time
+        be = self.be
+        self.vision_counter += 1
+        t0 = time.perf_counter()
+        if imu is not None:
+            be.propagate(imu)
+        t0 = self._tick("propagate", t0) or t0
+        off, ids, meas = self._pack_tracks(tracks)
+        t0 = self._tick("host_pre", t0) or t0
+        be.pool_life_begin(off, ids, meas, self.vision_counter >= self.cfg.strict_criteria_timesteps)
+        t0 = self._tick("edit", t0) or t0
+        mask = be.update(download=self.want_mask)
+        t0 = self._tick("update", t0) or t0
+        be.pool_life_end()
+        self._tick("edit", t0)
+        return mask
 
     def _frame_device(self, imu, tracks):
         """one camera frame with the life cycle on the device: the tracks of all filters go down in the off / ids / meas layout
@@ -628,13 +730,7 @@ class SequenceRunner:
         if imu is not None:
             be.propagate(imu)
         t0 = self._tick("propagate", t0) or t0
-        off = np.zeros(self.B + 1, dtype=np.int32)
-        off[1:] = np.cumsum([len(t[0]) for t in tracks])
-        if off[-1] > 0:
-            ids = np.concatenate([np.asarray(t[0], dtype=np.int64).reshape(-1) for t in tracks])
-            meas = np.concatenate([np.asarray(t[1], dtype=np.float64).reshape(-1, 3) for t in tracks])
-        else:
-            ids, meas = np.zeros(0, dtype=np.int64), np.zeros((0, 3))
+        off, ids, meas = self._pack_tracks(tracks)
         t0 = self._tick("host_pre", t0) or t0
         be.life_begin(off, ids, meas)
         t0 = self._tick("edit", t0) or t0
@@ -688,6 +784,8 @@ class SequenceRunner:
     def frame(self, imu, tracks):
         """imu: [B x K] xivo_imu_in records or None; tracks: per filter (ids [n], xp_and_depths [n x 3])."""
         if self.cfg.feature_init == "subfilter":
+            if self.device_pool_lifecycle:
+                return self._frame_subfilter_device(imu, tracks)
             return self._frame_subfilter(imu, tracks)
         if self.cfg.feature_init != "immediate":
             raise ValueError("feature_init must be 'immediate' or 'subfilter'")
@@ -1105,8 +1203,8 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
             elif host.xivo_batch_visual(est.h, float(t), off.ctypes.data, ids.ctypes.data, meas.ctypes.data,
                                         mask.ctypes.data if mask is not None else None) != 0:
                 raise RuntimeError("VisualMeasPointCloud failed")
-            if est.device_lifecycle and timers is not None:
-                # the device life cycle only enqueues the frame: a timed run waits for it here, so that "frame" ends where the
+            if (est.device_lifecycle or est.device_pool_lifecycle) and timers is not None:
+                # a device life cycle only enqueues the frame: a timed run waits for it here, so that "frame" ends where the
                 # host life cycle's does (its last call synchronises); "frame_enqueue" is the host's share of it
                 tm["frame_enqueue"] = tm.get("frame_enqueue", 0.0) + time.perf_counter() - t1
                 est.sync()
