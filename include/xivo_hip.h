@@ -1083,6 +1083,65 @@ int xivo_hip_life_begin_tracks(xivo_hip_ctx* ctx, int B, int F);
  * read -1 / 0. Any may be NULL. Synchronises. */
 int xivo_hip_pcw_get_tracks(xivo_hip_ctx* ctx, int b0, int nb, int* cnt, long long* ids, double* meas);
 
+/* ---- trajectory producer: the simulator's IMU records and ground-truth poses produced on the device (opt-in) --------------
+ * What BatchTrajectorySim (xivo_amd/pcw.py) and ImuFeeder.imu (xivo_amd/sequence.py) compute on the host between two camera
+ * frames: every filter follows a closed-form curve (Lissajous or trefoil, at its own rate) with one orientation profile for
+ * all, its IMU reports accel = Rsb^T (a_s - grav_s) + noise and gyro = Jr wd + noise at t_k = k imu_dt, and the feeder turns
+ * samples k - 1, k into the record of sample k (the value at k - 1, the slope to k, dt_k = t_k - t_{k-1}). With the worlds
+ * resident too (xivo_hip_pcw_config) a camera frame of all filters needs no host data and no host wait:
+ *   xivo_hip_trajsim_frame -> xivo_hip_propagate_resident -> xivo_hip_pcw_tracks_resident -> xivo_hip_life_begin_tracks ->
+ *   update -> xivo_hip_absorb_error -> xivo_hip_life_end
+ * Camera stamps coincide with IMU stamps and a frame covers a whole number of samples. The evaluation order and the noise
+ * generator (Philox4x32-10 keyed by the seed, counter = pair, filter, sample) are specified in xivo_amd/csrc/trajsim_device.h;
+ * a sample's noise depends on (seed, k, filter) only. The pixel noise of xivo_hip_pcw_tracks draws from the same generator:
+ * given the same seed the two streams share words, so give them different seeds. Online-calibration contexts
+ * (xivo_hip_set_calib with a motion side) are not supported: XIVO_HIP_ERR_UNSUPPORTED from config, frame and
+ * propagate_resident. */
+typedef struct {
+  int struct_size;             /* sizeof(xivo_trajsim_opts) */
+  int n_max;                   /* most samples one frame may cover; 0 releases everything */
+  int T_max;                   /* frames of the ground-truth log */
+  int reserved;
+  double imu_dt;               /* > 0 */
+  double rot_amp, rot_w[3];    /* orientation profile: rotation vector rot_amp sin(rot_w t), per component */
+  double noise_accel, noise_gyro;   /* standard deviations (>= 0); 0: that sensor draws nothing */
+  double grav_s[3];            /* gravity in the spatial frame */
+  double Rbc[9], Tbc[3];       /* body-to-camera, Rbc ROW-major (only the camera pose reads them) */
+  unsigned long long seed;     /* the IMU noise generator's key */
+} xivo_trajsim_opts;
+/* (Re-)allocates everything the frame calls use: records [batch_max][n_max], curve and rate per filter, the camera poses
+ * [batch_max][12] (the module's own block, with or without worlds configured: xivo_hip_pcw_tracks_resident hands it to the
+ * track producer), the ground-truth log [T_max][batch_max][12], the device copy of the propagation options and the propagate
+ * staging at its final size. Every filter starts as a Lissajous curve of rate 0 (stationary). XIVO_HIP_ERR_INVALID, nothing
+ * changed: wrong struct_size, n_max < 0, (n_max > 0:) T_max <= 0, imu_dt not > 0, a value that is not finite, a negative
+ * noise, a frame open between life_begin and life_end, a size that overflows. Synchronises. */
+int xivo_hip_trajsim_config(xivo_hip_ctx* ctx, const xivo_trajsim_opts* opts);
+/* Curve (0 Lissajous, 1 trefoil) and rate of filters [b0, b0 + nb). A set-up call: synchronises. */
+int xivo_hip_trajsim_set(xivo_hip_ctx* ctx, int b0, int nb, const int* motion, const double* rate);
+/* One frame of filters [0, B): records k0 + 1 .. k0 + n, the poses at t_{k0 + n}, one more frame of the ground-truth log.
+ * n = 0 (the frame at t = 0) writes poses only and leaves no records. Enqueues one kernel; allocates nothing and does not
+ * synchronise. Refused with nothing changed: n < 0 or n > n_max, B out
+ * of range, a frame open between life_begin and life_end, not configured (XIVO_HIP_ERR_INVALID); the log holds T_max frames
+ * (XIVO_HIP_ERR_FULL). */
+int xivo_hip_trajsim_frame(xivo_hip_ctx* ctx, int B, unsigned long long k0, int n);
+/* xivo_hip_propagate of filters [0, B) over the records the last xivo_hip_trajsim_frame(B, ., n > 0) left, which it consumes
+ * (once). Same kernels, same arguments; does not synchronise: Qimu / Qmodel are cached on the device and uploaded again only
+ * when opts differs from the context's copy (a synchronous copy, since opts is borrowed). control_stepsize works as in
+ * xivo_hip_propagate. XIVO_HIP_ERR_INVALID, nothing changed: no fresh records for this B, and what xivo_hip_propagate refuses. */
+int xivo_hip_propagate_resident(xivo_hip_ctx* ctx, int B, const xivo_prop_opts* opts);
+/* xivo_hip_pcw_tracks without the upload: reads the camera poses the last xivo_hip_trajsim_frame(B) left (they stay, a second
+ * call reads them again). XIVO_HIP_ERR_INVALID, nothing changed: no pose for this B, and what xivo_hip_pcw_tracks refuses. */
+int xivo_hip_pcw_tracks_resident(xivo_hip_ctx* ctx, int B, double noise_px_std, unsigned long long seed, unsigned long long frame);
+/* Read-back for tests and a host arm of what the last xivo_hip_trajsim_frame left for filters [b0, b0 + nb) (within its B):
+ * recs [nb][n] (n: that frame's, also written to n_out; consumed records can still be read), gsc [nb][12]. Any may be NULL.
+ * Synchronises. */
+int xivo_hip_trajsim_get(xivo_hip_ctx* ctx, int b0, int nb, xivo_imu_in* recs, double* gsc, int* n_out);
+/* The ground-truth log: frames [t0, t0 + nt) (all written) of filters [b0, b0 + nb), frame-major gt [nt][nb][12] (Rsb
+ * column-major, then Tsb: what xivo_hip_traj_score and xivo_hip_traj_nees take). Synchronises. */
+int xivo_hip_trajsim_get_gt(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, double* gt);
+int xivo_hip_trajsim_count(xivo_hip_ctx* ctx);   /* frames in the log; 0 when not configured */
+int xivo_hip_trajsim_reset(xivo_hip_ctx* ctx);   /* empties the log (and forgets the last frame's records and poses) */
+
 /* ---- covariance propagation tail (src/rk4.cpp:92-102, src/estimator.cpp:590) */
 /* P_mm <- Pmm_new ; P_ms <- Phi P_ms ; P_sm <- P_sm Phi^T. Phi and Pmm_new
  * are nm x nm (nm = kMotionSize: 23, or up to 40 for the online-calibration builds), one pair per filter. */

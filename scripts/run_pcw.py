@@ -85,6 +85,11 @@ def main():
                          "default), or the worlds resident on the device (xivo_hip_pcw_tracks: only the ground-truth camera "
                          "poses go down; pixel noise from its counter-based generator). Needs -lifecycle device and "
                          "-npts <= %d; not with -host cpp" % sequence.L.LIFE_MAX_TRACKS)
+    ap.add_argument("-imu", default="host", choices=["host", "device"],
+                    help="where the simulated IMU and the ground-truth poses come from: the numpy simulator, one message per "
+                         "sample (the default), or the device (xivo_hip_trajsim_frame / xivo_hip_propagate_resident: one call per "
+                         "camera frame, no host data; IMU noise from its counter-based generator). Needs -tracks device and "
+                         "-vectorized; sim_imu_s is then the host's remaining share")
     a = ap.parse_args()
     # (a sequence never brings more tracks than its world has points)
     life = dict(lifecycle=a.lifecycle, tracks_max=min(a.npts, sequence.L.LIFE_MAX_TRACKS))
@@ -102,6 +107,14 @@ def main():
             sequence.check_lifecycle(sequence.SequenceConfig(**life))
         except ValueError as e:
             ap.error(str(e))
+    if a.imu == "device":
+        life.update(imu_source="device")
+        if not a.vectorized:
+            ap.error("-imu device runs with -vectorized")
+        try:      # before any rank is spawned: what check_lifecycle rejects
+            sequence.check_lifecycle(sequence.SequenceConfig(**life))
+        except ValueError as e:
+            ap.error(str(e))
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         from xivo_amd.shard import spawn_ranks
         sys.exit(spawn_ranks([os.path.abspath(__file__)] + sys.argv[1:], a.gpus))
@@ -111,14 +124,15 @@ def main():
         t0 = time.perf_counter()
         out = sequence.run_pcw_batch(cfg, a.sequences, total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
                                      noise_vision_std=a.noise_vision_std, npts=a.npts, timers=tm, trajectory_log=a.traj_log,
-                                     map_log=a.map_log, rpe_dt=a.rpe_dt, innovation_log=a.innov_log, track_source=a.tracks)
+                                     map_log=a.map_log, rpe_dt=a.rpe_dt, innovation_log=a.innov_log, track_source=a.tracks,
+                                     imu_source=a.imu)
         wall = time.perf_counter() - t0
         st = out["estimator"].stats(); out["estimator"].close()
         frames = len(out["ts"])
         ate = np.sqrt(np.mean(np.sum((out["Tsb"] - out["gt_Tsb"]) ** 2, axis=2), axis=0))
         print(json.dumps({
             "sequences": a.sequences, "frames_per_sequence": frames, "N": cfg.N, "integration": a.integration_method,
-            "host": "cpp, vectorised simulators", "lifecycle": a.lifecycle, "tracks": a.tracks,
+            "host": "cpp, vectorised simulators", "lifecycle": a.lifecycle, "tracks": a.tracks, "imu": a.imu,
             "feature_init": a.feature_init, "pool_lifecycle": a.pool_lifecycle,
             **({"admitted": st["admitted"], "pool_dropped": st["pool_dropped"]} if a.feature_init == "subfilter" else {}),
             "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},

@@ -61,6 +61,8 @@ def load_host_library():
         _HOST.xivo_batch_enable_device_pool_lifecycle.argtypes = [C.c_void_p, C.c_int]
         _HOST.xivo_batch_enable_device_world.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_visual_world.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_ulonglong, C.c_void_p]
+        _HOST.xivo_batch_enable_device_imu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _HOST.xivo_batch_frame_resident.argtypes = [C.c_void_p, C.c_ulonglong, C.c_int, C.c_double, C.c_ulonglong, C.c_void_p]
     return _HOST
 
 
@@ -176,6 +178,33 @@ class BatchEstimator:
         if self.host.xivo_batch_visual_world(self.h, float(t), gsc.ctypes.data, float(noise_px_std), int(seed),
                                              mask.ctypes.data if mask is not None else None) != 0:
             raise RuntimeError("VisualMeasDeviceWorld failed")
+
+    def enable_device_imu(self, motion, rate, n_max, T_max, imu_dt, rot_amp=0.2, rot_w=None, noise_accel=1e-4,
+                          noise_gyro=1e-5, grav_s=(0, 0, -9.8), seed=1):
+        """BatchEstimator::EnableDeviceImu: the simulated IMU and the ground-truth poses come from the device
+        (xivo_hip_trajsim_*); motion [B] ("lissajous" / "trefoil"), rate [B], the rest as BatchTrajectorySim; the camera is
+        cfg.Wbc / cfg.Tbc. Needs the device world. The frames are then FrameResident."""
+        from .pcw import so3_exp
+        o = np.zeros(1, dtype=L.trajsim_opts_dtype)
+        o["n_max"], o["T_max"], o["imu_dt"] = int(n_max), int(T_max), imu_dt
+        # (the default profile is BatchTrajectorySim's, to the bit: 0.3 * 3.0 is not 0.9)
+        o["rot_amp"], o["rot_w"] = rot_amp, np.array([0.3, 0.4, 0.1]) * 3.0 if rot_w is None else rot_w
+        o["noise_accel"], o["noise_gyro"], o["grav_s"] = noise_accel, noise_gyro, grav_s
+        o["Rbc"], o["Tbc"], o["seed"] = so3_exp(self.cfg.Wbc).reshape(-1), self.cfg.Tbc, int(seed) & (2 ** 64 - 1)
+        m = np.ascontiguousarray([L.TRAJSIM_MOTIONS[x] if isinstance(x, str) else int(x) for x in motion], dtype=np.int32)
+        r = np.ascontiguousarray(rate, dtype=np.float64)
+        if m.shape != (self.B,) or r.shape != (self.B,):
+            raise ValueError("motion [B], rate [B]")
+        if self.host.xivo_batch_enable_device_imu(self.h, o.ctypes.data, m.ctypes.data, r.ctypes.data) != 0:
+            raise RuntimeError("xivo_batch_enable_device_imu failed")
+
+    def FrameResident(self, k0, n, noise_px_std, seed, mask=None):
+        """a whole camera frame at sample k0 + n from device-resident data: the IMU records k0 + 1 .. k0 + n, the ground-truth
+        poses, the tracks, the life cycle and the update are enqueued; nothing goes down, and nothing comes back unless mask
+        (a [B, F] uint8 array) is given"""
+        if self.host.xivo_batch_frame_resident(self.h, int(k0), int(n), float(noise_px_std), int(seed),
+                                               mask.ctypes.data if mask is not None else None) != 0:
+            raise RuntimeError("FrameResident failed")
 
     def sync(self):
         """wait for the estimator's stream (the device life cycle leaves a frame enqueued)"""

@@ -10,6 +10,7 @@
 //   capi_lifecycle.hip  device life cycle: the per-filter slot book, the two frame calls around the update, counters
 //   capi_pool_lifecycle.hip  device pool life cycle ("subfilter" mode): the pool book, the two frame calls, counters
 //   capi_pcw.hip        point-cloud world: the resident worlds, the per-frame track producer, read-back
+//   capi_trajsim.hip    trajectory producer: the simulated IMU records and ground-truth poses of a frame, the ground-truth log
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
 //
@@ -204,6 +205,16 @@ struct xivo_hip_ctx {
   double* pcw_Xs = nullptr; long long* pcw_ids = nullptr; long long* pcw_next_id = nullptr; int* pcw_cnt = nullptr;
   double* pcw_gsc = nullptr; double* pcw_pin[2] = {nullptr, nullptr}; hipEvent_t pcw_ev[2] = {nullptr, nullptr};
   int pcw_cur = 0, pcw_tracks_B = 0; bool pcw_fresh = false;
+  // trajectory producer (xivo_hip_trajsim_*, capi_trajsim.hip): curve / rate per filter [Bmax], the last frame's records
+  // [Bmax][n_max] (read as [B][n]) and camera poses [Bmax][12], the ground-truth log [T_max][Bmax][12] with frames [0, ts_T)
+  // written, the device copy of the propagation noise (Qimu 144 | Qmodel 529) with the host copy it was uploaded from; null until
+  // xivo_hip_trajsim_config. ts_B / ts_n: the shape of the last frame (ts_B = 0: none), ts_fresh: its records may still be
+  // consumed by xivo_hip_propagate_resident
+  xivo_trajsim_opts ts_opts{};
+  int* ts_motion = nullptr; double* ts_rate = nullptr; xivo_imu_in* ts_recs = nullptr; double* ts_gsc = nullptr;
+  double* ts_gt = nullptr; double* ts_Q = nullptr;
+  xivo_prop_opts ts_prop{}; bool ts_prop_valid = false;
+  int ts_T = 0, ts_B = 0, ts_n = 0; bool ts_fresh = false;
   std::vector<char> hstage;                        // host staging of d2h_rows
   char* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
   // one-filter plumbing call (xivo_hip_update_joseph_host): page-locked, device-mapped staging block owned by the context,
@@ -315,6 +326,14 @@ void pool_life_release(xivo_hip_ctx* c);   // everything xivo_hip_pool_life_conf
 
 // ---- capi_pcw.hip
 void pcw_release(xivo_hip_ctx* c);   // the worlds and the pose staging (the stream must be idle)
+// the track producer over device-resident camera poses gsc [B][12] (what xivo_hip_pcw_tracks enqueues behind its upload)
+int pcw_produce(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, unsigned long long seed, unsigned long long frame);
+
+// ---- capi_propagate.hip
+// Estimator::Propagate of filters [0, B) of a default-build context over device-resident records [B][n_imu] and noise blocks;
+// mean_dt: the samples' length for the profile's flop count. Enqueues only
+int propagate_device(xivo_hip_ctx* c, int B, int n_imu, const xivo_imu_in* recs, const double* dQimu, const double* dQmodel,
+                     const xivo_prop_opts* o, double mean_dt);
 
 // ---- capi_glevel.hip
 int ensure_gate_buffers(xivo_hip_ctx* c, int F);

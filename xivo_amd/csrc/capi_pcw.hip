@@ -21,6 +21,23 @@ void pcw_release(xivo_hip_ctx* c) {
   c->pcw_opts = xivo_pcw_opts{}; c->pcw_cur = 0; c->pcw_tracks_B = 0; c->pcw_fresh = false;
 }
 
+int pcw_produce(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, unsigned long long seed, unsigned long long frame) {
+  const xivo_pcw_opts& o = c->pcw_opts;
+  PcwArgs a{};
+  a.Xs = c->pcw_Xs; a.ids = c->pcw_ids; a.next_id = c->pcw_next_id; a.gsc = gsc; a.npts = o.npts;
+  a.fx = o.fx; a.fy = o.fy; a.cx = o.cx; a.cy = o.cy; a.imw = o.imw; a.imh = o.imh;
+  a.noise_px_std = noise_px_std; a.seed = seed; a.frame = frame;
+  a.track_ids = life_strided_ids(c); a.track_meas = life_strided_meas(c); a.cnt = c->pcw_cnt; a.track_ld = c->life_opts.tracks_max;
+  c->pcw_tracks_B = 0; c->pcw_fresh = false;   // (whatever the block held is being overwritten)
+  {
+    // per filter: the points and their ids in, the ids that changed and at most npts tracks of 32 bytes out
+    StageTimer st(c, ST_OTHER, 0.0, "pcw_tracks_kernel", (double)B * o.npts * (24.0 + 8.0 + 8.0 + 32.0));
+    if (launch_pcw_tracks(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
+  }
+  c->pcw_tracks_B = B; c->pcw_fresh = true;
+  return XIVO_HIP_OK;
+}
+
 }  // namespace xivo_hip::capi
 
 namespace {
@@ -111,20 +128,14 @@ int xivo_hip_pcw_tracks(xivo_hip_ctx* c, int B, const double* gsc, double noise_
   HIP_TRY(hipMemcpyAsync(c->pcw_gsc, c->pcw_pin[set], bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipEventRecord(c->pcw_ev[set], c->stream));
   c->pcw_cur = set;
-  const xivo_pcw_opts& o = c->pcw_opts;
-  PcwArgs a{};
-  a.Xs = c->pcw_Xs; a.ids = c->pcw_ids; a.next_id = c->pcw_next_id; a.gsc = c->pcw_gsc; a.npts = o.npts;
-  a.fx = o.fx; a.fy = o.fy; a.cx = o.cx; a.cy = o.cy; a.imw = o.imw; a.imh = o.imh;
-  a.noise_px_std = noise_px_std; a.seed = seed; a.frame = frame;
-  a.track_ids = life_strided_ids(c); a.track_meas = life_strided_meas(c); a.cnt = c->pcw_cnt; a.track_ld = c->life_opts.tracks_max;
-  c->pcw_tracks_B = 0; c->pcw_fresh = false;   // (whatever the block held is being overwritten)
-  {
-    // per filter: the points and their ids in, the ids that changed and at most npts tracks of 32 bytes out
-    StageTimer st(c, ST_OTHER, 0.0, "pcw_tracks_kernel", (double)B * o.npts * (24.0 + 8.0 + 8.0 + 32.0));
-    if (launch_pcw_tracks(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
-  }
-  c->pcw_tracks_B = B; c->pcw_fresh = true;
-  return XIVO_HIP_OK;
+  return pcw_produce(c, B, c->pcw_gsc, noise_px_std, seed, frame);
+}
+
+int xivo_hip_pcw_tracks_resident(xivo_hip_ctx* c, int B, double noise_px_std, unsigned long long seed, unsigned long long frame) {
+  if (!pcw_ready(c) || B <= 0 || B > c->Bmax || c->life_B != 0 || !isfinite(noise_px_std) || !c->ts_gsc || c->ts_B != B)
+    return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  return pcw_produce(c, B, c->ts_gsc, noise_px_std, seed, frame);
 }
 
 int xivo_hip_pcw_get_tracks(xivo_hip_ctx* c, int b0, int nb, int* cnt, long long* ids, double* meas) {

@@ -23,6 +23,41 @@ int prop_step_control(xivo_hip_ctx* c, const xivo_prop_opts* o) {
   return XIVO_HIP_OK;
 }
 
+// the arguments of the state kernel over device blocks: records, noise, and where Phi / P_mm go
+void prop_args(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_imu_in* dImu, const double* dQi, const double* dQm,
+               double* dPhi, double* dPmm, const xivo_prop_opts* o, PropStateArgs& a) {
+  a = PropStateArgs{};
+  a.poses = c->poses + b0; a.imu = dImu; a.n_imu = n_imu; a.Qimu = dQi; a.Qmodel = dQm;
+  a.g[0] = o->g[0]; a.g[1] = o->g[1]; a.g[2] = o->g[2]; a.method = o->method; a.stepsize = o->stepsize;
+  c->P.from(b0).to(a.P, a.strideP, a.ldp); a.Phi_out = dPhi; a.Pmm_out = dPmm; a.batch = nb;
+  if (o->control_stepsize) {
+    a.pd_h = c->pd_h + b0; a.pd_tol = o->tolerance; a.pd_min_scale = o->min_scale_factor; a.pd_max_scale = o->max_scale_factor;
+  }
+}
+
+// the two launches of the default build: the state kernel and the tail over the 23 motion rows and columns; substeps: integrator
+// sub-steps of one filter over the call (for the profile's flop count)
+int prop_launch(xivo_hip_ctx* c, int b0, int nb, int n_imu, const PropStateArgs& a, double substeps) {
+  {
+    char plabel[64];
+    snprintf(plabel, sizeof(plabel), "propagate_state_wave_kernel<%d>", a.method ? 7 : 4);
+    // algorithmic flops (SURVEY 8 a12 / a13): per integrator sub-step and stage the 23 x 23 Lyapunov right-hand side
+    // F P + P F^T (2 * 2 * 23^3) and the transition recursion F + c F FK (2 * 23^3), as the reference codes them (dense);
+    // sub-steps as src/rk4.cpp:19-31 cuts a sample: ceil(dt / stepsize), the sample's own dt when stepsize <= 0
+    const double stage_flops = 6.0 * 23.0 * 23.0 * 23.0 + 2.0 * 23.0 * 12.0 * (12.0 + 23.0);
+    StageTimer st(c, ST_PROP_STATE, (double)nb * substeps * (a.method ? 7.0 : 4.0) * stage_flops, plabel,
+                  (double)nb * (3.0 * 529 + n_imu * sizeof(xivo_imu_in) / 8.0 + 60.0) * sizeof(double));
+    HIP_TRY((hipError_t)launch_propagate_state(a, c->stream));
+  }
+  {
+    // tail: reads and writes the 23 rows and 23 columns of P that change (+ Phi, P_mm)
+    StageTimer st(c, ST_PROP_TAIL, (double)nb * 2.0 * (2.0 * 23.0 * 23.0 * (c->N - 23)), "propagate_cov_fixed_kernel<23>",
+                  (double)nb * (4.0 * 23 * c->N + 2.0 * 529) * sizeof(double));
+    HIP_TRY((hipError_t)launch_propagate_cov(c->P.p, c->P.stride, c->P.ld, c->N, c->Np, 23, a.Phi_out, a.Pmm_out, b0, nb, c->stream));
+  }
+  return XIVO_HIP_OK;
+}
+
 // What both integrators take: the staging block (Phi [nb][nm x nm] | P_mm [nb][nm x nm] | Qimu 12 x 12 | Qmodel nm x nm | imu),
 // its uploads and the arguments of the state kernel the two share. The caller adds its own (nm, iCg, calib) and launches.
 int prop_stage(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_imu_in* imu, const xivo_prop_opts* o, int nm,
@@ -36,17 +71,30 @@ int prop_stage(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_imu_in* im
   HIP_TRY(hipMemcpyAsync(dQi, o->Qimu, 144 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(dQm, Qmodel, per * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(dImu, imu, (size_t)nb * n_imu * sizeof(xivo_imu_in), hipMemcpyHostToDevice, c->stream));
-  a = PropStateArgs{};
-  a.poses = c->poses + b0; a.imu = dImu; a.n_imu = n_imu; a.Qimu = dQi; a.Qmodel = dQm;
-  a.g[0] = o->g[0]; a.g[1] = o->g[1]; a.g[2] = o->g[2]; a.method = o->method; a.stepsize = o->stepsize;
-  c->P.from(b0).to(a.P, a.strideP, a.ldp); a.Phi_out = dPhi; a.Pmm_out = dPmm; a.batch = nb;
-  if (o->control_stepsize) {
-    a.pd_h = c->pd_h + b0; a.pd_tol = o->tolerance; a.pd_min_scale = o->min_scale_factor; a.pd_max_scale = o->max_scale_factor;
-  }
+  prop_args(c, b0, nb, n_imu, dImu, dQi, dQm, dPhi, dPmm, o, a);
   return XIVO_HIP_OK;
 }
 
 }  // namespace
+
+namespace xivo_hip::capi {
+
+int propagate_device(xivo_hip_ctx* c, int B, int n_imu, const xivo_imu_in* recs, const double* dQimu, const double* dQmodel,
+                     const xivo_prop_opts* o, double mean_dt) {
+  if (bad_range(c, 0, B) || B <= 0 || !c->have_layout || !c->poses || !recs || !o || n_imu <= 0 || c->N < 23 || c->lay.group_begin < 23 ||
+      (o->stepsize >= 0 && o->stepsize < 1e-6))
+    return XIVO_HIP_ERR_INVALID;
+  if (c->calib_motion) return XIVO_HIP_ERR_UNSUPPORTED;
+  int rc = prop_step_control(c, o);
+  if (rc) return rc;
+  rc = ensure_staging(c, 2 * (size_t)529 * B);   // (sized by xivo_hip_trajsim_config: nothing happens here)
+  if (rc) return rc;
+  PropStateArgs a;
+  prop_args(c, 0, B, n_imu, recs, dQimu, dQmodel, c->staging, c->staging + (size_t)529 * B, o, a);
+  return prop_launch(c, 0, B, n_imu, a, n_imu * (o->stepsize > 0 ? std::ceil(mean_dt / o->stepsize) : 1.0));
+}
+
+}  // namespace xivo_hip::capi
 
 extern "C" {
 
@@ -83,25 +131,10 @@ int xivo_hip_propagate(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_im
   PropStateArgs a;
   rc = prop_stage(c, b0, nb, n_imu, imu, o, 23, o->Qmodel, a);
   if (rc) return rc;
-  {
-    char plabel[64];
-    snprintf(plabel, sizeof(plabel), "propagate_state_wave_kernel<%d>", a.method ? 7 : 4);
-    // algorithmic flops (SURVEY 8 a12 / a13): per integrator sub-step and stage the 23 x 23 Lyapunov right-hand side
-    // F P + P F^T (2 * 2 * 23^3) and the transition recursion F + c F FK (2 * 23^3), as the reference codes them (dense);
-    // sub-steps as src/rk4.cpp:19-31 cuts a sample: ceil(dt / stepsize), the sample's own dt when stepsize <= 0
-    double substeps = 0.0;
-    for (int s = 0; s < n_imu; ++s) substeps += o->stepsize > 0 ? std::ceil(imu[s].dt / o->stepsize) : 1.0;
-    const double stage_flops = 6.0 * 23.0 * 23.0 * 23.0 + 2.0 * 23.0 * 12.0 * (12.0 + 23.0);
-    StageTimer st(c, ST_PROP_STATE, (double)nb * substeps * (a.method ? 7.0 : 4.0) * stage_flops, plabel,
-                  (double)nb * (3.0 * 529 + n_imu * sizeof(xivo_imu_in) / 8.0 + 60.0) * sizeof(double));
-    HIP_TRY((hipError_t)launch_propagate_state(a, c->stream));
-  }
-  {
-    // tail: reads and writes the 23 rows and 23 columns of P that change (+ Phi, P_mm)
-    StageTimer st(c, ST_PROP_TAIL, (double)nb * 2.0 * (2.0 * 23.0 * 23.0 * (c->N - 23)), "propagate_cov_fixed_kernel<23>",
-                  (double)nb * (4.0 * 23 * c->N + 2.0 * 529) * sizeof(double));
-    HIP_TRY((hipError_t)launch_propagate_cov(c->P.p, c->P.stride, c->P.ld, c->N, c->Np, 23, a.Phi_out, a.Pmm_out, b0, nb, c->stream));
-  }
+  double substeps = 0.0;
+  for (int s = 0; s < n_imu; ++s) substeps += o->stepsize > 0 ? std::ceil(imu[s].dt / o->stepsize) : 1.0;
+  rc = prop_launch(c, b0, nb, n_imu, a, substeps);
+  if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));   // imu / opts are borrowed host memory
   return XIVO_HIP_OK;
 }

@@ -4,6 +4,7 @@
 #include "common.h"
 #include "ell.h"
 #include "../../include/xivo_hip.h"
+#include "trajsim_device.h"
 
 namespace xivo_hip {
 
@@ -183,6 +184,17 @@ struct PcwArgs {
   long long* track_ids; double* track_meas; int* cnt; int track_ld;
 };
 int launch_pcw_tracks(const PcwArgs& a, int batch, hipStream_t s);
+
+// ================================================================ trajsim_kernels.hip: the trajectory producer (capi_trajsim.hip)
+
+// One frame of filters [0, batch): records k0 + 1 .. k0 + n as recs [batch][n], and at t_{k0 + n} the camera poses gsc [batch][12]
+// and the body poses gt [batch][12] (the frame's row of the ground-truth log). The rules: trajsim_device.h
+struct TrajsimArgs {
+  TrajsimModel m; const int* motion; const double* rate;   // [batch]
+  unsigned long long k0; int n, batch;
+  xivo_imu_in* recs; double* gsc; double* gt;
+};
+int launch_trajsim_frame(const TrajsimArgs& a, hipStream_t s);
 
 // ================================================================ glevel_kernels.hip: feature-level kernels (capi_glevel.hip)
 

@@ -1,7 +1,7 @@
 // The point-cloud world's track producer as plain functions over ONE point of ONE world: projection through the frame's
 // ground-truth camera pose, the visibility test, the pixel noise and who gets which track id. Host and device: the kernel of
 // pcw_kernels.hip calls these functions, and a host compiler takes the header alone (tests/pcw_driver.cpp runs whole frames
-// through them without a GPU). No project header is included.
+// through them without a GPU). No project header is included but philox_device.h, the generator, which is as self-contained.
 //
 // Every rule restates BatchPCW.generate / RandomPCW.generate_measurements (xivo_amd/pcw.py), which follow the reference's
 // scripts/point_cloud_world.py:44-131: a point in front of the camera whose pixel lies inside the image (borders included) is
@@ -31,6 +31,8 @@
 
 #include <math.h>
 #include <stdint.h>
+
+#include "philox_device.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -67,36 +69,21 @@ XIVO_PCW_HD long long pcw_id_after(bool vis, long long id, long long next_id, in
   return !vis ? -1 : (id < 0 ? next_id + rank_new : id);
 }
 
-// ---- noise
-XIVO_PCW_HD void pcw_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
-  uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
-  for (int r = 0; r < 10; ++r) {
-    if (r > 0) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// ---- noise (the generator itself: philox_device.h, shared with the trajectory producer)
+XIVO_PCW_HD void pcw_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) { philox4x32_10(ctr, key, out); }
 // the generator's words of one point
 XIVO_PCW_HD void pcw_noise_words(unsigned long long seed, unsigned long long frame, int b, int p, uint32_t w[4]) {
   const uint32_t ctr[4] = {(uint32_t)p, (uint32_t)b, (uint32_t)(frame & 0xffffffffull), (uint32_t)(frame >> 32)};
   const uint32_t key[2] = {(uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32)};
-  pcw_philox4x32_10(ctr, key, w);
+  philox4x32_10(ctr, key, w);
 }
 // 52 bits -> (0, 1): every value and the + 0.5 are exact in a double
-XIVO_PCW_HD double pcw_uniform(uint32_t hi, uint32_t lo) {
-  return ((double)(((uint64_t)hi << 20) | (uint64_t)(lo >> 12)) + 0.5) * 2.220446049250313e-16;   // 2^-52
-}
+XIVO_PCW_HD double pcw_uniform(uint32_t hi, uint32_t lo) { return philox_uniform(hi, lo); }
 // a pair of unit normals for point p of filter b in that frame
 XIVO_PCW_HD void pcw_normal_pair(unsigned long long seed, unsigned long long frame, int b, int p, double* nu, double* nv) {
-#pragma clang fp contract(off)
   uint32_t w[4];
   pcw_noise_words(seed, frame, b, p, w);
-  const double u1 = pcw_uniform(w[0], w[1]), u2 = pcw_uniform(w[2], w[3]);
-  const double r = sqrt(-2.0 * log(u1)), a = 6.283185307179586 * u2;
-  *nu = r * cos(a); *nv = r * sin(a);
+  philox_box_muller(w, nu, nv);
 }
 // the pixel a track reports
 XIVO_PCW_HD double pcw_noisy(double u, double noise_px_std, double n) {

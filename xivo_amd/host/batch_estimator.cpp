@@ -428,6 +428,28 @@ void BatchEstimator::VisualMeasDeviceWorld(double t, const double* gsc, double n
   if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
 }
 
+void BatchEstimator::EnableDeviceImu(const xivo_trajsim_opts& opts, const int* motion, const double* rate) {
+  if (!device_life_ || !device_world_) throw std::runtime_error("the device IMU needs EnableDeviceLifecycle and EnableDeviceWorld");
+  xivo_trajsim_opts o = opts;
+  o.struct_size = (int)sizeof(o);
+  Check(xivo_hip_trajsim_config(ctx_, &o), "trajsim_config");
+  device_imu_ = o.n_max > 0; device_imu_dt_ = o.imu_dt;
+  if (device_imu_) Check(xivo_hip_trajsim_set(ctx_, 0, B_, motion, rate), "trajsim_set");
+}
+
+void BatchEstimator::FrameResident(unsigned long long k0, int n, double noise_px_std, unsigned long long seed, unsigned char* mask_out) {
+  if (!device_imu_ || !device_world_ || !device_life_) throw std::runtime_error("FrameResident needs EnableDeviceImu");
+  t_visual_ = (double)(k0 + (unsigned long long)n) * device_imu_dt_;
+  want_mask_ = mask_out != nullptr;
+  Check(xivo_hip_trajsim_frame(ctx_, B_, k0, n), "trajsim_frame");
+  if (n > 0) Check(xivo_hip_propagate_resident(ctx_, B_, &cfg_.prop), "propagate_resident");
+  Check(xivo_hip_pcw_tracks_resident(ctx_, B_, noise_px_std, seed, world_frame_++), "pcw_tracks_resident");
+  Check(xivo_hip_life_begin_tracks(ctx_, B_, cfg_.n_features), "life_begin_tracks");
+  RunUpdate();
+  Check(xivo_hip_life_end(ctx_, B_), "life_end");
+  if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
+}
+
 void BatchEstimator::ReadBook(int b) {
   const int F = cfg_.n_features;
   Book& bk = books_[b];
@@ -754,6 +776,15 @@ int xivo_batch_enable_device_world(void* h, int npts, const xivo_pcw_opts* cam, 
 int xivo_batch_visual_world(void* h, double t, const double* gsc, double noise_px_std, unsigned long long seed, unsigned char* mask_out) {
   if (!h) return -1;
   try { static_cast<xivo::hip::BatchEstimator*>(h)->VisualMeasDeviceWorld(t, gsc, noise_px_std, seed, mask_out); return 0; }
+  catch (const std::exception&) { return -1; }
+}
+int xivo_batch_enable_device_imu(void* h, const xivo_trajsim_opts* opts, const int* motion, const double* rate) {
+  if (!h || !opts) return -1;
+  try { static_cast<xivo::hip::BatchEstimator*>(h)->EnableDeviceImu(*opts, motion, rate); return 0; } catch (const std::exception&) { return -1; }
+}
+int xivo_batch_frame_resident(void* h, unsigned long long k0, int n, double noise_px_std, unsigned long long seed, unsigned char* mask_out) {
+  if (!h) return -1;
+  try { static_cast<xivo::hip::BatchEstimator*>(h)->FrameResident(k0, n, noise_px_std, seed, mask_out); return 0; }
   catch (const std::exception&) { return -1; }
 }
 void* xivo_batch_ctx(void* h) { return static_cast<xivo::hip::BatchEstimator*>(h)->ctx(); }

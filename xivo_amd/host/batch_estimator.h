@@ -122,6 +122,16 @@ class BatchEstimator {
   void EnableDeviceWorld(int npts, const xivo_pcw_opts& cam, const double* Xs);
   void VisualMeasDeviceWorld(double t, const double* gsc, double noise_px_std, unsigned long long seed, unsigned char* mask_out);
   bool device_world() const { return device_world_; }
+  // the simulated IMU and the ground-truth poses from the device too (xivo_hip_trajsim_*; after EnableDeviceWorld, both calls
+  // throw without it): EnableDeviceImu configures the trajectory producer (opts as xivo_hip_trajsim_config takes them;
+  // struct_size is filled in here) with curve motion[b] (0 Lissajous, 1 trefoil) and rate[b] per filter; n_max = 0 releases it.
+  // FrameResident is then a whole camera frame at sample k0 + n without host data or a host wait: trajsim frame -> resident
+  // propagate (n > 0) -> resident tracks -> life_begin_tracks -> update -> life_end. It takes the place of the InertialMeas
+  // calls of samples k0 + 1 .. k0 + n and the VisualMeasDeviceWorld call at t_{k0 + n}; the two kinds of frames do not mix in
+  // one run (the host feeder does not see the device's samples).
+  void EnableDeviceImu(const xivo_trajsim_opts& opts, const int* motion, const double* rate);
+  void FrameResident(unsigned long long k0, int n, double noise_px_std, unsigned long long seed, unsigned char* mask_out);
+  bool device_imu() const { return device_imu_; }
 
   struct Book {                                     // one filter's slots
     std::vector<int> group_refs;                    // -1 free, else number of in-state features anchored there
@@ -144,6 +154,7 @@ class BatchEstimator {
   long DeviceCount(int which) const { return device_life_ ? LifeCount(which) : (device_pool_life_ ? PoolLifeCount(which) : 0); }
   bool device_life_ = false, want_mask_ = false, device_world_ = false, device_pool_life_ = false;
   unsigned long long world_frame_ = 0;
+  bool device_imu_ = false; double device_imu_dt_ = 0.0;
 
   struct PoolBook {                                 // one filter's feature pool: tracks per entry, anchors and their links
     std::vector<int64_t> ent_id;                    // -1 free

@@ -135,6 +135,12 @@ POOL_LIFE_MAX_ANCHORS = 256
 pcw_opts_dtype = np.dtype([("struct_size", "i4"), ("npts", "i4"), ("fx", "f8"), ("fy", "f8"), ("cx", "f8"), ("cy", "f8"),
                            ("imw", "f8"), ("imh", "f8")])
 assert pcw_opts_dtype.itemsize == 56
+# trajectory producer (include/xivo_hip.h): xivo_trajsim_opts
+trajsim_opts_dtype = np.dtype([("struct_size", "i4"), ("n_max", "i4"), ("T_max", "i4"), ("reserved", "i4"), ("imu_dt", "f8"),
+                               ("rot_amp", "f8"), ("rot_w", "f8", 3), ("noise_accel", "f8"), ("noise_gyro", "f8"),
+                               ("grav_s", "f8", 3), ("Rbc", "f8", 9), ("Tbc", "f8", 3), ("seed", "u8")])
+assert trajsim_opts_dtype.itemsize == 200
+TRAJSIM_MOTIONS = {"lissajous": 0, "trefoil": 1}
 
 
 def lib_path():
@@ -272,6 +278,15 @@ _SIGS = {
     "xivo_hip_pcw_get_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "xivo_hip_pcw_tracks": [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_ulonglong, C.c_ulonglong],
     "xivo_hip_pcw_get_tracks": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_pcw_tracks_resident": [C.c_void_p, C.c_int, C.c_double, C.c_ulonglong, C.c_ulonglong],
+    "xivo_hip_trajsim_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_trajsim_set": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "xivo_hip_trajsim_frame": [C.c_void_p, C.c_int, C.c_ulonglong, C.c_int],
+    "xivo_hip_propagate_resident": [C.c_void_p, C.c_int, C.c_void_p],
+    "xivo_hip_trajsim_get": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_trajsim_get_gt": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_trajsim_count": [C.c_void_p],
+    "xivo_hip_trajsim_reset": [C.c_void_p],
 }
 HOST_P_RESIDENT, HOST_KEEP_P = 1, 2
 
@@ -350,6 +365,20 @@ def candidate_order(feats, strict=False, score_type=0):
     if rc != 0:
         raise XivoHipError(rc, lib.xivo_hip_strerror(rc).decode())
     return order, cnt, score
+
+
+def prop_options(Qimu, Qmodel, g, method="RK4", stepsize=0.002, pd_control=None):
+    """xivo_prop_opts: Qimu 12x12, Qmodel 23x23 (numpy row-major); pd_control: dict(tolerance, attempts, min_scale_factor,
+    max_scale_factor) switches on the step-size-controlled branch of Estimator::PrinceDormand"""
+    o = np.zeros(1, dtype=prop_opts_dtype)
+    o["Qimu"] = np.asarray(Qimu, dtype=np.float64).T.reshape(-1)
+    o["Qmodel"] = np.asarray(Qmodel, dtype=np.float64).T.reshape(-1)
+    o["g"] = g; o["method"] = 0 if method == "RK4" else 1; o["stepsize"] = stepsize
+    if pd_control is not None:
+        o["control_stepsize"] = 1
+        o["tolerance"] = pd_control.get("tolerance", 1e-3); o["attempts"] = pd_control.get("attempts", 12)
+        o["min_scale_factor"] = pd_control.get("min_scale_factor", 0.125); o["max_scale_factor"] = pd_control.get("max_scale_factor", 4.0)
+    return o
 
 
 def _ptr(a):
@@ -813,14 +842,7 @@ class Context:
         if imu.ndim == 1:
             imu = imu[:, None]
         imu = np.ascontiguousarray(imu)
-        o = np.zeros(1, dtype=prop_opts_dtype)
-        o["Qimu"] = np.asarray(Qimu, dtype=np.float64).T.reshape(-1)
-        o["Qmodel"] = np.asarray(Qmodel, dtype=np.float64).T.reshape(-1)
-        o["g"] = g; o["method"] = 0 if method == "RK4" else 1; o["stepsize"] = stepsize
-        if pd_control is not None:
-            o["control_stepsize"] = 1
-            o["tolerance"] = pd_control.get("tolerance", 1e-3); o["attempts"] = pd_control.get("attempts", 12)
-            o["min_scale_factor"] = pd_control.get("min_scale_factor", 0.125); o["max_scale_factor"] = pd_control.get("max_scale_factor", 4.0)
+        o = prop_options(Qimu, Qmodel, g, method, stepsize, pd_control)
         self._check(self.lib.xivo_hip_propagate(self.h, b0, imu.shape[0], imu.shape[1], _ptr(imu), _ptr(o)))
 
     def propagate_calib(self, imu, Qimu, Qmodel, g, method="RK4", stepsize=0.002, b0=0, pd_control=None):
@@ -1130,6 +1152,67 @@ class Context:
         meas = np.zeros((nb, int(tracks_max), 3))
         self._check(self.lib.xivo_hip_pcw_get_tracks(self.h, int(b0), nb, _ptr(cnt), _ptr(ids), _ptr(meas)))
         return cnt, ids, meas
+
+    def pcw_tracks_resident(self, noise_px_std, seed, frame, B=None):
+        """pcw_tracks on the camera poses the last trajsim_frame(B) left on the device (asynchronous, no upload)"""
+        self._check(self.lib.xivo_hip_pcw_tracks_resident(self.h, self.batch if B is None else int(B), float(noise_px_std),
+                                                          int(seed), int(frame)))
+
+    # ---- trajectory producer on the device (xivo_hip_trajsim_*)
+    def trajsim_config(self, n_max, T_max=0, imu_dt=0.0025, rot_amp=0.2, rot_w=None, noise_accel=1e-4, noise_gyro=1e-5,
+                       grav_s=(0, 0, -9.8), Rbc=None, Tbc=(0, 0, 0), seed=1):
+        """the simulated IMU and ground truth of every filter on the device: at most n_max samples per frame, a ground-truth
+        log of T_max frames (n_max = 0 releases it); Rbc [3, 3], Tbc [3]: body to camera; the rest as BatchTrajectorySim"""
+        o = np.zeros(1, dtype=trajsim_opts_dtype)
+        o["struct_size"], o["n_max"], o["T_max"], o["imu_dt"] = trajsim_opts_dtype.itemsize, int(n_max), int(T_max), imu_dt
+        # (the default profile is BatchTrajectorySim's, to the bit: 0.3 * 3.0 is not 0.9)
+        o["rot_amp"], o["rot_w"] = rot_amp, np.array([0.3, 0.4, 0.1]) * 3.0 if rot_w is None else rot_w
+        o["noise_accel"], o["noise_gyro"], o["grav_s"] = noise_accel, noise_gyro, grav_s
+        o["Rbc"] = (np.eye(3) if Rbc is None else np.asarray(Rbc, dtype=np.float64)).reshape(-1)
+        o["Tbc"], o["seed"] = Tbc, int(seed) & (2 ** 64 - 1)
+        self._check(self.lib.xivo_hip_trajsim_config(self.h, _ptr(o)))
+
+    def trajsim_set(self, motion, rate, b0=0):
+        """curve ("lissajous" / "trefoil" or 0 / 1) and rate of filters [b0, b0 + len(rate))"""
+        m = np.ascontiguousarray([TRAJSIM_MOTIONS[x] if isinstance(x, str) else int(x) for x in motion], dtype=np.int32)
+        r = np.ascontiguousarray(rate, dtype=np.float64)
+        if m.shape != r.shape or r.ndim != 1:
+            raise ValueError("motion [nb], rate [nb]")
+        self._check(self.lib.xivo_hip_trajsim_set(self.h, int(b0), r.shape[0], _ptr(m), _ptr(r)))
+
+    def trajsim_frame(self, k0, n, B=None):
+        """records k0 + 1 .. k0 + n and the poses at sample k0 + n of filters [0, B) (asynchronous)"""
+        self._check(self.lib.xivo_hip_trajsim_frame(self.h, self.batch if B is None else int(B), int(k0), int(n)))
+
+    def propagate_resident(self, Qimu=None, Qmodel=None, g=None, method="RK4", stepsize=0.002, pd_control=None, B=None, opts=None):
+        """propagate over the records the last trajsim_frame(B) left (asynchronous); opts: a prop_options() record kept by the
+        caller, instead of building one per call"""
+        o = prop_options(Qimu, Qmodel, g, method, stepsize, pd_control) if opts is None else opts
+        self._check(self.lib.xivo_hip_propagate_resident(self.h, self.batch if B is None else int(B), _ptr(o)))
+
+    def trajsim_get(self, b0=0, nb=None):
+        """what the last trajsim_frame left -> (recs [nb, n] imu_dtype, gsc [nb, 12]); one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        n = C.c_int(0)
+        self._check(self.lib.xivo_hip_trajsim_get(self.h, int(b0), 0, None, None, C.byref(n)))
+        recs = np.zeros((nb, n.value), dtype=imu_dtype)
+        gsc = np.zeros((nb, 12))
+        self._check(self.lib.xivo_hip_trajsim_get(self.h, int(b0), nb, _ptr(recs), _ptr(gsc), None))
+        return recs, gsc
+
+    def trajsim_count(self):
+        return int(self.lib.xivo_hip_trajsim_count(self.h))
+
+    def trajsim_get_gt(self, b0=0, nb=None, t0=0, nt=None):
+        """the ground-truth log -> gt [nt, nb, 12] (Rsb column-major, Tsb): what traj_score / traj_nees take packed"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        nt = self.trajsim_count() - t0 if nt is None else int(nt)
+        gt = np.zeros((nt, nb, 12))
+        self._check(self.lib.xivo_hip_trajsim_get_gt(self.h, int(b0), nb, int(t0), nt, _ptr(gt)))
+        return gt
+
+    def trajsim_reset(self):
+        self._check(self.lib.xivo_hip_trajsim_reset(self.h))
 
     def life_end(self, B=None):
         """after the update and absorb_error (asynchronous)"""

@@ -154,9 +154,16 @@ def so3_exp_batch(w):
 
 
 class BatchTrajectorySim:
-    """B trajectories: motion[b] in {"lissajous", "trefoil"}, rate[b]; one noise stream for all."""
+    """B trajectories: motion[b] in {"lissajous", "trefoil"}, rate[b]; one noise stream for all.
+    noise: "numpy" (default) draws the IMU noise from the simulator's numpy generator; "philox" draws the stream of the device
+    producer (trajsim_normals, keyed by noise_seed, the sample index k handed to meas() and the sequence), so that a host arm
+    can be held against a device arm. The arithmetic is the same either way."""
 
-    def __init__(self, motion, rate, rot_amp=0.2, noise_accel=1e-4, noise_gyro=1e-5, grav_s=(0, 0, -9.8), seed=1):
+    def __init__(self, motion, rate, rot_amp=0.2, noise_accel=1e-4, noise_gyro=1e-5, grav_s=(0, 0, -9.8), seed=1, noise="numpy",
+                 noise_seed=0):
+        if noise not in ("numpy", "philox"):
+            raise ValueError("noise must be 'numpy' or 'philox'")
+        self.noise, self.noise_seed = noise, int(noise_seed)
         self.is_tre = np.array([m == "trefoil" for m in motion])
         self.rate = np.asarray(rate, dtype=float)
         self.B = len(self.rate)
@@ -186,15 +193,22 @@ class BatchTrajectorySim:
     def vel(self, t):
         return self.rate[:, None] * self._curve(self.rate * t)[1]
 
-    def meas(self, t):
-        """-> (accel [B, 3], gyro [B, 3])"""
+    def meas(self, t, k=None):
+        """-> (accel [B, 3], gyro [B, 3]); k: the sample's index (noise="philox" needs it: the generator's counter)"""
         w = np.tile(self.rot_amp * np.sin(self.rot_w * t), (self.B, 1))
         wd = self.rot_amp * self.rot_w * np.cos(self.rot_w * t)
         R, W, th = so3_exp_batch(w)
         a_s = (self.rate ** 2)[:, None] * self._curve(self.rate * t)[2]
         Jr = _right_jacobian(w[0])                       # the orientation profile is shared by all sequences
-        accel = np.einsum("bji,bj->bi", R, a_s - self.grav_s) + self.noise_accel * self.rng.standard_normal((self.B, 3))
-        gyro = (Jr @ wd)[None] + self.noise_gyro * self.rng.standard_normal((self.B, 3))
+        if self.noise == "philox":
+            if k is None:
+                raise ValueError("noise='philox' needs the sample index k")
+            n6 = trajsim_normals(self.noise_seed, k, np.arange(self.B))
+            n_a, n_g = n6[:, :3], n6[:, 3:]
+        else:
+            n_a, n_g = self.rng.standard_normal((self.B, 3)), self.rng.standard_normal((self.B, 3))
+        accel = np.einsum("bji,bj->bi", R, a_s - self.grav_s) + self.noise_accel * n_a
+        gyro = (Jr @ wd)[None] + self.noise_gyro * n_g
         return accel, gyro
 
 
@@ -238,6 +252,15 @@ def philox_normal(seed, frame, b, p):
     u2 = (((w[..., 2] << np.uint64(20)) | (w[..., 3] >> np.uint64(12))).astype(np.float64) + 0.5) * 2.0 ** -52
     r, a = np.sqrt(-2.0 * np.log(u1)), 6.283185307179586 * u2
     return np.stack([r * np.cos(a), r * np.sin(a)], axis=-1)
+
+
+def trajsim_normals(seed, k, b):
+    """the six unit normals (accel x y z, gyro x y z) the device trajectory producer draws for IMU sample k of filter b
+    (xivo_amd/csrc/trajsim_device.h): the same generator with counter = (pair j, filter, k low, k high), pair 0 = accel x y,
+    pair 1 = accel z, gyro x, pair 2 = gyro y z -> [..., 6]. With the same seed these are the words of philox_normal for
+    point j, filter b, frame k: give the IMU and the pixel noise different seeds."""
+    b = np.asarray(b)
+    return philox_normal(seed, k, b[..., None], np.arange(3)).reshape(b.shape + (6,))
 
 
 def project_points(Xs, Rsc, Tsc, K, imw, imh):

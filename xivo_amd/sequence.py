@@ -41,6 +41,11 @@ What is mirrored from the reference and what is simplified:
     produces each frame's tracks from the ground-truth camera poses straight into the block the life cycle reads
     (`SequenceRunner.frame_world`): 96 bytes per filter go down instead of the tracks. Its pixel noise is the counter-based
     stream pcw.philox_normal restates.
+  * where the IMU records come from (`SequenceConfig.imu_source`): "host" (default) - the numpy simulator and `ImuFeeder`, uploaded
+    by xivo_hip_propagate; "device" (needs track_source="device") - xivo_hip_trajsim_frame (trajsim_kernels.hip) produces the
+    feeder's records and the ground-truth camera and body poses on the device, xivo_hip_propagate_resident consumes the records
+    there (`SequenceRunner.frame_resident`): a frame takes no host data and no host wait. Its IMU noise is the counter-based
+    stream pcw.trajsim_normals restates.
   * NOT IN EITHER: RefineDepth (`use_depth_opt`), gauge XY features and SwitchRefGroup, ownership transfer, OOS updates.
 The numerics of every step are the device path; this file holds no arithmetic of the filter itself.
 """
@@ -173,6 +178,10 @@ class SequenceConfig:
         # resident worlds of npts points each; needs lifecycle = "device" and npts <= tracks_max)
         self.track_source = "host"
         self.npts = 1000
+        # where the simulated IMU records and the ground-truth poses come from: "host" (the numpy simulator and ImuFeeder, the
+        # records uploaded by xivo_hip_propagate) or "device" (xivo_hip_trajsim_frame / xivo_hip_propagate_resident; needs
+        # track_source = "device": a frame then takes no host data at all)
+        self.imu_source = "host"
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option " + k)
@@ -400,6 +409,29 @@ class HipBackend:
     def life_begin_tracks(self):
         self.ctx.life_begin_tracks(self.F, B=self.B)
 
+    def enable_device_imu(self, motion, rate, n_max, T_max, imu_dt, **sim):
+        """allocate the device trajectory producer (xivo_hip_trajsim_config / _set): motion [B], rate [B] and the keyword
+        arguments of BatchTrajectorySim (rot_amp, noise_accel, noise_gyro, grav_s, seed) plus rot_w; the camera is cfg.Wbc /
+        cfg.Tbc; at most n_max samples per frame, a ground-truth log of T_max frames"""
+        self.ctx.trajsim_config(n_max, T_max, imu_dt=imu_dt, Rbc=so3_exp(self.cfg.Wbc), Tbc=self.cfg.Tbc, **sim)
+        self.ctx.trajsim_set(motion, rate)
+        self._prop_opts = L.prop_options(self.Qimu, self.Qmodel, self.cfg.gravity,
+                                         "RK4" if self.cfg.integration_method == "RK4" else "PD", self.cfg.stepsize)
+
+    def make_imu(self, k0, n):
+        """the records k0 + 1 .. k0 + n and the poses at sample k0 + n of every filter (asynchronous)"""
+        self.ctx.trajsim_frame(k0, n, B=self.B)
+
+    def propagate_resident(self):
+        self.ctx.propagate_resident(opts=self._prop_opts, B=self.B)
+
+    def make_tracks_resident(self, noise_px_std, seed, frame):
+        self.ctx.pcw_tracks_resident(noise_px_std, seed, frame, B=self.B)
+
+    def ground_truth(self):
+        """the device's ground-truth log -> gt [n, B, 12] (Rsb column-major, Tsb); one synchronising read"""
+        return self.ctx.trajsim_get_gt(0, self.B)
+
     def world_ids(self):
         """(ids [B, npts], next_id [B]) of the resident worlds; one synchronising read"""
         return self.ctx.pcw_get_world(0, self.B)
@@ -598,6 +630,11 @@ def check_lifecycle(cfg):
     src = getattr(cfg, "track_source", "host")
     if src not in ("host", "device"):
         raise ValueError("track_source must be 'host' or 'device'")
+    imu = getattr(cfg, "imu_source", "host")
+    if imu not in ("host", "device"):
+        raise ValueError("imu_source must be 'host' or 'device'")
+    if imu == "device" and src != "device":
+        raise ValueError("imu_source='device' needs track_source='device'")
     if src == "device":
         if cfg.lifecycle != "device":
             raise ValueError("track_source='device' needs lifecycle='device'")
@@ -753,6 +790,31 @@ class SequenceRunner:
             be.propagate(imu)
         t0 = self._tick("propagate", t0) or t0
         be.make_tracks(gsc, self.noise_px_std, self.noise_seed, frame)
+        t0 = self._tick("tracks", t0) or t0
+        be.life_begin_tracks()
+        t0 = self._tick("edit", t0) or t0
+        mask = be.update(download=self.want_mask)
+        t0 = self._tick("update", t0) or t0
+        be.life_end()
+        self._tick("edit", t0)
+        return mask
+
+    def frame_resident(self, k0, n, frame):
+        """one camera frame at IMU sample k0 + n that takes no host data (imu_source="device"): the device produces the records
+        k0 + 1 .. k0 + n and the ground-truth poses (make_imu), propagates over them, produces the tracks from the poses and
+        runs the life cycle and the update; n = 0: the frame at t = 0, nothing to propagate. frame: the pixel noise
+        generator's counter. Nothing is downloaded (unless want_mask)."""
+        import time
+        if getattr(self.cfg, "imu_source", "host") != "device":
+            raise ValueError("frame_resident needs imu_source='device'")
+        be = self.be
+        t0 = time.perf_counter()
+        be.make_imu(k0, n)
+        t0 = self._tick("imu", t0) or t0
+        if n > 0:
+            be.propagate_resident()
+        t0 = self._tick("propagate", t0) or t0
+        be.make_tracks_resident(self.noise_px_std, self.noise_seed, frame)
         t0 = self._tick("tracks", t0) or t0
         be.life_begin_tracks()
         t0 = self._tick("edit", t0) or t0
@@ -1017,6 +1079,9 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     cfg.track_source = "device": the points of `worlds` go to the device once and every frame is SequenceRunner.frame_world
     on the ground-truth camera poses; the worlds' own generate_measurements is not called, the pixel noise is the device's
     stream keyed by noise_seed, and with map_log the world ids are downloaded once per recorded frame."""
+    if getattr(cfg, "imu_source", "host") == "device":
+        raise ValueError("run_pcw feeds the simulators' IMU messages one by one: imu_source='device' runs with run_pcw_batch "
+                         "or SequenceRunner.frame_resident")
     B = len(sims)
     K = np.array([[cfg.cam["fx"], 0, cfg.cam["cx"]], [0, cfg.cam["fy"], cfg.cam["cy"]], [0, 0, 1.0]])
     Rbc = so3_exp(cfg.Wbc)
@@ -1127,7 +1192,7 @@ def camera_poses(Rsb, Tsb, Rbc, Tbc):
 
 def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0, npts=1000, seed=0, device=0,
                   timers=None, trajectory_log=False, map_log=False, rpe_dt=1.0, innovation_log=False, track_source=None,
-                  noise="numpy", noise_seed=0):
+                  noise="numpy", noise_seed=0, imu_source=None, imu_noise="numpy"):
     """Thousands of sequences end to end: the vectorised simulators of xivo_amd/pcw.py (BatchTrajectorySim, BatchPCW) feed
     xivo::hip::BatchEstimator message by message. -> dict(ts, Tsb [n x B x 3], gt_Tsb, estimator)
     trajectory_log: as in run_pcw - one record launch per frame on the estimator's context and one read at the end instead of
@@ -1140,6 +1205,13 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     the host track source the same stream and projection order (BatchPCW(noise="philox")), for comparing the two. With map_log
     and device tracks, the world's ids are read from the device once per recorded frame (xivo_hip_pcw_get_world: B x npts ids, a
     synchronising download - not for a timed run).
+    imu_source ("host" / "device", default cfg.imu_source): "device" (needs device tracks) keeps the trajectory simulator on
+    the device too (BatchEstimator::EnableDeviceImu): one FrameResident call per camera frame takes the place of the `every`
+    InertialMeas calls and the frame call, nothing goes down during the run, and the ground truth is read from the device's log
+    once at the end; only the initial poses and velocity come from the host simulator. The IMU noise is then the stream of
+    pcw.trajsim_normals keyed by seed + 1 (the host simulator's seed); imu_noise="philox" gives the host IMU arm the same
+    stream, for comparing the two. The IMU and the pixel stream share a generator: equal keys (seed + 1 == noise_seed) are
+    refused when both are in use.
     timers: "sim_imu" and "sim_tracks" are the two simulators' shares, "sim" their sum; with device tracks "sim_tracks" is the
     ground-truth pose alone."""
     import copy
@@ -1153,9 +1225,19 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
         if dev_tracks:
             cfg.npts = npts
         check_lifecycle(cfg)
+    dev_imu = (imu_source or getattr(cfg, "imu_source", "host")) == "device"
+    if imu_source is not None or dev_imu:
+        cfg = copy.copy(cfg)
+        cfg.imu_source = "device" if dev_imu else "host"
+        check_lifecycle(cfg)
+    if imu_noise not in ("numpy", "philox"):
+        raise ValueError("imu_noise must be 'numpy' or 'philox'")
+    if (dev_imu or imu_noise == "philox") and (dev_tracks or noise == "philox") and (seed + 1) % 2 ** 64 == noise_seed % 2 ** 64:
+        raise ValueError("the IMU noise (key seed + 1 = %d) and the pixel noise (key noise_seed) would share their words: "
+                         "choose different seeds" % (seed + 1))
     motion = ["lissajous" if b % 2 == 0 else "trefoil" for b in range(B)]
     rate = 0.08 + 0.04 * (np.arange(B) % 7) / 7
-    sim = BatchTrajectorySim(motion, rate, seed=seed + 1)
+    sim = BatchTrajectorySim(motion, rate, seed=seed + 1, noise=imu_noise, noise_seed=seed + 1)
     world = BatchPCW(B, npts=npts, seed=seed, noise=noise, noise_seed=noise_seed)
     K = np.array([[cfg.cam["fx"], 0, cfg.cam["cx"]], [0, cfg.cam["fy"], cfg.cam["cy"]], [0, 0, 1.0]])
     Rbc = so3_exp(cfg.Wbc)
@@ -1168,6 +1250,9 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     if dev_tracks:
         est.enable_device_world(world.Xs)
     n_imu = int(round(total_time / imu_dt)); every = int(round(vision_dt / imu_dt))
+    if dev_imu:
+        est.enable_device_imu(motion, rate, every, (n_imu + every - 1) // every, imu_dt, rot_amp=sim.rot_amp, rot_w=sim.rot_w,
+                              noise_accel=sim.noise_accel, noise_gyro=sim.noise_gyro, grav_s=sim.grav_s, seed=seed + 1)
     ts, est_T, gt_T, gt_R = [], [], [], []
     ctx = None
     if trajectory_log:      # the estimator's own context (it stays the owner)
@@ -1185,20 +1270,27 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     tm = timers if timers is not None else {}
     for k in range(n_imu):
         t = k * imu_dt
-        t0 = time.perf_counter()
-        accel, gyro = sim.meas(t)
-        tm["sim_imu"] = tm.get("sim_imu", 0.0) + time.perf_counter() - t0
-        est.InertialMeas(t, gyro, accel)
+        if dev_imu and k % every != 0:
+            continue
+        if not dev_imu:
+            t0 = time.perf_counter()
+            accel, gyro = sim.meas(t, k)
+            tm["sim_imu"] = tm.get("sim_imu", 0.0) + time.perf_counter() - t0
+            est.InertialMeas(t, gyro, accel)
         if k % every == 0:
             t0 = time.perf_counter()
-            Rsb, Tsb = sim.gsb(t)
-            Rsc, Tsc, gsc = camera_poses(Rsb, Tsb, Rbc, cfg.Tbc)
+            if not dev_imu:
+                Rsb, Tsb = sim.gsb(t)
+                Rsc, Tsc, gsc = camera_poses(Rsb, Tsb, Rbc, cfg.Tbc)
             if not dev_tracks:
                 off, ids, meas = world.generate(Rsc, Tsc, K, cfg.cam["cols"], cfg.cam["rows"], noise_vision_std)
             t1 = time.perf_counter()
             tm["sim_tracks"] = tm.get("sim_tracks", 0.0) + t1 - t0
             mask = np.zeros((B, cfg.n_features), dtype=np.uint8) if est.want_mask else None   # (device life cycle: no download)
-            if dev_tracks:
+            if dev_imu:
+                # samples k - every + 1 .. k since the last frame (none before the frame at t = 0)
+                est.FrameResident(k - every if k else 0, every if k else 0, noise_vision_std, noise_seed, mask)
+            elif dev_tracks:
                 est.VisualMeasDeviceWorld(t, gsc, noise_vision_std, noise_seed, mask)
             elif host.xivo_batch_visual(est.h, float(t), off.ctypes.data, ids.ctypes.data, meas.ctypes.data,
                                         mask.ctypes.data if mask is not None else None) != 0:
@@ -1209,15 +1301,24 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
                 tm["frame_enqueue"] = tm.get("frame_enqueue", 0.0) + time.perf_counter() - t1
                 est.sync()
             tm["frame"] = tm.get("frame", 0.0) + time.perf_counter() - t1
-            ts.append(int(round(t * 1e9))); gt_T.append(Tsb)
+            ts.append(int(round(t * 1e9)))
+            if not dev_imu:
+                gt_T.append(Tsb)
             if ctx is not None:
-                ctx.traj_record(ts[-1], B); gt_R.append(Rsb)
+                ctx.traj_record(ts[-1], B)
+                if not dev_imu:
+                    gt_R.append(Rsb)
             else:
                 est_T.append(est.poses()["Tsb"].copy())
             if mlog is not None:
                 mlog.record(ts[-1], [est.book(b)[0] for b in range(B)], mctx.pcw_get_world(0, B)[0] if dev_tracks else world.ids,
                             world.Xs)
-    tm["sim"] = tm.get("sim_imu", 0.0) + tm.get("sim_tracks", 0.0)
+    tm["sim_imu"] = tm.get("sim_imu", 0.0)
+    tm["sim"] = tm["sim_imu"] + tm.get("sim_tracks", 0.0)
+    if dev_imu:     # the ground truth of the whole run in one read of the device's log
+        gctx = ctx if ctx is not None else L.Context.borrow(host.xivo_batch_ctx(est.h), cfg.N, 2 * cfg.n_features, B)
+        gt = gctx.trajsim_get_gt(0, B)
+        gt_T, gt_R = gt[:, :, 9:], gt[:, :, :9].reshape(gt.shape[0], B, 3, 3).transpose(0, 1, 3, 2)
     out = dict(ts=np.array(ts), gt_Tsb=np.array(gt_T), estimator=est)
     if mlog is not None:
         mlog.finish(out)
