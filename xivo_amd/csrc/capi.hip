@@ -162,15 +162,11 @@ void xivo_hip_destroy(xivo_hip_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
+  track_block_release(c);   // the page-locked staging of the life cycles' tracks and of the world's poses
+  pcw_release(c);
   c->mem.free_all();
   if (c->ell_flags_h) hipHostFree(c->ell_flags_h);
   if (c->pin_h) hipHostFree(c->pin_h);
-  for (int i = 0; i < 2; ++i) {   // the life cycle's page-locked staging (xivo_hip_life_config)
-    if (c->life_pin[i]) hipHostFree(c->life_pin[i]);
-    if (c->life_ev[i]) hipEventDestroy(c->life_ev[i]);
-    if (c->pcw_pin[i]) hipHostFree(c->pcw_pin[i]);   // the world's pose staging (xivo_hip_pcw_config)
-    if (c->pcw_ev[i]) hipEventDestroy(c->pcw_ev[i]);
-  }
   for (auto& ep : c->pool) { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
   if (c->t0) hipEventDestroy(c->t0);
   if (c->t1) hipEventDestroy(c->t1);

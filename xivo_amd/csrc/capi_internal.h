@@ -7,7 +7,8 @@
 //   capi_score.hip      trajectory score: aligned / unaligned ATE and RPE of the logged poses against ground truth
 //   capi_map.hip        landmark log: per-frame in-state features, world positions and covariances, read-out, landmark NEES
 //   capi_innov.hip      innovation log: per-frame NIS / pre- and post-fit sums of every filter's update, read-out, ensemble sums
-//   capi_lifecycle.hip  device life cycle: the per-filter slot book, the two frame calls around the update, counters
+//   capi_lifecycle.hip  device life cycle: the frame calls around the update, counters; the in-state slot book and the track
+//                       block that both device life cycles use
 //   capi_pool_lifecycle.hip  device pool life cycle ("subfilter" mode): the pool book, the two frame calls, counters
 //   capi_pcw.hip        point-cloud world: the resident worlds, the per-frame track producer, read-back
 //   capi_trajsim.hip    trajectory producer: the simulated IMU records and ground-truth poses of a frame, the ground-truth log
@@ -70,6 +71,26 @@ struct BatchMat {
   BatchMat at(int i, int j) const { return {p + i + (long)j * ld, stride, ld}; }   // the block that starts at (i, j)
   template <class P, class S, class L> void to(P& ptr, S& str, L& l) const { ptr = p; str = stride; l = ld; }
 };
+
+// The in-state slot book of the device life cycle that is configured (capi_lifecycle.hip or capi_pool_lifecycle.hip: the two
+// exclude each other): feat_id [Bmax][ld] (-1: free slot), group_refs [Bmax][n_groups] (-1: free); null until book_alloc
+struct InstateBookBuffers {
+  long long* feat_id = nullptr; int* group_refs = nullptr; int ld = 0;
+};
+
+// The track block of the device life cycle that is configured: one device block that holds a frame's tracks and two page-locked
+// staging blocks of that size, each with the event of its last upload (cur: the one the last upload filled). Two forms share the
+// device block: packed, off [B + 1] | ids [n] | meas [n][3] as track_block_upload leaves them, and strided behind the offsets'
+// space, ids [Bmax][tracks_max] | meas [Bmax][tracks_max][3] with the counts in pcw_cnt, as the track producer (capi_pcw.hip)
+// leaves them. B > 0: a frame is open between a begin and an end call, on n packed tracks or (strided) on the producer's.
+// The track_block_* functions (capi_lifecycle.hip) are its interface; nothing else touches the fields.
+struct TrackBlock {
+  char* dev = nullptr; char* pin[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr};
+  size_t set_bytes = 0;
+  int tracks_max = 0, cur = 0, B = 0, n = 0;
+  bool strided = false;
+};
+
 
 }  // namespace xivo_hip::capi
 
@@ -174,33 +195,28 @@ struct xivo_hip_ctx {
   void dx_set(int b0, int nb, bool v) { if (dx_ok.size() != (size_t)Bmax) dx_ok.assign((size_t)Bmax, 0); std::fill_n(dx_ok.begin() + b0, nb, (char)v); }
   void dx_clear() { std::fill(dx_ok.begin(), dx_ok.end(), (char)0); }
   bool dx_current(int B) const { return dx_ok.size() >= (size_t)B && std::all_of(dx_ok.begin(), dx_ok.begin() + B, [](char v) { return v != 0; }); }
-  // device life cycle (xivo_hip_life_*, capi_lifecycle.hip): the book [Bmax][life_ld] / [Bmax][n_groups] / [Bmax], null until
-  // xivo_hip_life_config; one device block of track storage (the frame between life_begin and life_end, life_B > 0: off | ids |
-  // meas of life_n tracks) and two page-locked staging blocks of that size, each with the event of its last upload; life_cur
-  // is the staging block the last life_begin filled
+  // the device life cycles (capi_lifecycle.hip, capi_pool_lifecycle.hip; at most one of the two is configured): the in-state book
+  // and the track block of whichever is, both null when neither
+  xivo_hip::capi::InstateBookBuffers book;
+  xivo_hip::capi::TrackBlock tracks;
+  // device life cycle (xivo_hip_life_*): its options and counters [Bmax]; life_stats is null until xivo_hip_life_config - "the
+  // immediate life cycle is configured"
   xivo_life_opts life_opts{};
-  long long* life_feat_id = nullptr; int* life_group_refs = nullptr; xivo_life_stats* life_stats = nullptr;
-  int life_ld = 0;
-  char* life_dev = nullptr; char* life_pin[2] = {nullptr, nullptr}; hipEvent_t life_ev[2] = {nullptr, nullptr};
-  size_t life_set_bytes = 0;
-  int life_cur = 0, life_B = 0, life_n = 0;
-  bool life_strided = false;   // the open frame reads the strided form of the track block (xivo_hip_life_begin_tracks)
-  // device pool life cycle (xivo_hip_pool_life_*, capi_pool_lifecycle.hip): the in-state book [Bmax][plife_ld] / [Bmax][n_groups],
-  // the pool book [Bmax][pool_max] / [Bmax][anchor_max], the counters [Bmax], what a frame's kernels hand each other
-  // (slot_track, ent_track, the step's xp / order / n / live); null until xivo_hip_pool_life_config. The track block is the one
-  // above (life_dev, life_pin, life_ev, life_B: the two life cycles exclude each other). plife_frame: the frame counter
+  xivo_life_stats* life_stats = nullptr;
+  // device pool life cycle (xivo_hip_pool_life_*): the pool book [Bmax][pool_max] / [Bmax][anchor_max], the counters [Bmax], what
+  // a frame's kernels hand each other (slot_track, ent_track, the step's xp / order / n / live); null until
+  // xivo_hip_pool_life_config. plife_frame: the frame counter
   bool plife_on = false;
   xivo_pool_life_opts plife_opts{};
-  long long* plife_feat_id = nullptr; int* plife_group_refs = nullptr;
   long long* plife_ent_id = nullptr; int* plife_ent_born = nullptr; int* plife_anc_used = nullptr; int* plife_anc_life = nullptr;
   xivo_pool_life_stats* plife_stats = nullptr;
   int* plife_slot_track = nullptr; int* plife_ent_track = nullptr;
   double* plife_xp = nullptr; int* plife_order = nullptr; int* plife_n = nullptr; unsigned char* plife_live = nullptr;
-  int plife_ld = 0, plife_frame = 0;
+  int plife_frame = 0;
   // point-cloud world (xivo_hip_pcw_*, capi_pcw.hip): the resident worlds Xs [Bmax][npts][3] / ids [Bmax][npts] / next_id [Bmax],
-  // the frame's camera poses [Bmax][12] with two page-locked staging blocks (the scheme of life_pin) and cnt [Bmax]; null until
-  // xivo_hip_pcw_config. The producer writes the strided form of life_dev: pcw_tracks_B is the B whose tracks the block holds
-  // (0: none - a host-track life_begin overwrote them), pcw_fresh whether a life_begin_tracks may still consume them
+  // the frame's camera poses [Bmax][12] with two page-locked staging blocks (the scheme of the track block) and cnt [Bmax]; null until
+  // xivo_hip_pcw_config. The producer writes the strided form of the track block: pcw_tracks_B is the B whose tracks the block
+  // holds (0: none - a host-track life_begin overwrote them), pcw_fresh whether a life_begin_tracks may still consume them
   xivo_pcw_opts pcw_opts{};
   double* pcw_Xs = nullptr; long long* pcw_ids = nullptr; long long* pcw_next_id = nullptr; int* pcw_cnt = nullptr;
   double* pcw_gsc = nullptr; double* pcw_pin[2] = {nullptr, nullptr}; hipEvent_t pcw_ev[2] = {nullptr, nullptr};
@@ -307,19 +323,35 @@ int stage_measurements(xivo_hip_ctx* c, int b0, int nb, int M, const double* dH,
                        const double* dInn, long strideInn, const double* dR, long strideR);
 
 // ---- capi_lifecycle.hip
-// the strided form of the track block life_dev (behind the offsets' space): ids [Bmax][tracks_max], meas [Bmax][tracks_max][3]
-long long* life_strided_ids(xivo_hip_ctx* c);
-double* life_strided_meas(xivo_hip_ctx* c);
-// the track block both device life cycles keep a frame's tracks in (life_dev, two page-locked staging blocks with an event each)
+// the track block (TrackBlock above)
 int track_block_alloc(xivo_hip_ctx* c, int tracks_max);
 void track_block_release(xivo_hip_ctx* c);   // (the stream must be idle)
-bool track_block_frame_ok(int B, const int* off, const long long* ids, const double* meas, int tracks_max);
+inline int track_block_frame(const xivo_hip_ctx* c) { return c->tracks.B; }   // the B of the open frame, 0: none
+inline bool track_block_frame_open(const xivo_hip_ctx* c) { return c->tracks.B != 0; }
+// a frame's packed tracks as the caller hands them: off [B + 1] with off[0] = 0, non-decreasing, no filter above tracks_max; ids /
+// meas present when there is a track
+bool track_block_frame_ok(const xivo_hip_ctx* c, int B, const int* off, const long long* ids, const double* meas);
 int track_block_upload(xivo_hip_ctx* c, int B, const int* off, const long long* ids, const double* meas);
-void track_block_args(xivo_hip_ctx* c, int B, int n, LifeArgs& a);
-// the in-state book of either life cycle (xivo_hip_life_set_book / _get_book on the given device arrays)
-int book_set(xivo_hip_ctx* c, int b0, int nb, const long long* feat_id, long long* d_ids, int ld, int* d_refs);
-int book_get(xivo_hip_ctx* c, int b0, int nb, const long long* d_ids, int ld, const int* d_refs, long long* feat_id,
-             int* feat_ref, int* group_refs);
+// the strided form: row length, ids [Bmax][row], meas [Bmax][row][3]
+inline int track_block_row(const xivo_hip_ctx* c) { return c->tracks.tracks_max; }
+long long* track_block_strided_ids(xivo_hip_ctx* c);
+double* track_block_strided_meas(xivo_hip_ctx* c);
+inline void track_block_use_strided(xivo_hip_ctx* c) { c->tracks.strided = true; c->tracks.n = 0; }   // (an upload: packed again)
+// a frame of B filters opens on the tracks the block holds in the form it is in / closes
+inline void track_block_open_frame(xivo_hip_ctx* c, int B) { c->tracks.B = B; }
+inline void track_block_close_frame(xivo_hip_ctx* c) { c->tracks.B = 0; }
+// the in-state book (InstateBookBuffers above): every slot free / released; xivo_hip_life_set_book / _get_book
+int book_alloc(xivo_hip_ctx* c);   // (enqueues the fill: the caller synchronises)
+void book_release(xivo_hip_ctx* c);
+int book_set(xivo_hip_ctx* c, int b0, int nb, const long long* feat_id);
+int book_get(xivo_hip_ctx* c, int b0, int nb, long long* feat_id, int* feat_ref, int* group_refs);
+// what every frame call of either life cycle checks first: context, layout and poses present, B and F (against the book) in
+// range, the rows of F features fit, no frame open
+bool frame_can_begin(const xivo_hip_ctx* c, int B, int F);
+// what the kernels of either life cycle take of a frame of B filters: P, the scene, the book and the tracks of the open frame in
+// the form they are in; and what their end kernels take of the update
+LifeArgs life_args_common(xivo_hip_ctx* c, int B);
+void life_args_update(xivo_hip_ctx* c, LifeArgs& a);
 
 // ---- capi_pool_lifecycle.hip
 void pool_life_release(xivo_hip_ctx* c);   // everything xivo_hip_pool_life_config allocated (the stream must be idle)

@@ -27,7 +27,7 @@ int pcw_produce(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, 
   a.Xs = c->pcw_Xs; a.ids = c->pcw_ids; a.next_id = c->pcw_next_id; a.gsc = gsc; a.npts = o.npts;
   a.fx = o.fx; a.fy = o.fy; a.cx = o.cx; a.cy = o.cy; a.imw = o.imw; a.imh = o.imh;
   a.noise_px_std = noise_px_std; a.seed = seed; a.frame = frame;
-  a.track_ids = life_strided_ids(c); a.track_meas = life_strided_meas(c); a.cnt = c->pcw_cnt; a.track_ld = c->life_opts.tracks_max;
+  a.track_ids = track_block_strided_ids(c); a.track_meas = track_block_strided_meas(c); a.cnt = c->pcw_cnt; a.track_ld = track_block_row(c);
   c->pcw_tracks_B = 0; c->pcw_fresh = false;   // (whatever the block held is being overwritten)
   {
     // per filter: the points and their ids in, the ids that changed and at most npts tracks of 32 bytes out
@@ -42,7 +42,7 @@ int pcw_produce(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, 
 
 namespace {
 
-bool pcw_ready(const xivo_hip_ctx* c) { return c && c->pcw_Xs && c->life_dev && c->pcw_opts.npts > 0; }
+bool pcw_ready(const xivo_hip_ctx* c) { return c && c->pcw_Xs && track_block_row(c) > 0 && c->pcw_opts.npts > 0; }
 
 }  // namespace
 
@@ -51,11 +51,11 @@ extern "C" {
 int xivo_hip_pcw_config(xivo_hip_ctx* c, const xivo_pcw_opts* o) {
   if (!c || !o || o->struct_size != (int)sizeof(xivo_pcw_opts) || o->npts < 0) return XIVO_HIP_ERR_INVALID;
   if (o->npts > 0) {
-    if (!c->life_feat_id || !c->life_dev || o->npts > c->life_opts.tracks_max) return XIVO_HIP_ERR_INVALID;
+    if (!c->life_stats || o->npts > track_block_row(c)) return XIVO_HIP_ERR_INVALID;
     const double v[6] = {o->fx, o->fy, o->cx, o->cy, o->imw, o->imh};
     for (double x : v) if (!isfinite(x)) return XIVO_HIP_ERR_INVALID;
   }
-  if (c->life_B != 0) return XIVO_HIP_ERR_INVALID;   // an open frame may be reading the producer's tracks
+  if (track_block_frame_open(c)) return XIVO_HIP_ERR_INVALID;   // an open frame may be reading the producer's tracks
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   HIP_TRY(hipStreamSynchronize(c->stream));   // a frame call may still be using the blocks given back here
   pcw_release(c);
@@ -86,7 +86,7 @@ int xivo_hip_pcw_config(xivo_hip_ctx* c, const xivo_pcw_opts* o) {
 
 int xivo_hip_pcw_set_world(xivo_hip_ctx* c, int b0, int nb, const double* Xs, const long long* ids, const long long* next_id) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (bad_range(c, b0, nb) || !pcw_ready(c) || c->life_B != 0 || (nb > 0 && !Xs)) return XIVO_HIP_ERR_INVALID;
+  if (bad_range(c, b0, nb) || !pcw_ready(c) || track_block_frame_open(c) || (nb > 0 && !Xs)) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
   const size_t n = c->pcw_opts.npts;
   std::vector<long long> fill;
@@ -118,7 +118,7 @@ int xivo_hip_pcw_get_world(xivo_hip_ctx* c, int b0, int nb, long long* ids, long
 
 int xivo_hip_pcw_tracks(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, unsigned long long seed,
                         unsigned long long frame) {
-  if (!pcw_ready(c) || B <= 0 || B > c->Bmax || !gsc || c->life_B != 0 || !isfinite(noise_px_std)) return XIVO_HIP_ERR_INVALID;
+  if (!pcw_ready(c) || B <= 0 || B > c->Bmax || !gsc || track_block_frame_open(c) || !isfinite(noise_px_std)) return XIVO_HIP_ERR_INVALID;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   // the staging block the previous frame did not use; it is free once its upload (two frames back) has finished
   const int set = c->pcw_cur ^ 1;
@@ -132,7 +132,7 @@ int xivo_hip_pcw_tracks(xivo_hip_ctx* c, int B, const double* gsc, double noise_
 }
 
 int xivo_hip_pcw_tracks_resident(xivo_hip_ctx* c, int B, double noise_px_std, unsigned long long seed, unsigned long long frame) {
-  if (!pcw_ready(c) || B <= 0 || B > c->Bmax || c->life_B != 0 || !isfinite(noise_px_std) || !c->ts_gsc || c->ts_B != B)
+  if (!pcw_ready(c) || B <= 0 || B > c->Bmax || track_block_frame_open(c) || !isfinite(noise_px_std) || !c->ts_gsc || c->ts_B != B)
     return XIVO_HIP_ERR_INVALID;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   return pcw_produce(c, B, c->ts_gsc, noise_px_std, seed, frame);
@@ -142,16 +142,16 @@ int xivo_hip_pcw_get_tracks(xivo_hip_ctx* c, int b0, int nb, int* cnt, long long
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (bad_range(c, b0, nb) || !pcw_ready(c) || b0 + nb > c->pcw_tracks_B) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
-  const size_t ld = c->life_opts.tracks_max;
+  const size_t ld = track_block_row(c);
   std::vector<int> n((size_t)nb);
   int rc = d2h_rows(c, n.data(), sizeof(int), c->pcw_cnt + b0, sizeof(int), sizeof(int), nb);
   if (rc) return rc;
   if (ids) {
-    rc = d2h_rows(c, ids, ld * sizeof(long long), life_strided_ids(c) + (size_t)b0 * ld, ld * sizeof(long long), ld * sizeof(long long), nb);
+    rc = d2h_rows(c, ids, ld * sizeof(long long), track_block_strided_ids(c) + (size_t)b0 * ld, ld * sizeof(long long), ld * sizeof(long long), nb);
     if (rc) return rc;
   }
   if (meas) {
-    rc = d2h_rows(c, meas, 3 * ld * sizeof(double), life_strided_meas(c) + 3 * (size_t)b0 * ld, 3 * ld * sizeof(double), 3 * ld * sizeof(double), nb);
+    rc = d2h_rows(c, meas, 3 * ld * sizeof(double), track_block_strided_meas(c) + 3 * (size_t)b0 * ld, 3 * ld * sizeof(double), 3 * ld * sizeof(double), nb);
     if (rc) return rc;
   }
   // behind cnt[b] a row holds whatever an earlier frame left: blanked, so that two read-backs compare equal

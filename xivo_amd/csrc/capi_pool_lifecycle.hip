@@ -1,8 +1,9 @@
 // C ABI, device-resident feature life cycle of the "subfilter" mode (include/xivo_hip.h, "the pool life cycle"): configuration,
 // the books' set-up and read-out, the two frame calls and the counters. Host orchestration only - the kernels are in
-// pool_lifecycle_kernels.hip (and pool_kernels.hip for the step), the decisions in pool_lifecycle_device.h. The track block
-// and the in-state book's set-up / read-out are capi_lifecycle.hip's (track_block_*, book_*). Every entry point checks its
-// arguments before it touches the device; the frame calls allocate nothing and do not synchronise the stream.
+// pool_lifecycle_kernels.hip (and pool_kernels.hip for the step), the decisions in pool_lifecycle_device.h. The in-state book,
+// the track block and the frame calls' common check and kernel arguments are capi_lifecycle.hip's (book_*, track_block_*,
+// frame_can_begin, life_args_*). Every entry point checks its arguments before it touches the device; the frame calls
+// allocate nothing and do not synchronise the stream.
 #include <math.h>
 #include <stdint.h>
 
@@ -13,15 +14,10 @@ using namespace xivo_hip::capi;
 
 namespace {
 
-// what the three kernels take: P, the scene, the books, the packed tracks of the frame in the device block
-PoolLifeArgs plife_args(xivo_hip_ctx* c, int B, int n) {
+// what the three kernels take: the common arguments of a frame (P, the scene, the in-state book, the tracks), the pool and its book
+PoolLifeArgs plife_args(xivo_hip_ctx* c, int B) {
   PoolLifeArgs a{};
-  LifeArgs& l = a.life;
-  c->P.to(l.P, l.strideP, l.ldp); l.Np = c->Np; l.lay = c->lay;
-  l.poses = c->poses; l.groups = c->groups; l.feats = c->feats; l.Fmax = c->Fmax; l.F = c->F;
-  l.feat_id = c->plife_feat_id; l.slot_ld = c->plife_ld; l.group_refs = c->plife_group_refs;
-  track_block_args(c, B, n, l);
-  l.invdepth = (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0;
+  a.life = life_args_common(c, B);
   a.pool = c->fpool; a.anchors = c->anchors; a.pool_max = c->pool_max; a.anchor_max = c->anchor_max;
   a.ent_id = c->plife_ent_id; a.ent_born = c->plife_ent_born; a.anc_used = c->plife_anc_used; a.anc_life = c->plife_anc_life;
   a.stats = c->plife_stats;
@@ -52,11 +48,11 @@ int reread_mirrors(xivo_hip_ctx* c) {
 namespace xivo_hip::capi {
 void pool_life_release(xivo_hip_ctx* c) {
   if (!c->plife_on) return;
-  c->mem.release(&c->plife_feat_id, &c->plife_group_refs, &c->plife_ent_id, &c->plife_ent_born, &c->plife_anc_used,
-                 &c->plife_anc_life, &c->plife_stats);
+  c->mem.release(&c->plife_ent_id, &c->plife_ent_born, &c->plife_anc_used, &c->plife_anc_life, &c->plife_stats);
   c->mem.release(&c->plife_slot_track, &c->plife_ent_track, &c->plife_xp, &c->plife_order, &c->plife_n, &c->plife_live);
+  book_release(c);
   track_block_release(c);
-  c->plife_on = false; c->plife_ld = 0; c->plife_frame = 0;
+  c->plife_on = false; c->plife_frame = 0;
   c->plife_opts = xivo_pool_life_opts{};
 }
 }  // namespace xivo_hip::capi
@@ -74,7 +70,7 @@ int xivo_hip_pool_life_config(xivo_hip_ctx* c, const xivo_pool_life_opts* o) {
     pool_life_release(c);
     return rc;
   }
-  if (c->plife_on || !c->fpool || c->life_feat_id || !c->have_layout || !c->poses) return XIVO_HIP_ERR_INVALID;
+  if (c->plife_on || !c->fpool || c->life_stats || !c->have_layout || !c->poses) return XIVO_HIP_ERR_INVALID;
   if (o->max_group_lifetime < 0 || !isfinite(o->initial_z) || !(o->initial_z > 0.0) || (o->adaptive_z && !c->adapt_on))
     return XIVO_HIP_ERR_INVALID;
   for (int i = 0; i < 3; ++i) if (!isfinite(o->std_xyz[i])) return XIVO_HIP_ERR_INVALID;
@@ -90,9 +86,8 @@ int xivo_hip_pool_life_config(xivo_hip_ctx* c, const xivo_pool_life_opts* o) {
   int rc = ensure_gate_buffers(c, 1);   // the resident feature list, so that the frame calls allocate nothing
   if (rc) return rc;
   c->plife_on = true;                   // (pool_life_release gives back whatever the steps below got)
-  const size_t B = c->Bmax, ld = c->lay.n_features, G = c->lay.n_groups, pm = c->pool_max, am = c->anchor_max;
-  rc = c->mem.raw(&c->plife_feat_id, B * ld);
-  if (!rc) rc = c->mem.raw(&c->plife_group_refs, B * G);
+  const size_t B = c->Bmax, ld = c->lay.n_features, pm = c->pool_max, am = c->anchor_max;
+  rc = book_alloc(c);
   if (!rc) rc = c->mem.raw(&c->plife_ent_id, B * pm);
   if (!rc) rc = c->mem.zeroed(&c->plife_ent_born, B * pm);
   if (!rc) rc = c->mem.zeroed(&c->plife_anc_used, B * am);
@@ -105,22 +100,20 @@ int xivo_hip_pool_life_config(xivo_hip_ctx* c, const xivo_pool_life_opts* o) {
   if (!rc) rc = c->mem.raw(&c->plife_n, B);
   if (!rc) rc = c->mem.raw(&c->plife_live, B * pm);
   if (!rc) rc = track_block_alloc(c, o->tracks_max);
-  // all bytes 0xff: every feature slot, group slot and pool entry reads -1 - free
-  if (!rc && hipMemsetAsync(c->plife_feat_id, 0xff, B * ld * sizeof(long long), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
-  if (!rc && hipMemsetAsync(c->plife_group_refs, 0xff, B * G * sizeof(int), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  // all bytes 0xff: every pool entry reads -1 - free
   if (!rc && hipMemsetAsync(c->plife_ent_id, 0xff, B * pm * sizeof(long long), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
   if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
   if (rc) { pool_life_release(c); return rc; }
-  c->plife_ld = (int)ld; c->plife_opts = *o; c->plife_frame = 0;
+  c->plife_opts = *o; c->plife_frame = 0;
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_pool_life_set_book(xivo_hip_ctx* c, int b0, int nb, const long long* feat_id) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (bad_range(c, b0, nb) || !c->plife_on || c->life_B != 0 || c->F <= 0 || c->F > c->plife_ld || (nb > 0 && !feat_id))
+  if (bad_range(c, b0, nb) || !c->plife_on || track_block_frame_open(c) || c->F <= 0 || c->F > c->book.ld || (nb > 0 && !feat_id))
     return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
-  return book_set(c, b0, nb, feat_id, c->plife_feat_id, c->plife_ld, c->plife_group_refs);
+  return book_set(c, b0, nb, feat_id);
 }
 
 int xivo_hip_pool_life_get_book(xivo_hip_ctx* c, int b0, int nb, long long* feat_id, int* feat_ref, int* group_refs,
@@ -129,8 +122,8 @@ int xivo_hip_pool_life_get_book(xivo_hip_ctx* c, int b0, int nb, long long* feat
   if (bad_range(c, b0, nb) || !c->plife_on) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
   if (feat_id || feat_ref || group_refs) {
-    if (c->F <= 0 || c->F > c->plife_ld) return XIVO_HIP_ERR_INVALID;
-    int rc = book_get(c, b0, nb, c->plife_feat_id, c->plife_ld, c->plife_group_refs, feat_id, feat_ref, group_refs);
+    if (c->F <= 0 || c->F > c->book.ld) return XIVO_HIP_ERR_INVALID;
+    int rc = book_get(c, b0, nb, feat_id, feat_ref, group_refs);
     if (rc) return rc;
   }
   const size_t pm = c->pool_max, am = c->anchor_max;
@@ -143,11 +136,7 @@ int xivo_hip_pool_life_get_book(xivo_hip_ctx* c, int b0, int nb, long long* feat
 }
 
 int xivo_hip_pool_life_begin(xivo_hip_ctx* c, int B, int F, const int* off, const long long* ids, const double* meas, int strict) {
-  if (!c || !c->plife_on || !c->fpool || !c->have_layout || !c->poses || B <= 0 || B > c->Bmax || F <= 0 || F > c->plife_ld ||
-      2 * F > c->Mmax || c->life_B != 0)
-    return XIVO_HIP_ERR_INVALID;
-  if (!track_block_frame_ok(B, off, ids, meas, c->plife_opts.tracks_max)) return XIVO_HIP_ERR_INVALID;
-  const int n = off[B];
+  if (!frame_can_begin(c, B, F) || !c->plife_on || !c->fpool || !track_block_frame_ok(c, B, off, ids, meas)) return XIVO_HIP_ERR_INVALID;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   int rc = ensure_gate_buffers(c, F);   // (allocated by pool_life_config: checks F only)
   if (rc) return rc;
@@ -155,7 +144,7 @@ int xivo_hip_pool_life_begin(xivo_hip_ctx* c, int B, int F, const int* off, cons
   if (rc) return rc;
   c->F = F;   // the list length, as xivo_hip_edit_batch / xivo_hip_set_pixels set it
   // the frame counter advances and the frame opens only once everything is enqueued: a failed launch leaves neither behind
-  PoolLifeArgs a = plife_args(c, B, n);
+  PoolLifeArgs a = plife_args(c, B);
   a.frame = c->plife_frame + 1;
   {
     StageTimer st(c, ST_OTHER, 0.0, "pool_life_begin_kernel");
@@ -173,23 +162,21 @@ int xivo_hip_pool_life_begin(xivo_hip_ctx* c, int B, int F, const int* off, cons
     if (launch_pool_life_admit(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
   }
   c->plife_frame += 1;
-  c->life_B = B;
+  track_block_open_frame(c, B);
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_pool_life_end(xivo_hip_ctx* c, int B) {
-  if (!c || !c->plife_on || !c->fpool || B <= 0 || B != c->life_B || !c->mask || c->F <= 0) return XIVO_HIP_ERR_INVALID;
+  if (!c || !c->plife_on || !c->fpool || B <= 0 || B != track_block_frame(c) || !c->mask || c->F <= 0) return XIVO_HIP_ERR_INVALID;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  PoolLifeArgs a = plife_args(c, B, c->life_n);
-  // the inlier mask where the update left it (xivo_hip_get_gate): the layout-faithful gate strides by Fmax, the dense-row gate by F
-  a.life.mask = c->mask; a.life.mask_ld = c->rows.gate_layout() == GateLayout::strided ? c->Fmax : c->F;
-  a.life.status = c->status;
+  PoolLifeArgs a = plife_args(c, B);
+  life_args_update(c, a.life);
   const xivo_pool_life_opts& o = c->plife_opts;
   a.max_group_lifetime = o.max_group_lifetime; a.initial_z = o.initial_z;
   for (int i = 0; i < 3; ++i) a.std_xyz[i] = o.std_xyz[i];
   a.init_z = o.adaptive_z ? c->init_z : nullptr;
   a.cam = c->cam; a.calib = c->calib_on ? c->calib : nullptr; a.cam_dim = c->calib_on ? c->cl.cam_dim : 0;
-  c->life_B = 0;
+  track_block_close_frame(c);
   {
     StageTimer st(c, ST_OTHER, 0.0, "pool_life_end_kernel");
     if (launch_pool_life_end(a, B, c->stream)) return XIVO_HIP_ERR_HIP;

@@ -47,7 +47,7 @@ extern "C" {
 int xivo_hip_trajsim_config(xivo_hip_ctx* c, const xivo_trajsim_opts* o) {
   if (!c || !o || o->struct_size != (int)sizeof(xivo_trajsim_opts) || o->n_max < 0) return XIVO_HIP_ERR_INVALID;
   if (o->n_max > 0 && !opts_ok(o)) return XIVO_HIP_ERR_INVALID;
-  if (c->life_B != 0) return XIVO_HIP_ERR_INVALID;   // an open frame's tracks came from the poses given back here
+  if (track_block_frame_open(c)) return XIVO_HIP_ERR_INVALID;   // an open frame's tracks came from the poses given back here
   const size_t B = (size_t)c->Bmax;
   // (sizes in bytes stay far below 2^63: Bmax, n_max, T_max are ints; the products below are taken in size_t)
   if (o->n_max > 0 && (B * (size_t)o->n_max > ((size_t)1 << 40) / sizeof(xivo_imu_in) || B * (size_t)o->T_max > ((size_t)1 << 40) / 96))
@@ -71,7 +71,7 @@ int xivo_hip_trajsim_config(xivo_hip_ctx* c, const xivo_trajsim_opts* o) {
 
 int xivo_hip_trajsim_set(xivo_hip_ctx* c, int b0, int nb, const int* motion, const double* rate) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (bad_range(c, b0, nb) || !trajsim_ready(c) || c->life_B != 0 || (nb > 0 && (!motion || !rate))) return XIVO_HIP_ERR_INVALID;
+  if (bad_range(c, b0, nb) || !trajsim_ready(c) || track_block_frame_open(c) || (nb > 0 && (!motion || !rate))) return XIVO_HIP_ERR_INVALID;
   for (int b = 0; b < nb; ++b)
     if ((motion[b] != 0 && motion[b] != 1) || !isfinite(rate[b])) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
@@ -82,7 +82,7 @@ int xivo_hip_trajsim_set(xivo_hip_ctx* c, int b0, int nb, const int* motion, con
 }
 
 int xivo_hip_trajsim_frame(xivo_hip_ctx* c, int B, unsigned long long k0, int n) {
-  if (!trajsim_ready(c) || B <= 0 || B > c->Bmax || n < 0 || n > c->ts_opts.n_max || c->life_B != 0) return XIVO_HIP_ERR_INVALID;
+  if (!trajsim_ready(c) || B <= 0 || B > c->Bmax || n < 0 || n > c->ts_opts.n_max || track_block_frame_open(c)) return XIVO_HIP_ERR_INVALID;
   if (c->calib_motion) return XIVO_HIP_ERR_UNSUPPORTED;
   // every record's dt must be positive (xivo_hip_propagate's rule): t_k stops resolving imu_dt far beyond any run's length
   if (n > 0 && (k0 + (unsigned long long)n < k0 || !(trajsim_dt(k0 + 1, c->ts_opts.imu_dt) > 0.0) ||
@@ -151,7 +151,7 @@ int xivo_hip_trajsim_get_gt(xivo_hip_ctx* c, int b0, int nb, int t0, int nt, dou
 int xivo_hip_trajsim_count(xivo_hip_ctx* c) { return trajsim_ready(c) ? c->ts_T : 0; }
 
 int xivo_hip_trajsim_reset(xivo_hip_ctx* c) {
-  if (!trajsim_ready(c) || c->life_B != 0) return XIVO_HIP_ERR_INVALID;
+  if (!trajsim_ready(c) || track_block_frame_open(c)) return XIVO_HIP_ERR_INVALID;
   c->ts_T = 0; c->ts_B = 0; c->ts_n = 0; c->ts_fresh = false;
   return XIVO_HIP_OK;
 }

@@ -1,7 +1,8 @@
 // The per-frame feature life cycle of the "subfilter" mode on the device (gfx950): what SequenceRunner._frame_subfilter
 // (xivo_amd/sequence.py) decides per filter on the host around xivo_hip_pool_step and sends down as xivo_edit_op lists, pixel
 // arrays, anchor slots and xivo_pool_new records. One workgroup of 256 threads per filter; the filter's books, the frame's
-// track ids and the per-slot, per-entry and per-anchor tables in static LDS.
+// track ids and the per-slot, per-entry and per-anchor tables in static LDS. The in-state half (book, track ids, association,
+// removals, pixels) is instate_book_device.h's, shared with lifecycle_kernels.hip; this file keeps what is about entries and anchors.
 //
 //  pool_life_begin_kernel  before the step: Group::IncrementLifetime (src/manager.cpp:36-41), association of tracks with feature
 //                          slots and pool entries, tracker-dropped features leave the state with the groups they leave empty
@@ -19,10 +20,9 @@
 // scene, the pool and the anchors come out bit for bit as from the host life cycle. Nothing crosses workgroups: no atomics on
 // global memory, the counters and the books belong to the filter's own workgroup (LDS atomics only). The tracks are read
 // through life_track_begin / life_track_count (lifecycle_tracks_device.h) alone.
-#include "edit_device.h"
 #include "ekf_kernels.h"
 #include "geometry_device.h"
-#include "lifecycle_tracks_device.h"
+#include "instate_book_device.h"
 #include "pool_device.h"
 #include "pool_lifecycle_device.h"
 
@@ -33,17 +33,12 @@ namespace {
 constexpr int kTracks = XIVO_LIFE_MAX_TRACKS, kSlots = XIVO_LIFE_MAX_SLOTS, kEntries = XIVO_POOL_MAX_ENTRIES,
               kAnchors = XIVO_POOL_LIFE_MAX_ANCHORS;
 
-// the LDS plan of the three kernels: 16 KiB of ids, 8 KiB of per-track flags, 2 + 5 x 1 KiB per-slot tables, 4 + 5 x 2 KiB
-// per-entry tables, 3 x 1 KiB per-anchor tables, 3 x 2 KiB of walk ops = 54 KiB
+// the LDS plan of the three kernels: the in-state book (16 KiB of ids, 2 + 5 x 1 KiB per-slot tables), 8 KiB of per-track
+// flags, 4 + 5 x 2 KiB per-entry tables, 3 x 1 KiB per-anchor tables, 3 x 2 KiB of walk ops = 54 KiB
 struct PoolLifeLds {
-  long long ids[kTracks];      // begin, end: the filter's track ids
-  int fresh[kTracks];          // end: the track is new
-  long long fid[kSlots];       // in-state book: track id by feature slot
-  int fref[kSlots];            // reference group by feature slot (the resident ref_sind)
-  int slot_track[kSlots];      // slot -> track of the frame that feeds it (-1: none)
-  int gref[kSlots];            // in-state book: references by group slot
-  int rm_feat[kSlots], rm_group[kSlots];
+  InstateBook k;               // (ids: begin, end)
   long long eid[kEntries];     // pool book: track id by entry
+  int fresh[kTracks];          // end: the track is new
   int eborn[kEntries];
   int eanc[kEntries];          // anchor by entry (the resident ref_sind of a held entry)
   int etrack[kEntries];        // entry -> track of the frame that feeds it (-1: none)
@@ -51,22 +46,13 @@ struct PoolLifeLds {
   int aused[kAnchors], alife[kAnchors];  // pool book
   int alink[kAnchors];         // group slot by anchor (the resident slot)
   int op_kind[2 * kSlots], op_i0[2 * kSlots], op_i1[2 * kSlots];   // admit: the walk's ops
-  int n_rm_feat, n_rm_group, n_ops, n_dead, n_new, a_new, n_take, n_expired;
+  int n_ops, n_dead, n_new, a_new, n_take, n_expired;
 };
 
-__device__ __forceinline__ void plife_load(const PoolLifeArgs& a, PoolLifeLds& s, int b, int tid) {
-  const LifeArgs& l = a.life;
-  const int F = l.F, G = l.lay.n_groups, pm = a.pool_max, am = a.anchor_max;
-  const long long* book_id = l.feat_id + (long)b * l.slot_ld;
-  const xivo_feat_in* feats = l.feats + (long)b * l.Fmax;
-  for (int j = tid; j < F; j += 256) {
-    const long long id = book_id[j];
-    const int ref = feats[j].ref_sind;
-    s.fid[j] = id;
-    s.fref[j] = (id >= 0 && ref >= 0 && ref < G) ? ref : -1;
-    s.slot_track[j] = -1;
-  }
-  for (int g = tid; g < G; g += 256) s.gref[g] = l.group_refs[(long)b * G + g];
+// the books and the ids of the filter's n tracks come in (n = 0: a kernel that does not look at the ids)
+__device__ __forceinline__ void plife_load(const PoolLifeArgs& a, PoolLifeLds& s, int b, int n, int tid) {
+  const int pm = a.pool_max, am = a.anchor_max;
+  book_load(a.life, s.k, b, tid);
   for (int e = tid; e < pm; e += 256) {
     const long long id = a.ent_id[(long)b * pm + e];
     const int anc = a.pool[(long)b * pm + e].ref_sind;
@@ -80,47 +66,26 @@ __device__ __forceinline__ void plife_load(const PoolLifeArgs& a, PoolLifeLds& s
     s.alife[t] = a.anc_life[(long)b * am + t];
     s.alink[t] = a.anchors[(long)b * am + t].slot;
   }
-}
-__device__ __forceinline__ void plife_load_ids(const PoolLifeArgs& a, PoolLifeLds& s, int b, int n, int tid) {
-  const int k0 = life_track_begin(a.life, b);
-  for (int k = tid; k < n; k += 256) s.ids[k] = a.life.ids[k0 + k];
+  book_load_ids(a.life, s.k, b, n, tid);
 }
 
 // the books go back (the entry's anchor and the anchor's link are resident in the pool and the anchor table themselves)
 __device__ __forceinline__ void plife_store(const PoolLifeArgs& a, const PoolLifeLds& s, int b, int tid) {
-  const LifeArgs& l = a.life;
-  const int F = l.F, G = l.lay.n_groups, pm = a.pool_max, am = a.anchor_max;
-  for (int j = tid; j < F; j += 256) l.feat_id[(long)b * l.slot_ld + j] = s.fid[j];
-  for (int g = tid; g < G; g += 256) l.group_refs[(long)b * G + g] = s.gref[g];
+  const int pm = a.pool_max, am = a.anchor_max;
+  book_store(a.life, s.k, b, tid);
   for (int e = tid; e < pm; e += 256) { a.ent_id[(long)b * pm + e] = s.eid[e]; a.ent_born[(long)b * pm + e] = s.eborn[e]; }
   for (int t = tid; t < am; t += 256) { a.anc_used[(long)b * am + t] = s.aused[t]; a.anc_life[(long)b * am + t] = s.alife[t]; }
 }
 
-// thread 0: slots in rm_feat leave the book, groups left empty go to rm_group and their anchors are unlinked
+// thread 0: groups left empty go to rm_group and their anchors are unlinked
 __device__ __forceinline__ void plife_discard_groups(PoolLifeLds& s, int G, int am) {
-  s.n_rm_group = life_discard_empty_groups(s.gref, G, s.rm_group);
-  for (int q = 0; q < s.n_rm_group; ++q)
-    for (int t = 0; t < am; ++t) plife_unlink(s.alink, t, s.rm_group[q]);
+  book_discard_empty_groups(s.k, G);
+  for (int q = 0; q < s.k.n_rm_group; ++q)
+    for (int t = 0; t < am; ++t) plife_unlink(s.alink, t, s.k.rm_group[q]);
 }
 
-// the op list's XIVO_EDIT_REMOVE_FEATURE of every slot in rm_feat, then XIVO_EDIT_REMOVE_GROUP of every slot in rm_group
 __device__ __forceinline__ void plife_apply_removals(const PoolLifeArgs& a, const PoolLifeLds& s, int b, int tid) {
-  const LifeArgs& l = a.life;
-  double* P = l.P + (long)b * l.strideP;
-  xivo_feat_in* feats = l.feats + (long)b * l.Fmax;
-  for (int q = 0; q < s.n_rm_feat; ++q) {
-    const int j = s.rm_feat[q];
-    const int sind = feats[j].sind;
-    __syncthreads();
-    if (sind >= 0) {
-      if (sind < l.lay.n_features) edit_zero_rc(P, l.ldp, l.Np, l.lay.feature_begin + 3 * sind, 3, tid);
-      if (tid == 0) feats[j].sind = -1;
-      __syncthreads();
-    }
-  }
-  for (int q = 0; q < s.n_rm_group; ++q)
-    edit_remove_group(P, l.ldp, l.Np, l.lay, l.groups + (long)b * l.lay.n_groups, a.anchors + (long)b * a.anchor_max, a.anchor_max,
-                      s.rm_group[q], tid);
+  book_apply_removals(a.life, s.k, b, a.anchors + (long)b * a.anchor_max, a.anchor_max, tid);
 }
 
 __global__ __launch_bounds__(256) void pool_life_begin_kernel(PoolLifeArgs a) {
@@ -128,28 +93,19 @@ __global__ __launch_bounds__(256) void pool_life_begin_kernel(PoolLifeArgs a) {
   const LifeArgs& l = a.life;
   const int b = blockIdx.x, tid = threadIdx.x, F = l.F, G = l.lay.n_groups, pm = a.pool_max, am = a.anchor_max;
   const int k0 = life_track_begin(l, b), n = life_track_count(l, b);
-  plife_load(a, s, b, tid);
-  plife_load_ids(a, s, b, n, tid);
+  plife_load(a, s, b, n, tid);
   __syncthreads();
   for (int t = tid; t < am; t += 256) s.alife[t] = plife_anchor_tick(s.aused[t], s.alife[t]);
-  // association: one thread per track scans the in-state ids and the pool's; of a repeated id the last occurrence feeds
-  for (int k = tid; k < n; k += 256) {
-    const long long id = s.ids[k];
-    for (int j = 0; j < F; ++j)
-      if (life_slot_holds(s.fid, j, id)) atomicMax(&s.slot_track[j], k);
+  // association: one thread per track scans the in-state ids, then the pool's; of a repeated id the last occurrence feeds
+  book_associate(s.k, F, n, tid);
+  for (int k = tid; k < n; k += 256)
     for (int e = 0; e < pm; ++e)
-      if (plife_entry_holds(s.eid, e, id)) atomicMax(&s.etrack[e], k);
-  }
+      if (plife_entry_holds(s.eid, e, s.k.ids[k])) atomicMax(&s.etrack[e], k);
   __syncthreads();
-  if (tid == 0) {   // ProcessTracks (src/manager.cpp:152-169): a few dozen slots, serial
-    int n_rm = 0;
-    for (int j = 0; j < F; ++j) {
-      if (s.fid[j] < 0 || s.slot_track[j] >= 0) continue;
-      s.rm_feat[n_rm++] = j; life_drop_feature(s.fid, s.fref, s.gref, j);
-    }
-    s.n_rm_feat = n_rm;
+  if (tid == 0) {   // ProcessTracks (src/manager.cpp:152-169)
+    book_drop_where(s.k, F, [&](int j) { return s.k.slot_track[j] < 0; });
     plife_discard_groups(s, G, am);
-    a.stats[b].dropped += n_rm;
+    a.stats[b].dropped += s.k.n_rm_feat;
   }
   // the pool's side (:171-250): an entry without a track is freed; the step frees the resident entry on the NaN it gets
   for (int e = tid; e < pm; e += 256) {
@@ -160,7 +116,7 @@ __global__ __launch_bounds__(256) void pool_life_begin_kernel(PoolLifeArgs a) {
     a.ent_track[(long)b * pm + e] = leaves ? -1 : s.etrack[e];
   }
   __syncthreads();
-  for (int j = tid; j < F; j += 256) a.slot_track[(long)b * l.slot_ld + j] = s.fid[j] >= 0 ? s.slot_track[j] : -1;
+  for (int j = tid; j < F; j += 256) a.slot_track[(long)b * l.slot_ld + j] = s.k.fid[j] >= 0 ? s.k.slot_track[j] : -1;
   plife_apply_removals(a, s, b, tid);
   plife_store(a, s, b, tid);
 }
@@ -171,11 +127,10 @@ __global__ __launch_bounds__(256) void pool_life_admit_kernel(PoolLifeArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x, F = l.F, G = l.lay.n_groups, pm = a.pool_max, am = a.anchor_max;
   double* P = l.P + (long)b * l.strideP;
   xivo_feat_in* feats = l.feats + (long)b * l.Fmax;
-  const int k0 = life_track_begin(l, b);
-  plife_load(a, s, b, tid);
+  plife_load(a, s, b, 0, tid);
   if (tid == 0) s.n_dead = 0;
   __syncthreads();
-  for (int j = tid; j < F; j += 256) s.slot_track[j] = a.slot_track[(long)b * l.slot_ld + j];
+  for (int j = tid; j < F; j += 256) s.k.slot_track[j] = a.slot_track[(long)b * l.slot_ld + j];
   for (int e = tid; e < pm; e += 256) {
     s.etrack[e] = a.ent_track[(long)b * pm + e];
     if (plife_free_if_dead(s.eid, s.eanc, e, a.live[(long)b * pm + e])) atomicAdd(&s.n_dead, 1);   // (:236-240)
@@ -186,9 +141,9 @@ __global__ __launch_bounds__(256) void pool_life_admit_kernel(PoolLifeArgs a) {
     long long steps = 0;
     int n = a.n[b];
     n = n < 0 ? 0 : (n > pm ? pm : n);
-    s.n_ops = plife_walk(a.order + (long)b * pm, n, a.frame, s.fid, s.fref, s.gref, F, G, s.eid, s.eanc, s.eborn, s.etrack, pm,
-                         s.alink, am, s.slot_track, s.op_kind, s.op_i0, s.op_i1, &n_adm, &n_gadd, &steps);
-    for (int j = 0; j < F; ++j) n_in += s.fid[j] >= 0 ? 1 : 0;
+    s.n_ops = plife_walk(a.order + (long)b * pm, n, a.frame, s.k.fid, s.k.fref, s.k.gref, F, G, s.eid, s.eanc, s.eborn, s.etrack, pm,
+                         s.alink, am, s.k.slot_track, s.op_kind, s.op_i0, s.op_i1, &n_adm, &n_gadd, &steps);
+    for (int j = 0; j < F; ++j) n_in += s.k.fid[j] >= 0 ? 1 : 0;
     xivo_pool_life_stats& st = a.stats[b];
     st.pool_outliers += s.n_dead;
     st.admitted += n_adm; st.groups_added += n_gadd; st.admit_steps += steps;
@@ -202,15 +157,7 @@ __global__ __launch_bounds__(256) void pool_life_admit_kernel(PoolLifeArgs a) {
       edit_admit_pool(P, l.ldp, l.Np, l.lay, feats, a.pool[(long)b * pm + s.op_i1[o]], a.anchors + (long)b * am, s.op_i0[o],
                       s.op_i0[o], tid);
   }
-  // every in-state feature, those just admitted included, takes the frame's pixel (xivo_hip_set_pixels: a NaN pair leaves the
-  // entry as it is)
-  for (int j = tid; j < F; j += 256) {
-    if (s.fid[j] < 0 || s.slot_track[j] < 0) continue;
-    const double* m = l.meas + 3 * (long)(k0 + s.slot_track[j]);
-    const double u = m[0], v = m[1];
-    if (u != u || v != v) continue;
-    feats[j].xp[0] = u; feats[j].xp[1] = v;
-  }
+  book_take_pixels(l, s.k, b, tid);   // every in-state feature, those just admitted included
   plife_store(a, s, b, tid);
 }
 
@@ -219,30 +166,24 @@ __global__ __launch_bounds__(256) void pool_life_end_kernel(PoolLifeArgs a) {
   const LifeArgs& l = a.life;
   const int b = blockIdx.x, tid = threadIdx.x, F = l.F, G = l.lay.n_groups, pm = a.pool_max, am = a.anchor_max;
   const int k0 = life_track_begin(l, b), n = life_track_count(l, b);
-  plife_load(a, s, b, tid);
-  plife_load_ids(a, s, b, n, tid);
+  plife_load(a, s, b, n, tid);
   __syncthreads();
   if (tid == 0) {
     // gate-rejected features leave (src/update.cpp:105-113); their tracks are new tracks again
-    int n_rm = 0;
-    for (int j = 0; j < F; ++j) {
-      if (s.fid[j] < 0 || l.mask[(long)b * l.mask_ld + j]) continue;
-      s.rm_feat[n_rm++] = j; life_drop_feature(s.fid, s.fref, s.gref, j);
-    }
-    s.n_rm_feat = n_rm;
+    book_drop_where(s.k, F, [&](int j) { return !l.mask[(long)b * l.mask_ld + j]; });
     plife_discard_groups(s, G, am);
     s.n_new = 0; s.a_new = -1; s.n_take = 0; s.n_expired = 0;
     xivo_pool_life_stats& st = a.stats[b];
-    st.rejected += n_rm;
+    st.rejected += s.k.n_rm_feat;
     st.not_spd += (l.status && l.status[b]) ? 1 : 0;
   }
   __syncthreads();
   plife_apply_removals(a, s, b, tid);
   // new tracks: in neither the state nor the pool, the first occurrence of their id
-  for (int k = tid; k < n; k += 256) s.fresh[k] = plife_is_unheld(s.fid, F, s.eid, pm, s.ids[k]) ? 1 : 0;
+  for (int k = tid; k < n; k += 256) s.fresh[k] = plife_is_unheld(s.k.fid, F, s.eid, pm, s.k.ids[k]) ? 1 : 0;
   __syncthreads();
   for (int k = tid; k < n; k += 256)   // (an earlier occurrence is unheld exactly when this one is: same id)
-    if (s.fresh[k] && !plife_first_occurrence(s.ids, k)) s.fresh[k] = 2;
+    if (s.fresh[k] && !plife_first_occurrence(s.k.ids, k)) s.fresh[k] = 2;
   __syncthreads();
   for (int k = tid; k < n; k += 256) s.fresh[k] = s.fresh[k] == 1 ? 1 : 0;
   __syncthreads();
@@ -250,7 +191,7 @@ __global__ __launch_bounds__(256) void pool_life_end_kernel(PoolLifeArgs a) {
   for (int k = tid; k < n; k += 256) {
     if (!s.fresh[k]) continue;
     atomicAdd(&s.n_new, 1);
-    const int r = life_rank(s.ids, s.fresh, n, k);
+    const int r = life_rank(s.k.ids, s.fresh, n, k);
     if (r < pm) s.pick[r] = k;
   }
   __syncthreads();
@@ -262,7 +203,7 @@ __global__ __launch_bounds__(256) void pool_life_end_kernel(PoolLifeArgs a) {
     if (an >= 0) {
       plife_create_anchor(s.aused, s.alife, s.alink, an);
       const int n_take = n_free < s.n_new ? n_free : s.n_new;
-      for (int q = 0; q < n_take; ++q) plife_take_entry(s.eid, s.eanc, s.eborn, s.efree[q], s.ids[s.pick[q]], an, a.frame);
+      for (int q = 0; q < n_take; ++q) plife_take_entry(s.eid, s.eanc, s.eborn, s.efree[q], s.k.ids[s.pick[q]], an, a.frame);
       s.a_new = an; s.n_take = n_take;
       st.anchors_created += 1; st.pool_added += n_take;
     }

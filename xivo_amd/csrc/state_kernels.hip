@@ -87,7 +87,7 @@ __global__ void p_diag_kernel(const double* P, int ldp, int N, double* out) {
 }
 
 // ---------------------------------------------------------------- batched resident edits (xivo_hip_edit_batch)
-// (edit_zero_rc / edit_copy_rc: edit_device.h, shared with the device life cycle)
+// (every edit is a function of edit_device.h, shared with the device life cycles)
 // xivo_hip_set_pixels: one thread per (filter, list entry)
 __global__ void set_pixels_kernel(xivo_feat_in* feats, int Fmax, int F, const double* xp, int n) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -110,44 +110,15 @@ __global__ __launch_bounds__(256) void edit_batch_kernel(EditArgs a) {
     switch (op.kind) {
       case XIVO_EDIT_P_ZERO_RC: edit_zero_rc(P, a.ldp, a.Np, op.i0, op.i1, tid); break;
       case XIVO_EDIT_P_COPY_RC: edit_copy_rc(P, a.ldp, a.Np, op.i0, op.i1, op.i2, tid); break;
-      case XIVO_EDIT_P_SET_BLOCK3:
-        if (tid < 9) P[(op.i0 + tid % 3) + (long)(op.i0 + tid / 3) * a.ldp] = op.v[tid];
-        __syncthreads();
-        break;
-      case XIVO_EDIT_ADD_GROUP: {
-        if (tid < 9) groups[op.i0].Rsb[tid] = X.Rsb[tid];
-        else if (tid < 12) groups[op.i0].Tsb[tid - 9] = X.Tsb[tid - 9];
-        const int off = a.lay.group_begin + 6 * op.i0;
-        edit_copy_rc(P, a.ldp, a.Np, off, 0, 3, tid);       // Index::Wsb
-        edit_copy_rc(P, a.ldp, a.Np, off + 3, 3, 3, tid);   // Index::Tsb
-        break;
-      }
+      case XIVO_EDIT_P_SET_BLOCK3: edit_set_block3(P, a.ldp, op.i0, tid < 9 ? op.v[tid] : 0.0, tid); break;
+      case XIVO_EDIT_ADD_GROUP: edit_add_group(P, a.ldp, a.Np, a.lay, groups, X.Rsb, X.Tsb, op.i0, tid); break;
       case XIVO_EDIT_REMOVE_GROUP:
         edit_remove_group(P, a.ldp, a.Np, a.lay, groups, a.anchors + (long)filt * a.anchor_max, a.anchor_max, op.i0, tid);
         break;
-      case XIVO_EDIT_ADD_FEATURE: {
-        if (tid == 0) {
-          xivo_feat_in& f = feats[op.i0];
-          f.x[0] = op.v[0]; f.x[1] = op.v[1]; f.x[2] = op.v[2];
-          f.xp[0] = op.v[3]; f.xp[1] = op.v[4];
-          f.sind = op.i1; f.ref_sind = op.i2;
-        }
-        const int off = a.lay.feature_begin + 3 * op.i1;
-        edit_zero_rc(P, a.ldp, a.Np, off, 3, tid);
-        if (tid < 9) P[(off + tid % 3) + (long)(off + tid / 3) * a.ldp] = op.v[5 + tid];
-        __syncthreads();
+      case XIVO_EDIT_ADD_FEATURE:
+        edit_add_feature(P, a.ldp, a.Np, a.lay, feats[op.i0], op.v, op.v + 3, op.i1, op.i2, tid < 9 ? op.v[5 + tid] : 0.0, tid);
         break;
-      }
-      case XIVO_EDIT_REMOVE_FEATURE: {
-        const int sind = feats[op.i0].sind;
-        __syncthreads();
-        if (sind >= 0) {
-          edit_zero_rc(P, a.ldp, a.Np, a.lay.feature_begin + 3 * sind, 3, tid);
-          if (tid == 0) feats[op.i0].sind = -1;
-          __syncthreads();
-        }
-        break;
-      }
+      case XIVO_EDIT_REMOVE_FEATURE: edit_remove_feature(P, a.ldp, a.Np, a.lay, feats, op.i0, tid); break;
       case XIVO_EDIT_SET_XP:
         if (tid < 2) feats[op.i0].xp[tid] = op.v[tid];
         __syncthreads();

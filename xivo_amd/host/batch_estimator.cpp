@@ -284,9 +284,8 @@ void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_
   for (int b = 0; b < B_; ++b) n_updates_ += books_[b].id2slot.empty() ? 0 : 1;
   // --- after the update: MH-rejected features leave (src/update.cpp:105-113), new ones enter with a new group
   const double fx = cfg_.cam.fx, fy = cfg_.cam.fy, cx = cfg_.cam.cx, cy = cfg_.cam.cy;
-  // Camera::GetFocalLength() = 0.5 sqrt(fx^2 + fy^2) (src/camera_manager.cpp:56, src/estimator.cpp:351-352)
-  const double fl = 0.5 * std::sqrt(fx * fx + fy * fy);
-  const double sd[3] = {cfg_.initial_std_x / fl, cfg_.initial_std_y / fl, cfg_.initial_std_z};
+  double sd[3];
+  NewTrackStd(false, sd);
   long rejected = 0;
 #pragma omp parallel for schedule(static) reduction(+ : rejected) num_threads(kThreads) if (B_ >= 512)
   for (int b = 0; b < B_; ++b) {
@@ -337,6 +336,17 @@ void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_
   if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
 }
 
+// the initial std of a new feature's (x, y, depth): pixels over Camera::GetFocalLength() = 0.5 sqrt(fx^2 + fy^2)
+// (src/camera_manager.cpp:56, src/estimator.cpp:351-352). badtri: a new track of the pool is never triangulated yet and takes
+// the badtri stds (src/manager.cpp:585-586)
+void BatchEstimator::NewTrackStd(bool badtri, double sd[3]) const {
+  const double fx = cfg_.cam.fx, fy = cfg_.cam.fy;
+  const double fl = 0.5 * std::sqrt(fx * fx + fy * fy);
+  const double px[3] = {badtri ? dc_.std_badtri[0] : cfg_.initial_std_x, badtri ? dc_.std_badtri[1] : cfg_.initial_std_y,
+                        badtri ? dc_.std_badtri[2] : cfg_.initial_std_z};
+  sd[0] = px[0] / fl; sd[1] = px[1] / fl; sd[2] = px[2];
+}
+
 void BatchEstimator::EnableSubfilter(const SubfilterConfig& sc) {
   if (device_life_) throw std::runtime_error("the device life cycle runs the immediate mode only");
   if (device_pool_life_) throw std::runtime_error("EnableSubfilter would empty the pool under the device pool life cycle");
@@ -365,9 +375,8 @@ void BatchEstimator::EnableDeviceLifecycle(int tracks_max) {
     Check(xivo_hip_life_config(ctx_, &off), "life_config");
     return;
   }
-  const double fx = cfg_.cam.fx, fy = cfg_.cam.fy;
-  const double fl = 0.5 * std::sqrt(fx * fx + fy * fy);   // Camera::GetFocalLength() (src/camera_manager.cpp:56)
-  const double sd[3] = {cfg_.initial_std_x / fl, cfg_.initial_std_y / fl, cfg_.initial_std_z};
+  double sd[3];
+  NewTrackStd(false, sd);
   xivo_life_opts o;
   std::memset(&o, 0, sizeof(o));
   o.tracks_max = tracks_max; o.min_new_features = cfg_.min_new_features;
@@ -387,17 +396,11 @@ void BatchEstimator::EnableDevicePoolLifecycle(int tracks_max) {
   if (!subfilter_) throw std::runtime_error("the device pool life cycle needs EnableSubfilter first");
   if (device_life_) throw std::runtime_error("the device pool life cycle excludes the immediate device life cycle");
   if (device_pool_life_ || vision_counter_ > 0) throw std::runtime_error("the device pool life cycle starts on an empty pool, once");
-  const double fx = cfg_.cam.fx, fy = cfg_.cam.fy;
-  const double fl = 0.5 * std::sqrt(fx * fx + fy * fy);   // Camera::GetFocalLength() (src/camera_manager.cpp:56)
   xivo_pool_life_opts o;
   std::memset(&o, 0, sizeof(o));
   o.struct_size = (int)sizeof(o); o.tracks_max = tracks_max; o.max_group_lifetime = sc_.max_group_lifetime;
   o.adaptive_z = dc_.adaptive ? 1 : 0; o.initial_z = sc_.initial_z;
-  if (dc_.triangulate) {  // a new track is never triangulated yet: the badtri stds (manager.cpp:585-586)
-    o.std_xyz[0] = dc_.std_badtri[0] / fl; o.std_xyz[1] = dc_.std_badtri[1] / fl; o.std_xyz[2] = dc_.std_badtri[2];
-  } else {
-    o.std_xyz[0] = cfg_.initial_std_x / fl; o.std_xyz[1] = cfg_.initial_std_y / fl; o.std_xyz[2] = cfg_.initial_std_z;
-  }
+  NewTrackStd(dc_.triangulate, o.std_xyz);
   if (tracks_max <= 0) throw std::runtime_error("tracks_max must be positive");
   Check(xivo_hip_pool_life_config(ctx_, &o), "pool_life_config");
   device_pool_life_ = true;
@@ -422,6 +425,11 @@ void BatchEstimator::VisualMeasDeviceWorld(double t, const double* gsc, double n
   want_mask_ = mask_out != nullptr;
   // the frame's tracks are produced where the life cycle reads them: 96 bytes per filter go down, nothing comes back
   Check(xivo_hip_pcw_tracks(ctx_, B_, gsc, noise_px_std, seed, world_frame_++), "pcw_tracks");
+  FrameOnProducedTracks(mask_out);
+}
+
+// the rest of a frame whose tracks the producer left in the track block
+void BatchEstimator::FrameOnProducedTracks(unsigned char* mask_out) {
   Check(xivo_hip_life_begin_tracks(ctx_, B_, cfg_.n_features), "life_begin_tracks");
   RunUpdate();
   Check(xivo_hip_life_end(ctx_, B_), "life_end");
@@ -444,10 +452,7 @@ void BatchEstimator::FrameResident(unsigned long long k0, int n, double noise_px
   Check(xivo_hip_trajsim_frame(ctx_, B_, k0, n), "trajsim_frame");
   if (n > 0) Check(xivo_hip_propagate_resident(ctx_, B_, &cfg_.prop), "propagate_resident");
   Check(xivo_hip_pcw_tracks_resident(ctx_, B_, noise_px_std, seed, world_frame_++), "pcw_tracks_resident");
-  Check(xivo_hip_life_begin_tracks(ctx_, B_, cfg_.n_features), "life_begin_tracks");
-  RunUpdate();
-  Check(xivo_hip_life_end(ctx_, B_), "life_end");
-  if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
+  FrameOnProducedTracks(mask_out);
 }
 
 void BatchEstimator::ReadBook(int b) {
@@ -591,7 +596,8 @@ void BatchEstimator::VisualSubfilter(const int* off, const int64_t* ids, const d
   }
   Check(xivo_hip_edit_batch(ctx_, F, (int)ops.size(), ops.empty() ? nullptr : ops.data()), "edit_batch");
   // --- Group::Create(X_.Rsb, X_.Tsb) from the updated pose + InitializeJustCreatedTracks (:121-126, :575-600)
-  const double fl = 0.5 * std::sqrt(cfg_.cam.fx * cfg_.cam.fx + cfg_.cam.fy * cfg_.cam.fy);
+  double new_std[3];
+  NewTrackStd(dc_.triangulate, new_std);
   std::vector<int> slots(B_, -1);
   std::vector<xivo_pool_new> recs;
   for (int b = 0; b < B_; ++b) {
@@ -616,11 +622,7 @@ void BatchEstimator::VisualSubfilter(const int* off, const int64_t* ids, const d
       r.b = b; r.entry = e; r.anchor = a;
       r.xp[0] = meas[(size_t)k * 3]; r.xp[1] = meas[(size_t)k * 3 + 1];
       r.z0 = sc_.initial_z;   // (ignored under adaptive_initial_depth: the device's resident init_z)
-      if (dc_.triangulate) {  // a new track is never triangulated yet: the badtri stds (manager.cpp:585-586)
-        r.std_xyz[0] = dc_.std_badtri[0] / fl; r.std_xyz[1] = dc_.std_badtri[1] / fl; r.std_xyz[2] = dc_.std_badtri[2];
-      } else {
-        r.std_xyz[0] = cfg_.initial_std_x / fl; r.std_xyz[1] = cfg_.initial_std_y / fl; r.std_xyz[2] = cfg_.initial_std_z;
-      }
+      for (int i = 0; i < 3; ++i) r.std_xyz[i] = new_std[i];
       recs.push_back(r);
       pb.ent_id[e] = ids[k]; pb.ent_anchor[e] = a; pb.ent_born[e] = vision_counter_; pb.id2ent[ids[k]] = e;
     }

@@ -146,6 +146,8 @@ class BatchEstimator {
   void DropFeature(Book& bk, int j);
   void DiscardEmptyGroups(int b, std::vector<xivo_edit_op>& ops);
   void RunUpdate();
+  void FrameOnProducedTracks(unsigned char* mask_out);   // life_begin_tracks -> update -> life_end (-> mask)
+  void NewTrackStd(bool badtri, double sd[3]) const;
   void PropagateToFrame(double t, double& t0);
   void VisualSubfilter(const int* off, const int64_t* ids, const double* meas);
   void ReadBook(int b);                 // device life cycle: books_[b] <- xivo_hip_life_get_book

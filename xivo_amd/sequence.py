@@ -735,94 +735,67 @@ class SequenceRunner:
             ids, meas = np.zeros(0, dtype=np.int64), np.zeros((0, 3))
         return off, ids, meas
 
-    def _frame_subfilter_device(self, imu, tracks):
-        """one camera frame of the "subfilter" life cycle with the decisions on the device: propagate -> pool_life_begin (begin
-        kernel, pool step, admit kernel) -> update -> pool_life_end (end kernel, AdaptInitialDepth). No per-filter work here
-        and nothing is downloaded (unless want_mask); `admitted` stays empty - the counters admitted / admit_steps of
-        pool_life_stats stand for it."""
+    def _device_frame(self, produce, begin, end):
+        """one camera frame with the life cycle on the device: produce -> begin -> update -> end. produce: the (timer name, call)
+        steps that bring the IMU records and the tracks to where the begin call reads them; begin / end: the pair of the life
+        cycle. No per-feature work here and nothing is downloaded (unless want_mask)."""
         import time
-        be = self.be
-        self.vision_counter += 1
         t0 = time.perf_counter()
-        if imu is not None:
-            be.propagate(imu)
-        t0 = self._tick("propagate", t0) or t0
-        off, ids, meas = self._pack_tracks(tracks)
-        t0 = self._tick("host_pre", t0) or t0
-        be.pool_life_begin(off, ids, meas, self.vision_counter >= self.cfg.strict_criteria_timesteps)
+        for name, step in produce:
+            step()
+            t0 = self._tick(name, t0) or t0
+        begin()
         t0 = self._tick("edit", t0) or t0
-        mask = be.update(download=self.want_mask)
+        mask = self.be.update(download=self.want_mask)
         t0 = self._tick("update", t0) or t0
-        be.pool_life_end()
+        end()
         self._tick("edit", t0)
         return mask
 
-    def _frame_device(self, imu, tracks):
-        """one camera frame with the life cycle on the device: the tracks of all filters go down in the off / ids / meas layout
-        of xivo_batch_visual, then life_begin -> update -> life_end. No per-feature work here and nothing is downloaded
-        (unless want_mask)."""
-        import time
+    def _frame_host_tracks(self, imu, tracks, begin, end):
+        """_device_frame on host data: the IMU records go to propagate, the tracks of all filters go down in the off / ids /
+        meas layout of xivo_batch_visual as begin(off, ids, meas)"""
+        be, packed = self.be, []
+        return self._device_frame([("propagate", lambda: imu is not None and be.propagate(imu)),
+                                   ("host_pre", lambda: packed.extend(self._pack_tracks(tracks)))],
+                                  lambda: begin(*packed), end)
+
+    def _frame_subfilter_device(self, imu, tracks):
+        """one camera frame of the "subfilter" life cycle with the decisions on the device: propagate -> pool_life_begin (begin
+        kernel, pool step, admit kernel) -> update -> pool_life_end (end kernel, AdaptInitialDepth). `admitted` stays empty -
+        the counters admitted / admit_steps of pool_life_stats stand for it."""
         be = self.be
-        t0 = time.perf_counter()
-        if imu is not None:
-            be.propagate(imu)
-        t0 = self._tick("propagate", t0) or t0
-        off, ids, meas = self._pack_tracks(tracks)
-        t0 = self._tick("host_pre", t0) or t0
-        be.life_begin(off, ids, meas)
-        t0 = self._tick("edit", t0) or t0
-        mask = be.update(download=self.want_mask)
-        t0 = self._tick("update", t0) or t0
-        be.life_end()
-        self._tick("edit", t0)
-        return mask
+        self.vision_counter += 1
+        strict = self.vision_counter >= self.cfg.strict_criteria_timesteps
+        return self._frame_host_tracks(imu, tracks, lambda *t: be.pool_life_begin(*t, strict), be.pool_life_end)
+
+    def _frame_device(self, imu, tracks):
+        """one camera frame of the "immediate" life cycle on the device: propagate -> life_begin -> update -> life_end"""
+        return self._frame_host_tracks(imu, tracks, self.be.life_begin, self.be.life_end)
 
     def frame_world(self, imu, gsc, frame):
         """one camera frame whose tracks the device produces (track_source="device"): gsc [B, 12] the ground-truth camera pose
         of every filter (Rsc row-major, Tsc), frame the frame's number (the noise generator's counter). propagate -> pcw_tracks
         -> life_begin_tracks -> update -> life_end; nothing but the poses goes down and nothing comes back (unless want_mask)."""
-        import time
         if self.cfg.track_source != "device":
             raise ValueError("frame_world needs track_source='device'")
         be = self.be
-        t0 = time.perf_counter()
-        if imu is not None:
-            be.propagate(imu)
-        t0 = self._tick("propagate", t0) or t0
-        be.make_tracks(gsc, self.noise_px_std, self.noise_seed, frame)
-        t0 = self._tick("tracks", t0) or t0
-        be.life_begin_tracks()
-        t0 = self._tick("edit", t0) or t0
-        mask = be.update(download=self.want_mask)
-        t0 = self._tick("update", t0) or t0
-        be.life_end()
-        self._tick("edit", t0)
-        return mask
+        return self._device_frame([("propagate", lambda: imu is not None and be.propagate(imu)),
+                                   ("tracks", lambda: be.make_tracks(gsc, self.noise_px_std, self.noise_seed, frame))],
+                                  be.life_begin_tracks, be.life_end)
 
     def frame_resident(self, k0, n, frame):
         """one camera frame at IMU sample k0 + n that takes no host data (imu_source="device"): the device produces the records
         k0 + 1 .. k0 + n and the ground-truth poses (make_imu), propagates over them, produces the tracks from the poses and
         runs the life cycle and the update; n = 0: the frame at t = 0, nothing to propagate. frame: the pixel noise
         generator's counter. Nothing is downloaded (unless want_mask)."""
-        import time
         if getattr(self.cfg, "imu_source", "host") != "device":
             raise ValueError("frame_resident needs imu_source='device'")
         be = self.be
-        t0 = time.perf_counter()
-        be.make_imu(k0, n)
-        t0 = self._tick("imu", t0) or t0
-        if n > 0:
-            be.propagate_resident()
-        t0 = self._tick("propagate", t0) or t0
-        be.make_tracks_resident(self.noise_px_std, self.noise_seed, frame)
-        t0 = self._tick("tracks", t0) or t0
-        be.life_begin_tracks()
-        t0 = self._tick("edit", t0) or t0
-        mask = be.update(download=self.want_mask)
-        t0 = self._tick("update", t0) or t0
-        be.life_end()
-        self._tick("edit", t0)
-        return mask
+        return self._device_frame([("imu", lambda: be.make_imu(k0, n)),
+                                   ("propagate", lambda: n > 0 and be.propagate_resident()),
+                                   ("tracks", lambda: be.make_tracks_resident(self.noise_px_std, self.noise_seed, frame))],
+                                  be.life_begin_tracks, be.life_end)
 
     def _tick(self, name, t0):
         if self.timers is None:
