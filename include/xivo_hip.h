@@ -971,7 +971,9 @@ int xivo_hip_life_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_life_stats* out)
  * anc_used[anchor_max], anc_life[anchor_max] (Group::lifetime). An entry's anchor is the resident entry's ref_sind, an anchor's
  * link the resident anchor's slot (xivo_hip_pool_get). A frame is
  *   xivo_hip_propagate -> xivo_hip_pool_life_begin -> update -> xivo_hip_absorb_error -> xivo_hip_pool_life_end
- * and no call of it synchronises or downloads anything. P, the scene, the pool, the anchors and init_z equal those of the op
+ * and no call of it synchronises or downloads anything; with the tracks produced on the device (the point-cloud world below)
+ *   xivo_hip_propagate -> xivo_hip_pcw_tracks -> xivo_hip_pool_life_begin_tracks -> update -> xivo_hip_absorb_error -> xivo_hip_pool_life_end
+ * and frames of the two kinds may alternate on one context. P, the scene, the pool, the anchors and init_z equal those of the op
  * lists bit for bit: both run the same device functions in the same order. Every camera model is supported (a new entry is
  * initialised by the device code of xivo_hip_pool_add). The rules, per filter, in frame order:
  *   begin  - a used anchor's life is incremented, an unused anchor's is 0 (Group::IncrementLifetime, :36-41);
@@ -1018,7 +1020,9 @@ typedef struct {
  * xivo_hip_pool_step and the XIVO_EDIT_ADD_GROUP_ANCHOR / XIVO_EDIT_ADMIT_POOL ops return XIVO_HIP_ERR_INVALID and change
  * nothing (the context's host mirrors of the pool are stale); xivo_hip_pool_get / _tri_counts / _adapt_depth_config work.
  * tracks_max = 0 releases and re-reads the mirrors from the device, after which the host life cycle can go on; so does
- * xivo_hip_pool_config. Synchronises. */
+ * xivo_hip_pool_config. Every call that releases the track block (tracks_max = 0 on a configured context,
+ * xivo_hip_pool_config) releases the resident worlds of xivo_hip_pcw_config with it, as xivo_hip_life_config does: configure
+ * them again after the life cycle; a refused call releases nothing. Synchronises. */
 int xivo_hip_pool_life_config(xivo_hip_ctx* ctx, const xivo_pool_life_opts* opts);
 /* The in-state ids, as xivo_hip_life_set_book / xivo_hip_life_get_book; get_book also returns the pool book: ent_id
  * [nb][pool_max], ent_born [nb][pool_max], anc_used [nb][anchor_max], anc_life [nb][anchor_max]. Any output may be NULL. */
@@ -1030,12 +1034,19 @@ int xivo_hip_pool_life_get_book(xivo_hip_ctx* ctx, int b0, int nb, long long* fe
  * strict_criteria_timesteps). Increments the frame counter. XIVO_HIP_ERR_INVALID before anything is copied or launched: not
  * configured, a malformed off, a filter above tracks_max, begin twice without end. */
 int xivo_hip_pool_life_begin(xivo_hip_ctx* ctx, int B, int F, const int* off, const long long* ids, const double* meas, int strict);
+/* xivo_hip_pool_life_begin without the copy and the upload: consumes the tracks the last xivo_hip_pcw_tracks(B) or
+ * xivo_hip_pcw_tracks_resident(B) left in the block (once), one row of tracks_max per filter; the same begin kernel,
+ * triangulation, pool step and admit kernel follow, the frame counter is incremented and xivo_hip_pool_life_end reads the tracks
+ * in the block too. Neither synchronises nor allocates. XIVO_HIP_ERR_INVALID, nothing changed: no tracks were produced for this
+ * B since the last begin of either kind, and everything xivo_hip_pool_life_begin refuses (the immediate life cycle's context
+ * among it: that one takes xivo_hip_life_begin_tracks, which in turn refuses a pool context). */
+int xivo_hip_pool_life_begin_tracks(xivo_hip_ctx* ctx, int B, int F, int strict);
 /* After the update and xivo_hip_absorb_error, with the B of begin: the end kernel, then AdaptInitialDepth when configured. */
 int xivo_hip_pool_life_end(xivo_hip_ctx* ctx, int B);
 /* The counters of filters [b0, b0 + nb). Synchronises. */
 int xivo_hip_pool_life_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_pool_life_stats* out);
 
-/* ---- point-cloud world: the simulator's tracks produced on the device (opt-in; needs the device life cycle) ---------------
+/* ---- point-cloud world: the simulator's tracks produced on the device (opt-in; needs one of the device life cycles) -------
  * What BatchPCW.generate (xivo_amd/pcw.py, after the reference's scripts/point_cloud_world.py:44-131) computes on the host per
  * camera frame: every world point is projected through the frame's ground-truth camera pose, a point in front of the camera
  * whose pixel lies in [0, imw] x [0, imh] is visible, a visible point without a track id takes the world's next one in ascending
@@ -1043,25 +1054,39 @@ int xivo_hip_pool_life_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_pool_life_s
  * ascending point order - are the frame's tracks (id, u + noise, v + noise, depth). The worlds stay on the device (points, the id
  * each point holds, the next id of each world); a frame needs the camera poses only, 96 bytes per filter, and is
  *   xivo_hip_propagate -> xivo_hip_pcw_tracks -> xivo_hip_life_begin_tracks -> update -> xivo_hip_absorb_error -> xivo_hip_life_end
+ * (the pool life cycle: xivo_hip_pool_life_begin_tracks / xivo_hip_pool_life_end in their place).
  * The tracks are written into the life cycle's device block, one row of tracks_max per filter; frames fed by
- * xivo_hip_life_begin (host tracks) and by xivo_hip_life_begin_tracks may alternate freely. The evaluation order of the
+ * xivo_hip_life_begin / xivo_hip_pool_life_begin (host tracks) and by the _begin_tracks calls may alternate freely. The evaluation order of the
  * projection and the noise generator (Philox4x32-10 keyed by the seed, counter = point, filter, frame; one Box-Muller pair per
  * point) are specified in xivo_amd/csrc/pcw_device.h; pcw.philox_normal restates the generator for host code. A point's
  * noise depends on (seed, frame, filter, point) only. */
 typedef struct {
   int struct_size;         /* sizeof(xivo_pcw_opts) */
   int npts;                /* points per world; 0 releases the worlds */
-  double fx, fy, cx, cy;   /* pinhole intrinsics of the simulated camera (one set for all filters) */
+  double fx, fy, cx, cy;   /* pinhole intrinsics of the simulated camera (one set for all filters; xivo_hip_pcw_camera: any model) */
   double imw, imh;         /* image width and height in pixels; the borders count as inside */
 } xivo_pcw_opts;
 /* (Re-)allocates the resident worlds of batch_max filters - Xs [batch_max][npts][3], ids [batch_max][npts], next_id and the track
  * count per filter - and two page-locked blocks of batch_max x 12 doubles for the poses. The worlds start empty (points at
- * the origin, no ids, next id 0) until xivo_hip_pcw_set_world. XIVO_HIP_ERR_INVALID, nothing changed: no device life cycle is
- * configured (xivo_hip_life_config), npts > its tracks_max (a filter can then never produce more tracks than its row of the
- * block holds), a value that is not finite, a wrong struct_size, a frame open between life_begin and life_end.
- * xivo_hip_life_config (whatever its arguments) and xivo_hip_destroy release the worlds too: configure them again after
- * the life cycle. Synchronises. */
+ * the origin, no ids, next id 0) until xivo_hip_pcw_set_world. XIVO_HIP_ERR_INVALID, nothing changed: neither device life cycle
+ * is configured (xivo_hip_life_config, xivo_hip_pool_life_config), npts > its tracks_max (a filter can then never produce more tracks than its row of the
+ * block holds), a value that is not finite, a wrong struct_size, a frame open between a begin and its end of either life cycle.
+ * Who releases the worlds besides npts = 0: xivo_hip_life_config (whatever its arguments, unless the pool life cycle is
+ * configured - the block and the worlds are then that one's and stay), xivo_hip_pool_life_config and xivo_hip_pool_config
+ * whenever they release the pool life cycle's track block, and xivo_hip_destroy: configure the worlds again after the life
+ * cycle. Synchronises. */
 int xivo_hip_pcw_config(xivo_hip_ctx* ctx, const xivo_pcw_opts* opts);
+/* The camera the producer projects through, after xivo_hip_pcw_config (which returns to the pinhole of xivo_pcw_opts, as does
+ * cam = NULL here): any XIVO_CAM_* model, the struct the estimator itself takes (xivo_hip_set_layout); the image is cam->cols x
+ * cam->rows, borders included. With x = Xc_0 / z, y = Xc_1 / z the normalised camera coordinates of a point, the pixel is that
+ * of the estimator's own projection (xivo_amd/csrc/camera_device.h; XIVO_CAM_PINHOLE: (fx Xc_0) / z + cx as without a camera),
+ * and a point is visible when it is in front, hypot(x, y) <= max_radius and the pixel lies in the image. max_radius guards
+ * against the fold-back of a polynomial distortion far off axis, where points outside the field of view would land inside the
+ * image again; +inf: no guard. The evaluation order is specified in xivo_amd/csrc/pcw_device.h, pcw.project_points_cam restates
+ * it for host code. Ranks, ids and noise are as without a camera. Takes effect with the next frame call; does not synchronise.
+ * XIVO_HIP_ERR_INVALID, nothing changed: no worlds configured, a frame open between a begin and its end, an unknown model,
+ * rows or cols <= 0, an intrinsic or a coefficient that is not finite, max_radius NaN or <= 0. */
+int xivo_hip_pcw_camera(xivo_hip_ctx* ctx, const xivo_cam* cam, double max_radius);
 /* The worlds of filters [b0, b0 + nb): Xs [nb][npts][3]; ids [nb][npts] (NULL: every id -1, no point is tracked); next_id [nb]
  * (NULL: 10000, counter0 of src/feature.h). A set-up call: synchronises. */
 int xivo_hip_pcw_set_world(xivo_hip_ctx* ctx, int b0, int nb, const double* Xs, const long long* ids, const long long* next_id);
@@ -1071,12 +1096,12 @@ int xivo_hip_pcw_get_world(xivo_hip_ctx* ctx, int b0, int nb, long long* ids, lo
  * point X has camera coordinates Rsc^T (X - Tsc)). Copies the poses to page-locked staging, enqueues their upload and the
  * producer; does not synchronise and allocates nothing. noise_px_std: standard deviation of the pixel noise (0: none, bit for
  * bit the projection); seed, frame: the generator's key and the frame's part of its counter. XIVO_HIP_ERR_INVALID, nothing
- * changed: no worlds configured, B out of range, called between xivo_hip_life_begin* and xivo_hip_life_end. */
+ * changed: no worlds configured, B out of range, called between a begin and its end of either life cycle. */
 int xivo_hip_pcw_tracks(xivo_hip_ctx* ctx, int B, const double* gsc, double noise_px_std, unsigned long long seed,
                         unsigned long long frame);
 /* xivo_hip_life_begin without the upload: consumes the tracks the last xivo_hip_pcw_tracks(B) left in the block (once);
  * xivo_hip_life_end then reads them there too. XIVO_HIP_ERR_INVALID, nothing changed: no tracks were produced for this B since
- * the last life_begin of either kind, and everything xivo_hip_life_begin refuses. */
+ * the last life_begin of either kind, and everything xivo_hip_life_begin refuses (a pool life cycle's context among it). */
 int xivo_hip_life_begin_tracks(xivo_hip_ctx* ctx, int B, int F);
 /* Read-back for tests and debugging of what the last xivo_hip_pcw_tracks left for filters [b0, b0 + nb) (within its B; gone
  * after a host-track xivo_hip_life_begin): cnt [nb], ids [nb][tracks_max], meas [nb][tracks_max][3]; entries behind cnt[b]
@@ -1091,6 +1116,7 @@ int xivo_hip_pcw_get_tracks(xivo_hip_ctx* ctx, int b0, int nb, int* cnt, long lo
  * resident too (xivo_hip_pcw_config) a camera frame of all filters needs no host data and no host wait:
  *   xivo_hip_trajsim_frame -> xivo_hip_propagate_resident -> xivo_hip_pcw_tracks_resident -> xivo_hip_life_begin_tracks ->
  *   update -> xivo_hip_absorb_error -> xivo_hip_life_end
+ * (or xivo_hip_pool_life_begin_tracks / xivo_hip_pool_life_end: these calls ask only whether a frame of either life cycle is open).
  * Camera stamps coincide with IMU stamps and a frame covers a whole number of samples. The evaluation order and the noise
  * generator (Philox4x32-10 keyed by the seed, counter = pair, filter, sample) are specified in xivo_amd/csrc/trajsim_device.h;
  * a sample's noise depends on (seed, k, filter) only. The pixel noise of xivo_hip_pcw_tracks draws from the same generator:

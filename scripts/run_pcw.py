@@ -83,16 +83,30 @@ def main():
     ap.add_argument("-tracks", default="host", choices=["host", "device"],
                     help="where a frame's tracks come from: the numpy point-cloud world, uploaded by the frame call (the "
                          "default), or the worlds resident on the device (xivo_hip_pcw_tracks: only the ground-truth camera "
-                         "poses go down; pixel noise from its counter-based generator). Needs -lifecycle device and "
-                         "-npts <= %d; not with -host cpp" % sequence.L.LIFE_MAX_TRACKS)
+                         "poses go down; pixel noise from its counter-based generator). Needs -lifecycle device, or "
+                         "-feature_init subfilter -pool-lifecycle device, and -npts <= %d; not with -host cpp" % sequence.L.LIFE_MAX_TRACKS)
     ap.add_argument("-imu", default="host", choices=["host", "device"],
                     help="where the simulated IMU and the ground-truth poses come from: the numpy simulator, one message per "
                          "sample (the default), or the device (xivo_hip_trajsim_frame / xivo_hip_propagate_resident: one call per "
                          "camera frame, no host data; IMU noise from its counter-based generator). Needs -tracks device and "
                          "-vectorized; sim_imu_s is then the host's remaining share")
+    ap.add_argument("-cam-model", dest="cam_model", default="pinhole", choices=sorted(pcw.SIM_CAMERAS),
+                    help="the camera of the simulator and of the estimator (xivo_amd.pcw.SIM_CAMERAS): a distorted model runs "
+                         "the sub-filter life cycle (-feature_init subfilter), with -vectorized or -tracks device")
+    ap.add_argument("-max-radius", dest="max_radius", type=float, default=float("inf"),
+                    help="-cam-model other than pinhole: a point whose normalised radius exceeds this is not visible (the guard "
+                         "against a polynomial distortion's fold-back far off axis)")
     a = ap.parse_args()
     # (a sequence never brings more tracks than its world has points)
     life = dict(lifecycle=a.lifecycle, tracks_max=min(a.npts, sequence.L.LIFE_MAX_TRACKS))
+    if a.cam_model != "pinhole":
+        if a.feature_init != "subfilter":
+            ap.error("-cam-model %s needs -feature_init subfilter (the immediate life cycle un-projects with a pinhole)" % a.cam_model)
+        if not a.vectorized and a.tracks != "device":
+            ap.error("-cam-model %s needs -vectorized or -tracks device (the per-sequence host worlds are pinhole)" % a.cam_model)
+        if not a.max_radius > 0:
+            ap.error("-max-radius must be positive")
+        life.update(cam=pcw.SIM_CAMERAS[a.cam_model], pcw_max_radius=a.max_radius)
     if a.feature_init != "immediate" or a.pool_lifecycle != "host":
         life.update(feature_init=a.feature_init, pool_lifecycle=a.pool_lifecycle)
         try:      # before any rank is spawned: what check_lifecycle rejects
@@ -133,7 +147,7 @@ def main():
         print(json.dumps({
             "sequences": a.sequences, "frames_per_sequence": frames, "N": cfg.N, "integration": a.integration_method,
             "host": "cpp, vectorised simulators", "lifecycle": a.lifecycle, "tracks": a.tracks, "imu": a.imu,
-            "feature_init": a.feature_init, "pool_lifecycle": a.pool_lifecycle,
+            "feature_init": a.feature_init, "pool_lifecycle": a.pool_lifecycle, "cam_model": a.cam_model,
             **({"admitted": st["admitted"], "pool_dropped": st["pool_dropped"]} if a.feature_init == "subfilter" else {}),
             "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
             **_consistency(out),
@@ -207,6 +221,7 @@ def main():
         "sequences": B, "n_gpus": world, "frames_per_sequence": frames, "imu_samples_per_frame": int(round(a.vision_dt / a.imu_dt)),
         "N": cfg.N, "max_features": cfg.n_features, "integration": a.integration_method, "host": a.host,
         "lifecycle": a.lifecycle, "tracks": a.tracks, "feature_init": a.feature_init, "pool_lifecycle": a.pool_lifecycle,
+        "cam_model": a.cam_model,
         "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
         **_consistency(out),
         "updates": n_upd, "mh_rejected": n_rej,

@@ -59,7 +59,7 @@ def load_host_library():
         _HOST.xivo_batch_innov_log.argtypes = [C.c_void_p, C.c_int]
         _HOST.xivo_batch_enable_device_lifecycle.argtypes = [C.c_void_p, C.c_int]
         _HOST.xivo_batch_enable_device_pool_lifecycle.argtypes = [C.c_void_p, C.c_int]
-        _HOST.xivo_batch_enable_device_world.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _HOST.xivo_batch_enable_device_world.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double]
         _HOST.xivo_batch_visual_world.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_ulonglong, C.c_void_p]
         _HOST.xivo_batch_enable_device_imu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_frame_resident.argtypes = [C.c_void_p, C.c_ulonglong, C.c_int, C.c_double, C.c_ulonglong, C.c_void_p]
@@ -78,6 +78,7 @@ class BatchEstimator:
         cam = cfg.cam
         c["cam_model"], c["cam_rows"], c["cam_cols"] = cam["model"], cam["rows"], cam["cols"]
         c["fx"], c["fy"], c["cx"], c["cy"] = cam["fx"], cam["fy"], cam["cx"], cam["cy"]
+        c["d"][0, :len(cam.get("d", []))] = cam.get("d", [])
         c["visual_meas_std"], c["MH_thresh"], c["MH_adjust_factor"] = cfg.visual_meas_std, cfg.MH_thresh, cfg.MH_adjust_factor
         c["min_inliers"], c["min_new_features"], c["fix_group_block"] = cfg.min_inliers, cfg.min_new_features, int(cfg.fix_group_block)
         c["disable_MH_gating"] = 0 if getattr(cfg, "use_MH_gating", True) else 1
@@ -157,16 +158,19 @@ class BatchEstimator:
         if self.host.xivo_batch_enable_device_pool_lifecycle(self.h, int(tracks_max)) != 0:
             raise RuntimeError("xivo_batch_enable_device_pool_lifecycle failed")
 
-    def enable_device_world(self, Xs):
-        """BatchEstimator::EnableDeviceWorld: the worlds' points Xs [B, npts, 3] go to the device once (camera: cfg.cam); the
-        frames are then VisualMeasDeviceWorld. Needs the device life cycle and npts <= tracks_max"""
+    def enable_device_world(self, Xs, max_radius=None):
+        """BatchEstimator::EnableDeviceWorld: the worlds' points Xs [B, npts, 3] go to the device once (camera: cfg.cam, whatever
+        its model; max_radius, default cfg.pcw_max_radius: a distorted camera's guard against the fold-back far off axis); the
+        frames are then VisualMeasDeviceWorld. Needs one of the device life cycles and npts <= tracks_max"""
         Xs = np.ascontiguousarray(Xs, dtype=np.float64)
         if Xs.ndim != 3 or Xs.shape[0] != self.B or Xs.shape[2] != 3:
             raise ValueError("Xs [B, npts, 3]")
         cam = self.cfg.cam
         o = np.zeros(1, dtype=L.pcw_opts_dtype)
         o["fx"], o["fy"], o["cx"], o["cy"], o["imw"], o["imh"] = cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["cols"], cam["rows"]
-        if self.host.xivo_batch_enable_device_world(self.h, Xs.shape[1], o.ctypes.data, Xs.ctypes.data) != 0:
+        if max_radius is None:
+            max_radius = getattr(self.cfg, "pcw_max_radius", float("inf"))
+        if self.host.xivo_batch_enable_device_world(self.h, Xs.shape[1], o.ctypes.data, Xs.ctypes.data, float(max_radius)) != 0:
             raise RuntimeError("xivo_batch_enable_device_world failed")
 
     def VisualMeasDeviceWorld(self, t, gsc, noise_px_std, seed, mask=None):

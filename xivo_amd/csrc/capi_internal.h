@@ -221,6 +221,8 @@ struct xivo_hip_ctx {
   double* pcw_Xs = nullptr; long long* pcw_ids = nullptr; long long* pcw_next_id = nullptr; int* pcw_cnt = nullptr;
   double* pcw_gsc = nullptr; double* pcw_pin[2] = {nullptr, nullptr}; hipEvent_t pcw_ev[2] = {nullptr, nullptr};
   int pcw_cur = 0, pcw_tracks_B = 0; bool pcw_fresh = false;
+  // the camera of xivo_hip_pcw_camera in place of the pinhole of pcw_opts (pcw_use_cam), and its radius guard
+  bool pcw_use_cam = false; xivo_cam pcw_cam{}; double pcw_max_radius = 0.0;
   // trajectory producer (xivo_hip_trajsim_*, capi_trajsim.hip): curve / rate per filter [Bmax], the last frame's records
   // [Bmax][n_max] (read as [B][n]) and camera poses [Bmax][12], the ground-truth log [T_max][Bmax][12] with frames [0, ts_T)
   // written, the device copy of the propagation noise (Qimu 144 | Qmodel 529) with the host copy it was uploaded from; null until

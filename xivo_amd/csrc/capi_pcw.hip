@@ -1,7 +1,8 @@
 // C ABI, point-cloud world (include/xivo_hip.h, "point-cloud world"): the resident worlds, the per-frame track producer and the
 // read-back of what it left. Host orchestration only - the kernel is in pcw_kernels.hip, its rules in pcw_device.h. The frame
 // call checks its arguments before it touches the device, allocates nothing and does not synchronise the stream; the tracks
-// land in the strided form of the life cycle's track block (capi_lifecycle.hip), where xivo_hip_life_begin_tracks finds them.
+// land in the strided form of the life cycles' track block (capi_lifecycle.hip), where xivo_hip_life_begin_tracks and
+// xivo_hip_pool_life_begin_tracks find them.
 #include <math.h>
 #include <stdint.h>
 
@@ -19,6 +20,7 @@ void pcw_release(xivo_hip_ctx* c) {
     if (c->pcw_ev[i]) { hipEventDestroy(c->pcw_ev[i]); c->pcw_ev[i] = nullptr; }
   }
   c->pcw_opts = xivo_pcw_opts{}; c->pcw_cur = 0; c->pcw_tracks_B = 0; c->pcw_fresh = false;
+  c->pcw_use_cam = false; c->pcw_cam = xivo_cam{}; c->pcw_max_radius = 0.0;
 }
 
 int pcw_produce(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, unsigned long long seed, unsigned long long frame) {
@@ -27,11 +29,14 @@ int pcw_produce(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, 
   a.Xs = c->pcw_Xs; a.ids = c->pcw_ids; a.next_id = c->pcw_next_id; a.gsc = gsc; a.npts = o.npts;
   a.fx = o.fx; a.fy = o.fy; a.cx = o.cx; a.cy = o.cy; a.imw = o.imw; a.imh = o.imh;
   a.noise_px_std = noise_px_std; a.seed = seed; a.frame = frame;
+  a.use_cam = c->pcw_use_cam ? 1 : 0; a.cam = c->pcw_cam; a.max_radius = c->pcw_max_radius;
   a.track_ids = track_block_strided_ids(c); a.track_meas = track_block_strided_meas(c); a.cnt = c->pcw_cnt; a.track_ld = track_block_row(c);
   c->pcw_tracks_B = 0; c->pcw_fresh = false;   // (whatever the block held is being overwritten)
   {
     // per filter: the points and their ids in, the ids that changed and at most npts tracks of 32 bytes out
-    StageTimer st(c, ST_OTHER, 0.0, "pcw_tracks_kernel", (double)B * o.npts * (24.0 + 8.0 + 8.0 + 32.0));
+    char label[32];   // the instance launch_pcw_tracks picks, as the tracer prints it
+    snprintf(label, sizeof(label), "pcw_tracks_kernel<%d>", a.use_cam ? a.cam.model : -1);
+    StageTimer st(c, ST_OTHER, 0.0, label, (double)B * o.npts * (24.0 + 8.0 + 8.0 + 32.0));
     if (launch_pcw_tracks(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
   }
   c->pcw_tracks_B = B; c->pcw_fresh = true;
@@ -51,7 +56,7 @@ extern "C" {
 int xivo_hip_pcw_config(xivo_hip_ctx* c, const xivo_pcw_opts* o) {
   if (!c || !o || o->struct_size != (int)sizeof(xivo_pcw_opts) || o->npts < 0) return XIVO_HIP_ERR_INVALID;
   if (o->npts > 0) {
-    if (!c->life_stats || o->npts > track_block_row(c)) return XIVO_HIP_ERR_INVALID;
+    if ((!c->life_stats && !c->plife_on) || o->npts > track_block_row(c)) return XIVO_HIP_ERR_INVALID;   // either device life cycle
     const double v[6] = {o->fx, o->fy, o->cx, o->cy, o->imw, o->imh};
     for (double x : v) if (!isfinite(x)) return XIVO_HIP_ERR_INVALID;
   }
@@ -81,6 +86,23 @@ int xivo_hip_pcw_config(xivo_hip_ctx* c, const xivo_pcw_opts* o) {
   if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
   if (rc) { pcw_release(c); return rc; }
   c->pcw_opts = *o;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pcw_camera(xivo_hip_ctx* c, const xivo_cam* cam, double max_radius) {
+  if (!pcw_ready(c) || track_block_frame_open(c)) return XIVO_HIP_ERR_INVALID;
+  if (!cam) {   // back to the pinhole of xivo_pcw_opts
+    c->pcw_use_cam = false; c->pcw_cam = xivo_cam{}; c->pcw_max_radius = 0.0;
+    return XIVO_HIP_OK;
+  }
+  if (cam->model != XIVO_CAM_PINHOLE && cam->model != XIVO_CAM_ATAN && cam->model != XIVO_CAM_RADTAN && cam->model != XIVO_CAM_EQUI)
+    return XIVO_HIP_ERR_INVALID;
+  if (!(max_radius > 0.0) || cam->rows <= 0 || cam->cols <= 0) return XIVO_HIP_ERR_INVALID;   // (a NaN radius fails the comparison)
+  const double v[4] = {cam->fx, cam->fy, cam->cx, cam->cy};
+  for (double x : v) if (!isfinite(x)) return XIVO_HIP_ERR_INVALID;
+  for (double x : cam->d) if (!isfinite(x)) return XIVO_HIP_ERR_INVALID;
+  // the frame calls hand the camera to the kernel by value: frames already enqueued keep the one they were launched with
+  c->pcw_use_cam = true; c->pcw_cam = *cam; c->pcw_max_radius = max_radius;
   return XIVO_HIP_OK;
 }
 

@@ -1,5 +1,6 @@
 // C ABI, device-resident feature life cycle of the "subfilter" mode (include/xivo_hip.h, "the pool life cycle"): configuration,
-// the books' set-up and read-out, the two frame calls and the counters. Host orchestration only - the kernels are in
+// the books' set-up and read-out, the frame calls (pool_life_begin on uploaded tracks, pool_life_begin_tracks on the
+// tracks capi_pcw.hip's producer left in the block, pool_life_end) and the counters. Host orchestration only - the kernels are in
 // pool_lifecycle_kernels.hip (and pool_kernels.hip for the step), the decisions in pool_lifecycle_device.h. The in-state book,
 // the track block and the frame calls' common check and kernel arguments are capi_lifecycle.hip's (book_*, track_block_*,
 // frame_can_begin, life_args_*). Every entry point checks its arguments before it touches the device; the frame calls
@@ -43,11 +44,38 @@ int reread_mirrors(xivo_hip_ctx* c) {
   return XIVO_HIP_OK;
 }
 
+// the begin kernel, the step and the admit kernel on the tracks the block holds
+int plife_begin_frame(xivo_hip_ctx* c, int B, int F, int strict) {
+  c->F = F;   // the list length, as xivo_hip_edit_batch / xivo_hip_set_pixels set it
+  // the frame counter advances and the frame opens only once everything is enqueued: a failed launch leaves neither behind
+  PoolLifeArgs a = plife_args(c, B);
+  a.frame = c->plife_frame + 1;
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "pool_life_begin_kernel");
+    if (launch_pool_life_begin(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
+  }
+  // the step of xivo_hip_pool_step, on the pixels the begin kernel left and into device outputs
+  PoolStepArgs p = pool_step_args(c, B, strict);
+  p.xp = c->plife_xp; p.order = c->plife_order; p.n = c->plife_n; p.live = c->plife_live;
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "pool_step_kernel");
+    HIP_TRY((hipError_t)launch_pool_step(p, c->stream));
+  }
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "pool_life_admit_kernel");
+    if (launch_pool_life_admit(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
+  }
+  c->plife_frame += 1;
+  track_block_open_frame(c, B);
+  return XIVO_HIP_OK;
+}
+
 }  // namespace
 
 namespace xivo_hip::capi {
 void pool_life_release(xivo_hip_ctx* c) {
   if (!c->plife_on) return;
+  pcw_release(c);   // the producer writes into the track block: it goes with it
   c->mem.release(&c->plife_ent_id, &c->plife_ent_born, &c->plife_anc_used, &c->plife_anc_life, &c->plife_stats);
   c->mem.release(&c->plife_slot_track, &c->plife_ent_track, &c->plife_xp, &c->plife_order, &c->plife_n, &c->plife_live);
   book_release(c);
@@ -142,28 +170,17 @@ int xivo_hip_pool_life_begin(xivo_hip_ctx* c, int B, int F, const int* off, cons
   if (rc) return rc;
   rc = track_block_upload(c, B, off, ids, meas);
   if (rc) return rc;
-  c->F = F;   // the list length, as xivo_hip_edit_batch / xivo_hip_set_pixels set it
-  // the frame counter advances and the frame opens only once everything is enqueued: a failed launch leaves neither behind
-  PoolLifeArgs a = plife_args(c, B);
-  a.frame = c->plife_frame + 1;
-  {
-    StageTimer st(c, ST_OTHER, 0.0, "pool_life_begin_kernel");
-    if (launch_pool_life_begin(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
-  }
-  // the step of xivo_hip_pool_step, on the pixels the begin kernel left and into device outputs
-  PoolStepArgs p = pool_step_args(c, B, strict);
-  p.xp = c->plife_xp; p.order = c->plife_order; p.n = c->plife_n; p.live = c->plife_live;
-  {
-    StageTimer st(c, ST_OTHER, 0.0, "pool_step_kernel");
-    HIP_TRY((hipError_t)launch_pool_step(p, c->stream));
-  }
-  {
-    StageTimer st(c, ST_OTHER, 0.0, "pool_life_admit_kernel");
-    if (launch_pool_life_admit(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
-  }
-  c->plife_frame += 1;
-  track_block_open_frame(c, B);
-  return XIVO_HIP_OK;
+  return plife_begin_frame(c, B, F, strict);
+}
+
+int xivo_hip_pool_life_begin_tracks(xivo_hip_ctx* c, int B, int F, int strict) {
+  if (!frame_can_begin(c, B, F) || !c->plife_on || !c->fpool || !c->pcw_cnt || !c->pcw_fresh || c->pcw_tracks_B != B)
+    return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  int rc = ensure_gate_buffers(c, F);   // (allocated by pool_life_config: checks F only)
+  if (rc) return rc;
+  track_block_use_strided(c); c->pcw_fresh = false;
+  return plife_begin_frame(c, B, F, strict);
 }
 
 int xivo_hip_pool_life_end(xivo_hip_ctx* c, int B) {

@@ -182,6 +182,7 @@ struct PcwArgs {
   const double* Xs; long long* ids; long long* next_id; const double* gsc; int npts;
   double fx, fy, cx, cy, imw, imh, noise_px_std; unsigned long long seed, frame;
   long long* track_ids; double* track_meas; int* cnt; int track_ld;
+  int use_cam; xivo_cam cam; double max_radius;   // use_cam != 0 (xivo_hip_pcw_camera): project through cam instead of fx .. imh
 };
 int launch_pcw_tracks(const PcwArgs& a, int batch, hipStream_t s);
 

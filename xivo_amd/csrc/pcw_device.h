@@ -1,7 +1,8 @@
 // The point-cloud world's track producer as plain functions over ONE point of ONE world: projection through the frame's
 // ground-truth camera pose, the visibility test, the pixel noise and who gets which track id. Host and device: the kernel of
 // pcw_kernels.hip calls these functions, and a host compiler takes the header alone (tests/pcw_driver.cpp runs whole frames
-// through them without a GPU). No project header is included but philox_device.h, the generator, which is as self-contained.
+// through them without a GPU). No project header is included but philox_device.h, the generator, and camera_device.h, the
+// estimator's camera models, which are as self-contained (camera_device.h includes the public header only).
 //
 // Every rule restates BatchPCW.generate / RandomPCW.generate_measurements (xivo_amd/pcw.py), which follow the reference's
 // scripts/point_cloud_world.py:44-131: a point in front of the camera whose pixel lies inside the image (borders included) is
@@ -14,6 +15,14 @@
 //   front = Xc_2 > 0 ; z = front ? Xc_2 : 1
 //   u = fx Xc_0 / z + cx ; v = fy Xc_1 / z + cy           (fx Xc_0) / z: the product first
 //   vis = front && u >= 0 && v >= 0 && u <= imw && v <= imh
+// Through one of the estimator's camera models (xivo_hip_pcw_camera; c: the xivo_cam, the image is c.cols x c.rows), d, Xc,
+// front and z as above, then
+//   x = Xc_0 / z ; y = Xc_1 / z ; radius = hypot(x, y)
+//   XIVO_CAM_PINHOLE: u = fx Xc_0 / z + cx ; v = fy Xc_1 / z + cy      the statements above, bit for bit
+//   otherwise:        (u, v) = camera_project(c, x, y)                  camera_device.h, where each model is stated once
+//   vis = front && radius <= max_radius && u >= 0 && v >= 0 && u <= cols && v <= rows
+// max_radius guards against the fold-back of a polynomial distortion far off axis (+inf: no guard). camera_project's own
+// statements are compiled as the rest of the tree compiles them (the device build may fuse a product with a sum there).
 //
 // Noise - part of the interface: a host arm that wants the device's stream (pcw.philox_normal) restates exactly this. The
 // generator is counter based, so the noise of a point depends on (seed, frame, filter, point) alone, not on the launch shape
@@ -41,6 +50,8 @@
 #define XIVO_PCW_HD inline
 #endif
 
+#include "camera_device.h"
+
 namespace xivo_hip {
 
 struct PcwCam { double fx, fy, cx, cy, imw, imh; };
@@ -59,6 +70,29 @@ XIVO_PCW_HD bool pcw_project(const double* X, const double* g, const PcwCam& k, 
   const double v = k.fy * xc1 / z + k.cy;
   uvz[0] = u; uvz[1] = v; uvz[2] = xc2;
   return front && u >= 0.0 && v >= 0.0 && u <= k.imw && v <= k.imh;
+}
+
+// the same through camera model c.model; a point whose normalised radius exceeds max_radius is not visible
+XIVO_PCW_HD bool pcw_project(const double* X, const double* g, const xivo_cam& c, double max_radius, double* uvz) {
+#pragma clang fp contract(off)
+  const double d0 = X[0] - g[9], d1 = X[1] - g[10], d2 = X[2] - g[11];
+  const double xc0 = (g[0] * d0 + g[3] * d1) + g[6] * d2;
+  const double xc1 = (g[1] * d0 + g[4] * d1) + g[7] * d2;
+  const double xc2 = (g[2] * d0 + g[5] * d1) + g[8] * d2;
+  const bool front = xc2 > 0.0;
+  const double z = front ? xc2 : 1.0;
+  const double x = xc0 / z, y = xc1 / z;
+  const double radius = hypot(x, y);
+  double xp[2];
+  if (c.model == XIVO_CAM_PINHOLE) {
+    xp[0] = c.fx * xc0 / z + c.cx;
+    xp[1] = c.fy * xc1 / z + c.cy;
+  } else {
+    double J[2][2];   // (not read: the compiler drops what only it needs)
+    camera_project(c, x, y, xp, J);
+  }
+  uvz[0] = xp[0]; uvz[1] = xp[1]; uvz[2] = xc2;
+  return front && radius <= max_radius && xp[0] >= 0.0 && xp[1] >= 0.0 && xp[0] <= (double)c.cols && xp[1] <= (double)c.rows;
 }
 
 // ---- track ids

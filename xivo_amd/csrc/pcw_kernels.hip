@@ -9,6 +9,11 @@
 // ballot and the population count of the lanes below, the four wave totals through LDS - plus the totals of the chunks before,
 // which every thread carries in registers. Nothing crosses workgroups and no atomic is used: a filter's world, its row of the
 // track block and its two counters belong to its own workgroup.
+//
+// The kernel is a template on the camera: kModel = -1 is the pinhole of xivo_pcw_opts (today's kernel, instruction for
+// instruction), kModel = XIVO_CAM_* projects through the xivo_cam of xivo_hip_pcw_camera, which arrives by value in the kernel
+// arguments. One instance per model, because a single kernel that branched on the model would hold the equidistant model's
+// atan2 / sin / cos registers on every path: 147 VGPRs, 27 SGPR spills, 3 waves per SIMD for the pinhole too, against 94 / 0 / 5.
 #include "ekf_kernels.h"
 #include "pcw_device.h"
 
@@ -18,6 +23,7 @@ namespace {
 
 constexpr int kPcwThreads = 256, kPcwWaves = kPcwThreads / 64;
 
+template <int kModel>
 __global__ __launch_bounds__(kPcwThreads) void pcw_tracks_kernel(PcwArgs a) {
   // wave totals (visible, new) of a chunk, two sets taken in turn: a wave may write the next chunk's while another still
   // reads this one's, and the barrier of the next chunk keeps it from going further
@@ -27,6 +33,8 @@ __global__ __launch_bounds__(kPcwThreads) void pcw_tracks_kernel(PcwArgs a) {
   if (tid < 12) g[tid] = a.gsc[(long)b * 12 + tid];
   __syncthreads();
   const PcwCam cam{a.fx, a.fy, a.cx, a.cy, a.imw, a.imh};
+  xivo_cam lens = a.cam;
+  lens.model = kModel;   // (known at compile time: camera_project keeps this model's statements alone)
   const double* Xs = a.Xs + (long)b * npts * 3;
   long long* ids = a.ids + (long)b * npts;
   long long* tid_out = a.track_ids + (long)b * a.track_ld;
@@ -43,7 +51,7 @@ __global__ __launch_bounds__(kPcwThreads) void pcw_tracks_kernel(PcwArgs a) {
     if (in) {
       const double X[3] = {Xs[3 * (long)p], Xs[3 * (long)p + 1], Xs[3 * (long)p + 2]};
       id = ids[p];
-      vis = pcw_project(X, g, cam, uvz);
+      vis = kModel < 0 ? pcw_project(X, g, cam, uvz) : pcw_project(X, g, lens, a.max_radius, uvz);
     }
     const bool is_new = pcw_is_new(vis, id);
     const unsigned long long m_vis = __ballot(vis), m_new = __ballot(is_new);
@@ -74,7 +82,13 @@ __global__ __launch_bounds__(kPcwThreads) void pcw_tracks_kernel(PcwArgs a) {
 }  // namespace
 
 int launch_pcw_tracks(const PcwArgs& a, int batch, hipStream_t s) {
-  hipLaunchKernelGGL(pcw_tracks_kernel, dim3(batch), dim3(kPcwThreads), 0, s, a);
+  const dim3 grid(batch), block(kPcwThreads);
+  if (!a.use_cam) hipLaunchKernelGGL(pcw_tracks_kernel<-1>, grid, block, 0, s, a);
+  else if (a.cam.model == XIVO_CAM_PINHOLE) hipLaunchKernelGGL(pcw_tracks_kernel<XIVO_CAM_PINHOLE>, grid, block, 0, s, a);
+  else if (a.cam.model == XIVO_CAM_ATAN) hipLaunchKernelGGL(pcw_tracks_kernel<XIVO_CAM_ATAN>, grid, block, 0, s, a);
+  else if (a.cam.model == XIVO_CAM_RADTAN) hipLaunchKernelGGL(pcw_tracks_kernel<XIVO_CAM_RADTAN>, grid, block, 0, s, a);
+  else if (a.cam.model == XIVO_CAM_EQUI) hipLaunchKernelGGL(pcw_tracks_kernel<XIVO_CAM_EQUI>, grid, block, 0, s, a);
+  else return 1;   // (xivo_hip_pcw_camera refuses any other model)
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

@@ -46,8 +46,6 @@ void BatchEstimator::Check(int rc, const char* what) {
 
 BatchEstimator::BatchEstimator(const BatchConfig& cfg, int B, int device, const xivo_pose_in* poses0, const double* P0)
     : cfg_(cfg), B_(B) {
-  if (cfg.cam.model != XIVO_CAM_PINHOLE)
-    throw std::invalid_argument("point-cloud input initialises features with a pinhole un-projection");
   const int N = cfg.N(), F = cfg.n_features;
   Check(xivo_hip_create(&ctx_, device, N, 2 * F, B, (cfg.fix_group_block ? XIVO_HIP_FLAG_FIX_GROUP_BLOCK : 0u) |
                                                      (cfg.use_invdepth ? XIVO_HIP_FLAG_INVDEPTH : 0u)), "create");
@@ -235,6 +233,9 @@ void BatchEstimator::VisualMeasPointCloud(double t, const int* off, const int64_
     if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
     return;
   }
+  // (the sub-filter life cycles above initialise a new track on the device, through any camera model; this one un-projects here)
+  if (cfg_.cam.model != XIVO_CAM_PINHOLE)
+    throw std::invalid_argument("the immediate life cycle initialises features with a pinhole un-projection");
   // --- before the update: tracker-dropped features leave (ProcessTracks, src/manager.cpp:152-169), tracked ones get
   // their new pixel
   const double nan = std::numeric_limits<double>::quiet_NaN();
@@ -406,19 +407,23 @@ void BatchEstimator::EnableDevicePoolLifecycle(int tracks_max) {
   device_pool_life_ = true;
 }
 
-void BatchEstimator::EnableDeviceWorld(int npts, const xivo_pcw_opts& cam, const double* Xs) {
-  if (!device_life_) throw std::runtime_error("the device world needs the device life cycle (EnableDeviceLifecycle)");
+void BatchEstimator::EnableDeviceWorld(int npts, const xivo_pcw_opts& cam, const double* Xs, double max_radius) {
+  if (!device_life_ && !device_pool_life_)
+    throw std::runtime_error("the device world needs a device life cycle (EnableDeviceLifecycle or EnableDevicePoolLifecycle)");
   xivo_pcw_opts o = cam;
   o.struct_size = (int)sizeof(o); o.npts = npts;
   Check(xivo_hip_pcw_config(ctx_, &o), "pcw_config");
   device_world_ = npts > 0;
   world_frame_ = 0;
+  // the simulated camera is the estimator's: a distorted model goes down whole (cam's pinhole is then not read)
+  if (device_world_ && cfg_.cam.model != XIVO_CAM_PINHOLE) Check(xivo_hip_pcw_camera(ctx_, &cfg_.cam, max_radius), "pcw_camera");
   if (device_world_) Check(xivo_hip_pcw_set_world(ctx_, 0, B_, Xs, nullptr, nullptr), "pcw_set_world");
 }
 
 void BatchEstimator::VisualMeasDeviceWorld(double t, const double* gsc, double noise_px_std, unsigned long long seed,
                                            unsigned char* mask_out) {
-  if (!device_life_ || !device_world_) throw std::runtime_error("VisualMeasDeviceWorld needs EnableDeviceLifecycle and EnableDeviceWorld");
+  if (!(device_life_ || device_pool_life_) || !device_world_)
+    throw std::runtime_error("VisualMeasDeviceWorld needs a device life cycle and EnableDeviceWorld");
   double t0 = now_s();
   PropagateToFrame(t, t0);
   host_s_ += now_s() - t0;
@@ -430,14 +435,21 @@ void BatchEstimator::VisualMeasDeviceWorld(double t, const double* gsc, double n
 
 // the rest of a frame whose tracks the producer left in the track block
 void BatchEstimator::FrameOnProducedTracks(unsigned char* mask_out) {
-  Check(xivo_hip_life_begin_tracks(ctx_, B_, cfg_.n_features), "life_begin_tracks");
+  if (device_pool_life_) {
+    ++vision_counter_;   // (where VisualMeasPointCloud counts the frame)
+    Check(xivo_hip_pool_life_begin_tracks(ctx_, B_, cfg_.n_features, vision_counter_ >= sc_.strict_criteria_timesteps ? 1 : 0),
+          "pool_life_begin_tracks");
+  } else {
+    Check(xivo_hip_life_begin_tracks(ctx_, B_, cfg_.n_features), "life_begin_tracks");
+  }
   RunUpdate();
-  Check(xivo_hip_life_end(ctx_, B_), "life_end");
+  Check(device_pool_life_ ? xivo_hip_pool_life_end(ctx_, B_) : xivo_hip_life_end(ctx_, B_), device_pool_life_ ? "pool_life_end" : "life_end");
   if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
 }
 
 void BatchEstimator::EnableDeviceImu(const xivo_trajsim_opts& opts, const int* motion, const double* rate) {
-  if (!device_life_ || !device_world_) throw std::runtime_error("the device IMU needs EnableDeviceLifecycle and EnableDeviceWorld");
+  if (!(device_life_ || device_pool_life_) || !device_world_)
+    throw std::runtime_error("the device IMU needs a device life cycle and EnableDeviceWorld");
   xivo_trajsim_opts o = opts;
   o.struct_size = (int)sizeof(o);
   Check(xivo_hip_trajsim_config(ctx_, &o), "trajsim_config");
@@ -446,7 +458,7 @@ void BatchEstimator::EnableDeviceImu(const xivo_trajsim_opts& opts, const int* m
 }
 
 void BatchEstimator::FrameResident(unsigned long long k0, int n, double noise_px_std, unsigned long long seed, unsigned char* mask_out) {
-  if (!device_imu_ || !device_world_ || !device_life_) throw std::runtime_error("FrameResident needs EnableDeviceImu");
+  if (!device_imu_ || !device_world_ || !(device_life_ || device_pool_life_)) throw std::runtime_error("FrameResident needs EnableDeviceImu");
   t_visual_ = (double)(k0 + (unsigned long long)n) * device_imu_dt_;
   want_mask_ = mask_out != nullptr;
   Check(xivo_hip_trajsim_frame(ctx_, B_, k0, n), "trajsim_frame");
@@ -771,9 +783,10 @@ int xivo_batch_enable_device_pool_lifecycle(void* h, int tracks_max) {
 long xivo_batch_not_spd(void* h) {
   try { return static_cast<xivo::hip::BatchEstimator*>(h)->n_not_spd(); } catch (const std::exception&) { return -1; }
 }
-int xivo_batch_enable_device_world(void* h, int npts, const xivo_pcw_opts* cam, const double* Xs) {
+int xivo_batch_enable_device_world(void* h, int npts, const xivo_pcw_opts* cam, const double* Xs, double max_radius) {
   if (!h || !cam) return -1;
-  try { static_cast<xivo::hip::BatchEstimator*>(h)->EnableDeviceWorld(npts, *cam, Xs); return 0; } catch (const std::exception&) { return -1; }
+  try { static_cast<xivo::hip::BatchEstimator*>(h)->EnableDeviceWorld(npts, *cam, Xs, max_radius); return 0; }
+  catch (const std::exception&) { return -1; }
 }
 int xivo_batch_visual_world(void* h, double t, const double* gsc, double noise_px_std, unsigned long long seed, unsigned char* mask_out) {
   if (!h) return -1;

@@ -19,6 +19,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <limits>
 #include <unordered_map>
 #include <vector>
 
@@ -29,7 +30,7 @@ namespace hip {
 
 struct BatchConfig {
   int n_groups = 15, n_features = 30;              // kMaxGroup, kMaxFeature (src/core.h:95-105)
-  xivo_cam cam{};                                   // pinhole for point-cloud input (Feature::Initialize un-projects with it)
+  xivo_cam cam{};                                   // the immediate life cycle needs a pinhole (it un-projects a new feature on the host)
   double visual_meas_std = 1.0;
   double MH_thresh = 5.991, MH_adjust_factor = 1.1;
   int min_inliers = 5;
@@ -112,21 +113,25 @@ class BatchEstimator {
   // Not with EnableSubfilter, in either order (both throw).
   void EnableDeviceLifecycle(int tracks_max);
   bool device_lifecycle() const { return device_life_; }
-  // the point-cloud world's tracks from the device (xivo_hip_pcw_*; after EnableDeviceLifecycle, both calls throw without it):
+  // the point-cloud world's tracks from the device (xivo_hip_pcw_*; after EnableDeviceLifecycle or EnableDevicePoolLifecycle,
+  // both calls throw with neither):
   // EnableDeviceWorld places one world of npts points per filter (Xs [B][npts][3]; nothing tracked yet, ids from 10000) seen by
-  // the pinhole camera in cam (fx .. imh; struct_size and npts are filled in here). npts <= tracks_max; npts = 0 releases the
+  // the pinhole camera in cam (fx .. imh; struct_size and npts are filled in here) - or, when the estimator's own camera is not
+  // a pinhole, by that camera (xivo_hip_pcw_camera; a point beyond the normalised radius max_radius is then not visible: the
+  // guard against a polynomial distortion's fold-back). npts <= tracks_max; npts = 0 releases the
   // worlds, and so does every EnableDeviceLifecycle call. VisualMeasDeviceWorld is then the camera frame: gsc [B][12] are the
   // ground-truth camera poses (Rsc row-major, Tsc), the tracks are produced on the device (pixel noise of standard deviation
   // noise_px_std from the counter-based generator keyed by seed; the frame counter starts at 0 with EnableDeviceWorld) and the
-  // life cycle runs on them as in VisualMeasPointCloud. Frames of either kind may alternate.
-  void EnableDeviceWorld(int npts, const xivo_pcw_opts& cam, const double* Xs);
+  // life cycle runs on them as in VisualMeasPointCloud (the pool life cycle counts the frame and computes CandidateStrict
+  // there too). Frames of either kind may alternate.
+  void EnableDeviceWorld(int npts, const xivo_pcw_opts& cam, const double* Xs, double max_radius = std::numeric_limits<double>::infinity());
   void VisualMeasDeviceWorld(double t, const double* gsc, double noise_px_std, unsigned long long seed, unsigned char* mask_out);
   bool device_world() const { return device_world_; }
   // the simulated IMU and the ground-truth poses from the device too (xivo_hip_trajsim_*; after EnableDeviceWorld, both calls
   // throw without it): EnableDeviceImu configures the trajectory producer (opts as xivo_hip_trajsim_config takes them;
   // struct_size is filled in here) with curve motion[b] (0 Lissajous, 1 trefoil) and rate[b] per filter; n_max = 0 releases it.
   // FrameResident is then a whole camera frame at sample k0 + n without host data or a host wait: trajsim frame -> resident
-  // propagate (n > 0) -> resident tracks -> life_begin_tracks -> update -> life_end. It takes the place of the InertialMeas
+  // propagate (n > 0) -> resident tracks -> (pool_)life_begin_tracks -> update -> (pool_)life_end. It takes the place of the InertialMeas
   // calls of samples k0 + 1 .. k0 + n and the VisualMeasDeviceWorld call at t_{k0 + n}; the two kinds of frames do not mix in
   // one run (the host feeder does not see the device's samples).
   void EnableDeviceImu(const xivo_trajsim_opts& opts, const int* motion, const double* rate);
@@ -146,7 +151,7 @@ class BatchEstimator {
   void DropFeature(Book& bk, int j);
   void DiscardEmptyGroups(int b, std::vector<xivo_edit_op>& ops);
   void RunUpdate();
-  void FrameOnProducedTracks(unsigned char* mask_out);   // life_begin_tracks -> update -> life_end (-> mask)
+  void FrameOnProducedTracks(unsigned char* mask_out);   // (pool_)life_begin_tracks -> update -> (pool_)life_end (-> mask)
   void NewTrackStd(bool badtri, double sd[3]) const;
   void PropagateToFrame(double t, double& t0);
   void VisualSubfilter(const int* off, const int64_t* ids, const double* meas);

@@ -37,6 +37,17 @@ class Cam(C.Structure):
                 ("d", C.c_double * 5)]
 
 
+def make_cam(cam):
+    """a camera dict (model, fx, fy, cx, cy; rows / cols default 480 / 640; d: the model's coefficients) -> Cam"""
+    c = Cam()
+    c.model, c.rows, c.cols = cam["model"], cam.get("rows", 480), cam.get("cols", 640)
+    c.fx, c.fy, c.cx, c.cy = cam["fx"], cam["fy"], cam["cx"], cam["cy"]
+    d = list(cam.get("d", [])) + [0.0] * 5
+    for i in range(5):
+        c.d[i] = d[i]
+    return c
+
+
 # numpy dtypes mirroring the C structs (all naturally aligned, no padding surprises:
 # sizes are asserted against ctypes below)
 pose_dtype = np.dtype([("Rsb", "f8", 9), ("Tsb", "f8", 3), ("Rbc", "f8", 9), ("Tbc", "f8", 3),
@@ -271,6 +282,8 @@ _SIGS = {
     "xivo_hip_pool_life_set_book": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_pool_life_get_book": [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7,
     "xivo_hip_pool_life_begin": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+    "xivo_hip_pool_life_begin_tracks": [C.c_void_p, C.c_int, C.c_int, C.c_int],
+    "xivo_hip_pcw_camera": [C.c_void_p, C.c_void_p, C.c_double],
     "xivo_hip_pool_life_end": [C.c_void_p, C.c_int],
     "xivo_hip_pool_life_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_pcw_config": [C.c_void_p, C.c_void_p],
@@ -610,12 +623,7 @@ class Context:
     def set_layout(self, N, group_begin, n_groups, feature_begin, n_features, cam):
         lay = Layout(N, group_begin, n_groups, feature_begin, n_features)
         self.layout = lay
-        c = Cam()
-        c.model, c.rows, c.cols = cam["model"], cam.get("rows", 480), cam.get("cols", 640)
-        c.fx, c.fy, c.cx, c.cy = cam["fx"], cam["fy"], cam["cx"], cam["cy"]
-        d = list(cam.get("d", [])) + [0.0] * 5
-        for i in range(5):
-            c.d[i] = d[i]
+        c = make_cam(cam)
         self._check(self.lib.xivo_hip_set_layout(self.h, C.byref(lay), C.byref(c)))
 
     def set_scene(self, poses, groups, feats, b0=0):
@@ -1107,12 +1115,20 @@ class Context:
     # ---- point-cloud world on the device (xivo_hip_pcw_*)
     def pcw_config(self, npts, fx=0.0, fy=0.0, cx=0.0, cy=0.0, imw=0.0, imh=0.0):
         """the resident worlds of every filter, npts points each (<= the life cycle's tracks_max; 0 releases them), seen by
-        one pinhole camera; needs life_config first, and life_config releases them"""
+        one pinhole camera; needs life_config or pool_life_config first, and either releases them"""
         o = np.zeros(1, dtype=pcw_opts_dtype)
         o["struct_size"], o["npts"] = pcw_opts_dtype.itemsize, int(npts)
         o["fx"], o["fy"], o["cx"], o["cy"], o["imw"], o["imh"] = fx, fy, cx, cy, imw, imh
         self._check(self.lib.xivo_hip_pcw_config(self.h, _ptr(o)))
         self.pcw_npts = int(npts)
+
+    def pcw_camera(self, cam=None, max_radius=float("inf")):
+        """the camera the producer projects through, after pcw_config: a camera dict as set_layout takes it (any model; the image
+        is cols x rows); a point whose normalised radius exceeds max_radius is not visible. None: the pinhole of pcw_config"""
+        if cam is None:
+            self._check(self.lib.xivo_hip_pcw_camera(self.h, None, 0.0))
+        else:
+            self._check(self.lib.xivo_hip_pcw_camera(self.h, C.byref(make_cam(cam)), float(max_radius)))
 
     def pcw_set_world(self, Xs, ids=None, next_id=None, b0=0):
         """Xs [nb, npts, 3]; ids [nb, npts] int64 (None: no point is tracked); next_id [nb] (None: 10000)"""
@@ -1264,6 +1280,12 @@ class Context:
         if off.size != B + 1 or ids.size != int(off[-1]) or meas.size != 3 * ids.size:
             raise ValueError("off [B + 1], ids [off[B]], meas [off[B], 3]")
         self._check(self.lib.xivo_hip_pool_life_begin(self.h, B, int(F), _ptr(off), _ptr(ids), _ptr(meas), int(bool(strict))))
+        self.F = int(F)
+
+    def pool_life_begin_tracks(self, F, strict=False, B=None):
+        """pool_life_begin on the tracks the last pcw_tracks(B) / pcw_tracks_resident(B) left on the device (asynchronous, no
+        upload)"""
+        self._check(self.lib.xivo_hip_pool_life_begin_tracks(self.h, self.batch if B is None else int(B), int(F), int(bool(strict))))
         self.F = int(F)
 
     def pool_life_end(self, B=None):

@@ -275,6 +275,77 @@ def project_points(Xs, Rsc, Tsc, K, imw, imh):
     return front & (u >= 0) & (v >= 0) & (u <= imw) & (v <= imh), u, v, Xc[2]
 
 
+CAM_PINHOLE, CAM_ATAN, CAM_RADTAN, CAM_EQUI = 0, 1, 2, 3      # XIVO_CAM_* of include/xivo_hip.h
+# one simulated 640 x 480 camera per model around the default pinhole (d: atan w; radtan p1, p2, k1, k2, k3; equidistant
+# k0 .. k3). None of the three folds back inside the image; scripts/run_pcw.py -cam-model and the tests take them from here
+SIM_CAMERAS = {
+    "pinhole": dict(model=CAM_PINHOLE, rows=480, cols=640, fx=275.0, fy=275.0, cx=320.0, cy=240.0, d=[]),
+    "atan": dict(model=CAM_ATAN, rows=480, cols=640, fx=275.0, fy=275.0, cx=320.0, cy=240.0, d=[0.95]),
+    "radtan": dict(model=CAM_RADTAN, rows=480, cols=640, fx=275.0, fy=275.0, cx=320.0, cy=240.0, d=[1e-3, -5e-4, -0.28, 0.07, 0.0]),
+    "equi": dict(model=CAM_EQUI, rows=480, cols=640, fx=275.0, fy=275.0, cx=320.0, cy=240.0, d=[0.01, -0.005, 0.002, -0.001]),
+}
+
+
+def camera_project(cam, x, y):
+    """normalised camera coordinates -> pixel (u, v) through the camera dict `cam` (model, fx, fy, cx, cy, d), elementwise in
+    the statement order of camera_project of xivo_amd/csrc/camera_device.h; works in the dtype of x / y (float64, or
+    np.longdouble for a more precise restatement)"""
+    x, y = np.asarray(x), np.asarray(y)
+    T = np.result_type(x.dtype, y.dtype).type
+    fx, fy, cx, cy = (T(cam[k]) for k in ("fx", "fy", "cx", "cy"))
+    d = [T(v) for v in cam.get("d", [])] + [T(0)] * 5
+    model = cam["model"]
+    if model == CAM_PINHOLE:
+        return fx * x + cx, fy * y + cy
+    if model == CAM_EQUI:
+        k0, k1, k2, k3 = d[:4]
+        th = np.arctan2(np.sqrt(x * x + y * y), T(1))
+        phi = np.arctan2(y, x)
+        th2 = th * th; th3 = th2 * th; th5 = th3 * th2; th7 = th5 * th2; th9 = th7 * th2
+        r = th + k0 * th3 + k1 * th5 + k2 * th7 + k3 * th9
+        return fx * r * np.cos(phi) + cx, fy * r * np.sin(phi) + cy
+    if model == CAM_RADTAN:
+        p1, p2, k1, k2, k3 = d[:5]
+        t2, t3 = x * x, y * y
+        t6, t7 = p1 * x * T(2), p2 * y * T(2)
+        t8, t9 = t2 * T(3), t3 * T(3)
+        t10, t11, t12, t13, t14 = t6 * y, t7 * x, t2 + t3, t3 + t8, t2 + t9
+        t15, t16, t17 = t12 * t12, t12 * t12 * t12, k1 * t12
+        t18, t19, t20, t21 = k2 * t15, k3 * t16, p1 * t14, p2 * t13
+        t28 = t17 + t18 + t19 + T(1)
+        t29, t30 = t28 * x, t28 * y
+        return cx + fx * (t10 + t21 + t29), cy + fy * (t11 + t20 + t30)
+    if model != CAM_ATAN:
+        raise ValueError("camera model %r" % (model,))
+    w = d[0]
+    invw, w2 = T(1) / w if w != 0 else T(np.inf), T(2) * np.tan(w * T(0.5))
+    R = np.sqrt(x * x + y * y)
+    singular = (R < T(0.0001)) | (w == 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f = np.where(singular, T(1), invw * np.arctan(w2 * R) / np.where(singular, T(1), R))
+    return fx * f * x + cx, fy * f * y + cy
+
+
+def project_points_cam(Xs, Rsc, Tsc, cam, max_radius=np.inf):
+    """project_points through one of the estimator's camera models, in the evaluation order pcw_device.h states for
+    xivo_hip_pcw_camera: cam a camera dict (the image is cols x rows), a point whose normalised radius hypot(x, y) exceeds
+    max_radius is not visible -> (vis [B, npts] bool, u, v, Xc_2 [B, npts])"""
+    d = [Xs[..., i] - Tsc[:, None, i] for i in range(3)]
+    Xc = [(Rsc[:, None, 0, i] * d[0] + Rsc[:, None, 1, i] * d[1]) + Rsc[:, None, 2, i] * d[2] for i in range(3)]
+    front = Xc[2] > 0
+    z = np.where(front, Xc[2], Xc[2].dtype.type(1))
+    x, y = Xc[0] / z, Xc[1] / z
+    radius = np.hypot(x, y)
+    if cam["model"] == CAM_PINHOLE:
+        T = Xc[2].dtype.type
+        u = T(cam["fx"]) * Xc[0] / z + T(cam["cx"])
+        v = T(cam["fy"]) * Xc[1] / z + T(cam["cy"])
+    else:
+        u, v = camera_project(cam, x, y)
+    vis = front & (radius <= max_radius) & (u >= 0) & (v >= 0) & (u <= cam.get("cols", 640)) & (v <= cam.get("rows", 480))
+    return vis, u, v, Xc[2]
+
+
 class BatchPCW:
     """B point-cloud worlds with RandomPCW's track-id semantics; generate() returns the concatenated track lists in the
     layout xivo::hip::BatchEstimator::VisualMeasPointCloud takes (offsets, ids, (x, y, depth) rows).
@@ -292,13 +363,21 @@ class BatchPCW:
         self.ids = np.full(self.Xs.shape[:2], -1, dtype=np.int64)
         self.next_pt_id = np.full(self.Xs.shape[0], 10000, dtype=np.int64)
 
-    def generate(self, Rsc, Tsc, K, imw, imh, noise_px_std):
-        if self.noise == "philox":
-            vis, u, v, zc = project_points(self.Xs, Rsc, Tsc, K, imw, imh)
+    def generate(self, Rsc, Tsc, K, imw, imh, noise_px_std, cam=None, max_radius=np.inf):
+        """cam (a camera dict, any model) and max_radius: project through it as the device producer does after
+        xivo_hip_pcw_camera (project_points_cam; K, imw, imh are then not read); None: the pinhole K"""
+        if self.noise == "philox" or cam is not None:
+            if cam is not None:
+                vis, u, v, zc = project_points_cam(self.Xs, Rsc, Tsc, cam, max_radius)
+            else:
+                vis, u, v, zc = project_points(self.Xs, Rsc, Tsc, K, imw, imh)
             Xc = np.stack([u, v, zc], axis=-1)                                # (only [..., 2] is read below)
             B, npts = u.shape
-            noise = noise_px_std * philox_normal(self.noise_seed, self.frame, np.arange(B)[:, None], np.arange(npts)[None, :])
-            self.frame += 1
+            if self.noise == "philox":
+                noise = noise_px_std * philox_normal(self.noise_seed, self.frame, np.arange(B)[:, None], np.arange(npts)[None, :])
+                self.frame += 1
+            else:
+                noise = noise_px_std * self.rng.standard_normal(u.shape + (2,))
         else:
             Xc = np.einsum("bpj,bji->bpi", self.Xs - Tsc[:, None, :], Rsc)   # Rsc^T (Xs - Tsc)
             front = Xc[..., 2] > 0

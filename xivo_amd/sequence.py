@@ -37,7 +37,7 @@ What is mirrored from the reference and what is simplified:
     xivo_hip_life_end (lifecycle_kernels.hip): the tracks of all filters go down in one array, nothing is downloaded during
     a frame, `books` / `n_updates` / `n_rejected` are read from the device on demand. Same decisions, same results.
   * where the tracks come from (`SequenceConfig.track_source`): "host" (default) - the numpy worlds of xivo_amd/pcw.py, uploaded
-    by the frame call; "device" (needs lifecycle="device") - the worlds are resident and xivo_hip_pcw_tracks (pcw_kernels.hip)
+    by the frame call; "device" (needs lifecycle="device" or pool_lifecycle="device") - the worlds are resident and xivo_hip_pcw_tracks (pcw_kernels.hip)
     produces each frame's tracks from the ground-truth camera poses straight into the block the life cycle reads
     (`SequenceRunner.frame_world`): 96 bytes per filter go down instead of the tracks. Its pixel noise is the counter-based
     stream pcw.philox_normal restates.
@@ -175,9 +175,12 @@ class SequenceConfig:
         # above). A name of its own: lifecycle="device" stays the "immediate" mode's switch.
         self.pool_lifecycle = "host"
         # where a frame's tracks come from: "host" (the simulator's arrays, uploaded) or "device" (xivo_hip_pcw_tracks on the
-        # resident worlds of npts points each; needs lifecycle = "device" and npts <= tracks_max)
+        # resident worlds of npts points each; needs lifecycle or pool_lifecycle = "device" and npts <= tracks_max)
         self.track_source = "host"
         self.npts = 1000
+        # the simulated camera is `cam`, whatever its model; a distorted one sees no point whose normalised radius hypot(x, y)
+        # exceeds this (the guard against a polynomial distortion's fold-back far off axis; inf: no guard)
+        self.pcw_max_radius = float("inf")
         # where the simulated IMU records and the ground-truth poses come from: "host" (the numpy simulator and ImuFeeder, the
         # records uploaded by xivo_hip_propagate) or "device" (xivo_hip_trajsim_frame / xivo_hip_propagate_resident; needs
         # track_source = "device": a frame then takes no host data at all)
@@ -382,6 +385,9 @@ class HipBackend:
     def pool_life_begin(self, off, ids, meas, strict):
         self.ctx.pool_life_begin(self.F, off, ids, meas, strict, B=self.B)
 
+    def pool_life_begin_tracks(self, strict):
+        self.ctx.pool_life_begin_tracks(self.F, strict, B=self.B)
+
     def pool_life_end(self):
         self.ctx.pool_life_end(self.B)
 
@@ -394,9 +400,11 @@ class HipBackend:
 
     def enable_device_world(self):
         """allocate the resident worlds of the device track source (xivo_hip_pcw_config): cfg.npts points per filter, the
-        camera of cfg.cam"""
+        camera of cfg.cam (a distorted model goes down whole: xivo_hip_pcw_camera)"""
         cam = self.cfg.cam
         self.ctx.pcw_config(self.cfg.npts, cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["cols"], cam["rows"])
+        if cam["model"] != L_CAM_PINHOLE:
+            self.ctx.pcw_camera(cam, self.cfg.pcw_max_radius)
 
     def set_world(self, Xs, ids=None, next_id=None):
         """the world points [B, npts, 3] of every filter (ids None: nothing is tracked yet, next_id None: 10000)"""
@@ -636,8 +644,8 @@ def check_lifecycle(cfg):
     if imu == "device" and src != "device":
         raise ValueError("imu_source='device' needs track_source='device'")
     if src == "device":
-        if cfg.lifecycle != "device":
-            raise ValueError("track_source='device' needs lifecycle='device'")
+        if cfg.lifecycle != "device" and plc != "device":
+            raise ValueError("track_source='device' needs lifecycle='device' or pool_lifecycle='device'")
         if not 0 < cfg.npts <= cfg.tracks_max:
             raise ValueError("track_source='device' needs 0 < npts <= tracks_max (npts=%d, tracks_max=%d)" % (cfg.npts, cfg.tracks_max))
 
@@ -773,16 +781,27 @@ class SequenceRunner:
         """one camera frame of the "immediate" life cycle on the device: propagate -> life_begin -> update -> life_end"""
         return self._frame_host_tracks(imu, tracks, self.be.life_begin, self.be.life_end)
 
+    def _produced_tracks_pair(self):
+        """the begin / end pair of a frame on the tracks the device produced, by life cycle: the pool life cycle counts the
+        frame and passes CandidateStrict, as _frame_subfilter_device does"""
+        be = self.be
+        if not self.device_pool_lifecycle:
+            return be.life_begin_tracks, be.life_end
+        self.vision_counter += 1
+        strict = self.vision_counter >= self.cfg.strict_criteria_timesteps
+        return lambda: be.pool_life_begin_tracks(strict), be.pool_life_end
+
     def frame_world(self, imu, gsc, frame):
         """one camera frame whose tracks the device produces (track_source="device"): gsc [B, 12] the ground-truth camera pose
         of every filter (Rsc row-major, Tsc), frame the frame's number (the noise generator's counter). propagate -> pcw_tracks
-        -> life_begin_tracks -> update -> life_end; nothing but the poses goes down and nothing comes back (unless want_mask)."""
+        -> life_begin_tracks -> update -> life_end (pool_life_begin_tracks / pool_life_end with pool_lifecycle="device");
+        nothing but the poses goes down and nothing comes back (unless want_mask)."""
         if self.cfg.track_source != "device":
             raise ValueError("frame_world needs track_source='device'")
         be = self.be
         return self._device_frame([("propagate", lambda: imu is not None and be.propagate(imu)),
                                    ("tracks", lambda: be.make_tracks(gsc, self.noise_px_std, self.noise_seed, frame))],
-                                  be.life_begin_tracks, be.life_end)
+                                  *self._produced_tracks_pair())
 
     def frame_resident(self, k0, n, frame):
         """one camera frame at IMU sample k0 + n that takes no host data (imu_source="device"): the device produces the records
@@ -795,7 +814,7 @@ class SequenceRunner:
         return self._device_frame([("imu", lambda: be.make_imu(k0, n)),
                                    ("propagate", lambda: n > 0 and be.propagate_resident()),
                                    ("tracks", lambda: be.make_tracks_resident(self.noise_px_std, self.noise_seed, frame))],
-                                  be.life_begin_tracks, be.life_end)
+                                  *self._produced_tracks_pair())
 
     def _tick(self, name, t0):
         if self.timers is None:
@@ -1213,6 +1232,7 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     sim = BatchTrajectorySim(motion, rate, seed=seed + 1, noise=imu_noise, noise_seed=seed + 1)
     world = BatchPCW(B, npts=npts, seed=seed, noise=noise, noise_seed=noise_seed)
     K = np.array([[cfg.cam["fx"], 0, cfg.cam["cx"]], [0, cfg.cam["fy"], cfg.cam["cy"]], [0, 0, 1.0]])
+    sim_cam = cfg.cam if cfg.cam["model"] != L_CAM_PINHOLE else None      # both track sources simulate the estimator's camera
     Rbc = so3_exp(cfg.Wbc)
     poses = np.zeros(B, dtype=L.pose_dtype)
     R0, T0 = sim.gsb(0.0)
@@ -1256,7 +1276,8 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
                 Rsb, Tsb = sim.gsb(t)
                 Rsc, Tsc, gsc = camera_poses(Rsb, Tsb, Rbc, cfg.Tbc)
             if not dev_tracks:
-                off, ids, meas = world.generate(Rsc, Tsc, K, cfg.cam["cols"], cfg.cam["rows"], noise_vision_std)
+                off, ids, meas = world.generate(Rsc, Tsc, K, cfg.cam["cols"], cfg.cam["rows"], noise_vision_std, cam=sim_cam,
+                                                max_radius=cfg.pcw_max_radius)
             t1 = time.perf_counter()
             tm["sim_tracks"] = tm.get("sim_tracks", 0.0) + t1 - t0
             mask = np.zeros((B, cfg.n_features), dtype=np.uint8) if est.want_mask else None   # (device life cycle: no download)
