@@ -371,6 +371,12 @@ int xivo_hip_stack(xivo_hip_ctx* ctx, int B, double R);
  * (src/helpers.cpp:13-23): per feature (2k-3) projected rows appended after
  * the in-state rows with diagR = Roos. rows_out[b] = total OOS rows. feats == NULL projects the list of the
  * previous call again (it stays resident; same nb and n_oos) - for a caller that re-linearises without new tracks.
+ * The 2k-3 rows are a reservation for rank(Hf) = 3. When Hf has rank r < 3 (all k observing groups at one pose - a platform
+ * that has not moved - gives r = 2) the kernel of Hf^T has 2k-r vectors and the reference projects onto all of them; here the
+ * feature still gets 2k-3 rows: the FIRST 2k-3 columns of Eigen's kernel basis A (A[:, :2k-3]^T Hx, A[:, :2k-3]^T r,
+ * diagR = Roos), the last 3-r kernel vectors are dropped. Every row written is a null-space row of Hf; the update uses less
+ * information than the reference's, never wrong information. rows_out counts 2k-3 per feature whatever the rank. A group
+ * slot may be listed more than once in group_sind (its block accumulates).
  * Camera-calibration builds (cam_dim > 0): the observations are projected with the filter's own intrinsics, and - as the
  * reference codes ComputeOOSJacobianInternal (src/oos.cpp:39-89 writes the group / Wbc / Tbc blocks only) - the rows carry NO
  * intrinsics block; of the row builders in that file only ComputeLCJacobian has one (:125-142, xivo_hip_close_loop_stack). */
@@ -381,7 +387,8 @@ int xivo_hip_oos_project(xivo_hip_ctx* ctx, int b0, int nb, int n_oos, const xiv
  * feature contributes 2 * kMaxGroup - 3 rows (kMaxGroup = the layout's n_groups) however many groups saw it. What the
  * reference leaves in the rows behind 2k is unspecified (the buffers are Eigen::resize'd, never cleared); this mode defines
  * them as zero, for which FullPivLU::kernel appends one unit vector per such row: the first 2k - 3 rows are those of the
- * default call, the others are H = 0, inn = 0, diagR = Roos - they change M and S, not K, dx or P+. options = 0 is
+ * default call (at rank(Hf) < 3 truncated as described there), the others are H = 0, inn = 0, diagR = Roos - they change M
+ * and S, not K, dx or P+. options = 0 is
  * xivo_hip_oos_project (SURVEY 8 a9's specification: the top 2k rows). feats == NULL re-projects with the options of the
  * call that uploaded the list. */
 #define XIVO_HIP_OOS_WHOLE_BUFFER 1u

@@ -228,8 +228,16 @@ CAM_PINHOLE, CAM_ATAN, CAM_RADTAN, CAM_EQUI = 0, 1, 2, 3
 
 
 def camera_project(cam, xc):
+    """Project(xc, &jac) -> (xp, jac). Where the reference's C++ divides by zero (the equidistant camera on its axis, atan
+    with w = 0) this returns what IEEE arithmetic gives there - NaN / inf entries - and does not raise: x, y and w are numpy
+    scalars, evaluated under np.errstate."""
+    with np.errstate(all="ignore"):
+        return _camera_project(cam, xc)
+
+
+def _camera_project(cam, xc):
     fx, fy, cx, cy = cam["fx"], cam["fy"], cam["cx"], cam["cy"]
-    x, y = float(xc[0]), float(xc[1])
+    x, y = np.float64(xc[0]), np.float64(xc[1])
     model = cam["model"]
     d = cam.get("d", [])
     if model == CAM_PINHOLE:
@@ -263,7 +271,7 @@ def camera_project(cam, xc):
                       [fy * (t6 + t7 + t26 * y), fy * (t28 + p2 * x * 2.0 + p1 * y * 6.0 + t27 * y)]])
         return xp, J
     if model == CAM_ATAN:
-        w = d[0]
+        w = np.float64(d[0])
         invw = 1.0 / w; w2 = 2.0 * math.tan(w * 0.5)
         R = math.sqrt(x * x + y * y)
         singular = R < 0.0001 or w == 0
@@ -283,9 +291,15 @@ def camera_project(cam, xc):
 def camera_project_jacc(cam, xc):
     """d(xp)/d(intrinsics) of the USE_ONLINE_CAMERA_CALIB builds, [2, dim] in each model's own parameter order:
     pinhole fx fy cx cy (camera_pinhole.h:31-35); atan + w (camera_atan.h:62-91); radtan + p1 p2 k1 k2 k3
-    (camera_radtan.h:78-96); equidistant + k0..k3 (camera_equidist.h:80-94)."""
+    (camera_radtan.h:78-96); equidistant + k0..k3 (camera_equidist.h:80-94). IEEE results (NaN / inf) where the C++ divides
+    by zero, as camera_project."""
+    with np.errstate(all="ignore"):
+        return _camera_project_jacc(cam, xc)
+
+
+def _camera_project_jacc(cam, xc):
     fx, fy = cam["fx"], cam["fy"]
-    x, y = float(xc[0]), float(xc[1])
+    x, y = np.float64(xc[0]), np.float64(xc[1])
     model = cam["model"]
     d = cam.get("d", [])
     if model == CAM_PINHOLE:
@@ -316,7 +330,7 @@ def camera_project_jacc(cam, xc):
         J[1, 6] = fy * t12 * y; J[1, 7] = fy * t15 * y; J[1, 8] = fy * t16 * y
         return J
     if model == CAM_ATAN:
-        w = d[0]
+        w = np.float64(d[0])
         invw = 1.0 / w; w2 = 2.0 * math.tan(w * 0.5)
         R = math.sqrt(x * x + y * y)
         J = np.zeros((2, 5))

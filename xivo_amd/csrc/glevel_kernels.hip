@@ -591,8 +591,10 @@ __global__ __launch_bounds__(64) void oos_kernel(OosArgs a) {
   __shared__ int sRank;
   __shared__ int sRow0;
 
-  // row offset of this feature = row0 + sum_{o' < o} (2 k_o' - 3)  (rank 3 assumed for the
-  // reservation; rows beyond the actual kernel dimension stay neutral)
+  // row offset of this feature = row0 + sum_{o' < o} (2 k_o' - 3): the reservation assumes rank(Hf) = 3. The kernel of
+  // Hf^T has 2k - rank >= 2k - 3 vectors, so every reserved row is written; at rank < 3 (all observing groups at one pose)
+  // only the first 2k - 3 columns of Eigen's basis fit and the last 3 - rank are dropped (include/xivo_hip.h,
+  // xivo_hip_oos_project; tests/test_geometry_edges_gpu.py)
   if (lane == 0) {
     int r = a.row0;
     for (int q = 0; q < o; ++q) {
