@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import map_restate as mr
+import traj_restate as tr
 from xivo_amd import lib as L
 from xivo_amd import pcw, sequence
 
@@ -336,6 +337,37 @@ def test_nees_against_the_restatement(built):
         e2, n2, a2, u2 = ctx.map_nees(gt[1:, 1:4], b0=1, t0=1)
         assert e2.tobytes() == err3[1:, 1:4].tobytes() and n2.tobytes() == nees[1:, 1:4].tobytes()
         assert u2.tolist() == [int(np.isfinite(nees[1, 1:4]).sum())]
+
+
+def test_frame_mean_is_the_stated_tree_bit_for_bit(built):
+    """anees / n_used of xivo_hip_map_nees against tests/traj_restate.py frame_mean_tree on the very nees values the call returns.
+    9 filters of n_out = 30 slots: a frame is 270 values, one pass of the 256 threads and 14 of a second. Frame 0: filters with
+    30, 17 and 0 features (the slots behind n_pts are NaN), one truth missing; frame 1: every P negated, so no Sigma is
+    positive definite and nothing is finite - n_used = 0, anees NaN. Additions and one division in a fixed order: the bound
+    is equality."""
+    rng = np.random.default_rng(270)
+    B, lay, n_out = 9, WIDE, 30
+    present = [sorted(rng.permutation(70)[:k].tolist()) for k in (30, 70, 17, 0, 45, 30, 1, 29, 64)]
+    with _context(lay, B) as ctx:
+        poses, groups, feats = _scene(rng, lay, B, present, False)
+        ctx.set_scene(poses, groups, feats)
+        ctx.upload_P(_spd(rng, B, _N(lay)))
+        ctx.map_config(2, n_out)
+        ctx.map_record(1)
+        ctx.upload_P(-ctx.download_P())
+        ctx.map_record(2)
+        pts, n_pts, _ = ctx.map_read()
+        assert n_pts[0].tolist() == [min(len(p), n_out) for p in present]
+        gt = pts["Xs"] + rng.normal(size=(2, B, n_out, 3)) * 0.05
+        gt[0, 1, 3] = np.nan
+        _, nees, anees, used = ctx.map_nees(gt)
+    expect = sum(min(len(p), n_out) for p in present) - 1
+    assert int(np.isfinite(nees[0]).sum()) == expect and not np.isfinite(nees[1]).any()
+    mean, n = tr.frame_mean_tree(nees[0])
+    print("frame 0: n_used %d (restated %d) anees %r (restated %r)" % (used[0], n, anees[0], mean))
+    assert used[0] == n == expect and anees[0].tobytes() == mean.tobytes()
+    mean, n = tr.frame_mean_tree(nees[1])
+    assert used[1] == n == 0 and np.isnan(anees[1]) and np.isnan(mean)
 
 
 def test_after_a_real_frame(built):

@@ -329,6 +329,43 @@ def test_nees_against_the_longdouble_reference(built):
         assert ctx.lib.xivo_hip_traj_nees(ctx.h, 0, B, 0, 1, gt.ctypes.data, None, None, None, None) == -1
 
 
+@pytest.mark.parametrize("B", [1, 255, 256, 257, 513])
+def test_frame_mean_is_the_stated_tree_bit_for_bit(built, B):
+    """anees / n_used of xivo_hip_traj_nees against tests/traj_restate.py frame_mean_tree on the very nees values the call
+    returns: below, at and above one pass of the 256 threads and above two. Filters 0, 256 (where there is one), the last one
+    and a few between have a pose block that is not positive definite in one of the frames, so their nees is NaN and the
+    filter must be skipped, not added. Additions and one division in a fixed order: the bound is equality. With B = 1 the only
+    filter is such a one: nothing is finite, n_used = 0 and anees is NaN."""
+    rng = np.random.default_rng(160 + B)
+    T = 1 if B == 1 else 2
+    bad = [sorted({0, B - 1} | ({256} if B > 256 else set()) | set(rng.integers(0, B, size=3).tolist())),
+           sorted({B // 2, B - 1})][:T]
+    est = [_poses(rng, B) for _ in range(T)]
+    gt_R = np.zeros((T, B, 3, 3)); gt_T = np.zeros((T, B, 3))
+    with _context(rng, B, est[0]) as ctx:
+        ctx.traj_config(T, list(range(6)))
+        for t in range(T):
+            P = _spd(rng, B)
+            P[bad[t], 2, 2] *= -1.0                          # a negative third pivot
+            ctx.upload_P(P)
+            _set_poses(ctx, est[t])
+            ctx.traj_record(t)
+            for b in range(B):
+                e = rng.normal(size=6) * 0.1
+                Rg, Tg = tr.retract(est[t][b]["Rsb"].reshape(3, 3).T, est[t][b]["Tsb"], e)
+                gt_R[t, b], gt_T[t, b] = Rg.astype(np.float64), Tg.astype(np.float64)
+        _, nees, anees, used = ctx.traj_nees(gt_R, gt_T)
+    for t in range(T):
+        assert np.flatnonzero(~np.isfinite(nees[t])).tolist() == bad[t]
+        mean, n = tr.frame_mean_tree(nees[t])
+        print("B %d frame %d: n_used %d (restated %d) anees %r (restated %r)" % (B, t, used[t], n, anees[t], mean))
+        assert used[t] == n == B - len(bad[t])
+        if n == 0:
+            assert np.isnan(anees[t])
+        else:
+            assert anees[t].tobytes() == mean.tobytes()
+
+
 def test_drivers_return_the_same_trajectory_with_the_log(built):
     """run_pcw / run_pcw_batch with trajectory_log: the estimates come from one read of the log at the end and equal the
     per-frame downloads of the run without it; scripts/run_pcw.py -traj-log reports a finite anees_pose."""

@@ -112,3 +112,23 @@ def spd_with_spectrum(rng, eig):
     Q, _ = np.linalg.qr(rng.normal(size=(len(eig), len(eig))))
     S = (Q * np.asarray(eig)) @ Q.T
     return np.tril(S) + np.tril(S, -1).T
+
+
+def frame_mean_tree(values):
+    """The device's mean of the finite values of one frame (frame_anees_kernel), addition for addition in fp64: thread tid of 256
+    adds the finite entries tid, tid + 256, ... in ascending order, a halving tree adds the 256 partial sums and counts, one
+    division -> (mean, number of finite values); (NaN, 0) when nothing is finite"""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    s = np.zeros(256, dtype=np.float64)
+    c = np.zeros(256, dtype=np.int64)
+    for tid in range(256):
+        for x in v[tid::256]:
+            if np.isfinite(x):
+                s[tid] = s[tid] + x
+                c[tid] += 1
+    h = 128
+    while h > 0:
+        s[:h] = s[:h] + s[h:2 * h]
+        c[:h] = c[:h] + c[h:2 * h]
+        h //= 2
+    return (s[0] / np.float64(c[0]) if c[0] > 0 else np.float64(np.nan)), int(c[0])

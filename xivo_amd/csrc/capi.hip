@@ -58,7 +58,9 @@ SceneBuffers scene_buffers(xivo_hip_ctx* c) {
 
 // Device -> host copy of `rows` rows of `width` bytes (device pitch dpitch, host pitch hpitch). hipMemcpy2D issues one
 // small DMA per row - 13 ms for 2048 rows of 30 bytes - so short rows come over as one contiguous block and are
-// repacked on the host.
+// repacked on the host. The block includes the gaps between the rows: right for the ground-truth log's 96-byte entries
+// (capi_trajsim.hip), wrong for a few filters of the trajectory / landmark / innovation logs, whose frames are Bmax entries of up
+// to kilobytes apart - those keep the strided copy (d2h_frames).
 int d2h_rows(xivo_hip_ctx* c, void* dst, size_t hpitch, const void* src, size_t dpitch, size_t width, size_t rows) {
   if (rows == 0 || width == 0) return XIVO_HIP_OK;
   if (width == dpitch && width == hpitch) {
@@ -71,6 +73,35 @@ int d2h_rows(xivo_hip_ctx* c, void* dst, size_t hpitch, const void* src, size_t 
   HIP_TRY(hipMemcpyAsync(c->hstage.data(), src, span, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (size_t r = 0; r < rows; ++r) memcpy((char*)dst + r * hpitch, c->hstage.data() + r * dpitch, width);
+  return XIVO_HIP_OK;
+}
+
+// Frame-major storage: the filters [b0, b0 + nb) of one frame are contiguous, frames are Bmax entries apart - one row per frame,
+// as a strided copy (see d2h_rows for why not through it).
+int d2h_frames(xivo_hip_ctx* c, void* dst, const void* src, size_t per, int b0, int nb, int t0, int nt) {
+  if (!dst) return XIVO_HIP_OK;
+  HIP_TRY(hipMemcpy2DAsync(dst, (size_t)nb * per, (const char*)src + FrameLog::at(t0, c->Bmax, b0) * per, (size_t)c->Bmax * per,
+                           (size_t)nb * per, nt, hipMemcpyDeviceToHost, c->stream));
+  return XIVO_HIP_OK;
+}
+
+int NeesStaging::up(xivo_hip_ctx* c, char** io, size_t* io_cap, size_t per, int nt_, int gt_w, int err_w_, const double* gt_h) {
+  n = (size_t)nt_ * per; nt = (size_t)nt_; err_w = (size_t)err_w_;
+  const size_t o_err = n * gt_w, o_nees = o_err + n * err_w, o_an = o_nees + n, dbl = o_an + nt;
+  const int rc = c->mem.grow(io, io_cap, dbl * sizeof(double) + nt * sizeof(int));
+  if (rc) return rc;
+  gt = reinterpret_cast<double*>(*io);
+  err = gt + o_err; nees = gt + o_nees; anees = gt + o_an; n_used = reinterpret_cast<int*>(gt + dbl);
+  HIP_TRY(hipMemcpyAsync(gt, gt_h, n * gt_w * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return XIVO_HIP_OK;
+}
+
+int NeesStaging::down(xivo_hip_ctx* c, double* err_h, double* nees_h, double* anees_h, int* n_used_h) const {
+  if (err_h) HIP_TRY(hipMemcpyAsync(err_h, err, n * err_w * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (nees_h) HIP_TRY(hipMemcpyAsync(nees_h, nees, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (anees_h) HIP_TRY(hipMemcpyAsync(anees_h, anees, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (n_used_h) HIP_TRY(hipMemcpyAsync(n_used_h, n_used, nt * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return XIVO_HIP_OK;
 }
 

@@ -2,19 +2,12 @@
 // and the ensemble / per-filter sums. Host orchestration only - the kernels are in innov_kernels.hip, the arithmetic in
 // innov_device.h. Every entry point checks its arguments before it touches the device. The staged rows (StagedRows) are only
 // read here: the record picks the representation the update left and materialises nothing.
-#include <stdint.h>
-
 #include "capi_internal.h"
 
 using namespace xivo_hip;
 using namespace xivo_hip::capi;
 
 namespace {
-
-// a slice of recorded frames and of the context's filters (an empty slice is fine)
-bool bad_slice(xivo_hip_ctx* c, int b0, int nb, int t0, int nt) {
-  return bad_range(c, b0, nb) || !c->innov_rec || t0 < 0 || nt < 0 || t0 > c->innov_n || nt > c->innov_n - t0;
-}
 
 static_assert(LEAD_K <= 64, "innov_record_kernel: one lane of a wave per column of the lead block");
 // output staging of xivo_hip_innov_stats, sized once for the largest slice: per frame and per filter a sum, a dof and a count
@@ -27,26 +20,16 @@ extern "C" {
 int xivo_hip_innov_config(xivo_hip_ctx* c, const xivo_innov_opts* o) {
   if (!c || !o || o->T_max < 0) return XIVO_HIP_ERR_INVALID;
   size_t n_rec = 0;
-  if (o->T_max > 0) {
-    n_rec = (size_t)o->T_max * (size_t)c->Bmax;   // (two ints: no overflow in 64 bits)
-    if (n_rec > (size_t)INT64_MAX / sizeof(xivo_innov_rec)) return XIVO_HIP_ERR_INVALID;
-  }
+  if (o->T_max > 0 && !FrameLog::fits(o->T_max, c->Bmax, sizeof(xivo_innov_rec), &n_rec)) return XIVO_HIP_ERR_INVALID;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   HIP_TRY(hipStreamSynchronize(c->stream));   // a record launch may still be writing the blocks given back here
-  c->mem.release(&c->innov_rec, &c->innov_io);
-  c->innov_T = 0; c->innov_n = 0;
-  c->innov_ts.clear();
-  if (o->T_max == 0) return XIVO_HIP_OK;
-  int rc = c->mem.raw(&c->innov_rec, n_rec);
-  if (!rc) rc = c->mem.raw(&c->innov_io, ((size_t)o->T_max + (size_t)c->Bmax) * 2 * sizeof(double) * 2);
-  if (rc) { c->mem.release(&c->innov_rec, &c->innov_io); return rc; }
-  c->innov_T = o->T_max;
-  return XIVO_HIP_OK;
+  return log_realloc(c, c->innov_log, o->T_max, &c->innov_rec, n_rec, &c->innov_io,
+                     ((size_t)o->T_max + (size_t)c->Bmax) * 2 * sizeof(double) * 2);
 }
 
 int xivo_hip_innov_record(xivo_hip_ctx* c, int B, long long ts_ns, int* frame_out) {
-  if (!c || B <= 0 || B > c->Bmax || !c->innov_rec || !c->dx_current(B) || c->rows.rows() <= 0) return XIVO_HIP_ERR_INVALID;
-  if (c->innov_n >= c->innov_T) return XIVO_HIP_ERR_FULL;
+  if (!c || B <= 0 || B > c->Bmax || !c->innov_log.configured() || !c->dx_current(B) || c->rows.rows() <= 0) return XIVO_HIP_ERR_INVALID;
+  if (c->innov_log.full()) return XIVO_HIP_ERR_FULL;
   const StagedRows& r = c->rows;
   const int M = r.rows(), N = c->N;
   if (innov_record_lds(M, N) > 48 * 1024) return XIVO_HIP_ERR_UNSUPPORTED;
@@ -65,7 +48,7 @@ int xivo_hip_innov_record(xivo_hip_ctx* c, int B, long long ts_ns, int* frame_ou
   if (r.has_lead()) { c->Hlead.to(a.lead, a.strideLead, a.ldlead); a.lead_k = LEAD_K; }
   c->inn.to(a.inn, a.strideInn); c->diagR.to(a.diagR, a.strideR); c->err.to(a.err, a.strideErr);
   a.status = c->status; a.ldlt_used = c->ldlt_used; a.M = M; a.N = N;
-  a.rec = c->innov_rec + (size_t)c->innov_n * c->Bmax;
+  a.rec = c->innov_rec + FrameLog::at(c->innov_log.count(), c->Bmax, 0);
   {
     // per filter: dx, inn and diagR once, the rows in their representation, the record out
     const double rows_bytes = a.dense_all ? 8.0 * M * N
@@ -73,40 +56,34 @@ int xivo_hip_innov_record(xivo_hip_ctx* c, int B, long long ts_ns, int* frame_ou
     StageTimer st(c, ST_OTHER, 0.0, "innov_record_kernel", (double)B * (8.0 * N + 16.0 * M + rows_bytes + sizeof(xivo_innov_rec)));
     if (launch_innov_record(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
   }
-  if (frame_out) *frame_out = c->innov_n;
-  c->innov_ts.push_back(ts_ns);
-  c->innov_n++;
+  log_commit(c->innov_log, ts_ns, frame_out);
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_innov_count(xivo_hip_ctx* c) {
-  if (!c || !c->innov_rec) return XIVO_HIP_ERR_INVALID;
-  return c->innov_n;
+  if (!c || !c->innov_log.configured()) return XIVO_HIP_ERR_INVALID;
+  return c->innov_log.count();
 }
 
 int xivo_hip_innov_reset(xivo_hip_ctx* c) {
-  if (!c || !c->innov_rec) return XIVO_HIP_ERR_INVALID;
-  c->innov_n = 0;
-  c->innov_ts.clear();
+  if (!c || !c->innov_log.configured()) return XIVO_HIP_ERR_INVALID;
+  c->innov_log.reset();
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_innov_read(xivo_hip_ctx* c, int b0, int nb, int t0, int nt, xivo_innov_rec* recs, long long* ts) {
-  if (!c || bad_slice(c, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
-  if (ts) for (int t = 0; t < nt; ++t) ts[t] = c->innov_ts[(size_t)t0 + t];
+  if (!c || bad_slice(c, c->innov_log, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
+  c->innov_log.stamps(t0, nt, ts);
   if (nb == 0 || nt == 0 || !recs) return XIVO_HIP_OK;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  // frame-major storage: the filters [b0, b0 + nb) of one frame are contiguous, frames are Bmax entries apart
-  const size_t at = (size_t)t0 * c->Bmax + b0;
-  HIP_TRY(hipMemcpy2DAsync(recs, (size_t)nb * sizeof(xivo_innov_rec), c->innov_rec + at, (size_t)c->Bmax * sizeof(xivo_innov_rec),
-                           (size_t)nb * sizeof(xivo_innov_rec), nt, hipMemcpyDeviceToHost, c->stream));
+  if (d2h_frames(c, recs, c->innov_rec, sizeof(xivo_innov_rec), b0, nb, t0, nt)) return XIVO_HIP_ERR_HIP;
   HIP_TRY(hipStreamSynchronize(c->stream));
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_innov_stats(xivo_hip_ctx* c, int b0, int nb, int t0, int nt, double* frame_nis, long long* frame_dof,
                          int* frame_used, double* filt_nis, long long* filt_dof, int* filt_used) {
-  if (!c || bad_slice(c, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
+  if (!c || bad_slice(c, c->innov_log, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
   if (nb == 0 || nt == 0) return XIVO_HIP_OK;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   static_assert(kStatBytes <= 4 * sizeof(double), "the staging xivo_hip_innov_config allocates holds every output");
@@ -115,7 +92,7 @@ int xivo_hip_innov_stats(xivo_hip_ctx* c, int b0, int nb, int t0, int nt, double
   double* d_nis = reinterpret_cast<double*>(c->innov_io);
   long long* d_dof = reinterpret_cast<long long*>(d_nis + n);
   int* d_used = reinterpret_cast<int*>(d_dof + n);
-  const long at = (long)t0 * c->Bmax + b0;
+  const long at = (long)FrameLog::at(t0, c->Bmax, b0);
   InnovStatsArgs f{c->innov_rec, at, (long)c->Bmax, 1, nt, nb, d_nis, d_dof, d_used};                 // a frame: its filters
   InnovStatsArgs g{c->innov_rec, at, 1, (long)c->Bmax, nb, nt, d_nis + nt, d_dof + nt, d_used + nt};  // a filter: its frames
   if (launch_innov_stats(f, c->stream) || launch_innov_stats(g, c->stream)) return XIVO_HIP_ERR_HIP;

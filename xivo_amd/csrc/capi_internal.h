@@ -1,5 +1,6 @@
 // Host-side internals shared by the translation units of the C ABI (include/xivo_hip.h):
-//   capi.hip            context, P residency, resident device buffers, timing / profile, the helpers declared below
+//   capi.hip            context, P residency, resident device buffers, timing / profile, the helpers declared below (among
+//                       them what the per-frame logs share: the slice check, the frame-major read, the NEES staging)
 //   capi_update.hip     route table, measurement hand-over, the update pipelines, the L D L^T fallback, the one-filter call
 //   capi_glevel.hip     feature level: scene, Jacobians, gate, stacking, OOS rows, RANSAC, loop closure, Givens / QR, edits
 //   capi_propagate.hip  propagation
@@ -15,7 +16,7 @@
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
 //
-// Two things every one of those files goes through:
+// Three things those files go through:
 //   c->mem (device_buffers.h)  owns every device block of the context. Allocation is c->mem.zeroed / raw / grow, re-sizing a
 //                              group of buffers is c->mem.release + allocation, xivo_hip_destroy is c->mem.free_all(). The only
 //                              hipMalloc / hipFree of the C ABI are the owner's two function pointers (capi.hip) and the
@@ -24,6 +25,8 @@
 //                              ONE value. The context holds its buffers as such views, from(b0) is the view of the filters from
 //                              b0 on, to(...) writes the three into a kernel argument struct - a pointer cannot be passed with
 //                              another buffer's stride. A descriptor only: owns nothing, allocates nothing.
+//   FrameLog (frame_log.h)     the host bookkeeping of a per-frame log: capacity, frames written, stamps, the slice check. The
+//                              four logs (capi_traj / _map / _innov / _trajsim.hip) hold one each next to their device blocks.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -39,6 +42,7 @@
 #include "fused_update.h"
 #include "staged_rows.h"
 #include "device_buffers.h"
+#include "frame_log.h"
 
 namespace xivo_hip::capi {
 
@@ -172,25 +176,27 @@ struct xivo_hip_ctx {
   double* init_z = nullptr;         // [Bmax]
   xivo_adapt_depth_opts adapt{};
   bool adapt_on = false;
-  // trajectory log (xivo_hip_traj_*, capi_traj.hip): [traj_T][Bmax] records and packed covariance blocks of traj_cols, frames
-  // [0, traj_n) written; null until xivo_hip_traj_config. traj_io: per-call staging of xivo_hip_traj_nees / xivo_hip_traj_score
+  // The three per-frame logs below and the trajectory producer's ground truth: device pointers, options, the FrameLog (frame_log.h:
+  // capacity in frames, frames written, stamps), staging. A log's blocks are allocated exactly while its FrameLog is configured.
+  // trajectory log (xivo_hip_traj_*, capi_traj.hip): [capacity][Bmax] records and packed covariance blocks of traj_cols.
+  // traj_io: per-call staging of xivo_hip_traj_nees / xivo_hip_traj_score
   xivo_traj_rec* traj_rec = nullptr; double* traj_cov = nullptr;
-  int traj_T = 0, traj_n = 0, traj_ncols = 0, traj_cols[XIVO_TRAJ_MAX_COLS] = {0};
-  std::vector<long long> traj_ts;
+  int traj_ncols = 0, traj_cols[XIVO_TRAJ_MAX_COLS] = {0};
+  xivo_hip::capi::FrameLog traj_log;
   char* traj_io = nullptr; size_t traj_io_cap = 0;
-  // landmark log (xivo_hip_map_*, capi_map.hip): [map_T][Bmax][map_nout] entries and [map_T][Bmax] counts, frames [0, map_n)
-  // written; null until xivo_hip_map_config. map_io: per-call staging of xivo_hip_map_nees
+  // landmark log (xivo_hip_map_*, capi_map.hip): [capacity][Bmax][map_nout] entries and [capacity][Bmax] counts. map_io: per-call
+  // staging of xivo_hip_map_nees
   xivo_map_pt* map_pts = nullptr; int* map_npts = nullptr;
-  int map_T = 0, map_n = 0, map_nout = 0; unsigned map_flags = 0;
-  std::vector<long long> map_ts;
+  int map_nout = 0; unsigned map_flags = 0;
+  xivo_hip::capi::FrameLog map_log;
   char* map_io = nullptr; size_t map_io_cap = 0;
-  // innovation log (xivo_hip_innov_*, capi_innov.hip): [innov_T][Bmax] records, frames [0, innov_n) written; null until
-  // xivo_hip_innov_config, which also allocates innov_io, the output staging of xivo_hip_innov_stats. dx_ok[b]: the err
-  // buffer of filter b holds the dx of the rows staged for it right now (set by the update calls for the filters they update;
-  // cleared by absorb, new rows, restore_P) - a record of filters [0, B) needs it of every one of them
-  xivo_innov_rec* innov_rec = nullptr; char* innov_io = nullptr;
-  int innov_T = 0, innov_n = 0;
-  std::vector<long long> innov_ts;
+  // innovation log (xivo_hip_innov_*, capi_innov.hip): [capacity][Bmax] records. innov_io: the output staging of
+  // xivo_hip_innov_stats, allocated by xivo_hip_innov_config for the largest slice. dx_ok[b]: the err buffer of filter b holds the
+  // dx of the rows staged for it right now (set by the update calls for the filters they update; cleared by absorb, new rows,
+  // restore_P) - a record of filters [0, B) needs it of every one of them
+  xivo_innov_rec* innov_rec = nullptr;
+  xivo_hip::capi::FrameLog innov_log;
+  char* innov_io = nullptr;
   std::vector<char> dx_ok;
   void dx_set(int b0, int nb, bool v) { if (dx_ok.size() != (size_t)Bmax) dx_ok.assign((size_t)Bmax, 0); std::fill_n(dx_ok.begin() + b0, nb, (char)v); }
   void dx_clear() { std::fill(dx_ok.begin(), dx_ok.end(), (char)0); }
@@ -224,15 +230,16 @@ struct xivo_hip_ctx {
   // the camera of xivo_hip_pcw_camera in place of the pinhole of pcw_opts (pcw_use_cam), and its radius guard
   bool pcw_use_cam = false; xivo_cam pcw_cam{}; double pcw_max_radius = 0.0;
   // trajectory producer (xivo_hip_trajsim_*, capi_trajsim.hip): curve / rate per filter [Bmax], the last frame's records
-  // [Bmax][n_max] (read as [B][n]) and camera poses [Bmax][12], the ground-truth log [T_max][Bmax][12] with frames [0, ts_T)
-  // written, the device copy of the propagation noise (Qimu 144 | Qmodel 529) with the host copy it was uploaded from; null until
-  // xivo_hip_trajsim_config. ts_B / ts_n: the shape of the last frame (ts_B = 0: none), ts_fresh: its records may still be
-  // consumed by xivo_hip_propagate_resident
+  // [Bmax][n_max] (read as [B][n]) and camera poses [Bmax][12], the ground-truth log ts_gt [T_max][Bmax][12] with its FrameLog
+  // ts_log (no stamps: it commits 0), the device copy of the propagation noise (Qimu 144 | Qmodel 529) with the host copy it was
+  // uploaded from; null until xivo_hip_trajsim_config. ts_B / ts_n: the shape of the last frame (ts_B = 0: none), ts_fresh: its
+  // records may still be consumed by xivo_hip_propagate_resident
   xivo_trajsim_opts ts_opts{};
   int* ts_motion = nullptr; double* ts_rate = nullptr; xivo_imu_in* ts_recs = nullptr; double* ts_gsc = nullptr;
-  double* ts_gt = nullptr; double* ts_Q = nullptr;
+  double* ts_Q = nullptr;
+  double* ts_gt = nullptr; xivo_hip::capi::FrameLog ts_log;
   xivo_prop_opts ts_prop{}; bool ts_prop_valid = false;
-  int ts_T = 0, ts_B = 0, ts_n = 0; bool ts_fresh = false;
+  int ts_B = 0, ts_n = 0; bool ts_fresh = false;
   std::vector<char> hstage;                        // host staging of d2h_rows
   char* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
   // one-filter plumbing call (xivo_hip_update_joseph_host): page-locked, device-mapped staging block owned by the context,
@@ -319,6 +326,36 @@ int ensure_staging(xivo_hip_ctx* c, size_t elems);
 int d2h_rows(xivo_hip_ctx* c, void* dst, size_t hpitch, const void* src, size_t dpitch, size_t width, size_t rows);
 int h2d_packed(xivo_hip_ctx* c, double* dst, const double* src, int nb, int rows, int cols, long stride, int ld);
 int d2h_packed(xivo_hip_ctx* c, double* dst, const double* src, int nb, int rows, int cols, long stride, int ld);
+// what the per-frame logs share (FrameLog, frame_log.h; c is not null).
+// the one slice check: filters [b0, b0 + nb) of the context, a configured log, frames [t0, t0 + nt) of its written ones
+inline bool bad_slice(xivo_hip_ctx* c, const FrameLog& log, int b0, int nb, int t0, int nt) {
+  return bad_range(c, b0, nb) || !log.configured() || !log.slice_ok(t0, nt);
+}
+// that slice of a frame-major block src of `per` bytes per filter entry to dst [nt][nb], enqueued (dst null: nothing)
+int d2h_frames(xivo_hip_ctx* c, void* dst, const void* src, size_t per, int b0, int nb, int t0, int nt);
+// the two blocks of a log for T_max frames (the stream must be idle): the old ones given back and the log emptied, then for
+// T_max > 0 na / nb elements behind *a / *b - both or neither - and the log configured
+template <class A, class B> int log_realloc(xivo_hip_ctx* c, FrameLog& log, int T_max, A** a, size_t na, B** b, size_t nb) {
+  c->mem.release(a, b);
+  log.configure(0);
+  if (T_max == 0) return XIVO_HIP_OK;
+  int rc = c->mem.raw(a, na);
+  if (!rc) rc = c->mem.raw(b, nb);
+  if (rc) c->mem.release(a, b); else log.configure(T_max);
+  return rc;
+}
+// the tail of a record call whose launch went out: the frame counts, with its stamp
+inline void log_commit(FrameLog& log, long long ts_ns, int* frame_out) { const int t = log.commit(ts_ns); if (frame_out) *frame_out = t; }
+// The per-call staging of a NEES entry point (xivo_hip_traj_nees, xivo_hip_map_nees) in the log's growing block io: gt in | err,
+// nees, anees out (doubles), then n_used (ints), for nt frames of `per` entries with gt_w / err_w doubles an entry.
+struct NeesStaging {
+  double *gt, *err, *nees, *anees; int* n_used;
+  size_t n, nt, err_w;
+  // lay the block out, grow it and enqueue the upload of gt
+  int up(xivo_hip_ctx* c, char** io, size_t* io_cap, size_t per, int nt_, int gt_w, int err_w_, const double* gt_h);
+  // behind the kernels: the downloads the caller asked for (null: not that one), then the synchronise
+  int down(xivo_hip_ctx* c, double* err_h, double* nees_h, double* anees_h, int* n_used_h) const;
+};
 
 // ---- capi_update.hip
 int stage_measurements(xivo_hip_ctx* c, int b0, int nb, int M, const double* dH, long strideH, int ldh,

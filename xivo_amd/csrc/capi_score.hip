@@ -26,7 +26,7 @@ extern "C" {
 int xivo_hip_traj_score(xivo_hip_ctx* c, int b0, int nb, int t0, int nt, const double* gt, const xivo_traj_score_opts* o,
                         xivo_traj_score* out) {
   if (!c || !gt || !o || !out || o->rpe_lag < 0) return XIVO_HIP_ERR_INVALID;
-  if (bad_range(c, b0, nb) || !c->traj_rec || t0 < 0 || nt < 0 || t0 > c->traj_n || nt > c->traj_n - t0) return XIVO_HIP_ERR_INVALID;
+  if (bad_slice(c, c->traj_log, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
   if (nt == 0) {
     for (int b = 0; b < nb; ++b) out[b] = empty_score();

@@ -18,7 +18,7 @@ namespace {
 void trajsim_release(xivo_hip_ctx* c) {
   c->mem.release(&c->ts_motion, &c->ts_rate, &c->ts_recs, &c->ts_gsc, &c->ts_gt, &c->ts_Q);
   c->ts_opts = xivo_trajsim_opts{}; c->ts_prop_valid = false;
-  c->ts_T = 0; c->ts_B = 0; c->ts_n = 0; c->ts_fresh = false;
+  c->ts_log.configure(0); c->ts_B = 0; c->ts_n = 0; c->ts_fresh = false;
 }
 
 bool trajsim_ready(const xivo_hip_ctx* c) { return c && c->ts_recs && c->ts_opts.n_max > 0; }
@@ -65,7 +65,7 @@ int xivo_hip_trajsim_config(xivo_hip_ctx* c, const xivo_trajsim_opts* o) {
   if (!rc) rc = c->mem.zeroed(&c->ts_Q, (size_t)144 + 529);
   if (!rc) rc = ensure_staging(c, 2 * (size_t)529 * B);   // Phi | P_mm of xivo_hip_propagate_resident, at their final size
   if (rc) { trajsim_release(c); return rc; }
-  c->ts_opts = *o;
+  c->ts_opts = *o; c->ts_log.configure(o->T_max);
   return XIVO_HIP_OK;
 }
 
@@ -88,18 +88,18 @@ int xivo_hip_trajsim_frame(xivo_hip_ctx* c, int B, unsigned long long k0, int n)
   if (n > 0 && (k0 + (unsigned long long)n < k0 || !(trajsim_dt(k0 + 1, c->ts_opts.imu_dt) > 0.0) ||
                 !(trajsim_dt(k0 + (unsigned long long)n, c->ts_opts.imu_dt) > 0.0)))
     return XIVO_HIP_ERR_INVALID;
-  if (c->ts_T >= c->ts_opts.T_max) return XIVO_HIP_ERR_FULL;
+  if (c->ts_log.full()) return XIVO_HIP_ERR_FULL;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   TrajsimArgs a{};
   a.m = model_of(c->ts_opts); a.motion = c->ts_motion; a.rate = c->ts_rate; a.k0 = k0; a.n = n; a.batch = B;
-  a.recs = c->ts_recs; a.gsc = c->ts_gsc; a.gt = c->ts_gt + (size_t)c->ts_T * c->Bmax * 12;
+  a.recs = c->ts_recs; a.gsc = c->ts_gsc; a.gt = c->ts_gt + FrameLog::at(c->ts_log.count(), c->Bmax, 0) * 12;
   c->ts_B = 0; c->ts_fresh = false;   // (whatever the blocks held is being overwritten)
   {
     // per filter: n records of 104 bytes and two poses of 96 bytes out, curve and rate in
     StageTimer st(c, ST_OTHER, 0.0, "trajsim_frame_kernel", (double)B * (n * sizeof(xivo_imu_in) + 2.0 * 96.0 + 12.0));
     if (launch_trajsim_frame(a, c->stream)) return XIVO_HIP_ERR_HIP;
   }
-  c->ts_B = B; c->ts_n = n; c->ts_fresh = n > 0; c->ts_T += 1;
+  c->ts_B = B; c->ts_n = n; c->ts_fresh = n > 0; c->ts_log.commit(0);
   return XIVO_HIP_OK;
 }
 
@@ -141,18 +141,18 @@ int xivo_hip_trajsim_get(xivo_hip_ctx* c, int b0, int nb, xivo_imu_in* recs, dou
 
 int xivo_hip_trajsim_get_gt(xivo_hip_ctx* c, int b0, int nb, int t0, int nt, double* gt) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (bad_range(c, b0, nb) || !trajsim_ready(c) || t0 < 0 || nt < 0 || t0 > c->ts_T || nt > c->ts_T - t0 || (nb > 0 && nt > 0 && !gt))
+  if (!c || bad_slice(c, c->ts_log, b0, nb, t0, nt) || (nb > 0 && nt > 0 && !gt))
     return XIVO_HIP_ERR_INVALID;
   if (nb == 0 || nt == 0) return XIVO_HIP_OK;
   // frame t of the log is [Bmax][12]: nt rows of nb * 96 bytes, Bmax * 96 apart
-  return d2h_rows(c, gt, (size_t)nb * 96, c->ts_gt + ((size_t)t0 * c->Bmax + b0) * 12, (size_t)c->Bmax * 96, (size_t)nb * 96, nt);
+  return d2h_rows(c, gt, (size_t)nb * 96, c->ts_gt + FrameLog::at(t0, c->Bmax, b0) * 12, (size_t)c->Bmax * 96, (size_t)nb * 96, nt);
 }
 
-int xivo_hip_trajsim_count(xivo_hip_ctx* c) { return trajsim_ready(c) ? c->ts_T : 0; }
+int xivo_hip_trajsim_count(xivo_hip_ctx* c) { return trajsim_ready(c) ? c->ts_log.count() : 0; }
 
 int xivo_hip_trajsim_reset(xivo_hip_ctx* c) {
   if (!trajsim_ready(c) || track_block_frame_open(c)) return XIVO_HIP_ERR_INVALID;
-  c->ts_T = 0; c->ts_B = 0; c->ts_n = 0; c->ts_fresh = false;
+  c->ts_log.reset(); c->ts_B = 0; c->ts_n = 0; c->ts_fresh = false;
   return XIVO_HIP_OK;
 }
 

@@ -75,6 +75,9 @@ struct TrajNeesArgs {
   const double* gt; double* err6; double* nees; double* anees; int* n_used;
 };
 int launch_traj_nees(const TrajNeesArgs& a, hipStream_t s);
+// anees [nt], n_used [nt] = mean and number of the finite values of every frame of nees [nt][per], in one fixed summation order
+// (what launch_traj_nees and launch_map_nees both end with)
+int launch_frame_anees(const double* nees, long per, int nt, double* anees, int* n_used, hipStream_t s);
 
 // ================================================================ score_kernels.hip: trajectory score (capi_score.hip)
 

@@ -253,32 +253,6 @@ __global__ __launch_bounds__(256) void map_nees_kernel(MapNeesArgs a) {
   a.nees[id] = nees;
 }
 
-// One workgroup per frame: every thread adds the finite entries tid, tid + 256, ... of the frame's [nb][n_out] values in
-// that order, then a fixed-shape tree over the 256 partial sums - the same additions in the same order on every call.
-__global__ __launch_bounds__(256) void map_anees_kernel(MapNeesArgs a) {
-  __shared__ double ssum[256];
-  __shared__ int scnt[256];
-  const int t = blockIdx.x, tid = threadIdx.x;
-  const long per = (long)a.nb * a.n_out;
-  const double* v = a.nees + (long)t * per;
-  double s = 0.0;
-  int c = 0;
-  for (long i = tid; i < per; i += 256) {
-    const double x = v[i];
-    if (fabs(x) < INFINITY) { s += x; ++c; }
-  }
-  ssum[tid] = s; scnt[tid] = c;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (tid < h) { ssum[tid] += ssum[tid + h]; scnt[tid] += scnt[tid + h]; }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    a.anees[t] = scnt[0] > 0 ? ssum[0] / (double)scnt[0] : NAN;
-    a.n_used[t] = scnt[0];
-  }
-}
-
 }  // namespace
 
 #define CHECK_LAUNCH() return (int)hipGetLastError()
@@ -295,8 +269,7 @@ int launch_map_nees(const MapNeesArgs& a, hipStream_t s) {
   if (n <= 0) return 0;
   hipLaunchKernelGGL(map_nees_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
   if (hipGetLastError() != hipSuccess) return (int)hipErrorLaunchFailure;
-  hipLaunchKernelGGL(map_anees_kernel, dim3(a.nt), dim3(256), 0, s, a);
-  CHECK_LAUNCH();
+  return launch_frame_anees(a.nees, (long)a.nb * a.n_out, a.nt, a.anees, a.n_used, s);   // (traj_kernels.hip)
 }
 
 }  // namespace xivo_hip

@@ -104,17 +104,18 @@ __global__ __launch_bounds__(256) void traj_nees_kernel(TrajNeesArgs a) {
   a.nees[id] = ok ? nees : NAN;
 }
 
-// One workgroup per frame: every thread adds the finite entries of filters tid, tid + 256, ... in that order, then a
-// fixed-shape tree over the 256 partial sums - the same additions in the same order whatever the machine does.
-__global__ __launch_bounds__(256) void traj_anees_kernel(TrajNeesArgs a) {
+// The mean of the finite values of every frame, v [nt][per] -> anees [nt], n_used [nt] (the trajectory log's [nb] NEES, the
+// landmark log's [nb][n_out]). One workgroup per frame: every thread adds the finite entries tid, tid + 256, ... in that order,
+// then a fixed-shape tree over the 256 partial sums - the same additions in the same order whatever the machine does.
+__global__ __launch_bounds__(256) void frame_anees_kernel(const double* nees, long per, double* anees, int* n_used) {
   __shared__ double ssum[256];
   __shared__ int scnt[256];
   const int t = blockIdx.x, tid = threadIdx.x;
-  const double* v = a.nees + (long)t * a.nb;
+  const double* v = nees + (long)t * per;
   double s = 0.0;
   int c = 0;
-  for (int b = tid; b < a.nb; b += 256) {
-    const double x = v[b];
+  for (long i = tid; i < per; i += 256) {
+    const double x = v[i];
     if (fabs(x) < INFINITY) { s += x; ++c; }
   }
   ssum[tid] = s; scnt[tid] = c;
@@ -124,8 +125,8 @@ __global__ __launch_bounds__(256) void traj_anees_kernel(TrajNeesArgs a) {
     __syncthreads();
   }
   if (tid == 0) {
-    a.anees[t] = scnt[0] > 0 ? ssum[0] / (double)scnt[0] : NAN;
-    a.n_used[t] = scnt[0];
+    anees[t] = scnt[0] > 0 ? ssum[0] / (double)scnt[0] : NAN;
+    n_used[t] = scnt[0];
   }
 }
 
@@ -144,7 +145,12 @@ int launch_traj_nees(const TrajNeesArgs& a, hipStream_t s) {
   if (n <= 0) return 0;
   hipLaunchKernelGGL(traj_nees_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
   if (hipGetLastError() != hipSuccess) return (int)hipErrorLaunchFailure;
-  hipLaunchKernelGGL(traj_anees_kernel, dim3(a.nt), dim3(256), 0, s, a);
+  return launch_frame_anees(a.nees, a.nb, a.nt, a.anees, a.n_used, s);
+}
+
+int launch_frame_anees(const double* nees, long per, int nt, double* anees, int* n_used, hipStream_t s) {
+  if (nt <= 0 || per <= 0) return 0;
+  hipLaunchKernelGGL(frame_anees_kernel, dim3(nt), dim3(256), 0, s, nees, per, anees, n_used);
   CHECK_LAUNCH();
 }
 

@@ -906,6 +906,26 @@ class Context:
         self._check(self.lib.xivo_hip_get_H(self.h, b, None, _ptr(H), M, _ptr(inn), _ptr(dR)))
         return H.T.copy(), inn, dR
 
+    # ---- what the per-frame logs share: `log` is "traj", "map" or "innov" (xivo_hip_<log>_record / _count / _reset; _log_span
+    # also takes "trajsim", whose count is 0 where the others' is an error)
+    def _log_record(self, log, ts_ns, B):
+        k = C.c_int(-1)
+        self._check(getattr(self.lib, "xivo_hip_%s_record" % log)(self.h, self.batch if B is None else int(B), int(ts_ns), C.byref(k)))
+        return k.value
+
+    def _log_count(self, log):
+        n = getattr(self.lib, "xivo_hip_%s_count" % log)(self.h)
+        if n < 0:
+            self._check(n)
+        return n
+
+    def _log_reset(self, log):
+        self._check(getattr(self.lib, "xivo_hip_%s_reset" % log)(self.h))
+
+    def _log_span(self, log, b0, nb, t0, nt):
+        """(nb, nt) of a slice: by default the filters from b0 on and the recorded frames from t0 on"""
+        return (self.batch - b0 if nb is None else int(nb)), (self._log_count(log) - t0 if nt is None else int(nt))
+
     # ---- trajectory log (xivo_hip_traj_*)
     def traj_config(self, T_max, cols=()):
         """a device log of T_max frames: per frame and filter the motion state and the packed lower triangle of
@@ -920,23 +940,17 @@ class Context:
 
     def traj_record(self, ts_ns=0, B=None):
         """append one frame (asynchronous) -> its index"""
-        k = C.c_int(-1)
-        self._check(self.lib.xivo_hip_traj_record(self.h, self.batch if B is None else int(B), int(ts_ns), C.byref(k)))
-        return k.value
+        return self._log_record("traj", ts_ns, B)
 
     def traj_count(self):
-        n = self.lib.xivo_hip_traj_count(self.h)
-        if n < 0:
-            self._check(n)
-        return n
+        return self._log_count("traj")
 
     def traj_reset(self):
-        self._check(self.lib.xivo_hip_traj_reset(self.h))
+        self._log_reset("traj")
 
     def traj_read(self, b0=0, nb=None, t0=0, nt=None):
         """-> (recs [nt, nb] traj_dtype, cov [nt, nb, n, n] symmetric (from the packed lower triangle), ts [nt] ns)"""
-        nb = self.batch - b0 if nb is None else int(nb)
-        nt = self.traj_count() - t0 if nt is None else int(nt)
+        nb, nt = self._log_span("traj", b0, nb, t0, nt)
         n = int(self.traj_cols.size)
         recs = np.zeros((nt, nb), dtype=traj_dtype)
         packed = np.zeros((nt, nb, n * (n + 1) // 2))
@@ -971,8 +985,7 @@ class Context:
             g[:, :, 9:] = np.asarray(gt[1], dtype=np.float64).reshape(R.shape[:2] + (3,))
         else:
             g = _f64(gt)
-        nb = self.batch - b0 if nb is None else int(nb)
-        nt = self.traj_count() - t0 if nt is None else int(nt)
+        nb, nt = self._log_span("traj", b0, nb, t0, nt)
         if g.shape != (nt, nb, 12):
             raise ValueError("gt must be [nt = %d, nb = %d, 12], got %s" % (nt, nb, g.shape))
         o = np.zeros(1, dtype=traj_score_opts_dtype)
@@ -993,23 +1006,17 @@ class Context:
 
     def map_record(self, ts_ns=0, B=None):
         """append one frame (asynchronous) -> its index"""
-        k = C.c_int(-1)
-        self._check(self.lib.xivo_hip_map_record(self.h, self.batch if B is None else int(B), int(ts_ns), C.byref(k)))
-        return k.value
+        return self._log_record("map", ts_ns, B)
 
     def map_count(self):
-        n = self.lib.xivo_hip_map_count(self.h)
-        if n < 0:
-            self._check(n)
-        return n
+        return self._log_count("map")
 
     def map_reset(self):
-        self._check(self.lib.xivo_hip_map_reset(self.h))
+        self._log_reset("map")
 
     def map_read(self, b0=0, nb=None, t0=0, nt=None):
         """-> (pts [nt, nb, n_out] map_pt_dtype, n_pts [nt, nb], ts [nt] ns); slots behind n_pts are zeros with pos = sind = -1"""
-        nb = self.batch - b0 if nb is None else int(nb)
-        nt = self.map_count() - t0 if nt is None else int(nt)
+        nb, nt = self._log_span("map", b0, nb, t0, nt)
         pts = np.zeros((nt, nb, self.map_n_out), dtype=map_pt_dtype)
         n_pts = np.zeros((nt, nb), dtype=np.int32)
         ts = np.zeros(nt, dtype=np.int64)
@@ -1038,23 +1045,17 @@ class Context:
 
     def innov_record(self, ts_ns=0, B=None):
         """append one frame (asynchronous; after the update, before absorb_error) -> its index"""
-        k = C.c_int(-1)
-        self._check(self.lib.xivo_hip_innov_record(self.h, self.batch if B is None else int(B), int(ts_ns), C.byref(k)))
-        return k.value
+        return self._log_record("innov", ts_ns, B)
 
     def innov_count(self):
-        n = self.lib.xivo_hip_innov_count(self.h)
-        if n < 0:
-            self._check(n)
-        return n
+        return self._log_count("innov")
 
     def innov_reset(self):
-        self._check(self.lib.xivo_hip_innov_reset(self.h))
+        self._log_reset("innov")
 
     def innov_read(self, b0=0, nb=None, t0=0, nt=None):
         """-> (recs [nt, nb] innov_rec_dtype, ts [nt] ns)"""
-        nb = self.batch - b0 if nb is None else int(nb)
-        nt = self.innov_count() - t0 if nt is None else int(nt)
+        nb, nt = self._log_span("innov", b0, nb, t0, nt)
         recs = np.zeros((nt, nb), dtype=innov_rec_dtype)
         ts = np.zeros(nt, dtype=np.int64)
         self._check(self.lib.xivo_hip_innov_read(self.h, int(b0), nb, int(t0), nt, _ptr(recs), _ptr(ts)))
@@ -1064,8 +1065,7 @@ class Context:
         """sums over the records with flags = 0 and a finite nis -> dict: frame_nis / frame_dof / frame_used [nt] over the
         slice's filters, filt_nis / filt_dof / filt_used [nb] over its frames; frame_nis / frame_dof is the figure to hold
         against 1"""
-        nb = self.batch - b0 if nb is None else int(nb)
-        nt = self.innov_count() - t0 if nt is None else int(nt)
+        nb, nt = self._log_span("innov", b0, nb, t0, nt)
         out = {"frame_nis": np.zeros(nt), "frame_dof": np.zeros(nt, dtype=np.int64), "frame_used": np.zeros(nt, dtype=np.int32),
                "filt_nis": np.zeros(nb), "filt_dof": np.zeros(nb, dtype=np.int64), "filt_used": np.zeros(nb, dtype=np.int32)}
         self._check(self.lib.xivo_hip_innov_stats(self.h, int(b0), nb, int(t0), nt, _ptr(out["frame_nis"]), _ptr(out["frame_dof"]),
@@ -1221,8 +1221,7 @@ class Context:
 
     def trajsim_get_gt(self, b0=0, nb=None, t0=0, nt=None):
         """the ground-truth log -> gt [nt, nb, 12] (Rsb column-major, Tsb): what traj_score / traj_nees take packed"""
-        nb = self.batch - b0 if nb is None else int(nb)
-        nt = self.trajsim_count() - t0 if nt is None else int(nt)
+        nb, nt = self._log_span("trajsim", b0, nb, t0, nt)
         gt = np.zeros((nt, nb, 12))
         self._check(self.lib.xivo_hip_trajsim_get_gt(self.h, int(b0), nb, int(t0), nt, _ptr(gt)))
         return gt
