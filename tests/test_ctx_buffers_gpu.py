@@ -163,6 +163,53 @@ def test_repeated_resize_does_not_accumulate(built, world):
     assert allocs[2] == allocs[0] == allocs[1], allocs
 
 
+@pytest.mark.parametrize("life", ["pool", "immediate"])
+def test_configure_frame_release_cycles_return_to_the_same_blocks(built, world, life):
+    """Every area that is configured and released by a call of its own - a device life cycle (the pool's, on a pool of 4 entries
+    and 2 anchors, or the immediate one), the point-cloud world, the trajectory producer, the three logs - gives back on its
+    zero call what its configure call took: after one resident frame and the zero calls the context owns what it owned after
+    the first such cycle. (The pool itself has no zero call: it is configured again, which releases it first.)"""
+    rng = np.random.default_rng(8)
+    Xs = rng.uniform(-3.0, 3.0, size=(B, 4, 3))
+    groups = np.zeros((B, NG), dtype=L.group_dtype)
+    groups["Rsb"][:] = np.eye(3).reshape(-1)
+    feats = np.zeros((B, NF), dtype=L.feat_dtype)
+    feats["sind"] = -1                                 # an empty scene: the life cycle fills it
+    prop = L.prop_options(np.eye(12) * 1e-4, np.eye(23) * 1e-6, (0.0, 0.0, -9.8))
+    allocs = []
+    with context(world) as ctx:
+        ctx.upload_P(world["P"])
+        ctx.set_scene(world["poses"], groups, feats)
+        for _ in range(3):
+            if life == "pool":
+                ctx.pool_config(4, 2)
+                ctx.pool_life_config(8)
+            else:
+                ctx.life_config(8)
+            ctx.pcw_config(4, CAM["fx"], CAM["fy"], CAM["cx"], CAM["cy"], CAM["cols"], CAM["rows"])
+            ctx.pcw_set_world(Xs)
+            ctx.trajsim_config(2, 2)
+            ctx.trajsim_set(["lissajous"] * B, np.full(B, 0.5))
+            ctx.traj_config(2, range(6)); ctx.map_config(2, NF); ctx.innov_config(2)
+            # one resident frame: nothing goes down, nothing comes back
+            ctx.trajsim_frame(0, 2)
+            ctx.propagate_resident(opts=prop)
+            ctx.pcw_tracks_resident(0.5, 3, 0)
+            ctx.pool_life_begin_tracks(NF) if life == "pool" else ctx.life_begin_tracks(NF)
+            ctx.filter_update(R_VIS, MH, MULT, 2, True)
+            ctx.innov_record(0)
+            ctx.absorb_error()
+            ctx.pool_life_end() if life == "pool" else ctx.life_end()
+            ctx.traj_record(0); ctx.map_record(0)
+            assert (ctx.traj_count(), ctx.map_count(), ctx.innov_count(), ctx.trajsim_count()) == (1, 1, 1, 1)
+            ctx.innov_config(0); ctx.map_config(0); ctx.traj_config(0)
+            ctx.trajsim_config(0)
+            ctx.pcw_config(0)
+            ctx.pool_life_config(0) if life == "pool" else ctx.life_config(0)
+            allocs.append(ctx.ctx_allocs())
+    assert allocs[1] == allocs[0] and allocs[2] == allocs[0], allocs
+
+
 def test_create_use_destroy_cycles(built, world):
     with context(world) as a, context(world) as b:
         la, lb = a.ctx_allocs(), b.ctx_allocs()

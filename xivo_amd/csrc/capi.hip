@@ -1,6 +1,6 @@
 // C ABI of the MI355X EKF measurement-update path (include/xivo_hip.h): the context, P residency, resident device buffers,
 // timing / profile, and the host helpers every part of the ABI shares (capi_internal.h). The update pipelines are in
-// capi_update.hip, the feature level in capi_glevel.hip, propagation in capi_propagate.hip, the trajectory log in capi_traj.hip, the landmark log in capi_map.hip. Host-side orchestration only:
+// capi_update.hip, the feature level in capi_glevel.hip, the other areas in the files capi_internal.h lists. Host-side orchestration only:
 // owns the device buffers of a batch of filters, sequences the kernels on one HIP stream, never throws and never aborts.
 #include <new>
 
@@ -12,13 +12,14 @@ using namespace xivo_hip::capi;
 namespace xivo_hip::capi {
 
 static int collect_profile(xivo_hip_ctx* c) {
-  if (c->pool_used == 0) return XIVO_HIP_OK;
+  Profiler& p = c->prof;
+  if (p.used == 0) return XIVO_HIP_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  for (size_t i = 0; i < c->pool_used; ++i) {
+  for (size_t i = 0; i < p.used; ++i) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->pool[i].a, c->pool[i].b) == hipSuccess) c->stage_ms[c->pool[i].stage] += ms;
+    if (hipEventElapsedTime(&ms, p.events[i].a, p.events[i].b) == hipSuccess) p.ms[p.events[i].stage] += ms;
   }
-  c->pool_used = 0;
+  p.used = 0;
   return XIVO_HIP_OK;
 }
 
@@ -30,6 +31,46 @@ int device_alloc(void** p, size_t bytes, int zero) {
   return XIVO_HIP_OK;
 }
 void device_free(void* p) { hipFree(p); }
+
+// ---- the double-buffered page-locked upload (the only page-locked blocks with an event each of the C ABI)
+int PinnedUpload::alloc(size_t bytes) {
+  int rc = XIVO_HIP_OK;
+  for (int i = 0; i < 2 && !rc; ++i) {
+    if (hipHostMalloc(reinterpret_cast<void**>(&pin[i]), bytes, hipHostMallocDefault) != hipSuccess) {
+      pin[i] = nullptr; (void)hipGetLastError(); rc = XIVO_HIP_ERR_NOMEM;
+    }
+    if (!rc && hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) { ev[i] = nullptr; rc = XIVO_HIP_ERR_HIP; }
+  }
+  if (rc) release();
+  return rc;
+}
+void PinnedUpload::release() {
+  for (int i = 0; i < 2; ++i) {
+    if (pin[i]) { hipHostFree(pin[i]); pin[i] = nullptr; }
+    if (ev[i]) { hipEventDestroy(ev[i]); ev[i] = nullptr; }
+  }
+  cur = 0;
+}
+PinnedUpload& PinnedUpload::operator=(PinnedUpload&& o) noexcept {
+  if (this != &o) {
+    release();
+    for (int i = 0; i < 2; ++i) { pin[i] = o.pin[i]; ev[i] = o.ev[i]; o.pin[i] = nullptr; o.ev[i] = nullptr; }
+    cur = o.cur; o.cur = 0;
+  }
+  return *this;
+}
+int PinnedUpload::stage(char** h) {
+  HIP_TRY(hipEventSynchronize(ev[cur ^ 1]));
+  *h = pin[cur ^ 1];
+  return XIVO_HIP_OK;
+}
+int PinnedUpload::enqueue(void* dev, size_t bytes, hipStream_t stream) {
+  const int set = cur ^ 1;
+  HIP_TRY(hipMemcpyAsync(dev, pin[set], bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(ev[set], stream));
+  cur = set;
+  return XIVO_HIP_OK;
+}
 
 MeasBuffers meas_buffers(xivo_hip_ctx* c, int b0) {
   MeasBuffers mb;
@@ -193,14 +234,12 @@ void xivo_hip_destroy(xivo_hip_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
-  track_block_release(c);   // the page-locked staging of the life cycles' tracks and of the world's poses
-  pcw_release(c);
-  c->mem.free_all();
+  c->mem.free_all();         // (the page-locked staging of the tracks and of the world's poses goes with its record: delete below)
   if (c->ell_flags_h) hipHostFree(c->ell_flags_h);
   if (c->pin_h) hipHostFree(c->pin_h);
-  for (auto& ep : c->pool) { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
-  if (c->t0) hipEventDestroy(c->t0);
-  if (c->t1) hipEventDestroy(c->t1);
+  for (auto& ep : c->prof.events) { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
+  if (c->prof.t0) hipEventDestroy(c->prof.t0);
+  if (c->prof.t1) hipEventDestroy(c->prof.t1);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -245,8 +284,8 @@ int xivo_hip_create(xivo_hip_ctx** out, int device, int N, int M_max, int batch_
       hipHostFree(c->ell_flags_h); c->ell_flags_h = nullptr; c->ell_flags_d = nullptr;
     }
   } else c->ell_flags_h = nullptr;
-  if (rc == XIVO_HIP_OK && hipEventCreate(&c->t0) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
-  if (rc == XIVO_HIP_OK && hipEventCreate(&c->t1) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (rc == XIVO_HIP_OK && hipEventCreate(&c->prof.t0) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (rc == XIVO_HIP_OK && hipEventCreate(&c->prof.t1) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
   if (rc != XIVO_HIP_OK) { xivo_hip_destroy(c); return rc; }
   *out = c;
   return XIVO_HIP_OK;
@@ -407,16 +446,16 @@ int xivo_hip_selftest_ctx_allocs(xivo_hip_ctx* c, int* live, unsigned long long*
 int xivo_hip_timer_begin(xivo_hip_ctx* c) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c) return XIVO_HIP_ERR_INVALID;
-  HIP_TRY(hipEventRecord(c->t0, c->stream));
+  HIP_TRY(hipEventRecord(c->prof.t0, c->stream));
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_timer_end(xivo_hip_ctx* c, float* ms) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || !ms) return XIVO_HIP_ERR_INVALID;
-  HIP_TRY(hipEventRecord(c->t1, c->stream));
-  HIP_TRY(hipEventSynchronize(c->t1));
-  HIP_TRY(hipEventElapsedTime(ms, c->t0, c->t1));
+  HIP_TRY(hipEventRecord(c->prof.t1, c->stream));
+  HIP_TRY(hipEventSynchronize(c->prof.t1));
+  HIP_TRY(hipEventElapsedTime(ms, c->prof.t0, c->prof.t1));
   return XIVO_HIP_OK;
 }
 
@@ -424,7 +463,7 @@ int xivo_hip_profile_reset(xivo_hip_ctx* c) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c) return XIVO_HIP_ERR_INVALID;
   int rc = collect_profile(c);
-  for (int i = 0; i < ST_COUNT; ++i) { c->stage_ms[i] = 0.f; c->stage_launches[i] = 0; c->stage_flops[i] = 0.0; }
+  for (int i = 0; i < ST_COUNT; ++i) { c->prof.ms[i] = 0.f; c->prof.launches[i] = 0; c->prof.flops[i] = 0.0; }
   return rc;
 }
 
@@ -436,9 +475,9 @@ int xivo_hip_profile_get(xivo_hip_ctx* c, int* n, const char** names, float* ms,
   *n = ST_COUNT;
   for (int i = 0; i < ST_COUNT; ++i) {
     if (names) names[i] = kStageNames[i];
-    if (ms) ms[i] = c->stage_ms[i];
-    if (launches) launches[i] = c->stage_launches[i];
-    if (flops) flops[i] = c->stage_flops[i];
+    if (ms) ms[i] = c->prof.ms[i];
+    if (launches) launches[i] = c->prof.launches[i];
+    if (flops) flops[i] = c->prof.flops[i];
   }
   return XIVO_HIP_OK;
 }
@@ -455,12 +494,12 @@ int xivo_hip_bench_mfma_peak(xivo_hip_ctx* c, double* out4) {
   for (int mode = 0; mode < 2; ++mode) {
     const int blocks = mode == 0 ? 256 * 8 : 256;
     HIP_TRY((hipError_t)launch_mfma_peak(c->scratch, 10, blocks, c->stream));
-    HIP_TRY(hipEventRecord(c->t0, c->stream));
+    HIP_TRY(hipEventRecord(c->prof.t0, c->stream));
     HIP_TRY((hipError_t)launch_mfma_peak(c->scratch, iters, blocks, c->stream));
-    HIP_TRY(hipEventRecord(c->t1, c->stream));
-    HIP_TRY(hipEventSynchronize(c->t1));
+    HIP_TRY(hipEventRecord(c->prof.t1, c->stream));
+    HIP_TRY(hipEventSynchronize(c->prof.t1));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->t0, c->t1));
+    HIP_TRY(hipEventElapsedTime(&ms, c->prof.t0, c->prof.t1));
     double cyc = 0.0;
     HIP_TRY(hipMemcpy(&cyc, c->scratch + 1, sizeof(double), hipMemcpyDeviceToHost));
     const double flops = 2.0 * 16 * 16 * 4 * 8.0 * iters * 4.0 /*waves*/ * blocks;

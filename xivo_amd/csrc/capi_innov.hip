@@ -23,13 +23,15 @@ int xivo_hip_innov_config(xivo_hip_ctx* c, const xivo_innov_opts* o) {
   if (o->T_max > 0 && !FrameLog::fits(o->T_max, c->Bmax, sizeof(xivo_innov_rec), &n_rec)) return XIVO_HIP_ERR_INVALID;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   HIP_TRY(hipStreamSynchronize(c->stream));   // a record launch may still be writing the blocks given back here
-  return log_realloc(c, c->innov_log, o->T_max, &c->innov_rec, n_rec, &c->innov_io,
+  c->mem.release(&c->innov.rec, &c->innov.io);
+  c->innov = InnovLog{};
+  return log_alloc(c, c->innov.log, o->T_max, &c->innov.rec, n_rec, &c->innov.io,
                      ((size_t)o->T_max + (size_t)c->Bmax) * 2 * sizeof(double) * 2);
 }
 
 int xivo_hip_innov_record(xivo_hip_ctx* c, int B, long long ts_ns, int* frame_out) {
-  if (!c || B <= 0 || B > c->Bmax || !c->innov_log.configured() || !c->dx_current(B) || c->rows.rows() <= 0) return XIVO_HIP_ERR_INVALID;
-  if (c->innov_log.full()) return XIVO_HIP_ERR_FULL;
+  if (!c || B <= 0 || B > c->Bmax || !c->innov.configured() || !c->dx_current(B) || c->rows.rows() <= 0) return XIVO_HIP_ERR_INVALID;
+  if (c->innov.log.full()) return XIVO_HIP_ERR_FULL;
   const StagedRows& r = c->rows;
   const int M = r.rows(), N = c->N;
   if (innov_record_lds(M, N) > 48 * 1024) return XIVO_HIP_ERR_UNSUPPORTED;
@@ -48,7 +50,7 @@ int xivo_hip_innov_record(xivo_hip_ctx* c, int B, long long ts_ns, int* frame_ou
   if (r.has_lead()) { c->Hlead.to(a.lead, a.strideLead, a.ldlead); a.lead_k = LEAD_K; }
   c->inn.to(a.inn, a.strideInn); c->diagR.to(a.diagR, a.strideR); c->err.to(a.err, a.strideErr);
   a.status = c->status; a.ldlt_used = c->ldlt_used; a.M = M; a.N = N;
-  a.rec = c->innov_rec + FrameLog::at(c->innov_log.count(), c->Bmax, 0);
+  a.rec = c->innov.rec + FrameLog::at(c->innov.log.count(), c->Bmax, 0);
   {
     // per filter: dx, inn and diagR once, the rows in their representation, the record out
     const double rows_bytes = a.dense_all ? 8.0 * M * N
@@ -56,45 +58,45 @@ int xivo_hip_innov_record(xivo_hip_ctx* c, int B, long long ts_ns, int* frame_ou
     StageTimer st(c, ST_OTHER, 0.0, "innov_record_kernel", (double)B * (8.0 * N + 16.0 * M + rows_bytes + sizeof(xivo_innov_rec)));
     if (launch_innov_record(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
   }
-  log_commit(c->innov_log, ts_ns, frame_out);
+  log_commit(c->innov.log, ts_ns, frame_out);
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_innov_count(xivo_hip_ctx* c) {
-  if (!c || !c->innov_log.configured()) return XIVO_HIP_ERR_INVALID;
-  return c->innov_log.count();
+  if (!c || !c->innov.configured()) return XIVO_HIP_ERR_INVALID;
+  return c->innov.log.count();
 }
 
 int xivo_hip_innov_reset(xivo_hip_ctx* c) {
-  if (!c || !c->innov_log.configured()) return XIVO_HIP_ERR_INVALID;
-  c->innov_log.reset();
+  if (!c || !c->innov.configured()) return XIVO_HIP_ERR_INVALID;
+  c->innov.log.reset();
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_innov_read(xivo_hip_ctx* c, int b0, int nb, int t0, int nt, xivo_innov_rec* recs, long long* ts) {
-  if (!c || bad_slice(c, c->innov_log, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
-  c->innov_log.stamps(t0, nt, ts);
+  if (!c || bad_slice(c, c->innov.log, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
+  c->innov.log.stamps(t0, nt, ts);
   if (nb == 0 || nt == 0 || !recs) return XIVO_HIP_OK;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (d2h_frames(c, recs, c->innov_rec, sizeof(xivo_innov_rec), b0, nb, t0, nt)) return XIVO_HIP_ERR_HIP;
+  if (d2h_frames(c, recs, c->innov.rec, sizeof(xivo_innov_rec), b0, nb, t0, nt)) return XIVO_HIP_ERR_HIP;
   HIP_TRY(hipStreamSynchronize(c->stream));
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_innov_stats(xivo_hip_ctx* c, int b0, int nb, int t0, int nt, double* frame_nis, long long* frame_dof,
                          int* frame_used, double* filt_nis, long long* filt_dof, int* filt_used) {
-  if (!c || bad_slice(c, c->innov_log, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
+  if (!c || bad_slice(c, c->innov.log, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
   if (nb == 0 || nt == 0) return XIVO_HIP_OK;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   static_assert(kStatBytes <= 4 * sizeof(double), "the staging xivo_hip_innov_config allocates holds every output");
   // staging (allocated by xivo_hip_innov_config for T_max frames and Bmax filters): sums | dofs | counts, frames then filters
   const size_t n = (size_t)nt + nb;
-  double* d_nis = reinterpret_cast<double*>(c->innov_io);
+  double* d_nis = reinterpret_cast<double*>(c->innov.io);
   long long* d_dof = reinterpret_cast<long long*>(d_nis + n);
   int* d_used = reinterpret_cast<int*>(d_dof + n);
   const long at = (long)FrameLog::at(t0, c->Bmax, b0);
-  InnovStatsArgs f{c->innov_rec, at, (long)c->Bmax, 1, nt, nb, d_nis, d_dof, d_used};                 // a frame: its filters
-  InnovStatsArgs g{c->innov_rec, at, 1, (long)c->Bmax, nb, nt, d_nis + nt, d_dof + nt, d_used + nt};  // a filter: its frames
+  InnovStatsArgs f{c->innov.rec, at, (long)c->Bmax, 1, nt, nb, d_nis, d_dof, d_used};                 // a frame: its filters
+  InnovStatsArgs g{c->innov.rec, at, 1, (long)c->Bmax, nb, nt, d_nis + nt, d_dof + nt, d_used + nt};  // a filter: its frames
   if (launch_innov_stats(f, c->stream) || launch_innov_stats(g, c->stream)) return XIVO_HIP_ERR_HIP;
   auto down = [&](void* dst, const void* src, size_t bytes) {
     return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;

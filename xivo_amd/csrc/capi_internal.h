@@ -2,7 +2,10 @@
 //   capi.hip            context, P residency, resident device buffers, timing / profile, the helpers declared below (among
 //                       them what the per-frame logs share: the slice check, the frame-major read, the NEES staging)
 //   capi_update.hip     route table, measurement hand-over, the update pipelines, the L D L^T fallback, the one-filter call
-//   capi_glevel.hip     feature level: scene, Jacobians, gate, stacking, OOS rows, RANSAC, loop closure, Givens / QR, edits
+//   capi_glevel.hip     feature level: layout, scene, calibration, Jacobians, gate, stacking, filter_update, absorb, edits, pixels
+//   capi_oos.hip        OOS rows, loop-closure stacking, OOS compression, Givens / QR
+//   capi_ransac.hip     OnePointRANSAC on the resident state
+//   capi_pool.hip       sub-filter, candidate order, the feature pool, triangulation, AdaptInitialDepth
 //   capi_propagate.hip  propagation
 //   capi_traj.hip       trajectory log: per-frame records, read-out, NEES against ground truth
 //   capi_score.hip      trajectory score: aligned / unaligned ATE and RPE of the logged poses against ground truth
@@ -16,7 +19,7 @@
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
 //
-// Three things those files go through:
+// Four things those files go through:
 //   c->mem (device_buffers.h)  owns every device block of the context. Allocation is c->mem.zeroed / raw / grow, re-sizing a
 //                              group of buffers is c->mem.release + allocation, xivo_hip_destroy is c->mem.free_all(). The only
 //                              hipMalloc / hipFree of the C ABI are the owner's two function pointers (capi.hip) and the
@@ -27,6 +30,12 @@
 //                              another buffer's stride. A descriptor only: owns nothing, allocates nothing.
 //   FrameLog (frame_log.h)     the host bookkeeping of a per-frame log: capacity, frames written, stamps, the slice check. The
 //                              four logs (capi_traj / _map / _innov / _trajsim.hip) hold one each next to their device blocks.
+//   the records below          the state of one area each (profiler, RANSAC scratch, resident OOS list, feature pool, the two device
+//                              life cycles, world, trajectory producer, the three logs), held by the context by value. A record
+//                              says itself whether its area is configured(), is reset by assigning a default-constructed one once
+//                              its device blocks went back to c->mem, and is changed from outside only through its named functions.
+//                              Records own no device memory. PoolMirror (pool_mirror.h) is the pool's host mirrors;
+//                              PinnedUpload the one double-buffered page-locked upload (the track block's, the world's poses).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -43,6 +52,7 @@
 #include "staged_rows.h"
 #include "device_buffers.h"
 #include "frame_log.h"
+#include "pool_mirror.h"
 
 namespace xivo_hip::capi {
 
@@ -82,19 +92,181 @@ struct InstateBookBuffers {
   long long* feat_id = nullptr; int* group_refs = nullptr; int ld = 0;
 };
 
-// The track block of the device life cycle that is configured: one device block that holds a frame's tracks and two page-locked
-// staging blocks of that size, each with the event of its last upload (cur: the one the last upload filled). Two forms share the
+// A double-buffered page-locked upload (capi.hip): two page-locked blocks of one size, each with the event of its last upload
+// (cur: the one the last upload filled), so that the host writes the next frame's bytes while the previous upload may still be
+// reading. A frame is stage() - the block the previous frame did not use, once its last upload has finished -, the host copy,
+// enqueue(). It gives its blocks back when it is released, assigned over or destroyed with the context.
+struct __attribute__((visibility("hidden"))) PinnedUpload {
+  PinnedUpload() = default;
+  PinnedUpload(const PinnedUpload&) = delete;
+  PinnedUpload& operator=(PinnedUpload&& o) noexcept;
+  ~PinnedUpload() { release(); }
+  int alloc(size_t bytes);   // all or nothing: XIVO_HIP_ERR_NOMEM (sticky error cleared) / XIVO_HIP_ERR_HIP
+  void release();            // (nothing of it may still be in flight)
+  int stage(char** h);
+  int enqueue(void* dev, size_t bytes, hipStream_t stream);   // the staged block's leading bytes to dev, record, flip
+ private:
+  char* pin[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr};
+  int cur = 0;
+};
+
+// The track block of the device life cycle that is configured: one device block that holds a frame's tracks and the page-locked
+// staging of that size. Two forms share the
 // device block: packed, off [B + 1] | ids [n] | meas [n][3] as track_block_upload leaves them, and strided behind the offsets'
-// space, ids [Bmax][tracks_max] | meas [Bmax][tracks_max][3] with the counts in pcw_cnt, as the track producer (capi_pcw.hip)
+// space, ids [Bmax][tracks_max] | meas [Bmax][tracks_max][3] with the counts in the world's cnt, as the track producer (capi_pcw.hip)
 // leaves them. B > 0: a frame is open between a begin and an end call, on n packed tracks or (strided) on the producer's.
 // The track_block_* functions (capi_lifecycle.hip) are its interface; nothing else touches the fields.
 struct TrackBlock {
-  char* dev = nullptr; char* pin[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr};
+  char* dev = nullptr; PinnedUpload up;
   size_t set_bytes = 0;
-  int tracks_max = 0, cur = 0, B = 0, n = 0;
+  int tracks_max = 0, B = 0, n = 0;
   bool strided = false;
 };
 
+// ---- one record per area
+
+// timing / profile (StageTimer, xivo_hip_timer_*, xivo_hip_profile_*): the timer's two events, the stage event pairs of the
+// launches since the last collection (used of them taken), the sums per stage
+struct Profiler {
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  std::vector<EventPair> events;
+  size_t used = 0;
+  float ms[ST_COUNT] = {0};
+  int launches[ST_COUNT] = {0};
+  double flops[ST_COUNT] = {0};
+  double bytes[ST_COUNT] = {0};         // algorithmic HBM bytes of the stage's last launch (inputs once + outputs once)
+  char kernel[ST_COUNT][64] = {{0}};   // kernel instantiation of the stage's last launch (as rocprofv3 names it)
+};
+
+// OnePointRANSAC scratch (capi_ransac.hip, allocated on first use for Fmax features): BackupState copies of P, the nominal state,
+// the groups and (online-calibration builds) the calibration state; selection results
+struct RansacScratch {
+  double* P = nullptr; xivo_pose_in* poses = nullptr; xivo_group_in* groups = nullptr; xivo_calib_in* calib = nullptr;
+  unsigned char *low = nullptr, *lowkeep = nullptr, *keep = nullptr;
+  unsigned long long *zg = nullptr, *gmask = nullptr;
+  int *state = nullptr, *gauge = nullptr, *nrej = nullptr;
+  double* chi = nullptr;
+  int Fmax = 0;
+  bool sized_for(int F) const { return Fmax == F; }
+};
+
+// the resident OOS list (capi_oos.hip): what the last xivo_hip_oos_project with a list uploaded - nb filters of n features,
+// `whole` as its option set it - and the rows every filter got of it
+struct OosList {
+  xivo_oos_in* feats = nullptr; size_t cap = 0;
+  int nb = 0, n = 0, whole = 0;
+  int* rows = nullptr;   // [Bmax]
+  // xivo_hip_oos_project with feats == NULL: that very list is resident
+  bool holds(int nb_, int n_, int whole_) const { return feats && nb == nb_ && n == n_ && whole == whole_; }
+};
+
+// out-of-state feature pool (capi_pool.hip): entries [Bmax][pool_max] (ref_sind = the entry's anchor, -1: free), anchors
+// [Bmax][anchor_max] (their shapes: the mirror's); the host mirrors of who is live / linked, which validate pool_add and the pool's
+// edit kinds. Depth initialisation of new tracks (xivo_hip_pool_triangulation / xivo_hip_pool_adapt_depth*): triangulation
+// options (method XIVO_TRI_OFF: off), per-filter good / bad counters and the resident init_z (allocated by pool_config)
+struct FeaturePool {
+  xivo_subfilter_feat* entries = nullptr;
+  xivo_hip::PoolAnchor* anchors = nullptr;
+  PoolMirror mirror;
+  xivo_subfilter_opts opts{};
+  double remove_outlier = 0.0;
+  xivo_triangulate_opts tri{};
+  int* tri_counts = nullptr;        // [2][Bmax]: good, bad
+  double* init_z = nullptr;         // [Bmax]
+  xivo_adapt_depth_opts adapt{};
+  bool adapt_on = false;
+  // per-call device staging: records / pixels in, order / counts / live out. Not part of a pool's configuration -
+  // xivo_hip_triangulate stages through it without a pool -, so reset() keeps it
+  char* io = nullptr; size_t io_cap = 0;
+  bool configured() const { return entries != nullptr; }
+  int pool_max() const { return mirror.pool_max(); }
+  int anchor_max() const { return mirror.anchor_max(); }
+  void reset() { char* p = io; const size_t n = io_cap; *this = FeaturePool{}; io = p; io_cap = n; }
+};
+
+// device life cycle (xivo_hip_life_*, "the immediate life cycle"): its options and counters [Bmax]
+struct ImmediateLife {
+  xivo_life_opts opts{};
+  xivo_life_stats* stats = nullptr;
+  bool configured() const { return stats != nullptr; }
+};
+
+// device pool life cycle (xivo_hip_pool_life_*): the pool book [Bmax][pool_max] / [Bmax][anchor_max], the counters [Bmax], what
+// a frame's kernels hand each other (slot_track, ent_track, the step's xp / order / n / live); frame: the frame counter
+struct PoolLife {
+  bool on = false;
+  xivo_pool_life_opts opts{};
+  long long* ent_id = nullptr; int* ent_born = nullptr; int* anc_used = nullptr; int* anc_life = nullptr;
+  xivo_pool_life_stats* stats = nullptr;
+  int* slot_track = nullptr; int* ent_track = nullptr;
+  double* xp = nullptr; int* order = nullptr; int* n = nullptr; unsigned char* live = nullptr;
+  int frame = 0;
+  bool configured() const { return on; }
+};
+
+// point-cloud world (xivo_hip_pcw_*, capi_pcw.hip): the resident worlds Xs [Bmax][npts][3] / ids [Bmax][npts] / next_id [Bmax],
+// the frame's camera poses gsc [Bmax][12] with their page-locked staging and cnt [Bmax]. The producer writes the strided form of
+// the track block: tracks_B is the B whose tracks the block holds (0: none), fresh whether a begin_tracks call may still
+// consume them. cam: the camera of xivo_hip_pcw_camera in place of the pinhole of opts (use_cam), with its radius guard
+struct World {
+  xivo_pcw_opts opts{};
+  double* Xs = nullptr; long long* ids = nullptr; long long* next_id = nullptr; int* cnt = nullptr;
+  double* gsc = nullptr; PinnedUpload up;
+  int tracks_B = 0; bool fresh = false;
+  bool use_cam = false; xivo_cam cam{}; double max_radius = 0.0;
+  bool configured() const { return Xs != nullptr; }
+  // what the life cycles ask and tell (capi_lifecycle.hip, capi_pool_lifecycle.hip)
+  const int* track_counts() const { return cnt; }
+  bool tracks_fresh_for(int B) const { return cnt && fresh && tracks_B == B; }
+  void tracks_consumed() { fresh = false; }
+  void tracks_overwritten() { tracks_B = 0; fresh = false; }   // (a host-track upload, or the producer about to write)
+};
+
+// trajectory producer (xivo_hip_trajsim_*, capi_trajsim.hip): curve / rate per filter [Bmax], the last frame's records
+// [Bmax][n_max] (read as [B][n]) and camera poses [Bmax][12], the ground-truth log gt [T_max][Bmax][12] with its FrameLog
+// (no stamps: it commits 0), the device copy of the propagation noise (Qimu 144 | Qmodel 529) with the host copy it was
+// uploaded from. B / n: the shape of the last frame (B = 0: none), fresh: its records may still be consumed by
+// xivo_hip_propagate_resident
+struct TrajSim {
+  xivo_trajsim_opts opts{};
+  int* motion = nullptr; double* rate = nullptr; xivo_imu_in* recs = nullptr; double* gsc = nullptr;
+  double* Q = nullptr;
+  double* gt = nullptr; FrameLog log;
+  xivo_prop_opts prop{}; bool prop_valid = false;
+  int B = 0, n = 0; bool fresh = false;
+  bool configured() const { return recs != nullptr; }
+  // the camera poses of the last frame if it was one of B_ filters, else null (capi_pcw.hip)
+  const double* frame_poses(int B_) const { return B == B_ ? gsc : nullptr; }
+};
+
+// The three per-frame logs: device pointers, options, the FrameLog (frame_log.h: capacity in frames, frames written, stamps),
+// staging. A log's blocks are allocated exactly while its FrameLog is configured.
+// trajectory log (xivo_hip_traj_*, capi_traj.hip): [capacity][Bmax] records and packed covariance blocks of cols. io: per-call
+// staging of xivo_hip_traj_nees / xivo_hip_traj_score
+struct TrajLog {
+  xivo_traj_rec* rec = nullptr; double* cov = nullptr;
+  int ncols = 0, cols[XIVO_TRAJ_MAX_COLS] = {0};
+  FrameLog log;
+  char* io = nullptr; size_t io_cap = 0;
+  bool configured() const { return log.configured(); }
+};
+// landmark log (xivo_hip_map_*, capi_map.hip): [capacity][Bmax][nout] entries and [capacity][Bmax] counts. io: per-call staging of
+// xivo_hip_map_nees
+struct MapLog {
+  xivo_map_pt* pts = nullptr; int* npts = nullptr;
+  int nout = 0; unsigned flags = 0;
+  FrameLog log;
+  char* io = nullptr; size_t io_cap = 0;
+  bool configured() const { return log.configured(); }
+};
+// innovation log (xivo_hip_innov_*, capi_innov.hip): [capacity][Bmax] records. io: the output staging of xivo_hip_innov_stats,
+// allocated by xivo_hip_innov_config for the largest slice
+struct InnovLog {
+  xivo_innov_rec* rec = nullptr;
+  FrameLog log;
+  char* io = nullptr;
+  bool configured() const { return log.configured(); }
+};
 
 }  // namespace xivo_hip::capi
 
@@ -123,7 +295,7 @@ struct xivo_hip_ctx {
   int chunk = 0;      // filters per pipeline pass (0 = whole batch)
   int call_batch = 0; // filters of the whole update call being walked in chunks (0: not chunked)
   int* ldlt_used = nullptr;     // per filter: 1 = the last update went through the pivoted L D L^T fallback
-  // G-level
+  // G-level: layout, camera, the scene (poses, groups, feats, J, finn, dist, mask of F of Fmax features)
   xivo_layout lay{};
   xivo_cam cam{};
   bool have_layout = false;
@@ -136,67 +308,19 @@ struct xivo_hip_ctx {
   int Fmax = 0, F = 0;
   xivo_pose_in* poses = nullptr;
   int* absorb_count = nullptr;   // State::counter of every filter (src/core.h:120-122)
-  // OnePointRANSAC scratch (allocated on first use): BackupState copies, selection results
-  double* Prs = nullptr; xivo_pose_in* poses_rs = nullptr; xivo_group_in* groups_rs = nullptr;
-  unsigned char *rs_low = nullptr, *rs_lowkeep = nullptr, *rs_keep = nullptr;
-  unsigned long long *rs_zg = nullptr, *rs_gmask = nullptr;
-  int *rs_state = nullptr, *rs_gauge = nullptr, *rs_nrej = nullptr;
-  double* rs_chi = nullptr;
-  int rs_Fmax = 0;
   xivo_group_in* groups = nullptr;
   xivo_feat_in* feats = nullptr;
   double *J = nullptr, *finn = nullptr, *dist = nullptr;
   unsigned char* mask = nullptr;
   int* rows_instate = nullptr;
-  xivo_oos_in* oos = nullptr;
-  size_t oos_cap = 0;
   double* pd_h = nullptr; double pd_h0 = 0.0;   // step-size-controlled Dormand-Prince: the step each filter carries (xivo_hip_propagate)
-  int oos_nb = 0, oos_n = 0, oos_whole = 0;   // shape of the resident OOS list (xivo_hip_oos_project with feats == NULL; its row bound: rows)
-  int* oos_rows = nullptr;
-  xivo_calib_in* calib_rs = nullptr;            // BackupState of the calibration state (OnePointRANSAC, online-calibration builds)
   // online-calibration builds on the sparse pipeline (round 5): the calibration columns of the stacked rows as a dense
   // [Mpmax x LEAD_K] block per filter next to the row-pair compressed rows (rows.has_lead(): the current stacking has one)
   xivo_hip::capi::BatchMat Hlead;
   char* lc_buf = nullptr; size_t lc_cap = 0;   // xivo_hip_close_loop_stack: matches | dense rows | inn | diagR
-  xivo_subfilter_feat* sub = nullptr;   // staging of xivo_hip_subfilter_update
-  // out-of-state feature pool (xivo_hip_pool_*): entries [Bmax][pool_max] (ref_sind = the entry's anchor, -1: free), anchors
-  // [Bmax][anchor_max]; host mirrors of who is live / linked, which validate pool_add and the pool's edit kinds
-  int pool_max = 0, anchor_max = 0;
-  xivo_subfilter_opts pool_opts{};
-  double pool_remove_outlier = 0.0;
-  xivo_subfilter_feat* fpool = nullptr;
-  xivo_hip::PoolAnchor* anchors = nullptr;
-  char* pool_io = nullptr; size_t pool_io_cap = 0;   // per-call device staging: records / pixels in, order / counts / live out
-  std::vector<int> pool_anchor_h;   // [Bmax][pool_max]: anchor of a live entry, -1 = free
-  std::vector<int> anchor_link_h;   // [Bmax][anchor_max]: linked group slot, -1 = unlinked
-  // depth initialisation of new tracks (xivo_hip_pool_triangulation / xivo_hip_pool_adapt_depth*): triangulation options
-  // (method XIVO_TRI_OFF: off), per-filter good / bad counters and the resident init_z [Bmax] (allocated by pool_config)
-  xivo_triangulate_opts pool_tri{};
-  int* tri_counts = nullptr;        // [2][Bmax]: good, bad
-  double* init_z = nullptr;         // [Bmax]
-  xivo_adapt_depth_opts adapt{};
-  bool adapt_on = false;
-  // The three per-frame logs below and the trajectory producer's ground truth: device pointers, options, the FrameLog (frame_log.h:
-  // capacity in frames, frames written, stamps), staging. A log's blocks are allocated exactly while its FrameLog is configured.
-  // trajectory log (xivo_hip_traj_*, capi_traj.hip): [capacity][Bmax] records and packed covariance blocks of traj_cols.
-  // traj_io: per-call staging of xivo_hip_traj_nees / xivo_hip_traj_score
-  xivo_traj_rec* traj_rec = nullptr; double* traj_cov = nullptr;
-  int traj_ncols = 0, traj_cols[XIVO_TRAJ_MAX_COLS] = {0};
-  xivo_hip::capi::FrameLog traj_log;
-  char* traj_io = nullptr; size_t traj_io_cap = 0;
-  // landmark log (xivo_hip_map_*, capi_map.hip): [capacity][Bmax][map_nout] entries and [capacity][Bmax] counts. map_io: per-call
-  // staging of xivo_hip_map_nees
-  xivo_map_pt* map_pts = nullptr; int* map_npts = nullptr;
-  int map_nout = 0; unsigned map_flags = 0;
-  xivo_hip::capi::FrameLog map_log;
-  char* map_io = nullptr; size_t map_io_cap = 0;
-  // innovation log (xivo_hip_innov_*, capi_innov.hip): [capacity][Bmax] records. innov_io: the output staging of
-  // xivo_hip_innov_stats, allocated by xivo_hip_innov_config for the largest slice. dx_ok[b]: the err buffer of filter b holds the
-  // dx of the rows staged for it right now (set by the update calls for the filters they update; cleared by absorb, new rows,
-  // restore_P) - a record of filters [0, B) needs it of every one of them
-  xivo_innov_rec* innov_rec = nullptr;
-  xivo_hip::capi::FrameLog innov_log;
-  char* innov_io = nullptr;
+  xivo_subfilter_feat* sub = nullptr; size_t sub_cap = 0;   // staging of xivo_hip_subfilter_update (entries)
+  // dx_ok[b]: the err buffer of filter b holds the dx of the rows staged for it right now (set by the update calls for the filters
+  // they update; cleared by absorb, new rows, restore_P) - an innovation record of filters [0, B) needs it of every one of them
   std::vector<char> dx_ok;
   void dx_set(int b0, int nb, bool v) { if (dx_ok.size() != (size_t)Bmax) dx_ok.assign((size_t)Bmax, 0); std::fill_n(dx_ok.begin() + b0, nb, (char)v); }
   void dx_clear() { std::fill(dx_ok.begin(), dx_ok.end(), (char)0); }
@@ -205,57 +329,26 @@ struct xivo_hip_ctx {
   // and the track block of whichever is, both null when neither
   xivo_hip::capi::InstateBookBuffers book;
   xivo_hip::capi::TrackBlock tracks;
-  // device life cycle (xivo_hip_life_*): its options and counters [Bmax]; life_stats is null until xivo_hip_life_config - "the
-  // immediate life cycle is configured"
-  xivo_life_opts life_opts{};
-  xivo_life_stats* life_stats = nullptr;
-  // device pool life cycle (xivo_hip_pool_life_*): the pool book [Bmax][pool_max] / [Bmax][anchor_max], the counters [Bmax], what
-  // a frame's kernels hand each other (slot_track, ent_track, the step's xp / order / n / live); null until
-  // xivo_hip_pool_life_config. plife_frame: the frame counter
-  bool plife_on = false;
-  xivo_pool_life_opts plife_opts{};
-  long long* plife_ent_id = nullptr; int* plife_ent_born = nullptr; int* plife_anc_used = nullptr; int* plife_anc_life = nullptr;
-  xivo_pool_life_stats* plife_stats = nullptr;
-  int* plife_slot_track = nullptr; int* plife_ent_track = nullptr;
-  double* plife_xp = nullptr; int* plife_order = nullptr; int* plife_n = nullptr; unsigned char* plife_live = nullptr;
-  int plife_frame = 0;
-  // point-cloud world (xivo_hip_pcw_*, capi_pcw.hip): the resident worlds Xs [Bmax][npts][3] / ids [Bmax][npts] / next_id [Bmax],
-  // the frame's camera poses [Bmax][12] with two page-locked staging blocks (the scheme of the track block) and cnt [Bmax]; null until
-  // xivo_hip_pcw_config. The producer writes the strided form of the track block: pcw_tracks_B is the B whose tracks the block
-  // holds (0: none - a host-track life_begin overwrote them), pcw_fresh whether a life_begin_tracks may still consume them
-  xivo_pcw_opts pcw_opts{};
-  double* pcw_Xs = nullptr; long long* pcw_ids = nullptr; long long* pcw_next_id = nullptr; int* pcw_cnt = nullptr;
-  double* pcw_gsc = nullptr; double* pcw_pin[2] = {nullptr, nullptr}; hipEvent_t pcw_ev[2] = {nullptr, nullptr};
-  int pcw_cur = 0, pcw_tracks_B = 0; bool pcw_fresh = false;
-  // the camera of xivo_hip_pcw_camera in place of the pinhole of pcw_opts (pcw_use_cam), and its radius guard
-  bool pcw_use_cam = false; xivo_cam pcw_cam{}; double pcw_max_radius = 0.0;
-  // trajectory producer (xivo_hip_trajsim_*, capi_trajsim.hip): curve / rate per filter [Bmax], the last frame's records
-  // [Bmax][n_max] (read as [B][n]) and camera poses [Bmax][12], the ground-truth log ts_gt [T_max][Bmax][12] with its FrameLog
-  // ts_log (no stamps: it commits 0), the device copy of the propagation noise (Qimu 144 | Qmodel 529) with the host copy it was
-  // uploaded from; null until xivo_hip_trajsim_config. ts_B / ts_n: the shape of the last frame (ts_B = 0: none), ts_fresh: its
-  // records may still be consumed by xivo_hip_propagate_resident
-  xivo_trajsim_opts ts_opts{};
-  int* ts_motion = nullptr; double* ts_rate = nullptr; xivo_imu_in* ts_recs = nullptr; double* ts_gsc = nullptr;
-  double* ts_Q = nullptr;
-  double* ts_gt = nullptr; xivo_hip::capi::FrameLog ts_log;
-  xivo_prop_opts ts_prop{}; bool ts_prop_valid = false;
-  int ts_B = 0, ts_n = 0; bool ts_fresh = false;
   std::vector<char> hstage;                        // host staging of d2h_rows
   char* edit_buf = nullptr; size_t edit_cap = 0;   // device copy of the ops of xivo_hip_edit_batch
   // one-filter plumbing call (xivo_hip_update_joseph_host): page-locked, device-mapped staging block owned by the context,
   // scratch of the host-side row compression
   char* pin_h = nullptr; char* pin_d = nullptr;
   struct HostCompressScratch { std::vector<int> cnt, occ, cslot, n; std::vector<double> v; } hc;
-  size_t sub_cap = 0;   // entries
-  // timing
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  std::vector<xivo_hip::capi::EventPair> pool;
-  size_t pool_used = 0;
-  float stage_ms[xivo_hip::capi::ST_COUNT] = {0};
-  int stage_launches[xivo_hip::capi::ST_COUNT] = {0};
-  double stage_flops[xivo_hip::capi::ST_COUNT] = {0};
-  double stage_bytes[xivo_hip::capi::ST_COUNT] = {0};         // algorithmic HBM bytes of the stage's last launch (inputs once + outputs once)
-  char stage_kernel[xivo_hip::capi::ST_COUNT][64] = {{0}};   // kernel instantiation of the stage's last launch (as rocprofv3 names it)
+  // one record per area (above)
+  xivo_hip::capi::Profiler prof;
+  xivo_hip::capi::RansacScratch rs;
+  xivo_hip::capi::OosList resident_oos;
+  xivo_hip::capi::FeaturePool pool;
+  xivo_hip::capi::ImmediateLife life;
+  xivo_hip::capi::PoolLife plife;
+  xivo_hip::capi::World world;
+  xivo_hip::capi::TrajSim trajsim;
+  xivo_hip::capi::TrajLog traj;
+  xivo_hip::capi::MapLog map;
+  xivo_hip::capi::InnovLog innov;
+  // "a device life cycle exists" (whichever: the book and the track block are its)
+  bool life_cycle_configured() const { return life.configured() || plife.configured(); }
 };
 
 #pragma GCC visibility push(hidden)
@@ -276,17 +369,18 @@ struct StageTimer {
   xivo_hip_ctx* c; EventPair* ep = nullptr;
   StageTimer(xivo_hip_ctx* ctx, int stage, double flops, const char* kernel = nullptr, double bytes = 0.0) : c(ctx) {
     if (!(c->flags & XIVO_HIP_FLAG_PROFILE)) return;
-    c->stage_bytes[stage] = bytes;
-    if (kernel) { strncpy(c->stage_kernel[stage], kernel, 63); c->stage_kernel[stage][63] = 0; }
-    if (c->pool_used >= c->pool.size()) {
+    Profiler& p = c->prof;
+    p.bytes[stage] = bytes;
+    if (kernel) { strncpy(p.kernel[stage], kernel, 63); p.kernel[stage][63] = 0; }
+    if (p.used >= p.events.size()) {
       EventPair np; np.stage = stage;
       if (hipEventCreate(&np.a) != hipSuccess || hipEventCreate(&np.b) != hipSuccess) return;
-      c->pool.push_back(np);
+      p.events.push_back(np);
     }
-    ep = &c->pool[c->pool_used++];
+    ep = &p.events[p.used++];
     ep->stage = stage;
-    c->stage_launches[stage]++;
-    c->stage_flops[stage] = flops;
+    p.launches[stage]++;
+    p.flops[stage] = flops;
     hipEventRecord(ep->a, c->stream);
   }
   ~StageTimer() { if (ep) hipEventRecord(ep->b, c->stream); }
@@ -333,11 +427,9 @@ inline bool bad_slice(xivo_hip_ctx* c, const FrameLog& log, int b0, int nb, int 
 }
 // that slice of a frame-major block src of `per` bytes per filter entry to dst [nt][nb], enqueued (dst null: nothing)
 int d2h_frames(xivo_hip_ctx* c, void* dst, const void* src, size_t per, int b0, int nb, int t0, int nt);
-// the two blocks of a log for T_max frames (the stream must be idle): the old ones given back and the log emptied, then for
+// the two blocks of a log whose record was just reset (its old blocks given back, the stream idle), for T_max frames: for
 // T_max > 0 na / nb elements behind *a / *b - both or neither - and the log configured
-template <class A, class B> int log_realloc(xivo_hip_ctx* c, FrameLog& log, int T_max, A** a, size_t na, B** b, size_t nb) {
-  c->mem.release(a, b);
-  log.configure(0);
+template <class A, class B> int log_alloc(xivo_hip_ctx* c, FrameLog& log, int T_max, A** a, size_t na, B** b, size_t nb) {
   if (T_max == 0) return XIVO_HIP_OK;
   int rc = c->mem.raw(a, na);
   if (!rc) rc = c->mem.raw(b, nb);
@@ -406,10 +498,15 @@ int pcw_produce(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, 
 int propagate_device(xivo_hip_ctx* c, int B, int n_imu, const xivo_imu_in* recs, const double* dQimu, const double* dQmodel,
                      const xivo_prop_opts* o, double mean_dt);
 
-// ---- capi_glevel.hip
-int ensure_gate_buffers(xivo_hip_ctx* c, int F);
+// ---- capi_pool.hip
 // the arguments of one pool step but xp / order / n / live (xivo_hip_pool_step and the device pool life cycle share them)
 PoolStepArgs pool_step_args(xivo_hip_ctx* c, int B, int strict);
+
+// ---- capi_glevel.hip
+int ensure_gate_buffers(xivo_hip_ctx* c, int F);
+// the stacking of the gated scene of filters [0, B) (mask_override: another mask than the scene's, full_rows: the whole rows J()
+// of the dense-row gate / RANSAC). The gate helpers next to it (gate_impl, calib_gate) have no caller outside capi_glevel.hip
+int stack_impl(xivo_hip_ctx* c, int B, double R, int write_dense, unsigned char* mask_override = nullptr, int full_rows = 0);
 int ensure_dense(xivo_hip_ctx* c);
 int ensure_HT(xivo_hip_ctx* c);
 // H P (+ P H^T) of the stacked dense rows of filters [0, B) and the dense-row gate on them (gate_dense_kernel); `a` brings the

@@ -22,17 +22,17 @@ size_t set_bytes(int Bmax, int tracks_max) {
 
 void life_release(xivo_hip_ctx* c) {
   pcw_release(c);   // the producer writes into the track block: it goes with it
-  c->mem.release(&c->life_stats);
+  c->mem.release(&c->life.stats);
   book_release(c);
   track_block_release(c);
-  c->life_opts = xivo_life_opts{};
+  c->life = ImmediateLife{};
 }
 
 // the begin kernel on the tracks the block holds; the frame opens once it is enqueued
 int life_begin_frame(xivo_hip_ctx* c, int B, int F) {
   c->F = F;   // the list length, as xivo_hip_edit_batch / xivo_hip_set_pixels set it (neither touches the staged rows or dx_ok)
   LifeArgs a = life_args_common(c, B);
-  a.stats = c->life_stats;
+  a.stats = c->life.stats;
   {
     StageTimer st(c, ST_OTHER, 0.0, "life_begin_kernel");
     if (launch_life_begin(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
@@ -46,13 +46,8 @@ int life_begin_frame(xivo_hip_ctx* c, int B, int F) {
 namespace xivo_hip::capi {
 // ---- the track block
 void track_block_release(xivo_hip_ctx* c) {
-  TrackBlock& t = c->tracks;
-  c->mem.release(&t.dev);
-  for (int i = 0; i < 2; ++i) {
-    if (t.pin[i]) hipHostFree(t.pin[i]);
-    if (t.ev[i]) hipEventDestroy(t.ev[i]);
-  }
-  t = TrackBlock{};
+  c->mem.release(&c->tracks.dev);
+  c->tracks = TrackBlock{};
 }
 // one device block: everything runs on the context's stream, so the upload of frame t + 1 is ordered behind the last kernel of
 // frame t. Two page-locked blocks: the host writes the next frame's tracks while the previous upload may still be reading.
@@ -60,12 +55,7 @@ int track_block_alloc(xivo_hip_ctx* c, int tracks_max) {
   TrackBlock& t = c->tracks;
   const size_t bytes = set_bytes(c->Bmax, tracks_max);
   int rc = c->mem.raw(&t.dev, bytes);
-  for (int i = 0; i < 2 && !rc; ++i) {
-    if (hipHostMalloc(reinterpret_cast<void**>(&t.pin[i]), bytes, hipHostMallocDefault) != hipSuccess) {
-      t.pin[i] = nullptr; (void)hipGetLastError(); rc = XIVO_HIP_ERR_NOMEM;
-    }
-    if (!rc && hipEventCreateWithFlags(&t.ev[i], hipEventDisableTiming) != hipSuccess) { t.ev[i] = nullptr; rc = XIVO_HIP_ERR_HIP; }
-  }
+  if (!rc) rc = t.up.alloc(bytes);
   if (!rc) { t.set_bytes = bytes; t.tracks_max = tracks_max; }
   return rc;
 }
@@ -82,21 +72,19 @@ bool track_block_frame_ok(const xivo_hip_ctx* c, int B, const int* off, const lo
 int track_block_upload(xivo_hip_ctx* c, int B, const int* off, const long long* ids, const double* meas) {
   TrackBlock& t = c->tracks;
   const int n = off[B];
-  const int set = t.cur ^ 1;
-  HIP_TRY(hipEventSynchronize(t.ev[set]));
+  char* h = nullptr;
+  if (int rc = t.up.stage(&h)) return rc;
   const size_t off_bytes = pad8(((size_t)B + 1) * sizeof(int));
   const size_t bytes = off_bytes + (size_t)n * (sizeof(long long) + 3 * sizeof(double));
   if (bytes > t.set_bytes) return XIVO_HIP_ERR_INVALID;
-  char* h = t.pin[set];
   memcpy(h, off, ((size_t)B + 1) * sizeof(int));
   if (n > 0) {
     memcpy(h + off_bytes, ids, (size_t)n * sizeof(long long));
     memcpy(h + off_bytes + (size_t)n * sizeof(long long), meas, (size_t)n * 3 * sizeof(double));
   }
-  HIP_TRY(hipMemcpyAsync(t.dev, h, bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipEventRecord(t.ev[set], c->stream));
-  t.cur = set; t.n = n; t.strided = false;
-  c->pcw_tracks_B = 0; c->pcw_fresh = false;
+  if (int rc = t.up.enqueue(t.dev, bytes, c->stream)) return rc;
+  t.n = n; t.strided = false;
+  c->world.tracks_overwritten();
   return XIVO_HIP_OK;
 }
 long long* track_block_strided_ids(xivo_hip_ctx* c) {
@@ -184,7 +172,7 @@ LifeArgs life_args_common(xivo_hip_ctx* c, int B) {
   const TrackBlock& t = c->tracks;
   if (t.strided) {   // one row of tracks_max per filter with the counts next to them, as the producer left them
     a.ids = track_block_strided_ids(c); a.meas = track_block_strided_meas(c);
-    a.cnt = c->pcw_cnt; a.track_ld = t.tracks_max;
+    a.cnt = c->world.track_counts(); a.track_ld = t.tracks_max;
   } else {           // packed behind the B + 1 offsets, as the host uploaded them
     const size_t off_bytes = pad8(((size_t)B + 1) * sizeof(int));
     a.off = reinterpret_cast<const int*>(t.dev);
@@ -205,31 +193,31 @@ extern "C" {
 int xivo_hip_life_config(xivo_hip_ctx* c, const xivo_life_opts* o) {
   if (!c || !o || o->tracks_max < 0 || o->tracks_max > XIVO_LIFE_MAX_TRACKS) return XIVO_HIP_ERR_INVALID;
   if (o->tracks_max > 0) {
-    if (c->fpool || !c->have_layout) return XIVO_HIP_ERR_INVALID;
+    if (c->pool.configured() || !c->have_layout) return XIVO_HIP_ERR_INVALID;
     if (!isfinite(o->min_depth) || !isfinite(o->max_depth) || o->min_new_features < 0) return XIVO_HIP_ERR_INVALID;
     for (int i = 0; i < 3; ++i) if (!isfinite(o->var_xyz[i])) return XIVO_HIP_ERR_INVALID;
     if (c->lay.n_features > XIVO_LIFE_MAX_SLOTS || c->lay.n_groups > XIVO_LIFE_MAX_SLOTS || c->cam.model != XIVO_CAM_PINHOLE)
       return XIVO_HIP_ERR_UNSUPPORTED;
   }
-  if (c->plife_on) return XIVO_HIP_OK;   // (tracks_max = 0; the book and the track block are the pool life cycle's: nothing of this one to release)
+  if (c->plife.configured()) return XIVO_HIP_OK;   // (tracks_max = 0; the book and the track block are the pool life cycle's: nothing of this one to release)
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   HIP_TRY(hipStreamSynchronize(c->stream));   // a frame call may still be using the blocks given back here
   life_release(c);
   if (o->tracks_max == 0) return XIVO_HIP_OK;
   int rc = ensure_gate_buffers(c, 1);         // the resident feature list, so that the frame calls allocate nothing
   if (rc) return rc;
-  rc = c->mem.zeroed(&c->life_stats, (size_t)c->Bmax);
+  rc = c->mem.zeroed(&c->life.stats, (size_t)c->Bmax);
   if (!rc) rc = book_alloc(c);
   if (!rc) rc = track_block_alloc(c, o->tracks_max);
   if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
   if (rc) { life_release(c); return rc; }
-  c->life_opts = *o;
+  c->life.opts = *o;
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_life_set_book(xivo_hip_ctx* c, int b0, int nb, const long long* feat_id) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (bad_range(c, b0, nb) || !c->life_stats || track_block_frame_open(c) || c->F <= 0 || c->F > c->book.ld || (nb > 0 && !feat_id))
+  if (bad_range(c, b0, nb) || !c->life.configured() || track_block_frame_open(c) || c->F <= 0 || c->F > c->book.ld || (nb > 0 && !feat_id))
     return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
   return book_set(c, b0, nb, feat_id);
@@ -237,13 +225,13 @@ int xivo_hip_life_set_book(xivo_hip_ctx* c, int b0, int nb, const long long* fea
 
 int xivo_hip_life_get_book(xivo_hip_ctx* c, int b0, int nb, long long* feat_id, int* feat_ref, int* group_refs) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (bad_range(c, b0, nb) || !c->life_stats || c->F <= 0 || c->F > c->book.ld) return XIVO_HIP_ERR_INVALID;
+  if (bad_range(c, b0, nb) || !c->life.configured() || c->F <= 0 || c->F > c->book.ld) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
   return book_get(c, b0, nb, feat_id, feat_ref, group_refs);
 }
 
 int xivo_hip_life_begin(xivo_hip_ctx* c, int B, int F, const int* off, const long long* ids, const double* meas) {
-  if (!frame_can_begin(c, B, F) || !c->life_stats || c->fpool || !track_block_frame_ok(c, B, off, ids, meas)) return XIVO_HIP_ERR_INVALID;
+  if (!frame_can_begin(c, B, F) || !c->life.configured() || c->pool.configured() || !track_block_frame_ok(c, B, off, ids, meas)) return XIVO_HIP_ERR_INVALID;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   int rc = ensure_gate_buffers(c, F);   // (allocated by life_config: checks F only)
   if (rc) return rc;
@@ -253,22 +241,22 @@ int xivo_hip_life_begin(xivo_hip_ctx* c, int B, int F, const int* off, const lon
 }
 
 int xivo_hip_life_begin_tracks(xivo_hip_ctx* c, int B, int F) {
-  if (!frame_can_begin(c, B, F) || !c->life_stats || c->fpool || !c->pcw_cnt || !c->pcw_fresh || c->pcw_tracks_B != B)
+  if (!frame_can_begin(c, B, F) || !c->life.configured() || c->pool.configured() || !c->world.tracks_fresh_for(B))
     return XIVO_HIP_ERR_INVALID;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   int rc = ensure_gate_buffers(c, F);   // (allocated by life_config: checks F only)
   if (rc) return rc;
-  track_block_use_strided(c); c->pcw_fresh = false;
+  track_block_use_strided(c); c->world.tracks_consumed();
   return life_begin_frame(c, B, F);
 }
 
 int xivo_hip_life_end(xivo_hip_ctx* c, int B) {
-  if (!c || !c->life_stats || c->fpool || B <= 0 || B != track_block_frame(c) || !c->mask || c->F <= 0) return XIVO_HIP_ERR_INVALID;
+  if (!c || !c->life.configured() || c->pool.configured() || B <= 0 || B != track_block_frame(c) || !c->mask || c->F <= 0) return XIVO_HIP_ERR_INVALID;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   LifeArgs a = life_args_common(c, B);
   life_args_update(c, a);
-  a.stats = c->life_stats;
-  const xivo_life_opts& o = c->life_opts;
+  a.stats = c->life.stats;
+  const xivo_life_opts& o = c->life.opts;
   a.min_new_features = o.min_new_features; a.min_depth = o.min_depth; a.max_depth = o.max_depth;
   for (int i = 0; i < 3; ++i) a.var_xyz[i] = o.var_xyz[i];
   a.fx = c->cam.fx; a.fy = c->cam.fy; a.cx = c->cam.cx; a.cy = c->cam.cy;
@@ -279,9 +267,9 @@ int xivo_hip_life_end(xivo_hip_ctx* c, int B) {
 
 int xivo_hip_life_stats(xivo_hip_ctx* c, int b0, int nb, xivo_life_stats* out) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (bad_range(c, b0, nb) || !c->life_stats || (nb > 0 && !out)) return XIVO_HIP_ERR_INVALID;
+  if (bad_range(c, b0, nb) || !c->life.configured() || (nb > 0 && !out)) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
-  return d2h_rows(c, out, sizeof(xivo_life_stats), c->life_stats + b0, sizeof(xivo_life_stats), sizeof(xivo_life_stats), nb);
+  return d2h_rows(c, out, sizeof(xivo_life_stats), c->life.stats + b0, sizeof(xivo_life_stats), sizeof(xivo_life_stats), nb);
 }
 
 }  // extern "C"

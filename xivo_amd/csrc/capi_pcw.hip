@@ -14,24 +14,19 @@ using namespace xivo_hip::capi;
 namespace xivo_hip::capi {
 
 void pcw_release(xivo_hip_ctx* c) {
-  c->mem.release(&c->pcw_Xs, &c->pcw_ids, &c->pcw_next_id, &c->pcw_cnt, &c->pcw_gsc);
-  for (int i = 0; i < 2; ++i) {
-    if (c->pcw_pin[i]) { hipHostFree(c->pcw_pin[i]); c->pcw_pin[i] = nullptr; }
-    if (c->pcw_ev[i]) { hipEventDestroy(c->pcw_ev[i]); c->pcw_ev[i] = nullptr; }
-  }
-  c->pcw_opts = xivo_pcw_opts{}; c->pcw_cur = 0; c->pcw_tracks_B = 0; c->pcw_fresh = false;
-  c->pcw_use_cam = false; c->pcw_cam = xivo_cam{}; c->pcw_max_radius = 0.0;
+  c->mem.release(&c->world.Xs, &c->world.ids, &c->world.next_id, &c->world.cnt, &c->world.gsc);
+  c->world = World{};   // (the page-locked staging of the poses goes with it)
 }
 
 int pcw_produce(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, unsigned long long seed, unsigned long long frame) {
-  const xivo_pcw_opts& o = c->pcw_opts;
+  const xivo_pcw_opts& o = c->world.opts;
   PcwArgs a{};
-  a.Xs = c->pcw_Xs; a.ids = c->pcw_ids; a.next_id = c->pcw_next_id; a.gsc = gsc; a.npts = o.npts;
+  a.Xs = c->world.Xs; a.ids = c->world.ids; a.next_id = c->world.next_id; a.gsc = gsc; a.npts = o.npts;
   a.fx = o.fx; a.fy = o.fy; a.cx = o.cx; a.cy = o.cy; a.imw = o.imw; a.imh = o.imh;
   a.noise_px_std = noise_px_std; a.seed = seed; a.frame = frame;
-  a.use_cam = c->pcw_use_cam ? 1 : 0; a.cam = c->pcw_cam; a.max_radius = c->pcw_max_radius;
-  a.track_ids = track_block_strided_ids(c); a.track_meas = track_block_strided_meas(c); a.cnt = c->pcw_cnt; a.track_ld = track_block_row(c);
-  c->pcw_tracks_B = 0; c->pcw_fresh = false;   // (whatever the block held is being overwritten)
+  a.use_cam = c->world.use_cam ? 1 : 0; a.cam = c->world.cam; a.max_radius = c->world.max_radius;
+  a.track_ids = track_block_strided_ids(c); a.track_meas = track_block_strided_meas(c); a.cnt = c->world.cnt; a.track_ld = track_block_row(c);
+  c->world.tracks_overwritten();   // (whatever the block held)
   {
     // per filter: the points and their ids in, the ids that changed and at most npts tracks of 32 bytes out
     char label[32];   // the instance launch_pcw_tracks picks, as the tracer prints it
@@ -39,7 +34,7 @@ int pcw_produce(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, 
     StageTimer st(c, ST_OTHER, 0.0, label, (double)B * o.npts * (24.0 + 8.0 + 8.0 + 32.0));
     if (launch_pcw_tracks(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
   }
-  c->pcw_tracks_B = B; c->pcw_fresh = true;
+  c->world.tracks_B = B; c->world.fresh = true;
   return XIVO_HIP_OK;
 }
 
@@ -47,7 +42,7 @@ int pcw_produce(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, 
 
 namespace {
 
-bool pcw_ready(const xivo_hip_ctx* c) { return c && c->pcw_Xs && track_block_row(c) > 0 && c->pcw_opts.npts > 0; }
+bool pcw_ready(const xivo_hip_ctx* c) { return c && c->world.configured() && track_block_row(c) > 0 && c->world.opts.npts > 0; }
 
 }  // namespace
 
@@ -56,7 +51,7 @@ extern "C" {
 int xivo_hip_pcw_config(xivo_hip_ctx* c, const xivo_pcw_opts* o) {
   if (!c || !o || o->struct_size != (int)sizeof(xivo_pcw_opts) || o->npts < 0) return XIVO_HIP_ERR_INVALID;
   if (o->npts > 0) {
-    if ((!c->life_stats && !c->plife_on) || o->npts > track_block_row(c)) return XIVO_HIP_ERR_INVALID;   // either device life cycle
+    if (!c->life_cycle_configured() || o->npts > track_block_row(c)) return XIVO_HIP_ERR_INVALID;   // either device life cycle
     const double v[6] = {o->fx, o->fy, o->cx, o->cy, o->imw, o->imh};
     for (double x : v) if (!isfinite(x)) return XIVO_HIP_ERR_INVALID;
   }
@@ -66,33 +61,28 @@ int xivo_hip_pcw_config(xivo_hip_ctx* c, const xivo_pcw_opts* o) {
   pcw_release(c);
   if (o->npts == 0) return XIVO_HIP_OK;
   const size_t B = c->Bmax, n = o->npts;
-  int rc = c->mem.raw(&c->pcw_Xs, B * n * 3);
-  if (!rc) rc = c->mem.raw(&c->pcw_ids, B * n);
-  if (!rc) rc = c->mem.raw(&c->pcw_next_id, B);
-  if (!rc) rc = c->mem.zeroed(&c->pcw_cnt, B);
-  if (!rc) rc = c->mem.zeroed(&c->pcw_gsc, B * 12);
+  int rc = c->mem.raw(&c->world.Xs, B * n * 3);
+  if (!rc) rc = c->mem.raw(&c->world.ids, B * n);
+  if (!rc) rc = c->mem.raw(&c->world.next_id, B);
+  if (!rc) rc = c->mem.zeroed(&c->world.cnt, B);
+  if (!rc) rc = c->mem.zeroed(&c->world.gsc, B * 12);
   // the poses as the tracks of xivo_hip_life_begin: one device block behind the stream's order, two page-locked blocks so that
   // the host writes the next frame's poses while the previous upload may still be reading
-  for (int i = 0; i < 2 && !rc; ++i) {
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->pcw_pin[i]), B * 12 * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-      c->pcw_pin[i] = nullptr; (void)hipGetLastError(); rc = XIVO_HIP_ERR_NOMEM;
-    }
-    if (!rc && hipEventCreateWithFlags(&c->pcw_ev[i], hipEventDisableTiming) != hipSuccess) { c->pcw_ev[i] = nullptr; rc = XIVO_HIP_ERR_HIP; }
-  }
+  if (!rc) rc = c->world.up.alloc(B * 12 * sizeof(double));
   // an empty world until xivo_hip_pcw_set_world: points at the origin, no track (all bytes 0xff: -1), ids from 0
-  if (!rc && hipMemsetAsync(c->pcw_Xs, 0, B * n * 3 * sizeof(double), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
-  if (!rc && hipMemsetAsync(c->pcw_ids, 0xff, B * n * sizeof(long long), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
-  if (!rc && hipMemsetAsync(c->pcw_next_id, 0, B * sizeof(long long), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (!rc && hipMemsetAsync(c->world.Xs, 0, B * n * 3 * sizeof(double), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (!rc && hipMemsetAsync(c->world.ids, 0xff, B * n * sizeof(long long), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (!rc && hipMemsetAsync(c->world.next_id, 0, B * sizeof(long long), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
   if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
   if (rc) { pcw_release(c); return rc; }
-  c->pcw_opts = *o;
+  c->world.opts = *o;
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_pcw_camera(xivo_hip_ctx* c, const xivo_cam* cam, double max_radius) {
   if (!pcw_ready(c) || track_block_frame_open(c)) return XIVO_HIP_ERR_INVALID;
   if (!cam) {   // back to the pinhole of xivo_pcw_opts
-    c->pcw_use_cam = false; c->pcw_cam = xivo_cam{}; c->pcw_max_radius = 0.0;
+    c->world.use_cam = false; c->world.cam = xivo_cam{}; c->world.max_radius = 0.0;
     return XIVO_HIP_OK;
   }
   if (cam->model != XIVO_CAM_PINHOLE && cam->model != XIVO_CAM_ATAN && cam->model != XIVO_CAM_RADTAN && cam->model != XIVO_CAM_EQUI)
@@ -102,7 +92,7 @@ int xivo_hip_pcw_camera(xivo_hip_ctx* c, const xivo_cam* cam, double max_radius)
   for (double x : v) if (!isfinite(x)) return XIVO_HIP_ERR_INVALID;
   for (double x : cam->d) if (!isfinite(x)) return XIVO_HIP_ERR_INVALID;
   // the frame calls hand the camera to the kernel by value: frames already enqueued keep the one they were launched with
-  c->pcw_use_cam = true; c->pcw_cam = *cam; c->pcw_max_radius = max_radius;
+  c->world.use_cam = true; c->world.cam = *cam; c->world.max_radius = max_radius;
   return XIVO_HIP_OK;
 }
 
@@ -110,14 +100,14 @@ int xivo_hip_pcw_set_world(xivo_hip_ctx* c, int b0, int nb, const double* Xs, co
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (bad_range(c, b0, nb) || !pcw_ready(c) || track_block_frame_open(c) || (nb > 0 && !Xs)) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
-  const size_t n = c->pcw_opts.npts;
+  const size_t n = c->world.opts.npts;
   std::vector<long long> fill;
   if (!ids) { fill.assign((size_t)nb * n, -1); ids = fill.data(); }
   std::vector<long long> first;
   if (!next_id) { first.assign((size_t)nb, 10000); next_id = first.data(); }   // counter0 of src/feature.h
-  HIP_TRY(hipMemcpyAsync(c->pcw_Xs + (size_t)b0 * n * 3, Xs, (size_t)nb * n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->pcw_ids + (size_t)b0 * n, ids, (size_t)nb * n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->pcw_next_id + b0, next_id, (size_t)nb * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->world.Xs + (size_t)b0 * n * 3, Xs, (size_t)nb * n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->world.ids + (size_t)b0 * n, ids, (size_t)nb * n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->world.next_id + b0, next_id, (size_t)nb * sizeof(long long), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));   // pageable sources
   return XIVO_HIP_OK;
 }
@@ -126,13 +116,13 @@ int xivo_hip_pcw_get_world(xivo_hip_ctx* c, int b0, int nb, long long* ids, long
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (bad_range(c, b0, nb) || !pcw_ready(c)) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
-  const size_t n = c->pcw_opts.npts;
+  const size_t n = c->world.opts.npts;
   if (ids) {
-    int rc = d2h_rows(c, ids, n * sizeof(long long), c->pcw_ids + (size_t)b0 * n, n * sizeof(long long), n * sizeof(long long), nb);
+    int rc = d2h_rows(c, ids, n * sizeof(long long), c->world.ids + (size_t)b0 * n, n * sizeof(long long), n * sizeof(long long), nb);
     if (rc) return rc;
   }
   if (next_id) {
-    int rc = d2h_rows(c, next_id, sizeof(long long), c->pcw_next_id + b0, sizeof(long long), sizeof(long long), nb);
+    int rc = d2h_rows(c, next_id, sizeof(long long), c->world.next_id + b0, sizeof(long long), sizeof(long long), nb);
     if (rc) return rc;
   }
   return XIVO_HIP_OK;
@@ -143,30 +133,28 @@ int xivo_hip_pcw_tracks(xivo_hip_ctx* c, int B, const double* gsc, double noise_
   if (!pcw_ready(c) || B <= 0 || B > c->Bmax || !gsc || track_block_frame_open(c) || !isfinite(noise_px_std)) return XIVO_HIP_ERR_INVALID;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   // the staging block the previous frame did not use; it is free once its upload (two frames back) has finished
-  const int set = c->pcw_cur ^ 1;
-  HIP_TRY(hipEventSynchronize(c->pcw_ev[set]));
+  char* h = nullptr;
+  if (int rc = c->world.up.stage(&h)) return rc;
   const size_t bytes = (size_t)B * 12 * sizeof(double);
-  memcpy(c->pcw_pin[set], gsc, bytes);
-  HIP_TRY(hipMemcpyAsync(c->pcw_gsc, c->pcw_pin[set], bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipEventRecord(c->pcw_ev[set], c->stream));
-  c->pcw_cur = set;
-  return pcw_produce(c, B, c->pcw_gsc, noise_px_std, seed, frame);
+  memcpy(h, gsc, bytes);
+  if (int rc = c->world.up.enqueue(c->world.gsc, bytes, c->stream)) return rc;
+  return pcw_produce(c, B, c->world.gsc, noise_px_std, seed, frame);
 }
 
 int xivo_hip_pcw_tracks_resident(xivo_hip_ctx* c, int B, double noise_px_std, unsigned long long seed, unsigned long long frame) {
-  if (!pcw_ready(c) || B <= 0 || B > c->Bmax || track_block_frame_open(c) || !isfinite(noise_px_std) || !c->ts_gsc || c->ts_B != B)
+  if (!pcw_ready(c) || B <= 0 || B > c->Bmax || track_block_frame_open(c) || !isfinite(noise_px_std) || !c->trajsim.frame_poses(B))
     return XIVO_HIP_ERR_INVALID;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  return pcw_produce(c, B, c->ts_gsc, noise_px_std, seed, frame);
+  return pcw_produce(c, B, c->trajsim.frame_poses(B), noise_px_std, seed, frame);
 }
 
 int xivo_hip_pcw_get_tracks(xivo_hip_ctx* c, int b0, int nb, int* cnt, long long* ids, double* meas) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (bad_range(c, b0, nb) || !pcw_ready(c) || b0 + nb > c->pcw_tracks_B) return XIVO_HIP_ERR_INVALID;
+  if (bad_range(c, b0, nb) || !pcw_ready(c) || b0 + nb > c->world.tracks_B) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
   const size_t ld = track_block_row(c);
   std::vector<int> n((size_t)nb);
-  int rc = d2h_rows(c, n.data(), sizeof(int), c->pcw_cnt + b0, sizeof(int), sizeof(int), nb);
+  int rc = d2h_rows(c, n.data(), sizeof(int), c->world.cnt + b0, sizeof(int), sizeof(int), nb);
   if (rc) return rc;
   if (ids) {
     rc = d2h_rows(c, ids, ld * sizeof(long long), track_block_strided_ids(c) + (size_t)b0 * ld, ld * sizeof(long long), ld * sizeof(long long), nb);

@@ -26,7 +26,7 @@ extern "C" {
 int xivo_hip_traj_score(xivo_hip_ctx* c, int b0, int nb, int t0, int nt, const double* gt, const xivo_traj_score_opts* o,
                         xivo_traj_score* out) {
   if (!c || !gt || !o || !out || o->rpe_lag < 0) return XIVO_HIP_ERR_INVALID;
-  if (bad_slice(c, c->traj_log, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
+  if (bad_slice(c, c->traj.log, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
   if (nt == 0) {
     for (int b = 0; b < nb; ++b) out[b] = empty_score();
@@ -39,14 +39,14 @@ int xivo_hip_traj_score(xivo_hip_ctx* c, int b0, int nb, int t0, int nt, const d
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   // per-call staging (the trajectory log's, shared with xivo_hip_traj_nees): gt in | nb records out
   const size_t n_gt = (size_t)nt * nb * 12 * sizeof(double), bytes = n_gt + (size_t)nb * sizeof(xivo_traj_score);
-  int rc = c->mem.grow(&c->traj_io, &c->traj_io_cap, bytes);
+  int rc = c->mem.grow(&c->traj.io, &c->traj.io_cap, bytes);
   if (rc) return rc;
   TrajScoreArgs a{};
-  a.rec = c->traj_rec; a.Bmax = c->Bmax; a.b0 = b0; a.nb = nb; a.t0 = t0; a.nt = nt;
+  a.rec = c->traj.rec; a.Bmax = c->Bmax; a.b0 = b0; a.nb = nb; a.t0 = t0; a.nt = nt;
   a.align = o->align != 0; a.rpe_lag = o->rpe_lag;
-  a.gt = reinterpret_cast<const double*>(c->traj_io);
-  a.out = reinterpret_cast<xivo_traj_score*>(c->traj_io + n_gt);
-  HIP_TRY(hipMemcpyAsync(c->traj_io, gt, n_gt, hipMemcpyHostToDevice, c->stream));
+  a.gt = reinterpret_cast<const double*>(c->traj.io);
+  a.out = reinterpret_cast<xivo_traj_score*>(c->traj.io + n_gt);
+  HIP_TRY(hipMemcpyAsync(c->traj.io, gt, n_gt, hipMemcpyHostToDevice, c->stream));
   {
     StageTimer st(c, ST_OTHER, 0.0, "traj_score_kernel", 4.0 * nt * (double)nb * 2.0 * 96.0);
     if (launch_traj_score(a, c->stream)) return XIVO_HIP_ERR_HIP;

@@ -8,7 +8,7 @@ using namespace xivo_hip::capi;
 
 namespace {
 
-int traj_pack(const xivo_hip_ctx* c) { return c->traj_ncols * (c->traj_ncols + 1) / 2; }
+int traj_pack(const xivo_hip_ctx* c) { return c->traj.ncols * (c->traj.ncols + 1) / 2; }
 
 }  // namespace
 
@@ -30,70 +30,70 @@ int xivo_hip_traj_config(xivo_hip_ctx* c, const xivo_traj_opts* o) {
   }
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   HIP_TRY(hipStreamSynchronize(c->stream));   // a record launch may still be writing the blocks given back here
-  c->mem.release(&c->traj_io);
-  c->traj_io_cap = 0; c->traj_ncols = 0;
-  const int rc = log_realloc(c, c->traj_log, o->T_max, &c->traj_rec, n_rec, &c->traj_cov, n_cov);
+  c->mem.release(&c->traj.io, &c->traj.rec, &c->traj.cov);
+  c->traj = TrajLog{};
+  const int rc = log_alloc(c, c->traj.log, o->T_max, &c->traj.rec, n_rec, &c->traj.cov, n_cov);
   if (rc || o->T_max == 0) return rc;
-  c->traj_ncols = o->n_cols;
-  for (int i = 0; i < o->n_cols; ++i) c->traj_cols[i] = o->cols[i];
+  c->traj.ncols = o->n_cols;
+  for (int i = 0; i < o->n_cols; ++i) c->traj.cols[i] = o->cols[i];
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_traj_record(xivo_hip_ctx* c, int B, long long ts_ns, int* frame_out) {
-  if (!c || B <= 0 || B > c->Bmax || !c->traj_log.configured() || !c->poses) return XIVO_HIP_ERR_INVALID;
-  if (c->traj_log.full()) return XIVO_HIP_ERR_FULL;
+  if (!c || B <= 0 || B > c->Bmax || !c->traj.configured() || !c->poses) return XIVO_HIP_ERR_INVALID;
+  if (c->traj.log.full()) return XIVO_HIP_ERR_FULL;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   const int pack = traj_pack(c);
-  const size_t at = FrameLog::at(c->traj_log.count(), c->Bmax, 0);
+  const size_t at = FrameLog::at(c->traj.log.count(), c->Bmax, 0);
   TrajRecordArgs a{};
   a.poses = c->poses; a.status = c->status; c->P.to(a.P, a.strideP, a.ldp);
-  a.rec = c->traj_rec + at; a.cov = c->traj_cov + at * pack; a.n_cols = c->traj_ncols; a.pack = pack;
-  for (int i = 0; i < c->traj_ncols; ++i) a.cols[i] = c->traj_cols[i];
+  a.rec = c->traj.rec + at; a.cov = c->traj.cov + at * pack; a.n_cols = c->traj.ncols; a.pack = pack;
+  for (int i = 0; i < c->traj.ncols; ++i) a.cols[i] = c->traj.cols[i];
   {
     StageTimer st(c, ST_OTHER, 0.0, "traj_record_kernel", (double)B * (2.0 * sizeof(xivo_traj_rec) + 16.0 * pack));
     if (launch_traj_record(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
   }
-  log_commit(c->traj_log, ts_ns, frame_out);
+  log_commit(c->traj.log, ts_ns, frame_out);
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_traj_count(xivo_hip_ctx* c) {
-  if (!c || !c->traj_log.configured()) return XIVO_HIP_ERR_INVALID;
-  return c->traj_log.count();
+  if (!c || !c->traj.configured()) return XIVO_HIP_ERR_INVALID;
+  return c->traj.log.count();
 }
 
 int xivo_hip_traj_reset(xivo_hip_ctx* c) {
-  if (!c || !c->traj_log.configured()) return XIVO_HIP_ERR_INVALID;
-  c->traj_log.reset();
+  if (!c || !c->traj.configured()) return XIVO_HIP_ERR_INVALID;
+  c->traj.log.reset();
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_traj_read(xivo_hip_ctx* c, int b0, int nb, int t0, int nt, xivo_traj_rec* recs, double* cov, long long* ts) {
-  if (!c || bad_slice(c, c->traj_log, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
-  c->traj_log.stamps(t0, nt, ts);
+  if (!c || bad_slice(c, c->traj.log, b0, nb, t0, nt)) return XIVO_HIP_ERR_INVALID;
+  c->traj.log.stamps(t0, nt, ts);
   if (nb == 0 || nt == 0 || (!recs && !cov)) return XIVO_HIP_OK;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  if (d2h_frames(c, recs, c->traj_rec, sizeof(xivo_traj_rec), b0, nb, t0, nt) ||
-      d2h_frames(c, cov, c->traj_cov, (size_t)traj_pack(c) * sizeof(double), b0, nb, t0, nt)) return XIVO_HIP_ERR_HIP;
+  if (d2h_frames(c, recs, c->traj.rec, sizeof(xivo_traj_rec), b0, nb, t0, nt) ||
+      d2h_frames(c, cov, c->traj.cov, (size_t)traj_pack(c) * sizeof(double), b0, nb, t0, nt)) return XIVO_HIP_ERR_HIP;
   HIP_TRY(hipStreamSynchronize(c->stream));
   return XIVO_HIP_OK;
 }
 
 int xivo_hip_traj_nees(xivo_hip_ctx* c, int b0, int nb, int t0, int nt, const double* gt, double* err6, double* nees,
                        double* anees, int* n_used) {
-  if (!c || bad_slice(c, c->traj_log, b0, nb, t0, nt) || !gt) return XIVO_HIP_ERR_INVALID;
+  if (!c || bad_slice(c, c->traj.log, b0, nb, t0, nt) || !gt) return XIVO_HIP_ERR_INVALID;
   TrajNeesArgs a{};
   for (int k = 0; k < 6; ++k) {
     a.pos6[k] = -1;
-    for (int i = 0; i < c->traj_ncols; ++i) if (c->traj_cols[i] == k) a.pos6[k] = i;
+    for (int i = 0; i < c->traj.ncols; ++i) if (c->traj.cols[i] == k) a.pos6[k] = i;
     if (a.pos6[k] < 0) return XIVO_HIP_ERR_INVALID;   // the pose block (Wsb, Tsb) is not in the log
   }
   if (nb == 0 || nt == 0) return XIVO_HIP_OK;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   NeesStaging io;
-  const int rc = io.up(c, &c->traj_io, &c->traj_io_cap, (size_t)nb, nt, 12, 6, gt);
+  const int rc = io.up(c, &c->traj.io, &c->traj.io_cap, (size_t)nb, nt, 12, 6, gt);
   if (rc) return rc;
-  a.rec = c->traj_rec; a.cov = c->traj_cov; a.Bmax = c->Bmax; a.pack = traj_pack(c);
+  a.rec = c->traj.rec; a.cov = c->traj.cov; a.Bmax = c->Bmax; a.pack = traj_pack(c);
   a.b0 = b0; a.nb = nb; a.t0 = t0; a.nt = nt;
   a.gt = io.gt; a.err6 = err6 ? io.err : nullptr; a.nees = io.nees; a.anees = io.anees; a.n_used = io.n_used;
   if (launch_traj_nees(a, c->stream)) return XIVO_HIP_ERR_HIP;

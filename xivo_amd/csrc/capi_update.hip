@@ -663,11 +663,11 @@ int xivo_hip_last_route(xivo_hip_ctx* c) { return c ? c->last_route : -1; }
 const char* xivo_hip_route_name(int route) { return route >= 0 && route < ROUTE_COUNT ? kRouteNames[route] : ""; }
 
 double xivo_hip_stage_bytes(xivo_hip_ctx* c, int stage) {
-  return (c && stage >= 0 && stage < ST_COUNT) ? c->stage_bytes[stage] : 0.0;
+  return (c && stage >= 0 && stage < ST_COUNT) ? c->prof.bytes[stage] : 0.0;
 }
 
 const char* xivo_hip_stage_kernel(xivo_hip_ctx* c, int stage) {
-  return (c && stage >= 0 && stage < ST_COUNT) ? c->stage_kernel[stage] : "";
+  return (c && stage >= 0 && stage < ST_COUNT) ? c->prof.kernel[stage] : "";
 }
 
 int xivo_hip_get_gate(xivo_hip_ctx* c, int B, int F, unsigned char* mask_out, double* dist_out) {
