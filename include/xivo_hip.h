@@ -1053,6 +1053,71 @@ int xivo_hip_pool_life_end(xivo_hip_ctx* ctx, int B);
 /* The counters of filters [b0, b0 + nb). Synchronises. */
 int xivo_hip_pool_life_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_pool_life_stats* out);
 
+/* ---- MSCKF update from tracks that end outside the state (opt-in; needs xivo_hip_pool_config) --------------------------------
+ * The reference parses use_OOS / OOS_update_min_observations / oos_meas_std and stops with "MSCKF not implemented"
+ * (src/estimator.cpp:113-122). Here a pool entry whose track ends while it is READY, with a depth inside (min_depth, max_depth)
+ * and at least min_obs observations from anchors whose groups are in the state now, constrains those groups once: its world
+ * point Xs = Feature::Xs(gbc) of the resident entry and its anchor's pose goes with the observations (group slot, pixel) into
+ * the context's resident OOS list - the one xivo_hip_oos_project(feats == NULL) re-projects -, at most oos_max entries per filter
+ * and frame in ascending entry index. The integer rules are pool_lifecycle_device.h's (plife_oos_*, plife_hist_*).
+ * Frame order: ... -> xivo_hip_pool_oos_collect -> pool step / admissions -> Jacobians, gate, xivo_hip_stack ->
+ * xivo_hip_pool_oos_project -> xivo_hip_pool_oos_gate -> xivo_hip_update_joseph.
+ * Two life cycles, one list, byte for byte. Host life cycle: the observation rings are the host's (SequenceRunner's _PoolBook)
+ * and xivo_hip_pool_oos_collect hands its decisions down. Device pool life cycle (xivo_hip_pool_life_config first, then
+ * xivo_hip_pool_oos_config, before the first frame): the rings live in HBM next to the pool, xivo_hip_pool_life_begin[_tracks]
+ * makes the list itself between its begin kernel and the pool step (pool_oos_select_kernel), xivo_hip_pool_life_end records the
+ * frame's observations (pool_oos_record_kernel); nothing is uploaded, downloaded or waited for. */
+typedef struct {
+  int struct_size;   /* sizeof(xivo_pool_oos_opts) */
+  int oos_max;       /* OOS features per filter and frame; 0: off, the buffers are released */
+  int max_obs;       /* observations per feature, 2 .. XIVO_OOS_MAX_OBS */
+  int min_obs;       /* OOS_update_min_observations (5), 2 .. max_obs */
+  double Roos;       /* oos_meas_std^2, > 0 */
+  double chi2[32];   /* chi2[dof]: gate threshold of a feature with dof = 2k - 3 rows; 0: no gate for that dof */
+} xivo_pool_oos_opts;
+/* One dropped pool entry as the host life cycle hands it over: its valid observations, oldest first. Records are ordered by
+ * (b, entry); n_obs may be anything in 0 .. max_obs (the device decides with the entry's status and depth). */
+typedef struct {
+  int b, entry, n_obs, reserved;
+  int group_sind[XIVO_OOS_MAX_OBS];
+  double xp[XIVO_OOS_MAX_OBS][2];
+} xivo_pool_oos_cand;
+typedef struct {
+  long long oos_used;     /* entries put on a frame's list (counted when the list is made; gated ones included) */
+  long long oos_gated;    /* of those, gated out by xivo_hip_pool_oos_gate */
+  long long oos_surplus;  /* eligible beyond oos_max */
+  long long oos_short;    /* READY, dropped, fewer than min_obs valid observations */
+} xivo_pool_oos_stats;
+/* Every frame then reserves oos_max * (2 max_obs - 3) rows behind the in-state rows (xivo_hip_pool_oos_rows): create the context
+ * with that many rows more plus the 16 rows the mixed stacking pads the block with. Zeroes the counters. */
+int xivo_hip_pool_oos_config(xivo_hip_ctx* ctx, const xivo_pool_oos_opts* opts);
+int xivo_hip_pool_oos_rows(xivo_hip_ctx* ctx);
+/* Host life cycle only (the device one makes the list itself). The frame's list of filters [0, B) from the host's decisions: n records, before the pool step of the frame (which frees the
+ * dropped entries) and after the frame's group removals are known to the host - group_sind are the slots the observing
+ * anchors' groups hold in this frame's update. One wave per filter walks its records in order (plife_oos_decide), computes Xs of
+ * the used ones and writes positions [0, used) of the filter's oos_max list positions; the others get n_obs = 0. An observation
+ * whose group_sind is outside the layout is dropped. The entries' data never leave the device. Synchronises (cands is borrowed). */
+int xivo_hip_pool_oos_collect(xivo_hip_ctx* ctx, int B, int n, const xivo_pool_oos_cand* cands);
+/* After xivo_hip_stack: the resident list's rows (oos_kernel, the mixed stacking of xivo_hip_oos_project_ex) into the fixed
+ * block; rows no feature fills are H = 0, inn = 0, diagR = Roos - they change M and S but not K, dx or P+
+ * (XIVO_HIP_OOS_WHOLE_BUFFER). Neither synchronises nor downloads. XIVO_HIP_ERR_UNSUPPORTED where the mixed stacking does not
+ * apply (online calibration, XIVO_HIP_FLAG_DENSE_H, a context without the spare rows). */
+int xivo_hip_pool_oos_project(xivo_hip_ctx* ctx, int B);
+/* After xivo_hip_pool_oos_project: per (filter, list position) gamma = r^T (H_o P H_o^T + Roos I)^-1 r over the feature's
+ * 2k - 3 rows, from the sub-block of P under the Wbc / Tbc and the k observing groups' columns (chol in LDS, one workgroup each).
+ * gamma > chi2[2k - 3] (where that is > 0) or a non-positive pivot gates the feature out: its H rows and inn become zero, diagR
+ * stays, oos_gated counts it. gamma is kept per feature (-1: non-positive pivot, 0: unused position). No synchronisation. */
+int xivo_hip_pool_oos_gate(xivo_hip_ctx* ctx, int B);
+/* tests, diagnostics: the resident list [nb][oos_max] and gamma [nb][oos_max] of filters [b0, b0 + nb). Either may be NULL. */
+int xivo_hip_pool_oos_get(xivo_hip_ctx* ctx, int b0, int nb, xivo_oos_in* list, double* gamma);
+/* ... and the device life cycle's history of filters [b0, b0 + nb): the anchors' creation frames anc_born [nb][anchor_max] and the
+ * rings hist_cnt [nb][pool_max] (observations appended since the entry was taken; ring slot = count % max_obs), hist_anchor /
+ * hist_born [nb][pool_max][max_obs], hist_xp [nb][pool_max][max_obs][2]. Any pointer may be NULL. XIVO_HIP_ERR_INVALID without the
+ * device pool life cycle. */
+int xivo_hip_pool_oos_get_rings(xivo_hip_ctx* ctx, int b0, int nb, int* anc_born, int* hist_cnt, int* hist_anchor, int* hist_born,
+                                double* hist_xp);
+int xivo_hip_pool_oos_get_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_pool_oos_stats* out);
+
 /* ---- point-cloud world: the simulator's tracks produced on the device (opt-in; needs one of the device life cycles) -------
  * What BatchPCW.generate (xivo_amd/pcw.py, after the reference's scripts/point_cloud_world.py:44-131) computes on the host per
  * camera frame: every world point is projected through the frame's ground-truth camera pose, a point in front of the camera

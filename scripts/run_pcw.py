@@ -96,6 +96,13 @@ def main():
     ap.add_argument("-max-radius", dest="max_radius", type=float, default=float("inf"),
                     help="-cam-model other than pinhole: a point whose normalised radius exceeds this is not visible (the guard "
                          "against a polynomial distortion's fold-back far off axis)")
+    ap.add_argument("-use-oos", dest="use_oos", action="store_true",
+                    help="MSCKF update from pool entries whose track ends (SequenceConfig.use_oos): needs -feature_init subfilter with "
+                         "-host python, or -pool-lifecycle device with any host side; the report gains oos_used / oos_gated / oos_surplus / "
+                         "oos_short")
+    ap.add_argument("-oos-min-obs", dest="oos_min_obs", type=int, default=5,
+                    help="-use-oos: observations an entry needs (OOS_update_min_observations)")
+    ap.add_argument("-seed", type=int, default=0, help="-vectorized: the seed of the worlds and trajectories")
     a = ap.parse_args()
     # (a sequence never brings more tracks than its world has points)
     life = dict(lifecycle=a.lifecycle, tracks_max=min(a.npts, sequence.L.LIFE_MAX_TRACKS))
@@ -110,6 +117,17 @@ def main():
     if a.feature_init != "immediate" or a.pool_lifecycle != "host":
         life.update(feature_init=a.feature_init, pool_lifecycle=a.pool_lifecycle)
         try:      # before any rank is spawned: what check_lifecycle rejects
+            sequence.check_lifecycle(sequence.SequenceConfig(**life))
+        except ValueError as e:
+            ap.error(str(e))
+    if a.use_oos:
+        if (a.vectorized or a.host != "python") and a.pool_lifecycle != "device":
+            ap.error("-use-oos with -vectorized or -host cpp needs -pool-lifecycle device (the C++ host life cycle keeps no "
+                     "observation history)")
+        if a.innov_log:
+            ap.error("-use-oos and -innov-log exclude each other (the log's dof would count the empty rows of the OOS block)")
+        life.update(feature_init=a.feature_init, pool_lifecycle=a.pool_lifecycle, use_oos=True, oos_min_observations=a.oos_min_obs)
+        try:
             sequence.check_lifecycle(sequence.SequenceConfig(**life))
         except ValueError as e:
             ap.error(str(e))
@@ -139,8 +157,13 @@ def main():
         out = sequence.run_pcw_batch(cfg, a.sequences, total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
                                      noise_vision_std=a.noise_vision_std, npts=a.npts, timers=tm, trajectory_log=a.traj_log,
                                      map_log=a.map_log, rpe_dt=a.rpe_dt, innovation_log=a.innov_log, track_source=a.tracks,
-                                     imu_source=a.imu)
+                                     imu_source=a.imu, seed=a.seed)
         wall = time.perf_counter() - t0
+        oos = {}
+        if a.use_oos:     # the counters, and in how many sequences an entry was used at all
+            ost = out["estimator"].oos_stats()
+            oos = {k: int(ost[k].sum()) for k in ost.dtype.names}
+            oos["oos_sequences_with_used"] = int((ost["oos_used"] > 0).sum())
         st = out["estimator"].stats(); out["estimator"].close()
         frames = len(out["ts"])
         ate = np.sqrt(np.mean(np.sum((out["Tsb"] - out["gt_Tsb"]) ** 2, axis=2), axis=0))
@@ -148,7 +171,7 @@ def main():
             "sequences": a.sequences, "frames_per_sequence": frames, "N": cfg.N, "integration": a.integration_method,
             "host": "cpp, vectorised simulators", "lifecycle": a.lifecycle, "tracks": a.tracks, "imu": a.imu,
             "feature_init": a.feature_init, "pool_lifecycle": a.pool_lifecycle, "cam_model": a.cam_model,
-            **({"admitted": st["admitted"], "pool_dropped": st["pool_dropped"]} if a.feature_init == "subfilter" else {}),
+            **({"admitted": st["admitted"], "pool_dropped": st["pool_dropped"]} if a.feature_init == "subfilter" else {}), **oos,
             "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
             **_consistency(out),
             "updates": st["updates"], "mh_rejected": st["mh_rejected"], "wall_s": wall, "simulator_s": tm.get("sim", 0.0),
@@ -194,8 +217,11 @@ def main():
                                map_log=a.map_log, rpe_dt=a.rpe_dt, innovation_log=a.innov_log)
         r_ = out["runner"]
 
+        oos_st = out["backend"].oos_stats() if a.use_oos else None
+
         class _R:      # (read before the context goes: the device life cycle keeps the counters there)
             n_updates, n_rejected = r_.n_updates, r_.n_rejected
+            oos = {k: int(oos_st[k].sum()) for k in oos_st.dtype.names} if oos_st is not None else {}
         out["runner"] = _R
         out["backend"].close()
     wall = time.perf_counter() - t0
@@ -207,10 +233,11 @@ def main():
         os.makedirs(a.dump, exist_ok=True)
         for k, b in enumerate(mine):
             formats.write_trajectory(os.path.join(a.dump, "seq%04d.txt" % b), out["ts"], out["Tsb"][:, k], out["Wsb"][:, k])
-    n_upd, n_rej = r.n_updates, r.n_rejected
+    n_upd, n_rej, oos = r.n_updates, r.n_rejected, getattr(r, "oos", {})
     if dist is not None:
         parts = [None] * world
-        dist.all_gather_object(parts, (ate.tolist(), wall, dev, n_upd, n_rej))
+        dist.all_gather_object(parts, (ate.tolist(), wall, dev, n_upd, n_rej, oos))
+        oos = {k: sum(p_[5][k] for p_ in parts) for k in oos}
         ate = np.array(sum((p_[0] for p_ in parts), []))
         wall, dev = max(p_[1] for p_ in parts), max(p_[2] for p_ in parts)      # whole job = slowest rank
         n_upd, n_rej = sum(p_[3] for p_ in parts), sum(p_[4] for p_ in parts)
@@ -224,7 +251,7 @@ def main():
         "cam_model": a.cam_model,
         "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
         **_consistency(out),
-        "updates": n_upd, "mh_rejected": n_rej,
+        "updates": n_upd, "mh_rejected": n_rej, **oos,
         "wall_s": wall, "device_path_s": dev,
         "phase_s": {k: round(v, 4) for k, v in sorted(timers.items())},
         "device_frames_per_s": B * frames / dev if dev > 0 else None,

@@ -43,6 +43,8 @@ def load_host_library():
             raise FileNotFoundError(path + " not built: python -c 'import __graft_entry__ as g; g.build()'")
         _HOST = C.CDLL(path)
         _HOST.xivo_batch_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        _HOST.xivo_batch_create_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        _HOST.xivo_batch_enable_oos.argtypes = [C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_destroy.argtypes = [C.c_void_p]; _HOST.xivo_batch_destroy.restype = None
         _HOST.xivo_batch_imu.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_visual.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -93,7 +95,11 @@ class BatchEstimator:
         poses0 = np.ascontiguousarray(poses0, dtype=L.pose_dtype)
         P0 = np.asfortranarray(np.asarray(P0, dtype=np.float64))
         h = C.c_void_p()
-        if self.host.xivo_batch_create(c.ctypes.data, B, device, poses0.ctypes.data, P0.ctypes.data, C.byref(h)) != 0:
+        use_oos = bool(getattr(cfg, "use_oos", False))
+        if use_oos and getattr(cfg, "pool_lifecycle", "host") != "device":
+            raise ValueError("BatchEstimator: use_oos needs pool_lifecycle='device' (its host life cycle keeps no observation history)")
+        if self.host.xivo_batch_create_rows(c.ctypes.data, B, device, poses0.ctypes.data, P0.ctypes.data,
+                                            cfg.M_max() - 2 * cfg.n_features if use_oos else 0, C.byref(h)) != 0:
             raise RuntimeError("xivo_batch_create failed")
         self.h = h
         self.device_lifecycle = getattr(cfg, "lifecycle", "host") == "device"
@@ -133,6 +139,8 @@ class BatchEstimator:
                     raise RuntimeError("xivo_batch_enable_depth_init failed")
             if self.device_pool_lifecycle:
                 self.enable_device_pool_lifecycle(cfg.tracks_max)
+                if use_oos:
+                    self.enable_oos(cfg)
 
     def init_z(self):
         """AdaptInitialDepth's init_z [B] after the last frame (None while adaptive_initial_depth is off)"""
@@ -157,6 +165,20 @@ class BatchEstimator:
         asked for, book() and stats() read the device"""
         if self.host.xivo_batch_enable_device_pool_lifecycle(self.h, int(tracks_max)) != 0:
             raise RuntimeError("xivo_batch_enable_device_pool_lifecycle failed")
+
+    def enable_oos(self, cfg):
+        """BatchEstimator::EnableOosUpdates with cfg's oos_* options and the 0.95 chi-square table"""
+        o = np.zeros(1, dtype=L.pool_oos_opts_dtype)
+        o["struct_size"] = L.pool_oos_opts_dtype.itemsize
+        o["oos_max"], o["max_obs"], o["min_obs"] = cfg.oos_max, cfg.oos_max_obs, cfg.oos_min_observations
+        o["Roos"] = float(cfg.oos_meas_std) ** 2
+        o["chi2"][0, :] = L.CHI2_95
+        if self.host.xivo_batch_enable_oos(self.h, o.ctypes.data) != 0:
+            raise RuntimeError("xivo_batch_enable_oos failed")
+
+    def oos_stats(self):
+        """[B] pool_oos_stats_dtype read from the estimator's context"""
+        return L.Context.borrow(self.host.xivo_batch_ctx(self.h), self.cfg.N, self.cfg.M_max(), self.B).pool_oos_stats(0, self.B)
 
     def enable_device_world(self, Xs, max_radius=None):
         """BatchEstimator::EnableDeviceWorld: the worlds' points Xs [B, npts, 3] go to the device once (camera: cfg.cam, whatever

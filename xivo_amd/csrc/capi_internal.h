@@ -6,6 +6,7 @@
 //   capi_oos.hip        OOS rows, loop-closure stacking, OOS compression, Givens / QR
 //   capi_ransac.hip     OnePointRANSAC on the resident state
 //   capi_pool.hip       sub-filter, candidate order, the feature pool, triangulation, AdaptInitialDepth
+//   capi_pool_oos.hip   MSCKF update from dropped pool entries: the frame's list, its fixed row block, the chi-square gate
 //   capi_propagate.hip  propagation
 //   capi_traj.hip       trajectory log: per-frame records, read-out, NEES against ground truth
 //   capi_score.hip      trajectory score: aligned / unaligned ATE and RPE of the logged poses against ground truth
@@ -184,6 +185,22 @@ struct FeaturePool {
   void reset() { char* p = io; const size_t n = io_cap; *this = FeaturePool{}; io = p; io_cap = n; }
 };
 
+// MSCKF update from dropped pool entries (xivo_hip_pool_oos_*, capi_pool_oos.hip): options, the per-feature gate distances
+// gamma [Bmax][oos_max], the counters [Bmax]; the list itself is the resident OOS list (OosList). B: the filters whose list the last
+// collect call (host life cycle) or begin call (device life cycle) filled, 0: none; projected: its rows are in the block and not
+// gated yet. The device life cycle's part, next to the pool: the anchors' creation frames anc_born [Bmax][anchor_max] and the
+// observation rings hist_cnt [Bmax][pool_max], hist_anchor / hist_born [Bmax][pool_max][max_obs], hist_xp [..][max_obs][2]
+struct PoolOos {
+  xivo_pool_oos_opts opts{};
+  double* gamma = nullptr;
+  xivo_pool_oos_stats* stats = nullptr;
+  int *anc_born = nullptr, *hist_cnt = nullptr, *hist_anchor = nullptr, *hist_born = nullptr;
+  double* hist_xp = nullptr;
+  int B = 0; bool projected = false;
+  bool configured() const { return stats != nullptr; }
+  int rows() const { return opts.oos_max * (2 * opts.max_obs - 3); }
+};
+
 // device life cycle (xivo_hip_life_*, "the immediate life cycle"): its options and counters [Bmax]
 struct ImmediateLife {
   xivo_life_opts opts{};
@@ -340,6 +357,7 @@ struct xivo_hip_ctx {
   xivo_hip::capi::RansacScratch rs;
   xivo_hip::capi::OosList resident_oos;
   xivo_hip::capi::FeaturePool pool;
+  xivo_hip::capi::PoolOos pool_oos;
   xivo_hip::capi::ImmediateLife life;
   xivo_hip::capi::PoolLife plife;
   xivo_hip::capi::World world;
@@ -501,6 +519,21 @@ int propagate_device(xivo_hip_ctx* c, int B, int n_imu, const xivo_imu_in* recs,
 // ---- capi_pool.hip
 // the arguments of one pool step but xp / order / n / live (xivo_hip_pool_step and the device pool life cycle share them)
 PoolStepArgs pool_step_args(xivo_hip_ctx* c, int B, int strict);
+
+// ---- capi_oos.hip
+// the two halves of an OOS append that xivo_hip_oos_project_ex and xivo_hip_pool_oos_project share. oos_rows_begin: max_rows more
+// rows fit behind the staged ones (else XIVO_HIP_ERR_INVALID); *mixed: the mixed stacking applies (the block's columns are
+// cleared), else every row is made dense. oos_rows_launch: oos_kernel over the resident list of n_oos features per filter into
+// rows from M on; enqueues only
+int oos_rows_begin(xivo_hip_ctx* c, int b0, int nb, int max_rows, bool* mixed);
+int oos_rows_launch(xivo_hip_ctx* c, int nb, int n_oos, int M, double Roos, int whole, bool mixed);
+
+// ---- capi_pool_oos.hip
+void pool_oos_release(xivo_hip_ctx* c);   // everything xivo_hip_pool_oos_config allocated (the stream must be idle)
+// the device pool life cycle's two hooks (no-ops unless xivo_hip_pool_oos_config is on; enqueue only): the frame's list between
+// the begin kernel and the pool step of a frame of B filters, and the frame's observations behind the end kernel of frame `frame`
+int pool_oos_life_select(xivo_hip_ctx* c, int B);
+int pool_oos_life_record(xivo_hip_ctx* c, int B, int frame);
 
 // ---- capi_glevel.hip
 int ensure_gate_buffers(xivo_hip_ctx* c, int F);

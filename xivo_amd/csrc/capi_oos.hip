@@ -7,6 +7,50 @@
 using namespace xivo_hip;
 using namespace xivo_hip::capi;
 
+namespace xivo_hip::capi {
+
+int oos_rows_begin(xivo_hip_ctx* c, int b0, int nb, int max_rows, bool* mixed_out) {
+  const int M = c->rows.rows();
+  if (M + max_rows > c->Mmax) return XIVO_HIP_ERR_INVALID;
+  // Mixed stacking (round 3, default whenever the in-state rows were stacked in the compressed form only and nothing
+  // forces the dense pipeline): the OOS rows go to the dense buffer behind the in-state rows and the update keeps the
+  // sparse walk for the in-state rows - only the OOS block takes the MFMA products (update_sparse_range). Needs a
+  // 16-row-padded OOS block inside the allocation; otherwise (and with XIVO_HIP_FLAG_DENSE_H) every row
+  // becomes dense as before.
+  const bool mixed = !c->calib_on && !c->rows.dense_alive() && !c->rows.dense_from_compressed() && c->rows.oos_row0() < 0 && b0 == 0 &&
+                     !(c->flags & XIVO_HIP_FLAG_DENSE_H) && (M % 2 == 0) &&
+                     M + round_up16(max_rows + 16) <= c->Mpmax && c->Np <= 512;
+  *mixed_out = mixed;
+  if (!mixed) { int rcd = ensure_dense(c); if (rcd) return rcd; }
+  else {
+    // the OOS rows must start from zero: only the extrinsics and group columns are ever written there in this mode, so
+    // those are cleared (whole rows once, if anything else has used the dense buffer since it was allocated)
+    const int nz = std::min(round_up16(max_rows + 16), c->Mpmax - M);
+    if (!c->rows.dense_clean()) {
+      HIP_TRY((hipError_t)launch_zero_rows(c->H.p, c->H.stride, c->H.ld, 0, c->Mpmax, 0, c->Np, c->Bmax, c->stream));
+      c->rows.dense_zeroed();
+    } else {
+      HIP_TRY((hipError_t)launch_zero_rows(c->H.p, c->H.stride, c->H.ld, M, nz, 15, 21, nb, c->stream));
+      HIP_TRY((hipError_t)launch_zero_rows(c->H.p, c->H.stride, c->H.ld, M, nz, c->lay.group_begin, c->lay.group_begin + 6 * c->lay.n_groups, nb, c->stream));
+    }
+  }
+  return XIVO_HIP_OK;
+}
+
+int oos_rows_launch(xivo_hip_ctx* c, int nb, int n_oos, int M, double Roos, int whole, bool mixed) {
+  OosArgs a{};
+  a.feats = c->resident_oos.feats; a.n_oos = n_oos; a.poses = c->poses; a.groups = c->groups; a.lay = c->lay; a.cam = c->cam;
+  a.calib = c->calib_on ? c->calib : nullptr; a.cam_dim = c->calib_on ? c->cl.cam_dim : 0;
+  a.mb = meas_buffers(c); a.row0 = M; a.Mp = c->Mpmax; a.Np = c->Np; a.batch = nb; a.Roos = Roos; a.whole = whole;
+  if (mixed) a.mb.HT = nullptr;
+  a.rows_out = c->resident_oos.rows;
+  StageTimer st(c, ST_OTHER, 0.0, "oos_kernel");
+  HIP_TRY((hipError_t)launch_oos(a, c->stream));
+  return XIVO_HIP_OK;
+}
+
+}  // namespace xivo_hip::capi
+
 extern "C" {
 
 int xivo_hip_oos_project(xivo_hip_ctx* c, int b0, int nb, int n_oos, const xivo_oos_in* feats, double Roos,
@@ -38,28 +82,8 @@ int xivo_hip_oos_project_ex(xivo_hip_ctx* c, int b0, int nb, int n_oos, const xi
     if (rows > max_rows) max_rows = rows;
   }
   const int M = c->rows.rows();
-  if (M + max_rows > c->Mmax) return XIVO_HIP_ERR_INVALID;
-  // Mixed stacking (round 3, default whenever the in-state rows were stacked in the compressed form only and nothing
-  // forces the dense pipeline): the OOS rows go to the dense buffer behind the in-state rows and the update keeps the
-  // sparse walk for the in-state rows - only the OOS block takes the MFMA products (update_sparse_range). Needs a
-  // 16-row-padded OOS block inside the allocation; otherwise (and with XIVO_HIP_FLAG_DENSE_H) every row
-  // becomes dense as before.
-  const bool mixed = !c->calib_on && !c->rows.dense_alive() && !c->rows.dense_from_compressed() && c->rows.oos_row0() < 0 && b0 == 0 &&
-                     !(c->flags & XIVO_HIP_FLAG_DENSE_H) && (M % 2 == 0) &&
-                     M + round_up16(max_rows + 16) <= c->Mpmax && c->Np <= 512;
-  if (!mixed) { int rcd = ensure_dense(c); if (rcd) return rcd; }
-  else {
-    // the OOS rows must start from zero: only the extrinsics and group columns are ever written there in this mode, so
-    // those are cleared (whole rows once, if anything else has used the dense buffer since it was allocated)
-    const int nz = std::min(round_up16(max_rows + 16), c->Mpmax - M);
-    if (!c->rows.dense_clean()) {
-      HIP_TRY((hipError_t)launch_zero_rows(c->H.p, c->H.stride, c->H.ld, 0, c->Mpmax, 0, c->Np, c->Bmax, c->stream));
-      c->rows.dense_zeroed();
-    } else {
-      HIP_TRY((hipError_t)launch_zero_rows(c->H.p, c->H.stride, c->H.ld, M, nz, 15, 21, nb, c->stream));
-      HIP_TRY((hipError_t)launch_zero_rows(c->H.p, c->H.stride, c->H.ld, M, nz, c->lay.group_begin, c->lay.group_begin + 6 * c->lay.n_groups, nb, c->stream));
-    }
-  }
+  bool mixed = false;
+  if (int rc = oos_rows_begin(c, b0, nb, max_rows, &mixed)) return rc;
   if ((size_t)n_oos * nb > c->resident_oos.cap) {   // (a resident list - feats == NULL - fits by the check above)
     int rc = c->mem.grow(&c->resident_oos.feats, &c->resident_oos.cap, (size_t)n_oos * c->Bmax);
     if (rc) return rc;
@@ -69,16 +93,7 @@ int xivo_hip_oos_project_ex(xivo_hip_ctx* c, int b0, int nb, int n_oos, const xi
     HIP_TRY(hipMemcpyAsync(c->resident_oos.feats, feats, (size_t)nb * n_oos * sizeof(xivo_oos_in), hipMemcpyHostToDevice, c->stream));
     c->resident_oos.nb = nb; c->resident_oos.n = n_oos; c->resident_oos.whole = whole;
   }
-  OosArgs a{};
-  a.feats = c->resident_oos.feats; a.n_oos = n_oos; a.poses = c->poses; a.groups = c->groups; a.lay = c->lay; a.cam = c->cam;
-  a.calib = c->calib_on ? c->calib : nullptr; a.cam_dim = c->calib_on ? c->cl.cam_dim : 0;
-  a.mb = meas_buffers(c); a.row0 = M; a.Mp = c->Mpmax; a.Np = c->Np; a.batch = nb; a.Roos = Roos; a.whole = whole;
-  if (mixed) a.mb.HT = nullptr;
-  a.rows_out = c->resident_oos.rows;
-  {
-    StageTimer st(c, ST_OTHER, 0.0, "oos_kernel");
-    HIP_TRY((hipError_t)launch_oos(a, c->stream));
-  }
+  if (int rc = oos_rows_launch(c, nb, n_oos, M, Roos, whole, mixed)) return rc;
   if (rows_out) HIP_TRY(hipMemcpyAsync(rows_out, c->resident_oos.rows, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->dx_clear();

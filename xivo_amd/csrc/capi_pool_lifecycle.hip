@@ -53,6 +53,8 @@ int plife_begin_frame(xivo_hip_ctx* c, int B, int F, int strict) {
     StageTimer st(c, ST_OTHER, 0.0, "pool_life_begin_kernel");
     if (launch_pool_life_begin(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
   }
+  // use_oos: the frame's OOS list from the entries the tracker dropped, before the step frees them (capi_pool_oos.hip)
+  if (int rc = pool_oos_life_select(c, B)) return rc;
   // the step of xivo_hip_pool_step, on the pixels the begin kernel left and into device outputs
   PoolStepArgs p = pool_step_args(c, B, strict);
   p.xp = c->plife.xp; p.order = c->plife.order; p.n = c->plife.n; p.live = c->plife.live;
@@ -74,6 +76,7 @@ int plife_begin_frame(xivo_hip_ctx* c, int B, int F, int strict) {
 namespace xivo_hip::capi {
 void pool_life_release(xivo_hip_ctx* c) {
   if (!c->plife.configured()) return;
+  pool_oos_release(c);   // its rings follow this life cycle's books
   pcw_release(c);   // the producer writes into the track block: it goes with it
   c->mem.release(&c->plife.ent_id, &c->plife.ent_born, &c->plife.anc_used, &c->plife.anc_life, &c->plife.stats);
   c->mem.release(&c->plife.slot_track, &c->plife.ent_track, &c->plife.xp, &c->plife.order, &c->plife.n, &c->plife.live);
@@ -97,6 +100,7 @@ int xivo_hip_pool_life_config(xivo_hip_ctx* c, const xivo_pool_life_opts* o) {
     return rc;
   }
   if (c->plife.configured() || !c->pool.configured() || c->life.configured() || !c->have_layout || !c->poses) return XIVO_HIP_ERR_INVALID;
+  if (c->pool_oos.configured()) return XIVO_HIP_ERR_INVALID;   // (xivo_hip_pool_oos_config comes after: it sizes the rings by this)
   if (o->max_group_lifetime < 0 || !isfinite(o->initial_z) || !(o->initial_z > 0.0) || (o->adaptive_z && !c->pool.adapt_on))
     return XIVO_HIP_ERR_INVALID;
   for (int i = 0; i < 3; ++i) if (!isfinite(o->std_xyz[i])) return XIVO_HIP_ERR_INVALID;
@@ -195,6 +199,7 @@ int xivo_hip_pool_life_end(xivo_hip_ctx* c, int B) {
     StageTimer st(c, ST_OTHER, 0.0, "pool_life_end_kernel");
     if (launch_pool_life_end(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
   }
+  if (int rc = pool_oos_life_record(c, B, c->plife.frame)) return rc;   // use_oos: the frame's anchor observes the live entries
   if (c->pool.adapt_on) {   // AdaptInitialDepth (src/manager.cpp:131), after the new tracks took the old init_z; no copy out
     AdaptDepthArgs d{};
     d.feats = c->feats; d.F = c->F; d.Fmax = c->Fmax;

@@ -275,6 +275,24 @@ struct OosArgs {
 };
 int launch_oos(const OosArgs& a, hipStream_t s);
 
+// the fixed OOS block of the pool's MSCKF update (xivo_hip_pool_oos_project / _gate): the rows [row0, row0 + rows) of every filter
+// start as inn = 0, diagR = Roos (oos_kernel then overwrites the rows a feature fills)
+int launch_oos_block_init(const MeasBuffers& mb, int row0, int rows, double Roos, int batch, hipStream_t s);
+// chi-square gate of the projected rows, one workgroup per (filter, list position)
+struct OosGateArgs {
+  const xivo_oos_in* feats; int n_oos;          // [batch x n_oos], the list oos_kernel projected
+  xivo_layout lay;
+  double* H; long strideH; int ldh;             // dense rows (no H^T: the mixed stacking keeps none)
+  double* inn; long strideInn;
+  const double* P; long strideP; int ldp;
+  int row0, Mp; double Roos;
+  double chi2[32];
+  double* gamma;                                // [batch x n_oos]
+  long long* gated;                             // per filter counter, stride gated_stride (in long long)
+  int gated_stride, batch;
+};
+int launch_oos_gate(const OosGateArgs& a, hipStream_t s);
+
 // loop-closure rows: oos.cpp:92-145 + the stacking of update.cpp:183-196
 struct LcArgs {
   const xivo_lc_match* matches; int n;          // [batch x n]
@@ -354,6 +372,34 @@ struct PoolStepArgs {
   int* tri_good; int* tri_bad;                       // [batch]: accumulated while tri is on
 };
 int launch_pool_step(const PoolStepArgs& a, hipStream_t s);
+// The frame's OOS list from the dropped entries the host life cycle hands over (pool_oos_kernels.hip): one wave per filter
+struct PoolOosCollectArgs {
+  const xivo_subfilter_feat* pool; const PoolAnchor* anchors; int pool_max, anchor_max;
+  const xivo_pose_in* poses; const xivo_group_in* groups; int n_groups;
+  int invdepth; double min_depth, max_depth;
+  const xivo_pool_oos_cand* cands; const int* off;   // records of filter b: [off[b], off[b + 1])
+  int oos_max, max_obs, min_obs;
+  xivo_oos_in* list;                                 // [batch][oos_max]
+  xivo_pool_oos_stats* stats;                        // [batch]
+  int batch;
+};
+int launch_pool_oos_collect(const PoolOosCollectArgs& a, hipStream_t s);
+// The same list made in the device pool life cycle (select: between its begin kernel and the step) and the observation rings it
+// reads (record: behind its end kernel). Rings per filter: hist_cnt [pool_max], hist_anchor / hist_born [pool_max][max_obs],
+// hist_xp [pool_max][max_obs][2]; anc_born [anchor_max]
+struct PoolOosLifeArgs {
+  const xivo_subfilter_feat* pool; const PoolAnchor* anchors; int pool_max, anchor_max;
+  const xivo_pose_in* poses; const xivo_group_in* groups; int n_groups;
+  int invdepth; double min_depth, max_depth;
+  const long long* ent_id; const int* ent_born; const int* anc_used; const int* anc_life;   // the device life cycle's pool book
+  const double* xp;                                  // [batch][pool_max][2] the step's pixels (NaN: dropped)
+  int* anc_born; int* hist_cnt; int* hist_anchor; int* hist_born; double* hist_xp;
+  int oos_max, max_obs, min_obs, frame;
+  xivo_oos_in* list; xivo_pool_oos_stats* stats;
+  int batch;
+};
+int launch_pool_oos_select(const PoolOosLifeArgs& a, hipStream_t s);
+int launch_pool_oos_record(const PoolOosLifeArgs& a, hipStream_t s);
 // Feature::Triangulate's triangulators on host-array problems (xivo_hip_triangulate)
 int launch_triangulate(const xivo_tri_in* in, xivo_tri_out* out, int n, const xivo_triangulate_opts& o, hipStream_t s);
 // AdaptInitialDepth (xivo_hip_pool_adapt_depth): one workgroup per filter

@@ -802,6 +802,142 @@ __global__ __launch_bounds__(64) void oos_kernel(OosArgs a) {
   }
 }
 
+// The fixed OOS block of the pool's MSCKF update before oos_kernel fills it: inn = 0, diagR = Roos over rows [row0, row0 + rows)
+// of every filter (H arrives zero over the columns OOS rows ever touch: xivo_hip_pool_oos_project clears them)
+__global__ void oos_block_init_kernel(MeasBuffers mb, int row0, int rows, double Roos, int batch) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)batch * rows) return;
+  const int filt = (int)(t / rows), r = row0 + (int)(t % rows);
+  mb.inn[(long)filt * mb.strideInn + r] = 0.0;
+  mb.diagR[(long)filt * mb.strideR + r] = Roos;
+}
+
+// Chi-square gate of one OOS feature's projected rows, one wave64 per (filter, list position): gamma = r^T S_o^-1 r with
+// S_o = H_o P H_o^T + Roos I over the feature's rr = 2k - 3 rows. H_o is non-zero only under Wbc / Tbc (15..20) and the k
+// observing groups' 6-column blocks: those nc = 6 + 6k columns of the rows and that nc x nc sub-block of P are all that is read.
+//   T = H_o P_sub   lane c owns column c of T: it walks column cols[c] of P once (nc loads) against the LDS copy of H_o
+//   S = T H_o^T     lower triangle, one element per lane and pass, in LDS (at most 29 x 29)
+//   Cholesky        right-looking in LDS by the one wave, then the forward solve on lane 0 (rr <= 29)
+// A feature seen twice from one group has that block's columns once (the later copy is skipped).
+// One workgroup is one wave and the 54 KB of LDS leave one of them per SIMD: fine for batch x oos_max small blocks of a few
+// microseconds; the forward solve runs on lane 0 (at most 29 steps) and the S pass leaves lanes idle when rr^2 is no multiple of 64.
+constexpr int OOS_G_R = 2 * XIVO_OOS_MAX_OBS - 3;    // 29 rows
+constexpr int OOS_G_C = 6 + 6 * XIVO_OOS_MAX_OBS;    // 102 columns
+
+__global__ __launch_bounds__(64) void oos_gate_kernel(OosGateArgs a) {
+  const int filt = blockIdx.y, o = blockIdx.x, lane = threadIdx.x;
+  const xivo_oos_in& ft = a.feats[(long)filt * a.n_oos + o];
+  const int k = ft.n_obs;
+  double* gamma_out = a.gamma + (long)filt * a.n_oos + o;
+  if (k < 2 || k > XIVO_OOS_MAX_OBS) { if (lane == 0) *gamma_out = 0.0; return; }   // (block-uniform)
+  __shared__ double sH[OOS_G_R][OOS_G_C + 1];
+  __shared__ double sT[OOS_G_R][OOS_G_C + 1];
+  __shared__ double sS[OOS_G_R][OOS_G_R + 1];
+  __shared__ double sr[OOS_G_R];
+  __shared__ int sCol[OOS_G_C];
+  __shared__ int sBad;
+  __shared__ double sGamma;
+  const int rr = 2 * k - 3, nc = 6 + 6 * k;
+  int row0 = a.row0;                                   // as oos_kernel places the features: behind those before it
+  for (int q = 0; q < o; ++q) {
+    const int kq = a.feats[(long)filt * a.n_oos + q].n_obs;
+    row0 += kq >= 2 ? 2 * kq - 3 : 0;
+  }
+  if (row0 + rr > a.Mp) { if (lane == 0) *gamma_out = 0.0; return; }
+  double* H = a.H + (long)filt * a.strideH;
+  double* inn = a.inn + (long)filt * a.strideInn;
+  const double* P = a.P + (long)filt * a.strideP;
+  for (int c = lane; c < nc; c += 64) {
+    int col;
+    if (c < 6) col = 15 + c;
+    else {
+      const int ob = (c - 6) / 6, g = ft.group_sind[ob];
+      col = a.lay.group_begin + 6 * g + (c - 6) % 6;
+      if (g < 0 || g >= a.lay.n_groups) col = -1;
+      for (int q = 0; q < ob; ++q) if (ft.group_sind[q] == g) col = -1;
+    }
+    sCol[c] = col;
+  }
+  if (lane == 0) sBad = 0;
+  if (lane < rr) sr[lane] = inn[row0 + lane];
+  __syncthreads();
+  for (int e = lane; e < rr * nc; e += 64) {
+    const int i = e % rr, c = e / rr;                  // (consecutive lanes read consecutive rows of a column)
+    sH[i][c] = sCol[c] >= 0 ? H[row0 + i + (long)sCol[c] * a.ldh] : 0.0;
+  }
+  __syncthreads();
+  for (int c = lane; c < nc; c += 64) {
+    double acc[OOS_G_R];
+#pragma unroll
+    for (int i = 0; i < OOS_G_R; ++i) acc[i] = 0.0;
+    if (sCol[c] >= 0) {
+      const double* Pc = P + (long)sCol[c] * a.ldp;
+      for (int d = 0; d < nc; ++d) {
+        if (sCol[d] < 0) continue;
+        const double p = Pc[sCol[d]];
+#pragma unroll
+        for (int i = 0; i < OOS_G_R; ++i) if (i < rr) acc[i] += sH[i][d] * p;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < OOS_G_R; ++i) if (i < rr) sT[i][c] = acc[i];
+  }
+  __syncthreads();
+  for (int e = lane; e < rr * rr; e += 64) {
+    const int i = e / rr, j = e % rr;
+    if (j > i) continue;
+    double s = 0.0;
+    for (int c = 0; c < nc; ++c) s += sT[i][c] * sH[j][c];
+    sS[i][j] = s + (i == j ? a.Roos : 0.0);
+  }
+  __syncthreads();
+  for (int j = 0; j < rr; ++j) {
+    const double d = sS[j][j];                         // (every lane reads the same pivot)
+    if (!(d > 0.0)) { if (lane == 0) sBad = 1; break; }
+    const double l = sqrt(d);
+    __syncthreads();
+    if (lane == 0) sS[j][j] = l;
+    for (int i = j + 1 + lane; i < rr; i += 64) sS[i][j] /= l;
+    __syncthreads();
+    const int m = rr - j - 1;
+    for (int e = lane; e < m * m; e += 64) {
+      const int i = j + 1 + e / m, c = j + 1 + e % m;
+      if (c <= i) sS[i][c] -= sS[i][j] * sS[c][j];
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  const bool bad = sBad != 0;
+  if (lane == 0) {                                     // y = L^-1 r in place, gamma = y^T y (rr <= 29 steps)
+    double g = -1.0;
+    if (!bad) {
+      g = 0.0;
+      for (int i = 0; i < rr; ++i) {
+        double v = sr[i];
+        for (int c = 0; c < i; ++c) v -= sS[i][c] * sr[c];
+        v /= sS[i][i];
+        sr[i] = v;
+        g += v * v;
+      }
+    }
+    sGamma = g;
+  }
+  __syncthreads();
+  const double gamma = sGamma;
+  const double th = a.chi2[rr];
+  const bool out = bad || (th > 0.0 && gamma > th);
+  if (lane == 0) {
+    *gamma_out = gamma;
+    if (out) atomicAdd((unsigned long long*)(a.gated + (long)filt * a.gated_stride), 1ull);
+  }
+  if (!out) return;
+  for (int e = lane; e < rr * nc; e += 64) {
+    const int i = e % rr, c = e / rr;
+    if (sCol[c] >= 0) H[row0 + i + (long)sCol[c] * a.ldh] = 0.0;
+  }
+  if (lane < rr) inn[row0 + lane] = 0.0;
+}
+
 // ---------------------------------------------------------------- loop-closure rows
 // Feature::ComputeLCJacobian (oos.cpp:92-145) as Estimator::CloseLoopInternal drives it (update.cpp:183-196): one thread per
 // (filter, match). The OLD in-state feature's world position Xs = Feature::Xs(gbc) (feature.cpp:107-118: its own state and
@@ -1283,6 +1419,17 @@ int launch_stack(const StackArgs& a, hipStream_t s) {
 int launch_oos(const OosArgs& a, hipStream_t s) {
   if (a.n_oos <= 0) return 0;
   hipLaunchKernelGGL(oos_kernel, dim3(a.n_oos, a.batch), dim3(64), 0, s, a);
+  CHECK_LAUNCH();
+}
+int launch_oos_block_init(const MeasBuffers& mb, int row0, int rows, double Roos, int batch, hipStream_t s) {
+  const long tot = (long)batch * rows;
+  if (tot <= 0) return 0;
+  hipLaunchKernelGGL(oos_block_init_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, mb, row0, rows, Roos, batch);
+  CHECK_LAUNCH();
+}
+int launch_oos_gate(const OosGateArgs& a, hipStream_t s) {
+  if (a.n_oos <= 0 || a.batch <= 0) return 0;
+  hipLaunchKernelGGL(oos_gate_kernel, dim3(a.n_oos, a.batch), dim3(64), 0, s, a);
   CHECK_LAUNCH();
 }
 int launch_lc_rows(const LcArgs& a, hipStream_t s) {

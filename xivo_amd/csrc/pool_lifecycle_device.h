@@ -161,4 +161,65 @@ XIVO_LIFE_HD bool plife_expire_anchor(int* anc_used, const int* anc_life, const 
   return true;
 }
 
+// ---- OOS / MSCKF use of entries that leave the pool (SequenceConfig.use_oos; _frame_subfilter at "--- OOS selection" and
+// "--- OOS history"). Two more arrays of the pool book and the observation ring of every entry:
+//   anc_born[anchor_max]           the frame counter at which the anchor was created (tells a re-used anchor index apart)
+//   hist_cnt[pool_max]             observations appended since the entry was taken (not capped: slot = count % max_obs)
+//   hist_anchor / hist_born [pool_max][max_obs]   the observing anchor and its creation frame; the pixels sit beside them
+// An observation is appended at the end of a frame that created an anchor, for every live entry that had a track in that frame
+// (the reference's graph edge "feature seen from the group created this frame", src/manager.cpp:121-126). A history reference
+// does not keep an anchor alive.
+
+// what the walk over the dropped entries decides for one of them
+enum { PLIFE_OOS_NONE = 0, PLIFE_OOS_USED = 1, PLIFE_OOS_SHORT = 2, PLIFE_OOS_SURPLUS = 3 };
+
+// a new entry starts with an empty ring (with plife_take_entry)
+XIVO_LIFE_HD void plife_hist_reset(int* hist_cnt, int e) { hist_cnt[e] = 0; }
+// append (anchor a, created in `frame`) to entry e's ring; returns the ring slot the caller stores the pixel in. The oldest
+// observation is overwritten once the ring is full.
+XIVO_LIFE_HD int plife_hist_append(int* hist_cnt, int* hist_anchor, int* hist_born, int e, int max_obs, int a, int frame) {
+  const int s = hist_cnt[e] % max_obs;
+  hist_anchor[e * max_obs + s] = a; hist_born[e * max_obs + s] = frame;
+  hist_cnt[e] += 1;
+  return s;
+}
+// observations the ring holds, and the slot of the q-th oldest of them
+XIVO_LIFE_HD int plife_hist_len(int cnt, int max_obs) { return cnt < max_obs ? cnt : max_obs; }
+XIVO_LIFE_HD int plife_hist_slot(int cnt, int max_obs, int q) { return cnt <= max_obs ? q : (cnt + q) % max_obs; }
+// an observation counts when its anchor still exists with the same creation frame and is linked to a group slot now; returns
+// that slot, -1: the observation does not count
+XIVO_LIFE_HD int plife_obs_group(int a, int born, const int* anc_used, const int* anc_born, const int* anc_link, int anchor_max,
+                                 int n_groups) {
+  if (a < 0 || a >= anchor_max || !anc_used[a] || anc_born[a] != born) return -1;
+  const int g = anc_link[a];
+  return g >= 0 && g < n_groups ? g : -1;
+}
+// the valid observations of entry e, oldest first: slot_out / group_out [max_obs]; returns their number
+XIVO_LIFE_HD int plife_valid_obs(const int* hist_cnt, const int* hist_anchor, const int* hist_born, int e, int max_obs,
+                                 const int* anc_used, const int* anc_born, const int* anc_link, int anchor_max, int n_groups,
+                                 int* slot_out, int* group_out) {
+  const int len = plife_hist_len(hist_cnt[e], max_obs);
+  int k = 0;
+  for (int q = 0; q < len; ++q) {
+    const int s = plife_hist_slot(hist_cnt[e], max_obs, q);
+    const int g = plife_obs_group(hist_anchor[e * max_obs + s], hist_born[e * max_obs + s], anc_used, anc_born, anc_link,
+                                  anchor_max, n_groups);
+    if (g >= 0) { slot_out[k] = s; group_out[k] = g; ++k; }
+  }
+  return k;
+}
+// a live entry without a track this frame is looked at, in ascending entry index, before the pool step frees anything
+XIVO_LIFE_HD bool plife_oos_dropped(const long long* ent_id, int e, int track) { return ent_id[e] >= 0 && track < 0; }
+// ... and used when it is READY, has at least min_obs valid observations, its depth lies inside (min_depth, max_depth) - the
+// caller's comparison - and fewer than oos_max entries of the filter were used before it. READY with fewer observations counts
+// as short, eligible beyond oos_max as surplus.
+XIVO_LIFE_HD int plife_oos_decide(bool ready, bool depth_ok, int k, int min_obs, int n_used, int oos_max) {
+  if (!ready) return PLIFE_OOS_NONE;
+  if (k < min_obs) return PLIFE_OOS_SHORT;
+  if (!depth_ok) return PLIFE_OOS_NONE;
+  return n_used < oos_max ? PLIFE_OOS_USED : PLIFE_OOS_SURPLUS;
+}
+// rows of the fixed block every frame appends behind the in-state rows: oos_max features of at most 2 max_obs - 3 rows
+XIVO_LIFE_HD int plife_oos_rows(int oos_max, int max_obs) { return oos_max * (2 * max_obs - 3); }
+
 }  // namespace xivo_hip

@@ -47,7 +47,7 @@ void BatchEstimator::Check(int rc, const char* what) {
 BatchEstimator::BatchEstimator(const BatchConfig& cfg, int B, int device, const xivo_pose_in* poses0, const double* P0)
     : cfg_(cfg), B_(B) {
   const int N = cfg.N(), F = cfg.n_features;
-  Check(xivo_hip_create(&ctx_, device, N, 2 * F, B, (cfg.fix_group_block ? XIVO_HIP_FLAG_FIX_GROUP_BLOCK : 0u) |
+  Check(xivo_hip_create(&ctx_, device, N, 2 * F + (cfg.extra_rows > 0 ? cfg.extra_rows : 0), B, (cfg.fix_group_block ? XIVO_HIP_FLAG_FIX_GROUP_BLOCK : 0u) |
                                                      (cfg.use_invdepth ? XIVO_HIP_FLAG_INVDEPTH : 0u)), "create");
   xivo_layout lay{N, 23, cfg.n_groups, 23 + 6 * cfg.n_groups, F};
   Check(xivo_hip_set_layout(ctx_, &lay, &cfg.cam), "set_layout");
@@ -131,7 +131,17 @@ void BatchEstimator::DiscardEmptyGroups(int b, std::vector<xivo_edit_op>& ops) {
 void BatchEstimator::RunUpdate() {
   const int F = cfg_.n_features;
   const double R = cfg_.visual_meas_std * cfg_.visual_meas_std;
-  if (cfg_.use_1pt_RANSAC) {
+  if (oos_) {
+    // jacobians -> MH gate -> [RANSAC] -> stack -> the OOS block of the frame's list -> its chi-square gate -> update
+    Check(xivo_hip_jacobians_instate(ctx_, B_), "jacobians_instate");
+    Check(xivo_hip_mh_gate(ctx_, B_, R, cfg_.MH_thresh, cfg_.MH_adjust_factor, cfg_.use_MH_gating ? cfg_.min_inliers : (1 << 30), nullptr, nullptr), "mh_gate");
+    if (cfg_.use_1pt_RANSAC)
+      Check(xivo_hip_one_point_ransac(ctx_, B_, R, cfg_.ransac_thresh, cfg_.ransac_Chi2, nullptr, nullptr, nullptr, nullptr, nullptr), "one_point_ransac");
+    Check(xivo_hip_stack(ctx_, B_, R), "stack");
+    Check(xivo_hip_pool_oos_project(ctx_, B_), "pool_oos_project");
+    Check(xivo_hip_pool_oos_gate(ctx_, B_), "pool_oos_gate");
+    Check(xivo_hip_update_joseph(ctx_, B_), "update_joseph");
+  } else if (cfg_.use_1pt_RANSAC) {
     // Estimator::OutlierRejection with use_1pt_RANSAC (src/manager.cpp:629-650): MH gating, OnePointRANSAC on its inliers,
     // the update on what it keeps. (No gauge group / previous-frame group list in this simplified life cycle.)
     Check(xivo_hip_jacobians_instate(ctx_, B_), "jacobians_instate");
@@ -159,7 +169,15 @@ void BatchEstimator::RunUpdate() {
   Check(xivo_hip_absorb_error(ctx_, B_), "absorb_error");
 }
 
+void BatchEstimator::EnableOosUpdates(const xivo_pool_oos_opts& opts) {
+  if (!device_pool_life_) throw std::runtime_error("EnableOosUpdates needs EnableDevicePoolLifecycle first (the history rings are the device life cycle's)");
+  if (vision_counter_ > 0 || innov_log_) throw std::runtime_error("EnableOosUpdates comes before the first frame and excludes the innovation log");
+  Check(xivo_hip_pool_oos_config(ctx_, &opts), "pool_oos_config");
+  oos_ = opts.oos_max > 0;
+}
+
 void BatchEstimator::EnableInnovationLog(int T_max) {
+  if (oos_ && T_max > 0) throw std::runtime_error("the innovation log excludes EnableOosUpdates (its dof would count the block's empty rows)");
   const xivo_innov_opts o{T_max};
   Check(xivo_hip_innov_config(ctx_, &o), "innov_config");
   innov_log_ = T_max > 0;
@@ -676,7 +694,18 @@ struct xivo_batch_cfg {   // flat mirror of xivo::hip::BatchConfig
   double ransac_thresh, ransac_Chi2;
 };
 
+int xivo_batch_create_rows(const xivo_batch_cfg* c, int B, int device, const xivo_pose_in* poses0, const double* P0, int extra_rows,
+                           void** out);
 int xivo_batch_create(const xivo_batch_cfg* c, int B, int device, const xivo_pose_in* poses0, const double* P0, void** out) {
+  return xivo_batch_create_rows(c, B, device, poses0, P0, 0, out);
+}
+int xivo_batch_enable_oos(void* h, const xivo_pool_oos_opts* o) {
+  if (!h || !o) return -1;
+  try { static_cast<xivo::hip::BatchEstimator*>(h)->EnableOosUpdates(*o); return 0; } catch (const std::exception&) { return -1; }
+}
+// xivo_batch_create with room for extra_rows measurement rows behind the in-state ones (EnableOosUpdates)
+int xivo_batch_create_rows(const xivo_batch_cfg* c, int B, int device, const xivo_pose_in* poses0, const double* P0, int extra_rows,
+                           void** out) {
   try {
     xivo::hip::BatchConfig cfg;
     cfg.n_groups = c->n_groups; cfg.n_features = c->n_features; cfg.cam = c->cam;
@@ -684,7 +713,7 @@ int xivo_batch_create(const xivo_batch_cfg* c, int B, int device, const xivo_pos
     cfg.min_inliers = c->min_inliers; cfg.min_new_features = c->min_new_features; cfg.fix_group_block = c->fix_group_block;
     cfg.use_MH_gating = c->disable_MH_gating ? 0 : 1;
     cfg.use_1pt_RANSAC = c->use_1pt_RANSAC; cfg.ransac_thresh = c->ransac_thresh; cfg.ransac_Chi2 = c->ransac_Chi2;
-    cfg.use_invdepth = c->use_invdepth;
+    cfg.use_invdepth = c->use_invdepth; cfg.extra_rows = extra_rows;
     cfg.initial_std_x = c->initial_std_x; cfg.initial_std_y = c->initial_std_y; cfg.initial_std_z = c->initial_std_z;
     cfg.min_depth = c->min_depth; cfg.max_depth = c->max_depth; cfg.prop = c->prop;
     *out = new xivo::hip::BatchEstimator(cfg, B, device, poses0, P0);

@@ -41,6 +41,7 @@ struct BatchConfig {
   double min_depth = 0.05, max_depth = 10.0;
   int min_new_features = 3;                         // open a new group only when this many feature slots are free
   int fix_group_block = 1;                          // XIVO_HIP_FLAG_FIX_GROUP_BLOCK (see xivo_amd/sequence.py)
+  int extra_rows = 0;                               // measurement rows the context holds beyond the 2 F in-state ones (EnableOosUpdates: its block + padding)
   int use_invdepth = 0;                             // the reference's USE_INVDEPTH build: features are (X/Z, Y/Z, 1/Z); initial_std_z is then an inverse-depth std
   xivo_prop_opts prop{};                            // Qimu, Qmodel, gravity, integrator, step size
   int N() const { return 23 + 6 * n_groups + 3 * n_features; }
@@ -105,6 +106,11 @@ class BatchEstimator {
   // given; book(b) and the counters then read the device, init_z() stays as configured (xivo_hip_pool_get_init_z reads the
   // resident one). Throws if EnableSubfilter has not run or the immediate device life cycle is on.
   void EnableDevicePoolLifecycle(int tracks_max);
+  // MSCKF update from pool entries whose track ends (xivo_hip_pool_oos_config, a thin pass-through): after
+  // EnableDevicePoolLifecycle and before the first frame, on an estimator created with BatchConfig::extra_rows >= the block's
+  // oos_max * (2 max_obs - 3) rows rounded up with its 16 rows of padding. The frame's update then appends and gates the block
+  // (xivo_hip_pool_oos_project / _gate); the selection and the history are the device life cycle's. Not with EnableInnovationLog.
+  void EnableOosUpdates(const xivo_pool_oos_opts& opts);
   bool device_pool_lifecycle() const { return device_pool_life_; }
   // the "immediate" life cycle on the device (xivo_hip_life_*): the slot book moves to the context, VisualMeasPointCloud hands
   // the frame's tracks down (at most tracks_max per filter) and makes no get_gate / get_status call unless mask_out is given;
@@ -191,6 +197,7 @@ class BatchEstimator {
   long n_updates_ = 0, n_rejected_ = 0, n_not_spd_ = 0;
   std::vector<int> status_;
   bool innov_log_ = false;
+  bool oos_ = false;
   double t_visual_ = 0.0;                 // stamp of the camera frame being processed
   double host_s_ = 0.0;
   std::vector<unsigned char> mask_;

@@ -142,6 +142,21 @@ pool_life_stats_dtype = np.dtype([(k, "i8") for k in ("updates", "rejected", "dr
                                                        "anchors_freed", "admit_steps")])
 assert pool_life_opts_dtype.itemsize == 48 and pool_life_stats_dtype.itemsize == 96
 POOL_LIFE_MAX_ANCHORS = 256
+# MSCKF update from dropped pool entries (include/xivo_hip.h): xivo_pool_oos_opts, xivo_pool_oos_cand, xivo_pool_oos_stats
+pool_oos_opts_dtype = np.dtype([("struct_size", "i4"), ("oos_max", "i4"), ("max_obs", "i4"), ("min_obs", "i4"), ("Roos", "f8"),
+                                ("chi2", "f8", 32)])
+pool_oos_cand_dtype = np.dtype([("b", "i4"), ("entry", "i4"), ("n_obs", "i4"), ("reserved", "i4"),
+                                ("group_sind", "i4", OOS_MAX_OBS), ("xp", "f8", (OOS_MAX_OBS, 2))])
+pool_oos_stats_dtype = np.dtype([(k, "i8") for k in ("oos_used", "oos_gated", "oos_surplus", "oos_short")])
+assert pool_oos_opts_dtype.itemsize == 280 and pool_oos_cand_dtype.itemsize == 336 and pool_oos_stats_dtype.itemsize == 32
+# chi-square 0.95 quantiles for 1 .. 29 degrees of freedom (index = dof; 0 and 30, 31 unused): the gate of an OOS feature's
+# 2k - 3 projected rows (tests/test_pool_oos_cpu.py holds the table against scipy.stats.chi2.ppf)
+CHI2_95 = (0.0, 3.841458820694124, 5.991464547107979, 7.814727903251179, 9.487729036781154, 11.070497693516351,
+           12.591587243743977, 14.067140449340169, 15.50731305586545, 16.918977604620448, 18.307038053275146,
+           19.67513757268249, 21.02606981748307, 22.362032494826934, 23.684791304840576, 24.995790139728616,
+           26.29622760486423, 27.587111638275324, 28.869299430392623, 30.14352720564616, 31.410432844230918,
+           32.670573340917315, 33.92443847144381, 35.17246162690806, 36.41502850180731, 37.65248413348277,
+           38.885138659830055, 40.11327206941361, 41.33713815142739, 42.55696780429269, 0.0, 0.0)
 # point-cloud world (include/xivo_hip.h): xivo_pcw_opts
 pcw_opts_dtype = np.dtype([("struct_size", "i4"), ("npts", "i4"), ("fx", "f8"), ("fy", "f8"), ("cx", "f8"), ("cy", "f8"),
                            ("imw", "f8"), ("imh", "f8")])
@@ -286,6 +301,14 @@ _SIGS = {
     "xivo_hip_pcw_camera": [C.c_void_p, C.c_void_p, C.c_double],
     "xivo_hip_pool_life_end": [C.c_void_p, C.c_int],
     "xivo_hip_pool_life_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_pool_oos_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_pool_oos_rows": [C.c_void_p],
+    "xivo_hip_pool_oos_collect": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_pool_oos_project": [C.c_void_p, C.c_int],
+    "xivo_hip_pool_oos_gate": [C.c_void_p, C.c_int],
+    "xivo_hip_pool_oos_get": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "xivo_hip_pool_oos_get_rings": [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5,
+    "xivo_hip_pool_oos_get_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_pcw_config": [C.c_void_p, C.c_void_p],
     "xivo_hip_pcw_set_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_pcw_get_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
@@ -1296,6 +1319,60 @@ class Context:
         nb = self.batch - b0 if nb is None else int(nb)
         out = np.zeros(nb, dtype=pool_life_stats_dtype)
         self._check(self.lib.xivo_hip_pool_life_stats(self.h, int(b0), nb, _ptr(out)))
+        return out
+
+    def pool_oos_config(self, oos_max, max_obs=6, min_obs=5, Roos=3.5 ** 2, chi2=CHI2_95):
+        """MSCKF update from dropped pool entries (xivo_hip_pool_oos_config; after pool_config): oos_max features of at most
+        max_obs observations per filter and frame, used from min_obs valid observations on; chi2[dof] gates a feature's
+        2k - 3 rows (0: no gate; None: none at all). oos_max = 0 switches it off. -> the rows every frame appends"""
+        o = np.zeros(1, dtype=pool_oos_opts_dtype)
+        o["struct_size"] = pool_oos_opts_dtype.itemsize
+        o["oos_max"], o["max_obs"], o["min_obs"], o["Roos"] = oos_max, max_obs, min_obs, Roos
+        if chi2 is not None:
+            o["chi2"][0, :len(chi2)] = chi2
+        self._check(self.lib.xivo_hip_pool_oos_config(self.h, _ptr(o)))
+        self.oos_max, self.oos_max_obs = int(oos_max), int(max_obs)
+        return int(self.lib.xivo_hip_pool_oos_rows(self.h))
+
+    def pool_oos_collect(self, cands, B=None):
+        """the frame's OOS list from the dropped entries cands [n] pool_oos_cand_dtype, ordered by (b, entry), before the frame's
+        pool step"""
+        cands = np.ascontiguousarray(cands, dtype=pool_oos_cand_dtype)
+        self._check(self.lib.xivo_hip_pool_oos_collect(self.h, self.batch if B is None else int(B), len(cands),
+                                                       _ptr(cands) if len(cands) else None))
+
+    def pool_oos_project(self, B=None):
+        """after stack: the list's rows into the fixed block behind the in-state rows (asynchronous)"""
+        self._check(self.lib.xivo_hip_pool_oos_project(self.h, self.batch if B is None else int(B)))
+
+    def pool_oos_gate(self, B=None):
+        """after pool_oos_project: the chi-square gate of every feature's rows (asynchronous)"""
+        self._check(self.lib.xivo_hip_pool_oos_gate(self.h, self.batch if B is None else int(B)))
+
+    def pool_oos_get(self, b0=0, nb=None):
+        """-> (list [nb, oos_max] oos_dtype, gamma [nb, oos_max]); one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        lst = np.zeros((nb, self.oos_max), dtype=oos_dtype); gamma = np.zeros((nb, self.oos_max))
+        self._check(self.lib.xivo_hip_pool_oos_get(self.h, int(b0), nb, _ptr(lst), _ptr(gamma)))
+        return lst, gamma
+
+    def pool_oos_get_rings(self, b0=0, nb=None):
+        """device pool life cycle: dict(anc_born [nb, anchor_max], hist_cnt [nb, pool_max], hist_anchor / hist_born
+        [nb, pool_max, max_obs], hist_xp [nb, pool_max, max_obs, 2]); one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        pm, am, mo = self.pool_max, self.anchor_max, self.oos_max_obs
+        r = dict(anc_born=np.zeros((nb, am), dtype=np.int32), hist_cnt=np.zeros((nb, pm), dtype=np.int32),
+                 hist_anchor=np.zeros((nb, pm, mo), dtype=np.int32), hist_born=np.zeros((nb, pm, mo), dtype=np.int32),
+                 hist_xp=np.zeros((nb, pm, mo, 2)))
+        self._check(self.lib.xivo_hip_pool_oos_get_rings(self.h, int(b0), nb, _ptr(r["anc_born"]), _ptr(r["hist_cnt"]),
+                                                         _ptr(r["hist_anchor"]), _ptr(r["hist_born"]), _ptr(r["hist_xp"])))
+        return r
+
+    def pool_oos_stats(self, b0=0, nb=None):
+        """-> [nb] pool_oos_stats_dtype: the per-filter counters; one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        out = np.zeros(nb, dtype=pool_oos_stats_dtype)
+        self._check(self.lib.xivo_hip_pool_oos_get_stats(self.h, int(b0), nb, _ptr(out)))
         return out
 
     def propagate_cov(self, Phi, Pmm, b0=0):

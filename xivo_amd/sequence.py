@@ -46,7 +46,15 @@ What is mirrored from the reference and what is simplified:
     feeder's records and the ground-truth camera and body poses on the device, xivo_hip_propagate_resident consumes the records
     there (`SequenceRunner.frame_resident`): a frame takes no host data and no host wait. Its IMU noise is the counter-based
     stream pcw.trajsim_normals restates.
-  * NOT IN EITHER: RefineDepth (`use_depth_opt`), gauge XY features and SwitchRefGroup, ownership transfer, OOS updates.
+  * tracks that end outside the state (`SequenceConfig.use_oos`, needs feature_init="subfilter"; both pool life cycles): the
+    step the reference only announces (use_OOS parses, then "MSCKF not implemented", src/estimator.cpp:113-122). Every pool
+    entry keeps a ring of its last `oos_max_obs` observations (anchor, pixel), one per frame that created an anchor; an entry
+    whose track ends while it is READY with at least `oos_min_observations` observations from anchors whose groups are in the
+    state constrains those groups once, through the null-space rows (xivo_hip_pool_oos_*): at most `oos_max` per filter and
+    frame, chi-square gated, in a fixed block of oos_max * (2 * oos_max_obs - 3) rows behind the in-state rows. The rules are
+    pool_lifecycle_device.h's plife_hist_* / plife_oos_*; the device decides with the entry's status and depth. With
+    pool_lifecycle="device" the rings are resident too and xivo_hip_pool_life_begin / _end select and record themselves.
+  * NOT IN EITHER: RefineDepth (`use_depth_opt`), gauge XY features and SwitchRefGroup, ownership transfer.
 The numerics of every step are the device path; this file holds no arithmetic of the filter itself.
 """
 import numpy as np
@@ -185,6 +193,12 @@ class SequenceConfig:
         # records uploaded by xivo_hip_propagate) or "device" (xivo_hip_trajsim_frame / xivo_hip_propagate_resident; needs
         # track_source = "device": a frame then takes no host data at all)
         self.imu_source = "host"
+        # MSCKF update from pool entries whose track ends (cfg/pcw.json: use_OOS, OOS_update_min_observations, oos_meas_std);
+        # oos_max features per filter and frame of at most oos_max_obs observations each
+        self.use_oos = False
+        self.oos_min_observations = 5
+        self.oos_meas_std = 3.5
+        self.oos_max, self.oos_max_obs = 4, 6
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option " + k)
@@ -193,6 +207,16 @@ class SequenceConfig:
     @property
     def N(self):
         return 23 + 6 * self.n_groups + 3 * self.n_features
+
+    def oos_rows(self):
+        """rows the OOS block adds to every frame's update (0: use_oos off)"""
+        return self.oos_max * (2 * self.oos_max_obs - 3) if getattr(self, "use_oos", False) else 0
+
+    def M_max(self):
+        """rows a context of this configuration stages at most: the in-state rows, and with use_oos the fixed OOS block plus the
+        16 rows the mixed stacking pads it with (and the round-up of the block itself)"""
+        r = self.oos_rows()
+        return 2 * self.n_features + (((r + 16 + 15) // 16) * 16 if r else 0)
 
     def P_init(self):
         """Estimator ctor, src/estimator.cpp:257-304: P_ = identity (kFullSize - unused group / feature slots keep a
@@ -335,7 +359,7 @@ class HipBackend:
         if getattr(cfg, "use_invdepth", False):
             flags |= L.FLAG_INVDEPTH
         check_lifecycle(cfg)
-        self.ctx = L.Context(cfg.N, 2 * cfg.n_features, B, device=device, flags=flags)
+        self.ctx = L.Context(cfg.N, cfg.M_max(), B, device=device, flags=flags)
         self.ctx.set_layout(cfg.N, 23, cfg.n_groups, 23 + 6 * cfg.n_groups, cfg.n_features, cfg.cam)
         self.ctx.upload_P(P0)
         groups = np.zeros((B, cfg.n_groups), dtype=L.group_dtype)
@@ -354,6 +378,25 @@ class HipBackend:
             self.enable_device_pool_lifecycle()
         if cfg.track_source == "device":
             self.enable_device_world()
+        self.oos_on = False
+        if getattr(cfg, "use_oos", False):
+            self.enable_oos()
+
+    def enable_oos(self):
+        """allocate the OOS list, gate distances and counters of the MSCKF update from dropped pool entries
+        (xivo_hip_pool_oos_config), after enable_pool"""
+        c = self.cfg
+        if not self.pool_on:
+            raise ValueError("use_oos needs the feature pool (feature_init='subfilter')")
+        self.ctx.pool_oos_config(c.oos_max, max_obs=c.oos_max_obs, min_obs=c.oos_min_observations, Roos=float(c.oos_meas_std) ** 2)
+        self.oos_on = True
+
+    def pool_oos_collect(self, cands):
+        self.ctx.pool_oos_collect(cands, B=self.B)
+
+    def oos_stats(self):
+        """[B] pool_oos_stats_dtype: oos_used / oos_gated / oos_surplus / oos_short per filter; one synchronising read"""
+        return self.ctx.pool_oos_stats(0, self.B)
 
     def enable_device_lifecycle(self):
         """allocate the device-resident slot book and track staging (xivo_hip_life_config). The new feature's variances are
@@ -507,7 +550,17 @@ class HipBackend:
         mask and the status stay on the device, nothing synchronises, None is returned"""
         c = self.cfg
         R = c.visual_meas_std ** 2
-        if c.use_1pt_RANSAC:
+        if self.oos_on:
+            # jacobians -> MH gate -> [RANSAC] -> stack -> the OOS block of the frame's list -> its chi-square gate -> update
+            self.ctx.jacobians_instate()
+            self.ctx.mh_gate(R, c.MH_thresh, c.MH_adjust_factor, c.min_inliers if c.use_MH_gating else 1 << 30, want=False)
+            if c.use_1pt_RANSAC:
+                self.ctx.one_point_ransac(R, c.ransac_thresh, c.ransac_Chi2, want=False)
+            self.ctx.stack(R)
+            self.ctx.pool_oos_project(self.B)
+            self.ctx.pool_oos_gate(self.B)
+            self.ctx.update_joseph()
+        elif c.use_1pt_RANSAC:
             # Estimator::OutlierRejection with use_1pt_RANSAC (src/manager.cpp:629-650): MH gating, then OnePointRANSAC on
             # its inliers; the update runs on what RANSAC keeps. (No gauge group / previous-frame group list in this
             # simplified life cycle: temporary reference group every time, every slot absorbed.)
@@ -552,7 +605,10 @@ class HipBackend:
 
     def enable_innovation_log(self, T_max):
         """device log of T_max frames of every update's NIS (xivo_hip_innov_config); update() then records between the update
-        and absorb_error, stamped with frame_ts (ns, set by the driver before the frame); 0 releases it"""
+        and absorb_error, stamped with frame_ts (ns, set by the driver before the frame); 0 releases it. Refused with use_oos:
+        the log counts every staged row, so its dof would include the empty rows of the OOS block"""
+        if self.oos_on and T_max > 0:
+            raise ValueError("innovation_log with use_oos is not supported: the log's dof would count the empty rows of the OOS block")
         self.ctx.innov_config(T_max)
         self.innov_on = T_max > 0
 
@@ -609,6 +665,26 @@ class _PoolBook:
         self.anc_used = [False] * anchor_max
         self.anc_life = [0] * anchor_max         # Group::lifetime (frames since creation)
         self.anc_link = [-1] * anchor_max        # group slot the anchor's group occupies (-1: not in the state)
+        # use_oos (pool_lifecycle_device.h, plife_hist_*): the anchors' creation frames and every entry's observation ring
+        self.anc_born = [0] * anchor_max
+        self.hist_cnt = [0] * pool_max           # observations appended since the entry was taken (slot = count % max_obs)
+        self.hist = [[] for _ in range(pool_max)]   # ring slots: (anchor, its creation frame, pixel)
+
+    def hist_append(self, e, max_obs, a, frame, xp):
+        """plife_hist_append"""
+        if len(self.hist[e]) < max_obs:
+            self.hist[e] = self.hist[e] + [None] * (max_obs - len(self.hist[e]))
+        self.hist[e][self.hist_cnt[e] % max_obs] = (a, frame, (float(xp[0]), float(xp[1])))
+        self.hist_cnt[e] += 1
+
+    def valid_obs(self, e, max_obs, n_groups):
+        """plife_valid_obs: (group slot, pixel) of the observations that count, oldest first"""
+        cnt, out = self.hist_cnt[e], []
+        for q in range(min(cnt, max_obs)):
+            a, born, xp = self.hist[e][q if cnt <= max_obs else (cnt + q) % max_obs]
+            if 0 <= a < len(self.anc_used) and self.anc_used[a] and self.anc_born[a] == born and 0 <= self.anc_link[a] < n_groups:
+                out.append((self.anc_link[a], xp))
+        return out
 
     def free_entry(self, e):
         del self.id2ent[self.ent_id[e]]
@@ -643,6 +719,11 @@ def check_lifecycle(cfg):
         raise ValueError("imu_source must be 'host' or 'device'")
     if imu == "device" and src != "device":
         raise ValueError("imu_source='device' needs track_source='device'")
+    if getattr(cfg, "use_oos", False):
+        if cfg.feature_init != "subfilter":
+            raise ValueError("use_oos needs feature_init='subfilter' (feature_init=%r)" % (cfg.feature_init,))
+        if not 2 <= cfg.oos_max_obs <= L.OOS_MAX_OBS or not 2 <= cfg.oos_min_observations <= cfg.oos_max_obs or not 0 < cfg.oos_max <= 64:
+            raise ValueError("use_oos needs 2 <= oos_min_observations <= oos_max_obs <= %d and 0 < oos_max <= 64" % L.OOS_MAX_OBS)
     if src == "device":
         if cfg.lifecycle != "device" and plc != "device":
             raise ValueError("track_source='device' needs lifecycle='device' or pool_lifecycle='device'")
@@ -918,6 +999,7 @@ class SequenceRunner:
     def _frame_subfilter(self, imu, tracks):
         """one camera frame in the order of Estimator::UpdateStep (src/manager.cpp:18-130) with the feature pool"""
         cfg, be, B = self.cfg, self.be, self.B
+        use_oos = bool(getattr(cfg, "use_oos", False))
         if self.pools is None:
             self.pools = [_PoolBook(cfg.pool_max, cfg.anchor_max) for _ in range(B)]
         self.vision_counter += 1
@@ -937,6 +1019,23 @@ class SequenceRunner:
                     ops.append(_op(b, L.EDIT_REMOVE_FEATURE, j))
                     bk.drop_feature(j)
             self._discard_empty_groups(b, ops)
+        # --- OOS selection (use_oos): every live entry without a track, ascending, with its valid observations - after the groups
+        # above left, before anything is freed. The device decides with the entry's status and depth (plife_oos_decide)
+        if use_oos:
+            cands = []
+            for b in range(B):
+                pb = self.pools[b]
+                for e, fid in enumerate(pb.ent_id):
+                    if fid >= 0 and fid not in pos[b]:
+                        obs = pb.valid_obs(e, cfg.oos_max_obs, cfg.n_groups)
+                        r = np.zeros((), dtype=L.pool_oos_cand_dtype)
+                        r["b"], r["entry"], r["n_obs"] = b, e, len(obs)
+                        for q, (g, px) in enumerate(obs):
+                            r["group_sind"][q] = g; r["xp"][q] = px
+                        cands.append(r)
+            be.pool_oos_collect(np.array(cands, dtype=L.pool_oos_cand_dtype))
+        for b in range(B):
+            pb, meas = self.pools[b], tracks[b][1]
             for e, fid in enumerate(pb.ent_id):
                 if fid < 0:
                     continue
@@ -1013,6 +1112,7 @@ class SequenceRunner:
             a = afree[0]
             slots[b] = a
             pb.anc_used[a] = True; pb.anc_life[a] = 0; pb.anc_link[a] = -1
+            pb.anc_born[a] = self.vision_counter
             self.n_pool_dropped += max(0, len(new) - len(efree))
             for e, k in zip(efree, new):
                 r = np.zeros((), dtype=L.pool_new_dtype)
@@ -1020,6 +1120,12 @@ class SequenceRunner:
                 recs.append(r)
                 pb.ent_id[e] = int(ids[k]); pb.ent_anchor[e] = a; pb.ent_born[e] = self.vision_counter
                 pb.id2ent[int(ids[k])] = e
+                pb.hist_cnt[e] = 0; pb.hist[e] = []          # plife_hist_reset
+            # --- OOS history (use_oos): the frame's anchor observes every live entry that had a track, the new ones included
+            if use_oos:
+                for e, fid in enumerate(pb.ent_id):
+                    if fid >= 0:
+                        pb.hist_append(e, cfg.oos_max_obs, a, self.vision_counter, meas[pos[b][fid], :2])
         if (slots >= 0).any():
             be.pool_anchor(slots)
         if recs:
