@@ -1240,6 +1240,70 @@ int xivo_hip_trajsim_get_gt(xivo_hip_ctx* ctx, int b0, int nb, int t0, int nt, d
 int xivo_hip_trajsim_count(xivo_hip_ctx* ctx);   /* frames in the log; 0 when not configured */
 int xivo_hip_trajsim_reset(xivo_hip_ctx* ctx);   /* empties the log (and forgets the last frame's records and poses) */
 
+/* ---- loop closure on the device: the resident landmark map ------------------------------------------------------------
+ * What Estimator::CloseLoop needs around the rows of xivo_hip_close_loop_stack: a per-filter map of world points that
+ * outlives the features' stay in the state (DiscardFeatures -> Mapper::AddFeature, src/mapper.cpp:158-222), the matcher
+ * against it and the verification before the update (Mapper::DetectLoopClosures, src/mapper.cpp:335-418), all resident.
+ * What stands in for what: `key` is the caller's stand-in for the descriptor word - two observations with the same
+ * non-negative key are the mapper's descriptor match at distance 0 (a point-cloud world supplies its world-point index, a
+ * front end its own match id; a negative key matches nothing); a chi-square gate of every match on the filter's own
+ * covariance stands in for pnp_ransac's inlier test. The stored point is treated as exact, as the reference treats it. No
+ * merging (merge_features = false, mapper.cpp:189-191: the first estimate of a point is kept), no eviction, no pose graph.
+ * Off until configured; refused on a context with online calibration. */
+#define XIVO_LCMAP_MAX_ENTRIES 4096
+#define XIVO_LCMAP_MAX_MATCHES 64
+typedef struct {
+  int struct_size;        /* sizeof(xivo_lcmap_opts) */
+  int map_max;            /* entries per filter, <= XIVO_LCMAP_MAX_ENTRIES; 0 releases the map and zeroes the counters */
+  int lc_max;             /* matches per filter and frame, <= XIVO_LCMAP_MAX_MATCHES; 2 lc_max rows are staged */
+  int min_matches;        /* a filter closes with at least this many kept matches (>= 1; the reference's default is 5) */
+  double Rlc;             /* variance of the loop-closure pixel (> 0) */
+  double chi2;            /* gate of one match (2 degrees of freedom); 0: no gate */
+  double max_depth_var;   /* an added feature whose P(foff + 2, foff + 2) is above this is dropped; 0: no test */
+} xivo_lcmap_opts;
+typedef struct { long long key; double Xs[3]; } xivo_lcmap_entry;
+typedef struct { int b, feat; long long key; } xivo_lcmap_add_rec;                     /* ordered by b */
+typedef struct { int b, group_sind; long long key; double xp[2]; } xivo_lcmap_query;   /* ordered by b */
+typedef struct {
+  int entry;        /* position in the filter's map; -1: this list position is empty */
+  int group_sind;   /* the query's */
+  double xp[2];     /* the query's */
+  double gamma;     /* r^T (H P H^T + Rlc I)^-1 r of the pair; -1 where a pivot was not positive */
+  int kept, reserved;
+} xivo_lcmap_match;
+typedef struct {
+  long long added, dup, full, poor, skipped;   /* add records by outcome */
+  long long queries, matched, surplus, gated;  /* queries seen; list positions filled; matches beyond lc_max; gated out */
+  long long short_frames, closed_frames;       /* frames with a match and fewer than min_matches kept; frames that closed */
+} xivo_lcmap_stats;
+/* Refusals: XIVO_HIP_ERR_UNSUPPORTED for map_max > XIVO_LCMAP_MAX_ENTRIES, lc_max > XIVO_LCMAP_MAX_MATCHES or a context with
+ * online calibration; XIVO_HIP_ERR_INVALID for 2 lc_max > M_max, lc_max < 1, Rlc <= 0, min_matches < 1, negative or non-finite
+ * bounds, no layout. Every other entry point of this section returns XIVO_HIP_ERR_INVALID before a configuration. */
+int xivo_hip_lcmap_config(xivo_hip_ctx* ctx, const xivo_lcmap_opts* opts);
+/* The in-state features that leave (call it before the edit that removes them): n records of filters [0, B), ordered by b. One
+ * workgroup per filter takes its records in order: feat not in the state (sind < 0, ref_sind out of range) or key < 0 -
+ * skipped; depth variance above max_depth_var - poor; key stored already, by an earlier call or an earlier record - dup, the
+ * stored entry stays; map full - full; else the entry {key, Xs = Feature::Xs(gbc)} goes to position count. Enqueues and
+ * returns without waiting (the records are copied first). */
+int xivo_hip_lcmap_add(xivo_hip_ctx* ctx, int B, int n, const xivo_lcmap_add_rec* recs);
+/* DetectLoopClosures + CloseLoopInternal up to the update, for filters [0, B). Match: a query whose key is in its filter's map
+ * matches that entry; the first lc_max matching queries in query order fill the match list, the rest are surplus. Rows: every
+ * match gets the row pair of ComputeLCJacobian with the entry's Xs as the old feature's world point, observed by group
+ * group_sind or (group_sind = -1) by the body pose itself, whose blocks go to columns 0..5. Verify: gamma of every pair from
+ * the sub-block of P under its 12 columns; gamma > chi2 or a non-positive pivot gates it out. A filter with fewer than
+ * min_matches kept matches does not close: all its pairs are neutral (H = 0, inn = 0, diagR = 1); else only the gated and
+ * empty ones are. The 2 lc_max rows of every filter replace the staged measurement as those of xivo_hip_close_loop_stack do;
+ * xivo_hip_update_joseph + xivo_hip_absorb_error complete the closure. n_closing_out == NULL: always stages, never waits.
+ * Else: waits, returns the number of closing filters, and stages nothing when that is 0 (the staged rows stay as they were). */
+int xivo_hip_lcmap_close(xivo_hip_ctx* ctx, int B, int n, const xivo_lcmap_query* queries, int* n_closing_out);
+/* whole maps of filters [b0, b0 + nb): entries host [nb][map_max], count host [nb] (set: 0 <= count <= map_max, the keys of a
+ * filter non-negative and distinct) - a surveyed map, or one carried over from another run */
+int xivo_hip_lcmap_set(xivo_hip_ctx* ctx, int b0, int nb, const xivo_lcmap_entry* entries, const int* count);
+int xivo_hip_lcmap_get(xivo_hip_ctx* ctx, int b0, int nb, xivo_lcmap_entry* entries, int* count);
+/* the match lists of the last close call: host [nb][lc_max]; kept and gamma are valid where entry >= 0 */
+int xivo_hip_lcmap_get_matches(xivo_hip_ctx* ctx, int b0, int nb, xivo_lcmap_match* matches);
+int xivo_hip_lcmap_get_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_lcmap_stats* stats);
+
 /* ---- covariance propagation tail (src/rk4.cpp:92-102, src/estimator.cpp:590) */
 /* P_mm <- Pmm_new ; P_ms <- Phi P_ms ; P_sm <- P_sm Phi^T. Phi and Pmm_new
  * are nm x nm (nm = kMotionSize: 23, or up to 40 for the online-calibration builds), one pair per filter. */

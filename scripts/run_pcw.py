@@ -103,6 +103,20 @@ def main():
     ap.add_argument("-oos-min-obs", dest="oos_min_obs", type=int, default=5,
                     help="-use-oos: observations an entry needs (OOS_update_min_observations)")
     ap.add_argument("-seed", type=int, default=0, help="-vectorized: the seed of the worlds and trajectories")
+    d = sequence.SequenceConfig()
+    ap.add_argument("-loop-closure", dest="loop_closure", action="store_true",
+                    help="loop closure on the device-resident landmark map (SequenceConfig.loop_closure): the world-point index of "
+                         "every track is its key, features that leave the state go to the map, returning points close the loop. "
+                         "-host python with the host life cycles (the C++ host side and the device life cycles carry no keys); "
+                         "the report gains the summed map counters (lcmap)")
+    ap.add_argument("-lc-map-max", dest="lc_map_max", type=int, default=d.lc_map_max, help="-loop-closure: map entries per sequence")
+    ap.add_argument("-lc-max", dest="lc_max", type=int, default=d.lc_max, help="-loop-closure: matches per sequence and frame")
+    ap.add_argument("-lc-min-matches", dest="lc_min_matches", type=int, default=d.lc_min_matches,
+                    help="-loop-closure: kept matches a sequence needs to close")
+    ap.add_argument("-lc-meas-std", dest="lc_meas_std", type=float, default=d.lc_meas_std, help="-loop-closure: loop_closure_meas_std (px)")
+    ap.add_argument("-lc-chi2", dest="lc_chi2", type=float, default=d.lc_chi2, help="-loop-closure: gate of one match (0: none)")
+    ap.add_argument("-lc-max-depth-var", dest="lc_max_depth_var", type=float, default=d.lc_max_depth_var,
+                    help="-loop-closure: a feature whose depth variance is above this when it leaves is not stored (0: no test)")
     a = ap.parse_args()
     # (a sequence never brings more tracks than its world has points)
     life = dict(lifecycle=a.lifecycle, tracks_max=min(a.npts, sequence.L.LIFE_MAX_TRACKS))
@@ -127,6 +141,18 @@ def main():
         if a.innov_log:
             ap.error("-use-oos and -innov-log exclude each other (the log's dof would count the empty rows of the OOS block)")
         life.update(feature_init=a.feature_init, pool_lifecycle=a.pool_lifecycle, use_oos=True, oos_min_observations=a.oos_min_obs)
+        try:
+            sequence.check_lifecycle(sequence.SequenceConfig(**life))
+        except ValueError as e:
+            ap.error(str(e))
+    if a.loop_closure:
+        if a.vectorized or a.host != "python":
+            ap.error("-loop-closure runs with -host python (the C++ host side has no loop closure)")
+        if a.innov_log:
+            ap.error("-loop-closure and -innov-log exclude each other (the log holds one update per frame)")
+        life.update(feature_init=a.feature_init, pool_lifecycle=a.pool_lifecycle, loop_closure=True, lc_map_max=a.lc_map_max,
+                    lc_max=a.lc_max, lc_min_matches=a.lc_min_matches, lc_meas_std=a.lc_meas_std, lc_chi2=a.lc_chi2,
+                    lc_max_depth_var=a.lc_max_depth_var)
         try:
             sequence.check_lifecycle(sequence.SequenceConfig(**life))
         except ValueError as e:
@@ -218,10 +244,14 @@ def main():
         r_ = out["runner"]
 
         oos_st = out["backend"].oos_stats() if a.use_oos else None
+        lc_st = out.get("lcmap_stats")
 
         class _R:      # (read before the context goes: the device life cycle keeps the counters there)
             n_updates, n_rejected = r_.n_updates, r_.n_rejected
             oos = {k: int(oos_st[k].sum()) for k in oos_st.dtype.names} if oos_st is not None else {}
+            if lc_st is not None:     # the map counters summed over the sequences, and in how many a loop was closed at all
+                oos = dict(oos, **{"lcmap_" + k: int(lc_st[k].sum()) for k in lc_st.dtype.names},
+                           lcmap_sequences_with_closed=int((lc_st["closed_frames"] > 0).sum()))
         out["runner"] = _R
         out["backend"].close()
     wall = time.perf_counter() - t0
@@ -249,6 +279,7 @@ def main():
         "N": cfg.N, "max_features": cfg.n_features, "integration": a.integration_method, "host": a.host,
         "lifecycle": a.lifecycle, "tracks": a.tracks, "feature_init": a.feature_init, "pool_lifecycle": a.pool_lifecycle,
         "cam_model": a.cam_model,
+        "loop_closure": bool(a.loop_closure),
         "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
         **_consistency(out),
         "updates": n_upd, "mh_rejected": n_rej, **oos,
@@ -256,6 +287,7 @@ def main():
         "phase_s": {k: round(v, 4) for k, v in sorted(timers.items())},
         "device_frames_per_s": B * frames / dev if dev > 0 else None,
         "ms_per_frame_per_batch": {k: round(1e3 * timers.get(k, 0.0) / frames, 3) for k in ("propagate", "edit", "update")},
+        "ms_per_frame_of_all_sequences": round(1e3 * dev / frames, 3) if frames else None,
     }))
 
 

@@ -16,6 +16,7 @@
 //                       block that both device life cycles use
 //   capi_pool_lifecycle.hip  device pool life cycle ("subfilter" mode): the pool book, the two frame calls, counters
 //   capi_pcw.hip        point-cloud world: the resident worlds, the per-frame track producer, read-back
+//   capi_lcmap.hip      loop closure: the resident landmark map, its add / close calls, load / read-out, counters
 //   capi_trajsim.hip    trajectory producer: the simulated IMU records and ground-truth poses of a frame, the ground-truth log
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
@@ -285,6 +286,18 @@ struct InnovLog {
   bool configured() const { return log.configured(); }
 };
 
+// resident landmark map (xivo_hip_lcmap_*, capi_lcmap.hip): entries [Bmax][map_max], count [Bmax], the counters [Bmax], the
+// last close call's match lists [Bmax][lc_max] and closing flags [Bmax]; io: the device block a call's records / queries and
+// offsets are uploaded to, up: its page-locked staging (both only ever grow, up_cap bytes each)
+struct LcMap {
+  xivo_lcmap_opts opts{};
+  xivo_lcmap_entry* entries = nullptr; int* count = nullptr; xivo_lcmap_stats* stats = nullptr;
+  xivo_lcmap_match* matches = nullptr; int* closing = nullptr;
+  char* io = nullptr; size_t io_cap = 0;
+  PinnedUpload up; size_t up_cap = 0;
+  bool configured() const { return entries != nullptr; }
+};
+
 }  // namespace xivo_hip::capi
 
 struct xivo_hip_ctx {
@@ -365,6 +378,7 @@ struct xivo_hip_ctx {
   xivo_hip::capi::TrajLog traj;
   xivo_hip::capi::MapLog map;
   xivo_hip::capi::InnovLog innov;
+  xivo_hip::capi::LcMap lcmap;
   // "a device life cycle exists" (whichever: the book and the track block are its)
   bool life_cycle_configured() const { return life.configured() || plife.configured(); }
 };

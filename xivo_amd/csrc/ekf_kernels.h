@@ -304,6 +304,39 @@ struct LcArgs {
 };
 int launch_lc_rows(const LcArgs& a, hipStream_t s);
 
+// the resident landmark map (xivo_hip_lcmap_*, lcmap_kernels.hip). What both kernels take of it: entries [batch][map_max],
+// count [batch], the counters [batch]
+struct LcMapBuffers {
+  xivo_lcmap_entry* entries; int* count; xivo_lcmap_stats* stats; int map_max;
+};
+// add: the records of filter b are recs[off[b], off[b + 1])
+struct LcMapAddArgs {
+  LcMapBuffers map;
+  const xivo_lcmap_add_rec* recs; const int* off;
+  const xivo_pose_in* poses; const xivo_group_in* groups; const xivo_feat_in* feats; int Fmax, F;
+  xivo_layout lay; int invdepth;
+  const double* P; long strideP; int ldp;
+  double max_depth_var; int batch;
+};
+int launch_lcmap_add(const LcMapAddArgs& a, hipStream_t s);
+// close: match, rows, verify. The queries of filter b are queries[off[b], off[b + 1]); H [batch] 2 lc_max x N zero-filled
+struct LcMapCloseArgs {
+  LcMapBuffers map;
+  const xivo_lcmap_query* queries; const int* off;
+  const xivo_pose_in* poses; const xivo_group_in* groups;
+  xivo_layout lay; xivo_cam cam;
+  // always {-1, -1, 0, 0} (no online calibration here), but a run-time value: lc_row_pair is then compiled as in lc_rows_kernel,
+  // intrinsics branch included, and rounds as it does there (a product shared with that branch is not fused into an fma)
+  xivo_calib_layout cl;
+  const double* P; long strideP; int ldp;
+  double* H; long strideH; int ldh;
+  double* inn; double* diagR; long strideV;
+  xivo_lcmap_match* matches;   // [batch][lc_max]
+  int* closing;                // [batch] 1: the filter closes
+  int lc_max, min_matches; double Rlc, chi2; int batch;
+};
+int launch_lcmap_close(const LcMapCloseArgs& a, hipStream_t s);
+
 // measurement compression of the appended OOS rows (estimator.h:399-402, helpers.cpp:77-101)
 struct OosCompressArgs {
   xivo_layout lay; MeasBuffers mb;

@@ -1,6 +1,7 @@
 // Device helpers of the per-feature 3x3 chains, shared by glevel_kernels.hip, pool_kernels.hip, state_kernels.hip and
 // propagate_kernels.hip: 3x3 / 2x3 products, SO3::hat, pixel projection, the per-filter camera of the online-calibration
-// builds and Feature::Xc / Feature::z; SO3 exp / log (state_kernels.hip: AbsorbError, traj_kernels.hip: the pose error).
+// builds and Feature::Xc / Feature::z; SO3 exp / log (state_kernels.hip: AbsorbError, traj_kernels.hip: the pose error); the
+// loop-closure world point and row pair (glevel_kernels.hip, lcmap_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "camera_device.h"
@@ -170,5 +171,62 @@ __device__ __forceinline__ V3 feature_unproject(const double* x, int invdepth, M
   return Xc;
 }
 __device__ __forceinline__ double feature_depth(double x2, int invdepth) { return invdepth ? 1.0 / x2 : exp(x2); }
+
+// ---------------------------------------------------------------- loop closure (Feature::ComputeLCJacobian, oos.cpp:92-145)
+// Xs(gbc) = ref_->gsb() * gbc * Xc (feature.cpp:107-118) of in-state feature ft anchored in group gref: what lc_rows_kernel
+// re-observes and what the landmark map stores (lcmap_add_kernel) - one evaluation order for both
+__device__ __forceinline__ V3 lc_world_point(const xivo_pose_in& pose, const xivo_feat_in& ft, const xivo_group_in& gref, int invdepth) {
+  const M3 Rbc = m3_from_colmajor(pose.Rbc), Rsbr = m3_from_colmajor(gref.Rsb);
+  M3 dXc_dx;
+  const V3 Xc = feature_unproject(ft.x, invdepth, dXc_dx);
+  V3 Xbr = m3_mulv(Rbc, Xc);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) Xbr.v[i] += pose.Tbc[i];
+  V3 Xs = m3_mulv(Rsbr, Xbr);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) Xs.v[i] += gref.Tsb[i];
+  return Xs;
+}
+// The row pair r0, r0 + 1 of a zeroed H for world point Xs re-observed at pixel obs_xp from the pose (gRsb, gTsb) whose six
+// error-state columns (W, T) start at goff - a group slot, or the body pose itself at 0: the two share the retraction -:
+// d xp / d (W, T, Wbc, Tbc) [+ the intrinsics block of :141-144 when cam_dim > 0], inn = obs_xp - xp, diagR = Rlc. No block for
+// the point: as coded. The one place this arithmetic lives (lc_rows_kernel, lcmap_close_kernel).
+__device__ __forceinline__ void lc_row_pair(const V3& Xs, const double* gRsb, const double* gTsb, int goff, const xivo_pose_in& pose,
+                                            const xivo_cam& cam, int cam_begin, int cam_dim, const double* obs_xp, double Rlc,
+                                            double* H, int ldh, int r0, double* inn, double* dR) {
+  const M3 Rbc = m3_from_colmajor(pose.Rbc), Rsb = m3_from_colmajor(gRsb);
+  const M3 Rsb_t = m3_t(Rsb), Rbc_t = m3_t(Rbc);
+  V3 d;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) d.v[i] = Xs.v[i] - gTsb[i];
+  const V3 Xb = m3_mulv(Rsb_t, d);                              // :107
+#pragma unroll
+  for (int i = 0; i < 3; ++i) d.v[i] = Xb.v[i] - pose.Tbc[i];
+  const V3 Xcn = m3_mulv(Rbc_t, d);                             // :113
+  double xp[2], dxp_dXcn[2][3];
+  project_pixel(cam, Xcn, xp, dxp_dXcn);                        // :123-133
+  const M3 dXcn_dTsb = m3_mul(Rbc_t, m3_neg(Rsb_t));            // :120  dXcn_dXb * dXb_dTsb
+  const M3 dXcn_dWsb = m3_mul(Rbc_t, hat(Xb));                  // :121  dXcn_dXb * dXb_dWsb
+  double blk[2][3];
+  auto put = [&](int col) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) H[r0 + i + (long)(col + j) * ldh] = blk[i][j];
+  };
+  m23_mul(dxp_dXcn, dXcn_dWsb, blk); put(goff);                 // :136
+  m23_mul(dxp_dXcn, dXcn_dTsb, blk); put(goff + 3);             // :137
+  m23_mul(dxp_dXcn, hat(Xcn), blk); put(15);                    // :138  Index::Wbc
+  m23_mul(dxp_dXcn, m3_neg(Rbc_t), blk); put(18);               // :139  Index::Tbc
+  if (cam_dim > 0) {                                            // :141-144
+    double xq[2], Jq[2][2], jacc[2][9];
+    camera_project_jacc(cam, Xcn.v[0] / Xcn.v[2], Xcn.v[1] / Xcn.v[2], xq, Jq, jacc);
+#pragma unroll
+    for (int j = 0; j < 9; ++j)                                 // (unrolled and predicated: jacc stays in registers)
+      if (j < cam_dim) { H[r0 + (long)(cam_begin + j) * ldh] = jacc[0][j]; H[r0 + 1 + (long)(cam_begin + j) * ldh] = jacc[1][j]; }
+  }
+  inn[r0] = obs_xp[0] - xp[0]; inn[r0 + 1] = obs_xp[1] - xp[1];   // :146
+  dR[r0] = Rlc; dR[r0 + 1] = Rlc;                                 // update.cpp:193
+}
 
 }  // namespace xivo_hip

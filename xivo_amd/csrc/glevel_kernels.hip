@@ -963,47 +963,9 @@ __global__ void lc_rows_kernel(LcArgs a) {
   const xivo_group_in& gref = a.groups[(long)filt * a.lay.n_groups + ft.ref_sind];
   const xivo_group_in& g = a.groups[(long)filt * a.lay.n_groups + mt.group_sind];
   const xivo_cam cam = filter_cam(a.cam, a.calib, a.cl.cam_dim, filt);
-  const M3 Rbc = m3_from_colmajor(pose.Rbc), Rsbr = m3_from_colmajor(gref.Rsb), Rsb = m3_from_colmajor(g.Rsb);
-  const M3 Rsb_t = m3_t(Rsb), Rbc_t = m3_t(Rbc);
-  // Xs(gbc) = ref_->gsb() * gbc * Xc (feature.cpp:112-113)
-  M3 dXc_dx;
-  const V3 Xc = feature_unproject(ft.x, a.invdepth, dXc_dx);
-  V3 Xbr = m3_mulv(Rbc, Xc);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) Xbr.v[i] += pose.Tbc[i];
-  V3 Xs = m3_mulv(Rsbr, Xbr);
-  V3 d;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { Xs.v[i] += gref.Tsb[i]; d.v[i] = Xs.v[i] - g.Tsb[i]; }
-  const V3 Xb = m3_mulv(Rsb_t, d);                              // :107
-#pragma unroll
-  for (int i = 0; i < 3; ++i) d.v[i] = Xb.v[i] - pose.Tbc[i];
-  const V3 Xcn = m3_mulv(Rbc_t, d);                             // :113
-  double xp[2], dxp_dXcn[2][3];
-  project_pixel(cam, Xcn, xp, dxp_dXcn);                        // :123-133
-  const M3 dXcn_dTsb = m3_mul(Rbc_t, m3_neg(Rsb_t));            // :120  dXcn_dXb * dXb_dTsb
-  const M3 dXcn_dWsb = m3_mul(Rbc_t, hat(Xb));                  // :121  dXcn_dXb * dXb_dWsb
-  double blk[2][3];
-  const int goff = a.lay.group_begin + 6 * mt.group_sind;
-  auto put = [&](int col) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) H[r0 + i + (long)(col + j) * a.ldh] = blk[i][j];
-  };
-  m23_mul(dxp_dXcn, dXcn_dWsb, blk); put(goff);                 // :136
-  m23_mul(dxp_dXcn, dXcn_dTsb, blk); put(goff + 3);             // :137
-  m23_mul(dxp_dXcn, hat(Xcn), blk); put(15);                    // :138  Index::Wbc
-  m23_mul(dxp_dXcn, m3_neg(Rbc_t), blk); put(18);               // :139  Index::Tbc
-  if (a.cl.cam_dim > 0) {                                       // :141-144
-    double xq[2], Jq[2][2], jacc[2][9];
-    camera_project_jacc(cam, Xcn.v[0] / Xcn.v[2], Xcn.v[1] / Xcn.v[2], xq, Jq, jacc);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      for (int j = 0; j < a.cl.cam_dim && j < 9; ++j) H[r0 + i + (long)(a.cl.cam_begin + j) * a.ldh] = jacc[i][j];
-  }
-  inn[r0] = mt.xp[0] - xp[0]; inn[r0 + 1] = mt.xp[1] - xp[1];   // :146
-  dR[r0] = a.Rlc; dR[r0 + 1] = a.Rlc;                           // update.cpp:193
+  const V3 Xs = lc_world_point(pose, ft, gref, a.invdepth);
+  lc_row_pair(Xs, g.Rsb, g.Tsb, a.lay.group_begin + 6 * mt.group_sind, pose, cam, a.cl.cam_begin, a.cl.cam_dim, mt.xp, a.Rlc,
+              H, a.ldh, r0, inn, dR);
 }
 
 // ---------------------------------------------------------------- measurement compression of the OOS rows

@@ -1,0 +1,58 @@
+// The integer rules of the resident landmark map (xivo_hip_lcmap_*, include/xivo_hip.h): what becomes of an add record, which
+// place a matching query takes in a filter's match list, whether a filter closes. Plain functions of integers, shared by the
+// kernels (lcmap_kernels.hip) and by a host program that holds them against a restatement (tests/lcmap_driver.cpp): this file
+// includes no project header and takes HIP's only under __HIPCC__.
+#pragma once
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#define LCMAP_HD __host__ __device__ __forceinline__
+#else
+#define LCMAP_HD inline
+#endif
+
+namespace xivo_hip {
+
+// ---- add (DiscardFeatures -> Mapper::AddFeature, src/mapper.cpp:158-222 with merge_features = false, :189-191)
+enum { LCMAP_ADD_ACCEPT = 0, LCMAP_ADD_SKIPPED = 1, LCMAP_ADD_POOR = 2, LCMAP_ADD_DUP = 3, LCMAP_ADD_FULL = 4 };
+
+// One record, the tests in this order: not in the state (or a negative key, which no query can ever match) - skipped; depth
+// variance above the bound - poor; key stored already (in the map or by an earlier record of the call) - dup, the first
+// estimate stays; no room - full, nothing is evicted; else it takes position `count`.
+LCMAP_HD int lcmap_add_decide(int in_state, int poor, int dup, int count, int map_max) {
+  if (!in_state) return LCMAP_ADD_SKIPPED;
+  if (poor) return LCMAP_ADD_POOR;
+  if (dup) return LCMAP_ADD_DUP;
+  if (count >= map_max) return LCMAP_ADD_FULL;
+  return LCMAP_ADD_ACCEPT;
+}
+// the depth-variance test: var = P(foff + 2, foff + 2); max_depth_var = 0 means no test, equality keeps the record
+LCMAP_HD int lcmap_poor(double var, double max_depth_var) { return max_depth_var > 0.0 && var > max_depth_var; }
+
+// the position of `key` among keys[0, count), -1: none (a negative key matches nothing)
+LCMAP_HD int lcmap_find(const long long* keys, long stride, int count, long long key) {
+  if (key < 0) return -1;
+  for (int i = 0; i < count; ++i)
+    if (keys[(long)i * stride] == key) return i;
+  return -1;
+}
+
+// ---- match: the matching query that has `rank` matching queries before it in query order takes list position `rank` while
+// there is room, the others are surplus (-1)
+LCMAP_HD int lcmap_match_slot(int rank, int lc_max) { return rank < lc_max ? rank : -1; }
+
+// ---- verify (stands in for pnp_ransac's inlier count, src/mapper.cpp:411-415)
+// gate of one match: a non-positive pivot of the 2 x 2 Cholesky, or gamma above chi2 (0: no gate; equality keeps) - not kept
+LCMAP_HD int lcmap_kept(int pivots_ok, double gamma, double chi2) { return pivots_ok && !(chi2 > 0.0 && gamma > chi2); }
+
+enum { LCMAP_FRAME_NONE = 0, LCMAP_FRAME_SHORT = 1, LCMAP_FRAME_CLOSED = 2 };
+// a filter with n_matched list positions filled of which n_kept passed the gate
+LCMAP_HD int lcmap_frame_decide(int n_matched, int n_kept, int min_matches) {
+  if (n_kept >= min_matches && n_kept > 0) return LCMAP_FRAME_CLOSED;
+  return n_matched > 0 ? LCMAP_FRAME_SHORT : LCMAP_FRAME_NONE;
+}
+// is the row pair of list position m neutral (H = 0, inn = 0, diagR = 1)?
+LCMAP_HD int lcmap_pair_neutral(int frame, int m, int n_matched, int kept) {
+  return frame != LCMAP_FRAME_CLOSED || m >= n_matched || !kept;
+}
+
+}  // namespace xivo_hip

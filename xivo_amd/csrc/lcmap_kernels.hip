@@ -1,0 +1,213 @@
+// The resident landmark map (gfx950), driven by capi_lcmap.hip: loop closure without a round trip to the host.
+//
+//  lcmap_add_kernel     DiscardFeatures -> Mapper::AddFeature (src/mapper.cpp:158-222, merge_features = false): the in-state
+//                       features that leave become map entries {key, Xs = Feature::Xs(gbc)}
+//  lcmap_match_kernel   Mapper::DetectLoopClosures (src/mapper.cpp:335-418), the matching: the frame's queries against the map,
+//                       the first lc_max matching ones in query order fill the filter's match list
+//  lcmap_close_kernel   the stacking of Estimator::CloseLoopInternal (src/update.cpp:183-196) on that list: the row pair of every
+//                       match (lc_row_pair, geometry_device.h - lc_rows_kernel's arithmetic), its gate on the filter's covariance
+//                       (the stand-in for pnp_ransac), whether the filter closes, neutral pairs for what does not take part
+// One workgroup of one wave per filter in all three: a filter's map is only ever touched by its own workgroup, so the order of
+// the records decides (never a race) and the counters are plain sums - no global atomics. The integer rules are
+// lcmap_device.h's, which a host program tests; the kernels only evaluate them.
+#include "ekf_kernels.h"
+#include "gate_device.h"
+#include "geometry_device.h"
+#include "lcmap_device.h"
+
+namespace xivo_hip {
+
+namespace {
+
+constexpr long kKeyStride = sizeof(xivo_lcmap_entry) / sizeof(long long);   // entry to entry, in keys
+static_assert(sizeof(xivo_lcmap_entry) == 32 && sizeof(xivo_lcmap_entry) % sizeof(long long) == 0, "lcmap_find walks the keys");
+
+__device__ __forceinline__ int lcmap_count(const LcMapBuffers& m, int filt) {
+  const int n = m.count[filt];
+  return n < 0 ? 0 : (n > m.map_max ? m.map_max : n);
+}
+
+// The records of a filter in order. The lanes share the search for the key among the stored entries, lane 0 writes the entry
+// a record becomes; the barrier behind an accepted record makes it visible to the search of the next one.
+__global__ __launch_bounds__(64) void lcmap_add_kernel(LcMapAddArgs a) {
+  const int filt = blockIdx.x, lane = threadIdx.x;
+  if (filt >= a.batch) return;
+  xivo_lcmap_entry* ent = a.map.entries + (long)filt * a.map.map_max;
+  const double* P = a.P + (long)filt * a.strideP;
+  const xivo_pose_in& pose = a.poses[filt];
+  int count = lcmap_count(a.map, filt);
+  long long n_add = 0, n_skip = 0, n_poor = 0, n_dup = 0, n_full = 0;
+  const int r0 = a.off[filt], r1 = a.off[filt + 1];
+  for (int i = r0; i < r1; ++i) {                        // (every lane walks the same records: the branches are uniform)
+    const xivo_lcmap_add_rec r = a.recs[i];
+    int in_state = 0, poor = 0, ref = 0;
+    const xivo_feat_in* ft = nullptr;
+    if (r.key >= 0 && r.feat >= 0 && r.feat < a.F) {
+      ft = a.feats + (long)filt * a.Fmax + r.feat;
+      ref = ft->ref_sind;
+      const int foff = a.lay.feature_begin + 3 * ft->sind;
+      in_state = ft->sind >= 0 && ft->sind < a.lay.n_features && foff + 2 < a.lay.N && ref >= 0 && ref < a.lay.n_groups;
+      if (in_state) poor = lcmap_poor(P[(foff + 2) + (long)(foff + 2) * a.ldp], a.max_depth_var);
+    }
+    int hit = 0;
+    if (in_state && !poor)
+      for (int e = lane; e < count; e += 64) hit |= ent[e].key == r.key ? 1 : 0;
+    const int dup = __ballot(hit) != 0ull;
+    const int d = lcmap_add_decide(in_state, poor, dup, count, a.map.map_max);
+    n_add += d == LCMAP_ADD_ACCEPT; n_skip += d == LCMAP_ADD_SKIPPED; n_poor += d == LCMAP_ADD_POOR;
+    n_dup += d == LCMAP_ADD_DUP; n_full += d == LCMAP_ADD_FULL;
+    if (d == LCMAP_ADD_ACCEPT) {
+      if (lane == 0) {
+        const V3 Xs = lc_world_point(pose, *ft, a.groups[(long)filt * a.lay.n_groups + ref], a.invdepth);
+        xivo_lcmap_entry& o = ent[count];
+        o.key = r.key; o.Xs[0] = Xs.v[0]; o.Xs[1] = Xs.v[1]; o.Xs[2] = Xs.v[2];
+      }
+      ++count;
+      __syncthreads();
+    }
+  }
+  if (lane == 0) {
+    a.map.count[filt] = count;
+    xivo_lcmap_stats& st = a.map.stats[filt];
+    st.added += n_add; st.skipped += n_skip; st.poor += n_poor; st.dup += n_dup; st.full += n_full;
+  }
+}
+
+// the 12 columns a row pair touches: the observing pose's six from goff, then Wbc Tbc (15..20)
+__device__ __forceinline__ int lc_col(int k, int goff) { return k < 6 ? goff + k : 15 + (k - 6); }
+
+// match: 64 queries at a time, one lane each; a matching query's rank is the number of matching queries before it, counted in
+// LDS (as the life-cycle kernels rank their candidates)
+__global__ __launch_bounds__(64) void lcmap_match_kernel(LcMapCloseArgs a) {
+  const int filt = blockIdx.x, lane = threadIdx.x;
+  if (filt >= a.batch) return;
+  __shared__ int sFlag[64];
+  const xivo_lcmap_entry* ent = a.map.entries + (long)filt * a.map.map_max;
+  const int count = lcmap_count(a.map, filt);
+  xivo_lcmap_match* list = a.matches + (long)filt * a.lc_max;
+  const int q0 = a.off[filt], q1 = a.off[filt + 1];
+  int base = 0;
+  for (int c0 = q0; c0 < q1; c0 += 64) {
+    const int q = c0 + lane;
+    const int e = q < q1 ? lcmap_find(&ent[0].key, kKeyStride, count, a.queries[q].key) : -1;
+    sFlag[lane] = e >= 0 ? 1 : 0;
+    __syncthreads();
+    int rank = base, tot = 0;
+#pragma unroll 8
+    for (int j = 0; j < 64; ++j) { tot += sFlag[j]; rank += sFlag[j] & ((j - lane) >> 31); }   // (the mask: all ones for j < lane)
+    const int slot = e >= 0 ? lcmap_match_slot(rank, a.lc_max) : -1;
+    if (slot >= 0) {
+      const xivo_lcmap_query& qu = a.queries[q];
+      xivo_lcmap_match& o = list[slot];
+      o.entry = e; o.group_sind = qu.group_sind; o.xp[0] = qu.xp[0]; o.xp[1] = qu.xp[1]; o.gamma = 0.0; o.kept = 0; o.reserved = 0;
+    }
+    base += tot;
+    __syncthreads();
+  }
+  const int n_matched = base < a.lc_max ? base : a.lc_max;
+  if (lane < a.lc_max && lane >= n_matched) {
+    xivo_lcmap_match& o = list[lane];
+    o.entry = -1; o.group_sind = 0; o.xp[0] = 0.0; o.xp[1] = 0.0; o.gamma = 0.0; o.kept = 0; o.reserved = 0;
+  }
+  if (lane == 0) {
+    xivo_lcmap_stats& st = a.map.stats[filt];
+    st.queries += q1 - q0; st.matched += n_matched; st.surplus += base - n_matched;
+  }
+}
+
+// rows, verify and the filter's decision: one lane per list position (the filled ones are the leading n_matched)
+__global__ __launch_bounds__(64) void lcmap_close_kernel(LcMapCloseArgs a) {
+  const int filt = blockIdx.x, lane = threadIdx.x;
+  if (filt >= a.batch) return;
+  __shared__ int sKept[64];
+  __shared__ double sH[64][25];                          // (odd row length: the lanes' rows fall in different banks)
+  const xivo_lcmap_entry* ent = a.map.entries + (long)filt * a.map.map_max;
+  const int count = lcmap_count(a.map, filt);
+  xivo_lcmap_match* list = a.matches + (long)filt * a.lc_max;
+  const int my_entry = lane < a.lc_max ? list[lane].entry : -1;
+  const int n_matched = __popcll(__ballot(my_entry >= 0 && my_entry < count));
+  double* H = a.H + (long)filt * a.strideH;
+  double* inn = a.inn + (long)filt * a.strideV;
+  double* dR = a.diagR + (long)filt * a.strideV;
+  const int r0 = 2 * lane;
+  int kept = 0, goff = 0;
+  if (lane < n_matched && my_entry >= 0 && my_entry < count) {   // (the second test: a list never has a gap, but is an address)
+    const xivo_lcmap_match mt = list[lane];
+    const xivo_pose_in& pose = a.poses[filt];
+    const xivo_lcmap_entry& en = ent[mt.entry];
+    const V3 Xs{{en.Xs[0], en.Xs[1], en.Xs[2]}};
+    const bool body = mt.group_sind < 0;                 // observed by the body pose itself: columns 0..5 (Wsb, Tsb)
+    const double *gR = pose.Rsb, *gT = pose.Tsb;
+    if (!body) {
+      const xivo_group_in& g = a.groups[(long)filt * a.lay.n_groups + mt.group_sind];
+      gR = g.Rsb; gT = g.Tsb; goff = a.lay.group_begin + 6 * mt.group_sind;
+    }
+    lc_row_pair(Xs, gR, gT, goff, pose, a.cam, a.cl.cam_begin, a.cl.cam_dim, mt.xp, a.Rlc, H, a.ldh, r0, inn, dR);
+    // gamma = r^T (H_i P H_i^T + Rlc I)^-1 r over the 12 columns of the pair (Estimator::MHGating's 2 x 2 Cholesky)
+    const double* P = a.P + (long)filt * a.strideP;
+    double* h = sH[lane];                                // the pair's 2 x 12 block, row-major (LDS: indexed by a loop counter)
+#pragma unroll 1
+    for (int k = 0; k < 12; ++k) {
+      const long c = lc_col(k, goff);
+      h[k] = H[r0 + c * a.ldh]; h[12 + k] = H[r0 + 1 + c * a.ldh];
+    }
+    double s00 = 0.0, s10 = 0.0, s11 = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < 12; ++j) {                       // column j of the sub-block of P under the pair's columns
+      const double* Pc = P + (long)lc_col(j, goff) * a.ldp;
+      double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) {
+        const double p = Pc[lc_col(k, goff)];
+        t0 += h[k] * p; t1 += h[12 + k] * p;
+      }
+      s00 += t0 * h[j]; s10 += t1 * h[j]; s11 += t1 * h[12 + j];
+    }
+    s00 += a.Rlc; s11 += a.Rlc;
+    const double l10 = s10 / sqrt(s00);
+    const int ok = s00 > 0.0 && (s11 - l10 * l10) > 0.0;
+    const double gamma = ok ? mh_dist_2x2(s00, s10, s11, inn[r0], inn[r0 + 1]) : -1.0;
+    kept = lcmap_kept(ok, gamma, a.chi2);
+    list[lane].gamma = gamma; list[lane].kept = kept;
+  }
+  sKept[lane] = kept;
+  __syncthreads();
+  int n_kept = 0;
+  for (int j = 0; j < n_matched; ++j) n_kept += sKept[j];
+  const int frame = lcmap_frame_decide(n_matched, n_kept, a.min_matches);
+  if (lane < a.lc_max && lcmap_pair_neutral(frame, lane, n_matched, kept)) {
+    if (lane < n_matched) {
+#pragma unroll 1
+      for (int k = 0; k < 12; ++k) {
+        const long c = lc_col(k, goff);
+        H[r0 + c * a.ldh] = 0.0; H[r0 + 1 + c * a.ldh] = 0.0;
+      }
+    }
+    inn[r0] = 0.0; inn[r0 + 1] = 0.0; dR[r0] = 1.0; dR[r0 + 1] = 1.0;
+  }
+  if (lane == 0) {
+    a.closing[filt] = frame == LCMAP_FRAME_CLOSED ? 1 : 0;
+    xivo_lcmap_stats& st = a.map.stats[filt];
+    st.gated += n_matched - n_kept;
+    st.short_frames += frame == LCMAP_FRAME_SHORT ? 1 : 0; st.closed_frames += frame == LCMAP_FRAME_CLOSED ? 1 : 0;
+  }
+}
+
+}  // namespace
+
+#define CHECK_LAUNCH() return (int)hipGetLastError()
+
+int launch_lcmap_add(const LcMapAddArgs& a, hipStream_t s) {
+  if (a.batch <= 0) return 0;
+  hipLaunchKernelGGL(lcmap_add_kernel, dim3(a.batch), dim3(64), 0, s, a);
+  CHECK_LAUNCH();
+}
+int launch_lcmap_close(const LcMapCloseArgs& a, hipStream_t s) {
+  if (a.batch <= 0) return 0;
+  hipLaunchKernelGGL(lcmap_match_kernel, dim3(a.batch), dim3(64), 0, s, a);
+  if (hipError_t e = hipGetLastError()) return (int)e;
+  hipLaunchKernelGGL(lcmap_close_kernel, dim3(a.batch), dim3(64), 0, s, a);
+  CHECK_LAUNCH();
+}
+
+}  // namespace xivo_hip

@@ -150,6 +150,19 @@ pool_oos_cand_dtype = np.dtype([("b", "i4"), ("entry", "i4"), ("n_obs", "i4"), (
 pool_oos_stats_dtype = np.dtype([(k, "i8") for k in ("oos_used", "oos_gated", "oos_surplus", "oos_short")])
 assert pool_oos_opts_dtype.itemsize == 280 and pool_oos_cand_dtype.itemsize == 336 and pool_oos_stats_dtype.itemsize == 32
 # chi-square 0.95 quantiles for 1 .. 29 degrees of freedom (index = dof; 0 and 30, 31 unused): the gate of an OOS feature's
+# the resident landmark map (include/xivo_hip.h): xivo_lcmap_opts, _entry, _add_rec, _query, _match, _stats
+lcmap_opts_dtype = np.dtype([("struct_size", "i4"), ("map_max", "i4"), ("lc_max", "i4"), ("min_matches", "i4"), ("Rlc", "f8"),
+                             ("chi2", "f8"), ("max_depth_var", "f8")])
+lcmap_entry_dtype = np.dtype([("key", "i8"), ("Xs", "f8", 3)])
+lcmap_add_dtype = np.dtype([("b", "i4"), ("feat", "i4"), ("key", "i8")])
+lcmap_query_dtype = np.dtype([("b", "i4"), ("group_sind", "i4"), ("key", "i8"), ("xp", "f8", 2)])
+lcmap_match_dtype = np.dtype([("entry", "i4"), ("group_sind", "i4"), ("xp", "f8", 2), ("gamma", "f8"), ("kept", "i4"), ("reserved", "i4")])
+LCMAP_STATS_FIELDS = ("added", "dup", "full", "poor", "skipped", "queries", "matched", "surplus", "gated", "short_frames", "closed_frames")
+lcmap_stats_dtype = np.dtype([(k, "i8") for k in LCMAP_STATS_FIELDS])
+assert (lcmap_opts_dtype.itemsize, lcmap_entry_dtype.itemsize, lcmap_add_dtype.itemsize, lcmap_query_dtype.itemsize,
+        lcmap_match_dtype.itemsize, lcmap_stats_dtype.itemsize) == (40, 32, 16, 32, 40, 88)
+LCMAP_MAX_ENTRIES, LCMAP_MAX_MATCHES = 4096, 64
+CHI2_2DOF_95 = 5.991464547107979   # -2 ln 0.05: the 95 % point of chi-square with 2 degrees of freedom
 # 2k - 3 projected rows (tests/test_pool_oos_cpu.py holds the table against scipy.stats.chi2.ppf)
 CHI2_95 = (0.0, 3.841458820694124, 5.991464547107979, 7.814727903251179, 9.487729036781154, 11.070497693516351,
            12.591587243743977, 14.067140449340169, 15.50731305586545, 16.918977604620448, 18.307038053275146,
@@ -309,6 +322,13 @@ _SIGS = {
     "xivo_hip_pool_oos_get": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "xivo_hip_pool_oos_get_rings": [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5,
     "xivo_hip_pool_oos_get_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_lcmap_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_lcmap_add": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_lcmap_close": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "xivo_hip_lcmap_set": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "xivo_hip_lcmap_get": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "xivo_hip_lcmap_get_matches": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_lcmap_get_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_pcw_config": [C.c_void_p, C.c_void_p],
     "xivo_hip_pcw_set_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_pcw_get_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
@@ -1373,6 +1393,59 @@ class Context:
         nb = self.batch - b0 if nb is None else int(nb)
         out = np.zeros(nb, dtype=pool_oos_stats_dtype)
         self._check(self.lib.xivo_hip_pool_oos_get_stats(self.h, int(b0), nb, _ptr(out)))
+        return out
+
+    # ---- loop closure: the resident landmark map --------------------------------
+    def lcmap_config(self, map_max, lc_max=8, min_matches=5, Rlc=1.5 ** 2, chi2=CHI2_2DOF_95, max_depth_var=0.0):
+        """the resident landmark map (xivo_hip_lcmap_config): map_max entries per filter, at most lc_max matches a frame (2 lc_max
+        staged rows), a filter closes with at least min_matches matches kept by the chi2 gate (0: no gate); map_max = 0 releases"""
+        o = np.zeros(1, dtype=lcmap_opts_dtype)
+        o["struct_size"] = lcmap_opts_dtype.itemsize
+        o["map_max"] = map_max; o["lc_max"] = lc_max; o["min_matches"] = min_matches
+        o["Rlc"] = Rlc; o["chi2"] = chi2; o["max_depth_var"] = max_depth_var
+        self._check(self.lib.xivo_hip_lcmap_config(self.h, _ptr(o)))
+        self.lcmap_max, self.lc_max = int(map_max), int(lc_max)
+
+    def lcmap_add(self, recs, B=None):
+        """the in-state features that leave, recs [n] lcmap_add_dtype ordered by b, before the edit that removes them
+        (asynchronous)"""
+        recs = np.ascontiguousarray(recs, dtype=lcmap_add_dtype)
+        self._check(self.lib.xivo_hip_lcmap_add(self.h, self.batch if B is None else int(B), len(recs), _ptr(recs) if len(recs) else None))
+
+    def lcmap_close(self, queries, B=None, wait=True):
+        """match queries [n] lcmap_query_dtype (ordered by b) against the maps, verify, stage the 2 lc_max loop-closure rows.
+        wait: -> the number of closing filters, and nothing is staged when that is 0; else always stages, returns None"""
+        queries = np.ascontiguousarray(queries, dtype=lcmap_query_dtype)
+        k = C.c_int(0)
+        self._check(self.lib.xivo_hip_lcmap_close(self.h, self.batch if B is None else int(B), len(queries),
+                                                  _ptr(queries) if len(queries) else None, C.byref(k) if wait else None))
+        return k.value if wait else None
+
+    def lcmap_set(self, entries, count, b0=0):
+        """load whole maps: entries [nb, map_max] lcmap_entry_dtype, count [nb]"""
+        entries = np.ascontiguousarray(entries, dtype=lcmap_entry_dtype); count = np.ascontiguousarray(count, dtype=np.int32)
+        assert entries.shape == (len(count), self.lcmap_max)
+        self._check(self.lib.xivo_hip_lcmap_set(self.h, int(b0), len(count), _ptr(entries), _ptr(count)))
+
+    def lcmap_get(self, b0=0, nb=None):
+        """-> (entries [nb, map_max] lcmap_entry_dtype, count [nb]); one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        ent = np.zeros((nb, self.lcmap_max), dtype=lcmap_entry_dtype); cnt = np.zeros(nb, dtype=np.int32)
+        self._check(self.lib.xivo_hip_lcmap_get(self.h, int(b0), nb, _ptr(ent), _ptr(cnt)))
+        return ent, cnt
+
+    def lcmap_matches(self, b0=0, nb=None):
+        """-> [nb, lc_max] lcmap_match_dtype: the match lists of the last lcmap_close (entry = -1: empty position)"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        out = np.zeros((nb, self.lc_max), dtype=lcmap_match_dtype)
+        self._check(self.lib.xivo_hip_lcmap_get_matches(self.h, int(b0), nb, _ptr(out)))
+        return out
+
+    def lcmap_stats(self, b0=0, nb=None):
+        """-> [nb] lcmap_stats_dtype: the per-filter counters; one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        out = np.zeros(nb, dtype=lcmap_stats_dtype)
+        self._check(self.lib.xivo_hip_lcmap_get_stats(self.h, int(b0), nb, _ptr(out)))
         return out
 
     def propagate_cov(self, Phi, Pmm, b0=0):

@@ -56,11 +56,14 @@ class RandomPCW:
         self.Xs = self.rng.uniform(lo, hi, size=(npts, 3))
         self.ids = np.full(npts, -1, dtype=np.int64)
         self.next_pt_id = 10000
+        self.last_point_index = np.zeros(0, dtype=np.int64)   # world-point index of every track the last call returned
 
     def generate_measurements(self, Rsc, Tsc, K, imw, imh, noise_px_std):
         """-> (feature_ids [n], xp_and_depths [n x 3]) of the points inside the image, ascending point order
         (point_cloud_world.py:64-99). Noise is drawn for every point in front of the camera, visible or not, as the
-        reference does, so that the stream does not depend on who is visible."""
+        reference does, so that the stream does not depend on who is visible. last_point_index keeps the world-point index of
+        every returned track, parallel to the ids: a point that leaves and returns gets a new id and keeps its index (a loop
+        closure key, xivo_hip_lcmap_*)."""
         Xc = (self.Xs - Tsc) @ Rsc          # rows: Rsc^T (Xs - Tsc)
         front = Xc[:, 2] > 0
         z = np.where(front, Xc[:, 2], 1.0)
@@ -75,6 +78,7 @@ class RandomPCW:
         self.ids[~vis] = -1
         sel = np.nonzero(vis)[0]
         out = np.stack([u[sel] + noise[sel, 0], v[sel] + noise[sel, 1], Xc[sel, 2]], axis=1)
+        self.last_point_index = sel.astype(np.int64)
         return self.ids[sel].copy(), out
 
 
@@ -362,10 +366,13 @@ class BatchPCW:
         self.Xs = self.rng.uniform(lo, hi, size=(B, npts, 3)) if Xs is None else np.asarray(Xs, dtype=float)
         self.ids = np.full(self.Xs.shape[:2], -1, dtype=np.int64)
         self.next_pt_id = np.full(self.Xs.shape[0], 10000, dtype=np.int64)
+        self.last_point_index = np.zeros(0, dtype=np.int64)   # world-point index of every track the last generate() returned
 
     def generate(self, Rsc, Tsc, K, imw, imh, noise_px_std, cam=None, max_radius=np.inf):
         """cam (a camera dict, any model) and max_radius: project through it as the device producer does after
-        xivo_hip_pcw_camera (project_points_cam; K, imw, imh are then not read); None: the pinhole K"""
+        xivo_hip_pcw_camera (project_points_cam; K, imw, imh are then not read); None: the pinhole K. last_point_index keeps the
+        index of every returned track's point inside its world, parallel to the ids (the same for a point that returns under a
+        new id: a loop closure key)"""
         if self.noise == "philox" or cam is not None:
             if cam is not None:
                 vis, u, v, zc = project_points_cam(self.Xs, Rsc, Tsc, cam, max_radius)
@@ -395,4 +402,5 @@ class BatchPCW:
         off[1:] = np.cumsum(vis.sum(axis=1))
         sel = np.nonzero(vis)                                                 # row-major: sequences in order, points ascending
         meas = np.stack([u[sel] + noise[sel][:, 0], v[sel] + noise[sel][:, 1], Xc[..., 2][sel]], axis=1)
+        self.last_point_index = sel[1].astype(np.int64)
         return off, self.ids[sel].copy(), np.ascontiguousarray(meas)

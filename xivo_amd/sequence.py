@@ -54,7 +54,17 @@ What is mirrored from the reference and what is simplified:
     frame, chi-square gated, in a fixed block of oos_max * (2 * oos_max_obs - 3) rows behind the in-state rows. The rules are
     pool_lifecycle_device.h's plife_hist_* / plife_oos_*; the device decides with the entry's status and depth. With
     pool_lifecycle="device" the rings are resident too and xivo_hip_pool_life_begin / _end select and record themselves.
-  * NOT IN EITHER: RefineDepth (`use_depth_opt`), gauge XY features and SwitchRefGroup, ownership transfer.
+  * loop closure (`SequenceConfig.loop_closure`, both host life cycles): Estimator::CloseLoop on a device-resident landmark map
+    (xivo_hip_lcmap_*). `frame(imu, tracks, keys)` takes one key per track - the stand-in for the mapper's descriptor match
+    (src/mapper.cpp:158-222, :335-418): equal non-negative keys are one world point; the point-cloud worlds supply the point's
+    index (`last_point_index`). The in-state features the tracker dropped go to the map before they are removed
+    (DiscardFeatures -> Mapper::AddFeature; gate-rejected ones never do, DestroyFeatures); right after the frame's update and
+    AbsorbError every tracked, gate-kept in-state feature queries the map with this frame's pixel, observed by the body pose,
+    and the filters with at least `lc_min_matches` chi-square-kept matches take a second update on the loop-closure rows
+    (CloseLoopInternal, src/update.cpp:171-212). The stored point is treated as exact, as the reference does. Refused with
+    the device life cycles (their track block carries no keys yet), use_oos and the innovation log.
+  * NOT IN EITHER: RefineDepth (`use_depth_opt`), gauge XY features and SwitchRefGroup, ownership transfer, feature merging and
+    map eviction, the g2o pose graph.
 The numerics of every step are the device path; this file holds no arithmetic of the filter itself.
 """
 import numpy as np
@@ -199,6 +209,14 @@ class SequenceConfig:
         self.oos_min_observations = 5
         self.oos_meas_std = 3.5
         self.oos_max, self.oos_max_obs = 4, 6
+        # loop closure on the resident landmark map (xivo_hip_lcmap_*; off by default): lc_map_max entries per filter, at most
+        # lc_max matches a frame, a filter closes with lc_min_matches kept ones (the mapper's default, src/mapper.cpp:411-415);
+        # lc_meas_std: cfg loop_closure_meas_std (cfg/pcw.json); lc_chi2: the gate of one match, the 95 % point of chi-square
+        # with 2 degrees of freedom, -2 ln 0.05 (0: no gate); lc_max_depth_var: a feature whose depth variance is above this
+        # when it leaves is not stored (0: no test)
+        self.loop_closure = False
+        self.lc_map_max, self.lc_max, self.lc_min_matches = 1024, 16, 5
+        self.lc_meas_std, self.lc_chi2, self.lc_max_depth_var = 4.0, 5.99, 0.0
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option " + k)
@@ -216,7 +234,9 @@ class SequenceConfig:
         """rows a context of this configuration stages at most: the in-state rows, and with use_oos the fixed OOS block plus the
         16 rows the mixed stacking pads it with (and the round-up of the block itself)"""
         r = self.oos_rows()
-        return 2 * self.n_features + (((r + 16 + 15) // 16) * 16 if r else 0)
+        m = 2 * self.n_features + (((r + 16 + 15) // 16) * 16 if r else 0)
+        # (loop_closure: its 2 lc_max rows replace the frame's rows for the second update)
+        return max(m, 2 * self.lc_max) if getattr(self, "loop_closure", False) else m
 
     def P_init(self):
         """Estimator ctor, src/estimator.cpp:257-304: P_ = identity (kFullSize - unused group / feature slots keep a
@@ -381,6 +401,35 @@ class HipBackend:
         self.oos_on = False
         if getattr(cfg, "use_oos", False):
             self.enable_oos()
+        self.lc_on = False
+        if getattr(cfg, "loop_closure", False):
+            self.enable_loop_closure()
+
+    def enable_loop_closure(self):
+        """allocate the resident landmark map, its match lists and counters (xivo_hip_lcmap_config)"""
+        c = self.cfg
+        if self.innov_on:
+            raise ValueError("loop_closure with the innovation log is not supported: the log holds one update per frame")
+        self.ctx.lcmap_config(c.lc_map_max, lc_max=c.lc_max, min_matches=c.lc_min_matches, Rlc=float(c.lc_meas_std) ** 2,
+                              chi2=c.lc_chi2, max_depth_var=c.lc_max_depth_var)
+        self.lc_on = True
+
+    def lcmap_add(self, recs):
+        """the in-state features about to leave -> map entries (asynchronous); before the edit that removes them"""
+        self.ctx.lcmap_add(recs, B=self.B)
+
+    def lcmap_close(self, queries):
+        """match, verify and stage the loop-closure rows; if any filter closes, the second update and AbsorbError
+        (CloseLoopInternal, src/update.cpp:207-208) -> the number of closing filters"""
+        n = self.ctx.lcmap_close(queries, B=self.B, wait=True)
+        if n > 0:
+            self.ctx.update_joseph()
+            self.ctx.absorb_error()
+        return n
+
+    def lcmap_stats(self):
+        """[B] lcmap_stats_dtype; one synchronising read"""
+        return self.ctx.lcmap_stats(0, self.B)
 
     def enable_oos(self):
         """allocate the OOS list, gate distances and counters of the MSCKF update from dropped pool entries
@@ -609,6 +658,8 @@ class HipBackend:
         the log counts every staged row, so its dof would include the empty rows of the OOS block"""
         if self.oos_on and T_max > 0:
             raise ValueError("innovation_log with use_oos is not supported: the log's dof would count the empty rows of the OOS block")
+        if getattr(self, "lc_on", False) and T_max > 0:
+            raise ValueError("innovation_log with loop_closure is not supported: the log holds one update per frame")
         self.ctx.innov_config(T_max)
         self.innov_on = T_max > 0
 
@@ -643,6 +694,7 @@ class _Book:
         self.group_gen = [0] * n_groups          # how many groups have lived in the slot (tells a re-used slot apart)
         self.feat_id = [-1] * n_features         # track id held by feature slot j (-1: free)
         self.feat_ref = [-1] * n_features
+        self.feat_key = [-1] * n_features        # loop_closure: the key of the slot's track, from the frame it was first seen
         self.id2slot = {}
 
     def drop_feature(self, j):
@@ -661,6 +713,7 @@ class _PoolBook:
         self.ent_id = [-1] * pool_max            # track id held by pool entry e (-1: free)
         self.ent_anchor = [-1] * pool_max
         self.ent_born = [0] * pool_max           # camera frame the entry was created in
+        self.ent_key = [-1] * pool_max           # loop_closure: the track's key, handed on to the slot book at admission
         self.id2ent = {}
         self.anc_used = [False] * anchor_max
         self.anc_life = [0] * anchor_max         # Group::lifetime (frames since creation)
@@ -724,6 +777,16 @@ def check_lifecycle(cfg):
             raise ValueError("use_oos needs feature_init='subfilter' (feature_init=%r)" % (cfg.feature_init,))
         if not 2 <= cfg.oos_max_obs <= L.OOS_MAX_OBS or not 2 <= cfg.oos_min_observations <= cfg.oos_max_obs or not 0 < cfg.oos_max <= 64:
             raise ValueError("use_oos needs 2 <= oos_min_observations <= oos_max_obs <= %d and 0 < oos_max <= 64" % L.OOS_MAX_OBS)
+    if getattr(cfg, "loop_closure", False):
+        if cfg.lifecycle == "device" or plc == "device":
+            raise ValueError("loop_closure runs with the host life cycles only: the device life cycles' track block carries no keys")
+        if getattr(cfg, "use_oos", False):
+            raise ValueError("loop_closure with use_oos is not supported: both stage rows of their own behind the frame's update")
+        if not 0 < cfg.lc_map_max <= L.LCMAP_MAX_ENTRIES or not 0 < cfg.lc_max <= L.LCMAP_MAX_MATCHES or cfg.lc_min_matches < 1:
+            raise ValueError("loop_closure needs 0 < lc_map_max <= %d, 0 < lc_max <= %d and lc_min_matches >= 1"
+                             % (L.LCMAP_MAX_ENTRIES, L.LCMAP_MAX_MATCHES))
+        if not cfg.lc_meas_std > 0 or cfg.lc_chi2 < 0 or cfg.lc_max_depth_var < 0:
+            raise ValueError("loop_closure needs lc_meas_std > 0, lc_chi2 >= 0 and lc_max_depth_var >= 0")
     if src == "device":
         if cfg.lifecycle != "device" and plc != "device":
             raise ValueError("track_source='device' needs lifecycle='device' or pool_lifecycle='device'")
@@ -916,12 +979,46 @@ class SequenceRunner:
                 if self.pools is not None:
                     self.pools[b].unlink_slot(g)      # the device freezes the anchor at the group's last pose
 
-    def frame(self, imu, tracks):
-        """imu: [B x K] xivo_imu_in records or None; tracks: per filter (ids [n], xp_and_depths [n x 3])."""
+    def _lc_keys(self, tracks, keys):
+        """loop_closure: per filter {track id: key} of the frame (None when it is off)"""
+        if not getattr(self.cfg, "loop_closure", False):
+            return None
+        if keys is None:
+            raise ValueError("loop_closure needs keys: one per track of every filter, parallel to tracks[b][0]")
+        out = []
+        for b in range(self.B):
+            if len(keys[b]) != len(tracks[b][0]):
+                raise ValueError("keys[%d] is not parallel to tracks[%d][0]" % (b, b))
+            out.append({int(i): int(k) for i, k in zip(tracks[b][0], keys[b])})
+        return out
+
+    def _lc_add(self, leaving):
+        """loop_closure: the in-state features (b, slot, key) the tracker dropped, in filter order, go to the map before their edit"""
+        if leaving:
+            recs = np.zeros(len(leaving), dtype=L.lcmap_add_dtype)
+            for i, (b, j, key) in enumerate(leaving):
+                recs[i]["b"], recs[i]["feat"], recs[i]["key"] = b, j, key
+            self.be.lcmap_add(recs)
+
+    def _lc_close(self, xp, mask):
+        """loop_closure: one query per in-state feature that was tracked this frame and kept by the gate, observed by the body
+        pose at this frame's pixel; then the second update of the filters that close"""
+        q = []
+        for b in range(self.B):
+            bk = self.books[b]
+            for j in range(self.cfg.n_features):
+                if bk.feat_id[j] >= 0 and mask[b, j] and not np.isnan(xp[b, j, 0]):
+                    q.append((b, -1, bk.feat_key[j], (xp[b, j, 0], xp[b, j, 1])))
+        self.n_lc_closed = getattr(self, "n_lc_closed", 0) + self.be.lcmap_close(np.array(q, dtype=L.lcmap_query_dtype))
+
+    def frame(self, imu, tracks, keys=None):
+        """imu: [B x K] xivo_imu_in records or None; tracks: per filter (ids [n], xp_and_depths [n x 3]); keys (loop_closure):
+        per filter the key of every track, parallel to tracks[b][0]."""
+        lck = self._lc_keys(tracks, keys)
         if self.cfg.feature_init == "subfilter":
             if self.device_pool_lifecycle:
                 return self._frame_subfilter_device(imu, tracks)
-            return self._frame_subfilter(imu, tracks)
+            return self._frame_subfilter(imu, tracks, lck)
         if self.cfg.feature_init != "immediate":
             raise ValueError("feature_init must be 'immediate' or 'subfilter'")
         if self.device_lifecycle:
@@ -933,7 +1030,7 @@ class SequenceRunner:
             be.propagate(imu)
         t0 = self._tick("propagate", t0) or t0
         # --- before the update: tracker-dropped features leave, tracked ones get their new pixel
-        ops = []
+        ops, leaving = [], []
         xp = np.full((self.B, cfg.n_features, 2), np.nan)     # the frame's pixels of the tracked in-state features
         for b in range(self.B):
             bk = self.books[b]
@@ -947,15 +1044,20 @@ class SequenceRunner:
                     xp[b, j] = meas[pos[fid], :2]
                 else:
                     ops.append(_op(b, L.EDIT_REMOVE_FEATURE, j))
+                    leaving.append((b, j, bk.feat_key[j]))
                     bk.drop_feature(j)
             self._discard_empty_groups(b, ops)
         ops = np.array(ops, dtype=L.edit_dtype)
         t0 = self._tick("host_pre", t0) or t0
+        if lck is not None:
+            self._lc_add(leaving)
         be.edit(ops)
         be.set_pixels(xp)
         t0 = self._tick("edit", t0) or t0
         # --- measurement update on the tracked in-state features (every filter, ragged)
         mask = be.update()
+        if lck is not None:
+            self._lc_close(xp, mask)
         t0 = self._tick("update", t0) or t0
         self.n_updates += sum(1 for bk in self.books if bk.n_instate() > 0)
         # --- after the update: MH-rejected features leave, then new features enter with a new group
@@ -988,6 +1090,7 @@ class SequenceRunner:
                 x = [(meas[k, 0] - cx) / fx, (meas[k, 1] - cy) / fy, (1.0 / meas[k, 2] if getattr(cfg, "use_invdepth", False) else np.log(meas[k, 2]))]   # Feature::Initialize, feature.cpp:144-150
                 ops.append(_op(b, L.EDIT_ADD_FEATURE, j, j, g, v=np.concatenate([x, meas[k, :2], P3])))
                 bk.feat_id[j] = int(ids[k]); bk.feat_ref[j] = g; bk.id2slot[int(ids[k])] = j
+                bk.feat_key[j] = lck[b][int(ids[k])] if lck is not None else -1
                 bk.group_refs[g] += 1
         ops = np.array(ops, dtype=L.edit_dtype)
         t0 = self._tick("host_post", t0) or t0
@@ -996,7 +1099,7 @@ class SequenceRunner:
         return mask
 
 
-    def _frame_subfilter(self, imu, tracks):
+    def _frame_subfilter(self, imu, tracks, lck=None):
         """one camera frame in the order of Estimator::UpdateStep (src/manager.cpp:18-130) with the feature pool"""
         cfg, be, B = self.cfg, self.be, self.B
         use_oos = bool(getattr(cfg, "use_oos", False))
@@ -1010,15 +1113,18 @@ class SequenceRunner:
         pos = [{int(i): k for k, i in enumerate(tracks[b][0])} for b in range(B)]
         # --- ProcessTracks (:171-250): in-state features the tracker dropped leave the state, pool entries it dropped
         # leave the pool, every other pool entry takes its sub-filter step
-        ops = []
+        ops, leaving = [], []
         xpp = np.full((B, cfg.pool_max, 2), np.nan)
         for b in range(B):
             bk, pb, meas = self.books[b], self.pools[b], tracks[b][1]
             for j in range(cfg.n_features):
                 if bk.feat_id[j] >= 0 and bk.feat_id[j] not in pos[b]:
                     ops.append(_op(b, L.EDIT_REMOVE_FEATURE, j))
+                    leaving.append((b, j, bk.feat_key[j]))
                     bk.drop_feature(j)
             self._discard_empty_groups(b, ops)
+        if lck is not None:   # (the ops above go down with the admissions below: the map sees the features before either)
+            self._lc_add(leaving)
         # --- OOS selection (use_oos): every live entry without a track, ascending, with its valid observations - after the groups
         # above left, before anything is freed. The device decides with the entry's status and depth (plife_oos_decide)
         if use_oos:
@@ -1067,6 +1173,7 @@ class SequenceRunner:
                 ops.append(_op(b, L.EDIT_ADMIT_POOL, j, j, int(e)))
                 self.admitted.append((self.vision_counter, b, fid, self.vision_counter - pb.ent_born[e]))
                 bk.feat_id[j] = fid; bk.feat_ref[j] = g; bk.id2slot[fid] = j
+                bk.feat_key[j] = pb.ent_key[e]
                 bk.group_refs[g] += 1
                 pb.free_entry(int(e))
         be.edit(np.array(ops, dtype=L.edit_dtype))
@@ -1079,6 +1186,8 @@ class SequenceRunner:
         be.set_pixels(xp)
         # --- OutlierRejection + FilterUpdate, then DiscardAffectedGroups
         mask = be.update()
+        if lck is not None:
+            self._lc_close(xp, mask)
         self.n_updates += sum(1 for bk in self.books if bk.n_instate() > 0)
         ops = []
         for b in range(B):
@@ -1119,6 +1228,7 @@ class SequenceRunner:
                 r["b"], r["entry"], r["anchor"], r["xp"], r["z0"], r["std_xyz"] = b, e, a, meas[k, :2], cfg.initial_z, std
                 recs.append(r)
                 pb.ent_id[e] = int(ids[k]); pb.ent_anchor[e] = a; pb.ent_born[e] = self.vision_counter
+                pb.ent_key[e] = lck[b][int(ids[k])] if lck is not None else -1
                 pb.id2ent[int(ids[k])] = e
                 pb.hist_cnt[e] = 0; pb.hist[e] = []          # plife_hist_reset
             # --- OOS history (use_oos): the frame's anchor observes every live entry that had a track, the new ones included
@@ -1176,7 +1286,9 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     (_innovation). A backend without enable_innovation_log (the oracle) leaves the keys out.
     cfg.track_source = "device": the points of `worlds` go to the device once and every frame is SequenceRunner.frame_world
     on the ground-truth camera poses; the worlds' own generate_measurements is not called, the pixel noise is the device's
-    stream keyed by noise_seed, and with map_log the world ids are downloaded once per recorded frame."""
+    stream keyed by noise_seed, and with map_log the world ids are downloaded once per recorded frame.
+    cfg.loop_closure: every frame hands the worlds' last_point_index to the runner as the tracks' keys; adds `lcmap_stats`
+    ([B] lcmap_stats_dtype)."""
     if getattr(cfg, "imu_source", "host") == "device":
         raise ValueError("run_pcw feeds the simulators' IMU messages one by one: imu_source='device' runs with run_pcw_batch "
                          "or SequenceRunner.frame_resident")
@@ -1189,6 +1301,7 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     runner = SequenceRunner(be, cfg, B)
     runner.timers = timers
     dev_tracks = cfg.track_source == "device"
+    lc = bool(getattr(cfg, "loop_closure", False))      # the worlds' point indices are the tracks' keys
     if dev_tracks:
         be.set_world(np.array([w.Xs for w in worlds]))
         runner.noise_px_std, runner.noise_seed = noise_vision_std, noise_seed
@@ -1222,7 +1335,7 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
             if dev_tracks:
                 runner.frame_world(feeder.take(), np.array(tracks), len(ts))
             else:
-                runner.frame(feeder.take(), tracks)
+                runner.frame(feeder.take(), tracks, [w.last_point_index for w in worlds] if lc else None)
             ts.append(int(round(t * 1e9)))
             if trajectory_log:
                 be.record(ts[-1])
@@ -1235,6 +1348,8 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
                 mlog.record(ts[-1], [bk.feat_id for bk in runner.books],
                             be.world_ids()[0] if dev_tracks else np.array([w.ids for w in worlds]), np.array([w.Xs for w in worlds]))
     out = dict(ts=np.array(ts), gt_Tsb=np.array(gt_T), runner=runner, backend=be)
+    if lc and hasattr(be, "lcmap_stats"):
+        out["lcmap_stats"] = be.lcmap_stats()
     if mlog is not None:
         mlog.finish(out)
     if ilog:
