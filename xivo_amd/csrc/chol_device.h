@@ -1,6 +1,8 @@
-// The 16 x 16 diagonal-block factor-and-invert step shared by every kernel that factors S: the two Cholesky kernels of
-// chol_f64.hip (chol_f64_kernel, chol_reg_f64_kernel) and the one-kernel update (fused_update.hip). They all use this routine
-// with the same operand order around it, so that they all produce the SAME bits.
+// The 16 x 16 diagonal-block factor-and-invert step shared by every kernel that factors S: the Cholesky kernels of
+// chol_f64.hip (chol_f64_kernel, chol_reg_f64_kernel, chol_reg_la_f64_kernel) and the one-kernel update (fused_update.hip).
+// They all use this one routine (there is no second form and no build switch that selects one) with the same operand order
+// around it, so that they all produce the SAME bits. A non-positive pivot is recorded, not replaced: the factor of a flagged
+// filter may hold NaNs, and its caller discards it (status, ldlt_fallback.hip).
 #pragma once
 #include "mfma_util.h"
 

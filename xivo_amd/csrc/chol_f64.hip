@@ -6,8 +6,11 @@
 // chol_f64_kernel : one wave64 per filter, left-looking, 16x16 blocks (the v_mfma_f64_16x16x4_f64 tile); its explicit
 //   inverse of every diagonal block is kept so every panel / triangular-solve step is an MFMA.
 //   Output: L in the lower triangle, L^T mirrored into the upper triangle.
-// chol_reg_f64_kernel : four waves per filter, the factor in registers (M <= 192).
-// Both factor and invert a diagonal block with the SAME routine (factor_invert_diag, chol_device.h: four steps of four columns;
+// chol_reg_f64_kernel : four waves per filter, the factor in registers (M <= 192), as few factors run it (batch < 512); the
+//   same kernel on eight waves for 13 - 19 block rows (M <= 304).
+// chol_reg_la_f64_kernel : the same for many factors (batch >= 512): no scratch at three workgroups per CU, look-ahead over
+//   the diagonal blocks, one barrier per block column; carries the gate.
+// All of them factor and invert a diagonal block with the SAME routine (factor_invert_diag, chol_device.h: four steps of four columns;
 // chol_S 1.95 -> 1.86 ms per 16384 at M = 160, 2.65 -> 2.48 per 4096 at M = 300, 0.27 -> 0.25 at M = 120 against the
 // sixteen-column loop of rounds 3-5) and use the same operand order everywhere else, so they produce the same bits: which of
 // them a node runs faster changes the time, never the result.
@@ -129,17 +132,14 @@ __global__ __launch_bounds__(64, 4) void chol_f64_kernel(CholArgs g) {
 //              chain) -> LDS / global; publishes the row panel L_jk, k < j, in LDS
 //   C  all   : own rows i > j:  L_ij^T = inv(L_jj) (S_ij^T - sum_k L_jk L_ik^T), kept + stored
 // with one barrier between A and C and one after C.
-// MINB = workgroups per CU the register budget is cut for: 3 (168 VGPRs, a few spills) is faster for thousands of
-// factors (0.67 vs 0.75 ms / 4096 at M = 160), 2 (212 VGPRs) for a single one (76 vs 82 us)
-
-// GATE (round 5): Estimator::MHGating (src/update.cpp:60-96) in the prologue of the factorisation - the chi-square distances
-// from the 2 x 2 diagonal blocks of S (the compact copy ell<S> leaves), the relaxation loop, the mask; the rows / columns of
-// the rejected pairs are then decoupled WHERE S IS LOADED (0, unit diagonal - what gate_ell_kernel writes into S), their
-// inn / diagR / compressed values / P H^T columns neutralised from here. One launch and one pass over S fewer per update;
-// with three factors in flight per CU the gate's two dependent round trips hide behind the other workgroups. Same values as
-// gate_ell_kernel bit for bit (same expressions), so the factor and everything behind it are unchanged.
-template <int NB, int MINB, bool PRE, bool UPFRONT, int NW = 4, bool GATE = false>
-__global__ __launch_bounds__(64 * NW, MINB) void chol_reg_f64_kernel(CholArgs g, int mirror, CholGateArgs gt) {
+// These are the few-factors instantiations (PRE + UPFRONT: every block of S requested up front, the diagonal update one
+// column ahead; register budget cut for MINB = 2 workgroups per CU) and the eight-wave ones. With the budget cut for three
+// workgroups per CU (168 VGPRs) this schedule does not fit: rows dealt from the top keep up to 14 blocks of L live, three
+// diagonal blocks per wave are held from kernel start and the blocks of S land in registers of their own - 76 of 168
+// VGPRs spilled, 196 bytes of scratch per lane, every reload in the column chain a wait on vmcnt behind the wave's loads
+// and stores (what this comment called "a few spills" until it was counted). The many-factors kernel below replaces it there.
+template <int NB, int MINB, bool PRE, bool UPFRONT, int NW = 4>
+__global__ __launch_bounds__(64 * NW, MINB) void chol_reg_f64_kernel(CholArgs g, int mirror) {
   constexpr int RW = (NB + NW - 1) / NW;   // NW waves per factor: 4 (M <= 192), 8 (M <= 320: one workgroup per CU)
   const int filt = blockIdx.x;
   if (filt >= g.batch) return;
@@ -154,53 +154,6 @@ __global__ __launch_bounds__(64 * NW, MINB) void chol_reg_f64_kernel(CholArgs g,
   __shared__ __attribute__((aligned(16))) double sRow[(NB - 1) * 256];   // [k][lane][4]
   __shared__ int sBad;
   if (tid == 0) sBad = 0;
-  __shared__ unsigned char sRej[GATE ? 16 * NB : 1];    // 1: the row belongs to a rejected feature
-  if constexpr (GATE) {
-    static_assert(NW == 4 && !UPFRONT, "the gate rides in the many-factors instantiations");
-    double* sdist = sRow;                                // F <= 8 NB distances + the threshold: scratch until the first panel is published
-    const int F = gt.F;
-    double* inn = gt.inn + (long)filt * gt.strideInn;
-    double* dr = gt.diagR + (long)filt * gt.strideR;
-    const double* sd = gt.Sdiag + (long)filt * gt.strideSdiag;
-    for (int f = tid; f < F; f += 64 * NW) {             // (gate_ell_body, from_S with the compact diagonal blocks)
-      const double s00 = sd[4 * f] - dr[2 * f] + gt.R;
-      const double s10 = sd[4 * f + 2];
-      const double s11 = sd[4 * f + 3] - dr[2 * f + 1] + gt.R;
-      sdist[f] = mh_dist_2x2(s00, s10, s11, inn[2 * f], inn[2 * f + 1]);
-    }
-    for (int m = tid; m < 16 * NB; m += 64 * NW) sRej[m] = 0;
-    __syncthreads();
-    if (wave == 0) {
-      const double th = relax_threshold(sdist, F, gt.thresh, gt.mult, gt.min_inliers, lane);
-      if (lane == 0) sdist[F] = th;
-    }
-    __syncthreads();
-    const double th = sdist[F];
-    for (int f = tid; f < F; f += 64 * NW) {
-      const bool in = sdist[f] < th;
-      gt.mask[(long)filt * F + f] = in ? 1 : 0;
-      gt.dist[(long)filt * F + f] = sdist[f];
-      if (!in) {
-        sRej[2 * f] = 1; sRej[2 * f + 1] = 1;
-        inn[2 * f] = 0.0; inn[2 * f + 1] = 0.0;
-        dr[2 * f] = 1.0; dr[2 * f + 1] = 1.0;
-        double* val = gt.ellval + (long)filt * gt.strideVal + (long)f * gt.ell_w * 2;
-        for (int t = 0; t < 2 * gt.ell_w; ++t) val[t] = 0.0;
-      }
-    }
-    __syncthreads();
-    double* PHT = gt.PHT + (long)filt * gt.stridePHT;    // the solve's right-hand sides: columns of the rejected pairs
-    for (int f = 0; f < F; ++f) {
-      if (!sRej[2 * f]) continue;
-      for (int n = tid; n < gt.Np; n += 64 * NW) { PHT[n + (long)(2 * f) * gt.ldpht] = 0.0; PHT[n + (long)(2 * f + 1) * gt.ldpht] = 0.0; }
-    }
-    __syncthreads();                                      // sRow is scratch no longer
-  }
-  // element (row, col) of S as the gate leaves it: rows / columns of rejected pairs decoupled (gate_ell_body's in-place edit)
-  auto gated = [&](double v, int row, int col) -> double {
-    if constexpr (GATE) return (sRej[row] | sRej[col]) ? (row == col ? 1.0 : 0.0) : v;
-    else return v;
-  };
 
   d4 L[RW][NB];   // L[ii][k] = block (i = wave + 4 ii, k); only k < i is ever touched
   // the diagonal blocks this wave will factor, fetched up front (their latency would otherwise sit in
@@ -211,7 +164,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void chol_reg_f64_kernel(CholArgs g,
     const int jd = wave + NW * ii;
     if (NW == 4 && jd < nb) {   // (eight waves, up to 19 block rows: no registers to spare - requested per block column below)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) sdiag[ii][r] = gated(S[(16 * jd + li) + (long)(16 * jd + lg + 4 * r) * ld], 16 * jd + li, 16 * jd + lg + 4 * r);
+      for (int r = 0; r < 4; ++r) sdiag[ii][r] = S[(16 * jd + li) + (long)(16 * jd + lg + 4 * r) * ld];
     }
   }
 
@@ -244,7 +197,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void chol_reg_f64_kernel(CholArgs g,
       const int i = wave + NW * ii;
       if (!UPFRONT && NW * ii + NW - 1 > j && i > j && i < nb) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) sreg[ii][r] = gated(S[(16 * i + li) + (long)(16 * j + lg + 4 * r) * ld], 16 * i + li, 16 * j + lg + 4 * r);
+        for (int r = 0; r < 4; ++r) sreg[ii][r] = S[(16 * i + li) + (long)(16 * j + lg + 4 * r) * ld];
       }
     }
     // diagonal block in the 64-lane layout x[r] = X[row li][col lg + 4 r] - which is what the MFMA
@@ -339,14 +292,234 @@ __global__ __launch_bounds__(64 * NW, MINB) void chol_reg_f64_kernel(CholArgs g,
   if (tid == 0) g.status[filt] = sBad;
 }
 
+// The many-factors instantiations (batch >= 512, chol_reg_mode 0): the same four waves, the same operations on the same
+// operands in the same order for every block of L - so the same bits - dealt and scheduled for thousands of co-resident
+// factors, where the register file is cut for three workgroups per CU (168 VGPRs) and must hold without scratch: on this ISA
+// a scratch reload goes through vmcnt, loads and stores retire in order, so every reload in the block-column chain waits
+// for the wave's outstanding loads of S and stores of L.
+//   Ownership: block rows are dealt from the BOTTOM, row i = NB - 1 - 4 ii - wave in slot ii of a wave. Consecutive rows are
+//     still on different waves, but slot ii is now busy in every wave over the same columns (j < NB - 1 - 4 ii), so the
+//     registers of a finished slot are free for all four waves at once: at most 11 blocks of L live at ten block rows
+//     (top-dealt rows: 14, slot ii of wave 3 outlives slot ii of wave 0 by three columns and the allocator holds the union).
+//   Requests: the blocks of S of column j + 1 and the diagonal block of column j + 2 are requested in column j, the former
+//     straight into the register block of L they become, the latter into ONE block per wave. Three waves - the owner of row
+//     j + 2, which carries the chain of the next column, among them - issue them at the top of the column, before its
+//     stores, so no load of the chain queues behind a store; the look-ahead wave issues them behind its factorisation, which
+//     then does not have to hold the landing blocks. (Three diagonal blocks per wave from kernel start and a second set of
+//     registers for the blocks of S were 48 VGPRs of the budget before.)
+//   Look-ahead, one step deep: in column j the owner of block row j + 1 finishes L(j+1, j) first, forms the whole diagonal
+//     update of block (j+1, j+1) (k ascending, the two accumulators alternating as everywhere), factors and inverts it and
+//     publishes inv(L) and its row panel into the OTHER LDS buffer; only then does it do its remaining rows of column j.
+//     The other three waves work through their rows of column j meanwhile, so the serial chain per column is one panel
+//     block + one diagonal block instead of the diagonal block + the busiest wave's panel, and ONE barrier per column is
+//     enough: the buffers column j + 2 writes (during column j + 1) were last read in column j, before its barrier.
+// GATE (round 5): Estimator::MHGating (src/update.cpp:60-96) in the prologue of the factorisation - the chi-square distances
+// from the 2 x 2 diagonal blocks of S (the compact copy ell<S> leaves), the relaxation loop, the mask; the rows / columns of
+// the rejected pairs are then decoupled WHERE A BLOCK OF S IS CONSUMED (0, unit diagonal - what gate_ell_kernel writes into S;
+// the requests above are already in flight behind the gate), their inn / diagR / compressed values / P H^T columns
+// neutralised from here. One launch and one pass over S fewer per update. Same values as gate_ell_kernel bit for bit (same
+// expressions), so the factor and everything behind it are unchanged.
+template <int NB, int MINB, bool GATE>
+__global__ __launch_bounds__(256, MINB) void chol_reg_la_f64_kernel(CholArgs g, int mirror, CholGateArgs gt) {
+  constexpr int RW = (NB + 3) / 4;
+  const int filt = blockIdx.x;
+  if (filt >= g.batch) return;
+  double* S = g.S + (long)filt * g.strideS;
+  double* invD = g.invD + (long)filt * g.strideInvD;
+  const long ld = g.lds;
+  const int nb = g.Mp / 16;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lg = lane >> 4;
+
+  __shared__ double sInv[2][2][256];                                        // [buffer][inv(L), inv(L)^T]
+  __shared__ __attribute__((aligned(16))) double sRow[2][(NB - 1) * 256];   // [buffer][k][lane][4]
+  __shared__ int sBad;
+  __shared__ unsigned char sRej[GATE ? 16 * NB : 1];    // 1: the row belongs to a rejected feature
+  // block row r: wave (NB - 1 - r) % 4, slot (NB - 1 - r) / 4 - both compile-time wherever r is
+  constexpr int owner0 = (NB - 1) % 4;
+  if (wave == owner0 && lane == 0) sBad = 0;            // (the lane that may set it in the prologue; later owners write behind a barrier)
+
+  d4 L[RW][NB];   // L[ii][k] = block (i = NB - 1 - 4 ii - wave, k); only k <= i is ever touched (k = i: S_ik in flight)
+  d4 xd;          // the diagonal block of S this wave factors next: element r = S[row li][col lg + 4 r]
+  // blocks of S of column c for the rows this wave still has to finish, and the diagonal block of column c + 1
+  auto request = [&](auto cc) {
+    constexpr int c = decltype(cc)::value;
+    static_for<RW>([&](auto iic) {
+      constexpr int ii = decltype(iic)::value, top = NB - 1 - 4 * ii;
+      if constexpr (top > c) {
+        const int i = top - wave;
+        if (i > c && i < nb) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) L[ii][c][r] = S[(16 * i + li) + (long)(16 * c + lg + 4 * r) * ld];
+        }
+      }
+    });
+    if constexpr (c + 1 < NB) {
+      if (c + 1 < nb && wave == (NB - 2 - c) % 4) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xd[r] = S[(16 * (c + 1) + li) + (long)(16 * (c + 1) + lg + 4 * r) * ld];
+      }
+    }
+  };
+  if (wave == owner0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) xd[r] = S[li + (long)(lg + 4 * r) * ld];
+  }
+  request(std::integral_constant<int, 0>{});
+
+  if constexpr (GATE) {
+    double* sdist = sRow[0];                             // F <= 8 NB distances + the threshold: scratch until the first panel is published
+    const int F = gt.F;
+    double* inn = gt.inn + (long)filt * gt.strideInn;
+    double* dr = gt.diagR + (long)filt * gt.strideR;
+    const double* sd = gt.Sdiag + (long)filt * gt.strideSdiag;
+    for (int f = tid; f < F; f += 256) {                 // (gate_ell_body, from_S with the compact diagonal blocks)
+      const double s00 = sd[4 * f] - dr[2 * f] + gt.R;
+      const double s10 = sd[4 * f + 2];
+      const double s11 = sd[4 * f + 3] - dr[2 * f + 1] + gt.R;
+      sdist[f] = mh_dist_2x2(s00, s10, s11, inn[2 * f], inn[2 * f + 1]);
+    }
+    for (int m = tid; m < 16 * NB; m += 256) sRej[m] = 0;
+    __syncthreads();
+    if (wave == 0) {
+      const double th = relax_threshold(sdist, F, gt.thresh, gt.mult, gt.min_inliers, lane);
+      if (lane == 0) sdist[F] = th;
+    }
+    __syncthreads();
+    const double th = sdist[F];
+    for (int f = tid; f < F; f += 256) {
+      const bool in = sdist[f] < th;
+      gt.mask[(long)filt * F + f] = in ? 1 : 0;
+      gt.dist[(long)filt * F + f] = sdist[f];
+      if (!in) {
+        sRej[2 * f] = 1; sRej[2 * f + 1] = 1;
+        inn[2 * f] = 0.0; inn[2 * f + 1] = 0.0;
+        dr[2 * f] = 1.0; dr[2 * f + 1] = 1.0;
+        double* val = gt.ellval + (long)filt * gt.strideVal + (long)f * gt.ell_w * 2;
+        for (int t = 0; t < 2 * gt.ell_w; ++t) val[t] = 0.0;
+      }
+    }
+    __syncthreads();
+    double* PHT = gt.PHT + (long)filt * gt.stridePHT;    // the solve's right-hand sides: columns of the rejected pairs
+    for (int f = 0; f < F; ++f) {
+      if (!sRej[2 * f]) continue;
+      for (int n = tid; n < gt.Np; n += 256) { PHT[n + (long)(2 * f) * gt.ldpht] = 0.0; PHT[n + (long)(2 * f + 1) * gt.ldpht] = 0.0; }
+    }
+    __syncthreads();                                      // sRow is scratch no longer
+  }
+  // element (row, col) of S as the gate leaves it: rows / columns of rejected pairs decoupled (gate_ell_body's in-place edit)
+  auto gated = [&](double v, int row, int col) -> double {
+    if constexpr (GATE) return (sRej[row] | sRej[col]) ? (row == col ? 1.0 : 0.0) : v;
+    else return v;
+  };
+
+  // the wave that owns block row c (slot s): diagonal update from its registers, factor + invert (64-lane layout
+  // x[r] = X[row li][col lg + 4 r] - what the accumulators of the symmetric update already are), L_cc and inv(L_cc) out,
+  // inv(L_cc) and the row panel L_ck, k < c, published in LDS buffer `buf`
+  auto factor_publish = [&](auto sc, auto cc, const int buf) {
+    constexpr int s = decltype(sc)::value, c = decltype(cc)::value;
+    d4 acc0 = d4{0.0, 0.0, 0.0, 0.0}, acc1 = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < c; ++k) {
+      const d4 a = L[s][k];
+      acc0 = mfma(a[0], a[0], acc0);
+      acc1 = mfma(a[1], a[1], acc1);
+      acc0 = mfma(a[2], a[2], acc0);
+      acc1 = mfma(a[3], a[3], acc1);
+    }
+    d4 x, y;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) x[r] = gated(xd[r], 16 * c + li, 16 * c + lg + 4 * r) - (acc0[r] + acc1[r]);
+    // the row panel goes out BEFORE the factorisation: block row c is finished with it, and its registers are free
+    // for the longest straight-line stretch of the kernel (their live range is ended below)
+#pragma unroll
+    for (int k = 0; k < c; ++k) *reinterpret_cast<d4*>(&sRow[buf][(k * 64 + lane) * 4]) = L[s][k];
+    int bad = 0;
+    factor_invert_diag(x, y, bad, 16 * c, li, lg);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int cl = lg + 4 * r;
+      if (cl <= li) {
+        S[(16 * c + li) + (long)(16 * c + cl) * ld] = x[r];
+        S[(16 * c + cl) + (long)(16 * c + li) * ld] = x[r];
+      }
+      sInv[buf][0][cl + li * 16] = y[r];   // inv(L)(cl, li)
+      sInv[buf][1][li + cl * 16] = y[r];   // inv(L)^T(li, cl)
+    }
+    if (bad && lane == 0 && sBad == 0) sBad = bad;
+    // this wave's row in slot s is done. The slot's registers hold the rows of the other three waves, which are not here, so
+    // the allocator would carry them through the factorisation above: an empty definition tells it that it need not
+#pragma unroll
+    for (int k = 0; k < c; ++k) asm volatile("" : "=v"(L[s][k]));
+  };
+  // block (i, j) of L, i in slot ii of this wave: L_ij^T = inv(L_jj) (S_ij^T - sum_k L_jk L_ik^T), kept + stored
+  auto panel_block = [&](auto iic, auto jc, const int buf, const int i) {
+    constexpr int ii = decltype(iic)::value, j = decltype(jc)::value;
+    d4 accA = d4{0.0, 0.0, 0.0, 0.0}, accB = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < j; ++k) {
+      const d4 a = *reinterpret_cast<const d4*>(&sRow[buf][(k * 64 + lane) * 4]);
+      const d4 bb = L[ii][k];
+      accA = mfma(a[0], bb[0], accA);
+      accB = mfma(a[1], bb[1], accB);
+      accA = mfma(a[2], bb[2], accA);
+      accB = mfma(a[3], bb[3], accB);
+    }
+    d4 rhs;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) rhs[r] = gated(L[ii][j][r], 16 * i + li, 16 * j + lg + 4 * r) - (accA[r] + accB[r]);
+    d4 out = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) out = mfma(sInv[buf][0][li + (4 * s4 + lg) * 16], rhs[s4], out);
+    L[ii][j] = out;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      S[(16 * i + li) + (long)(16 * j + lg + 4 * r) * ld] = out[r];                 // L(i-block, j-block)
+      if (mirror) S[(16 * j + lg + 4 * r) + (long)(16 * i + li) * ld] = out[r];     // L^T for the streamed solve
+    }
+  };
+
+  if (wave == owner0) factor_publish(std::integral_constant<int, (NB - 1) / 4>{}, std::integral_constant<int, 0>{}, 0);
+  lds_barrier();
+  // compile-time column index: every L[][] subscript below is a constant, so the factor stays in registers
+  static_for<NB>([&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+    if (j < nb) {
+      constexpr int buf = j & 1;
+      if constexpr (j + 1 < NB) {
+        constexpr int nxt = (NB - 2 - j) % 4, sn = (NB - 2 - j) / 4;   // block row j + 1: the look-ahead
+        if (j + 1 < nb && wave == nxt) {
+          panel_block(std::integral_constant<int, sn>{}, jc, buf, j + 1);
+          factor_publish(std::integral_constant<int, sn>{}, std::integral_constant<int, j + 1>{}, buf ^ 1);
+        }
+        // (behind the look-ahead, so that its factorisation does not hold the landing blocks: the other three waves, the
+        // next look-ahead wave among them, skip it and are here at once)
+        request(std::integral_constant<int, j + 1>{});
+      }
+      static_for<RW>([&](auto iic) {
+        constexpr int ii = decltype(iic)::value, top = NB - 1 - 4 * ii;
+        if constexpr (top > j + 1) {
+          const int i = top - wave;
+          if (i > j + 1 && i < nb) panel_block(iic, jc, buf, i);
+        }
+      });
+      if (wave == (NB - 1 - j) % 4)   // (before the barrier: the next column's look-ahead rewrites this buffer)
+        for (int e = lane; e < 512; e += 64) invD[(long)j * 512 + e] = (&sInv[buf][0][0])[e];
+      lds_barrier();
+    }
+  });
+  if (tid == 0) g.status[filt] = sBad;
+}
+
 }  // namespace
 
 // XIVO_HIP_CHOL_WAVE (A/B, and the bit-identity test of the two factorisation kernels): the one-wave kernel for every size
 static bool chol_one_wave_forced() { static const bool on = getenv("XIVO_HIP_CHOL_WAVE") != nullptr; return on; }
 // the instantiation of the four-wave register kernel a (size, batch) takes - ONE place decides it, for the launcher, the gate
-// and the label alike: mode 0 = many factors (three workgroups per CU at >= nine block rows, blocks of S requested per block
-// column, no look-ahead: the only instantiations that carry the gate), mode 2 = few factors (two workgroups per CU, every
-// block of S requested up front, look-ahead on the diagonal update)
+// and the label alike: mode 0 = many factors (chol_reg_la_f64_kernel: three workgroups per CU at >= nine block rows, blocks of
+// S requested one block column ahead, look-ahead over the diagonal blocks: the only instantiations that carry the gate),
+// mode 2 = few factors (chol_reg_f64_kernel: two workgroups per CU, every block of S requested up front, look-ahead on the
+// diagonal update)
 static int chol_reg_mode(int batch) { return batch >= 512 ? 0 : 2; }
 
 // whether launch_chol_f64 would run an instantiation that carries the gate for this factor size / batch
@@ -363,27 +536,26 @@ int launch_chol_f64(const CholArgs& g, hipStream_t stream, const CholGateArgs* g
   // was ~45 000: 170-200 KB of straight-line code that lost 2.6x on nodes with slow instruction fetch) and is the
   // default for every batch size it holds; the k-slice loop of that step then brought it to 42 KB. Measured at
   // M = 160: one factor 48-52 us (round 2: 80), 16384 factors 1.6-1.7 ms (register kernel, three workgroups per CU, no
-  // look-ahead) against 2.4-2.6 ms for the one-wave kernel and 2.3-2.4 ms for either kernel before. Thirteen to nineteen
-  // block rows run the same kernel on eight waves (below); the one-wave kernel serves what is left (M > 304).
+  // look-ahead) against 2.4-2.6 ms for the one-wave kernel and 2.3-2.4 ms for either kernel before; 1.88 -> 1.46 ms with
+  // the gate in the prologue once the many-factors kernel ran without scratch and with look-ahead
+  // (profiles/chol_lookahead_ab.json). Thirteen to nineteen block rows run the register kernel on eight waves (below); the
+  // one-wave kernel serves what is left (M > 304).
   // Every instantiation produces the same bits (tests/test_update_gpu.py::test_cholesky_kernels_are_bit_identical).
   if (!chol_one_wave_forced() && nb <= 12) {
     const int mirror = (nb > 10 || g.latency) ? 1 : 0;   // the streamed solve reads the mirrored upper triangle: nb >= 12, and nb = 11 when the
                                                          // whitened outputs leave the kernel (launch_trsm_f64)
-    const bool many = g.batch >= 512;
     const int mode = chol_reg_mode(g.batch);
     if (gate && mode != 0) return (int)hipErrorInvalidValue;   // (only the mode-0 instantiations carry the gate)
 #define CHOL_REG_LAUNCH(NB_, MINB_)                                                                                                     \
   do {                                                                                                                                  \
-    if (mode == 0 && gate) hipLaunchKernelGGL((chol_reg_f64_kernel<NB_, MINB_, false, false, 4, true>), dim3(g.batch), dim3(256), 0, stream, g, mirror, *gate); \
-    else if (mode == 0) hipLaunchKernelGGL((chol_reg_f64_kernel<NB_, MINB_, false, false>), dim3(g.batch), dim3(256), 0, stream, g, mirror, nogate);   \
-    else hipLaunchKernelGGL((chol_reg_f64_kernel<NB_, MINB_, true, true>), dim3(g.batch), dim3(256), 0, stream, g, mirror, nogate);             \
+    if (mode == 0 && gate) hipLaunchKernelGGL((chol_reg_la_f64_kernel<NB_, MINB_, true>), dim3(g.batch), dim3(256), 0, stream, g, mirror, *gate); \
+    else if (mode == 0) hipLaunchKernelGGL((chol_reg_la_f64_kernel<NB_, MINB_, false>), dim3(g.batch), dim3(256), 0, stream, g, mirror, nogate);  \
+    else hipLaunchKernelGGL((chol_reg_f64_kernel<NB_, 2, true, true>), dim3(g.batch), dim3(256), 0, stream, g, mirror);                            \
   } while (0)
     if (nb <= 4) CHOL_REG_LAUNCH(4, 2);
     else if (nb <= 8) CHOL_REG_LAUNCH(8, 2);
-    else if (nb <= 10 && many) CHOL_REG_LAUNCH(10, 3);
-    else if (nb <= 10) CHOL_REG_LAUNCH(10, 2);
-    else if (many) CHOL_REG_LAUNCH(12, 3);
-    else CHOL_REG_LAUNCH(12, 2);
+    else if (nb <= 10) CHOL_REG_LAUNCH(10, 3);   // (MINB_ is the many-factors cut: mode 0 <=> batch >= 512; few factors run at two per CU)
+    else CHOL_REG_LAUNCH(12, 3);
 #undef CHOL_REG_LAUNCH
     return (int)hipGetLastError();
   }
@@ -395,11 +567,11 @@ int launch_chol_f64(const CholArgs& g, hipStream_t stream, const CholGateArgs* g
     const int mirror = 1;
     const bool pre = g.batch < 512;
     if (nb <= 16) {
-      if (pre) hipLaunchKernelGGL((chol_reg_f64_kernel<16, 1, true, false, 8>), dim3(g.batch), dim3(512), 0, stream, g, mirror, nogate);
-      else hipLaunchKernelGGL((chol_reg_f64_kernel<16, 1, false, false, 8>), dim3(g.batch), dim3(512), 0, stream, g, mirror, nogate);
+      if (pre) hipLaunchKernelGGL((chol_reg_f64_kernel<16, 1, true, false, 8>), dim3(g.batch), dim3(512), 0, stream, g, mirror);
+      else hipLaunchKernelGGL((chol_reg_f64_kernel<16, 1, false, false, 8>), dim3(g.batch), dim3(512), 0, stream, g, mirror);
     } else {
-      if (pre) hipLaunchKernelGGL((chol_reg_f64_kernel<19, 1, true, false, 8>), dim3(g.batch), dim3(512), 0, stream, g, mirror, nogate);
-      else hipLaunchKernelGGL((chol_reg_f64_kernel<19, 1, false, false, 8>), dim3(g.batch), dim3(512), 0, stream, g, mirror, nogate);
+      if (pre) hipLaunchKernelGGL((chol_reg_f64_kernel<19, 1, true, false, 8>), dim3(g.batch), dim3(512), 0, stream, g, mirror);
+      else hipLaunchKernelGGL((chol_reg_f64_kernel<19, 1, false, false, 8>), dim3(g.batch), dim3(512), 0, stream, g, mirror);
     }
     return (int)hipGetLastError();
   }
@@ -412,7 +584,7 @@ void chol_kernel_label(int Mp, int batch, char* buf, size_t n) {
   const bool reg8 = nb > 12 && nb <= 19;
   if (chol_one_wave_forced() || (nb > 12 && !reg8)) snprintf(buf, n, "chol_f64_kernel");
   else if (reg8) snprintf(buf, n, "chol_reg_f64_kernel<%d,1,8 waves>", nb <= 16 ? 16 : 19);
-  else snprintf(buf, n, "chol_reg_f64_kernel<%d,%d>", nb <= 4 ? 4 : (nb <= 8 ? 8 : (nb <= 10 ? 10 : 12)), (nb > 8 && batch >= 512) ? 3 : 2);
+  else snprintf(buf, n, "%s<%d,%d>", chol_reg_mode(batch) == 0 ? "chol_reg_la_f64_kernel" : "chol_reg_f64_kernel", nb <= 4 ? 4 : (nb <= 8 ? 8 : (nb <= 10 ? 10 : 12)), (nb > 8 && batch >= 512) ? 3 : 2);
 }
 
 }  // namespace xivo_hip
