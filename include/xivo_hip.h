@@ -1247,7 +1247,7 @@ int xivo_hip_trajsim_reset(xivo_hip_ctx* ctx);   /* empties the log (and forgets
  * What stands in for what: `key` is the caller's stand-in for the descriptor word - two observations with the same
  * non-negative key are the mapper's descriptor match at distance 0 (a point-cloud world supplies its world-point index, a
  * front end its own match id; a negative key matches nothing); a chi-square gate of every match on the filter's own
- * covariance stands in for pnp_ransac's inlier test. The stored point is treated as exact, as the reference treats it. No
+ * covariance stands in for pnp_ransac's inlier test. The stored point is treated as exact, as the reference treats it (xivo_hip_lcmap_cov_config gives it a covariance). No
  * merging (merge_features = false, mapper.cpp:189-191: the first estimate of a point is kept), no eviction, no pose graph.
  * Off until configured; refused on a context with online calibration. */
 #define XIVO_LCMAP_MAX_ENTRIES 4096
@@ -1269,7 +1269,7 @@ typedef struct {
   int group_sind;   /* the query's */
   double xp[2];     /* the query's */
   double gamma;     /* r^T (H P H^T + Rlc I)^-1 r of the pair; -1 where a pivot was not positive */
-  int kept, reserved;
+  int kept, reserved;   /* reserved: 1 where the match rested (xivo_hip_lcmap_cov_config, revisit_gap), else 0 */
 } xivo_lcmap_match;
 typedef struct {
   long long added, dup, full, poor, skipped;   /* add records by outcome */
@@ -1303,6 +1303,39 @@ int xivo_hip_lcmap_get(xivo_hip_ctx* ctx, int b0, int nb, xivo_lcmap_entry* entr
 /* the match lists of the last close call: host [nb][lc_max]; kept and gamma are valid where entry >= 0 */
 int xivo_hip_lcmap_get_matches(xivo_hip_ctx* ctx, int b0, int nb, xivo_lcmap_match* matches);
 int xivo_hip_lcmap_get_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_lcmap_stats* stats);
+/* Two options on top of a configured map, both off until this call and independent of each other (the structs above keep their
+ * sizes: what the options need lives in arrays of its own, next to the entries).
+ * point_cov = 1: every entry carries the covariance Sigma of its world point, packed (0,0),(0,1),(0,2),(1,1),(1,2),(2,2) like
+ * xivo_map_pt's cov_world. xivo_hip_lcmap_add stores Sigma = J Pcc J^T of an accepted record (J = dXs / d error state over
+ * the 15 columns Wbc, Tbc, the anchor group's six and the feature's three, Pcc gathered from the lower triangle of P and
+ * mirrored: the arithmetic of the landmark log's cov_world); xivo_hip_lcmap_set zeroes it for the filters it loads. The close
+ * call then weighs a match with R_e = Rlc I + H_T Sigma H_T^T, H_T the pair's block for Tsb (d xp / d Xs = -H_T): gamma is
+ * r^T (H P H^T + R_e)^-1 r, a match whose R_e has a non-positive pivot is not kept (gamma = -1, counted in bad_cov and in
+ * gated), and a pair that takes part is whitened - R_e = L L^T, rows and innovation <- L^-1 times themselves, diagR = 1 - so
+ * that the update calls run as they are. No cross-covariance between a stored point and the state is kept.
+ * revisit_gap > 0: an entry closes the loop once per visit. Every entry keeps {last_seen, used}; t numbers the close calls
+ * since this call, from 1. used_now = (last_seen > 0 && t - last_seen <= revisit_gap) ? used : 0, and a match whose entry is
+ * used_now rests: it takes its list position, gets its rows and its gate, a kept one counts towards min_matches (it verifies
+ * the place), but its pair is neutral and xivo_lcmap_match.reserved is 1. A frame with min_matches kept matches all of which
+ * rest does not close (rested_frames; closing = 0). After the decision every matched entry gets last_seen = t and
+ * used = used_now || (the frame closed and the match was kept and did not rest); a key that fills two list positions in one
+ * call is used if either position used it, both having seen the state from before the call.
+ * Both zero: releases the arrays, every entry point behaves as before this call. Entries already in the map get Sigma = 0 and
+ * "never seen". Zeroes the counters below and t. XIVO_HIP_ERR_INVALID: no configured map, a wrong struct_size, point_cov
+ * outside {0, 1}, a negative gap. xivo_hip_lcmap_config (a new configuration or a release) drops these options too. */
+typedef struct { int struct_size; int point_cov; int revisit_gap; int reserved; } xivo_lcmap_cov_opts;
+typedef struct {
+  long long resting;         /* kept matches that rested */
+  long long rested_frames;   /* frames with min_matches kept matches, every one resting */
+  long long bad_cov;         /* matches not kept because a pivot of R_e was not positive */
+} xivo_lcmap_cov_stats;
+int xivo_hip_lcmap_cov_config(xivo_hip_ctx* ctx, const xivo_lcmap_cov_opts* opts);
+/* Sigma of filters [b0, b0 + nb): host [nb][map_max][6]. set refuses non-finite values and negative diagonal entries
+ * (XIVO_HIP_ERR_INVALID, nothing changed) and stores everything else as given: whether R_e is definite is the close call's
+ * pivot test. Both return XIVO_HIP_ERR_INVALID without point_cov, xivo_hip_lcmap_get_cov_stats while both options are off. */
+int xivo_hip_lcmap_set_cov(xivo_hip_ctx* ctx, int b0, int nb, const double* cov);
+int xivo_hip_lcmap_get_cov(xivo_hip_ctx* ctx, int b0, int nb, double* cov);
+int xivo_hip_lcmap_get_cov_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_lcmap_cov_stats* stats);
 
 /* ---- covariance propagation tail (src/rk4.cpp:92-102, src/estimator.cpp:590) */
 /* P_mm <- Pmm_new ; P_ms <- Phi P_ms ; P_sm <- P_sm Phi^T. Phi and Pmm_new

@@ -117,6 +117,12 @@ def main():
     ap.add_argument("-lc-chi2", dest="lc_chi2", type=float, default=d.lc_chi2, help="-loop-closure: gate of one match (0: none)")
     ap.add_argument("-lc-max-depth-var", dest="lc_max_depth_var", type=float, default=d.lc_max_depth_var,
                     help="-loop-closure: a feature whose depth variance is above this when it leaves is not stored (0: no test)")
+    ap.add_argument("-lc-point-cov", dest="lc_point_cov", action="store_true",
+                    help="-loop-closure: a stored point carries the covariance it left the state with and its matches are weighed "
+                         "with it (SequenceConfig.lc_point_cov); the report gains lcmap_resting / _rested_frames / _bad_cov")
+    ap.add_argument("-lc-revisit-gap", dest="lc_revisit_gap", type=int, default=d.lc_revisit_gap,
+                    help="-loop-closure: N > 0 - a stored point closes the loop once per visit, a visit ending after N frames "
+                         "without a match of it (SequenceConfig.lc_revisit_gap); 0: in every frame it is seen")
     a = ap.parse_args()
     # (a sequence never brings more tracks than its world has points)
     life = dict(lifecycle=a.lifecycle, tracks_max=min(a.npts, sequence.L.LIFE_MAX_TRACKS))
@@ -152,7 +158,7 @@ def main():
             ap.error("-loop-closure and -innov-log exclude each other (the log holds one update per frame)")
         life.update(feature_init=a.feature_init, pool_lifecycle=a.pool_lifecycle, loop_closure=True, lc_map_max=a.lc_map_max,
                     lc_max=a.lc_max, lc_min_matches=a.lc_min_matches, lc_meas_std=a.lc_meas_std, lc_chi2=a.lc_chi2,
-                    lc_max_depth_var=a.lc_max_depth_var)
+                    lc_max_depth_var=a.lc_max_depth_var, lc_point_cov=bool(a.lc_point_cov), lc_revisit_gap=a.lc_revisit_gap)
         try:
             sequence.check_lifecycle(sequence.SequenceConfig(**life))
         except ValueError as e:
@@ -252,6 +258,8 @@ def main():
             if lc_st is not None:     # the map counters summed over the sequences, and in how many a loop was closed at all
                 oos = dict(oos, **{"lcmap_" + k: int(lc_st[k].sum()) for k in lc_st.dtype.names},
                            lcmap_sequences_with_closed=int((lc_st["closed_frames"] > 0).sum()))
+                if out.get("lcmap_cov_stats") is not None:
+                    oos = dict(oos, **{"lcmap_" + k: int(out["lcmap_cov_stats"][k].sum()) for k in out["lcmap_cov_stats"].dtype.names})
         out["runner"] = _R
         out["backend"].close()
     wall = time.perf_counter() - t0
@@ -280,6 +288,7 @@ def main():
         "lifecycle": a.lifecycle, "tracks": a.tracks, "feature_init": a.feature_init, "pool_lifecycle": a.pool_lifecycle,
         "cam_model": a.cam_model,
         "loop_closure": bool(a.loop_closure),
+        **({"lc_point_cov": bool(a.lc_point_cov), "lc_revisit_gap": a.lc_revisit_gap} if a.loop_closure else {}),
         "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
         **_consistency(out),
         "updates": n_upd, "mh_rejected": n_rej, **oos,

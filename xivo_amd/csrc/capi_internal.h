@@ -288,11 +288,16 @@ struct InnovLog {
 
 // resident landmark map (xivo_hip_lcmap_*, capi_lcmap.hip): entries [Bmax][map_max], count [Bmax], the counters [Bmax], the
 // last close call's match lists [Bmax][lc_max] and closing flags [Bmax]; io: the device block a call's records / queries and
-// offsets are uploaded to, up: its page-locked staging (both only ever grow, up_cap bytes each)
+// offsets are uploaded to, up: its page-locked staging (both only ever grow, up_cap bytes each). xivo_hip_lcmap_cov_config's
+// options: cov [Bmax][map_max][6] while point_cov is on, visit [Bmax][map_max][2] = {last_seen, used} while revisit_gap > 0,
+// their counters [Bmax] while either is; t: close calls since that configuration
 struct LcMap {
   xivo_lcmap_opts opts{};
   xivo_lcmap_entry* entries = nullptr; int* count = nullptr; xivo_lcmap_stats* stats = nullptr;
   xivo_lcmap_match* matches = nullptr; int* closing = nullptr;
+  xivo_lcmap_cov_opts cov_opts{};
+  double* cov = nullptr; int* visit = nullptr; xivo_lcmap_cov_stats* cov_stats = nullptr;
+  int t = 0;
   char* io = nullptr; size_t io_cap = 0;
   PinnedUpload up; size_t up_cap = 0;
   bool configured() const { return entries != nullptr; }

@@ -13,13 +13,19 @@ namespace {
 
 void lcmap_release(xivo_hip_ctx* c) {   // (the stream must be idle; the staging blocks stay: they are no part of a configuration)
   LcMap& m = c->lcmap;
-  c->mem.release(&m.entries, &m.count, &m.stats, &m.matches, &m.closing);
+  c->mem.release(&m.entries, &m.count, &m.stats, &m.matches, &m.closing, &m.cov, &m.visit, &m.cov_stats);
   m.opts = xivo_lcmap_opts{};
+  m.cov_opts = xivo_lcmap_cov_opts{}; m.t = 0;
 }
 
 LcMapBuffers map_buffers(xivo_hip_ctx* c) {
   const LcMap& m = c->lcmap;
   return LcMapBuffers{m.entries, m.count, m.stats, m.opts.map_max};
+}
+// (all null without xivo_hip_lcmap_cov_config: the kernels' first instantiation runs)
+LcMapCovBuffers cov_buffers(xivo_hip_ctx* c) {
+  const LcMap& m = c->lcmap;
+  return LcMapCovBuffers{m.cov, m.visit, m.cov_stats, m.cov_opts.revisit_gap, m.t};
 }
 
 // a call's records (rec_bytes of them) and the offsets off [B + 1] of every filter's share, through the page-locked staging to
@@ -100,7 +106,7 @@ int xivo_hip_lcmap_add(xivo_hip_ctx* c, int B, int n, const xivo_lcmap_add_rec* 
   LcMapAddArgs a{};
   const char* d_recs = nullptr;
   if (int rc = upload_call(c, recs, (size_t)n * sizeof(xivo_lcmap_add_rec), off, &d_recs, &a.off)) return rc;
-  a.map = map_buffers(c); a.recs = reinterpret_cast<const xivo_lcmap_add_rec*>(d_recs);
+  a.map = map_buffers(c); a.ext = cov_buffers(c); a.recs = reinterpret_cast<const xivo_lcmap_add_rec*>(d_recs);
   a.poses = c->poses; a.groups = c->groups; a.feats = c->feats; a.Fmax = c->Fmax; a.F = c->F;
   a.lay = c->lay; a.invdepth = (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0;
   c->P.to(a.P, a.strideP, a.ldp);
@@ -132,7 +138,8 @@ int xivo_hip_lcmap_close(xivo_hip_ctx* c, int B, int n, const xivo_lcmap_query* 
   if (int rc = upload_call(c, queries, (size_t)n * sizeof(xivo_lcmap_query), off, &d_q, &a.off)) return rc;
   char* base = c->lc_buf;
   HIP_TRY(hipMemsetAsync(base + o_H, 0, (size_t)B * M * N * sizeof(double), c->stream));   // H_.setZero(2n, N) (update.cpp:184)
-  a.map = map_buffers(c); a.queries = reinterpret_cast<const xivo_lcmap_query*>(d_q);
+  c->lcmap.t += 1;   // (a call that stages nothing below is a call all the same)
+  a.map = map_buffers(c); a.ext = cov_buffers(c); a.queries = reinterpret_cast<const xivo_lcmap_query*>(d_q);
   a.poses = c->poses; a.groups = c->groups; a.lay = c->lay; a.cam = c->cam; a.cl = xivo_calib_layout{-1, -1, 0, 0};
   c->P.to(a.P, a.strideP, a.ldp);
   a.H = reinterpret_cast<double*>(base + o_H); a.strideH = (long)M * N; a.ldh = M;
@@ -170,6 +177,9 @@ int xivo_hip_lcmap_set(xivo_hip_ctx* c, int b0, int nb, const xivo_lcmap_entry* 
   }
   HIP_TRY(hipMemcpyAsync(c->lcmap.entries + b0 * mm, entries, nb * mm * sizeof(xivo_lcmap_entry), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->lcmap.count + b0, count, (size_t)nb * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  // a loaded map: exact points until xivo_hip_lcmap_set_cov says otherwise, never seen
+  if (c->lcmap.cov) HIP_TRY(hipMemsetAsync(c->lcmap.cov + b0 * mm * 6, 0, nb * mm * 6 * sizeof(double), c->stream));
+  if (c->lcmap.visit) HIP_TRY(hipMemsetAsync(c->lcmap.visit + b0 * mm * 2, 0, nb * mm * 2 * sizeof(int), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));   // entries / count are borrowed host memory
   return XIVO_HIP_OK;
 }
@@ -200,6 +210,58 @@ int xivo_hip_lcmap_get_stats(xivo_hip_ctx* c, int b0, int nb, xivo_lcmap_stats* 
   if (bad_range(c, b0, nb) || !c->lcmap.configured() || (nb > 0 && !out)) return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
   HIP_TRY(hipMemcpyAsync(out, c->lcmap.stats + b0, (size_t)nb * sizeof(xivo_lcmap_stats), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_lcmap_cov_config(xivo_hip_ctx* c, const xivo_lcmap_cov_opts* o) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || !c->lcmap.configured() || !o || o->struct_size != (int)sizeof(xivo_lcmap_cov_opts) || (o->point_cov != 0 && o->point_cov != 1) ||
+      o->revisit_gap < 0)
+    return XIVO_HIP_ERR_INVALID;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  LcMap& m = c->lcmap;
+  c->mem.release(&m.cov, &m.visit, &m.cov_stats);
+  m.cov_opts = xivo_lcmap_cov_opts{}; m.t = 0;
+  if (!o->point_cov && o->revisit_gap == 0) return XIVO_HIP_OK;
+  const size_t B = (size_t)c->Bmax, ne = B * m.opts.map_max;
+  int rc = c->mem.zeroed(&m.cov_stats, B);
+  if (!rc && o->point_cov) rc = c->mem.zeroed(&m.cov, ne * 6);
+  if (!rc && o->revisit_gap > 0) rc = c->mem.zeroed(&m.visit, ne * 2);
+  if (rc) { c->mem.release(&m.cov, &m.visit, &m.cov_stats); return rc; }
+  m.cov_opts = *o;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_lcmap_set_cov(xivo_hip_ctx* c, int b0, int nb, const double* cov) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->lcmap.cov || (nb > 0 && !cov)) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  const size_t per = (size_t)c->lcmap.opts.map_max * 6, n = (size_t)nb * per;
+  for (size_t i = 0; i < n; ++i) {
+    const size_t k = i % 6;
+    if (!std::isfinite(cov[i]) || ((k == 0 || k == 3 || k == 5) && cov[i] < 0.0)) return XIVO_HIP_ERR_INVALID;
+  }
+  HIP_TRY(hipMemcpyAsync(c->lcmap.cov + b0 * per, cov, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // cov is borrowed host memory
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_lcmap_get_cov(xivo_hip_ctx* c, int b0, int nb, double* cov) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->lcmap.cov || (nb > 0 && !cov)) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  const size_t per = (size_t)c->lcmap.opts.map_max * 6;
+  HIP_TRY(hipMemcpyAsync(cov, c->lcmap.cov + b0 * per, (size_t)nb * per * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_lcmap_get_cov_stats(xivo_hip_ctx* c, int b0, int nb, xivo_lcmap_cov_stats* out) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->lcmap.cov_stats || (nb > 0 && !out)) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  HIP_TRY(hipMemcpyAsync(out, c->lcmap.cov_stats + b0, (size_t)nb * sizeof(xivo_lcmap_cov_stats), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return XIVO_HIP_OK;
 }

@@ -309,6 +309,13 @@ int launch_lc_rows(const LcArgs& a, hipStream_t s);
 struct LcMapBuffers {
   xivo_lcmap_entry* entries; int* count; xivo_lcmap_stats* stats; int map_max;
 };
+// what xivo_hip_lcmap_cov_config adds, parallel to the entries: cov [batch][map_max][6] (null: the points are exact), visit
+// [batch][map_max] {last_seen, used} (null: gap = 0), the counters [batch]; t: the number of this close call. on(): either
+// option is set - the launchers then take the kernels' second instantiation, else the first, which never reads this
+struct LcMapCovBuffers {
+  double* cov; int* visit; xivo_lcmap_cov_stats* stats; int gap, t;
+  bool on() const { return cov != nullptr || visit != nullptr; }
+};
 // add: the records of filter b are recs[off[b], off[b + 1])
 struct LcMapAddArgs {
   LcMapBuffers map;
@@ -317,6 +324,7 @@ struct LcMapAddArgs {
   xivo_layout lay; int invdepth;
   const double* P; long strideP; int ldp;
   double max_depth_var; int batch;
+  LcMapCovBuffers ext;   // (last: the arguments before it keep their places)
 };
 int launch_lcmap_add(const LcMapAddArgs& a, hipStream_t s);
 // close: match, rows, verify. The queries of filter b are queries[off[b], off[b + 1]); H [batch] 2 lc_max x N zero-filled
@@ -334,6 +342,7 @@ struct LcMapCloseArgs {
   xivo_lcmap_match* matches;   // [batch][lc_max]
   int* closing;                // [batch] 1: the filter closes
   int lc_max, min_matches; double Rlc, chi2; int batch;
+  LcMapCovBuffers ext;         // (last: the arguments before it keep their places)
 };
 int launch_lcmap_close(const LcMapCloseArgs& a, hipStream_t s);
 

@@ -55,4 +55,24 @@ LCMAP_HD int lcmap_pair_neutral(int frame, int m, int n_matched, int kept) {
   return frame != LCMAP_FRAME_CLOSED || m >= n_matched || !kept;
 }
 
+// ---- one use per visit (xivo_hip_lcmap_cov_config, revisit_gap): an entry keeps {last_seen, used}, t numbers the close
+// calls from 1. With gap = 0 nothing ever rests and the three rules below are the two above.
+enum { LCMAP_FRAME_RESTED = 3 };
+// has the entry closed a loop in the visit that call t falls into? A visit ends after gap calls without a match of the entry:
+// t - last_seen == gap is still the same visit, gap + 1 a new one; last_seen = 0 is "never seen"
+LCMAP_HD int lcmap_used_now(int last_seen, int used, int t, int gap) { return (last_seen > 0 && t - last_seen <= gap) ? used : 0; }
+LCMAP_HD int lcmap_resting(int gap, int used_now) { return gap > 0 && used_now; }
+// n_kept counts the resting matches too (they verify the place), n_fresh the kept ones that do not rest
+LCMAP_HD int lcmap_frame_decide_visit(int n_matched, int n_kept, int n_fresh, int min_matches) {
+  const int frame = lcmap_frame_decide(n_matched, n_kept, min_matches);
+  return frame == LCMAP_FRAME_CLOSED && n_fresh == 0 ? LCMAP_FRAME_RESTED : frame;
+}
+LCMAP_HD int lcmap_pair_neutral_visit(int frame, int m, int n_matched, int kept, int resting) {
+  return lcmap_pair_neutral(frame, m, n_matched, kept) || resting;
+}
+// `used` of a matched entry after the call (its last_seen becomes t)
+LCMAP_HD int lcmap_used_next(int used_now, int frame, int kept, int resting) {
+  return used_now || (frame == LCMAP_FRAME_CLOSED && kept && !resting);
+}
+
 }  // namespace xivo_hip

@@ -161,6 +161,11 @@ LCMAP_STATS_FIELDS = ("added", "dup", "full", "poor", "skipped", "queries", "mat
 lcmap_stats_dtype = np.dtype([(k, "i8") for k in LCMAP_STATS_FIELDS])
 assert (lcmap_opts_dtype.itemsize, lcmap_entry_dtype.itemsize, lcmap_add_dtype.itemsize, lcmap_query_dtype.itemsize,
         lcmap_match_dtype.itemsize, lcmap_stats_dtype.itemsize) == (40, 32, 16, 32, 40, 88)
+# its options on top (xivo_hip_lcmap_cov_config): xivo_lcmap_cov_opts, _cov_stats
+lcmap_cov_opts_dtype = np.dtype([("struct_size", "i4"), ("point_cov", "i4"), ("revisit_gap", "i4"), ("reserved", "i4")])
+LCMAP_COV_STATS_FIELDS = ("resting", "rested_frames", "bad_cov")
+lcmap_cov_stats_dtype = np.dtype([(k, "i8") for k in LCMAP_COV_STATS_FIELDS])
+assert (lcmap_cov_opts_dtype.itemsize, lcmap_cov_stats_dtype.itemsize) == (16, 24)
 LCMAP_MAX_ENTRIES, LCMAP_MAX_MATCHES = 4096, 64
 CHI2_2DOF_95 = 5.991464547107979   # -2 ln 0.05: the 95 % point of chi-square with 2 degrees of freedom
 # 2k - 3 projected rows (tests/test_pool_oos_cpu.py holds the table against scipy.stats.chi2.ppf)
@@ -329,6 +334,10 @@ _SIGS = {
     "xivo_hip_lcmap_get": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "xivo_hip_lcmap_get_matches": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_lcmap_get_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_lcmap_cov_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_lcmap_set_cov": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_lcmap_get_cov": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_lcmap_get_cov_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_pcw_config": [C.c_void_p, C.c_void_p],
     "xivo_hip_pcw_set_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_pcw_get_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
@@ -1446,6 +1455,35 @@ class Context:
         nb = self.batch - b0 if nb is None else int(nb)
         out = np.zeros(nb, dtype=lcmap_stats_dtype)
         self._check(self.lib.xivo_hip_lcmap_get_stats(self.h, int(b0), nb, _ptr(out)))
+        return out
+
+    def lcmap_cov_config(self, point_cov=False, revisit_gap=0):
+        """the map's two options (xivo_hip_lcmap_cov_config, after lcmap_config): point_cov - every entry carries the covariance
+        of its point, which weighs its matches; revisit_gap > 0 - an entry closes the loop once per visit, a visit ending after
+        that many close calls without a match of it. Both off: releases, the map behaves as without this call"""
+        o = np.zeros(1, dtype=lcmap_cov_opts_dtype)
+        o["struct_size"] = lcmap_cov_opts_dtype.itemsize
+        o["point_cov"] = int(point_cov); o["revisit_gap"] = int(revisit_gap)
+        self._check(self.lib.xivo_hip_lcmap_cov_config(self.h, _ptr(o)))
+
+    def lcmap_set_cov(self, cov, b0=0):
+        """the points' covariances of whole maps: cov [nb, map_max, 6], packed (0,0),(0,1),(0,2),(1,1),(1,2),(2,2)"""
+        cov = _f64(cov)
+        assert cov.ndim == 3 and cov.shape[1:] == (self.lcmap_max, 6)
+        self._check(self.lib.xivo_hip_lcmap_set_cov(self.h, int(b0), len(cov), _ptr(cov)))
+
+    def lcmap_get_cov(self, b0=0, nb=None):
+        """-> [nb, map_max, 6]; one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        out = np.zeros((nb, self.lcmap_max, 6))
+        self._check(self.lib.xivo_hip_lcmap_get_cov(self.h, int(b0), nb, _ptr(out)))
+        return out
+
+    def lcmap_cov_stats(self, b0=0, nb=None):
+        """-> [nb] lcmap_cov_stats_dtype: the counters of the two options; one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        out = np.zeros(nb, dtype=lcmap_cov_stats_dtype)
+        self._check(self.lib.xivo_hip_lcmap_get_cov_stats(self.h, int(b0), nb, _ptr(out)))
         return out
 
     def propagate_cov(self, Phi, Pmm, b0=0):

@@ -217,6 +217,10 @@ class SequenceConfig:
         self.loop_closure = False
         self.lc_map_max, self.lc_max, self.lc_min_matches = 1024, 16, 5
         self.lc_meas_std, self.lc_chi2, self.lc_max_depth_var = 4.0, 5.99, 0.0
+        # lc_point_cov: a stored point carries the covariance it had when it left the state and its matches are weighed with
+        # it; lc_revisit_gap > 0: a stored point closes the loop once per visit, a visit ending after that many frames without
+        # a match of it (xivo_hip_lcmap_cov_config; both off: the stored point is exact and closes in every frame it is seen)
+        self.lc_point_cov, self.lc_revisit_gap = False, 0
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option " + k)
@@ -412,6 +416,9 @@ class HipBackend:
             raise ValueError("loop_closure with the innovation log is not supported: the log holds one update per frame")
         self.ctx.lcmap_config(c.lc_map_max, lc_max=c.lc_max, min_matches=c.lc_min_matches, Rlc=float(c.lc_meas_std) ** 2,
                               chi2=c.lc_chi2, max_depth_var=c.lc_max_depth_var)
+        self.lc_cov_on = bool(getattr(c, "lc_point_cov", False)) or int(getattr(c, "lc_revisit_gap", 0)) > 0
+        if self.lc_cov_on:
+            self.ctx.lcmap_cov_config(point_cov=bool(c.lc_point_cov), revisit_gap=int(c.lc_revisit_gap))
         self.lc_on = True
 
     def lcmap_add(self, recs):
@@ -430,6 +437,12 @@ class HipBackend:
     def lcmap_stats(self):
         """[B] lcmap_stats_dtype; one synchronising read"""
         return self.ctx.lcmap_stats(0, self.B)
+
+    def lcmap_cov_stats(self):
+        """[B] lcmap_cov_stats_dtype (zeros while lc_point_cov and lc_revisit_gap are both off); one synchronising read"""
+        if not getattr(self, "lc_cov_on", False):
+            return np.zeros(self.B, dtype=L.lcmap_cov_stats_dtype)
+        return self.ctx.lcmap_cov_stats(0, self.B)
 
     def enable_oos(self):
         """allocate the OOS list, gate distances and counters of the MSCKF update from dropped pool entries
@@ -787,6 +800,11 @@ def check_lifecycle(cfg):
                              % (L.LCMAP_MAX_ENTRIES, L.LCMAP_MAX_MATCHES))
         if not cfg.lc_meas_std > 0 or cfg.lc_chi2 < 0 or cfg.lc_max_depth_var < 0:
             raise ValueError("loop_closure needs lc_meas_std > 0, lc_chi2 >= 0 and lc_max_depth_var >= 0")
+        if getattr(cfg, "lc_point_cov", False) not in (False, True) or int(getattr(cfg, "lc_revisit_gap", 0)) != getattr(cfg, "lc_revisit_gap", 0) \
+                or getattr(cfg, "lc_revisit_gap", 0) < 0:
+            raise ValueError("loop_closure needs lc_point_cov False or True and an integer lc_revisit_gap >= 0")
+    elif getattr(cfg, "lc_point_cov", False) or getattr(cfg, "lc_revisit_gap", 0):
+        raise ValueError("lc_point_cov and lc_revisit_gap need loop_closure")
     if src == "device":
         if cfg.lifecycle != "device" and plc != "device":
             raise ValueError("track_source='device' needs lifecycle='device' or pool_lifecycle='device'")
@@ -1288,7 +1306,7 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     on the ground-truth camera poses; the worlds' own generate_measurements is not called, the pixel noise is the device's
     stream keyed by noise_seed, and with map_log the world ids are downloaded once per recorded frame.
     cfg.loop_closure: every frame hands the worlds' last_point_index to the runner as the tracks' keys; adds `lcmap_stats`
-    ([B] lcmap_stats_dtype)."""
+    ([B] lcmap_stats_dtype) and `lcmap_cov_stats` ([B] lcmap_cov_stats_dtype, the counters of lc_point_cov / lc_revisit_gap)."""
     if getattr(cfg, "imu_source", "host") == "device":
         raise ValueError("run_pcw feeds the simulators' IMU messages one by one: imu_source='device' runs with run_pcw_batch "
                          "or SequenceRunner.frame_resident")
@@ -1350,6 +1368,8 @@ def run_pcw(backend_factory, cfg, worlds, sims, total_time=4.0, imu_dt=0.0025, v
     out = dict(ts=np.array(ts), gt_Tsb=np.array(gt_T), runner=runner, backend=be)
     if lc and hasattr(be, "lcmap_stats"):
         out["lcmap_stats"] = be.lcmap_stats()
+        if hasattr(be, "lcmap_cov_stats"):
+            out["lcmap_cov_stats"] = be.lcmap_cov_stats()
     if mlog is not None:
         mlog.finish(out)
     if ilog:
