@@ -630,7 +630,14 @@ typedef struct {
   double tolerance, min_scale_factor, max_scale_factor;
 } xivo_prop_opts;
 /* imu: [nb][n_imu] - the n_imu samples of each filter since its last call (one Estimator::Propagate each, in order);
- * their transitions are accumulated on chip and the O(23 N) cross-covariance tail is applied once. */
+ * their transitions are accumulated on chip and the O(23 N) cross-covariance tail is applied once.
+ * Refused (XIVO_HIP_ERR_INVALID) before anything is uploaded or launched - P, the poses and the carried steps unchanged:
+ *  - a dt that is not positive and finite (NaN, <= 0, +inf: `while (total_step < dt)` would not end);
+ *  - a stepsize that is NaN, or in [0, 1e-6);
+ *  - under control_stepsize: method != 1, stepsize not > 0, or max_scale_factor not >= 1 (NaN included). As coded every
+ *    controlled step is followed by h *= max_scale_factor; below 1 the steps form a convergent series, and where its sum
+ *    stays under dt the step underflows to 0 and the loop never ends - in the reference as here.
+ * There is no cap on the number of sub-steps, as in the reference: a finite dt / stepsize ratio is the caller's budget. */
 int xivo_hip_propagate(xivo_hip_ctx* ctx, int b0, int nb, int n_imu, const xivo_imu_in* imu, const xivo_prop_opts* opts);
 /* The same for an online-calibration build (xivo_hip_set_calib with td >= 0 or Cg >= 0): kMotionSize = Index::End
  * (src/core.h:40-75) = Cg + 15, or td + 1 without the IMU calibration; ComposeMotion with the resident imu_.Cg() / imu_.Ca()
@@ -1218,7 +1225,8 @@ int xivo_hip_trajsim_config(xivo_hip_ctx* ctx, const xivo_trajsim_opts* opts);
 int xivo_hip_trajsim_set(xivo_hip_ctx* ctx, int b0, int nb, const int* motion, const double* rate);
 /* One frame of filters [0, B): records k0 + 1 .. k0 + n, the poses at t_{k0 + n}, one more frame of the ground-truth log.
  * n = 0 (the frame at t = 0) writes poses only and leaves no records. Enqueues one kernel; allocates nothing and does not
- * synchronise. Refused with nothing changed: n < 0 or n > n_max, B out
+ * synchronise. Refused with nothing changed: n < 0 or n > n_max, a sample index at which dt_k is not positive or t_k not finite
+ * (xivo_hip_propagate_resident cannot read the records it is handed: their dt is vouched for here), B out
  * of range, a frame open between life_begin and life_end, not configured (XIVO_HIP_ERR_INVALID); the log holds T_max frames
  * (XIVO_HIP_ERR_FULL). */
 int xivo_hip_trajsim_frame(xivo_hip_ctx* ctx, int B, unsigned long long k0, int n);

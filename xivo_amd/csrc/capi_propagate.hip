@@ -10,11 +10,27 @@ using namespace xivo_hip::capi;
 
 namespace {
 
-// control_stepsize (src/princedormand.cpp:26-60): Dormand-Prince with a positive cfg step and a growth factor only. The
-// reference's function-local static `h` starts at the cfg step (:23): one per filter here, reset when the cfg step changes.
+// What no sub-step loop may be handed (rk4.cpp:19, princedormand.cpp:38, :68 loop `while (total_step < dt)` with no cap on
+// the count): a step that is NaN or in [0, 1e-6), and under control_stepsize (Dormand-Prince with a positive cfg step only) a
+// growth factor below 1 - as coded the error estimate is 0 (:216-220), every step is followed by h *= max_scale_factor, and
+// with a factor below 1 the steps form a convergent series: where its sum stays below dt, h underflows and the loop never ends.
+bool prop_opts_bad(const xivo_prop_opts* o) {
+  if (std::isnan(o->stepsize) || (o->stepsize >= 0 && o->stepsize < 1e-6)) return true;
+  if (o->control_stepsize && (o->method != 1 || !(o->stepsize > 0) || !(o->max_scale_factor >= 1.0))) return true;
+  return false;
+}
+
+// a sample's length: positive and finite (`while (total_step < dt)` never ends on dt = +inf)
+bool prop_dt_bad(const xivo_imu_in* imu, size_t n) {
+  for (size_t b = 0; b < n; ++b)
+    if (!(imu[b].dt > 0.0) || !std::isfinite(imu[b].dt)) return true;
+  return false;
+}
+
+// control_stepsize (src/princedormand.cpp:26-60). The reference's function-local static `h` starts at the cfg step (:23): one
+// per filter here, reset when the cfg step changes. The options have passed prop_opts_bad.
 int prop_step_control(xivo_hip_ctx* c, const xivo_prop_opts* o) {
   if (!o->control_stepsize) return XIVO_HIP_OK;
-  if (o->method != 1 || !(o->stepsize > 0) || !(o->max_scale_factor > 0)) return XIVO_HIP_ERR_INVALID;
   if (c->pd_h && c->pd_h0 == o->stepsize) return XIVO_HIP_OK;
   if (!c->pd_h) { int rcd = c->mem.zeroed(&c->pd_h, (size_t)c->Bmax); if (rcd) return rcd; }
   std::vector<double> h0((size_t)c->Bmax, o->stepsize);
@@ -82,8 +98,10 @@ namespace xivo_hip::capi {
 int propagate_device(xivo_hip_ctx* c, int B, int n_imu, const xivo_imu_in* recs, const double* dQimu, const double* dQmodel,
                      const xivo_prop_opts* o, double mean_dt) {
   if (bad_range(c, 0, B) || B <= 0 || !c->have_layout || !c->poses || !recs || !o || n_imu <= 0 || c->N < 23 || c->lay.group_begin < 23 ||
-      (o->stepsize >= 0 && o->stepsize < 1e-6))
+      prop_opts_bad(o))
     return XIVO_HIP_ERR_INVALID;
+  // (the records' dt cannot be read here: they are device memory. xivo_hip_trajsim_frame, their only producer, refuses a
+  //  sample index at which t_k = k imu_dt leaves the finite range, so every dt_k it writes is positive and finite)
   if (c->calib_motion) return XIVO_HIP_ERR_UNSUPPORTED;
   int rc = prop_step_control(c, o);
   if (rc) return rc;
@@ -124,8 +142,7 @@ int xivo_hip_propagate(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_im
     return XIVO_HIP_ERR_INVALID;
   if (c->calib_motion) return XIVO_HIP_ERR_UNSUPPORTED;   // kMotionSize > 23: xivo_hip_propagate_calib
   if (nb == 0) return XIVO_HIP_OK;
-  for (size_t b = 0; b < (size_t)nb * n_imu; ++b)
-    if (!(imu[b].dt > 0.0) || (o->stepsize >= 0 && o->stepsize < 1e-6)) return XIVO_HIP_ERR_INVALID;
+  if (prop_opts_bad(o) || prop_dt_bad(imu, (size_t)nb * n_imu)) return XIVO_HIP_ERR_INVALID;   // before any upload or launch
   int rc = prop_step_control(c, o);
   if (rc) return rc;
   PropStateArgs a;
@@ -148,11 +165,11 @@ int xivo_hip_propagate_calib(xivo_hip_ctx* c, int b0, int nb, int n_imu, const x
     return XIVO_HIP_ERR_INVALID;
   const int nm = c->cl.Cg >= 0 ? c->cl.Cg + 15 : c->cl.td + 1;
   if (nm > 40 || c->N < nm || c->lay.group_begin < nm) return XIVO_HIP_ERR_INVALID;
-  int rc = prop_step_control(c, o);   // (before the empty-range return, unlike xivo_hip_propagate)
+  // the options are judged before the empty-range return (unlike xivo_hip_propagate), every refusal before any upload or launch
+  if (prop_opts_bad(o) || (nb > 0 && prop_dt_bad(imu, (size_t)nb * n_imu))) return XIVO_HIP_ERR_INVALID;
+  int rc = prop_step_control(c, o);
   if (rc) return rc;
   if (nb == 0) return XIVO_HIP_OK;
-  for (size_t b = 0; b < (size_t)nb * n_imu; ++b)
-    if (!(imu[b].dt > 0.0) || (o->stepsize >= 0 && o->stepsize < 1e-6)) return XIVO_HIP_ERR_INVALID;
   PropStateArgs a;
   rc = prop_stage(c, b0, nb, n_imu, imu, o, nm, Qmodel, a);
   if (rc) return rc;

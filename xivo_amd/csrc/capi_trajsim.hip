@@ -83,9 +83,12 @@ int xivo_hip_trajsim_set(xivo_hip_ctx* c, int b0, int nb, const int* motion, con
 int xivo_hip_trajsim_frame(xivo_hip_ctx* c, int B, unsigned long long k0, int n) {
   if (!trajsim_ready(c) || B <= 0 || B > c->Bmax || n < 0 || n > c->trajsim.opts.n_max || track_block_frame_open(c)) return XIVO_HIP_ERR_INVALID;
   if (c->calib_motion) return XIVO_HIP_ERR_UNSUPPORTED;
-  // every record's dt must be positive (xivo_hip_propagate's rule): t_k stops resolving imu_dt far beyond any run's length
+  // every record's dt must be positive and finite (xivo_hip_propagate's rule; xivo_hip_propagate_resident cannot read the
+  // records): t_k stops resolving imu_dt far beyond any run's length, and a finite imu_dt times a large k can still leave the
+  // finite range - the last time finite makes every t_k, so every dt_k, of the frame finite
   if (n > 0 && (k0 + (unsigned long long)n < k0 || !(trajsim_dt(k0 + 1, c->trajsim.opts.imu_dt) > 0.0) ||
-                !(trajsim_dt(k0 + (unsigned long long)n, c->trajsim.opts.imu_dt) > 0.0)))
+                !(trajsim_dt(k0 + (unsigned long long)n, c->trajsim.opts.imu_dt) > 0.0) ||
+                !std::isfinite(trajsim_time(k0 + (unsigned long long)n, c->trajsim.opts.imu_dt))))
     return XIVO_HIP_ERR_INVALID;
   if (c->trajsim.log.full()) return XIVO_HIP_ERR_FULL;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;

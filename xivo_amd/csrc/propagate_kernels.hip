@@ -733,9 +733,13 @@ __global__ __launch_bounds__(64) void propagate_state_wave_kernel(PropStateArgs 
           const int e = min(lane + 64 * m, NN - 1);
           double sp = 0.0;
 #pragma unroll
+          // (explicit fma in the sums over P, here and in the stage combination: left to contraction, the compiler fused some
+          //  of a lane's nine unrolled element instances and not others, and the two triangles of P_mm - which are different
+          //  instances - rounded differently, while phase B takes P0 as symmetric. The FK sums next to them may stay as they
+          //  are: no element of F is taken for another)
           for (int q = 0; q < st; ++q)
-            if (TB::a[st][q] != 0.0) sp += TB::a[st][q] * PK[q][m];
-          P0[e] = Pmm[m] + sp * h;
+            if (TB::a[st][q] != 0.0) sp = fma(TB::a[st][q], PK[q][m], sp);
+          P0[e] = fma(sp, h, Pmm[m]);
         }
 #pragma unroll
         for (int u = 0; u < FL; ++u) {
@@ -842,8 +846,8 @@ __global__ __launch_bounds__(64) void propagate_state_wave_kernel(PropStateArgs 
         double pk = 0.0;
 #pragma unroll
         for (int q = 0; q < NS; ++q)
-          if (TB::b[q] != 0.0) pk += TB::b[q] * PK[q][m];
-        Pmm[m] += pk * h;                              // rk4.cpp:92-93
+          if (TB::b[q] != 0.0) pk = fma(TB::b[q], PK[q][m], pk);
+        Pmm[m] = fma(pk, h, Pmm[m]);                   // rk4.cpp:92-93
       }
 #pragma unroll
       for (int u = 0; u < FL; ++u) {
