@@ -1113,7 +1113,7 @@ def feature_score(P):
 # a7: Estimator::OnePointRANSAC (src/update.cpp:213-393), numeric core for one filter.
 # ----------------------------------------------------------------------------
 def one_point_ransac(st, P, xp, cam, layout, R, ransac_thresh, ransac_chi2, gauge_group, instate_groups,
-                     in_current_ekf_update=(), calib_gyro=None):
+                     in_current_ekf_update=(), calib_gyro=None, low=None):
     """st as in absorb_error plus ref [F]. All F features are the MH inliers handed in.
     Returns dict(inliers=sorted feature indices kept, rejected=..., chi2={feature: distance},
     low=low-innovation mask, err=dx of the partial update, P_partial=P after it).
@@ -1135,7 +1135,10 @@ def one_point_ransac(st, P, xp, cam, layout, R, ransac_thresh, ransac_chi2, gaug
                                         cm, layout, r, int(s["sind"][i]), calib=cal)[:2])
         return out
     J0 = jac_all(st)
-    low = np.array([np.linalg.norm(J0[i][1]) < ransac_thresh for i in range(F)])         # :245-249
+    if low is None:
+        low = np.array([np.linalg.norm(J0[i][1]) < ransac_thresh for i in range(F)])     # :245-249
+    else:                                                                                  # (the low-innovation set decided by the caller:
+        low = np.asarray(low, dtype=bool)                                                  #  tests/gate_restate.py, innovations at the threshold)
     res = dict(low=low, chi2={}, err=None, P_partial=None)
     if low.all():                                                                          # :263-265
         res.update(inliers=list(range(F)), rejected=[])
@@ -1163,6 +1166,7 @@ def one_point_ransac(st, P, xp, cam, layout, R, ransac_thresh, ransac_chi2, gaug
         res["err"], res["P_partial"] = err, P2
     kept, rejected = [i for i in range(F) if low[i]], []
     J1 = jac_all(s2)                                                                       # :348 (at the updated state)
+    res["rows"], res["P_rescue"] = J1, P2                                                  # what the rescue test is made on (tests/gate_edge_cases.py)
     for i in range(F):
         if not low[i]:
             d = mh_distances(J1[i][0][None], P2, J1[i][1][None], R)[0]                     # :352-356

@@ -445,6 +445,15 @@ struct GemmExtra {
   BatchVec scale1;       // per-k scale of the second segment's B operand, per filter
 };
 
+// Gate parameters that cannot mean anything, refused before anything is uploaded or launched (every gating entry point and
+// OnePointRANSAC): a measurement variance R that is not a positive finite number (S = J P J^T + R I2 is then no covariance), a
+// NaN threshold (every comparison false), and a relaxation factor that is NaN or below 1 - the reference's loop
+// (src/update.cpp:73-96) then shrinks its threshold and never ends; the device's 4096-pass guard would return an empty
+// mask that no run of the reference produces. mult = 1 is accepted and pinned as coded (the guard ends it).
+inline bool bad_gate_params(double R, double thresh, double mult = 1.0) {
+  return !(R > 0.0) || R > 1.7976931348623157e308 || thresh != thresh || !(mult >= 1.0);
+}
+
 // ---- capi.hip
 bool bad_range(xivo_hip_ctx* c, int b0, int nb);
 MeasBuffers meas_buffers(xivo_hip_ctx* c, int b0 = 0);   // the dense rows, inn and diagR of the filters from b0 on

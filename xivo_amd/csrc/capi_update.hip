@@ -651,6 +651,7 @@ int xivo_hip_update_dense_gated(xivo_hip_ctx* c, int B, int F, double R, double 
                                 int min_inliers) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || B <= 0 || B > c->Bmax || c->rows.rows_padded() <= 0 || F <= 0 || 2 * F > c->rows.rows()) return XIVO_HIP_ERR_INVALID;
+  if (bad_gate_params(R, mh_thresh, mh_mult)) return XIVO_HIP_ERR_INVALID;
   int rc = ensure_gate_buffers(c, F);
   if (rc) return rc;
   GateParams gp{F, R, mh_thresh, mh_mult, min_inliers};
@@ -825,6 +826,7 @@ int xivo_hip_mh_gate_dense(xivo_hip_ctx* c, int B, int F, double R, double mh_th
                            int min_inliers, unsigned char* mask_out, double* dist_out) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || B <= 0 || B > c->Bmax || F <= 0 || 2 * F > c->rows.rows()) return XIVO_HIP_ERR_INVALID;
+  if (bad_gate_params(R, mh_thresh, mh_mult)) return XIVO_HIP_ERR_INVALID;
   int rc = ensure_gate_buffers(c, F);
   if (rc) return rc;
   rc = ensure_dense(c);

@@ -1206,6 +1206,16 @@ __global__ __launch_bounds__(64) void givens_kernel(GivensArgs a) {
   }
 }
 
+// |res| as Eigen's res.norm() forms it (src/update.cpp:245): two rounded products, one rounded add. Contracted to a fused
+// multiply-add the norm differs by one ulp on about 8 % of innovations, and a feature whose norm EQUALS ransac_thresh_ is then
+// low-innovation with the contracted norm and not with this one (tests/test_gate_edges_gpu.py, the norm tie).
+__device__ __forceinline__ double innovation_norm(double r0, double r1) {
+#pragma clang fp contract(off)
+  const double a = r0 * r0;
+  const double b = r1 * r1;
+  return sqrt(a + b);
+}
+
 // ---------------------------------------------------------------- Estimator::OnePointRANSAC (src/update.cpp:213-393)
 // select: the low-innovation set among the MH inliers (:238-258 - the hypothesis index k is drawn but never used, so
 // the maximal set is {f : |xp - Predict| < ransac_thresh_}; xp - Predict is the innovation of the Jacobian pass), the
@@ -1228,7 +1238,7 @@ __global__ __launch_bounds__(64) void ransac_select_kernel(RansacArgs a) {
       mh = sb.mask[(long)filt * sb.Fmax + f] && ft.sind >= 0;
       ref = mh ? ft.ref_sind : 0;
       const double r0 = sb.finn[((long)filt * sb.Fmax + f) * 2], r1 = sb.finn[((long)filt * sb.Fmax + f) * 2 + 1];
-      low = mh && sqrt(r0 * r0 + r1 * r1) < a.thresh;
+      low = mh && innovation_norm(r0, r1) < a.thresh;
       a.low[(long)filt * sb.Fmax + f] = low ? 1 : 0;
     }
     n_mh += __popcll(__ballot(mh));
