@@ -266,7 +266,7 @@ int xivo_hip_selftest_fused_tiles(int column_blocks, int* per_simd);
 int xivo_hip_selftest_fused_shape(int Mp, int Np, int pw, char* label, int n);
 int xivo_hip_selftest_host_compress(const double* H, int ldh, int M, int N, int pairs_clear, int* idx, double* val, int* nc, int* pw);
 /* Host-only answer to "which kernel would this shape launch" for the feature-level and propagation kernels whose launch picks
- * by size (csrc/glevel_kernels.hip, csrc/propagate_kernels.hip; the launch calls the same function). label[n] (optional) receives the stage label that
+ * by size (csrc/gate_kernels.hip, csrc/glevel_kernels.hip, csrc/propagate_kernels.hip; the launch calls the same function). label[n] (optional) receives the stage label that
  * xivo_hip_stage_kernel reports for that launch. No GPU needed.
  *   XIVO_HIP_LAUNCH_GATE          a = filters in the call, b = F, c = online-calibration build (0 / 1): returns the threads per
  *                                 filter of gate_sparse_kernel; label "gate_sparse_kernel@<threads>".

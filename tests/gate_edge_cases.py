@@ -2,17 +2,16 @@
 (src/update.cpp:213-393) at thresholds and ties, against tests/gate_restate.py. tests/test_gate_edges_cpu.py checks that every case
 sits where it claims; tests/test_gate_edges_gpu.py runs them on the device.
 
-The gate exists five times around gate_device.h. What reaches which copy (ROUTES below; asserted from the FLAG_PROFILE stage
+The gate runs in five kernels, each stating its rules through gate_device.h. What reaches which copy (ROUTES below; asserted from the FLAG_PROFILE stage
 labels / last_route() in every GPU test):
   gate_sparse_kernel                 xivo_hip_mh_gate on the resident scene             counts present entries (sind >= 0)
   gate_dense_kernel                  xivo_hip_mh_gate_dense, update_dense_gated on      present = F (a scene's entries are counted only
                                      dense rows / XIVO_HIP_FLAG_DENSE_H                 by the calibration gate, which hands them in)
-  gate_ell_body, from_S              update_dense_gated on compressed rows, < 512       present = F
-                                     filters or the latency route
+  gate_ell_kernel                    update_dense_gated on compressed rows, < 512       present = F
+                                     filters or the latency route; the 2 x 2 blocks from
+                                     the S kernel's compact copy, or off S (ell_blocks_off_S)
   fused_update_f64_kernel's gate     update_dense_gated on the one-kernel route         present = F
   chol_reg_la_f64_kernel's prologue  update_dense_gated, >= 512 filters                 present = F
-gate_ell_body's other form (distances from P H^T, from_S = 0) and its call from the tail of the S kernel have no caller in the
-C ABI: read from the code, not run.
 
 The feature-level calls exist on two scenes, "feature" (the default build: gate_sparse_kernel) and "calib" (an online-calibration
 build, 43-column rows: gate_sparse_kernel's wide form, with XIVO_HIP_FLAG_DENSE_H gate_dense_kernel counting the scene's present
@@ -72,12 +71,15 @@ MT, TP, SYM, TAIL, DH = FLAG_MULTI_KERNEL, FLAG_THROUGHPUT_ROUTE, FLAG_SYMMETRIC
 CLASSES = ("k1e2", "k1e4", "k1e6", "k1e8", "k1e10", "k1e12", "r_dominates", "decades")
 KAPPA_TARGET = dict(k1e2=1e2, k1e4=1e4, k1e6=1e6, k1e8=1e8, k1e10=1e10, k1e12=1e12)
 
-# name, context flags, rows ("rows": compressed 21-column rows, "dense": every column non-zero), filters, entry point
+# name, context flags, rows ("rows": compressed 21-column rows, "dense": every column non-zero, "rows_n320": the compressed rows
+# in a state of WIDE_STATE_N columns - zero columns of H, an identity prior on them - where the S kernel walks 32-wide slabs and
+# leaves no compact copy of the diagonal blocks: gate_ell_kernel reads them off S), filters, entry point
 # ("g" xivo_hip_update_dense_gated, "d" xivo_hip_mh_gate_dense), last_route() ("" = none: no update ran), gate copy
 ROUTES = [
     ("fused", 0, "rows", NB, "g", "fused", "fused"),
     ("ell_latency", MT, "rows", NB, "g", "sparse_whitened", "gate_ell"),
     ("ell_in_solve", MT | TP, "rows", NB, "g", "sparse_in_solve", "gate_ell"),
+    ("ell_blocks_off_S", MT, "rows_n320", NB, "g", "sparse_whitened", "gate_ell"),
     ("chol_prologue", MT | TP, "rows", 512, "g", "sparse_in_solve", "chol"),
     ("ell_symmetric", SYM, "rows", NB, "g", "sparse_symmetric", "gate_ell"),
     ("ell_tail", TAIL, "rows", NB, "g", "sparse_tail", "gate_ell"),
@@ -89,6 +91,7 @@ ROUTES = [
     ("mh_gate_dense_dh", DH, "rows", NB, "d", "", "gate_dense"),
 ]
 ROUTE_NAMES = [r[0] for r in ROUTES]
+WIDE_STATE_N = 320               # 64 values of 320 source columns pass the 160 KB of LDS: the S kernel takes 32-wide slabs
 LEVELS = ("update", "dense", "feature", "calib")   # a call's inputs: compressed rows | dense rows | a scene | a scene of an online-calibration build
 SCENE_LEVELS = ("feature", "calib")                # the gates of these count the present entries
 
@@ -241,7 +244,7 @@ def calib_arrays(scn, poses):
 
 def full_rows_calib(J21, Jc, lay, ref, sind):
     """whole 43-column rows from xivo_hip_get_jacobians and xivo_hip_get_jacobians_calib ([.., F, 2, 22]: td | Cg 9 | bg 3 |
-    intrinsics 9, wide_scol of glevel_kernels.hip)"""
+    intrinsics 9, wide_scol of gate_kernels.hip)"""
     out = full_rows(J21, lay, ref, sind)
     cols = np.concatenate([[lay.td], lay.Cg + np.arange(9), BG_COL + np.arange(3), lay.cam_begin + np.arange(lay.cam_dim)])
     here = (np.asarray(sind) >= 0)[..., None, None]
@@ -253,7 +256,7 @@ BG_COL = 9                       # Index::bg
 
 
 def full_rows(J21, lay, ref, sind):
-    """compact rows [.., F, 2, 21] as xivo_hip_get_jacobians returns them -> whole rows [.., F, 2, N] (jcol of glevel_kernels.hip);
+    """compact rows [.., F, 2, 21] as xivo_hip_get_jacobians returns them -> whole rows [.., F, 2, N] (jcol of feature_chi2_device.h);
     an absent entry (sind < 0) is a zero row"""
     J21 = np.asarray(J21)
     out = np.zeros(J21.shape[:-1] + (lay.N,))

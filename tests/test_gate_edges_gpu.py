@@ -1,5 +1,5 @@
 """The in-state gate (Estimator::MHGating, src/update.cpp:60-96) in all its copies - gate_sparse_kernel, gate_dense_kernel,
-gate_ell_body, the gate of fused_update_f64_kernel, the prologue of the register Cholesky - and Estimator::OnePointRANSAC
+gate_ell_kernel, the gate of fused_update_f64_kernel, the prologue of the register Cholesky - and Estimator::OnePointRANSAC
 (src/update.cpp:213-393) at thresholds and ties, against the 80-bit restatement of tests/gate_restate.py on the cases of
 tests/gate_edge_cases.py (tests/test_gate_edges_cpu.py checks without a GPU that each case sits where it claims).
 Every test asserts which gate copy ran from the profile's stage labels / last_route(). The bounds are imported, not typed in."""
@@ -44,10 +44,14 @@ def run_update(call, rdef, thresh=None, mult=None, min_inliers=None):
     mu = call.mult if mult is None else mult
     mi = call.min_inliers if min_inliers is None else min_inliers
     idx = np.arange(max(B, call.B)) % call.B if B > call.B else np.arange(call.B)
-    H, inn = call.H()[idx], call.inn.reshape(call.B, 2 * call.F)[idx]
+    H, inn, P, N = call.H()[idx], call.inn.reshape(call.B, 2 * call.F)[idx], call.P[idx], call.N
     nb = len(idx)
-    with Context(call.N, 2 * call.F, nb, flags=flags | FLAG_PROFILE) as ctx:
-        ctx.upload_P(call.P[idx]); ctx.set_measurements(H, inn, np.full((nb, 2 * call.F), call.R))
+    if rows == "rows_n320":                             # the same rows and prior in a wider state: exact zeros in every sum
+        N = gc.WIDE_STATE_N
+        H = np.concatenate([H, np.zeros(H.shape[:2] + (N - call.N,))], axis=2)
+        P = np.tile(np.eye(N), (nb, 1, 1)); P[:, :call.N, :call.N] = call.P[idx]
+    with Context(N, 2 * call.F, nb, flags=flags | FLAG_PROFILE) as ctx:
+        ctx.upload_P(P); ctx.set_measurements(H, inn, np.full((nb, 2 * call.F), call.R))
         if entry == "g":
             ctx.update_dense_gated(call.F, call.R, th, mu, mi, nb)
             mask, dist = ctx.get_gate(call.F, nb)
@@ -55,6 +59,11 @@ def run_update(call, rdef, thresh=None, mult=None, min_inliers=None):
             mask, dist = ctx.mh_gate_dense(call.F, call.R, th, mu, mi, nb)
         prof, route = ctx.profile_get(), ctx.last_route()
     _assert_copy(copy, want_route if entry == "g" else None, prof, route)
+    # gate_ell_kernel's two sources of the 2 x 2 blocks. What is asserted is the slab width of the S kernel; the source follows
+    # from the launcher's condition, not from an observation of the branch: on these routes (no mixed stacking, no leading block,
+    # the T buffer large enough) 64-wide slabs leave the compact copy and the gate is handed it, 32-wide ones leave none
+    if copy == "gate_ell":
+        assert prof["gemm_S"]["kernel"].split(",")[2] == ("32" if rows == "rows_n320" else "64"), prof["gemm_S"]
     for b in range(call.B, nb):                         # the tiled copies of a large batch: the same bits
         assert np.array_equal(mask[b], mask[b % call.B]) and np.array_equal(dist[b], dist[b % call.B]), b
     return mask[:call.B], dist[:call.B]

@@ -10,10 +10,10 @@ using namespace xivo_hip::capi;
 
 namespace {
 
-int gate_impl(xivo_hip_ctx* c, int B, double R, double th, double mult, int min_inl, int use_gating) {
+int gate_impl(xivo_hip_ctx* c, int B, const GateParams& gp, int use_gating) {
   GateArgs a{};
   a.sb = scene_buffers(c); a.lay = c->lay; c->P.to(a.P, a.strideP, a.ldp);
-  a.R = R; a.thresh = th; a.mult = mult; a.min_inliers = min_inl; a.batch = B; a.use_gating = use_gating;
+  a.gp = gp; a.batch = B; a.use_gating = use_gating;
   char label[64];
   gate_sparse_threads(B, a.sb.F, a.sb.Jc ? 1 : 0, label, sizeof(label));
   StageTimer st(c, ST_GATE, 0.0, label);
@@ -25,17 +25,17 @@ int gate_impl(xivo_hip_ctx* c, int B, double R, double th, double mult, int min_
 // blocks (update.cpp:60-70), which is not the row FillJacobianBlock stacks (the :675-676 overwrite): every present feature is
 // stacked once as its full J() (dense rows) and gated on (J P) J^T + R by the dense-row gate. gate = 0: every present feature
 // is an inlier (Estimator::OutlierRejection does not gate F <= min_required_inliers_, src/manager.cpp:635).
-int calib_gate(xivo_hip_ctx* c, int B, double R, double mh_thresh, double mh_mult, int min_inliers, int gate) {
-  int rc = gate_impl(c, B, R, mh_thresh, mh_mult, min_inliers, 0);
+int calib_gate(xivo_hip_ctx* c, int B, const GateParams& gp, int gate) {
+  int rc = gate_impl(c, B, gp, 0);
   if (rc) return rc;
   if (gate) {
-    c->rows.stacked(B, c->F, R, Stacking::full_rows, /*pw=*/9, /*dense=*/true, CalibCols::in_rows);
+    c->rows.stacked(B, c->F, gp.R, Stacking::full_rows, /*pw=*/9, /*dense=*/true, CalibCols::in_rows);
     c->dx_clear();
-    rc = stack_impl(c, B, R, 1, nullptr, /*full_rows=*/1);
+    rc = stack_impl(c, B, gp.R, 1, nullptr, /*full_rows=*/1);
     if (rc) return rc;
     GateDenseArgs a{};
     a.mask = c->mask; a.dist = c->dist; a.F = c->F; a.mask_ld = c->Fmax;   // (the stride xivo_hip_stack reads the mask with)
-    a.R = R; a.thresh = mh_thresh; a.mult = mh_mult; a.min_inliers = min_inliers; a.have_ell = 0;
+    a.gp = gp; a.have_ell = 0;
     a.feats = c->feats; a.Fmax = c->Fmax;        // absent entries of ragged batches are no candidates (per-filter present count)
     return gate_dense_rows(c, B, a);   // (mask / dist stay in the strided layout gate_impl left)
   }
@@ -117,8 +117,7 @@ int gate_dense_rows(xivo_hip_ctx* c, int B, GateDenseArgs a) {
   GemmExtra x; x.C2 = c->PHT;
   rc = gemm(c, ST_HP, B, c->rows.rows_padded(), Np, {c->H, c->P, Np}, c->HP, x);
   if (rc) return rc;
-  c->H.to(a.H, a.strideH, a.ldh); c->HP.to(a.HP, a.strideHP, a.ldhp);
-  a.Hw = c->H.p; c->HT.to(a.HTw, a.strideHT, a.ldht); a.HPw = nullptr; a.PHTw = nullptr; a.PHTr = c->PHT.p;
+  c->H.to(a.Hw, a.strideH, a.ldh); c->HT.to(a.HTw, a.strideHT, a.ldht); a.HPw = nullptr; a.PHTw = nullptr; a.PHTr = c->PHT.p;
   c->inn.to(a.inn, a.strideInn); c->diagR.to(a.diagR, a.strideR); a.Np = Np; a.batch = B; a.ell = c->ell;
   StageTimer st(c, ST_GATE, 0.0, "gate_dense_kernel");
   HIP_TRY((hipError_t)launch_gate_dense(a, c->stream));
@@ -257,11 +256,11 @@ int xivo_hip_mh_gate(xivo_hip_ctx* c, int B, double R, double mh_thresh, double 
                      unsigned char* mask_out, double* dist_out) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0) return XIVO_HIP_ERR_INVALID;
-  if (bad_gate_params(R, mh_thresh, mh_mult)) return XIVO_HIP_ERR_INVALID;
+  const GateParams gp{R, mh_thresh, mh_mult, min_inliers};
+  if (bad_gate_params(gp)) return XIVO_HIP_ERR_INVALID;
   // (online-calibration builds: the compact gate works on the whole row too - 43 columns, gate_sparse_kernel's wide form;
   //  with XIVO_HIP_FLAG_DENSE_H the dense-row gate of round 4)
-  int rc = (c->calib_on && !calib_sparse(c)) ? calib_gate(c, B, R, mh_thresh, mh_mult, min_inliers, 1)
-                                             : gate_impl(c, B, R, mh_thresh, mh_mult, min_inliers, 1);
+  int rc = (c->calib_on && !calib_sparse(c)) ? calib_gate(c, B, gp, 1) : gate_impl(c, B, gp, 1);
   return rc ? rc : xivo_hip_get_gate(c, B, c->F, mask_out, dist_out);   // (in the strided layout the gate just left)
 }
 
@@ -282,7 +281,8 @@ int xivo_hip_filter_update(xivo_hip_ctx* c, int B, double R, double mh_thresh, d
                            int use_gating) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0) return XIVO_HIP_ERR_INVALID;
-  if (bad_gate_params(R, mh_thresh, mh_mult)) return XIVO_HIP_ERR_INVALID;
+  const GateParams gp{R, mh_thresh, mh_mult, min_inliers};
+  if (bad_gate_params(gp)) return XIVO_HIP_ERR_INVALID;
   int rc = xivo_hip_jacobians_instate(c, B);
   if (rc) return rc;
   // Estimator::OutlierRejection only gates when F > min_required_inliers_ (src/manager.cpp:635)
@@ -290,8 +290,7 @@ int xivo_hip_filter_update(xivo_hip_ctx* c, int B, double R, double mh_thresh, d
   // online-calibration builds on dense rows (XIVO_HIP_FLAG_DENSE_H): the gate needs the WHOLE row J() incl. the td / Cg / bg / intrinsics blocks (update.cpp:60-70),
   // which is not the row FillJacobianBlock stacks (the :675-676 overwrite): every present feature is stacked once as its
   // full J() (dense rows), gated on (J P) J^T + R by the dense-row gate, then the inliers are stacked as coded and updated
-  rc = (c->calib_on && !calib_sparse(c)) ? calib_gate(c, B, R, mh_thresh, mh_mult, min_inliers, gate)
-                                         : gate_impl(c, B, R, mh_thresh, mh_mult, min_inliers, gate);
+  rc = (c->calib_on && !calib_sparse(c)) ? calib_gate(c, B, gp, gate) : gate_impl(c, B, gp, gate);
   if (rc) return rc;
   rc = xivo_hip_stack(c, B, R);
   if (rc) return rc;

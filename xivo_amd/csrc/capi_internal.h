@@ -450,8 +450,9 @@ struct GemmExtra {
 // NaN threshold (every comparison false), and a relaxation factor that is NaN or below 1 - the reference's loop
 // (src/update.cpp:73-96) then shrinks its threshold and never ends; the device's 4096-pass guard would return an empty
 // mask that no run of the reference produces. mult = 1 is accepted and pinned as coded (the guard ends it).
-inline bool bad_gate_params(double R, double thresh, double mult = 1.0) {
-  return !(R > 0.0) || R > 1.7976931348623157e308 || thresh != thresh || !(mult >= 1.0);
+// (OnePointRANSAC has no relaxation: it hands its R and threshold over with mult = 1)
+inline bool bad_gate_params(const GateParams& gp) {
+  return !(gp.R > 0.0) || gp.R > 1.7976931348623157e308 || gp.thresh != gp.thresh || !(gp.mult >= 1.0);
 }
 
 // ---- capi.hip

@@ -21,7 +21,7 @@ int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_th
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0 || !c->mask || !c->poses) return XIVO_HIP_ERR_INVALID;
   if (c->lay.n_groups > 64) return XIVO_HIP_ERR_UNSUPPORTED;
-  if (bad_gate_params(R, ransac_thresh) || ransac_chi2 != ransac_chi2) return XIVO_HIP_ERR_INVALID;
+  if (bad_gate_params({R, ransac_thresh, 1.0, 0}) || ransac_chi2 != ransac_chi2) return XIVO_HIP_ERR_INVALID;
   const size_t Bm = c->Bmax, ng = c->lay.n_groups;
   // online-calibration builds: the calibration state is backed up / restored with X_ (imu_.BackupState, Camera::BackupState,
   // src/estimator.cpp:1421-1427), the partial update stacks the whole rows J() as dense rows, AbsorbError retracts td / Cg / Ca /
@@ -94,7 +94,7 @@ int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_th
     // (scratch outputs: the mask goes to rs_low - dead once the partial update is stacked -, the distances to rs_chi, where the
     //  decision kernel below reads them and leaves chi2 per tested feature; c->dist keeps the MH distances)
     ga.mask = c->rs.low; ga.dist = c->rs.chi; ga.F = c->F; ga.mask_ld = c->Fmax;
-    ga.R = R; ga.thresh = ransac_chi2; ga.mult = 1.0; ga.min_inliers = -1; ga.no_relax = 1;
+    ga.gp = {R, ransac_chi2, 1.0, -1}; ga.no_relax = 1;
     ga.have_ell = 0; ga.feats = c->feats; ga.Fmax = c->Fmax;
     rc = gate_dense_rows(c, B, ga);
     if (rc) return rc;

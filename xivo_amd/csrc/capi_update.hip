@@ -69,8 +69,8 @@ static UpdatePlan plan_update(const xivo_hip_ctx* c, int b0, int B, bool gate) {
   return p;
 }
 
-// One pass of the update pipeline over filters [b0, b0 + B).
-struct GateParams { int F; double R, thresh, mult; int min_inliers; };
+// One pass of the update pipeline over filters [b0, b0 + B); `gate` (or null): MH gating of its F features per filter first
+struct UpdateGate { int F; GateParams gp; };
 
 // The row-pair compressed rows of filters [b0, ...)
 EllBuffers ell_range(const EllBuffers& ell, int b0) {
@@ -203,7 +203,7 @@ static int finish_whitened(xivo_hip_ctx* c, const UpdatePlan& plan, const Update
 //                    [MH gating]                   in the prologue of the factorisation / gate_ell    update.cpp:60-96
 //                    then finish_whitened / finish_symmetric, or (SPARSE_TAIL)
 //                    T = K (HP) - P, G = T H^T + K R, P+ = G K^T - T                          estimator.cpp:1276-1287 re-associated
-static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const UpdateViews& v, int b0, int B, const GateParams* gate) {
+static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const UpdateViews& v, int b0, int B, const UpdateGate* gate) {
   const int Np = c->Np, Mp = c->rows.rows_padded();
   const BatchMat &P = v.P, &HP = v.HP, &PHT = v.PHT, &S = v.S, &K = v.K, &G = v.G, &T = v.T;
   const BatchVec &inn = v.inn, &diagR = v.diagR;
@@ -222,7 +222,7 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Up
     v.err.to(a.err, a.strideErr); PHT.to(a.PHT, a.stridePHT, a.ldpht); a.status = v.status;
     a.Np = Np; a.Mp = Mp; a.batch = B; a.pw = pw_max;
     if (gate) {
-      a.gate = 1; a.F = gate->F; a.R = gate->R; a.thresh = gate->thresh; a.mult = gate->mult; a.min_inliers = gate->min_inliers;
+      a.gate = 1; a.F = gate->F; a.gp = gate->gp;
       a.mask = c->mask + (long)b0 * gate->F; a.dist = c->dist + (long)b0 * gate->F;
       if (c->rows.dense_alive()) { v.H.to(a.H, a.strideH, a.ldh); v.HT.to(a.HT, a.strideHT, a.ldht); }
     }
@@ -272,13 +272,11 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Up
     ga.ell = e;
     v.H.to(ga.H, ga.strideH, ga.ldh); v.HT.to(ga.HT, ga.strideHT, ga.ldht);
     if (!c->rows.dense_alive()) { ga.H = nullptr; ga.HT = nullptr; }
-    ga.PHT = PHT.p;
-    ga.HP = nullptr;   // H P [Mp x Np] has no reader behind this point (S is formed already, the solve reads P H^T)
+    ga.PHT = PHT.p;   // (H P [Mp x Np] has no reader behind this point: S is formed already, the solve reads P H^T)
     inn.to(ga.inn, ga.strideInn); diagR.to(ga.diagR, ga.strideR);
     ga.mask = c->mask + (long)b0 * gate->F; ga.dist = c->dist + (long)b0 * gate->F;
     ga.F = gate->F; ga.Np = Np; ga.batch = B;
-    S.to(ga.S, ga.strideS, ga.lds); ga.Mp = Mp; ga.from_S = 1;   // distances from the diagonal blocks of S
-    ga.R = gate->R; ga.thresh = gate->thresh; ga.mult = gate->mult; ga.min_inliers = gate->min_inliers;
+    S.to(ga.S, ga.strideS, ga.lds); ga.Mp = Mp; ga.gp = gate->gp;   // distances from the diagonal blocks of S
   }
   // the compact copy of the 2 x 2 diagonal blocks of S lives in the T buffer (free until the solve): 2 Mp doubles per filter
   const BatchVec Sdiag{T.p, T.stride};
@@ -317,8 +315,7 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Up
     if (gate_folded) {
       Sdiag.to(cg.Sdiag, cg.strideSdiag); inn.to(cg.inn, cg.strideInn); diagR.to(cg.diagR, cg.strideR);
       cg.ellval = e.val; cg.strideVal = e.stride_val(); cg.ell_w = ELL_W; PHT.to(cg.PHT, cg.stridePHT, cg.ldpht); cg.Np = Np;
-      cg.mask = ga.mask; cg.dist = ga.dist; cg.F = gate->F; cg.R = gate->R; cg.thresh = gate->thresh; cg.mult = gate->mult;
-      cg.min_inliers = gate->min_inliers;
+      cg.mask = ga.mask; cg.dist = ga.dist; cg.F = gate->F; cg.gp = gate->gp;
     } else {
       StageTimer st(c, ST_GATE, 0.0, "gate_ell_kernel");
       HIP_TRY((hipError_t)launch_gate_ell(ga, c->stream));
@@ -370,7 +367,7 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Up
   return gemm(c, ST_PNEW, B, Np, Np, {G, K, Mp}, P, x);
 }
 
-static int update_dense_range(xivo_hip_ctx* c, const UpdatePlan& plan, const UpdateViews& v, int b0, int B, const GateParams* gate) {
+static int update_dense_range(xivo_hip_ctx* c, const UpdatePlan& plan, const UpdateViews& v, int b0, int B, const UpdateGate* gate) {
   const int Np = c->Np, Mp = c->rows.rows_padded();
   const BatchMat &H = v.H, &HT = v.HT, &P = v.P, &HP = v.HP, &PHT = v.PHT, &S = v.S, &K = v.K, &A = v.KHI, &T = v.T;
   int rc = ensure_dense(c);   // (mixed stacking / a leading block: the in-state rows are rebuilt densely next to the rows already in place)
@@ -384,13 +381,12 @@ static int update_dense_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Upd
     rc = ensure_HT(c);   // the gate reads (and neutralises) the transposed rows
     if (rc) return rc;
     GateDenseArgs a{};
-    H.to(a.H, a.strideH, a.ldh); HP.to(a.HP, a.strideHP, a.ldhp);
-    a.Hw = H.p; HT.to(a.HTw, a.strideHT, a.ldht);
-    a.HPw = HP.p; a.PHTw = PHT.p; a.PHTr = PHT.p;
+    H.to(a.Hw, a.strideH, a.ldh); HT.to(a.HTw, a.strideHT, a.ldht);
+    HP.to(a.HPw, a.strideHP, a.ldhp); a.PHTw = PHT.p; a.PHTr = PHT.p;
     v.inn.to(a.inn, a.strideInn); v.diagR.to(a.diagR, a.strideR);
     a.mask = c->mask + (long)b0 * gate->F; a.dist = c->dist + (long)b0 * gate->F;
     a.F = gate->F; a.Np = Np; a.batch = B;
-    a.R = gate->R; a.thresh = gate->thresh; a.mult = gate->mult; a.min_inliers = gate->min_inliers;
+    a.gp = gate->gp;
     a.ell = c->ell; a.have_ell = 0;
     StageTimer st(c, ST_GATE, 0.0, "gate_dense_kernel");
     HIP_TRY((hipError_t)launch_gate_dense(a, c->stream));
@@ -438,7 +434,7 @@ static int update_dense_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Upd
 // could not factor: Eigen's diagonally pivoted L D L^T (what src/estimator.cpp:1266 runs for EVERY filter) and the
 // as-coded Joseph update, on exactly those filters (ldlt_fallback.hip). Every pipeline leaves the covariance of such a
 // filter untouched and its status set, so the fallback starts from the prior.
-static int update_joseph_range(xivo_hip_ctx* c, int b0, int B, const GateParams* gate = nullptr) {
+static int update_joseph_range(xivo_hip_ctx* c, int b0, int B, const UpdateGate* gate = nullptr) {
   const UpdateViews v = views_from(c, b0);
   const UpdatePlan plan = plan_update(c, b0, B, gate != nullptr);
   c->last_path = plan.sparse ? 1 : 0;
@@ -467,7 +463,7 @@ static int update_joseph_range(xivo_hip_ctx* c, int b0, int B, const GateParams*
 // Filters are independent, so the batch is walked in chunks (XIVO_HIP_CHUNK) whose intermediates (HP, PH^T, S, K, A, T:
 // ~2.7 MB per filter at N=250/M=160) stay resident in the 256 MiB Infinity Cache between consecutive kernels instead of
 // round-tripping HBM.
-static int update_chunks(xivo_hip_ctx* c, int B, const GateParams* gate) {
+static int update_chunks(xivo_hip_ctx* c, int B, const UpdateGate* gate) {
   const int chunk = c->chunk > 0 ? c->chunk : B;
   c->call_batch = chunk < B ? B : 0;
   for (int b0 = 0; b0 < B; b0 += chunk) {
@@ -651,12 +647,12 @@ int xivo_hip_update_dense_gated(xivo_hip_ctx* c, int B, int F, double R, double 
                                 int min_inliers) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || B <= 0 || B > c->Bmax || c->rows.rows_padded() <= 0 || F <= 0 || 2 * F > c->rows.rows()) return XIVO_HIP_ERR_INVALID;
-  if (bad_gate_params(R, mh_thresh, mh_mult)) return XIVO_HIP_ERR_INVALID;
+  const UpdateGate gate{F, {R, mh_thresh, mh_mult, min_inliers}};
+  if (bad_gate_params(gate.gp)) return XIVO_HIP_ERR_INVALID;
   int rc = ensure_gate_buffers(c, F);
   if (rc) return rc;
-  GateParams gp{F, R, mh_thresh, mh_mult, min_inliers};
   // Estimator::OutlierRejection only gates when F > min_required_inliers_ (src/manager.cpp:635)
-  return update_chunks(c, B, F > min_inliers ? &gp : nullptr);
+  return update_chunks(c, B, F > min_inliers ? &gate : nullptr);
 }
 
 int xivo_hip_last_path(xivo_hip_ctx* c) { return c ? c->last_path : -1; }
@@ -826,13 +822,14 @@ int xivo_hip_mh_gate_dense(xivo_hip_ctx* c, int B, int F, double R, double mh_th
                            int min_inliers, unsigned char* mask_out, double* dist_out) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || B <= 0 || B > c->Bmax || F <= 0 || 2 * F > c->rows.rows()) return XIVO_HIP_ERR_INVALID;
-  if (bad_gate_params(R, mh_thresh, mh_mult)) return XIVO_HIP_ERR_INVALID;
+  GateDenseArgs a{};
+  a.gp = {R, mh_thresh, mh_mult, min_inliers};
+  if (bad_gate_params(a.gp)) return XIVO_HIP_ERR_INVALID;
   int rc = ensure_gate_buffers(c, F);
   if (rc) return rc;
   rc = ensure_dense(c);
   if (rc) return rc;
-  GateDenseArgs a{};
-  a.mask = c->mask; a.dist = c->dist; a.F = F; a.R = R; a.thresh = mh_thresh; a.mult = mh_mult; a.min_inliers = min_inliers; a.have_ell = 1;
+  a.mask = c->mask; a.dist = c->dist; a.F = F; a.have_ell = 1;
   rc = gate_dense_rows(c, B, a);
   if (rc) return rc;
   c->rows.gate_wrote(GateLayout::packed);

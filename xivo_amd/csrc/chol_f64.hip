@@ -373,41 +373,22 @@ __global__ __launch_bounds__(256, MINB) void chol_reg_la_f64_kernel(CholArgs g, 
     double* inn = gt.inn + (long)filt * gt.strideInn;
     double* dr = gt.diagR + (long)filt * gt.strideR;
     const double* sd = gt.Sdiag + (long)filt * gt.strideSdiag;
-    for (int f = tid; f < F; f += 256) {                 // (gate_ell_body, from_S with the compact diagonal blocks)
-      const double s00 = sd[4 * f] - dr[2 * f] + gt.R;
-      const double s10 = sd[4 * f + 2];
-      const double s11 = sd[4 * f + 3] - dr[2 * f + 1] + gt.R;
-      sdist[f] = mh_dist_2x2(s00, s10, s11, inn[2 * f], inn[2 * f + 1]);
-    }
+    for (int f = tid; f < F; f += 256)                   // (the compact diagonal blocks, [row in block][column in block])
+      sdist[f] = gate_dist_S(sd[4 * f], sd[4 * f + 2], sd[4 * f + 3], dr[2 * f], dr[2 * f + 1], gt.gp.R, inn[2 * f], inn[2 * f + 1]);
     for (int m = tid; m < 16 * NB; m += 256) sRej[m] = 0;
-    __syncthreads();
-    if (wave == 0) {
-      const double th = relax_threshold(sdist, F, gt.thresh, gt.mult, gt.min_inliers, lane);
-      if (lane == 0) sdist[F] = th;
-    }
-    __syncthreads();
-    const double th = sdist[F];
+    const double th = gate_threshold(sdist, F, wave, lane, [&] { return relax_threshold(sdist, F, gt.gp, lane); });
     for (int f = tid; f < F; f += 256) {
-      const bool in = sdist[f] < th;
-      gt.mask[(long)filt * F + f] = in ? 1 : 0;
-      gt.dist[(long)filt * F + f] = sdist[f];
-      if (!in) {
-        sRej[2 * f] = 1; sRej[2 * f + 1] = 1;
-        inn[2 * f] = 0.0; inn[2 * f + 1] = 0.0;
-        dr[2 * f] = 1.0; dr[2 * f + 1] = 1.0;
-        double* val = gt.ellval + (long)filt * gt.strideVal + (long)f * gt.ell_w * 2;
-        for (int t = 0; t < 2 * gt.ell_w; ++t) val[t] = 0.0;
-      }
+      if (gate_verdict(sdist, f, th, gt.mask, gt.dist, (long)filt * F + f)) continue;
+      sRej[2 * f] = 1; sRej[2 * f + 1] = 1;
+      gate_reject_pair(inn, dr, f, gt.ellval + (long)filt * gt.strideVal + (long)f * gt.ell_w * 2, 2 * gt.ell_w);
     }
     __syncthreads();
     double* PHT = gt.PHT + (long)filt * gt.stridePHT;    // the solve's right-hand sides: columns of the rejected pairs
-    for (int f = 0; f < F; ++f) {
-      if (!sRej[2 * f]) continue;
-      for (int n = tid; n < gt.Np; n += 256) { PHT[n + (long)(2 * f) * gt.ldpht] = 0.0; PHT[n + (long)(2 * f + 1) * gt.ldpht] = 0.0; }
-    }
+    for (int f = 0; f < F; ++f)
+      if (sRej[2 * f]) gate_zero_rows(PHT, gt.ldpht, f, gt.Np, tid, 256);
     __syncthreads();                                      // sRow is scratch no longer
   }
-  // element (row, col) of S as the gate leaves it: rows / columns of rejected pairs decoupled (gate_ell_body's in-place edit)
+  // element (row, col) of S as the gate leaves it: rows / columns of rejected pairs decoupled (gate_ell_kernel's in-place edit)
   auto gated = [&](double v, int row, int col) -> double {
     if constexpr (GATE) return (sRej[row] | sRej[col]) ? (row == col ? 1.0 : 0.0) : v;
     else return v;

@@ -91,6 +91,10 @@ struct CholArgs {
   int batch;
   int latency;      // the solve behind it takes the latency route (streamed kernel: reads the mirrored upper triangle)
 };
+// The parameters of Estimator::MHGating (src/update.cpp:60-96; gate_device.h), as every gating kernel takes them: the
+// measurement variance of S_f = J P J^T + R I2, the chi-square threshold, the factor the relaxation loop multiplies it by
+// while fewer than min_inliers entries pass
+struct GateParams { double R, thresh, mult; int min_inliers; };
 // MH gating folded into the prologue of the factorisation (chol_f64.hip, GATE instantiations): what gate_ell_kernel takes,
 // minus S (the factorisation applies the decoupling of the rejected pairs where it loads S)
 struct CholGateArgs {
@@ -101,7 +105,7 @@ struct CholGateArgs {
   double* PHT; long stridePHT; int ldpht; int Np;
   unsigned char* mask; double* dist;        // [batch x F]
   int F;
-  double R, thresh, mult; int min_inliers;
+  GateParams gp;
 };
 bool chol_gate_supported(int Mp, int batch);
 int launch_chol_f64(const CholArgs& args, hipStream_t stream, const CholGateArgs* gate = nullptr);

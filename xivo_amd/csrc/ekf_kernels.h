@@ -1,5 +1,5 @@
 // Launchers of the EKF-specific (non-GEMM) kernels, one section per translation unit: state_kernels.hip,
-// traj_kernels.hip, score_kernels.hip, map_kernels.hip, glevel_kernels.hip, pool_kernels.hip, propagate_kernels.hip, then ldlt_fallback.hip and dropin.hip.
+// traj_kernels.hip, score_kernels.hip, map_kernels.hip, glevel_kernels.hip, gate_kernels.hip, pool_kernels.hip, propagate_kernels.hip, then ldlt_fallback.hip and dropin.hip.
 #pragma once
 #include "common.h"
 #include "ell.h"
@@ -219,37 +219,6 @@ struct SceneBuffers {
 };
 int launch_jac_instate(const SceneBuffers& sb, const xivo_layout& lay, const xivo_cam& cam, int batch,
                        hipStream_t s);
-struct GateArgs {
-  SceneBuffers sb; xivo_layout lay;
-  const double* P; long strideP; int ldp;
-  double R, thresh, mult; int min_inliers; int batch; int use_gating;
-};
-int launch_gate_sparse(const GateArgs& a, hipStream_t s);
-// the launch choices below are made here only: the launch and xivo_hip_selftest_glevel_launch (capi_glevel.hip) call the same
-// functions. Each writes the stage label (the kernel as rocprofv3 names it; the gate's block size after an '@') to label[n].
-// gate_sparse_kernel: threads per filter - 1024 below 256 filters, 256 from there, halved while the LDS passes 64 KB
-// (online-calibration builds, wide != 0, carry more scratch per wave)
-int gate_sparse_threads(int batch, int F, int wide, char* label, size_t n);
-
-// dense-row Mahalanobis gating (update.cpp:60-96) + neutralising rejected rows
-struct GateDenseArgs {
-  const double* H; long strideH; int ldh;       // candidate rows (J of feature f = rows 2f, 2f+1)
-  const double* HP; long strideHP; int ldhp;    // H * P of the same rows
-  double* Hw; double* HTw; long strideHT; int ldht;  // H / H^T to neutralise
-  double* HPw; double* PHTw;                         // optional: HP / (HP)^T rows to neutralise too
-  const double* PHTr;                                // (HP)^T = P H^T of the candidate rows [Np x Mp]
-  double* inn; long strideInn;
-  double* diagR; long strideR;
-  unsigned char* mask; double* dist;            // [batch x F]  (row stride mask_ld when it is set)
-  int F, Np, batch;
-  double R, thresh, mult; int min_inliers;
-  EllBuffers ell; int have_ell;                 // also zero the rejected pairs of the compressed form (ell.h)
-  int mask_ld;                                  // 0: rows of mask / dist are F entries apart
-  const xivo_feat_in* feats; int Fmax;          // optional [batch x Fmax]: entries with sind < 0 are absent (ragged batches)
-  int no_relax;                                 // 1: inlier <=> distance < thresh, no relaxation loop (min_inliers = -1: every filter tested)
-};
-int launch_gate_dense(const GateDenseArgs& a, hipStream_t s);
-
 struct StackArgs {
   SceneBuffers sb; xivo_layout lay; MeasBuffers mb;
   int Mp, Np, batch; double R; int fix_group_block;
@@ -385,6 +354,41 @@ int launch_ransac_select(const RansacArgs& a, hipStream_t s);
 int launch_ransac_zero(const RansacArgs& a, double* P, hipStream_t s);
 int launch_ransac_rescue(const RansacArgs& a, hipStream_t s);
 int launch_ransac_rescue_dist(const RansacArgs& a, const double* dist /* [batch x ld] */, int ld, hipStream_t s);
+
+// ================================================================ gate_kernels.hip: the stand-alone MH gates (capi_glevel.hip, capi_update.hip, capi_ransac.hip)
+// (gate_ell_kernel, the third of them, takes the compressed rows: its arguments and launcher are in ell.h)
+
+struct GateArgs {
+  SceneBuffers sb; xivo_layout lay;
+  const double* P; long strideP; int ldp;
+  GateParams gp; int batch; int use_gating;
+};
+int launch_gate_sparse(const GateArgs& a, hipStream_t s);
+// the launch choices below are made here only: the launch and xivo_hip_selftest_glevel_launch (capi_glevel.hip) call the same
+// functions. Each writes the stage label (the kernel as rocprofv3 names it; the gate's block size after an '@') to label[n].
+// gate_sparse_kernel: threads per filter - 1024 below 256 filters, 256 from there, halved while the LDS passes 64 KB
+// (online-calibration builds, wide != 0, carry more scratch per wave)
+int gate_sparse_threads(int batch, int F, int wide, char* label, size_t n);
+
+// dense-row Mahalanobis gating (update.cpp:60-96) + neutralising rejected rows
+struct GateDenseArgs {
+  // candidate rows (J of feature f = rows 2f, 2f+1): H [Mp x Np] and H^T [Np x Mp], read through H^T and neutralised in both
+  double* Hw; long strideH; int ldh;
+  double* HTw; long strideHT; int ldht;
+  double* HPw; long strideHP; int ldhp;              // optional: H P / (HP)^T rows to neutralise too (PHTw: strides of H^T)
+  double* PHTw;
+  const double* PHTr;                                // (HP)^T = P H^T of the candidate rows [Np x Mp]
+  double* inn; long strideInn;
+  double* diagR; long strideR;
+  unsigned char* mask; double* dist;            // [batch x F]  (row stride mask_ld when it is set)
+  int F, Np, batch;
+  GateParams gp;
+  EllBuffers ell; int have_ell;                 // also zero the rejected pairs of the compressed form (ell.h)
+  int mask_ld;                                  // 0: rows of mask / dist are F entries apart
+  const xivo_feat_in* feats; int Fmax;          // optional [batch x Fmax]: entries with sind < 0 are absent (ragged batches)
+  int no_relax;                                 // 1: inlier <=> distance < thresh, no relaxation loop (min_inliers = -1: every filter tested)
+};
+int launch_gate_dense(const GateDenseArgs& a, hipStream_t s);
 
 // ================================================================ pool_kernels.hip: depth sub-filter and feature pool
 

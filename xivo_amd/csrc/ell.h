@@ -65,25 +65,25 @@ enum EllMode : int {
   ELL_G = 2,    // Src = T  [Np x Np] : out = T H^T + K diag(R)  [Np x Mp]               (re-associated :1280-1287)
   ELL_GF = 3,   // ELL_G with the result stored as float (slab form only; strideOut / ldo in float elements)
 };
-// Estimator::MHGating numeric core (src/update.cpp:60-96) on the ELL rows: S_f = H_f (P H_f^T) + R I2
-// from the already formed P H^T, threshold relaxation, then neutralisation of the rejected pairs
-// (ELL values, H / H^T / HP / P H^T rows = 0, inn = 0, diagR = 1).
+// Estimator::MHGating (src/update.cpp:60-96; gate_device.h) on the ELL rows, gate_ell_kernel (gate_kernels.hip): S = H P H^T +
+// diag(R) of ALL candidate rows is already formed (ell<S>); the 2 x 2 blocks S_f are read off its diagonal, the threshold is
+// relaxed, and the rejected pairs are neutralised (ELL values, H / H^T / P H^T rows = 0, inn = 0, diagR = 1) and their rows /
+// columns of S decoupled in place (0, unit diagonal).
 struct GateEllArgs {
   EllBuffers ell;
-  double* H; long strideH; int ldh;        // dense copies kept consistent for xivo_hip_get_H
+  double* H; long strideH; int ldh;        // dense copies kept consistent for xivo_hip_get_H (or null)
   double* HT; long strideHT; int ldht;
-  double* HP; double* PHT;                 // same shapes / strides as H / HT
+  double* PHT;                             // same shape / strides as HT
   double* inn; long strideInn;
   double* diagR; long strideR;
   unsigned char* mask; double* dist;       // [batch x F]
   int F, Np, batch;
-  double R, thresh, mult; int min_inliers;
-  // from_S: S = H P H^T + diag(R) of ALL candidate rows is already formed (ell<S>); the 2x2 blocks S_f are read
-  // off its diagonal and the rows / columns of the rejected pairs are then decoupled in place (0, unit diagonal)
-  double* S; long strideS; int lds; int Mp; int from_S;
-  // from_S, optional: the 2 x 2 diagonal blocks of S as the S kernel left them, [pair][row in block][column in block]
+  GateParams gp;
+  double* S; long strideS; int lds; int Mp;
+  // optional: the 2 x 2 diagonal blocks of S as the S kernel left them, [pair][row in block][column in block]
   // (32 contiguous bytes per feature instead of three cache lines 2 lds doubles apart: the gate's reads of S were 3.9 M
-  // random 64-byte fetches per 16384 filters); same values bit for bit. null: read them off S.
+  // random 64-byte fetches per 16384 filters); same values bit for bit. null: read them off S (mixed stacking, a leading
+  // calibration block, 32-wide slabs).
   const double* Sdiag; long strideSdiag;
 };
 struct EllMulArgs {
@@ -105,11 +105,6 @@ struct EllMulArgs {
   int nc_max;   // upper bound of nc over the filters of the launch (host mirror)
   int pw_max;   // upper bound of pw (0 = unknown -> ELL_PW)
   int batch;
-  // ELL_S only: run the gate (src/update.cpp:60-96, gate.from_S semantics) in the tail of the S kernel when one workgroup
-  // forms the whole S of its filter (big batches); *gate_done tells the caller whether that happened (else: launch_gate_ell)
-  GateEllArgs gate;
-  int gate_here;
-  int* gate_done;
 };
 int launch_ell_mul(int mode, const EllMulArgs& a, hipStream_t s);
 // name of the kernel instantiation launch_ell_mul runs for these arguments

@@ -14,7 +14,7 @@ struct FusedArgs {
   int* status;                               // out: 0, or 1 + the first non-positive pivot
   int Np, Mp, batch;
   // MH gating (src/update.cpp:60-96) in front of the factorisation; gate = 0: none
-  int gate, F; double R, thresh, mult; int min_inliers;
+  int gate, F; GateParams gp;
   unsigned char* mask; double* dist;         // [batch x F]
   double* H; long strideH; int ldh;          // dense copies of the stacked rows kept consistent with the gate (or null)
   double* HT; long strideHT; int ldht;

@@ -435,34 +435,30 @@ __global__ __launch_bounds__(64 * NWV, 1) void fused_update_f64_kernel(FusedArgs
   }
   FTR(3);
 
-  // ---- 3  Estimator::MHGating on the diagonal of S (gate_ell_body, from_S): same expressions, same bits
+  // ---- 3  Estimator::MHGating on the diagonal of S (gate_device.h; what gate_ell_kernel does): same expressions, same bits
   if (g.gate) {
     const int F = g.F;
     for (int f = tid; f < F; f += NT) {
       const double* d = sD + ((2 * f) >> 4) * BLK;
       const int o = (2 * f) & 15;
-      const double s00 = d[o + 17 * o] - sR[2 * f] + g.R;
-      const double s10 = d[o + 1 + 17 * o];
-      const double s11 = d[o + 1 + 17 * (o + 1)] - sR[2 * f + 1] + g.R;
-      sdist[f] = mh_dist_2x2(s00, s10, s11, sInn[2 * f], sInn[2 * f + 1]);
+      sdist[f] = gate_dist_S(d[o + 17 * o], d[o + 1 + 17 * o], d[o + 1 + 17 * (o + 1)], sR[2 * f], sR[2 * f + 1], g.gp.R,
+                             sInn[2 * f], sInn[2 * f + 1]);
     }
     lds_barrier();
     // (every wave runs the relaxation loop on the distances in LDS and arrives at the same threshold: one barrier fewer
     //  than a single wave publishing it)
-    const double th = relax_threshold(sdist, F, g.thresh, g.mult, g.min_inliers, lane);
+    const double th = relax_threshold(sdist, F, g.gp, lane);
     for (int f = tid; f < F; f += NT) {
-      const bool in = sdist[f] < th;
-      g.mask[(long)filt * F + f] = in ? 1 : 0;
-      g.dist[(long)filt * F + f] = sdist[f];
-      if (!in) {
-        sAny = 1;
-        sRej[2 * f] = 1; sRej[2 * f + 1] = 1;
-        sInn[2 * f] = 0.0; sInn[2 * f + 1] = 0.0;
-        innG[2 * f] = 0.0; innG[2 * f + 1] = 0.0;
-        dRG[2 * f] = 1.0; dRG[2 * f + 1] = 1.0;
-        double* val = g.ell.val + (long)filt * g.ell.stride_val() + (long)f * ELL_W * 2;
-        for (int t = 0; t < 2 * ELL_W; ++t) val[t] = 0.0;
-      }
+      if (gate_verdict(sdist, f, th, g.mask, g.dist, (long)filt * F + f)) continue;
+      sAny = 1;
+      sRej[2 * f] = 1; sRej[2 * f + 1] = 1;
+      sInn[2 * f] = 0.0; sInn[2 * f + 1] = 0.0;      // (the copy in LDS the solve reads)
+      // gate_reject_pair and, below, gate_zero_rows written out: called from here they cost this kernel scalar registers
+      // (up to 5 more SGPR spills in the seven-block instantiations), DESIGN.md section 5
+      innG[2 * f] = 0.0; innG[2 * f + 1] = 0.0;
+      dRG[2 * f] = 1.0; dRG[2 * f + 1] = 1.0;
+      double* val = g.ell.val + (long)filt * g.ell.stride_val() + (long)f * ELL_W * 2;
+      for (int t = 0; t < 2 * ELL_W; ++t) val[t] = 0.0;
     }
     lds_barrier();
     if (sAny) {                                    // (the common case - every candidate passes - ends here)

@@ -1,9 +1,7 @@
-// Feature-level kernels of the EKF update (gfx950), driven by capi_glevel.hip: Jacobians, both gates, stacking, OOS and
-// loop-closure rows, OOS compression, Givens / QR and OnePointRANSAC.
+// Feature-level kernels of the EKF update (gfx950), driven by capi_glevel.hip: Jacobians, stacking, OOS and
+// loop-closure rows, OOS compression, Givens / QR and OnePointRANSAC. (The MH gates: gate_kernels.hip.)
 //
 //  jac_instate_kernel   Feature::ComputeJacobian           src/feature.cpp:542-656
-//  gate_sparse_kernel   Estimator::MHGating                src/update.cpp:50-116
-//  gate_dense_kernel    same numeric core on dense J rows  src/update.cpp:60-96
 //  stack_kernel         FilterUpdate stacking + Feature::FillJacobianBlock
 //                                                          src/update.cpp:129-138, src/feature.cpp:658-684
 //  oos_kernel           ComputeOOSJacobian(+Internal) + SlowGivens
@@ -22,7 +20,7 @@
 
 #include "ekf_kernels.h"
 #include "camera_device.h"
-#include "gate_device.h"
+#include "feature_chi2_device.h"
 #include "geometry_device.h"
 
 namespace xivo_hip {
@@ -167,284 +165,6 @@ __global__ void jac_instate_kernel(SceneBuffers sb, xivo_layout lay, xivo_cam ca
   double* inn = sb.finn + ((long)filt * sb.Fmax + f) * 2;
   inn[0] = ft.xp[0] - xp[0];   // feature.cpp:654-655
   inn[1] = ft.xp[1] - xp[1];
-}
-
-// column of the error state that compact-J column c (0..20) maps to
-__device__ __forceinline__ int jcol(const xivo_layout& lay, const xivo_feat_in& ft, int c) {
-  const int b = c / 3, o = c % 3;
-  switch (b) {
-    case 0: return 0 + o;    // Index::Wsb  (core.h:41)
-    case 1: return 3 + o;    // Index::Tsb
-    case 2: return 15 + o;   // Index::Wbc
-    case 3: return 18 + o;   // Index::Tbc
-    case 4: return lay.group_begin + 6 * ft.ref_sind + o;
-    case 5: return lay.group_begin + 6 * ft.ref_sind + 3 + o;
-    default: return lay.feature_begin + 3 * ft.sind + o;
-  }
-}
-
-// res^T (J P J^T + R I2)^-1 res of one feature by one wave64 (src/update.cpp:60-70, :352-356): the 21 x 21 sub-block of
-// P the full row J touches, lane (a, c) forming (P J^T)(a, c) in ascending b, reduced across lanes, 2x2 LLT. The value is
-// valid in every lane. The gathers of P are issued as seven wave-wide loads: the wave parks the sub-block (element
-// e = a + 21 b in lane e mod 64) and the two rows of J in its own LDS scratch and reads its operands from there. (The first
-// version had every lane (a, c) gather its 21 elements itself - 42 gather instructions per feature, half of them duplicates
-// between the c = 0 and c = 1 lanes - and the gate kernel was bound by the number of 8-byte gathers a CU's address unit
-// retires, not by memory latency: 0.40 -> 0.28 ms per 4096 filters x 60 features, same bits.) scratch: 441 + 42 doubles.
-__device__ __forceinline__ double feature_chi2_lds(const double* P, int ldp, const xivo_layout& lay, const xivo_feat_in& ft,
-                                                   const double* J, const double* inn, double R, int lane, double* scratch) {
-  double* sP = scratch;          // [a + 21 b]
-  double* sJ = scratch + 441;    // [c * 21 + b]
-  double pv[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    const int e = lane + 64 * k;
-    const int ea = e < 441 ? e % 21 : 0, eb = e < 441 ? e / 21 : 0;
-    pv[k] = P[jcol(lay, ft, ea) + (long)jcol(lay, ft, eb) * ldp];
-  }
-  const double jmine = lane < 42 ? J[lane] : 0.0;
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    const int e = lane + 64 * k;
-    if (e < 441) sP[e] = pv[k];
-  }
-  if (lane < 42) sJ[lane] = jmine;
-  __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's own LDS writes are done (one wave, no barrier needed)
-  __builtin_amdgcn_wave_barrier();
-  double v = 0.0;
-  const int ra = lane % 21, rc = lane / 21;
-  if (lane < 42) {
-#pragma unroll
-    for (int b = 0; b < 21; ++b) v = fma(sP[ra + 21 * b], sJ[rc * 21 + b], v);
-  }
-  const double j0 = lane < 42 ? sJ[ra] : 0.0, j1 = lane < 42 ? sJ[21 + ra] : 0.0;
-  __builtin_amdgcn_wave_barrier();      // (the next feature's writes stay behind these reads: program order within the wave)
-  double s00 = (lane < 21) ? j0 * v : 0.0;
-  double s10 = (lane < 21) ? j1 * v : 0.0;
-  double s11 = (lane >= 21 && lane < 42) ? j1 * v : 0.0;
-  s00 = wave_sum(s00) + R;
-  s10 = wave_sum(s10);
-  s11 = wave_sum(s11) + R;
-  return mh_dist_2x2(s00, s10, s11, inn[0], inn[1]);
-}
-
-// One workgroup per filter (4 waves; 16 for fewer than 256 filters - latency); a wave64 per feature computes S = J P J^T + R I2
-// from the 21 x 21 sub-block of P the feature touches (J is structurally
-// sparse), reduces it across lanes, and the 2x2 LLT gives the Mahalanobis
-// distance. Then one wave runs the threshold-relaxation loop.
-// Online-calibration builds: J() has 22 more columns EVERY feature shares - td, Cg (9), bg (3), the intrinsics (9 slots) - next
-// to the 21 of the default build (src/feature.cpp:623-651); 12 of those 21 (Wsb, Tsb, Wbc, Tbc) are shared as well. The 34 x 34
-// block of P on the shared columns is therefore the same for all features of a filter: the workgroup parks it in LDS once,
-// and a feature gathers only its 9 private columns (group, feature) against the shared ones and themselves - 387 elements,
-// seven wave-wide loads as in the default build, instead of the 43 x 43 = 1849 of a gather per feature (2.0 -> 0.46 ms per 4096
-// filters x 60 features at N = 276). The sums run over the 43 columns in the order of the whole row, as before.
-constexpr int WIDE_NS = 34, WIDE_NP = 9, WIDE_NC = 43;
-constexpr int WIDE_X = WIDE_NS * WIDE_NP, WIDE_Y = WIDE_NP * WIDE_NP;         // P[shared, private] | P[private, private]
-constexpr int WIDE_SCR = WIDE_X + WIDE_Y + 2 * WIDE_NC + 1;                   // doubles of LDS scratch per wave (474)
-constexpr int WIDE_PSS = WIDE_NS * WIDE_NS;                                   // doubles of the per-filter shared block
-__device__ __forceinline__ int wide_scol(const xivo_calib_layout& cl, int s) {   // state column of shared slot s
-  if (s < 6) return s;                                    // Index::Wsb, Tsb
-  if (s < 12) return 15 + (s - 6);                        // Index::Wbc, Tbc
-  const int k = s - 12;                                   // the layout of Jc: td | Cg 9 | bg 3 | intrinsics 9
-  if (k == 0) return cl.td >= 0 ? cl.td : 0;              // (a block that is switched off carries zeros in Jc: any valid column will do)
-  if (k < 10) return cl.Cg >= 0 ? cl.Cg + (k - 1) : 0;
-  if (k < 13) return 9 + (k - 10);                        // Index::bg
-  return (k - 13) < cl.cam_dim ? cl.cam_begin + (k - 13) : 0;
-}
-__device__ __forceinline__ double feature_chi2_wide(const double* P, int ldp, const xivo_layout& lay, const xivo_calib_layout& cl,
-                                                    const xivo_feat_in& ft, const double* J, const double* Jc, const double* inn, double R,
-                                                    int lane, const double* sPss, double* scratch) {
-  double* X = scratch;                        // [s + 34 p] = P[shared s, private p]
-  double* Y = scratch + WIDE_X;               // [p + 9 q]
-  double* sJ = scratch + WIDE_X + WIDE_Y;     // [row * 43 + w], w in the order of the whole row: 12 common | 9 private | 22 calibration
-  auto pcol = [&](int q) -> int { return q < 6 ? lay.group_begin + 6 * ft.ref_sind + q : lay.feature_begin + 3 * ft.sind + (q - 6); };
-  double pv[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    const int e = lane + 64 * k;
-    int row = 0, col = 0;
-    if (e < WIDE_X) { row = wide_scol(cl, e % WIDE_NS); col = pcol(e / WIDE_NS); }
-    else if (e < WIDE_X + WIDE_Y) { const int q = e - WIDE_X; row = pcol(q % WIDE_NP); col = pcol(q / WIDE_NP); }
-    pv[k] = P[row + (long)col * ldp];
-  }
-  double j0 = 0.0, j1 = 0.0;
-  if (lane < WIDE_NC) { j0 = lane < 21 ? J[lane] : Jc[lane - 21]; j1 = lane < 21 ? J[21 + lane] : Jc[22 + lane - 21]; }
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    const int e = lane + 64 * k;
-    if (e < WIDE_X + WIDE_Y) scratch[e] = pv[k];
-  }
-  if (lane < WIDE_NC) { sJ[lane] = j0; sJ[WIDE_NC + lane] = j1; }
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
-  double v0 = 0.0, v1 = 0.0;
-  if (lane < WIDE_NC) {
-    // lane a of the whole row: shared (a < 12 or a >= 21: slot a or a - 9) or private (slot a - 12)
-    const bool ash = lane < 12 || lane >= 21;
-    const int as = lane < 12 ? lane : lane - 9, ap = lane - 12;
-    const double* ps = ash ? sPss + as : X + WIDE_NS * ap;   // P[a, shared b]: step over b
-    const int ss = ash ? WIDE_NS : 1;
-    const double* pp = ash ? X + as : Y + ap;                // P[a, private b]
-    const int sp = ash ? WIDE_NS : WIDE_NP;
-    for (int b = 0; b < 12; ++b) { const double p = ps[b * ss]; v0 = fma(p, sJ[b], v0); v1 = fma(p, sJ[WIDE_NC + b], v1); }
-    for (int b = 12; b < 21; ++b) { const double p = pp[(b - 12) * sp]; v0 = fma(p, sJ[b], v0); v1 = fma(p, sJ[WIDE_NC + b], v1); }
-    for (int b = 21; b < WIDE_NC; ++b) { const double p = ps[(b - 9) * ss]; v0 = fma(p, sJ[b], v0); v1 = fma(p, sJ[WIDE_NC + b], v1); }
-  }
-  __builtin_amdgcn_wave_barrier();
-  const double s00 = wave_sum(j0 * v0) + R;
-  const double s10 = wave_sum(j1 * v0);
-  const double s11 = wave_sum(j1 * v1) + R;
-  return mh_dist_2x2(s00, s10, s11, inn[0], inn[1]);
-}
-
-__global__ __launch_bounds__(1024) void gate_sparse_kernel(GateArgs a) {
-  const int filt = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nt = blockDim.x, nw = nt >> 6;   // 4 waves per filter for a big batch, 16 when few filters must finish fast
-  extern __shared__ double sdist[];
-  const SceneBuffers& sb = a.sb;
-  const double* P = a.P + (long)filt * a.strideP;
-  // entries present in this filter (sind >= 0); Estimator::OutlierRejection gates only when there are more
-  // than min_required_inliers_ of them (src/manager.cpp:635)
-  __shared__ int s_present;
-  if (tid == 0) s_present = 0;
-  __syncthreads();
-  // the two slot indices of every entry, parked in LDS by this pass: the per-feature loop below then starts its gathers of
-  // P and J right away instead of behind a load of the entry (two dependent memory round trips per feature, fifteen
-  // features per wave one after the other, were what the kernel's time was)
-  int* s_slot = reinterpret_cast<int*>(sdist + sb.F + 1);   // [2 F]: sind, ref_sind
-  double* s_pss = sdist + sb.F + 1 + (2 * sb.F + 1) / 2;    // online-calibration builds: P on the 34 shared columns
-  double* s_scr = s_pss + (sb.Jc ? WIDE_PSS : 0) + (long)wave * (sb.Jc ? WIDE_SCR : 484);   // per wave: feature_chi2_lds / _wide scratch
-  if (sb.Jc && a.use_gating) {
-    for (int e = tid; e < WIDE_PSS; e += nt) s_pss[e] = P[wide_scol(sb.cl, e % WIDE_NS) + (long)wide_scol(sb.cl, e / WIDE_NS) * a.ldp];
-  }
-  {
-    int cnt = 0;
-    for (int f = tid; f < sb.F; f += nt) {
-      const xivo_feat_in& ft = sb.feats[(long)filt * sb.Fmax + f];
-      const int si = ft.sind, rs = ft.ref_sind;
-      s_slot[2 * f] = si; s_slot[2 * f + 1] = rs;
-      cnt += si >= 0 ? 1 : 0;
-    }
-    if (cnt) atomicAdd(&s_present, cnt);
-  }
-  __syncthreads();
-  const int present = s_present;
-  const bool gating = a.use_gating && present > a.min_inliers;
-  if (gating) {
-    for (int f = wave; f < sb.F; f += nw) {
-      xivo_feat_in ft;                      // only the slots are read by feature_chi2 / jcol
-      ft.sind = s_slot[2 * f]; ft.ref_sind = s_slot[2 * f + 1];
-      if (ft.sind < 0) { if (lane == 0) sdist[f] = __builtin_inf(); continue; }
-      const double* J = sb.J + ((long)filt * sb.Fmax + f) * 42;
-      const double* inn = sb.finn + ((long)filt * sb.Fmax + f) * 2;
-      const double d = sb.Jc ? feature_chi2_wide(P, a.ldp, a.lay, sb.cl, ft, J, sb.Jc + ((long)filt * sb.Fmax + f) * 44, inn, a.R, lane, s_pss, s_scr)
-                             : feature_chi2_lds(P, a.ldp, a.lay, ft, J, inn, a.R, lane, s_scr);
-      if (lane == 0) sdist[f] = d;
-    }
-    __syncthreads();
-    if (wave == 0) {
-      const double th = relax_threshold(sdist, sb.F, a.thresh, a.mult, a.min_inliers, lane, present);
-      if (lane == 0) sdist[sb.F] = th;
-    }
-    __syncthreads();
-  }
-  const double th = gating ? sdist[sb.F] : 0.0;
-  for (int f = tid; f < sb.F; f += nt) {
-    const bool here = s_slot[2 * f] >= 0;
-    const bool in = gating ? (sdist[f] < th) : here;
-    sb.mask[(long)filt * sb.Fmax + f] = in ? 1 : 0;
-    sb.dist[(long)filt * sb.Fmax + f] = (gating && here) ? sdist[f] : 0.0;
-  }
-}
-
-// ---------------------------------------------------------------- dense-row gate
-__global__ __launch_bounds__(256) void gate_dense_kernel(GateDenseArgs a) {
-  const int filt = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  extern __shared__ double sdist[];  // F doubles + 1
-  const double* H = a.H + (long)filt * a.strideH;
-  const double* HP = a.HP + (long)filt * a.strideHP;
-  double* inn = a.inn + (long)filt * a.strideInn;
-  // S_f = (HP)_f H_f^T + R I2 from the TRANSPOSED copies (P H^T and H^T are [Np x Mp] with
-  // the state index contiguous), so every lane streams four contiguous columns.
-  const double* PHT = a.PHTr + (long)filt * a.strideHT;
-  const double* HT = a.HTw + (long)filt * a.strideHT;
-  // ragged batches (a.feats given): absent entries (sind < 0) were stacked as zero rows; they are no candidates - distance
-  // +inf, never an inlier, not counted - and a filter gates only with more than min_inliers present entries, exactly as
-  // gate_sparse_kernel does (src/manager.cpp:635)
-  __shared__ int s_present;
-  if (tid == 0) s_present = 0;
-  __syncthreads();
-  if (a.feats) {
-    int cnt = 0;
-    for (int f = tid; f < a.F; f += 256) cnt += a.feats[(long)filt * a.Fmax + f].sind >= 0 ? 1 : 0;
-    if (cnt) atomicAdd(&s_present, cnt);
-  }
-  __syncthreads();
-  const int present = a.feats ? s_present : a.F;
-  const bool gating = !a.feats || present > a.min_inliers;
-  for (int f = wave; f < a.F; f += 4) {
-    const bool here = !a.feats || a.feats[(long)filt * a.Fmax + f].sind >= 0;
-    if (!here || !gating) { if (lane == 0) sdist[f] = here ? 0.0 : __builtin_inf(); continue; }
-    double s00 = 0, s10 = 0, s11 = 0;
-    const double* p0 = PHT + (long)(2 * f) * a.ldht;
-    const double* p1 = p0 + a.ldht;
-    const double* h0 = HT + (long)(2 * f) * a.ldht;
-    const double* h1 = h0 + a.ldht;
-    for (int n = lane; n < a.Np; n += 64) {
-      const double hp0 = p0[n], hp1 = p1[n], hh0 = h0[n], hh1 = h1[n];
-      s00 = fma(hp0, hh0, s00);
-      s10 = fma(hp1, hh0, s10);
-      s11 = fma(hp1, hh1, s11);
-    }
-    s00 = wave_sum(s00) + a.R;
-    s10 = wave_sum(s10);
-    s11 = wave_sum(s11) + a.R;
-    if (lane == 0) sdist[f] = mh_dist_2x2(s00, s10, s11, inn[2 * f], inn[2 * f + 1]);
-  }
-  __syncthreads();
-  if (wave == 0) {
-    // (not gating: present entries carry 0, absent ones +inf - any positive threshold keeps exactly the present ones)
-    // (no_relax: a plain chi-square test against thresh - the rescue pass of OnePointRANSAC, update.cpp:352-356)
-    const double th = gating ? (a.no_relax ? a.thresh : relax_threshold(sdist, a.F, a.thresh, a.mult, a.min_inliers, lane, present)) : 1.0;
-    if (lane == 0) sdist[a.F] = th;
-  }
-  __syncthreads();
-  const double th = sdist[a.F];
-  for (int f = tid; f < a.F; f += 256) {
-    const bool in = sdist[f] < th;
-    a.mask[(long)filt * (a.mask_ld ? a.mask_ld : a.F) + f] = in ? 1 : 0;
-    a.dist[(long)filt * (a.mask_ld ? a.mask_ld : a.F) + f] = (gating && sdist[f] != __builtin_inf()) ? sdist[f] : 0.0;
-    if (!in) {
-      inn[2 * f] = 0.0; inn[2 * f + 1] = 0.0;
-      double* dr = a.diagR + (long)filt * a.strideR;
-      dr[2 * f] = 1.0; dr[2 * f + 1] = 1.0;
-      if (a.have_ell) {
-        double* ev = a.ell.val + (long)filt * a.ell.stride_val() + (long)f * ELL_W * 2;
-        for (int t = 0; t < 2 * ELL_W; ++t) ev[t] = 0.0;
-      }
-    }
-  }
-  // neutralise rejected rows of H / H^T
-  double* Hw = a.Hw + (long)filt * a.strideH;
-  double* HTw = a.HTw + (long)filt * a.strideHT;
-  for (int f = 0; f < a.F; ++f) {
-    if (sdist[f] < th) continue;
-    for (int n = tid; n < a.Np; n += 256) {
-      Hw[2 * f + (long)n * a.ldh] = 0.0;
-      Hw[2 * f + 1 + (long)n * a.ldh] = 0.0;
-      HTw[n + (long)(2 * f) * a.ldht] = 0.0;
-      HTw[n + (long)(2 * f + 1) * a.ldht] = 0.0;
-      if (a.HPw) {
-        double* HPw = a.HPw + (long)filt * a.strideHP;
-        double* PHTw = a.PHTw + (long)filt * a.strideHT;
-        HPw[2 * f + (long)n * a.ldhp] = 0.0;
-        HPw[2 * f + 1 + (long)n * a.ldhp] = 0.0;
-        PHTw[n + (long)(2 * f) * a.ldht] = 0.0;
-        PHTw[n + (long)(2 * f + 1) * a.ldht] = 0.0;
-      }
-    }
-  }
 }
 
 // Stack H (and H^T), inn, diagR for one filter: rows 2f, 2f+1 belong to feature
@@ -1361,27 +1081,6 @@ int launch_jac_instate(const SceneBuffers& sb, const xivo_layout& lay, const xiv
   const int tot = batch * sb.F;
   if (tot <= 0) return 0;
   hipLaunchKernelGGL(jac_instate_kernel, dim3((tot + 127) / 128), dim3(128), 0, s, sb, lay, cam, batch);
-  CHECK_LAUNCH();
-}
-// distances + threshold | slot indices | per-wave scratch of feature_chi2_lds (64 KB without an opt-in: fewer waves if F is large)
-static size_t gate_sparse_lds(int F, int wide, int nt) {
-  const size_t scr = wide ? WIDE_SCR : 484, pss = wide ? WIDE_PSS : 0;
-  return ((size_t)(F + 1) + (2 * F + 1) / 2 + pss + (size_t)(nt / 64) * scr) * sizeof(double);
-}
-int gate_sparse_threads(int batch, int F, int wide, char* label, size_t n) {
-  int nt = batch < 256 ? 1024 : 256;
-  while (nt > 64 && gate_sparse_lds(F, wide, nt) > 65536) nt /= 2;
-  if (label && n) snprintf(label, n, "gate_sparse_kernel@%d", nt);
-  return nt;
-}
-int launch_gate_sparse(const GateArgs& a, hipStream_t s) {
-  const int wide = a.sb.Jc ? 1 : 0;
-  const int nt = gate_sparse_threads(a.batch, a.sb.F, wide, nullptr, 0);
-  hipLaunchKernelGGL(gate_sparse_kernel, dim3(a.batch), dim3(nt), gate_sparse_lds(a.sb.F, wide, nt), s, a);
-  CHECK_LAUNCH();
-}
-int launch_gate_dense(const GateDenseArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(gate_dense_kernel, dim3(a.batch), dim3(256), (a.F + 1) * sizeof(double), s, a);
   CHECK_LAUNCH();
 }
 int launch_stack(const StackArgs& a, hipStream_t s) {
