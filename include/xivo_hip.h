@@ -1345,6 +1345,49 @@ int xivo_hip_lcmap_set_cov(xivo_hip_ctx* ctx, int b0, int nb, const double* cov)
 int xivo_hip_lcmap_get_cov(xivo_hip_ctx* ctx, int b0, int nb, double* cov);
 int xivo_hip_lcmap_get_cov_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_lcmap_cov_stats* stats);
 
+/* ---- loop closure inside the device life cycle ("immediate" mode, xivo_hip_life_*): every track carries a key, the in-state
+ * book keeps it per slot, and the add records and the queries of a frame are made where the book is - on the device. A frame:
+ *   xivo_hip_life_begin_keys (or _begin, _begin_tracks) -> xivo_hip_lcmap_add_resident -> update -> xivo_hip_absorb_error ->
+ *   xivo_hip_lcmap_close_resident -> [xivo_hip_update_joseph -> xivo_hip_absorb_error] -> xivo_hip_life_end
+ * The rules - which slot yields a record, which a query, where either lies in its filter's list - are lcmap_life_device.h's;
+ * what becomes of a record or a query is decided as xivo_hip_lcmap_add / _close decide it.
+ * on = 1 needs xivo_hip_life_config and xivo_hip_lcmap_config, and allocates: a key per track next to the track block (long long
+ * [batch_max][tracks_max], in the form the tracks are in) with two page-locked staging blocks of its own, feat_key per feature
+ * slot next to the book's feat_id (-1: free slot), the per-filter lists of add records and of queries (one row of n_features
+ * per filter with a count: no list position depends on another filter), what the begin call hands to the add call, and a copy of
+ * the first update's status. on = 0 releases them; so does every call that releases the track block or the map
+ * (xivo_hip_life_config, xivo_hip_pool_life_config, xivo_hip_pool_config, xivo_hip_lcmap_config). Off by default, and while
+ * off every other entry point behaves as it did without this call. XIVO_HIP_ERR_INVALID, nothing changed: no life cycle or no map
+ * configured, a frame open, on outside {0, 1}. XIVO_HIP_ERR_UNSUPPORTED: the context runs the pool life cycle
+ * (xivo_hip_pool_life_config), whose pool book carries no keys. */
+int xivo_hip_lcmap_life_config(xivo_hip_ctx* ctx, int on);
+/* xivo_hip_life_begin plus keys [off[B]], parallel to ids (negative: the track matches nothing and adds nothing). Needs
+ * xivo_hip_lcmap_life_config(1) (else XIVO_HIP_ERR_INVALID, nothing changed). With the option on, xivo_hip_life_begin gives every
+ * track the key -1, and xivo_hip_life_begin_tracks takes the keys the track producer left: the world-point index of every track
+ * (xivo_hip_pcw_tracks writes them while the option is on).
+ * With the option on a begin call of any kind decides but does not edit: the features the tracker dropped leave the book and
+ * become the frame's add records {b, slot, feat_key[slot]} in ascending slot order, the tracked ones take their pixel, and P and
+ * the scene stay as they were until xivo_hip_lcmap_add_resident - the map reads the leaving features from the state as it was. */
+int xivo_hip_life_begin_keys(xivo_hip_ctx* ctx, int B, int F, const int* off, const long long* ids, const double* meas, const long long* keys);
+/* xivo_hip_lcmap_add on the records the begin call of the open frame of B filters left on the device, then the removals that
+ * begin call decided (the edits xivo_hip_life_begin makes itself while the option is off). Once per frame, before the update.
+ * No upload, no host loop; enqueues only. XIVO_HIP_ERR_INVALID: the option is off, no frame of B filters is open, or the frame's
+ * records were consumed already. */
+int xivo_hip_lcmap_add_resident(xivo_hip_ctx* ctx, int B);
+/* xivo_hip_lcmap_close on queries made on the device, behind the frame's update and xivo_hip_absorb_error: one query {b, -1,
+ * feat_key[slot], the pixel the begin call stored} per slot that holds a feature, was associated with a track by the begin call
+ * and whose entry of the update's inlier mask is not zero, in ascending slot order. It also keeps the update's status of every
+ * filter, which xivo_hip_life_end then counts in not_spd instead of the second update's. n_closing_out as xivo_hip_lcmap_close:
+ * NULL - always stages, never waits; else waits, and stages nothing when no filter closes. Once per frame. XIVO_HIP_ERR_INVALID:
+ * the option is off, no frame of B filters is open, the frame's add call has not run or the close call ran already. */
+int xivo_hip_lcmap_close_resident(xivo_hip_ctx* ctx, int B, int* n_closing_out);
+/* Read-back for tests: feat_key host [nb][F] (F of the last frame call; -1: free slot). ent_key must be NULL (the pool book
+ * carries no keys). Synchronises. */
+int xivo_hip_lcmap_life_get_keys(xivo_hip_ctx* ctx, int b0, int nb, long long* feat_key, long long* ent_key);
+/* Read-back for tests of the keys the last xivo_hip_pcw_tracks left for filters [b0, b0 + nb), as xivo_hip_pcw_get_tracks reads
+ * the ids: keys host [nb][tracks_max], -1 behind the filter's count. Synchronises. */
+int xivo_hip_lcmap_life_get_track_keys(xivo_hip_ctx* ctx, int b0, int nb, long long* keys);
+
 /* ---- covariance propagation tail (src/rk4.cpp:92-102, src/estimator.cpp:590) */
 /* P_mm <- Pmm_new ; P_ms <- Phi P_ms ; P_sm <- P_sm Phi^T. Phi and Pmm_new
  * are nm x nm (nm = kMotionSize: 23, or up to 40 for the online-calibration builds), one pair per filter. */

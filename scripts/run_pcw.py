@@ -107,8 +107,13 @@ def main():
     ap.add_argument("-loop-closure", dest="loop_closure", action="store_true",
                     help="loop closure on the device-resident landmark map (SequenceConfig.loop_closure): the world-point index of "
                          "every track is its key, features that leave the state go to the map, returning points close the loop. "
-                         "-host python with the host life cycles (the C++ host side and the device life cycles carry no keys); "
-                         "the report gains the summed map counters (lcmap)")
+                         "-host python; with the host life cycles, or (-lc-lifecycle device) inside -lifecycle device; the C++ "
+                         "host side and the device pool life cycle carry no keys; the report gains the summed map counters (lcmap)")
+    ap.add_argument("-lc-lifecycle", dest="lc_lifecycle", default="host", choices=["host", "device"],
+                    help="-loop-closure: who feeds and queries the map - host: the runner's slot book, filter by filter, with a "
+                         "download of the inlier mask every frame; device (needs -lifecycle device): the keys ride in the track "
+                         "block and the resident book, the add records and the queries are made on the device "
+                         "(SequenceConfig.lc_lifecycle)")
     ap.add_argument("-lc-map-max", dest="lc_map_max", type=int, default=d.lc_map_max, help="-loop-closure: map entries per sequence")
     ap.add_argument("-lc-max", dest="lc_max", type=int, default=d.lc_max, help="-loop-closure: matches per sequence and frame")
     ap.add_argument("-lc-min-matches", dest="lc_min_matches", type=int, default=d.lc_min_matches,
@@ -158,11 +163,14 @@ def main():
             ap.error("-loop-closure and -innov-log exclude each other (the log holds one update per frame)")
         life.update(feature_init=a.feature_init, pool_lifecycle=a.pool_lifecycle, loop_closure=True, lc_map_max=a.lc_map_max,
                     lc_max=a.lc_max, lc_min_matches=a.lc_min_matches, lc_meas_std=a.lc_meas_std, lc_chi2=a.lc_chi2,
-                    lc_max_depth_var=a.lc_max_depth_var, lc_point_cov=bool(a.lc_point_cov), lc_revisit_gap=a.lc_revisit_gap)
+                    lc_max_depth_var=a.lc_max_depth_var, lc_point_cov=bool(a.lc_point_cov), lc_revisit_gap=a.lc_revisit_gap,
+                    lc_lifecycle=a.lc_lifecycle)
         try:
             sequence.check_lifecycle(sequence.SequenceConfig(**life))
         except ValueError as e:
             ap.error(str(e))
+    elif a.lc_lifecycle != "host":
+        ap.error("-lc-lifecycle device needs -loop-closure")
     if a.tracks == "device":
         life.update(track_source="device", npts=a.npts)
         if a.host == "cpp" and not a.vectorized:
@@ -287,7 +295,7 @@ def main():
         "N": cfg.N, "max_features": cfg.n_features, "integration": a.integration_method, "host": a.host,
         "lifecycle": a.lifecycle, "tracks": a.tracks, "feature_init": a.feature_init, "pool_lifecycle": a.pool_lifecycle,
         "cam_model": a.cam_model,
-        "loop_closure": bool(a.loop_closure),
+        "loop_closure": bool(a.loop_closure), **({"lc_lifecycle": a.lc_lifecycle} if a.loop_closure else {}),
         **({"lc_point_cov": bool(a.lc_point_cov), "lc_revisit_gap": a.lc_revisit_gap} if a.loop_closure else {}),
         "ate_m": {"median": float(np.median(ate)), "p90": float(np.quantile(ate, 0.9)), "max": float(ate.max())},
         **_consistency(out),

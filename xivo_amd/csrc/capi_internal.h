@@ -16,7 +16,8 @@
 //                       block that both device life cycles use
 //   capi_pool_lifecycle.hip  device pool life cycle ("subfilter" mode): the pool book, the two frame calls, counters
 //   capi_pcw.hip        point-cloud world: the resident worlds, the per-frame track producer, read-back
-//   capi_lcmap.hip      loop closure: the resident landmark map, its add / close calls, load / read-out, counters
+//   capi_lcmap.hip      loop closure: the resident landmark map, its add / close calls, load / read-out, counters; inside the
+//                       device life cycle: the keys beside the track block and the book, the resident add / close calls
 //   capi_trajsim.hip    trajectory producer: the simulated IMU records and ground-truth poses of a frame, the ground-truth log
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
@@ -303,6 +304,22 @@ struct LcMap {
   bool configured() const { return entries != nullptr; }
 };
 
+// loop closure inside the device life cycle (xivo_hip_lcmap_life_config, capi_lcmap.hip): keys [Bmax][tracks_max] beside the
+// track block (in the form the tracks are in) with their page-locked staging; feat_key [Bmax][book.ld] beside the book's
+// feat_id; the frame's add records recs [Bmax][book.ld] / n_recs [Bmax] and queries / n_queries of the same shape; tracked
+// [Bmax][book.ld] and rm [Bmax][2 + book.ld + n_groups], which the begin kernel leaves for the close and the add call; status
+// [Bmax], the first update's. stage: where the open frame stands
+struct LcLife {
+  enum Stage { kNone = 0, kBegun, kAdded, kClosed };
+  long long* keys = nullptr; PinnedUpload up;
+  long long* feat_key = nullptr;
+  xivo_lcmap_add_rec* recs = nullptr; int* n_recs = nullptr;
+  xivo_lcmap_query* queries = nullptr; int* n_queries = nullptr;
+  unsigned char* tracked = nullptr; int* rm = nullptr; int* status = nullptr;
+  Stage stage = kNone;
+  bool configured() const { return feat_key != nullptr; }
+};
+
 }  // namespace xivo_hip::capi
 
 struct xivo_hip_ctx {
@@ -384,6 +401,7 @@ struct xivo_hip_ctx {
   xivo_hip::capi::MapLog map;
   xivo_hip::capi::InnovLog innov;
   xivo_hip::capi::LcMap lcmap;
+  xivo_hip::capi::LcLife lclife;
   // "a device life cycle exists" (whichever: the book and the track block are its)
   bool life_cycle_configured() const { return life.configured() || plife.configured(); }
 };
@@ -530,6 +548,15 @@ bool frame_can_begin(const xivo_hip_ctx* c, int B, int F);
 // the form they are in; and what their end kernels take of the update
 LifeArgs life_args_common(xivo_hip_ctx* c, int B);
 void life_args_update(xivo_hip_ctx* c, LifeArgs& a);
+
+// ---- capi_lcmap.hip
+// loop closure inside the device life cycle (LcLife above). Everything xivo_hip_lcmap_life_config allocated goes back (the
+// stream must be idle): called by whoever releases the track block or the map
+void lclife_release(xivo_hip_ctx* c);
+// the begin calls' part: the frame's keys to the key block (keys null: every track gets lclife_no_key()), in the packed form
+// of n tracks - behind track_block_upload; and what the life cycle's kernels take of the option (nothing while it is off)
+int lclife_upload_keys(xivo_hip_ctx* c, int n, const long long* keys);
+void lclife_args(xivo_hip_ctx* c, LifeArgs& a);
 
 // ---- capi_pool_lifecycle.hip
 void pool_life_release(xivo_hip_ctx* c);   // everything xivo_hip_pool_life_config allocated (the stream must be idle)

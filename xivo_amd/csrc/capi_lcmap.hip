@@ -1,5 +1,7 @@
 // C ABI, loop closure on the device (include/xivo_hip.h, xivo_hip_lcmap_*): the resident landmark map, the add and close calls
-// around it, loading and reading whole maps, the counters. Host-side orchestration only (capi_internal.h); the kernels are
+// around it, loading and reading whole maps, the counters; and loop closure inside the device life cycle
+// (xivo_hip_lcmap_life_config): the keys beside the track block and the book, the add and close calls on the records and
+// queries the device made itself. Host-side orchestration only (capi_internal.h); the kernels are
 // lcmap_kernels.hip's, the rows are handed over as xivo_hip_close_loop_stack hands its rows over (capi_oos.hip).
 #include <algorithm>
 #include <cmath>
@@ -12,6 +14,7 @@ using namespace xivo_hip::capi;
 namespace {
 
 void lcmap_release(xivo_hip_ctx* c) {   // (the stream must be idle; the staging blocks stay: they are no part of a configuration)
+  lclife_release(c);   // the life cycle's records and queries are this map's
   LcMap& m = c->lcmap;
   c->mem.release(&m.entries, &m.count, &m.stats, &m.matches, &m.closing, &m.cov, &m.visit, &m.cov_stats);
   m.opts = xivo_lcmap_opts{};
@@ -58,9 +61,181 @@ int call_status(xivo_hip_ctx* c, int B, int n, const void* recs) {
   return XIVO_HIP_OK;
 }
 
+// the add kernel over records that are on the device: a.recs and a.off, or a.cnt / a.row, are the caller's
+int add_launch(xivo_hip_ctx* c, int B, LcMapAddArgs& a) {
+  a.map = map_buffers(c); a.ext = cov_buffers(c);
+  a.poses = c->poses; a.groups = c->groups; a.feats = c->feats; a.Fmax = c->Fmax; a.F = c->F;
+  a.lay = c->lay; a.invdepth = (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0;
+  c->P.to(a.P, a.strideP, a.ldp);
+  a.max_depth_var = c->lcmap.opts.max_depth_var; a.batch = B;
+  StageTimer st(c, ST_OTHER, 0.0, "lcmap_add_kernel");
+  HIP_TRY((hipError_t)launch_lcmap_add(a, c->stream));
+  return XIVO_HIP_OK;
+}
+
+// match, rows, verify and the hand-over of the rows over queries that are on the device (a.queries and a.off, or a.cnt / a.row,
+// are the caller's); n_closing_out as xivo_hip_lcmap_close takes it
+int close_launch(xivo_hip_ctx* c, int B, LcMapCloseArgs& a, int* n_closing_out) {
+  const xivo_lcmap_opts& o = c->lcmap.opts;
+  const int M = 2 * o.lc_max, N = c->N;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_H = 0, o_inn = al((size_t)B * M * N * sizeof(double)), o_R = al(o_inn + (size_t)B * M * sizeof(double)),
+               total = al(o_R + (size_t)B * M * sizeof(double));
+  if (total > c->lc_cap) HIP_TRY(hipStreamSynchronize(c->stream));   // (growing frees the block an earlier call's kernels read)
+  if (int rc = c->mem.grow(&c->lc_buf, &c->lc_cap, total)) return rc;
+  char* base = c->lc_buf;
+  HIP_TRY(hipMemsetAsync(base + o_H, 0, (size_t)B * M * N * sizeof(double), c->stream));   // H_.setZero(2n, N) (update.cpp:184)
+  c->lcmap.t += 1;   // (a call that stages nothing below is a call all the same)
+  a.map = map_buffers(c); a.ext = cov_buffers(c);
+  a.poses = c->poses; a.groups = c->groups; a.lay = c->lay; a.cam = c->cam; a.cl = xivo_calib_layout{-1, -1, 0, 0};
+  c->P.to(a.P, a.strideP, a.ldp);
+  a.H = reinterpret_cast<double*>(base + o_H); a.strideH = (long)M * N; a.ldh = M;
+  a.inn = reinterpret_cast<double*>(base + o_inn); a.diagR = reinterpret_cast<double*>(base + o_R); a.strideV = M;
+  a.matches = c->lcmap.matches; a.closing = c->lcmap.closing;
+  a.lc_max = o.lc_max; a.min_matches = o.min_matches; a.Rlc = o.Rlc; a.chi2 = o.chi2; a.batch = B;
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "lcmap_close_kernel");
+    HIP_TRY((hipError_t)launch_lcmap_close(a, c->stream));
+  }
+  if (n_closing_out) {
+    std::vector<int> closing((size_t)B);
+    HIP_TRY(hipMemcpyAsync(closing.data(), c->lcmap.closing, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int k = 0;
+    for (int v : closing) k += v != 0;
+    *n_closing_out = k;
+    if (k == 0) return XIVO_HIP_OK;   // nobody closes: the frame's staged rows stay as they were
+  }
+  return stage_measurements(c, 0, B, M, a.H, a.strideH, a.ldh, a.inn, a.strideV, a.diagR, a.strideV);
+}
+
+// xivo_hip_lcmap_add_resident / _close_resident: the option is on and a frame of B filters of the immediate life cycle is open
+bool lclife_frame(const xivo_hip_ctx* c, int B) {
+  return c && c->lclife.configured() && c->lcmap.configured() && c->life.configured() && B > 0 && B == track_block_frame(c);
+}
+
 }  // namespace
 
+namespace xivo_hip::capi {
+
+void lclife_release(xivo_hip_ctx* c) {
+  LcLife& k = c->lclife;
+  c->mem.release(&k.keys, &k.feat_key, &k.recs, &k.n_recs, &k.queries, &k.n_queries, &k.tracked, &k.rm, &k.status);
+  k = LcLife{};   // (the page-locked staging of the keys goes with it)
+}
+
+int lclife_upload_keys(xivo_hip_ctx* c, int n, const long long* keys) {
+  LcLife& k = c->lclife;
+  if (n <= 0) return XIVO_HIP_OK;
+  if (!keys) {   // all bytes 0xff: every key reads -1 (lclife_no_key)
+    HIP_TRY(hipMemsetAsync(k.keys, 0xff, (size_t)n * sizeof(long long), c->stream));
+    return XIVO_HIP_OK;
+  }
+  char* h = nullptr;
+  if (int rc = k.up.stage(&h)) return rc;
+  memcpy(h, keys, (size_t)n * sizeof(long long));   // (n <= Bmax * tracks_max: track_block_frame_ok)
+  return k.up.enqueue(k.keys, (size_t)n * sizeof(long long), c->stream);
+}
+
+void lclife_args(xivo_hip_ctx* c, LifeArgs& a) {
+  const LcLife& k = c->lclife;
+  if (!k.configured() || !c->life.configured()) return;
+  a.keys = k.keys; a.feat_key = k.feat_key; a.lc_recs = k.recs; a.lc_n_recs = k.n_recs; a.lc_tracked = k.tracked; a.lc_rm = k.rm;
+}
+
+}  // namespace xivo_hip::capi
+
 extern "C" {
+
+int xivo_hip_lcmap_life_config(xivo_hip_ctx* c, int on) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (!c || (on != 0 && on != 1) || track_block_frame_open(c)) return XIVO_HIP_ERR_INVALID;
+  if (on) {
+    if (!c->life_cycle_configured() || !c->lcmap.configured()) return XIVO_HIP_ERR_INVALID;
+    if (c->plife.configured()) return XIVO_HIP_ERR_UNSUPPORTED;   // the pool book carries no keys
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  lclife_release(c);
+  if (!on) return XIVO_HIP_OK;
+  LcLife& k = c->lclife;
+  const size_t B = (size_t)c->Bmax, ld = (size_t)c->book.ld, G = (size_t)c->lay.n_groups, nt = B * track_block_row(c);
+  int rc = c->mem.raw(&k.keys, nt);
+  if (!rc) rc = k.up.alloc(nt * sizeof(long long));
+  if (!rc) rc = c->mem.raw(&k.feat_key, B * ld);
+  if (!rc) rc = c->mem.zeroed(&k.recs, B * ld);
+  if (!rc) rc = c->mem.zeroed(&k.n_recs, B);
+  if (!rc) rc = c->mem.zeroed(&k.queries, B * ld);
+  if (!rc) rc = c->mem.zeroed(&k.n_queries, B);
+  if (!rc) rc = c->mem.zeroed(&k.tracked, B * ld);
+  if (!rc) rc = c->mem.zeroed(&k.rm, B * (2 + ld + G));
+  if (!rc) rc = c->mem.zeroed(&k.status, B);
+  // all bytes 0xff: every track and every slot - the features in the state now among them - has the key -1
+  if (!rc && hipMemsetAsync(k.keys, 0xff, nt * sizeof(long long), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (!rc && hipMemsetAsync(k.feat_key, 0xff, B * ld * sizeof(long long), c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (rc) { lclife_release(c); return rc; }
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_lcmap_add_resident(xivo_hip_ctx* c, int B) {
+  if (!lclife_frame(c, B) || c->lclife.stage != LcLife::kBegun) return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (int rc = call_status(c, B, 0, nullptr)) return rc;
+  LcMapAddArgs a{};
+  a.recs = c->lclife.recs; a.cnt = c->lclife.n_recs; a.row = c->book.ld;
+  if (int rc = add_launch(c, B, a)) return rc;
+  LifeArgs la = life_args_common(c, B);
+  StageTimer st(c, ST_OTHER, 0.0, "life_lc_apply_kernel");
+  if (launch_life_lc_apply(la, B, c->stream)) return XIVO_HIP_ERR_HIP;
+  c->lclife.stage = LcLife::kAdded;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_lcmap_close_resident(xivo_hip_ctx* c, int B, int* n_closing_out) {
+  if (!lclife_frame(c, B) || c->lclife.stage != LcLife::kAdded || !c->mask || c->F <= 0) return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (int rc = call_status(c, B, 0, nullptr)) return rc;
+  LcLife& k = c->lclife;
+  LcLifeQueryArgs q{};
+  LifeArgs la = life_args_common(c, B);
+  life_args_update(c, la);   // (the mask and its row stride as xivo_hip_life_end reads them)
+  q.feat_id = c->book.feat_id; q.feat_key = k.feat_key; q.slot_ld = c->book.ld; q.tracked = k.tracked;
+  q.mask = la.mask; q.mask_ld = la.mask_ld; q.feats = c->feats; q.Fmax = c->Fmax; q.F = c->F;
+  q.status = c->status; q.status_out = k.status; q.queries = k.queries; q.n_queries = k.n_queries; q.batch = B;
+  {
+    StageTimer st(c, ST_OTHER, 0.0, "lclife_query_kernel");
+    HIP_TRY((hipError_t)launch_lclife_queries(q, c->stream));
+  }
+  k.stage = LcLife::kClosed;   // (the status is kept from here on, whatever becomes of the calls below)
+  LcMapCloseArgs a{};
+  a.queries = k.queries; a.cnt = k.n_queries; a.row = c->book.ld;
+  return close_launch(c, B, a, n_closing_out);
+}
+
+int xivo_hip_lcmap_life_get_keys(xivo_hip_ctx* c, int b0, int nb, long long* feat_key, long long* ent_key) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->lclife.configured() || ent_key || c->F <= 0 || c->F > c->book.ld) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  if (feat_key) {
+    const size_t w = (size_t)c->F * sizeof(long long), ld = (size_t)c->book.ld;
+    if (int rc = d2h_rows(c, feat_key, w, c->lclife.feat_key + (size_t)b0 * ld, ld * sizeof(long long), w, nb)) return rc;
+  }
+  return hipStreamSynchronize(c->stream) == hipSuccess ? XIVO_HIP_OK : XIVO_HIP_ERR_HIP;
+}
+
+int xivo_hip_lcmap_life_get_track_keys(xivo_hip_ctx* c, int b0, int nb, long long* keys) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !c->lclife.configured() || !c->world.configured() || b0 + nb > c->world.tracks_B || (nb > 0 && !keys))
+    return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  const size_t ld = (size_t)track_block_row(c);
+  std::vector<int> n((size_t)nb);
+  if (int rc = d2h_rows(c, n.data(), sizeof(int), c->world.track_counts() + b0, sizeof(int), sizeof(int), nb)) return rc;
+  if (int rc = d2h_rows(c, keys, ld * sizeof(long long), c->lclife.keys + (size_t)b0 * ld, ld * sizeof(long long), ld * sizeof(long long), nb)) return rc;
+  // behind cnt[b] a row holds whatever an earlier frame left: blanked, as xivo_hip_pcw_get_tracks blanks the ids
+  for (int b = 0; b < nb; ++b) std::fill(keys + (size_t)b * ld + n[(size_t)b], keys + (size_t)(b + 1) * ld, -1LL);
+  return XIVO_HIP_OK;
+}
 
 int xivo_hip_lcmap_config(xivo_hip_ctx* c, const xivo_lcmap_opts* o) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
@@ -106,14 +281,8 @@ int xivo_hip_lcmap_add(xivo_hip_ctx* c, int B, int n, const xivo_lcmap_add_rec* 
   LcMapAddArgs a{};
   const char* d_recs = nullptr;
   if (int rc = upload_call(c, recs, (size_t)n * sizeof(xivo_lcmap_add_rec), off, &d_recs, &a.off)) return rc;
-  a.map = map_buffers(c); a.ext = cov_buffers(c); a.recs = reinterpret_cast<const xivo_lcmap_add_rec*>(d_recs);
-  a.poses = c->poses; a.groups = c->groups; a.feats = c->feats; a.Fmax = c->Fmax; a.F = c->F;
-  a.lay = c->lay; a.invdepth = (c->flags & XIVO_HIP_FLAG_INVDEPTH) ? 1 : 0;
-  c->P.to(a.P, a.strideP, a.ldp);
-  a.max_depth_var = c->lcmap.opts.max_depth_var; a.batch = B;
-  StageTimer st(c, ST_OTHER, 0.0, "lcmap_add_kernel");
-  HIP_TRY((hipError_t)launch_lcmap_add(a, c->stream));
-  return XIVO_HIP_OK;
+  a.recs = reinterpret_cast<const xivo_lcmap_add_rec*>(d_recs);
+  return add_launch(c, B, a);
 }
 
 int xivo_hip_lcmap_close(xivo_hip_ctx* c, int B, int n, const xivo_lcmap_query* queries, int* n_closing_out) {
@@ -126,40 +295,11 @@ int xivo_hip_lcmap_close(xivo_hip_ctx* c, int B, int n, const xivo_lcmap_query* 
     off[(size_t)q.b + 1] += 1;
   }
   for (int b = 0; b < B; ++b) off[(size_t)b + 1] += off[b];
-  const xivo_lcmap_opts& o = c->lcmap.opts;
-  const int M = 2 * o.lc_max, N = c->N;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_H = 0, o_inn = al((size_t)B * M * N * sizeof(double)), o_R = al(o_inn + (size_t)B * M * sizeof(double)),
-               total = al(o_R + (size_t)B * M * sizeof(double));
-  if (total > c->lc_cap) HIP_TRY(hipStreamSynchronize(c->stream));   // (growing frees the block an earlier call's kernels read)
-  if (int rc = c->mem.grow(&c->lc_buf, &c->lc_cap, total)) return rc;
   LcMapCloseArgs a{};
   const char* d_q = nullptr;
   if (int rc = upload_call(c, queries, (size_t)n * sizeof(xivo_lcmap_query), off, &d_q, &a.off)) return rc;
-  char* base = c->lc_buf;
-  HIP_TRY(hipMemsetAsync(base + o_H, 0, (size_t)B * M * N * sizeof(double), c->stream));   // H_.setZero(2n, N) (update.cpp:184)
-  c->lcmap.t += 1;   // (a call that stages nothing below is a call all the same)
-  a.map = map_buffers(c); a.ext = cov_buffers(c); a.queries = reinterpret_cast<const xivo_lcmap_query*>(d_q);
-  a.poses = c->poses; a.groups = c->groups; a.lay = c->lay; a.cam = c->cam; a.cl = xivo_calib_layout{-1, -1, 0, 0};
-  c->P.to(a.P, a.strideP, a.ldp);
-  a.H = reinterpret_cast<double*>(base + o_H); a.strideH = (long)M * N; a.ldh = M;
-  a.inn = reinterpret_cast<double*>(base + o_inn); a.diagR = reinterpret_cast<double*>(base + o_R); a.strideV = M;
-  a.matches = c->lcmap.matches; a.closing = c->lcmap.closing;
-  a.lc_max = o.lc_max; a.min_matches = o.min_matches; a.Rlc = o.Rlc; a.chi2 = o.chi2; a.batch = B;
-  {
-    StageTimer st(c, ST_OTHER, 0.0, "lcmap_close_kernel");
-    HIP_TRY((hipError_t)launch_lcmap_close(a, c->stream));
-  }
-  if (n_closing_out) {
-    std::vector<int> closing((size_t)B);
-    HIP_TRY(hipMemcpyAsync(closing.data(), c->lcmap.closing, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    int k = 0;
-    for (int v : closing) k += v != 0;
-    *n_closing_out = k;
-    if (k == 0) return XIVO_HIP_OK;   // nobody closes: the frame's staged rows stay as they were
-  }
-  return stage_measurements(c, 0, B, M, a.H, a.strideH, a.ldh, a.inn, a.strideV, a.diagR, a.strideV);
+  a.queries = reinterpret_cast<const xivo_lcmap_query*>(d_q);
+  return close_launch(c, B, a, n_closing_out);
 }
 
 int xivo_hip_lcmap_set(xivo_hip_ctx* c, int b0, int nb, const xivo_lcmap_entry* entries, const int* count) {

@@ -38,7 +38,24 @@ int life_begin_frame(xivo_hip_ctx* c, int B, int F) {
     if (launch_life_begin(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
   }
   track_block_open_frame(c, B);
+  // (loop closure inside the life cycle: the kernel decided only - xivo_hip_lcmap_add_resident makes the removals)
+  c->lclife.stage = c->lclife.configured() ? LcLife::kBegun : LcLife::kNone;
   return XIVO_HIP_OK;
+}
+
+// xivo_hip_life_begin / _begin_keys: keys null - the plain call
+int life_begin_uploaded(xivo_hip_ctx* c, int B, int F, const int* off, const long long* ids, const double* meas, const long long* keys) {
+  if (!frame_can_begin(c, B, F) || !c->life.configured() || c->pool.configured() || !track_block_frame_ok(c, B, off, ids, meas)) return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  int rc = ensure_gate_buffers(c, F);   // (allocated by life_config: checks F only)
+  if (rc) return rc;
+  rc = track_block_upload(c, B, off, ids, meas);
+  if (rc) return rc;
+  if (c->lclife.configured()) {
+    rc = lclife_upload_keys(c, off[B], keys);
+    if (rc) return rc;
+  }
+  return life_begin_frame(c, B, F);
 }
 
 }  // namespace
@@ -46,6 +63,7 @@ int life_begin_frame(xivo_hip_ctx* c, int B, int F) {
 namespace xivo_hip::capi {
 // ---- the track block
 void track_block_release(xivo_hip_ctx* c) {
+  lclife_release(c);   // the keys lie beside the tracks: they go with them
   c->mem.release(&c->tracks.dev);
   c->tracks = TrackBlock{};
 }
@@ -179,6 +197,7 @@ LifeArgs life_args_common(xivo_hip_ctx* c, int B) {
     a.ids = reinterpret_cast<const long long*>(t.dev + off_bytes);
     a.meas = reinterpret_cast<const double*>(t.dev + off_bytes + (size_t)t.n * sizeof(long long));
   }
+  lclife_args(c, a);
   return a;
 }
 // the inlier mask where the update left it (xivo_hip_get_gate): the layout-faithful gate strides by Fmax, the dense-row gate by F
@@ -220,6 +239,8 @@ int xivo_hip_life_set_book(xivo_hip_ctx* c, int b0, int nb, const long long* fea
   if (bad_range(c, b0, nb) || !c->life.configured() || track_block_frame_open(c) || c->F <= 0 || c->F > c->book.ld || (nb > 0 && !feat_id))
     return XIVO_HIP_ERR_INVALID;
   if (nb == 0) return XIVO_HIP_OK;
+  if (c->lclife.configured())   // a book set from outside brings no keys: all bytes 0xff, every slot reads -1
+    HIP_TRY(hipMemsetAsync(c->lclife.feat_key + (size_t)b0 * c->book.ld, 0xff, (size_t)nb * c->book.ld * sizeof(long long), c->stream));
   return book_set(c, b0, nb, feat_id);
 }
 
@@ -231,13 +252,12 @@ int xivo_hip_life_get_book(xivo_hip_ctx* c, int b0, int nb, long long* feat_id, 
 }
 
 int xivo_hip_life_begin(xivo_hip_ctx* c, int B, int F, const int* off, const long long* ids, const double* meas) {
-  if (!frame_can_begin(c, B, F) || !c->life.configured() || c->pool.configured() || !track_block_frame_ok(c, B, off, ids, meas)) return XIVO_HIP_ERR_INVALID;
-  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
-  int rc = ensure_gate_buffers(c, F);   // (allocated by life_config: checks F only)
-  if (rc) return rc;
-  rc = track_block_upload(c, B, off, ids, meas);
-  if (rc) return rc;
-  return life_begin_frame(c, B, F);
+  return life_begin_uploaded(c, B, F, off, ids, meas, nullptr);
+}
+
+int xivo_hip_life_begin_keys(xivo_hip_ctx* c, int B, int F, const int* off, const long long* ids, const double* meas, const long long* keys) {
+  if (!c || !c->lclife.configured() || !off || B <= 0 || B > c->Bmax || (off[B] > 0 && !keys)) return XIVO_HIP_ERR_INVALID;
+  return life_begin_uploaded(c, B, F, off, ids, meas, keys);
 }
 
 int xivo_hip_life_begin_tracks(xivo_hip_ctx* c, int B, int F) {
@@ -253,8 +273,13 @@ int xivo_hip_life_begin_tracks(xivo_hip_ctx* c, int B, int F) {
 int xivo_hip_life_end(xivo_hip_ctx* c, int B) {
   if (!c || !c->life.configured() || c->pool.configured() || B <= 0 || B != track_block_frame(c) || !c->mask || c->F <= 0) return XIVO_HIP_ERR_INVALID;
   if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  // loop closure inside the life cycle: the removals the begin call decided must have been made (xivo_hip_lcmap_add_resident),
+  // and after a close call the status to count is the first update's, which it kept - the second update overwrote c->status
+  if (c->lclife.configured() && c->lclife.stage == LcLife::kBegun) return XIVO_HIP_ERR_INVALID;
   LifeArgs a = life_args_common(c, B);
   life_args_update(c, a);
+  if (c->lclife.configured() && c->lclife.stage == LcLife::kClosed) a.status = c->lclife.status;
+  c->lclife.stage = LcLife::kNone;
   a.stats = c->life.stats;
   const xivo_life_opts& o = c->life.opts;
   a.min_new_features = o.min_new_features; a.min_depth = o.min_depth; a.max_depth = o.max_depth;

@@ -26,6 +26,7 @@ int pcw_produce(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, 
   a.noise_px_std = noise_px_std; a.seed = seed; a.frame = frame;
   a.use_cam = c->world.use_cam ? 1 : 0; a.cam = c->world.cam; a.max_radius = c->world.max_radius;
   a.track_ids = track_block_strided_ids(c); a.track_meas = track_block_strided_meas(c); a.cnt = c->world.cnt; a.track_ld = track_block_row(c);
+  a.track_keys = c->lclife.keys;   // (null unless xivo_hip_lcmap_life_config is on: the keys go where the begin_tracks call reads them)
   c->world.tracks_overwritten();   // (whatever the block held)
   {
     // per filter: the points and their ids in, the ids that changed and at most npts tracks of 32 bytes out

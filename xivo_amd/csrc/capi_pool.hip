@@ -86,6 +86,7 @@ int xivo_hip_pool_config(xivo_hip_ctx* c, int pool_max, int anchor_max, const xi
   if (pool_max > XIVO_POOL_MAX_ENTRIES) return XIVO_HIP_ERR_UNSUPPORTED;
   HIP_TRY(hipStreamSynchronize(c->stream));
   pool_life_release(c);   // the device pool life cycle's books describe the pool given back here
+  lclife_release(c);      // (a context with a pool runs no immediate life cycle: its keys go too)
   pool_oos_release(c);    // ... and so do the OOS list and counters of its dropped entries
   c->mem.release(&c->pool.entries, &c->pool.anchors, &c->pool.tri_counts, &c->pool.init_z);
   c->pool.reset();   // (the mirrors, the triangulation and adaptive-depth options with it)

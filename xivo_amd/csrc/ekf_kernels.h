@@ -149,9 +149,16 @@ struct LifeArgs {
   // life_end only: the update's inlier mask (row stride mask_ld) and status, the admission options, the camera
   const unsigned char* mask; int mask_ld; const int* status;
   int min_new_features, invdepth; double min_depth, max_depth, var_xyz[3], fx, fy, cx, cy;
+  // loop closure inside the life cycle (xivo_hip_lcmap_life_config; all null while it is off, and always in the pool life cycle):
+  // keys - one per track, indexed as ids; feat_key [batch][slot_ld]; what the begin kernel leaves for the add and the close call:
+  // lc_recs [batch][slot_ld] / lc_n_recs [batch] the add records, lc_tracked [batch][slot_ld], lc_rm [batch][2 + slot_ld +
+  // n_groups] = n_rm_feat, n_rm_group, rm_feat, rm_group - the removals it decided and life_lc_apply_kernel makes
+  const long long* keys; long long* feat_key;
+  xivo_lcmap_add_rec* lc_recs; int* lc_n_recs; unsigned char* lc_tracked; int* lc_rm;
 };
 int launch_life_begin(const LifeArgs& a, int batch, hipStream_t s);
 int launch_life_end(const LifeArgs& a, int batch, hipStream_t s);
+int launch_life_lc_apply(const LifeArgs& a, int batch, hipStream_t s);
 
 // ================================================================ pool_lifecycle_kernels.hip: device pool life cycle (capi_pool_lifecycle.hip)
 
@@ -185,6 +192,7 @@ struct PcwArgs {
   const double* Xs; long long* ids; long long* next_id; const double* gsc; int npts;
   double fx, fy, cx, cy, imw, imh, noise_px_std; unsigned long long seed, frame;
   long long* track_ids; double* track_meas; int* cnt; int track_ld;
+  long long* track_keys;   // null, or [batch][track_ld]: the world-point index of every track (xivo_hip_lcmap_life_config)
   int use_cam; xivo_cam cam; double max_radius;   // use_cam != 0 (xivo_hip_pcw_camera): project through cam instead of fx .. imh
 };
 int launch_pcw_tracks(const PcwArgs& a, int batch, hipStream_t s);
@@ -293,7 +301,10 @@ struct LcMapAddArgs {
   xivo_layout lay; int invdepth;
   const double* P; long strideP; int ldp;
   double max_depth_var; int batch;
-  LcMapCovBuffers ext;   // (last: the arguments before it keep their places)
+  LcMapCovBuffers ext;   // (the arguments before it keep their places)
+  // the resident form (xivo_hip_lcmap_add_resident): cnt non-null - off is not read, the records of filter b are
+  // recs[b row, b row + cnt[b]) (lclife_list_pos, lcmap_life_device.h)
+  const int* cnt; int row;
 };
 int launch_lcmap_add(const LcMapAddArgs& a, hipStream_t s);
 // close: match, rows, verify. The queries of filter b are queries[off[b], off[b + 1]); H [batch] 2 lc_max x N zero-filled
@@ -311,9 +322,21 @@ struct LcMapCloseArgs {
   xivo_lcmap_match* matches;   // [batch][lc_max]
   int* closing;                // [batch] 1: the filter closes
   int lc_max, min_matches; double Rlc, chi2; int batch;
-  LcMapCovBuffers ext;         // (last: the arguments before it keep their places)
+  LcMapCovBuffers ext;         // (the arguments before it keep their places)
+  const int* cnt; int row;     // the resident form (xivo_hip_lcmap_close_resident), as LcMapAddArgs'
 };
 int launch_lcmap_close(const LcMapCloseArgs& a, hipStream_t s);
+// the queries of a frame of the device life cycle, made where the book is (xivo_hip_lcmap_close_resident): per filter one query
+// per slot lclife_queries names, in slot order, into queries [batch][slot_ld] / n_queries [batch]; the update's status of every
+// filter is copied to status_out, where the second update does not reach it
+struct LcLifeQueryArgs {
+  const long long* feat_id; const long long* feat_key; int slot_ld;
+  const unsigned char* tracked; const unsigned char* mask; int mask_ld;
+  const xivo_feat_in* feats; int Fmax, F;
+  const int* status; int* status_out;
+  xivo_lcmap_query* queries; int* n_queries; int batch;
+};
+int launch_lclife_queries(const LcLifeQueryArgs& a, hipStream_t s);
 
 // measurement compression of the appended OOS rows (estimator.h:399-402, helpers.cpp:77-101)
 struct OosCompressArgs {

@@ -12,10 +12,14 @@
 // One workgroup of one wave per filter in all three: a filter's map is only ever touched by its own workgroup, so the order of
 // the records decides (never a race) and the counters are plain sums - no global atomics. The integer rules are
 // lcmap_device.h's, which a host program tests; the kernels only evaluate them.
+// The records and the queries come packed behind offsets, as the host uploads them, or (cnt non-null) one row per filter with a
+// count, as the device life cycle leaves them (xivo_hip_lcmap_add_resident / _close_resident): lc_list_begin / lc_list_end are
+// the only place that tells the two apart. lclife_query_kernel makes that life cycle's queries (lcmap_life_device.h's rules).
 #include "ekf_kernels.h"
 #include "gate_device.h"
 #include "geometry_device.h"
 #include "lcmap_device.h"
+#include "lcmap_life_device.h"
 
 namespace xivo_hip {
 
@@ -23,6 +27,14 @@ namespace {
 
 constexpr long kKeyStride = sizeof(xivo_lcmap_entry) / sizeof(long long);   // entry to entry, in keys
 static_assert(sizeof(xivo_lcmap_entry) == 32 && sizeof(xivo_lcmap_entry) % sizeof(long long) == 0, "lcmap_find walks the keys");
+
+// where filter filt's records / queries start and end, in either form of the list (ekf_kernels.h)
+template <class Args> __device__ __forceinline__ int lc_list_begin(const Args& a, int filt) {
+  return a.cnt ? (int)lclife_list_pos(filt, a.row, 0) : a.off[filt];
+}
+template <class Args> __device__ __forceinline__ int lc_list_end(const Args& a, int filt) {
+  return a.cnt ? (int)lclife_list_pos(filt, a.row, lclife_list_count(a.cnt[filt], a.row)) : a.off[filt + 1];
+}
 
 __device__ __forceinline__ int lcmap_count(const LcMapBuffers& m, int filt) {
   const int n = m.count[filt];
@@ -110,7 +122,7 @@ __global__ __launch_bounds__(64) void lcmap_add_kernel(LcMapAddArgs a) {
   const xivo_pose_in& pose = a.poses[filt];
   int count = lcmap_count(a.map, filt);
   long long n_add = 0, n_skip = 0, n_poor = 0, n_dup = 0, n_full = 0;
-  const int r0 = a.off[filt], r1 = a.off[filt + 1];
+  const int r0 = lc_list_begin(a, filt), r1 = lc_list_end(a, filt);
   for (int i = r0; i < r1; ++i) {                        // (every lane walks the same records: the branches are uniform)
     const xivo_lcmap_add_rec r = a.recs[i];
     int in_state = 0, poor = 0, ref = 0;
@@ -165,7 +177,7 @@ __global__ __launch_bounds__(64) void lcmap_match_kernel(LcMapCloseArgs a) {
   const xivo_lcmap_entry* ent = a.map.entries + (long)filt * a.map.map_max;
   const int count = lcmap_count(a.map, filt);
   xivo_lcmap_match* list = a.matches + (long)filt * a.lc_max;
-  const int q0 = a.off[filt], q1 = a.off[filt + 1];
+  const int q0 = lc_list_begin(a, filt), q1 = lc_list_end(a, filt);
   int base = 0;
   for (int c0 = q0; c0 < q1; c0 += 64) {
     const int q = c0 + lane;
@@ -349,6 +361,37 @@ __global__ __launch_bounds__(64) void lcmap_close_kernel(LcMapCloseArgs a) {
   }
 }
 
+// The queries of a frame of the device life cycle (SequenceRunner._lc_close on the host): 64 slots at a time, one lane each; a
+// yielding slot's rank is the number of yielding slots before it, counted in LDS as lcmap_match_kernel ranks its matches. Lane 0
+// also copies the filter's update status to where the second update does not write.
+__global__ __launch_bounds__(64) void lclife_query_kernel(LcLifeQueryArgs a) {
+  const int filt = blockIdx.x, lane = threadIdx.x;
+  if (filt >= a.batch) return;
+  __shared__ int sFlag[64];
+  const long long* fid = a.feat_id + (long)filt * a.slot_ld;
+  const long long* key = a.feat_key + (long)filt * a.slot_ld;
+  const unsigned char* tracked = a.tracked + (long)filt * a.slot_ld;
+  const unsigned char* mask = a.mask + (long)filt * a.mask_ld;
+  const xivo_feat_in* feats = a.feats + (long)filt * a.Fmax;
+  int base = 0;
+  for (int j0 = 0; j0 < a.F; j0 += 64) {
+    const int j = j0 + lane;
+    const int yes = j < a.F ? lclife_queries(fid[j], mask[j], tracked[j]) : 0;
+    sFlag[lane] = yes;
+    __syncthreads();
+    int rank = base, tot = 0;
+#pragma unroll 8
+    for (int i = 0; i < 64; ++i) { tot += sFlag[i]; rank += sFlag[i] & ((i - lane) >> 31); }   // (the mask: all ones for i < lane)
+    if (yes) {   // rank < the slots before j <= F - 1 < slot_ld: inside the filter's row
+      xivo_lcmap_query& q = a.queries[lclife_list_pos(filt, a.slot_ld, rank)];
+      q.b = filt; q.group_sind = -1; q.key = key[j]; q.xp[0] = feats[j].xp[0]; q.xp[1] = feats[j].xp[1];
+    }
+    base += tot;
+    __syncthreads();
+  }
+  if (lane == 0) { a.n_queries[filt] = base; a.status_out[filt] = a.status[filt]; }
+}
+
 }  // namespace
 
 #define CHECK_LAUNCH() return (int)hipGetLastError()
@@ -357,6 +400,11 @@ int launch_lcmap_add(const LcMapAddArgs& a, hipStream_t s) {
   if (a.batch <= 0) return 0;
   if (a.ext.on()) hipLaunchKernelGGL(lcmap_add_kernel<true>, dim3(a.batch), dim3(64), 0, s, a);
   else hipLaunchKernelGGL(lcmap_add_kernel<false>, dim3(a.batch), dim3(64), 0, s, a);
+  CHECK_LAUNCH();
+}
+int launch_lclife_queries(const LcLifeQueryArgs& a, hipStream_t s) {
+  if (a.batch <= 0) return 0;
+  hipLaunchKernelGGL(lclife_query_kernel, dim3(a.batch), dim3(64), 0, s, a);
   CHECK_LAUNCH();
 }
 int launch_lcmap_close(const LcMapCloseArgs& a, hipStream_t s) {

@@ -17,8 +17,15 @@
 // The frame's tracks are read in one of two forms (LifeArgs, ekf_kernels.h): packed behind offsets as the host uploads them, or
 // one row per filter with a count as pcw_tracks_kernel (pcw_kernels.hip) leaves them; life_track_begin / life_track_count
 // (lifecycle_tracks_device.h) are the only place that tells them apart.
+// Loop closure inside the life cycle (xivo_hip_lcmap_life_config: LifeArgs::feat_key is then not null; the rules are
+// lcmap_life_device.h's): the begin kernel decides and does not edit - the leaving slots become the frame's add records, with
+// the key the book held, and the removals wait in LifeArgs::lc_rm until the map has read the leaving features from the state as
+// it was; life_lc_apply_kernel then makes them, with book_apply_removals as the begin kernel does otherwise. The end kernel
+// hands a new feature its track's key and frees the key of a rejected one (no record: DestroyFeatures). feat_key is read and
+// written in global memory by thread 0 alone: the LDS plan stays what it was.
 #include "ekf_kernels.h"
 #include "instate_book_device.h"
+#include "lcmap_life_device.h"
 
 namespace xivo_hip {
 
@@ -45,16 +52,55 @@ __global__ __launch_bounds__(256) void life_begin_kernel(LifeArgs a) {
   book_associate(s.k, a.F, n, tid);
   __syncthreads();
   book_take_pixels(a, s.k, b, tid);
+  if (a.feat_key) {   // (uniform; before thread 0 frees the slots that leave: fid of a tracked slot is not written)
+    const int k0 = life_track_begin(a, b);
+    for (int j = tid; j < a.F; j += 256) {
+      const int k = s.k.slot_track[j];
+      const double u = k >= 0 ? a.meas[3 * (long)(k0 + k)] : 0.0;
+      a.lc_tracked[(long)b * a.slot_ld + j] = k >= 0 && lclife_tracked(s.k.fid[j], k, u != u) ? 1 : 0;
+    }
+  }
   if (tid == 0) {   // ProcessTracks (src/manager.cpp:152-169)
-    const int n_in = book_drop_where(s.k, a.F, [&](int j) { return s.k.slot_track[j] < 0; });
+    const int n_in = book_drop_where(s.k, a.F, [&](int j) { return lclife_leaves(s.k.fid[j], s.k.slot_track[j]) != 0; });
     book_discard_empty_groups(s.k, a.lay.n_groups);
     xivo_life_stats& st = a.stats[b];
     st.dropped += s.k.n_rm_feat;
     st.updates += n_in > 0 ? 1 : 0;
   }
   __syncthreads();
+  if (a.feat_key) {   // (uniform) decide only: the records and the removals go to the add call
+    if (tid == 0) {
+      long long* key = a.feat_key + (long)b * a.slot_ld;
+      int* rm = a.lc_rm + (long)b * (2 + a.slot_ld + a.lay.n_groups);
+      for (int q = 0; q < s.k.n_rm_feat; ++q) {   // (rm_feat is in ascending slot order)
+        const int j = s.k.rm_feat[q];
+        xivo_lcmap_add_rec& r = a.lc_recs[lclife_list_pos(b, a.slot_ld, q)];
+        r.b = b; r.feat = j; r.key = key[j];
+        key[j] = lclife_no_key();
+        rm[2 + q] = j;
+      }
+      for (int q = 0; q < s.k.n_rm_group; ++q) rm[2 + a.slot_ld + q] = s.k.rm_group[q];
+      rm[0] = s.k.n_rm_feat; rm[1] = s.k.n_rm_group;
+      a.lc_n_recs[b] = s.k.n_rm_feat;
+    }
+    book_store(a, s.k, b, tid);
+    return;
+  }
   book_apply_removals(a, s.k, b, nullptr, 0, tid);
   book_store(a, s.k, b, tid);
+}
+
+// the removals a deciding begin kernel left in lc_rm, behind the map's add kernel: the begin kernel's own last step
+__global__ __launch_bounds__(256) void life_lc_apply_kernel(LifeArgs a) {
+  __shared__ InstateBook s;
+  const int b = blockIdx.x, tid = threadIdx.x, G = a.lay.n_groups;
+  const int* rm = a.lc_rm + (long)b * (2 + a.slot_ld + G);
+  const int n_feat = min(max(rm[0], 0), min(a.F, kSlots)), n_group = min(max(rm[1], 0), min(G, kSlots));
+  for (int q = tid; q < n_feat; q += 256) s.rm_feat[q] = rm[2 + q];
+  for (int q = tid; q < n_group; q += 256) s.rm_group[q] = rm[2 + a.slot_ld + q];
+  if (tid == 0) { s.n_rm_feat = n_feat; s.n_rm_group = n_group; }
+  __syncthreads();
+  book_apply_removals(a, s, b, nullptr, 0, tid);
 }
 
 // Feature::Initialize (src/feature.cpp:144-150) of a point-cloud track: no product is followed by a sum here, and contraction
@@ -79,6 +125,8 @@ __global__ __launch_bounds__(256) void life_end_kernel(LifeArgs a) {
     // gate-rejected features leave (src/update.cpp:105-113); their tracks are candidates again
     const int n_in = book_drop_where(s.k, F, [&](int j) { return !a.mask[(long)b * a.mask_ld + j]; });
     book_discard_empty_groups(s.k, G);
+    if (a.feat_key)   // a rejected feature's key goes with it and makes no record (DestroyFeatures)
+      for (int q = 0; q < s.k.n_rm_feat; ++q) a.feat_key[(long)b * a.slot_ld + s.k.rm_feat[q]] = lclife_no_key();
     s.g_new = life_free_group(s.k.gref, G);
     s.n_free = life_free_slots(s.k.fid, F, s.free_slots);
     s.open = life_admission_open(s.g_new, s.n_free, n_in, a.min_new_features) ? 1 : 0;
@@ -114,6 +162,8 @@ __global__ __launch_bounds__(256) void life_end_kernel(LifeArgs a) {
       }
       if (tid == 0) {
         for (int q = 0; q < n_new; ++q) { s.k.fid[s.free_slots[q]] = s.k.ids[s.pick[q]]; }
+        if (a.feat_key)   // the new feature takes its track's key
+          for (int q = 0; q < n_new; ++q) a.feat_key[(long)b * a.slot_ld + s.free_slots[q]] = a.keys[k0 + s.pick[q]];
         s.k.gref[g] = n_new;
         xivo_life_stats& st = a.stats[b];
         st.admitted += n_new;
@@ -129,6 +179,10 @@ __global__ __launch_bounds__(256) void life_end_kernel(LifeArgs a) {
 
 int launch_life_begin(const LifeArgs& a, int batch, hipStream_t s) {
   hipLaunchKernelGGL(life_begin_kernel, dim3(batch), dim3(256), 0, s, a);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+int launch_life_lc_apply(const LifeArgs& a, int batch, hipStream_t s) {
+  hipLaunchKernelGGL(life_lc_apply_kernel, dim3(batch), dim3(256), 0, s, a);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 int launch_life_end(const LifeArgs& a, int batch, hipStream_t s) {

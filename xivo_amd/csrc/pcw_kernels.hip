@@ -70,6 +70,7 @@ __global__ __launch_bounds__(kPcwThreads) void pcw_tracks_kernel(PcwArgs a) {
         double nu = 0.0, nv = 0.0;
         if (a.noise_px_std != 0.0) pcw_normal_pair(a.seed, a.frame, b, p, &nu, &nv);
         tid_out[r_vis] = id_after;
+        if (a.track_keys) a.track_keys[(long)b * a.track_ld + r_vis] = p;   // the track's key: its world point (BatchPCW's last_point_index)
         meas_out[3 * (long)r_vis] = pcw_noisy(uvz[0], a.noise_px_std, nu);
         meas_out[3 * (long)r_vis + 1] = pcw_noisy(uvz[1], a.noise_px_std, nv);
         meas_out[3 * (long)r_vis + 2] = uvz[2];

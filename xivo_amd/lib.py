@@ -338,6 +338,12 @@ _SIGS = {
     "xivo_hip_lcmap_set_cov": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_lcmap_get_cov": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_lcmap_get_cov_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_lcmap_life_config": [C.c_void_p, C.c_int],
+    "xivo_hip_life_begin_keys": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "xivo_hip_lcmap_add_resident": [C.c_void_p, C.c_int],
+    "xivo_hip_lcmap_close_resident": [C.c_void_p, C.c_int, C.c_void_p],
+    "xivo_hip_lcmap_life_get_keys": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "xivo_hip_lcmap_life_get_track_keys": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_pcw_config": [C.c_void_p, C.c_void_p],
     "xivo_hip_pcw_set_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_pcw_get_world": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
@@ -1159,6 +1165,18 @@ class Context:
         self._check(self.lib.xivo_hip_life_begin(self.h, B, int(F), _ptr(off), _ptr(ids), _ptr(meas)))
         self.F = int(F)
 
+    def life_begin_keys(self, F, off, ids, meas, keys, B=None):
+        """life_begin plus keys [n] int64, parallel to ids (after lcmap_life_config(True))"""
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        meas = np.ascontiguousarray(meas, dtype=np.float64)
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        B = off.size - 1 if B is None else int(B)
+        if off.size != B + 1 or ids.size != int(off[-1]) or meas.size != 3 * ids.size or keys.size != ids.size:
+            raise ValueError("off [B + 1], ids [off[B]], meas [off[B], 3], keys [off[B]]")
+        self._check(self.lib.xivo_hip_life_begin_keys(self.h, B, int(F), _ptr(off), _ptr(ids), _ptr(meas), _ptr(keys)))
+        self.F = int(F)
+
     def life_begin_tracks(self, F, B=None):
         """life_begin on the tracks the last pcw_tracks(B) left on the device (asynchronous, no upload)"""
         self._check(self.lib.xivo_hip_life_begin_tracks(self.h, self.batch if B is None else int(B), int(F)))
@@ -1429,6 +1447,37 @@ class Context:
         self._check(self.lib.xivo_hip_lcmap_close(self.h, self.batch if B is None else int(B), len(queries),
                                                   _ptr(queries) if len(queries) else None, C.byref(k) if wait else None))
         return k.value if wait else None
+
+    # ---- loop closure inside the device life cycle (xivo_hip_lcmap_life_config)
+    def lcmap_life_config(self, on=True):
+        """keys beside the track block and the in-state book, the device's own add records and queries (after life_config and
+        lcmap_config); False releases them"""
+        self._check(self.lib.xivo_hip_lcmap_life_config(self.h, 1 if on else 0))
+
+    def lcmap_add_resident(self, B=None):
+        """lcmap_add on the records the frame's begin call left on the device, then the removals it decided (asynchronous)"""
+        self._check(self.lib.xivo_hip_lcmap_add_resident(self.h, self.batch if B is None else int(B)))
+
+    def lcmap_close_resident(self, B=None, wait=True):
+        """lcmap_close on queries the device makes from the book, the inlier mask and the frame's pixels. wait: -> the number of
+        closing filters, nothing staged when it is 0; else asynchronous, always stages, -> None"""
+        n = C.c_int(0)
+        self._check(self.lib.xivo_hip_lcmap_close_resident(self.h, self.batch if B is None else int(B), C.byref(n) if wait else None))
+        return n.value if wait else None
+
+    def lcmap_life_get_keys(self, b0=0, nb=None):
+        """-> feat_key [nb, F] int64 (-1: free slot); one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        out = np.full((nb, self.F), -1, dtype=np.int64)
+        self._check(self.lib.xivo_hip_lcmap_life_get_keys(self.h, int(b0), nb, _ptr(out), None))
+        return out
+
+    def lcmap_life_get_track_keys(self, tracks_max, b0=0, nb=None):
+        """the keys the last pcw_tracks left -> [nb, tracks_max] int64 (-1 behind the filter's count); one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        out = np.full((nb, int(tracks_max)), -1, dtype=np.int64)
+        self._check(self.lib.xivo_hip_lcmap_life_get_track_keys(self.h, int(b0), nb, _ptr(out)))
+        return out
 
     def lcmap_set(self, entries, count, b0=0):
         """load whole maps: entries [nb, map_max] lcmap_entry_dtype, count [nb]"""

@@ -54,15 +54,24 @@ What is mirrored from the reference and what is simplified:
     frame, chi-square gated, in a fixed block of oos_max * (2 * oos_max_obs - 3) rows behind the in-state rows. The rules are
     pool_lifecycle_device.h's plife_hist_* / plife_oos_*; the device decides with the entry's status and depth. With
     pool_lifecycle="device" the rings are resident too and xivo_hip_pool_life_begin / _end select and record themselves.
-  * loop closure (`SequenceConfig.loop_closure`, both host life cycles): Estimator::CloseLoop on a device-resident landmark map
+  * loop closure (`SequenceConfig.loop_closure`; both host life cycles, and the device "immediate" life cycle with
+    `lc_lifecycle="device"`): Estimator::CloseLoop on a device-resident landmark map
     (xivo_hip_lcmap_*). `frame(imu, tracks, keys)` takes one key per track - the stand-in for the mapper's descriptor match
     (src/mapper.cpp:158-222, :335-418): equal non-negative keys are one world point; the point-cloud worlds supply the point's
     index (`last_point_index`). The in-state features the tracker dropped go to the map before they are removed
     (DiscardFeatures -> Mapper::AddFeature; gate-rejected ones never do, DestroyFeatures); right after the frame's update and
     AbsorbError every tracked, gate-kept in-state feature queries the map with this frame's pixel, observed by the body pose,
     and the filters with at least `lc_min_matches` chi-square-kept matches take a second update on the loop-closure rows
-    (CloseLoopInternal, src/update.cpp:171-212). The stored point is treated as exact, as the reference does. Refused with
-    the device life cycles (their track block carries no keys yet), use_oos and the innovation log.
+    (CloseLoopInternal, src/update.cpp:171-212). The stored point is treated as exact, as the reference does.
+    `lc_lifecycle`: "host" (default) - this file keeps the keys in its slot book, makes the add records and the queries filter
+    by filter and downloads the inlier mask every frame; refused with the device life cycles. "device" (needs
+    lifecycle="device") - the keys go down beside the tracks (`frame(imu, tracks, keys)`; with track_source="device" the
+    producer writes each track's world-point index), the resident book keeps one per slot, and the frame is life_begin ->
+    lcmap_add_resident -> update -> lcmap_close_resident -> [second update] -> life_end (xivo_hip_lcmap_life_config): no
+    per-filter Python, and no download but the close call's count of closing filters - which `frame_resident` does not wait
+    for either: there every filter takes the second update, the ones that do not close on neutral rows. Same decisions, same
+    results. Refused with use_oos and the innovation log whoever runs it; with pool_lifecycle="device" the pool book carries
+    no keys yet (not there: ent_key and its hand-over at admission), so loop closure stays refused there.
   * NOT IN EITHER: RefineDepth (`use_depth_opt`), gauge XY features and SwitchRefGroup, ownership transfer, feature merging and
     map eviction, the g2o pose graph.
 The numerics of every step are the device path; this file holds no arithmetic of the filter itself.
@@ -221,6 +230,9 @@ class SequenceConfig:
         # it; lc_revisit_gap > 0: a stored point closes the loop once per visit, a visit ending after that many frames without
         # a match of it (xivo_hip_lcmap_cov_config; both off: the stored point is exact and closes in every frame it is seen)
         self.lc_point_cov, self.lc_revisit_gap = False, 0
+        # who feeds and queries the map: "host" (the runner's slot book keeps the keys; host life cycles only) or "device" (the
+        # keys ride in the track block and the resident book, xivo_hip_lcmap_life_config; needs lifecycle = "device")
+        self.lc_lifecycle = "host"
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option " + k)
@@ -419,6 +431,8 @@ class HipBackend:
         self.lc_cov_on = bool(getattr(c, "lc_point_cov", False)) or int(getattr(c, "lc_revisit_gap", 0)) > 0
         if self.lc_cov_on:
             self.ctx.lcmap_cov_config(point_cov=bool(c.lc_point_cov), revisit_gap=int(c.lc_revisit_gap))
+        if getattr(c, "lc_lifecycle", "host") == "device":      # after the life cycle and the map: keys beside tracks and book
+            self.ctx.lcmap_life_config(True)
         self.lc_on = True
 
     def lcmap_add(self, recs):
@@ -430,6 +444,23 @@ class HipBackend:
         (CloseLoopInternal, src/update.cpp:207-208) -> the number of closing filters"""
         n = self.ctx.lcmap_close(queries, B=self.B, wait=True)
         if n > 0:
+            self.ctx.update_joseph()
+            self.ctx.absorb_error()
+        return n
+
+    def life_begin_keys(self, off, ids, meas, keys):
+        self.ctx.life_begin_keys(self.F, off, ids, meas, keys, B=self.B)
+
+    def lcmap_add_resident(self):
+        """the add records the begin call left on the device -> map entries, then the removals it decided (asynchronous)"""
+        self.ctx.lcmap_add_resident(self.B)
+
+    def lcmap_close_resident(self, wait=True):
+        """lcmap_close on the device's own queries. wait: as lcmap_close above -> the number of closing filters; else nothing is
+        waited for: the rows are always staged and every filter takes the second update and AbsorbError, the ones that do not
+        close on neutral rows (H = 0, inn = 0) -> None"""
+        n = self.ctx.lcmap_close_resident(self.B, wait=wait)
+        if n is None or n > 0:
             self.ctx.update_joseph()
             self.ctx.absorb_error()
         return n
@@ -790,8 +821,18 @@ def check_lifecycle(cfg):
             raise ValueError("use_oos needs feature_init='subfilter' (feature_init=%r)" % (cfg.feature_init,))
         if not 2 <= cfg.oos_max_obs <= L.OOS_MAX_OBS or not 2 <= cfg.oos_min_observations <= cfg.oos_max_obs or not 0 < cfg.oos_max <= 64:
             raise ValueError("use_oos needs 2 <= oos_min_observations <= oos_max_obs <= %d and 0 < oos_max <= 64" % L.OOS_MAX_OBS)
+    lcl = getattr(cfg, "lc_lifecycle", "host")
+    if lcl not in ("host", "device"):
+        raise ValueError("lc_lifecycle must be 'host' or 'device'")
+    if lcl == "device":
+        if not getattr(cfg, "loop_closure", False):
+            raise ValueError("lc_lifecycle='device' needs loop_closure")
+        if plc == "device":
+            raise ValueError("lc_lifecycle='device' runs with lifecycle='device' only: the device pool life cycle's pool book carries no keys")
+        if cfg.lifecycle != "device":
+            raise ValueError("lc_lifecycle='device' needs a device life cycle (lifecycle='device')")
     if getattr(cfg, "loop_closure", False):
-        if cfg.lifecycle == "device" or plc == "device":
+        if lcl == "host" and (cfg.lifecycle == "device" or plc == "device"):
             raise ValueError("loop_closure runs with the host life cycles only: the device life cycles' track block carries no keys")
         if getattr(cfg, "use_oos", False):
             raise ValueError("loop_closure with use_oos is not supported: both stage rows of their own behind the frame's update")
@@ -829,6 +870,8 @@ class SequenceRunner:
         self.be, self.cfg, self.B = backend, cfg, B
         self.device_lifecycle = cfg.lifecycle == "device"
         self.device_pool_lifecycle = cfg.pool_lifecycle == "device"
+        self.device_lc = getattr(cfg, "lc_lifecycle", "host") == "device"      # the map is fed and queried on the device
+        self.lc_wait = True          # ... and frame / frame_world wait for the close call's count (frame_resident never does)
         self._books = [_Book(cfg.n_groups, cfg.n_features) for _ in range(B)]
         self._n_updates = 0
         self._n_rejected = 0
@@ -905,29 +948,49 @@ class SequenceRunner:
             ids, meas = np.zeros(0, dtype=np.int64), np.zeros((0, 3))
         return off, ids, meas
 
-    def _device_frame(self, produce, begin, end):
+    def _device_frame(self, produce, begin, end, lc_wait=None):
         """one camera frame with the life cycle on the device: produce -> begin -> update -> end. produce: the (timer name, call)
         steps that bring the IMU records and the tracks to where the begin call reads them; begin / end: the pair of the life
-        cycle. No per-feature work here and nothing is downloaded (unless want_mask)."""
+        cycle. No per-feature work here and nothing is downloaded (unless want_mask). lc_lifecycle="device": the map's add
+        call behind begin, its close call (and the second update) behind the update; lc_wait: the close call waits for the
+        number of closing filters, as the host life cycle's does (None: the runner's lc_wait)."""
         import time
+        lc_wait = self.lc_wait if lc_wait is None else lc_wait
         t0 = time.perf_counter()
         for name, step in produce:
             step()
             t0 = self._tick(name, t0) or t0
         begin()
+        if self.device_lc:
+            self.be.lcmap_add_resident()
         t0 = self._tick("edit", t0) or t0
         mask = self.be.update(download=self.want_mask)
+        if self.device_lc:
+            self.n_lc_closed = getattr(self, "n_lc_closed", 0) + (self.be.lcmap_close_resident(wait=lc_wait) or 0)
         t0 = self._tick("update", t0) or t0
         end()
         self._tick("edit", t0)
         return mask
 
-    def _frame_host_tracks(self, imu, tracks, begin, end):
+    def _pack_keys(self, tracks, keys):
+        """the keys of all filters' tracks in the order _pack_tracks packs the ids"""
+        if keys is None:
+            raise ValueError("loop_closure needs keys: one per track of every filter, parallel to tracks[b][0]")
+        for b in range(self.B):
+            if len(keys[b]) != len(tracks[b][0]):
+                raise ValueError("keys[%d] is not parallel to tracks[%d][0]" % (b, b))
+        return np.concatenate([np.asarray(k, dtype=np.int64).reshape(-1) for k in keys]) if self.B else np.zeros(0, dtype=np.int64)
+
+    def _frame_host_tracks(self, imu, tracks, begin, end, keys=None):
         """_device_frame on host data: the IMU records go to propagate, the tracks of all filters go down in the off / ids /
-        meas layout of xivo_batch_visual as begin(off, ids, meas)"""
+        meas layout of xivo_batch_visual as begin(off, ids, meas) - with lc_lifecycle="device" as begin(off, ids, meas, keys)"""
         be, packed = self.be, []
-        return self._device_frame([("propagate", lambda: imu is not None and be.propagate(imu)),
-                                   ("host_pre", lambda: packed.extend(self._pack_tracks(tracks)))],
+        if self.device_lc:      # (the keys are checked before anything is enqueued)
+            kp = self._pack_keys(tracks, keys)
+            pack = lambda: packed.extend(self._pack_tracks(tracks) + (kp,))
+        else:
+            pack = lambda: packed.extend(self._pack_tracks(tracks))
+        return self._device_frame([("propagate", lambda: imu is not None and be.propagate(imu)), ("host_pre", pack)],
                                   lambda: begin(*packed), end)
 
     def _frame_subfilter_device(self, imu, tracks):
@@ -939,8 +1002,12 @@ class SequenceRunner:
         strict = self.vision_counter >= self.cfg.strict_criteria_timesteps
         return self._frame_host_tracks(imu, tracks, lambda *t: be.pool_life_begin(*t, strict), be.pool_life_end)
 
-    def _frame_device(self, imu, tracks):
-        """one camera frame of the "immediate" life cycle on the device: propagate -> life_begin -> update -> life_end"""
+    def _frame_device(self, imu, tracks, keys=None):
+        """one camera frame of the "immediate" life cycle on the device: propagate -> life_begin -> update -> life_end; with
+        lc_lifecycle="device" life_begin_keys -> lcmap_add_resident -> update -> lcmap_close_resident -> life_end (keys: per
+        filter one key per track)"""
+        if self.device_lc:
+            return self._frame_host_tracks(imu, tracks, self.be.life_begin_keys, self.be.life_end, keys)
         return self._frame_host_tracks(imu, tracks, self.be.life_begin, self.be.life_end)
 
     def _produced_tracks_pair(self):
@@ -953,11 +1020,12 @@ class SequenceRunner:
         strict = self.vision_counter >= self.cfg.strict_criteria_timesteps
         return lambda: be.pool_life_begin_tracks(strict), be.pool_life_end
 
-    def frame_world(self, imu, gsc, frame):
+    def frame_world(self, imu, gsc, frame, keys=None):
         """one camera frame whose tracks the device produces (track_source="device"): gsc [B, 12] the ground-truth camera pose
         of every filter (Rsc row-major, Tsc), frame the frame's number (the noise generator's counter). propagate -> pcw_tracks
         -> life_begin_tracks -> update -> life_end (pool_life_begin_tracks / pool_life_end with pool_lifecycle="device");
-        nothing but the poses goes down and nothing comes back (unless want_mask)."""
+        nothing but the poses goes down and nothing comes back (unless want_mask). keys: ignored - with lc_lifecycle="device" the
+        producer writes every track's world-point index as its key, and the close call's count of closing filters comes back."""
         if self.cfg.track_source != "device":
             raise ValueError("frame_world needs track_source='device'")
         be = self.be
@@ -965,18 +1033,19 @@ class SequenceRunner:
                                    ("tracks", lambda: be.make_tracks(gsc, self.noise_px_std, self.noise_seed, frame))],
                                   *self._produced_tracks_pair())
 
-    def frame_resident(self, k0, n, frame):
+    def frame_resident(self, k0, n, frame, keys=None):
         """one camera frame at IMU sample k0 + n that takes no host data (imu_source="device"): the device produces the records
         k0 + 1 .. k0 + n and the ground-truth poses (make_imu), propagates over them, produces the tracks from the poses and
         runs the life cycle and the update; n = 0: the frame at t = 0, nothing to propagate. frame: the pixel noise
-        generator's counter. Nothing is downloaded (unless want_mask)."""
+        generator's counter. Nothing is downloaded (unless want_mask). keys: ignored, as in frame_world; with
+        lc_lifecycle="device" the close call does not wait: every filter takes the second update, neutral where it does not close."""
         if getattr(self.cfg, "imu_source", "host") != "device":
             raise ValueError("frame_resident needs imu_source='device'")
         be = self.be
         return self._device_frame([("imu", lambda: be.make_imu(k0, n)),
                                    ("propagate", lambda: n > 0 and be.propagate_resident()),
                                    ("tracks", lambda: be.make_tracks_resident(self.noise_px_std, self.noise_seed, frame))],
-                                  *self._produced_tracks_pair())
+                                  *self._produced_tracks_pair(), lc_wait=False)
 
     def _tick(self, name, t0):
         if self.timers is None:
@@ -1031,8 +1100,8 @@ class SequenceRunner:
 
     def frame(self, imu, tracks, keys=None):
         """imu: [B x K] xivo_imu_in records or None; tracks: per filter (ids [n], xp_and_depths [n x 3]); keys (loop_closure):
-        per filter the key of every track, parallel to tracks[b][0]."""
-        lck = self._lc_keys(tracks, keys)
+        per filter the key of every track, parallel to tracks[b][0] (lc_lifecycle="device": they go down with the tracks)."""
+        lck = None if self.device_lc else self._lc_keys(tracks, keys)
         if self.cfg.feature_init == "subfilter":
             if self.device_pool_lifecycle:
                 return self._frame_subfilter_device(imu, tracks)
@@ -1040,7 +1109,7 @@ class SequenceRunner:
         if self.cfg.feature_init != "immediate":
             raise ValueError("feature_init must be 'immediate' or 'subfilter'")
         if self.device_lifecycle:
-            return self._frame_device(imu, tracks)
+            return self._frame_device(imu, tracks, keys)
         import time
         cfg, be = self.cfg, self.be
         t0 = time.perf_counter()
