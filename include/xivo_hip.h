@@ -1266,7 +1266,7 @@ typedef struct {
   int lc_max;             /* matches per filter and frame, <= XIVO_LCMAP_MAX_MATCHES; 2 lc_max rows are staged */
   int min_matches;        /* a filter closes with at least this many kept matches (>= 1; the reference's default is 5) */
   double Rlc;             /* variance of the loop-closure pixel (> 0) */
-  double chi2;            /* gate of one match (2 degrees of freedom); 0: no gate */
+  double chi2;            /* gate of one match (2 degrees of freedom); 0: no gate (a gamma that is not finite is gated all the same) */
   double max_depth_var;   /* an added feature whose P(foff + 2, foff + 2) is above this is dropped; 0: no test */
 } xivo_lcmap_opts;
 typedef struct { long long key; double Xs[3]; } xivo_lcmap_entry;
@@ -1276,7 +1276,8 @@ typedef struct {
   int entry;        /* position in the filter's map; -1: this list position is empty */
   int group_sind;   /* the query's */
   double xp[2];     /* the query's */
-  double gamma;     /* r^T (H P H^T + Rlc I)^-1 r of the pair; -1 where a pivot was not positive */
+  double gamma;     /* r^T (H P H^T + Rlc I)^-1 r of the pair; -1 where a pivot was not positive or the value is not finite
+                       (a NaN or inf pixel or stored point): such a match is not kept, whatever chi2 is */
   int kept, reserved;   /* reserved: 1 where the match rested (xivo_hip_lcmap_cov_config, revisit_gap), else 0 */
 } xivo_lcmap_match;
 typedef struct {
@@ -1298,7 +1299,8 @@ int xivo_hip_lcmap_add(xivo_hip_ctx* ctx, int B, int n, const xivo_lcmap_add_rec
  * matches that entry; the first lc_max matching queries in query order fill the match list, the rest are surplus. Rows: every
  * match gets the row pair of ComputeLCJacobian with the entry's Xs as the old feature's world point, observed by group
  * group_sind or (group_sind = -1) by the body pose itself, whose blocks go to columns 0..5. Verify: gamma of every pair from
- * the sub-block of P under its 12 columns; gamma > chi2 or a non-positive pivot gates it out. A filter with fewer than
+ * the sub-block of P under its 12 columns; gamma > chi2, a non-positive pivot or a gamma that is not finite (with chi2 = 0
+ * too: NaN is "no match" here as it is "not tracked" elsewhere) gates it out and counts in `gated`. A filter with fewer than
  * min_matches kept matches does not close: all its pairs are neutral (H = 0, inn = 0, diagR = 1); else only the gated and
  * empty ones are. The 2 lc_max rows of every filter replace the staged measurement as those of xivo_hip_close_loop_stack do;
  * xivo_hip_update_joseph + xivo_hip_absorb_error complete the closure. n_closing_out == NULL: always stages, never waits.

@@ -10,9 +10,12 @@
 //   A n  key x n                      -> "c count"  (a key stored already, a negative key or a full map: nothing)
 //   Q n  key x n  kept x lc_max       -> "l entry..." the list, "r resting..." per position, "f frame neutral x lc_max",
 //                                        "v (last_seen used) x count" the visit records after the call
+//   C 0  c00 c01 c02 c11 c12 c22  a0 a1 a2  b0 b1 b2 (hex floats)  -> "q lcmap_quad3(C, a, b)" as a hex float
 // stdout starts with "S" and the sizeof of xivo_lcmap_cov_opts, _cov_stats, and ends with "g mismatches tried": the rules
-// with gap = 0 against lcmap_frame_decide / lcmap_pair_neutral on every input of a small grid.
+// with gap = 0 against lcmap_frame_decide / lcmap_pair_neutral on every input of a small grid, and "n": what the visit rule
+// makes of a gamma that is not finite.
 #include <cstdio>
+#include <limits>
 #include <vector>
 
 #include "../include/xivo_hip.h"
@@ -80,6 +83,13 @@ int main() {
       printf("\nv");
       for (int e = 0; e < count; ++e) printf(" %d %d", last_seen[(size_t)e], used[(size_t)e]);
       printf("\n");
+    } else if (kind == 'C') {                             // (n is not used: one case a line)
+      double c[6], a[3], b[3];
+      for (double& v : c) if (scanf("%la", &v) != 1) return 2;
+      for (double& v : a) if (scanf("%la", &v) != 1) return 2;
+      for (double& v : b) if (scanf("%la", &v) != 1) return 2;
+      const double C[3][3] = {{c[0], c[1], c[2]}, {c[1], c[3], c[4]}, {c[2], c[4], c[5]}};
+      printf("q %a\n", lcmap_quad3(C, a, b));
     } else {
       return 2;
     }
@@ -103,5 +113,10 @@ int main() {
                 }
             }
   printf("g %ld %ld\n", bad, tried);
+  // a gamma that is not finite (on R_e as on Rlc I): never kept, so it neither counts as fresh nor uses its entry in a closing frame
+  const double qnan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  const int kn = lcmap_kept(1, qnan, 0.0), ki = lcmap_kept(1, inf, 0.0);
+  printf("n %d %d %d %d %d\n", kn, ki, lcmap_kept(1, qnan, 5.99), lcmap_used_next(0, LCMAP_FRAME_CLOSED, kn, 0),
+         lcmap_pair_neutral_visit(LCMAP_FRAME_CLOSED, 0, 1, ki, 0));
   return 0;
 }

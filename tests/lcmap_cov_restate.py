@@ -76,11 +76,14 @@ def pivots_ok(S):
 
 
 def gamma(Hi, P, r, Re):
-    """r^T (H_i P H_i^T + R_e)^-1 r on the unwhitened pair; None where R_e or the sum has a non-positive pivot"""
+    """r^T (H_i P H_i^T + R_e)^-1 r on the unwhitened pair; None where R_e or the sum has a non-positive pivot, or the value is
+    not finite (lcmap_restate.kept: never kept)"""
     S = Hi @ P @ Hi.T + Re
     if not pivots_ok(Re) or not pivots_ok(S):
         return None
-    return float(r @ np.linalg.solve(S, r))
+    with np.errstate(all="ignore"):
+        g = float(r @ np.linalg.solve(S, r))
+    return g if np.isfinite(g) else None
 
 
 def whiten(H, inn, dR, Res, neutral):

@@ -7,8 +7,10 @@
 // stdin:  map_max lc_max min_matches n_ops, then per op
 //   A n  (key in_state poor) x n      -> "a d..." the outcome of every record, "c count"
 //   Q n  key x n  kept x lc_max       -> "s slot..." (-1: no match, -2: surplus), "l entry..." the list, "f frame neutral x lc_max"
-// stdout starts with "S" and the sizeof of xivo_lcmap_opts, _entry, _add_rec, _query, _match, _stats.
+// stdout starts with "S" and the sizeof of xivo_lcmap_opts, _entry, _add_rec, _query, _match, _stats, and ends with the
+// floating-point rules at their ties ("p", "k") and lcmap_kept on gammas that are not finite ("n").
 #include <cstdio>
+#include <limits>
 #include <vector>
 
 #include "../include/xivo_hip.h"
@@ -79,5 +81,9 @@ int main() {
   // the two floating-point rules at their ties
   printf("p %d %d %d %d\n", lcmap_poor(1.0, 1.0), lcmap_poor(1.0000000000000002, 1.0), lcmap_poor(5.0, 0.0), lcmap_poor(0.5, 1.0));
   printf("k %d %d %d %d\n", lcmap_kept(1, 5.0, 5.0), lcmap_kept(1, 5.000000000000001, 5.0), lcmap_kept(1, 1e9, 0.0), lcmap_kept(0, 0.0, 5.0));
+  // a gamma that is not finite is never kept, with a gate or without one; the largest finite one is, without a gate
+  const double qnan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  printf("n %d %d %d %d %d %d %d\n", lcmap_kept(1, qnan, 5.99), lcmap_kept(1, qnan, 0.0), lcmap_kept(1, inf, 5.99), lcmap_kept(1, inf, 0.0),
+         lcmap_kept(1, -inf, 5.99), lcmap_kept(1, -qnan, 0.0), lcmap_kept(1, std::numeric_limits<double>::max(), 0.0));
   return 0;
 }

@@ -92,11 +92,20 @@ def rows(matches, Rbc, Tbc, cam, lay, lc_max, Rlc):
 
 
 def gamma(Hi, P, r, Rlc):
-    """r^T (H_i P H_i^T + Rlc I)^-1 r of one pair; None where S has a non-positive pivot"""
+    """r^T (H_i P H_i^T + Rlc I)^-1 r of one pair; None (the device shows -1) where S has a non-positive pivot or the value is
+    not finite - a NaN or inf pixel or stored point"""
     S = Hi @ P @ Hi.T + Rlc * np.eye(2)
     if not (S[0, 0] > 0 and S[1, 1] - S[1, 0] ** 2 / S[0, 0] > 0):
         return None
-    return float(r @ np.linalg.solve(S, r))
+    with np.errstate(all="ignore"):
+        g = float(r @ np.linalg.solve(S, r))
+    return g if np.isfinite(g) else None
+
+
+def kept(g, chi2):
+    """the gate of one match on gamma() (lcmap_kept): no pivot or no finite gamma is never kept, whatever chi2 is; chi2 = 0 is no
+    gate, equality keeps"""
+    return g is not None and bool(np.isfinite(g)) and not (chi2 > 0.0 and g > chi2)
 
 
 def neutralise(H, inn, dR, neutral):

@@ -27,6 +27,7 @@ CSRC = os.path.join(ROOT, "xivo_amd", "csrc")
 DRIVER = os.path.join(ROOT, "tests", "lcmap_cov_driver.cpp")
 BUILDS = {"plain": ["-O2"], "sanitized": ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}
 GRID = "g 0 %d" % (sum(nm + 1 for nm in range(8)) * 8 * 4 * 2 * 4 * (2 + 16))
+NONFINITE = "n 0 0 0 0 1"                  # NaN / inf gamma: not kept without a gate or with one, uses nothing, its pair neutral
 
 
 @pytest.fixture(scope="module", params=sorted(BUILDS))
@@ -65,8 +66,9 @@ def _play(exe, map_max, lc_max, min_matches, gap, ops):
                 assert not any(r["resting"]) and (r["frame"], r["neutral"]) == (frame, [int(x) for x in neutral])
     out = subprocess.run([exe], input="\n".join(lines) + "\n", check=True, capture_output=True, text=True).stdout.splitlines()
     assert out[0].startswith("S ")
-    assert out[1:-1] == want
-    assert out[-1] == GRID                 # gap = 0 on the whole grid: no mismatch
+    assert out[1:-2] == want
+    assert out[-2] == GRID                 # gap = 0 on the whole grid: no mismatch
+    assert out[-1] == NONFINITE
     return v, res
 
 
@@ -76,7 +78,53 @@ def test_struct_sizes_equal_the_numpy_mirrors(driver):
     assert L.lcmap_cov_stats_dtype.names == CR.COV_STATS == L.LCMAP_COV_STATS_FIELDS
     for name in ("xivo_hip_lcmap_cov_config", "xivo_hip_lcmap_set_cov", "xivo_hip_lcmap_get_cov", "xivo_hip_lcmap_get_cov_stats"):
         assert name in L.ALL_SYMBOLS
-    assert out[-1] == GRID
+    assert out[-2] == GRID and out[-1] == NONFINITE
+
+
+def test_an_entry_of_H_Sigma_Ht_is_rounded_once_where_a_plain_sum_loses_digits(driver):
+    """lcmap_quad3 (a^T C b, the entries of R_e - Rlc I) against exact rational arithmetic on 300 nearly rank-one C = s^2 n n^T +
+    (1 mm)^2 I with a and b within 1e-1 .. 1e-4 of orthogonal to n: within one ulp of the exact value (plus 2^-100 of the sum of
+    the |products|, what two doubles carry), where numpy's plain sums of the same products are tens of ulp off"""
+    from fractions import Fraction as Fr
+    rng = np.random.default_rng(77)
+    cases = []
+    for _ in range(300):
+        n = rng.normal(size=3); n /= np.linalg.norm(n)
+        C = 10.0 ** rng.uniform(0, 4) * np.outer(n, n) + 1e-6 * np.eye(3)
+        C = np.triu(C) + np.triu(C, 1).T
+        v = []
+        for _ in range(2):
+            t = rng.normal(size=3); t -= (t @ n) * n
+            v.append(100.0 * (t / np.linalg.norm(t) + 10.0 ** rng.uniform(-4, -1) * n))
+        cases.append((C, v[0], v[0] if rng.uniform() < 0.5 else v[1]))
+    lines = ["1 1 1 0 %d" % len(cases)]
+    for C, a, b in cases:
+        lines.append("C 0 " + " ".join(float(x).hex() for x in [C[0, 0], C[0, 1], C[0, 2], C[1, 1], C[1, 2], C[2, 2], *a, *b]))
+    out = subprocess.run([driver], input="\n".join(lines) + "\n", check=True, capture_output=True, text=True).stdout.splitlines()
+    got = [float.fromhex(l.split()[1]) for l in out[1:-2]]
+    assert len(got) == len(cases) and out[-2] == GRID
+    worst = plain = 0.0
+    for (C, a, b), q in zip(cases, got):
+        terms = [Fr(float(C[i, j])) * Fr(float(a[j])) * Fr(float(b[i])) for i in range(3) for j in range(3)]
+        exact = sum(terms)
+        ulp = Fr(float(np.spacing(abs(float(exact)))))
+        assert abs(Fr(q) - exact) <= ulp + sum(abs(t) for t in terms) / 2 ** 100, (C, a, b, q)
+        worst = max(worst, float(abs(Fr(q) - exact) / ulp)); plain = max(plain, float(abs(Fr(float(b @ (C @ a))) - exact) / ulp))
+    print("lcmap_quad3: worst %.2f ulp; the plain sum: %.0f ulp" % (worst, plain))
+    assert plain > 16.0                                                   # (the cases are hard: what the kernel's sums used to lose)
+
+
+def test_a_gamma_that_is_not_finite_is_never_kept_on_R_e_either():
+    """the restatement's side of the rule: a NaN or inf innovation on a definite R_e gives no gamma, with a gate or without"""
+    c = CC.gate_case(synth.EQUI)
+    H, inn, dR, Res = CC.rows0(c, synth.EQUI)
+    assert CR.gamma(H[0:2], c["P"][0], inn[0:2], Res[0]) is not None
+    for bad in ((np.nan, inn[1]), (inn[0], np.nan), (np.inf, inn[1]), (-np.inf, np.inf)):
+        g = CR.gamma(H[0:2], c["P"][0], np.array(bad), Res[0])
+        assert g is None and not R.kept(g, LC.CHI2) and not R.kept(g, 0.0), bad
+    v = CR.VisitRestate(8, 6, 1, 2); v.add(range(8))
+    r = v.close([0, 1], [R.kept(None, 0.0), True])                        # closes on the other match; the NaN one uses nothing
+    assert r["frame"] == CR.CLOSED and r["neutral"][:2] == [1, 0] and v.used[:2] == [0, 1] and v.stats["gated"] == 1
 
 
 ADD8 = ("A", list(range(8)))

@@ -56,9 +56,10 @@ def _play(exe, map_max, lc_max, min_matches, ops):
             res.append((slots, lst, frame, neutral))
     out = subprocess.run([exe], input="\n".join(lines) + "\n", check=True, capture_output=True, text=True).stdout.splitlines()
     assert out[0].startswith("S ")
-    assert out[1:-2] == want
-    assert out[-2] == "p 0 1 0 0"          # poor: equality keeps, one ulp above drops, 0 means no test
-    assert out[-1] == "k 1 0 1 0"          # kept: equality keeps, above gates, 0 means no gate, a bad pivot never passes
+    assert out[1:-3] == want
+    assert out[-3] == "p 0 1 0 0"          # poor: equality keeps, one ulp above drops, 0 means no test
+    assert out[-2] == "k 1 0 1 0"          # kept: equality keeps, above gates, 0 means no gate, a bad pivot never passes
+    assert out[-1] == "n 0 0 0 0 0 0 1"    # kept: NaN and inf never pass, with a gate (5.99) or without (0); DBL_MAX without one does
     return m, res
 
 
@@ -120,6 +121,29 @@ def test_one_fewer_than_min_matches_is_short(driver):
     assert res[1][2] == R.SHORT and res[1][3] == [True] * 6                        # 4 kept: every pair neutral
     assert res[2][2] == R.CLOSED and res[2][3] == [False, False, True, False, False, False]
     assert res[3][2] == R.NONE and res[3][3] == [True] * 6
+
+
+@pytest.mark.parametrize("chi2", [LC.CHI2, 0.0])
+def test_a_gamma_that_is_not_finite_is_gated_and_does_not_count(chi2):
+    """the restatement's side of the rule the driver prints: a NaN or inf pixel gives finite rows and pivots, no gamma, and a
+    match that is not kept with a gate or without one - five of six kept still close, four of five are short"""
+    cam = LC.CAMS["equi"]
+    c = LC.update_case(cam)
+    sc, lay = c["sc"], LC.layout()
+    for bad in ((np.nan, 7.0), (7.0, np.nan), (np.inf, 7.0)):
+        ms = [dict(Xs=c["Xs"][0, j], Rsb=c["Rsb_p"][0], Tsb=c["Tsb_p"][0], g_sind=-1, xp=np.array(bad) if j == 2 else c["queries"][j][2])
+              for j in range(6)]
+        H, inn, dR = R.rows(ms, sc["Rbc"][0], sc["Tbc"][0], cam, lay, LC.LC_MAX, LC.RLC)
+        assert np.isfinite(H).all() and not np.isfinite(inn[4:6]).all()
+        g = [R.gamma(H[2 * m:2 * m + 2], c["P"][0], inn[2 * m:2 * m + 2], LC.RLC) for m in range(6)]
+        k = [R.kept(v, chi2) for v in g]
+        assert g[2] is None and k == [True, True, False, True, True, True]
+        m = R.MapRestate(LC.MAP_MAX, LC.LC_MAX, LC.MIN_MATCHES)
+        frame, neutral = m.decide(k)
+        assert frame == R.CLOSED and neutral[2] and m.stats["gated"] == 1
+        assert np.isfinite(R.neutralise(H, inn, dR, neutral)[1]).all()
+        assert R.MapRestate(LC.MAP_MAX, LC.LC_MAX, LC.MIN_MATCHES).decide(k[:5])[0] == R.SHORT     # four kept of five
+    assert R.kept(1e300, 0.0) and R.kept(chi2, chi2) and not R.kept(None, chi2)
 
 
 def test_header_stays_plain_cxx():

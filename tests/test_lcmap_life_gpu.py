@@ -339,6 +339,54 @@ def test_more_than_64_feature_slots_and_a_surplus(built):
         H.close(); D.close()
 
 
+class _Recording(sequence.HipBackend):
+    """the host life cycle's backend, keeping every add record and query it hands down"""
+
+    def lcmap_add(self, recs):
+        self.__dict__.setdefault("said", []).append(("A", recs.copy()))
+        super().lcmap_add(recs)
+
+    def lcmap_close(self, queries):
+        self.__dict__.setdefault("said", []).append(("Q", queries.copy()))
+        return super().lcmap_close(queries)
+
+
+def test_all_72_slots_leave_in_one_frame_and_return(built):
+    """the row / count form of the records past 64 entries: n_features = 72, every slot of filters 0 and 1 leaves in frame 1 into
+    lc_map_max = 80 - the add kernel's duplicate search takes its second pass from entry 64 on - and returns under its key. Both
+    life cycles agree, and the map's keys and counters are those of tests/lcmap_restate.py's MapRestate on the records and
+    queries the host life cycle handed down: the comparison is not between two runs of the same kernels only."""
+    import lcmap_restate as R
+    shape = dict(n_groups=4, n_features=72)
+    lc = dict(lc_map_max=80, lc_max=64, lc_min_matches=2)
+    script = _revisit(4, leave=tuple(range(72)), n_pts=72, short_keys=False)
+    cfg_h, cfg_d = _cfgs(True, shape=shape, tracks_max=80, **lc)
+    H, D, rh, rd = _open(cfg_h, cfg_d, host_cls=_Recording)
+    try:
+        for t, (tracks, keys) in enumerate(_frames(script, True)):
+            rh.frame(None, tracks, keys); rd.frame(None, tracks, keys)
+            _same(H, D, rh, "72 leave, frame %d" % t)
+        want = [R.MapRestate(80, 64, 2) for _ in range(B)]
+        for kind, a in getattr(H, "said", []):
+            for b in range(B):
+                mine = a[a["b"] == b]
+                if kind == "A":
+                    want[b].add([(int(k), True, False, None) for k in mine["key"]])
+                else:
+                    want[b].match([int(k) for k in mine["key"]])
+        st, (ent, cnt) = D.lcmap_stats(), D.ctx.lcmap_get(0, B)
+        print({k: st[k].tolist() for k in ("added", "dup", "full", "queries", "matched", "surplus")})
+        assert cnt.tolist() == [72, 72, 0]
+        for b in range(B):
+            assert ent["key"][b, :cnt[b]].tolist() == want[b].keys, b
+            for k in ("added", "dup", "full", "poor", "skipped", "queries", "matched", "surplus"):
+                assert st[k][b] == want[b].stats[k], (b, k)
+        assert want[0].keys == list(range(72)) and st["added"].tolist() == [72, 72, 0]       # slot order: the key is the point
+        assert st["matched"][0] > 0 and st["surplus"][0] > 0                                 # 72 returning keys, 64 list positions
+    finally:
+        H.close(); D.close()
+
+
 def test_lc_max_smaller_than_the_matching_queries(built):
     st, _, _, _ = _run(_revisit(5), lc_max=2)
     assert st["surplus"][0] == 2 * 2 and st["matched"][0] == 2 * 2

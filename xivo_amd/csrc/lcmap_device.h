@@ -1,5 +1,6 @@
 // The integer rules of the resident landmark map (xivo_hip_lcmap_*, include/xivo_hip.h): what becomes of an add record, which
-// place a matching query takes in a filter's match list, whether a filter closes. Plain functions of integers, shared by the
+// place a matching query takes in a filter's match list, whether a filter closes - and the one piece of its arithmetic that
+// needs care, an entry of H_T Sigma H_T^T (lcmap_quad3). Plain functions of integers and doubles, shared by the
 // kernels (lcmap_kernels.hip) and by a host program that holds them against a restatement (tests/lcmap_driver.cpp): this file
 // includes no project header and takes HIP's only under __HIPCC__.
 #pragma once
@@ -41,8 +42,13 @@ LCMAP_HD int lcmap_find(const long long* keys, long stride, int count, long long
 LCMAP_HD int lcmap_match_slot(int rank, int lc_max) { return rank < lc_max ? rank : -1; }
 
 // ---- verify (stands in for pnp_ransac's inlier count, src/mapper.cpp:411-415)
-// gate of one match: a non-positive pivot of the 2 x 2 Cholesky, or gamma above chi2 (0: no gate; equality keeps) - not kept
-LCMAP_HD int lcmap_kept(int pivots_ok, double gamma, double chi2) { return pivots_ok && !(chi2 > 0.0 && gamma > chi2); }
+// gate of one match: a non-positive pivot of the 2 x 2 Cholesky, a gamma that is not finite (a NaN or inf pixel or stored
+// point: whatever chi2 is, 0 included - as everywhere else here NaN is "no candidate"), or gamma above chi2 (0: no gate;
+// equality keeps) - not kept. (gamma - gamma is 0 for a finite gamma alone: no <math.h> in this header)
+LCMAP_HD int lcmap_gamma_finite(double gamma) { return gamma - gamma == 0.0; }
+LCMAP_HD int lcmap_kept(int pivots_ok, double gamma, double chi2) {
+  return pivots_ok && lcmap_gamma_finite(gamma) && !(chi2 > 0.0 && gamma > chi2);
+}
 
 enum { LCMAP_FRAME_NONE = 0, LCMAP_FRAME_SHORT = 1, LCMAP_FRAME_CLOSED = 2 };
 // a filter with n_matched list positions filled of which n_kept passed the gate
@@ -53,6 +59,27 @@ LCMAP_HD int lcmap_frame_decide(int n_matched, int n_kept, int min_matches) {
 // is the row pair of list position m neutral (H = 0, inn = 0, diagR = 1)?
 LCMAP_HD int lcmap_pair_neutral(int frame, int m, int n_matched, int kept) {
   return frame != LCMAP_FRAME_CLOSED || m >= n_matched || !kept;
+}
+
+// ---- the point's covariance in the gate and the whitening (xivo_hip_lcmap_cov_config, point_cov): an entry of H_T Sigma H_T^T
+// a^T C b for a symmetric 3 x 3 C. The nine products a_j C_ij b_i are of size |C||a||b| and cancel where C is nearly rank one
+// and a or b nearly orthogonal to its large direction; summed plainly they leave 8 - 15 ulp in the entry, which kappa_2(R_e)
+// multiplies in gamma and in the whitened rows. Here every product is error-free (fma) and the sum runs in two doubles
+// (TwoSum): the entry is rounded once. No contraction inside - the roundings are the algorithm.
+LCMAP_HD double lcmap_quad3(const double (&C)[3][3], const double (&a)[3], const double (&b)[3]) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+  double sh = 0.0, sl = 0.0;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double ph = C[i][j] * a[j], pl = __builtin_fma(C[i][j], a[j], -ph);
+      const double qh = ph * b[i], ql = __builtin_fma(ph, b[i], -qh) + pl * b[i];
+      const double t = sh + qh, v = t - sh;
+      sl += ((sh - (t - v)) + (qh - v)) + ql;
+      sh = t;
+    }
+  return sh + sl;
 }
 
 // ---- one use per visit (xivo_hip_lcmap_cov_config, revisit_gap): an entry keeps {last_seen, used}, t numbers the close

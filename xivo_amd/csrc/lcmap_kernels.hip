@@ -278,11 +278,10 @@ __global__ __launch_bounds__(64) void lcmap_close_kernel(LcMapCloseArgs a) {
     if (EXT && a.ext.cov) {
       // R_e = Rlc I + H_T Sigma H_T^T, H_T = d xp / d Tsb: positions 3..5 of the pair's block (d xp / d Xs = -H_T)
       const double* sg = a.ext.cov + ((long)filt * a.map.map_max + mt.entry) * 6;
-      const double c00 = sg[0], c01 = sg[1], c02 = sg[2], c11 = sg[3], c12 = sg[4], c22 = sg[5];
-      const double a0 = h[3], a1 = h[4], a2 = h[5], b0 = h[15], b1 = h[16], b2 = h[17];
-      const double u0 = c00 * a0 + c01 * a1 + c02 * a2, u1 = c01 * a0 + c11 * a1 + c12 * a2, u2 = c02 * a0 + c12 * a1 + c22 * a2;
-      const double w0 = c00 * b0 + c01 * b1 + c02 * b2, w1 = c01 * b0 + c11 * b1 + c12 * b2, w2 = c02 * b0 + c12 * b1 + c22 * b2;
-      const double e00 = a.Rlc + (a0 * u0 + a1 * u1 + a2 * u2), e10 = b0 * u0 + b1 * u1 + b2 * u2, e11 = a.Rlc + (b0 * w0 + b1 * w1 + b2 * w2);
+      // (each entry rounded once, lcmap_quad3: a plain sum of the nine products loses what kappa_2(R_e) then multiplies)
+      const double C[3][3] = {{sg[0], sg[1], sg[2]}, {sg[1], sg[3], sg[4]}, {sg[2], sg[4], sg[5]}};
+      const double ha[3] = {h[3], h[4], h[5]}, hb[3] = {h[15], h[16], h[17]};
+      const double e00 = a.Rlc + lcmap_quad3(C, ha, ha), e10 = lcmap_quad3(C, ha, hb), e11 = a.Rlc + lcmap_quad3(C, hb, hb);
       w00 = sqrt(e00); w10 = e10 / w00;
       const double d11 = e11 - w10 * w10;
       w11 = sqrt(d11);
@@ -294,8 +293,9 @@ __global__ __launch_bounds__(64) void lcmap_close_kernel(LcMapCloseArgs a) {
     }
     const double l10 = s10 / sqrt(s00);
     const int ok = s00 > 0.0 && (s11 - l10 * l10) > 0.0 && ok_cov;
-    const double gamma = ok ? mh_dist_2x2(s00, s10, s11, inn[r0], inn[r0 + 1]) : -1.0;
+    double gamma = ok ? mh_dist_2x2(s00, s10, s11, inn[r0], inn[r0 + 1]) : -1.0;
     kept = lcmap_kept(ok, gamma, a.chi2);
+    if (!lcmap_gamma_finite(gamma)) gamma = -1.0;        // (a NaN or inf pixel: shown as a failed pivot is)
     list[lane].gamma = gamma; list[lane].kept = kept;
     if constexpr (EXT) list[lane].reserved = resting;
   }
