@@ -285,10 +285,13 @@ static int update_sparse_range(xivo_hip_ctx* c, const UpdatePlan& plan, const Up
     EllMulArgs a{}; a.ell = e; PHT.to(a.Src, a.strideSrc, a.ldsrc); HP.to(a.SrcAlt, a.strideSrcAlt, a.ldsrcAlt);
     S.to(a.out, a.strideOut, a.ldo); a.cols = Np;
     diagR.to(a.diagR, a.strideR); a.X = Mp; a.Mp = Mp_ell; a.batch = B; a.nc_max = nc_max; a.pw_max = pw_max;
+    // the lead product below starts its accumulators from S and, on 96 x 96 tiles, runs its diagonal tiles in full: it reads
+    // the 16 x 16 blocks above the diagonal inside them (and drops what it made of them) - S keeps them for it
+    a.keep_upper = lead ? 1 : 0;
     // the 2 x 2 diagonal blocks of S once more, compact: what the gate reads
     if (gate && mr0 < 0 && !lead && (long)2 * Mp <= Sdiag.stride) { Sdiag.to(a.diag_out, a.strideDiag); a.diag_done = &diag_done; }
     char label[64]; ell_kernel_label(ELL_S, a, label, sizeof(label));
-    StageTimer st(c, ST_S, nnz_flops * Mf * B, label, 8.0 * B * ((double)Np * Mp + (double)Mp * Mp));
+    StageTimer st(c, ST_S, nnz_flops * Mf * B, label, B * (8.0 * Np * Mp + ell_s_bytes_written(a)));
     HIP_TRY((hipError_t)launch_ell_mul(ELL_S, a, c->stream));
   }
   if (mr0 >= 0) {   // the OOS x OOS block of S (the OOS x in-state block came out of the walk above: rows of S run over all M)

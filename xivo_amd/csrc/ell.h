@@ -101,6 +101,7 @@ struct EllMulArgs {
   int Mp;       // rows of H in use (multiple of 16)
   int slabs_per_wg; // set by the launcher (slab form): consecutive slabs one workgroup streams
   int persist_stride; // set by the launcher (slab form, prefetching instantiation): > 0 = a workgroup walks filters b, b + stride, ...
+  int keep_upper; // ELL_S, slab form: also store the 16 x 16 tiles above the block diagonal (default: a later reader takes the lower triangle + the diagonal blocks only)
   int rb_per_wg; // set by the launcher: 16-row blocks one workgroup walks
   int nc_max;   // upper bound of nc over the filters of the launch (host mirror)
   int pw_max;   // upper bound of pw (0 = unknown -> ELL_PW)
@@ -111,6 +112,9 @@ int launch_ell_mul(int mode, const EllMulArgs& a, hipStream_t s);
 void ell_kernel_label(int mode, const EllMulArgs& a, char* buf, size_t n);
 // true when launch_ell_mul will run the slab-in-LDS form for these arguments
 bool ell_uses_slab_form(const EllMulArgs& a);
+// bytes of S that launch_ell_mul(ELL_S) writes per filter: the slab form stores the 16 x 16 tiles on and below the block
+// diagonal only, the gather form every element
+double ell_s_bytes_written(const EllMulArgs& a);
 
 int launch_gate_ell(const GateEllArgs& a, hipStream_t s);
 

@@ -318,6 +318,7 @@ __device__ __forceinline__ void ell_buf_st(double v, __amdgpu_buffer_rsrc_t r, u
 constexpr bool ell_tile_mf(int mode, int cwu, int xc, int pwu) {
   return (xc == 64 || xc == 32) && cwu % 4 == 0 && pwu % 3 == 0 && (mode == ELL_HP || mode == ELL_S);
 }
+template <int V> struct ell_ic { static constexpr int value = V; };   // a compile-time block count as a lambda argument
 constexpr int ell_tile_threads(int mode, int cwu, int xc, int pwu) {
   return (mode == ELL_S || ell_tile_pf(mode, cwu, xc, pwu)) ? 512 : 1024;
 }
@@ -416,14 +417,27 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
       }
     }
   };
-  auto park = [&]() {
+  // park the prefetched slab and, register by register, request the next one (slab nsidx of FSrc, if there is one): a
+  // register of r[] is free as soon as its LDS write has issued and the loads touch no LDS, so they need not wait for the
+  // barrier that publishes the slab - the workgroup owns its CU and would have nothing in flight until then
+  static_assert(!PF || MODE == ELL_S, "the prefetching form is the S instantiation");
+  auto park = [&](const double* FSrc, int nsidx, bool have) {
     if (MODE == ELL_S) {
       constexpr int KU = RN / (XC / NW);
+      const __amdgpu_buffer_rsrc_t rs = ell_rsrc(FSrc);
+      const unsigned vo = (unsigned)lane * 8u;
+      const int nx0 = nsidx * XC;
 #pragma unroll
       for (int q = 0; q < XC / NW; ++q) {
         const int jj = wave + NW * q;
+        const bool ok = have && nx0 + jj < a.X;
+        const unsigned so = (unsigned)((nx0 + (ok ? jj : 0)) * a.ldsrc) * 8u;
 #pragma unroll
-        for (int u = 0; u < KU; ++u) { const int k = lane + 64 * u; if (k < cols) tile[k * XC + (jj ^ (k & 15))] = r[q * KU + u]; }
+        for (int u = 0; u < KU; ++u) {
+          const int k = lane + 64 * u;
+          if (k < cols) tile[k * XC + (jj ^ (k & 15))] = r[q * KU + u];
+          r[q * KU + u] = (ok && k < cols) ? ell_buf_ld(rs, vo, so + (unsigned)(64 * u) * 8u) : 0.0;
+        }
       }
     } else {
       const int xx = tid % XC, kq = tid / XC;
@@ -435,6 +449,16 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
   const int xx = lane % XC, half = lane / XC;
   auto slab = [&](int k) -> double { return tile[k * XC + (xx ^ (k & 15))]; };
 
+  // S, matrix-core walk: R of a slab's columns, lane l = column l, requested one slab ahead like the slab itself and behind
+  // it. The walk then waits for no load: loads return in order, and one requested next to the walk (the four of the
+  // earlier form were) makes its first use wait for the whole prefetch in front of it - load and walk added up
+  constexpr bool SMF = MODE == ELL_S && ell_tile_mf(MODE, CWU, XC, PWU);
+  auto load_dR = [&](int f, int s) -> double {
+    const int xr = s * XC + lane % XC;
+    return xr < a.X ? a.diagR[(long)f * a.strideR + xr] : 0.0;
+  };
+  double dRn = 0.0;
+  if (SMF) dRn = load_dR(filt, s_begin);
   const int fstep = PF ? a.persist_stride : 0;
   if (PF) fetch(Src, s_begin);
   for (;;) {   // (one trip unless persistent)
@@ -443,8 +467,12 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
   const int nfilt = filt + fstep;
   const bool more = fstep > 0 && nfilt < a.batch;
   for (int sidx = s_begin; sidx < s_end; ++sidx) {
+    const double dRs = dRn;
+    // what comes after this slab: the next slab of the filter, or the first one of the next filter (persistent form)
+    const bool last = sidx + 1 == s_end, have = !last || more;
+    const int nf = last && more ? nfilt : filt, ns = last ? s_begin : sidx + 1;
     if (PF) {
-      park();
+      park(a.Src + (long)nf * a.strideSrc, ns, have);
     } else if (MODE == ELL_S) {
       const int x0 = sidx * XC;
       for (int jj = wave; jj < XC; jj += NW) {
@@ -471,14 +499,11 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
       }
     }
     // (prefetching form: LDS-only barrier - __syncthreads() would also wait for the acknowledgement of the output stores the
-    //  walk before just issued, a round trip to memory per slab; the prefetched registers were waited for by park())
+    //  walk before just issued, a round trip to memory per slab, and for the next slab park() just requested)
     if (PF) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     else __syncthreads();
-    if (PF) {
-      if (sidx + 1 < s_end) fetch(Src, sidx + 1);
-      else if (more) fetch(a.Src + (long)nfilt * a.strideSrc, s_begin);
-    }
 
+    if (SMF && have) dRn = load_dR(nf, ns);
     if constexpr (ell_tile_mf(MODE, CWU, XC, PWU)) {
       // ---- walk, matrix-core form (the hot instantiations: 12 common + 9 private slots, 64-wide slabs) --------------------
       // The scalar-coefficient walk below is bound by the LDS: every coefficient pair reaches its 64 lanes as a 16-byte
@@ -501,21 +526,24 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
       const int x0 = sidx * XC;
       const __amdgpu_buffer_rsrc_t rO = ell_rsrc(a.out + (long)filt * a.strideOut);
       const unsigned vO = (unsigned)(2 * lg * a.ldo + li) * 8u;          // row 2 lg, column li of a tile; the rest of the address is wave-uniform
-      double dRc[NC];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) dRc[c] = 0.0;
-      if (MODE == ELL_S) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) if (x0 + 16 * c + li < a.X) dRc[c] = a.diagR[(long)filt * a.strideR + x0 + 16 * c + li];
-      }
       // (S: the row-pair blocks to the right of this slab's diagonal square are skipped - lower triangle + diagonal blocks)
       const int rb_end = MODE == ELL_S ? min(pairs / 8, NC * (sidx + 1)) : pairs / 8;
       const int pa = (li & 3) + 4 * (li >> 3), ra = (li >> 2) & 1;     // A operand: MFMA row li = pair pa, row ra of it
-      for (int rb = wave; rb < rb_end; rb += NW) {
-        const int p0 = 8 * rb;
-        d4 acc[NC];
+      // one step: row-pair block rb x the NB sixteen-column blocks c0 .. c0 + NB - 1 of the slab. NB is a compile-time count
+      // and c0 only moves addresses, so acc[] and g[][] keep their static indices (registers) at every width
+      auto step = [&](auto nb_tag, int rb, int c0) {
+        constexpr int NB = decltype(nb_tag)::value;
+        const int p0 = 8 * rb, cofs = 16 * c0;
+        // S: R goes onto the diagonal, which only the diagonal block of the row-pair block holds - if it is one of this
+        // step's (lane l of dRs holds R of slab column l)
+        double dRv = 0.0;
+        if (MODE == ELL_S) {
+          const int cd = rb - NC * sidx;
+          if (cd >= c0 && cd < c0 + NB) dRv = __shfl(dRs, 16 * cd + li);
+        }
+        d4 acc[NB];
 #pragma unroll
-        for (int c = 0; c < NC; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
+        for (int c = 0; c < NB; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
         // the private slots first (plain FMAs into the zeroed tile), the dense common part on top of them: the other way
         // round the scheduler hoists every LDS read of the private part above the MFMA chain it depends on - and spills
         if constexpr (NT == 512) {   // (the 8-wave instantiations have the registers for it: 256 per wave)
@@ -541,17 +569,17 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
             for (int t0 = 0; t0 < PWU; t0 += 3) {
               // three slots per step, their 12 gathers in flight together (the scheduler, left alone, serialises them in the
               // second half-tile - one LDS round trip per gather)
-              d2 v[3]; double g[3][NC];
+              d2 v[3]; double g[3][NB];
   #pragma unroll
               for (int u = 0; u < 3; ++u) {
                 const int t = t0 + u;
                 v[u] = vn[u];
                 const unsigned w = (t & 2) ? iq[q][t >> 2].y : iq[q][t >> 2].x;
                 const int k = (int)((t & 1) ? (w >> 16) : (w & 0xffffu));
-                const double* trow = tile + k * XC;
+                const double* trow = tile + k * XC + cofs;
                 const int sw = k & 15;
   #pragma unroll
-                for (int c = 0; c < NC; ++c) g[u][c] = trow[(16 * c + li) ^ sw];
+                for (int c = 0; c < NB; ++c) g[u][c] = trow[(16 * c + li) ^ sw];
               }
               if (t0 + 3 < PWU) {
   #pragma unroll
@@ -561,7 +589,7 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
   #pragma unroll
               for (int u = 0; u < 3; ++u) {
   #pragma unroll
-                for (int c = 0; c < NC; ++c) {
+                for (int c = 0; c < NB; ++c) {
                   acc[c][2 * q] = fma(v[u][0], g[u][c], acc[c][2 * q]);
                   acc[c][2 * q + 1] = fma(v[u][1], g[u][c], acc[c][2 * q + 1]);
                 }
@@ -579,21 +607,21 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
             for (int t0 = 0; t0 < PWU; t0 += 3) {
               // three slots per step, their 12 gathers in flight together (the scheduler, left alone, serialises them in the
               // second half-tile - one LDS round trip per gather)
-              d2 v[3]; double g[3][NC];
+              d2 v[3]; double g[3][NB];
   #pragma unroll
               for (int u = 0; u < 3; ++u) {
                 v[u] = pv[t0 + u];
                 const int k = (int)pkp[t0 + u];
-                const double* trow = tile + k * XC;
+                const double* trow = tile + k * XC + cofs;
                 const int sw = k & 15;
   #pragma unroll
-                for (int c = 0; c < NC; ++c) g[u][c] = trow[(16 * c + li) ^ sw];
+                for (int c = 0; c < NB; ++c) g[u][c] = trow[(16 * c + li) ^ sw];
               }
               __builtin_amdgcn_sched_barrier(0);
   #pragma unroll
               for (int u = 0; u < 3; ++u) {
   #pragma unroll
-                for (int c = 0; c < NC; ++c) {
+                for (int c = 0; c < NB; ++c) {
                   acc[c][2 * q] = fma(v[u][0], g[u][c], acc[c][2 * q]);
                   acc[c][2 * q + 1] = fma(v[u][1], g[u][c], acc[c][2 * q + 1]);
                 }
@@ -604,35 +632,76 @@ __global__ __launch_bounds__(ell_tile_threads(MODE, CWU, XC, PWU)) void ell_tile
         {
           // (the B operand is re-read from the slab per tile, 12 reads: held across the private part its 24 registers made
           //  the scheduler serialise that part's gathers)
-          double av[KS], cb[KS][NC];
+          double av[KS], cb[KS][NB];
 #pragma unroll
           for (int s = 0; s < KS; ++s) {
             av[s] = ops[((long)(p0 + pa) * NSLOT + 4 * s + lg) * 2 + ra];
 #pragma unroll
-            for (int c = 0; c < NC; ++c) cb[s][c] = tile[ck[s] * XC + ((16 * c + li) ^ (ck[s] & 15))];
+            for (int c = 0; c < NB; ++c) cb[s][c] = tile[ck[s] * XC + cofs + ((16 * c + li) ^ (ck[s] & 15))];
           }
 #pragma unroll
-          for (int c = 0; c < NC; ++c) {
+          for (int c = 0; c < NB; ++c) {
 #pragma unroll
             for (int s = 0; s < KS; ++s) acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], cb[s][c], acc[c], 0, 0, 0);
           }
         }
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          const int x = x0 + 16 * c + li;
+        for (int c = 0; c < NB; ++c) {
+          const int x = x0 + cofs + 16 * c + li;
           if (x >= a.X) continue;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int pp = p0 + lg + 4 * (r >> 1), i = r & 1, m = 2 * pp + i;
-            const unsigned sO = (unsigned)((2 * p0 + 8 * (r >> 1) + i) * a.ldo + x0 + 16 * c) * 8u;
+            const unsigned sO = (unsigned)((2 * p0 + 8 * (r >> 1) + i) * a.ldo + x0 + cofs + 16 * c) * 8u;
             if (MODE == ELL_HP) ell_buf_st(acc[c][r], rO, vO, sO);
             else {
-              const double sv_ = acc[c][r] + (x == m ? dRc[c] : 0.0);
+              const double sv_ = acc[c][r] + (x == m ? dRv : 0.0);
               ell_buf_st(sv_, rO, vO, sO);
               if (a.diag_out && (x >> 1) == pp) a.diag_out[(long)filt * a.strideDiag + 4 * pp + 2 * (x & 1) + i] = sv_;
             }
           }
         }
+      };
+      if constexpr (MODE == ELL_S) {
+        // Only the column blocks somebody reads are formed: block c of the slab is live for row-pair block rb when it starts
+        // left of a.X (the last slab is partly padding) and lies on or below the block diagonal (NC sidx + c >= rb; the
+        // diagonal blocks stay complete, both triangles: diag_out and the factorisation read them). The slab's live blocks,
+        // counted row after row (rows above the slab's diagonal square: all chi of them, then chi, chi - 1, ... on the
+        // square), are dealt to the waves in runs of cap = ceil(total / NW): no wave forms more than cap, the least any deal
+        // can reach, and a row cut by a run's end repeats its index and coefficient reads in two waves. Live blocks per
+        // slab -> cap, against the 4 per step of the deal "rb = wave, wave + NW, ..." over whole slabs:
+        //   Mp = 128: 10, 26      -> 2 + 4     =  6 per filter in the busiest wave (was 4 + 4     =  8)
+        //   Mp = 160: 10, 26, 19  -> 2 + 4 + 3 =  9                                (was 4 + 4 + 8 = 16)
+        //   Mp = 176: 10, 26, 30  -> 2 + 4 + 4 = 10                                (was 4 + 4 + 8 = 16)
+        const int chi = min(NC, (a.X - x0 + 15) / 16);
+        // (a.keep_upper: a reader of the blocks above the diagonal follows - every row-pair block takes all chi)
+        const int nfull = a.keep_upper ? rb_end : min(rb_end, NC * sidx), nd = min(rb_end - nfull, chi);
+        const int total = nfull * chi + nd * chi - nd * (nd - 1) / 2;
+        const int cap = (total + NW - 1) / NW;
+        int pos = wave * cap;
+        const int hi = min(total, pos + cap);
+        if (pos < hi) {
+          int rb, c;
+          if (pos < nfull * chi) { rb = pos / chi; c = pos - rb * chi; }
+          else {
+            int q = pos - nfull * chi, d = 0;
+            while (q >= chi - d) { q -= chi - d; ++d; }
+            rb = nfull + d; c = d + q;
+          }
+          while (pos < hi) {
+            const int n = min(chi - c, hi - pos);
+            if (n == 1) step(ell_ic<1>{}, rb, c);
+            else if (n == 2) step(ell_ic<2>{}, rb, c);
+            else if constexpr (NC > 2) {
+              if (n == 3) step(ell_ic<3>{}, rb, c);
+              else step(ell_ic<NC>{}, rb, c);
+            }
+            pos += n; c += n;
+            if (c == chi) { ++rb; c = rb < nfull ? 0 : rb - NC * sidx; }
+          }
+        }
+      } else {
+        for (int rb = wave; rb < rb_end; rb += NW) step(ell_ic<NC>{}, rb, 0);
       }
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       continue;
@@ -814,6 +883,20 @@ bool ell_uses_slab_form(const EllMulArgs& a) {
   int xc, cwu, pwu; size_t lds;
   ell_pick(a, &xc, &cwu, &pwu, &lds);
   return xc != 0;
+}
+
+double ell_s_bytes_written(const EllMulArgs& a) {
+  int xc, cwu, pwu; size_t lds;
+  ell_pick(a, &xc, &cwu, &pwu, &lds);
+  if (!xc) return 8.0 * a.X * a.Mp;
+  const int NC = xc / 16;
+  long tiles = 0;                                   // the live blocks of every slab, counted as the kernel's deal counts them
+  for (int sidx = 0; sidx * xc < a.X; ++sidx) {
+    const int rb_end = std::min(a.Mp / 16, NC * (sidx + 1)), chi = std::min(NC, (a.X - sidx * xc + 15) / 16);
+    const int nfull = a.keep_upper ? rb_end : std::min(rb_end, NC * sidx), nd = std::min(rb_end - nfull, chi);
+    tiles += nfull * chi + nd * chi - nd * (nd - 1) / 2;
+  }
+  return 2048.0 * tiles;
 }
 
 void ell_kernel_label(int mode, const EllMulArgs& a, char* buf, size_t n) {
