@@ -1390,6 +1390,46 @@ int xivo_hip_lcmap_life_get_keys(xivo_hip_ctx* ctx, int b0, int nb, long long* f
  * the ids: keys host [nb][tracks_max], -1 behind the filter's count. Synchronises. */
 int xivo_hip_lcmap_life_get_track_keys(xivo_hip_ctx* ctx, int b0, int nb, long long* keys);
 
+/* ---- tuning table: per-filter noise parameters (opt-in) -----------------------------------------------------------------
+ * Every call above takes one R, one MH_thresh, one Qimu / Qmodel and one var_xyz for all the filters it touches. A configured
+ * table gives every filter of the context its own: T tunings x W worlds = batch_max filters in one context, one run, one score
+ * per tuning (xivo_amd/sweep.py). Off by default; without a table every call computes what it computes without this section.
+ *
+ * The table is device memory of the context, one array per field: R [batch_max], mh_thresh [batch_max], var_xyz [batch_max][3],
+ * Qimu [batch_max][144], Qmodel [batch_max][529] (the two matrices as xivo_prop_opts holds them). While it is configured
+ *   xivo_hip_mh_gate, xivo_hip_stack, xivo_hip_filter_update   use filter b's R (the in-state gate's R and the stacked rows'
+ *       diagR) and mh_thresh; their scalar R / mh_thresh arguments are still validated and otherwise not read. mh_mult,
+ *       min_inliers and use_gating stay the call's. A re-stacking of the dense rows (xivo_hip_get_H, the dense pipeline) reads
+ *       the table again;
+ *   xivo_hip_propagate, xivo_hip_propagate_resident             use filter b's Qimu / Qmodel - for a range [b0, b0 + nb) the
+ *       entries of those filters -, not the matrices of xivo_prop_opts (resp. of the trajectory producer);
+ *   xivo_hip_life_end                                           gives a new feature of filter b diag(var_xyz[b]).
+ * The values enter the same expressions in the same order as the scalar arguments do: a table whose rows all equal the scalar
+ * arguments leaves every result bit for bit what it is without a table. What carries an R of its own is untouched: Roos, Rlc,
+ * the sub-filter's Rtri; the pool life cycle's std_xyz is not var_xyz and is not tuned.
+ * Calls that take one parameter set and would have to apply it silently are refused while a table is configured
+ * (XIVO_HIP_ERR_UNSUPPORTED, nothing changed): xivo_hip_one_point_ransac, xivo_hip_mh_gate_dense, xivo_hip_update_dense_gated,
+ * xivo_hip_propagate_calib, and xivo_hip_set_calib with a layout. Not tuned: gravity, mh_mult / min_inliers, the RANSAC
+ * thresholds, the sub-filter's options. */
+typedef struct {
+  double R;            /* visual_meas_std^2: the in-state gate's R and the stacked rows' diagR */
+  double mh_thresh;    /* MH_thresh */
+  double var_xyz[3];   /* a new feature's variances in xivo_hip_life_end */
+  double Qimu[144];    /* as xivo_prop_opts */
+  double Qmodel[529];
+} xivo_tune_in;        /* 5424 bytes */
+/* Configure the table with every filter of batch_max = *all (already configured: every row is overwritten), or release it
+ * (all = NULL: the scalar arguments are back; synchronises). Allocates the five arrays and two page-locked staging blocks of
+ * batch_max entries. XIVO_HIP_ERR_INVALID, nothing changed: an entry xivo_hip_tune_set refuses. XIVO_HIP_ERR_UNSUPPORTED: a
+ * context with online calibration (xivo_hip_set_calib). */
+int xivo_hip_tune_config(xivo_hip_ctx* ctx, const xivo_tune_in* all);
+/* Rows [b0, b0 + nb) <- t [nb]. Stages through page-locked memory and only enqueues: t may be reused at once, the rows take
+ * effect for the calls enqueued after this one. XIVO_HIP_ERR_INVALID, nothing changed - not one row of the call: no table, a
+ * bad range, a non-finite value anywhere, R or mh_thresh not positive, a negative var_xyz. */
+int xivo_hip_tune_set(xivo_hip_ctx* ctx, int b0, int nb, const xivo_tune_in* t);
+/* Read-back of rows [b0, b0 + nb). Synchronises. */
+int xivo_hip_tune_get(xivo_hip_ctx* ctx, int b0, int nb, xivo_tune_in* t);
+
 /* ---- covariance propagation tail (src/rk4.cpp:92-102, src/estimator.cpp:590) */
 /* P_mm <- Pmm_new ; P_ms <- Phi P_ms ; P_sm <- P_sm Phi^T. Phi and Pmm_new
  * are nm x nm (nm = kMotionSize: 23, or up to 40 for the online-calibration builds), one pair per filter. */

@@ -14,6 +14,7 @@ int gate_impl(xivo_hip_ctx* c, int B, const GateParams& gp, int use_gating) {
   GateArgs a{};
   a.sb = scene_buffers(c); a.lay = c->lay; c->P.to(a.P, a.strideP, a.ldp);
   a.gp = gp; a.batch = B; a.use_gating = use_gating;
+  a.tune_R = c->tune.R; a.tune_thresh = c->tune.thresh;   // (tuning table: null without one)
   char label[64];
   gate_sparse_threads(B, a.sb.F, a.sb.Jc ? 1 : 0, label, sizeof(label));
   StageTimer st(c, ST_GATE, 0.0, label);
@@ -53,6 +54,7 @@ int stack_impl(xivo_hip_ctx* c, int B, double R, int write_dense, unsigned char*
   a.Mp = c->Mpmax; a.Np = c->Np; a.batch = B; a.R = R;
   a.fix_group_block = (full_rows || (c->flags & XIVO_HIP_FLAG_FIX_GROUP_BLOCK)) ? 1 : 0;
   a.rows_instate = c->rows_instate;
+  a.tune_R = c->tune.R;   // (tuning table: filter b's R in place of R - also when ensure_dense stacks again from restack_args())
   a.ell = c->ell; a.emit_ell = 1; a.write_dense = write_dense;
   // as-coded stacking of an online-calibration build on the sparse pipeline: compressed rows + the leading dense block
   // (full_rows - the whole-row stackings of the gate / RANSAC - stay dense rows)
@@ -197,6 +199,7 @@ int xivo_hip_get_jacobians(xivo_hip_ctx* c, int b0, int nb, double* J, double* i
 int xivo_hip_set_calib(xivo_hip_ctx* c, const xivo_calib_layout* layout) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
   if (!c || !c->have_layout) return XIVO_HIP_ERR_INVALID;
+  if (layout && c->tune.configured()) return XIVO_HIP_ERR_UNSUPPORTED;   // the tuning table has no calibration form
   if (!layout) { c->calib_on = false; c->calib_motion = false; c->cl = xivo_calib_layout{-1, -1, 0, 0}; return XIVO_HIP_OK; }
   const xivo_calib_layout& l = *layout;
   const int N = c->N;

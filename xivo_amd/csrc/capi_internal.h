@@ -19,6 +19,7 @@
 //   capi_lcmap.hip      loop closure: the resident landmark map, its add / close calls, load / read-out, counters; inside the
 //                       device life cycle: the keys beside the track block and the book, the resident add / close calls
 //   capi_trajsim.hip    trajectory producer: the simulated IMU records and ground-truth poses of a frame, the ground-truth log
+//   capi_tune.hip       tuning table: per-filter R, MH_thresh, var_xyz, Qimu, Qmodel and who reads them
 // Host code only (no kernels). Nothing here is exported from the library: the shared functions live in xivo_hip::capi, each
 // defined once, in the file named next to its declaration, and are hidden (the declarations below carry the visibility).
 //
@@ -320,6 +321,15 @@ struct LcLife {
   bool configured() const { return feat_key != nullptr; }
 };
 
+// tuning table (xivo_hip_tune_*, capi_tune.hip): one array [Bmax] per field, all five or none; up: the page-locked staging of
+// a set call. While configured() the in-state gate, the stacking, propagation and life_end are handed the arrays and read
+// filter b's entry in place of their scalar arguments
+struct TuneTable {
+  double *R = nullptr, *thresh = nullptr, *var = nullptr, *Qimu = nullptr, *Qmodel = nullptr;
+  PinnedUpload up;
+  bool configured() const { return R != nullptr; }
+};
+
 }  // namespace xivo_hip::capi
 
 struct xivo_hip_ctx {
@@ -402,6 +412,7 @@ struct xivo_hip_ctx {
   xivo_hip::capi::InnovLog innov;
   xivo_hip::capi::LcMap lcmap;
   xivo_hip::capi::LcLife lclife;
+  xivo_hip::capi::TuneTable tune;
   // "a device life cycle exists" (whichever: the book and the track block are its)
   bool life_cycle_configured() const { return life.configured() || plife.configured(); }
 };

@@ -284,6 +284,7 @@ int xivo_hip_life_end(xivo_hip_ctx* c, int B) {
   const xivo_life_opts& o = c->life.opts;
   a.min_new_features = o.min_new_features; a.min_depth = o.min_depth; a.max_depth = o.max_depth;
   for (int i = 0; i < 3; ++i) a.var_xyz[i] = o.var_xyz[i];
+  a.tune_var = c->tune.var;   // (tuning table: filter b's variances in place of var_xyz)
   a.fx = c->cam.fx; a.fy = c->cam.fy; a.cx = c->cam.cx; a.cy = c->cam.cy;
   track_block_close_frame(c);
   StageTimer st(c, ST_OTHER, 0.0, "life_end_kernel");

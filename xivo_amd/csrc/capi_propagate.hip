@@ -44,6 +44,10 @@ void prop_args(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_imu_in* dI
                double* dPhi, double* dPmm, const xivo_prop_opts* o, PropStateArgs& a) {
   a = PropStateArgs{};
   a.poses = c->poses + b0; a.imu = dImu; a.n_imu = n_imu; a.Qimu = dQi; a.Qmodel = dQm;
+  if (c->tune.configured()) {   // tuning table: the entries of filters [b0, b0 + nb) in place of the call's pair
+    a.Qimu = c->tune.Qimu + (size_t)b0 * 144; a.strideQimu = 144;
+    a.Qmodel = c->tune.Qmodel + (size_t)b0 * 529; a.strideQmodel = 529;
+  }
   a.g[0] = o->g[0]; a.g[1] = o->g[1]; a.g[2] = o->g[2]; a.method = o->method; a.stepsize = o->stepsize;
   c->P.from(b0).to(a.P, a.strideP, a.ldp); a.Phi_out = dPhi; a.Pmm_out = dPmm; a.batch = nb;
   if (o->control_stepsize) {
@@ -161,6 +165,9 @@ int xivo_hip_propagate(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_im
 int xivo_hip_propagate_calib(xivo_hip_ctx* c, int b0, int nb, int n_imu, const xivo_imu_in* imu, const xivo_prop_opts* o,
                              const double* Qmodel) {
   if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  // a tuning table: this call takes one Qimu / Qmodel for its range and must not apply it silently (such a context has no
+  // calibration layout either, which the check below would refuse as invalid)
+  if (c && c->tune.configured()) return XIVO_HIP_ERR_UNSUPPORTED;
   if (bad_range(c, b0, nb) || !c->have_layout || !c->poses || !imu || !o || !Qmodel || n_imu <= 0 || !c->calib_motion || !c->calib)
     return XIVO_HIP_ERR_INVALID;
   const int nm = c->cl.Cg >= 0 ? c->cl.Cg + 15 : c->cl.td + 1;

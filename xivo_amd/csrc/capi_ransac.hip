@@ -22,6 +22,7 @@ int xivo_hip_one_point_ransac(xivo_hip_ctx* c, int B, double R, double ransac_th
   if (!c || !c->have_layout || B <= 0 || B > c->Bmax || c->F <= 0 || !c->mask || !c->poses) return XIVO_HIP_ERR_INVALID;
   if (c->lay.n_groups > 64) return XIVO_HIP_ERR_UNSUPPORTED;
   if (bad_gate_params({R, ransac_thresh, 1.0, 0}) || ransac_chi2 != ransac_chi2) return XIVO_HIP_ERR_INVALID;
+  if (c->tune.configured()) return XIVO_HIP_ERR_UNSUPPORTED;   // tuning table: one parameter set for all filters is not applied silently
   const size_t Bm = c->Bmax, ng = c->lay.n_groups;
   // online-calibration builds: the calibration state is backed up / restored with X_ (imu_.BackupState, Camera::BackupState,
   // src/estimator.cpp:1421-1427), the partial update stacks the whole rows J() as dense rows, AbsorbError retracts td / Cg / Ca /

@@ -652,6 +652,7 @@ int xivo_hip_update_dense_gated(xivo_hip_ctx* c, int B, int F, double R, double 
   if (!c || B <= 0 || B > c->Bmax || c->rows.rows_padded() <= 0 || F <= 0 || 2 * F > c->rows.rows()) return XIVO_HIP_ERR_INVALID;
   const UpdateGate gate{F, {R, mh_thresh, mh_mult, min_inliers}};
   if (bad_gate_params(gate.gp)) return XIVO_HIP_ERR_INVALID;
+  if (c->tune.configured()) return XIVO_HIP_ERR_UNSUPPORTED;   // tuning table: one parameter set for all filters is not applied silently
   int rc = ensure_gate_buffers(c, F);
   if (rc) return rc;
   // Estimator::OutlierRejection only gates when F > min_required_inliers_ (src/manager.cpp:635)
@@ -828,6 +829,7 @@ int xivo_hip_mh_gate_dense(xivo_hip_ctx* c, int B, int F, double R, double mh_th
   GateDenseArgs a{};
   a.gp = {R, mh_thresh, mh_mult, min_inliers};
   if (bad_gate_params(a.gp)) return XIVO_HIP_ERR_INVALID;
+  if (c->tune.configured()) return XIVO_HIP_ERR_UNSUPPORTED;   // tuning table: one parameter set for all filters is not applied silently
   int rc = ensure_gate_buffers(c, F);
   if (rc) return rc;
   rc = ensure_dense(c);

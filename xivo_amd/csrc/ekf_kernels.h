@@ -149,6 +149,7 @@ struct LifeArgs {
   // life_end only: the update's inlier mask (row stride mask_ld) and status, the admission options, the camera
   const unsigned char* mask; int mask_ld; const int* status;
   int min_new_features, invdepth; double min_depth, max_depth, var_xyz[3], fx, fy, cx, cy;
+  const double* tune_var;   // tuning table: [batch][3], filter b's variances in place of var_xyz (null: var_xyz)
   // loop closure inside the life cycle (xivo_hip_lcmap_life_config; all null while it is off, and always in the pool life cycle):
   // keys - one per track, indexed as ids; feat_key [batch][slot_ld]; what the begin kernel leaves for the add and the close call:
   // lc_recs [batch][slot_ld] / lc_n_recs [batch] the add records, lc_tracked [batch][slot_ld], lc_rm [batch][2 + slot_ld +
@@ -236,6 +237,7 @@ struct StackArgs {
   // online-calibration builds on the sparse pipeline: [batch] dense blocks [Mp x lead_k] (leading dimension Mp) that take the
   // calibration columns of every row pair; null: those builds stack dense rows
   double* lead; long strideLead; int lead_k;
+  const double* tune_R;   // tuning table: [batch], filter b's R in place of R (null: R)
 };
 int launch_stack(const StackArgs& a, hipStream_t s);
 
@@ -385,6 +387,7 @@ struct GateArgs {
   SceneBuffers sb; xivo_layout lay;
   const double* P; long strideP; int ldp;
   GateParams gp; int batch; int use_gating;
+  const double* tune_R; const double* tune_thresh;   // tuning table: [batch] each, filter b's R / thresh in place of gp's (both null: gp's)
 };
 int launch_gate_sparse(const GateArgs& a, hipStream_t s);
 // the launch choices below are made here only: the launch and xivo_hip_selftest_glevel_launch (capi_glevel.hip) call the same
@@ -499,6 +502,8 @@ struct PropStateArgs {
   // step-size-controlled Dormand-Prince (princedormand.cpp:26-60; default-build kernel only): the per-filter step carried between
   // samples and calls (the reference's function-local static h), null = fixed steps
   double* pd_h; double pd_tol, pd_min_scale, pd_max_scale;
+  // tuning table: Qimu / Qmodel of filter b start b * strideQimu / b * strideQmodel doubles in (144 / 529); 0: one pair for all
+  long strideQimu, strideQmodel;
 };
 int launch_propagate_state(const PropStateArgs& a, hipStream_t s);
 int launch_propagate_state_calib(const PropStateArgs& a, hipStream_t s);

@@ -103,17 +103,20 @@ __global__ __launch_bounds__(1024) void gate_sparse_kernel(GateArgs a) {
   const bool gating = a.use_gating && present > a.gp.min_inliers;
   double th = 1.0;
   if (gating) {
+    // tuning table: the filter's own R and threshold, a load every lane shares; the same operands of the same expressions
+    GateParams gp = a.gp;
+    if (a.tune_R) { gp.R = a.tune_R[filt]; gp.thresh = a.tune_thresh[filt]; }
     for (int f = wave; f < sb.F; f += nw) {
       xivo_feat_in ft;                      // only the slots are read by feature_chi2 / jcol
       ft.sind = s_slot[2 * f]; ft.ref_sind = s_slot[2 * f + 1];
       if (ft.sind < 0) { if (lane == 0) sdist[f] = __builtin_inf(); continue; }
       const double* J = sb.J + ((long)filt * sb.Fmax + f) * 42;
       const double* inn = sb.finn + ((long)filt * sb.Fmax + f) * 2;
-      const double d = sb.Jc ? feature_chi2_wide(P, a.ldp, a.lay, sb.cl, ft, J, sb.Jc + ((long)filt * sb.Fmax + f) * 44, inn, a.gp.R, lane, s_pss, s_scr)
-                             : feature_chi2_lds(P, a.ldp, a.lay, ft, J, inn, a.gp.R, lane, s_scr);
+      const double d = sb.Jc ? feature_chi2_wide(P, a.ldp, a.lay, sb.cl, ft, J, sb.Jc + ((long)filt * sb.Fmax + f) * 44, inn, gp.R, lane, s_pss, s_scr)
+                             : feature_chi2_lds(P, a.ldp, a.lay, ft, J, inn, gp.R, lane, s_scr);
       if (lane == 0) sdist[f] = d;
     }
-    th = gate_threshold(sdist, sb.F, wave, lane, [&] { return relax_threshold(sdist, sb.F, a.gp, lane, present); });
+    th = gate_threshold(sdist, sb.F, wave, lane, [&] { return relax_threshold(sdist, sb.F, gp, lane, present); });
   } else {
     // (not gating: present entries carry 0, absent ones +inf - any positive threshold keeps exactly the present ones; every
     //  thread reads back below what it wrote here)

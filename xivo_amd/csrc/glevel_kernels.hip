@@ -197,6 +197,7 @@ __global__ __launch_bounds__(256) void stack_kernel(StackArgs a) {
   double* dR = a.mb.diagR + (long)filt * a.mb.strideR;
   for (int m = tid; m < a.Mp; m += 256) { inn[m] = 0.0; dR[m] = 1.0; }
   __syncthreads();
+  const double R = a.tune_R ? a.tune_R[filt] : a.R;   // (tuning table: the filter's own)
   for (int f = tid; f < sb.F; f += 256) {
     if (!sb.mask[(long)filt * sb.Fmax + f]) continue;
     const xivo_feat_in& ft = sb.feats[(long)filt * sb.Fmax + f];
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(256) void stack_kernel(StackArgs a) {
       }
     }
     inn[2 * f] = fi[0]; inn[2 * f + 1] = fi[1];      // update.cpp:136
-    dR[2 * f] = a.R; dR[2 * f + 1] = a.R;            // update.cpp:137
+    dR[2 * f] = R; dR[2 * f + 1] = R;                // update.cpp:137
   }
   if (tid == 0 && a.rows_instate) a.rows_instate[filt] = 2 * sb.F;
   if (!a.emit_ell) return;

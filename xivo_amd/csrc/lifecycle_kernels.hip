@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void life_end_kernel(LifeArgs a) {
         const double* m = a.meas + 3 * (long)(k0 + s.pick[q]);
         double x[3] = {0.0, 0.0, 0.0};
         if (tid == 0) life_init_feature(a, m, x);
-        edit_add_feature(P, a.ldp, a.Np, a.lay, feats[j], x, m, j, g, tid % 4 == 0 && tid < 9 ? a.var_xyz[tid / 4] : 0.0, tid);
+        edit_add_feature(P, a.ldp, a.Np, a.lay, feats[j], x, m, j, g, tid % 4 == 0 && tid < 9 ? (a.tune_var ? a.tune_var[3 * (long)b + tid / 4] : a.var_xyz[tid / 4]) : 0.0, tid);
       }
       if (tid == 0) {
         for (int q = 0; q < n_new; ++q) { s.k.fid[s.free_slots[q]] = s.k.ids[s.pick[q]]; }

@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256) void propagate_state_calib_kernel(PropStateArg
   double* Phi = PhiA;
   double* PhiN = PhiB;
   for (int e = lane; e < 144; e += NT) {
-    const double q = a.Qimu[e];
+    const double q = a.Qimu[filt * a.strideQimu + e];
     Q[e] = q;
     const int r = e % 12;     // rows of G Q that do not depend on the state: Wsb = -Q[0:3,:], bg = Q[6:9,:], ba = Q[9:12,:]
     if (r < 3) GQc[e] = -q;
@@ -528,7 +528,7 @@ __global__ __launch_bounds__(256) void propagate_state_calib_kernel(PropStateArg
         __syncthreads();
       } else if (a.stepsize < 0) break;
     }
-    for (int e = lane; e < NN; e += NT) Pmm[e] += a.Qmodel[e];   // estimator.cpp:590, per Propagate
+    for (int e = lane; e < NN; e += NT) Pmm[e] += a.Qmodel[filt * a.strideQmodel + e];   // estimator.cpp:590, per Propagate
     __syncthreads();
   }
   for (int e = lane; e < NN; e += NT) {
@@ -606,7 +606,7 @@ __global__ __launch_bounds__(64) void propagate_state_wave_kernel(PropStateArgs 
   }
   if (lane == 0) zero[0] = 0.0;
   for (int e = lane; e < 144; e += 64) {
-    const double q = a.Qimu[e];
+    const double q = a.Qimu[filt * a.strideQimu + e];
     Q[e] = q;
     const int r = e % 12;      // rows of G Q that do not depend on the state: Wsb rows = -Q[0:3,:], bg / ba rows = Q[6:12,:]
     if (r < 3) GQc[e] = -q;
@@ -894,7 +894,7 @@ __global__ __launch_bounds__(64) void propagate_state_wave_kernel(PropStateArgs 
       } else if (a.stepsize < 0) break;
     }
 #pragma unroll
-    for (int m = 0; m < EL; ++m) Pmm[m] += a.Qmodel[min(lane + 64 * m, NN - 1)];   // P_mm += Qmodel (estimator.cpp:590), per Propagate
+    for (int m = 0; m < EL; ++m) Pmm[m] += a.Qmodel[filt * a.strideQmodel + min(lane + 64 * m, NN - 1)];   // P_mm += Qmodel (estimator.cpp:590), per Propagate
   }
   __syncthreads();
   if (ctl && lane == 0) a.pd_h[filt] = hs;

@@ -134,6 +134,10 @@ life_opts_dtype = np.dtype([("tracks_max", "i4"), ("min_new_features", "i4"), ("
 life_stats_dtype = np.dtype([("updates", "i8"), ("rejected", "i8"), ("dropped", "i8"), ("admitted", "i8"), ("groups_added", "i8"),
                              ("not_spd", "i8")])
 assert life_opts_dtype.itemsize == 48 and life_stats_dtype.itemsize == 48
+# tuning table (include/xivo_hip.h): xivo_tune_in, one filter's R, MH_thresh, var_xyz, Qimu 12 x 12 and Qmodel 23 x 23 (the two
+# matrices column-major, as prop_opts_dtype holds them)
+tune_dtype = np.dtype([("R", "f8"), ("mh_thresh", "f8"), ("var_xyz", "f8", 3), ("Qimu", "f8", 144), ("Qmodel", "f8", 529)])
+assert tune_dtype.itemsize == 5424
 # device pool life cycle (include/xivo_hip.h): xivo_pool_life_opts, xivo_pool_life_stats
 pool_life_opts_dtype = np.dtype([("struct_size", "i4"), ("tracks_max", "i4"), ("max_group_lifetime", "i4"), ("adaptive_z", "i4"),
                                  ("initial_z", "f8"), ("std_xyz", "f8", 3)])
@@ -358,6 +362,9 @@ _SIGS = {
     "xivo_hip_trajsim_get_gt": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_trajsim_count": [C.c_void_p],
     "xivo_hip_trajsim_reset": [C.c_void_p],
+    "xivo_hip_tune_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_tune_set": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_tune_get": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
 }
 HOST_P_RESIDENT, HOST_KEEP_P = 1, 2
 
@@ -450,6 +457,15 @@ def prop_options(Qimu, Qmodel, g, method="RK4", stepsize=0.002, pd_control=None)
         o["tolerance"] = pd_control.get("tolerance", 1e-3); o["attempts"] = pd_control.get("attempts", 12)
         o["min_scale_factor"] = pd_control.get("min_scale_factor", 0.125); o["max_scale_factor"] = pd_control.get("max_scale_factor", 4.0)
     return o
+
+
+def tune_entry(R, mh_thresh, var_xyz, Qimu, Qmodel):
+    """one xivo_tune_in record: Qimu 12x12, Qmodel 23x23 (numpy row-major, as prop_options takes them)"""
+    e = np.zeros((), dtype=tune_dtype)
+    e["R"], e["mh_thresh"], e["var_xyz"] = R, mh_thresh, np.asarray(var_xyz, dtype=np.float64)
+    e["Qimu"] = np.asarray(Qimu, dtype=np.float64).T.reshape(-1)
+    e["Qmodel"] = np.asarray(Qmodel, dtype=np.float64).T.reshape(-1)
+    return e
 
 
 def _ptr(a):
@@ -1181,6 +1197,28 @@ class Context:
         """life_begin on the tracks the last pcw_tracks(B) left on the device (asynchronous, no upload)"""
         self._check(self.lib.xivo_hip_life_begin_tracks(self.h, self.batch if B is None else int(B), int(F)))
         self.F = int(F)
+
+    # ---- tuning table (xivo_hip_tune_*)
+    def tune_config(self, entry=None):
+        """every filter's R, MH_thresh, var_xyz, Qimu and Qmodel from a resident table whose rows all start as `entry` (one
+        tune_dtype record; tune_entry builds one); None releases the table and brings the calls' scalar arguments back"""
+        if entry is None:
+            self._check(self.lib.xivo_hip_tune_config(self.h, None))
+            return
+        e = np.ascontiguousarray(entry, dtype=tune_dtype).reshape(1)
+        self._check(self.lib.xivo_hip_tune_config(self.h, _ptr(e)))
+
+    def tune_set(self, table, b0=0):
+        """rows [b0, b0 + len(table)) <- table (tune_dtype); staged and enqueued, all rows or none"""
+        t = np.ascontiguousarray(table, dtype=tune_dtype).reshape(-1)
+        self._check(self.lib.xivo_hip_tune_set(self.h, int(b0), t.shape[0], _ptr(t)))
+
+    def tune_get(self, b0=0, nb=None):
+        """-> rows [b0, b0 + nb) as a tune_dtype array; one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        t = np.zeros(nb, dtype=tune_dtype)
+        self._check(self.lib.xivo_hip_tune_get(self.h, int(b0), nb, _ptr(t)))
+        return t
 
     # ---- point-cloud world on the device (xivo_hip_pcw_*)
     def pcw_config(self, npts, fx=0.0, fy=0.0, cx=0.0, cy=0.0, imw=0.0, imh=0.0):

@@ -495,10 +495,41 @@ class HipBackend:
         """allocate the device-resident slot book and track staging (xivo_hip_life_config). The new feature's variances are
         computed here as the host life cycle computes them (std * std, src/estimator.cpp:349-353)."""
         c = self.cfg
+        self.ctx.life_config(c.tracks_max, min_depth=c.min_depth, max_depth=c.max_depth, min_new_features=c.min_new_features,
+                             var_xyz=self.life_var_xyz(c))
+
+    @staticmethod
+    def life_var_xyz(c):
+        """the variances a new feature of the device life cycle starts with under configuration c"""
         fl = c.focal_length()
         std = np.array([c.initial_std_x / fl, c.initial_std_y / fl, c.initial_std_z])
-        self.ctx.life_config(c.tracks_max, min_depth=c.min_depth, max_depth=c.max_depth, min_new_features=c.min_new_features,
-                             var_xyz=std * std)
+        return std * std
+
+    @staticmethod
+    def tuning_entry(c):
+        """one row of the tuning table (lib.tune_dtype) that stands for configuration c: the numbers the calls of this class
+        pass as scalars - visual_meas_std ** 2 and MH_thresh (update), Qimu_matrix() / Qmodel_matrix() (propagate), the
+        variances of enable_device_lifecycle - computed by the same expressions, so that a tuned filter and a plain run of c
+        start from the same bits"""
+        return L.tune_entry(c.visual_meas_std ** 2, c.MH_thresh, HipBackend.life_var_xyz(c), c.Qimu_matrix(), c.Qmodel_matrix())
+
+    def enable_tuning(self, table):
+        """per-filter noise parameters (xivo_hip_tune_config / _set): table [B] lib.tune_dtype, row b filter b's. update(),
+        propagate(), propagate_resident() and life_end() then read the table on the device; the scalars they pass from cfg are
+        still validated and otherwise not read. None: back to cfg's values. Refused with use_1pt_RANSAC (one threshold pair for
+        every filter)."""
+        if table is None:
+            self.ctx.tune_config(None)
+            self.tune = None
+            return
+        table = np.ascontiguousarray(table, dtype=L.tune_dtype)
+        if table.shape != (self.B,):
+            raise ValueError("enable_tuning takes one row per filter: a lib.tune_dtype array of shape [%d]" % self.B)
+        if self.cfg.use_1pt_RANSAC:
+            raise ValueError("enable_tuning with use_1pt_RANSAC is not supported: OnePointRANSAC takes one parameter set")
+        self.ctx.tune_config(table[0])
+        self.ctx.tune_set(table)
+        self.tune = table
 
     def new_track_std(self):
         """the stds a new pool entry starts with: a new track is never triangulated yet, so with triangulation on they are the
