@@ -316,10 +316,19 @@ static int stream_capacity(int nb, bool whitened) {
   return nb <= 16 ? 16 : (nb <= 22 ? 22 : 24);
 }
 
-template <int NBM, int TF>
+// XIVO_HIP_SOLVE_GENERIC (A/B, and the bit-identity test of the two instantiations): the general instantiation of the solve
+// kernel - run-time block-row count - also where the factor fills every block row the kernel was compiled for
+static bool solve_generic_forced() { static const bool on = getenv("XIVO_HIP_SOLVE_GENERIC") != nullptr; return on; }
+
+template <int NBM, int TF, bool FULL = false>
 int launch_trsm_lds_tf(const TrsmArgs& g_in, hipStream_t stream) {
   TrsmArgs g = g_in;
   const int nb = g.Mp / 16;
+  // the full-shape instantiation (compile-time block-row count: straight-line substitutions) of the metric point's kernel and of
+  // its eleven-row sibling; every other shape and variant runs the general form
+  if constexpr (!FULL && TF == 4 && (NBM == 10 || NBM == 11)) {
+    if (nb == NBM && !solve_generic_forced()) return launch_trsm_lds_tf<NBM, TF, true>(g_in, stream);
+  }
   const int chunks = (g.Np + 255) / 256;
   const int grid = ((g.batch + 7) / 8) * 8 * chunks;
   size_t lds = (size_t)nb * (nb + 1) / 2 * 16 * 17 * sizeof(double);
@@ -330,11 +339,11 @@ int launch_trsm_lds_tf(const TrsmArgs& g_in, hipStream_t stream) {
   }
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&trsm_lds_f64_kernel<NBM, TF>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&trsm_lds_f64_kernel<NBM, TF, 16, 1, FULL>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set = true;
   }
-  hipLaunchKernelGGL((trsm_lds_f64_kernel<NBM, TF>), dim3(grid), dim3(1024), lds, stream, g);
+  hipLaunchKernelGGL((trsm_lds_f64_kernel<NBM, TF, 16, 1, FULL>), dim3(grid), dim3(1024), lds, stream, g);
   return (int)hipGetLastError();
 }
 template <int NBM>

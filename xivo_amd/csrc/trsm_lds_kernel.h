@@ -196,10 +196,11 @@ __device__ __forceinline__ void sym_tiles_from_regs(const d4 (&X)[NBM], const d4
 // sum of the same products, of entry (a, b) or (b, a) of V^T Y (they differ by the antisymmetric term that the
 // lower-triangle + mirror evaluation drops; the diagonal tile is V_w^T Y_w entry (a, b)).
 // All NWV waves of the workgroup must call it (barriers); `sL` = the whole 160 KB of LDS.
-template <int NBM, int NWV>
+template <int NBM, int NWV, bool FULL = false>
 __device__ __forceinline__ void whitened_tiles_from_stash(d4 (&X)[NBM], double* sL, const double* __restrict__ Src, int ldsrc,
-                                                          double* __restrict__ Pio, int ldp, int nb, int nwl, int jbp, bool live,
+                                                          double* __restrict__ Pio, int ldp, int nb_rt, int nwl, int jbp, bool live,
                                                           int w, int wave, int lane) {
+  const int nb = FULL ? NBM : nb_rt;              // (FULL: the tile chains are 4 NBM MFMAs in a row, no test between them)
   const int li = lane & 15, lg = lane >> 4;
   const int nph = (nwl + jbp - 1) / jbp;
   const int bufsz = jbp * nb * 256;                // doubles per LDS buffer (two of them)
@@ -274,6 +275,12 @@ __device__ __forceinline__ void whitened_tiles_from_stash(d4 (&X)[NBM], double* 
       if (fetch) { asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3])); issue(p + 1); fetch = false; }
       if (todo) load_m(jb0 + __builtin_ctz(todo), nxt);
       const double* Bop = buf + jl * nb * 256 + lane;
+      // FULL: the two orientations below read the same 4 NBM addresses in straight-line code, and the compiler would merge the
+      // reads in front of the branch - 8 NBM VGPRs at once, spilled. The second one's lane offset is hidden from it. (Seen with
+      // hipcc 7.2; scripts/resource_usage.sh chol_trsm.hip shows at once whether a later compiler still needs or honours it.)
+      int lane2 = lane;
+      if (FULL) asm volatile("" : "+v"(lane2));
+      const double* Bop2 = buf + jl * nb * 256 + lane2;
       if (jb < w) {
 #pragma unroll
         for (int mb = 0; mb < NBM; ++mb) {
@@ -287,7 +294,7 @@ __device__ __forceinline__ void whitened_tiles_from_stash(d4 (&X)[NBM], double* 
         for (int mb = 0; mb < NBM; ++mb) {
           if (mb < nb) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc = mfma(X[mb][r], Bop[(mb * 4 + r) * 64], acc);
+            for (int r = 0; r < 4; ++r) acc = mfma(X[mb][r], Bop2[(mb * 4 + r) * 64], acc);
           }
         }
       }
@@ -325,11 +332,17 @@ __device__ __forceinline__ void whitened_tiles_from_stash(d4 (&X)[NBM], double* 
 // workgroup per CU (BASELINE config 2: N = 150 -> ten waves, seven block rows: 76 KB of LDS, 96 VGPRs): the memory phases
 // of one filter (right-hand sides in, covariance tiles in and out) then run under the matrix phases of another - the
 // overlap a single workgroup cannot have, because one filter's working set fills the CU at the metric point.
-template <int NBM, int TF, int NWV = 16, int MINB = 1>
+// FULL: the factor has all NBM block rows (Mp == 16 NBM). The block-row count is then a compile-time constant and the fully
+// unrolled loops below lose their `i < nb` tests: the forward substitution, the stash stores and the product's tile chains are
+// straight-line code whose LDS reads the scheduler requests ahead of the MFMAs that use them (with a run-time count every
+// update MFMA sat in a basic block of its own behind its read's round trip, a hazard nop and a branch). The general form serves
+// nb < NBM.
+template <int NBM, int TF, int NWV = 16, int MINB = 1, bool FULL = false>
 __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g) {
   constexpr int BLK = 16 * 17;
   constexpr int NT = 64 * NWV;
   static_assert(TF != 3, "TF == 3 (the round-2 expanded Joseph form) was removed in round 6");
+  static_assert(!FULL || (TF == 4 && NBM >= 8), "the full-shape form is that of the in-kernel product off the stash");
   // the whitened form needs the diagonal blocks L_kk next to their inverses: in slots of their own while the LDS has room (<= 10
   // block rows), else packed into the unused upper triangle + pad row of the inverse's slot (a few selects per read)
   constexpr bool T4 = TF == 4 || TF == 5;   // whitened Joseph form; TF == 5: its outputs V^T, Y^T for a product outside the kernel
@@ -351,7 +364,7 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
   if (filt >= g.batch) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lg = lane >> 4;
-  const int nb = g.Mp / 16;
+  const int nb = FULL ? NBM : g.Mp / 16;
   const double* __restrict__ LU = g.LU + (long)filt * g.strideLU;
   const double* __restrict__ invD = g.invD + (long)filt * g.strideInvD;
   const double* __restrict__ PHT = g.PHT + (long)filt * g.stridePHT;
@@ -393,6 +406,16 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
   constexpr int CPD = DIAG ? (NBM * 128 + NT - 1) / NT : 0;         // ... + diagonal blocks
   constexpr int CPB = 4;                                              // loads in flight per thread
   double* sD = sL + nblk * BLK;                                       // (upper triangle zeroed)
+  // the product off the stash (DREGS): inn rides along into LDS, behind the factor. dx = K inn reads it in the backward loop, and
+  // a global load there is waited for with vmcnt - behind the acknowledgements of the stash stores just issued (memory operations
+  // retire in order), which then drain under the whole loop: it has no other vector-memory operation. (The other variants read
+  // the stash back or store Y inside the loop and keep the global load: with the LDS read <10,5> spills 321 VGPRs - hipcc 7.2.)
+  // (DREGS is TF == 4, which the launchers pick only with !fwd_only: rInn is g.inn here, never the y of a forward-only call;
+  //  its room is the 160 KB every TF != 0 launch asks for - at most 143 616 + 1 408 B are in use in front of the product.)
+  constexpr bool INN_LDS = DREGS;
+  double* sInn = sL + (nblk + (DIAG ? nb : 0)) * BLK;
+  double innv = 0.0;
+  if (INN_LDS && tid < 16 * nb) innv = buf_ld(rInn, (unsigned)tid * 8u, 0u);
 #pragma unroll
   for (int u0 = 0; u0 < CPY + CPD; u0 += CPB) {
     d2 cv[CPB], cu[CPB];
@@ -434,16 +457,17 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
           // diagonal slot: inv(L_kk) in the lower triangle; packed: L_kk^T above it (the strictly lower part of L_kk read
           // transposed: the factorisation need not have mirrored it) and the diagonal of L_kk in the pad row
           if (PACK && i == k) { v[0] = r >= c ? v[0] : cu[q][0]; v[1] = r + 1 >= c ? v[1] : cu[q][1]; }
-          sL[t * BLK + r + 17 * c] = v[0];
-          sL[t * BLK + r + 1 + 17 * c] = v[1];
+          // off-diagonal blocks are stored NEGATED: every MFMA that reads one subtracts its product
+          sL[t * BLK + r + 17 * c] = i != k ? -v[0] : v[0];
+          sL[t * BLK + r + 1 + 17 * c] = i != k ? -v[1] : v[1];
         }
       } else if (u < CPY + CPD) {
         const int e = tid + NT * (u - CPY);
         if (e < nb * 128) {
           const int k = e >> 7, w = e & 127;
           const int r = (w & 7) * 2, c = w >> 3;
-          sD[k * BLK + r + 17 * c] = r >= c ? cv[q][0] : 0.0;
-          sD[k * BLK + r + 1 + 17 * c] = r + 1 >= c ? cv[q][1] : 0.0;
+          sD[k * BLK + r + 17 * c] = r >= c ? -cv[q][0] : -0.0;          // (-L_kk, as the residual consumes it)
+          sD[k * BLK + r + 1 + 17 * c] = r + 1 >= c ? -cv[q][1] : -0.0;
         }
       }
     }
@@ -455,6 +479,7 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
       sL[(k * (k + 1) / 2 + k) * BLK + 16 + 17 * c] = LU[(16 * k + c) + (long)(16 * k + c) * ld];
     }
   }
+  if (INN_LDS && tid < 16 * nb) sInn[tid] = innv;
   XTR(1);
   __syncthreads();
   XTR(2);
@@ -479,10 +504,13 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
         for (int i = k + 1; i < NBM; ++i) {
           if (i < nb) {
             const double a = sL[(i * (i + 1) / 2 + k) * BLK + li + 17 * (4 * s + lg)];
-            X[i] = mfma(-a, t[s], X[i]);
+            X[i] = mfma(a, t[s], X[i]);                      // (a = -L_ik)
           }
         }
       }
+      // (FULL: the whole loop is one basic block - a step's LDS reads are requested a few MFMAs ahead, but not those of the steps
+      //  behind it: that spills)
+      if (FULL) __builtin_amdgcn_sched_barrier(0);
     }
   }
   XTR(3);
@@ -540,11 +568,11 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
             const double a = Lk[kk > li ? li + 17 * kk : 16 + 17 * li];
             X[k] = mfma(kk >= li ? -a : 0.0, t[s2], X[k]);
           } else {
-            X[k] = mfma(-Lk[kk + 17 * li], t[s2], X[k]);
+            X[k] = mfma(Lk[kk + 17 * li], t[s2], X[k]);     // (sD holds -L_kk)
           }
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) part = fma(t[r], buf_ld(rInn, (unsigned)lg * 8u, (unsigned)(16 * k + 4 * r) * 8u), part);
+        for (int r = 0; r < 4; ++r) part = fma(t[r], INN_LDS ? sInn[16 * k + 4 * r + lg] : buf_ld(rInn, (unsigned)lg * 8u, (unsigned)(16 * k + 4 * r) * 8u), part);
       } else {
         X[k] = t;
       }
@@ -552,8 +580,8 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
       for (int s = 0; s < 4; ++s) {
 #pragma unroll
         for (int i = 0; i < k; ++i) {
-          const double a = sL[(k * (k + 1) / 2 + i) * BLK + (4 * s + lg) + 17 * li];   // (L_ki)^T
-          X[i] = mfma(-a, t[s], X[i]);
+          const double a = sL[(k * (k + 1) / 2 + i) * BLK + (4 * s + lg) + 17 * li];   // -(L_ki)^T
+          X[i] = mfma(a, t[s], X[i]);
         }
       }
       // TF == 4: V_k = W_k - D_k, the row block of V^T = (W - D)^T - the register operand of the covariance product below
@@ -618,7 +646,7 @@ __global__ __launch_bounds__(64 * NWV, MINB) void trsm_lds_f64_kernel(TrsmArgs g
     double* Pio = g.T + (long)filt * g.strideT;
     if constexpr (KEEPW) sym_tiles_from_regs<NBM, true, true, true, NWV>(X, Wk, sL, nullptr, 0, Pio, g.ldt, Pio, g.ldt, nb, g.Np / 16, g.t_jbp,
                                                                  live, c0 >> 4, wave, lane);
-    else whitened_tiles_from_stash<NBM, NWV>(X, sL, g.K + (long)filt * g.strideK, g.ldk, Pio, g.ldt, nb, g.Np / 16, g.t_jbp, live, c0 >> 4, wave, lane);
+    else whitened_tiles_from_stash<NBM, NWV, FULL>(X, sL, g.K + (long)filt * g.strideK, g.ldk, Pio, g.ldt, nb, g.Np / 16, g.t_jbp, live, c0 >> 4, wave, lane);
     return;
   }
   if (TF == 2) {
