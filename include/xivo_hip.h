@@ -1187,6 +1187,49 @@ int xivo_hip_life_begin_tracks(xivo_hip_ctx* ctx, int B, int F);
  * read -1 / 0. Any may be NULL. Synchronises. */
 int xivo_hip_pcw_get_tracks(xivo_hip_ctx* ctx, int b0, int nb, int* cnt, long long* ids, double* meas);
 
+/* ---- track faults of the point-cloud world's producer (opt-in) ---------------------------------------------------------------
+ * Random track loss, gross outliers (one frame, or sticky: a bias the track keeps until it ends) and heavy-tailed noise, drawn
+ * on the device from two more counters of the pixel noise's generator, with a ground-truth flag byte beside every track and a
+ * device-side score of the gate's decisions against the flags. The rules, the two draws and the flag bits are specified in
+ * xivo_amd/csrc/pcw_device.h ("Track faults"); pcw.fault_draw and BatchPCW.generate(faults=...) restate them for host code bit
+ * for bit. Off (never configured, or released) every call computes what it computes without this section. */
+typedef struct {
+  int struct_size;                        /* sizeof(xivo_pcw_fault_opts) */
+  int sticky;                             /* 0: an outlier lasts one frame; 1: its offset stays on the track until the track ends */
+  double p_drop, p_outlier, p_tail;       /* per visible point and frame, each in [0, 1], their sum <= 1 */
+  double outlier_min_px, outlier_max_px;  /* each component of an outlier's offset is +-[min, max] px, 0 <= min <= max */
+  double tail_scale;                      /* a tail event multiplies noise_px_std by this (>= 1) */
+} xivo_pcw_fault_opts;
+/* per filter, summed over the frames since xivo_hip_pcw_fault_config. The producer's: tracks written, visible points dropped,
+ * outlier events, tail events, tracks that carried an earlier outlier's bias. The score's, over the in-state features whose
+ * track the frame held: faulty (flag & 5) or nominal against rejected (inlier mask 0) or kept. */
+typedef struct {
+  long long tracks, dropped, outlier_events, tail_events, biased;
+  long long outlier_rejected, outlier_kept, nominal_rejected, nominal_kept;
+} xivo_pcw_fault_stats;
+/* Turns the fault path of xivo_hip_pcw_tracks / _tracks_resident on (opts) or off (NULL: releases). Allocates the resident bias
+ * [batch_max][npts][2], the flag row [batch_max][tracks_max] and the counters [batch_max], all zero. XIVO_HIP_ERR_INVALID,
+ * nothing changed: no worlds configured; a frame open between a begin and its end; a wrong struct_size; a probability outside
+ * [0, 1] or their sum (p_drop + p_outlier) + p_tail > 1; outlier_min_px < 0 or > outlier_max_px; tail_scale < 1; any value that
+ * is not finite; sticky outside {0, 1}. xivo_hip_pcw_set_world zeroes the bias of the filters it sets; whatever releases the
+ * worlds releases these with them. Synchronises. */
+int xivo_hip_pcw_fault_config(xivo_hip_ctx* ctx, const xivo_pcw_fault_opts* opts);
+/* W > 0: the filter word of the pixel-noise and fault counters is b % W from the next frame call on, so that filters w, w + W,
+ * w + 2 W, ... draw the same words (T tunings over W worlds); 0: every filter its own stream. The trajectory producer's IMU
+ * stream is not touched. XIVO_HIP_ERR_INVALID: no worlds configured, W < 0, a frame open. Does not synchronise. */
+int xivo_hip_pcw_stream_share(xivo_hip_ctx* ctx, int W);
+/* Between the update and the life_end / pool_life_end of a frame of B filters that was begun on the producer's tracks
+ * (xivo_hip_life_begin_tracks / xivo_hip_pool_life_begin_tracks): for every feature slot of the book that holds an id, the
+ * frame's track with that id (the last one on a repeated id), its flag byte and the update's inlier mask entry add one to one
+ * of the four cells of the filter's counters. Enqueues only. XIVO_HIP_ERR_INVALID, nothing changed: faults off; no frame of B
+ * filters open; the open frame's tracks did not come from the producer; called twice in a frame; no update has left a mask. */
+int xivo_hip_pcw_fault_score(xivo_hip_ctx* ctx, int B);
+/* the counters of filters [b0, b0 + nb). Synchronises. */
+int xivo_hip_pcw_fault_get_stats(xivo_hip_ctx* ctx, int b0, int nb, xivo_pcw_fault_stats* out);
+/* flags [nb][tracks_max]: the flag byte of every track the last frame call left, parallel to xivo_hip_pcw_get_tracks' ids (0
+ * behind a filter's count). XIVO_HIP_ERR_INVALID as xivo_hip_pcw_get_tracks, and with faults off. Synchronises. */
+int xivo_hip_pcw_fault_get_flags(xivo_hip_ctx* ctx, int b0, int nb, unsigned char* flags);
+
 /* ---- trajectory producer: the simulator's IMU records and ground-truth poses produced on the device (opt-in) --------------
  * What BatchTrajectorySim (xivo_amd/pcw.py) and ImuFeeder.imu (xivo_amd/sequence.py) compute on the host between two camera
  * frames: every filter follows a closed-form curve (Lissajous or trefoil, at its own rate) with one orientation profile for

@@ -20,6 +20,9 @@ def main():
     ap.add_argument("--frames", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--noise", type=float, default=1.0, help="pixel noise std (0: the generator is skipped)")
+    ap.add_argument("--faults", action="store_true",
+                    help="the fault instance of the kernel at the tests' probabilities: p_drop = p_outlier = p_tail = 0.2, sticky "
+                         "offsets of 20 - 60 px, tail_scale 4")
     a = ap.parse_args()
     B = a.filters
     cfg = sequence.SequenceConfig(lifecycle="device", track_source="device", npts=a.npts,
@@ -35,6 +38,8 @@ def main():
     be = sequence.HipBackend(cfg, B, poses, np.repeat(cfg.P_init()[None], B, axis=0))
     try:
         be.set_world(world.Xs)
+        if a.faults:
+            be.set_track_faults(dict(sticky=1, p_drop=0.2, p_outlier=0.2, p_tail=0.2, outlier_min_px=20.0, outlier_max_px=60.0, tail_scale=4.0))
         gsc = [sequence.camera_poses(*sim.gsb(0.04 * k), Rbc, cfg.Tbc)[2] for k in range(a.warmup + a.frames)]
         for k in range(a.warmup):
             be.make_tracks(gsc[k], a.noise, 0, k)
@@ -46,7 +51,7 @@ def main():
         cnt = be.ctx.pcw_get_tracks(cfg.tracks_max, 0, B)[0]
         # per filter and frame: 24 B per point and 8 B per id in, 32 B per track out (the ids that change are not counted)
         traffic = B * (a.npts * 32.0 + float(cnt.mean()) * 32.0)
-        print(json.dumps({"filters": B, "npts": a.npts, "frames": a.frames, "noise_px_std": a.noise,
+        print(json.dumps({"filters": B, "npts": a.npts, "frames": a.frames, "noise_px_std": a.noise, "faults": bool(a.faults),
                           "ms_per_frame_between_events": ms / a.frames, "tracks_per_filter_mean": float(cnt.mean()),
                           "bytes_per_frame": traffic, "GBps_between_events": traffic / (ms / a.frames * 1e-3) / 1e9}))
     finally:

@@ -128,7 +128,31 @@ def main():
     ap.add_argument("-lc-revisit-gap", dest="lc_revisit_gap", type=int, default=d.lc_revisit_gap,
                     help="-loop-closure: N > 0 - a stored point closes the loop once per visit, a visit ending after N frames "
                          "without a match of it (SequenceConfig.lc_revisit_gap); 0: in every frame it is seen")
+    ap.add_argument("-drop-prob", dest="drop_prob", type=float, default=0.0,
+                    help="track faults (xivo_hip_pcw_fault_config): the chance per visible point and frame that its track is lost")
+    ap.add_argument("-outlier-prob", dest="outlier_prob", type=float, default=0.0, help="track faults: the chance of a gross outlier")
+    ap.add_argument("-outlier-px", dest="outlier_px", type=float, nargs=2, default=[20.0, 60.0], metavar=("MIN", "MAX"),
+                    help="track faults: each component of an outlier's offset is +-[MIN, MAX] px")
+    ap.add_argument("-outlier-sticky", dest="outlier_sticky", action="store_true",
+                    help="track faults: an outlier's offset stays on the track until the track ends (default: one frame)")
+    ap.add_argument("-tail-prob", dest="tail_prob", type=float, default=0.0, help="track faults: the chance of a heavy-tailed pixel noise draw")
+    ap.add_argument("-tail-scale", dest="tail_scale", type=float, default=4.0, help="track faults: a tail draw multiplies noise_vision_std by this")
+    ap.add_argument("-pixel-noise", dest="pixel_noise", default="numpy", choices=["numpy", "philox"],
+                    help="-vectorized -tracks host: the pixel noise's generator - numpy's, or the device producer's counter-based "
+                         "stream restated on the host (what -tracks device always draws)")
     a = ap.parse_args()
+    faults = None
+    if a.drop_prob or a.outlier_prob or a.tail_prob or a.outlier_sticky:
+        try:
+            faults = pcw.fault_opts(sticky=int(a.outlier_sticky), p_drop=a.drop_prob, p_outlier=a.outlier_prob, p_tail=a.tail_prob,
+                                    outlier_min_px=a.outlier_px[0], outlier_max_px=a.outlier_px[1], tail_scale=a.tail_scale)
+        except ValueError as e:
+            ap.error("track faults: %s" % e)
+        if a.tracks == "host" and not (a.vectorized and a.pixel_noise == "philox"):
+            ap.error("the track-fault options with -tracks host need -vectorized -pixel-noise philox: the faults are draws of the "
+                     "device producer's generator, which only that host arm restates (or use -tracks device)")
+    if a.pixel_noise != "numpy" and not a.vectorized:
+        ap.error("-pixel-noise philox runs with -vectorized")
     # (a sequence never brings more tracks than its world has points)
     life = dict(lifecycle=a.lifecycle, tracks_max=min(a.npts, sequence.L.LIFE_MAX_TRACKS))
     if a.cam_model != "pinhole":
@@ -171,6 +195,8 @@ def main():
             ap.error(str(e))
     elif a.lc_lifecycle != "host":
         ap.error("-lc-lifecycle device needs -loop-closure")
+    if faults is not None:
+        life.update(track_faults=faults)
     if a.tracks == "device":
         life.update(track_source="device", npts=a.npts)
         if a.host == "cpp" and not a.vectorized:
@@ -197,13 +223,15 @@ def main():
         out = sequence.run_pcw_batch(cfg, a.sequences, total_time=a.total_time, imu_dt=a.imu_dt, vision_dt=a.vision_dt,
                                      noise_vision_std=a.noise_vision_std, npts=a.npts, timers=tm, trajectory_log=a.traj_log,
                                      map_log=a.map_log, rpe_dt=a.rpe_dt, innovation_log=a.innov_log, track_source=a.tracks,
-                                     imu_source=a.imu, seed=a.seed)
+                                     imu_source=a.imu, seed=a.seed, noise=a.pixel_noise)
         wall = time.perf_counter() - t0
         oos = {}
         if a.use_oos:     # the counters, and in how many sequences an entry was used at all
             ost = out["estimator"].oos_stats()
             oos = {k: int(ost[k].sum()) for k in ost.dtype.names}
             oos["oos_sequences_with_used"] = int((ost["oos_used"] > 0).sum())
+        if "fault_stats" in out:     # track faults: the producer's counters and (-tracks device) the score's four cells, summed
+            oos.update({"fault_" + k: v for k, v in out["fault_stats"]["sum"].items()})
         st = out["estimator"].stats(); out["estimator"].close()
         frames = len(out["ts"])
         ate = np.sqrt(np.mean(np.sum((out["Tsb"] - out["gt_Tsb"]) ** 2, axis=2), axis=0))
@@ -259,10 +287,13 @@ def main():
 
         oos_st = out["backend"].oos_stats() if a.use_oos else None
         lc_st = out.get("lcmap_stats")
+        fault_st = out["backend"].fault_stats() if faults is not None else None
 
         class _R:      # (read before the context goes: the device life cycle keeps the counters there)
             n_updates, n_rejected = r_.n_updates, r_.n_rejected
             oos = {k: int(oos_st[k].sum()) for k in oos_st.dtype.names} if oos_st is not None else {}
+            if fault_st is not None:
+                oos = dict(oos, **{"fault_" + k: int(fault_st[k].sum()) for k in fault_st.dtype.names})
             if lc_st is not None:     # the map counters summed over the sequences, and in how many a loop was closed at all
                 oos = dict(oos, **{"lcmap_" + k: int(lc_st[k].sum()) for k in lc_st.dtype.names},
                            lcmap_sequences_with_closed=int((lc_st["closed_frames"] > 0).sum()))

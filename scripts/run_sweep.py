@@ -48,6 +48,23 @@ def make_parser():
     ap.add_argument("-seed", type=int, default=0)
     ap.add_argument("-feature_init", default="immediate", choices=["immediate", "subfilter"],
                     help="the device life cycle the sweep runs on: lifecycle='device' or, for subfilter, pool_lifecycle='device'")
+    ap.add_argument("-tracks", default="host", choices=["host", "device"],
+                    help="host (default): the numpy worlds' tracks, uploaded and tiled; device: the worlds tiled on the device, the "
+                         "producer's streams shared between the tunings (xivo_hip_pcw_stream_share)")
+    ap.add_argument("-noise-seed", dest="noise_seed", type=int, default=0,
+                    help="-tracks device: the key of the producer's generator (pixel noise and track faults)")
+    # track faults of the device producer (xivo_hip_pcw_fault_config), the options of scripts/run_pcw.py; they need -tracks device
+    ap.add_argument("-drop-prob", dest="drop_prob", type=float, default=0.0,
+                    help="track faults: the chance per visible point and frame that its track is lost")
+    ap.add_argument("-outlier-prob", dest="outlier_prob", type=float, default=0.0, help="track faults: the chance of a gross outlier")
+    ap.add_argument("-outlier-px", dest="outlier_px", type=float, nargs=2, default=[20.0, 60.0], metavar=("MIN", "MAX"),
+                    help="track faults: each component of an outlier's offset is +-[MIN, MAX] px")
+    ap.add_argument("-outlier-sticky", dest="outlier_sticky", action="store_true",
+                    help="track faults: an outlier's offset stays on the track until the track ends (default: one frame)")
+    ap.add_argument("-tail-prob", dest="tail_prob", type=float, default=0.0,
+                    help="track faults: the chance of a heavy-tailed pixel noise draw")
+    ap.add_argument("-tail-scale", dest="tail_scale", type=float, default=4.0,
+                    help="track faults: a tail draw multiplies noise_vision_std by this")
     ap.add_argument("-out", default="", metavar="FILE.json", help="also write the JSON there")
     return ap
 
@@ -75,11 +92,20 @@ def main(argv=None):
     from xivo_amd import sequence, sweep
     axes = axes_of(args)
     kw = dict(feature_init="subfilter", pool_lifecycle="device") if args.feature_init == "subfilter" else dict(lifecycle="device")
+    if args.drop_prob or args.outlier_prob or args.tail_prob or args.outlier_sticky:
+        if args.tracks != "device":
+            raise SystemExit("the track-fault options need -tracks device: host tracks are not scored")
+        kw["track_faults"] = dict(sticky=int(args.outlier_sticky), p_drop=args.drop_prob, p_outlier=args.outlier_prob,
+                                  p_tail=args.tail_prob, outlier_min_px=args.outlier_px[0], outlier_max_px=args.outlier_px[1],
+                                  tail_scale=args.tail_scale)
+    if args.tracks == "device":      # a world never brings more tracks than it has points
+        kw["tracks_max"] = max(sequence.SequenceConfig().tracks_max, min(args.npts, sequence.L.LIFE_MAX_TRACKS))
     cfg = sequence.SequenceConfig(**kw)
     timers = {}
     t0 = time.perf_counter()
     out = sweep.run_sweep(cfg, axes, args.worlds, total_time=args.total_time, imu_dt=args.imu_dt, vision_dt=args.vision_dt,
-                          noise_vision_std=args.noise_vision_std, npts=args.npts, seed=args.seed, timers=timers)
+                          noise_vision_std=args.noise_vision_std, npts=args.npts, seed=args.seed, timers=timers,
+                          track_source=args.tracks, noise_seed=args.noise_seed)
     wall = time.perf_counter() - t0
     names = list(axes)
     table = []
@@ -88,10 +114,14 @@ def main(argv=None):
         rec.update({n: (getattr(out["cfgs"][t], n.split(".")[0])[n.split(".")[1]] if "." in n else getattr(out["cfgs"][t], n))
                     for n in names})
         rec.update(row)
+        if "outlier_rejected" in row:     # track faults: the gate's detection and false-alarm rates of the tuning
+            n_out, n_nom = row["outlier_rejected"] + row["outlier_kept"], row["nominal_rejected"] + row["nominal_kept"]
+            rec["detection_rate"] = row["outlier_rejected"] / n_out if n_out else None
+            rec["false_alarm_rate"] = row["nominal_rejected"] / n_nom if n_nom else None
         table.append(rec)
     best = best_rows(out["summary"])
     rep = {"axes": out["axes"], "tunings": out["T"], "worlds": out["W"], "filters": out["T"] * out["W"], "frames": out["frames"],
-           "contexts": 1, "runs": 1, "wall_s": wall, "frame_ms": 1e3 * timers.get("frame", 0.0) / max(out["frames"], 1),
+           "contexts": 1, "runs": 1, "tracks": args.tracks, "wall_s": wall, "frame_ms": 1e3 * timers.get("frame", 0.0) / max(out["frames"], 1),
            "table": table, "best": {k: (table[i] if i is not None else None) for k, i in best.items()}}
     line = json.dumps(rep)
     print(line)

@@ -62,6 +62,7 @@ def load_host_library():
         _HOST.xivo_batch_enable_device_lifecycle.argtypes = [C.c_void_p, C.c_int]
         _HOST.xivo_batch_enable_device_pool_lifecycle.argtypes = [C.c_void_p, C.c_int]
         _HOST.xivo_batch_enable_device_world.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double]
+        _HOST.xivo_batch_set_track_faults.argtypes = [C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_visual_world.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_ulonglong, C.c_void_p]
         _HOST.xivo_batch_enable_device_imu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _HOST.xivo_batch_frame_resident.argtypes = [C.c_void_p, C.c_ulonglong, C.c_int, C.c_double, C.c_ulonglong, C.c_void_p]
@@ -180,10 +181,29 @@ class BatchEstimator:
         """[B] pool_oos_stats_dtype read from the estimator's context"""
         return L.Context.borrow(self.host.xivo_batch_ctx(self.h), self.cfg.N, self.cfg.M_max(), self.B).pool_oos_stats(0, self.B)
 
-    def enable_device_world(self, Xs, max_radius=None):
+    def set_track_faults(self, faults=None):
+        """BatchEstimator::SetTrackFaults: the producer's track faults (a dict of xivo_pcw_fault_opts' fields; None: off) that the
+        next enable_device_world turns on with the worlds"""
+        from .pcw import fault_opts
+        if faults is None:
+            self.host.xivo_batch_set_track_faults(self.h, None)
+            return
+        o = np.zeros(1, dtype=L.pcw_fault_opts_dtype)
+        o["struct_size"] = L.pcw_fault_opts_dtype.itemsize
+        for k, v in fault_opts(faults).items():
+            o[k] = v
+        self.host.xivo_batch_set_track_faults(self.h, o.ctypes.data)
+
+    def fault_stats(self):
+        """[B] pcw_fault_stats_dtype read from the estimator's context (track faults on)"""
+        return L.Context.borrow(self.host.xivo_batch_ctx(self.h), self.cfg.N, self.cfg.M_max(), self.B).pcw_fault_stats(0, self.B)
+
+    def enable_device_world(self, Xs, max_radius=None, faults=None):
         """BatchEstimator::EnableDeviceWorld: the worlds' points Xs [B, npts, 3] go to the device once (camera: cfg.cam, whatever
         its model; max_radius, default cfg.pcw_max_radius: a distorted camera's guard against the fold-back far off axis); the
-        frames are then VisualMeasDeviceWorld. Needs one of the device life cycles and npts <= tracks_max"""
+        frames are then VisualMeasDeviceWorld. Needs one of the device life cycles and npts <= tracks_max. faults (default
+        cfg.track_faults): the producer's track faults, scored after every update"""
+        self.set_track_faults(getattr(self.cfg, "track_faults", None) if faults is None else faults)
         Xs = np.ascontiguousarray(Xs, dtype=np.float64)
         if Xs.ndim != 3 or Xs.shape[0] != self.B or Xs.shape[2] != 3:
             raise ValueError("Xs [B, npts, 3]")

@@ -234,6 +234,13 @@ struct World {
   double* gsc = nullptr; PinnedUpload up;
   int tracks_B = 0; bool fresh = false;
   bool use_cam = false; xivo_cam cam{}; double max_radius = 0.0;
+  // track faults (xivo_hip_pcw_fault_*): the options, the resident bias [Bmax][npts][2], the flag row [Bmax][tracks_max] and the
+  // counters [Bmax], allocated exactly while faults are on; scored: the score ran on the tracks the block holds. stream_mod:
+  // xivo_hip_pcw_stream_share
+  xivo_pcw_fault_opts fault{};
+  double* bias = nullptr; unsigned char* flags = nullptr; xivo_pcw_fault_stats* fstats = nullptr;
+  bool scored = false; int stream_mod = 0;
+  bool faults_on() const { return fstats != nullptr; }
   bool configured() const { return Xs != nullptr; }
   // what the life cycles ask and tell (capi_lifecycle.hip, capi_pool_lifecycle.hip)
   const int* track_counts() const { return cnt; }

@@ -15,6 +15,7 @@ namespace xivo_hip::capi {
 
 void pcw_release(xivo_hip_ctx* c) {
   c->mem.release(&c->world.Xs, &c->world.ids, &c->world.next_id, &c->world.cnt, &c->world.gsc);
+  c->mem.release(&c->world.bias, &c->world.flags, &c->world.fstats);   // the fault path's blocks go with the worlds
   c->world = World{};   // (the page-locked staging of the poses goes with it)
 }
 
@@ -27,11 +28,22 @@ int pcw_produce(xivo_hip_ctx* c, int B, const double* gsc, double noise_px_std, 
   a.use_cam = c->world.use_cam ? 1 : 0; a.cam = c->world.cam; a.max_radius = c->world.max_radius;
   a.track_ids = track_block_strided_ids(c); a.track_meas = track_block_strided_meas(c); a.cnt = c->world.cnt; a.track_ld = track_block_row(c);
   a.track_keys = c->lclife.keys;   // (null unless xivo_hip_lcmap_life_config is on: the keys go where the begin_tracks call reads them)
+  // the fault path: its own instances of the kernel, picked when faults are configured or a stream is shared (thresholds 0 and
+  // no blocks: a shared stream alone)
+  const World& w = c->world;
+  a.fault_path = (w.faults_on() || w.stream_mod > 0) ? 1 : 0; a.stream_mod = w.stream_mod;
+  if (w.faults_on()) {
+    const xivo_pcw_fault_opts& f = w.fault;
+    a.sticky = f.sticky; a.t1 = f.p_drop; a.t2 = a.t1 + f.p_outlier; a.t3 = a.t2 + f.p_tail;
+    a.outlier_min_px = f.outlier_min_px; a.outlier_max_px = f.outlier_max_px; a.tail_scale = f.tail_scale;
+    a.bias = w.bias; a.flags = w.flags; a.fstats = w.fstats;
+  }
   c->world.tracks_overwritten();   // (whatever the block held)
+  c->world.scored = false;
   {
     // per filter: the points and their ids in, the ids that changed and at most npts tracks of 32 bytes out
     char label[32];   // the instance launch_pcw_tracks picks, as the tracer prints it
-    snprintf(label, sizeof(label), "pcw_tracks_kernel<%d>", a.use_cam ? a.cam.model : -1);
+    snprintf(label, sizeof(label), a.fault_path ? "pcw_tracks_kernel<%d, true>" : "pcw_tracks_kernel<%d>", a.use_cam ? a.cam.model : -1);
     StageTimer st(c, ST_OTHER, 0.0, label, (double)B * o.npts * (24.0 + 8.0 + 8.0 + 32.0));
     if (launch_pcw_tracks(a, B, c->stream)) return XIVO_HIP_ERR_HIP;
   }
@@ -109,6 +121,7 @@ int xivo_hip_pcw_set_world(xivo_hip_ctx* c, int b0, int nb, const double* Xs, co
   HIP_TRY(hipMemcpyAsync(c->world.Xs + (size_t)b0 * n * 3, Xs, (size_t)nb * n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->world.ids + (size_t)b0 * n, ids, (size_t)nb * n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->world.next_id + b0, next_id, (size_t)nb * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  if (c->world.bias) HIP_TRY(hipMemsetAsync(c->world.bias + (size_t)b0 * n * 2, 0, (size_t)nb * n * 2 * sizeof(double), c->stream));   // new worlds carry no bias
   HIP_TRY(hipStreamSynchronize(c->stream));   // pageable sources
   return XIVO_HIP_OK;
 }
@@ -171,6 +184,72 @@ int xivo_hip_pcw_get_tracks(xivo_hip_ctx* c, int b0, int nb, int* cnt, long long
     if (meas) std::fill(meas + 3 * ((size_t)b * ld + n[b]), meas + 3 * (size_t)(b + 1) * ld, 0.0);
     if (cnt) cnt[b] = n[b];
   }
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pcw_fault_config(xivo_hip_ctx* c, const xivo_pcw_fault_opts* o) {
+  if (!pcw_ready(c) || track_block_frame_open(c)) return XIVO_HIP_ERR_INVALID;
+  if (o) {
+    if (o->struct_size != (int)sizeof(xivo_pcw_fault_opts) || (o->sticky != 0 && o->sticky != 1)) return XIVO_HIP_ERR_INVALID;
+    const double v[6] = {o->p_drop, o->p_outlier, o->p_tail, o->outlier_min_px, o->outlier_max_px, o->tail_scale};
+    for (double x : v) if (!isfinite(x)) return XIVO_HIP_ERR_INVALID;
+    for (int i = 0; i < 3; ++i) if (v[i] < 0.0 || v[i] > 1.0) return XIVO_HIP_ERR_INVALID;
+    if ((o->p_drop + o->p_outlier) + o->p_tail > 1.0) return XIVO_HIP_ERR_INVALID;   // t3 as the frame calls sum it
+    if (o->outlier_min_px < 0.0 || o->outlier_min_px > o->outlier_max_px || o->tail_scale < 1.0) return XIVO_HIP_ERR_INVALID;
+  }
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  HIP_TRY(hipStreamSynchronize(c->stream));   // a frame call may still be using the blocks given back here
+  World& w = c->world;
+  c->mem.release(&w.bias, &w.flags, &w.fstats);
+  w.fault = xivo_pcw_fault_opts{}; w.scored = false;
+  if (!o) return XIVO_HIP_OK;
+  const size_t B = c->Bmax, n = w.opts.npts, ld = track_block_row(c);
+  int rc = c->mem.zeroed(&w.bias, B * n * 2);
+  if (!rc) rc = c->mem.zeroed(&w.flags, B * ld);
+  if (!rc) rc = c->mem.zeroed(&w.fstats, B);
+  if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = XIVO_HIP_ERR_HIP;
+  if (rc) { c->mem.release(&w.bias, &w.flags, &w.fstats); return rc; }
+  w.fault = *o;
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pcw_stream_share(xivo_hip_ctx* c, int W) {
+  if (!pcw_ready(c) || W < 0 || track_block_frame_open(c)) return XIVO_HIP_ERR_INVALID;
+  c->world.stream_mod = W;   // (a kernel argument: frames already enqueued keep the one they were launched with)
+  return XIVO_HIP_OK;
+}
+
+int xivo_hip_pcw_fault_score(xivo_hip_ctx* c, int B) {
+  if (!pcw_ready(c) || !c->world.faults_on() || B <= 0 || B != track_block_frame(c) || !c->tracks.strided || c->world.tracks_B != B ||
+      c->world.scored || !c->mask || c->F <= 0)
+    return XIVO_HIP_ERR_INVALID;
+  if (hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  PcwScoreArgs a{};
+  a.life = life_args_common(c, B);
+  life_args_update(c, a.life);
+  a.flags = c->world.flags; a.stats = c->world.fstats;
+  c->world.scored = true;
+  StageTimer st(c, ST_OTHER, 0.0, "pcw_fault_score_kernel");
+  return launch_pcw_fault_score(a, B, c->stream) ? XIVO_HIP_ERR_HIP : XIVO_HIP_OK;
+}
+
+int xivo_hip_pcw_fault_get_stats(xivo_hip_ctx* c, int b0, int nb, xivo_pcw_fault_stats* out) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !pcw_ready(c) || !c->world.faults_on() || (nb > 0 && !out)) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  return d2h_rows(c, out, sizeof(xivo_pcw_fault_stats), c->world.fstats + b0, sizeof(xivo_pcw_fault_stats), sizeof(xivo_pcw_fault_stats), nb);
+}
+
+int xivo_hip_pcw_fault_get_flags(xivo_hip_ctx* c, int b0, int nb, unsigned char* flags) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return XIVO_HIP_ERR_HIP;
+  if (bad_range(c, b0, nb) || !pcw_ready(c) || !c->world.faults_on() || b0 + nb > c->world.tracks_B || (nb > 0 && !flags)) return XIVO_HIP_ERR_INVALID;
+  if (nb == 0) return XIVO_HIP_OK;
+  const size_t ld = track_block_row(c);
+  std::vector<int> n((size_t)nb);
+  int rc = d2h_rows(c, n.data(), sizeof(int), c->world.cnt + b0, sizeof(int), sizeof(int), nb);
+  if (!rc) rc = d2h_rows(c, flags, ld, c->world.flags + (size_t)b0 * ld, ld, ld, nb);
+  if (rc) return rc;
+  for (int b = 0; b < nb; ++b) std::fill(flags + (size_t)b * ld + n[b], flags + (size_t)(b + 1) * ld, (unsigned char)0);   // as get_tracks blanks its rows
   return XIVO_HIP_OK;
 }
 

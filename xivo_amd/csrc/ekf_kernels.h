@@ -195,8 +195,21 @@ struct PcwArgs {
   long long* track_ids; double* track_meas; int* cnt; int track_ld;
   long long* track_keys;   // null, or [batch][track_ld]: the world-point index of every track (xivo_hip_lcmap_life_config)
   int use_cam; xivo_cam cam; double max_radius;   // use_cam != 0 (xivo_hip_pcw_camera): project through cam instead of fx .. imh
+  // The fault path (pcw_device.h "Track faults"), its own instances of the kernel: launched when fault_path != 0, which the host
+  // sets when faults are configured or a stream is shared; the instances without it read none of these fields. t1 .. sticky: PcwFault
+  // (all 0: no event ever); stream_mod: pcw_stream_filter; bias [batch][npts][2] (sticky only), flags [batch][track_ld] and
+  // fstats [batch] may be null (faults off, a shared stream alone)
+  int fault_path, sticky, stream_mod;
+  double t1, t2, t3, outlier_min_px, outlier_max_px, tail_scale;
+  double* bias; unsigned char* flags; xivo_pcw_fault_stats* fstats;
 };
 int launch_pcw_tracks(const PcwArgs& a, int batch, hipStream_t s);
+
+// the score of one frame of filters [0, batch) (xivo_hip_pcw_fault_score): life - the book (feat_id, slot_ld, F), the strided
+// tracks of the open frame and the update's mask as the life cycles' end kernels take them; flags [batch][life.track_ld] as the
+// producer left them; the four cells are added to stats [batch]
+struct PcwScoreArgs { LifeArgs life; const unsigned char* flags; xivo_pcw_fault_stats* stats; };
+int launch_pcw_fault_score(const PcwScoreArgs& a, int batch, hipStream_t s);
 
 // ================================================================ trajsim_kernels.hip: the trajectory producer (capi_trajsim.hip)
 

@@ -36,6 +36,37 @@
 //   (w0 / w2 are the high 32 bits, the top 20 bits of w1 / w3 the low ones; u >= 2^-53, so |normal| <= sqrt(106 ln 2) < 8.6)
 //   one Box-Muller pair: r = sqrt(-2 ln u1), a = 6.283185307179586 u2, (noise_u, noise_v) = (r cos a, r sin a)
 //   the track's pixel is (u + noise_px_std noise_u, v + noise_px_std noise_v).
+//
+// Track faults (xivo_hip_pcw_fault_config; opt-in) - part of the interface as the noise is: pcw.fault_draw and
+// BatchPCW.generate(faults=...) restate exactly this. Random track loss, gross outliers (one frame, or sticky: a bias the track
+// keeps until it ends) and heavy-tailed noise, from two more draws of the same generator under the pixel noise's key:
+//   draw A: counter = (point | 0x80000000, filter, frame & 0xffffffff, frame >> 32)
+//   draw B: counter = (point | 0x40000000, filter, frame & 0xffffffff, frame >> 32)
+// The pixel noise has word 0 = point < 2048 (XIVO_LIFE_MAX_TRACKS bounds a world) and the trajectory producer word 0 in
+// {0, 1, 2}: draw A, draw B and those two never share a counter, so under any key the streams are disjoint (the pixel noise
+// and the IMU noise still need different seeds, as before). "filter" is b, or b % stream_mod after
+// xivo_hip_pcw_stream_share(stream_mod) - in the pixel noise's counter too: filters w, w + W, w + 2 W, ... then draw the same
+// words. The trajectory producer's stream is not touched by it.
+//   draw A  e = uniform(w0, w1) selects the event against t1 = p_drop, t2 = t1 + p_outlier, t3 = t2 + p_tail, summed on the
+//           host in this order and handed over as they are (all <= 1):
+//             e < t1: drop ; t1 <= e < t2: outlier ; t2 <= e < t3: tail ; otherwise nominal
+//           bit 0 of w2 is the sign of the outlier offset's u component, bit 1 that of v (set: negative)
+//   draw B  (read on an outlier event only) m_u = uniform(w0, w1), m_v = uniform(w2, w3);
+//           off_u = +-(outlier_min_px + (outlier_max_px - outlier_min_px) m_u), off_v likewise with m_v, contraction off.
+//           No trigonometry and no logarithm: host and device agree to the last bit.
+// Per point and frame, in this order:
+//   1. vis: the geometric visibility above
+//   2. if vis, draw A
+//   3. vis_eff = vis && !drop. Ids, ranks, the count, next_id and the keys follow vis_eff where they followed vis: a dropped
+//      point loses its id and returns as a new track, exactly as a point that left the image
+//   4. the offset. sticky = 0: off on an outlier event, else 0. sticky = 1: a resident bias [2] per point holds it - an outlier
+//      event overwrites it, it is added on every later frame of the same track, and it is zeroed when vis_eff is false
+//   5. pixel = pcw_noisy(u + offset_u, noise_px_std * (tail ? tail_scale : 1), noise_u): the sum u + offset first, the product
+//      std * scale formed once; v likewise
+//   6. the track's flag byte: bit 0 an outlier event this frame, bit 1 a tail event, bit 2 a non-zero bias carried over from an
+//      earlier frame and added unchanged (an outlier event that overwrites a carried bias sets bit 0 alone)
+// The score (pcw_fault_cell): a track is faulty when flag & 5; with the update's inlier mask entry of the feature that follows
+// the track, rejected = !mask, the four cells are outlier_rejected, outlier_kept, nominal_rejected, nominal_kept.
 #pragma once
 
 #include <math.h>
@@ -123,6 +154,85 @@ XIVO_PCW_HD void pcw_normal_pair(unsigned long long seed, unsigned long long fra
 XIVO_PCW_HD double pcw_noisy(double u, double noise_px_std, double n) {
 #pragma clang fp contract(off)
   return u + noise_px_std * n;
+}
+
+// ---- track faults (the rules: the header's opening comment)
+// t1 <= t2 <= t3 <= 1: the event thresholds as the host summed them; sticky in {0, 1}
+struct PcwFault { double t1, t2, t3, outlier_min_px, outlier_max_px, tail_scale; int sticky; };
+enum PcwEvent { PCW_EV_NOMINAL = 0, PCW_EV_DROP = 1, PCW_EV_OUTLIER = 2, PCW_EV_TAIL = 3 };
+enum PcwFlag { PCW_FLAG_OUTLIER = 1, PCW_FLAG_TAIL = 2, PCW_FLAG_BIASED = 4, PCW_FLAG_FAULTY = PCW_FLAG_OUTLIER | PCW_FLAG_BIASED };
+constexpr uint32_t kPcwDrawA = 0x80000000u, kPcwDrawB = 0x40000000u;
+// the filter word of the pixel-noise and fault counters (stream_mod 0: every filter its own stream)
+XIVO_PCW_HD int pcw_stream_filter(int b, int stream_mod) { return stream_mod > 0 ? b % stream_mod : b; }
+// the words of draw A / draw B (draw = kPcwDrawA / kPcwDrawB) of one point; b: the filter word
+XIVO_PCW_HD void pcw_fault_words(unsigned long long seed, unsigned long long frame, int b, int p, uint32_t draw, uint32_t w[4]) {
+  const uint32_t ctr[4] = {(uint32_t)p | draw, (uint32_t)b, (uint32_t)(frame & 0xffffffffull), (uint32_t)(frame >> 32)};
+  const uint32_t key[2] = {(uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32)};
+  philox4x32_10(ctr, key, w);
+}
+XIVO_PCW_HD int pcw_fault_event(const PcwFault& f, double e) {
+  return e < f.t1 ? PCW_EV_DROP : (e < f.t2 ? PCW_EV_OUTLIER : (e < f.t3 ? PCW_EV_TAIL : PCW_EV_NOMINAL));
+}
+// the outlier offset of draw A's sign bits (wa) and draw B's two uniforms (wb)
+XIVO_PCW_HD void pcw_fault_offset(const PcwFault& f, const uint32_t wa[4], const uint32_t wb[4], double off[2]) {
+#pragma clang fp contract(off)
+  const double m_u = philox_uniform(wb[0], wb[1]), m_v = philox_uniform(wb[2], wb[3]);
+  const double span = f.outlier_max_px - f.outlier_min_px;
+  const double a_u = f.outlier_min_px + span * m_u, a_v = f.outlier_min_px + span * m_v;
+  off[0] = (wa[2] & 1u) ? -a_u : a_u;
+  off[1] = (wa[2] & 2u) ? -a_v : a_v;
+}
+// Steps 2 - 4 and 6 of one point in one frame. vis: the geometric visibility; b: the filter word; bias [2]: the point's resident
+// bias, read and written when f.sticky (else not touched; may be null). -> vis_eff; *event the draw's event (nominal when not
+// visible); for a track (vis_eff) off [2] the offset to add, *scale the factor of noise_px_std and *flag its flag byte
+XIVO_PCW_HD bool pcw_fault_point(const PcwFault& f, unsigned long long seed, unsigned long long frame, int b, int p, bool vis,
+                                 double* bias, double off[2], double* scale, unsigned char* flag, int* event) {
+  uint32_t wa[4] = {0u, 0u, 0u, 0u};
+  int ev = PCW_EV_NOMINAL;
+  if (vis && f.t3 > 0.0) {   // (t3 = 0: every event is nominal whatever the draw says)
+    pcw_fault_words(seed, frame, b, p, kPcwDrawA, wa);
+    ev = pcw_fault_event(f, philox_uniform(wa[0], wa[1]));
+  }
+  *event = ev;
+  off[0] = 0.0; off[1] = 0.0; *scale = 1.0; *flag = 0;
+  const bool vis_eff = vis && ev != PCW_EV_DROP;
+  if (!vis_eff) {
+    if (f.sticky) { bias[0] = 0.0; bias[1] = 0.0; }
+    return false;
+  }
+  unsigned char fl = 0;
+  if (ev == PCW_EV_OUTLIER) {
+    uint32_t wb[4];
+    pcw_fault_words(seed, frame, b, p, kPcwDrawB, wb);
+    pcw_fault_offset(f, wa, wb, off);
+    fl |= PCW_FLAG_OUTLIER;
+    if (f.sticky) { bias[0] = off[0]; bias[1] = off[1]; }
+  } else if (f.sticky) {
+    off[0] = bias[0]; off[1] = bias[1];
+    if (off[0] != 0.0 || off[1] != 0.0) fl |= PCW_FLAG_BIASED;
+  }
+  if (ev == PCW_EV_TAIL) { fl |= PCW_FLAG_TAIL; *scale = f.tail_scale; }
+  *flag = fl;
+  return true;
+}
+// step 5: the pixel a faulty track reports; std_eff = noise_px_std * scale, formed once by the caller (pcw_fault_std)
+XIVO_PCW_HD double pcw_fault_std(double noise_px_std, double scale) {
+#pragma clang fp contract(off)
+  return noise_px_std * scale;
+}
+XIVO_PCW_HD double pcw_fault_pixel(double u, double offset, double std_eff, double n) {
+#pragma clang fp contract(off)
+  const double s = u + offset;
+  return pcw_noisy(s, std_eff, n);
+}
+
+// ---- the score of the gate's decisions against the labels
+enum PcwCell { PCW_CELL_OUTLIER_REJECTED = 0, PCW_CELL_OUTLIER_KEPT = 1, PCW_CELL_NOMINAL_REJECTED = 2, PCW_CELL_NOMINAL_KEPT = 3 };
+// mask: the update's inlier mask entry of the feature (0: rejected); flag: the flag byte of the track it followed
+XIVO_PCW_HD int pcw_fault_cell(unsigned char mask, unsigned char flag) {
+  const bool faulty = (flag & PCW_FLAG_FAULTY) != 0, rejected = mask == 0;
+  return faulty ? (rejected ? PCW_CELL_OUTLIER_REJECTED : PCW_CELL_OUTLIER_KEPT)
+                : (rejected ? PCW_CELL_NOMINAL_REJECTED : PCW_CELL_NOMINAL_KEPT);
 }
 
 }  // namespace xivo_hip

@@ -435,6 +435,8 @@ void BatchEstimator::EnableDeviceWorld(int npts, const xivo_pcw_opts& cam, const
   world_frame_ = 0;
   // the simulated camera is the estimator's: a distorted model goes down whole (cam's pinhole is then not read)
   if (device_world_ && cfg_.cam.model != XIVO_CAM_PINHOLE) Check(xivo_hip_pcw_camera(ctx_, &cfg_.cam, max_radius), "pcw_camera");
+  faults_on_ = device_world_ && have_faults_;   // (pcw_config released whatever an earlier call turned on)
+  if (faults_on_) Check(xivo_hip_pcw_fault_config(ctx_, &faults_), "pcw_fault_config");
   if (device_world_) Check(xivo_hip_pcw_set_world(ctx_, 0, B_, Xs, nullptr, nullptr), "pcw_set_world");
 }
 
@@ -461,6 +463,7 @@ void BatchEstimator::FrameOnProducedTracks(unsigned char* mask_out) {
     Check(xivo_hip_life_begin_tracks(ctx_, B_, cfg_.n_features), "life_begin_tracks");
   }
   RunUpdate();
+  if (faults_on_) Check(xivo_hip_pcw_fault_score(ctx_, B_), "pcw_fault_score");   // (enqueued: no host wait)
   Check(device_pool_life_ ? xivo_hip_pool_life_end(ctx_, B_) : xivo_hip_life_end(ctx_, B_), device_pool_life_ ? "pool_life_end" : "life_end");
   if (mask_out) std::memcpy(mask_out, mask_.data(), mask_.size());
 }
@@ -816,6 +819,12 @@ int xivo_batch_enable_device_world(void* h, int npts, const xivo_pcw_opts* cam, 
   if (!h || !cam) return -1;
   try { static_cast<xivo::hip::BatchEstimator*>(h)->EnableDeviceWorld(npts, *cam, Xs, max_radius); return 0; }
   catch (const std::exception&) { return -1; }
+}
+int xivo_batch_set_track_faults(void* h, const xivo_pcw_fault_opts* opts) {
+  if (!h) return -1;
+  auto* e = static_cast<xivo::hip::BatchEstimator*>(h);
+  if (opts) e->SetTrackFaults(*opts); else e->ClearTrackFaults();
+  return 0;
 }
 int xivo_batch_visual_world(void* h, double t, const double* gsc, double noise_px_std, unsigned long long seed, unsigned char* mask_out) {
   if (!h) return -1;

@@ -133,6 +133,12 @@ class BatchEstimator {
   void EnableDeviceWorld(int npts, const xivo_pcw_opts& cam, const double* Xs, double max_radius = std::numeric_limits<double>::infinity());
   void VisualMeasDeviceWorld(double t, const double* gsc, double noise_px_std, unsigned long long seed, unsigned char* mask_out);
   bool device_world() const { return device_world_; }
+  // track faults of the device producer (xivo_hip_pcw_fault_config): set before EnableDeviceWorld, which turns them on with the
+  // worlds; VisualMeasDeviceWorld / FrameResident then score every update's gate decisions against the tracks' flags
+  // (xivo_hip_pcw_fault_score; the counters: xivo_hip_pcw_fault_get_stats on ctx()). ClearTrackFaults: off from the next
+  // EnableDeviceWorld on
+  void SetTrackFaults(const xivo_pcw_fault_opts& opts) { faults_ = opts; faults_.struct_size = (int)sizeof(faults_); have_faults_ = true; }
+  void ClearTrackFaults() { have_faults_ = false; }
   // the simulated IMU and the ground-truth poses from the device too (xivo_hip_trajsim_*; after EnableDeviceWorld, both calls
   // throw without it): EnableDeviceImu configures the trajectory producer (opts as xivo_hip_trajsim_config takes them;
   // struct_size is filled in here) with curve motion[b] (0 Lissajous, 1 trefoil) and rate[b] per filter; n_max = 0 releases it.
@@ -167,6 +173,7 @@ class BatchEstimator {
   long DeviceCount(int which) const { return device_life_ ? LifeCount(which) : (device_pool_life_ ? PoolLifeCount(which) : 0); }
   bool device_life_ = false, want_mask_ = false, device_world_ = false, device_pool_life_ = false;
   unsigned long long world_frame_ = 0;
+  xivo_pcw_fault_opts faults_{}; bool have_faults_ = false, faults_on_ = false;
   bool device_imu_ = false; double device_imu_dt_ = 0.0;
 
   struct PoolBook {                                 // one filter's feature pool: tracks per entry, anchors and their links

@@ -183,6 +183,13 @@ CHI2_95 = (0.0, 3.841458820694124, 5.991464547107979, 7.814727903251179, 9.48772
 pcw_opts_dtype = np.dtype([("struct_size", "i4"), ("npts", "i4"), ("fx", "f8"), ("fy", "f8"), ("cx", "f8"), ("cy", "f8"),
                            ("imw", "f8"), ("imh", "f8")])
 assert pcw_opts_dtype.itemsize == 56
+# track faults of the producer (include/xivo_hip.h): xivo_pcw_fault_opts, xivo_pcw_fault_stats
+pcw_fault_opts_dtype = np.dtype([("struct_size", "i4"), ("sticky", "i4"), ("p_drop", "f8"), ("p_outlier", "f8"), ("p_tail", "f8"),
+                                 ("outlier_min_px", "f8"), ("outlier_max_px", "f8"), ("tail_scale", "f8")])
+assert pcw_fault_opts_dtype.itemsize == 56
+pcw_fault_stats_dtype = np.dtype([(k, "i8") for k in ("tracks", "dropped", "outlier_events", "tail_events", "biased",
+                                                      "outlier_rejected", "outlier_kept", "nominal_rejected", "nominal_kept")])
+assert pcw_fault_stats_dtype.itemsize == 72
 # trajectory producer (include/xivo_hip.h): xivo_trajsim_opts
 trajsim_opts_dtype = np.dtype([("struct_size", "i4"), ("n_max", "i4"), ("T_max", "i4"), ("reserved", "i4"), ("imu_dt", "f8"),
                                ("rot_amp", "f8"), ("rot_w", "f8", 3), ("noise_accel", "f8"), ("noise_gyro", "f8"),
@@ -354,6 +361,11 @@ _SIGS = {
     "xivo_hip_pcw_tracks": [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_ulonglong, C.c_ulonglong],
     "xivo_hip_pcw_get_tracks": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "xivo_hip_pcw_tracks_resident": [C.c_void_p, C.c_int, C.c_double, C.c_ulonglong, C.c_ulonglong],
+    "xivo_hip_pcw_fault_config": [C.c_void_p, C.c_void_p],
+    "xivo_hip_pcw_stream_share": [C.c_void_p, C.c_int],
+    "xivo_hip_pcw_fault_score": [C.c_void_p, C.c_int],
+    "xivo_hip_pcw_fault_get_stats": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "xivo_hip_pcw_fault_get_flags": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "xivo_hip_trajsim_config": [C.c_void_p, C.c_void_p],
     "xivo_hip_trajsim_set": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "xivo_hip_trajsim_frame": [C.c_void_p, C.c_int, C.c_ulonglong, C.c_int],
@@ -1281,6 +1293,40 @@ class Context:
         """pcw_tracks on the camera poses the last trajsim_frame(B) left on the device (asynchronous, no upload)"""
         self._check(self.lib.xivo_hip_pcw_tracks_resident(self.h, self.batch if B is None else int(B), float(noise_px_std),
                                                           int(seed), int(frame)))
+
+    # ---- track faults of the producer (xivo_hip_pcw_fault_*)
+    def pcw_fault_config(self, faults=None):
+        """faults: a dict of xivo_pcw_fault_opts' fields (pcw.fault_opts fills the defaults) - on; None - off, releases"""
+        if faults is None:
+            self._check(self.lib.xivo_hip_pcw_fault_config(self.h, None))
+            return
+        o = np.zeros(1, dtype=pcw_fault_opts_dtype)
+        o["struct_size"] = pcw_fault_opts_dtype.itemsize
+        for k, v in faults.items():
+            o[k] = v
+        self._check(self.lib.xivo_hip_pcw_fault_config(self.h, _ptr(o)))
+
+    def pcw_stream_share(self, W):
+        """filters w, w + W, ... draw the same pixel-noise and fault words from the next frame call on (0: each its own)"""
+        self._check(self.lib.xivo_hip_pcw_stream_share(self.h, int(W)))
+
+    def pcw_fault_score(self, B=None):
+        """the gate's decisions of the open frame against the tracks' fault flags, added to the counters (asynchronous)"""
+        self._check(self.lib.xivo_hip_pcw_fault_score(self.h, self.batch if B is None else int(B)))
+
+    def pcw_fault_stats(self, b0=0, nb=None):
+        """-> [nb] pcw_fault_stats_dtype; one synchronising read"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        out = np.zeros(nb, dtype=pcw_fault_stats_dtype)
+        self._check(self.lib.xivo_hip_pcw_fault_get_stats(self.h, int(b0), nb, _ptr(out)))
+        return out
+
+    def pcw_fault_flags(self, tracks_max, b0=0, nb=None):
+        """the flag byte of every track the last pcw_tracks left -> [nb, tracks_max] uint8, parallel to pcw_get_tracks' ids"""
+        nb = self.batch - b0 if nb is None else int(nb)
+        out = np.zeros((nb, int(tracks_max)), dtype=np.uint8)
+        self._check(self.lib.xivo_hip_pcw_fault_get_flags(self.h, int(b0), nb, _ptr(out)))
+        return out
 
     # ---- trajectory producer on the device (xivo_hip_trajsim_*)
     def trajsim_config(self, n_max, T_max=0, imu_dt=0.0025, rot_amp=0.2, rot_w=None, noise_accel=1e-4, noise_gyro=1e-5,

@@ -267,6 +267,70 @@ def trajsim_normals(seed, k, b):
     return philox_normal(seed, k, b[..., None], np.arange(3)).reshape(b.shape + (6,))
 
 
+# ---- the device producer's track faults on the host (xivo_amd/csrc/pcw_device.h "Track faults" is the specification)
+FAULT_NOMINAL, FAULT_DROP, FAULT_OUTLIER, FAULT_TAIL = 0, 1, 2, 3        # the event of draw A
+FLAG_OUTLIER, FLAG_TAIL, FLAG_BIASED = 1, 2, 4                            # a track's flag byte; faulty: flag & 5
+FAULT_COUNTERS = ("tracks", "dropped", "outlier_events", "tail_events", "biased")
+_FAULT_DEFAULTS = dict(sticky=0, p_drop=0.0, p_outlier=0.0, p_tail=0.0, outlier_min_px=0.0, outlier_max_px=0.0, tail_scale=1.0)
+
+
+def fault_opts(faults=None, **kw):
+    """the fields of xivo_pcw_fault_opts as a dict, defaults filled in (no event, scale 1); refuses what
+    xivo_hip_pcw_fault_config refuses"""
+    o = dict(_FAULT_DEFAULTS)
+    o.update(faults or {})
+    o.update(kw)
+    if set(o) != set(_FAULT_DEFAULTS):
+        raise ValueError("unknown fault option(s) %s" % sorted(set(o) - set(_FAULT_DEFAULTS)))
+    if o["sticky"] not in (0, 1, False, True):
+        raise ValueError("sticky must be 0 or 1")
+    o["sticky"] = int(o["sticky"])
+    for k in _FAULT_DEFAULTS:
+        if k != "sticky":
+            o[k] = float(o[k])
+            if not np.isfinite(o[k]):
+                raise ValueError("%s is not finite" % k)
+    if any(not 0.0 <= o[k] <= 1.0 for k in ("p_drop", "p_outlier", "p_tail")) or (o["p_drop"] + o["p_outlier"]) + o["p_tail"] > 1.0:
+        raise ValueError("p_drop, p_outlier, p_tail must lie in [0, 1] and sum to at most 1")
+    if o["outlier_min_px"] < 0.0 or o["outlier_min_px"] > o["outlier_max_px"]:
+        raise ValueError("0 <= outlier_min_px <= outlier_max_px")
+    if o["tail_scale"] < 1.0:
+        raise ValueError("tail_scale >= 1")
+    return o
+
+
+def _philox_uniform(hi, lo):
+    hi, lo = hi.astype(np.uint64), lo.astype(np.uint64)
+    return (((hi << np.uint64(20)) | (lo >> np.uint64(12))).astype(np.float64) + 0.5) * 2.0 ** -52
+
+
+def fault_words(seed, frame, b, p, draw):
+    """the four words of draw "A" (word 0 of the counter: p | 0x80000000) or "B" (p | 0x40000000) of point p, filter word b"""
+    tag = {"A": 0x80000000, "B": 0x40000000}[draw]
+    return philox_words(seed, frame, b, np.asarray(p, dtype=np.uint32) | np.uint32(tag))
+
+
+def fault_draw(seed, frame, b, p, opts):
+    """what the device producer draws for point p of filter (word) b in that frame, b and p broadcast ->
+    dict(event [...] (FAULT_*), off [..., 2] the outlier offset (meaningful on an outlier event), tail [...] bool).
+    Integer words, 52-bit uniforms and one multiply-add without contraction: the device's values bit for bit."""
+    o = fault_opts(opts)
+    t1 = o["p_drop"]; t2 = t1 + o["p_outlier"]; t3 = t2 + o["p_tail"]
+    wa, wb = fault_words(seed, frame, b, p, "A"), fault_words(seed, frame, b, p, "B")
+    e = _philox_uniform(wa[..., 0], wa[..., 1])
+    event = np.where(e < t1, FAULT_DROP, np.where(e < t2, FAULT_OUTLIER, np.where(e < t3, FAULT_TAIL, FAULT_NOMINAL)))
+    span = o["outlier_max_px"] - o["outlier_min_px"]
+    a_u = o["outlier_min_px"] + span * _philox_uniform(wb[..., 0], wb[..., 1])
+    a_v = o["outlier_min_px"] + span * _philox_uniform(wb[..., 2], wb[..., 3])
+    off = np.stack([np.where(wa[..., 2] & np.uint32(1), -a_u, a_u), np.where(wa[..., 2] & np.uint32(2), -a_v, a_v)], axis=-1)
+    return dict(event=event, off=off, tail=event == FAULT_TAIL)
+
+
+def fault_cell(mask, flag):
+    """the score's rule (pcw_fault_cell): 0 outlier_rejected, 1 outlier_kept, 2 nominal_rejected, 3 nominal_kept"""
+    return (0 if flag & (FLAG_OUTLIER | FLAG_BIASED) else 2) + (0 if not mask else 1)
+
+
 def project_points(Xs, Rsc, Tsc, K, imw, imh):
     """the projection and the visibility test in the evaluation order of pcw_device.h, elementwise (no einsum: its summation
     order is not fixed): Xs [B, npts, 3], Rsc [B, 3, 3], Tsc [B, 3] -> (vis [B, npts] bool, u, v, Xc_2 [B, npts])"""
@@ -355,11 +419,21 @@ class BatchPCW:
     layout xivo::hip::BatchEstimator::VisualMeasPointCloud takes (offsets, ids, (x, y, depth) rows).
     noise: "numpy" (default) draws the pixel noise from the world's numpy generator; "philox" draws the stream of the device
     producer (philox_normal, keyed by noise_seed and the number of generate() calls so far as the frame) and projects in its
-    evaluation order (project_points), so that a host arm can be held against a device arm."""
+    evaluation order (project_points), so that a host arm can be held against a device arm.
+    faults (a dict of xivo_pcw_fault_opts' fields; needs noise="philox"): the device producer's track faults, restated - loss,
+    outliers (with the sticky bias state in self.bias), heavy tails; generate() then leaves the tracks' flag bytes in
+    last_fault_flags and adds to fault_stats, the producer's five counters per world. stream_mod (philox too): world b draws the
+    words of filter b % stream_mod (xivo_hip_pcw_stream_share)."""
 
-    def __init__(self, B, npts=1000, xlim=(-10, 10), ylim=(-10, 10), zlim=(-5, 5), seed=0, Xs=None, noise="numpy", noise_seed=0):
+    def __init__(self, B, npts=1000, xlim=(-10, 10), ylim=(-10, 10), zlim=(-5, 5), seed=0, Xs=None, noise="numpy", noise_seed=0,
+                 faults=None, stream_mod=0):
         if noise not in ("numpy", "philox"):
             raise ValueError("noise must be 'numpy' or 'philox'")
+        if noise != "philox" and (faults is not None or stream_mod):
+            raise ValueError("faults and stream_mod need noise='philox': they are draws of the device producer's generator")
+        if int(stream_mod) < 0:
+            raise ValueError("stream_mod >= 0")
+        self.faults, self.stream_mod = (None if faults is None else fault_opts(faults)), int(stream_mod)
         self.noise, self.noise_seed, self.frame = noise, int(noise_seed), 0
         self.rng = np.random.default_rng(seed)
         lo = np.array([xlim[0], ylim[0], zlim[0]], dtype=float); hi = np.array([xlim[1], ylim[1], zlim[1]], dtype=float)
@@ -367,6 +441,9 @@ class BatchPCW:
         self.ids = np.full(self.Xs.shape[:2], -1, dtype=np.int64)
         self.next_pt_id = np.full(self.Xs.shape[0], 10000, dtype=np.int64)
         self.last_point_index = np.zeros(0, dtype=np.int64)   # world-point index of every track the last generate() returned
+        self.last_fault_flags = np.zeros(0, dtype=np.uint8)   # and its flag byte (faults)
+        self.bias = np.zeros(self.Xs.shape[:2] + (2,))        # the sticky outliers' offsets (faults with sticky = 1)
+        self.fault_stats = {k: np.zeros(self.Xs.shape[0], dtype=np.int64) for k in FAULT_COUNTERS}
 
     def generate(self, Rsc, Tsc, K, imw, imh, noise_px_std, cam=None, max_radius=np.inf):
         """cam (a camera dict, any model) and max_radius: project through it as the device producer does after
@@ -381,7 +458,13 @@ class BatchPCW:
             Xc = np.stack([u, v, zc], axis=-1)                                # (only [..., 2] is read below)
             B, npts = u.shape
             if self.noise == "philox":
-                noise = noise_px_std * philox_normal(self.noise_seed, self.frame, np.arange(B)[:, None], np.arange(npts)[None, :])
+                bw = np.arange(B) % self.stream_mod if self.stream_mod else np.arange(B)
+                std = noise_px_std
+                if self.faults is not None:
+                    vis, off, std = self._faults(vis, bw, npts, noise_px_std)   # from here on vis is vis_eff
+                    u, v = u + off[..., 0], v + off[..., 1]                      # the sum with the offset first
+                    std = std[..., None]
+                noise = std * philox_normal(self.noise_seed, self.frame, bw[:, None], np.arange(npts)[None, :])
                 self.frame += 1
             else:
                 noise = noise_px_std * self.rng.standard_normal(u.shape + (2,))
@@ -403,4 +486,27 @@ class BatchPCW:
         sel = np.nonzero(vis)                                                 # row-major: sequences in order, points ascending
         meas = np.stack([u[sel] + noise[sel][:, 0], v[sel] + noise[sel][:, 1], Xc[..., 2][sel]], axis=1)
         self.last_point_index = sel[1].astype(np.int64)
+        self.last_fault_flags = self._flags[sel] if self.faults is not None else np.zeros(len(sel[0]), dtype=np.uint8)
         return off, self.ids[sel].copy(), np.ascontiguousarray(meas)
+
+    def _faults(self, vis, bw, npts, noise_px_std):
+        """steps 2 - 4 and 6 of pcw_device.h "Track faults" for every point: geometric vis -> (vis_eff, offset [B, npts, 2],
+        noise std [B, npts]); leaves the flag bytes in self._flags, updates self.bias and self.fault_stats"""
+        o = self.faults
+        d = fault_draw(self.noise_seed, self.frame, bw[:, None], np.arange(npts)[None, :], o)
+        ev = np.where(vis, d["event"], FAULT_NOMINAL)
+        dropped = ev == FAULT_DROP
+        vis_eff = vis & ~dropped
+        outl, tail = ev == FAULT_OUTLIER, ev == FAULT_TAIL
+        if o["sticky"]:
+            carried = vis_eff & ~outl & (self.bias != 0.0).any(axis=-1)
+            self.bias = np.where(outl[..., None], d["off"], self.bias)
+            self.bias = np.where(vis_eff[..., None], self.bias, 0.0)
+            off = self.bias
+        else:
+            carried = np.zeros_like(vis)
+            off = np.where(outl[..., None], d["off"], 0.0)
+        self._flags = (outl * FLAG_OUTLIER + tail * FLAG_TAIL + carried * FLAG_BIASED).astype(np.uint8)
+        for k, m in zip(FAULT_COUNTERS, (vis_eff, dropped, outl, tail, carried)):
+            self.fault_stats[k] += m.sum(axis=1)
+        return vis_eff, off, noise_px_std * np.where(tail, o["tail_scale"], 1.0)

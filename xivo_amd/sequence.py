@@ -41,6 +41,11 @@ What is mirrored from the reference and what is simplified:
     produces each frame's tracks from the ground-truth camera poses straight into the block the life cycle reads
     (`SequenceRunner.frame_world`): 96 bytes per filter go down instead of the tracks. Its pixel noise is the counter-based
     stream pcw.philox_normal restates.
+  * what goes wrong with the tracks (`SequenceConfig.track_faults`, needs track_source="device"; None by default): a dict of
+    xivo_pcw_fault_opts' fields - random track loss, gross outliers (one frame or sticky) and heavy-tailed noise drawn by the
+    producer (xivo_hip_pcw_fault_config), a ground-truth flag byte beside every track, and after every update
+    xivo_hip_pcw_fault_score adds the gate's decisions against the flags to `HipBackend.fault_stats()`. BatchPCW(noise="philox",
+    faults=...) restates the producer bit for bit.
   * where the IMU records come from (`SequenceConfig.imu_source`): "host" (default) - the numpy simulator and `ImuFeeder`, uploaded
     by xivo_hip_propagate; "device" (needs track_source="device") - xivo_hip_trajsim_frame (trajsim_kernels.hip) produces the
     feeder's records and the ground-truth camera and body poses on the device, xivo_hip_propagate_resident consumes the records
@@ -205,6 +210,9 @@ class SequenceConfig:
         # resident worlds of npts points each; needs lifecycle or pool_lifecycle = "device" and npts <= tracks_max)
         self.track_source = "host"
         self.npts = 1000
+        # track faults of the device producer (xivo_hip_pcw_fault_config): None, or a dict of xivo_pcw_fault_opts' fields
+        # (sticky, p_drop, p_outlier, p_tail, outlier_min_px, outlier_max_px, tail_scale; pcw.fault_opts fills the rest)
+        self.track_faults = None
         # the simulated camera is `cam`, whatever its model; a distorted one sees no point whose normalised radius hypot(x, y)
         # exceeds this (the guard against a polynomial distortion's fold-back far off axis; inf: no guard)
         self.pcw_max_radius = float("inf")
@@ -412,8 +420,9 @@ class HipBackend:
             self.enable_device_lifecycle()
         if cfg.pool_lifecycle == "device":
             self.enable_device_pool_lifecycle()
+        self.faults_on = False
         if cfg.track_source == "device":
-            self.enable_device_world()
+            self.enable_device_world(faults=getattr(cfg, "track_faults", None))
         self.oos_on = False
         if getattr(cfg, "use_oos", False):
             self.enable_oos()
@@ -565,13 +574,37 @@ class HipBackend:
     def pool_life_stats(self):
         return self.ctx.pool_life_stats(0, self.B)
 
-    def enable_device_world(self):
+    def enable_device_world(self, faults=None):
         """allocate the resident worlds of the device track source (xivo_hip_pcw_config): cfg.npts points per filter, the
-        camera of cfg.cam (a distorted model goes down whole: xivo_hip_pcw_camera)"""
+        camera of cfg.cam (a distorted model goes down whole: xivo_hip_pcw_camera). faults: a dict of xivo_pcw_fault_opts'
+        fields - the producer's track faults on (xivo_hip_pcw_fault_config); None: off"""
         cam = self.cfg.cam
         self.ctx.pcw_config(self.cfg.npts, cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["cols"], cam["rows"])
         if cam["model"] != L_CAM_PINHOLE:
             self.ctx.pcw_camera(cam, self.cfg.pcw_max_radius)
+        self.set_track_faults(faults)
+
+    def set_track_faults(self, faults=None):
+        """the producer's track faults on (a dict of xivo_pcw_fault_opts' fields; the counters start at 0) or off (None)"""
+        from .pcw import fault_opts
+        self.ctx.pcw_fault_config(None if faults is None else fault_opts(faults))
+        self.faults_on = faults is not None
+
+    def stream_share(self, W):
+        """filters w, w + W, ... draw the same pixel-noise and fault words (xivo_hip_pcw_stream_share; 0: each its own)"""
+        self.ctx.pcw_stream_share(W)
+
+    def fault_score(self):
+        """the open frame's gate decisions against the tracks' fault flags, between the update and the end call (asynchronous)"""
+        self.ctx.pcw_fault_score(self.B)
+
+    def fault_stats(self):
+        """[B] pcw_fault_stats_dtype: the producer's and the score's counters; one synchronising read"""
+        return self.ctx.pcw_fault_stats(0, self.B)
+
+    def fault_flags(self):
+        """the flag byte of every track the last make_tracks left -> [B, tracks_max] uint8"""
+        return self.ctx.pcw_fault_flags(self.cfg.tracks_max, 0, self.B)
 
     def set_world(self, Xs, ids=None, next_id=None):
         """the world points [B, npts, 3] of every filter (ids None: nothing is tracked yet, next_id None: 10000)"""
@@ -1045,11 +1078,18 @@ class SequenceRunner:
         """the begin / end pair of a frame on the tracks the device produced, by life cycle: the pool life cycle counts the
         frame and passes CandidateStrict, as _frame_subfilter_device does"""
         be = self.be
+        end = be.pool_life_end if self.device_pool_lifecycle else be.life_end
+        if getattr(be, "faults_on", False):   # track faults: the score between the update and the end call (enqueued, no wait)
+            end_call = end
+
+            def end():
+                be.fault_score()
+                return end_call()
         if not self.device_pool_lifecycle:
-            return be.life_begin_tracks, be.life_end
+            return be.life_begin_tracks, end
         self.vision_counter += 1
         strict = self.vision_counter >= self.cfg.strict_criteria_timesteps
-        return lambda: be.pool_life_begin_tracks(strict), be.pool_life_end
+        return lambda: be.pool_life_begin_tracks(strict), end
 
     def frame_world(self, imu, gsc, frame, keys=None):
         """one camera frame whose tracks the device produces (track_source="device"): gsc [B, 12] the ground-truth camera pose
@@ -1534,7 +1574,9 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     innovation_log: as in run_pcw; the C++ frame records between its update and AbsorbError (BatchEstimator::EnableInnovationLog).
     track_source ("host" / "device", default cfg.track_source): "device" keeps the worlds on the device
     (BatchEstimator::EnableDeviceWorld) and every frame hands down the ground-truth camera poses only
-    (VisualMeasDeviceWorld); the pixel noise is then the stream of pcw.philox_normal keyed by noise_seed. noise="philox" gives
+    (VisualMeasDeviceWorld; with cfg.track_faults the producer's track faults are on, every update is scored and the report
+    gains "fault_stats": the counters' sums and per filter - the host-track arm hands the same options to BatchPCW.generate,
+    which needs noise="philox", and reports the producer's five counters only); the pixel noise is then the stream of pcw.philox_normal keyed by noise_seed. noise="philox" gives
     the host track source the same stream and projection order (BatchPCW(noise="philox")), for comparing the two. With map_log
     and device tracks, the world's ids are read from the device once per recorded frame (xivo_hip_pcw_get_world: B x npts ids, a
     synchronising download - not for a timed run).
@@ -1571,7 +1613,10 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
     motion = ["lissajous" if b % 2 == 0 else "trefoil" for b in range(B)]
     rate = 0.08 + 0.04 * (np.arange(B) % 7) / 7
     sim = BatchTrajectorySim(motion, rate, seed=seed + 1, noise=imu_noise, noise_seed=seed + 1)
-    world = BatchPCW(B, npts=npts, seed=seed, noise=noise, noise_seed=noise_seed)
+    faults = getattr(cfg, "track_faults", None)
+    if faults is not None and not dev_tracks and noise != "philox":
+        raise ValueError("track_faults on host tracks need noise='philox': they are draws of the device producer's generator")
+    world = BatchPCW(B, npts=npts, seed=seed, noise=noise, noise_seed=noise_seed, faults=None if dev_tracks else faults)
     K = np.array([[cfg.cam["fx"], 0, cfg.cam["cx"]], [0, cfg.cam["fy"], cfg.cam["cy"]], [0, 0, 1.0]])
     sim_cam = cfg.cam if cfg.cam["model"] != L_CAM_PINHOLE else None      # both track sources simulate the estimator's camera
     Rbc = so3_exp(cfg.Wbc)
@@ -1655,6 +1700,15 @@ def run_pcw_batch(cfg, B, total_time=2.0, imu_dt=0.0025, vision_dt=0.04, noise_v
         gt = gctx.trajsim_get_gt(0, B)
         gt_T, gt_R = gt[:, :, 9:], gt[:, :, :9].reshape(gt.shape[0], B, 3, 3).transpose(0, 1, 3, 2)
     out = dict(ts=np.array(ts), gt_Tsb=np.array(gt_T), estimator=est)
+    if faults is not None:
+        # the producer's counters and (device tracks: the score's) four cells: the sums and per filter. Host tracks are not
+        # scored; their producer counters are the restatement's
+        if dev_tracks:
+            st = est.fault_stats()
+            per = {k: st[k].astype(np.int64) for k in st.dtype.names}
+        else:
+            per = {k: v.copy() for k, v in world.fault_stats.items()}
+        out["fault_stats"] = dict(sum={k: int(v.sum()) for k, v in per.items()}, per_filter=per)
     if mlog is not None:
         mlog.finish(out)
     if ictx is not None:

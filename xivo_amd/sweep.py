@@ -18,7 +18,8 @@ import numpy as np
 
 from . import lib as L
 from .pcw import BatchPCW, BatchTrajectorySim, so3_exp
-from .sequence import (HipBackend, ImuFeeder, L_CAM_PINHOLE, SequenceRunner, _innovation, _score, _traj_cols, camera_poses, rpe_lag_frames)
+from .sequence import (HipBackend, ImuFeeder, L_CAM_PINHOLE, SequenceRunner, _innovation, _score, _traj_cols, camera_poses, check_lifecycle,
+                       rpe_lag_frames)
 
 # the fields of SequenceConfig a table row is computed from: plain attributes and "dict.key" entries of Qimu / Qmodel
 TUNABLE = ("visual_meas_std", "MH_thresh", "initial_std_x", "initial_std_y", "initial_std_z",
@@ -91,9 +92,22 @@ def _tile_tracks(off, ids, meas, T):
     return offs, np.tile(ids, T), np.tile(meas, (T, 1))
 
 
-def _run(cfg, W, T, table, total_time, imu_dt, vision_dt, noise_vision_std, npts, seed, device, rpe_dt, timers):
+def _run(cfg, W, T, table, total_time, imu_dt, vision_dt, noise_vision_std, npts, seed, device, rpe_dt, timers,
+         track_source="host", noise_seed=0):
+    import copy
     import time
     B = T * W
+    if track_source not in ("host", "device"):
+        raise ValueError("track_source must be 'host' or 'device'")
+    dev_tracks = track_source == "device"
+    if dev_tracks:
+        # the W worlds tiled T times on the device, the producer's streams shared with period W: filter t * W + w draws the
+        # words of filter w, so every tuning sees the same tracks - and the same track faults (cfg.track_faults)
+        cfg = copy.copy(cfg)
+        cfg.track_source, cfg.npts = "device", npts
+        check_lifecycle(cfg)
+    elif getattr(cfg, "track_faults", None) is not None:
+        raise ValueError("track_faults need track_source='device': host tracks are not scored")
     motion = ["lissajous" if w % 2 == 0 else "trefoil" for w in range(W)]
     rate = 0.08 + 0.04 * (np.arange(W) % 7) / 7
     sim = BatchTrajectorySim(motion, rate, seed=seed + 1)
@@ -109,6 +123,10 @@ def _run(cfg, W, T, table, total_time, imu_dt, vision_dt, noise_vision_std, npts
     if table is not None:
         be.enable_tuning(np.repeat(table, W))
     runner = SequenceRunner(be, cfg, B)
+    if dev_tracks:
+        be.set_world(np.tile(world.Xs, (T, 1, 1)))
+        be.stream_share(W)
+        runner.noise_px_std, runner.noise_seed = noise_vision_std, noise_seed
     n_imu = int(round(total_time / imu_dt)); every = int(round(vision_dt / imu_dt))
     n_frames = (n_imu + every - 1) // every
     be.enable_trajectory_log(n_frames, _traj_cols(True))
@@ -127,21 +145,25 @@ def _run(cfg, W, T, table, total_time, imu_dt, vision_dt, noise_vision_std, npts
             continue
         feeder.visual(t)
         Rsb, Tsb = sim.gsb(t)
-        Rsc, Tsc, _ = camera_poses(Rsb, Tsb, Rbc, cfg.Tbc)
-        off, ids, meas = _tile_tracks(*world.generate(Rsc, Tsc, K, cfg.cam["cols"], cfg.cam["rows"], noise_vision_std, cam=sim_cam,
-                                                      max_radius=cfg.pcw_max_radius), T)
+        Rsc, Tsc, gsc = camera_poses(Rsb, Tsb, Rbc, cfg.Tbc)
+        if not dev_tracks:
+            off, ids, meas = _tile_tracks(*world.generate(Rsc, Tsc, K, cfg.cam["cols"], cfg.cam["rows"], noise_vision_std, cam=sim_cam,
+                                                          max_radius=cfg.pcw_max_radius), T)
         imu = feeder.take()
         if imu is not None and T > 1:
             imu = np.tile(imu, (T, 1))
         be.frame_ts = int(round(t * 1e9))
         t1 = time.perf_counter()
-        if pool:
-            runner.vision_counter += 1
-            strict = runner.vision_counter >= cfg.strict_criteria_timesteps
-            begin, end = (lambda: be.pool_life_begin(off, ids, meas, strict)), be.pool_life_end
+        if dev_tracks:      # the ground-truth camera poses tiled; the frame's number is the generator's counter
+            runner.frame_world(imu, np.tile(gsc, (T, 1)), len(ts))
         else:
-            begin, end = (lambda: be.life_begin(off, ids, meas)), be.life_end
-        runner._device_frame([("propagate", lambda: imu is not None and be.propagate(imu))], begin, end)
+            if pool:
+                runner.vision_counter += 1
+                strict = runner.vision_counter >= cfg.strict_criteria_timesteps
+                begin, end = (lambda: be.pool_life_begin(off, ids, meas, strict)), be.pool_life_end
+            else:
+                begin, end = (lambda: be.life_begin(off, ids, meas)), be.life_end
+            runner._device_frame([("propagate", lambda: imu is not None and be.propagate(imu))], begin, end)
         if timers is not None:
             be.sync()
             tm["frame"] = tm.get("frame", 0.0) + time.perf_counter() - t1
@@ -152,6 +174,8 @@ def _run(cfg, W, T, table, total_time, imu_dt, vision_dt, noise_vision_std, npts
     _innovation(be.ctx, out)
     _score(be.ctx, be.trajectory(), out["gt_Rsb"], out["gt_Tsb"], out, rpe_lag_frames(rpe_dt, vision_dt))
     out["life_stats"] = be.pool_life_stats() if pool else be.life_stats()
+    if be.faults_on:
+        out["fault_stats"] = be.fault_stats()
     return out
 
 
@@ -177,36 +201,46 @@ def summarize(out, T, W):
             anees_pose=float(np.nanmean(per_frame)) if np.isfinite(per_frame).any() else float("nan"),
             nis_per_dof=float(st["filt_nis"][s].sum() / dof) if dof > 0 else float("nan"),
             rejected=int(out["life_stats"]["rejected"][s].sum()), not_spd=int(out["life_stats"]["not_spd"][s].sum())))
+        if "fault_stats" in out:      # track faults: the score's four sums and the dropped tracks of the tuning
+            fs = out["fault_stats"]
+            rows[-1].update({k: int(fs[k][s].sum()) for k in ("outlier_rejected", "outlier_kept", "nominal_rejected", "nominal_kept",
+                                                             "dropped")})
     return rows
 
 
 def run_sweep(cfg, axes, worlds, total_time=4.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0, npts=1000, seed=0,
-              device=0, rpe_dt=1.0, timers=None):
+              device=0, rpe_dt=1.0, timers=None, track_source="host", noise_seed=0):
     """Run the grid of `axes` (grid()) on `worlds` shared worlds: one context of B = T x W filters, filter t * W + w tuning t on
     world w, one BatchTrajectorySim / BatchPCW of W sequences whose tracks and IMU records every tuning sees. Needs a device
     life cycle on host tracks (check_sweep). The trajectory log, the score and the innovation log are on.
     -> dict(axes, cfgs [T], table [T], T, W, summary [T] (summarize), and the run's per-filter arrays: ate_aligned / ate_raw /
     rpe_pos / rpe_rot [B], nees [n, B], nis_per_dof_seq [B], life_stats [B], trajectory, innovation, ts, gt_Tsb, runner,
-    backend). timers: a dict that takes "frame", the seconds of the frame calls with a wait behind each."""
+    backend). timers: a dict that takes "frame", the seconds of the frame calls with a wait behind each.
+    track_source="device" (cfg itself stays on host tracks): the W worlds are tiled T times on the device with
+    xivo_hip_pcw_set_world, the producer's streams are shared with period W (xivo_hip_pcw_stream_share) and keyed by noise_seed,
+    the ground-truth camera poses are tiled, the IMU stays the host's. cfg.track_faults then turns the producer's track faults
+    on, and the summary gains per tuning the four sums of the score and `dropped`."""
     check_sweep(cfg, axes)
     W = int(worlds)
     if W <= 0:
         raise ValueError("run_sweep needs at least one world")
     cfgs, table = grid(cfg, axes)
     T = len(cfgs)
-    out = _run(cfg, W, T, table, total_time, imu_dt, vision_dt, noise_vision_std, npts, seed, device, rpe_dt, timers)
+    out = _run(cfg, W, T, table, total_time, imu_dt, vision_dt, noise_vision_std, npts, seed, device, rpe_dt, timers,
+               track_source, noise_seed)
     out.update(axes={n: [float(v) for v in np.atleast_1d(axes[n])] for n in axes}, cfgs=cfgs, table=table, T=T, W=W)
     out["summary"] = summarize(out, T, W)
     return out
 
 
 def run_plain(cfg, worlds, total_time=4.0, imu_dt=0.0025, vision_dt=0.04, noise_vision_std=1.0, npts=1000, seed=0, device=0,
-              rpe_dt=1.0, timers=None):
+              rpe_dt=1.0, timers=None, track_source="host", noise_seed=0):
     """the W worlds of run_sweep(seed, npts) through the same driver with cfg's own parameters and no tuning table: what row t
     of a sweep is held against when cfg = cfgs[t]"""
     check_sweep(cfg, {})
     W = int(worlds)
-    out = _run(cfg, W, 1, None, total_time, imu_dt, vision_dt, noise_vision_std, npts, seed, device, rpe_dt, timers)
+    out = _run(cfg, W, 1, None, total_time, imu_dt, vision_dt, noise_vision_std, npts, seed, device, rpe_dt, timers,
+               track_source, noise_seed)
     out.update(T=1, W=W)
     out["summary"] = summarize(out, 1, W)
     return out
